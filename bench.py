@@ -14,14 +14,19 @@ Multi-GPU is weak scaling: each rank owns 65 536 envs (global ids rank*65536 ...
 collective, one all-gather of episode returns per 500-step episode (RCCL over xGMI, issued by the C++ host:
 rq_allgather_returns), enqueued behind the rollout that completed the episode and overlapped with the next one.
 
-Timing: after exactly --warmup untimed steps, the timed region - exactly --steps steps (one fused launch
-per <= 500 of them), bracketed by barrier + synchronize on both sides - is REPEATED (at least 5 times and
-until 0.25 s of timed regions have accumulated, at most 2000); every region is timed (max over ranks) and
-`timing` reports first / min / median / mean / max.  The exchange belongs to the episode: one all-gather per
-500 steps, posted by the region in which the 500th step falls and waited for inside that region.  `ms_per_step`
-and `value` charge every region its share of it: the median region WITHOUT an exchange plus steps/500 of the
-difference to the median region WITH one (round 3; the plain median of round 2 never saw the 1-in-25 region
-that carries the collective when --steps is 20).  A short region (the driver's --steps 20 is one 70 us launch)
+Timing: after 0.25 s of rollouts on a scratch shard (the chip's clocks) and, on the benchmarked shard, one untimed step and
+exactly --warmup more, ONE timed region of exactly --steps steps (one fused launch per <= 500
+of them), bracketed by barrier + synchronize on both sides (max over ranks), gives `value` and `ms_per_step`.  That is all a
+plain run does before it prints its line; `--dump-outputs DIR` first writes what the last timed step left (GpuEngine.outputs,
+write_outputs).  Everything below is `--full`, which runs after the headline region:
+
+With --full, timed regions of exactly --steps steps are REPEATED (at least 5 times and until 0.25 s of timed
+regions have accumulated, at most 2000); every region is timed (max over ranks) and `timing.repeated_regions`
+reports first / min / median / mean / max.  The exchange belongs to the episode: one all-gather per 500 steps,
+posted by the region in which the 500th step falls and waited for inside that region.  The repeated regions'
+`ms_per_step` and `value` charge every region its share of it: the median region WITHOUT an exchange plus
+steps/500 of the difference to the median region WITH one (round 3; the plain median of round 2 never saw the
+1-in-25 region that carries the collective when --steps is 20).  A short region (--steps 20 is one 70 us launch)
 is bound by launch overhead and by the clock ramp of the first ~20 ms; `steady_state` therefore adds 10
 back-to-back 500-step launches measured in the same run, so that the record carries the steady-state figure
 too, and `config4` the same workload at BASELINE config 3/4's 262 144 envs per GPU.
@@ -32,8 +37,9 @@ ranks, the one JSON line) is `run_benchmark(args, engine, ...)`: `engine` is the
 --backend gloo`: tests/test_bench_orchestration.py runs two gloo ranks through it, including a rank that
 fails phase 1 or phase 2 of the consensus).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
-  timing        repetitions and the spread of the timed regions
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step, config and `timing` (the
+headline region), and with --full these extra objects:
+  timing.repeated_regions  repetitions and the spread of the repeated timed regions
   steady_state  10 x 500-step launches back to back: env-steps/s, us/step, fraction of the fp32 peak
   roofline      dominant kernel of the timed region (the fused rollout kernel)
   cpu_baseline  the oracle's C restatement timed on this box's host cores (a reported
@@ -57,6 +63,7 @@ if ROOT not in sys.path:
 ENVS_PER_GPU = 65536
 EPISODE = 500
 MIN_REPETITIONS, MAX_REPETITIONS, MIN_TIMED_SECONDS = 5, 2000, 0.25
+CLOCK_WARMUP_SECONDS = 0.25
 
 # ---- algorithmic work per env-step (DESIGN.md "Work per env-step") ---------------------------
 # actor: 2*(16*22 + 48*16 + 48*16 + 4*16) = 3904 FLOP + gates: per hidden element
@@ -101,6 +108,13 @@ def parse_args(argv=None):
                     help="TESTS ONLY: more ranks than GPUs - rank r drives GPU r %% (GPUs of the node), the rendezvous backend defaults to "
                          "gloo (RCCL cannot put two ranks on one device; RQ_RCCL_LIBRARY names the tests' stand-in for the native exchange). "
                          "What the driver's 8-GPU command meets, on the one GPU of a test box; the record says `oversubscribed`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the record can hold: repeated timed regions, kernel-level timing, "
+                         "steady state, the gathered returns' layout check, config 4, roofline, API-granular kernels, extensions, "
+                         "parity and the CPU baseline (a plain run sets up, warms up, times --steps steps and prints the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (rank 0's shard) as DIR/<name>.npy, float32, at most 64 MB in all "
+                         "(a fixed, seeded sample of envs beyond that)")
     return ap.parse_args(argv)
 
 
@@ -129,6 +143,28 @@ class Shard:
     def rollout(self, steps, mode):
         self.vector.rollout(self.device, self.env, self.params, self.state, self.policy, self.rng, steps, mode,
                             autoreset=True)
+
+
+OUTPUT_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(directory, arrays, limit=OUTPUT_LIMIT_BYTES):
+    """`--dump-outputs`: one DIR/<name>.npy per array (float32, env-major: row i = env i).  Beyond `limit` bytes in all, the same
+    rows of every array are kept - a sorted sample drawn with a fixed seed - and `sample_envs.npy` (float64) says which envs."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    rows = {v.shape[0] for v in arrays.values()}
+    assert len(rows) == 1, f"outputs of different lengths: { {k: v.shape for k, v in arrays.items()} }"
+    n = rows.pop()
+    total = sum(v.nbytes for v in arrays.values())
+    limit -= 256 * (len(arrays) + 1)                 # the .npy headers (128 bytes each as numpy writes them)
+    if total > limit:
+        keep = limit * n // (total + 8 * n)          # 8 more bytes per kept row: its index
+        pick = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: v[pick] for k, v in arrays.items()}
+        arrays["sample_envs"] = pick.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
 
 
 def actor_groups_per_wave(n):
@@ -995,6 +1031,16 @@ class GpuEngine:
     def local_returns(self, shard):
         return shard.env.finished_returns()
 
+    @staticmethod
+    def outputs(shard):
+        """What a caller of the rollout has after its last step, one row per env: the state, the policy's hidden state and the
+        env's episode statistics (counts and flags as float32, exact below 2**24)."""
+        env = shard.env
+        return {"state": shard.state.numpy(), "hidden_state": shard.policy.hidden_state(shard.n), "rewards": env.rewards(),
+                "terminated": env.terminated().astype(np.float32), "returns": env.returns(),
+                "episode_steps": env.episode_steps().astype(np.float32), "finished_returns": env.finished_returns(),
+                "finished_counts": env.finished_counts().astype(np.float32)}
+
     def set_rollout_timing(self, enable):
         self.device.set_rollout_timing(enable)
 
@@ -1222,6 +1268,16 @@ def run_benchmark(args, engine, rank, local_rank, world, dist):
         probe_clock[0] = float(np.mean(clocks)) if clocks else None       # core clock of the launches just timed
         return float(np.mean(out)) if args.mode == "fused" else float(np.median(out))
 
+    # ---- the chip's clocks first: a region that follows an idle chip runs its first milliseconds at a lower clock (the first of
+    # 2000-step regions read 6.3 ms against a 5.7 ms median), so 500-step rollouts of a scratch shard of the same size run for
+    # CLOCK_WARMUP_SECONDS.  It has state of its own: the benchmarked shard still sees exactly 1 + --warmup steps before its
+    # timed ones ----
+    scratch, t_end = engine.make_shard(n, rank * n), time.perf_counter() + CLOCK_WARMUP_SECONDS
+    while time.perf_counter() < t_end:
+        scratch.rollout(EPISODE, args.mode)
+        engine.synchronize()
+    del scratch
+
     # ---- warm-up: one-off costs first (RCCL communicator, first barrier, lazy allocations), then EXACTLY
     # --warmup untimed steps of the same rollout ----
     run([1])
@@ -1231,8 +1287,39 @@ def run_benchmark(args, engine, rank, local_rank, world, dist):
         run(chunks(args.warmup, EPISODE))
         finish()
 
-    # ---- timed regions: each exactly --steps steps; repeated (module docstring) ----
+    # ---- the headline: ONE timed region of exactly --steps steps (barrier + synchronize on both sides, max over ranks) ----
     plan = chunks(args.steps, EPISODE)
+    wall, posted = timed_region(plan)
+    elapsed = max_over_ranks([wall])[0]
+    if args.dump_outputs and rank == 0:            # what the last timed step left, before anything else touches the shard
+        write_outputs(args.dump_outputs, engine.outputs(shard))
+    value = n_total * args.steps / elapsed
+    result = {
+        "metric": f"env-steps/sec (whole node) at {n} quadrotors per GPU",
+        "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 6),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": {"fp32": "f32", "bf16": "bf16 actor operands (fp32 accumulate) + f32 dynamics",
+                  "f16x2": "actor operands as two f16 pieces each (22 significand bits, fp32 accumulate) + f32 dynamics"
+                  }[args.precision],
+        "data": "synthetic",
+        "config": {"workload": f"{n} parallel quadrotors per GPU, fp32 RK4 dynamics + {args.precision} GRU actor "
+                               f"(RAPTOR checkpoint), domain-randomised params, auto-reset, {args.mode} rollout",
+                   "envs_per_gpu": n, "total_envs": n_total, "episode_length": EPISODE,
+                   "parallelism": f"env-sharded x{world}, all-gather of returns per episode" if world > 1
+                                  else "single GPU", "mode": args.mode, "engine": engine.name, **engine.describe(),
+                   "exchange": exchange_kind},
+        "timing": {"repetitions": 1, "steps_per_region": args.steps,
+                   "statistic": "one region of exactly --steps steps, barrier + synchronize on both sides, max over ranks",
+                   "region_ms": {"charged": round(elapsed * 1e3, 4)}, "exchanges_in_region": posted,
+                   "untimed_steps_before_first_region": args.warmup + 1},
+    }
+    if rccl is not None:
+        result["config"]["rccl"] = rccl
+    if not args.full:
+        return result if rank == 0 else None
+
+    # ---- --full: timed regions of exactly --steps steps each, repeated (module docstring) ----
     per_region = args.steps / EPISODE if exchange is not None else 0.0
     fractional = per_region != int(per_region)
     walls, posts = [], []
@@ -1247,7 +1334,7 @@ def run_benchmark(args, engine, rank, local_rank, world, dist):
         if len(walls) >= MAX_REPETITIONS or enough:
             break
     walls = max_over_ranks(walls)                    # max over ranks, region by region
-    elapsed, share = effective_region(walls, posts, args.steps, exchange is not None)
+    rep_elapsed, share = effective_region(walls, posts, args.steps, exchange is not None)
     # one rollout launch of the region's kind; fused: whole episode periods of regions (at least 2, ~0.2 s at most)
     periods = max(1, int(np.ceil(EPISODE / max(args.steps, 1)))) if args.steps < EPISODE else 1
     # fused: samples spread over the phases of an episode (two per phase, at most 60), `stride` regions apart
@@ -1359,31 +1446,16 @@ def run_benchmark(args, engine, rank, local_rank, world, dist):
             config4["exchange_verified"] = ok4
         del shard4
 
-    value = n_total * args.steps / elapsed
-    result = {
-        "metric": f"env-steps/sec (whole node) at {n} quadrotors per GPU",
-        "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 6),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": {"fp32": "f32", "bf16": "bf16 actor operands (fp32 accumulate) + f32 dynamics",
-                  "f16x2": "actor operands as two f16 pieces each (22 significand bits, fp32 accumulate) + f32 dynamics"
-                  }[args.precision],
-        "data": "synthetic",
-        "config": {"workload": f"{n} parallel quadrotors per GPU, fp32 RK4 dynamics + {args.precision} GRU actor "
-                               f"(RAPTOR checkpoint), domain-randomised params, auto-reset, {args.mode} rollout",
-                   "envs_per_gpu": n, "total_envs": n_total, "episode_length": EPISODE,
-                   "parallelism": f"env-sharded x{world}, all-gather of returns per episode" if world > 1
-                                  else "single GPU", "mode": args.mode, "engine": engine.name, **engine.describe()},
-        "timing": {"repetitions": len(walls), "steps_per_region": args.steps,
-                   "statistic": "median region without an exchange + steps/500 of the difference to the median region with one"
-                                if exchange is not None else "median",
-                   "region_ms": {"first": round(walls[0] * 1e3, 4), "min": round(min(walls) * 1e3, 4),
-                                 "median": round(float(np.median(walls)) * 1e3, 4),
-                                 "mean": round(float(np.mean(walls)) * 1e3, 4),
-                                 "max": round(max(walls) * 1e3, 4), "charged": round(elapsed * 1e3, 4)},
-                   "exchange_share": share,
-                   "untimed_steps_before_first_region": args.warmup + 1},
-    }
+    result["timing"]["repeated_regions"] = {
+        "repetitions": len(walls), "steps_per_region": args.steps,
+        "statistic": "median region without an exchange + steps/500 of the difference to the median region with one"
+                     if exchange is not None else "median",
+        "region_ms": {"first": round(walls[0] * 1e3, 4), "min": round(min(walls) * 1e3, 4),
+                      "median": round(float(np.median(walls)) * 1e3, 4),
+                      "mean": round(float(np.mean(walls)) * 1e3, 4),
+                      "max": round(max(walls) * 1e3, 4), "charged": round(rep_elapsed * 1e3, 4)},
+        "exchange_share": share,
+        "value": round(n_total * args.steps / rep_elapsed, 1), "ms_per_step": round(rep_elapsed / args.steps * 1e3, 6)}
     if steady is not None:
         result["steady_state"] = steady
     if config4 is not None:
@@ -1435,7 +1507,7 @@ def run_benchmark(args, engine, rank, local_rank, world, dist):
         rl = result["roofline"]
         rl["avg_launch_ms_in_run"] = round(avg_launch_s * 1e3, 4)
         rl["frac_in_run"] = round(achieved / PEAK_FP32_TFLOPS, 4)
-        region_s = elapsed / len(plan)
+        region_s = rep_elapsed / len(plan)
         rl["frac_by_region"] = round(flop_per_launch / region_s / 1e12 / PEAK_FP32_TFLOPS, 4)
         if event_launch_ms:
             rl["avg_launch_ms_hip_events"] = round(event_launch_ms, 4)
@@ -1513,13 +1585,10 @@ def run_benchmark(args, engine, rank, local_rank, world, dist):
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     result["config"]["exchanges_per_timed_region"] = round(args.steps / EPISODE, 4) if exchange is not None else 0
     result["config"]["gathered_returns"] = gathered_count
-    result["config"]["exchange"] = exchange_kind
     result["config"]["exchange_verified"] = exchange_verified
     if exchange_check is not None:
         result["config"]["exchange_check"] = exchange_check
-    if rccl is not None:
-        result["config"]["rccl"] = rccl
-    elif isinstance(result.get("native_exchange_1rank"), dict) and "rccl" in result["native_exchange_1rank"]:
+    if rccl is None and isinstance(result.get("native_exchange_1rank"), dict) and "rccl" in result["native_exchange_1rank"]:
         # one rank and nothing to gather in the timed regions: the 1-rank communicator of the `native_exchange_1rank` block
         # is the one RCCL this process met - its own account of itself (ranks == 1 from ncclCommCount)
         result["config"]["rccl"] = result["native_exchange_1rank"]["rccl"]

@@ -134,6 +134,10 @@ class StubEngine:
     def local_returns(self, shard):
         return shard.env.finished_returns()
 
+    def outputs(self, shard):
+        return {"finished_returns": shard.env.finished_returns(),
+                "episode_steps": np.full(shard.n, shard.steps % 500, np.float32)}
+
     def set_rollout_timing(self, enable):
         self.timing = bool(enable)
 

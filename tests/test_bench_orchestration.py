@@ -29,7 +29,7 @@ def _run(world, extra_env=None, args=("--steps", "20", "--warmup", "5"), timeout
                    MASTER_PORT=str(port), PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
         env.update(extra_env or {})
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--engine", "tests.bench_stub_engine",
-               "--backend", "gloo", "--no-cpu-baseline", "--envs-per-gpu", "64", *args]
+               "--backend", "gloo", "--full", "--no-cpu-baseline", "--envs-per-gpu", "64", *args]
         procs.append(subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
@@ -62,10 +62,10 @@ def test_two_ranks_native_exchange_one_json_line():
     assert d["config"]["gathered_returns"] == 128                   # every rank's shard arrived
     assert d["value"] > 0 and d["higher_is_better"] is True and d["unit"] == "env-steps/s"
     # 20-step regions: one exchange in 25 regions; the regions that carry it were sampled and charged for
-    share = d["timing"]["exchange_share"]
+    share = d["timing"]["repeated_regions"]["exchange_share"]
     assert share["exchanges_per_region"] == pytest.approx(0.04)
     assert share["regions_with_extra_exchange"] >= 3
-    assert d["timing"]["region_ms"]["charged"] >= d["timing"]["region_ms"]["min"]
+    assert d["timing"]["repeated_regions"]["region_ms"]["charged"] >= d["timing"]["repeated_regions"]["region_ms"]["min"]
     assert d["config4"]["total_envs"] == 2 * 262144 and d["config4"]["exchanges"] == 4
     assert d["steady_state"]["exchanges"] == 10
     # round 5: the record proves what it gathered - the communicator's own account of itself, rank by rank, and the layout of
@@ -101,7 +101,7 @@ def test_no_value_without_a_verified_exchange(fault):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), **fault)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--engine", "tests.bench_stub_engine", "--backend", "gloo",
-               "--no-cpu-baseline", "--envs-per-gpu", "64", "--steps", "20", "--warmup", "5", "--no-config4"]
+               "--full", "--no-cpu-baseline", "--envs-per-gpu", "64", "--steps", "20", "--warmup", "5", "--no-config4"]
         procs.append(subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     for p in procs:
         out, err = p.communicate(timeout=240)
@@ -118,7 +118,7 @@ def test_consensus_falls_back_on_every_rank_without_deadlock(phase, rank):
     assert d["config"]["exchange"].startswith("torch.distributed all_gather_into_tensor")
     assert f"rank {rank}" in d["config"]["exchange"]               # the reason names the rank that failed
     assert d["config"]["gathered_returns"] == 128
-    assert d["timing"]["exchange_share"]["exchanges_per_region"] == 1.0
+    assert d["timing"]["repeated_regions"]["exchange_share"]["exchanges_per_region"] == 1.0
 
 
 @pytest.mark.timeout(300)
@@ -126,14 +126,14 @@ def test_single_process_has_nothing_to_gather():
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--engine", "tests.bench_stub_engine", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--engine", "tests.bench_stub_engine", "--full", "--no-cpu-baseline",
                           "--envs-per-gpu", "64", "--steps", "20", "--warmup", "5", "--no-config4"], env=env, cwd=ROOT,
                          capture_output=True, text=True, timeout=200)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _json_line(out.stdout)
     assert d["n_gpus"] == 1 and d["config"]["exchange"].startswith("none") and d["config"]["gathered_returns"] == 64
     assert d["config"]["exchange_verified"] is None and "rccl" not in d["config"]        # nothing gathered, nothing claimed
-    assert d["timing"]["statistic"] == "median"
+    assert d["timing"]["repeated_regions"]["statistic"] == "median"
 
 
 def _plain(args, extra_env=None, timeout=240):
@@ -149,7 +149,7 @@ def _plain(args, extra_env=None, timeout=240):
 
 @pytest.mark.timeout(300)
 def test_plain_command_with_gpus_2_launches_two_ranks_itself():
-    out = _plain(["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-config4"])
+    out = _plain(["--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-config4"])
     assert out.returncode == 0, out.stderr[-2000:]
     d = _json_line(out.stdout)                      # ONE record, the last line of the launcher's stdout
     assert d["n_gpus"] == 2 and d["config"]["total_envs"] == 128 and d["config"]["gathered_returns"] == 128
@@ -268,3 +268,52 @@ def test_record_readers_pick_the_right_committed_profiles():
     assert rp is not None and rp["launches"] > 1000 and 55.0 < rp["median_us"] <= rp["mean_us"] < 80.0, rp
     assert bench.rocprof_launch_stats(bench.fused_kernel_name("fp32", 65536, 20), 1000, 20)[0] is None
     assert bench.rocprof_launch_stats(bench.fused_kernel_name("fp32", 65536, 500), 65536, 500)[0] is None
+
+
+@pytest.mark.timeout(300)
+def test_a_plain_run_times_exactly_its_steps_and_dumps_what_they_left(tmp_path):
+    """Without --full the command runs 1 + --warmup untimed steps and exactly --steps timed ones, and prints the headline alone;
+    --dump-outputs writes what the last timed step left as float32 .npy files - the same bytes from run to run, and from a --full
+    run, whose extras come after the dump."""
+    dumps = []
+    for k, extra in enumerate(([], [], ["--full", "--no-config4"])):
+        where = tmp_path / f"run{k}"
+        out = _plain(["--steps", "500", "--warmup", "20", "--dump-outputs", str(where), *extra])
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = _json_line(out.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 500 and d["warmup"] == 20 and d["timing"]["repetitions"] == 1
+        assert d["value"] == pytest.approx(64 * 500 / (d["ms_per_step"] * 500 * 1e-3), rel=2e-3)
+        full_only = ("steady_state", "config4", "roofline", "kernels", "parity", "cpu_baseline")
+        if extra:
+            assert "repeated_regions" in d["timing"] and "steady_state" in d
+        else:
+            assert "repeated_regions" not in d["timing"] and not [x for x in full_only if x in d], sorted(d)
+        assert sorted(os.listdir(where)) == ["episode_steps.npy", "finished_returns.npy"]
+        got = {f: np.load(where / f) for f in sorted(os.listdir(where))}
+        assert all(a.dtype == np.float32 and a.shape == (64,) for a in got.values())
+        assert (got["episode_steps.npy"] == (1 + 20 + 500) % 500).all()           # nothing else stepped the shard before the dump
+        assert np.array_equal(got["finished_returns.npy"], np.arange(64, dtype=np.float32) + 1000.0)
+        dumps.append({f: a.tobytes() for f, a in got.items()})
+    assert dumps[0] == dumps[1] == dumps[2]
+
+
+def test_dumped_outputs_stay_within_their_budget_as_a_fixed_sample(tmp_path):
+    import bench
+    n = 1000
+    arrays = {"a": np.arange(3 * n, dtype=np.float32).reshape(n, 3), "b": np.arange(n, dtype=np.uint32)}
+    bench.write_outputs(tmp_path / "all", arrays)
+    assert sorted(os.listdir(tmp_path / "all")) == ["a.npy", "b.npy"]
+    assert np.load(tmp_path / "all" / "b.npy").dtype == np.float32 and np.array_equal(np.load(tmp_path / "all" / "a.npy"), arrays["a"])
+    for k in (1, 2):
+        bench.write_outputs(tmp_path / f"s{k}", arrays, limit=8000)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["a.npy", "b.npy", "sample_envs.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= 8000
+    pick = np.load(tmp_path / "s1" / "sample_envs.npy")
+    assert pick.dtype == np.float64 and 100 < pick.size < n and (np.diff(pick) > 0).all()
+    rows = pick.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s1" / "a.npy"), arrays["a"][rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "b.npy"), arrays["b"][rows].astype(np.float32))
+    assert all((tmp_path / "s1" / f).read_bytes() == (tmp_path / "s2" / f).read_bytes() for f in files)

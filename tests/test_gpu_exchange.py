@@ -294,7 +294,7 @@ def test_bench_py_with_two_ranks_on_one_gpu(device, tmp_path):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    RQ_BENCH_DEVICE="0", RQ_RCCL_LIBRARY=fake)
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "20",
-                                       "--warmup", "5", "--no-cpu-baseline", "--envs-per-gpu", "8192"], env=env, cwd=root,
+                                       "--warmup", "5", "--full", "--no-cpu-baseline", "--envs-per-gpu", "8192"], env=env, cwd=root,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
@@ -316,11 +316,12 @@ def test_bench_py_with_two_ranks_on_one_gpu(device, tmp_path):
     assert d["config"]["rccl"]["ranks"] == 2 and d["config"]["rccl"]["library_path"] == fake and d["config"]["rccl"]["version_code"] == 0
     assert [r["rank"] for r in d["config"]["rccl"]["per_rank"]] == [0, 1]
     assert d["config"]["rccl"]["distinct_gpus"] == 1        # both ranks of THIS test share the box's one GPU, and the record shows it
-    assert d["timing"]["exchange_share"]["regions_with_extra_exchange"] >= 3
+    assert d["timing"]["repeated_regions"]["exchange_share"]["regions_with_extra_exchange"] >= 3
     assert d["steady_state"]["exchanges"] == 10 and d["config4"]["total_envs"] == 2 * 262144 and d["config4"]["exchanges"] == 4
     assert d["value"] > 1e8 and d["roofline"]["frac"] > 0.01
-    print(f"[bench.py, 2 ranks on one GPU, fake RCCL] value {d['value']:.3g} env-steps/s, region {d['timing']['region_ms']['charged']:.4f} ms, "
-          f"exchange share {d['timing']['exchange_share']}")
+    rep = d["timing"]["repeated_regions"]
+    print(f"[bench.py, 2 ranks on one GPU, fake RCCL] value {rep['value']:.3g} env-steps/s, region {rep['region_ms']['charged']:.4f} ms, "
+          f"exchange share {rep['exchange_share']}")
 
 
 @pytest.mark.timeout(600)
@@ -345,7 +346,7 @@ def test_the_drivers_eight_rank_command_end_to_end_on_one_gpu(device, tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "RQ_BENCH_DEVICE"):
         env.pop(k, None)
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--allow-oversubscribe"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--full", "--allow-oversubscribe"],
                        env=env, cwd=root, capture_output=True, text=True, timeout=500)
     wall = time.perf_counter() - t0
     assert r.returncode == 0, r.stderr[-3000:]
@@ -360,12 +361,13 @@ def test_the_drivers_eight_rank_command_end_to_end_on_one_gpu(device, tmp_path):
     rccl = d["config"]["rccl"]
     assert rccl["ranks"] == 8 and [x["rank"] for x in rccl["per_rank"]] == list(range(8)) and rccl["library_path"] == fake and rccl["distinct_gpus"] == 1
     assert d["config4"]["total_envs"] == 2097152 and d["config4"]["exchange_verified"] is True and d["config4"]["exchanges"] == 4      # BASELINE config 4
-    assert d["timing"]["exchange_share"]["regions_with_extra_exchange"] >= 3
+    assert d["timing"]["repeated_regions"]["exchange_share"]["regions_with_extra_exchange"] >= 3
     assert d["value"] > 1e8 and d["scaling"] == "weak" and d["metric"].startswith("env-steps/sec (whole node) at 65536 quadrotors")
     out = os.path.join(root, "gpurun_out")
     if os.path.isdir(out):
         with open(os.path.join(out, "eight_ranks_one_gpu.json"), "w") as fh:
-            json.dump({"wall_s": round(wall, 1), "command": "python bench.py --gpus 8 --steps 20 --warmup 5 --allow-oversubscribe", "record": d}, fh, indent=1)
+            json.dump({"wall_s": round(wall, 1), "command": "python bench.py --gpus 8 --steps 20 --warmup 5 --full --allow-oversubscribe", "record": d},
+                      fh, indent=1)
     print(f"[bench.py --gpus 8 on one GPU, fake RCCL] wall {wall:.1f} s, value {d['value']:.3g} env-steps/s (8 ranks time-share one GPU)")
     assert wall < 120.0, f"the eight-rank command took {wall:.0f} s on one GPU: over the 120 s box"
 
@@ -387,7 +389,7 @@ def test_plain_bench_command_launches_its_own_ranks_on_the_gpu(device, tmp_path)
                    check=True, capture_output=True)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "20", "--warmup", "5",
-           "--no-cpu-baseline", "--no-config4", "--envs-per-gpu", "8192"]
+           "--full", "--no-cpu-baseline", "--no-config4", "--envs-per-gpu", "8192"]
     out = subprocess.run(cmd, env=dict(env, RQ_BENCH_DEVICE="0", RQ_RCCL_LIBRARY=fake), cwd=root, capture_output=True, text=True,
                          timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]

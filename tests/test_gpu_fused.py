@@ -489,3 +489,34 @@ def test_a_diverged_env_stays_alone_in_a_rollout(device, oracle, precision, mode
                 others = np.ones(n, bool); others[victim] = False
                 for clean, dirty in zip(*out):
                     assert np.array_equal(clean[others], dirty[others]), (n, autoreset, bad, victim)
+
+
+@pytest.mark.timeout(600)
+def test_bench_dumps_what_its_timed_rollout_left(device, tmp_path):
+    """`bench.py --dump-outputs DIR`, a plain run (1 + --warmup untimed steps, exactly --steps timed ones, across an auto-reset):
+    every file is what the same rollout in this process leaves - state, hidden state, episode statistics - bit for bit, and a
+    second run writes the same bytes."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, warmup, steps = 4096, 5, 520
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--envs-per-gpu", str(n), "--dump-outputs", str(tmp_path / f"run{k}")], cwd=root, capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads(r.stdout.strip().split("\n")[-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and "roofline" not in d and "cpu_baseline" not in d
+    shard = bench.Shard(device, n, 0)
+    for plan in ([1], bench.chunks(warmup, bench.EPISODE), bench.chunks(steps, bench.EPISODE)):
+        for c in plan:
+            shard.rollout(c, "fused")
+    want = bench.GpuEngine.outputs(shard)
+    assert want["finished_counts"].max() >= 1                     # the run crossed an episode boundary
+    for k in range(2):
+        assert sorted(os.listdir(tmp_path / f"run{k}")) == sorted(f"{name}.npy" for name in want)
+        for name, a in want.items():
+            got = np.load(tmp_path / f"run{k}" / f"{name}.npy")
+            assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), np.asarray(a, np.float32).view(np.uint32)), name

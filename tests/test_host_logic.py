@@ -46,26 +46,6 @@ def test_checkpoint_header_round_trip(tmp_path):
         load_checkpoint_header(bad)
 
 
-def test_checkpoint_header_of_the_reference(tmp_path):
-    """When the reference tarball is present (build container only), its checkpoint.h parses to the
-    shipped weights and carries the first known-answer vector."""
-    import os
-    import tarfile
-    tar = "/root/reference/data/raptor-policy-checkpoint.tar.gz"
-    if not os.path.exists(tar):
-        pytest.skip("reference not present on this box")
-    from raptor_amd.checkpoint import load_checkpoint_header
-    from raptor_amd.foundation_policy import load_weights
-    from conftest import GOLDEN
-    with tarfile.open(tar) as tf:
-        tf.extract("2025-04-19_16-16-17/checkpoint.h", tmp_path)
-    w, ex = load_checkpoint_header(tmp_path / "2025-04-19_16-16-17" / "checkpoint.h")
-    assert np.array_equal(w, load_weights())
-    assert ex[0].shape == (500, 2, 22)
-    assert np.array_equal(ex[0].ravel(), np.fromfile(os.path.join(GOLDEN, "kat_h_input.bin"), "<f4"))
-    assert np.array_equal(ex[1].ravel(), np.fromfile(os.path.join(GOLDEN, "kat_h_output.bin"), "<f4"))
-
-
 def test_hdf5_checkpoint_reader(oracle):
     """The published checkpoint.h5 (fixture) through the dependency-free HDF5 reader: same weights
     as the shipped parameter file, the second known-answer pair, the observation spec string, and

@@ -11,8 +11,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # the command the driver runs at round end, unless one is given: bash tools/profile_round.sh r02 "--steps 10000 --warmup 5000"
 ARGS=${2:---gpus 1 --steps 20 --warmup 5}
-BENCH="python $R/bench.py $ARGS --no-cpu-baseline"
-echo "python bench.py $ARGS --no-cpu-baseline" > $OUT/command.txt
+BENCH="python $R/bench.py $ARGS --full --no-cpu-baseline"
+echo "python bench.py $ARGS --full --no-cpu-baseline" > $OUT/command.txt
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- $BENCH > $OUT/bench_trace.json 2> $OUT/trace.err
 echo "trace rc=$?"
 timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o bench -- $BENCH > $OUT/bench_fetch.json 2> $OUT/fetch.err

@@ -14,7 +14,7 @@ bash tools/profile_round.sh $TAG > $DST/profile_round.log 2>&1; echo "profile_ro
 cp $DST/${TAG}_fused_launch_stats.json $DST/${TAG}_pmc.json $R/profiles/ 2>/dev/null
 bash tools/sq_profile.sh $TAG > $DST/sq_profile.log 2>&1; echo "sq_profile rc=$?"
 cp $DST/${TAG}_sq_counters.json $R/profiles/ 2>/dev/null
-python bench.py --gpus 1 --steps 20 --warmup 5 > $DST/${TAG}_bench_driver_cmd.json 2> $DST/driver_cmd.err; echo "driver cmd rc=$?"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $DST/${TAG}_bench_driver_cmd.json 2> $DST/driver_cmd.err; echo "driver cmd rc=$?"
 bash tools/profile_extras.sh $TAG > $DST/profile_extras.log 2>&1; echo "profile_extras rc=$?"
 bash tools/teacher_traffic.sh $TAG > $DST/teacher_traffic.log 2>&1; echo "teacher_traffic rc=$?"
 {
