@@ -178,11 +178,6 @@ int state_make_private(rq_state* s, bool keep) {
 using namespace rqh;
 
 namespace rq {
-int resident_scope_hook(const rq_device* dev_) {
-    rq_device* dev = const_cast<rq_device*>(dev_);
-    dev->res_streak = 0; dev->res_pol_streak = 0;
-    return dev->res_running ? resident_retire(dev) : RQ_OK;
-}
 int device_ordinal(const rq_device* dev) { return dev->ordinal; }
 hipStream_t device_stream(const rq_device* dev) { return dev->stream; }
 rq_device* env_device(const rq_env* env) { return env->dev; }
@@ -243,15 +238,7 @@ RQ_API int rq_device_create(int ordinal, rq_device** out) {
     }
     d->speculate = std::getenv("RQ_NO_SPECULATION") == nullptr;
     d->graphs_enabled = std::getenv("RQ_NO_GRAPHS") == nullptr;
-    d->res_enabled = std::getenv("RQ_NO_RESIDENT") == nullptr;
-    d->res_timing = std::getenv("RQ_RESIDENT_TIMING") != nullptr;
-    if (const char* v = std::getenv("RQ_RESIDENT_IDLE_TICKS")) d->res_idle_ticks = std::strtoull(v, nullptr, 10);
-    if (const char* v = std::getenv("RQ_RESIDENT_LIFE_TICKS")) d->res_life_ticks = std::strtoull(v, nullptr, 10);
-    if (const char* v = std::getenv("RQ_RESIDENT_HOST_IDLE_NS")) d->res_host_idle_ns = std::strtoull(v, nullptr, 10);
-    if (const char* v = std::getenv("RQ_RESIDENT_HOST_LIFE_NS")) d->res_host_life_ns = std::strtoull(v, nullptr, 10);
-    // the resident executor's stream and command memory now, not inside somebody's loop: creating a second stream costs ~8 ms (a
-    // hardware queue of its own); a failure here is not the device's - the loop tries again when it first wants them
-    if (d->res_enabled && ensure_resident_memory(d) != RQ_OK) (void)hipGetLastError();
+    resident_setup(d);
     device_registry(d, +1);
     *out = d;
     return RQ_OK;
@@ -260,13 +247,8 @@ RQ_API int rq_device_create(int ordinal, rq_device** out) {
 RQ_API int rq_device_destroy(rq_device* dev) {
     if (!dev) return RQ_OK;
     DeviceScope on_device(dev->ordinal);
-    (void)resident_retire(dev);
+    resident_teardown(dev);
     device_registry(dev, -1);
-    if (dev->res_stream) (void)hipStreamDestroy(dev->res_stream);
-    if (dev->res_cmd_on_device && dev->res_cmd_mem) (void)hipFree(dev->res_cmd_mem);
-    if (dev->res_mem) (void)hipHostFree(dev->res_mem);
-    delete dev->res_cmd;
-    delete dev->res_pol_cmd;
     if (dev->stream) { (void)hipStreamSynchronize(dev->stream); (void)hipStreamDestroy(dev->stream); }
     if (dev->ev_start) (void)hipEventDestroy(dev->ev_start);
     if (dev->ev_stop) (void)hipEventDestroy(dev->ev_stop);
@@ -527,7 +509,7 @@ RQ_API int rq_env_create(rq_device* dev, uint32_t n_envs, uint64_t global_env_of
 RQ_API int rq_env_destroy(rq_env* env) {
     if (!env) return RQ_OK;
     DeviceScope on_device(env->ordinal);   // hipFree synchronises the device; the parent is not touched - unless it is alive and
-    if (device_registry(env->dev, 0) && env->dev->res_running) (void)resident_retire(env->dev);     // keeps a resident executor
+    if (device_registry(env->dev, 0)) (void)resident_retire(env->dev);     // keeps a resident executor
     if (env->obs) (void)hipFree(env->obs);
     if (env->obs_alt) (void)hipFree(env->obs_alt);
     for (float* b : env->state_pool) (void)hipFree(b);

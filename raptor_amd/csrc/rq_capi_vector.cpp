@@ -1,6 +1,6 @@
 // rq_capi_vector.cpp - the five l2f vector:: functions (README.md:60,61,96,98) and what serves the reference's loop at small batches behind
-// them: the pinned mailbox, the observation cache, the speculative policy step and the resident executor (include/raptor_quad.h
-// rq_device_set_speculation / rq_device_set_resident).  Objects and shared helpers: rq_objects.hpp.
+// them: the pinned mailbox, the observation cache and the speculative policy step (include/raptor_quad.h rq_device_set_speculation);
+// rq_step posts to the resident executor (rq_resident.cpp) where it can.  Objects and shared helpers: rq_objects.hpp.
 #include "rq_objects.hpp"
 
 namespace rqh {
@@ -56,24 +56,22 @@ bool obs_cache_holds(const rq_device* dev, const rq_env* env, const rq_params* p
     return false;
 }
 
-int resident_gone(rq_device* dev);
-
 // spin until the launch with sequence number seq (or a later one: launches finish in stream order) signalled.  While the
 // resident executor runs, the work waited for may be a command posted to it: if it has left (`exited`) without consuming the
 // command, resident_gone() replays the command as launches on the stream and the wait goes on.
 int mailbox_wait(rq_device* dev, uint32_t seq) {
+    const ResidentExecutor& rx = dev->resident;
     for (uint64_t spins = 1;; ++spins) {
         const uint32_t f = __atomic_load_n(dev->mb_flag, __ATOMIC_ACQUIRE);
         if ((int32_t)(f - seq) >= 0) return RQ_OK;
-        if (dev->res_running && (spins & 0xFFu) == 0 &&
-            __atomic_load_n(&dev->res_mem[16], __ATOMIC_ACQUIRE) == dev->res_launch_id) {
+        if (rx.running && (spins & 0xFFu) == 0 && resident_left(dev)) {
             const int rc = resident_gone(dev); if (rc) return rc;
             continue;
         }
         if ((spins & 0xFFFFu) == 0) {           // every ~100 us: is the stream still alive?
-            const hipError_t q = hipStreamQuery(dev->res_running ? dev->res_stream : dev->stream);
+            const hipError_t q = hipStreamQuery(rx.running ? rx.stream : dev->stream);
             if (q == hipSuccess) {
-                if (dev->res_running) { const int rc = resident_gone(dev); if (rc) return rc; continue; }
+                if (rx.running) { const int rc = resident_gone(dev); if (rc) return rc; continue; }
                 const uint32_t g = __atomic_load_n(dev->mb_flag, __ATOMIC_ACQUIRE);
                 if ((int32_t)(g - seq) >= 0) return RQ_OK;
                 return fail(RQ_ERR_HIP, "mailbox_wait: the stream drained without the kernel signalling");
@@ -109,13 +107,6 @@ void mailbox_abort(rq_device* dev, const rq::Mailbox& mb) {
     if (dev->mb_seq == mb.seq) dev->mb_seq = mb.seq - 1;      // 0 ("nothing pending") is skipped by mailbox_for
 }
 
-// ---- resident executor (rq_device::res_*; kernel: rq_kernels.hip k_resident_loop) ----------------------------------------------
-uint64_t host_now_ns() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-}
-
 // the two launches of a small-batch step on the device's stream (what rounds 3-5 always did; now also the replay of a command the
 // resident executor never consumed)
 hipError_t launch_step_pair(rq_device* dev, const StepPair& p) {
@@ -125,122 +116,6 @@ hipError_t launch_step_pair(rq_device* dev, const StepPair& p) {
         e = rq::launch_actor_step(dev->stream, p.b.n, p.packed, p.obs_alt, p.b.ld, p.hidden_out, p.ld_h, p.pol_act, p.ld_h, nullptr,
                                   p.precision, p.sas, p.mb_spec, p.hidden_in);
     return e;
-}
-
-// the resident kernel has left (told to, idle for too long, or never started properly): take note, and if the command posted last
-// was not consumed, run it as launches - nothing will ever publish its sequence numbers otherwise
-int resident_gone(rq_device* dev) {
-    if (!dev->res_running) return RQ_OK;
-    dev->res_running = false;
-    // A kernel that has published `exited` has nothing left to do but end (its stores were fenced before that word): whatever follows
-    // may go ahead - the next resident kernel queues behind it on res_stream by itself - and a restart does not pay for a stream
-    // synchronize (~10 us of completion signalling, once per ~100 iterations of the loop).  Otherwise (the stream was found drained,
-    // or failed) the synchronize returns at once or reports the error.
-    if (__atomic_load_n(&dev->res_mem[16], __ATOMIC_ACQUIRE) != dev->res_launch_id) RQ_HIP(hipStreamSynchronize(dev->res_stream));
-    // was it worth its launch?  A kernel that idled out after a handful of commands was not (see kResidentMinCommands): back off.
-    const uint64_t served = dev->res_posts - dev->res_posts_at_start;
-    const uint32_t why = __atomic_load_n(&dev->res_mem[17], __ATOMIC_ACQUIRE);
-    if (served >= kResidentGoodCommands) {
-        dev->res_backoff = 0;
-    } else if ((why & rq::kRbLeftIdle) && served < kResidentMinCommands) {
-        dev->res_backoff = dev->res_backoff ? std::min(2 * dev->res_backoff, kResidentMaxBackoff) : kResidentMinCommands;
-        dev->res_backoff_left = dev->res_backoff;
-    }
-    if (dev->res_pending) {
-        dev->res_pending = false;
-        const uint32_t f = __atomic_load_n(dev->mb_flag, __ATOMIC_ACQUIRE);
-        if ((int32_t)(f - dev->res_pending_last) < 0) {
-            RQ_REQUIRE((int32_t)(f - dev->res_pending_first) < 0, RQ_ERR_HIP, "the resident executor left in the middle of a command");
-            ++dev->res_replays;
-            if (dev->res_policy_mode) {
-                const PolicyCmd& p = *dev->res_pol_cmd;
-                RQ_HIP(rq::launch_actor_step(dev->stream, p.batch, p.packed, p.obs, p.ld, p.hidden, p.ld, p.act, p.ld, nullptr, p.precision,
-                                             p.sas, p.mb));
-            } else {
-                RQ_HIP(launch_step_pair(dev, *dev->res_cmd));
-            }
-        }
-    }
-    return RQ_OK;
-}
-
-// wait until the command posted last has been consumed (its first sequence number published) or the kernel has left
-int resident_drain(rq_device* dev) {
-    if (!dev->res_running || !dev->res_pending) return RQ_OK;
-    const int rc = mailbox_wait(dev, dev->res_pending_first);
-    if (rc == RQ_OK && dev->res_running) dev->res_pending = false;
-    return rc;
-}
-
-// The command line is written as four 16-byte stores, the quarter that holds `head` last: device memory behind the BAR is mapped
-// uncached or write-combining, where every store is a transaction of its own (forty 4-byte stores cost rq_step 0.5 us) and, write-
-// combining, may leave in any order until a store fence.  A reader that finds head == tail == id has the whole line - and the action
-// rows, which were written (one 16-byte store per env) before it.
-void resident_write_packet(rq_device* dev, uint32_t bits, const float* state_in, float* state_out, uint32_t seq_step, uint32_t seq_spec,
-                           uint32_t checksum) {
-    const uint32_t id = ++dev->res_packet;
-    const uint64_t a = reinterpret_cast<uint64_t>(state_in), b = reinterpret_cast<uint64_t>(state_out);
-    alignas(16) uint32_t line[16] = {};
-    line[rq::kRpHead] = id; line[rq::kRpBits] = bits;
-    line[rq::kRpStateInLo] = (uint32_t)a; line[rq::kRpStateInHi] = (uint32_t)(a >> 32);
-    line[rq::kRpStateOutLo] = (uint32_t)b; line[rq::kRpStateOutHi] = (uint32_t)(b >> 32);
-    line[rq::kRpSeqStep] = seq_step; line[rq::kRpSeqSpec] = seq_spec; line[rq::kRpChecksum] = checksum;
-    line[rq::kRpTail] = id;
-    __m128i* dst = reinterpret_cast<__m128i*>(dev->res_cmd_mem);
-    const __m128i* src = reinterpret_cast<const __m128i*>(line);
-    _mm_store_si128(dst + 1, _mm_load_si128(src + 1));
-    _mm_store_si128(dst + 2, _mm_load_si128(src + 2));
-    _mm_store_si128(dst + 3, _mm_load_si128(src + 3));
-    _mm_sfence();
-    _mm_store_si128(dst + 0, _mm_load_si128(src + 0));
-    _mm_sfence();
-}
-
-// tell the kernel to leave and wait until it has
-int resident_retire(rq_device* dev) {
-    if (!dev->res_running) return RQ_OK;
-    int rc = resident_drain(dev); if (rc) return rc;
-    if (!dev->res_running) return RQ_OK;                   // it left by itself meanwhile (resident_gone has dealt with it)
-    resident_write_packet(dev, rq::kRbQuit, nullptr, nullptr, 0, 0, 0);
-    for (uint64_t spins = 1;; ++spins) {
-        if (__atomic_load_n(&dev->res_mem[16], __ATOMIC_ACQUIRE) == dev->res_launch_id) break;
-        if ((spins & 0xFFFFu) == 0 && hipStreamQuery(dev->res_stream) != hipErrorNotReady) break;
-        __builtin_ia32_pause();
-    }
-    return resident_gone(dev);
-}
-
-int ensure_resident_memory(rq_device* dev) {
-    if (dev->res_mem) return RQ_OK;
-    void* mem = nullptr;
-    RQ_HIP(hipHostMalloc(&mem, 4096, hipHostMallocDefault));        // [0..15] command line, [16] exited, [17] why, [32..43] timing, [64..] the rows that
-    std::memset(mem, 0, 4096);                                       // travel beside a command (12 x 4 action dwords; 16 x 24 observation dwords)
-    const hipError_t e = hipStreamCreateWithFlags(&dev->res_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { (void)hipHostFree(mem); RQ_HIP(e); }
-    dev->res_mem = static_cast<uint32_t*>(mem);
-    dev->res_cmd_mem = dev->res_mem;
-    // Where the wave looks for its commands.  Pinned host memory works everywhere: every poll is a read across PCIe, and a command is
-    // seen ~1.7 us after it was written.  Where the platform maps VRAM for the CPU (large BAR) the command line lives in fine-grained
-    // device memory instead: the host's stores cross PCIe once, as posted writes, the wave polls its own memory - a host -> wave ->
-    // host round trip of 1.8 us instead of 2.5 (tools/bar_probe.hip).  The host never reads that memory.
-    int large_bar = 0;
-    if (std::getenv("RQ_RESIDENT_HOST_COMMANDS") == nullptr &&
-        hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev->ordinal) == hipSuccess && large_bar) {
-        void* fine = nullptr;
-        if (hipExtMallocWithFlags(&fine, kResCmdBytes, hipDeviceMallocFinegrained) == hipSuccess) {
-            // zeroed by the host through the BAR it will write its commands through (a hipMemset of this memory costs 8 ms the first time)
-            __m128i* z = static_cast<__m128i*>(fine);
-            for (size_t k = 0; k < kResCmdBytes / sizeof(__m128i); ++k) _mm_store_si128(z + k, _mm_setzero_si128());
-            _mm_sfence();
-            dev->res_cmd_mem = static_cast<uint32_t*>(fine);
-            dev->res_cmd_on_device = true;
-        }
-        (void)hipGetLastError();
-    }
-    if (!dev->res_cmd) dev->res_cmd = new (std::nothrow) StepPair();
-    if (!dev->res_pol_cmd) dev->res_pol_cmd = new (std::nothrow) PolicyCmd();
-    RQ_REQUIRE(dev->res_cmd && dev->res_pol_cmd, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
-    return RQ_OK;
 }
 
 
@@ -255,31 +130,6 @@ RQ_API int rq_device_set_speculation(rq_device* dev, int enable) {
     dev->speculate = enable != 0;
     dev->sp_suspended = false; dev->sp_misses = 0;
     if (!dev->speculate) { dev->sp_policy = nullptr; dev->sp_outstanding = false; }
-    return RQ_OK;
-}
-
-RQ_API int rq_device_set_resident(rq_device* dev, int enable) {
-    RQ_REQUIRE(dev, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;      // retires a running one
-    dev->res_enabled = enable != 0;
-    dev->res_backoff = dev->res_backoff_left = 0;
-    return RQ_OK;
-}
-
-RQ_API int rq_device_get_resident(const rq_device* dev, int* enabled, int* running, uint64_t* starts, uint64_t* commands, uint64_t* replays) {
-    RQ_REQUIRE(dev, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    if (enabled) *enabled = dev->res_enabled ? 1 : 0;
-    if (running) *running = dev->res_running && __atomic_load_n(&dev->res_mem[16], __ATOMIC_ACQUIRE) != dev->res_launch_id ? 1 : 0;
-    if (starts) *starts = dev->res_starts;
-    if (commands) *commands = dev->res_posts;
-    if (replays) *replays = dev->res_replays;
-    return RQ_OK;
-}
-
-RQ_API int rq_device_get_resident_timing(const rq_device* dev, uint64_t* ticks6) {
-    RQ_REQUIRE(dev && ticks6, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    RQ_REQUIRE(dev->res_mem, RQ_ERR_NOT_INITIALIZED, "no resident executor has run on this device");
-    std::memcpy(ticks6, dev->res_mem + 32, 6 * sizeof(uint64_t));
     return RQ_OK;
 }
 
@@ -367,21 +217,19 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
         pol = nullptr;
     // Could the resident executor take this step?  The loop's own shape only: host actions in, observation cached, a speculated
     // fp32 policy step behind it, out of place, on buffers the library alone writes - and the same objects as the kernel in flight.
-    const bool eligible = dev->res_enabled && pol && env->obs_alt && env->n <= kResidentMaxEnvs && next_state != state && !state->exposed &&
+    ResidentExecutor& rx = dev->resident;
+    const bool eligible = rx.enabled && pol && env->obs_alt && env->n <= kResidentMaxEnvs && next_state != state && !state->exposed &&
                           pol->precision == RQ_POLICY_FP32 && pol->sas_mode == RQ_SAS_OFF;
     const uint64_t now_ns = eligible ? host_now_ns() : 0;
-    dev->res_streak = !eligible ? 0 : now_ns - dev->res_last_step_ns < kResidentMaxGapNs && dev->res_last_step_env == env->uid ? dev->res_streak + 1 : 1;
-    if (eligible) { dev->res_last_step_ns = now_ns; dev->res_last_step_env = env->uid; }      // (in a row = the same env: two loops taking turns keep their launches)
-    dev->res_pol_streak = 0;
-    const bool bound = dev->res_running && !dev->res_policy_mode && dev->res_env == env && dev->res_env_uid == env->uid && dev->res_params == params &&
-                       dev->res_params_version == params->version && dev->res_policy == pol && dev->res_seed == rng->seed &&
-                       dev->res_packed == packed_of(pol) && std::memcmp(&dev->res_cfg, &env->cfg, sizeof(rq_env_config)) == 0 &&
-                       (env->obs_alt == dev->res_obs[0] || env->obs_alt == dev->res_obs[1]) &&
-                       (pol->hidden == dev->res_hidden[0] || pol->hidden == dev->res_hidden[1]) &&
-                       now_ns - dev->res_last_post_ns < dev->res_host_idle_ns && now_ns - dev->res_born_ns < dev->res_host_life_ns;
-    if (dev->res_running && !(eligible && bound)) { rc = resident_retire(dev); if (rc) return rc; }
-    bool resident = eligible && (bound || dev->res_streak >= kResidentStreak);
-    if (resident && !dev->res_running && dev->res_backoff_left) { --dev->res_backoff_left; resident = false; }     // see kResidentMinCommands
+    // in a row = the same env: two loops taking turns keep their launches
+    const uint32_t streak = rx.loop_streak.n = rx.loop_streak.follow(eligible, now_ns, nullptr, env->uid);
+    rx.policy_streak.n = 0;
+    ResidentBinding want{};
+    if (eligible)
+        want = {false, env, env->uid, params, params->version, pol, packed_of(pol), env->n, env->cfg, rng->seed, {env->obs, env->obs_alt},
+                {pol->hidden, pol->hidden_alt}};
+    bool resident = false;
+    rc = resident_admit(dev, eligible, want, now_ns, streak, &resident); if (rc) return rc;
     // next_state is written in full: if it shares its buffer (state.assign(next_state) of the previous iteration) it
     // gets another one; stepping a state in place (next_state == state) keeps the contents it is about to read
     rc = state_make_private(next_state, next_state == state); if (rc) return rc;
@@ -419,56 +267,25 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
     }
     bool posted = false;
     if (resident) {
-        rc = ensure_resident_memory(dev); if (rc) return rc;
-        if (!dev->res_running) {
-            // nothing of the stream's may still be in flight when a kernel outside it starts reading the same buffers
-            const hipError_t se = hipStreamSynchronize(dev->stream);
-            if (se != hipSuccess) {
-                mailbox_abort(dev, pair.mb_spec); mailbox_abort(dev, mb);
-                return fail(RQ_ERR_HIP, std::string("rq_step: hipStreamSynchronize -> ") + hipGetErrorString(se));
-            }
+        if (!rx.running) {
             rq::ResidentArgs ra{};
             ra.b = pair.b; ra.c = pair.c; ra.sc = pair.sc; ra.seed = pair.seed;
             ra.params = pair.params; ra.act = pair.act; ra.st = pair.st;
-            ra.obs_buf[0] = env->obs; ra.obs_buf[1] = env->obs_alt;
-            ra.packed = pair.packed; ra.hidden[0] = pol->hidden; ra.hidden[1] = pol->hidden_alt; ra.ld_h = pol->ld; ra.pol_act = pol->act;
+            ra.ld_h = pol->ld; ra.pol_act = pol->act;
             ra.rows_action = dev->mb_in; ra.rows_obs = dev->mb_obs; ra.rows_act = dev->mb_act; ra.flag = dev->mb_flag;
-            ra.packet = dev->res_cmd_mem; ra.exited = dev->res_mem + 16;
-            if (dev->res_cmd_on_device) ra.rows_action = reinterpret_cast<const float*>(dev->res_cmd_mem + 64);     // the rows beside the line
-            ra.timing = dev->res_timing ? reinterpret_cast<unsigned long long*>(dev->res_mem + 32) : nullptr;
-            ra.small_rows = dev->res_cmd_mem + 64;
-            ra.launch_id = ++dev->res_launch_id; if (ra.launch_id == 0) ra.launch_id = ++dev->res_launch_id;
-            ra.first_packet = dev->res_packet + 1;
-            ra.idle_ticks = dev->res_idle_ticks; ra.life_ticks = dev->res_life_ticks;
-            const hipError_t e = rq::launch_resident(dev->res_stream, ra);
-            if (e == hipSuccess) {
-                dev->res_running = true; ++dev->res_starts; dev->res_born_ns = host_now_ns(); dev->res_posts_at_start = dev->res_posts;
-                dev->res_policy_mode = false;
-                dev->res_env = env; dev->res_env_uid = env->uid; dev->res_params = params; dev->res_params_version = params->version;
-                dev->res_policy = pol; dev->res_cfg = env->cfg; dev->res_seed = rng->seed; dev->res_packed = pair.packed;
-                dev->res_obs[0] = env->obs; dev->res_obs[1] = env->obs_alt; dev->res_hidden[0] = pol->hidden; dev->res_hidden[1] = pol->hidden_alt;
-            } else {
-                (void)hipGetLastError();         // no resident executor this time: the launches below do the step
-            }
+            rc = resident_start(dev, ra, want);
         }
-        if (dev->res_running) {
-            rc = resident_drain(dev);            // one command slot: the previous command must have been taken out of it
-            if (rc) { mailbox_abort(dev, pair.mb_spec); mailbox_abort(dev, mb); return rc; }
-        }
-        if (dev->res_running) {
+        if (rc == RQ_OK && rx.running) rc = resident_drain(dev);     // one command slot: the previous command must have been taken out of it
+        if (rc) { mailbox_abort(dev, pair.mb_spec); mailbox_abort(dev, mb); return rc; }
+        if (rx.running) {
             uint32_t sum = 0;
             const uint32_t* au = reinterpret_cast<const uint32_t*>(dev->mb_in);
             for (uint32_t k = 0; k < env->n * RQ_ACTION_DIM; ++k) sum += au[k];
-            if (env->n <= rq::kResidentSmallEnvs || dev->res_cmd_on_device) {  // the small kernel reads the rows in the same load as the
-                __m128i* rows = reinterpret_cast<__m128i*>(dev->res_cmd_mem + 64);     // command line; in device memory every kernel reads them there
+            if (env->n <= rq::kResidentSmallEnvs || rx.cmd_on_device) {     // the small kernel reads the rows in the same load as the
+                __m128i* rows = reinterpret_cast<__m128i*>(resident_rows(dev));   // command line; in device memory every kernel reads them there
                 for (uint32_t k = 0; k < env->n; ++k) _mm_store_si128(rows + k, _mm_loadu_si128(reinterpret_cast<const __m128i*>(au) + k));
             }
-            *dev->res_cmd = pair;
-            dev->res_pending = true; dev->res_pending_first = pair.mb_step.seq; dev->res_pending_last = pair.mb_spec.seq;
-            const uint32_t bits = (env->obs_alt == dev->res_obs[1] ? rq::kRbObsSel : 0u) | (pol->hidden == dev->res_hidden[1] ? rq::kRbHiddenSel : 0u);
-            resident_write_packet(dev, bits, pair.state_in, pair.state_out, pair.mb_step.seq, pair.mb_spec.seq, sum);
-            dev->res_last_post_ns = host_now_ns();
-            ++dev->res_posts;
+            resident_post(dev, pair, sum);
             posted = true;
         }
     }

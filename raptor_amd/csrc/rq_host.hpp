@@ -50,9 +50,8 @@ rq_device* env_device(const rq_env* env);
 uint32_t env_num_envs(const rq_env* env);
 const float* env_finished_returns(const rq_env* env);      // device [ld]
 
-// The resident executor of the small-batch loop (rq_capi_vector.cpp resident_*) works outside the device's stream; any entry point that may touch
-// that stream first retires it (a few microseconds, and only when one is running): that is this hook, run by every DeviceScope made
-// from an rq_device.  The three calls of the loop itself construct their scope with KeepResident and retire explicitly on their slow paths.
+// The resident executor (rq_resident.cpp) works outside the device's stream; any entry point that may touch that stream first retires
+// it (a few microseconds, and only when one is running): that is this hook, run by every DeviceScope made from an rq_device.  The three calls of the loop itself construct their scope with KeepResident and retire explicitly on their slow paths.
 int resident_scope_hook(const rq_device* dev);
 struct KeepResident {};
 

@@ -3,7 +3,8 @@
 // one file) by what the entry points serve:
 //   rq_capi.cpp          library, Device, Rng, Environment, Parameters / State containers, statistics, timing diagnostics
 //   rq_capi_vector.cpp   the five l2f vector:: functions and the small-batch loop behind them: mailbox, observation cache,
-//                        speculative policy step, resident executor
+//                        speculative policy step
+//   rq_resident.cpp      the resident executor's host side (both kinds: the loop's rq_step and the policy alone)
 //   rq_capi_policy.cpp   Raptor: create / configure / reset / evaluate_step / evaluate_sequence / selftest
 //   rq_capi_rollout.cpp  the loop body x K on the device (fused, or chained under a hipGraph), trajectories, relabelling with a policy
 //   rq_capi_teacher.cpp  the teacher bank
@@ -44,24 +45,69 @@ inline uint64_t fresh_version() {
     return counter.fetch_add(1, std::memory_order_relaxed) + 1;
 }
 
-constexpr uint32_t kResidentMaxEnvs = 256;            // one workgroup, a wave per SIMD of one CU (at 512 envs the launches, spread over the chip, are faster)
-constexpr uint32_t kResidentStreak = 3;               // eligible steps in a row before a kernel is started
-// The loop must really be running: an eligible step counts towards the streak only when it follows the previous one within 200 us (the
-// README loop as the reference writes it sleeps 10 ms per step: it keeps its launches, nothing spins for it).
-constexpr uint64_t kResidentMaxGapNs = 200000;
-constexpr uint64_t kResidentIdleTicks = 30000;        // the kernel leaves after 300 us without a command (100 MHz ticks) ...
-constexpr uint64_t kResidentHostIdleNs = 150000;      // ... and the host stops posting to one it has not fed for 150 us
-// A kernel that never ends would make hipDeviceSynchronize - a learner's torch.cuda.synchronize() on another thread, any hipFree - wait
-// for as long as the loop runs: the kernel leaves between two commands once it is 1 ms old, and the host, which knows its age, retires it
-// at 0.75 ms and starts the next one (one launch per ~100 iterations at 8 envs).
-constexpr uint64_t kResidentLifeTicks = 100000;
-constexpr uint64_t kResidentHostLifeNs = 750000;
-// A kernel that left by itself (idle) after fewer than 8 commands was not worth its launch - something stalls the loop that the host
-// cannot see (a device-wide synchronize of the caller's own, a slow consumer): the next kernel is started only after 8, 16, ... 1 024
-// further eligible steps; a kernel that served 64 commands resets that.
-constexpr uint32_t kResidentMinCommands = 8, kResidentGoodCommands = 64, kResidentMaxBackoff = 1024;
-constexpr size_t kResCmdBytes = 8192;                 // command memory: [0..15] the command line, [64 .. 64 + 4 x 256) the action rows
+// the two launches of a small-batch step: k_step (+ the next observation) and the speculative policy step on it
+struct StepPair {
+    rq::Batch b; rq::StepCfg c; rq::SampleCfg sc; uint64_t seed;
+    const float* params; const float* state_in; float* act; float* state_out; rq::StatsPtrs st;
+    rq::Mailbox mb_step; float* obs_alt;
+    bool spec;
+    const float* packed; float* hidden_out; uint32_t ld_h; float* pol_act; int precision; rq::SasArgs sas;
+    rq::Mailbox mb_spec; const float* hidden_in;
+};
 
+// the launch of a small-batch policy step on host rows (dev->mb_in -> dev->mb_out): what a policy command replays as
+struct PolicyCmd {
+    uint32_t batch; const float* packed; float* obs; float* hidden; uint32_t ld; float* act; int precision; rq::SasArgs sas; rq::Mailbox mb;
+};
+
+// ---- resident executor (rq_resident.cpp; kernels: rq_kernels.hip k_resident_small / k_resident_loop / k_resident_policy) -------------
+constexpr uint32_t kResidentMaxEnvs = 256;            // one workgroup, a wave per SIMD of one CU (at 512 envs the launches, spread over the chip, are faster)
+
+// What a resident kernel is started for, and what a call must still be for if its command is to go to that kernel: the same objects at
+// the same versions, and the buffers it names among the kernel's ping-pong pairs.  The loop's pairs are {obs, obs_alt} and {hidden,
+// hidden_alt} (a command's bits pick the current one); the policy's are {nullptr, nullptr} and {hidden, hidden} (updated in place).
+// Of a call's own pairs, obs[1] is where its step writes the observation and hidden[0] the hidden state it reads.
+struct ResidentBinding {
+    bool policy_kind;                            // k_resident_policy (else the loop's kernels)
+    const rq_env* env; uint64_t env_uid;
+    const rq_params* params; uint64_t params_version;
+    const rq_policy* pol; const float* packed; uint32_t batch;
+    rq_env_config cfg; uint64_t seed;
+    float* obs[2]; float* hidden[2];
+};
+
+// eligible calls in a row, each within kResidentMaxGapNs of the one before and for the same (who, key)
+struct ResidentStreak {
+    uint32_t n = 0;
+    uint64_t last_ns = 0; const void* who = nullptr; uint64_t key = 0;      // the last eligible call (`who` is never dereferenced)
+    uint32_t follow(bool eligible, uint64_t now_ns, const void* call_who, uint64_t call_key);     // this call's length (0: not eligible)
+};
+
+struct ResidentExecutor {
+    // settings, read from the environment at rq_device_create (resident_setup)
+    bool enabled = true;                 // RQ_NO_RESIDENT: off; rq_device_set_resident
+    bool timing = false;                 // RQ_RESIDENT_TIMING: the kernel records its timestamps (rq_device_get_resident_timing)
+    uint64_t idle_ticks = 0, life_ticks = 0, host_idle_ns = 0, host_life_ns = 0;
+    // memory (rq_resident.cpp ResidentWord)
+    hipStream_t stream = nullptr;
+    uint32_t* mem = nullptr;             // pinned: the command line, what the kernel says as it leaves, its timing, the rows
+    uint32_t* cmd = nullptr;             // where commands are written: mem, or - on a large-BAR platform - fine-grained device memory
+    bool cmd_on_device = false;
+    // the kernel
+    bool running = false;
+    ResidentBinding bound{};             // what the running kernel was started for
+    uint32_t launch_id = 0, packet = 0;  // id of the kernel that is running; commands posted to it
+    uint64_t born_ns = 0;                // host clock at its launch
+    uint64_t last_post_ns = 0;           // host clock of the last command: a kernel idle for too long may be leaving, it is not posted to
+    uint64_t posts_at_start = 0;         // posts when it was started: what it has served = posts - this
+    uint32_t backoff = 0, backoff_left = 0;     // eligible calls still to let pass before another kernel is started
+    ResidentStreak loop_streak, policy_streak;  // the two kinds count apart: rq_step zeroes the policy's, any other call both
+    // the command posted last: what a replay as launches needs (of the running kernel's kind)
+    bool pending = false;                // posted and not known to have been consumed
+    uint32_t pending_first = 0, pending_last = 0;   // its sequence numbers: the first one published = consumed
+    union { StepPair step; PolicyCmd policy; } last{};
+    uint64_t starts = 0, posts = 0, replays = 0;    // diagnostics
+};
 
 struct rq_device {
     int ordinal = 0;
@@ -125,63 +171,13 @@ struct rq_device {
     bool sp_outstanding = false;         // a speculated step was launched and not taken (yet)
     bool sp_suspended = false;
     uint32_t sp_misses = 0;
-    // Resident executor of the small-batch loop (round 6; kernel: rq_kernels.hip k_resident_loop).  While the host keeps calling
-    // rq_step on the same small env / params / policy, the step and the speculative policy step are not launched: they are posted,
-    // as a 64-byte command in pinned memory, to one workgroup that stays on the device - on a stream of its own - and publishes the
-    // same two sequence numbers in mb_flag.  Anything else the device is asked to do retires it first (resident_scope_hook).
-    hipStream_t res_stream = nullptr;
-    uint32_t* res_mem = nullptr;         // pinned: [0..15] the command line, [16] launch id of the kernel that has left
-    uint32_t* res_cmd_mem = nullptr;     // where commands are written: res_mem, or - on a large-BAR platform - fine-grained DEVICE memory the
-                                         // host writes straight into ([0..15] command line, [64..] action rows): the wave polls local memory
-    bool res_cmd_on_device = false;
-    bool res_enabled = true;             // RQ_NO_RESIDENT in the environment: off
-    bool res_running = false;
-    uint32_t res_launch_id = 0, res_packet = 0;     // id of the kernel that is running; commands posted to it
-    uint32_t res_streak = 0;             // eligible rq_step calls in a row with nothing else asked of the device in between
-    uint64_t res_last_post_ns = 0;       // host clock of the last command: a kernel idle for too long may be leaving, it is not posted to
-    uint64_t res_born_ns = 0;            // host clock at the kernel's launch
-    uint64_t res_last_step_ns = 0;       // host clock of the last eligible rq_step (the streak counts steps that follow one another closely)
-    uint64_t res_last_step_env = 0;      // ... and the uid of the env it stepped
-    uint64_t res_posts_at_start = 0;     // res_posts when the running kernel was started: what it has served = res_posts - this
-    uint32_t res_backoff = 0, res_backoff_left = 0;    // eligible steps still to let pass before another kernel is started
-    uint64_t res_idle_ticks = kResidentIdleTicks, res_life_ticks = kResidentLifeTicks;       // RQ_RESIDENT_IDLE_TICKS / _LIFE_TICKS (tests)
-    uint64_t res_host_idle_ns = kResidentHostIdleNs, res_host_life_ns = kResidentHostLifeNs; // RQ_RESIDENT_HOST_IDLE_NS / _HOST_LIFE_NS (tests)
-    uint64_t res_starts = 0, res_posts = 0, res_replays = 0;     // diagnostics
-    const rq_env* res_env = nullptr; uint64_t res_env_uid = 0;   // what the running kernel was started for
-    const rq_params* res_params = nullptr; uint64_t res_params_version = 0;
-    rq_policy* res_policy = nullptr;
-    rq_env_config res_cfg{}; uint64_t res_seed = 0;
-    float* res_obs[2] = {nullptr, nullptr}; float* res_hidden[2] = {nullptr, nullptr}; const float* res_packed = nullptr;
-    bool res_timing = false;             // RQ_RESIDENT_TIMING in the environment: the kernel records its timestamps (rq_device_get_resident_timing)
-    bool res_pending = false;            // res_cmd was posted and is not known to have been consumed
-    struct StepPair* res_cmd = nullptr;  // the command most recently posted: what a replay as launches needs
-    // The same executor serving a policy ALONE (rq_policy_evaluate_step with host rows, at most 16 of them: README.md:17-25, a caller
-    // with a simulator of its own; kernel: k_resident_policy).  One kernel per device at a time, of either kind.
-    bool res_policy_mode = false;        // the running kernel is k_resident_policy
-    uint32_t res_pol_streak = 0;         // eligible rq_policy_evaluate_step calls in a row (each within kResidentMaxGapNs of the one before)
-    uint64_t res_pol_last_ns = 0;        // host clock of the last of them
-    const rq_policy* res_pol_last = nullptr; uint32_t res_pol_last_batch = 0;      // ... and whose it was (never dereferenced)
-    uint32_t res_pol_batch = 0;          // the batch the running kernel was started for
-    float* res_pol_hidden = nullptr;     // the hidden-state buffer it keeps up to date
-    uint32_t res_pending_first = 0, res_pending_last = 0;   // the posted command's sequence numbers: the first one published = consumed
-    struct PolicyCmd* res_pol_cmd = nullptr;                // the policy command most recently posted (replay)
+    // Resident executor (round 6; rq_resident.cpp): while the host keeps calling rq_step on the same small env / params / policy, or
+    // rq_policy_evaluate_step on the same policy, the work is not launched but posted, as a 64-byte command, to one workgroup that stays
+    // on the device - on a stream of its own - and publishes the same sequence numbers in mb_flag.  Anything else the device is asked
+    // to do retires it first (resident_scope_hook).
+    ResidentExecutor resident;
 };
 constexpr uint32_t kSpeculationMissLimit = 4;
-// the two launches of a small-batch step: k_step (+ the next observation) and the speculative policy step on it
-struct StepPair {
-    rq::Batch b; rq::StepCfg c; rq::SampleCfg sc; uint64_t seed;
-    const float* params; const float* state_in; float* act; float* state_out; rq::StatsPtrs st;
-    rq::Mailbox mb_step; float* obs_alt;
-    bool spec;
-    const float* packed; float* hidden_out; uint32_t ld_h; float* pol_act; int precision; rq::SasArgs sas;
-    rq::Mailbox mb_spec; const float* hidden_in;
-};
-
-// the launch of a small-batch policy step on host rows (dev->mb_in -> dev->mb_out): what a policy command replays as
-struct PolicyCmd {
-    uint32_t batch; const float* packed; float* obs; float* hidden; uint32_t ld; float* act; int precision; rq::SasArgs sas; rq::Mailbox mb;
-};
-
 struct rq_rng {
     rq_device* dev = nullptr;
     uint64_t seed = 0;
@@ -311,12 +307,21 @@ int mailbox_wait(rq_device* dev, uint32_t seq);
 int mailbox_in_free(rq_device* dev);
 rq::Mailbox mailbox_for(rq_device* dev, const float* rows_in, uint32_t in_stride, float* rows_out);
 void mailbox_abort(rq_device* dev, const rq::Mailbox& mb);
-int resident_gone(rq_device* dev);
-int resident_retire(rq_device* dev);
-int ensure_resident_memory(rq_device* dev);
+hipError_t launch_step_pair(rq_device* dev, const StepPair& p);
+
+// ---- rq_resident.cpp: the resident executor ----
 uint64_t host_now_ns();
-void resident_write_packet(rq_device* dev, uint32_t bits, const float* state_in, float* state_out, uint32_t seq_step, uint32_t seq_spec,
-                           uint32_t checksum);
+void resident_setup(rq_device* dev);         // rq_device_create: settings, stream and command memory (a failure is tolerated)
+void resident_teardown(rq_device* dev);      // rq_device_destroy: retire, free
+int resident_retire(rq_device* dev);         // tell a running kernel to leave and wait until it has
+int resident_gone(rq_device* dev);           // the kernel has left: replay its command if it never consumed it
+bool resident_left(const rq_device* dev);    // has the running kernel published that it left?
+int resident_admit(rq_device* dev, bool ready, const ResidentBinding& want, uint64_t now_ns, uint32_t streak, bool* use);
+int resident_start(rq_device* dev, rq::ResidentArgs& ra, const ResidentBinding& want);
+uint32_t* resident_rows(const rq_device* dev);   // command memory beside the line: the rows that travel with a command
+void resident_post(rq_device* dev, const StepPair& p, uint32_t checksum);
+void resident_post(rq_device* dev, const PolicyCmd& p, uint32_t checksum);
+int resident_drain(rq_device* dev);
 
 // ---- rq_capi_policy.cpp ----
 void policy_free_buffers(rq_policy* pol);

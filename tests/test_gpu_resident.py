@@ -61,7 +61,7 @@ def test_readme_loop_is_bit_identical_with_and_without_the_resident_executor(dev
     on = _loop(device, n, 150, True)
     assert _same(off, on)
     assert off[6]["commands"] == 0 and on[6]["commands"] >= 140 and on[6]["replays"] == 0, (off[6], on[6])
-    assert on[6]["starts"] <= 10         # one kernel per 0.75 ms of looping (rq_objects.hpp kResidentHostLifeNs), none per iteration
+    assert on[6]["starts"] <= 10         # one kernel per 0.75 ms of looping (rq_resident.cpp kResidentHostLifeNs), none per iteration
 
 
 def test_beyond_256_envs_the_loop_keeps_its_launches(device):
@@ -195,7 +195,7 @@ def test_idle_and_old_kernels_leave_by_themselves_and_the_loop_goes_on(device):
 
 def test_the_loop_as_the_reference_paces_it_keeps_its_launches(device):
     """README.md:94-101 sleeps dts[-1] = 10 ms after every step: a wave spinning through that sleep would serve nobody.  Steps count
-    towards a resident kernel only when they follow one another within 200 us (rq_objects.hpp kResidentMaxGapNs)."""
+    towards a resident kernel only when they follow one another within 200 us (rq_resident.cpp kResidentMaxGapNs)."""
     on = _loop(device, 8, 12, True, lambda it, L: time.sleep(0.002))
     assert on[6]["starts"] == 0 and on[6]["commands"] == 0, on[6]
 
@@ -243,7 +243,7 @@ sys.path.insert(0, %r); sys.path.insert(0, %r)
 import raptor_amd.l2f as l2f
 from test_gpu_resident import _loop, _same
 dev = l2f.Device(0)
-pause = lambda it, L: time.sleep(0.001) if it %% 23 == 3 else None     # (>= 8 commands per kernel: no back-off, see rq_objects.hpp)
+pause = lambda it, L: time.sleep(0.001) if it %% 23 == 3 else None     # (>= 8 commands per kernel: no back-off, see rq_resident.cpp)
 on = _loop(dev, 8, 400, True, pause)
 off = _loop(dev, 8, 400, False, pause)
 print("STATS", on[6])

@@ -12,8 +12,7 @@ mkdir -p "$out/tools"; git show "$rev:tools/codeobj_check.py" > "$out/tools/code
 touch "$out/raptor_amd/__init__.py"
 (cd "$out" && python -c "
 import sys; sys.path.insert(0, '.')
-import importlib.util
-spec = importlib.util.spec_from_file_location('b', 'raptor_amd/build.py'); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+import raptor_amd.build as b      # as a package module: build.py imports gfx950_errata relatively
 print(b.build(force=True))")
 cp "$out/raptor_amd/libraptor_quad.so" "$out.so"
 echo "$out.so"
