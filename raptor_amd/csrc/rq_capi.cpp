@@ -236,8 +236,8 @@ RQ_API int rq_device_create(int ordinal, rq_device** out) {
         delete d;
         return fail(RQ_ERR_HIP, "rq_device_create: stream/event creation failed");
     }
-    d->speculate = std::getenv("RQ_NO_SPECULATION") == nullptr;
     d->graphs_enabled = std::getenv("RQ_NO_GRAPHS") == nullptr;
+    small_batch_setup(d);
     resident_setup(d);
     device_registry(d, +1);
     *out = d;
@@ -257,12 +257,7 @@ RQ_API int rq_device_destroy(rq_device* dev) {
     if (dev->staging) (void)hipHostFree(dev->staging);
     if (dev->rows) (void)hipFree(dev->rows);
     if (dev->rows2) (void)hipFree(dev->rows2);
-    if (dev->mb_flag) (void)hipHostFree(dev->mb_flag);
-    if (dev->mb_in) (void)hipHostFree(dev->mb_in);
-    if (dev->mb_out) (void)hipHostFree(dev->mb_out);
-    if (dev->mb_obs) (void)hipHostFree(dev->mb_obs);
-    if (dev->mb_act) (void)hipHostFree(dev->mb_act);
-    if (dev->mb_counter) (void)hipFree(dev->mb_counter);
+    mailbox_free(dev);
     if (dev->staging_in) (void)hipHostFree(dev->staging_in);
     delete dev;
     return RQ_OK;
@@ -635,10 +630,7 @@ RQ_API int rq_state_assign(rq_state* dst, const rq_state* src) {
         dst->d = src->d; dst->refs = src->refs; ++*dst->refs;
     }
     dst->version = fresh_version();
-    rq_device* dev = dst->env->dev;                   // the cached observation of src is the observation of dst now
-    if (dev->oc_state[0] == src && dev->oc_version[0] == src->version && !src->exposed) {
-        dev->oc_state[1] = dst; dev->oc_version[1] = dst->version;
-    }
+    obs_cache_follow_assign(dst->env->dev, dst, src);
     return RQ_OK;
 }
 RQ_API int rq_state_get(const rq_state* s, float* host_out) {

@@ -1,7 +1,5 @@
 // rq_capi_policy.cpp - foundation_policy.Raptor behind the C ABI (README.md:19-24,48,94,97; checkpoint.h:34-194): create, the optional
 // Standardize / SampleAndSquash stages, reset, evaluate_step (with the small-batch loop's speculation hit), evaluate_sequence, selftest.
-#include <emmintrin.h>
-
 #include "rq_objects.hpp"
 
 namespace rqh {
@@ -130,7 +128,7 @@ RQ_API int rq_policy_destroy(rq_policy* pol) {
     if (!pol) return RQ_OK;
     DeviceScope on_device(pol->ordinal);
     if (device_registry(pol->dev, 0)) (void)resident_retire(pol->dev);
-    policy_registry(pol, -1);      // rq_device::last_policy may still name this object: it is checked against the registry
+    policy_registry(pol, -1);      // rq_device::spec.last_policy may still name this object: it is checked against the registry
     policy_free_buffers(pol);
     if (pol->w_dev) (void)hipFree(pol->w_dev);
     if (pol->w_packed) (void)hipFree(pol->w_packed);
@@ -231,40 +229,8 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
     DeviceScope on_device(pol->dev, rq::KeepResident{}); int rc = on_device.rc; if (rc) return rc;
     rq_device* dev = pol->dev;
     if (observation && action && !env && batch < kGpuLayoutMinEnvs) {
-        // Did rq_step already evaluate this policy on exactly these rows (speculative step)?  Same policy, hidden state
-        // untouched since, the cached observation still the one it read, and the caller's rows bit-identical to it.
-        if (dev->sp_policy == pol && dev->sp_policy_version == pol->version && dev->sp_batch == batch && dev->oc_env &&
-            dev->sp_oc_seq == dev->oc_seq && mailbox_wait(dev, dev->oc_seq) == RQ_OK) {
-            bool same = true;
-            for (uint32_t i = 0; i < batch && same; ++i)
-                same = std::memcmp(observation + (size_t)i * obs_stride, dev->mb_obs + (size_t)i * RQ_OBSERVATION_DIM,
-                                   RQ_POLICY_INPUT_DIM * sizeof(float)) == 0;
-            if (same) {
-                rc = mailbox_wait(dev, dev->sp_seq); if (rc) return rc;
-                std::memcpy(action, dev->mb_act, (size_t)batch * RQ_ACTION_DIM * sizeof(float));
-                std::swap(pol->hidden, pol->hidden_alt);       // the speculated step becomes the policy's state
-                pol->version = fresh_version();
-                dev->sp_policy = nullptr;
-                dev->last_policy = pol;
-                dev->sp_outstanding = false; dev->sp_misses = 0;
-                return RQ_OK;
-            }
-        }
-        // a speculated step of THIS policy that did not match (other rows, hidden state touched since) is spent; ANOTHER policy's
-        // stays available - it depends on that policy's version and the cached rows only (a loop evaluating a student and a teacher
-        // on the same rows used to throw the teacher's step away here, every iteration, until speculation was suspended for good)
-        if (dev->sp_policy == pol) { speculation_unused(dev); dev->sp_policy = nullptr; }
-        if (dev->sp_suspended && dev->speculate && dev->last_policy == pol && dev->oc_env && batch == dev->oc_n &&
-            mailbox_wait(dev, dev->oc_seq) == RQ_OK) {
-            // suspended after a run of misses: this call is what a hit looks like (the rows the last step cached, handed
-            // to the policy that was evaluated before it) - the loop is back in the reference's shape, speculate again
-            bool same = true;
-            for (uint32_t i = 0; i < batch && same; ++i)
-                same = std::memcmp(observation + (size_t)i * obs_stride, dev->mb_obs + (size_t)i * RQ_OBSERVATION_DIM,
-                                   RQ_POLICY_INPUT_DIM * sizeof(float)) == 0;
-            if (same) { dev->sp_suspended = false; dev->sp_misses = 0; }
-        }
-        dev->last_policy = pol;         // the policy rq_step will speculate with
+        bool hit = false;
+        rc = speculation_take(dev, pol, observation, batch, obs_stride, action, &hit); if (rc || hit) return rc;
     }
     // ---- the policy alone, at most 16 rows, called again and again (README.md:17-25: a caller with a simulator of its own): from the
     // third call in a row on - each within 200 us of the one before, nothing else asked of the device in between - the rows go to a
@@ -287,31 +253,18 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
         rc = ensure_mailbox(dev); if (rc) return rc;
         if (!rx.running) {
             rq::ResidentArgs ra{};
-            ra.b = rq::Batch{batch, pol->ld, 0};
-            ra.ld_h = pol->ld; ra.pol_act = pol->act; ra.rows_act = dev->mb_out; ra.flag = dev->mb_flag;
+            ra.b = rq::Batch{batch, pol->ld, 0}; ra.ld_h = pol->ld; ra.pol_act = pol->act;
             rc = resident_start(dev, ra, want); if (rc) return rc;
         }
         if (rx.running) {
-            rc = mailbox_in_free(dev); if (rc) return rc;
-            // the rows twice: compact in the mailbox (what a replay as a launch reads), and - padded to whole 16-byte words, one store
-            // each - in command memory, before the line that announces them
-            uint32_t sum = 0;
-            __m128i* rows = reinterpret_cast<__m128i*>(resident_rows(dev));
-            for (uint32_t i = 0; i < batch; ++i) {
-                alignas(16) float row[rq::kResidentPolicyRow] = {};
-                std::memcpy(row, observation + (size_t)i * obs_stride, RQ_POLICY_INPUT_DIM * sizeof(float));
-                std::memcpy(dev->mb_in + (size_t)i * RQ_POLICY_INPUT_DIM, row, RQ_POLICY_INPUT_DIM * sizeof(float));
-                for (int k = 0; k < RQ_POLICY_INPUT_DIM; ++k) { uint32_t u; std::memcpy(&u, &row[k], 4); sum += u; }
-                for (uint32_t k = 0; k < rq::kResidentPolicyRow / 4; ++k)
-                    _mm_store_si128(rows + (size_t)i * (rq::kResidentPolicyRow / 4) + k, _mm_load_si128(reinterpret_cast<const __m128i*>(row) + k));
-            }
-            const rq::Mailbox mb = mailbox_for(dev, dev->mb_in, RQ_POLICY_INPUT_DIM, dev->mb_out);
+            rc = mailbox_put_in(dev, observation, batch, RQ_POLICY_INPUT_DIM, obs_stride); if (rc) return rc;     // what a replay reads
+            const rq::Mailbox mb = mailbox_for(dev, true, RQ_POLICY_INPUT_DIM, MbOut::out);
             resident_post(dev, PolicyCmd{batch, packed_of(pol), pol->obs, pol->hidden, pol->ld, pol->act, pol->precision,
-                                         sas_of(pol, pol->sas_counter, nullptr, 0), mb}, sum);
+                                         sas_of(pol, pol->sas_counter, nullptr, 0), mb});
             pol->version = fresh_version();                 // as policy_size does for the launch: the hidden state moves on
             rx.policy_streak.n = streak;
             rc = resident_drain(dev); if (rc) return rc;    // (a kernel that had left: noticed in there, replayed as the launch)
-            std::memcpy(action, dev->mb_out, (size_t)batch * RQ_ACTION_DIM * sizeof(float));
+            std::memcpy(action, mb.rows_out, (size_t)batch * RQ_ACTION_DIM * sizeof(float));
             return RQ_OK;
         }
     }
@@ -319,43 +272,22 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
     rc = policy_size(pol, batch); if (rc) return rc;
     rx.policy_streak.n = streak;                              // (the two calls above are "something else asked of the device": not this one)
     const bool mailbox = batch < kGpuLayoutMinEnvs && (observation || action);
-    const float* d_obs; uint32_t ld_obs;
-    const float* rows_in = nullptr;
-    if (observation && mailbox) {
-        rc = ensure_mailbox(dev); if (rc) return rc;
-        rc = mailbox_in_free(dev); if (rc) return rc;
-        if (obs_stride == RQ_POLICY_INPUT_DIM) {
-            std::memcpy(dev->mb_in, observation, (size_t)batch * RQ_POLICY_INPUT_DIM * sizeof(float));
-        } else {
-            for (uint32_t i = 0; i < batch; ++i)
-                std::memcpy(dev->mb_in + (size_t)i * RQ_POLICY_INPUT_DIM, observation + (size_t)i * obs_stride,
-                            RQ_POLICY_INPUT_DIM * sizeof(float));
-        }
-        rows_in = dev->mb_in;
-        d_obs = pol->obs; ld_obs = pol->ld;     // unused by the kernel when rows_in is set
-    } else if (observation) {
-        rc = host_to_soa(dev, observation, batch, obs_stride, pol->ld, RQ_POLICY_INPUT_DIM, pol->obs);
-        if (rc) return rc;
-        d_obs = pol->obs; ld_obs = pol->ld;
-    } else {
-        d_obs = env->obs; ld_obs = env->ld;
-    }
+    if (mailbox) { rc = ensure_mailbox(dev); if (rc) return rc; }
+    const bool rows_in = observation && mailbox;      // the kernel reads the mailbox's rows, not d_obs
+    if (rows_in) rc = mailbox_put_in(dev, observation, batch, RQ_POLICY_INPUT_DIM, obs_stride);
+    else if (observation) rc = host_to_soa(dev, observation, batch, obs_stride, pol->ld, RQ_POLICY_INPUT_DIM, pol->obs);
+    if (rc) return rc;
+    const float* d_obs = observation ? pol->obs : env->obs;
+    const uint32_t ld_obs = observation ? pol->ld : env->ld;
     float* d_act = action ? pol->act : env->act;
     const uint32_t ld_act = action ? pol->ld : env->ld;
     rq::Mailbox mb{};
-    if (mailbox) {
-        rc = ensure_mailbox(dev); if (rc) return rc;
-        mb = mailbox_for(dev, rows_in, RQ_POLICY_INPUT_DIM, action ? dev->mb_out : nullptr);
-    }
+    if (mailbox) mb = mailbox_for(dev, rows_in, RQ_POLICY_INPUT_DIM, action ? MbOut::out : MbOut::none);
     RQ_HIP_MB(rq::launch_actor_step(dev->stream, batch, packed_of(pol), d_obs, ld_obs, pol->hidden, pol->ld, d_act,
                                     ld_act, nullptr, pol->precision,
                                     sas_of(pol, pol->sas_counter, nullptr, env ? env->offset : 0), mb), dev, mb);
     if (pol->sas_mode == RQ_SAS_SAMPLE) pol->sas_counter += 1;
-    if (action && mailbox) {
-        rc = mailbox_wait(dev, mb.seq); if (rc) return rc;
-        std::memcpy(action, dev->mb_out, (size_t)batch * RQ_ACTION_DIM * sizeof(float));
-        return RQ_OK;
-    }
+    if (action && mailbox) return mailbox_copy_out(dev, mb.seq, mb.rows_out, action, (size_t)batch * RQ_ACTION_DIM);
     if (action) return soa_to_host(dev, pol->act, batch, pol->ld, RQ_ACTION_DIM, action);
     return RQ_OK;
 }

@@ -48,7 +48,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = policy_size(policy, env->n); if (rc) return rc;
     RQ_REQUIRE(policy->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy batch does not match the env");
-    if (dev->oc_env == env) obs_cache_drop(dev);
+    obs_cache_drop_if(dev, env);
     if (n_steps) { rc = state_make_private(state, true); if (rc) return rc; }      // steps the state in place
     const rq::Batch b = batch_of(env);
     const rq::StepCfg sc = rq::step_cfg(env->cfg);

@@ -2,8 +2,8 @@
 // C-ABI layer share.  Round 6 split rq_capi.cpp (2 300 lines: handle management, host caches, speculation, graphs, teacher packing in
 // one file) by what the entry points serve:
 //   rq_capi.cpp          library, Device, Rng, Environment, Parameters / State containers, statistics, timing diagnostics
-//   rq_capi_vector.cpp   the five l2f vector:: functions and the small-batch loop behind them: mailbox, observation cache,
-//                        speculative policy step
+//   rq_capi_vector.cpp   the five l2f vector:: functions
+//   rq_small_batch.cpp   the small-batch loop behind them and behind evaluate_step: mailbox, observation cache, speculative policy step
 //   rq_resident.cpp      the resident executor's host side (both kinds: the loop's rq_step and the policy alone)
 //   rq_capi_policy.cpp   Raptor: create / configure / reset / evaluate_step / evaluate_sequence / selftest
 //   rq_capi_rollout.cpp  the loop body x K on the device (fused, or chained under a hipGraph), trajectories, relabelling with a policy
@@ -55,7 +55,7 @@ struct StepPair {
     rq::Mailbox mb_spec; const float* hidden_in;
 };
 
-// the launch of a small-batch policy step on host rows (dev->mb_in -> dev->mb_out): what a policy command replays as
+// the launch of a small-batch policy step on host rows (mailbox in -> out): what a policy command replays as
 struct PolicyCmd {
     uint32_t batch; const float* packed; float* obs; float* hidden; uint32_t ld; float* act; int precision; rq::SasArgs sas; rq::Mailbox mb;
 };
@@ -109,6 +109,43 @@ struct ResidentExecutor {
     uint64_t starts = 0, posts = 0, replays = 0;    // diagnostics
 };
 
+// ---- the small-batch loop (rq_small_batch.cpp).  Mailbox (rq::Mailbox): below kGpuLayoutMinEnvs envs rows cross the boundary in pinned
+// host memory the kernels read and write themselves, and the host waits on a flag instead of the stream.
+struct HostMailbox {
+    uint32_t* flag = nullptr;      // pinned host: sequence number of the last finished mailbox launch
+    uint32_t* counter = nullptr;   // device: workgroup counter of the launch in flight
+    float* in = nullptr, *out = nullptr;     // pinned host rows read by kernels (observations / actions), rows written by kernels
+    float* obs = nullptr, *act = nullptr;    // pinned host rows of the observation cache [n][RQ_OBSERVATION_DIM], of the speculated action [n][4]
+    uint32_t seq = 0, in_busy = 0;     // the last sequence number handed to a launch; that of the last launch that reads `in`
+};
+enum class MbOut { none, out, obs, act };     // which pinned rows a mailbox launch writes
+// Observation cache (round 3): k_step also assembles the observation of the state it produced - into the env's device buffer and, row-major,
+// into the mailbox's `obs` rows - so that the observe() that follows step() + assign() (README.md:96-99) is a host memcpy, no launch.  Valid
+// for the (env, params, state) objects and versions recorded here; any write to one of them, a real observe launch or another step ends it.
+struct ObservationCache {
+    const rq_env* env = nullptr; uint64_t env_uid = 0;                     // env == nullptr: nothing cached
+    const rq_params* params = nullptr; uint64_t params_version = 0;
+    const rq_state* state[2] = {nullptr, nullptr};     // the state k_step wrote, and the one it was assigned to
+    uint64_t version[2] = {0, 0};
+    uint32_t seq = 0, n = 0;       // mailbox sequence number of the launch that fills the cache; its rows (the env may be gone by then)
+    bool in_alt = false;           // the field-major copy still sits in the env's obs_alt (not yet swapped in)
+};
+// Speculative policy step (round 3): the reference's loop hands the observation it was just given straight to Raptor.evaluate_step
+// (README.md:96-97), so rq_step also launches the policy last evaluated here on the observation it caches (hidden state into the policy's
+// spare buffer, actions into the mailbox's `act`).  evaluate_step takes that result - a memcmp, a memcpy and a pointer swap, no launch - iff
+// called with bit-identical rows and the same policy at the same version, and only while the cache entry it was made from still exists
+// (speculation_current: obs_cache.env set and oc_seq == obs_cache.seq).  After kSpeculationMissLimit untaken steps in a row (each a wasted
+// launch) the device stops speculating; it resumes when evaluate_step is again called with exactly the cached rows.
+struct Speculation {
+    bool enabled = true;                 // rq_device_set_speculation; RQ_NO_SPECULATION in the environment: off at creation
+    rq_policy* last_policy = nullptr;    // the policy of the most recent small-batch host evaluate_step
+    rq_policy* policy = nullptr; uint64_t policy_version = 0;    // speculation in flight / available for this policy at this version
+    uint32_t batch = 0, seq = 0, oc_seq = 0;
+    bool outstanding = false;            // a speculated step was launched and not taken (yet)
+    bool suspended = false; uint32_t misses = 0;
+};
+constexpr uint32_t kSpeculationMissLimit = 4;
+
 struct rq_device {
     int ordinal = 0;
     hipStream_t stream = nullptr;
@@ -133,51 +170,15 @@ struct rq_device {
     size_t staging_in_bytes = 0;
     hipEvent_t ev_h2d = nullptr;   // recorded after the last copy out of staging_in
     bool h2d_pending = false;
-    // small-batch mailbox (rq::Mailbox): pinned, device-visible rows + completion flag
-    uint32_t* mb_flag = nullptr;   // pinned host: sequence number of the last finished mailbox launch
-    uint32_t* mb_counter = nullptr;  // device: workgroup counter of the launch in flight
-    float* mb_in = nullptr;        // pinned host rows read by kernels (observations / actions)
-    float* mb_out = nullptr;       // pinned host rows written by kernels
-    uint32_t mb_seq = 0;           // last sequence number handed to a launch
-    uint32_t mb_in_busy = 0;       // sequence number of the last launch that reads mb_in
-    // observation cache of the small-batch loop (round 3): k_step also assembles the observation of the state it
-    // produced - into the env's device buffer and, row-major, into pinned host memory - so that the observe() that
-    // follows step() + assign() (README.md:96-99) is a host memcpy, no launch.  Valid for the (env, params, state)
-    // objects and versions recorded here; any write to one of them, a real observe launch or another env's step ends it.
-    float* mb_obs = nullptr;       // pinned host rows [n][RQ_OBSERVATION_DIM]
-    const rq_env* oc_env = nullptr;
-    const rq_params* oc_params = nullptr;
-    uint64_t oc_params_version = 0;
-    const rq_state* oc_state[2] = {nullptr, nullptr};   // the state k_step wrote, and the one it was assigned to
-    uint64_t oc_version[2] = {0, 0};
-    uint64_t oc_env_uid = 0;
-    uint32_t oc_seq = 0;           // mailbox sequence number of the launch that fills the cache
-    uint32_t oc_n = 0;             // rows in the cache (the env itself may be gone by the time this is looked at)
-    bool oc_in_alt = false;        // the field-major copy still sits in the env's obs_alt (not yet swapped in)
-    // speculative policy step of the small-batch loop (round 3): the reference's loop hands the observation it was just
-    // given straight to Raptor.evaluate_step (README.md:96-97).  rq_step therefore also launches the policy this device
-    // last evaluated on the observation it cached - new hidden state into the policy's spare buffer, action rows into
-    // pinned memory.  evaluate_step takes that result iff it is called with bit-identical rows, the same policy and an
-    // untouched hidden state (then: memcmp + memcpy + a pointer swap, no launch); anything else ignores it.
-    rq_policy* last_policy = nullptr;    // the policy of the most recent small-batch host evaluate_step
-    rq_policy* sp_policy = nullptr;      // speculation in flight / available for this policy ...
-    uint64_t sp_policy_version = 0;      // ... at this hidden-state version
-    uint32_t sp_batch = 0, sp_seq = 0, sp_oc_seq = 0;
-    float* mb_act = nullptr;             // pinned host rows [n][4] of the speculated action
-    bool speculate = true;               // rq_device_set_speculation; RQ_NO_SPECULATION in the environment: off at creation
-    // A speculated step nobody takes is a wasted launch on the latency-bound path (the caller perturbs the observation,
-    // alternates policies, only steps the env): after kSpeculationMissLimit of them in a row the device stops speculating,
-    // and resumes when evaluate_step is again called with exactly the rows the step cached (what a hit would have been).
-    bool sp_outstanding = false;         // a speculated step was launched and not taken (yet)
-    bool sp_suspended = false;
-    uint32_t sp_misses = 0;
+    HostMailbox mailbox;
+    ObservationCache obs_cache;
+    Speculation spec;
     // Resident executor (round 6; rq_resident.cpp): while the host keeps calling rq_step on the same small env / params / policy, or
     // rq_policy_evaluate_step on the same policy, the work is not launched but posted, as a 64-byte command, to one workgroup that stays
-    // on the device - on a stream of its own - and publishes the same sequence numbers in mb_flag.  Anything else the device is asked
+    // on the device - on a stream of its own - and publishes the same sequence numbers in mailbox.flag.  Anything else the device is asked
     // to do retires it first (resident_scope_hook).
     ResidentExecutor resident;
 };
-constexpr uint32_t kSpeculationMissLimit = 4;
 struct rq_rng {
     rq_device* dev = nullptr;
     uint64_t seed = 0;
@@ -298,15 +299,25 @@ void state_release_buffer(rq_state* s);
 int state_make_private(rq_state* s, bool keep);
 inline rq::Batch batch_of(const rq_env* env) { return {env->n, env->ld, env->offset}; }
 
-// ---- rq_capi_vector.cpp: the small-batch loop ----
+// ---- rq_small_batch.cpp: the small-batch loop (rq_device::mailbox, obs_cache, spec) ----
+void small_batch_setup(rq_device* dev);      // rq_device_create: settings
 int ensure_mailbox(rq_device* dev);
-void speculation_unused(rq_device* dev);
-void obs_cache_drop(rq_device* dev);
-bool obs_cache_holds(const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state);
+void mailbox_free(rq_device* dev);
 int mailbox_wait(rq_device* dev, uint32_t seq);
-int mailbox_in_free(rq_device* dev);
-rq::Mailbox mailbox_for(rq_device* dev, const float* rows_in, uint32_t in_stride, float* rows_out);
+int mailbox_copy_out(rq_device* dev, uint32_t seq, const float* rows, float* dst, size_t floats);
+int mailbox_put_in(rq_device* dev, const float* rows, uint32_t n, uint32_t dim, size_t stride);
+rq::Mailbox mailbox_for(rq_device* dev, bool reads_in, uint32_t in_stride, MbOut out);
+int mailbox_for_step(rq_device* dev, const float* action, uint32_t n, bool cache_obs, rq::Mailbox* mb);
 void mailbox_abort(rq_device* dev, const rq::Mailbox& mb);
+void mailbox_resident_args(const rq_device* dev, rq::ResidentArgs& ra, bool policy_kind);
+bool obs_cache_holds(const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state);
+int obs_cache_read(rq_device* dev, rq_env* env, float* observation);
+void obs_cache_drop(rq_device* dev);
+void obs_cache_drop_if(rq_device* dev, const rq_env* env);     // only if the cache holds env's observation
+void obs_cache_fill(rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state, uint32_t seq, rq_policy* pol, uint32_t spec_seq);
+void obs_cache_follow_assign(rq_device* dev, const rq_state* dst, const rq_state* src);
+rq_policy* speculation_candidate(rq_device* dev, const rq_env* env, bool cache_obs, bool action);
+int speculation_take(rq_device* dev, rq_policy* pol, const float* observation, uint32_t batch, uint32_t obs_stride, float* action, bool* hit);
 hipError_t launch_step_pair(rq_device* dev, const StepPair& p);
 
 // ---- rq_resident.cpp: the resident executor ----
@@ -318,9 +329,8 @@ int resident_gone(rq_device* dev);           // the kernel has left: replay its 
 bool resident_left(const rq_device* dev);    // has the running kernel published that it left?
 int resident_admit(rq_device* dev, bool ready, const ResidentBinding& want, uint64_t now_ns, uint32_t streak, bool* use);
 int resident_start(rq_device* dev, rq::ResidentArgs& ra, const ResidentBinding& want);
-uint32_t* resident_rows(const rq_device* dev);   // command memory beside the line: the rows that travel with a command
-void resident_post(rq_device* dev, const StepPair& p, uint32_t checksum);
-void resident_post(rq_device* dev, const PolicyCmd& p, uint32_t checksum);
+void resident_post(rq_device* dev, const StepPair& p);      // the command's rows and checksum, then its line
+void resident_post(rq_device* dev, const PolicyCmd& p);
 int resident_drain(rq_device* dev);
 
 // ---- rq_capi_policy.cpp ----

@@ -1,7 +1,7 @@
 // rq_resident.cpp - the resident executor's host side (round 6): one workgroup that stays on the device, on a stream of its own, and takes
 // commands in memory instead of launches - the README loop's rq_step (rq_kernels.hip k_resident_small / k_resident_loop) or the policy
-// alone, rq_policy_evaluate_step on host rows (k_resident_policy); one kernel per device at a time.  What a kind computes, and the rows
-// it writes beside a command, stay with its caller.
+// alone, rq_policy_evaluate_step on host rows (k_resident_policy); one kernel per device at a time.  What a kind computes stays with its
+// caller; the command format - line, rows, checksum - is this file's.
 #include "rq_objects.hpp"
 
 namespace rqh {
@@ -92,8 +92,6 @@ void resident_teardown(rq_device* dev) {
     if (rx.mem) (void)hipHostFree(rx.mem);
 }
 
-uint32_t* resident_rows(const rq_device* dev) { return dev->resident.cmd + kRwRows; }
-
 bool resident_left(const rq_device* dev) { return __atomic_load_n(&dev->resident.mem[kRwExited], __ATOMIC_ACQUIRE) == dev->resident.launch_id; }
 
 // ---- lifecycle --------------------------------------------------------------------------------------------------------------------
@@ -119,7 +117,7 @@ int resident_gone(rq_device* dev) {
     }
     if (rx.pending) {
         rx.pending = false;
-        const uint32_t f = __atomic_load_n(dev->mb_flag, __ATOMIC_ACQUIRE);
+        const uint32_t f = __atomic_load_n(dev->mailbox.flag, __ATOMIC_ACQUIRE);
         if ((int32_t)(f - rx.pending_last) < 0) {
             RQ_REQUIRE((int32_t)(f - rx.pending_first) < 0, RQ_ERR_HIP, "the resident executor left in the middle of a command");
             ++rx.replays;
@@ -206,12 +204,13 @@ int resident_admit(rq_device* dev, bool ready, const ResidentBinding& want, uint
 }
 
 // Start a kernel of want's kind (none is running) on ra: the caller's objects as its kernel reads them; the pairs and the operand image
-// are the binding's, the rest is the executor's.  A failed launch is no error: no resident kernel this time, the caller launches.
+// are the binding's, the rows and flag the mailbox's, the rest the executor's.  A failed launch is no error: the caller launches.
 int resident_start(rq_device* dev, rq::ResidentArgs& ra, const ResidentBinding& want) {
     ResidentExecutor& rx = dev->resident;
     int rc = ensure_memory(dev); if (rc) return rc;
     // nothing of the stream's may still be in flight when a kernel outside it starts reading the same buffers
     RQ_HIP(hipStreamSynchronize(dev->stream));
+    mailbox_resident_args(dev, ra, want.policy_kind);
     ra.obs_buf[0] = want.obs[0]; ra.obs_buf[1] = want.obs[1]; ra.hidden[0] = want.hidden[0]; ra.hidden[1] = want.hidden[1]; ra.packed = want.packed;
     ra.packet = rx.cmd + kRwLine; ra.exited = rx.mem + kRwExited; ra.small_rows = rx.cmd + kRwRows;
     if (rx.cmd_on_device) ra.rows_action = reinterpret_cast<const float*>(rx.cmd + kRwRows);     // the rows beside the line
@@ -225,7 +224,7 @@ int resident_start(rq_device* dev, rq::ResidentArgs& ra, const ResidentBinding& 
     return RQ_OK;
 }
 
-// one command slot: the caller has drained the previous command and written this one's rows
+// one command slot: the caller has drained the previous command; this one's rows are in command memory
 static void post(ResidentExecutor& rx, uint32_t bits, const float* state_in, float* state_out, uint32_t seq_step, uint32_t seq_spec,
                  uint32_t checksum, uint32_t seq_first) {
     rx.pending = true; rx.pending_first = seq_first; rx.pending_last = seq_spec;
@@ -233,16 +232,38 @@ static void post(ResidentExecutor& rx, uint32_t bits, const float* state_in, flo
     rx.last_post_ns = host_now_ns(); ++rx.posts;
 }
 
-void resident_post(rq_device* dev, const StepPair& p, uint32_t checksum) {
-    ResidentExecutor& rx = dev->resident;
-    rx.last.step = p;
-    const uint32_t bits = (p.obs_alt == rx.bound.obs[1] ? rq::kRbObsSel : 0u) | (p.hidden_in == rx.bound.hidden[1] ? rq::kRbHiddenSel : 0u);
-    post(rx, bits, p.state_in, p.state_out, p.mb_step.seq, p.mb_spec.seq, checksum, p.mb_step.seq);
+// what the kernel verifies a command's rows (n x dim floats at `stride`; the ones its mailbox reads) against: the uint32 sum of their dwords
+static uint32_t checksum(const float* rows, uint32_t n, uint32_t dim, uint32_t stride) {
+    uint32_t sum = 0, u;
+    for (uint32_t i = 0; i < n; ++i) for (uint32_t k = 0; k < dim; ++k) { std::memcpy(&u, rows + (size_t)i * stride + k, 4); sum += u; }
+    return sum;
 }
 
-void resident_post(rq_device* dev, const PolicyCmd& p, uint32_t checksum) {
-    dev->resident.last.policy = p;
-    post(dev->resident, 0u, nullptr, nullptr, 0u, p.mb.seq, checksum, p.mb.seq);
+// the loop's actions, n x 4 dwords, beside the line where the small kernel reads them in the same load; in device memory all kernels do
+void resident_post(rq_device* dev, const StepPair& p) {
+    ResidentExecutor& rx = dev->resident;
+    const float* a = p.mb_step.rows_in;
+    if (p.b.n <= rq::kResidentSmallEnvs || rx.cmd_on_device) {
+        __m128i* rows = reinterpret_cast<__m128i*>(rx.cmd + kRwRows);
+        for (uint32_t k = 0; k < p.b.n; ++k) _mm_store_si128(rows + k, _mm_loadu_si128(reinterpret_cast<const __m128i*>(a) + k));
+    }
+    rx.last.step = p;
+    const uint32_t bits = (p.obs_alt == rx.bound.obs[1] ? rq::kRbObsSel : 0u) | (p.hidden_in == rx.bound.hidden[1] ? rq::kRbHiddenSel : 0u);
+    post(rx, bits, p.state_in, p.state_out, p.mb_step.seq, p.mb_spec.seq, checksum(a, p.b.n, RQ_ACTION_DIM, RQ_ACTION_DIM), p.mb_step.seq);
+}
+
+// the policy's observation rows, each padded to kResidentPolicyRow floats: whole 16-byte stores
+void resident_post(rq_device* dev, const PolicyCmd& p) {
+    ResidentExecutor& rx = dev->resident;
+    __m128i* rows = reinterpret_cast<__m128i*>(rx.cmd + kRwRows);
+    for (uint32_t i = 0; i < p.batch; ++i) {
+        alignas(16) float row[rq::kResidentPolicyRow] = {};
+        std::memcpy(row, p.mb.rows_in + (size_t)i * p.mb.in_stride, RQ_POLICY_INPUT_DIM * sizeof(float));
+        for (uint32_t k = 0; k < rq::kResidentPolicyRow / 4; ++k)
+            _mm_store_si128(rows + (size_t)i * (rq::kResidentPolicyRow / 4) + k, _mm_load_si128(reinterpret_cast<const __m128i*>(row) + k));
+    }
+    rx.last.policy = p;
+    post(rx, 0u, nullptr, nullptr, 0u, p.mb.seq, checksum(p.mb.rows_in, p.batch, RQ_POLICY_INPUT_DIM, p.mb.in_stride), p.mb.seq);
 }
 
 }  // namespace rqh
