@@ -41,7 +41,9 @@ RQ_API int rq_teacher_bank_create(rq_device* dev, const float* weights, uint32_t
     for (uint32_t t = 0; t < n_teachers; ++t) {
         rq::pack_teacher_f32(weights + per * t, (int)in_dim, (int)h1, (int)h2, b->act, b->out_act, img32.data() + f32_floats * t);
         rq::pack_teacher_bf16(weights + per * t, (int)in_dim, (int)h1, (int)h2, b->act, b->out_act, img16.data() + bf16_floats * t);
-        rq::pack_teacher_f16x2(weights + per * t, (int)in_dim, (int)h1, (int)h2, b->act, b->out_act, img_split.data() + split_floats * t);
+        if (!rq::pack_teacher_f16x2(weights + per * t, (int)in_dim, (int)h1, (int)h2, b->act, b->out_act, img_split.data() + split_floats * t) &&
+            b->f16x2_misfit == UINT32_MAX)
+            b->f16x2_misfit = t;
     }
     hipError_t e1 = hipMalloc(&b->images_f32, img32.size() * sizeof(float));
     hipError_t e2 = hipMalloc(&b->images_bf16, img16.size() * sizeof(float));
@@ -125,6 +127,12 @@ RQ_API int rq_teacher_bank_set_precision(rq_teacher_bank* bank, int precision) {
                RQ_ERR_INVALID_ARGUMENT, "unknown precision");
     RQ_REQUIRE(!bank->layers || precision == RQ_POLICY_FP32, RQ_ERR_INVALID_ARGUMENT,
                "a bank outside the two-hidden-layer {16, 32, 64} family is evaluated in fp32 only");
+    if (precision == RQ_POLICY_F16X2_MFMA && bank->f16x2_misfit != UINT32_MAX) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "teacher %u has a weight outside the f16 range (|w| >= 65520 after the tanh pre-scale of "
+                      "-2 log2 e): the f16x2 image cannot hold it, use fp32 or bf16", bank->f16x2_misfit);
+        return fail(RQ_ERR_INVALID_ARGUMENT, msg);
+    }
     bank->precision = precision;
     return RQ_OK;
 }

@@ -276,7 +276,8 @@ constexpr int teacher_image_regs_f16x2(int h1, int h2) {
 // one teacher's parameters, [W1 (h1 x in) | b1 | W2 (h2 x h1) | b2 | W3 (4 x h2) | b3], rows = outputs -> its image
 void pack_teacher_f32(const float* w, int in_dim, int h1, int h2, int act, int out_act, float* image);
 void pack_teacher_bf16(const float* w, int in_dim, int h1, int h2, int act, int out_act, float* image);
-void pack_teacher_f16x2(const float* w, int in_dim, int h1, int h2, int act, int out_act, float* image);
+// pack_teacher_f16x2 -> false when a pre-scaled weight lies outside the f16 range (|w| >= 65 520: its pieces would be +-inf)
+bool pack_teacher_f16x2(const float* w, int in_dim, int h1, int h2, int act, int out_act, float* image);
 // the generic dense stack (rq_teacher.hip k_teacher_relabel_layers): hidden layers padded to hp = 64 or 128 units, the fp32 image resident in LDS
 // (layer 1 [6][hp/16][64] | per further hidden layer [hp/4][hp/16][64] + [hp] biases | output [hp/16][64][4] + [4] biases)
 constexpr size_t teacher_layers_image_floats(int hp, int n_hidden) {

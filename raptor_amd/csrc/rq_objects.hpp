@@ -268,6 +268,7 @@ struct rq_teacher_bank {
     float* images_f32 = nullptr;     // [n_teachers][teacher_image_regs_f32 * 64]
     float* images_bf16 = nullptr;    // [n_teachers][teacher_image_regs_bf16 * 64]
     float* images_f16x2 = nullptr;   // [n_teachers][teacher_image_regs_f16x2 * 64]
+    uint32_t f16x2_misfit = UINT32_MAX;  // the first teacher with a weight the f16x2 image cannot hold (set_precision refuses it)
     uint32_t* tiles = nullptr;       // device: tile_teacher [tiles] followed by tile_env [tiles][16]; dense stacks: teacher_start | sorted_env
     size_t tile_words = 0;           // its capacity in 32-bit words
     // the generic dense stack (rq_teacher_bank_create_layers outside the register-stationary family): fp32, operands streamed

@@ -214,12 +214,15 @@ void pack_teacher_f32(const float* w, int in_dim, int h1, int h2, int act, int o
     }
 }
 
-// the 16-bit teacher images: bf16 (one operand per contraction chunk) or split f16 (hi operand, then lo operand)
-static void pack_teacher_16(const float* w, int in_dim, int h1, int h2, int act, int out_act, bool split, float* image) {
+// the 16-bit teacher images: bf16 (one operand per contraction chunk) or split f16 (hi operand, then lo operand).
+// -> false when a split operand does not fit f16: a pre-scaled weight of magnitude >= 65 520 becomes hi = inf,
+// lo = -inf, and every label it touches NaN
+static bool pack_teacher_16(const float* w, int in_dim, int h1, int h2, int act, int out_act, bool split, float* image) {
     const TeacherView t = view(w, in_dim, h1, h2, act, out_act);
     const int regs = split ? teacher_image_regs_f16x2(h1, h2) : teacher_image_regs_bf16(h1, h2);
     uint32_t* pu = reinterpret_cast<uint32_t*>(image);
     for (int i = 0; i < regs * 64; ++i) pu[i] = 0u;
+    bool fits = true;
     for (int l = 0; l < 64; ++l) {
         const int q = l >> 4, i = l & 15;
         int v = 0;
@@ -231,6 +234,7 @@ static void pack_teacher_16(const float* w, int in_dim, int h1, int h2, int act,
             for (int e = 0; e < 8; ++e) {
                 if (!split) { put16(v, e, to_bf16_rne(x[e])); continue; }
                 const uint16_t hi = to_f16_rne(x[e]);
+                fits = fits && ((hi & 0x7c00u) != 0x7c00u || !std::isfinite(x[e]));
                 put16(v, e, hi);
                 put16(v + 4, e, to_f16_rne(x[e] - from_f16(hi)));
             }
@@ -258,6 +262,7 @@ static void pack_teacher_16(const float* w, int in_dim, int h1, int h2, int act,
             for (int r = 0; r < 4; ++r) putf(t.k2 * t.b2[16 * m + 4 * q + r]);
         for (int r = 0; r < 4; ++r) putf(q == 0 ? t.k3 * t.b3[r] : 0.0f);
     }
+    return fits;
 }
 
 // the generic dense stack's streamed image (layout: rq_teacher.hip k_teacher_relabel_layers)
@@ -315,10 +320,10 @@ void pack_teacher_layers(const float* w, int in_dim, int n_hidden, const uint32_
 }
 
 void pack_teacher_bf16(const float* w, int in_dim, int h1, int h2, int act, int out_act, float* image) {
-    pack_teacher_16(w, in_dim, h1, h2, act, out_act, false, image);
+    (void)pack_teacher_16(w, in_dim, h1, h2, act, out_act, false, image);
 }
-void pack_teacher_f16x2(const float* w, int in_dim, int h1, int h2, int act, int out_act, float* image) {
-    pack_teacher_16(w, in_dim, h1, h2, act, out_act, true, image);
+bool pack_teacher_f16x2(const float* w, int in_dim, int h1, int h2, int act, int out_act, float* image) {
+    return pack_teacher_16(w, in_dim, h1, h2, act, out_act, true, image);
 }
 
 }  // namespace rq

@@ -276,6 +276,23 @@ __device__ __forceinline__ void split2(float v0, float v1, uint32_t& hi, uint32_
     const f32x2 r = {r0, r1};
     lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, f16x2));
 }
+// The same for values that are not bounded by construction (observations, ReLU activations): f16 overflows to infinity
+// at 65 520 and the residual v - inf makes hi.w + lo.w NaN where the fp32 and bf16 kernels stay finite.  Clamped to the
+// largest f16 first (one v_med3_f32 each; a NaN input becomes -65 504), as ActorF16X2::split2_sat does for the student.
+// So a NaN observation gives finite f16x2 labels where the fp32 kernel gives NaN: look for a diverged env in the
+// observations, not in the f16x2 labels.
+__device__ __forceinline__ void split2_sat(float v0, float v1, uint32_t& hi, uint32_t& lo) {
+    split2(__builtin_amdgcn_fmed3f(v0, -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(v1, -65504.0f, 65504.0f), hi, lo);
+}
+// a hidden layer's activations from its accumulators, as pieces: ReLU and the saturation in one v_med3_f32 each (max(v, 0)
+// clamped to the largest f16: the instruction count of the plain ReLU); tanh is bounded by 1 and needs no clamp
+template <int ACT>
+__device__ __forceinline__ void act_split2(float v0, float v1, uint32_t& hi, uint32_t& lo) {
+    if (ACT == RQ_ACT_RELU)
+        split2(__builtin_amdgcn_fmed3f(v0, 0.0f, 65504.0f), __builtin_amdgcn_fmed3f(v1, 0.0f, 65504.0f), hi, lo);
+    else
+        split2(teacher_act<ACT>(v0), teacher_act<ACT>(v1), hi, lo);
+}
 __device__ __forceinline__ f16x8 tuple16(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3) {
     const dwordx4 u = {d0, d1, d2, d3};
     return __builtin_bit_cast(f16x8, u);
@@ -336,7 +353,7 @@ __global__ __launch_bounds__(64, 2) void k_teacher_relabel_f16x2(uint32_t ld, ui
         in.finish(X);
         uint32_t xh[3], xl[3];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) split2(X[2 * d], X[2 * d + 1], xh[d], xl[d]);
+        for (int d = 0; d < 3; ++d) split2_sat(X[2 * d], X[2 * d + 1], xh[d], xl[d]);
         const f16x8 bh = tuple16(xh[0], xh[1], xh[2], 0u), bl = tuple16(xl[0], xl[1], xl[2], 0u);
         f32x4 H1a[M1];
 #pragma unroll
@@ -351,8 +368,8 @@ __global__ __launch_bounds__(64, 2) void k_teacher_relabel_f16x2(uint32_t ld, ui
 #pragma unroll
         for (int m = 0; m < M1; ++m) {
             const f32x4 y = H1a[m];
-            split2(teacher_act<ACT>(y[0]), teacher_act<ACT>(y[1]), y1h[m][0], y1l[m][0]);
-            split2(teacher_act<ACT>(y[2]), teacher_act<ACT>(y[3]), y1h[m][1], y1l[m][1]);
+            act_split2<ACT>(y[0], y[1], y1h[m][0], y1l[m][0]);
+            act_split2<ACT>(y[2], y[3], y1h[m][1], y1l[m][1]);
         }
         y1h[M1][0] = y1h[M1][1] = y1l[M1][0] = y1l[M1][1] = 0u;          // the zero tile that pads an odd chunk
         f32x4 H2a[M2];
@@ -375,8 +392,8 @@ __global__ __launch_bounds__(64, 2) void k_teacher_relabel_f16x2(uint32_t ld, ui
 #pragma unroll
         for (int m = 0; m < M2; ++m) {
             const f32x4 y = H2a[m];
-            split2(teacher_act<ACT>(y[0]), teacher_act<ACT>(y[1]), y2h[m][0], y2l[m][0]);
-            split2(teacher_act<ACT>(y[2]), teacher_act<ACT>(y[3]), y2h[m][1], y2l[m][1]);
+            act_split2<ACT>(y[0], y[1], y2h[m][0], y2l[m][0]);
+            act_split2<ACT>(y[2], y[3], y2h[m][1], y2l[m][1]);
         }
         y2h[M2][0] = y2h[M2][1] = y2l[M2][0] = y2l[M2][1] = 0u;
         f32x4 Ho = B3;

@@ -120,8 +120,8 @@ class TeacherBank:
     def set_precision(self, precision):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
-        self.precision = precision
         _lib.call("rq_teacher_bank_set_precision", self._h, PRECISIONS[precision])
+        self.precision = precision
 
 
 def balanced_teacher_assignment(n_envs, n_teachers):
