@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""The distillation loop of post-training (README.md:208-216) on the device: collect with the student (auto-reset, recorded),
+label the recorded observations with a bank of MLP teachers, take K Adam steps on the MSE between the student's actions over the
+recording and the labels (masked by done != 4), push the new weights into the student, collect again.
+
+Forward and backward over the recording are HIP launches of the engine (raptor_amd.training.trajectory_actions); the optimiser is
+torch's; only the 8 KB weight vector crosses to the host per update.
+
+    python examples/distill.py [--envs 16384] [--steps 100] [--epochs 3] [--adam-steps 10] [--lr 1e-3]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import raptor_amd.l2f as l2f                       # noqa: E402
+from raptor_amd.foundation_policy import Raptor    # noqa: E402
+from raptor_amd.teachers import TeacherBank, balanced_teacher_assignment, parameter_count    # noqa: E402
+from raptor_amd.training import masked_mse, trajectory_actions  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=16384)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--adam-steps", type=int, default=10)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--teachers", type=int, default=64)
+    args = ap.parse_args()
+
+    device = l2f.Device()
+    vector = l2f.vector(args.envs)
+    rng, env = vector.VectorRng(), vector.VectorEnvironment()
+    params, state = vector.VectorParameters(), vector.VectorState()
+    vector.initialize_rng(device, rng, 0)
+    vector.initialize_environment(device, env)
+    vector.sample_initial_parameters(device, env, params, rng)
+    vector.sample_initial_state(device, env, params, state, rng)
+    n, T = env.N_ENVIRONMENTS, args.steps
+
+    student = Raptor(device)
+    # stand-in teachers (the trained ones are not in the reference tree): 22-64-64-4 MLPs, one per group of quadrotors
+    bank = TeacherBank(device, (np.random.default_rng(1).standard_normal((args.teachers, parameter_count(22, 64, 64))) * 0.1)
+                       .astype(np.float32), 22, 64, 64, "relu", "tanh")
+    ids = balanced_teacher_assignment(n, args.teachers)
+    weights = torch.tensor(student.weights, device="cuda", requires_grad=True)
+    opt = torch.optim.Adam([weights], lr=args.lr)
+    traj = vector.Trajectory(env, T)
+
+    for epoch in range(args.epochs):
+        traj.reset()
+        student.reset()
+        vector.rollout(device, env, params, state, student, rng, T, "fused", autoreset=True, trajectory=traj)
+        traj.relabel_teachers(bank, ids, overwrite=True, fetch=False)          # stored actions <- the teachers' labels
+        rec = traj.tensors()
+        labels = rec["act"][:, :, :n].clone()
+        live = (rec["done"][:, :n] != 4)[:, None, :].expand(T, 4, n)           # frozen steps carry no label
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(args.adam_steps):
+            opt.zero_grad()
+            act = trajectory_actions(traj, student, weights)[:, :, :n]
+            loss = masked_mse(act, labels, live)        # masks the inputs: frozen steps may hold NaN
+            loss.backward()
+            opt.step()
+            print(f"epoch {epoch} step {k}: masked MSE {loss.item():.5f}", flush=True)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        student.set_weights(weights)                    # the next collection runs the updated student
+        print(f"epoch {epoch}: {args.adam_steps} gradient passes over {n} envs x {T} steps in {dt * 1e3:.1f} ms "
+              f"({args.adam_steps / dt:.1f} passes/s, {args.adam_steps * n * T / dt:.3g} env-steps/s)", flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -25,7 +25,7 @@
  *                  observation, rng)                    :96      rq_observe
  *   vector.step(device, env, params, state, action,
  *               next_state, rng) -> dts                 :98      rq_step
- *   foundation_policy.Raptor()                          :20,48   rq_policy_create (+ rq_policy_load_weights)
+ *   foundation_policy.Raptor()                          :20,48   rq_policy_create (+ rq_policy_set_weights)
  *   Raptor.reset()                                      :21,94   rq_policy_reset
  *   Raptor.evaluate_step(obs[B,22]) -> act[B,4]         :24,97   rq_policy_evaluate_step
  *   the loop body README.md:95-99 x K                            rq_rollout  (fused or hipGraph-chained)
@@ -35,6 +35,7 @@
  *   post-training data collection                       :208     rq_rollout_record + rq_trajectory_*
  *   distillation: ~1000 MLP teachers queried on
  *     student-visited states                            :208-216 rq_teacher_bank_create / rq_trajectory_relabel_teachers
+ *   distillation: the student's regression gradient    :208-216 rq_trajectory_policy_forward / _backward + rq_policy_set_weights
  *   (the reference is single-process) env shards over
  *     GPUs + all-gather of episode returns (RCCL)                rq_env_create(global_env_offset) / rq_comm_* / rq_allgather_returns
  *
@@ -333,6 +334,10 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
                             uint32_t batch, uint32_t obs_stride, float* action);
 RQ_API int rq_policy_get_hidden(const rq_policy* pol, float* host_out, uint32_t batch); /* [batch,16] */
 RQ_API int rq_policy_set_hidden(rq_policy* pol, const float* host_in, uint32_t batch);
+/* New parameters for an existing policy (a learner's update): `weights` as at rq_policy_create, repacked in place.  Precision, the
+ * Standardize and SampleAndSquash stages and the current hidden state are kept; a resident executor is retired first.  Afterwards
+ * every path computes what a policy freshly created with these weights computes, bit for bit. */
+RQ_API int rq_policy_set_weights(rq_policy* pol, const float* weights, size_t n_weights);
 /* Raptor over a SEQUENCE tensor, the layout rl-tools evaluates and the checkpoint's known-answer example
  * uses (checkpoint.h:197-215, [seq, batch, feature]): observation [steps, batch, obs_stride] (first 22
  * columns) -> action [steps, batch, 4].  Equivalent to `steps` calls of rq_policy_evaluate_step - the hidden
@@ -392,6 +397,29 @@ RQ_API int rq_trajectory_device_ptrs(const rq_trajectory* t, float** obs, float*
 RQ_API int rq_rollout_record(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state,
                       rq_policy* policy, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                       rq_trajectory* trajectory);
+
+/* ---- Learner: the student's gradient over a recorded trajectory (README.md:208-216, the distillation step's regression) ----
+ * Forward: the policy on the recorded observations obs [T][22][ld] under rq_trajectory_relabel's episode rules (GRU state back to
+ * the learned initial state after done codes 1 and 2, held on code 4) -> action [T][4][ld_action] (ld_action >= n_envs; only the
+ * columns of the n_envs envs are written, in every memory mode).  With
+ * RQ_GRAD_START_CURRENT the first state is the policy's current one, a constant, and the actions equal rq_trajectory_relabel's bit
+ * for bit; with RQ_GRAD_START_INITIAL it is the learned initial state (weights [2000:2016]) and its gradient counts.  The policy's
+ * hidden state is not changed.  What the backward needs (the state entering each step, 64 B per env and step) stays in the
+ * trajectory, tagged with the policy and its weights.
+ * Backward: dL/da [T][4][ld_grad] -> grad_weights [2084] in the flat order (the initial state's slice included) and, optionally
+ * and for RQ_GRAD_START_CURRENT only, grad_hidden_start [16][ld].  The exact gradient of the forward: ReLU'(0) = 0, actions of
+ * frozen (code 4) steps depend on the parameters too, columns n_envs .. ld-1 contribute nothing whatever they hold.  Deterministic:
+ * no float atomics, the same bits every run.  Refused (rq_last_error says which): no matching forward, weights changed since it
+ * (rq_policy_set_weights, rq_policy_set_standardize), a bf16 / f16x2 policy, a Standardize or SampleAndSquash stage, objects of
+ * two devices, an empty trajectory.  Gradients of those stages and of the observations are not computed.
+ * memory: RQ_DST_HOST = host arrays (copied, synchronous), RQ_DST_DEVICE = device pointers (synchronised before return),
+ * RQ_DST_DEVICE_ASYNC = device pointers, only enqueued on rq_device_stream(). */
+enum rq_grad_start { RQ_GRAD_START_CURRENT = 0, RQ_GRAD_START_INITIAL = 1 };
+RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* policy, int start,
+                                        float* action, uint32_t ld_action, int memory);
+RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* policy, const float* grad_action,
+                                         uint32_t ld_grad, float* grad_weights, float* grad_hidden_start,
+                                         int memory);
 
 /* ---- Teacher bank: the distillation step of the reference (README.md:208-216: ~1000 teacher policies, one per
  * sampled quadrotor, queried on the states the student visited).  The teachers'

@@ -157,6 +157,7 @@ _SIGNATURES = {
     "rq_policy_evaluate_step": [_vp, _vp, _fp, C.c_uint32, C.c_uint32, _fp],
     "rq_policy_get_hidden": [_vp, _fp, C.c_uint32],
     "rq_policy_set_hidden": [_vp, _fp, C.c_uint32],
+    "rq_policy_set_weights": [_vp, _fp, C.c_size_t],
     "rq_policy_selftest": [_vp, _fp, _fp, C.c_uint32, C.c_uint32, C.c_float, _fp],
     "rq_policy_evaluate_sequence": [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_int],
     "rq_rollout": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32],
@@ -168,6 +169,8 @@ _SIGNATURES = {
     "rq_trajectory_device_ptrs": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _u32p],
     "rq_rollout_record": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp],
     "rq_trajectory_relabel": [_vp, _vp, _fp, C.c_int],
+    "rq_trajectory_policy_forward": [_vp, _vp, C.c_int, _fp, C.c_uint32, C.c_int],
+    "rq_trajectory_policy_backward": [_vp, _vp, _fp, C.c_uint32, _fp, _fp, C.c_int],
     "rq_comm_unique_id": [_vp, C.c_size_t],
     "rq_comm_create": [_vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.POINTER(_vp)],
     "rq_comm_destroy": [_vp],

@@ -64,6 +64,7 @@ extern "C" {
 // (re)build the effective parameters and both MFMA operand images, and upload them
 static int policy_upload(rq_policy* p) {
     p->version = fresh_version();
+    p->weight_version = fresh_version();
     std::memcpy(p->w_eff, p->w_host, sizeof(p->w_eff));
     if (p->standardize) {
         // Standardize (x - mean) / std followed by Dense folds into the Dense:
@@ -135,8 +136,22 @@ RQ_API int rq_policy_destroy(rq_policy* pol) {
     if (pol->w_packed_bf16) (void)hipFree(pol->w_packed_bf16);
     if (pol->w_packed_f16x2) (void)hipFree(pol->w_packed_f16x2);
     if (pol->ls_image) (void)hipFree(pol->ls_image);
+    if (pol->w_packed_grad) (void)hipFree(pol->w_packed_grad);
     delete pol;
     return RQ_OK;
+}
+
+// New parameters for an existing policy: precision, the Standardize and SampleAndSquash stages and the hidden state stay; every
+// path then computes what a policy created with these weights computes.  A resident executor bound to the device is retired first
+// (it holds the old operands in registers), as rq_policy_destroy does.
+RQ_API int rq_policy_set_weights(rq_policy* pol, const float* weights, size_t n_weights) {
+    RQ_REQUIRE(pol && weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(n_weights == RQ_POLICY_NUM_WEIGHTS, RQ_ERR_INVALID_ARGUMENT,
+               "expected 2084 weights: W0[16,22] b0[16] Wi[48,16] Wh[48,16] bi[48] bh[48] h0[16] W2[4,16] b2[4]");
+    DeviceScope on_device(pol->dev); int rc = on_device.rc; if (rc) return rc;
+    if (device_registry(pol->dev, 0)) { rc = resident_retire(pol->dev); if (rc) return rc; }
+    std::memcpy(pol->w_host, weights, sizeof(pol->w_host));
+    return policy_upload(pol);
 }
 
 RQ_API int rq_policy_pack_image(const float* weights, size_t n_weights, int precision, float* image, size_t capacity,

@@ -208,6 +208,9 @@ RQ_API int rq_trajectory_destroy(rq_trajectory* t) {
     if (t->act) (void)hipFree(t->act);
     if (t->rew) (void)hipFree(t->rew);
     if (t->done) (void)hipFree(t->done);
+    if (t->grad.saved) (void)hipFree(t->grad.saved);
+    if (t->grad.partial) (void)hipFree(t->grad.partial);
+    if (t->grad.rows) (void)hipFree(t->grad.rows);
     delete t;
     return RQ_OK;
 }
@@ -215,6 +218,7 @@ RQ_API int rq_trajectory_destroy(rq_trajectory* t) {
 RQ_API int rq_trajectory_reset(rq_trajectory* t) {
     RQ_REQUIRE(t, RQ_ERR_INVALID_ARGUMENT, "null argument");
     t->length = 0;
+    t->grad.valid = false;
     return RQ_OK;
 }
 

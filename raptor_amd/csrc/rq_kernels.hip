@@ -1164,3 +1164,6 @@ hipError_t launch_fill_f32(hipStream_t s, float* p, float v, uint32_t count) {
 }
 
 }  // namespace rq
+
+// the learner's kernels (forward with saved state, reverse pass, reduction): their own file, compiled in this unit
+#include "rq_grad.hpp"

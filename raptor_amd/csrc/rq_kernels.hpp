@@ -186,6 +186,18 @@ hipError_t launch_actor_sequence(hipStream_t s, uint32_t n, uint32_t steps, cons
 hipError_t launch_actor_relabel(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
                                 const float* obs, const uint8_t* done, float* hidden, uint32_t ld_h, float* act,
                                 int precision);
+// The learner (rq_grad.hpp).  Forward: launch_actor_relabel's pass over obs [steps][22][ld] / done [steps][ld] with the state
+// entering each step saved to `saved` [steps][16][ld]; it starts from hidden [16][ld_h] (start_initial = 0) or the learned initial
+// state, writes act [steps][4][ld_act] and leaves `hidden` alone.  Backward: dL/da [steps][4][ld_g] -> per-wave partial gradients
+// partial [ceil(n / 64)][2084] (flat weight order) and dL/dh_start [16][ld] (grad_h_start, may be null; start_initial = 0 only),
+// then a fixed-order sum of the partials into grad [2084].  `gpacked`: the transposed image (pack_policy_grad).
+hipError_t launch_policy_grad_forward(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
+                                      const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h,
+                                      int start_initial, float* act, uint32_t ld_act, float* saved);
+hipError_t launch_policy_grad_backward(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
+                                       const float* gpacked, const float* obs, const uint8_t* done, const float* saved,
+                                       const float* grad_act, uint32_t ld_g, int start_initial, float* grad_h_start,
+                                       float* partial, float* grad);
 // vector.step (README.md:98) + reward/termination/statistics.  rollout != 0 adds the
 // episode-end handling of rq_rollout (freeze or auto-reset incl. hidden-state reset).
 // With mb.rows_in the actions come from the mailbox and are also written to `action` (field-major).
@@ -258,6 +270,17 @@ void pack_policy(const float* weights, float* packed);
 void pack_policy_bf16(const float* weights, float* packed);
 // and for the split-f16 actor: 72 dword images of f16 pairs + 24 fp32 images
 void pack_policy_f16x2(const float* weights, float* packed);
+// The learner's transposed operands (rq_grad.hpp k_policy_grad_backward): unscaled weights, one 64-lane image per A operand.
+// K-step (g, r) of a transposed gate product carries gate row 16 g + 4 q + r in k-slot q - the row the Q-layout delta holds
+// in register r - so lane (q, j) = W[16 g + 4 q + r][j]; W2T: lane (q, j) = W2[q][j] (the 4 actions on K).
+enum {
+    GW_WIT = 0,   // 12: [g][r]: lane (q,j) = Wi[16g+4q+r][j]
+    GW_WHT = 12,  // 12: [g][r]: lane (q,j) = Wh[16g+4q+r][j]
+    GW_W2T = 24,  //  1: lane (q,j) = W2[q][j]
+    GW_REGS = 25
+};
+enum { RQ_PACKED_GRAD_FLOATS = GW_REGS * 64 };
+void pack_policy_grad(const float* weights, float* packed);
 // log-std rows of a SampleAndSquash head: w_ls [4][16] row-major (nullptr = zeros), b_ls [4] -> 20 x 64 floats
 enum { RQ_LOGSTD_FLOATS = 20 * 64 };
 void pack_logstd_head(const float* w_ls, const float* b_ls, float* image);

@@ -232,6 +232,20 @@ struct rq_trajectory {
     float* act = nullptr;    // [capacity][4][ld]
     float* rew = nullptr;    // [capacity][ld]
     uint8_t* done = nullptr; // [capacity][ld]
+    // the learner's workspace (rq_capi_grad.cpp): what the last rq_trajectory_policy_forward saved for the backward, and by whom
+    struct Grad {
+        float* saved = nullptr;        // [length][16][ld]: the state entering each step
+        size_t saved_bytes = 0;
+        float* partial = nullptr;      // [waves][2084]: per-wave partial gradients
+        size_t partial_bytes = 0;
+        float* rows = nullptr;         // host-memory calls: the device side of the caller's arrays
+        size_t rows_bytes = 0;
+        bool valid = false;            // a forward ran and nothing it read has changed since (rq_trajectory_reset clears it)
+        const rq_policy* policy = nullptr;
+        uint64_t weight_version = 0;   // rq_policy::weight_version at the forward
+        uint32_t length = 0;
+        int start = 0;                 // enum rq_grad_start
+    } grad;
 };
 
 struct rq_policy {
@@ -255,6 +269,9 @@ struct rq_policy {
     float* hidden = nullptr;      // [16][ld]
     float* hidden_alt = nullptr;  // [16][ld]: where a speculative step leaves the next hidden state (swapped in on a hit)
     uint64_t version = fresh_version();   // renewed by every call that reads-and-writes or reconfigures the policy's state
+    uint64_t weight_version = fresh_version();   // renewed whenever the parameters are (re)uploaded: create, set_standardize, set_weights
+    float* w_packed_grad = nullptr;   // the learner's transposed image, rq::RQ_PACKED_GRAD_FLOATS floats (allocated on first use)
+    uint64_t grad_image_version = 0;  // the weight_version w_packed_grad was packed from
     float* obs = nullptr;         // [22][ld] staging for host observations
     float* act = nullptr;         // [4][ld]
 };

@@ -43,6 +43,21 @@ void pack_policy(const float* w, float* packed) {
 }
 
 
+// The learner's transposed operands (enum GW_*, rq_grad.hpp): the weights as they are, without the gate pre-scaling
+void pack_policy_grad(const float* w, float* packed) {
+    enum { WI = 368, WH = 1136, W2 = 2016 };
+    for (int l = 0; l < 64; ++l) {
+        const int q = l >> 4, j = l & 15;
+        for (int g = 0; g < 3; ++g)
+            for (int r = 0; r < 4; ++r) {
+                packed[(GW_WIT + 4 * g + r) * 64 + l] = w[WI + (16 * g + 4 * q + r) * 16 + j];
+                packed[(GW_WHT + 4 * g + r) * 64 + l] = w[WH + (16 * g + 4 * q + r) * 16 + j];
+            }
+        packed[GW_W2T * 64 + l] = w[W2 + q * 16 + j];
+    }
+}
+
+
 static uint16_t to_bf16_rne(float f) {
     uint32_t u;
     std::memcpy(&u, &f, 4);

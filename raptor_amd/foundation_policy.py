@@ -120,6 +120,20 @@ class Raptor:
         if self._h is not None:
             _lib.call("rq_policy_set_precision", self._h, PRECISIONS[precision])
 
+    def set_weights(self, weights):
+        """New parameters, 2 084 float32 in the checkpoint order (a NumPy array or any torch tensor, on the host or a device): the
+        policy is repacked in place and afterwards computes what ``Raptor(weights=...)`` would.  Precision, the optional stages and
+        the hidden state are kept."""
+        if hasattr(weights, "detach"):                    # torch
+            import torch
+            weights = weights.detach().to("cpu", dtype=torch.float32).contiguous().numpy()
+        w = np.array(weights, dtype=np.float32, copy=True).reshape(-1)
+        if w.size != POLICY_NUM_WEIGHTS:
+            raise ValueError(f"expected {POLICY_NUM_WEIGHTS} weights")
+        self._weights = w
+        if self._h is not None:
+            _lib.call("rq_policy_set_weights", self._h, _lib.fptr(w), w.size)
+
     def set_standardize(self, mean=None, std=None):
         """Optional Standardize input stage (x - mean) / std (not part of the shipped checkpoint;
         folded into layer_0 on the host).  ``None`` disables."""
