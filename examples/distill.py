@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--adam-steps", type=int, default=10)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--teachers", type=int, default=64)
+    ap.add_argument("--teacher-epochs", type=int, default=0,
+                    help="the first K epochs collect with the teachers flying the envs (behaviour cloning), then the student acts")
     args = ap.parse_args()
 
     device = l2f.Device()
@@ -55,8 +57,11 @@ def main():
     for epoch in range(args.epochs):
         traj.reset()
         student.reset()
-        vector.rollout(device, env, params, state, student, rng, T, "fused", autoreset=True, trajectory=traj)
-        traj.relabel_teachers(bank, ids, overwrite=True, fetch=False)          # stored actions <- the teachers' labels
+        if epoch < args.teacher_epochs:     # the teachers act: the recorded actions ARE their labels
+            vector.rollout(device, env, params, state, bank, rng, T, "fused", autoreset=True, trajectory=traj, teacher_ids=ids)
+        else:
+            vector.rollout(device, env, params, state, student, rng, T, "fused", autoreset=True, trajectory=traj)
+            traj.relabel_teachers(bank, ids, overwrite=True, fetch=False)      # stored actions <- the teachers' labels
         rec = traj.tensors()
         labels = rec["act"][:, :, :n].clone()
         live = (rec["done"][:, :n] != 4)[:, None, :].expand(T, 4, n)           # frozen steps carry no label

@@ -35,6 +35,8 @@
  *   post-training data collection                       :208     rq_rollout_record + rq_trajectory_*
  *   distillation: ~1000 MLP teachers queried on
  *     student-visited states                            :208-216 rq_teacher_bank_create / rq_trajectory_relabel_teachers
+ *   distillation: the teachers flying their own
+ *     quadrotors (checks, teacher-acting collection)    :207-216 rq_rollout_teachers / rq_teacher_bank_evaluate
  *   distillation: the student's regression gradient    :208-216 rq_trajectory_policy_forward / _backward + rq_policy_set_weights
  *   (the reference is single-process) env shards over
  *     GPUs + all-gather of episode returns (RCCL)                rq_env_create(global_env_offset) / rq_comm_* / rq_allgather_returns
@@ -454,6 +456,26 @@ RQ_API int rq_teacher_bank_set_precision(rq_teacher_bank* bank, int precision); 
  * whatever observation is stored there. */
 RQ_API int rq_trajectory_relabel_teachers(rq_trajectory* t, rq_teacher_bank* bank, const uint32_t* teacher_id,
                                    float* action_out, int overwrite);
+/* Teacher teacher_id[i] on row i of a batch: the bank's counterpart of rq_policy_evaluate_step (a teacher has no state).
+ * observation: host [batch, obs_stride] (obs_stride >= the teachers' in_dim; the first in_dim columns are read), or NULL: the env's
+ * device observation buffer; action: host [batch, 4], or NULL: the env's device action buffer (rq_step / rq_rollout read it).  env
+ * may be NULL when both are host arrays; otherwise batch must be the env's N_ENVIRONMENTS.  Every bank kind and precision.
+ * The tile list built from teacher_id is cached in the bank: calls with the same ids upload nothing. */
+RQ_API int rq_teacher_bank_evaluate(rq_teacher_bank* bank, rq_env* env, const uint32_t* teacher_id, const float* observation,
+                                    uint32_t batch, uint32_t obs_stride, float* action);
+/* The loop body README.md:95-99 x n_steps with env i flown by teacher teacher_id[i] of the bank: rq_rollout's semantics point for
+ * point (observation noise by (rng epoch + step, env id), the epoch advanced by n_steps; statistics and finished-episode records;
+ * RQ_ROLLOUT_AUTORESET re-samples in place, without it an ended env freezes and a later auto-reset rollout thaws it; done codes
+ * 0 / 1 / 2 / 4).  trajectory: NULL, or a buffer of this env the rollout appends to - obs = the 22 policy-visible features, act =
+ * the teacher's output after its output activation (before the env's clipping).
+ * mode RQ_ROLLOUT_FUSED: one launch (rq_teacher_rollout.hip), fp32 banks of the two-hidden-layer {16, 32, 64} family only - a bf16 /
+ * f16x2 bank or a dense stack is refused, never run chained in its place.  RQ_ROLLOUT_CHAINED: observe -> rq_teacher_bank_evaluate on
+ * the env's buffers -> step per step, plain launches, every bank; fused and chained give the same bits.  Refused before anything is
+ * enqueued (state, rng epoch, statistics and trajectory untouched): an id out of range, a bank / trajectory of another device or
+ * env, a trajectory without room for n_steps, an unknown mode or flag, fused mode on a bank it does not run. */
+RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
+                               const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                               rq_trajectory* trajectory);
 
 
 /* ---- Multi-GPU: the path's one exchange ---------------------------------------------

@@ -116,6 +116,10 @@ struct TeacherBank : detail::Handle<rq_teacher_bank, rq_teacher_bank_destroy> {
         check(rq_teacher_bank_create(d.h, weights, n_teachers, in_dim, h1, h2, hidden, output, &h));
     }
     void set_precision(rq_policy_precision p) { check(rq_teacher_bank_set_precision(h, p)); }
+    // teacher ids[i] on row i: observation host [batch, obs_stride] -> action host [batch, 4]
+    void evaluate(const std::uint32_t* ids, const float* observation, std::uint32_t batch, std::uint32_t obs_stride, float* action) {
+        check(rq_teacher_bank_evaluate(h, nullptr, ids, observation, batch, obs_stride, action));
+    }
 };
 
 // one rank of the multi-GPU job: RCCL all-gather of episode returns issued by the library itself
@@ -162,6 +166,12 @@ inline void rollout(Device& d, Environment& env, Parameters& p, State& s, Raptor
                     std::uint32_t n_steps, Trajectory& traj, rq_rollout_mode mode = RQ_ROLLOUT_FUSED, bool autoreset = false) {
     check(rq_rollout_record(d.h, env.h, p.h, s.h, policy.h, rng.h, n_steps, mode,
                             autoreset ? std::uint32_t(RQ_ROLLOUT_AUTORESET) : 0u, traj.h));
+}
+// the loop body README.md:95-99, n_steps times, env i flown by teacher ids[i] of the bank; traj: nullptr or the buffer it appends to
+inline void rollout(Device& d, Environment& env, Parameters& p, State& s, TeacherBank& bank, const std::uint32_t* ids, Rng& rng,
+                    std::uint32_t n_steps, rq_rollout_mode mode = RQ_ROLLOUT_FUSED, bool autoreset = false, Trajectory* traj = nullptr) {
+    check(rq_rollout_teachers(d.h, env.h, p.h, s.h, bank.h, ids, rng.h, n_steps, mode, autoreset ? std::uint32_t(RQ_ROLLOUT_AUTORESET) : 0u,
+                              traj ? traj->h : nullptr));
 }
 // teacher teacher_id[i] labels every recorded step of env i; action_out: host [length, N, 4] or nullptr
 inline void relabel_teachers(Trajectory& traj, TeacherBank& bank, const std::uint32_t* teacher_id, float* action_out,

@@ -183,6 +183,8 @@ _SIGNATURES = {
     "rq_teacher_bank_destroy": [_vp],
     "rq_teacher_bank_set_precision": [_vp, C.c_int],
     "rq_trajectory_relabel_teachers": [_vp, _vp, _vp, _fp, C.c_int],
+    "rq_teacher_bank_evaluate": [_vp, _vp, _vp, _fp, C.c_uint32, C.c_uint32, _fp],
+    "rq_rollout_teachers": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp],
 }
 _RESTYPES = {"rq_last_error": C.c_char_p, "rq_status_string": C.c_char_p}
 

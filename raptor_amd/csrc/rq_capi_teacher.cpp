@@ -117,6 +117,8 @@ RQ_API int rq_teacher_bank_destroy(rq_teacher_bank* bank) {
     if (bank->images_bf16) (void)hipFree(bank->images_bf16);
     if (bank->images_f16x2) (void)hipFree(bank->images_f16x2);
     if (bank->tiles) (void)hipFree(bank->tiles);
+    if (bank->sink) (void)hipFree(bank->sink);
+    if (bank->eval_buf) (void)hipFree(bank->eval_buf);
     delete bank;
     return RQ_OK;
 }
@@ -137,24 +139,31 @@ RQ_API int rq_teacher_bank_set_precision(rq_teacher_bank* bank, int precision) {
     return RQ_OK;
 }
 
-RQ_API int rq_trajectory_relabel_teachers(rq_trajectory* t, rq_teacher_bank* bank, const uint32_t* teacher_id, float* action_out,
-                                   int overwrite) {
-    RQ_REQUIRE(t && bank && teacher_id, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    rq_env* env = t->env;
-    rq_device* dev = env->dev;
-    RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "teacher bank lives on another device");
-    if (t->length == 0) return RQ_OK;
-    const uint32_t n = env->n;
-    // group the envs by teacher: a tile = up to 16 envs of ONE teacher (counting sort over the teacher ids, env
-    // order kept inside a teacher, so sorted inputs give contiguous tiles and coalesced rows)
+}  // extern "C"
+
+namespace {
+
+// teacher_id[0..n) all name a teacher of the bank (checked before anything is enqueued)
+int check_ids(const rq_teacher_bank* bank, const uint32_t* teacher_id, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i)
         RQ_REQUIRE(teacher_id[i] < bank->n_teachers, RQ_ERR_INVALID_ARGUMENT, "teacher id out of range");
-    // register-stationary family: tile_teacher [n_tiles] | tile_env [n_tiles][16] (a tile = up to 16 envs of ONE teacher);
-    // dense stacks (round 6): teacher_start [n_teachers + 1] | sorted_env [n] - the kernel forms its 16-wide tiles out of (env, step) pairs
+    return RQ_OK;
+}
+
+// The bank's device tile list for n envs assigned by teacher_id, built and uploaded only when (key, ids) differ from what `tiles`
+// holds - a loop of rollout chunks or relabels with one assignment pays no copy and no stream synchronisation after its first call.
+// Group the envs by teacher: register-stationary family: tile_teacher [n_tiles] | tile_env [n_tiles][16] (a tile = up to 16 envs of
+// ONE teacher, counting sort over the ids, env order kept inside a teacher, so sorted inputs give contiguous tiles and coalesced rows);
+// dense stacks (round 6): teacher_start [n_teachers + 1] | sorted_env [n] - the kernel forms its 16-wide tiles out of (env, step) pairs.
+// Needs the caller's DeviceScope.
+int bank_tiles(rq_teacher_bank* bank, rq_device* dev, uint64_t key, const uint32_t* teacher_id, uint32_t n, uint32_t* n_tiles_out) {
+    if (bank->tiles_valid && bank->tiles_key == key && bank->tiles_ids.size() == n &&
+        std::memcmp(bank->tiles_ids.data(), teacher_id, (size_t)n * sizeof(uint32_t)) == 0) {
+        *n_tiles_out = bank->tiles_count;
+        return RQ_OK;
+    }
     std::vector<uint32_t> host;
     uint32_t n_tiles = 0;
-    if (bank->layers)
-        RQ_REQUIRE((uint64_t)n * t->length < (1ull << 32), RQ_ERR_INVALID_ARGUMENT, "envs x steps must stay below 2^32 for a dense-stack bank");
     try {                                   // nothing throws across the boundary
         std::vector<uint32_t> count(bank->n_teachers, 0), start(bank->n_teachers, 0), filled(bank->n_teachers, 0);
         for (uint32_t i = 0; i < n; ++i) ++count[teacher_id[i]];
@@ -177,10 +186,11 @@ RQ_API int rq_trajectory_relabel_teachers(rq_trajectory* t, rq_teacher_bank* ban
                 host[(size_t)n_tiles + (size_t)tile * 16 + pos % 16u] = i;
             }
         }
+        bank->tiles_valid = false;
+        bank->tiles_ids.assign(teacher_id, teacher_id + n);
     } catch (const std::bad_alloc&) {
-        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_trajectory_relabel_teachers: host allocation failed");
+        return fail(RQ_ERR_OUT_OF_MEMORY, "teacher bank: host allocation failed");
     }
-    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     if (bank->tile_words < host.size()) {
         RQ_HIP(hipStreamSynchronize(dev->stream));
         if (bank->tiles) { RQ_HIP(hipFree(bank->tiles)); bank->tiles = nullptr; bank->tile_words = 0; }
@@ -189,6 +199,56 @@ RQ_API int rq_trajectory_relabel_teachers(rq_trajectory* t, rq_teacher_bank* ban
     }
     RQ_HIP(hipMemcpyAsync(bank->tiles, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, dev->stream));
     RQ_HIP(hipStreamSynchronize(dev->stream));                // `host` is pageable and about to go out of scope
+    bank->tiles_valid = true;
+    bank->tiles_key = key;
+    bank->tiles_count = n_tiles;
+    *n_tiles_out = n_tiles;
+    return RQ_OK;
+}
+
+// the bank's actions on obs [steps][22][ld] -> act [steps][4][ld] for the n envs of the tile list bank_tiles made (any kind, any precision)
+int bank_label(rq_teacher_bank* bank, rq_device* dev, uint32_t n, uint32_t n_tiles, uint32_t ld, uint32_t steps, const float* obs,
+               float* act) {
+    const float* images = bank->precision == RQ_POLICY_BF16_MFMA ? bank->images_bf16
+                        : bank->precision == RQ_POLICY_F16X2_MFMA ? bank->images_f16x2 : bank->images_f32;
+    if (bank->layers)
+        RQ_HIP(rq::launch_teacher_relabel_layers(dev->stream, bank->n_teachers, n, ld, steps, bank->in_dim, bank->n_hidden, bank->hp,
+                                                 bank->act, bank->out_act, bank->images_layers, bank->tiles, bank->tiles + bank->n_teachers + 1,
+                                                 obs, act));
+    else
+        RQ_HIP(rq::launch_teacher_relabel(dev->stream, n_tiles, ld, steps, bank->in_dim, bank->h1, bank->h2, bank->act,
+                                          bank->out_act, bank->precision, images, bank->tiles, bank->tiles + n_tiles, obs, act));
+    return RQ_OK;
+}
+
+// device scratch of the bank: *buf holds at least `floats` floats afterwards
+int bank_scratch(rq_device* dev, float** buf, size_t* have, size_t floats) {
+    if (*have >= floats) return RQ_OK;
+    RQ_HIP(hipStreamSynchronize(dev->stream));
+    if (*buf) { RQ_HIP(hipFree(*buf)); *buf = nullptr; *have = 0; }
+    RQ_HIP(hipMalloc(buf, floats * sizeof(float)));
+    *have = floats;
+    return RQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+RQ_API int rq_trajectory_relabel_teachers(rq_trajectory* t, rq_teacher_bank* bank, const uint32_t* teacher_id, float* action_out,
+                                   int overwrite) {
+    RQ_REQUIRE(t && bank && teacher_id, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "teacher bank lives on another device");
+    if (t->length == 0) return RQ_OK;
+    const uint32_t n = env->n;
+    int rc = check_ids(bank, teacher_id, n); if (rc) return rc;
+    if (bank->layers)
+        RQ_REQUIRE((uint64_t)n * t->length < (1ull << 32), RQ_ERR_INVALID_ARGUMENT, "envs x steps must stay below 2^32 for a dense-stack bank");
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    uint32_t n_tiles = 0;
+    rc = bank_tiles(bank, dev, env->uid, teacher_id, n, &n_tiles); if (rc) return rc;
     const size_t act_bytes = (size_t)t->length * RQ_ACTION_DIM * env->ld * sizeof(float);
     float* d_act = t->act;
     if (!overwrite) {
@@ -199,17 +259,114 @@ RQ_API int rq_trajectory_relabel_teachers(rq_trajectory* t, rq_teacher_bank* ban
         }
         d_act = dev->rows2;
     }
-    const float* images = bank->precision == RQ_POLICY_BF16_MFMA ? bank->images_bf16
-                        : bank->precision == RQ_POLICY_F16X2_MFMA ? bank->images_f16x2 : bank->images_f32;
-    if (bank->layers)
-        RQ_HIP(rq::launch_teacher_relabel_layers(dev->stream, bank->n_teachers, n, env->ld, t->length, bank->in_dim, bank->n_hidden, bank->hp,
-                                                 bank->act, bank->out_act, bank->images_layers, bank->tiles, bank->tiles + bank->n_teachers + 1,
-                                                 t->obs, d_act));
-    else
-    RQ_HIP(rq::launch_teacher_relabel(dev->stream, n_tiles, env->ld, t->length, bank->in_dim, bank->h1, bank->h2, bank->act,
-                                      bank->out_act, bank->precision, images, bank->tiles, bank->tiles + n_tiles, t->obs,
-                                      d_act));
+    rc = bank_label(bank, dev, n, n_tiles, env->ld, t->length, t->obs, d_act); if (rc) return rc;
     if (action_out) return traj_block_to_host(dev, d_act, t->length, env->n, env->ld, RQ_ACTION_DIM, action_out);
+    return RQ_OK;
+}
+
+RQ_API int rq_teacher_bank_evaluate(rq_teacher_bank* bank, rq_env* env, const uint32_t* teacher_id, const float* observation,
+                                    uint32_t batch, uint32_t obs_stride, float* action) {
+    RQ_REQUIRE(bank && teacher_id, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    const bool on_env = observation == nullptr || action == nullptr;          // reads or writes the env's device buffers
+    RQ_REQUIRE(env || !on_env, RQ_ERR_INVALID_ARGUMENT, "a NULL observation / action names the env's device buffer: env is required");
+    rq_device* dev = bank->dev;
+    if (env) {
+        RQ_REQUIRE(env->dev == dev, RQ_ERR_SHAPE_MISMATCH, "env lives on another device than the teacher bank");
+        RQ_REQUIRE(env->initialized, RQ_ERR_NOT_INITIALIZED, "initialize_environment was not called");
+    }
+    RQ_REQUIRE(batch > 0, RQ_ERR_INVALID_ARGUMENT, "batch must be positive");
+    if (on_env) RQ_REQUIRE(batch == env->n, RQ_ERR_SHAPE_MISMATCH, "the env's buffers hold N_ENVIRONMENTS rows: batch must equal it");
+    if (observation) RQ_REQUIRE(obs_stride >= bank->in_dim, RQ_ERR_INVALID_ARGUMENT, "obs_stride is below the teachers' input width");
+    int rc = check_ids(bank, teacher_id, batch); if (rc) return rc;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    const uint32_t ld = on_env ? env->ld : round_up64(batch);
+    uint32_t n_tiles = 0;
+    rc = bank_tiles(bank, dev, on_env ? env->uid : 0, teacher_id, batch, &n_tiles); if (rc) return rc;
+    const float* d_obs = on_env && !observation ? env->obs : nullptr;
+    float* d_act = action ? nullptr : env->act;
+    if (observation || action) {
+        const size_t rows = observation ? (size_t)batch * obs_stride : 0;
+        rc = bank_scratch(dev, &bank->eval_buf, &bank->eval_floats, rows + (size_t)(RQ_POLICY_INPUT_DIM + RQ_ACTION_DIM) * ld);
+        if (rc) return rc;
+        if (observation) {
+            float* soa = bank->eval_buf + rows;
+            RQ_HIP(hipMemcpyAsync(bank->eval_buf, observation, rows * sizeof(float), hipMemcpyHostToDevice, dev->stream));
+            RQ_HIP(rq::launch_rows_to_soa(dev->stream, bank->eval_buf, obs_stride, std::min<uint32_t>(obs_stride, RQ_POLICY_INPUT_DIM),
+                                          batch, ld, soa));
+            d_obs = soa;
+        }
+        if (action) d_act = bank->eval_buf + rows + (size_t)RQ_POLICY_INPUT_DIM * ld;
+    }
+    if (!action) obs_cache_drop_if(dev, env);
+    rc = bank_label(bank, dev, batch, n_tiles, ld, 1, d_obs, d_act); if (rc) return rc;
+    if (action) return traj_block_to_host(dev, d_act, 1, batch, ld, RQ_ACTION_DIM, action);
+    RQ_HIP(hipStreamSynchronize(dev->stream));                // the host rows are read before the call returns
+    return RQ_OK;
+}
+
+RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
+                               const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                               rq_trajectory* traj) {
+    int rc = check_env_objects(dev, env, params, state); if (rc) return rc;
+    RQ_REQUIRE(params && state && bank && teacher_id && rng, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "teacher bank lives on another device");
+    RQ_REQUIRE(rng->initialized, RQ_ERR_NOT_INITIALIZED, "initialize_rng was not called");
+    RQ_REQUIRE(mode == RQ_ROLLOUT_FUSED || mode == RQ_ROLLOUT_CHAINED, RQ_ERR_INVALID_ARGUMENT, "unknown mode");
+    RQ_REQUIRE((flags & ~(uint32_t)RQ_ROLLOUT_AUTORESET) == 0, RQ_ERR_INVALID_ARGUMENT, "unknown flags");
+    RQ_REQUIRE(mode != RQ_ROLLOUT_FUSED || (!bank->layers && bank->precision == RQ_POLICY_FP32), RQ_ERR_INVALID_ARGUMENT,
+               "the fused teacher rollout runs the fp32 two-hidden-layer {16, 32, 64} family: fly this bank (bf16 / f16x2 precision "
+               "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
+    rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
+    if (traj) {
+        RQ_REQUIRE(traj->env == env, RQ_ERR_SHAPE_MISMATCH, "trajectory belongs to another env");
+        RQ_REQUIRE((uint64_t)traj->length + n_steps <= traj->capacity, RQ_ERR_INVALID_ARGUMENT,
+                   "trajectory buffer too small for this rollout");
+        tp = {traj->obs, traj->act, traj->rew, traj->done, traj->length};
+    }
+    rc = check_ids(bank, teacher_id, env->n); if (rc) return rc;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    uint32_t n_tiles = 0;
+    rc = bank_tiles(bank, dev, env->uid, teacher_id, env->n, &n_tiles); if (rc) return rc;
+    if (mode == RQ_ROLLOUT_CHAINED && n_steps) {
+        rc = bank_scratch(dev, &bank->sink, &bank->sink_floats, RQ_POLICY_NUM_WEIGHTS + (size_t)16 * env->ld);
+        if (rc) return rc;
+    }
+    obs_cache_drop_if(dev, env);
+    if (n_steps) { rc = state_make_private(state, true); if (rc) return rc; }      // steps the state in place
+    const rq::Batch b = batch_of(env);
+    const rq::StepCfg sc = rq::step_cfg(env->cfg);
+    const rq::NoiseCfg nc = rq::noise_cfg(env->cfg);
+    const rq::SampleCfg smp = rq::sample_cfg(env->cfg);
+    const bool noise = rq::noise_enabled(env->cfg);
+    if (traj && n_steps && !(flags & RQ_ROLLOUT_AUTORESET))   // steps a frozen wave never reaches read as "not stepped"
+        RQ_HIP(hipMemsetAsync(traj->done + (size_t)traj->length * env->ld, 4, (size_t)n_steps * env->ld, dev->stream));
+    if (mode == RQ_ROLLOUT_FUSED) {
+        rq::TeacherRolloutArgs a{b, sc, nc, smp, rng->seed, rng->epoch, n_steps, noise ? 1u : 0u,
+                                 (flags & RQ_ROLLOUT_AUTORESET) ? 1u : 0u, params->d, state->d, env->st, tp,
+                                 bank->in_dim, bank->images_f32, bank->tiles, bank->tiles + n_tiles};
+        RQ_HIP(rq::launch_rollout_teachers(dev->stream, n_tiles, bank->h1, bank->h2, bank->act, bank->out_act, a));
+    } else if (n_steps) {
+        // one step = observe -> the bank on the env's buffers (rq_teacher_bank_evaluate's launch) -> step (-> record), plain launches on
+        // the device's stream.  k_step's auto-reset also resets a policy state: here it writes the bank's sink (zero weight block)
+        float* sink_w = bank->sink;
+        float* sink_h = bank->sink + RQ_POLICY_NUM_WEIGHTS;
+        RQ_HIP(hipMemsetAsync(sink_w, 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float), dev->stream));
+        if (flags & RQ_ROLLOUT_AUTORESET)   // envs frozen by an earlier rollout start their next episode
+            RQ_HIP(rq::launch_thaw_frozen(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, sink_h, sink_w));
+        for (uint32_t t = 0; t < n_steps; ++t) {
+            RQ_HIP(rq::launch_observe(dev->stream, b, nc, noise, rng->seed, rng->epoch + t, nullptr, params->d, state->d, env->obs));
+            rc = bank_label(bank, dev, env->n, n_tiles, env->ld, 1, env->obs, env->act); if (rc) return rc;
+            RQ_HIP(rq::launch_step(dev->stream, b, sc, params->d, state->d, env->act, state->d, env->st, /*rollout=*/1, flags, smp,
+                                   rng->seed, sink_h, sink_w));
+            if (traj) {
+                rq::TrajPtrs tt = tp; tt.t0 = tp.t0 + t;
+                RQ_HIP(rq::launch_record(dev->stream, b, env->obs, env->act, env->st, tt));
+            }
+        }
+    }
+    rng->epoch += n_steps;
+    if (traj) traj->length += n_steps;
+    if (n_steps) state->version = fresh_version();
     return RQ_OK;
 }
 

@@ -292,6 +292,18 @@ struct rq_teacher_bank {
     bool layers = false;
     uint32_t n_hidden = 2, widths[3] = {0, 0, 0}, hp = 0;
     float* images_layers = nullptr;  // [n_teachers][teacher_layers_image_floats(hp, n_hidden)]
+    // what `tiles` holds (rq_capi_teacher.cpp bank_tiles): the list built from tiles_ids for tiles_key (the env's uid, 0 = host rows)
+    // - a loop of rollout chunks or relabels with one assignment uploads it once
+    bool tiles_valid = false;
+    uint64_t tiles_key = 0;
+    uint32_t tiles_count = 0;
+    std::vector<uint32_t> tiles_ids;
+    // teacher rollouts, chained mode: k_step's policy-state reset needs a [16][ld] target and a weight block (a teacher has no state)
+    float* sink = nullptr;
+    size_t sink_floats = 0;
+    // rq_teacher_bank_evaluate from host rows: [batch][stride] rows | [22][ld] observation | [4][ld] actions
+    float* eval_buf = nullptr;
+    size_t eval_floats = 0;
 };
 
 

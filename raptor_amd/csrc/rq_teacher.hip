@@ -27,54 +27,10 @@
 #include <stdint.h>
 
 #include "rq_kernels.hpp"
+#include "rq_rollout.hpp"
+#include "rq_teacher.hpp"
 
 namespace rq {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t dwordx4 __attribute__((ext_vector_type(4)));
-
-template <int ACT>
-__device__ __forceinline__ float teacher_act(float x) {
-    if (ACT == RQ_ACT_RELU) {          // one v_max_i32 on the bit pattern (see relu() in rq_device_math.hpp)
-        const int b = __builtin_bit_cast(int, x);
-        return __builtin_bit_cast(float, b > 0 ? b : 0);
-    }
-    if (ACT == RQ_ACT_TANH)            // rows pre-scaled by -2 log2 e: x = -2 log2e * pre-activation
-        return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x)), -1.0f);
-    return x;
-}
-
-// B operand of layer 1 for this lane: feature f = 4s + q of env `e` at step t; feature in_dim is the constant 1
-// that carries the bias, anything beyond is padding.  obs is the trajectory's [T][22][ld] block.  The lane's six
-// element offsets inside a step's block are fixed; the step's block base is wave-uniform (scalar registers), so a
-// load is one instruction with no per-step 64-bit address arithmetic on the VALU.
-struct InputPlan {
-    uint32_t off[6];       // (feature row) * ld + env, in elements (< 2^30: ld <= 2^24 rows of 22)
-    uint32_t f[6];
-    uint32_t in_dim, ld;
-    __device__ __forceinline__ InputPlan(uint32_t ld_, uint32_t e, uint32_t q, uint32_t in_dim_) : in_dim(in_dim_), ld(ld_) {
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-            f[s] = 4 * s + q;
-            off[s] = (f[s] < in_dim ? f[s] : 0u) * ld + e;
-        }
-    }
-    // the bias constant and the padding replace what was loaded for features >= in_dim.  Kept apart from load(): the
-    // loads run one or two steps ahead and their values cross the loop's back edge raw - written as one expression
-    // the compiler sinks each load into its select and a step pays six exec-masked branches
-    __device__ __forceinline__ void finish(float (&x)[6]) const {
-#pragma unroll
-        for (int s = 0; s < 6; ++s) x[s] = f[s] < in_dim ? x[s] : (f[s] == in_dim ? 1.0f : 0.0f);
-    }
-    __device__ __forceinline__ void load(const float* __restrict__ obs, uint32_t t, float (&x)[6]) const {
-        const float* __restrict__ block = obs + (size_t)t * RQ_POLICY_INPUT_DIM * ld;      // wave-uniform
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-            x[s] = block[off[s]];
-        }
-    }
-};
 
 template <int H1, int H2, int ACT, int OUT_ACT>
 __global__ __launch_bounds__(64, 2) void k_teacher_relabel_f32(uint32_t ld, uint32_t steps, uint32_t in_dim,
@@ -681,6 +637,177 @@ hipError_t launch_teacher_relabel(hipStream_t s, uint32_t n_tiles, uint32_t ld, 
     RQ_T_HH(64, 64); RQ_T_HH(64, 32); RQ_T_HH(32, 64); RQ_T_HH(32, 32); RQ_T_HH(32, 16); RQ_T_HH(16, 32); RQ_T_HH(16, 16);
     RQ_T_HH(64, 16); RQ_T_HH(16, 64);
 #undef RQ_T_HH
+    return hipErrorInvalidValue;
+}
+
+// ---- a teacher bank FLYING its envs: the loop body of README.md:95-99 (observe -> act -> step -> assign)
+// n_steps times in one launch, env i driven by its own MLP teacher (rq_rollout_teachers, fused mode; the register-stationary
+// family in fp32).  Checking each teacher in closed loop and collecting teacher-driven data (the teacher-acting phase of
+// distillation) both need it; the relabel kernels of rq_teacher.hip only label what a student already recorded.
+//
+// Mapping (DESIGN.md "Teacher rollouts").  One wave per TILE = up to 16 envs of ONE teacher (the tile list rq_capi_teacher.cpp builds
+// for relabelling), so the teacher's A operands are loaded once and stay in registers for all n_steps.  Lane (q = l >> 4, j = l & 15)
+// carries env j of the tile and steps it - all four lane groups step the same env, redundantly.  That costs the env step's vector
+// work four times over, and buys the observation in the B-operand layout at no cost: lane (q, j) needs feature 4s + q of env j, which
+// it computed itself, so nothing is exchanged on the way into the MFMAs.  The four actions come out in lane (0, j) and reach the
+// other lane groups with one ds_bpermute each.  Env state, per-env constants, episode statistics and operands stay in registers for
+// the whole launch; HBM is touched in the prologue, by the trajectory's stores, and in the epilogue.
+//
+// The env arithmetic is rq_device_math.hpp's, the same functions in the same order as k_step's step_env / k_observe / k_thaw_frozen
+// (the unit is built with -ffp-contract=off like the others), so a transition equals the chained mode's bit for bit; the layers are
+// TeacherF32 (rq_teacher.hpp), so an action equals k_teacher_relabel_f32's label of the recorded observation bit for bit.
+template <int H1, int H2, int ACT, int OUT_ACT>
+__global__ __launch_bounds__(64, 1) void k_rollout_teachers(TeacherRolloutArgs a) {
+    typedef TeacherF32<H1, H2> W;
+    constexpr int M1 = W::M1, M2 = W::M2, K2 = W::K2, K3 = W::K3;
+    const uint32_t lane = threadIdx.x, q = lane >> 4, j = lane & 15;
+    const uint32_t tile = blockIdx.x;
+    float A1[M1][6], A2[M2][K2], A3[K3];
+    f32x4 B2[M2], B3;
+    W::load(a.images + (size_t)a.tile_teacher[tile] * W::REGS * 64 + lane, A1, A2, A3, B2, B3);
+    const uint32_t e0 = a.tile_env[tile * 16 + j];
+    const bool valid = e0 != 0xFFFFFFFFu;
+    const uint32_t i = valid ? e0 : a.tile_env[tile * 16];     // padding lanes shadow the tile's first env and never store
+    const bool owner = valid && q == 0;                         // the lane that writes env i's state and statistics back
+    const size_t ld = a.b.ld;
+    const uint64_t genv = a.b.env_offset + i;
+    const StepCfg& c = a.c;
+    const StatsPtrs& st = a.st;
+    const EnvConsts k = make_consts([&](int f) { return field(a.params, f, ld)[i]; });
+    const float mass = field(a.params, RQ_P_MASS, ld)[i], hover_rpm = field(a.params, RQ_P_HOVER_RPM, ld)[i];
+    const float pos0x = field(a.params, RQ_P_ROTOR_POS, ld)[i], pos0y = field(a.params, (RQ_P_ROTOR_POS + 1), ld)[i];
+    QuadState y;
+    y.load([&](int f) { return field(a.state, f, ld)[i]; });
+    f32x2 LA01 = {field(a.state, (RQ_S_LAST_ACTION + 0), ld)[i], field(a.state, (RQ_S_LAST_ACTION + 1), ld)[i]};
+    f32x2 LA23 = {field(a.state, (RQ_S_LAST_ACTION + 2), ld)[i], field(a.state, (RQ_S_LAST_ACTION + 3), ld)[i]};
+    float f6[6];
+#pragma unroll
+    for (int f = 0; f < 6; ++f) f6[f] = field(a.state, (RQ_S_FORCE + f), ld)[i];
+    Stats s = {st.returns[i], st.steps[i], st.fin_returns[i], st.fin_lengths[i], st.fin_counts[i], st.fin_terminated[i]};
+    float last_r = st.last_reward[i];
+    bool last_t = st.last_terminated[i] != 0;
+    uint8_t last_d = st.last_done[i];
+    uint32_t ep = st.episode[i];
+    bool frozen = st.frozen[i] != 0;
+    // sample_initial_state for the episode counter ep, as step_env's auto-reset and k_thaw_frozen make it
+    auto resample = [&]() {
+        float s0[17], la0[4];
+        sample_state(a.sc, a.seed, ep, genv, mass, hover_rpm, pos0x, pos0y, s0, la0, f6);
+        y.load([&](int f) { return s0[f]; });
+        LA01 = f32x2{la0[0], la0[1]}; LA23 = f32x2{la0[2], la0[3]};
+        ep += 1;
+    };
+    if (a.autoreset && frozen) {      // left frozen by an earlier rollout without auto-reset: its next episode starts here
+        resample();
+        frozen = false;
+    }
+    Disturbance ds = make_disturbance(k, c.gravity, f6);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const InputPlan in(ld, i, q, a.in_dim);                     // (only its bias / padding rule: the features come from registers)
+    const bool record = a.traj.obs != nullptr;                  // wave-uniform
+    const uint32_t row = (uint32_t)ld * 4u;                     // bytes per field row of a trajectory step
+    const uint32_t lane_off = valid ? i * 4u : 0xFFFFFFFFu;     // out of range: the hardware drops the store
+    bool sat_out = false;                                       // the wave left the loop early: every env frozen
+    for (uint32_t t = 0; t < a.n_steps; ++t) {
+        if (!a.autoreset && __builtin_amdgcn_ballot_w64(!frozen) == 0) { sat_out = true; break; }    // wave-uniform
+        float o[22];
+        if (a.noise) observe_head<true>(y, LA01, LA23, a.nc, a.seed, a.epoch0 + t, genv, o);
+        else         observe_head<false>(y, LA01, LA23, a.nc, a.seed, a.epoch0 + t, genv, o);
+        // K-step s, k-slot q: feature 4s + q (features 22, 23 are the bias slot / padding, set by finish)
+        float X[6];
+#pragma unroll
+        for (int sk = 0; sk < 6; ++sk) {
+            const float v0 = o[4 * sk], v1 = o[4 * sk + 1];
+            const float v2 = 4 * sk + 2 < 22 ? o[(4 * sk + 2) % 22] : 0.0f, v3 = 4 * sk + 3 < 22 ? o[(4 * sk + 3) % 22] : 0.0f;
+            X[sk] = q == 0 ? v0 : (q == 1 ? v1 : (q == 2 ? v2 : v3));
+        }
+        const size_t tt = (size_t)a.traj.t0 + t;
+        if (record) {   // the lane groups split the 22 observation rows: one store per K-step, 16 envs x 4 rows each
+            const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(a.traj.obs + tt * 22 * ld, 0, 22u * row, 0x00020000);
+#pragma unroll
+            for (int sk = 0; sk < 6; ++sk) {
+                const uint32_t f = 4u * sk + q;
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, X[sk]), ro, f < 22u ? lane_off : 0xFFFFFFFFu,
+                                                      f * row, kNtTrajAux);
+            }
+        }
+        in.finish(X);
+        const f32x4 out = W::template forward<ACT>(A1, A2, A3, B2, B3, zero, X);
+        float act[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) act[r] = __shfl(teacher_act<OUT_ACT>(out[r]), (int)j, 64);     // lane (0, j) -> lane (q, j)
+        if (record) {   // lane group q stores action row q
+            const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(a.traj.act + tt * 4 * ld, 0, 4u * row, 0x00020000);
+            const float aq = q == 0 ? act[0] : (q == 1 ? act[1] : (q == 2 ? act[2] : act[3]));
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, aq), ra, lane_off, q * row, kNtTrajAux);
+        }
+        if (a.autoreset || !frozen) {
+            // step_env's transition: RK4 on the clipped action, ActionHistory, statistics, episode end
+            QuadState yn = y;
+            f32x2 A01, A23;
+            bool term;
+            const float r = step_inplace<false>(c, k, ds, yn, act, A01, A23, term);
+            if (c.action_history_raw) { A01 = f32x2{act[0], act[1]}; A23 = f32x2{act[2], act[3]}; }
+            const bool ended = stats_update(c.episode_step_limit, r, term, s);
+            last_r = r;
+            last_t = term;
+            last_d = term ? 1 : (ended ? 2 : 0);
+            y = yn;
+            LA01 = A01; LA23 = A23;
+            if (ended) {
+                if (a.autoreset) {
+                    resample();
+                    ds = make_disturbance(k, c.gravity, f6);
+                } else {
+                    frozen = true;
+                }
+            }
+        } else {
+            last_d = 4;                 // frozen: not stepped
+        }
+        if (record && q == 0) {   // reward and done code of this transition, as k_record copies them
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(a.traj.rew + tt * ld, 0, row, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(a.traj.done + tt * ld, 0, (uint32_t)ld, 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, last_r), rr, lane_off, 0, kNtTrajAux);
+            __builtin_amdgcn_raw_buffer_store_b8(last_d, rd, valid ? i : 0xFFFFFFFFu, 0, kNtTrajAux);
+        }
+    }
+    // a wave that stopped early sat out the remaining steps: its envs' last transition of this rollout is "not stepped"
+    if (sat_out) last_d = 4;
+    if (owner) {
+        y.store([&](int f, float v) { field(a.state, f, ld)[i] = v; });
+        field(a.state, (RQ_S_LAST_ACTION + 0), ld)[i] = LA01[0]; field(a.state, (RQ_S_LAST_ACTION + 1), ld)[i] = LA01[1];
+        field(a.state, (RQ_S_LAST_ACTION + 2), ld)[i] = LA23[0]; field(a.state, (RQ_S_LAST_ACTION + 3), ld)[i] = LA23[1];
+#pragma unroll
+        for (int f = 0; f < 6; ++f) field(a.state, (RQ_S_FORCE + f), ld)[i] = f6[f];
+        st.returns[i] = s.ret; st.steps[i] = s.steps;
+        st.fin_returns[i] = s.fin_ret; st.fin_lengths[i] = s.fin_len; st.fin_counts[i] = s.fin_cnt; st.fin_terminated[i] = s.fin_term;
+        st.last_reward[i] = last_r;
+        st.last_terminated[i] = last_t ? 1 : 0;
+        st.last_done[i] = last_d;
+        st.episode[i] = ep;
+        st.frozen[i] = frozen ? 1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------------------- launcher ---
+// Instantiated per (H1, H2) and activation pair only: noise, auto-reset and recording are kernel arguments (9 x 4 = 36 kernels).
+template <int H1, int H2>
+static hipError_t launch_teachers_hh(hipStream_t s, uint32_t n_tiles, int act, int out_act, const TeacherRolloutArgs& a) {
+#define RQ_TR(A, O) k_rollout_teachers<H1, H2, A, O><<<n_tiles, 64, 0, s>>>(a)
+    if (act == RQ_ACT_RELU) { if (out_act == RQ_ACT_TANH) RQ_TR(RQ_ACT_RELU, RQ_ACT_TANH); else RQ_TR(RQ_ACT_RELU, RQ_ACT_IDENTITY); }
+    else                    { if (out_act == RQ_ACT_TANH) RQ_TR(RQ_ACT_TANH, RQ_ACT_TANH); else RQ_TR(RQ_ACT_TANH, RQ_ACT_IDENTITY); }
+#undef RQ_TR
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_teachers(hipStream_t s, uint32_t n_tiles, uint32_t h1, uint32_t h2, int act, int out_act,
+                                   const TeacherRolloutArgs& a) {
+    if (n_tiles == 0 || a.n_steps == 0) return hipSuccess;
+#define RQ_TR_HH(A, B) if (h1 == A && h2 == B) return launch_teachers_hh<A, B>(s, n_tiles, act, out_act, a)
+    RQ_TR_HH(64, 64); RQ_TR_HH(64, 32); RQ_TR_HH(32, 64); RQ_TR_HH(32, 32); RQ_TR_HH(32, 16); RQ_TR_HH(16, 32); RQ_TR_HH(16, 16);
+    RQ_TR_HH(64, 16); RQ_TR_HH(16, 64);
+#undef RQ_TR_HH
     return hipErrorInvalidValue;
 }
 

@@ -585,10 +585,25 @@ class VectorModule:
                   state._require("VectorState"), None, next_state._ensure(env), rng._require("rng"), None)
 
     def rollout(self, device, env, params, state, policy, rng, n_steps, mode="fused", autoreset=False,
-                trajectory=None):
+                trajectory=None, teacher_ids=None):
         """The loop body README.md:95-99, ``n_steps`` times, entirely on the device; with
-        ``trajectory`` every transition is also appended to that buffer."""
+        ``trajectory`` every transition is also appended to that buffer.  ``policy`` is a ``Raptor`` or a
+        ``raptor_amd.teachers.TeacherBank``; with a bank, ``teacher_ids`` ([N] integers) names the teacher that flies
+        each env (``mode="fused"``: fp32 banks of two hidden layers of 16 / 32 / 64 units; ``"chained"``: every bank)."""
         m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
+        from .teachers import TeacherBank
+        if isinstance(policy, TeacherBank):
+            if teacher_ids is None:
+                raise ValueError("a TeacherBank flies the envs by teacher_ids: one teacher id per env is required")
+            ids = np.ascontiguousarray(teacher_ids, np.uint32)
+            if ids.shape != (self.N_ENVIRONMENTS,):
+                raise ValueError("teacher_ids must hold one id per env")
+            _lib.call("rq_rollout_teachers", device._h, env._require("environment"), params._require("VectorParameters"),
+                      state._require("VectorState"), policy._h, ids.ctypes.data, rng._require("rng"), int(n_steps), m,
+                      ROLLOUT_AUTORESET if autoreset else 0, trajectory._require("trajectory") if trajectory is not None else None)
+            return
+        if teacher_ids is not None:
+            raise ValueError("teacher_ids belong to a TeacherBank rollout; a Raptor policy flies every env itself")
         fast = _lib.fast
         if fast is not None and trajectory is None and state._mirror is None and hasattr(fast, "rollout"):
             status = fast.rollout(_lib.fn_addr("rq_rollout"), device._h, env._h, params._h, state._h, policy._handle(device), rng._h,

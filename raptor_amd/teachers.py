@@ -117,6 +117,35 @@ class TeacherBank:
         self._fin = weakref.finalize(self, _lib.load().rq_teacher_bank_destroy, h)
         self.set_precision(precision)
 
+    def evaluate(self, observation, teacher_ids, env=None, to_device=False):
+        """Teacher ``teacher_ids[i]`` on row i (the bank's ``Raptor.evaluate_step``; a teacher has no state).
+        ``observation`` [B, >= in_dim] (numpy, the first ``in_dim`` columns are read) -> [B, 4] float32.  ``observation=None``
+        reads the device observation buffer of ``env`` (a ``VectorEnvironment``, e.g. after ``vector.observe(..., None, ...)``);
+        ``to_device=True`` writes the actions into that env's device action buffer instead (``vector.step_device`` reads it)
+        and returns None."""
+        ids = np.ascontiguousarray(teacher_ids, np.uint32).ravel()
+        envh = None
+        if env is not None:
+            envh = env._require("environment")
+        elif observation is None or to_device:
+            raise ValueError("observation=None / to_device=True name the device buffers of an env: pass env=")
+        obs_ptr, stride = None, 0
+        if observation is not None:
+            obs = np.ascontiguousarray(observation, np.float32)
+            if obs.ndim == 1:
+                obs = obs[None, :]
+            if obs.ndim != 2 or obs.shape[1] < self.in_dim:
+                raise ValueError(f"observation must be [B, >= {self.in_dim}]")
+            obs_ptr, stride, batch = _lib.fptr(obs), obs.shape[1], obs.shape[0]
+        else:
+            batch = env.N_ENVIRONMENTS
+        if ids.shape != (batch,):
+            raise ValueError("teacher_ids must hold one id per row")
+        out = None if to_device else np.empty((batch, 4), np.float32)
+        _lib.call("rq_teacher_bank_evaluate", self._h, envh, ids.ctypes.data, obs_ptr, batch, stride,
+                  _lib.fptr(out) if out is not None else None)
+        return out
+
     def set_precision(self, precision):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
@@ -142,3 +171,28 @@ def balanced_teacher_assignment(n_envs, n_teachers):
     per_teacher[:extra] += 1                                  # tiles of each teacher
     ids = np.repeat(np.arange(n_teachers, dtype=np.uint32), per_teacher * 16)[:n_envs]
     return np.ascontiguousarray(ids)
+
+
+def teacher_episode_table(env, teacher_ids, n_teachers):
+    """Per-teacher closed-loop summary of the env's finished episodes (what anyone checks first after pre-training).
+
+    Reads the env's finished-episode records (``env.finished_*``: per env, the number of finished episodes, how many of them
+    terminated, and the return / length of the last one) and groups them by ``teacher_ids``.  -> dict of [n_teachers] arrays:
+    ``envs`` (envs flown), ``episodes`` (finished), ``mean_return`` / ``mean_length`` (over the envs' last finished episodes,
+    NaN for a teacher without one) and ``termination_share`` (terminated / finished, NaN without episodes)."""
+    ids = np.asarray(teacher_ids, np.int64).ravel()
+    counts = np.asarray(env.finished_counts(), np.float64)
+    done = counts > 0
+    ret = np.where(done, np.asarray(env.finished_returns(), np.float64), 0.0)
+    length = np.where(done, np.asarray(env.finished_lengths(), np.float64), 0.0)
+    term = np.asarray(env.finished_terminated(), np.float64)
+    k = int(n_teachers)
+    envs = np.bincount(ids, minlength=k)
+    with_episode = np.bincount(ids, weights=done.astype(np.float64), minlength=k)
+    episodes = np.bincount(ids, weights=counts, minlength=k)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_return = np.bincount(ids, weights=ret, minlength=k) / with_episode
+        mean_length = np.bincount(ids, weights=length, minlength=k) / with_episode
+        termination_share = np.bincount(ids, weights=term, minlength=k) / episodes
+    return dict(envs=envs, episodes=episodes.astype(np.int64), mean_return=mean_return, mean_length=mean_length,
+                termination_share=termination_share)
