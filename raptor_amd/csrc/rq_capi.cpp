@@ -42,40 +42,24 @@ bool policy_registry(const void* pol, int op) {
     return live.count(pol) != 0;
 }
 
-int ensure_staging(rq_device* dev, size_t bytes) {
-    if (dev->staging_bytes >= bytes) return RQ_OK;
-    if (dev->staging) { RQ_HIP(hipHostFree(dev->staging)); dev->staging = nullptr; dev->staging_bytes = 0; }
-    size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    RQ_HIP(hipHostMalloc(&dev->staging, want, hipHostMallocDefault));
-    dev->staging_bytes = want;
-    return RQ_OK;
-}
-
-int ensure_rows(rq_device* dev, size_t bytes) {
-    if (dev->rows_bytes >= bytes) return RQ_OK;
-    RQ_HIP(hipStreamSynchronize(dev->stream));
-    if (dev->rows) { RQ_HIP(hipFree(dev->rows)); dev->rows = nullptr; dev->rows_bytes = 0; }
-    RQ_HIP(hipMalloc(&dev->rows, bytes));
-    dev->rows_bytes = bytes;
-    return RQ_OK;
-}
+constexpr size_t kStagingFloorFloats = (1u << 20) / sizeof(float);     // the two pinned staging buffers start at 1 MiB
 
 // device SoA [dim][ld] -> host row-major [n][dim]
 int soa_to_host(rq_device* dev, const float* d_soa, uint32_t n, uint32_t ld, uint32_t dim, float* host) {
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     if (n >= kGpuLayoutMinEnvs) {
         const size_t row_bytes = (size_t)n * dim * sizeof(float);
-        rc = ensure_rows(dev, row_bytes); if (rc) return rc;
+        RQ_HIP(dev->rows.reserve(dev->stream, (size_t)n * dim));
         RQ_HIP(rq::launch_soa_to_rows(dev->stream, d_soa, ld, dim, n, dev->rows));
         RQ_HIP(hipMemcpyAsync(host, dev->rows, row_bytes, hipMemcpyDeviceToHost, dev->stream));
         RQ_HIP(hipStreamSynchronize(dev->stream));
         return RQ_OK;
     }
     const size_t bytes = (size_t)dim * ld * sizeof(float);
-    rc = ensure_staging(dev, bytes); if (rc) return rc;
+    RQ_HIP(dev->staging.reserve(dev->stream, (size_t)dim * ld, kStagingFloorFloats));
     RQ_HIP(hipMemcpyAsync(dev->staging, d_soa, bytes, hipMemcpyDeviceToHost, dev->stream));
     RQ_HIP(hipStreamSynchronize(dev->stream));
-    const float* s = static_cast<const float*>(dev->staging);
+    const float* s = dev->staging;
     for (uint32_t f = 0; f < dim; ++f) {
         const float* col = s + (size_t)f * ld;
         for (uint32_t i = 0; i < n; ++i) host[(size_t)i * dim + f] = col[i];
@@ -92,7 +76,7 @@ int host_to_soa(rq_device* dev, const float* host, uint32_t n, uint32_t stride, 
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     if (n >= kGpuLayoutMinEnvs && stride <= 2 * dim) {
         const size_t row_bytes = ((size_t)(n - 1) * stride + dim) * sizeof(float);   // last row: only its first dim columns
-        rc = ensure_rows(dev, (size_t)n * stride * sizeof(float)); if (rc) return rc;
+        RQ_HIP(dev->rows.reserve(dev->stream, (size_t)n * stride));
         RQ_HIP(hipMemcpyAsync(dev->rows, host, row_bytes, hipMemcpyHostToDevice, dev->stream));
         RQ_HIP(rq::launch_rows_to_soa(dev->stream, dev->rows, stride, dim, n, ld, d_soa));
         RQ_HIP(hipStreamSynchronize(dev->stream));
@@ -100,13 +84,8 @@ int host_to_soa(rq_device* dev, const float* host, uint32_t n, uint32_t stride, 
     }
     const size_t bytes = (size_t)dim * ld * sizeof(float);
     if (dev->h2d_pending) { RQ_HIP(hipEventSynchronize(dev->ev_h2d)); dev->h2d_pending = false; }
-    if (dev->staging_in_bytes < bytes) {
-        if (dev->staging_in) { RQ_HIP(hipHostFree(dev->staging_in)); dev->staging_in = nullptr; dev->staging_in_bytes = 0; }
-        const size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-        RQ_HIP(hipHostMalloc(&dev->staging_in, want, hipHostMallocDefault));
-        dev->staging_in_bytes = want;
-    }
-    float* s = static_cast<float*>(dev->staging_in);
+    RQ_HIP(dev->staging_in.reserve(dev->stream, (size_t)dim * ld, kStagingFloorFloats));
+    float* s = dev->staging_in;
     for (uint32_t f = 0; f < dim; ++f) {
         float* col = s + (size_t)f * ld;
         for (uint32_t i = 0; i < n; ++i) col[i] = host[(size_t)i * stride + f];
@@ -130,6 +109,9 @@ int check_env_objects(const rq_device* dev, const rq_env* env, const rq_params* 
 // ---- copy-on-write state buffers ---------------------------------------------------------------------------
 // Everything is enqueued on the device's one stream, so a buffer that went back to the pool is safe to hand out again:
 // whatever still reads it was enqueued before whatever will write it.
+// The one block that is not held through rq::DeviceBuffer: it has two holders (rq_state::refs counts them), goes back to the env's pool
+// rather than to HIP, and its env may be gone before it (rq_state_destroy) - the raw calls of this scheme are here, in rq_state_create /
+// rq_state_destroy and in rq_env_destroy's release of the pool.
 int state_fresh_buffer(rq_env* env, float** out) {
     if (!env->state_pool.empty()) { *out = env->state_pool.back(); env->state_pool.pop_back(); return RQ_OK; }
     const size_t bytes = (size_t)RQ_STATE_DIM * env->ld * sizeof(float);
@@ -253,12 +235,6 @@ RQ_API int rq_device_destroy(rq_device* dev) {
     if (dev->ev_start) (void)hipEventDestroy(dev->ev_start);
     if (dev->ev_stop) (void)hipEventDestroy(dev->ev_stop);
     if (dev->ev_h2d) (void)hipEventDestroy(dev->ev_h2d);
-    if (dev->k_span) (void)hipFree(dev->k_span);
-    if (dev->staging) (void)hipHostFree(dev->staging);
-    if (dev->rows) (void)hipFree(dev->rows);
-    if (dev->rows2) (void)hipFree(dev->rows2);
-    mailbox_free(dev);
-    if (dev->staging_in) (void)hipHostFree(dev->staging_in);
     delete dev;
     return RQ_OK;
 }
@@ -307,7 +283,7 @@ int fetch_rollout_records(rq_device* dev) {
     if (dev->k_fetched) return RQ_OK;
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     try { dev->k_host.resize((size_t)dev->k_span_used * 5); } catch (...) { return fail(RQ_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-    RQ_HIP(hipMemcpyAsync(dev->k_host.data(), dev->k_span, dev->k_host.size() * sizeof(unsigned long long),
+    RQ_HIP(hipMemcpyAsync(dev->k_host.data(), dev->k_span.get(), dev->k_host.size() * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, dev->stream));
     RQ_HIP(hipStreamSynchronize(dev->stream));
     dev->k_fetched = true;
@@ -370,7 +346,7 @@ RQ_API int rq_device_launch_floor(rq_device* dev, uint32_t n, uint32_t reps, flo
     RQ_REQUIRE(dev && us_per_launch, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(n > 0 && reps > 0, RQ_ERR_INVALID_ARGUMENT, "n and reps must be positive");
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
-    rc = ensure_rows(dev, (size_t)n * sizeof(float)); if (rc) return rc;
+    RQ_HIP(dev->rows.reserve(dev->stream, n));
     for (int i = 0; i < 3; ++i) RQ_HIP(rq::launch_fill_f32(dev->stream, dev->rows, 0.0f, n));
     RQ_HIP(hipEventRecord(dev->ev_start, dev->stream));
     for (uint32_t i = 0; i < reps; ++i) RQ_HIP(rq::launch_fill_f32(dev->stream, dev->rows, 0.0f, n));
@@ -466,19 +442,12 @@ RQ_API int rq_env_create(rq_device* dev, uint32_t n_envs, uint64_t global_env_of
     const size_t ld = e->ld;
     // one block for all statistics: 8 x 4-byte arrays + 3 x 1-byte arrays
     const size_t stats_bytes = ld * (8 * 4 + 3 * 1);
-    hipError_t e1 = hipMalloc(&e->obs, (size_t)RQ_OBSERVATION_DIM * ld * sizeof(float));
-    hipError_t e2 = hipMalloc(&e->act, (size_t)RQ_ACTION_DIM * ld * sizeof(float));
-    hipError_t e3 = hipMalloc(&e->stats_block, stats_bytes);
-    if (e3 == hipSuccess) e3 = hipMalloc(&e->epoch_dev, sizeof(uint32_t));
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-        if (e->obs) (void)hipFree(e->obs);
-        if (e->act) (void)hipFree(e->act);
-        if (e->stats_block) (void)hipFree(e->stats_block);
-        if (e->epoch_dev) (void)hipFree(e->epoch_dev);
+    if (e->obs.alloc((size_t)RQ_OBSERVATION_DIM * ld) != hipSuccess || e->act.alloc((size_t)RQ_ACTION_DIM * ld) != hipSuccess ||
+        e->stats_block.alloc(stats_bytes) != hipSuccess || e->epoch_dev.alloc(1) != hipSuccess) {
         delete e;
         return fail(RQ_ERR_OUT_OF_MEMORY, "rq_env_create: device allocation failed");
     }
-    char* b = static_cast<char*>(e->stats_block);
+    char* b = e->stats_block;
     e->st.returns = (float*)(b + 0 * 4 * ld);
     e->st.steps = (uint32_t*)(b + 1 * 4 * ld);
     e->st.fin_returns = (float*)(b + 2 * 4 * ld);
@@ -505,12 +474,7 @@ RQ_API int rq_env_destroy(rq_env* env) {
     if (!env) return RQ_OK;
     DeviceScope on_device(env->ordinal);   // hipFree synchronises the device; the parent is not touched - unless it is alive and
     if (device_registry(env->dev, 0)) (void)resident_retire(env->dev);     // keeps a resident executor
-    if (env->obs) (void)hipFree(env->obs);
-    if (env->obs_alt) (void)hipFree(env->obs_alt);
     for (float* b : env->state_pool) (void)hipFree(b);
-    if (env->act) (void)hipFree(env->act);
-    if (env->stats_block) (void)hipFree(env->stats_block);
-    if (env->epoch_dev) (void)hipFree(env->epoch_dev);
     for (auto& g : env->graphs) (void)hipGraphExecDestroy(g.exec);
     delete env;
     return RQ_OK;
@@ -559,8 +523,7 @@ RQ_API int rq_params_create(rq_env* env, rq_params** out) {
     RQ_REQUIRE(p, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
     p->env = env; p->ordinal = env->ordinal;
     const size_t bytes = (size_t)RQ_PARAM_DIM * env->ld * sizeof(float);
-    hipError_t e = hipMalloc(&p->d, bytes);
-    if (e != hipSuccess) { delete p; return fail(RQ_ERR_OUT_OF_MEMORY, "rq_params_create: device allocation failed"); }
+    if (p->d.alloc((size_t)RQ_PARAM_DIM * env->ld) != hipSuccess) { delete p; return fail(RQ_ERR_OUT_OF_MEMORY, "rq_params_create: device allocation failed"); }
     (void)hipMemsetAsync(p->d, 0, bytes, env->dev->stream);
     *out = p;
     return RQ_OK;
@@ -568,7 +531,6 @@ RQ_API int rq_params_create(rq_env* env, rq_params** out) {
 RQ_API int rq_params_destroy(rq_params* p) {
     if (!p) return RQ_OK;
     DeviceScope on_device(p->ordinal);
-    if (p->d) (void)hipFree(p->d);
     delete p;
     return RQ_OK;
 }
@@ -671,7 +633,7 @@ RQ_API int rq_env_reset_statistics(rq_env* env) {
     const size_t ld = env->ld;
     // everything except the per-env episode counters (they key the initial-state RNG); the frozen flags go too:
     // every env counts as running a fresh episode from its current state (contract in raptor_quad.h)
-    RQ_HIP(hipMemsetAsync(env->stats_block, 0, 7 * 4 * ld, env->dev->stream));
+    RQ_HIP(hipMemsetAsync(env->stats_block.get(), 0, 7 * 4 * ld, env->dev->stream));
     RQ_HIP(hipMemsetAsync(env->st.last_terminated, 0, 3 * ld, env->dev->stream));
     return RQ_OK;
 }

@@ -7,16 +7,6 @@ using namespace rqh;
 
 namespace {
 
-// grow a device buffer (contents not kept); the stream is drained first, a launch may still read the old one
-int ensure_buffer(rq_device* dev, float** p, size_t* have, size_t need) {
-    if (*have >= need && *p) return RQ_OK;
-    RQ_HIP(hipStreamSynchronize(dev->stream));
-    if (*p) { RQ_HIP(hipFree(*p)); *p = nullptr; *have = 0; }
-    RQ_HIP(hipMalloc(p, need));
-    *have = need;
-    return RQ_OK;
-}
-
 // what both directions refuse: only the fp32 student without input or output stages has a gradient here
 int check_pair(rq_trajectory* t, rq_policy* pol, const char* what) {
     RQ_REQUIRE(t && pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
@@ -61,17 +51,15 @@ RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* pol, int st
         }
         rq::pack_policy_grad(pol->w_eff, image.data());
         RQ_HIP(hipStreamSynchronize(dev->stream));
-        if (!pol->w_packed_grad) RQ_HIP(hipMalloc(&pol->w_packed_grad, image.size() * sizeof(float)));
+        RQ_HIP(pol->w_packed_grad.reserve(dev->stream, image.size()));
         RQ_HIP(hipMemcpy(pol->w_packed_grad, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
         pol->grad_image_version = pol->weight_version;
     }
     t->grad.valid = false;
-    rc = ensure_buffer(dev, &t->grad.saved, &t->grad.saved_bytes, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld * sizeof(float));
-    if (rc) return rc;
-    const size_t act_bytes = (size_t)T * RQ_ACTION_DIM * ld_action * sizeof(float);
+    RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld));
     float* d_act = action;
     if (memory == RQ_DST_HOST) {
-        rc = ensure_buffer(dev, &t->grad.rows, &t->grad.rows_bytes, act_bytes); if (rc) return rc;
+        RQ_HIP(t->grad.rows.reserve(dev->stream, (size_t)T * RQ_ACTION_DIM * ld_action));
         d_act = t->grad.rows;
     }
     RQ_HIP(rq::launch_policy_grad_forward(dev->stream, env->n, ld, T, pol->w_packed, t->obs, t->done,
@@ -106,9 +94,7 @@ RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* pol, const
     RQ_REQUIRE(ld_grad >= env->n, RQ_ERR_INVALID_ARGUMENT, "ld_grad must be at least the number of envs");
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const uint32_t T = t->length, ld = env->ld, waves = (env->n + 63) / 64;
-    rc = ensure_buffer(dev, &t->grad.partial, &t->grad.partial_bytes,
-                       ((size_t)waves * RQ_POLICY_NUM_WEIGHTS) * sizeof(float));
-    if (rc) return rc;
+    RQ_HIP(t->grad.partial.reserve(dev->stream, (size_t)waves * RQ_POLICY_NUM_WEIGHTS));
     const float* d_ga = grad_action;
     float* d_gw = grad_weights;
     float* d_gh = grad_hidden_start;
@@ -117,8 +103,8 @@ RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* pol, const
     const size_t gw_bytes = (size_t)RQ_POLICY_NUM_WEIGHTS * sizeof(float);
     if (memory == RQ_DST_HOST) {          // one device block: dL/da | dL/dtheta | dL/dh_start
         const size_t off_gw = (ga_bytes + 255) & ~(size_t)255, off_gh = off_gw + ((gw_bytes + 255) & ~(size_t)255);
-        rc = ensure_buffer(dev, &t->grad.rows, &t->grad.rows_bytes, off_gh + gh_bytes); if (rc) return rc;
-        char* base = reinterpret_cast<char*>(t->grad.rows);
+        RQ_HIP(t->grad.rows.reserve(dev->stream, (off_gh + gh_bytes) / sizeof(float)));
+        char* base = reinterpret_cast<char*>(t->grad.rows.get());
         RQ_HIP(hipMemcpyAsync(base, grad_action, ga_bytes, hipMemcpyHostToDevice, dev->stream));
         d_ga = reinterpret_cast<const float*>(base);
         d_gw = reinterpret_cast<float*>(base + off_gw);

@@ -25,12 +25,13 @@ int policy_size(rq_policy* pol, uint32_t batch) {
         RQ_REQUIRE(pol->batch == 0 || pol->needs_reset, RQ_ERR_SHAPE_MISMATCH,
                    "batch size changed without reset (hidden state is per batch element)");
         RQ_HIP(hipStreamSynchronize(pol->dev->stream));
-        policy_free_buffers(pol);
+        pol->hidden.reset(); pol->hidden_alt.reset(); pol->obs.reset(); pol->act.reset();
+        pol->batch = pol->ld = 0;                  // not sized, should an allocation below fail
         const uint32_t ld = round_up64(batch);
-        RQ_HIP(hipMalloc(&pol->hidden, (size_t)RQ_POLICY_HIDDEN_DIM * ld * sizeof(float)));
-        RQ_HIP(hipMalloc(&pol->hidden_alt, (size_t)RQ_POLICY_HIDDEN_DIM * ld * sizeof(float)));
-        RQ_HIP(hipMalloc(&pol->obs, (size_t)RQ_POLICY_INPUT_DIM * ld * sizeof(float)));
-        RQ_HIP(hipMalloc(&pol->act, (size_t)RQ_ACTION_DIM * ld * sizeof(float)));
+        RQ_HIP(pol->hidden.alloc((size_t)RQ_POLICY_HIDDEN_DIM * ld));
+        RQ_HIP(pol->hidden_alt.alloc((size_t)RQ_POLICY_HIDDEN_DIM * ld));
+        RQ_HIP(pol->obs.alloc((size_t)RQ_POLICY_INPUT_DIM * ld));
+        RQ_HIP(pol->act.alloc((size_t)RQ_ACTION_DIM * ld));
         pol->batch = batch; pol->ld = ld;
         pol->needs_reset = true;
     }
@@ -41,16 +42,6 @@ int policy_size(rq_policy* pol, uint32_t batch) {
         pol->needs_reset = false;
     }
     return RQ_OK;
-}
-
-void policy_free_buffers(rq_policy* pol) {
-    if (pol->hidden) (void)hipFree(pol->hidden);
-    if (pol->hidden_alt) (void)hipFree(pol->hidden_alt);
-    pol->hidden_alt = nullptr;
-    if (pol->obs) (void)hipFree(pol->obs);
-    if (pol->act) (void)hipFree(pol->act);
-    pol->hidden = pol->obs = pol->act = nullptr;
-    pol->batch = pol->ld = 0;
 }
 
 
@@ -107,14 +98,8 @@ RQ_API int rq_policy_create(rq_device* dev, const float* weights, size_t n_weigh
     RQ_REQUIRE(p, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
     p->dev = dev; p->ordinal = dev->ordinal;
     std::memcpy(p->w_host, weights, sizeof(p->w_host));
-    hipError_t e = hipMalloc(&p->w_dev, sizeof(p->w_host));
-    if (e != hipSuccess) { delete p; return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_create: device allocation failed"); }
-    e = hipMalloc(&p->w_packed, (size_t)rq::RQ_PACKED_FLOATS * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&p->w_packed_bf16, (size_t)rq::RQ_PACKED_BF16_FLOATS * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&p->w_packed_f16x2, (size_t)rq::RQ_PACKED_F16X2_FLOATS * sizeof(float));
-    if (e != hipSuccess) {
-        (void)hipFree(p->w_dev); if (p->w_packed) (void)hipFree(p->w_packed);
-        if (p->w_packed_bf16) (void)hipFree(p->w_packed_bf16);
+    if (p->w_dev.alloc(RQ_POLICY_NUM_WEIGHTS) != hipSuccess || p->w_packed.alloc(rq::RQ_PACKED_FLOATS) != hipSuccess ||
+        p->w_packed_bf16.alloc(rq::RQ_PACKED_BF16_FLOATS) != hipSuccess || p->w_packed_f16x2.alloc(rq::RQ_PACKED_F16X2_FLOATS) != hipSuccess) {
         delete p;
         return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_create: device allocation failed");
     }
@@ -130,13 +115,6 @@ RQ_API int rq_policy_destroy(rq_policy* pol) {
     DeviceScope on_device(pol->ordinal);
     if (device_registry(pol->dev, 0)) (void)resident_retire(pol->dev);
     policy_registry(pol, -1);      // rq_device::spec.last_policy may still name this object: it is checked against the registry
-    policy_free_buffers(pol);
-    if (pol->w_dev) (void)hipFree(pol->w_dev);
-    if (pol->w_packed) (void)hipFree(pol->w_packed);
-    if (pol->w_packed_bf16) (void)hipFree(pol->w_packed_bf16);
-    if (pol->w_packed_f16x2) (void)hipFree(pol->w_packed_f16x2);
-    if (pol->ls_image) (void)hipFree(pol->ls_image);
-    if (pol->w_packed_grad) (void)hipFree(pol->w_packed_grad);
     delete pol;
     return RQ_OK;
 }
@@ -212,7 +190,7 @@ RQ_API int rq_policy_set_sample_and_squash(rq_policy* pol, int mode, const float
         try { image.resize(rq::RQ_LOGSTD_FLOATS); } catch (const std::bad_alloc&) { return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_set_sample_and_squash: host allocation failed"); }
         rq::pack_logstd_head(log_std_weights, log_std_bias, image.data());
         RQ_HIP(hipStreamSynchronize(pol->dev->stream));
-        if (!pol->ls_image) RQ_HIP(hipMalloc(&pol->ls_image, image.size() * sizeof(float)));
+        RQ_HIP(pol->ls_image.reserve(pol->dev->stream, image.size()));
         RQ_HIP(hipMemcpy(pol->ls_image, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     pol->sas_mode = mode;
@@ -326,13 +304,8 @@ RQ_API int rq_policy_evaluate_sequence(rq_policy* pol, const float* observation,
     float* d_act = action;
     if (memory == RQ_DST_HOST) {
         const size_t obs_bytes = ((rows - 1) * obs_stride + RQ_POLICY_INPUT_DIM) * sizeof(float);
-        rc = ensure_rows(dev, rows * obs_stride * sizeof(float)); if (rc) return rc;
-        if (dev->rows2_bytes < rows * RQ_ACTION_DIM * sizeof(float)) {
-            RQ_HIP(hipStreamSynchronize(dev->stream));
-            if (dev->rows2) { RQ_HIP(hipFree(dev->rows2)); dev->rows2 = nullptr; dev->rows2_bytes = 0; }
-            RQ_HIP(hipMalloc(&dev->rows2, rows * RQ_ACTION_DIM * sizeof(float)));
-            dev->rows2_bytes = rows * RQ_ACTION_DIM * sizeof(float);
-        }
+        RQ_HIP(dev->rows.reserve(dev->stream, rows * obs_stride));
+        RQ_HIP(dev->rows2.reserve(dev->stream, rows * RQ_ACTION_DIM));
         RQ_HIP(hipMemcpyAsync(dev->rows, observation, obs_bytes, hipMemcpyHostToDevice, dev->stream));
         d_obs = dev->rows; d_act = dev->rows2;
     }

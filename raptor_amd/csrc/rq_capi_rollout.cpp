@@ -9,7 +9,7 @@ int traj_block_to_host(rq_device* dev, const float* d_soa, uint32_t steps, uint3
     const size_t per_step = (size_t)n * dim * sizeof(float);
     uint32_t chunk = (uint32_t)std::min<size_t>(steps, std::max<size_t>(1, ((size_t)1 << 30) / per_step));   // <= 1 GiB scratch
     if (chunk > 65535u) chunk = 65535u;
-    int rc = ensure_rows(dev, per_step * chunk); if (rc) return rc;
+    RQ_HIP(dev->rows.reserve(dev->stream, (size_t)n * dim * chunk));
     for (uint32_t s0 = 0; s0 < steps; s0 += chunk) {
         const uint32_t c = std::min(chunk, steps - s0);
         RQ_HIP(rq::launch_soa_to_rows(dev->stream, d_soa + (size_t)s0 * dim * ld, ld, dim, n, dev->rows, c));
@@ -19,6 +19,41 @@ int traj_block_to_host(rq_device* dev, const float* d_soa, uint32_t steps, uint3
     return RQ_OK;
 }
 
+// `actor`: the caller was given what acts (a policy; a bank and its assignment)
+int rollout_check(RolloutFrame& f, const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,
+                  bool actor, uint32_t n_steps, int mode, uint32_t flags, const rq_trajectory* traj) {
+    int rc = check_env_objects(dev, env, params, state); if (rc) return rc;
+    RQ_REQUIRE(params && state && actor && rng, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(rng->initialized, RQ_ERR_NOT_INITIALIZED, "initialize_rng was not called");
+    RQ_REQUIRE(mode == RQ_ROLLOUT_FUSED || mode == RQ_ROLLOUT_CHAINED, RQ_ERR_INVALID_ARGUMENT, "unknown mode");
+    RQ_REQUIRE((flags & ~(uint32_t)RQ_ROLLOUT_AUTORESET) == 0, RQ_ERR_INVALID_ARGUMENT, "unknown flags");
+    if (traj) {
+        RQ_REQUIRE(traj->env == env, RQ_ERR_SHAPE_MISMATCH, "trajectory belongs to another env");
+        RQ_REQUIRE((uint64_t)traj->length + n_steps <= traj->capacity, RQ_ERR_INVALID_ARGUMENT,
+                   "trajectory buffer too small for this rollout");
+        f.tp = {traj->obs, traj->act, traj->rew, traj->done, traj->length};
+    }
+    return RQ_OK;
+}
+
+int rollout_begin(RolloutFrame& f, rq_device* dev, rq_env* env, rq_state* state, uint32_t n_steps, uint32_t flags, rq_trajectory* traj) {
+    obs_cache_drop_if(dev, env);
+    if (n_steps) { const int rc = state_make_private(state, true); if (rc) return rc; }      // steps the state in place
+    f.b = batch_of(env);
+    f.sc = rq::step_cfg(env->cfg);
+    f.nc = rq::noise_cfg(env->cfg);
+    f.smp = rq::sample_cfg(env->cfg);
+    f.noise = rq::noise_enabled(env->cfg);
+    if (traj && n_steps && !(flags & RQ_ROLLOUT_AUTORESET))   // steps a frozen wave never reaches read as "not stepped"
+        RQ_HIP(hipMemsetAsync(traj->done + (size_t)traj->length * env->ld, 4, (size_t)n_steps * env->ld, dev->stream));
+    return RQ_OK;
+}
+
+void rollout_end(rq_state* state, rq_rng* rng, uint32_t n_steps, rq_trajectory* traj) {
+    rng->epoch += n_steps;
+    if (traj) traj->length += n_steps;
+    if (n_steps) state->version = fresh_version();
+}
 
 }  // namespace rqh
 
@@ -32,46 +67,26 @@ static constexpr size_t kMaxGraphs = 8;       // executable graphs kept per env 
 
 static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy* policy,
                         rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags, rq_trajectory* traj) {
-    int rc = check_env_objects(dev, env, params, state); if (rc) return rc;
-    RQ_REQUIRE(params && state && policy && rng, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RolloutFrame f;
+    int rc = rollout_check(f, dev, env, params, state, rng, policy != nullptr, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(policy->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy lives on another device");
-    RQ_REQUIRE(rng->initialized, RQ_ERR_NOT_INITIALIZED, "initialize_rng was not called");
-    RQ_REQUIRE(mode == RQ_ROLLOUT_FUSED || mode == RQ_ROLLOUT_CHAINED, RQ_ERR_INVALID_ARGUMENT, "unknown mode");
-    RQ_REQUIRE((flags & ~(uint32_t)RQ_ROLLOUT_AUTORESET) == 0, RQ_ERR_INVALID_ARGUMENT, "unknown flags");
-    rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
-    if (traj) {
-        RQ_REQUIRE(traj->env == env, RQ_ERR_SHAPE_MISMATCH, "trajectory belongs to another env");
-        RQ_REQUIRE((uint64_t)traj->length + n_steps <= traj->capacity, RQ_ERR_INVALID_ARGUMENT,
-                   "trajectory buffer too small for this rollout");
-        tp = {traj->obs, traj->act, traj->rew, traj->done, traj->length};
-    }
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = policy_size(policy, env->n); if (rc) return rc;
     RQ_REQUIRE(policy->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy batch does not match the env");
-    obs_cache_drop_if(dev, env);
-    if (n_steps) { rc = state_make_private(state, true); if (rc) return rc; }      // steps the state in place
-    const rq::Batch b = batch_of(env);
-    const rq::StepCfg sc = rq::step_cfg(env->cfg);
-    const rq::NoiseCfg nc = rq::noise_cfg(env->cfg);
-    const rq::SampleCfg smp = rq::sample_cfg(env->cfg);
-    const bool noise = rq::noise_enabled(env->cfg);
-    if (traj && n_steps && !(flags & RQ_ROLLOUT_AUTORESET))   // steps a frozen wave never reaches read as "not stepped"
-        RQ_HIP(hipMemsetAsync(traj->done + (size_t)traj->length * env->ld, 4, (size_t)n_steps * env->ld, dev->stream));
+    rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
+    const rq::TrajPtrs& tp = f.tp;
+    const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
+    const bool noise = f.noise;
     if (mode == RQ_ROLLOUT_FUSED) {
         if (dev->k_timing && n_steps) {                   // one (in, out) record per wave = per workgroup of the fused kernel
             const uint32_t waves = (env->n + 63u) / 64u;
-            if (dev->k_span_waves < waves) {
-                RQ_HIP(hipStreamSynchronize(dev->stream));
-                if (dev->k_span) { RQ_HIP(hipFree(dev->k_span)); dev->k_span = nullptr; dev->k_span_waves = 0; }
-                RQ_HIP(hipMalloc(&dev->k_span, (size_t)waves * 5 * sizeof(unsigned long long)));
-                dev->k_span_waves = waves;
-            }
+            RQ_HIP(dev->k_span.reserve(dev->stream, (size_t)waves * 5));
             dev->k_span_used = waves;
         }
         RQ_HIP(rq::launch_rollout_fused(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
                                         params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
                                         policy->precision, sas_of(policy, rng->epoch, nullptr, env->offset), tp,
-                                        dev->k_timing ? dev->k_span : nullptr));
+                                        dev->k_timing ? dev->k_span.get() : nullptr));
         dev->k_timed = dev->k_timing && n_steps > 0;
         dev->k_fetched = false;
     } else {
@@ -159,9 +174,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
         }
         for (uint32_t t = done_steps; t < n_steps; ++t) RQ_HIP(enqueue_step(rng->epoch + t, nullptr, t));
     }
-    rng->epoch += n_steps;
-    if (traj) traj->length += n_steps;
-    if (n_steps) state->version = fresh_version();
+    rollout_end(state, rng, n_steps, traj);
     return RQ_OK;
 }
 
@@ -189,12 +202,9 @@ RQ_API int rq_trajectory_create(rq_env* env, uint32_t capacity_steps, rq_traject
     RQ_REQUIRE(t, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
     t->env = env; t->ordinal = env->ordinal; t->capacity = capacity_steps;
     const size_t per = (size_t)capacity_steps * env->ld;
-    hipError_t e1 = hipMalloc(&t->obs, per * RQ_POLICY_INPUT_DIM * sizeof(float));
-    hipError_t e2 = hipMalloc(&t->act, per * RQ_ACTION_DIM * sizeof(float));
-    hipError_t e3 = hipMalloc(&t->rew, per * sizeof(float));
-    hipError_t e4 = hipMalloc(&t->done, per);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
-        rq_trajectory_destroy(t);
+    if (t->obs.alloc(per * RQ_POLICY_INPUT_DIM) != hipSuccess || t->act.alloc(per * RQ_ACTION_DIM) != hipSuccess ||
+        t->rew.alloc(per) != hipSuccess || t->done.alloc(per) != hipSuccess) {
+        delete t;
         return fail(RQ_ERR_OUT_OF_MEMORY, "rq_trajectory_create: device allocation failed");
     }
     *out = t;
@@ -204,13 +214,6 @@ RQ_API int rq_trajectory_create(rq_env* env, uint32_t capacity_steps, rq_traject
 RQ_API int rq_trajectory_destroy(rq_trajectory* t) {
     if (!t) return RQ_OK;
     DeviceScope on_device(t->ordinal);
-    if (t->obs) (void)hipFree(t->obs);
-    if (t->act) (void)hipFree(t->act);
-    if (t->rew) (void)hipFree(t->rew);
-    if (t->done) (void)hipFree(t->done);
-    if (t->grad.saved) (void)hipFree(t->grad.saved);
-    if (t->grad.partial) (void)hipFree(t->grad.partial);
-    if (t->grad.rows) (void)hipFree(t->grad.rows);
     delete t;
     return RQ_OK;
 }
@@ -269,15 +272,9 @@ RQ_API int rq_trajectory_relabel(rq_trajectory* t, rq_policy* pol, float* action
     if (t->length == 0) return RQ_OK;
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     rc = policy_size(pol, env->n); if (rc) return rc;
-    const size_t act_bytes = (size_t)t->length * RQ_ACTION_DIM * env->ld * sizeof(float);
     float* d_act = t->act;
     if (!overwrite) {
-        if (dev->rows2_bytes < act_bytes) {
-            RQ_HIP(hipStreamSynchronize(dev->stream));
-            if (dev->rows2) { RQ_HIP(hipFree(dev->rows2)); dev->rows2 = nullptr; dev->rows2_bytes = 0; }
-            RQ_HIP(hipMalloc(&dev->rows2, act_bytes));
-            dev->rows2_bytes = act_bytes;
-        }
+        RQ_HIP(dev->rows2.reserve(dev->stream, (size_t)t->length * RQ_ACTION_DIM * env->ld));
         d_act = dev->rows2;
     }
     RQ_HIP(rq::launch_actor_relabel(dev->stream, env->n, env->ld, t->length, packed_of(pol), t->obs, t->done, pol->hidden,

@@ -4,6 +4,24 @@
 
 using namespace rqh;
 
+// what both constructors refuse
+static int check_bank_args(uint32_t n_teachers, uint32_t in_dim, int hidden_activation, int output_activation) {
+    RQ_REQUIRE(n_teachers > 0, RQ_ERR_INVALID_ARGUMENT, "n_teachers must be positive");
+    RQ_REQUIRE(in_dim >= 1 && in_dim <= RQ_POLICY_INPUT_DIM, RQ_ERR_INVALID_ARGUMENT,
+               "in_dim must be 1..22 (the recorded policy inputs)");
+    RQ_REQUIRE(hidden_activation == RQ_ACT_RELU || hidden_activation == RQ_ACT_TANH, RQ_ERR_INVALID_ARGUMENT,
+               "hidden activation must be RQ_ACT_RELU or RQ_ACT_TANH");
+    RQ_REQUIRE(output_activation == RQ_ACT_IDENTITY || output_activation == RQ_ACT_TANH, RQ_ERR_INVALID_ARGUMENT,
+               "output activation must be RQ_ACT_IDENTITY or RQ_ACT_TANH");
+    return RQ_OK;
+}
+
+// the image, allocated and uploaded
+static hipError_t upload(DeviceBuffer<float>& dst, const std::vector<float>& image) {
+    const hipError_t e = dst.alloc(image.size());
+    return e != hipSuccess ? e : hipMemcpy(dst, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice);
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------------------- Teacher bank
@@ -11,16 +29,10 @@ RQ_API int rq_teacher_bank_create(rq_device* dev, const float* weights, uint32_t
                            uint32_t h2, int hidden_activation, int output_activation, rq_teacher_bank** out) {
     RQ_REQUIRE(dev && weights && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    RQ_REQUIRE(n_teachers > 0, RQ_ERR_INVALID_ARGUMENT, "n_teachers must be positive");
-    RQ_REQUIRE(in_dim >= 1 && in_dim <= RQ_POLICY_INPUT_DIM, RQ_ERR_INVALID_ARGUMENT,
-               "in_dim must be 1..22 (the recorded policy inputs)");
     auto ok_width = [](uint32_t h) { return h == 16 || h == 32 || h == 64; };
     RQ_REQUIRE(ok_width(h1) && ok_width(h2), RQ_ERR_INVALID_ARGUMENT, "hidden widths must be 16, 32 or 64");
-    RQ_REQUIRE(hidden_activation == RQ_ACT_RELU || hidden_activation == RQ_ACT_TANH, RQ_ERR_INVALID_ARGUMENT,
-               "hidden activation must be RQ_ACT_RELU or RQ_ACT_TANH");
-    RQ_REQUIRE(output_activation == RQ_ACT_IDENTITY || output_activation == RQ_ACT_TANH, RQ_ERR_INVALID_ARGUMENT,
-               "output activation must be RQ_ACT_IDENTITY or RQ_ACT_TANH");
-    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    int rc = check_bank_args(n_teachers, in_dim, hidden_activation, output_activation); if (rc) return rc;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rq_teacher_bank* b = new (std::nothrow) rq_teacher_bank();
     RQ_REQUIRE(b, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
     b->dev = dev; b->ordinal = dev->ordinal; b->n_teachers = n_teachers; b->in_dim = in_dim; b->h1 = h1; b->h2 = h2;
@@ -45,14 +57,9 @@ RQ_API int rq_teacher_bank_create(rq_device* dev, const float* weights, uint32_t
             b->f16x2_misfit == UINT32_MAX)
             b->f16x2_misfit = t;
     }
-    hipError_t e1 = hipMalloc(&b->images_f32, img32.size() * sizeof(float));
-    hipError_t e2 = hipMalloc(&b->images_bf16, img16.size() * sizeof(float));
-    if (e1 == hipSuccess) e1 = hipMemcpy(b->images_f32, img32.data(), img32.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e2 == hipSuccess) e2 = hipMemcpy(b->images_bf16, img16.data(), img16.size() * sizeof(float), hipMemcpyHostToDevice);
-    hipError_t e3 = hipMalloc(&b->images_f16x2, img_split.size() * sizeof(float));
-    if (e3 == hipSuccess) e3 = hipMemcpy(b->images_f16x2, img_split.data(), img_split.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-        rq_teacher_bank_destroy(b);
+    if (upload(b->images_f32, img32) != hipSuccess || upload(b->images_bf16, img16) != hipSuccess ||
+        upload(b->images_f16x2, img_split) != hipSuccess) {
+        delete b;
         return fail(RQ_ERR_OUT_OF_MEMORY, "rq_teacher_bank_create: device allocation or upload failed");
     }
     *out = b;
@@ -67,20 +74,14 @@ RQ_API int rq_teacher_bank_create_layers(rq_device* dev, const float* weights, u
     auto fast_width = [](uint32_t h) { return h == 16 || h == 32 || h == 64; };
     if (n_hidden == 2 && fast_width(widths[0]) && fast_width(widths[1]))      // the register-stationary family (three precisions)
         return rq_teacher_bank_create(dev, weights, n_teachers, in_dim, widths[0], widths[1], hidden_activation, output_activation, out);
-    RQ_REQUIRE(n_teachers > 0, RQ_ERR_INVALID_ARGUMENT, "n_teachers must be positive");
-    RQ_REQUIRE(in_dim >= 1 && in_dim <= RQ_POLICY_INPUT_DIM, RQ_ERR_INVALID_ARGUMENT,
-               "in_dim must be 1..22 (the recorded policy inputs)");
     uint32_t widest = 0;
     for (uint32_t l = 0; l < n_hidden; ++l) {
         RQ_REQUIRE(widths[l] >= 16 && widths[l] <= 128 && widths[l] % 16 == 0, RQ_ERR_INVALID_ARGUMENT,
                    "hidden widths must be multiples of 16 from 16 to 128");
         widest = widths[l] > widest ? widths[l] : widest;
     }
-    RQ_REQUIRE(hidden_activation == RQ_ACT_RELU || hidden_activation == RQ_ACT_TANH, RQ_ERR_INVALID_ARGUMENT,
-               "hidden activation must be RQ_ACT_RELU or RQ_ACT_TANH");
-    RQ_REQUIRE(output_activation == RQ_ACT_IDENTITY || output_activation == RQ_ACT_TANH, RQ_ERR_INVALID_ARGUMENT,
-               "output activation must be RQ_ACT_IDENTITY or RQ_ACT_TANH");
-    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    int rc = check_bank_args(n_teachers, in_dim, hidden_activation, output_activation); if (rc) return rc;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rq_teacher_bank* b = new (std::nothrow) rq_teacher_bank();
     RQ_REQUIRE(b, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
     b->dev = dev; b->ordinal = dev->ordinal; b->n_teachers = n_teachers; b->in_dim = in_dim;
@@ -99,10 +100,8 @@ RQ_API int rq_teacher_bank_create_layers(rq_device* dev, const float* weights, u
     }
     for (uint32_t t = 0; t < n_teachers; ++t)
         rq::pack_teacher_layers(weights + per * t, (int)in_dim, (int)n_hidden, widths, (int)b->hp, b->act, b->out_act, img.data() + floats * t);
-    hipError_t e = hipMalloc(&b->images_layers, img.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(b->images_layers, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        rq_teacher_bank_destroy(b);
+    if (upload(b->images_layers, img) != hipSuccess) {
+        delete b;
         return fail(RQ_ERR_OUT_OF_MEMORY, "rq_teacher_bank_create_layers: device allocation or upload failed");
     }
     *out = b;
@@ -112,13 +111,6 @@ RQ_API int rq_teacher_bank_create_layers(rq_device* dev, const float* weights, u
 RQ_API int rq_teacher_bank_destroy(rq_teacher_bank* bank) {
     if (!bank) return RQ_OK;
     DeviceScope on_device(bank->ordinal);
-    if (bank->images_layers) (void)hipFree(bank->images_layers);
-    if (bank->images_f32) (void)hipFree(bank->images_f32);
-    if (bank->images_bf16) (void)hipFree(bank->images_bf16);
-    if (bank->images_f16x2) (void)hipFree(bank->images_f16x2);
-    if (bank->tiles) (void)hipFree(bank->tiles);
-    if (bank->sink) (void)hipFree(bank->sink);
-    if (bank->eval_buf) (void)hipFree(bank->eval_buf);
     delete bank;
     return RQ_OK;
 }
@@ -191,12 +183,7 @@ int bank_tiles(rq_teacher_bank* bank, rq_device* dev, uint64_t key, const uint32
     } catch (const std::bad_alloc&) {
         return fail(RQ_ERR_OUT_OF_MEMORY, "teacher bank: host allocation failed");
     }
-    if (bank->tile_words < host.size()) {
-        RQ_HIP(hipStreamSynchronize(dev->stream));
-        if (bank->tiles) { RQ_HIP(hipFree(bank->tiles)); bank->tiles = nullptr; bank->tile_words = 0; }
-        RQ_HIP(hipMalloc(&bank->tiles, host.size() * sizeof(uint32_t)));
-        bank->tile_words = host.size();
-    }
+    RQ_HIP(bank->tiles.reserve(dev->stream, host.size()));
     RQ_HIP(hipMemcpyAsync(bank->tiles, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, dev->stream));
     RQ_HIP(hipStreamSynchronize(dev->stream));                // `host` is pageable and about to go out of scope
     bank->tiles_valid = true;
@@ -221,16 +208,6 @@ int bank_label(rq_teacher_bank* bank, rq_device* dev, uint32_t n, uint32_t n_til
     return RQ_OK;
 }
 
-// device scratch of the bank: *buf holds at least `floats` floats afterwards
-int bank_scratch(rq_device* dev, float** buf, size_t* have, size_t floats) {
-    if (*have >= floats) return RQ_OK;
-    RQ_HIP(hipStreamSynchronize(dev->stream));
-    if (*buf) { RQ_HIP(hipFree(*buf)); *buf = nullptr; *have = 0; }
-    RQ_HIP(hipMalloc(buf, floats * sizeof(float)));
-    *have = floats;
-    return RQ_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -249,14 +226,9 @@ RQ_API int rq_trajectory_relabel_teachers(rq_trajectory* t, rq_teacher_bank* ban
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     uint32_t n_tiles = 0;
     rc = bank_tiles(bank, dev, env->uid, teacher_id, n, &n_tiles); if (rc) return rc;
-    const size_t act_bytes = (size_t)t->length * RQ_ACTION_DIM * env->ld * sizeof(float);
     float* d_act = t->act;
     if (!overwrite) {
-        if (dev->rows2_bytes < act_bytes) {
-            if (dev->rows2) { RQ_HIP(hipFree(dev->rows2)); dev->rows2 = nullptr; dev->rows2_bytes = 0; }
-            RQ_HIP(hipMalloc(&dev->rows2, act_bytes));
-            dev->rows2_bytes = act_bytes;
-        }
+        RQ_HIP(dev->rows2.reserve(dev->stream, (size_t)t->length * RQ_ACTION_DIM * env->ld));
         d_act = dev->rows2;
     }
     rc = bank_label(bank, dev, n, n_tiles, env->ld, t->length, t->obs, d_act); if (rc) return rc;
@@ -286,8 +258,7 @@ RQ_API int rq_teacher_bank_evaluate(rq_teacher_bank* bank, rq_env* env, const ui
     float* d_act = action ? nullptr : env->act;
     if (observation || action) {
         const size_t rows = observation ? (size_t)batch * obs_stride : 0;
-        rc = bank_scratch(dev, &bank->eval_buf, &bank->eval_floats, rows + (size_t)(RQ_POLICY_INPUT_DIM + RQ_ACTION_DIM) * ld);
-        if (rc) return rc;
+        RQ_HIP(bank->eval_buf.reserve(dev->stream, rows + (size_t)(RQ_POLICY_INPUT_DIM + RQ_ACTION_DIM) * ld));
         if (observation) {
             float* soa = bank->eval_buf + rows;
             RQ_HIP(hipMemcpyAsync(bank->eval_buf, observation, rows * sizeof(float), hipMemcpyHostToDevice, dev->stream));
@@ -307,39 +278,21 @@ RQ_API int rq_teacher_bank_evaluate(rq_teacher_bank* bank, rq_env* env, const ui
 RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
                                const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                rq_trajectory* traj) {
-    int rc = check_env_objects(dev, env, params, state); if (rc) return rc;
-    RQ_REQUIRE(params && state && bank && teacher_id && rng, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RolloutFrame f;
+    int rc = rollout_check(f, dev, env, params, state, rng, bank && teacher_id, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "teacher bank lives on another device");
-    RQ_REQUIRE(rng->initialized, RQ_ERR_NOT_INITIALIZED, "initialize_rng was not called");
-    RQ_REQUIRE(mode == RQ_ROLLOUT_FUSED || mode == RQ_ROLLOUT_CHAINED, RQ_ERR_INVALID_ARGUMENT, "unknown mode");
-    RQ_REQUIRE((flags & ~(uint32_t)RQ_ROLLOUT_AUTORESET) == 0, RQ_ERR_INVALID_ARGUMENT, "unknown flags");
     RQ_REQUIRE(mode != RQ_ROLLOUT_FUSED || (!bank->layers && bank->precision == RQ_POLICY_FP32), RQ_ERR_INVALID_ARGUMENT,
                "the fused teacher rollout runs the fp32 two-hidden-layer {16, 32, 64} family: fly this bank (bf16 / f16x2 precision "
                "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
-    rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
-    if (traj) {
-        RQ_REQUIRE(traj->env == env, RQ_ERR_SHAPE_MISMATCH, "trajectory belongs to another env");
-        RQ_REQUIRE((uint64_t)traj->length + n_steps <= traj->capacity, RQ_ERR_INVALID_ARGUMENT,
-                   "trajectory buffer too small for this rollout");
-        tp = {traj->obs, traj->act, traj->rew, traj->done, traj->length};
-    }
     rc = check_ids(bank, teacher_id, env->n); if (rc) return rc;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     uint32_t n_tiles = 0;
     rc = bank_tiles(bank, dev, env->uid, teacher_id, env->n, &n_tiles); if (rc) return rc;
-    if (mode == RQ_ROLLOUT_CHAINED && n_steps) {
-        rc = bank_scratch(dev, &bank->sink, &bank->sink_floats, RQ_POLICY_NUM_WEIGHTS + (size_t)16 * env->ld);
-        if (rc) return rc;
-    }
-    obs_cache_drop_if(dev, env);
-    if (n_steps) { rc = state_make_private(state, true); if (rc) return rc; }      // steps the state in place
-    const rq::Batch b = batch_of(env);
-    const rq::StepCfg sc = rq::step_cfg(env->cfg);
-    const rq::NoiseCfg nc = rq::noise_cfg(env->cfg);
-    const rq::SampleCfg smp = rq::sample_cfg(env->cfg);
-    const bool noise = rq::noise_enabled(env->cfg);
-    if (traj && n_steps && !(flags & RQ_ROLLOUT_AUTORESET))   // steps a frozen wave never reaches read as "not stepped"
-        RQ_HIP(hipMemsetAsync(traj->done + (size_t)traj->length * env->ld, 4, (size_t)n_steps * env->ld, dev->stream));
+    if (mode == RQ_ROLLOUT_CHAINED && n_steps) RQ_HIP(bank->sink.reserve(dev->stream, RQ_POLICY_NUM_WEIGHTS + (size_t)16 * env->ld));
+    rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
+    const rq::TrajPtrs& tp = f.tp;
+    const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
+    const bool noise = f.noise;
     if (mode == RQ_ROLLOUT_FUSED) {
         rq::TeacherRolloutArgs a{b, sc, nc, smp, rng->seed, rng->epoch, n_steps, noise ? 1u : 0u,
                                  (flags & RQ_ROLLOUT_AUTORESET) ? 1u : 0u, params->d, state->d, env->st, tp,
@@ -364,9 +317,7 @@ RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* par
             }
         }
     }
-    rng->epoch += n_steps;
-    if (traj) traj->length += n_steps;
-    if (n_steps) state->version = fresh_version();
+    rollout_end(state, rng, n_steps, traj);
     return RQ_OK;
 }
 

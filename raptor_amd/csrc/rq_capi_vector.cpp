@@ -83,7 +83,7 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
     // gets another one; stepping a state in place (next_state == state) keeps the contents it is about to read
     rc = state_make_private(next_state, next_state == state); if (rc) return rc;
     if (cache_obs && !env->obs_alt) {
-        RQ_HIP(hipMalloc(&env->obs_alt, (size_t)RQ_OBSERVATION_DIM * env->ld * sizeof(float)));
+        RQ_HIP(env->obs_alt.alloc((size_t)RQ_OBSERVATION_DIM * env->ld));
         RQ_HIP(hipMemsetAsync(env->obs_alt, 0, (size_t)RQ_OBSERVATION_DIM * env->ld * sizeof(float), dev->stream));
     }
     rq::Mailbox mb{};

@@ -22,6 +22,7 @@
 
 #include "../../include/raptor_quad.h"
 #include "rq_host.hpp"
+#include "rq_memory.hpp"
 
 namespace {
 
@@ -96,26 +97,12 @@ struct rq_comm {
     NcclComm comm = nullptr;
     hipStream_t side = nullptr;
     uint32_t count = 0;                   // envs per rank of the buffers below (sized on first use)
-    float* send[2] = {nullptr, nullptr};  // [count]
-    float* recv[2] = {nullptr, nullptr};  // [n_ranks * count]
+    rq::DeviceBuffer<float> send[2];      // [count]
+    rq::DeviceBuffer<float> recv[2];      // [n_ranks * count]
     hipEvent_t ready[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
     bool pending[2] = {false, false};
     uint64_t posts = 0;
 };
-
-namespace {
-
-void comm_free_buffers(rq_comm* c) {
-    for (int j = 0; j < 2; ++j) {
-        if (c->send[j]) (void)hipFree(c->send[j]);
-        if (c->recv[j]) (void)hipFree(c->recv[j]);
-        c->send[j] = c->recv[j] = nullptr;
-        c->pending[j] = false;
-    }
-    c->count = 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -174,7 +161,6 @@ RQ_API int rq_comm_destroy(rq_comm* c) {
     rq::DeviceScope on_device(c->ordinal);
     if (c->side) (void)hipStreamSynchronize(c->side);
     if (c->comm) (void)rccl()->comm_destroy(c->comm);
-    comm_free_buffers(c);
     for (int j = 0; j < 2; ++j) {
         if (c->ready[j]) (void)hipEventDestroy(c->ready[j]);
         if (c->done[j]) (void)hipEventDestroy(c->done[j]);
@@ -229,10 +215,11 @@ RQ_API int rq_allgather_returns(rq_env* env, rq_comm* c) {
     if (c->count != n) {        // (re)size: every rank must pass envs of the same size (equal shards)
         RQ_HIP(hipStreamSynchronize(c->side));
         RQ_HIP(hipStreamSynchronize(engine));
-        comm_free_buffers(c);
+        c->count = 0;           // not sized, should an allocation below fail
         for (int j = 0; j < 2; ++j) {
-            RQ_HIP(hipMalloc(&c->send[j], (size_t)n * sizeof(float)));
-            RQ_HIP(hipMalloc(&c->recv[j], (size_t)n * c->n_ranks * sizeof(float)));
+            c->send[j].reset(); c->recv[j].reset(); c->pending[j] = false;
+            RQ_HIP(c->send[j].alloc(n));
+            RQ_HIP(c->recv[j].alloc((size_t)n * c->n_ranks));
         }
         c->count = n;
     }
@@ -244,7 +231,7 @@ RQ_API int rq_allgather_returns(rq_env* env, rq_comm* c) {
     RQ_HIP(hipMemcpyAsync(c->send[j], rq::env_finished_returns(env), (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, engine));
     RQ_HIP(hipEventRecord(c->ready[j], engine));
     RQ_HIP(hipStreamWaitEvent(c->side, c->ready[j], 0));
-    const int nrc = rccl()->all_gather(c->send[j], c->recv[j], n, /*ncclFloat32*/ 7, c->comm, c->side);
+    const int nrc = rccl()->all_gather(c->send[j].get(), c->recv[j].get(), n, /*ncclFloat32*/ 7, c->comm, c->side);
     if (nrc != 0) return rq::fail(RQ_ERR_HIP, std::string("rq_allgather_returns: ") + nccl_message(nrc));
     RQ_HIP(hipEventRecord(c->done[j], c->side));
     c->pending[j] = true;

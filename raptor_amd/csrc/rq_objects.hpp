@@ -8,6 +8,9 @@
 //   rq_capi_policy.cpp   Raptor: create / configure / reset / evaluate_step / evaluate_sequence / selftest
 //   rq_capi_rollout.cpp  the loop body x K on the device (fused, or chained under a hipGraph), trajectories, relabelling with a policy
 //   rq_capi_teacher.cpp  the teacher bank
+//   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory
+//   rq_memory.hpp        rq::DeviceBuffer / rq::PinnedBuffer: every object below owns its device and pinned memory through them
+// rollout_check / rollout_begin / rollout_end (rq_capi_rollout.cpp) are the frame rq_rollout* and rq_rollout_teachers share.
 // Helpers live in namespace rqh (each .cpp says `using namespace rqh;`); nothing here is visible outside libraptor_quad.so.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -31,9 +34,12 @@
 #include "rq_kernels.hpp"
 
 #include "rq_host.hpp"
+#include "rq_memory.hpp"
 
 using rq::fail;
 using rq::DeviceScope;
+using rq::DeviceBuffer;
+using rq::PinnedBuffer;
 
 inline uint32_t round_up64(uint32_t n) { return (n + 63u) & ~63u; }
 
@@ -90,8 +96,9 @@ struct ResidentExecutor {
     uint64_t idle_ticks = 0, life_ticks = 0, host_idle_ns = 0, host_life_ns = 0;
     // memory (rq_resident.cpp ResidentWord)
     hipStream_t stream = nullptr;
-    uint32_t* mem = nullptr;             // pinned: the command line, what the kernel says as it leaves, its timing, the rows
-    uint32_t* cmd = nullptr;             // where commands are written: mem, or - on a large-BAR platform - fine-grained device memory
+    PinnedBuffer<uint32_t> mem;          // the command line, what the kernel says as it leaves, its timing, the rows
+    DeviceBuffer<uint32_t> cmd_dev;      // on a large-BAR platform: fine-grained device memory for the commands
+    uint32_t* cmd = nullptr;             // where commands are written: mem or cmd_dev
     bool cmd_on_device = false;
     // the kernel
     bool running = false;
@@ -112,10 +119,10 @@ struct ResidentExecutor {
 // ---- the small-batch loop (rq_small_batch.cpp).  Mailbox (rq::Mailbox): below kGpuLayoutMinEnvs envs rows cross the boundary in pinned
 // host memory the kernels read and write themselves, and the host waits on a flag instead of the stream.
 struct HostMailbox {
-    uint32_t* flag = nullptr;      // pinned host: sequence number of the last finished mailbox launch
-    uint32_t* counter = nullptr;   // device: workgroup counter of the launch in flight
-    float* in = nullptr, *out = nullptr;     // pinned host rows read by kernels (observations / actions), rows written by kernels
-    float* obs = nullptr, *act = nullptr;    // pinned host rows of the observation cache [n][RQ_OBSERVATION_DIM], of the speculated action [n][4]
+    PinnedBuffer<uint32_t> flag;     // sequence number of the last finished mailbox launch
+    DeviceBuffer<uint32_t> counter;  // workgroup counter of the launch in flight
+    PinnedBuffer<float> in, out;     // rows read by kernels (observations / actions), rows written by kernels
+    PinnedBuffer<float> obs, act;    // rows of the observation cache [n][RQ_OBSERVATION_DIM], of the speculated action [n][4]
     uint32_t seq = 0, in_busy = 0;     // the last sequence number handed to a launch; that of the last launch that reads `in`
 };
 enum class MbOut { none, out, obs, act };     // which pinned rows a mailbox launch writes
@@ -150,9 +157,9 @@ struct rq_device {
     int ordinal = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    unsigned long long* k_span = nullptr;        // device [k_span_waves][4]: per wave, in / out / loop begin / loop end ticks of the last timed fused rollout;
+    DeviceBuffer<unsigned long long> k_span;     // [waves][4]: per wave, in / out / loop begin / loop end ticks of the last timed fused rollout;
                                                  // behind the [k_span_used][4] in use: [k_span_used] core-clock cycles of the waves' steps
-    uint32_t k_span_waves = 0, k_span_used = 0;
+    uint32_t k_span_used = 0;
     std::vector<unsigned long long> k_host;      // the records of the last timed rollout on the host (fetched once per launch)
     bool k_fetched = false;
     double k_ticks_per_ms = 1e5;                 // wall clock rate (100 MHz on gfx950)
@@ -160,14 +167,10 @@ struct rq_device {
     uint32_t graph_fallbacks = 0;  // chained rollouts whose hipGraph capture was invalidated from outside and that went out as plain launches
     bool k_timing = false;         // rq_device_set_rollout_timing
     bool k_timed = false;          // a launch carried the two events
-    void* staging = nullptr;       // pinned host buffer for transposing device -> host copies
-    float* rows = nullptr;         // device scratch, row-major side of the GPU layout changes (large batches)
-    size_t rows_bytes = 0;
-    float* rows2 = nullptr;        // second device scratch (sequence evaluation: actions)
-    size_t rows2_bytes = 0;
-    size_t staging_bytes = 0;
-    void* staging_in = nullptr;    // pinned host buffer for host -> device copies (asynchronous)
-    size_t staging_in_bytes = 0;
+    PinnedBuffer<float> staging;   // for transposing device -> host copies
+    DeviceBuffer<float> rows;      // scratch, row-major side of the GPU layout changes (large batches)
+    DeviceBuffer<float> rows2;     // second scratch (sequence evaluation, relabelling: actions)
+    PinnedBuffer<float> staging_in;    // for host -> device copies (asynchronous)
     hipEvent_t ev_h2d = nullptr;   // recorded after the last copy out of staging_in
     bool h2d_pending = false;
     HostMailbox mailbox;
@@ -195,10 +198,10 @@ struct rq_env {
     uint64_t offset = 0;
     rq_env_config cfg{};
     bool initialized = false;
-    float* obs = nullptr;       // [RQ_OBSERVATION_DIM][ld]
-    float* act = nullptr;       // [RQ_ACTION_DIM][ld]
-    void* stats_block = nullptr;
-    rq::StatsPtrs st{};
+    DeviceBuffer<float> obs;    // [RQ_OBSERVATION_DIM][ld]
+    DeviceBuffer<float> act;    // [RQ_ACTION_DIM][ld]
+    DeviceBuffer<char> stats_block;
+    rq::StatsPtrs st{};         // views into stats_block
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
     // epoch-counter bump); one executable graph per distinct argument set
     struct GraphEntry {
@@ -208,16 +211,16 @@ struct rq_env {
         hipGraphExec_t exec;
     };
     std::vector<GraphEntry> graphs;
-    uint32_t* epoch_dev = nullptr;   // device-side noise epoch read by the graph's observe nodes
+    DeviceBuffer<uint32_t> epoch_dev;    // device-side noise epoch read by the graph's observe nodes
     bool obs_exposed = false;        // rq_env_observation_device_ptr was called: the caller may write the buffer (no observation cache)
     std::vector<float*> state_pool;  // state buffers [RQ_STATE_DIM][ld] no rq_state holds at the moment (copy-on-write assign)
-    float* obs_alt = nullptr;        // [RQ_OBSERVATION_DIM][ld]: where k_step leaves the observation of the state it wrote; a cached
+    DeviceBuffer<float> obs_alt;     // [RQ_OBSERVATION_DIM][ld]: where k_step leaves the observation of the state it wrote; a cached
                                      // observe() swaps it with `obs` (the env's observation buffer changes on observe only)
 };
 
 // version: bumped by every library call that writes the buffer; exposed: the raw device pointer was handed out, the
 // library no longer knows when it is written (the observation cache then never applies)
-struct rq_params { rq_env* env = nullptr; int ordinal = 0; float* d = nullptr; uint64_t version = fresh_version(); bool exposed = false; };
+struct rq_params { rq_env* env = nullptr; int ordinal = 0; DeviceBuffer<float> d; uint64_t version = fresh_version(); bool exposed = false; };
 // rq_state buffers are copy-on-write (round 3): state.assign(next_state) makes the two objects SHARE one buffer, and the
 // next call that overwrites one of them (the following step writes next_state in full) gives it a fresh buffer from the
 // env's pool instead - the README loop's assign costs no copy command.  `refs` counts the objects on a buffer.
@@ -228,18 +231,15 @@ struct rq_trajectory {
     rq_env* env = nullptr;
     int ordinal = 0;
     uint32_t capacity = 0, length = 0;
-    float* obs = nullptr;    // [capacity][22][ld]
-    float* act = nullptr;    // [capacity][4][ld]
-    float* rew = nullptr;    // [capacity][ld]
-    uint8_t* done = nullptr; // [capacity][ld]
+    DeviceBuffer<float> obs;     // [capacity][22][ld]
+    DeviceBuffer<float> act;     // [capacity][4][ld]
+    DeviceBuffer<float> rew;     // [capacity][ld]
+    DeviceBuffer<uint8_t> done;  // [capacity][ld]
     // the learner's workspace (rq_capi_grad.cpp): what the last rq_trajectory_policy_forward saved for the backward, and by whom
     struct Grad {
-        float* saved = nullptr;        // [length][16][ld]: the state entering each step
-        size_t saved_bytes = 0;
-        float* partial = nullptr;      // [waves][2084]: per-wave partial gradients
-        size_t partial_bytes = 0;
-        float* rows = nullptr;         // host-memory calls: the device side of the caller's arrays
-        size_t rows_bytes = 0;
+        DeviceBuffer<float> saved;     // [length][16][ld]: the state entering each step
+        DeviceBuffer<float> partial;   // [waves][2084]: per-wave partial gradients
+        DeviceBuffer<float> rows;      // host-memory calls: the device side of the caller's arrays
         bool valid = false;            // a forward ran and nothing it read has changed since (rq_trajectory_reset clears it)
         const rq_policy* policy = nullptr;
         uint64_t weight_version = 0;   // rq_policy::weight_version at the forward
@@ -251,10 +251,10 @@ struct rq_trajectory {
 struct rq_policy {
     rq_device* dev = nullptr;
     int ordinal = 0;
-    float* w_dev = nullptr;       // raw parameters (checkpoint order)
-    float* w_packed = nullptr;    // f32 MFMA operand image, rq::RQ_PACKED_FLOATS floats
-    float* w_packed_bf16 = nullptr;   // bf16 MFMA operand image, rq::RQ_PACKED_BF16_FLOATS floats
-    float* w_packed_f16x2 = nullptr;  // split-f16 MFMA operand image, rq::RQ_PACKED_F16X2_FLOATS floats
+    DeviceBuffer<float> w_dev;           // raw parameters (checkpoint order)
+    DeviceBuffer<float> w_packed;        // f32 MFMA operand image, rq::RQ_PACKED_FLOATS floats
+    DeviceBuffer<float> w_packed_bf16;   // bf16 MFMA operand image, rq::RQ_PACKED_BF16_FLOATS floats
+    DeviceBuffer<float> w_packed_f16x2;  // split-f16 MFMA operand image, rq::RQ_PACKED_F16X2_FLOATS floats
     float w_host[RQ_POLICY_NUM_WEIGHTS];      // as loaded (checkpoint order)
     float w_eff[RQ_POLICY_NUM_WEIGHTS];       // with the optional Standardize stage folded into layer_0
     bool standardize = false;
@@ -262,18 +262,18 @@ struct rq_policy {
     int sas_mode = RQ_SAS_OFF;        // SampleAndSquash output stage
     uint64_t sas_seed = 0;
     uint32_t sas_counter = 0;         // sampling step of the next rq_policy_evaluate_step call
-    float* ls_image = nullptr;        // device: rq::RQ_LOGSTD_FLOATS (log-std head operands), allocated on first use
+    DeviceBuffer<float> ls_image;     // rq::RQ_LOGSTD_FLOATS (log-std head operands), allocated on first use
     int precision = RQ_POLICY_FP32;
     uint32_t batch = 0, ld = 0;   // 0 = not sized yet
     bool needs_reset = true;      // hidden must be (re)filled with initial_hidden_state before use
-    float* hidden = nullptr;      // [16][ld]
-    float* hidden_alt = nullptr;  // [16][ld]: where a speculative step leaves the next hidden state (swapped in on a hit)
+    DeviceBuffer<float> hidden;      // [16][ld]
+    DeviceBuffer<float> hidden_alt;  // [16][ld]: where a speculative step leaves the next hidden state (swapped in on a hit)
     uint64_t version = fresh_version();   // renewed by every call that reads-and-writes or reconfigures the policy's state
     uint64_t weight_version = fresh_version();   // renewed whenever the parameters are (re)uploaded: create, set_standardize, set_weights
-    float* w_packed_grad = nullptr;   // the learner's transposed image, rq::RQ_PACKED_GRAD_FLOATS floats (allocated on first use)
+    DeviceBuffer<float> w_packed_grad;    // the learner's transposed image, rq::RQ_PACKED_GRAD_FLOATS floats (allocated on first use)
     uint64_t grad_image_version = 0;  // the weight_version w_packed_grad was packed from
-    float* obs = nullptr;         // [22][ld] staging for host observations
-    float* act = nullptr;         // [4][ld]
+    DeviceBuffer<float> obs;      // [22][ld] staging for host observations
+    DeviceBuffer<float> act;      // [4][ld]
 };
 
 struct rq_teacher_bank {
@@ -282,16 +282,15 @@ struct rq_teacher_bank {
     uint32_t n_teachers = 0, in_dim = 0, h1 = 0, h2 = 0;
     int act = RQ_ACT_RELU, out_act = RQ_ACT_IDENTITY;
     int precision = RQ_POLICY_FP32;
-    float* images_f32 = nullptr;     // [n_teachers][teacher_image_regs_f32 * 64]
-    float* images_bf16 = nullptr;    // [n_teachers][teacher_image_regs_bf16 * 64]
-    float* images_f16x2 = nullptr;   // [n_teachers][teacher_image_regs_f16x2 * 64]
+    DeviceBuffer<float> images_f32;      // [n_teachers][teacher_image_regs_f32 * 64]
+    DeviceBuffer<float> images_bf16;     // [n_teachers][teacher_image_regs_bf16 * 64]
+    DeviceBuffer<float> images_f16x2;    // [n_teachers][teacher_image_regs_f16x2 * 64]
     uint32_t f16x2_misfit = UINT32_MAX;  // the first teacher with a weight the f16x2 image cannot hold (set_precision refuses it)
-    uint32_t* tiles = nullptr;       // device: tile_teacher [tiles] followed by tile_env [tiles][16]; dense stacks: teacher_start | sorted_env
-    size_t tile_words = 0;           // its capacity in 32-bit words
+    DeviceBuffer<uint32_t> tiles;    // tile_teacher [tiles] followed by tile_env [tiles][16]; dense stacks: teacher_start | sorted_env
     // the generic dense stack (rq_teacher_bank_create_layers outside the register-stationary family): fp32, operands streamed
     bool layers = false;
     uint32_t n_hidden = 2, widths[3] = {0, 0, 0}, hp = 0;
-    float* images_layers = nullptr;  // [n_teachers][teacher_layers_image_floats(hp, n_hidden)]
+    DeviceBuffer<float> images_layers;   // [n_teachers][teacher_layers_image_floats(hp, n_hidden)]
     // what `tiles` holds (rq_capi_teacher.cpp bank_tiles): the list built from tiles_ids for tiles_key (the env's uid, 0 = host rows)
     // - a loop of rollout chunks or relabels with one assignment uploads it once
     bool tiles_valid = false;
@@ -299,11 +298,9 @@ struct rq_teacher_bank {
     uint32_t tiles_count = 0;
     std::vector<uint32_t> tiles_ids;
     // teacher rollouts, chained mode: k_step's policy-state reset needs a [16][ld] target and a weight block (a teacher has no state)
-    float* sink = nullptr;
-    size_t sink_floats = 0;
+    DeviceBuffer<float> sink;
     // rq_teacher_bank_evaluate from host rows: [batch][stride] rows | [22][ld] observation | [4][ld] actions
-    float* eval_buf = nullptr;
-    size_t eval_floats = 0;
+    DeviceBuffer<float> eval_buf;
 };
 
 
@@ -319,8 +316,6 @@ namespace rqh {
 // policy is followed only while it is in here
 bool device_registry(const void* dev, int op);
 bool policy_registry(const void* pol, int op);
-int ensure_staging(rq_device* dev, size_t bytes);
-int ensure_rows(rq_device* dev, size_t bytes);
 int soa_to_host(rq_device* dev, const float* d_soa, uint32_t n, uint32_t ld, uint32_t dim, float* host);
 int host_to_soa(rq_device* dev, const float* host, uint32_t n, uint32_t stride, uint32_t ld, uint32_t dim, float* d_soa);
 int check_env_objects(const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state);
@@ -332,7 +327,6 @@ inline rq::Batch batch_of(const rq_env* env) { return {env->n, env->ld, env->off
 // ---- rq_small_batch.cpp: the small-batch loop (rq_device::mailbox, obs_cache, spec) ----
 void small_batch_setup(rq_device* dev);      // rq_device_create: settings
 int ensure_mailbox(rq_device* dev);
-void mailbox_free(rq_device* dev);
 int mailbox_wait(rq_device* dev, uint32_t seq);
 int mailbox_copy_out(rq_device* dev, uint32_t seq, const float* rows, float* dst, size_t floats);
 int mailbox_put_in(rq_device* dev, const float* rows, uint32_t n, uint32_t dim, size_t stride);
@@ -364,13 +358,24 @@ void resident_post(rq_device* dev, const PolicyCmd& p);
 int resident_drain(rq_device* dev);
 
 // ---- rq_capi_policy.cpp ----
-void policy_free_buffers(rq_policy* pol);
 int mode_of(const rq_policy* pol);       // precision in bits 0-7, bit 8 = tanh on the output (what the sequence / relabel launchers take)
 rq::SasArgs sas_of(const rq_policy* pol, uint32_t epoch, const uint32_t* epoch_base, uint64_t env_offset);
 const float* packed_of(const rq_policy* pol);
 int policy_size(rq_policy* pol, uint32_t batch);
 
 // ---- rq_capi_rollout.cpp ----
+// What a rollout of either kind (a policy's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope: the checks
+// both make, and where a recording goes.  rollout_begin, inside it and after what is the caller's own (policy sizing; tile list and
+// sink): the observation cache dropped, the state private, the env's configuration as the kernels take it, the `done` rows preset.
+// rollout_end: the noise epoch, the recording's length and the state's version move on.
+struct RolloutFrame {
+    rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
+    rq::Batch b; rq::StepCfg sc; rq::NoiseCfg nc; rq::SampleCfg smp; bool noise;
+};
+int rollout_check(RolloutFrame& f, const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,
+                  bool actor, uint32_t n_steps, int mode, uint32_t flags, const rq_trajectory* traj);
+int rollout_begin(RolloutFrame& f, rq_device* dev, rq_env* env, rq_state* state, uint32_t n_steps, uint32_t flags, rq_trajectory* traj);
+void rollout_end(rq_state* state, rq_rng* rng, uint32_t n_steps, rq_trajectory* traj);
 int traj_block_to_host(rq_device* dev, const float* d_soa, uint32_t steps, uint32_t n, uint32_t ld, uint32_t dim, float* host);
 
 template <typename T>

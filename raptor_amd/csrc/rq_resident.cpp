@@ -42,12 +42,11 @@ uint64_t host_now_ns() {
 static int ensure_memory(rq_device* dev) {
     ResidentExecutor& rx = dev->resident;
     if (rx.mem) return RQ_OK;
-    void* mem = nullptr;
-    RQ_HIP(hipHostMalloc(&mem, kResMemBytes, hipHostMallocDefault));
-    std::memset(mem, 0, kResMemBytes);
-    const hipError_t e = hipStreamCreateWithFlags(&rx.stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { (void)hipHostFree(mem); RQ_HIP(e); }
-    rx.mem = static_cast<uint32_t*>(mem);
+    PinnedBuffer<uint32_t> mem;
+    RQ_HIP(mem.alloc(kResMemBytes / sizeof(uint32_t)));
+    std::memset(mem.get(), 0, kResMemBytes);
+    RQ_HIP(hipStreamCreateWithFlags(&rx.stream, hipStreamNonBlocking));
+    rx.mem = std::move(mem);
     rx.cmd = rx.mem;
     // Where the wave looks for its commands.  Pinned host memory works everywhere: every poll is a read across PCIe, and a command is
     // seen ~1.7 us after it was written.  Where the platform maps VRAM for the CPU (large BAR) the command line lives in fine-grained
@@ -62,7 +61,8 @@ static int ensure_memory(rq_device* dev) {
             __m128i* z = static_cast<__m128i*>(fine);
             for (size_t k = 0; k < kResCmdBytes / sizeof(__m128i); ++k) _mm_store_si128(z + k, _mm_setzero_si128());
             _mm_sfence();
-            rx.cmd = static_cast<uint32_t*>(fine);
+            rx.cmd_dev.adopt(static_cast<uint32_t*>(fine), kResCmdBytes / sizeof(uint32_t));
+            rx.cmd = rx.cmd_dev;
             rx.cmd_on_device = true;
         }
         (void)hipGetLastError();
@@ -85,11 +85,8 @@ void resident_setup(rq_device* dev) {
 }
 
 void resident_teardown(rq_device* dev) {
-    ResidentExecutor& rx = dev->resident;
     (void)resident_retire(dev);
-    if (rx.stream) (void)hipStreamDestroy(rx.stream);
-    if (rx.cmd_on_device && rx.cmd) (void)hipFree(rx.cmd);
-    if (rx.mem) (void)hipHostFree(rx.mem);
+    if (dev->resident.stream) (void)hipStreamDestroy(dev->resident.stream);
 }
 
 bool resident_left(const rq_device* dev) { return __atomic_load_n(&dev->resident.mem[kRwExited], __ATOMIC_ACQUIRE) == dev->resident.launch_id; }
@@ -117,7 +114,7 @@ int resident_gone(rq_device* dev) {
     }
     if (rx.pending) {
         rx.pending = false;
-        const uint32_t f = __atomic_load_n(dev->mailbox.flag, __ATOMIC_ACQUIRE);
+        const uint32_t f = __atomic_load_n(dev->mailbox.flag.get(), __ATOMIC_ACQUIRE);
         if ((int32_t)(f - rx.pending_last) < 0) {
             RQ_REQUIRE((int32_t)(f - rx.pending_first) < 0, RQ_ERR_HIP, "the resident executor left in the middle of a command");
             ++rx.replays;
@@ -306,7 +303,7 @@ RQ_API int rq_device_get_resident(const rq_device* dev, int* enabled, int* runni
 
 RQ_API int rq_device_get_resident_timing(const rq_device* dev, uint64_t* ticks6) {
     RQ_REQUIRE(dev && ticks6, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    RQ_REQUIRE(dev->resident.mem, RQ_ERR_NOT_INITIALIZED, "no resident executor has run on this device");
+    RQ_REQUIRE(!dev->resident.mem.empty(), RQ_ERR_NOT_INITIALIZED, "no resident executor has run on this device");
     std::memcpy(ticks6, dev->resident.mem + kRwTiming, 6 * sizeof(uint64_t));
     return RQ_OK;
 }

@@ -11,23 +11,16 @@ constexpr size_t kMailboxRowFloats = (size_t)(kGpuLayoutMinEnvs - 1) * 32;
 int ensure_mailbox(rq_device* dev) {
     HostMailbox& m = dev->mailbox;
     if (m.flag) return RQ_OK;
-    RQ_HIP(hipHostMalloc(&m.flag, 64, hipHostMallocDefault));
-    *static_cast<volatile uint32_t*>(m.flag) = 0;
-    hipError_t e = hipHostMalloc(&m.in, kMailboxRowFloats * sizeof(float), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&m.out, kMailboxRowFloats * sizeof(float), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&m.counter, sizeof(uint32_t));
+    RQ_HIP(m.flag.alloc(16));
+    *static_cast<volatile uint32_t*>(m.flag.get()) = 0;
+    hipError_t e = m.in.alloc(kMailboxRowFloats);
+    if (e == hipSuccess) e = m.out.alloc(kMailboxRowFloats);
+    if (e == hipSuccess) e = m.counter.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(m.counter, 0, sizeof(uint32_t), dev->stream);
-    if (e == hipSuccess) e = hipHostMalloc(&m.obs, kMailboxRowFloats * sizeof(float), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&m.act, (size_t)kGpuLayoutMinEnvs * RQ_ACTION_DIM * sizeof(float), hipHostMallocDefault);
-    if (e != hipSuccess) { mailbox_free(dev); return fail(RQ_ERR_OUT_OF_MEMORY, "ensure_mailbox: pinned host allocation failed"); }
+    if (e == hipSuccess) e = m.obs.alloc(kMailboxRowFloats);
+    if (e == hipSuccess) e = m.act.alloc((size_t)kGpuLayoutMinEnvs * RQ_ACTION_DIM);
+    if (e != hipSuccess) { m = HostMailbox{}; return fail(RQ_ERR_OUT_OF_MEMORY, "ensure_mailbox: pinned host allocation failed"); }
     return RQ_OK;
-}
-
-void mailbox_free(rq_device* dev) {
-    HostMailbox& m = dev->mailbox;
-    for (void* p : {(void*)m.flag, (void*)m.in, (void*)m.out, (void*)m.obs, (void*)m.act}) if (p) (void)hipHostFree(p);
-    if (m.counter) (void)hipFree(m.counter);
-    m = HostMailbox{};
 }
 
 // spin until the launch with sequence number seq (or a later one: launches finish in stream order) signalled.  While the
@@ -36,7 +29,7 @@ void mailbox_free(rq_device* dev) {
 int mailbox_wait(rq_device* dev, uint32_t seq) {
     const ResidentExecutor& rx = dev->resident;
     for (uint64_t spins = 1;; ++spins) {
-        const uint32_t f = __atomic_load_n(dev->mailbox.flag, __ATOMIC_ACQUIRE);
+        const uint32_t f = __atomic_load_n(dev->mailbox.flag.get(), __ATOMIC_ACQUIRE);
         if ((int32_t)(f - seq) >= 0) return RQ_OK;
         if (rx.running && (spins & 0xFFu) == 0 && resident_left(dev)) {
             const int rc = resident_gone(dev); if (rc) return rc;
@@ -46,7 +39,7 @@ int mailbox_wait(rq_device* dev, uint32_t seq) {
             const hipError_t q = hipStreamQuery(rx.running ? rx.stream : dev->stream);
             if (q == hipSuccess) {
                 if (rx.running) { const int rc = resident_gone(dev); if (rc) return rc; continue; }
-                const uint32_t g = __atomic_load_n(dev->mailbox.flag, __ATOMIC_ACQUIRE);
+                const uint32_t g = __atomic_load_n(dev->mailbox.flag.get(), __ATOMIC_ACQUIRE);
                 if ((int32_t)(g - seq) >= 0) return RQ_OK;
                 return fail(RQ_ERR_HIP, "mailbox_wait: the stream drained without the kernel signalling");
             }
@@ -121,7 +114,7 @@ bool obs_cache_holds(const rq_device* dev, const rq_env* env, const rq_params* p
 // a hit: obs_alt holds the observation on the device (swapped in here), the cache's rows for the host (once its launch's flag is set)
 int obs_cache_read(rq_device* dev, rq_env* env, float* observation) {
     ObservationCache& oc = dev->obs_cache;
-    if (oc.in_alt) { std::swap(env->obs, env->obs_alt); oc.in_alt = false; }
+    if (oc.in_alt) { env->obs.swap(env->obs_alt); oc.in_alt = false; }
     return observation ? mailbox_copy_out(dev, oc.seq, dev->mailbox.obs, observation, (size_t)env->n * RQ_OBSERVATION_DIM) : RQ_OK;
 }
 
@@ -182,7 +175,7 @@ int speculation_take(rq_device* dev, rq_policy* pol, const float* observation, u
     if (sp.policy == pol && sp.policy_version == pol->version && sp.batch == batch && speculation_current(dev) &&
         mailbox_wait(dev, oc.seq) == RQ_OK && rows_match(dev, observation, batch, obs_stride)) {
         const int rc = mailbox_copy_out(dev, sp.seq, dev->mailbox.act, action, (size_t)batch * RQ_ACTION_DIM); if (rc) return rc;
-        std::swap(pol->hidden, pol->hidden_alt);       // the speculated step becomes the policy's state
+        pol->hidden.swap(pol->hidden_alt);             // the speculated step becomes the policy's state
         pol->version = fresh_version();
         sp.policy = nullptr; sp.last_policy = pol; sp.outstanding = false; sp.misses = 0;
         *hit = true; return RQ_OK;

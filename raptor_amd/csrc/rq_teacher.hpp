@@ -1,6 +1,6 @@
-// rq_teacher.hpp - the register-stationary teacher's layers as device code shared by the two kernels that run them:
-//   rq_teacher.hip          k_teacher_relabel_f32: a teacher over a recorded trajectory (the relabel pass, T steps per wave)
-//   rq_teacher_rollout.hip  k_rollout_teachers:    a teacher flying its env (the closed loop of README.md:95-99)
+// rq_teacher.hpp - the register-stationary teacher's layers as device code shared by the two kernels of rq_teacher.hip that run them:
+//   k_teacher_relabel_f32: a teacher over a recorded trajectory (the relabel pass, T steps per wave)
+//   k_rollout_teachers:    a teacher flying its env (the closed loop of README.md:95-99)
 // The input plan (bias constant at K slot in_dim) and the activations are shared as they are.  TeacherF32 below is the MFMA chain of
 // k_teacher_relabel_f32 - same K order, same accumulator seeds - as functions; the relabel kernel keeps its own text of it because
 // routed through these functions its scheduling moves (24 - 36 of the unit's 116 listings change: rq_teacher.hip is unchanged code).
