@@ -3,10 +3,12 @@
 label the recorded observations with a bank of MLP teachers, take K Adam steps on the MSE between the student's actions over the
 recording and the labels (masked by done != 4), push the new weights into the student, collect again.
 
-Forward and backward over the recording are HIP launches of the engine (raptor_amd.training.trajectory_actions); the optimiser is
-torch's; only the 8 KB weight vector crosses to the host per update.
+The K updates of a collection are ONE call (raptor_amd.training.Distiller.step): forward, loss-seeded backward, Adam and the rebuilt
+operand images are HIP launches enqueued back to back, and nothing of the recording's size or the weights visits the host.
+--torch-optimizer keeps the earlier loop instead - trajectory_actions + masked_mse + torch.optim.Adam + set_weights, the way any
+other loss than the masked MSE still goes - and prints the same lines.
 
-    python examples/distill.py [--envs 16384] [--steps 100] [--epochs 3] [--adam-steps 10] [--lr 1e-3]
+    python examples/distill.py [--envs 16384] [--steps 100] [--epochs 3] [--adam-steps 10] [--lr 1e-3] [--torch-optimizer]
 """
 import argparse
 import os
@@ -20,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import raptor_amd.l2f as l2f                       # noqa: E402
 from raptor_amd.foundation_policy import Raptor    # noqa: E402
 from raptor_amd.teachers import TeacherBank, balanced_teacher_assignment, parameter_count    # noqa: E402
-from raptor_amd.training import masked_mse, trajectory_actions  # noqa: E402
+from raptor_amd.training import Distiller, masked_mse, trajectory_actions  # noqa: E402
 
 
 def main():
@@ -33,6 +35,8 @@ def main():
     ap.add_argument("--teachers", type=int, default=64)
     ap.add_argument("--teacher-epochs", type=int, default=0,
                     help="the first K epochs collect with the teachers flying the envs (behaviour cloning), then the student acts")
+    ap.add_argument("--torch-optimizer", action="store_true",
+                    help="the loss and Adam in torch (trajectory_actions + masked_mse) instead of Distiller.step")
     args = ap.parse_args()
 
     device = l2f.Device()
@@ -50,8 +54,11 @@ def main():
     bank = TeacherBank(device, (np.random.default_rng(1).standard_normal((args.teachers, parameter_count(22, 64, 64))) * 0.1)
                        .astype(np.float32), 22, 64, 64, "relu", "tanh")
     ids = balanced_teacher_assignment(n, args.teachers)
-    weights = torch.tensor(student.weights, device="cuda", requires_grad=True)
-    opt = torch.optim.Adam([weights], lr=args.lr)
+    if args.torch_optimizer:
+        weights = torch.tensor(student.weights, device="cuda", requires_grad=True)
+        opt = torch.optim.Adam([weights], lr=args.lr)
+    else:
+        distiller = Distiller(student, lr=args.lr)
     traj = vector.Trajectory(env, T)
 
     for epoch in range(args.epochs):
@@ -62,21 +69,29 @@ def main():
         else:
             vector.rollout(device, env, params, state, student, rng, T, "fused", autoreset=True, trajectory=traj)
             traj.relabel_teachers(bank, ids, overwrite=True, fetch=False)      # stored actions <- the teachers' labels
-        rec = traj.tensors()
-        labels = rec["act"][:, :, :n].clone()
-        live = (rec["done"][:, :n] != 4)[:, None, :].expand(T, 4, n)           # frozen steps carry no label
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for k in range(args.adam_steps):
-            opt.zero_grad()
-            act = trajectory_actions(traj, student, weights)[:, :, :n]
-            loss = masked_mse(act, labels, live)        # masks the inputs: frozen steps may hold NaN
-            loss.backward()
-            opt.step()
-            print(f"epoch {epoch} step {k}: masked MSE {loss.item():.5f}", flush=True)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        student.set_weights(weights)                    # the next collection runs the updated student
+        if args.torch_optimizer:
+            rec = traj.tensors()
+            labels = rec["act"][:, :, :n].clone()
+            live = (rec["done"][:, :n] != 4)[:, None, :].expand(T, 4, n)       # frozen steps carry no label
+            losses = []
+            for k in range(args.adam_steps):
+                opt.zero_grad()
+                act = trajectory_actions(traj, student, weights)[:, :, :n]
+                loss = masked_mse(act, labels, live)    # masks the inputs: frozen steps may hold NaN
+                loss.backward()
+                opt.step()
+                losses.append(loss.item())
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            student.set_weights(weights)                # the next collection runs the updated student
+        else:
+            # the labels are the trajectory's stored actions, frozen steps are masked in the kernel; the student is updated in place
+            losses = distiller.step(traj, updates=args.adam_steps).tolist()
+            dt = time.perf_counter() - t0
+        for k, loss in enumerate(losses):
+            print(f"epoch {epoch} step {k}: masked MSE {loss:.5f}", flush=True)
         print(f"epoch {epoch}: {args.adam_steps} gradient passes over {n} envs x {T} steps in {dt * 1e3:.1f} ms "
               f"({args.adam_steps / dt:.1f} passes/s, {args.adam_steps * n * T / dt:.3g} env-steps/s)", flush=True)
 

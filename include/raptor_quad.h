@@ -37,7 +37,8 @@
  *     student-visited states                            :208-216 rq_teacher_bank_create / rq_trajectory_relabel_teachers
  *   distillation: the teachers flying their own
  *     quadrotors (checks, teacher-acting collection)    :207-216 rq_rollout_teachers / rq_teacher_bank_evaluate
- *   distillation: the student's regression gradient    :208-216 rq_trajectory_policy_forward / _backward + rq_policy_set_weights
+ *   distillation: the student's regression gradient    :208-216 rq_trajectory_policy_forward / _backward + rq_policy_set_weights;
+ *                                                              rq_trajectory_distill (loss, Adam and repack on the device)
  *   (the reference is single-process) env shards over
  *     GPUs + all-gather of episode returns (RCCL)                rq_env_create(global_env_offset) / rq_comm_* / rq_allgather_returns
  *
@@ -422,6 +423,38 @@ RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* policy, int
 RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* policy, const float* grad_action,
                                          uint32_t ld_grad, float* grad_weights, float* grad_hidden_start,
                                          int memory);
+
+/* The distillation update without leaving the device.  The loss is the masked mean squared error between the policy's actions over
+ * the recording (the forward above) and a target y [T][4][ld_target] (ld_target >= n_envs): the mean over the LIVE entries - done
+ * code != 4, column < n_envs - of (a - y)^2, M = 4 x the live env-steps of them.  target == NULL: the trajectory's own stored
+ * actions (what rq_trajectory_relabel_teachers(..., overwrite) or a teacher-acting rollout left there; ld_target is ignored).  What
+ * is not live contributes nothing, whatever it holds (NaN in the targets or the observations of frozen steps included); M = 0 gives
+ * loss 0 and a zero gradient.  No action or dL/da tensor is written or read: the backward recomputes the action from the state it
+ * recomputes anyway, with the forward's own arithmetic.  Deterministic: no float atomics, the same bits every run.
+ * rq_trajectory_policy_loss_grad: loss [1] and grad_weights [2084] = dloss/dtheta, no update.  Refusals and `memory` as for the
+ * pair above (with RQ_DST_DEVICE* the target, loss and grad_weights are device memory of the trajectory's device; with RQ_DST_HOST
+ * all three are host arrays).  It leaves the saved state of a forward behind: rq_trajectory_policy_backward may follow.
+ * rq_optimizer: Adam's moments m, v [2084] and step count for ONE policy, zero at creation, with the hyper-parameters in device
+ * memory.  The update is torch.optim.Adam's (bias-corrected moments, w -= lr m^ / (sqrt(v^) + eps)); weight_decay is decoupled
+ * (w *= 1 - lr weight_decay first, torch.optim.AdamW's), 0 = none.  rq_optimizer_set_lr takes effect in stream order: updates
+ * already enqueued keep the rate they were enqueued under.
+ * rq_trajectory_distill: n_updates x (forward, loss-seeded backward, reduction, Adam, both fp32 operand images rebuilt on the
+ * device), enqueued back to back on rq_device_stream() with no host synchronisation in between; losses [n_updates]: the loss
+ * BEFORE each update.  With RQ_DST_DEVICE_ASYNC the call returns after enqueueing; whatever is enqueued on the same stream
+ * afterwards - a rollout, a relabel - runs the updated policy.  The host's copy of the weights is refreshed (one 8 KB copy) by the
+ * first call that needs it: rq_policy_get_weights, rq_policy_set_precision to a 16-bit precision, rq_policy_set_standardize,
+ * rq_policy_selftest.  The policy's hidden state is kept.  Refused beyond the above: an optimizer made for another policy. */
+typedef struct rq_optimizer rq_optimizer;
+typedef struct rq_adam_config { double lr, beta1, beta2, eps, weight_decay; } rq_adam_config;
+RQ_API int rq_trajectory_policy_loss_grad(rq_trajectory* t, rq_policy* policy, const float* target, uint32_t ld_target,
+                                          int start, float* loss, float* grad_weights, int memory);
+RQ_API int rq_optimizer_create(rq_policy* policy, const rq_adam_config* config, rq_optimizer** out);
+RQ_API int rq_optimizer_destroy(rq_optimizer* optimizer);
+RQ_API int rq_optimizer_set_lr(rq_optimizer* optimizer, double lr);
+RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* policy, rq_optimizer* optimizer, const float* target,
+                                 uint32_t ld_target, int start, uint32_t n_updates, float* losses, int memory);
+/* the policy's current parameters, 2 084 floats in the checkpoint order (after device-side updates: fetched from the device) */
+RQ_API int rq_policy_get_weights(rq_policy* policy, float* host_out);
 
 /* ---- Teacher bank: the distillation step of the reference (README.md:208-216: ~1000 teacher policies, one per
  * sampled quadrotor, queried on the states the student visited).  The teachers'

@@ -71,6 +71,11 @@ class EnvConfig(C.Structure):
 EnvConfig._field_names = frozenset(n for n, _ in EnvConfig._fields_)
 
 
+class AdamConfig(C.Structure):
+    """``rq_adam_config`` (include/raptor_quad.h)"""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double)]
+
+
 _vp = C.c_void_p
 # array arguments are declared void* so that a plain integer address can be passed: numpy's
 # ``a.ctypes.data_as(POINTER(c_float))`` costs 3 us per call, ``a.ctypes.data`` 1 us - five arrays cross the
@@ -171,6 +176,12 @@ _SIGNATURES = {
     "rq_trajectory_relabel": [_vp, _vp, _fp, C.c_int],
     "rq_trajectory_policy_forward": [_vp, _vp, C.c_int, _fp, C.c_uint32, C.c_int],
     "rq_trajectory_policy_backward": [_vp, _vp, _fp, C.c_uint32, _fp, _fp, C.c_int],
+    "rq_trajectory_policy_loss_grad": [_vp, _vp, _fp, C.c_uint32, C.c_int, _fp, _fp, C.c_int],
+    "rq_optimizer_create": [_vp, C.POINTER(AdamConfig), C.POINTER(_vp)],
+    "rq_optimizer_destroy": [_vp],
+    "rq_optimizer_set_lr": [_vp, C.c_double],
+    "rq_trajectory_distill": [_vp, _vp, _vp, _fp, C.c_uint32, C.c_int, C.c_uint32, _fp, C.c_int],
+    "rq_policy_get_weights": [_vp, _fp],
     "rq_comm_unique_id": [_vp, C.c_size_t],
     "rq_comm_create": [_vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.POINTER(_vp)],
     "rq_comm_destroy": [_vp],

@@ -1,6 +1,8 @@
 // rq_capi_grad.cpp - the learner half of distillation (README.md:208-216) behind the C ABI: the fp32 student over a recorded
 // trajectory (rq_trajectory_policy_forward) and the exact gradient of those actions with respect to its 2 084 parameters, back
-// through time along the recorded episode structure (rq_trajectory_policy_backward).  Kernels: rq_grad.hpp.
+// through time along the recorded episode structure (rq_trajectory_policy_backward); and the whole distillation update on the device:
+// masked-MSE loss and gradient (rq_trajectory_policy_loss_grad), Adam and the operand images (rq_trajectory_distill).
+// Kernels: rq_grad.hpp.
 #include "rq_objects.hpp"
 
 using namespace rqh;
@@ -26,6 +28,79 @@ int check_memory(int memory) {
     return RQ_OK;
 }
 
+// the transposed image of the backward, packed once per weight version (a device-side update writes it itself)
+int ensure_grad_image(rq_policy* pol) {
+    if (pol->w_packed_grad && pol->grad_image_version == pol->weight_version) return RQ_OK;
+    rq_device* dev = pol->dev;
+    int rc = policy_mirror(pol); if (rc) return rc;
+    std::vector<float> image;
+    try { image.resize(rq::RQ_PACKED_GRAD_FLOATS); } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_trajectory_policy_forward: host allocation failed");
+    }
+    rq::pack_policy_grad(pol->w_eff, image.data());
+    RQ_HIP(hipStreamSynchronize(dev->stream));
+    RQ_HIP(pol->w_packed_grad.reserve(dev->stream, image.size()));
+    RQ_HIP(hipMemcpy(pol->w_packed_grad, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
+    pol->grad_image_version = pol->weight_version;
+    return RQ_OK;
+}
+
+// What the two loss-seeded calls share.  loss_check: the refusals, before the call's DeviceScope (a refused call leaves the device,
+// a resident executor included, alone).  loss_begin, inside it: the workspace and the target on the device; n_losses: floats wanted
+// behind the gradient in t->grad.out.  -> d_target / ld_y as the kernel takes them.
+int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, const char* what) {
+    int rc = check_pair(t, pol, what); if (rc) return rc;
+    rc = check_memory(memory); if (rc) return rc;
+    RQ_REQUIRE(start == RQ_GRAD_START_CURRENT || start == RQ_GRAD_START_INITIAL, RQ_ERR_INVALID_ARGUMENT,
+               "start must be RQ_GRAD_START_CURRENT or RQ_GRAD_START_INITIAL");
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    if (target) {
+        RQ_REQUIRE(ld_target >= env->n, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": ld_target must be at least the number of envs");
+        if (memory != RQ_DST_HOST) {
+            hipPointerAttribute_t at{};
+            const hipError_t e = hipPointerGetAttributes(&at, target);
+            if (e != hipSuccess) (void)hipGetLastError();
+            RQ_REQUIRE(e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == dev->ordinal, RQ_ERR_SHAPE_MISMATCH,
+                       std::string(what) + ": the target lives on another device (or on the host): device memory of the trajectory's device is expected");
+        }
+    }
+    return RQ_OK;
+}
+
+int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, size_t n_losses,
+               const float** d_target, uint32_t* ld_y) {
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    const uint32_t T = t->length, ld = env->ld;
+    int rc = RQ_OK;
+    if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, env->n); if (rc) return rc; }
+    rc = ensure_grad_image(pol); if (rc) return rc;
+    t->grad.valid = false;
+    RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld));
+    RQ_HIP(t->grad.partial.reserve(dev->stream, rq::policy_loss_partial_floats(env->n)));
+    RQ_HIP(t->grad.out.reserve(dev->stream, RQ_POLICY_NUM_WEIGHTS + n_losses));
+    RQ_HIP(t->grad.live.reserve(dev->stream, 1));
+    *d_target = target ? target : t->act.get();          // the stored actions: what a relabel or a teacher-acting rollout left
+    *ld_y = target ? ld_target : ld;
+    if (target && memory == RQ_DST_HOST) {
+        const size_t floats = (size_t)T * RQ_ACTION_DIM * ld_target;
+        RQ_HIP(t->grad.rows.reserve(dev->stream, floats));
+        RQ_HIP(hipMemcpyAsync(t->grad.rows, target, floats * sizeof(float), hipMemcpyHostToDevice, dev->stream));
+        *d_target = t->grad.rows;
+    }
+    return RQ_OK;
+}
+
+hipError_t enqueue_loss_grad(rq_trajectory* t, rq_policy* pol, int start, const float* d_target, uint32_t ld_y, float* d_grad,
+                             float* d_loss) {
+    rq_env* env = t->env;
+    return rq::launch_policy_loss_grad(env->dev->stream, env->n, env->ld, t->length, pol->w_packed, pol->w_packed_grad, t->obs,
+                                       t->done, start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr, pol->ld,
+                                       start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y, t->grad.partial, d_grad,
+                                       d_loss, t->grad.live);
+}
+
 }  // namespace
 
 extern "C" {
@@ -43,18 +118,7 @@ RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* pol, int st
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const uint32_t T = t->length, ld = env->ld;
     if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, env->n); if (rc) return rc; }
-    // the transposed image of the backward, packed once per weight version
-    if (!pol->w_packed_grad || pol->grad_image_version != pol->weight_version) {
-        std::vector<float> image;
-        try { image.resize(rq::RQ_PACKED_GRAD_FLOATS); } catch (const std::bad_alloc&) {
-            return fail(RQ_ERR_OUT_OF_MEMORY, "rq_trajectory_policy_forward: host allocation failed");
-        }
-        rq::pack_policy_grad(pol->w_eff, image.data());
-        RQ_HIP(hipStreamSynchronize(dev->stream));
-        RQ_HIP(pol->w_packed_grad.reserve(dev->stream, image.size()));
-        RQ_HIP(hipMemcpy(pol->w_packed_grad, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
-        pol->grad_image_version = pol->weight_version;
-    }
+    rc = ensure_grad_image(pol); if (rc) return rc;
     t->grad.valid = false;
     RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld));
     float* d_act = action;
@@ -117,6 +181,113 @@ RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* pol, const
         RQ_HIP(hipMemcpyAsync(grad_weights, d_gw, gw_bytes, hipMemcpyDeviceToHost, dev->stream));
         if (grad_hidden_start) RQ_HIP(hipMemcpyAsync(grad_hidden_start, d_gh, gh_bytes, hipMemcpyDeviceToHost, dev->stream));
     }
+    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    return RQ_OK;
+}
+
+// ---------------------------------------------------------------------------- the update on the device ---
+RQ_API int rq_trajectory_policy_loss_grad(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start,
+                                          float* loss, float* grad_weights, int memory) {
+    RQ_REQUIRE(t && pol && loss && grad_weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = loss_check(t, pol, target, ld_target, start, memory, "rq_trajectory_policy_loss_grad"); if (rc) return rc;
+    DeviceScope on_device(t->env->dev); rc = on_device.rc; if (rc) return rc;
+    const float* d_target = nullptr; uint32_t ld_y = 0;
+    rc = loss_begin(t, pol, target, ld_target, start, memory, 1, &d_target, &ld_y); if (rc) return rc;
+    rq_device* dev = t->env->dev;
+    float* d_grad = memory == RQ_DST_HOST ? t->grad.out.get() : grad_weights;
+    float* d_loss = memory == RQ_DST_HOST ? t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS : loss;
+    RQ_HIP(enqueue_loss_grad(t, pol, start, d_target, ld_y, d_grad, d_loss));
+    // the saved state is the forward's: a rq_trajectory_policy_backward may follow
+    t->grad.valid = true; t->grad.policy = pol; t->grad.weight_version = pol->weight_version; t->grad.length = t->length; t->grad.start = start;
+    if (memory == RQ_DST_HOST) {
+        RQ_HIP(hipMemcpyAsync(grad_weights, d_grad, RQ_POLICY_NUM_WEIGHTS * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
+        RQ_HIP(hipMemcpyAsync(loss, d_loss, sizeof(float), hipMemcpyDeviceToHost, dev->stream));
+    }
+    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    return RQ_OK;
+}
+
+RQ_API int rq_optimizer_create(rq_policy* pol, const rq_adam_config* config, rq_optimizer** out) {
+    RQ_REQUIRE(pol && config && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    RQ_REQUIRE(config->lr >= 0.0 && config->eps >= 0.0 && config->weight_decay >= 0.0 && config->beta1 >= 0.0 && config->beta1 < 1.0 &&
+               config->beta2 >= 0.0 && config->beta2 < 1.0, RQ_ERR_INVALID_ARGUMENT,
+               "lr, eps and weight_decay must be non-negative and the betas in [0, 1)");
+    rq_device* dev = pol->dev;
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    rq_optimizer* o = new (std::nothrow) rq_optimizer();
+    RQ_REQUIRE(o, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
+    o->dev = dev; o->ordinal = dev->ordinal; o->policy = pol;
+    const size_t entries = (size_t)rq::RQ_PACKED_FLOATS + rq::RQ_PACKED_GRAD_FLOATS;
+    std::vector<rq::PackGather> table;
+    try { table.resize(entries); rq::pack_gather_table(table.data()); } catch (const std::bad_alloc&) {
+        delete o;
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_optimizer_create: host allocation failed");
+    }
+    const rq::AdamState st{config->lr, config->beta1, config->beta2, config->eps, config->weight_decay, 1.0, 1.0, 0u, 0u};
+    hipError_t e = o->m.alloc(RQ_POLICY_NUM_WEIGHTS);
+    if (e == hipSuccess) e = o->v.alloc(RQ_POLICY_NUM_WEIGHTS);
+    if (e == hipSuccess) e = o->grad.alloc(RQ_POLICY_NUM_WEIGHTS);
+    if (e == hipSuccess) e = o->state.alloc(1);
+    if (e == hipSuccess) e = o->table.alloc(entries);
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e == hipSuccess) e = hipMemset(o->m, 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(o->v, 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(o->state, &st, sizeof(st), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->table, table.data(), entries * sizeof(rq::PackGather), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        delete o;
+        return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string("rq_optimizer_create: ") + hipGetErrorString(e));
+    }
+    *out = o;
+    return RQ_OK;
+}
+
+RQ_API int rq_optimizer_destroy(rq_optimizer* opt) {
+    if (!opt) return RQ_OK;
+    DeviceScope on_device(opt->ordinal);
+    if (device_registry(opt->dev, 0)) (void)hipStreamSynchronize(opt->dev->stream);      // an update may still be queued
+    delete opt;
+    return RQ_OK;
+}
+
+RQ_API int rq_optimizer_set_lr(rq_optimizer* opt, double lr) {
+    RQ_REQUIRE(opt, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(lr >= 0.0, RQ_ERR_INVALID_ARGUMENT, "lr must be non-negative");
+    DeviceScope on_device(opt->dev); int rc = on_device.rc; if (rc) return rc;
+    RQ_HIP(rq::launch_adam_set_lr(opt->dev->stream, opt->state, lr));
+    return RQ_OK;
+}
+
+RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer* opt, const float* target, uint32_t ld_target,
+                                 int start, uint32_t n_updates, float* losses, int memory) {
+    RQ_REQUIRE(t && pol && opt && losses, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(policy_registry(pol, 0) && opt->policy == pol, RQ_ERR_INVALID_ARGUMENT,
+               "rq_trajectory_distill: the optimizer was made for another policy");
+    RQ_REQUIRE(n_updates > 0, RQ_ERR_INVALID_ARGUMENT, "n_updates must be positive");
+    int rc = loss_check(t, pol, target, ld_target, start, memory, "rq_trajectory_distill"); if (rc) return rc;
+    DeviceScope on_device(t->env->dev); rc = on_device.rc; if (rc) return rc;          // (retires a resident executor: it holds the old operands)
+    const float* d_target = nullptr; uint32_t ld_y = 0;
+    rc = loss_begin(t, pol, target, ld_target, start, memory, n_updates, &d_target, &ld_y); if (rc) return rc;
+    rq_device* dev = t->env->dev;
+    float* d_losses = memory == RQ_DST_HOST ? t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS : losses;
+    hipError_t e = hipSuccess;
+    uint32_t done_updates = 0;
+    for (; done_updates < n_updates && e == hipSuccess; ++done_updates) {
+        e = enqueue_loss_grad(t, pol, start, d_target, ld_y, opt->grad, d_losses + done_updates);
+        if (e == hipSuccess) e = rq::launch_adam_repack(dev->stream, opt->grad, pol->w_dev, opt->m, opt->v, opt->state, opt->table,
+                                                        pol->w_packed, pol->w_packed_grad);
+    }
+    if (done_updates > 0) {             // the weights on the device are new (even if a later launch failed): everything derived is behind
+        pol->version = fresh_version();
+        pol->weight_version = fresh_version();
+        pol->grad_image_version = pol->weight_version;
+        pol->mirror_stale = pol->images16_stale = true;
+    }
+    RQ_HIP(e);
+    if (memory == RQ_DST_HOST)
+        RQ_HIP(hipMemcpyAsync(losses, d_losses, (size_t)n_updates * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
     if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
     return RQ_OK;
 }

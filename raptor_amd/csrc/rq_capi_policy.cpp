@@ -36,11 +36,41 @@ int policy_size(rq_policy* pol, uint32_t batch) {
         pol->needs_reset = true;
     }
     if (pol->needs_reset) {
-        for (int j = 0; j < RQ_POLICY_HIDDEN_DIM; ++j)
-            RQ_HIP(rq::launch_fill_f32(pol->dev->stream, pol->hidden + (size_t)j * pol->ld,
-                                       pol->w_host[2000 + j], pol->ld));
+        if (pol->mirror_stale)       // updated on the device: the initial state is read there, in stream order
+            RQ_HIP(rq::launch_fill_rows(pol->dev->stream, pol->hidden, pol->ld, pol->w_dev + 2000, RQ_POLICY_HIDDEN_DIM));
+        else
+            for (int j = 0; j < RQ_POLICY_HIDDEN_DIM; ++j)
+                RQ_HIP(rq::launch_fill_f32(pol->dev->stream, pol->hidden + (size_t)j * pol->ld,
+                                           pol->w_host[2000 + j], pol->ld));
         pol->needs_reset = false;
     }
+    return RQ_OK;
+}
+
+int policy_mirror(rq_policy* pol) {
+    if (!pol->mirror_stale) return RQ_OK;
+    DeviceScope on_device(pol->dev); int rc = on_device.rc; if (rc) return rc;
+    RQ_HIP(hipMemcpyAsync(pol->w_host, pol->w_dev, sizeof(pol->w_host), hipMemcpyDeviceToHost, pol->dev->stream));
+    RQ_HIP(hipStreamSynchronize(pol->dev->stream));
+    std::memcpy(pol->w_eff, pol->w_host, sizeof(pol->w_eff));      // a device-side update is refused with a Standardize stage
+    pol->mirror_stale = false;
+    return RQ_OK;
+}
+
+int policy_images16(rq_policy* pol) {
+    if (!pol->images16_stale) return RQ_OK;
+    int rc = policy_mirror(pol); if (rc) return rc;
+    std::vector<float> packed16, packed_split;
+    try { packed16.resize(rq::RQ_PACKED_BF16_FLOATS); packed_split.resize(rq::RQ_PACKED_F16X2_FLOATS); } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "policy images: host allocation failed");
+    }
+    rq::pack_policy_bf16(pol->w_eff, packed16.data());
+    rq::pack_policy_f16x2(pol->w_eff, packed_split.data());
+    DeviceScope on_device(pol->dev); rc = on_device.rc; if (rc) return rc;
+    RQ_HIP(hipStreamSynchronize(pol->dev->stream));
+    RQ_HIP(hipMemcpy(pol->w_packed_bf16, packed16.data(), packed16.size() * sizeof(float), hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(pol->w_packed_f16x2, packed_split.data(), packed_split.size() * sizeof(float), hipMemcpyHostToDevice));
+    pol->images16_stale = false;
     return RQ_OK;
 }
 
@@ -85,6 +115,7 @@ static int policy_upload(rq_policy* p) {
     RQ_HIP(hipMemcpy(p->w_packed, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
     RQ_HIP(hipMemcpy(p->w_packed_bf16, packed16.data(), packed16.size() * sizeof(float), hipMemcpyHostToDevice));
     RQ_HIP(hipMemcpy(p->w_packed_f16x2, packed_split.data(), packed_split.size() * sizeof(float), hipMemcpyHostToDevice));
+    p->mirror_stale = p->images16_stale = false;
     return RQ_OK;
 }
 
@@ -132,6 +163,13 @@ RQ_API int rq_policy_set_weights(rq_policy* pol, const float* weights, size_t n_
     return policy_upload(pol);
 }
 
+RQ_API int rq_policy_get_weights(rq_policy* pol, float* host_out) {
+    RQ_REQUIRE(pol && host_out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = policy_mirror(pol); if (rc) return rc;
+    std::memcpy(host_out, pol->w_host, sizeof(pol->w_host));
+    return RQ_OK;
+}
+
 RQ_API int rq_policy_pack_image(const float* weights, size_t n_weights, int precision, float* image, size_t capacity,
                                 size_t* floats) {
     RQ_REQUIRE(weights && floats, RQ_ERR_INVALID_ARGUMENT, "null argument");
@@ -154,6 +192,7 @@ RQ_API int rq_policy_set_precision(rq_policy* pol, int precision) {
     pol->version = fresh_version();
     RQ_REQUIRE(precision == RQ_POLICY_FP32 || precision == RQ_POLICY_BF16_MFMA || precision == RQ_POLICY_F16X2_MFMA,
                RQ_ERR_INVALID_ARGUMENT, "unknown precision");
+    if (precision != RQ_POLICY_FP32) { int rc = policy_images16(pol); if (rc) return rc; }
     pol->precision = precision;
     return RQ_OK;
 }
@@ -161,6 +200,7 @@ RQ_API int rq_policy_set_precision(rq_policy* pol, int precision) {
 RQ_API int rq_policy_set_standardize(rq_policy* pol, const float* mean, const float* std) {
     RQ_REQUIRE(pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE((mean == nullptr) == (std == nullptr), RQ_ERR_INVALID_ARGUMENT, "mean and std must be given together");
+    { int rc = policy_mirror(pol); if (rc) return rc; }
     if (mean) {
         for (int k = 0; k < RQ_POLICY_INPUT_DIM; ++k) {
             RQ_REQUIRE(std[k] > 0.0f, RQ_ERR_INVALID_ARGUMENT, "std must be positive");
@@ -336,7 +376,9 @@ RQ_API int rq_policy_selftest(rq_policy* pol, const float* input, const float* e
     RQ_REQUIRE(steps > 0 && batch > 0, RQ_ERR_INVALID_ARGUMENT, "empty test");
     // runs on a private policy object so the caller's hidden state is untouched
     rq_policy* tmp = nullptr;
-    int rc = rq_policy_create(pol->dev, pol->w_host, RQ_POLICY_NUM_WEIGHTS, &tmp); if (rc) return rc;
+    int rc = policy_mirror(pol); if (rc) return rc;
+    rc = policy_images16(pol); if (rc) return rc;
+    rc = rq_policy_create(pol->dev, pol->w_host, RQ_POLICY_NUM_WEIGHTS, &tmp); if (rc) return rc;
     tmp->precision = pol->precision;
     tmp->sas_mode = pol->sas_mode == RQ_SAS_SAMPLE ? RQ_SAS_MEAN : pol->sas_mode;   // known answers are deterministic
     if (pol->standardize) {

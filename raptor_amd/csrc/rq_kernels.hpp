@@ -198,6 +198,27 @@ hipError_t launch_policy_grad_backward(hipStream_t s, uint32_t n, uint32_t ld, u
                                        const float* gpacked, const float* obs, const uint8_t* done, const float* saved,
                                        const float* grad_act, uint32_t ld_g, int start_initial, float* grad_h_start,
                                        float* partial, float* grad);
+// The distillation update on the device (rq_grad.hpp).  launch_policy_loss_grad: the forward without the action store, the backward
+// seeded by the masked squared error against target [steps][4][ld_y] (live = done code != 4, column < n) and the reduction: grad
+// [2084] = d/dtheta of loss = mean over live entries of (a - y)^2, loss [1], live [1] = M.  partial: [waves][2084] floats followed
+// by 2 x waves words (policy_loss_partial_floats).  Deterministic; M = 0 gives loss 0 and a zero gradient.
+constexpr size_t policy_loss_partial_floats(uint32_t n) { return (size_t)((n + 63) / 64) * (RQ_POLICY_NUM_WEIGHTS + 2); }
+hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed, const float* gpacked,
+                                   const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial,
+                                   float* saved, const float* target, uint32_t ld_y, float* partial, float* grad, float* loss,
+                                   unsigned long long* live);
+// Adam's state on the device: hyper-parameters, the step count t and the running powers beta^t (1 before the first step)
+struct AdamState { double lr, beta1, beta2, eps, weight_decay, beta1_t, beta2_t; uint32_t step, pad; };
+// one element of an operand image as a function of the flat weights: 0 (a == PACK_GATHER_NONE), k w[a], or k (w[a] + w[b])
+struct PackGather { uint16_t a, b; float k; };
+enum { PACK_GATHER_NONE = 0xFFFF };
+// one Adam step on w / m / v [2084] from grad, then packed (pack_policy's image) and gpacked (pack_policy_grad's) rebuilt from the
+// new weights through table [RQ_PACKED_FLOATS + RQ_PACKED_GRAD_FLOATS] (pack_gather_table)
+hipError_t launch_adam_repack(hipStream_t s, const float* grad, float* w, float* m, float* v, AdamState* st, const PackGather* table,
+                              float* packed, float* gpacked);
+hipError_t launch_adam_set_lr(hipStream_t s, AdamState* st, double lr);
+// dst [rows][ld] <- src [rows] (device), row by row
+hipError_t launch_fill_rows(hipStream_t s, float* dst, uint32_t ld, const float* src, uint32_t rows);
 // vector.step (README.md:98) + reward/termination/statistics.  rollout != 0 adds the
 // episode-end handling of rq_rollout (freeze or auto-reset incl. hidden-state reset).
 // With mb.rows_in the actions come from the mailbox and are also written to `action` (field-major).
@@ -281,6 +302,9 @@ enum {
 };
 enum { RQ_PACKED_GRAD_FLOATS = GW_REGS * 64 };
 void pack_policy_grad(const float* weights, float* packed);
+// both fp32 images as gather tables: pack_policy and pack_policy_grad themselves, run on symbols instead of numbers
+// (table [RQ_PACKED_FLOATS] for the forward image, then [RQ_PACKED_GRAD_FLOATS] for the transposed one)
+void pack_gather_table(PackGather* table);
 // log-std rows of a SampleAndSquash head: w_ls [4][16] row-major (nullptr = zeros), b_ls [4] -> 20 x 64 floats
 enum { RQ_LOGSTD_FLOATS = 20 * 64 };
 void pack_logstd_head(const float* w_ls, const float* b_ls, float* image);

@@ -8,7 +8,7 @@
 //   rq_capi_policy.cpp   Raptor: create / configure / reset / evaluate_step / evaluate_sequence / selftest
 //   rq_capi_rollout.cpp  the loop body x K on the device (fused, or chained under a hipGraph), trajectories, relabelling with a policy
 //   rq_capi_teacher.cpp  the teacher bank
-//   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory
+//   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory; the distillation update (loss, Adam, repack)
 //   rq_memory.hpp        rq::DeviceBuffer / rq::PinnedBuffer: every object below owns its device and pinned memory through them
 // rollout_check / rollout_begin / rollout_end (rq_capi_rollout.cpp) are the frame rq_rollout* and rq_rollout_teachers share.
 // Helpers live in namespace rqh (each .cpp says `using namespace rqh;`); nothing here is visible outside libraptor_quad.so.
@@ -245,6 +245,8 @@ struct rq_trajectory {
         uint64_t weight_version = 0;   // rq_policy::weight_version at the forward
         uint32_t length = 0;
         int start = 0;                 // enum rq_grad_start
+        DeviceBuffer<float> out;       // the loss-seeded calls: grad [2084] | losses [n_updates] before they go to the caller
+        DeviceBuffer<unsigned long long> live;    // [1]: M, the live entries of the last loss
     } grad;
 };
 
@@ -274,6 +276,21 @@ struct rq_policy {
     uint64_t grad_image_version = 0;  // the weight_version w_packed_grad was packed from
     DeviceBuffer<float> obs;      // [22][ld] staging for host observations
     DeviceBuffer<float> act;      // [4][ld]
+    // A device-side update (rq_trajectory_distill) writes w_dev, w_packed and w_packed_grad only.  Until policy_mirror() has fetched
+    // w_dev, w_host / w_eff are not read (policy_size fills the state from w_dev), and the 16-bit images are repacked before a
+    // 16-bit precision is next selected.
+    bool mirror_stale = false;    // w_host, w_eff are older than w_dev
+    bool images16_stale = false;  // w_packed_bf16, w_packed_f16x2 are older than w_dev
+};
+
+// Adam's state for one policy (rq_capi_grad.cpp; kernel: rq_grad.hpp k_adam_repack)
+struct rq_optimizer {
+    rq_device* dev = nullptr;
+    int ordinal = 0;
+    rq_policy* policy = nullptr;
+    DeviceBuffer<float> m, v, grad;          // [2084] each
+    DeviceBuffer<rq::AdamState> state;       // [1]
+    DeviceBuffer<rq::PackGather> table;      // pack_gather_table
 };
 
 struct rq_teacher_bank {
@@ -362,6 +379,8 @@ int mode_of(const rq_policy* pol);       // precision in bits 0-7, bit 8 = tanh 
 rq::SasArgs sas_of(const rq_policy* pol, uint32_t epoch, const uint32_t* epoch_base, uint64_t env_offset);
 const float* packed_of(const rq_policy* pol);
 int policy_size(rq_policy* pol, uint32_t batch);
+int policy_mirror(rq_policy* pol);       // w_host / w_eff <- w_dev after a device-side update (one 8 KB copy; nothing to do otherwise)
+int policy_images16(rq_policy* pol);     // the bf16 / f16x2 images repacked from the weights if an update left them behind
 
 // ---- rq_capi_rollout.cpp ----
 // What a rollout of either kind (a policy's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope: the checks

@@ -3,6 +3,7 @@
 #include <cstdint>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "rq_kernels.hpp"
 
@@ -10,15 +11,31 @@ namespace rq {
 
 // One 64-lane VGPR image per MFMA A operand / bias vector; lane l = (q = l >> 4, j = l & 15).
 // Layout table: rq_device_math.hpp "actor" (enum QW_*).
-void pack_policy(const float* w, float* packed) {
+// V: float (the image) or Sym below (which weights each element is made of, for the device-side repack): one index arithmetic
+namespace {
+// a weight, or what the packers make of weights: 0, k w[a], k (w[a] + w[b])
+struct Sym {
+    uint16_t a = PACK_GATHER_NONE, b = PACK_GATHER_NONE;
+    float k = 1.0f;
+    Sym() = default;
+    Sym(float zero) { (void)zero; }                       // the packers' literal 0.0f
+    Sym(uint16_t a_, uint16_t b_, float k_) : a(a_), b(b_), k(k_) {}
+};
+Sym operator+(const Sym& x, const Sym& y) { return Sym(x.a, y.a, 1.0f); }      // of two plain weights
+Sym operator*(float k, const Sym& x) { return Sym(x.a, x.b, k); }               // of a weight or a sum, once
+struct SymWeights { Sym operator[](int i) const { return Sym((uint16_t)i, PACK_GATHER_NONE, 1.0f); } };
+}  // namespace
+
+template <typename V, typename W>
+static void pack_policy_t(const W& w, V* packed) {
     enum { W0 = 0, B0 = 352, WI = 368, WH = 1136, BI = 1904, BH = 1952, H0 = 2000, W2 = 2016, B2 = 2080 };
     for (int i = 0; i < RQ_PACKED_FLOATS; ++i) packed[i] = 0.0f;
     for (int l = 0; l < 64; ++l) {
         const int q = l >> 4, j = l & 15;
-        auto img = [&](int v) -> float& { return packed[qw_slot(v, l)]; };
+        auto img = [&](int v) -> V& { return packed[qw_slot(v, l)]; };
         for (int s = 0; s < 6; ++s) {
             const int f = 4 * s + q;     // input feature of k-slot q in K-step s
-            img(QW_L0 + s) = f < 22 ? w[W0 + j * 22 + f] : (f == 22 ? w[B0 + j] : 0.0f);
+            img(QW_L0 + s) = f < 22 ? w[W0 + j * 22 + f] : (f == 22 ? w[B0 + j] : V(0.0f));
         }
         // gate rows pre-scaled so that the MFMA accumulators are the exp2 arguments of the gates
         // (gru_gates_prescaled): r and z rows by -log2 e, n rows by -2 log2 e; the biases below likewise
@@ -37,14 +54,16 @@ void pack_policy(const float* w, float* packed) {
             img(QW_BNI + r) = kT * w[BI + 32 + 4 * q + r];
             img(QW_BNH + r) = kT * w[BH + 32 + 4 * q + r];
             img(QW_H0 + r) = w[H0 + 4 * q + r];
-            img(QW_B2 + r) = q == 0 ? w[B2 + r] : 0.0f;
+            img(QW_B2 + r) = q == 0 ? w[B2 + r] : V(0.0f);
         }
     }
 }
+void pack_policy(const float* w, float* packed) { pack_policy_t<float>(w, packed); }
 
 
 // The learner's transposed operands (enum GW_*, rq_grad.hpp): the weights as they are, without the gate pre-scaling
-void pack_policy_grad(const float* w, float* packed) {
+template <typename V, typename W>
+static void pack_policy_grad_t(const W& w, V* packed) {
     enum { WI = 368, WH = 1136, W2 = 2016 };
     for (int l = 0; l < 64; ++l) {
         const int q = l >> 4, j = l & 15;
@@ -55,6 +74,15 @@ void pack_policy_grad(const float* w, float* packed) {
             }
         packed[GW_W2T * 64 + l] = w[W2 + q * 16 + j];
     }
+}
+void pack_policy_grad(const float* w, float* packed) { pack_policy_grad_t<float>(w, packed); }
+
+void pack_gather_table(PackGather* table) {
+    static_assert(RQ_POLICY_NUM_WEIGHTS < PACK_GATHER_NONE, "weight indices are 16-bit");
+    std::vector<Sym> sym((size_t)RQ_PACKED_FLOATS + RQ_PACKED_GRAD_FLOATS);
+    pack_policy_t<Sym>(SymWeights{}, sym.data());
+    pack_policy_grad_t<Sym>(SymWeights{}, sym.data() + RQ_PACKED_FLOATS);
+    for (size_t i = 0; i < sym.size(); ++i) table[i] = PackGather{sym[i].a, sym[i].b, sym[i].k};
 }
 
 

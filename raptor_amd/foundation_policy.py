@@ -62,6 +62,7 @@ class Raptor:
         self._device = device
         self._h = None
         self._fin = None
+        self._weights_on_device = False
         self.example = None
         self.observation_spec = None
 
@@ -87,9 +88,9 @@ class Raptor:
         from .checkpoint import write_checkpoint_h5, write_checkpoint_header
         example = self.example if example is None else example
         if str(path).endswith((".h5", ".hdf5")):
-            write_checkpoint_h5(path, self._weights, example)
+            write_checkpoint_h5(path, self.weights, example)
         else:
-            write_checkpoint_header(path, self._weights, example)
+            write_checkpoint_header(path, self.weights, example)
 
     # the C object is created on first use so that ``Raptor()`` itself needs no device argument
     def _handle(self, device=None):
@@ -107,6 +108,10 @@ class Raptor:
 
     @property
     def weights(self):
+        if self._weights_on_device:       # updated on the device (training.Distiller.step): fetched once, when first asked for
+            w = np.empty(POLICY_NUM_WEIGHTS, np.float32)
+            _lib.call("rq_policy_get_weights", self._h, _lib.fptr(w))
+            self._weights, self._weights_on_device = w, False
         return self._weights
 
     @property
@@ -130,7 +135,7 @@ class Raptor:
         w = np.array(weights, dtype=np.float32, copy=True).reshape(-1)
         if w.size != POLICY_NUM_WEIGHTS:
             raise ValueError(f"expected {POLICY_NUM_WEIGHTS} weights")
-        self._weights = w
+        self._weights, self._weights_on_device = w, False
         if self._h is not None:
             _lib.call("rq_policy_set_weights", self._h, _lib.fptr(w), w.size)
 

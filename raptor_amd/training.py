@@ -9,6 +9,14 @@ torch function, so that collect -> relabel -> loss -> gradient -> update stays o
 
 The forward is one HIP launch, the backward two (rq_trajectory_policy_forward / _backward, csrc/rq_grad.hpp); the optimiser is
 torch's.  Only the fp32 policy without Standardize / SampleAndSquash stages has a gradient here.
+
+For the distillation loss itself - the masked MSE against the labels - the whole update stays on the device, torch not needed:
+
+    distiller = Distiller(policy, lr=1e-3)
+    losses = distiller.step(traj, updates=10)               # 10 x (forward, loss-seeded backward, Adam, repack), one enqueue
+    loss, grad = distiller.loss_and_grad(traj)              # the same loss and its gradient, no update
+
+Any other loss goes the first way.
 """
 import ctypes as C
 
@@ -102,3 +110,118 @@ try:
 
 except ImportError:        # the engine itself does not need torch; only this module's autograd function does
     _TrajectoryActions = None
+
+
+class Distiller:
+    """Adam on the masked mean squared error between ``policy``'s actions over a recording and a target, entirely on the device
+    (rq_trajectory_distill: forward, loss-seeded backward, reduction, Adam and the rebuilt operand images are enqueued back to
+    back; no action or gradient tensor the size of the recording exists, and the weights do not visit the host).
+
+    The loss is ``masked_mse(trajectory_actions(traj, policy, w)[:, :, :N], target[:, :, :N], live)`` with ``live`` = done code
+    != 4: a loss other than this masked MSE still goes through ``trajectory_actions`` and torch.  The update is
+    ``torch.optim.Adam``'s with these hyper-parameters (``weight_decay`` decoupled as in ``AdamW``; 0 = none).  ``policy`` must be
+    the fp32 policy without Standardize / SampleAndSquash stages; its weights are updated in place - the next rollout, relabel or
+    ``evaluate_step`` runs the updated policy, ``policy.weights`` fetches them when first read.
+
+    ``target``: None - the trajectory's own stored actions (what ``relabel_teachers(..., overwrite=True)`` or a teacher-acting
+    rollout left there) - or a [T, 4, ld_target] float32 array with ld_target >= N: a torch tensor on the trajectory's device, or
+    (``loss_and_grad`` only needs it) a NumPy array.  ``start`` as in ``trajectory_actions``."""
+
+    def __init__(self, policy, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        self.policy = policy
+        self._cfg = _lib.AdamConfig(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
+        self._h = None
+        self._fin = None
+        self._target_in_flight = None      # the target an enqueued-only step may still be reading (a contiguous copy, perhaps)
+
+    def _handle(self, traj):
+        pol = self.policy._handle(traj._env._device)
+        if self._h is None:
+            import weakref
+            h = C.c_void_p()
+            _lib.call("rq_optimizer_create", pol, C.byref(self._cfg), C.byref(h))
+            self._h = h
+            self._fin = weakref.finalize(self, _lib.load().rq_optimizer_destroy, h)
+        return pol, self._h
+
+    def set_lr(self, lr):
+        """A new learning rate for the updates enqueued from now on (schedules)."""
+        self._cfg.lr = float(lr)
+        if self._h is not None:
+            _lib.call("rq_optimizer_set_lr", self._h, float(lr))
+
+    @staticmethod
+    def _target(traj, target):
+        """-> (pointer or None, ld_target, on_device, keep-alive)"""
+        if target is None:
+            return None, 0, None, None
+        T = len(traj)
+        if hasattr(target, "data_ptr"):
+            import torch
+            t = target
+            if t.dim() != 3 or t.shape[0] != T or t.shape[1] != _lib.POLICY_OUTPUT_DIM or t.dtype != torch.float32 or not t.is_cuda:
+                raise ValueError(f"target must be a float32 device tensor [{T}, 4, >= N]")
+            t = t.contiguous()
+            return _device_ptr(t), t.shape[2], True, t
+        t = np.ascontiguousarray(target, np.float32)
+        if t.ndim != 3 or t.shape[0] != T or t.shape[1] != _lib.POLICY_OUTPUT_DIM:
+            raise ValueError(f"target must be [{T}, 4, >= N]")
+        return C.c_void_p(t.ctypes.data), t.shape[2], False, t
+
+    @staticmethod
+    def _torch_device(traj):
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            return None
+        return traj.tensors()["act"].device
+
+    def loss_and_grad(self, traj, target=None, start="initial"):
+        """-> (loss, dloss/dweights [2084]): device tensors when torch is present, NumPy otherwise (or with a NumPy target)."""
+        if start not in START:
+            raise ValueError('start must be "initial" or "current"')
+        ptr, ld_t, on_device, keep = self._target(traj, target)
+        pol = self.policy._handle(traj._env._device)
+        dev = self._torch_device(traj) if on_device is not False else None
+        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1      # the trajectory's saved state is this call's now
+        if dev is None:
+            loss, grad = np.empty(1, np.float32), np.empty(_lib.POLICY_NUM_WEIGHTS, np.float32)
+            if on_device:
+                raise ValueError("a device target needs torch")
+            _lib.call("rq_trajectory_policy_loss_grad", traj._require("trajectory"), pol, ptr, ld_t, START[start],
+                      _lib.fptr(loss), _lib.fptr(grad), 0)
+            return loss[0], grad
+        import torch
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        grad = torch.empty(_lib.POLICY_NUM_WEIGHTS, dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
+        _lib.call("rq_trajectory_policy_loss_grad", traj._require("trajectory"), pol, ptr, ld_t, START[start],
+                  _device_ptr(loss), _device_ptr(grad), 1)
+        return loss, grad
+
+    def step(self, traj, target=None, start="initial", updates=1, wait=True):
+        """``updates`` Adam steps on the recording, enqueued in one call -> the loss before each of them, [updates] (a device
+        tensor when torch is present, NumPy otherwise).  ``wait=False`` (torch only) returns once the work is enqueued on the
+        engine's stream: what the engine is asked to do next is ordered behind it; read the losses after ``device.synchronize()``."""
+        if start not in START:
+            raise ValueError('start must be "initial" or "current"')
+        updates = int(updates)
+        if updates < 1:
+            raise ValueError("updates must be at least 1")
+        ptr, ld_t, on_device, keep = self._target(traj, target)
+        pol, opt = self._handle(traj)
+        dev = self._torch_device(traj)
+        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
+        if dev is None or on_device is False:
+            losses = np.empty(updates, np.float32)
+            _lib.call("rq_trajectory_distill", traj._require("trajectory"), pol, opt, ptr, ld_t, START[start], updates,
+                      _lib.fptr(losses), 0)
+        else:
+            import torch
+            losses = torch.empty(updates, dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()      # once per call, not per update
+            _lib.call("rq_trajectory_distill", traj._require("trajectory"), pol, opt, ptr, ld_t, START[start], updates,
+                      _device_ptr(losses), 1 if wait else 2)
+        self._target_in_flight = keep      # until the next step: with wait=False the engine's stream may not have read it yet
+        self.policy._weights_on_device = True
+        return losses
