@@ -401,6 +401,31 @@ RQ_API int rq_rollout_record(rq_device* dev, rq_env* env, const rq_params* param
                       rq_policy* policy, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                       rq_trajectory* trajectory);
 
+/* ---- Tracking a moving setpoint (the reference environment's `trajectory` state component) ----
+ * The policy is a position controller: it sees position and velocity relative to a target, and flies a path when it is fed
+ * p - p_ref(t), v - v_ref(t).  A reference is a table host_rows [rows][6] of float32, row-major: columns 0..2 the target position,
+ * columns 3..5 the target linear velocity, world frame (FLU).  The row an env uses at a step is ITS OWN episode step count at
+ * observe time (rq_env_get_episode_steps before the step): every episode flies the path from its start, envs that reset at
+ * different times are at different rows.  rq_reference_create refuses rows == 0 and non-finite entries.
+ * rq_rollout_track is rq_rollout / rq_rollout_record (trajectory may be NULL) with ONE difference: after the observation is complete,
+ * noise included, o[0..2] -= ref[k][0..2] and o[12..14] -= ref[k][3..5] (single fp32 subtractions) - what rq_observe, the same
+ * subtraction on the host, rq_policy_evaluate_step and rq_step compute, bit for bit, in both modes.  Rotation matrix, body rates and
+ * previous action are untouched; state, reward, termination thresholds, RNG streams and episode statistics stay on the ABSOLUTE
+ * state - termination_position must contain the path.  A trajectory buffer records the shifted observation (what the policy saw),
+ * so a tracked recording goes into rq_trajectory_relabel*, the learner and rq_trajectory_distill as it is.
+ * Refused before anything is enqueued: a null argument, rows < episode_step_limit (no modulo: the table covers an episode), a
+ * reference of another rq_device, a policy with a SampleAndSquash stage.  Teacher banks do not track.
+ * Tracking error: per env, sum_sq = fp32 running sum of |p - ref[k][0..2]|^2 on the true (noise-free) position at observe time over
+ * the steps actually taken (a frozen env adds nothing), steps = their count; both exist in tracked rollouts only, are the same bit
+ * for bit in both modes, and are zeroed by rq_env_reset_statistics.  Either destination may be NULL. */
+typedef struct rq_reference rq_reference;
+RQ_API int rq_reference_create(rq_device* dev, const float* host_rows, uint32_t rows, rq_reference** out);
+RQ_API int rq_reference_destroy(rq_reference* reference);
+RQ_API int rq_rollout_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state,
+                     rq_policy* policy, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                     rq_trajectory* trajectory /* may be NULL */, const rq_reference* reference);
+RQ_API int rq_env_get_tracking_error(const rq_env* env, float* sum_sq, uint32_t* steps, int dst_is_device);
+
 /* ---- Learner: the student's gradient over a recorded trajectory (README.md:208-216, the distillation step's regression) ----
  * Forward: the policy on the recorded observations obs [T][22][ld] under rq_trajectory_relabel's episode rules (GRU state back to
  * the learned initial state after done codes 1 and 2, held on code 4) -> action [T][4][ld_action] (ld_action >= n_envs; only the

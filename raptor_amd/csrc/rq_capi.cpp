@@ -106,6 +106,18 @@ int check_env_objects(const rq_device* dev, const rq_env* env, const rq_params* 
     return RQ_OK;
 }
 
+int env_track_stats(rq_env* env, float** sum_sq, uint32_t** steps) {
+    const size_t ld = env->ld;
+    if (env->track_block.empty()) {
+        if (env->track_block.alloc(2 * 4 * ld) != hipSuccess) return fail(RQ_ERR_OUT_OF_MEMORY, "tracking statistics: device allocation failed");
+        const hipError_t e = hipMemsetAsync(env->track_block.get(), 0, 2 * 4 * ld, env->dev->stream);
+        if (e != hipSuccess) { env->track_block.reset(); return fail(RQ_ERR_HIP, "tracking statistics: hipMemsetAsync failed"); }
+    }
+    *sum_sq = (float*)env->track_block.get();
+    *steps = (uint32_t*)(env->track_block.get() + 4 * ld);
+    return RQ_OK;
+}
+
 // ---- copy-on-write state buffers ---------------------------------------------------------------------------
 // Everything is enqueued on the device's one stream, so a buffer that went back to the pool is safe to hand out again:
 // whatever still reads it was enqueued before whatever will write it.
@@ -627,6 +639,16 @@ RQ_API int rq_env_get_finished_lengths(const rq_env* env, uint32_t* dst, int dev
 RQ_API int rq_env_get_finished_counts(const rq_env* env, uint32_t* dst, int dev_dst) { return copy_out(env, env ? env->st.fin_counts : nullptr, dst, dev_dst); }
 RQ_API int rq_env_get_finished_terminated(const rq_env* env, uint32_t* dst, int dev_dst) { return copy_out(env, env ? env->st.fin_terminated : nullptr, dst, dev_dst); }
 
+RQ_API int rq_env_get_tracking_error(const rq_env* env, float* sum_sq, uint32_t* steps, int dev_dst) {
+    RQ_REQUIRE(env, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    float* d_sq = nullptr; uint32_t* d_steps = nullptr;
+    { DeviceScope on_device(env->dev); int rc = on_device.rc; if (rc) return rc;
+      rc = env_track_stats(const_cast<rq_env*>(env), &d_sq, &d_steps); if (rc) return rc; }
+    if (sum_sq) { const int rc = copy_out(env, d_sq, sum_sq, dev_dst); if (rc) return rc; }
+    if (steps) { const int rc = copy_out(env, d_steps, steps, dev_dst); if (rc) return rc; }
+    return RQ_OK;
+}
+
 RQ_API int rq_env_reset_statistics(rq_env* env) {
     RQ_REQUIRE(env, RQ_ERR_INVALID_ARGUMENT, "null argument");
     DeviceScope on_device(env->dev); int rc = on_device.rc; if (rc) return rc;
@@ -635,6 +657,7 @@ RQ_API int rq_env_reset_statistics(rq_env* env) {
     // every env counts as running a fresh episode from its current state (contract in raptor_quad.h)
     RQ_HIP(hipMemsetAsync(env->stats_block.get(), 0, 7 * 4 * ld, env->dev->stream));
     RQ_HIP(hipMemsetAsync(env->st.last_terminated, 0, 3 * ld, env->dev->stream));
+    if (!env->track_block.empty()) RQ_HIP(hipMemsetAsync(env->track_block.get(), 0, 2 * 4 * ld, env->dev->stream));
     return RQ_OK;
 }
 

@@ -2,6 +2,8 @@
 // by node), the trajectory buffer and relabelling a recorded trajectory with a policy.
 #include "rq_objects.hpp"
 
+#include <cmath>
+
 namespace rqh {
 
 int traj_block_to_host(rq_device* dev, const float* d_soa, uint32_t steps, uint32_t n, uint32_t ld, uint32_t dim,
@@ -66,13 +68,26 @@ static constexpr uint32_t kGraphSteps = 25;   // steps per captured graph (divid
 static constexpr size_t kMaxGraphs = 8;       // executable graphs kept per env (one per distinct argument set)
 
 static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy* policy,
-                        rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags, rq_trajectory* traj) {
+                        rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags, rq_trajectory* traj,
+                        const rq_reference* ref = nullptr) {
     RolloutFrame f;
     int rc = rollout_check(f, dev, env, params, state, rng, policy != nullptr, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(policy->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy lives on another device");
+    if (ref) {          // a tracked rollout is refused here, before anything is enqueued
+        RQ_REQUIRE(ref->dev == dev, RQ_ERR_SHAPE_MISMATCH, "reference lives on another device");
+        RQ_REQUIRE(ref->rows >= env->cfg.episode_step_limit, RQ_ERR_INVALID_ARGUMENT,
+                   "reference has fewer rows than episode_step_limit: the table must cover an episode");
+        RQ_REQUIRE(policy->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
+                   "tracked rollouts do not carry the SampleAndSquash stage");
+    }
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = policy_size(policy, env->n); if (rc) return rc;
     RQ_REQUIRE(policy->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy batch does not match the env");
+    rq::TrackPtrs trk{nullptr, 0, nullptr, nullptr};
+    if (ref) {
+        rc = env_track_stats(env, &trk.sq, &trk.steps); if (rc) return rc;
+        trk.ref = ref->d; trk.rows = ref->rows;
+    }
     rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
     const rq::TrajPtrs& tp = f.tp;
     const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
@@ -83,21 +98,32 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
             RQ_HIP(dev->k_span.reserve(dev->stream, (size_t)waves * 5));
             dev->k_span_used = waves;
         }
-        RQ_HIP(rq::launch_rollout_fused(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
-                                        params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
-                                        policy->precision, sas_of(policy, rng->epoch, nullptr, env->offset), tp,
-                                        dev->k_timing ? dev->k_span.get() : nullptr));
+        if (ref) {
+            RQ_HIP(rq::launch_rollout_fused_track(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
+                                                  params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
+                                                  policy->precision, tp, trk, dev->k_timing ? dev->k_span.get() : nullptr));
+        } else {
+            RQ_HIP(rq::launch_rollout_fused(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
+                                            params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
+                                            policy->precision, sas_of(policy, rng->epoch, nullptr, env->offset), tp,
+                                            dev->k_timing ? dev->k_span.get() : nullptr));
+        }
         dev->k_timed = dev->k_timing && n_steps > 0;
         dev->k_fetched = false;
     } else {
         // one step = observe -> evaluate_step -> step (-> record) on the stream.  Without a recording the step kernel
         // also assembles the NEXT step's observation (round 3: two launches per step instead of three; the first
         // observation of the rollout is a launch of its own, the one assembled by the last step is not used)
+        // A tracked rollout puts one small kernel in front of the actor: it takes the setpoint off the assembled observation,
+        // wherever that came from, and keeps the tracking error (the observation the last step assembles is never shifted).
+        const uint32_t step_nodes = ref ? 3u : 2u;
         const bool fold_observe = traj == nullptr;
         auto enqueue_step = [&](uint32_t epoch, const uint32_t* epoch_base, uint32_t t_record) -> hipError_t {
             hipError_t e = hipSuccess;
             if (!fold_observe)
                 e = rq::launch_observe(dev->stream, b, nc, noise, rng->seed, epoch, epoch_base, params->d, state->d, env->obs);
+            if (e == hipSuccess && ref)
+                e = rq::launch_track_shift(dev->stream, b, state->d, env->st, env->obs, trk);
             if (e == hipSuccess)
                 e = rq::launch_actor_step(dev->stream, env->n, packed_of(policy), env->obs, env->ld, policy->hidden,
                                           policy->ld, env->act, env->ld, env->st.frozen, policy->precision,
@@ -126,7 +152,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                 if (g.params == params->d && g.state == state->d && g.hidden == policy->hidden && g.obs == env->obs &&
                     g.packed == packed_of(policy) && g.weights == policy->w_dev && g.flags == flags &&
                     g.precision == policy->precision && g.seed == rng->seed && g.sas_mode == policy->sas_mode &&
-                    g.sas_seed == policy->sas_seed && g.ls_image == policy->ls_image &&
+                    g.sas_seed == policy->sas_seed && g.ls_image == policy->ls_image && g.ref == trk.ref && g.ref_rows == trk.rows &&
                     std::memcmp(&g.cfg, &env->cfg, sizeof(rq_env_config)) == 0) { exec = g.exec; break; }
             if (!exec) {
                 // Built node by node (rq_kernels.hpp GraphSink), NOT by stream capture: while any stream of a process captures, HIP
@@ -142,7 +168,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                     for (uint32_t t = 0; t < kGraphSteps && ce == hipSuccess; ++t) ce = enqueue_step(t, env->epoch_dev, 0);
                     if (ce == hipSuccess) ce = rq::launch_add_u32(dev->stream, env->epoch_dev, kGraphSteps);
                     rq::set_graph_sink(nullptr);
-                    if (ce == hipSuccess && sink.nodes != 2 * kGraphSteps + 1) ce = hipErrorUnknown;     // a launcher that bypassed the sink
+                    if (ce == hipSuccess && sink.nodes != step_nodes * kGraphSteps + 1) ce = hipErrorUnknown;     // a launcher that bypassed the sink
                 }
                 if (ce == hipSuccess) ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
                 if (graph) (void)hipGraphDestroy(graph);
@@ -159,7 +185,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                     try {                       // nothing throws across the boundary
                         env->graphs.push_back({params->d, state->d, policy->hidden, packed_of(policy), policy->w_dev, env->obs, flags,
                                                policy->precision, env->cfg, rng->seed, policy->sas_mode, policy->sas_seed,
-                                               policy->ls_image, exec});
+                                               policy->ls_image, trk.ref, trk.rows, exec});
                     } catch (const std::bad_alloc&) {
                         (void)hipGraphExecDestroy(exec);
                         return fail(RQ_ERR_OUT_OF_MEMORY, "rollout: host allocation failed");
@@ -187,6 +213,45 @@ RQ_API int rq_rollout_record(rq_device* dev, rq_env* env, const rq_params* param
                       rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags, rq_trajectory* trajectory) {
     RQ_REQUIRE(trajectory, RQ_ERR_INVALID_ARGUMENT, "null trajectory");
     return rollout_impl(dev, env, params, state, policy, rng, n_steps, mode, flags, trajectory);
+}
+
+// ---------------------------------------------------------------------------- Tracking
+RQ_API int rq_reference_create(rq_device* dev, const float* host_rows, uint32_t rows, rq_reference** out) {
+    RQ_REQUIRE(dev && host_rows && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    RQ_REQUIRE(rows > 0, RQ_ERR_INVALID_ARGUMENT, "a reference needs at least one row");
+    for (size_t j = 0; j < (size_t)rows * 6; ++j)
+        RQ_REQUIRE(std::isfinite(host_rows[j]), RQ_ERR_INVALID_ARGUMENT, "reference holds a non-finite entry");
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    rq_reference* r = new (std::nothrow) rq_reference();
+    RQ_REQUIRE(r, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
+    r->dev = dev; r->ordinal = dev->ordinal; r->rows = rows;
+    if (r->d.alloc((size_t)rows * 6) != hipSuccess) {
+        delete r;
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_reference_create: device allocation failed");
+    }
+    // (synchronous: the caller's rows are its own again on return)
+    const hipError_t e = hipMemcpy(r->d, host_rows, (size_t)rows * 6 * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete r;
+        return fail(RQ_ERR_HIP, std::string("rq_reference_create: hipMemcpy -> ") + hipGetErrorString(e));
+    }
+    *out = r;
+    return RQ_OK;
+}
+
+RQ_API int rq_reference_destroy(rq_reference* reference) {
+    if (!reference) return RQ_OK;
+    DeviceScope on_device(reference->ordinal);     // (hipFree synchronises the device: no launch still reads the table)
+    delete reference;
+    return RQ_OK;
+}
+
+RQ_API int rq_rollout_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy* policy,
+                     rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags, rq_trajectory* trajectory,
+                     const rq_reference* reference) {
+    RQ_REQUIRE(reference, RQ_ERR_INVALID_ARGUMENT, "null reference");
+    return rollout_impl(dev, env, params, state, policy, rng, n_steps, mode, flags, trajectory, reference);
 }
 
 // ---------------------------------------------------------------------------- Trajectory

@@ -377,6 +377,31 @@ __device__ __forceinline__ void observe_head(const QuadState& y, f32x2 LA01, f32
     o[18] = LA01[0]; o[19] = LA01[1]; o[20] = LA23[0]; o[21] = LA23[1];
 }
 
+// ------------------------------------------------------------------ tracking -----------
+// A tracked rollout (rq_rollout_track) flies a moving setpoint: row k of the reference table [rows][6] = (target position, target
+// velocity) in the world frame, k = the env's episode step count at observe time.  Only what the policy sees changes - the finished
+// observation (noise included) has the row subtracted from its position and linear-velocity entries - so the fused kernel, the
+// chained kernels and a caller that subtracts on the host agree bit for bit.  The three functions below are the only place any
+// path does this arithmetic: single rounded operations in a fixed order, nothing the compiler may contract.
+// (k is clamped to the table: the host refuses rows < episode_step_limit, the clamp keeps a stale step count inside the block)
+__device__ __forceinline__ void track_row(const float* __restrict__ ref, uint32_t rows, uint32_t k, float (&r)[6]) {
+    const float* row = ref + (size_t)(k < rows ? k : rows - 1u) * 6u;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) r[j] = row[j];
+}
+// o[0..2] -= target position, o[12..14] -= target velocity: the head's p and v entries (observe_head)
+template <int N>
+__device__ __forceinline__ void track_shift(const float (&r)[6], float (&o)[N]) {
+    static_assert(N >= 15, "the policy-visible head");
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { o[j] = __fsub_rn(o[j], r[j]); o[12 + j] = __fsub_rn(o[12 + j], r[3 + j]); }
+}
+// sum + |p - target position|^2 on the TRUE (noise-free) position: d = p - r per axis, e = fma(dz, dz, fma(dy, dy, dx dx)), sum + e
+__device__ __forceinline__ float track_accumulate(float sum, float px, float py, float pz, const float (&r)[6]) {
+    const float dx = __fsub_rn(px, r[0]), dy = __fsub_rn(py, r[1]), dz = __fsub_rn(pz, r[2]);
+    return __fadd_rn(sum, __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx))));
+}
+
 // ------------------------------------------------------------------ parameter sampling -
 
 __device__ __forceinline__ void sample_params(const SampleCfg& c, uint64_t seed, uint32_t epoch, uint64_t genv,

@@ -1085,6 +1085,22 @@ hipError_t launch_rollout_fused(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, 
     return hipGetLastError();
 }
 
+hipError_t launch_rollout_fused_track(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                      uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                      const float* params, float* state, float* hidden, const float* weights,
+                                      const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
+                                      unsigned long long* span) {
+    if (b.n == 0 || n_steps == 0) return hipSuccess;
+    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, packed, st, traj, SasArgs{}, span, trk};
+    if (precision == RQ_POLICY_F16X2_MFMA || precision == RQ_POLICY_BF16_MFMA)
+        return launch_rollout_fused_track_16bit(s, a, noise, ar, precision);
+    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
+    if (b.n > 65536u) launch_fused_track_actor<ActorF32Lean>(s, a, noise, ar);
+    else              launch_fused_track_actor<ActorF32>(s, a, noise, ar);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(kBlock) void k_record(Batch b, const float* __restrict__ obs,
                                                    const float* __restrict__ act, StatsPtrs st, TrajPtrs traj) {
     const uint32_t i = env_index();
@@ -1161,6 +1177,31 @@ hipError_t launch_fill_f32(hipStream_t s, float* p, float v, uint32_t count) {
     if (count == 0) return hipSuccess;
     k_fill_f32<<<grid_for(count, kBlock), kBlock, 0, s>>>(p, v, count);
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ tracking ----------
+// the chained mode's share of a tracked rollout: see launch_track_shift
+__global__ __launch_bounds__(kBlock) void k_track_shift(Batch b, const float* __restrict__ state, StatsPtrs st,
+                                                        float* __restrict__ obs, TrackPtrs trk) {
+    const uint32_t i = env_index();
+    if (i >= b.n) return;
+    float tr[6], o[15];
+    track_row(trk.ref, trk.rows, st.steps[i], tr);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { o[j] = field(obs, j, b.ld)[i]; o[12 + j] = field(obs, (12 + j), b.ld)[i]; }
+    track_shift(tr, o);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { field(obs, j, b.ld)[i] = o[j]; field(obs, (12 + j), b.ld)[i] = o[12 + j]; }
+    if (!st.frozen[i]) {
+        trk.sq[i] = track_accumulate(trk.sq[i], field(state, 0, b.ld)[i], field(state, 1, b.ld)[i], field(state, 2, b.ld)[i], tr);
+        trk.steps[i] += 1;
+    }
+}
+
+hipError_t launch_track_shift(hipStream_t s, Batch b, const float* state, StatsPtrs st, float* obs, TrackPtrs trk) {
+    if (b.n == 0) return hipSuccess;
+    RQ_KLAUNCH(k_track_shift, grid_for(b.n, kBlock), kBlock, s, b, state, st, obs, trk);
+    return RQ_KLAUNCH_STATUS();
 }
 
 }  // namespace rq

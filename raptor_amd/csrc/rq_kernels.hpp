@@ -66,6 +66,14 @@ struct TrajPtrs {
     uint32_t t0;          // index of the first step this launch writes
 };
 
+// A tracked rollout (rq_rollout_track): the reference table and the env's two tracking statistics.
+struct TrackPtrs {
+    const float* ref;     // [rows][6] row-major: target position, target linear velocity (world frame); nullptr = untracked
+    uint32_t rows;
+    float* sq;            // [ld]: running sum of |p - p_ref|^2 over the steps taken
+    uint32_t* steps;      // [ld]: how many
+};
+
 // SampleAndSquash output stage of the actor (rq_policy_set_sample_and_squash): mode = rq_sample_and_squash_mode
 struct SasArgs {
     uint32_t mode;                // RQ_SAS_OFF / RQ_SAS_MEAN / RQ_SAS_SAMPLE
@@ -240,6 +248,16 @@ hipError_t launch_rollout_fused(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, 
                                 const float* params, float* state, float* hidden, const float* weights,
                                 const float* packed, StatsPtrs st, int precision, SasArgs sas, TrajPtrs traj,
                                 unsigned long long* span = nullptr);
+// the TRACK variant of the fused kernel (no SampleAndSquash stage)
+hipError_t launch_rollout_fused_track(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                      uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                      const float* params, float* state, float* hidden, const float* weights,
+                                      const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
+                                      unsigned long long* span = nullptr);
+// chained mode of a tracked rollout, between the observation's assembly (k_observe, or the k_step before) and the actor: the row of
+// each env's episode step count comes off obs [RQ_OBSERVATION_DIM][ld] in place, and the envs that are not frozen add this step's
+// tracking error - the fused kernel's arithmetic (rq_device_math.hpp track_*).  Appends a graph node under a GraphSink.
+hipError_t launch_track_shift(hipStream_t s, Batch b, const float* state, StatsPtrs st, float* obs, TrackPtrs trk);
 // chained mode: copy step t (env obs/action buffers + last reward / done code) into the trajectory
 hipError_t launch_record(hipStream_t s, Batch b, const float* obs, const float* act, StatsPtrs st, TrajPtrs traj);
 // ---- MFMA operand images of the policy (layout rationale: rq_device_math.hpp "actor") ----------

@@ -25,4 +25,11 @@ hipError_t launch_rollout_fused_16bit(hipStream_t s, const FusedArgs& a, bool no
     return hipGetLastError();
 }
 
+// the TRACK variant (rq_rollout_track; no SampleAndSquash stage)
+hipError_t launch_rollout_fused_track_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision) {
+    if (precision == RQ_POLICY_F16X2_MFMA) launch_fused_track_actor<ActorF16X2>(s, a, noise, ar);
+    else                                   launch_fused_track_actor<ActorBF16>(s, a, noise, ar);
+    return hipGetLastError();
+}
+
 }  // namespace rq

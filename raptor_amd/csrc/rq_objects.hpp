@@ -202,12 +202,14 @@ struct rq_env {
     DeviceBuffer<float> act;    // [RQ_ACTION_DIM][ld]
     DeviceBuffer<char> stats_block;
     rq::StatsPtrs st{};         // views into stats_block
+    DeviceBuffer<char> track_block;     // tracked rollouts' statistics, [ld] float sums then [ld] uint32 counts (env_track_stats: first use)
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
     // epoch-counter bump); one executable graph per distinct argument set
     struct GraphEntry {
         const float* params; float* state; float* hidden; const float* packed; const float* weights; const float* obs;
         uint32_t flags; int precision; rq_env_config cfg; uint64_t seed;
         int sas_mode; uint64_t sas_seed; const float* ls_image;
+        const float* ref; uint32_t ref_rows;     // tracked rollouts: the reference table (nullptr: untracked)
         hipGraphExec_t exec;
     };
     std::vector<GraphEntry> graphs;
@@ -248,6 +250,14 @@ struct rq_trajectory {
         DeviceBuffer<float> out;       // the loss-seeded calls: grad [2084] | losses [n_updates] before they go to the caller
         DeviceBuffer<unsigned long long> live;    // [1]: M, the live entries of the last loss
     } grad;
+};
+
+// a moving setpoint's table on the device (rq_reference_create)
+struct rq_reference {
+    const rq_device* dev = nullptr;     // compared, never followed: the device may be gone before its references
+    int ordinal = 0;
+    uint32_t rows = 0;
+    DeviceBuffer<float> d;              // [rows][6] row-major
 };
 
 struct rq_policy {
@@ -340,6 +350,8 @@ int state_fresh_buffer(rq_env* env, float** out);
 void state_release_buffer(rq_state* s);
 int state_make_private(rq_state* s, bool keep);
 inline rq::Batch batch_of(const rq_env* env) { return {env->n, env->ld, env->offset}; }
+// the env's tracking statistics, allocated and zeroed (on the device's stream) at their first use; call inside a DeviceScope
+int env_track_stats(rq_env* env, float** sum_sq, uint32_t** steps);
 
 // ---- rq_small_batch.cpp: the small-batch loop (rq_device::mailbox, obs_cache, spec) ----
 void small_batch_setup(rq_device* dev);      // rq_device_create: settings

@@ -37,7 +37,7 @@ from . import _lib
 from ._lib import (ACTION_DIM, OBSERVATION_DIM, PARAM_DIM, STATE_DIM, ROLLOUT_AUTORESET, ROLLOUT_CHAINED,
                    ROLLOUT_FUSED, EnvConfig, RaptorQuadError)
 
-__all__ = ["Device", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
+__all__ = ["Device", "Reference", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
 
 
 class UI:
@@ -146,6 +146,32 @@ class Device:
         lib = _lib.load()
         lib.rq_device_count(C.byref(n))
         return n.value
+
+
+def _reference_table(table):
+    """The table of a ``Reference`` as the C layer takes it, or ValueError: float32, C-contiguous, [rows >= 1, 6], finite."""
+    if not isinstance(table, np.ndarray) or table.dtype != np.float32:
+        raise ValueError("a reference table is a float32 NumPy array [rows, 6] (raptor_amd.tracking builds them)")
+    if table.ndim != 2 or table.shape[1] != 6 or table.shape[0] < 1:
+        raise ValueError(f"a reference table has shape [rows >= 1, 6]: target position, target velocity; got {table.shape}")
+    if not np.isfinite(table).all():
+        raise ValueError("a reference table holds finite entries only")
+    return np.ascontiguousarray(table)
+
+
+class Reference:
+    """A moving setpoint for ``vector.rollout(..., reference=ref)``: ``table`` [rows, 6] float32, columns 0..2 the target position and
+    3..5 the target linear velocity in the world frame (``raptor_amd.tracking.lissajous`` / ``hold``).  An env reads the row of its
+    own episode step count, so ``rows`` must cover ``episode_step_limit``.  The table is copied to ``device`` once, here."""
+
+    def __init__(self, device, table):
+        t = _reference_table(table)             # refused before the device is touched
+        h = C.c_void_p()
+        _lib.call("rq_reference_create", device._h, _lib.fptr(t), int(t.shape[0]), C.byref(h))
+        self._h = h
+        self._device = device
+        self.rows = int(t.shape[0])
+        self._fin = weakref.finalize(self, _lib.load().rq_reference_destroy, h)
 
 
 class _Handle:
@@ -352,6 +378,20 @@ class VectorModule:
 
             def reset_statistics(self):
                 _lib.call("rq_env_reset_statistics", self._require("environment"))
+
+            def tracking_error(self):
+                """-> (sum_sq [N] float32, steps [N] uint32): per env, the running sum of |p - p_ref|^2 over the steps it took in
+                tracked rollouts (``rollout(..., reference=ref)``; true position, at observe time) and their count.
+                ``reset_statistics`` zeroes both."""
+                sq, steps = np.empty(mod.N_ENVIRONMENTS, np.float32), np.empty(mod.N_ENVIRONMENTS, np.uint32)
+                _lib.call("rq_env_get_tracking_error", self._require("environment"), sq.ctypes.data, steps.ctypes.data, 0)
+                return sq, steps
+
+            def tracking_rmse(self):
+                """Root mean square distance to the setpoint per env, float64 [N] (NaN for an env that took no tracked step)."""
+                sq, steps = self.tracking_error()
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    return np.sqrt(sq.astype(np.float64) / steps)
 
         class _Container(_Handle):
             _create = None
@@ -585,14 +625,21 @@ class VectorModule:
                   state._require("VectorState"), None, next_state._ensure(env), rng._require("rng"), None)
 
     def rollout(self, device, env, params, state, policy, rng, n_steps, mode="fused", autoreset=False,
-                trajectory=None, teacher_ids=None):
+                trajectory=None, teacher_ids=None, reference=None):
         """The loop body README.md:95-99, ``n_steps`` times, entirely on the device; with
         ``trajectory`` every transition is also appended to that buffer.  ``policy`` is a ``Raptor`` or a
         ``raptor_amd.teachers.TeacherBank``; with a bank, ``teacher_ids`` ([N] integers) names the teacher that flies
-        each env (``mode="fused"``: fp32 banks of two hidden layers of 16 / 32 / 64 units; ``"chained"``: every bank)."""
+        each env (``mode="fused"``: fp32 banks of two hidden layers of 16 / 32 / 64 units; ``"chained"``: every bank).
+        ``reference`` (a ``Reference``): the policy tracks that moving setpoint - it sees position and linear velocity relative to
+        the row of each env's own episode step count; everything else (state, reward, termination, statistics) stays absolute, a
+        ``trajectory`` records what the policy saw, and ``env.tracking_error()`` accumulates.  ``Raptor`` policies only."""
+        if reference is not None and teacher_ids is not None:
+            raise ValueError("reference and teacher_ids do not combine: a TeacherBank rollout does not track")
         m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
         from .teachers import TeacherBank
         if isinstance(policy, TeacherBank):
+            if reference is not None:
+                raise ValueError("a TeacherBank rollout does not track a reference")
             if teacher_ids is None:
                 raise ValueError("a TeacherBank flies the envs by teacher_ids: one teacher id per env is required")
             ids = np.ascontiguousarray(teacher_ids, np.uint32)
@@ -604,6 +651,14 @@ class VectorModule:
             return
         if teacher_ids is not None:
             raise ValueError("teacher_ids belong to a TeacherBank rollout; a Raptor policy flies every env itself")
+        if reference is not None:
+            if not isinstance(reference, Reference):
+                raise ValueError("reference must be an l2f.Reference")
+            _lib.call("rq_rollout_track", device._h, env._require("environment"), params._require("VectorParameters"),
+                      state._require("VectorState"), policy._handle(device), rng._require("rng"), int(n_steps), m,
+                      ROLLOUT_AUTORESET if autoreset else 0,
+                      trajectory._require("trajectory") if trajectory is not None else None, reference._h)
+            return
         fast = _lib.fast
         if fast is not None and trajectory is None and state._mirror is None and hasattr(fast, "rollout"):
             status = fast.rollout(_lib.fn_addr("rq_rollout"), device._h, env._h, params._h, state._h, policy._handle(device), rng._h,
