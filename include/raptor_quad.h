@@ -78,7 +78,8 @@ extern "C" {
                               3 (round 4): rq_device_{set,get}_speculation, rq_device_last_rollout_clock; no struct changed
                               4 (round 5): rq_comm_describe (new struct rq_comm_description); rq_comm_info / rq_comm_create ask RCCL for
                               the communicator's own rank and size; rq_teacher_bank_create_layers
-                              5 (round 6): rq_device_{set,get}_resident; no struct changed */
+                              5 (round 6): rq_device_{set,get}_resident; no struct changed
+                              (still 5: rq_policy_{set,get}_native_interval added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -326,6 +327,27 @@ RQ_API int rq_policy_set_squash(rq_policy* pol, int enable);   /* = set_sample_a
 typedef enum rq_sample_and_squash_mode { RQ_SAS_OFF = 0, RQ_SAS_MEAN = 1, RQ_SAS_SAMPLE = 2 } rq_sample_and_squash_mode;
 RQ_API int rq_policy_set_sample_and_squash(rq_policy* pol, int mode, const float* log_std_weights,
                                     const float* log_std_bias, uint64_t seed);
+/* The native interval R of a policy flown faster than it was trained (the reference's deployment section: a 2.5 ms control
+ * interval against the 10 ms native one, "the native state progression in the policy is only triggered every 4 steps").
+ * R = 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL; 1 is the default and every call then does what it did before this entry point existed.
+ * This engine's definition [UPSTREAM-UNVERIFIED] (which phase upstream's executor calls native, and whether its tentative
+ * step starts before or after the last commit, are not in the reference tree):
+ *   the call with index k computes (a, h') = step(o, h) with the arithmetic of R = 1 and returns a;
+ *   h <- h' iff k % R == 0 (a native step); otherwise h stays, and the next call is again a tentative step from the last
+ *   committed state.
+ * k is, in rollouts (rq_rollout, rq_rollout_record, rq_rollout_track, both modes), the env's own episode step count at observe
+ * time - the count a tracked rollout indexes its table with: the first step of every episode is native, an env that auto-resets
+ * gets the initial hidden state and k = 0, a frozen env changes nothing, and the phase crosses launches in the env's step count;
+ * in rq_policy_evaluate_step, a per-policy call counter, one for the whole batch, that rq_policy_reset and this call rewind.
+ * The env side is untouched: the previous action in the observation stays the action last applied.
+ * Setting R keeps weights, precision and hidden state.  Refused, with rq_last_error naming the interval and nothing changed:
+ * R = 0 or above the maximum; R > 1 beside a SampleAndSquash stage (whichever is set second); and with R > 1
+ * rq_policy_evaluate_sequence, rq_policy_selftest, rq_trajectory_relabel, rq_trajectory_policy_forward / _backward /
+ * _loss_grad and rq_trajectory_distill - a recording does not carry the phase it started at, and training is at the native
+ * rate.  The small-batch loop neither speculates nor keeps a resident executor for such a policy: its calls are plain launches. */
+#define RQ_POLICY_MAX_NATIVE_INTERVAL 64
+RQ_API int rq_policy_set_native_interval(rq_policy* pol, uint32_t interval);
+RQ_API int rq_policy_get_native_interval(const rq_policy* pol, uint32_t* interval);
 /* hidden state h[B,16] <- initial_hidden_state (checkpoint.h:123); sized on first use */
 RQ_API int rq_policy_reset(rq_policy* pol);
 /* One recurrent step for a batch.  observation: host [batch, obs_stride] (first 22 columns

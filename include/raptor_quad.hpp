@@ -94,6 +94,9 @@ struct Raptor : detail::Handle<rq_policy, rq_policy_destroy> {
         check(rq_policy_evaluate_sequence(h, observation, steps, batch, obs_stride, action, RQ_DST_HOST));
     }
     void set_precision(rq_policy_precision p) { check(rq_policy_set_precision(h, p)); }
+    // the hidden state moves on every interval-th step (raptor_quad.h rq_policy_set_native_interval)
+    void set_native_interval(std::uint32_t interval) { check(rq_policy_set_native_interval(h, interval)); }
+    std::uint32_t native_interval() const { std::uint32_t r = 1; check(rq_policy_get_native_interval(h, &r)); return r; }
     // optional layers named by rl-tools (README.md:114,116), identity in the shipped checkpoint
     void set_standardize(const float* mean, const float* std) { check(rq_policy_set_standardize(h, mean, std)); }
     void set_sample_and_squash(rq_sample_and_squash_mode mode, const float* log_std_weights = nullptr,

@@ -20,7 +20,7 @@ int check_pair(rq_trajectory* t, rq_policy* pol, const char* what) {
                std::string(what) + ": the Standardize stage has no gradient here (disable it)");
     RQ_REQUIRE(pol->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
                std::string(what) + ": the SampleAndSquash stage has no gradient here (RQ_SAS_OFF)");
-    return RQ_OK;
+    return require_native_rate(pol, what);
 }
 
 int check_memory(int memory) {

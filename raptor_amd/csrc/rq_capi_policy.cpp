@@ -57,6 +57,13 @@ int policy_mirror(rq_policy* pol) {
     return RQ_OK;
 }
 
+int require_native_rate(const rq_policy* pol, const char* what) {
+    RQ_REQUIRE(pol->native_interval == 1, RQ_ERR_INVALID_ARGUMENT,
+               std::string(what) + ": defined at the native rate only, the policy's native interval is " +
+                   std::to_string(pol->native_interval) + " (rq_policy_set_native_interval(policy, 1))");
+    return RQ_OK;
+}
+
 int policy_images16(rq_policy* pol) {
     if (!pol->images16_stale) return RQ_OK;
     int rc = policy_mirror(pol); if (rc) return rc;
@@ -214,8 +221,33 @@ RQ_API int rq_policy_set_standardize(rq_policy* pol, const float* mean, const fl
 
 RQ_API int rq_policy_set_squash(rq_policy* pol, int enable) {
     RQ_REQUIRE(pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(!enable || pol->native_interval == 1, RQ_ERR_INVALID_ARGUMENT,
+               "the SampleAndSquash stage is not carried at a native interval above 1 (the policy's is " +
+                   std::to_string(pol->native_interval) + ")");
     pol->version = fresh_version();
     pol->sas_mode = enable ? RQ_SAS_MEAN : RQ_SAS_OFF;
+    return RQ_OK;
+}
+
+// The native interval R (include/raptor_quad.h): weights, precision and hidden state stay; the call counter starts again.  A resident
+// executor bound to the device is retired first (it knows R = 1 only), as rq_policy_set_weights does.
+RQ_API int rq_policy_set_native_interval(rq_policy* pol, uint32_t interval) {
+    RQ_REQUIRE(pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(interval >= 1 && interval <= RQ_POLICY_MAX_NATIVE_INTERVAL, RQ_ERR_INVALID_ARGUMENT,
+               "native interval " + std::to_string(interval) + " is outside 1 .. 64");
+    RQ_REQUIRE(interval == 1 || pol->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
+               "native interval " + std::to_string(interval) + ": an interval above 1 does not carry the SampleAndSquash stage (RQ_SAS_OFF)");
+    DeviceScope on_device(pol->dev); int rc = on_device.rc; if (rc) return rc;
+    if (device_registry(pol->dev, 0)) { rc = resident_retire(pol->dev); if (rc) return rc; }
+    pol->version = fresh_version();
+    pol->native_interval = interval;
+    pol->rate_counter = 0;
+    return RQ_OK;
+}
+
+RQ_API int rq_policy_get_native_interval(const rq_policy* pol, uint32_t* interval) {
+    RQ_REQUIRE(pol && interval, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *interval = pol->native_interval;
     return RQ_OK;
 }
 
@@ -224,6 +256,9 @@ RQ_API int rq_policy_set_sample_and_squash(rq_policy* pol, int mode, const float
     RQ_REQUIRE(pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
     pol->version = fresh_version();
     RQ_REQUIRE(mode == RQ_SAS_OFF || mode == RQ_SAS_MEAN || mode == RQ_SAS_SAMPLE, RQ_ERR_INVALID_ARGUMENT, "unknown mode");
+    RQ_REQUIRE(mode == RQ_SAS_OFF || pol->native_interval == 1, RQ_ERR_INVALID_ARGUMENT,
+               "the SampleAndSquash stage is not carried at a native interval above 1 (the policy's is " +
+                   std::to_string(pol->native_interval) + ")");
     if (mode == RQ_SAS_SAMPLE) {
         DeviceScope on_device(pol->dev); int rc = on_device.rc; if (rc) return rc;
         std::vector<float> image;
@@ -245,6 +280,7 @@ RQ_API int rq_policy_reset(rq_policy* pol) {
     DeviceScope on_device(pol->dev); int rc = on_device.rc; if (rc) return rc;
     pol->needs_reset = true;   // applied (h <- initial_hidden_state, checkpoint.h:123) on the next use
     pol->sas_counter = 0;
+    pol->rate_counter = 0;     // the next call is native
     return RQ_OK;
 }
 
@@ -261,7 +297,8 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
     if (observation) RQ_REQUIRE(obs_stride >= RQ_POLICY_INPUT_DIM, RQ_ERR_INVALID_ARGUMENT, "obs_stride < 22");
     DeviceScope on_device(pol->dev, rq::KeepResident{}); int rc = on_device.rc; if (rc) return rc;
     rq_device* dev = pol->dev;
-    if (observation && action && !env && batch < kGpuLayoutMinEnvs) {
+    const bool rated = pol->native_interval > 1;      // never speculated, never resident: plain launches of k_actor_step_rate
+    if (observation && action && !env && batch < kGpuLayoutMinEnvs && !rated) {
         bool hit = false;
         rc = speculation_take(dev, pol, observation, batch, obs_stride, action, &hit); if (rc || hit) return rc;
     }
@@ -271,7 +308,7 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
     // (rq_resident.cpp): retired before anything else touches the device, replayed as a launch if it had left.
     ResidentExecutor& rx = dev->resident;
     const bool pol_eligible = rx.enabled && observation && action && !env && batch <= rq::kResidentPolicyBatch &&
-                              pol->precision == RQ_POLICY_FP32 && pol->sas_mode == RQ_SAS_OFF;
+                              pol->precision == RQ_POLICY_FP32 && pol->sas_mode == RQ_SAS_OFF && !rated;
     const uint64_t now_ns = pol_eligible ? host_now_ns() : 0;
     // in a row = the same policy at the same batch: two policies evaluated in turns (a student and a teacher on the same rows) would
     // otherwise retire each other's kernel call after call.  Stored below, once the call has gone the one way or the other.
@@ -316,9 +353,16 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
     const uint32_t ld_act = action ? pol->ld : env->ld;
     rq::Mailbox mb{};
     if (mailbox) mb = mailbox_for(dev, rows_in, RQ_POLICY_INPUT_DIM, action ? MbOut::out : MbOut::none);
-    RQ_HIP_MB(rq::launch_actor_step(dev->stream, batch, packed_of(pol), d_obs, ld_obs, pol->hidden, pol->ld, d_act,
-                                    ld_act, nullptr, pol->precision,
-                                    sas_of(pol, pol->sas_counter, nullptr, env ? env->offset : 0), mb), dev, mb);
+    if (rated) {
+        RQ_HIP_MB(rq::launch_actor_step_rate(dev->stream, batch, packed_of(pol), d_obs, ld_obs, pol->hidden, pol->ld, d_act, ld_act,
+                                             nullptr, pol->precision, nullptr, pol->native_interval,
+                                             pol->rate_counter % pol->native_interval == 0 ? 1u : 0u, mb), dev, mb);
+        pol->rate_counter += 1;
+    } else {
+        RQ_HIP_MB(rq::launch_actor_step(dev->stream, batch, packed_of(pol), d_obs, ld_obs, pol->hidden, pol->ld, d_act,
+                                        ld_act, nullptr, pol->precision,
+                                        sas_of(pol, pol->sas_counter, nullptr, env ? env->offset : 0), mb), dev, mb);
+    }
     if (pol->sas_mode == RQ_SAS_SAMPLE) pol->sas_counter += 1;
     if (action && mailbox) return mailbox_copy_out(dev, mb.seq, mb.rows_out, action, (size_t)batch * RQ_ACTION_DIM);
     if (action) return soa_to_host(dev, pol->act, batch, pol->ld, RQ_ACTION_DIM, action);
@@ -333,6 +377,7 @@ RQ_API int rq_policy_evaluate_sequence(rq_policy* pol, const float* observation,
     RQ_REQUIRE(memory >= RQ_DST_HOST && memory <= RQ_DST_DEVICE_ASYNC, RQ_ERR_INVALID_ARGUMENT, "memory must be 0, 1 or 2");
     RQ_REQUIRE(pol->sas_mode != RQ_SAS_SAMPLE, RQ_ERR_INVALID_ARGUMENT,
                "sequence evaluation is a deterministic pass: RQ_SAS_SAMPLE is defined for evaluate_step and rollouts");
+    { const int rate_rc = require_native_rate(pol, "rq_policy_evaluate_sequence"); if (rate_rc) return rate_rc; }
     if (memory != RQ_DST_HOST)      // the kernel moves rows with 8-byte loads and actions with 16-byte stores
         RQ_REQUIRE((reinterpret_cast<uintptr_t>(observation) & 7u) == 0 && (reinterpret_cast<uintptr_t>(action) & 15u) == 0,
                    RQ_ERR_INVALID_ARGUMENT, "device tensors must be 8-byte (observation) / 16-byte (action) aligned");
@@ -374,6 +419,7 @@ RQ_API int rq_policy_selftest(rq_policy* pol, const float* input, const float* e
                        float tolerance, float* max_abs_err) {
     RQ_REQUIRE(pol && input && expected, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(steps > 0 && batch > 0, RQ_ERR_INVALID_ARGUMENT, "empty test");
+    { const int rate_rc = require_native_rate(pol, "rq_policy_selftest"); if (rate_rc) return rate_rc; }
     // runs on a private policy object so the caller's hidden state is untouched
     rq_policy* tmp = nullptr;
     int rc = policy_mirror(pol); if (rc) return rc;

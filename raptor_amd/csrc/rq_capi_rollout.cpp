@@ -80,6 +80,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
         RQ_REQUIRE(policy->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
                    "tracked rollouts do not carry the SampleAndSquash stage");
     }
+    const uint32_t interval = policy->native_interval;      // above 1: the RATE kernels (a SampleAndSquash stage cannot be set beside it)
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = policy_size(policy, env->n); if (rc) return rc;
     RQ_REQUIRE(policy->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy batch does not match the env");
@@ -98,7 +99,11 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
             RQ_HIP(dev->k_span.reserve(dev->stream, (size_t)waves * 5));
             dev->k_span_used = waves;
         }
-        if (ref) {
+        if (interval > 1) {
+            RQ_HIP(rq::launch_rollout_fused_rate(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
+                                                 params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
+                                                 policy->precision, tp, trk, interval, dev->k_timing ? dev->k_span.get() : nullptr));
+        } else if (ref) {
             RQ_HIP(rq::launch_rollout_fused_track(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
                                                   params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
                                                   policy->precision, tp, trk, dev->k_timing ? dev->k_span.get() : nullptr));
@@ -124,7 +129,11 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                 e = rq::launch_observe(dev->stream, b, nc, noise, rng->seed, epoch, epoch_base, params->d, state->d, env->obs);
             if (e == hipSuccess && ref)
                 e = rq::launch_track_shift(dev->stream, b, state->d, env->st, env->obs, trk);
-            if (e == hipSuccess)
+            if (e == hipSuccess && interval > 1)     // the env's episode step count is that of this step's observation: k_step moves it on
+                e = rq::launch_actor_step_rate(dev->stream, env->n, packed_of(policy), env->obs, env->ld, policy->hidden,
+                                               policy->ld, env->act, env->ld, env->st.frozen, policy->precision, env->st.steps,
+                                               interval, 0u);
+            else if (e == hipSuccess)
                 e = rq::launch_actor_step(dev->stream, env->n, packed_of(policy), env->obs, env->ld, policy->hidden,
                                           policy->ld, env->act, env->ld, env->st.frozen, policy->precision,
                                           sas_of(policy, epoch, epoch_base, env->offset));
@@ -153,6 +162,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                     g.packed == packed_of(policy) && g.weights == policy->w_dev && g.flags == flags &&
                     g.precision == policy->precision && g.seed == rng->seed && g.sas_mode == policy->sas_mode &&
                     g.sas_seed == policy->sas_seed && g.ls_image == policy->ls_image && g.ref == trk.ref && g.ref_rows == trk.rows &&
+                    g.interval == interval &&
                     std::memcmp(&g.cfg, &env->cfg, sizeof(rq_env_config)) == 0) { exec = g.exec; break; }
             if (!exec) {
                 // Built node by node (rq_kernels.hpp GraphSink), NOT by stream capture: while any stream of a process captures, HIP
@@ -185,7 +195,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                     try {                       // nothing throws across the boundary
                         env->graphs.push_back({params->d, state->d, policy->hidden, packed_of(policy), policy->w_dev, env->obs, flags,
                                                policy->precision, env->cfg, rng->seed, policy->sas_mode, policy->sas_seed,
-                                               policy->ls_image, trk.ref, trk.rows, exec});
+                                               policy->ls_image, trk.ref, trk.rows, interval, exec});
                     } catch (const std::bad_alloc&) {
                         (void)hipGraphExecDestroy(exec);
                         return fail(RQ_ERR_OUT_OF_MEMORY, "rollout: host allocation failed");
@@ -334,6 +344,7 @@ RQ_API int rq_trajectory_relabel(rq_trajectory* t, rq_policy* pol, float* action
     RQ_REQUIRE(pol->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy lives on another device");
     RQ_REQUIRE(pol->sas_mode != RQ_SAS_SAMPLE, RQ_ERR_INVALID_ARGUMENT,
                "relabelling is a deterministic pass: RQ_SAS_SAMPLE is defined for evaluate_step and rollouts");
+    { const int rate_rc = require_native_rate(pol, "rq_trajectory_relabel"); if (rate_rc) return rate_rc; }
     if (t->length == 0) return RQ_OK;
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     rc = policy_size(pol, env->n); if (rc) return rc;

@@ -1208,3 +1208,85 @@ hipError_t launch_track_shift(hipStream_t s, Batch b, const float* state, StatsP
 
 // the learner's kernels (forward with saved state, reverse pass, reduction): their own file, compiled in this unit
 #include "rq_grad.hpp"
+
+namespace rq {
+
+// ------------------------------------------------------------------ native interval above 1 (rq_policy_set_native_interval) ---
+// Everything below serves policies whose hidden state moves on every native_interval-th step only, and stands at the END of this
+// unit (behind the learner's kernels too) on purpose: the compiler numbers a unit's functions in the order it meets them, the numbers appear in every label of a listing,
+// and the listings of the kernels above are to stay what they were before these existed.
+// k_actor_step under a native interval above 1 (launch_actor_step_rate): the same loads, the same ACTOR::step, the same action
+// stores - and the hidden state written back only for the rows at a native step.  A kernel of its own: k_actor_step is compiled from what it
+// was compiled from before.
+template <typename ACTOR>
+__global__ __launch_bounds__(kBlock, 2) void k_actor_step_rate(uint32_t n, const float* __restrict__ packed,
+                                                            const float* __restrict__ obs, uint32_t ld_obs,
+                                                            float* hidden, uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
+                                                            const uint8_t* __restrict__ frozen,
+                                                            const uint32_t* __restrict__ steps, uint32_t interval, uint32_t native,
+                                                            Mailbox mb) {
+    ACTOR actor;
+    actor.template load<kBlock / 64>(packed);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave_base = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64;
+    if (wave_base >= n) { mailbox_signal(mb); return; }          // wave-uniform
+    const uint32_t i0 = wave_base + lane;
+    const uint32_t i = i0 < n ? i0 : n - 1;
+    float x[22], hQ[4][4], a[4];
+    if (mb.rows_in != nullptr) {         // wave-uniform (kernel argument)
+#pragma unroll
+        for (int k = 0; k < 22; ++k) x[k] = mb.rows_in[(size_t)i * mb.in_stride + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
+    }
+    load_hidden_q(hidden, ld_h, wave_base, n, hQ);
+    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
+    const bool commit = (i0 < n) && fz == 0;
+    const bool at_native = steps != nullptr ? steps[i] % interval == 0 : native != 0;
+    const uint64_t hidden_mask = __builtin_amdgcn_ballot_w64(commit && at_native);
+    actor.step(x, hQ, a);
+    store_hidden_q(hidden, ld_h, wave_base, hidden_mask, hQ);
+    if (commit) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
+        if (mb.rows_out != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) mb.rows_out[(size_t)i * 4 + k] = a[k];
+        }
+    }
+    mailbox_signal(mb);
+}
+
+hipError_t launch_actor_step_rate(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
+                                  float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
+                                  int precision, const uint32_t* steps, uint32_t interval, uint32_t native, Mailbox mb) {
+    if (n == 0) return hipSuccess;
+    const unsigned grid = grid_for((n + 63) / 64 * 64, kBlock);
+#define RQ_LAUNCH_ACTOR(ACT) RQ_KLAUNCH(k_actor_step_rate<ACT>, grid, kBlock, s, n, packed, obs, ld_obs, hidden, ld_h, act, ld_act, frozen, \
+                                        steps, interval, native, mb)
+    if (precision == RQ_POLICY_F16X2_MFMA)     RQ_LAUNCH_ACTOR(ActorF16X2);
+    else if (precision == RQ_POLICY_BF16_MFMA) RQ_LAUNCH_ACTOR(ActorBF16);
+    else                                       RQ_LAUNCH_ACTOR(ActorF32Lean);   // launch_actor_step's build: the same bits
+#undef RQ_LAUNCH_ACTOR
+    return RQ_KLAUNCH_STATUS();
+}
+
+hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                     const float* params, float* state, float* hidden, const float* weights,
+                                     const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
+                                     uint32_t interval, unsigned long long* span) {
+    if (b.n == 0 || n_steps == 0) return hipSuccess;
+    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, packed, st, traj, SasArgs{}, span, trk, interval};
+    if (precision == RQ_POLICY_F16X2_MFMA || precision == RQ_POLICY_BF16_MFMA)
+        return launch_rollout_fused_rate_16bit(s, a, noise, ar, precision);
+    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
+    const bool rec = traj.obs != nullptr, track = trk.ref != nullptr;
+    if (b.n > 65536u) launch_fused_rate_actor<ActorF32Lean>(s, a, noise, ar, rec, track);
+    else              launch_fused_rate_actor<ActorF32>(s, a, noise, ar, rec, track);
+    return hipGetLastError();
+}
+
+}  // namespace rq

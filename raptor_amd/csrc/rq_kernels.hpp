@@ -185,6 +185,13 @@ inline uint32_t actor_groups_per_wave(uint32_t n) {
 hipError_t launch_actor_step(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
                              float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
                              int precision, SasArgs sas, Mailbox mb = Mailbox{}, const float* hidden_in = nullptr);
+// The same step under a native interval above 1 (rq_policy_set_native_interval): the actions are written as above, the hidden state
+// only for the rows at a native step - steps != nullptr: row i iff steps[i] % interval == 0 (the chained rollout: the env's episode
+// step count at observe time); steps == nullptr: every row iff native != 0 (evaluate_step: one call counter for the batch).
+// One 64-env group per wave at every batch size.
+hipError_t launch_actor_step_rate(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
+                                  float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
+                                  int precision, const uint32_t* steps, uint32_t interval, uint32_t native, Mailbox mb = Mailbox{});
 // Raptor over a sequence: obs [steps][n][stride] (first 22 columns) -> act [steps][n][4], both row-major on
 // the device; hidden [16][ld_h] is the state before step 0 on entry and after the last step on return
 hipError_t launch_actor_sequence(hipStream_t s, uint32_t n, uint32_t steps, const float* packed, const float* obs,
@@ -254,6 +261,13 @@ hipError_t launch_rollout_fused_track(hipStream_t s, Batch b, StepCfg c, NoiseCf
                                       const float* params, float* state, float* hidden, const float* weights,
                                       const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
                                       unsigned long long* span = nullptr);
+// the RATE variant of the fused kernel: the hidden state moves on at the steps whose episode step count is a
+// multiple of `interval`; tracked when trk.ref != nullptr; no SampleAndSquash stage
+hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                     const float* params, float* state, float* hidden, const float* weights,
+                                     const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
+                                     uint32_t interval, unsigned long long* span = nullptr);
 // chained mode of a tracked rollout, between the observation's assembly (k_observe, or the k_step before) and the actor: the row of
 // each env's episode step count comes off obs [RQ_OBSERVATION_DIM][ld] in place, and the envs that are not frozen add this step's
 // tracking error - the fused kernel's arithmetic (rq_device_math.hpp track_*).  Appends a graph node under a GraphSink.

@@ -210,6 +210,7 @@ struct rq_env {
         uint32_t flags; int precision; rq_env_config cfg; uint64_t seed;
         int sas_mode; uint64_t sas_seed; const float* ls_image;
         const float* ref; uint32_t ref_rows;     // tracked rollouts: the reference table (nullptr: untracked)
+        uint32_t interval;                       // the policy's native interval: the actor nodes of another one are other kernels
         hipGraphExec_t exec;
     };
     std::vector<GraphEntry> graphs;
@@ -274,6 +275,8 @@ struct rq_policy {
     int sas_mode = RQ_SAS_OFF;        // SampleAndSquash output stage
     uint64_t sas_seed = 0;
     uint32_t sas_counter = 0;         // sampling step of the next rq_policy_evaluate_step call
+    uint32_t native_interval = 1;     // rq_policy_set_native_interval: the hidden state moves on every native_interval-th step
+    uint32_t rate_counter = 0;        // index k of the next rq_policy_evaluate_step call (native iff k % native_interval == 0)
     DeviceBuffer<float> ls_image;     // rq::RQ_LOGSTD_FLOATS (log-std head operands), allocated on first use
     int precision = RQ_POLICY_FP32;
     uint32_t batch = 0, ld = 0;   // 0 = not sized yet
@@ -393,6 +396,9 @@ const float* packed_of(const rq_policy* pol);
 int policy_size(rq_policy* pol, uint32_t batch);
 int policy_mirror(rq_policy* pol);       // w_host / w_eff <- w_dev after a device-side update (one 8 KB copy; nothing to do otherwise)
 int policy_images16(rq_policy* pol);     // the bf16 / f16x2 images repacked from the weights if an update left them behind
+// what is defined at the native rate only (sequence evaluation, relabelling, the learner, the self test) refuses a policy whose
+// native interval is above 1: a recording does not carry the phase it started at
+int require_native_rate(const rq_policy* pol, const char* what);
 
 // ---- rq_capi_rollout.cpp ----
 // What a rollout of either kind (a policy's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope: the checks

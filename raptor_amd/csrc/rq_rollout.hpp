@@ -66,8 +66,9 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const float* __restrict__ packed, StatsPtrs st,
                                                                TrajPtrs traj, SasArgs sas,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool TRACK = false;
+    constexpr bool TRACK = false, RATE = false;
     constexpr TrackPtrs trk{};
+    constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
 
@@ -84,7 +85,27 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const float* __restrict__ packed, StatsPtrs st,
                                                                TrajPtrs traj, TrackPtrs trk,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool TRACK = true, SAS = false;
+    constexpr bool TRACK = true, SAS = false, RATE = false;
+    constexpr SasArgs sas{};
+    constexpr uint32_t interval = 1;
+#include "rq_rollout_body.inc"
+}
+
+// The RATE variant (rq_policy_set_native_interval above 1): the same loop with the policy's hidden state moving on only at an env's
+// native steps - those whose episode step count is a multiple of `interval` - and the action of every other step computed from the
+// last committed state.  Tracked or not (trk.ref), no SampleAndSquash stage (the host refuses the pair).  Instantiated at
+// the end of the two translation units, behind everything else they hold.
+template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_rate(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ packed, StatsPtrs st,
+                                                               TrajPtrs traj, TrackPtrs trk, uint32_t interval,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool RATE = true, SAS = false;
     constexpr SasArgs sas{};
 #include "rq_rollout_body.inc"
 }
@@ -100,6 +121,7 @@ struct FusedArgs {
     const float* params; float* state; float* hidden; const float* weights; const float* packed;
     StatsPtrs st; TrajPtrs traj; SasArgs sas; unsigned long long* span;
     TrackPtrs trk;             // ref != nullptr: the TRACK variant
+    uint32_t interval;         // the RATE variant's native interval (launch_rollout_fused_rate)
 };
 
 // the 16-bit actors' instantiations (rq_kernels_16bit.hip)
@@ -132,6 +154,23 @@ inline void launch_fused_track_actor(hipStream_t s, const FusedArgs& a, bool noi
     if (noise) { if (ar) RQ_FUSED_RC(true, true); else RQ_FUSED_RC(true, false); }
     else       { if (ar) RQ_FUSED_RC(false, true); else RQ_FUSED_RC(false, false); }
 #undef RQ_FUSED_RC
+}
+
+// the RATE variant's instantiations for the 16-bit actors (rq_kernels_16bit.hip)
+hipError_t launch_rollout_fused_rate_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision);
+
+// the RATE instantiation for (noise, auto-reset, recording, tracking) of one actor build: one run-time switch per call
+template <typename ACTOR, bool NZ, bool AR, bool RC, bool TK>
+inline void launch_fused_rate_actor(hipStream_t s, const FusedArgs& a) {
+    const unsigned g = (a.b.n + kFusedBlock - 1) / kFusedBlock;
+    hipLaunchKernelGGL((k_rollout_fused_rate<NZ, AR, RC, TK, ACTOR>), dim3(g), dim3(kFusedBlock), 0, s,
+                       a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
+                       a.st, a.traj, a.trk, a.interval, a.span);
+}
+template <typename ACTOR, bool... DONE, typename... REST>
+inline void launch_fused_rate_actor(hipStream_t s, const FusedArgs& a, bool next, REST... rest) {
+    if (next) launch_fused_rate_actor<ACTOR, DONE..., true>(s, a, rest...);
+    else      launch_fused_rate_actor<ACTOR, DONE..., false>(s, a, rest...);
 }
 
 // the instantiation for (noise, auto-reset, recording) of one actor build; SAS = with the SampleAndSquash output stage

@@ -1,9 +1,9 @@
 // rq_rollout_body.inc - the body of the fused rollout kernel, included once per entry point by rq_rollout.hpp: k_rollout_fused
-// (TRACK = false) and k_rollout_fused_track (TRACK = true, SAS = false).  Text, not a function: the untracked kernel is compiled from
+// (TRACK = false), k_rollout_fused_track (TRACK = true, SAS = false) and k_rollout_fused_rate (RATE = true, SAS = false).  Text, not a function: the untracked kernel is compiled from
 // exactly what it was compiled from when the body stood between its braces - its listing does not move when the tracked variant
 // changes - and a __device__ function in between does cost that (the work-group-size folds of a kernel are made before inlining).
-// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, ACTOR and the names
-// b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, span.
+// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, ACTOR and the names
+// b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, interval, span.
     // kernel-level timing (rq_device_set_rollout_timing): every wave leaves the wall-clock ticks (constant rate) at which it
     // came in and went out, and its XCD: the eight dies' counters are offset against one another by microseconds, one die's
     // are consistent - the host takes first-in / last-out per die
@@ -39,6 +39,10 @@
     float trk_sq = 0.0f;
     uint32_t trk_n = 0;
     if constexpr (TRACK) { trk_sq = trk.sq[i]; trk_n = trk.steps[i]; }
+    // RATE (rq_policy_set_native_interval): the env's episode step count modulo the native interval - the launch's only division.
+    // The hidden state moves on at the steps where it is 0; at the others the policy acts from the last committed state.
+    [[maybe_unused]] uint32_t phase = 0;
+    if constexpr (RATE) phase = ep_steps % interval;
     const uint8_t last_t_raw = st.last_terminated[i];
     uint8_t last_d = AUTORESET ? (uint8_t)0 : st.last_done[i];       // auto-reset: rebuilt in the epilogue
     const uint8_t frozen_raw = st.frozen[i];
@@ -170,6 +174,13 @@
         for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) hn[tt][r] = hQ[tt][r];
+        // RATE: the envs at a native step, and what the actor carries for the others (it is theirs again after the step)
+        [[maybe_unused]] uint64_t native = ~0ull;
+        [[maybe_unused]] typename ACTOR::Saved held{};
+        if constexpr (RATE) {
+            native = __builtin_amdgcn_ballot_w64(phase == 0);
+            held = actor.carry_of(carry);
+        }
         // Trajectory stores (RECORD): one coalesced 256-byte store per field per wave; buffer stores: resource = this
         // step's block of the trajectory (base moved on the SALU), scalar offset = field row, vector offset = the
         // lane's env - no per-lane 64-bit address arithmetic, no per-lane pointers kept alive across the loop; lanes
@@ -197,7 +208,10 @@
             for (int j = 0; j < 4; ++j)
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, a[j]), ra, lane_off, (uint32_t)j * row, kNtTrajAux);
         }
-        if (AUTORESET) {
+        if constexpr (RATE) {
+            select_hidden_q(AUTORESET ? native : live & native, hn, hQ);      // a tentative step leaves the hidden state alone
+            actor.hold_carry(~native, held, carry);
+        } else if (AUTORESET) {
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
@@ -233,6 +247,7 @@
             last_r = r; last_t = term;
             ep_ret += r;
             ep_steps += 1;
+            if constexpr (RATE) { phase += 1; phase = phase >= interval ? 0u : phase; }
             // ONE compare whose result is the ballot (a termination counts as the limit reached): the ballot of an OR of
             // two lane masks is rebuilt by the compiler from a 0 / 1 select and a compare
             // (opaque, or the compiler turns the select + compare back into the OR)
@@ -249,6 +264,7 @@
             last_r = r; last_t = term;
             ep_ret += r;
             ep_steps += 1;
+            if constexpr (RATE) { phase += 1; phase = phase >= interval ? 0u : phase; }
             ended = term || ep_steps >= c.episode_step_limit;
             done_code = term ? 1 : (ended ? 2 : 0);
             last_d = done_code;
@@ -263,6 +279,7 @@
                 }
                 ep_ret = 0.0f;
                 ep_steps = 0;
+                if constexpr (RATE) phase = 0;
                 frozen = true;
             }
         }
@@ -286,6 +303,7 @@
                     }
                     ep_ret = 0.0f;
                     ep_steps = 0;
+                    if constexpr (RATE) phase = 0;      // the first step of every episode is native
                 }
                 if constexpr (kAhead) {
                     if ((ended_mask & ~pre_mask) != 0) refill();      // wave-uniform; rare (see above)

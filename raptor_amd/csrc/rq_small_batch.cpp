@@ -164,7 +164,7 @@ rq_policy* speculation_candidate(rq_device* dev, const rq_env* env, bool cache_o
     const Speculation& sp = dev->spec;
     rq_policy* pol = sp.enabled && !sp.suspended && action ? sp.last_policy : nullptr;
     return pol && policy_registry(pol, 0) && pol->dev == dev && pol->batch == env->n && pol->ld == env->ld && pol->hidden &&
-           pol->hidden_alt && !pol->needs_reset && pol->sas_mode != RQ_SAS_SAMPLE ? pol : nullptr;
+           pol->hidden_alt && !pol->needs_reset && pol->sas_mode != RQ_SAS_SAMPLE && pol->native_interval == 1 ? pol : nullptr;
 }
 
 // evaluate_step of pol on host rows, before anything is launched.  *hit: rq_step speculated exactly this call, `action` holds the result.

@@ -50,12 +50,18 @@ class Raptor:
     (BASELINE config 5: bf16 operands on v_mfma_f32_16x16x32_bf16, fp32 accumulate and gates;
     ~2e-2 max abs action deviation on the KATs) or "f16x2" (every operand as two f16 pieces on
     v_mfma_f32_16x16x32_f16: fp32-grade results, KATs to ~1e-6, at close to the bf16 actor's speed; not fp32
-    arithmetic, so not the default)."""
+    arithmetic, so not the default).
 
-    def __init__(self, device=None, weights=None, precision="fp32"):
+    ``native_interval``: R, 1 to 64.  The policy was trained at 100 Hz; flown at R times that (``dt = 0.01 / R``) its hidden
+    state moves on every R-th step only - in rollouts the steps of an episode whose count is a multiple of R, in
+    ``evaluate_step`` every R-th call since ``reset()`` - and the other steps act from the last committed state
+    (``include/raptor_quad.h`` rq_policy_set_native_interval; 1, the default, is the native rate)."""
+
+    def __init__(self, device=None, weights=None, precision="fp32", native_interval=1):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
         self._precision = precision
+        self._native_interval = self._checked_interval(native_interval)
         self._weights = load_weights() if weights is None else np.ascontiguousarray(weights, np.float32)
         if self._weights.size != POLICY_NUM_WEIGHTS:
             raise ValueError(f"expected {POLICY_NUM_WEIGHTS} weights")
@@ -102,6 +108,8 @@ class Raptor:
             self._h = h
             self._fin = weakref.finalize(self, _lib.load().rq_policy_destroy, h)
             _lib.call("rq_policy_set_precision", h, PRECISIONS[self._precision])
+            if self._native_interval != 1:
+                _lib.call("rq_policy_set_native_interval", h, self._native_interval)
         elif device is not None and device is not self._device:
             raise _lib.RaptorQuadError(-5, "policy was created on another device")
         return self._h
@@ -124,6 +132,23 @@ class Raptor:
         self._precision = precision
         if self._h is not None:
             _lib.call("rq_policy_set_precision", self._h, PRECISIONS[precision])
+
+    @staticmethod
+    def _checked_interval(interval):
+        if int(interval) != interval or not 1 <= int(interval) <= 64:
+            raise ValueError(f"native interval must be an integer from 1 to 64, not {interval!r}")
+        return int(interval)
+
+    @property
+    def native_interval(self):
+        return self._native_interval
+
+    @native_interval.setter
+    def native_interval(self, interval):
+        interval = self._checked_interval(interval)
+        if self._h is not None:       # (refused beside a SampleAndSquash stage: the policy then keeps the interval it had)
+            _lib.call("rq_policy_set_native_interval", self._h, interval)
+        self._native_interval = interval
 
     def set_weights(self, weights):
         """New parameters, 2 084 float32 in the checkpoint order (a NumPy array or any torch tensor, on the host or a device): the
