@@ -79,7 +79,8 @@ extern "C" {
                               4 (round 5): rq_comm_describe (new struct rq_comm_description); rq_comm_info / rq_comm_create ask RCCL for
                               the communicator's own rank and size; rq_teacher_bank_create_layers
                               5 (round 6): rq_device_{set,get}_resident; no struct changed
-                              (still 5: rq_policy_{set,get}_native_interval added, no struct changed) */
+                              (still 5: rq_policy_{set,get}_native_interval added, no struct changed)
+                              (still 5: rq_policy_bank_* and rq_rollout_policies added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -555,6 +556,43 @@ RQ_API int rq_teacher_bank_evaluate(rq_teacher_bank* bank, rq_env* env, const ui
  * env, a trajectory without room for n_steps, an unknown mode or flag, fused mode on a bank it does not run. */
 RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
                                const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                               rq_trajectory* trajectory);
+
+/* ---- Policy bank: many student policies in ONE rollout, one per wave.  Post-training writes a checkpoint per epoch and its
+ * users pick the student by closed-loop return, episode length and share terminated; sweeps and seed populations ask the same
+ * question.  A bank holds P policies of the Raptor topology (fp32; no Standardize stage, no SampleAndSquash stage, native interval
+ * 1) as P operand images - the image rq_policy_pack_image returns for RQ_POLICY_FP32, slot after slot on the device - and a
+ * rollout flies every aligned block of 64 envs with the policy named for it: a block is one wave, the weights are that wave's
+ * MFMA operands, so 1 000 checkpoints x 64 quadrotors is one launch of 64 000 envs.
+ * weights: [n_policies][2084], each block in the checkpoint order of rq_policy_create. */
+typedef struct rq_policy_bank rq_policy_bank;
+RQ_API int rq_policy_bank_create(rq_device* dev, const float* weights, uint32_t n_policies, rq_policy_bank** out);
+RQ_API int rq_policy_bank_destroy(rq_policy_bank* bank);
+/* New parameters for policy `index` (2084 floats): its slot is repacked in place, after the device's stream has drained; the
+ * bank then computes what a bank created with these weights computes.  The hidden state stays. */
+RQ_API int rq_policy_bank_set_weights(rq_policy_bank* bank, uint32_t index, const float* weights);
+/* The bank's hidden state [n_envs, 16] is sized by the first rollout, as a policy's is by its first batch.  The initial state of
+ * an env is its OWN policy's initial_hidden_state, so a reset is applied by the next use that knows the assignment: the next
+ * rq_rollout_policies, or rq_policy_bank_get_hidden with the assignment of the last rollout.  rq_policy_bank_get_hidden before
+ * the first rollout is RQ_ERR_NOT_INITIALIZED, with another batch than the last rollout's RQ_ERR_SHAPE_MISMATCH. */
+RQ_API int rq_policy_bank_reset(rq_policy_bank* bank);
+RQ_API int rq_policy_bank_get_hidden(rq_policy_bank* bank, float* host_out, uint32_t batch); /* [batch,16] */
+/* The loop body README.md:95-99 x n_steps with env i flown by policy policy_id[i] (host array, one id per env) of the bank:
+ * rq_rollout / rq_rollout_record's semantics point for point (observation noise by (rng epoch + step, env id), the epoch advanced
+ * by n_steps; statistics and finished-episode records; RQ_ROLLOUT_AUTORESET re-samples in place and resets the env's policy state
+ * to its policy's initial state, without it an ended env freezes and a later auto-reset rollout thaws it; done codes 0 / 1 / 2 /
+ * 4).  trajectory: NULL, or a buffer of this env the rollout appends to.  What env i computes is, bit for bit, what rq_rollout
+ * computes for it with a policy created from the weights of policy_id[i].
+ * GRANULARITY IS THE WAVE: policy_id must be constant on every aligned block of 64 local env indices (the ragged last block is one
+ * block); raptor_amd.policy_bank.block_policy_assignment deals blocks round-robin.
+ * mode RQ_ROLLOUT_FUSED: one launch (k_rollout_fused_bank: k_rollout_fused with the image chosen per wave).  RQ_ROLLOUT_CHAINED:
+ * observe -> actor step -> step (-> record) per step, plain launches; fused and chained give the same bits.  Refused before
+ * anything is enqueued (state, rng epoch, statistics and trajectory untouched): an id >= n_policies or ids that differ inside a
+ * block (RQ_ERR_INVALID_ARGUMENT), a bank / trajectory of another device or env (RQ_ERR_SHAPE_MISMATCH), a trajectory without
+ * room for n_steps, an unknown mode or flag (RQ_ERR_INVALID_ARGUMENT).  The per-block id table is cached in the bank: calls with
+ * the same ids upload nothing.  Not offered with a bank: bf16 / f16x2, tracking, a native interval above 1, relabelling. */
+RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
+                               const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                rq_trajectory* trajectory);
 
 

@@ -198,6 +198,12 @@ _SIGNATURES = {
     "rq_trajectory_relabel_teachers": [_vp, _vp, _vp, _fp, C.c_int],
     "rq_teacher_bank_evaluate": [_vp, _vp, _vp, _fp, C.c_uint32, C.c_uint32, _fp],
     "rq_rollout_teachers": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp],
+    "rq_policy_bank_create": [_vp, _fp, C.c_uint32, C.POINTER(_vp)],
+    "rq_policy_bank_destroy": [_vp],
+    "rq_policy_bank_set_weights": [_vp, C.c_uint32, _fp],
+    "rq_policy_bank_reset": [_vp],
+    "rq_policy_bank_get_hidden": [_vp, _fp, C.c_uint32],
+    "rq_rollout_policies": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp],
     "rq_reference_create": [_vp, _fp, C.c_uint32, C.POINTER(_vp)],
     "rq_reference_destroy": [_vp],
     "rq_rollout_track": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp],

@@ -1,0 +1,197 @@
+// rq_capi_policy_bank.cpp - the policy bank: P fp32 student policies (checkpoints of a run, a sweep, a seed population) flown in ONE
+// rollout, one policy per 64-env block (= per wave of the fused kernel).  The student-side mirror of the teacher bank's rollout
+// (rq_capi_teacher.cpp): same frame (rollout_check / rollout_begin / rollout_end), the id table cached in the bank.
+#include "rq_objects.hpp"
+
+using namespace rqh;
+
+namespace {
+
+constexpr const char* kWeightsShape = "expected 2084 weights per policy: W0[16,22] b0[16] Wi[48,16] Wh[48,16] bi[48] bh[48] h0[16] W2[4,16] b2[4]";
+
+inline uint32_t blocks_of(uint32_t n) { return (n + 63u) / 64u; }
+
+// policy_id[0 .. n): every id names a policy of the bank and is constant on every aligned block of 64 (checked before anything is
+// enqueued); the ragged last block is one block
+int check_ids(const rq_policy_bank* bank, const uint32_t* policy_id, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        RQ_REQUIRE(policy_id[i] < bank->n_policies, RQ_ERR_INVALID_ARGUMENT,
+                   "policy id out of range: env " + std::to_string(i) + " names policy " + std::to_string(policy_id[i]) + " of a bank of " +
+                       std::to_string(bank->n_policies));
+        RQ_REQUIRE(policy_id[i] == policy_id[i & ~63u], RQ_ERR_INVALID_ARGUMENT,
+                   "policy ids differ inside a 64-env block: env " + std::to_string(i) + " names policy " + std::to_string(policy_id[i]) +
+                       ", env " + std::to_string(i & ~63u) + " policy " + std::to_string(policy_id[i & ~63u]) +
+                       " (a policy flies whole blocks of 64 envs: one wave, one operand image)");
+    }
+    return RQ_OK;
+}
+
+// The bank's device table of one id per block for the n envs assigned by policy_id, uploaded only when (key, ids) differ from what
+// `table` holds.  Needs the caller's DeviceScope.
+int bank_table(rq_policy_bank* bank, rq_device* dev, uint64_t key, const uint32_t* policy_id, uint32_t n) {
+    const uint32_t blocks = blocks_of(n);
+    bool same = bank->table_valid && bank->table_key == key && bank->table_ids.size() == blocks;
+    for (uint32_t g = 0; same && g < blocks; ++g) same = bank->table_ids[g] == policy_id[(size_t)g * 64];
+    if (same) return RQ_OK;
+    bank->table_valid = false;
+    try {                                   // nothing throws across the boundary
+        bank->table_ids.resize(blocks);
+    } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "policy bank: host allocation failed");
+    }
+    for (uint32_t g = 0; g < blocks; ++g) bank->table_ids[g] = policy_id[(size_t)g * 64];
+    RQ_HIP(bank->table.reserve(dev->stream, blocks));
+    RQ_HIP(hipMemcpyAsync(bank->table, bank->table_ids.data(), (size_t)blocks * sizeof(uint32_t), hipMemcpyHostToDevice, dev->stream));
+    RQ_HIP(hipStreamSynchronize(dev->stream));                // table_ids is pageable, and may change before the copy would run
+    bank->table_valid = true;
+    bank->table_key = key;
+    return RQ_OK;
+}
+
+// The hidden state sized on first use, as a policy's is (policy_size).  Needs the caller's DeviceScope.
+int bank_size(rq_policy_bank* bank, uint32_t batch) {
+    if (bank->batch == batch && bank->hidden) return RQ_OK;
+    RQ_REQUIRE(bank->batch == 0 || bank->needs_reset, RQ_ERR_SHAPE_MISMATCH,
+               "batch size changed without reset (hidden state is per batch element)");
+    RQ_HIP(hipStreamSynchronize(bank->dev->stream));
+    bank->hidden.reset();
+    bank->batch = bank->ld = 0;                    // not sized, should the allocation fail
+    const uint32_t ld = round_up64(batch);
+    RQ_HIP(bank->hidden.alloc((size_t)RQ_POLICY_HIDDEN_DIM * ld));
+    bank->batch = batch; bank->ld = ld;
+    bank->needs_reset = true;
+    return RQ_OK;
+}
+
+// a pending reset applied: every env's hidden state <- the initial state of the policy the table gives its block
+int bank_apply_reset(rq_policy_bank* bank) {
+    if (!bank->needs_reset) return RQ_OK;
+    RQ_HIP(rq::launch_bank_initial_hidden(bank->dev->stream, bank->ld, bank->hidden, bank->weights, bank->table));
+    bank->needs_reset = false;
+    return RQ_OK;
+}
+
+// slot `index` of both device arrays from 2084 host weights (synchronous: the caller's array is its own again on return)
+int bank_upload_slot(rq_policy_bank* bank, uint32_t index, const float* weights) {
+    std::vector<float> image;
+    try { image.resize(rq::RQ_PACKED_FLOATS); } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "policy bank: host allocation failed");
+    }
+    rq::pack_policy(weights, image.data());
+    RQ_HIP(hipMemcpy(bank->images + (size_t)index * rq::RQ_PACKED_FLOATS, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(bank->weights + (size_t)index * RQ_POLICY_NUM_WEIGHTS, weights, RQ_POLICY_NUM_WEIGHTS * sizeof(float), hipMemcpyHostToDevice));
+    return RQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+RQ_API int rq_policy_bank_create(rq_device* dev, const float* weights, uint32_t n_policies, rq_policy_bank** out) {
+    RQ_REQUIRE(dev && weights && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    RQ_REQUIRE(n_policies > 0, RQ_ERR_INVALID_ARGUMENT, "n_policies must be positive");
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    rq_policy_bank* b = new (std::nothrow) rq_policy_bank();
+    RQ_REQUIRE(b, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
+    b->dev = dev; b->ordinal = dev->ordinal; b->n_policies = n_policies;
+    std::vector<float> images;
+    try { images.resize((size_t)rq::RQ_PACKED_FLOATS * n_policies); } catch (const std::bad_alloc&) {
+        delete b;
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_bank_create: host allocation failed");
+    }
+    for (uint32_t k = 0; k < n_policies; ++k)
+        rq::pack_policy(weights + (size_t)k * RQ_POLICY_NUM_WEIGHTS, images.data() + (size_t)k * rq::RQ_PACKED_FLOATS);
+    const size_t raw = (size_t)RQ_POLICY_NUM_WEIGHTS * n_policies;
+    if (b->images.alloc(images.size()) != hipSuccess || b->weights.alloc(raw) != hipSuccess ||
+        hipMemcpy(b->images, images.data(), images.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b->weights, weights, raw * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        delete b;
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_bank_create: device allocation or upload failed");
+    }
+    *out = b;
+    return RQ_OK;
+}
+
+RQ_API int rq_policy_bank_destroy(rq_policy_bank* bank) {
+    if (!bank) return RQ_OK;
+    DeviceScope on_device(bank->ordinal);      // (hipFree synchronises the device: no launch still reads the images)
+    delete bank;
+    return RQ_OK;
+}
+
+RQ_API int rq_policy_bank_set_weights(rq_policy_bank* bank, uint32_t index, const float* weights) {
+    RQ_REQUIRE(bank && weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(index < bank->n_policies, RQ_ERR_INVALID_ARGUMENT,
+               "policy index " + std::to_string(index) + " is outside a bank of " + std::to_string(bank->n_policies) + " (" + kWeightsShape + ")");
+    DeviceScope on_device(bank->dev); int rc = on_device.rc; if (rc) return rc;
+    RQ_HIP(hipStreamSynchronize(bank->dev->stream));          // a rollout in flight reads the slot
+    return bank_upload_slot(bank, index, weights);
+}
+
+RQ_API int rq_policy_bank_reset(rq_policy_bank* bank) {
+    RQ_REQUIRE(bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    bank->needs_reset = true;      // applied on the next use, when the assignment says whose initial state an env takes
+    return RQ_OK;
+}
+
+RQ_API int rq_policy_bank_get_hidden(rq_policy_bank* bank, float* host_out, uint32_t batch) {
+    RQ_REQUIRE(bank && host_out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(bank->hidden && bank->table_valid, RQ_ERR_NOT_INITIALIZED,
+               "the hidden state is sized, and its initial value chosen per env, by the first rq_rollout_policies");
+    RQ_REQUIRE(batch == bank->batch && bank->table_ids.size() == blocks_of(batch), RQ_ERR_SHAPE_MISMATCH,
+               "batch does not match the envs this bank last flew");
+    DeviceScope on_device(bank->dev); int rc = on_device.rc; if (rc) return rc;
+    rc = bank_apply_reset(bank); if (rc) return rc;
+    return soa_to_host(bank->dev, bank->hidden, batch, bank->ld, RQ_POLICY_HIDDEN_DIM, host_out);
+}
+
+RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
+                               const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                               rq_trajectory* traj) {
+    RolloutFrame f;
+    int rc = rollout_check(f, dev, env, params, state, rng, bank && policy_id, n_steps, mode, flags, traj); if (rc) return rc;
+    RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy bank lives on another device");
+    rc = check_ids(bank, policy_id, env->n); if (rc) return rc;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    rc = bank_size(bank, env->n); if (rc) return rc;
+    RQ_REQUIRE(bank->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");
+    rc = bank_table(bank, dev, env->uid, policy_id, env->n); if (rc) return rc;
+    rc = bank_apply_reset(bank); if (rc) return rc;
+    rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
+    const rq::TrajPtrs& tp = f.tp;
+    const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
+    const bool noise = f.noise;
+    if (mode == RQ_ROLLOUT_FUSED) {
+        if (dev->k_timing && n_steps) {                   // one (in, out) record per wave = per workgroup of the fused kernel
+            const uint32_t waves = blocks_of(env->n);
+            RQ_HIP(dev->k_span.reserve(dev->stream, (size_t)waves * 5));
+            dev->k_span_used = waves;
+        }
+        RQ_HIP(rq::launch_rollout_fused_bank(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags, params->d,
+                                             state->d, bank->hidden, bank->weights, bank->images, bank->table, env->st, tp,
+                                             dev->k_timing ? dev->k_span.get() : nullptr));
+        dev->k_timed = dev->k_timing && n_steps > 0;
+        dev->k_fetched = false;
+    } else if (n_steps) {
+        // one step = observe -> the bank's actor step -> step (-> record), plain launches on the device's stream
+        if (flags & RQ_ROLLOUT_AUTORESET)   // envs frozen by an earlier rollout start their next episode
+            RQ_HIP(rq::launch_thaw_frozen_bank(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, bank->hidden, bank->weights,
+                                               bank->table));
+        for (uint32_t t = 0; t < n_steps; ++t) {
+            RQ_HIP(rq::launch_observe(dev->stream, b, nc, noise, rng->seed, rng->epoch + t, nullptr, params->d, state->d, env->obs));
+            RQ_HIP(rq::launch_actor_step_bank(dev->stream, env->n, bank->images, bank->table, env->obs, env->ld, bank->hidden, bank->ld,
+                                              env->act, env->ld, env->st.frozen));
+            RQ_HIP(rq::launch_step_bank(dev->stream, b, sc, params->d, state->d, env->act, env->st, flags, smp, rng->seed, bank->hidden,
+                                        bank->weights, bank->table));
+            if (traj) {
+                rq::TrajPtrs tt = tp; tt.t0 = tp.t0 + t;
+                RQ_HIP(rq::launch_record(dev->stream, b, env->obs, env->act, env->st, tt));
+            }
+        }
+    }
+    rollout_end(state, rng, n_steps, traj);
+    return RQ_OK;
+}
+
+}  // extern "C"

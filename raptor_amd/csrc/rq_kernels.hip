@@ -1289,4 +1289,176 @@ hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ policy bank (rq_rollout_policies) ---
+// A bank of student policies, one per WAVE: the 64-env block g of a batch is flown by policy block_policy[g], whose operand image is
+// images + block_policy[g] * image_floats.  The weights are wave-uniform MFMA A operands, so choosing the image per wave is all a
+// bank needs: everything below is an existing kernel with the image (or, for the policy-state reset, the weight block) picked from
+// that table, and calls the existing __device__ functions - no new arithmetic, which is what makes a bank rollout equal, bit for
+// bit, the single-policy rollouts of its 64-env slices.  Behind everything else of this unit for the reason given above.
+
+// k_rollout_fused with the image chosen per workgroup (one workgroup = one wave = one 64-env block in both builds): the id is read
+// with a scalar load (a kernel argument indexed by blockIdx: provably wave-uniform, so `packed` is a scalar base for the image's
+// loads as it is in k_rollout_fused) ahead of the prologue's env loads, which hide its latency.  No SampleAndSquash stage, no
+// tracking, native interval 1 (the host offers none of them for a bank).
+template <bool NOISE, bool AUTORESET, bool RECORD, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_bank(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ images,
+                                                               const uint32_t* __restrict__ block_policy, uint32_t image_floats,
+                                                               StatsPtrs st, TrajPtrs traj,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool TRACK = false, RATE = false, SAS = false;
+    constexpr TrackPtrs trk{};
+    constexpr SasArgs sas{};
+    constexpr uint32_t interval = 1;
+    const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
+#include "rq_rollout_body.inc"
+}
+
+// k_actor_step with the image of the wave's block (block = wave_base / 64); the chained bank rollout's actor: no host rows, no
+// SampleAndSquash stage, no speculation.  The wave index is made a scalar first: the table read is then a scalar load too.
+template <typename ACTOR>
+__global__ __launch_bounds__(kBlock, 2) void k_actor_step_bank(uint32_t n, const float* __restrict__ images,
+                                                            const uint32_t* __restrict__ block_policy, uint32_t image_floats,
+                                                            const float* __restrict__ obs, uint32_t ld_obs,
+                                                            float* hidden, uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
+                                                            const uint8_t* __restrict__ frozen) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t wave_base = wave * 64u;
+    if (wave_base >= n) return;                                  // wave-uniform; the table has ceil(n / 64) entries
+    ACTOR actor;
+    actor.template load<kBlock / 64>(images + (size_t)block_policy[wave] * image_floats);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t i0 = wave_base + lane;
+    const uint32_t i = i0 < n ? i0 : n - 1;
+    float x[22], hQ[4][4], a[4];
+#pragma unroll
+    for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
+    load_hidden_q(hidden, ld_h, wave_base, n, hQ);
+    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
+    const bool commit = (i0 < n) && fz == 0;
+    const uint64_t commit_mask = __builtin_amdgcn_ballot_w64(commit);
+    actor.step(x, hQ, a);
+    store_hidden_q(hidden, ld_h, wave_base, commit_mask, hQ);
+    if (commit) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
+    }
+}
+
+// k_step<true> whose policy-state reset (auto-reset at an episode end: h <- initial_hidden_state) reads the weight block of the env's
+// own policy: weights [P][RQ_POLICY_NUM_WEIGHTS], checkpoint order
+__global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                      float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                      uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                      const uint32_t* __restrict__ block_policy) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                       weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{});
+}
+
+// k_thaw_frozen likewise: an env left frozen starts its next episode with ITS policy's initial state
+__global__ __launch_bounds__(kBlock) void k_thaw_frozen_bank(Batch b, SampleCfg c, uint64_t seed,
+                                                             const float* __restrict__ params, float* __restrict__ state,
+                                                             StatsPtrs st, float* __restrict__ hidden,
+                                                             const float* __restrict__ weights,
+                                                             const uint32_t* __restrict__ block_policy) {
+    const uint32_t i = env_index();
+    if (i >= b.n || !st.frozen[i]) return;
+    const size_t ld = b.ld;
+    const uint32_t ep = st.episode[i];
+    const float* w = weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS;
+    float s[17], la[4], f[6];
+    sample_state(c, seed, ep, b.env_offset + i, field(params, RQ_P_MASS, ld)[i], field(params, RQ_P_HOVER_RPM, ld)[i],
+                 field(params, RQ_P_ROTOR_POS, ld)[i], field(params, (RQ_P_ROTOR_POS + 1), ld)[i], s, la, f);
+#pragma unroll
+    for (int k = 0; k < 17; ++k) field(state, k, ld)[i] = s[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) field(state, (RQ_S_LAST_ACTION + k), ld)[i] = la[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) field(state, (RQ_S_FORCE + k), ld)[i] = f[k];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) field(hidden, j, ld)[i] = w[OFF_H0 + j];
+    st.episode[i] = ep + 1;
+    st.frozen[i] = 0;
+}
+
+// rq_policy_bank_reset: hidden [16][ld] <- the initial hidden state of every column's policy (columns n .. ld - 1 belong to the last block)
+__global__ __launch_bounds__(kBlock) void k_bank_initial_hidden(uint32_t ld, float* __restrict__ hidden,
+                                                                const float* __restrict__ weights,
+                                                                const uint32_t* __restrict__ block_policy) {
+    const uint32_t i = env_index();
+    if (i >= ld) return;
+    const float* w = weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) field(hidden, j, ld)[i] = w[OFF_H0 + j];
+}
+
+template <bool NZ, bool AR, bool RC, typename ACTOR>
+static inline void launch_fused_bank_instance(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy) {
+    const unsigned g = (a.b.n + kFusedBlock - 1) / kFusedBlock;
+    hipLaunchKernelGGL((k_rollout_fused_bank<NZ, AR, RC, ACTOR>), dim3(g), dim3(kFusedBlock), 0, s,
+                       a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
+                       (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.span);
+}
+template <typename ACTOR>
+static inline void launch_fused_bank_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
+                                           bool noise, bool ar) {
+    const bool rec = a.traj.obs != nullptr;
+#define RQ_FUSED_RC(NZ, AR) do { if (rec) launch_fused_bank_instance<NZ, AR, true, ACTOR>(s, a, images, block_policy); \
+                                 else     launch_fused_bank_instance<NZ, AR, false, ACTOR>(s, a, images, block_policy); } while (0)
+    if (noise) { if (ar) RQ_FUSED_RC(true, true); else RQ_FUSED_RC(true, false); }
+    else       { if (ar) RQ_FUSED_RC(false, true); else RQ_FUSED_RC(false, false); }
+#undef RQ_FUSED_RC
+}
+
+hipError_t launch_rollout_fused_bank(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                     const float* params, float* state, float* hidden, const float* weights,
+                                     const float* images, const uint32_t* block_policy, StatsPtrs st, TrajPtrs traj,
+                                     unsigned long long* span) {
+    if (b.n == 0 || n_steps == 0) return hipSuccess;
+    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span};
+    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
+    if (b.n > 65536u) launch_fused_bank_actor<ActorF32Lean>(s, a, images, block_policy, noise, ar);
+    else              launch_fused_bank_actor<ActorF32>(s, a, images, block_policy, noise, ar);
+    return hipGetLastError();
+}
+
+hipError_t launch_actor_step_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy, const float* obs,
+                                  uint32_t ld_obs, float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen) {
+    if (n == 0) return hipSuccess;
+    // launch_actor_step's build for fp32 policies (one 64-env group per wave): the same bits
+    k_actor_step_bank<ActorF32Lean><<<grid_for((n + 63) / 64 * 64, kBlock), kBlock, 0, s>>>(
+        n, images, block_policy, (uint32_t)RQ_PACKED_FLOATS, obs, ld_obs, hidden, ld_h, act, ld_act, frozen);
+    return hipGetLastError();
+}
+
+hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
+                            uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
+                            const uint32_t* block_policy) {
+    if (b.n == 0) return hipSuccess;
+    k_step_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, params, state, action, st, flags, sc, seed, hidden, weights, block_policy);
+    return hipGetLastError();
+}
+
+hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
+                                   StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy) {
+    if (b.n == 0) return hipSuccess;
+    k_thaw_frozen_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, seed, params, state, st, hidden, weights, block_policy);
+    return hipGetLastError();
+}
+
+hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden, const float* weights, const uint32_t* block_policy) {
+    if (ld == 0) return hipSuccess;
+    k_bank_initial_hidden<<<grid_for(ld, kBlock), kBlock, 0, s>>>(ld, hidden, weights, block_policy);
+    return hipGetLastError();
+}
+
 }  // namespace rq

@@ -268,6 +268,23 @@ hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg
                                      const float* params, float* state, float* hidden, const float* weights,
                                      const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
                                      uint32_t interval, unsigned long long* span = nullptr);
+// ---- policy bank (rq_rollout_policies): P fp32 operand images [P][RQ_PACKED_FLOATS], raw weights [P][RQ_POLICY_NUM_WEIGHTS] and
+// block_policy [ceil(n / 64)]: the policy of each 64-env block.  The fused kernel with the image chosen per wave; its chained
+// counterpart's actor step, env step and thaw (the latter two reset a policy state to the initial state of the env's own policy);
+// hidden [16][ld] <- every column's initial state.  Plain launches: none of them appends to a GraphSink.
+hipError_t launch_rollout_fused_bank(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                     const float* params, float* state, float* hidden, const float* weights,
+                                     const float* images, const uint32_t* block_policy, StatsPtrs st, TrajPtrs traj,
+                                     unsigned long long* span = nullptr);
+hipError_t launch_actor_step_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy, const float* obs,
+                                  uint32_t ld_obs, float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen);
+hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
+                            uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
+                            const uint32_t* block_policy);
+hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
+                                   StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy);
+hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden, const float* weights, const uint32_t* block_policy);
 // chained mode of a tracked rollout, between the observation's assembly (k_observe, or the k_step before) and the actor: the row of
 // each env's episode step count comes off obs [RQ_OBSERVATION_DIM][ld] in place, and the envs that are not frozen add this step's
 // tracking error - the fused kernel's arithmetic (rq_device_math.hpp track_*).  Appends a graph node under a GraphSink.

@@ -8,6 +8,7 @@
 //   rq_capi_policy.cpp   Raptor: create / configure / reset / evaluate_step / evaluate_sequence / selftest
 //   rq_capi_rollout.cpp  the loop body x K on the device (fused, or chained under a hipGraph), trajectories, relabelling with a policy
 //   rq_capi_teacher.cpp  the teacher bank
+//   rq_capi_policy_bank.cpp  the policy bank: many student checkpoints in one rollout, one per 64-env block
 //   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory; the distillation update (loss, Adam, repack)
 //   rq_memory.hpp        rq::DeviceBuffer / rq::PinnedBuffer: every object below owns its device and pinned memory through them
 // rollout_check / rollout_begin / rollout_end (rq_capi_rollout.cpp) are the frame rq_rollout* and rq_rollout_teachers share.
@@ -333,6 +334,23 @@ struct rq_teacher_bank {
     DeviceBuffer<float> eval_buf;
 };
 
+// a bank of fp32 student policies flown one per 64-env block (rq_capi_policy_bank.cpp)
+struct rq_policy_bank {
+    rq_device* dev = nullptr;
+    int ordinal = 0;
+    uint32_t n_policies = 0;
+    DeviceBuffer<float> images;      // [n_policies][rq::RQ_PACKED_FLOATS]: the images rq::pack_policy makes, slot after slot
+    DeviceBuffer<float> weights;     // [n_policies][RQ_POLICY_NUM_WEIGHTS], checkpoint order: the initial hidden states are read here
+    // the per-block id table and what it was built from: (table_key = the env's uid, table_ids = one id per block) - a loop of
+    // rollouts with one assignment uploads it once (as rq_teacher_bank::tiles)
+    DeviceBuffer<uint32_t> table;    // [blocks]
+    bool table_valid = false;
+    uint64_t table_key = 0;
+    std::vector<uint32_t> table_ids;
+    uint32_t batch = 0, ld = 0;      // 0 = not sized yet
+    bool needs_reset = true;         // hidden must be (re)filled with every env's own policy's initial state before use
+    DeviceBuffer<float> hidden;      // [16][ld]
+};
 
 // From kGpuLayoutMinEnvs envs up the row-major <-> field-major change runs on the GPU (k_soa_to_rows /
 // k_rows_to_soa) and the PCIe copy goes straight between the caller's array and a device row buffer; below

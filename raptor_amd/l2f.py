@@ -513,7 +513,10 @@ class VectorModule:
             def tensors(self):
                 """The recorded steps as torch tensor VIEWS of the device buffers (zero copy), in the device layout:
                 obs [T, 22, ld], act [T, 4, ld], rew [T, ld], done [T, ld] uint8 - env i is index i < N of the
-                last axis.  ``obs.permute(0, 2, 1)[:, :N]`` is the learner layout [T, N, 22]."""
+                last axis.  ``obs.permute(0, 2, 1)[:, :N]`` is the learner layout [T, N, 22].
+                What the engine has enqueued is waited for first: rollouts return before they have run, the engine's stream
+                does not order itself against torch's, and a view read too early shows the buffer's previous contents."""
+                _lib.call("rq_device_synchronize", self._env._device._h)
                 o, a, r, d, ld = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32()
                 _lib.call("rq_trajectory_device_ptrs", self._require("trajectory"), C.byref(o), C.byref(a), C.byref(r),
                           C.byref(d), C.byref(ld))
@@ -625,17 +628,35 @@ class VectorModule:
                   state._require("VectorState"), None, next_state._ensure(env), rng._require("rng"), None)
 
     def rollout(self, device, env, params, state, policy, rng, n_steps, mode="fused", autoreset=False,
-                trajectory=None, teacher_ids=None, reference=None):
+                trajectory=None, teacher_ids=None, reference=None, policy_ids=None):
         """The loop body README.md:95-99, ``n_steps`` times, entirely on the device; with
         ``trajectory`` every transition is also appended to that buffer.  ``policy`` is a ``Raptor`` or a
         ``raptor_amd.teachers.TeacherBank``; with a bank, ``teacher_ids`` ([N] integers) names the teacher that flies
         each env (``mode="fused"``: fp32 banks of two hidden layers of 16 / 32 / 64 units; ``"chained"``: every bank).
         ``reference`` (a ``Reference``): the policy tracks that moving setpoint - it sees position and linear velocity relative to
         the row of each env's own episode step count; everything else (state, reward, termination, statistics) stays absolute, a
-        ``trajectory`` records what the policy saw, and ``env.tracking_error()`` accumulates.  ``Raptor`` policies only."""
+        ``trajectory`` records what the policy saw, and ``env.tracking_error()`` accumulates.  ``Raptor`` policies only.
+        ``policy`` may also be a ``raptor_amd.policy_bank.PolicyBank``: ``policy_ids`` ([N] integers, constant on every aligned
+        block of 64 envs) names the student policy that flies each env, both modes."""
         if reference is not None and teacher_ids is not None:
             raise ValueError("reference and teacher_ids do not combine: a TeacherBank rollout does not track")
         m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
+        from .policy_bank import PolicyBank, check_policy_ids
+        if isinstance(policy, PolicyBank):
+            if reference is not None:
+                raise ValueError("a PolicyBank rollout does not track a reference")
+            if teacher_ids is not None:
+                raise ValueError("teacher_ids belong to a TeacherBank rollout; a PolicyBank flies the envs by policy_ids")
+            if policy_ids is None:
+                raise ValueError("a PolicyBank flies the envs by policy_ids: one policy id per env is required")
+            ids = check_policy_ids(policy_ids, policy.n_policies, self.N_ENVIRONMENTS)
+            _lib.call("rq_rollout_policies", device._h, env._require("environment"), params._require("VectorParameters"),
+                      state._require("VectorState"), policy._h, ids.ctypes.data, rng._require("rng"), int(n_steps), m,
+                      ROLLOUT_AUTORESET if autoreset else 0, trajectory._require("trajectory") if trajectory is not None else None)
+            return
+        if policy_ids is not None:
+            raise ValueError("policy_ids belong to a PolicyBank rollout; a Raptor policy flies every env itself and a TeacherBank "
+                             "takes teacher_ids")
         from .teachers import TeacherBank
         if isinstance(policy, TeacherBank):
             if reference is not None:

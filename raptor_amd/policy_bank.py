@@ -1,0 +1,144 @@
+"""Policy bank: many student policies flown in one rollout, one policy per wave.
+
+Post-training of rl-tools/raptor writes a checkpoint and an ``evaluation/*`` record every epoch, and its users pick the student by
+closed-loop return, episode length and share terminated; hyper-parameter sweeps and seed populations of ``training.Distiller`` ask
+the same question of many weight vectors.  ``PolicyBank`` holds P policies of the ``Raptor`` topology on the device (fp32) and
+``vector.rollout(..., bank, ..., policy_ids=ids)`` flies env ``i`` with policy ``ids[i]`` - in ONE launch: a 64-env block is one
+wave of the fused kernel and the weights are that wave's matrix operands, so the granularity is the block: ``ids`` must be
+constant on every aligned block of 64 env indices (``block_policy_assignment`` deals blocks round-robin).  What an env computes
+is, bit for bit, what ``Raptor(weights=W[ids[i]])`` computes for it in a rollout of its own.
+"""
+import ctypes as C
+import weakref
+
+import numpy as np
+
+from . import _lib
+from ._lib import POLICY_HIDDEN_DIM, POLICY_NUM_WEIGHTS
+
+BLOCK = 64      # envs per wave: the granularity of an assignment
+
+
+def block_policy_assignment(n_envs, n_policies):
+    """policy id of every env (uint32 [n_envs]): the blocks of 64 envs dealt round-robin, block g -> policy g % n_policies (the
+    ragged last block is one block).  1 000 policies x 64 envs: ``block_policy_assignment(64000, 1000)``."""
+    n_envs, n_policies = int(n_envs), int(n_policies)
+    if n_envs <= 0 or n_policies <= 0:
+        raise ValueError("n_envs and n_policies must be positive")
+    return np.ascontiguousarray(((np.arange(n_envs) // BLOCK) % n_policies).astype(np.uint32))
+
+
+def check_policy_ids(ids, n_policies, n_envs=None):
+    """The host-side validator of an assignment (no GPU): integers, one per env (``n_envs`` given: exactly that many), each in
+    [0, n_policies), constant on every aligned block of 64.  -> the ids as a contiguous uint32 array; ValueError otherwise."""
+    a = np.asarray(ids)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError("policy_ids must be a non-empty one-dimensional array: one id per env")
+    if n_envs is not None and a.size != int(n_envs):
+        raise ValueError(f"policy_ids must hold one id per env: {a.size} ids for {int(n_envs)} envs")
+    if not (np.issubdtype(a.dtype, np.integer) or (np.issubdtype(a.dtype, np.floating) and np.all(a == np.floor(a)))):
+        raise ValueError("policy_ids must be integers")
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= int(n_policies):
+        bad = int(np.flatnonzero((a < 0) | (a >= int(n_policies)))[0])
+        raise ValueError(f"policy id out of range: env {bad} names policy {int(a[bad])} of a bank of {int(n_policies)}")
+    first = a[(np.arange(a.size) // BLOCK) * BLOCK]
+    if not np.array_equal(a, first):
+        bad = int(np.flatnonzero(a != first)[0])
+        raise ValueError(f"policy ids differ inside a 64-env block: env {bad} names policy {int(a[bad])}, env {bad // BLOCK * BLOCK} "
+                         f"policy {int(first[bad])} (a policy flies whole blocks of 64 envs)")
+    return np.ascontiguousarray(a.astype(np.uint32))
+
+
+def policy_episode_table(env, policy_ids, n_policies):
+    """Per-policy closed-loop summary of the env's finished episodes - what a checkpoint is picked by.
+
+    Reads the env's finished-episode records (``env.finished_*``: per env, the number of finished episodes, how many of them
+    terminated, and the return / length of the last one) and groups them by ``policy_ids``.  -> dict of [n_policies] arrays:
+    ``envs`` (envs flown), ``episodes`` (finished), ``mean_return`` / ``std_return`` / ``mean_length`` (over the envs' last finished
+    episodes, NaN for a policy without one) and ``termination_share`` (terminated / finished, NaN without episodes)."""
+    ids = np.asarray(policy_ids, np.int64).ravel()
+    counts = np.asarray(env.finished_counts(), np.float64)
+    done = counts > 0
+    ret = np.where(done, np.asarray(env.finished_returns(), np.float64), 0.0)
+    length = np.where(done, np.asarray(env.finished_lengths(), np.float64), 0.0)
+    term = np.asarray(env.finished_terminated(), np.float64)
+    k = int(n_policies)
+    envs = np.bincount(ids, minlength=k)
+    with_episode = np.bincount(ids, weights=done.astype(np.float64), minlength=k)
+    episodes = np.bincount(ids, weights=counts, minlength=k)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_return = np.bincount(ids, weights=ret, minlength=k) / with_episode
+        dev = np.where(done, ret - mean_return[ids], 0.0)
+        std_return = np.sqrt(np.bincount(ids, weights=dev * dev, minlength=k) / with_episode)
+        mean_length = np.bincount(ids, weights=length, minlength=k) / with_episode
+        termination_share = np.bincount(ids, weights=term, minlength=k) / episodes
+    return dict(envs=envs, episodes=episodes.astype(np.int64), mean_return=mean_return, std_return=std_return,
+                mean_length=mean_length, termination_share=termination_share)
+
+
+class PolicyBank:
+    """``weights`` [P, 2084] float32, each row in the checkpoint order ``Raptor`` takes.  fp32 only; no Standardize or
+    SampleAndSquash stage, native interval 1."""
+
+    def __init__(self, device, weights):
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.ndim != 2 or w.shape[0] == 0 or w.shape[1] != POLICY_NUM_WEIGHTS:
+            raise ValueError(f"weights must be [n_policies, {POLICY_NUM_WEIGHTS}]")
+        self.n_policies = int(w.shape[0])
+        self._weights = w.copy()
+        self._device = device
+        h = C.c_void_p()
+        _lib.call("rq_policy_bank_create", device._h, _lib.fptr(w), self.n_policies, C.byref(h))
+        self._h = h
+        self._fin = weakref.finalize(self, _lib.load().rq_policy_bank_destroy, h)
+
+    @classmethod
+    def from_checkpoints(cls, device, paths, check_observation=True):
+        """One policy per file, each an rl-tools policy checkpoint (``checkpoint.h5`` or the C++ export, as
+        ``Raptor.from_checkpoint`` reads them).  A file whose ``/actor@meta`` names another observation layout than this
+        engine's ``observe`` assembles is refused, as ``Raptor`` refuses it.  -> PolicyBank, policy k = paths[k]."""
+        from . import checkpoint as ck
+        paths = list(paths)
+        if not paths:
+            raise ValueError("no checkpoint files")
+        rows = []
+        for path in paths:
+            w, _, meta = ck.load_checkpoint(path, with_meta=True)
+            if check_observation:
+                ck.check_observation(meta, path)
+            rows.append(np.asarray(w, np.float32))
+        return cls(device, np.stack(rows))
+
+    @property
+    def weights(self):
+        return self._weights
+
+    def set_weights(self, index, weights):
+        """New parameters for policy ``index``: its slot is repacked in place; the hidden state stays."""
+        w = np.array(weights, dtype=np.float32, copy=True).reshape(-1)
+        if w.size != POLICY_NUM_WEIGHTS:
+            raise ValueError(f"expected {POLICY_NUM_WEIGHTS} weights")
+        if not 0 <= int(index) < self.n_policies:
+            raise ValueError(f"policy index {index} is outside a bank of {self.n_policies}")
+        _lib.call("rq_policy_bank_set_weights", self._h, int(index), _lib.fptr(w))
+        self._weights[int(index)] = w
+
+    def reset(self):
+        """hidden state <- every env's own policy's initial_hidden_state (applied by the next use that knows the assignment)."""
+        _lib.call("rq_policy_bank_reset", self._h)
+
+    def hidden(self, batch):
+        """The hidden state [batch, 16] of the envs the bank last flew."""
+        out = np.empty((int(batch), POLICY_HIDDEN_DIM), np.float32)
+        _lib.call("rq_policy_bank_get_hidden", self._h, _lib.fptr(out), int(batch))
+        return out
+
+    def evaluate(self, vector, device, env, params, state, rng, n_steps, policy_ids=None, mode="fused", autoreset=True):
+        """The closed-loop evaluation of the whole bank: statistics and hidden state start afresh, one rollout of ``n_steps`` flies
+        env i with policy ``policy_ids[i]`` (default: blocks dealt round-robin) -> ``policy_episode_table`` of what it finished."""
+        ids = block_policy_assignment(vector.N_ENVIRONMENTS, self.n_policies) if policy_ids is None else policy_ids
+        env.reset_statistics()
+        self.reset()
+        vector.rollout(device, env, params, state, self, rng, n_steps, mode=mode, autoreset=autoreset, policy_ids=ids)
+        return policy_episode_table(env, ids, self.n_policies)
