@@ -80,7 +80,8 @@ extern "C" {
                               the communicator's own rank and size; rq_teacher_bank_create_layers
                               5 (round 6): rq_device_{set,get}_resident; no struct changed
                               (still 5: rq_policy_{set,get}_native_interval added, no struct changed)
-                              (still 5: rq_policy_bank_* and rq_rollout_policies added, no struct changed) */
+                              (still 5: rq_policy_bank_* and rq_rollout_policies, then rq_bank_optimizer_* and rq_trajectory_policies_*
+                              added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -594,6 +595,35 @@ RQ_API int rq_policy_bank_get_hidden(rq_policy_bank* bank, float* host_out, uint
 RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
                                const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                rq_trajectory* trajectory);
+
+/* ---- Distilling a bank: the update of rq_trajectory_distill for every policy of a bank at once - a sweep of learning rates or a seed
+ * population costs one student's launch count, and "fly the bank, distil the bank, fly it again" never leaves the device.  The
+ * recording's 64-env blocks are dealt to the policies by policy_id as in rq_rollout_policies (host array, one id per env, constant
+ * on every aligned block of 64); policy p's loss is the masked mean squared error of rq_trajectory_policy_loss_grad over ITS blocks
+ * only, M_p = its live entries.  What policy p gets - loss, gradient, update - is, bit for bit, what a rq_policy created from its
+ * weights gets from the single-policy calls on a recording that holds p's blocks alone, in order.
+ * rq_trajectory_policies_loss_grad: loss [P], grad_weights [P][2084]; a policy that owns no block: loss NaN, its gradient row is
+ * left as it was.  rq_bank_optimizer: Adam's state per policy, [P][2084] moments, and the hyper-parameters per policy: config
+ * [n_cfg], n_cfg = 1 (one for all) or P; rq_bank_optimizer_set_lr: lr [n], n = 1 or P, in stream order.
+ * rq_trajectory_policies_distill: n_updates x (forward, loss-seeded backward, per-policy reduction, Adam and both operand images of
+ * every policy), enqueued back to back; losses [n_updates][P]: the loss before each update.  A policy that owns no block in this
+ * assignment is skipped whole - weights, moments, step count, images untouched - and its losses are NaN.  The updated weights are
+ * what every later use of the bank on the same stream sees (a rollout, rq_policy_bank_get_hidden after a reset);
+ * rq_policy_bank_get_weights fetches them ([P][2084], behind everything enqueued).
+ * start, target, ld_target and memory as for the single-policy calls; RQ_GRAD_START_CURRENT reads the bank's hidden state, sized
+ * for this env as by rq_rollout_policies, a pending reset applied first.  Refused before anything is enqueued: an id >= P or ids that
+ * differ inside a block, a bank on another device, an optimizer made for another bank, n_updates = 0, an empty trajectory,
+ * ld_target < n_envs, a target that is not device memory of the trajectory's device when one is announced. */
+typedef struct rq_bank_optimizer rq_bank_optimizer;
+RQ_API int rq_policy_bank_get_weights(rq_policy_bank* bank, float* host_out); /* [P][2084] */
+RQ_API int rq_trajectory_policies_loss_grad(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target,
+                                            uint32_t ld_target, int start, float* loss, float* grad_weights, int memory);
+RQ_API int rq_bank_optimizer_create(rq_policy_bank* bank, const rq_adam_config* config, uint32_t n_cfg, rq_bank_optimizer** out);
+RQ_API int rq_bank_optimizer_destroy(rq_bank_optimizer* optimizer);
+RQ_API int rq_bank_optimizer_set_lr(rq_bank_optimizer* optimizer, const double* lr, uint32_t n);
+RQ_API int rq_trajectory_policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* optimizer,
+                                          const uint32_t* policy_id, const float* target, uint32_t ld_target, int start,
+                                          uint32_t n_updates, float* losses, int memory);
 
 
 /* ---- Multi-GPU: the path's one exchange ---------------------------------------------

@@ -1,8 +1,9 @@
 // rq_capi_grad.cpp - the learner half of distillation (README.md:208-216) behind the C ABI: the fp32 student over a recorded
 // trajectory (rq_trajectory_policy_forward) and the exact gradient of those actions with respect to its 2 084 parameters, back
 // through time along the recorded episode structure (rq_trajectory_policy_backward); and the whole distillation update on the device:
-// masked-MSE loss and gradient (rq_trajectory_policy_loss_grad), Adam and the operand images (rq_trajectory_distill).
-// Kernels: rq_grad.hpp.
+// masked-MSE loss and gradient (rq_trajectory_policy_loss_grad), Adam and the operand images (rq_trajectory_distill); and that update
+// for every policy of a policy bank at once (rq_trajectory_policies_loss_grad, rq_bank_optimizer_*, rq_trajectory_policies_distill).
+// Kernels: rq_grad.hpp, rq_grad_bank.hpp.
 #include "rq_objects.hpp"
 
 using namespace rqh;
@@ -47,10 +48,10 @@ int ensure_grad_image(rq_policy* pol) {
 
 // What the two loss-seeded calls share.  loss_check: the refusals, before the call's DeviceScope (a refused call leaves the device,
 // a resident executor included, alone).  loss_begin, inside it: the workspace and the target on the device; n_losses: floats wanted
-// behind the gradient in t->grad.out.  -> d_target / ld_y as the kernel takes them.
-int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, const char* what) {
-    int rc = check_pair(t, pol, what); if (rc) return rc;
-    rc = check_memory(memory); if (rc) return rc;
+// behind the gradient in t->grad.out.  -> d_target / ld_y as the kernel takes them.  loss_check_call and loss_workspace are the parts
+// that do not ask whose weights they are: the bank's calls below share them.
+int loss_check_call(rq_trajectory* t, const float* target, uint32_t ld_target, int start, int memory, const char* what) {
+    int rc = check_memory(memory); if (rc) return rc;
     RQ_REQUIRE(start == RQ_GRAD_START_CURRENT || start == RQ_GRAD_START_INITIAL, RQ_ERR_INVALID_ARGUMENT,
                "start must be RQ_GRAD_START_CURRENT or RQ_GRAD_START_INITIAL");
     rq_env* env = t->env;
@@ -68,18 +69,21 @@ int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t l
     return RQ_OK;
 }
 
-int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, size_t n_losses,
-               const float** d_target, uint32_t* ld_y) {
+int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, const char* what) {
+    int rc = check_pair(t, pol, what); if (rc) return rc;
+    return loss_check_call(t, target, ld_target, start, memory, what);
+}
+
+// the workspace and the target on the device; out_floats: what t->grad.out is to hold (gradients, then losses)
+int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, int memory, size_t out_floats, const float** d_target,
+                   uint32_t* ld_y) {
     rq_env* env = t->env;
     rq_device* dev = env->dev;
     const uint32_t T = t->length, ld = env->ld;
-    int rc = RQ_OK;
-    if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, env->n); if (rc) return rc; }
-    rc = ensure_grad_image(pol); if (rc) return rc;
     t->grad.valid = false;
     RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld));
     RQ_HIP(t->grad.partial.reserve(dev->stream, rq::policy_loss_partial_floats(env->n)));
-    RQ_HIP(t->grad.out.reserve(dev->stream, RQ_POLICY_NUM_WEIGHTS + n_losses));
+    RQ_HIP(t->grad.out.reserve(dev->stream, out_floats));
     RQ_HIP(t->grad.live.reserve(dev->stream, 1));
     *d_target = target ? target : t->act.get();          // the stored actions: what a relabel or a teacher-acting rollout left
     *ld_y = target ? ld_target : ld;
@@ -92,6 +96,14 @@ int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t l
     return RQ_OK;
 }
 
+int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, size_t n_losses,
+               const float** d_target, uint32_t* ld_y) {
+    int rc = RQ_OK;
+    if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, t->env->n); if (rc) return rc; }
+    rc = ensure_grad_image(pol); if (rc) return rc;
+    return loss_workspace(t, target, ld_target, memory, RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y);
+}
+
 hipError_t enqueue_loss_grad(rq_trajectory* t, rq_policy* pol, int start, const float* d_target, uint32_t ld_y, float* d_grad,
                              float* d_loss) {
     rq_env* env = t->env;
@@ -99,6 +111,52 @@ hipError_t enqueue_loss_grad(rq_trajectory* t, rq_policy* pol, int start, const 
                                        t->done, start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr, pol->ld,
                                        start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y, t->grad.partial, d_grad,
                                        d_loss, t->grad.live);
+}
+
+// ---- the same for a policy bank (rq_trajectory_policies_loss_grad / _distill) ----
+// bank_loss_check: every refusal, before the call's DeviceScope.  bank_loss_begin, inside it: the id table and the policies' wave
+// lists (cached in the bank), the transposed images, for RQ_GRAD_START_CURRENT the bank's hidden state sized for this env and a
+// pending reset applied - as rq_rollout_policies does -, then the workspace; n_losses: floats wanted behind the [P][2084]
+// gradients in t->grad.out.
+int bank_loss_check(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target, uint32_t ld_target,
+                    int start, int memory, const char* what) {
+    RQ_REQUIRE(bank->dev == t->env->dev, RQ_ERR_SHAPE_MISMATCH, std::string(what) + ": the policy bank lives on another device");
+    RQ_REQUIRE(t->length > 0, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": the trajectory is empty");
+    int rc = loss_check_call(t, target, ld_target, start, memory, what); if (rc) return rc;
+    rc = bank_check_ids(bank, policy_id, t->env->n); if (rc) return rc;
+    if (start == RQ_GRAD_START_CURRENT)
+        RQ_REQUIRE(bank->batch == t->env->n || bank->batch == 0 || bank->needs_reset, RQ_ERR_SHAPE_MISMATCH,
+                   std::string(what) + ": RQ_GRAD_START_CURRENT reads the bank's hidden state, which is sized for another batch");
+    return RQ_OK;
+}
+
+int bank_loss_begin(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target, uint32_t ld_target,
+                    int start, int memory, size_t n_losses, const float** d_target, uint32_t* ld_y) {
+    rq_env* env = t->env;
+    int rc = RQ_OK;
+    if (start == RQ_GRAD_START_CURRENT) {
+        rc = bank_size(bank, env->n); if (rc) return rc;
+        RQ_REQUIRE(bank->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");
+    }
+    rc = bank_table(bank, env->dev, env->uid, policy_id, env->n); if (rc) return rc;
+    rc = bank_wave_lists(bank); if (rc) return rc;
+    rc = bank_grad_images(bank); if (rc) return rc;
+    if (start == RQ_GRAD_START_CURRENT) { rc = bank_apply_reset(bank); if (rc) return rc; }
+    return loss_workspace(t, target, ld_target, memory, (size_t)bank->n_policies * RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y);
+}
+
+hipError_t enqueue_bank_loss_grad(rq_trajectory* t, rq_policy_bank* bank, int start, const float* d_target, uint32_t ld_y, float* d_grad,
+                                  float* d_loss) {
+    rq_env* env = t->env;
+    return rq::launch_policy_loss_grad_bank(env->dev->stream, env->n, env->ld, t->length, bank->n_policies, bank->images, bank->gimages,
+                                            bank->table, bank->waves, bank->waves + bank->n_policies + 1, t->obs, t->done,
+                                            start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr, bank->ld,
+                                            start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y, t->grad.partial, d_grad,
+                                            d_loss);
+}
+
+bool adam_config_ok(const rq_adam_config& c) {
+    return c.lr >= 0.0 && c.eps >= 0.0 && c.weight_decay >= 0.0 && c.beta1 >= 0.0 && c.beta1 < 1.0 && c.beta2 >= 0.0 && c.beta2 < 1.0;
 }
 
 }  // namespace
@@ -210,9 +268,7 @@ RQ_API int rq_trajectory_policy_loss_grad(rq_trajectory* t, rq_policy* pol, cons
 RQ_API int rq_optimizer_create(rq_policy* pol, const rq_adam_config* config, rq_optimizer** out) {
     RQ_REQUIRE(pol && config && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    RQ_REQUIRE(config->lr >= 0.0 && config->eps >= 0.0 && config->weight_decay >= 0.0 && config->beta1 >= 0.0 && config->beta1 < 1.0 &&
-               config->beta2 >= 0.0 && config->beta2 < 1.0, RQ_ERR_INVALID_ARGUMENT,
-               "lr, eps and weight_decay must be non-negative and the betas in [0, 1)");
+    RQ_REQUIRE(adam_config_ok(*config), RQ_ERR_INVALID_ARGUMENT, "lr, eps and weight_decay must be non-negative and the betas in [0, 1)");
     rq_device* dev = pol->dev;
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     rq_optimizer* o = new (std::nothrow) rq_optimizer();
@@ -288,6 +344,128 @@ RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer*
     RQ_HIP(e);
     if (memory == RQ_DST_HOST)
         RQ_HIP(hipMemcpyAsync(losses, d_losses, (size_t)n_updates * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
+    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    return RQ_OK;
+}
+
+// ---------------------------------------------------------------------------- the update on the device, a bank at once ---
+RQ_API int rq_trajectory_policies_loss_grad(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target,
+                                            uint32_t ld_target, int start, float* loss, float* grad_weights, int memory) {
+    RQ_REQUIRE(t && bank && policy_id && loss && grad_weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = bank_loss_check(t, bank, policy_id, target, ld_target, start, memory, "rq_trajectory_policies_loss_grad"); if (rc) return rc;
+    rq_device* dev = t->env->dev;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    const size_t P = bank->n_policies, grad_floats = P * RQ_POLICY_NUM_WEIGHTS;
+    const float* d_target = nullptr; uint32_t ld_y = 0;
+    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, start, memory, P, &d_target, &ld_y); if (rc) return rc;
+    float* d_grad = memory == RQ_DST_HOST ? t->grad.out.get() : grad_weights;
+    float* d_loss = memory == RQ_DST_HOST ? t->grad.out.get() + grad_floats : loss;
+    RQ_HIP(enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, d_grad, d_loss));
+    // (t->grad.valid stays false: the saved state is no single policy's, rq_trajectory_policy_backward has nothing to follow)
+    if (memory == RQ_DST_HOST) {
+        // a policy that owns no wave has no gradient row on the device: the caller's row stays as it was
+        std::vector<uint32_t> owns;
+        try { owns.assign(P, 0u); } catch (const std::bad_alloc&) { return fail(RQ_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+        for (uint32_t id : bank->table_ids) owns[id] = 1u;
+        for (size_t p = 0; p < P; ++p)
+            if (owns[p])
+                RQ_HIP(hipMemcpyAsync(grad_weights + p * RQ_POLICY_NUM_WEIGHTS, d_grad + p * RQ_POLICY_NUM_WEIGHTS,
+                                      RQ_POLICY_NUM_WEIGHTS * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
+        RQ_HIP(hipMemcpyAsync(loss, d_loss, P * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
+    }
+    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    return RQ_OK;
+}
+
+RQ_API int rq_bank_optimizer_create(rq_policy_bank* bank, const rq_adam_config* config, uint32_t n_cfg, rq_bank_optimizer** out) {
+    RQ_REQUIRE(bank && config && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    const uint32_t P = bank->n_policies;
+    RQ_REQUIRE(n_cfg == 1 || n_cfg == P, RQ_ERR_INVALID_ARGUMENT,
+               "n_cfg must be 1 (one configuration for every policy) or the bank's " + std::to_string(P) + " policies, not " + std::to_string(n_cfg));
+    for (uint32_t k = 0; k < n_cfg; ++k)
+        RQ_REQUIRE(adam_config_ok(config[k]), RQ_ERR_INVALID_ARGUMENT,
+                   "lr, eps and weight_decay must be non-negative and the betas in [0, 1) (configuration " + std::to_string(k) + ")");
+    rq_device* dev = bank->dev;
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    rq_bank_optimizer* o = new (std::nothrow) rq_bank_optimizer();
+    RQ_REQUIRE(o, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
+    o->dev = dev; o->ordinal = dev->ordinal; o->bank = bank; o->bank_uid = bank->uid; o->n_policies = P;
+    const size_t entries = (size_t)rq::RQ_PACKED_FLOATS + rq::RQ_PACKED_GRAD_FLOATS, floats = (size_t)P * RQ_POLICY_NUM_WEIGHTS;
+    std::vector<rq::PackGather> table;
+    std::vector<rq::AdamState> st;
+    try {
+        table.resize(entries); rq::pack_gather_table(table.data());
+        st.resize(P);
+    } catch (const std::bad_alloc&) {
+        delete o;
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_bank_optimizer_create: host allocation failed");
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        const rq_adam_config& c = config[n_cfg == 1 ? 0 : p];
+        st[p] = rq::AdamState{c.lr, c.beta1, c.beta2, c.eps, c.weight_decay, 1.0, 1.0, 0u, 0u};
+    }
+    hipError_t e = o->m.alloc(floats);
+    if (e == hipSuccess) e = o->v.alloc(floats);
+    if (e == hipSuccess) e = o->grad.alloc(floats);
+    if (e == hipSuccess) e = o->state.alloc(P);
+    if (e == hipSuccess) e = o->table.alloc(entries);
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e == hipSuccess) e = hipMemset(o->m, 0, floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(o->v, 0, floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(o->grad, 0, floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(o->state, st.data(), (size_t)P * sizeof(rq::AdamState), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->table, table.data(), entries * sizeof(rq::PackGather), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        delete o;
+        return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string("rq_bank_optimizer_create: ") + hipGetErrorString(e));
+    }
+    *out = o;
+    return RQ_OK;
+}
+
+RQ_API int rq_bank_optimizer_destroy(rq_bank_optimizer* opt) {
+    if (!opt) return RQ_OK;
+    DeviceScope on_device(opt->ordinal);
+    if (device_registry(opt->dev, 0)) (void)hipStreamSynchronize(opt->dev->stream);      // an update may still be queued
+    delete opt;
+    return RQ_OK;
+}
+
+RQ_API int rq_bank_optimizer_set_lr(rq_bank_optimizer* opt, const double* lr, uint32_t n) {
+    RQ_REQUIRE(opt && lr, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(n == 1 || n == opt->n_policies, RQ_ERR_INVALID_ARGUMENT,
+               "n must be 1 (one rate for every policy) or the bank's " + std::to_string(opt->n_policies) + " policies, not " + std::to_string(n));
+    for (uint32_t k = 0; k < n; ++k) RQ_REQUIRE(lr[k] >= 0.0, RQ_ERR_INVALID_ARGUMENT, "lr must be non-negative");
+    DeviceScope on_device(opt->dev); int rc = on_device.rc; if (rc) return rc;
+    RQ_HIP(rq::launch_adam_set_lr_bank(opt->dev->stream, opt->state, opt->n_policies, lr, n));
+    return RQ_OK;
+}
+
+RQ_API int rq_trajectory_policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* opt, const uint32_t* policy_id,
+                                          const float* target, uint32_t ld_target, int start, uint32_t n_updates, float* losses,
+                                          int memory) {
+    RQ_REQUIRE(t && bank && opt && policy_id && losses, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(opt->bank == bank && opt->bank_uid == bank->uid, RQ_ERR_INVALID_ARGUMENT,
+               "rq_trajectory_policies_distill: the optimizer was made for another bank");
+    RQ_REQUIRE(n_updates > 0, RQ_ERR_INVALID_ARGUMENT, "n_updates must be positive");
+    int rc = bank_loss_check(t, bank, policy_id, target, ld_target, start, memory, "rq_trajectory_policies_distill"); if (rc) return rc;
+    rq_device* dev = t->env->dev;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    const size_t P = bank->n_policies, n_losses = (size_t)n_updates * P;
+    const float* d_target = nullptr; uint32_t ld_y = 0;
+    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, start, memory, n_losses, &d_target, &ld_y); if (rc) return rc;
+    float* d_losses = memory == RQ_DST_HOST ? t->grad.out.get() + P * RQ_POLICY_NUM_WEIGHTS : losses;
+    hipError_t e = hipSuccess;
+    for (uint32_t k = 0; k < n_updates && e == hipSuccess; ++k) {       // back to back: nothing waits in between
+        e = enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, opt->grad, d_losses + (size_t)k * P);
+        if (e == hipSuccess) e = rq::launch_adam_repack_bank(dev->stream, bank->n_policies, bank->waves, opt->grad, bank->weights, opt->m,
+                                                             opt->v, opt->state, opt->table, bank->images, bank->gimages);
+    }
+    RQ_HIP(e);
+    if (memory == RQ_DST_HOST)
+        RQ_HIP(hipMemcpyAsync(losses, d_losses, n_losses * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
     if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
     return RQ_OK;
 }

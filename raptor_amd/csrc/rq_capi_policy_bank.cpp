@@ -11,9 +11,13 @@ constexpr const char* kWeightsShape = "expected 2084 weights per policy: W0[16,2
 
 inline uint32_t blocks_of(uint32_t n) { return (n + 63u) / 64u; }
 
+}  // namespace
+
+namespace rqh {
+
 // policy_id[0 .. n): every id names a policy of the bank and is constant on every aligned block of 64 (checked before anything is
 // enqueued); the ragged last block is one block
-int check_ids(const rq_policy_bank* bank, const uint32_t* policy_id, uint32_t n) {
+int bank_check_ids(const rq_policy_bank* bank, const uint32_t* policy_id, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) {
         RQ_REQUIRE(policy_id[i] < bank->n_policies, RQ_ERR_INVALID_ARGUMENT,
                    "policy id out of range: env " + std::to_string(i) + " names policy " + std::to_string(policy_id[i]) + " of a bank of " +
@@ -33,7 +37,7 @@ int bank_table(rq_policy_bank* bank, rq_device* dev, uint64_t key, const uint32_
     bool same = bank->table_valid && bank->table_key == key && bank->table_ids.size() == blocks;
     for (uint32_t g = 0; same && g < blocks; ++g) same = bank->table_ids[g] == policy_id[(size_t)g * 64];
     if (same) return RQ_OK;
-    bank->table_valid = false;
+    bank->table_valid = bank->waves_valid = false;
     try {                                   // nothing throws across the boundary
         bank->table_ids.resize(blocks);
     } catch (const std::bad_alloc&) {
@@ -71,14 +75,63 @@ int bank_apply_reset(rq_policy_bank* bank) {
     return RQ_OK;
 }
 
-// slot `index` of both device arrays from 2084 host weights (synchronous: the caller's array is its own again on return)
-int bank_upload_slot(rq_policy_bank* bank, uint32_t index, const float* weights) {
-    std::vector<float> image;
-    try { image.resize(rq::RQ_PACKED_FLOATS); } catch (const std::bad_alloc&) {
+// The learner's transposed images [P][RQ_PACKED_GRAD_FLOATS], packed once from the master weights ON THE DEVICE (set_weights and
+// device-side updates have written there); from then on every writer of a slot's weights writes its transposed image too.
+int bank_grad_images(rq_policy_bank* bank) {
+    if (bank->gimages) return RQ_OK;
+    const size_t P = bank->n_policies;
+    std::vector<float> w, images;
+    try { w.resize(P * RQ_POLICY_NUM_WEIGHTS); images.resize(P * rq::RQ_PACKED_GRAD_FLOATS); } catch (const std::bad_alloc&) {
         return fail(RQ_ERR_OUT_OF_MEMORY, "policy bank: host allocation failed");
     }
+    RQ_HIP(hipStreamSynchronize(bank->dev->stream));
+    RQ_HIP(hipMemcpy(w.data(), bank->weights, w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < P; ++k) rq::pack_policy_grad(w.data() + k * RQ_POLICY_NUM_WEIGHTS, images.data() + k * rq::RQ_PACKED_GRAD_FLOATS);
+    DeviceBuffer<float> d;
+    RQ_HIP(d.alloc(images.size()));
+    RQ_HIP(hipMemcpy(d, images.data(), images.size() * sizeof(float), hipMemcpyHostToDevice));
+    bank->gimages = std::move(d);
+    return RQ_OK;
+}
+
+// The policies' waves as a CSR list, from the table in place (bank_table first): wave_offsets [P + 1] | wave_list [blocks], the
+// waves of a policy in ascending order.  Cached like the table: rebuilt only when bank_table uploaded another one.
+int bank_wave_lists(rq_policy_bank* bank) {
+    RQ_REQUIRE(bank->table_valid, RQ_ERR_NOT_INITIALIZED, "policy bank: no id table");
+    if (bank->waves_valid) return RQ_OK;
+    const uint32_t P = bank->n_policies, blocks = (uint32_t)bank->table_ids.size();
+    std::vector<uint32_t> csr;
+    try { csr.assign((size_t)P + 1 + blocks, 0u); } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "policy bank: host allocation failed");
+    }
+    for (uint32_t g = 0; g < blocks; ++g) ++csr[bank->table_ids[g] + 1];              // counts, one slot up
+    for (uint32_t p = 0; p < P; ++p) csr[p + 1] += csr[p];                            // -> offsets
+    std::vector<uint32_t> fill(csr.begin(), csr.begin() + P);
+    for (uint32_t g = 0; g < blocks; ++g) csr[(size_t)P + 1 + fill[bank->table_ids[g]]++] = g;     // block order: ascending per policy
+    RQ_HIP(bank->waves.reserve(bank->dev->stream, csr.size()));
+    RQ_HIP(hipMemcpyAsync(bank->waves, csr.data(), csr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, bank->dev->stream));
+    RQ_HIP(hipStreamSynchronize(bank->dev->stream));          // csr is pageable and goes away
+    bank->waves_valid = true;
+    return RQ_OK;
+}
+
+}  // namespace rqh
+
+namespace {
+
+// slot `index` of the device arrays from 2084 host weights (synchronous: the caller's array is its own again on return)
+int bank_upload_slot(rq_policy_bank* bank, uint32_t index, const float* weights) {
+    std::vector<float> image;
+    try { image.resize(std::max<size_t>(rq::RQ_PACKED_FLOATS, rq::RQ_PACKED_GRAD_FLOATS)); } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "policy bank: host allocation failed");
+    }
+    if (bank->gimages) {               // the learner has been used: its transposed image of the slot follows
+        rq::pack_policy_grad(weights, image.data());
+        RQ_HIP(hipMemcpy(bank->gimages + (size_t)index * rq::RQ_PACKED_GRAD_FLOATS, image.data(),
+                         (size_t)rq::RQ_PACKED_GRAD_FLOATS * sizeof(float), hipMemcpyHostToDevice));
+    }
     rq::pack_policy(weights, image.data());
-    RQ_HIP(hipMemcpy(bank->images + (size_t)index * rq::RQ_PACKED_FLOATS, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice));
+    RQ_HIP(hipMemcpy(bank->images + (size_t)index * rq::RQ_PACKED_FLOATS, image.data(), (size_t)rq::RQ_PACKED_FLOATS * sizeof(float), hipMemcpyHostToDevice));
     RQ_HIP(hipMemcpy(bank->weights + (size_t)index * RQ_POLICY_NUM_WEIGHTS, weights, RQ_POLICY_NUM_WEIGHTS * sizeof(float), hipMemcpyHostToDevice));
     return RQ_OK;
 }
@@ -129,6 +182,15 @@ RQ_API int rq_policy_bank_set_weights(rq_policy_bank* bank, uint32_t index, cons
     return bank_upload_slot(bank, index, weights);
 }
 
+RQ_API int rq_policy_bank_get_weights(rq_policy_bank* bank, float* out) {
+    RQ_REQUIRE(bank && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    DeviceScope on_device(bank->dev); int rc = on_device.rc; if (rc) return rc;
+    RQ_HIP(hipMemcpyAsync(out, bank->weights, (size_t)bank->n_policies * RQ_POLICY_NUM_WEIGHTS * sizeof(float), hipMemcpyDeviceToHost,
+                          bank->dev->stream));              // behind every update enqueued so far
+    RQ_HIP(hipStreamSynchronize(bank->dev->stream));
+    return RQ_OK;
+}
+
 RQ_API int rq_policy_bank_reset(rq_policy_bank* bank) {
     RQ_REQUIRE(bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
     bank->needs_reset = true;      // applied on the next use, when the assignment says whose initial state an env takes
@@ -152,7 +214,7 @@ RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* par
     RolloutFrame f;
     int rc = rollout_check(f, dev, env, params, state, rng, bank && policy_id, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy bank lives on another device");
-    rc = check_ids(bank, policy_id, env->n); if (rc) return rc;
+    rc = bank_check_ids(bank, policy_id, env->n); if (rc) return rc;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = bank_size(bank, env->n); if (rc) return rc;
     RQ_REQUIRE(bank->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");

@@ -11,7 +11,13 @@
 //                                 arithmetic, dL/da = a - y on live entries; + per wave the squared error and the live count
 //   k_policy_loss_reduce          partials in wave order, x 2 / M once; loss = SSE / M
 //   k_adam_repack                 one workgroup: Adam on the 2 084 master weights, then both operand images from a gather table
-// The two forwards and the two backwards are one text each (rq_grad_forward.inc, rq_grad_backward.inc), compiled once per kernel.
+// The same update for a bank of P policies, one per 64-env block (rq_grad_bank.hpp, compiled at the end of the unit):
+//   k_policy_grad_forward_state_bank   k_policy_grad_forward_state with the wave's image picked by block_policy[blockIdx.x]
+//   k_policy_loss_backward_bank        k_policy_loss_backward likewise, both images
+//   k_policy_loss_reduce_bank          per policy: its waves' partials in ascending wave order (a CSR list), x 2 / M_p; loss_p
+//   k_adam_repack_bank                 one workgroup per policy: k_adam_repack on slot p; a policy without a wave is skipped whole
+//   k_adam_set_lr_bank                 [P] learning rates in stream order
+// The forwards and the backwards are one text each (rq_grad_forward.inc, rq_grad_backward.inc), compiled once per kernel.
 //
 // Layouts (rq_device_math.hpp "actor"): a wave owns 64 envs as 4 tiles of 16; lane (q, j) = (l >> 4, l & 15) holds, in the Q
 // layout, rows 4q .. 4q+3 of a 16-vector of env (tile t, j).  What the reverse pass needs where:
@@ -41,11 +47,13 @@ namespace rq {
 // rq_trajectory_relabel's bit for bit.
 #define RQ_GRAD_FORWARD_KERNEL k_policy_grad_forward
 #define RQ_GRAD_STORE_ACT 1
+#define RQ_GRAD_BANK 0
 #include "rq_grad_forward.inc"
 
 // the same pass without the action store: the saved state is all the loss-seeded backward reads
 #define RQ_GRAD_FORWARD_KERNEL k_policy_grad_forward_state
 #define RQ_GRAD_STORE_ACT 0
+#define RQ_GRAD_BANK 0
 #include "rq_grad_forward.inc"
 
 // ------------------------------------------------------------------ backward -----------
@@ -65,11 +73,13 @@ __device__ __forceinline__ float sigm2(float x) { return __builtin_amdgcn_rcpf(1
 // element), so r, z, n and h' are the values the actions were computed from.  dc[t] = dL/d(state after the step) of tile t.
 #define RQ_GRAD_BACKWARD_KERNEL k_policy_grad_backward
 #define RQ_GRAD_SEEDED 0
+#define RQ_GRAD_BANK 0
 #include "rq_grad_backward.inc"
 
 // the backward seeded by the loss itself (rq_grad_backward.inc)
 #define RQ_GRAD_BACKWARD_KERNEL k_policy_loss_backward
 #define RQ_GRAD_SEEDED 1
+#define RQ_GRAD_BANK 0
 #include "rq_grad_backward.inc"
 
 // grad[p] = sum over waves w = 0, 1, ... of partial[w][p], in that order

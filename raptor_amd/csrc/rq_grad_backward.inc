@@ -2,6 +2,8 @@
 //   RQ_GRAD_BACKWARD_KERNEL  the kernel's name
 //   RQ_GRAD_SEEDED           0: dL/da is read from gact (k_policy_grad_backward)
 //                            1: it is formed here from the masked squared error against a target (k_policy_loss_backward)
+//   RQ_GRAD_BANK             1: both images are those of the wave's policy, images + block_policy[blockIdx.x] * image_floats and
+//                            gimages + block_policy[blockIdx.x] * gimage_floats (k_policy_loss_backward_bank); 0: `packed`, `gpacked`
 // One text for both, and each a kernel of its own rather than a call into a shared function: the existing kernel's listing stays
 // the parent build's to the instruction.
 //
@@ -13,7 +15,13 @@
 // the reduction.  Beside its partials the wave leaves its squared error (lane-local sums, folded lane 0 .. 63) and its count of
 // live entries in wave_sse / wave_live [gridDim.x].
 __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
-        uint32_t n, uint32_t ld, uint32_t steps, const float* __restrict__ packed, const float* __restrict__ gpacked,
+        uint32_t n, uint32_t ld, uint32_t steps,
+#if RQ_GRAD_BANK
+        const float* __restrict__ images, const float* __restrict__ gimages, const uint32_t* __restrict__ block_policy,
+        uint32_t image_floats, uint32_t gimage_floats,
+#else
+        const float* __restrict__ packed, const float* __restrict__ gpacked,
+#endif
         const float* __restrict__ obs, const uint8_t* __restrict__ done, const float* __restrict__ saved,
 #if RQ_GRAD_SEEDED
         const float* __restrict__ target, uint32_t ld_y, uint32_t start_initial, float* __restrict__ partial,
@@ -25,6 +33,10 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
 #else
         const float* __restrict__ gact, uint32_t ld_g, uint32_t start_initial, float* __restrict__ gh_start,
         float* __restrict__ partial) {
+#endif
+#if RQ_GRAD_BANK
+    const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
+    const float* __restrict__ gpacked = gimages + (size_t)block_policy[blockIdx.x] * gimage_floats;
 #endif
     __shared__ float tile[16 * GL_ROW];
     __shared__ float sums[64 * GRAD_LANE_SUMS];
@@ -285,3 +297,4 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
 }
 #undef RQ_GRAD_BACKWARD_KERNEL
 #undef RQ_GRAD_SEEDED
+#undef RQ_GRAD_BANK

@@ -2,16 +2,26 @@
 //   RQ_GRAD_FORWARD_KERNEL   the kernel's name
 //   RQ_GRAD_STORE_ACT        1: the actions are written to act [t][4][ld_act] (k_policy_grad_forward); 0: they are not, and the
 //                            kernel has no such parameters (k_policy_grad_forward_state: the distillation update's pass)
+//   RQ_GRAD_BANK             1: the wave's image is that of its block's policy, images + block_policy[blockIdx.x] * image_floats
+//                            (k_policy_grad_forward_state_bank: one workgroup = one wave = one 64-env block); 0: `packed` is it
 // One text for both, and each a kernel of its own rather than a call into a shared function: the existing kernel's listing stays
 // the parent build's to the instruction.
 template <typename ACTOR>
 __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void RQ_GRAD_FORWARD_KERNEL(
-        uint32_t n, uint32_t ld, uint32_t steps, const float* __restrict__ packed, const float* __restrict__ obs,
-        const uint8_t* __restrict__ done, const float* __restrict__ hidden, uint32_t ld_h, uint32_t start_initial,
+        uint32_t n, uint32_t ld, uint32_t steps,
+#if RQ_GRAD_BANK
+        const float* __restrict__ images, const uint32_t* __restrict__ block_policy, uint32_t image_floats,
+#else
+        const float* __restrict__ packed,
+#endif
+        const float* __restrict__ obs, const uint8_t* __restrict__ done, const float* __restrict__ hidden, uint32_t ld_h, uint32_t start_initial,
 #if RQ_GRAD_STORE_ACT
         float* __restrict__ act, uint32_t ld_act,
 #endif
         float* __restrict__ saved) {
+#if RQ_GRAD_BANK
+    const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
+#endif
     ACTOR actor;
     actor.template load<kFusedBlock / 64>(packed);
     const uint32_t lane = threadIdx.x & 63, q = lane >> 4, j = lane & 15;
@@ -67,3 +77,4 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void RQ_GR
 }
 #undef RQ_GRAD_FORWARD_KERNEL
 #undef RQ_GRAD_STORE_ACT
+#undef RQ_GRAD_BANK

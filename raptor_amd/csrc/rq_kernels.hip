@@ -1462,3 +1462,6 @@ hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden,
 }
 
 }  // namespace rq
+
+// the population learner (the distillation update for a policy bank): its own file, behind everything else of this unit
+#include "rq_grad_bank.hpp"

@@ -232,6 +232,20 @@ enum { PACK_GATHER_NONE = 0xFFFF };
 hipError_t launch_adam_repack(hipStream_t s, const float* grad, float* w, float* m, float* v, AdamState* st, const PackGather* table,
                               float* packed, float* gpacked);
 hipError_t launch_adam_set_lr(hipStream_t s, AdamState* st, double lr);
+// The same update for a policy bank (rq_grad_bank.hpp): images [P][RQ_PACKED_FLOATS], gimages [P][RQ_PACKED_GRAD_FLOATS],
+// block_policy [ceil(n / 64)] as the bank's rollout takes them, and the policies' waves as a CSR list: wave_offsets [P + 1] into
+// wave_list [ceil(n / 64)], ascending within a policy.  launch_policy_loss_grad_bank: grad [P][2084] and loss [P], each policy's over
+// its own blocks (M_p = 0: 0; a policy without a wave: loss NaN, its gradient row not written); partial as above.
+// launch_adam_repack_bank: one Adam step per policy that owns a wave, on w / m / v [P][2084] with st [P], and both its images
+// rebuilt.  launch_adam_set_lr_bank: lr [n_lr], n_lr = 1 (for all) or P, a host array read before the call returns.
+hipError_t launch_policy_loss_grad_bank(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, uint32_t n_policies, const float* images,
+                                        const float* gimages, const uint32_t* block_policy, const uint32_t* wave_offsets,
+                                        const uint32_t* wave_list, const float* obs, const uint8_t* done, const float* hidden,
+                                        uint32_t ld_h, int start_initial, float* saved, const float* target, uint32_t ld_y,
+                                        float* partial, float* grad, float* loss);
+hipError_t launch_adam_repack_bank(hipStream_t s, uint32_t n_policies, const uint32_t* wave_offsets, const float* grad, float* w, float* m,
+                                   float* v, AdamState* st, const PackGather* table, float* images, float* gimages);
+hipError_t launch_adam_set_lr_bank(hipStream_t s, AdamState* st, uint32_t n_policies, const double* lr, uint32_t n_lr);
 // dst [rows][ld] <- src [rows] (device), row by row
 hipError_t launch_fill_rows(hipStream_t s, float* dst, uint32_t ld, const float* src, uint32_t rows);
 // vector.step (README.md:98) + reward/termination/statistics.  rollout != 0 adds the

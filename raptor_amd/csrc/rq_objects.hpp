@@ -9,7 +9,8 @@
 //   rq_capi_rollout.cpp  the loop body x K on the device (fused, or chained under a hipGraph), trajectories, relabelling with a policy
 //   rq_capi_teacher.cpp  the teacher bank
 //   rq_capi_policy_bank.cpp  the policy bank: many student checkpoints in one rollout, one per 64-env block
-//   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory; the distillation update (loss, Adam, repack)
+//   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory; the distillation update (loss, Adam, repack),
+//                        for one policy and for a policy bank
 //   rq_memory.hpp        rq::DeviceBuffer / rq::PinnedBuffer: every object below owns its device and pinned memory through them
 // rollout_check / rollout_begin / rollout_end (rq_capi_rollout.cpp) are the frame rq_rollout* and rq_rollout_teachers share.
 // Helpers live in namespace rqh (each .cpp says `using namespace rqh;`); nothing here is visible outside libraptor_quad.so.
@@ -307,6 +308,19 @@ struct rq_optimizer {
     DeviceBuffer<rq::PackGather> table;      // pack_gather_table
 };
 
+struct rq_policy_bank;
+// Adam's state for every policy of a bank (rq_capi_grad.cpp; kernel: rq_grad_bank.hpp k_adam_repack_bank)
+struct rq_bank_optimizer {
+    rq_device* dev = nullptr;
+    int ordinal = 0;
+    const rq_policy_bank* bank = nullptr;    // compared, with bank_uid, never followed
+    uint64_t bank_uid = 0;
+    uint32_t n_policies = 0;
+    DeviceBuffer<float> m, v, grad;          // [n_policies][2084] each
+    DeviceBuffer<rq::AdamState> state;       // [n_policies]: every hyper-parameter per policy
+    DeviceBuffer<rq::PackGather> table;      // pack_gather_table, shared
+};
+
 struct rq_teacher_bank {
     rq_device* dev = nullptr;
     int ordinal = 0;
@@ -350,6 +364,13 @@ struct rq_policy_bank {
     uint32_t batch = 0, ld = 0;      // 0 = not sized yet
     bool needs_reset = true;         // hidden must be (re)filled with every env's own policy's initial state before use
     DeviceBuffer<float> hidden;      // [16][ld]
+    // the learner (rq_trajectory_policies_loss_grad / _distill): the transposed images, packed from `weights` at the first learner
+    // use and kept current from then on (rq_policy_bank_set_weights; a device-side update writes them itself), and the policies'
+    // waves as a CSR list built from table_ids - valid while `table` is what it was built from
+    uint64_t uid = fresh_version();  // what an optimizer knows its bank by, beside the address
+    DeviceBuffer<float> gimages;     // [n_policies][rq::RQ_PACKED_GRAD_FLOATS]
+    DeviceBuffer<uint32_t> waves;    // wave_offsets [n_policies + 1] | wave_list [blocks]
+    bool waves_valid = false;
 };
 
 // From kGpuLayoutMinEnvs envs up the row-major <-> field-major change runs on the GPU (k_soa_to_rows /
@@ -417,6 +438,15 @@ int policy_images16(rq_policy* pol);     // the bf16 / f16x2 images repacked fro
 // what is defined at the native rate only (sequence evaluation, relabelling, the learner, the self test) refuses a policy whose
 // native interval is above 1: a recording does not carry the phase it started at
 int require_native_rate(const rq_policy* pol, const char* what);
+
+// ---- rq_capi_policy_bank.cpp: what the bank's rollout and its learner (rq_capi_grad.cpp) share; all but bank_check_ids need the
+// caller's DeviceScope ----
+int bank_check_ids(const rq_policy_bank* bank, const uint32_t* policy_id, uint32_t n);      // before anything is enqueued
+int bank_table(rq_policy_bank* bank, rq_device* dev, uint64_t key, const uint32_t* policy_id, uint32_t n);
+int bank_size(rq_policy_bank* bank, uint32_t batch);
+int bank_apply_reset(rq_policy_bank* bank);
+int bank_grad_images(rq_policy_bank* bank);       // gimages packed from the device's weights, once
+int bank_wave_lists(rq_policy_bank* bank);        // `waves` for the current table
 
 // ---- rq_capi_rollout.cpp ----
 // What a rollout of either kind (a policy's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope: the checks

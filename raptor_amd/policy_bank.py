@@ -2,7 +2,8 @@
 
 Post-training of rl-tools/raptor writes a checkpoint and an ``evaluation/*`` record every epoch, and its users pick the student by
 closed-loop return, episode length and share terminated; hyper-parameter sweeps and seed populations of ``training.Distiller`` ask
-the same question of many weight vectors.  ``PolicyBank`` holds P policies of the ``Raptor`` topology on the device (fp32) and
+the same question of many weight vectors - and ``training.BankDistiller`` is their learner: it updates every policy of a bank on
+its own blocks of a recording in one go, on the device, so the bank flies again with the new weights.  ``PolicyBank`` holds P policies of the ``Raptor`` topology on the device (fp32) and
 ``vector.rollout(..., bank, ..., policy_ids=ids)`` flies env ``i`` with policy ``ids[i]`` - in ONE launch: a 64-env block is one
 wave of the fused kernel and the weights are that wave's matrix operands, so the granularity is the block: ``ids`` must be
 constant on every aligned block of 64 env indices (``block_policy_assignment`` deals blocks round-robin).  What an env computes
@@ -87,6 +88,7 @@ class PolicyBank:
             raise ValueError(f"weights must be [n_policies, {POLICY_NUM_WEIGHTS}]")
         self.n_policies = int(w.shape[0])
         self._weights = w.copy()
+        self._weights_on_device = False      # training.BankDistiller.step: the device's weights are newer than _weights
         self._device = device
         h = C.c_void_p()
         _lib.call("rq_policy_bank_create", device._h, _lib.fptr(w), self.n_policies, C.byref(h))
@@ -112,6 +114,10 @@ class PolicyBank:
 
     @property
     def weights(self):
+        if self._weights_on_device:          # updated on the device (training.BankDistiller.step): fetched once, when first asked for
+            w = np.empty((self.n_policies, POLICY_NUM_WEIGHTS), np.float32)
+            _lib.call("rq_policy_bank_get_weights", self._h, _lib.fptr(w))
+            self._weights, self._weights_on_device = w, False
         return self._weights
 
     def set_weights(self, index, weights):
@@ -122,7 +128,7 @@ class PolicyBank:
         if not 0 <= int(index) < self.n_policies:
             raise ValueError(f"policy index {index} is outside a bank of {self.n_policies}")
         _lib.call("rq_policy_bank_set_weights", self._h, int(index), _lib.fptr(w))
-        self._weights[int(index)] = w
+        self.weights[int(index)] = w         # (the other rows fetched first, should an update have left the host copy behind)
 
     def reset(self):
         """hidden state <- every env's own policy's initial_hidden_state (applied by the next use that knows the assignment)."""

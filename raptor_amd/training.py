@@ -17,6 +17,15 @@ For the distillation loss itself - the masked MSE against the labels - the whole
     loss, grad = distiller.loss_and_grad(traj)              # the same loss and its gradient, no update
 
 Any other loss goes the first way.
+
+A sweep or a seed population is distilled in one go: ``BankDistiller`` runs that update for every policy of a
+``policy_bank.PolicyBank`` at once, each on the 64-env blocks of the recording that ``policy_ids`` deals it, with its own
+hyper-parameters - one student's launch count for the whole bank, and the bank flies its next rollout with the updated weights:
+
+    bank = PolicyBank(device, W)                              # [P, 2084]
+    sweep = BankDistiller(bank, lr=np.geomspace(1e-4, 1e-2, P))
+    losses = sweep.step(traj, ids, target=labels, updates=10) # [10, P]
+    table = bank.evaluate(vector, device, env, params, state, rng, 500, ids)
 """
 import ctypes as C
 
@@ -224,4 +233,112 @@ class Distiller:
                       _device_ptr(losses), 1 if wait else 2)
         self._target_in_flight = keep      # until the next step: with wait=False the engine's stream may not have read it yet
         self.policy._weights_on_device = True
+        return losses
+
+
+def _per_policy(name, value, n_policies):
+    """a hyper-parameter given as a scalar or as one value per policy -> float64 [n_policies]"""
+    a = np.asarray(value, np.float64)
+    if a.ndim == 0:
+        return np.full(n_policies, float(a))
+    if a.ndim != 1 or a.size not in (1, n_policies):
+        raise ValueError(f"{name} must be a scalar or hold one value per policy ({n_policies}), not {a.shape}")
+    return np.full(n_policies, a[0]) if a.size == 1 else np.ascontiguousarray(a)
+
+
+class BankDistiller:
+    """``Distiller`` for every policy of a ``PolicyBank`` at once (rq_trajectory_policies_distill): policy p is updated on the
+    64-env blocks of the recording that ``policy_ids`` names it for - its loss is the masked MSE over those envs alone - with
+    its own Adam state and hyper-parameters.  ``lr``, ``betas[0]``, ``betas[1]``, ``eps`` and ``weight_decay`` are each a scalar or
+    a length-P sequence: that is the sweep.  What policy p gets is, bit for bit, what a ``Distiller`` of its own gets on a
+    recording of its blocks; the cost is one student's launches.  The bank's weights are updated in place on the device: its next
+    rollout flies them, ``bank.weights`` fetches them when first read.  A policy that owns no block is left alone (loss NaN).
+
+    ``policy_ids``: one id per env of the trajectory, constant on every aligned block of 64 (``check_policy_ids``).  ``target``
+    and ``start`` as for ``Distiller``; ``start="current"`` reads the bank's hidden state."""
+
+    def __init__(self, bank, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        P = int(bank.n_policies)
+        if len(betas) != 2:
+            raise ValueError("betas must be a pair")
+        cols = [_per_policy("lr", lr, P), _per_policy("betas[0]", betas[0], P), _per_policy("betas[1]", betas[1], P),
+                _per_policy("eps", eps, P), _per_policy("weight_decay", weight_decay, P)]
+        self.bank = bank
+        self._cfg = (_lib.AdamConfig * P)(*[_lib.AdamConfig(*(float(c[p]) for c in cols)) for p in range(P)])
+        self._h = None
+        self._fin = None
+        self._target_in_flight = None
+
+    def _handle(self):
+        if self._h is None:
+            import weakref
+            h = C.c_void_p()
+            _lib.call("rq_bank_optimizer_create", self.bank._h, self._cfg, len(self._cfg), C.byref(h))
+            self._h = h
+            self._fin = weakref.finalize(self, _lib.load().rq_bank_optimizer_destroy, h)
+        return self._h
+
+    def set_lr(self, lr):
+        """New learning rates (a scalar or one per policy) for the updates enqueued from now on."""
+        rates = _per_policy("lr", lr, len(self._cfg))
+        for c, r in zip(self._cfg, rates):
+            c.lr = float(r)
+        if self._h is not None:
+            _lib.call("rq_bank_optimizer_set_lr", self._h, rates.ctypes.data, rates.size)
+
+    def _check(self, traj, policy_ids, start, updates=1):
+        """the refusals Python makes itself, before any library call -> (ids, updates)"""
+        from .policy_bank import check_policy_ids
+        if start not in START:
+            raise ValueError('start must be "initial" or "current"')
+        updates = int(updates)
+        if updates < 1:
+            raise ValueError("updates must be at least 1")
+        return check_policy_ids(policy_ids, self.bank.n_policies, traj._env.N_ENVIRONMENTS), updates
+
+    def loss_and_grad(self, traj, policy_ids, target=None, start="initial"):
+        """-> (loss [P], dloss/dweights [P, 2084]), every policy's over its own blocks; no update.  Device tensors when torch is
+        present, NumPy otherwise (or with a NumPy target).  A policy that owns no block: loss NaN, its gradient row zero."""
+        ids, _ = self._check(traj, policy_ids, start)
+        P = int(self.bank.n_policies)
+        ptr, ld_t, on_device, keep = Distiller._target(traj, target)
+        dev = Distiller._torch_device(traj) if on_device is not False else None
+        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
+        if dev is None:
+            if on_device:
+                raise ValueError("a device target needs torch")
+            loss, grad = np.empty(P, np.float32), np.zeros((P, _lib.POLICY_NUM_WEIGHTS), np.float32)
+            _lib.call("rq_trajectory_policies_loss_grad", traj._require("trajectory"), self.bank._h, ids.ctypes.data, ptr, ld_t,
+                      START[start], _lib.fptr(loss), _lib.fptr(grad), 0)
+            return loss, grad
+        import torch
+        loss = torch.empty(P, dtype=torch.float32, device=dev)
+        grad = torch.zeros((P, _lib.POLICY_NUM_WEIGHTS), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
+        _lib.call("rq_trajectory_policies_loss_grad", traj._require("trajectory"), self.bank._h, ids.ctypes.data, ptr, ld_t,
+                  START[start], _device_ptr(loss), _device_ptr(grad), 1)
+        return loss, grad
+
+    def step(self, traj, policy_ids, target=None, start="initial", updates=1, wait=True):
+        """``updates`` Adam steps of every policy on its blocks of the recording, enqueued in one call -> the losses before each
+        of them, [updates, P] (a device tensor when torch is present, NumPy otherwise).  ``wait=False`` (torch only) returns once
+        the work is enqueued on the engine's stream: a rollout of the bank asked for next flies the updated weights."""
+        ids, updates = self._check(traj, policy_ids, start, updates)
+        P = int(self.bank.n_policies)
+        ptr, ld_t, on_device, keep = Distiller._target(traj, target)
+        opt = self._handle()
+        dev = Distiller._torch_device(traj)
+        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
+        if dev is None or on_device is False:
+            losses = np.empty((updates, P), np.float32)
+            _lib.call("rq_trajectory_policies_distill", traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, ptr, ld_t,
+                      START[start], updates, _lib.fptr(losses), 0)
+        else:
+            import torch
+            losses = torch.empty((updates, P), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()      # once per call, not per update
+            _lib.call("rq_trajectory_policies_distill", traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, ptr, ld_t,
+                      START[start], updates, _device_ptr(losses), 1 if wait else 2)
+        self._target_in_flight = keep      # until the next step: with wait=False the engine's stream may not have read it yet
+        self.bank._weights_on_device = True
         return losses
