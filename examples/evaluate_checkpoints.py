@@ -3,6 +3,12 @@
 policy's closed-loop record: what a checkpoint of a post-training run is picked by (return, episode length, share terminated).
 
     python examples/evaluate_checkpoints.py [--policies 1000] [--blocks 1] [--checkpoints DIR] [--sigma 0.05] [--show 10] [--mode fused|chained]
+                                            [--native-interval R [R ...]] [--dt SECONDS] [--figure-eight]
+
+At deployment conditions: --dt 0.0025 --native-interval 4 flies every checkpoint at 400 Hz with its hidden state moving every 4th step
+(the episode stays 5 s: 2 000 steps); several values of R are dealt to the policies in turn (policy k: R[k % len(R)]), which sweeps the
+interval when the policies are copies of one checkpoint (--sigma 0).  --figure-eight: the bank tracks the 0.3 m x 0.15 m figure-eight
+of examples/track_figure_eight.py from hover at the origin, and the table gains every policy's RMS distance to the setpoint.
 
 Without --checkpoints the bank holds the shipped policy (policy 0) and perturbed copies of it, weights + sigma * N(0, 1): the further a
 copy strays, the worse it flies.  --blocks: 64-env blocks per policy (more envs, tighter means).
@@ -16,6 +22,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import raptor_amd.l2f as l2f                                                           # noqa: E402
+from raptor_amd import tracking                                                        # noqa: E402
 from raptor_amd.foundation_policy import load_weights                                  # noqa: E402
 from raptor_amd.policy_bank import PolicyBank, block_policy_assignment                 # noqa: E402
 
@@ -28,6 +35,10 @@ def main():
     ap.add_argument("--sigma", type=float, default=0.05)
     ap.add_argument("--show", type=int, default=10)
     ap.add_argument("--mode", default="fused", choices=["fused", "chained"])
+    ap.add_argument("--native-interval", type=int, nargs="+", default=[1], metavar="R",
+                    help="native interval of the policies, 1 .. 64; several: dealt to the policies in turn")
+    ap.add_argument("--dt", type=float, default=None, help="control interval in seconds (default: the env's 0.01); the episode stays as long")
+    ap.add_argument("--figure-eight", action="store_true", help="track a figure-eight instead of holding the origin")
     args = ap.parse_args()
 
     device = l2f.Device()
@@ -40,26 +51,41 @@ def main():
         W = np.stack([w0] + [w0 + np.float32(args.sigma) * np.random.default_rng(100 + k).standard_normal(w0.size).astype(np.float32)
                              for k in range(1, args.policies)])
         bank = PolicyBank(device, W.astype(np.float32))
+    intervals = np.resize(np.asarray(args.native_interval, np.uint32), bank.n_policies)
+    bank.native_interval = intervals
     n = bank.n_policies * 64 * args.blocks
     vector = l2f.vector(n)
     rng, env = vector.VectorRng(), vector.VectorEnvironment()
     params, state = vector.VectorParameters(), vector.VectorState()
     vector.initialize_rng(device, rng, 0)
     vector.initialize_environment(device, env)
+    cfg = env.config
+    if args.dt is not None:                        # the same seconds per episode at another control rate
+        cfg.episode_step_limit = int(round(cfg.episode_step_limit * float(cfg.dt) / args.dt))
+        cfg.dt = args.dt
+    if args.figure_eight:
+        cfg.init_guidance = 1.0                    # hover at the origin, where the path starts
+    env.config = cfg
     vector.sample_initial_parameters(device, env, params, rng)
     vector.sample_initial_state(device, env, params, state, rng)
     ids = block_policy_assignment(n, bank.n_policies)
-    steps = env.config.episode_step_limit
+    steps = int(cfg.episode_step_limit)
+    ref = None
+    if args.figure_eight:
+        ref = l2f.Reference(device, tracking.lissajous(steps, float(cfg.dt), amplitude=(0.3, 0.15, 0.0), period=5.0))
     device.timer_start()
-    tab = bank.evaluate(vector, device, env, params, state, rng, steps, ids, mode=args.mode)
+    tab = bank.evaluate(vector, device, env, params, state, rng, steps, ids, mode=args.mode, reference=ref)
     ms = device.timer_stop()
-    print(f"{bank.n_policies} policies x {64 * args.blocks} envs = {n} envs, {steps} steps ({args.mode}): {ms:.1f} ms on the device, "
-          f"{int(tab['episodes'].sum())} episodes finished")
-    print(f"{'policy':>8} {'envs':>6} {'episodes':>9} {'mean return':>12} {'std':>9} {'mean length':>12} {'terminated':>11}")
+    print(f"{bank.n_policies} policies x {64 * args.blocks} envs = {n} envs, {steps} steps of {float(cfg.dt):g} s ({args.mode}"
+          f"{', figure-eight' if ref is not None else ''}): {ms:.1f} ms on the device, {int(tab['episodes'].sum())} episodes finished")
+    rmse = tab.get("tracking_rmse")
+    print(f"{'policy':>8} {'R':>3} {'envs':>6} {'episodes':>9} {'mean return':>12} {'std':>9} {'mean length':>12} {'terminated':>11}" +
+          (f" {'RMSE [m]':>9}" if rmse is not None else ""))
     order = np.argsort(-np.nan_to_num(tab["mean_return"], nan=-np.inf))
     for k in order[:args.show]:
-        print(f"{k:8d} {tab['envs'][k]:6d} {tab['episodes'][k]:9d} {tab['mean_return'][k]:12.3f} {tab['std_return'][k]:9.3f} "
-              f"{tab['mean_length'][k]:12.1f} {tab['termination_share'][k]:11.3f}" + (f"  {os.path.basename(names[k])}" if names else ""))
+        print(f"{k:8d} {intervals[k]:3d} {tab['envs'][k]:6d} {tab['episodes'][k]:9d} {tab['mean_return'][k]:12.3f} {tab['std_return'][k]:9.3f} "
+              f"{tab['mean_length'][k]:12.1f} {tab['termination_share'][k]:11.3f}" + (f" {rmse[k]:9.4f}" if rmse is not None else "") +
+              (f"  {os.path.basename(names[k])}" if names else ""))
     best = int(order[0])
     print(f"best by return: policy {best}" + (f" ({names[best]})" if names else "") +
           f", mean return {tab['mean_return'][best]:.3f}, mean length {tab['mean_length'][best]:.1f}, "

@@ -81,7 +81,8 @@ extern "C" {
                               5 (round 6): rq_device_{set,get}_resident; no struct changed
                               (still 5: rq_policy_{set,get}_native_interval added, no struct changed)
                               (still 5: rq_policy_bank_* and rq_rollout_policies, then rq_bank_optimizer_* and rq_trajectory_policies_*
-                              added, no struct changed) */
+                              added, no struct changed)
+                              (still 5: rq_policy_bank_{set,get}_native_interval and rq_rollout_policies_track added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -561,8 +562,8 @@ RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* par
 
 /* ---- Policy bank: many student policies in ONE rollout, one per wave.  Post-training writes a checkpoint per epoch and its
  * users pick the student by closed-loop return, episode length and share terminated; sweeps and seed populations ask the same
- * question.  A bank holds P policies of the Raptor topology (fp32; no Standardize stage, no SampleAndSquash stage, native interval
- * 1) as P operand images - the image rq_policy_pack_image returns for RQ_POLICY_FP32, slot after slot on the device - and a
+ * question.  A bank holds P policies of the Raptor topology (fp32; no Standardize stage, no SampleAndSquash stage; a native interval
+ * per policy, 1 by default) as P operand images - the image rq_policy_pack_image returns for RQ_POLICY_FP32, slot after slot on the device - and a
  * rollout flies every aligned block of 64 envs with the policy named for it: a block is one wave, the weights are that wave's
  * MFMA operands, so 1 000 checkpoints x 64 quadrotors is one launch of 64 000 envs.
  * weights: [n_policies][2084], each block in the checkpoint order of rq_policy_create. */
@@ -591,10 +592,33 @@ RQ_API int rq_policy_bank_get_hidden(rq_policy_bank* bank, float* host_out, uint
  * anything is enqueued (state, rng epoch, statistics and trajectory untouched): an id >= n_policies or ids that differ inside a
  * block (RQ_ERR_INVALID_ARGUMENT), a bank / trajectory of another device or env (RQ_ERR_SHAPE_MISMATCH), a trajectory without
  * room for n_steps, an unknown mode or flag (RQ_ERR_INVALID_ARGUMENT).  The per-block id table is cached in the bank: calls with
- * the same ids upload nothing.  Not offered with a bank: bf16 / f16x2, tracking, a native interval above 1, relabelling. */
+ * the same ids upload nothing.  The bank's native intervals (below) are honoured.  Not offered with a bank: bf16 / f16x2, the
+ * Standardize and SampleAndSquash stages, relabelling, the resident small-batch executors. */
 RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
                                const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                rq_trajectory* trajectory);
+/* Deployment control rate of a bank: rq_policy_set_native_interval's rule per policy - in every later rollout the hidden state of an
+ * env flown by policy p moves on only at the steps whose episode step count is a multiple of interval[p], and the action of every
+ * other step is computed from the last committed state (the first step of every episode is native).  interval: host array, n = 1
+ * (one interval for every policy) or n = n_policies; each entry 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL, anything else is refused
+ * (RQ_ERR_INVALID_ARGUMENT, the message names the index) and changes nothing.  The call waits for the device's stream first, as
+ * rq_policy_bank_set_weights does.  All intervals 1 (the default): every call does what it did before this entry point existed.
+ * What env i computes is, bit for bit, what rq_rollout computes for it with a policy created from the weights of policy_id[i] and
+ * set to interval[policy_id[i]] - policies of different intervals fly side by side in one launch (fused: k_rollout_fused_bank_rate,
+ * the RATE loop with image and interval chosen per wave; chained: k_actor_step_rate_bank).  The bank's learner
+ * (rq_trajectory_policies_loss_grad, rq_trajectory_policies_distill) is defined at the native rate only and refuses a bank with an
+ * interval above 1.  rq_policy_bank_get_native_interval: out [n_policies]. */
+RQ_API int rq_policy_bank_set_native_interval(rq_policy_bank* bank, const uint32_t* interval, uint32_t n);
+RQ_API int rq_policy_bank_get_native_interval(const rq_policy_bank* bank, uint32_t* out); /* [P] */
+/* rq_rollout_policies on a moving setpoint: rq_rollout_track's one difference (the row of the env's own episode step count comes off
+ * the position and linear velocity the policy sees; state, reward, termination and statistics stay absolute; a trajectory records
+ * what the policy saw; rq_env_get_tracking_error accumulates) with env i flown by policy policy_id[i] at its native interval.
+ * trajectory may be NULL.  Refused before anything is enqueued, beside rq_rollout_policies' refusals: a NULL reference
+ * (RQ_ERR_INVALID_ARGUMENT), a reference of another device (RQ_ERR_SHAPE_MISMATCH), one with fewer rows than episode_step_limit
+ * (RQ_ERR_INVALID_ARGUMENT).  Bit for bit rq_rollout_track of the 64-env slices; fused and chained give the same bits. */
+RQ_API int rq_rollout_policies_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
+                                     const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                     rq_trajectory* trajectory, const rq_reference* reference);
 
 /* ---- Distilling a bank: the update of rq_trajectory_distill for every policy of a bank at once - a sweep of learning rates or a seed
  * population costs one student's launch count, and "fly the bank, distil the bank, fly it again" never leaves the device.  The

@@ -205,6 +205,9 @@ _SIGNATURES = {
     "rq_policy_bank_get_hidden": [_vp, _fp, C.c_uint32],
     "rq_rollout_policies": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp],
     "rq_policy_bank_get_weights": [_vp, _fp],
+    "rq_policy_bank_set_native_interval": [_vp, _vp, C.c_uint32],
+    "rq_policy_bank_get_native_interval": [_vp, _vp],
+    "rq_rollout_policies_track": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp],
     "rq_trajectory_policies_loss_grad": [_vp, _vp, _vp, _fp, C.c_uint32, C.c_int, _fp, _fp, C.c_int],
     "rq_bank_optimizer_create": [_vp, C.POINTER(AdamConfig), C.c_uint32, C.POINTER(_vp)],
     "rq_bank_optimizer_destroy": [_vp],

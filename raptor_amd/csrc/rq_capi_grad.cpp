@@ -122,7 +122,8 @@ int bank_loss_check(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* poli
                     int start, int memory, const char* what) {
     RQ_REQUIRE(bank->dev == t->env->dev, RQ_ERR_SHAPE_MISMATCH, std::string(what) + ": the policy bank lives on another device");
     RQ_REQUIRE(t->length > 0, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": the trajectory is empty");
-    int rc = loss_check_call(t, target, ld_target, start, memory, what); if (rc) return rc;
+    int rc = require_bank_native_rate(bank, what); if (rc) return rc;
+    rc = loss_check_call(t, target, ld_target, start, memory, what); if (rc) return rc;
     rc = bank_check_ids(bank, policy_id, t->env->n); if (rc) return rc;
     if (start == RQ_GRAD_START_CURRENT)
         RQ_REQUIRE(bank->batch == t->env->n || bank->batch == 0 || bank->needs_reset, RQ_ERR_SHAPE_MISMATCH,

@@ -115,6 +115,15 @@ int bank_wave_lists(rq_policy_bank* bank) {
     return RQ_OK;
 }
 
+int require_bank_native_rate(const rq_policy_bank* bank, const char* what) {
+    if (!bank->rated) return RQ_OK;
+    uint32_t p = 0;
+    while (p + 1 < bank->n_policies && bank->intervals[p] == 1) ++p;
+    return fail(RQ_ERR_INVALID_ARGUMENT,
+                std::string(what) + ": defined at the native rate only, policy " + std::to_string(p) + " of the bank has native interval " +
+                    std::to_string(bank->intervals[p]) + " (rq_policy_bank_set_native_interval(bank, &one, 1) with one = 1)");
+}
+
 }  // namespace rqh
 
 namespace {
@@ -155,10 +164,16 @@ RQ_API int rq_policy_bank_create(rq_device* dev, const float* weights, uint32_t 
     }
     for (uint32_t k = 0; k < n_policies; ++k)
         rq::pack_policy(weights + (size_t)k * RQ_POLICY_NUM_WEIGHTS, images.data() + (size_t)k * rq::RQ_PACKED_FLOATS);
+    try { b->intervals.assign(n_policies, 1u); } catch (const std::bad_alloc&) {
+        delete b;
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_bank_create: host allocation failed");
+    }
     const size_t raw = (size_t)RQ_POLICY_NUM_WEIGHTS * n_policies;
     if (b->images.alloc(images.size()) != hipSuccess || b->weights.alloc(raw) != hipSuccess ||
+        b->intervals_dev.alloc(n_policies) != hipSuccess ||
         hipMemcpy(b->images, images.data(), images.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b->weights, weights, raw * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(b->weights, weights, raw * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b->intervals_dev, b->intervals.data(), (size_t)n_policies * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
         delete b;
         return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_bank_create: device allocation or upload failed");
     }
@@ -191,6 +206,35 @@ RQ_API int rq_policy_bank_get_weights(rq_policy_bank* bank, float* out) {
     return RQ_OK;
 }
 
+RQ_API int rq_policy_bank_set_native_interval(rq_policy_bank* bank, const uint32_t* interval, uint32_t n) {
+    RQ_REQUIRE(bank && interval, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    RQ_REQUIRE(n == 1 || n == bank->n_policies, RQ_ERR_INVALID_ARGUMENT,
+               "n must be 1 (one interval for every policy) or the bank's " + std::to_string(bank->n_policies) + " policies, not " + std::to_string(n));
+    for (uint32_t k = 0; k < n; ++k)
+        RQ_REQUIRE(interval[k] >= 1 && interval[k] <= RQ_POLICY_MAX_NATIVE_INTERVAL, RQ_ERR_INVALID_ARGUMENT,
+                   "native interval must be 1 .. " + std::to_string(RQ_POLICY_MAX_NATIVE_INTERVAL) + ": interval[" + std::to_string(k) + "] is " +
+                       std::to_string(interval[k]));
+    DeviceScope on_device(bank->dev); int rc = on_device.rc; if (rc) return rc;
+    RQ_HIP(hipStreamSynchronize(bank->dev->stream));          // a rollout in flight reads the table
+    std::vector<uint32_t> table;
+    try { table.resize(bank->n_policies); } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "policy bank: host allocation failed");
+    }
+    bool rated = false;
+    for (uint32_t p = 0; p < bank->n_policies; ++p) { table[p] = interval[n == 1 ? 0 : p]; rated = rated || table[p] > 1; }
+    // (synchronous: the caller's array is its own again on return; the host's copy changes only with the device's)
+    RQ_HIP(hipMemcpy(bank->intervals_dev, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    bank->intervals.swap(table);
+    bank->rated = rated;
+    return RQ_OK;
+}
+
+RQ_API int rq_policy_bank_get_native_interval(const rq_policy_bank* bank, uint32_t* out) {
+    RQ_REQUIRE(bank && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    std::memcpy(out, bank->intervals.data(), (size_t)bank->n_policies * sizeof(uint32_t));
+    return RQ_OK;
+}
+
 RQ_API int rq_policy_bank_reset(rq_policy_bank* bank) {
     RQ_REQUIRE(bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
     bank->needs_reset = true;      // applied on the next use, when the assignment says whose initial state an env takes
@@ -208,18 +252,31 @@ RQ_API int rq_policy_bank_get_hidden(rq_policy_bank* bank, float* host_out, uint
     return soa_to_host(bank->dev, bank->hidden, batch, bank->ld, RQ_POLICY_HIDDEN_DIM, host_out);
 }
 
-RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
-                               const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
-                               rq_trajectory* traj) {
+// rq_rollout_policies (ref == nullptr) and rq_rollout_policies_track.  With no reference and every interval 1 the launches are the
+// ones a bank's rollout always made; otherwise the RATE kernels, which take both.
+static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
+                                 const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                 rq_trajectory* traj, const rq_reference* ref) {
     RolloutFrame f;
     int rc = rollout_check(f, dev, env, params, state, rng, bank && policy_id, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy bank lives on another device");
+    if (ref) {          // a tracked rollout is refused here, before anything is enqueued (as rq_rollout_track refuses it)
+        RQ_REQUIRE(ref->dev == dev, RQ_ERR_SHAPE_MISMATCH, "reference lives on another device");
+        RQ_REQUIRE(ref->rows >= env->cfg.episode_step_limit, RQ_ERR_INVALID_ARGUMENT,
+                   "reference has fewer rows than episode_step_limit: the table must cover an episode");
+    }
     rc = bank_check_ids(bank, policy_id, env->n); if (rc) return rc;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = bank_size(bank, env->n); if (rc) return rc;
     RQ_REQUIRE(bank->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");
     rc = bank_table(bank, dev, env->uid, policy_id, env->n); if (rc) return rc;
     rc = bank_apply_reset(bank); if (rc) return rc;
+    rq::TrackPtrs trk{nullptr, 0, nullptr, nullptr};
+    if (ref) {
+        rc = env_track_stats(env, &trk.sq, &trk.steps); if (rc) return rc;
+        trk.ref = ref->d; trk.rows = ref->rows;
+    }
+    const bool rated = bank->rated;
     rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
     const rq::TrajPtrs& tp = f.tp;
     const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
@@ -230,20 +287,32 @@ RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* par
             RQ_HIP(dev->k_span.reserve(dev->stream, (size_t)waves * 5));
             dev->k_span_used = waves;
         }
-        RQ_HIP(rq::launch_rollout_fused_bank(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags, params->d,
-                                             state->d, bank->hidden, bank->weights, bank->images, bank->table, env->st, tp,
-                                             dev->k_timing ? dev->k_span.get() : nullptr));
+        if (ref || rated)
+            RQ_HIP(rq::launch_rollout_fused_bank_rate(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags, params->d,
+                                                      state->d, bank->hidden, bank->weights, bank->images, bank->table,
+                                                      bank->intervals_dev, env->st, tp, trk,
+                                                      dev->k_timing ? dev->k_span.get() : nullptr));
+        else
+            RQ_HIP(rq::launch_rollout_fused_bank(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags, params->d,
+                                                 state->d, bank->hidden, bank->weights, bank->images, bank->table, env->st, tp,
+                                                 dev->k_timing ? dev->k_span.get() : nullptr));
         dev->k_timed = dev->k_timing && n_steps > 0;
         dev->k_fetched = false;
     } else if (n_steps) {
-        // one step = observe -> the bank's actor step -> step (-> record), plain launches on the device's stream
+        // one step = observe (-> the setpoint taken off it) -> the bank's actor step -> step (-> record), plain launches on the
+        // device's stream.  The env's episode step count is that of this step's observation until k_step_bank moves it on.
         if (flags & RQ_ROLLOUT_AUTORESET)   // envs frozen by an earlier rollout start their next episode
             RQ_HIP(rq::launch_thaw_frozen_bank(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, bank->hidden, bank->weights,
                                                bank->table));
         for (uint32_t t = 0; t < n_steps; ++t) {
             RQ_HIP(rq::launch_observe(dev->stream, b, nc, noise, rng->seed, rng->epoch + t, nullptr, params->d, state->d, env->obs));
-            RQ_HIP(rq::launch_actor_step_bank(dev->stream, env->n, bank->images, bank->table, env->obs, env->ld, bank->hidden, bank->ld,
-                                              env->act, env->ld, env->st.frozen));
+            if (ref) RQ_HIP(rq::launch_track_shift(dev->stream, b, state->d, env->st, env->obs, trk));
+            if (rated)
+                RQ_HIP(rq::launch_actor_step_rate_bank(dev->stream, env->n, bank->images, bank->table, bank->intervals_dev, env->obs, env->ld,
+                                                       bank->hidden, bank->ld, env->act, env->ld, env->st.frozen, env->st.steps));
+            else
+                RQ_HIP(rq::launch_actor_step_bank(dev->stream, env->n, bank->images, bank->table, env->obs, env->ld, bank->hidden, bank->ld,
+                                                  env->act, env->ld, env->st.frozen));
             RQ_HIP(rq::launch_step_bank(dev->stream, b, sc, params->d, state->d, env->act, env->st, flags, smp, rng->seed, bank->hidden,
                                         bank->weights, bank->table));
             if (traj) {
@@ -254,6 +323,19 @@ RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* par
     }
     rollout_end(state, rng, n_steps, traj);
     return RQ_OK;
+}
+
+RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
+                               const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                               rq_trajectory* traj) {
+    return rollout_policies_impl(dev, env, params, state, bank, policy_id, rng, n_steps, mode, flags, traj, nullptr);
+}
+
+RQ_API int rq_rollout_policies_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
+                                     const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                     rq_trajectory* traj, const rq_reference* reference) {
+    RQ_REQUIRE(reference, RQ_ERR_INVALID_ARGUMENT, "null reference");
+    return rollout_policies_impl(dev, env, params, state, bank, policy_id, rng, n_steps, mode, flags, traj, reference);
 }
 
 }  // extern "C"

@@ -1299,7 +1299,7 @@ hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg
 // k_rollout_fused with the image chosen per workgroup (one workgroup = one wave = one 64-env block in both builds): the id is read
 // with a scalar load (a kernel argument indexed by blockIdx: provably wave-uniform, so `packed` is a scalar base for the image's
 // loads as it is in k_rollout_fused) ahead of the prologue's env loads, which hide its latency.  No SampleAndSquash stage, no
-// tracking, native interval 1 (the host offers none of them for a bank).
+// tracking, native interval 1 (a tracked bank, or one with an interval above 1: k_rollout_fused_bank_rate, last in this unit).
 template <bool NOISE, bool AUTORESET, bool RECORD, typename ACTOR>
 __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_bank(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
                                                                uint64_t seed, uint32_t epoch0, uint32_t n_steps,
@@ -1465,3 +1465,115 @@ hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden,
 
 // the population learner (the distillation update for a policy bank): its own file, behind everything else of this unit
 #include "rq_grad_bank.hpp"
+
+namespace rq {
+
+// ------------------------------------------------------------------ policy bank at a deployment rate, on a moving setpoint ---
+// (rq_policy_bank_set_native_interval, rq_rollout_policies_track.)  The bank's kernels above fly every policy at native interval 1 and
+// the origin; these fly policy p at policy_interval[p] and, with trk.ref, on the moving setpoint.  Still no new arithmetic: the RATE
+// text of rq_rollout_body.inc and k_actor_step_rate's rule, with the image AND the interval those of the wave's block.  Behind the
+// population learner, last in the unit, for the reason given above: the listings of everything before stay what they were.
+
+// k_rollout_fused_rate with the image and the interval chosen per workgroup: both table reads are scalar loads indexed by blockIdx
+// (the second by the first's result), issued ahead of the prologue's env loads as k_rollout_fused_bank's one is.  A wave whose policy
+// has interval 1 runs the RATE text with interval == 1: phase stays 0, every step is native, hold_carry holds nothing - the bits of
+// the plain kernel.  policy_interval [P], every entry 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL (the host refuses anything else: the phase
+// is a remainder by it).
+template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_bank_rate(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ images,
+                                                               const uint32_t* __restrict__ block_policy,
+                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
+                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool RATE = true, SAS = false;
+    constexpr SasArgs sas{};
+    const uint32_t policy = block_policy[blockIdx.x];
+    const uint32_t interval = policy_interval[policy];
+    const float* __restrict__ packed = images + (size_t)policy * image_floats;
+#include "rq_rollout_body.inc"
+}
+
+// k_actor_step_bank under the policies' native intervals (the chained bank rollout's actor when any interval is above 1):
+// k_actor_step_rate's rule - the hidden state is stored only for the rows at a native step, steps[i] % interval == 0 - with the image
+// and the interval of the wave's block.  steps: the envs' episode step counts at this step's observation (k_step_bank moves them on).
+template <typename ACTOR>
+__global__ __launch_bounds__(kBlock, 2) void k_actor_step_rate_bank(uint32_t n, const float* __restrict__ images,
+                                                            const uint32_t* __restrict__ block_policy,
+                                                            const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
+                                                            const float* __restrict__ obs, uint32_t ld_obs,
+                                                            float* hidden, uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
+                                                            const uint8_t* __restrict__ frozen, const uint32_t* __restrict__ steps) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t wave_base = wave * 64u;
+    if (wave_base >= n) return;                                  // wave-uniform; the table has ceil(n / 64) entries
+    const uint32_t policy = block_policy[wave];
+    const uint32_t interval = policy_interval[policy];
+    ACTOR actor;
+    actor.template load<kBlock / 64>(images + (size_t)policy * image_floats);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t i0 = wave_base + lane;
+    const uint32_t i = i0 < n ? i0 : n - 1;
+    float x[22], hQ[4][4], a[4];
+#pragma unroll
+    for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
+    load_hidden_q(hidden, ld_h, wave_base, n, hQ);
+    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
+    const bool commit = (i0 < n) && fz == 0;
+    const bool at_native = steps[i] % interval == 0;
+    const uint64_t hidden_mask = __builtin_amdgcn_ballot_w64(commit && at_native);
+    actor.step(x, hQ, a);
+    store_hidden_q(hidden, ld_h, wave_base, hidden_mask, hQ);
+    if (commit) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
+    }
+}
+
+// the instantiation for (noise, auto-reset, recording, tracking) of one actor build: one run-time switch per call
+template <typename ACTOR, bool NZ, bool AR, bool RC, bool TK>
+static inline void launch_fused_bank_rate_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
+                                                const uint32_t* policy_interval) {
+    const unsigned g = (a.b.n + kFusedBlock - 1) / kFusedBlock;
+    hipLaunchKernelGGL((k_rollout_fused_bank_rate<NZ, AR, RC, TK, ACTOR>), dim3(g), dim3(kFusedBlock), 0, s,
+                       a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
+                       policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.trk, a.span);
+}
+template <typename ACTOR, bool... DONE, typename... REST>
+static inline void launch_fused_bank_rate_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
+                                                const uint32_t* policy_interval, bool next, REST... rest) {
+    if (next) launch_fused_bank_rate_actor<ACTOR, DONE..., true>(s, a, images, block_policy, policy_interval, rest...);
+    else      launch_fused_bank_rate_actor<ACTOR, DONE..., false>(s, a, images, block_policy, policy_interval, rest...);
+}
+
+hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                          uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                          const float* params, float* state, float* hidden, const float* weights,
+                                          const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
+                                          StatsPtrs st, TrajPtrs traj, TrackPtrs trk, unsigned long long* span) {
+    if (b.n == 0 || n_steps == 0) return hipSuccess;
+    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span, trk};
+    // the two builds of launch_rollout_fused_bank: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
+    const bool rec = traj.obs != nullptr, track = trk.ref != nullptr;
+    if (b.n > 65536u) launch_fused_bank_rate_actor<ActorF32Lean>(s, a, images, block_policy, policy_interval, noise, ar, rec, track);
+    else              launch_fused_bank_rate_actor<ActorF32>(s, a, images, block_policy, policy_interval, noise, ar, rec, track);
+    return hipGetLastError();
+}
+
+hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy,
+                                       const uint32_t* policy_interval, const float* obs, uint32_t ld_obs, float* hidden, uint32_t ld_h,
+                                       float* act, uint32_t ld_act, const uint8_t* frozen, const uint32_t* steps) {
+    if (n == 0) return hipSuccess;
+    // launch_actor_step_bank's build (one 64-env group per wave): the same bits
+    k_actor_step_rate_bank<ActorF32Lean><<<grid_for((n + 63) / 64 * 64, kBlock), kBlock, 0, s>>>(
+        n, images, block_policy, policy_interval, (uint32_t)RQ_PACKED_FLOATS, obs, ld_obs, hidden, ld_h, act, ld_act, frozen, steps);
+    return hipGetLastError();
+}
+
+}  // namespace rq

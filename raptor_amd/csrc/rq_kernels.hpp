@@ -299,6 +299,18 @@ hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* para
 hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
                                    StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy);
 hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden, const float* weights, const uint32_t* block_policy);
+// The bank at its policies' native intervals and / or on a moving setpoint (rq_policy_bank_set_native_interval,
+// rq_rollout_policies_track): policy_interval [P], every entry 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL; trk.ref == nullptr: untracked.
+// The fused kernel is k_rollout_fused_rate with image and interval chosen per wave; the chained actor stores the hidden state of the
+// rows at a native step only (steps: the envs' episode step counts, as launch_actor_step_rate takes them).
+hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                          uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                          const float* params, float* state, float* hidden, const float* weights,
+                                          const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
+                                          StatsPtrs st, TrajPtrs traj, TrackPtrs trk, unsigned long long* span = nullptr);
+hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy,
+                                       const uint32_t* policy_interval, const float* obs, uint32_t ld_obs, float* hidden, uint32_t ld_h,
+                                       float* act, uint32_t ld_act, const uint8_t* frozen, const uint32_t* steps);
 // chained mode of a tracked rollout, between the observation's assembly (k_observe, or the k_step before) and the actor: the row of
 // each env's episode step count comes off obs [RQ_OBSERVATION_DIM][ld] in place, and the envs that are not frozen add this step's
 // tracking error - the fused kernel's arithmetic (rq_device_math.hpp track_*).  Appends a graph node under a GraphSink.

@@ -364,6 +364,11 @@ struct rq_policy_bank {
     uint32_t batch = 0, ld = 0;      // 0 = not sized yet
     bool needs_reset = true;         // hidden must be (re)filled with every env's own policy's initial state before use
     DeviceBuffer<float> hidden;      // [16][ld]
+    // rq_policy_bank_set_native_interval: policy p's hidden state moves on every intervals[p]-th step.  The device table is what the
+    // RATE kernels read; `rated` = any entry above 1 (all 1: the rollout launches the kernels it launched before the table existed)
+    std::vector<uint32_t> intervals;         // [n_policies], the host's copy
+    DeviceBuffer<uint32_t> intervals_dev;    // [n_policies]
+    bool rated = false;
     // the learner (rq_trajectory_policies_loss_grad / _distill): the transposed images, packed from `weights` at the first learner
     // use and kept current from then on (rq_policy_bank_set_weights; a device-side update writes them itself), and the policies'
     // waves as a CSR list built from table_ids - valid while `table` is what it was built from
@@ -447,6 +452,9 @@ int bank_size(rq_policy_bank* bank, uint32_t batch);
 int bank_apply_reset(rq_policy_bank* bank);
 int bank_grad_images(rq_policy_bank* bank);       // gimages packed from the device's weights, once
 int bank_wave_lists(rq_policy_bank* bank);        // `waves` for the current table
+// what is defined at the native rate only (the bank's learner) refuses a bank with a native interval above 1, as
+// require_native_rate refuses a policy
+int require_bank_native_rate(const rq_policy_bank* bank, const char* what);
 
 // ---- rq_capi_rollout.cpp ----
 // What a rollout of either kind (a policy's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope: the checks

@@ -637,7 +637,8 @@ class VectorModule:
         the row of each env's own episode step count; everything else (state, reward, termination, statistics) stays absolute, a
         ``trajectory`` records what the policy saw, and ``env.tracking_error()`` accumulates.  ``Raptor`` policies only.
         ``policy`` may also be a ``raptor_amd.policy_bank.PolicyBank``: ``policy_ids`` ([N] integers, constant on every aligned
-        block of 64 envs) names the student policy that flies each env, both modes."""
+        block of 64 envs) names the student policy that flies each env, both modes, every policy at the bank's native interval for
+        it.  A bank does not take ``reference`` here: ``PolicyBank.fly(..., reference=ref)`` is the bank's tracked rollout."""
         if reference is not None and teacher_ids is not None:
             raise ValueError("reference and teacher_ids do not combine: a TeacherBank rollout does not track")
         m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]

@@ -78,15 +78,35 @@ def policy_episode_table(env, policy_ids, n_policies):
                 mean_length=mean_length, termination_share=termination_share)
 
 
+def policy_tracking_table(sum_sq, steps, policy_ids, n_policies):
+    """Per-policy tracking error from the per-env sums ``env.tracking_error()`` returns: ``sum_sq`` [N] (sum of |p - p_ref|^2 over
+    the counted steps) and ``steps`` [N] (how many), grouped by ``policy_ids`` -> ``tracking_rmse`` [n_policies] (float64):
+    sqrt(sum of the policy's sums / sum of its counts), NaN for a policy without a counted step."""
+    ids = np.asarray(policy_ids, np.int64).ravel()
+    sq = np.asarray(sum_sq, np.float64).ravel()
+    cnt = np.asarray(steps, np.float64).ravel()
+    if not (ids.shape == sq.shape == cnt.shape):
+        raise ValueError("sum_sq, steps and policy_ids must hold one entry per env")
+    k = int(n_policies)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.sqrt(np.bincount(ids, weights=sq, minlength=k) / np.bincount(ids, weights=cnt, minlength=k))
+
+
+MAX_NATIVE_INTERVAL = 64      # RQ_POLICY_MAX_NATIVE_INTERVAL
+
+
 class PolicyBank:
     """``weights`` [P, 2084] float32, each row in the checkpoint order ``Raptor`` takes.  fp32 only; no Standardize or
-    SampleAndSquash stage, native interval 1."""
+    SampleAndSquash stage.  ``native_interval``: R, 1 to 64, a scalar or one per policy - policy p's hidden state moves on every
+    R[p]-th step of an episode only, as ``Raptor(native_interval=R)``'s does (flown at ``dt = 0.01 / R``); policies of different
+    intervals fly side by side in one rollout.  The learner (``training.BankDistiller``) takes a bank at interval 1 only."""
 
-    def __init__(self, device, weights):
+    def __init__(self, device, weights, native_interval=1):
         w = np.ascontiguousarray(weights, np.float32)
         if w.ndim != 2 or w.shape[0] == 0 or w.shape[1] != POLICY_NUM_WEIGHTS:
             raise ValueError(f"weights must be [n_policies, {POLICY_NUM_WEIGHTS}]")
         self.n_policies = int(w.shape[0])
+        intervals = self._checked_intervals(native_interval)
         self._weights = w.copy()
         self._weights_on_device = False      # training.BankDistiller.step: the device's weights are newer than _weights
         self._device = device
@@ -94,6 +114,33 @@ class PolicyBank:
         _lib.call("rq_policy_bank_create", device._h, _lib.fptr(w), self.n_policies, C.byref(h))
         self._h = h
         self._fin = weakref.finalize(self, _lib.load().rq_policy_bank_destroy, h)
+        self._intervals = np.ones(self.n_policies, np.uint32)
+        if (intervals != 1).any():
+            self.native_interval = intervals
+
+    def _checked_intervals(self, interval):
+        """a scalar or a length-P sequence of integers in 1 .. 64 -> uint32 [P]; ValueError otherwise (no library call)"""
+        a = np.asarray(interval)
+        if a.ndim > 1 or (a.ndim == 1 and a.size != self.n_policies):
+            raise ValueError(f"native_interval must be a scalar or one interval per policy: {a.size} for a bank of {self.n_policies}")
+        if a.dtype == bool or not (np.issubdtype(a.dtype, np.integer) or (np.issubdtype(a.dtype, np.floating) and np.all(a == np.floor(a)))):
+            raise ValueError("native_interval must be integers")
+        a = np.broadcast_to(a.astype(np.int64), (self.n_policies,))
+        bad = np.flatnonzero((a < 1) | (a > MAX_NATIVE_INTERVAL))
+        if bad.size:
+            raise ValueError(f"native_interval must be 1 .. {MAX_NATIVE_INTERVAL}: policy {int(bad[0])} is given {int(a[bad[0]])}")
+        return np.ascontiguousarray(a.astype(np.uint32))
+
+    @property
+    def native_interval(self):
+        """[P] uint32: policy p's native interval (a copy)."""
+        return self._intervals.copy()
+
+    @native_interval.setter
+    def native_interval(self, interval):
+        a = self._checked_intervals(interval)
+        _lib.call("rq_policy_bank_set_native_interval", self._h, a.ctypes.data, a.size)
+        self._intervals = a
 
     @classmethod
     def from_checkpoints(cls, device, paths, check_observation=True):
@@ -140,11 +187,37 @@ class PolicyBank:
         _lib.call("rq_policy_bank_get_hidden", self._h, _lib.fptr(out), int(batch))
         return out
 
-    def evaluate(self, vector, device, env, params, state, rng, n_steps, policy_ids=None, mode="fused", autoreset=True):
+    def fly(self, vector, device, env, params, state, rng, n_steps, policy_ids, mode="fused", autoreset=False, trajectory=None,
+            reference=None):
+        """The bank's own rollout call: ``vector.rollout(..., bank, ..., policy_ids=ids)`` - every policy at its native interval -
+        and, with ``reference`` (an ``l2f.Reference``), on that moving setpoint: each env sees position and linear velocity relative
+        to the row of its own episode step count, a ``trajectory`` records what the policy saw and ``env.tracking_error()``
+        accumulates, as in a ``Raptor`` policy's tracked rollout."""
+        from .l2f import ROLLOUT_AUTORESET, ROLLOUT_CHAINED, ROLLOUT_FUSED, Reference
+        m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
+        ids = check_policy_ids(policy_ids, self.n_policies, vector.N_ENVIRONMENTS)
+        args = (device._h, env._require("environment"), params._require("VectorParameters"), state._require("VectorState"), self._h,
+                ids.ctypes.data, rng._require("rng"), int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0,
+                trajectory._require("trajectory") if trajectory is not None else None)
+        if reference is None:
+            _lib.call("rq_rollout_policies", *args)
+        else:
+            if not isinstance(reference, Reference):
+                raise ValueError("reference must be an l2f.Reference")
+            _lib.call("rq_rollout_policies_track", *args, reference._h)
+
+    def evaluate(self, vector, device, env, params, state, rng, n_steps, policy_ids=None, mode="fused", autoreset=True,
+                 reference=None):
         """The closed-loop evaluation of the whole bank: statistics and hidden state start afresh, one rollout of ``n_steps`` flies
-        env i with policy ``policy_ids[i]`` (default: blocks dealt round-robin) -> ``policy_episode_table`` of what it finished."""
+        env i with policy ``policy_ids[i]`` (default: blocks dealt round-robin) at its native interval ->
+        ``policy_episode_table`` of what it finished.  With ``reference`` the bank tracks that moving setpoint and the table gains
+        ``tracking_rmse`` [P] (``policy_tracking_table`` of ``env.tracking_error()``, which starts afresh too)."""
         ids = block_policy_assignment(vector.N_ENVIRONMENTS, self.n_policies) if policy_ids is None else policy_ids
         env.reset_statistics()
         self.reset()
-        vector.rollout(device, env, params, state, self, rng, n_steps, mode=mode, autoreset=autoreset, policy_ids=ids)
-        return policy_episode_table(env, ids, self.n_policies)
+        self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference)
+        table = policy_episode_table(env, ids, self.n_policies)
+        if reference is not None:
+            sum_sq, steps = env.tracking_error()
+            table["tracking_rmse"] = policy_tracking_table(sum_sq, steps, ids, self.n_policies)
+        return table
