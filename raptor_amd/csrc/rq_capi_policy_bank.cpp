@@ -260,66 +260,41 @@ static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* p
     RolloutFrame f;
     int rc = rollout_check(f, dev, env, params, state, rng, bank && policy_id, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy bank lives on another device");
-    if (ref) {          // a tracked rollout is refused here, before anything is enqueued (as rq_rollout_track refuses it)
-        RQ_REQUIRE(ref->dev == dev, RQ_ERR_SHAPE_MISMATCH, "reference lives on another device");
-        RQ_REQUIRE(ref->rows >= env->cfg.episode_step_limit, RQ_ERR_INVALID_ARGUMENT,
-                   "reference has fewer rows than episode_step_limit: the table must cover an episode");
-    }
+    // a tracked rollout is refused here, before anything is enqueued (as rq_rollout_track refuses it)
+    if (ref) { rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc; }
     rc = bank_check_ids(bank, policy_id, env->n); if (rc) return rc;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = bank_size(bank, env->n); if (rc) return rc;
     RQ_REQUIRE(bank->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");
     rc = bank_table(bank, dev, env->uid, policy_id, env->n); if (rc) return rc;
     rc = bank_apply_reset(bank); if (rc) return rc;
-    rq::TrackPtrs trk{nullptr, 0, nullptr, nullptr};
-    if (ref) {
-        rc = env_track_stats(env, &trk.sq, &trk.steps); if (rc) return rc;
-        trk.ref = ref->d; trk.rows = ref->rows;
-    }
+    rc = rollout_track(f, env, ref); if (rc) return rc;
     const bool rated = bank->rated;
     rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
-    const rq::TrajPtrs& tp = f.tp;
-    const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
-    const bool noise = f.noise;
     if (mode == RQ_ROLLOUT_FUSED) {
-        if (dev->k_timing && n_steps) {                   // one (in, out) record per wave = per workgroup of the fused kernel
-            const uint32_t waves = blocks_of(env->n);
-            RQ_HIP(dev->k_span.reserve(dev->stream, (size_t)waves * 5));
-            dev->k_span_used = waves;
-        }
+        unsigned long long* span = nullptr;
+        rc = fused_span_begin(__func__, dev, env, n_steps, &span); if (rc) return rc;
         if (ref || rated)
-            RQ_HIP(rq::launch_rollout_fused_bank_rate(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags, params->d,
-                                                      state->d, bank->hidden, bank->weights, bank->images, bank->table,
-                                                      bank->intervals_dev, env->st, tp, trk,
-                                                      dev->k_timing ? dev->k_span.get() : nullptr));
+            RQ_HIP(rq::launch_rollout_fused_bank_rate(dev->stream, f.b, f.sc, f.nc, f.noise, f.smp, rng->seed, rng->epoch, n_steps, flags,
+                                                      params->d, state->d, bank->hidden, bank->weights, bank->images, bank->table,
+                                                      bank->intervals_dev, env->st, f.tp, f.trk, span));
         else
-            RQ_HIP(rq::launch_rollout_fused_bank(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags, params->d,
-                                                 state->d, bank->hidden, bank->weights, bank->images, bank->table, env->st, tp,
-                                                 dev->k_timing ? dev->k_span.get() : nullptr));
-        dev->k_timed = dev->k_timing && n_steps > 0;
-        dev->k_fetched = false;
-    } else if (n_steps) {
-        // one step = observe (-> the setpoint taken off it) -> the bank's actor step -> step (-> record), plain launches on the
-        // device's stream.  The env's episode step count is that of this step's observation until k_step_bank moves it on.
-        if (flags & RQ_ROLLOUT_AUTORESET)   // envs frozen by an earlier rollout start their next episode
-            RQ_HIP(rq::launch_thaw_frozen_bank(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, bank->hidden, bank->weights,
-                                               bank->table));
-        for (uint32_t t = 0; t < n_steps; ++t) {
-            RQ_HIP(rq::launch_observe(dev->stream, b, nc, noise, rng->seed, rng->epoch + t, nullptr, params->d, state->d, env->obs));
-            if (ref) RQ_HIP(rq::launch_track_shift(dev->stream, b, state->d, env->st, env->obs, trk));
-            if (rated)
-                RQ_HIP(rq::launch_actor_step_rate_bank(dev->stream, env->n, bank->images, bank->table, bank->intervals_dev, env->obs, env->ld,
-                                                       bank->hidden, bank->ld, env->act, env->ld, env->st.frozen, env->st.steps));
-            else
-                RQ_HIP(rq::launch_actor_step_bank(dev->stream, env->n, bank->images, bank->table, env->obs, env->ld, bank->hidden, bank->ld,
-                                                  env->act, env->ld, env->st.frozen));
-            RQ_HIP(rq::launch_step_bank(dev->stream, b, sc, params->d, state->d, env->act, env->st, flags, smp, rng->seed, bank->hidden,
-                                        bank->weights, bank->table));
-            if (traj) {
-                rq::TrajPtrs tt = tp; tt.t0 = tp.t0 + t;
-                RQ_HIP(rq::launch_record(dev->stream, b, env->obs, env->act, env->st, tt));
-            }
-        }
+            RQ_HIP(rq::launch_rollout_fused_bank(dev->stream, f.b, f.sc, f.nc, f.noise, f.smp, rng->seed, rng->epoch, n_steps, flags,
+                                                 params->d, state->d, bank->hidden, bank->weights, bank->images, bank->table, env->st,
+                                                 f.tp, span));
+        fused_span_end(dev, n_steps);
+    } else {
+        rc = rollout_chained(__func__, f, dev, env, params, state, rng, n_steps, flags, traj,
+            [&] { return rq::launch_thaw_frozen_bank(dev->stream, f.b, f.smp, rng->seed, params->d, state->d, env->st, bank->hidden,
+                                                     bank->weights, bank->table); },
+            [&] { return rated ? rq::launch_actor_step_rate_bank(dev->stream, env->n, bank->images, bank->table, bank->intervals_dev,
+                                                                 env->obs, env->ld, bank->hidden, bank->ld, env->act, env->ld,
+                                                                 env->st.frozen, env->st.steps)
+                               : rq::launch_actor_step_bank(dev->stream, env->n, bank->images, bank->table, env->obs, env->ld,
+                                                            bank->hidden, bank->ld, env->act, env->ld, env->st.frozen); },
+            [&] { return rq::launch_step_bank(dev->stream, f.b, f.sc, params->d, state->d, env->act, env->st, flags, f.smp, rng->seed,
+                                              bank->hidden, bank->weights, bank->table); });
+        if (rc) return rc;
     }
     rollout_end(state, rng, n_steps, traj);
     return RQ_OK;

@@ -38,6 +38,21 @@ int rollout_check(RolloutFrame& f, const rq_device* dev, const rq_env* env, cons
     return RQ_OK;
 }
 
+int rollout_check_reference(const char* who, const rq_device* dev, const rq_env* env, const rq_reference* ref) {
+    if (ref->dev != dev) return fail(RQ_ERR_SHAPE_MISMATCH, std::string(who) + ": reference lives on another device");
+    if (ref->rows < env->cfg.episode_step_limit)
+        return fail(RQ_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": reference has fewer rows than episode_step_limit: the table must cover an episode");
+    return RQ_OK;
+}
+
+int rollout_track(RolloutFrame& f, rq_env* env, const rq_reference* ref) {
+    if (!ref) return RQ_OK;
+    const int rc = env_track_stats(env, &f.trk.sq, &f.trk.steps); if (rc) return rc;
+    f.trk.ref = ref->d; f.trk.rows = ref->rows;
+    return RQ_OK;
+}
+
 int rollout_begin(RolloutFrame& f, rq_device* dev, rq_env* env, rq_state* state, uint32_t n_steps, uint32_t flags, rq_trajectory* traj) {
     obs_cache_drop_if(dev, env);
     if (n_steps) { const int rc = state_make_private(state, true); if (rc) return rc; }      // steps the state in place
@@ -57,6 +72,22 @@ void rollout_end(rq_state* state, rq_rng* rng, uint32_t n_steps, rq_trajectory* 
     if (n_steps) state->version = fresh_version();
 }
 
+int fused_span_begin(const char* who, rq_device* dev, const rq_env* env, uint32_t n_steps, unsigned long long** span) {
+    if (dev->k_timing && n_steps) {                   // one (in, out) record per wave = per workgroup of the fused kernel
+        const uint32_t waves = (env->n + 63u) / 64u;
+        const hipError_t e = dev->k_span.reserve(dev->stream, (size_t)waves * 5);
+        if (e != hipSuccess) return hip_failed(who, "dev->k_span.reserve(dev->stream, (size_t)waves * 5)", e);
+        dev->k_span_used = waves;
+    }
+    *span = dev->k_timing ? dev->k_span.get() : nullptr;
+    return RQ_OK;
+}
+
+void fused_span_end(rq_device* dev, uint32_t n_steps) {
+    dev->k_timed = dev->k_timing && n_steps > 0;
+    dev->k_fetched = false;
+}
+
 }  // namespace rqh
 
 using namespace rqh;
@@ -74,9 +105,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
     int rc = rollout_check(f, dev, env, params, state, rng, policy != nullptr, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(policy->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy lives on another device");
     if (ref) {          // a tracked rollout is refused here, before anything is enqueued
-        RQ_REQUIRE(ref->dev == dev, RQ_ERR_SHAPE_MISMATCH, "reference lives on another device");
-        RQ_REQUIRE(ref->rows >= env->cfg.episode_step_limit, RQ_ERR_INVALID_ARGUMENT,
-                   "reference has fewer rows than episode_step_limit: the table must cover an episode");
+        rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc;
         RQ_REQUIRE(policy->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
                    "tracked rollouts do not carry the SampleAndSquash stage");
     }
@@ -84,37 +113,28 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = policy_size(policy, env->n); if (rc) return rc;
     RQ_REQUIRE(policy->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy batch does not match the env");
-    rq::TrackPtrs trk{nullptr, 0, nullptr, nullptr};
-    if (ref) {
-        rc = env_track_stats(env, &trk.sq, &trk.steps); if (rc) return rc;
-        trk.ref = ref->d; trk.rows = ref->rows;
-    }
+    rc = rollout_track(f, env, ref); if (rc) return rc;
     rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
-    const rq::TrajPtrs& tp = f.tp;
+    const rq::TrajPtrs& tp = f.tp; const rq::TrackPtrs& trk = f.trk;
     const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
     const bool noise = f.noise;
     if (mode == RQ_ROLLOUT_FUSED) {
-        if (dev->k_timing && n_steps) {                   // one (in, out) record per wave = per workgroup of the fused kernel
-            const uint32_t waves = (env->n + 63u) / 64u;
-            RQ_HIP(dev->k_span.reserve(dev->stream, (size_t)waves * 5));
-            dev->k_span_used = waves;
-        }
+        unsigned long long* span = nullptr;
+        rc = fused_span_begin(__func__, dev, env, n_steps, &span); if (rc) return rc;
         if (interval > 1) {
             RQ_HIP(rq::launch_rollout_fused_rate(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
                                                  params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
-                                                 policy->precision, tp, trk, interval, dev->k_timing ? dev->k_span.get() : nullptr));
+                                                 policy->precision, tp, trk, interval, span));
         } else if (ref) {
             RQ_HIP(rq::launch_rollout_fused_track(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
                                                   params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
-                                                  policy->precision, tp, trk, dev->k_timing ? dev->k_span.get() : nullptr));
+                                                  policy->precision, tp, trk, span));
         } else {
             RQ_HIP(rq::launch_rollout_fused(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
                                             params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
-                                            policy->precision, sas_of(policy, rng->epoch, nullptr, env->offset), tp,
-                                            dev->k_timing ? dev->k_span.get() : nullptr));
+                                            policy->precision, sas_of(policy, rng->epoch, nullptr, env->offset), tp, span));
         }
-        dev->k_timed = dev->k_timing && n_steps > 0;
-        dev->k_fetched = false;
+        fused_span_end(dev, n_steps);
     } else {
         // one step = observe -> evaluate_step -> step (-> record) on the stream.  Without a recording the step kernel
         // also assembles the NEXT step's observation (round 3: two launches per step instead of three; the first

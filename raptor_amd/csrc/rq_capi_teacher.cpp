@@ -193,18 +193,22 @@ int bank_tiles(rq_teacher_bank* bank, rq_device* dev, uint64_t key, const uint32
     return RQ_OK;
 }
 
-// the bank's actions on obs [steps][22][ld] -> act [steps][4][ld] for the n envs of the tile list bank_tiles made (any kind, any precision)
-int bank_label(rq_teacher_bank* bank, rq_device* dev, uint32_t n, uint32_t n_tiles, uint32_t ld, uint32_t steps, const float* obs,
-               float* act) {
+// bank_label's launch alone (any kind, any precision), for callers that report a failure themselves (rollout_chained)
+hipError_t bank_label_launch(rq_teacher_bank* bank, rq_device* dev, uint32_t n, uint32_t n_tiles, uint32_t ld, uint32_t steps,
+                             const float* obs, float* act) {
     const float* images = bank->precision == RQ_POLICY_BF16_MFMA ? bank->images_bf16
                         : bank->precision == RQ_POLICY_F16X2_MFMA ? bank->images_f16x2 : bank->images_f32;
     if (bank->layers)
-        RQ_HIP(rq::launch_teacher_relabel_layers(dev->stream, bank->n_teachers, n, ld, steps, bank->in_dim, bank->n_hidden, bank->hp,
+        return rq::launch_teacher_relabel_layers(dev->stream, bank->n_teachers, n, ld, steps, bank->in_dim, bank->n_hidden, bank->hp,
                                                  bank->act, bank->out_act, bank->images_layers, bank->tiles, bank->tiles + bank->n_teachers + 1,
-                                                 obs, act));
-    else
-        RQ_HIP(rq::launch_teacher_relabel(dev->stream, n_tiles, ld, steps, bank->in_dim, bank->h1, bank->h2, bank->act,
-                                          bank->out_act, bank->precision, images, bank->tiles, bank->tiles + n_tiles, obs, act));
+                                                 obs, act);
+    return rq::launch_teacher_relabel(dev->stream, n_tiles, ld, steps, bank->in_dim, bank->h1, bank->h2, bank->act, bank->out_act,
+                                      bank->precision, images, bank->tiles, bank->tiles + n_tiles, obs, act);
+}
+// the bank's actions on obs [steps][22][ld] -> act [steps][4][ld] for the n envs of the tile list bank_tiles made (any kind, any precision)
+int bank_label(rq_teacher_bank* bank, rq_device* dev, uint32_t n, uint32_t n_tiles, uint32_t ld, uint32_t steps, const float* obs,
+               float* act) {
+    RQ_HIP(bank_label_launch(bank, dev, n, n_tiles, ld, steps, obs, act));
     return RQ_OK;
 }
 
@@ -304,18 +308,12 @@ RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* par
         float* sink_w = bank->sink;
         float* sink_h = bank->sink + RQ_POLICY_NUM_WEIGHTS;
         RQ_HIP(hipMemsetAsync(sink_w, 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float), dev->stream));
-        if (flags & RQ_ROLLOUT_AUTORESET)   // envs frozen by an earlier rollout start their next episode
-            RQ_HIP(rq::launch_thaw_frozen(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, sink_h, sink_w));
-        for (uint32_t t = 0; t < n_steps; ++t) {
-            RQ_HIP(rq::launch_observe(dev->stream, b, nc, noise, rng->seed, rng->epoch + t, nullptr, params->d, state->d, env->obs));
-            rc = bank_label(bank, dev, env->n, n_tiles, env->ld, 1, env->obs, env->act); if (rc) return rc;
-            RQ_HIP(rq::launch_step(dev->stream, b, sc, params->d, state->d, env->act, state->d, env->st, /*rollout=*/1, flags, smp,
-                                   rng->seed, sink_h, sink_w));
-            if (traj) {
-                rq::TrajPtrs tt = tp; tt.t0 = tp.t0 + t;
-                RQ_HIP(rq::launch_record(dev->stream, b, env->obs, env->act, env->st, tt));
-            }
-        }
+        rc = rollout_chained(__func__, f, dev, env, params, state, rng, n_steps, flags, traj,
+            [&] { return rq::launch_thaw_frozen(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, sink_h, sink_w); },
+            [&] { return bank_label_launch(bank, dev, env->n, n_tiles, env->ld, 1, env->obs, env->act); },
+            [&] { return rq::launch_step(dev->stream, b, sc, params->d, state->d, env->act, state->d, env->st, /*rollout=*/1, flags, smp,
+                                         rng->seed, sink_h, sink_w); });
+        if (rc) return rc;
     }
     rollout_end(state, rng, n_steps, traj);
     return RQ_OK;

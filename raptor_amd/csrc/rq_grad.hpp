@@ -11,7 +11,7 @@
 //                                 arithmetic, dL/da = a - y on live entries; + per wave the squared error and the live count
 //   k_policy_loss_reduce          partials in wave order, x 2 / M once; loss = SSE / M
 //   k_adam_repack                 one workgroup: Adam on the 2 084 master weights, then both operand images from a gather table
-// The same update for a bank of P policies, one per 64-env block (rq_grad_bank.hpp, compiled at the end of the unit):
+// The same update for a bank of P policies, one per 64-env block (rq_grad_bank.hpp):
 //   k_policy_grad_forward_state_bank   k_policy_grad_forward_state with the wave's image picked by block_policy[blockIdx.x]
 //   k_policy_loss_backward_bank        k_policy_loss_backward likewise, both images
 //   k_policy_loss_reduce_bank          per policy: its waves' partials in ascending wave order (a CSR list), x 2 / M_p; loss_p

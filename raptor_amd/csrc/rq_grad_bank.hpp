@@ -12,8 +12,7 @@
 // k_rollout_fused_bank chooses it: a wave computes what it computes for a policy of its own, bit for bit.  The reduction is the single
 // policy's, segmented: a policy's waves come from a CSR list (wave_offsets [P + 1] into wave_list [waves], ascending within a
 // policy), so its gradient and loss are those of a recording that holds its blocks only, in order.
-// Device code, compiled as part of rq_kernels.hip, at the END of the unit: the compiler numbers a unit's functions in the order it
-// meets them and the numbers appear in every label of a listing - the listings of the kernels above stay what they were.
+// Device code, compiled as part of rq_kernels.hip.
 #pragma once
 #include "rq_grad.hpp"
 

@@ -188,6 +188,48 @@ __global__ __launch_bounds__(kBlock, 2) void k_actor_step(uint32_t n, const floa
     mailbox_signal(mb);
 }
 
+// k_actor_step under a native interval above 1 (rq_policy_set_native_interval, launch_actor_step_rate): the same loads, the same
+// ACTOR::step, the same action stores - and the hidden state written back only for the rows at a native step.
+template <typename ACTOR>
+__global__ __launch_bounds__(kBlock, 2) void k_actor_step_rate(uint32_t n, const float* __restrict__ packed,
+                                                            const float* __restrict__ obs, uint32_t ld_obs,
+                                                            float* hidden, uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
+                                                            const uint8_t* __restrict__ frozen,
+                                                            const uint32_t* __restrict__ steps, uint32_t interval, uint32_t native,
+                                                            Mailbox mb) {
+    ACTOR actor;
+    actor.template load<kBlock / 64>(packed);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave_base = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64;
+    if (wave_base >= n) { mailbox_signal(mb); return; }          // wave-uniform
+    const uint32_t i0 = wave_base + lane;
+    const uint32_t i = i0 < n ? i0 : n - 1;
+    float x[22], hQ[4][4], a[4];
+    if (mb.rows_in != nullptr) {         // wave-uniform (kernel argument)
+#pragma unroll
+        for (int k = 0; k < 22; ++k) x[k] = mb.rows_in[(size_t)i * mb.in_stride + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
+    }
+    load_hidden_q(hidden, ld_h, wave_base, n, hQ);
+    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
+    const bool commit = (i0 < n) && fz == 0;
+    const bool at_native = steps != nullptr ? steps[i] % interval == 0 : native != 0;
+    const uint64_t hidden_mask = __builtin_amdgcn_ballot_w64(commit && at_native);
+    actor.step(x, hQ, a);
+    store_hidden_q(hidden, ld_h, wave_base, hidden_mask, hQ);
+    if (commit) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
+        if (mb.rows_out != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) mb.rows_out[(size_t)i * 4 + k] = a[k];
+        }
+    }
+    mailbox_signal(mb);
+}
+
 // The streaming form for the large batches (from 262 144 envs): a wave works through groups_per_wave consecutive 64-env groups,
 // the next group's inputs in flight while this one is on the matrix cores - the 18 KB operand image per wave is amortised and
 // memory and matrix phases overlap (the waves of a launch move in lock-step, so without it they alternate).  Round 4 took the
@@ -1009,6 +1051,20 @@ hipError_t launch_actor_step(hipStream_t s, uint32_t n, const float* packed, con
     return RQ_KLAUNCH_STATUS();
 }
 
+hipError_t launch_actor_step_rate(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
+                                  float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
+                                  int precision, const uint32_t* steps, uint32_t interval, uint32_t native, Mailbox mb) {
+    if (n == 0) return hipSuccess;
+    const unsigned grid = grid_for((n + 63) / 64 * 64, kBlock);
+#define RQ_LAUNCH_ACTOR(ACT) RQ_KLAUNCH(k_actor_step_rate<ACT>, grid, kBlock, s, n, packed, obs, ld_obs, hidden, ld_h, act, ld_act, frozen, \
+                                        steps, interval, native, mb)
+    if (precision == RQ_POLICY_F16X2_MFMA)     RQ_LAUNCH_ACTOR(ActorF16X2);
+    else if (precision == RQ_POLICY_BF16_MFMA) RQ_LAUNCH_ACTOR(ActorBF16);
+    else                                       RQ_LAUNCH_ACTOR(ActorF32Lean);   // launch_actor_step's build: the same bits
+#undef RQ_LAUNCH_ACTOR
+    return RQ_KLAUNCH_STATUS();
+}
+
 hipError_t launch_actor_sequence(hipStream_t s, uint32_t n, uint32_t steps, const float* packed, const float* obs,
                                  uint32_t stride, float* hidden, uint32_t ld_h, float* act, int precision) {
     if (n == 0 || steps == 0) return hipSuccess;
@@ -1098,6 +1154,22 @@ hipError_t launch_rollout_fused_track(hipStream_t s, Batch b, StepCfg c, NoiseCf
     // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
     if (b.n > 65536u) launch_fused_track_actor<ActorF32Lean>(s, a, noise, ar);
     else              launch_fused_track_actor<ActorF32>(s, a, noise, ar);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                     const float* params, float* state, float* hidden, const float* weights,
+                                     const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
+                                     uint32_t interval, unsigned long long* span) {
+    if (b.n == 0 || n_steps == 0) return hipSuccess;
+    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, packed, st, traj, SasArgs{}, span, trk, interval};
+    if (precision == RQ_POLICY_F16X2_MFMA || precision == RQ_POLICY_BF16_MFMA)
+        return launch_rollout_fused_rate_16bit(s, a, noise, ar, precision);
+    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
+    if (b.n > 65536u) launch_fused_rate_actor<ActorF32Lean>(s, a, noise, ar);
+    else              launch_fused_rate_actor<ActorF32>(s, a, noise, ar);
     return hipGetLastError();
 }
 
@@ -1204,102 +1276,18 @@ hipError_t launch_track_shift(hipStream_t s, Batch b, const float* state, StatsP
     return RQ_KLAUNCH_STATUS();
 }
 
-}  // namespace rq
-
-// the learner's kernels (forward with saved state, reverse pass, reduction): their own file, compiled in this unit
-#include "rq_grad.hpp"
-
-namespace rq {
-
-// ------------------------------------------------------------------ native interval above 1 (rq_policy_set_native_interval) ---
-// Everything below serves policies whose hidden state moves on every native_interval-th step only, and stands at the END of this
-// unit (behind the learner's kernels too) on purpose: the compiler numbers a unit's functions in the order it meets them, the numbers appear in every label of a listing,
-// and the listings of the kernels above are to stay what they were before these existed.
-// k_actor_step under a native interval above 1 (launch_actor_step_rate): the same loads, the same ACTOR::step, the same action
-// stores - and the hidden state written back only for the rows at a native step.  A kernel of its own: k_actor_step is compiled from what it
-// was compiled from before.
-template <typename ACTOR>
-__global__ __launch_bounds__(kBlock, 2) void k_actor_step_rate(uint32_t n, const float* __restrict__ packed,
-                                                            const float* __restrict__ obs, uint32_t ld_obs,
-                                                            float* hidden, uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
-                                                            const uint8_t* __restrict__ frozen,
-                                                            const uint32_t* __restrict__ steps, uint32_t interval, uint32_t native,
-                                                            Mailbox mb) {
-    ACTOR actor;
-    actor.template load<kBlock / 64>(packed);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave_base = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64;
-    if (wave_base >= n) { mailbox_signal(mb); return; }          // wave-uniform
-    const uint32_t i0 = wave_base + lane;
-    const uint32_t i = i0 < n ? i0 : n - 1;
-    float x[22], hQ[4][4], a[4];
-    if (mb.rows_in != nullptr) {         // wave-uniform (kernel argument)
-#pragma unroll
-        for (int k = 0; k < 22; ++k) x[k] = mb.rows_in[(size_t)i * mb.in_stride + k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
-    }
-    load_hidden_q(hidden, ld_h, wave_base, n, hQ);
-    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
-    const bool commit = (i0 < n) && fz == 0;
-    const bool at_native = steps != nullptr ? steps[i] % interval == 0 : native != 0;
-    const uint64_t hidden_mask = __builtin_amdgcn_ballot_w64(commit && at_native);
-    actor.step(x, hQ, a);
-    store_hidden_q(hidden, ld_h, wave_base, hidden_mask, hQ);
-    if (commit) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
-        if (mb.rows_out != nullptr) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) mb.rows_out[(size_t)i * 4 + k] = a[k];
-        }
-    }
-    mailbox_signal(mb);
-}
-
-hipError_t launch_actor_step_rate(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
-                                  float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
-                                  int precision, const uint32_t* steps, uint32_t interval, uint32_t native, Mailbox mb) {
-    if (n == 0) return hipSuccess;
-    const unsigned grid = grid_for((n + 63) / 64 * 64, kBlock);
-#define RQ_LAUNCH_ACTOR(ACT) RQ_KLAUNCH(k_actor_step_rate<ACT>, grid, kBlock, s, n, packed, obs, ld_obs, hidden, ld_h, act, ld_act, frozen, \
-                                        steps, interval, native, mb)
-    if (precision == RQ_POLICY_F16X2_MFMA)     RQ_LAUNCH_ACTOR(ActorF16X2);
-    else if (precision == RQ_POLICY_BF16_MFMA) RQ_LAUNCH_ACTOR(ActorBF16);
-    else                                       RQ_LAUNCH_ACTOR(ActorF32Lean);   // launch_actor_step's build: the same bits
-#undef RQ_LAUNCH_ACTOR
-    return RQ_KLAUNCH_STATUS();
-}
-
-hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                     const float* params, float* state, float* hidden, const float* weights,
-                                     const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
-                                     uint32_t interval, unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, packed, st, traj, SasArgs{}, span, trk, interval};
-    if (precision == RQ_POLICY_F16X2_MFMA || precision == RQ_POLICY_BF16_MFMA)
-        return launch_rollout_fused_rate_16bit(s, a, noise, ar, precision);
-    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
-    const bool rec = traj.obs != nullptr, track = trk.ref != nullptr;
-    if (b.n > 65536u) launch_fused_rate_actor<ActorF32Lean>(s, a, noise, ar, rec, track);
-    else              launch_fused_rate_actor<ActorF32>(s, a, noise, ar, rec, track);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ policy bank (rq_rollout_policies) ---
+// ------------------------------------------------------------------ policy bank (rq_rollout_policies[_track]) ---
 // A bank of student policies, one per WAVE: the 64-env block g of a batch is flown by policy block_policy[g], whose operand image is
-// images + block_policy[g] * image_floats.  The weights are wave-uniform MFMA A operands, so choosing the image per wave is all a
-// bank needs: everything below is an existing kernel with the image (or, for the policy-state reset, the weight block) picked from
-// that table, and calls the existing __device__ functions - no new arithmetic, which is what makes a bank rollout equal, bit for
-// bit, the single-policy rollouts of its 64-env slices.  Behind everything else of this unit for the reason given above.
+// images + block_policy[g] * image_floats, at native interval policy_interval[block_policy[g]].  The weights are wave-uniform MFMA A
+// operands, so choosing the image per wave is all a bank needs: everything below is an existing kernel with the image (or, for the
+// policy-state reset, the weight block) picked from that table, and calls the existing __device__ functions - no new arithmetic,
+// which is what makes a bank rollout equal, bit for bit, the single-policy rollouts of its 64-env slices.
 
+// ---- the bank's fused kernels
 // k_rollout_fused with the image chosen per workgroup (one workgroup = one wave = one 64-env block in both builds): the id is read
 // with a scalar load (a kernel argument indexed by blockIdx: provably wave-uniform, so `packed` is a scalar base for the image's
 // loads as it is in k_rollout_fused) ahead of the prologue's env loads, which hide its latency.  No SampleAndSquash stage, no
-// tracking, native interval 1 (a tracked bank, or one with an interval above 1: k_rollout_fused_bank_rate, last in this unit).
+// tracking, native interval 1 (a tracked bank, or one with an interval above 1: k_rollout_fused_bank_rate).
 template <bool NOISE, bool AUTORESET, bool RECORD, typename ACTOR>
 __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_bank(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
                                                                uint64_t seed, uint32_t epoch0, uint32_t n_steps,
@@ -1319,6 +1307,79 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
 #include "rq_rollout_body.inc"
 }
 
+// k_rollout_fused_rate with the image and the interval chosen per workgroup: both table reads are scalar loads indexed by blockIdx
+// (the second by the first's result), issued ahead of the prologue's env loads as k_rollout_fused_bank's one is.  A wave whose policy
+// has interval 1 runs the RATE text with interval == 1: phase stays 0, every step is native, hold_carry holds nothing - the bits of
+// the plain kernel.  policy_interval [P], every entry 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL (the host refuses anything else: the phase
+// is a remainder by it).
+template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_bank_rate(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ images,
+                                                               const uint32_t* __restrict__ block_policy,
+                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
+                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool RATE = true, SAS = false;
+    constexpr SasArgs sas{};
+    const uint32_t policy = block_policy[blockIdx.x];
+    const uint32_t interval = policy_interval[policy];
+    const float* __restrict__ packed = images + (size_t)policy * image_floats;
+#include "rq_rollout_body.inc"
+}
+
+template <typename ACTOR>
+static inline void launch_fused_bank_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
+                                           bool noise, bool ar) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC) {
+        hipLaunchKernelGGL((k_rollout_fused_bank<NZ(), AR(), RC(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
+                           (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.span);
+    }, noise, ar, a.traj.obs != nullptr);
+}
+
+template <typename ACTOR>
+static inline void launch_fused_bank_rate_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
+                                                const uint32_t* policy_interval, bool noise, bool ar) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
+        hipLaunchKernelGGL((k_rollout_fused_bank_rate<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
+                           policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.trk, a.span);
+    }, noise, ar, a.traj.obs != nullptr, a.trk.ref != nullptr);
+}
+
+hipError_t launch_rollout_fused_bank(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                     const float* params, float* state, float* hidden, const float* weights,
+                                     const float* images, const uint32_t* block_policy, StatsPtrs st, TrajPtrs traj,
+                                     unsigned long long* span) {
+    if (b.n == 0 || n_steps == 0) return hipSuccess;
+    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span};
+    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
+    if (b.n > 65536u) launch_fused_bank_actor<ActorF32Lean>(s, a, images, block_policy, noise, ar);
+    else              launch_fused_bank_actor<ActorF32>(s, a, images, block_policy, noise, ar);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                          uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                          const float* params, float* state, float* hidden, const float* weights,
+                                          const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
+                                          StatsPtrs st, TrajPtrs traj, TrackPtrs trk, unsigned long long* span) {
+    if (b.n == 0 || n_steps == 0) return hipSuccess;
+    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span, trk};
+    if (b.n > 65536u) launch_fused_bank_rate_actor<ActorF32Lean>(s, a, images, block_policy, policy_interval, noise, ar);
+    else              launch_fused_bank_rate_actor<ActorF32>(s, a, images, block_policy, policy_interval, noise, ar);
+    return hipGetLastError();
+}
+
+// ---- the bank's chained actor step
 // k_actor_step with the image of the wave's block (block = wave_base / 64); the chained bank rollout's actor: no host rows, no
 // SampleAndSquash stage, no speculation.  The wave index is made a scalar first: the table read is then a scalar load too.
 template <typename ACTOR>
@@ -1348,155 +1409,6 @@ __global__ __launch_bounds__(kBlock, 2) void k_actor_step_bank(uint32_t n, const
 #pragma unroll
         for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
     }
-}
-
-// k_step<true> whose policy-state reset (auto-reset at an episode end: h <- initial_hidden_state) reads the weight block of the env's
-// own policy: weights [P][RQ_POLICY_NUM_WEIGHTS], checkpoint order
-__global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const float* __restrict__ params, float* state,
-                                                      float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
-                                                      uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
-                                                      const uint32_t* __restrict__ block_policy) {
-    const uint32_t i = env_index();
-    if (i < b.n)
-        step_env<true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
-                       weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{});
-}
-
-// k_thaw_frozen likewise: an env left frozen starts its next episode with ITS policy's initial state
-__global__ __launch_bounds__(kBlock) void k_thaw_frozen_bank(Batch b, SampleCfg c, uint64_t seed,
-                                                             const float* __restrict__ params, float* __restrict__ state,
-                                                             StatsPtrs st, float* __restrict__ hidden,
-                                                             const float* __restrict__ weights,
-                                                             const uint32_t* __restrict__ block_policy) {
-    const uint32_t i = env_index();
-    if (i >= b.n || !st.frozen[i]) return;
-    const size_t ld = b.ld;
-    const uint32_t ep = st.episode[i];
-    const float* w = weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS;
-    float s[17], la[4], f[6];
-    sample_state(c, seed, ep, b.env_offset + i, field(params, RQ_P_MASS, ld)[i], field(params, RQ_P_HOVER_RPM, ld)[i],
-                 field(params, RQ_P_ROTOR_POS, ld)[i], field(params, (RQ_P_ROTOR_POS + 1), ld)[i], s, la, f);
-#pragma unroll
-    for (int k = 0; k < 17; ++k) field(state, k, ld)[i] = s[k];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) field(state, (RQ_S_LAST_ACTION + k), ld)[i] = la[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) field(state, (RQ_S_FORCE + k), ld)[i] = f[k];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) field(hidden, j, ld)[i] = w[OFF_H0 + j];
-    st.episode[i] = ep + 1;
-    st.frozen[i] = 0;
-}
-
-// rq_policy_bank_reset: hidden [16][ld] <- the initial hidden state of every column's policy (columns n .. ld - 1 belong to the last block)
-__global__ __launch_bounds__(kBlock) void k_bank_initial_hidden(uint32_t ld, float* __restrict__ hidden,
-                                                                const float* __restrict__ weights,
-                                                                const uint32_t* __restrict__ block_policy) {
-    const uint32_t i = env_index();
-    if (i >= ld) return;
-    const float* w = weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) field(hidden, j, ld)[i] = w[OFF_H0 + j];
-}
-
-template <bool NZ, bool AR, bool RC, typename ACTOR>
-static inline void launch_fused_bank_instance(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy) {
-    const unsigned g = (a.b.n + kFusedBlock - 1) / kFusedBlock;
-    hipLaunchKernelGGL((k_rollout_fused_bank<NZ, AR, RC, ACTOR>), dim3(g), dim3(kFusedBlock), 0, s,
-                       a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
-                       (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.span);
-}
-template <typename ACTOR>
-static inline void launch_fused_bank_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
-                                           bool noise, bool ar) {
-    const bool rec = a.traj.obs != nullptr;
-#define RQ_FUSED_RC(NZ, AR) do { if (rec) launch_fused_bank_instance<NZ, AR, true, ACTOR>(s, a, images, block_policy); \
-                                 else     launch_fused_bank_instance<NZ, AR, false, ACTOR>(s, a, images, block_policy); } while (0)
-    if (noise) { if (ar) RQ_FUSED_RC(true, true); else RQ_FUSED_RC(true, false); }
-    else       { if (ar) RQ_FUSED_RC(false, true); else RQ_FUSED_RC(false, false); }
-#undef RQ_FUSED_RC
-}
-
-hipError_t launch_rollout_fused_bank(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                     const float* params, float* state, float* hidden, const float* weights,
-                                     const float* images, const uint32_t* block_policy, StatsPtrs st, TrajPtrs traj,
-                                     unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span};
-    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
-    if (b.n > 65536u) launch_fused_bank_actor<ActorF32Lean>(s, a, images, block_policy, noise, ar);
-    else              launch_fused_bank_actor<ActorF32>(s, a, images, block_policy, noise, ar);
-    return hipGetLastError();
-}
-
-hipError_t launch_actor_step_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy, const float* obs,
-                                  uint32_t ld_obs, float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen) {
-    if (n == 0) return hipSuccess;
-    // launch_actor_step's build for fp32 policies (one 64-env group per wave): the same bits
-    k_actor_step_bank<ActorF32Lean><<<grid_for((n + 63) / 64 * 64, kBlock), kBlock, 0, s>>>(
-        n, images, block_policy, (uint32_t)RQ_PACKED_FLOATS, obs, ld_obs, hidden, ld_h, act, ld_act, frozen);
-    return hipGetLastError();
-}
-
-hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
-                            uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
-                            const uint32_t* block_policy) {
-    if (b.n == 0) return hipSuccess;
-    k_step_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, params, state, action, st, flags, sc, seed, hidden, weights, block_policy);
-    return hipGetLastError();
-}
-
-hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
-                                   StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy) {
-    if (b.n == 0) return hipSuccess;
-    k_thaw_frozen_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, seed, params, state, st, hidden, weights, block_policy);
-    return hipGetLastError();
-}
-
-hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden, const float* weights, const uint32_t* block_policy) {
-    if (ld == 0) return hipSuccess;
-    k_bank_initial_hidden<<<grid_for(ld, kBlock), kBlock, 0, s>>>(ld, hidden, weights, block_policy);
-    return hipGetLastError();
-}
-
-}  // namespace rq
-
-// the population learner (the distillation update for a policy bank): its own file, behind everything else of this unit
-#include "rq_grad_bank.hpp"
-
-namespace rq {
-
-// ------------------------------------------------------------------ policy bank at a deployment rate, on a moving setpoint ---
-// (rq_policy_bank_set_native_interval, rq_rollout_policies_track.)  The bank's kernels above fly every policy at native interval 1 and
-// the origin; these fly policy p at policy_interval[p] and, with trk.ref, on the moving setpoint.  Still no new arithmetic: the RATE
-// text of rq_rollout_body.inc and k_actor_step_rate's rule, with the image AND the interval those of the wave's block.  Behind the
-// population learner, last in the unit, for the reason given above: the listings of everything before stay what they were.
-
-// k_rollout_fused_rate with the image and the interval chosen per workgroup: both table reads are scalar loads indexed by blockIdx
-// (the second by the first's result), issued ahead of the prologue's env loads as k_rollout_fused_bank's one is.  A wave whose policy
-// has interval 1 runs the RATE text with interval == 1: phase stays 0, every step is native, hold_carry holds nothing - the bits of
-// the plain kernel.  policy_interval [P], every entry 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL (the host refuses anything else: the phase
-// is a remainder by it).
-template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
-__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_bank_rate(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
-                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
-                                                               const float* __restrict__ params,
-                                                               float* __restrict__ state,
-                                                               float* __restrict__ hidden,
-                                                               const float* __restrict__ w,
-                                                               const float* __restrict__ images,
-                                                               const uint32_t* __restrict__ block_policy,
-                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
-                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk,
-                                                               unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false;
-    constexpr SasArgs sas{};
-    const uint32_t policy = block_policy[blockIdx.x];
-    const uint32_t interval = policy_interval[policy];
-    const float* __restrict__ packed = images + (size_t)policy * image_floats;
-#include "rq_rollout_body.inc"
 }
 
 // k_actor_step_bank under the policies' native intervals (the chained bank rollout's actor when any interval is above 1):
@@ -1535,34 +1447,12 @@ __global__ __launch_bounds__(kBlock, 2) void k_actor_step_rate_bank(uint32_t n, 
     }
 }
 
-// the instantiation for (noise, auto-reset, recording, tracking) of one actor build: one run-time switch per call
-template <typename ACTOR, bool NZ, bool AR, bool RC, bool TK>
-static inline void launch_fused_bank_rate_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
-                                                const uint32_t* policy_interval) {
-    const unsigned g = (a.b.n + kFusedBlock - 1) / kFusedBlock;
-    hipLaunchKernelGGL((k_rollout_fused_bank_rate<NZ, AR, RC, TK, ACTOR>), dim3(g), dim3(kFusedBlock), 0, s,
-                       a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
-                       policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.trk, a.span);
-}
-template <typename ACTOR, bool... DONE, typename... REST>
-static inline void launch_fused_bank_rate_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
-                                                const uint32_t* policy_interval, bool next, REST... rest) {
-    if (next) launch_fused_bank_rate_actor<ACTOR, DONE..., true>(s, a, images, block_policy, policy_interval, rest...);
-    else      launch_fused_bank_rate_actor<ACTOR, DONE..., false>(s, a, images, block_policy, policy_interval, rest...);
-}
-
-hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                          uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                          const float* params, float* state, float* hidden, const float* weights,
-                                          const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
-                                          StatsPtrs st, TrajPtrs traj, TrackPtrs trk, unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span, trk};
-    // the two builds of launch_rollout_fused_bank: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
-    const bool rec = traj.obs != nullptr, track = trk.ref != nullptr;
-    if (b.n > 65536u) launch_fused_bank_rate_actor<ActorF32Lean>(s, a, images, block_policy, policy_interval, noise, ar, rec, track);
-    else              launch_fused_bank_rate_actor<ActorF32>(s, a, images, block_policy, policy_interval, noise, ar, rec, track);
+// launch_actor_step's build for fp32 policies (one 64-env group per wave): the same bits
+hipError_t launch_actor_step_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy, const float* obs,
+                                  uint32_t ld_obs, float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen) {
+    if (n == 0) return hipSuccess;
+    k_actor_step_bank<ActorF32Lean><<<grid_for((n + 63) / 64 * 64, kBlock), kBlock, 0, s>>>(
+        n, images, block_policy, (uint32_t)RQ_PACKED_FLOATS, obs, ld_obs, hidden, ld_h, act, ld_act, frozen);
     return hipGetLastError();
 }
 
@@ -1570,10 +1460,85 @@ hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* i
                                        const uint32_t* policy_interval, const float* obs, uint32_t ld_obs, float* hidden, uint32_t ld_h,
                                        float* act, uint32_t ld_act, const uint8_t* frozen, const uint32_t* steps) {
     if (n == 0) return hipSuccess;
-    // launch_actor_step_bank's build (one 64-env group per wave): the same bits
     k_actor_step_rate_bank<ActorF32Lean><<<grid_for((n + 63) / 64 * 64, kBlock), kBlock, 0, s>>>(
         n, images, block_policy, policy_interval, (uint32_t)RQ_PACKED_FLOATS, obs, ld_obs, hidden, ld_h, act, ld_act, frozen, steps);
     return hipGetLastError();
 }
 
+// ---- the bank's env step, thaw and initial hidden state
+// k_step<true> whose policy-state reset (auto-reset at an episode end: h <- initial_hidden_state) reads the weight block of the env's
+// own policy: weights [P][RQ_POLICY_NUM_WEIGHTS], checkpoint order
+__global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                      float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                      uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                      const uint32_t* __restrict__ block_policy) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                       weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{});
+}
+
+hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
+                            uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
+                            const uint32_t* block_policy) {
+    if (b.n == 0) return hipSuccess;
+    k_step_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, params, state, action, st, flags, sc, seed, hidden, weights, block_policy);
+    return hipGetLastError();
+}
+
+// k_thaw_frozen likewise: an env left frozen starts its next episode with ITS policy's initial state
+__global__ __launch_bounds__(kBlock) void k_thaw_frozen_bank(Batch b, SampleCfg c, uint64_t seed,
+                                                             const float* __restrict__ params, float* __restrict__ state,
+                                                             StatsPtrs st, float* __restrict__ hidden,
+                                                             const float* __restrict__ weights,
+                                                             const uint32_t* __restrict__ block_policy) {
+    const uint32_t i = env_index();
+    if (i >= b.n || !st.frozen[i]) return;
+    const size_t ld = b.ld;
+    const uint32_t ep = st.episode[i];
+    const float* w = weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS;
+    float s[17], la[4], f[6];
+    sample_state(c, seed, ep, b.env_offset + i, field(params, RQ_P_MASS, ld)[i], field(params, RQ_P_HOVER_RPM, ld)[i],
+                 field(params, RQ_P_ROTOR_POS, ld)[i], field(params, (RQ_P_ROTOR_POS + 1), ld)[i], s, la, f);
+#pragma unroll
+    for (int k = 0; k < 17; ++k) field(state, k, ld)[i] = s[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) field(state, (RQ_S_LAST_ACTION + k), ld)[i] = la[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) field(state, (RQ_S_FORCE + k), ld)[i] = f[k];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) field(hidden, j, ld)[i] = w[OFF_H0 + j];
+    st.episode[i] = ep + 1;
+    st.frozen[i] = 0;
+}
+
+hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
+                                   StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy) {
+    if (b.n == 0) return hipSuccess;
+    k_thaw_frozen_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, seed, params, state, st, hidden, weights, block_policy);
+    return hipGetLastError();
+}
+
+// rq_policy_bank_reset: hidden [16][ld] <- the initial hidden state of every column's policy (columns n .. ld - 1 belong to the last block)
+__global__ __launch_bounds__(kBlock) void k_bank_initial_hidden(uint32_t ld, float* __restrict__ hidden,
+                                                                const float* __restrict__ weights,
+                                                                const uint32_t* __restrict__ block_policy) {
+    const uint32_t i = env_index();
+    if (i >= ld) return;
+    const float* w = weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) field(hidden, j, ld)[i] = w[OFF_H0 + j];
+}
+
+hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden, const float* weights, const uint32_t* block_policy) {
+    if (ld == 0) return hipSuccess;
+    k_bank_initial_hidden<<<grid_for(ld, kBlock), kBlock, 0, s>>>(ld, hidden, weights, block_policy);
+    return hipGetLastError();
+}
+
 }  // namespace rq
+
+// the learner's kernels (forward with saved state, reverse pass, reduction) and the population learner (the distillation update for
+// a policy bank): their own files, compiled in this unit
+#include "rq_grad.hpp"
+#include "rq_grad_bank.hpp"

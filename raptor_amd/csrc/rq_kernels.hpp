@@ -282,35 +282,36 @@ hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg
                                      const float* params, float* state, float* hidden, const float* weights,
                                      const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
                                      uint32_t interval, unsigned long long* span = nullptr);
-// ---- policy bank (rq_rollout_policies): P fp32 operand images [P][RQ_PACKED_FLOATS], raw weights [P][RQ_POLICY_NUM_WEIGHTS] and
-// block_policy [ceil(n / 64)]: the policy of each 64-env block.  The fused kernel with the image chosen per wave; its chained
-// counterpart's actor step, env step and thaw (the latter two reset a policy state to the initial state of the env's own policy);
-// hidden [16][ld] <- every column's initial state.  Plain launches: none of them appends to a GraphSink.
+// ---- policy bank (rq_rollout_policies, rq_rollout_policies_track): P fp32 operand images [P][RQ_PACKED_FLOATS], raw weights
+// [P][RQ_POLICY_NUM_WEIGHTS], block_policy [ceil(n / 64)]: the policy of each 64-env block, and policy_interval [P]: every entry
+// 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL (rq_policy_bank_set_native_interval).  Plain launches: none of them appends to a GraphSink.
+// The fused kernel with the image chosen per wave; _rate: k_rollout_fused_rate with image and interval chosen per wave, on a moving
+// setpoint when trk.ref != nullptr.
 hipError_t launch_rollout_fused_bank(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
                                      uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
                                      const float* params, float* state, float* hidden, const float* weights,
                                      const float* images, const uint32_t* block_policy, StatsPtrs st, TrajPtrs traj,
                                      unsigned long long* span = nullptr);
+hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                          uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                          const float* params, float* state, float* hidden, const float* weights,
+                                          const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
+                                          StatsPtrs st, TrajPtrs traj, TrackPtrs trk, unsigned long long* span = nullptr);
+// The chained counterpart's actor step; _rate stores the hidden state of the rows at a native step only (steps: the envs' episode step
+// counts, as launch_actor_step_rate takes them).
 hipError_t launch_actor_step_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy, const float* obs,
                                   uint32_t ld_obs, float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen);
+hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy,
+                                       const uint32_t* policy_interval, const float* obs, uint32_t ld_obs, float* hidden, uint32_t ld_h,
+                                       float* act, uint32_t ld_act, const uint8_t* frozen, const uint32_t* steps);
+// Env step and thaw (both reset a policy state to the initial state of the env's own policy); hidden [16][ld] <- every column's
+// initial state.
 hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
                             uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
                             const uint32_t* block_policy);
 hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
                                    StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy);
 hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden, const float* weights, const uint32_t* block_policy);
-// The bank at its policies' native intervals and / or on a moving setpoint (rq_policy_bank_set_native_interval,
-// rq_rollout_policies_track): policy_interval [P], every entry 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL; trk.ref == nullptr: untracked.
-// The fused kernel is k_rollout_fused_rate with image and interval chosen per wave; the chained actor stores the hidden state of the
-// rows at a native step only (steps: the envs' episode step counts, as launch_actor_step_rate takes them).
-hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                          uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                          const float* params, float* state, float* hidden, const float* weights,
-                                          const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
-                                          StatsPtrs st, TrajPtrs traj, TrackPtrs trk, unsigned long long* span = nullptr);
-hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy,
-                                       const uint32_t* policy_interval, const float* obs, uint32_t ld_obs, float* hidden, uint32_t ld_h,
-                                       float* act, uint32_t ld_act, const uint8_t* frozen, const uint32_t* steps);
 // chained mode of a tracked rollout, between the observation's assembly (k_observe, or the k_step before) and the actor: the row of
 // each env's episode step count comes off obs [RQ_OBSERVATION_DIM][ld] in place, and the envs that are not frozen add this step's
 // tracking error - the fused kernel's arithmetic (rq_device_math.hpp track_*).  Appends a graph node under a GraphSink.

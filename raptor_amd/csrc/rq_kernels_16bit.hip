@@ -32,12 +32,10 @@ hipError_t launch_rollout_fused_track_16bit(hipStream_t s, const FusedArgs& a, b
     return hipGetLastError();
 }
 
-// the RATE variant (rq_policy_set_native_interval above 1; tracked or not, no SampleAndSquash stage).  Last in the unit: the labels of
-// the listings above keep their numbers.
+// the RATE variant (rq_policy_set_native_interval above 1; tracked or not, no SampleAndSquash stage)
 hipError_t launch_rollout_fused_rate_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision) {
-    const bool rec = a.traj.obs != nullptr, track = a.trk.ref != nullptr;
-    if (precision == RQ_POLICY_F16X2_MFMA) launch_fused_rate_actor<ActorF16X2>(s, a, noise, ar, rec, track);
-    else                                   launch_fused_rate_actor<ActorBF16>(s, a, noise, ar, rec, track);
+    if (precision == RQ_POLICY_F16X2_MFMA) launch_fused_rate_actor<ActorF16X2>(s, a, noise, ar);
+    else                                   launch_fused_rate_actor<ActorBF16>(s, a, noise, ar);
     return hipGetLastError();
 }
 

@@ -12,7 +12,7 @@
 //   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory; the distillation update (loss, Adam, repack),
 //                        for one policy and for a policy bank
 //   rq_memory.hpp        rq::DeviceBuffer / rq::PinnedBuffer: every object below owns its device and pinned memory through them
-// rollout_check / rollout_begin / rollout_end (rq_capi_rollout.cpp) are the frame rq_rollout* and rq_rollout_teachers share.
+// rollout_check / rollout_begin / rollout_end (rq_capi_rollout.cpp) are the frame rq_rollout*, rq_rollout_policies* and rq_rollout_teachers share.
 // Helpers live in namespace rqh (each .cpp says `using namespace rqh;`); nothing here is visible outside libraptor_quad.so.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -457,18 +457,57 @@ int bank_wave_lists(rq_policy_bank* bank);        // `waves` for the current tab
 int require_bank_native_rate(const rq_policy_bank* bank, const char* what);
 
 // ---- rq_capi_rollout.cpp ----
-// What a rollout of either kind (a policy's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope: the checks
-// both make, and where a recording goes.  rollout_begin, inside it and after what is the caller's own (policy sizing; tile list and
-// sink): the observation cache dropped, the state private, the env's configuration as the kernels take it, the `done` rows preset.
-// rollout_end: the noise epoch, the recording's length and the state's version move on.
+// What a rollout of any kind (a policy's, a policy bank's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope:
+// the checks all make, and where a recording goes; rollout_check_reference, behind the caller's device check: a tracked rollout's
+// table (`who`: the caller's name, as its own messages begin).  rollout_track, inside the scope: the tracked rollout's pointers (a
+// null reference: none).  rollout_begin, after what is the caller's own (policy sizing; tile list and sink): the observation cache
+// dropped, the state private, the env's configuration as the kernels take it, the `done` rows preset.  rollout_end: the noise epoch,
+// the recording's length and the state's version move on.
 struct RolloutFrame {
     rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
+    rq::TrackPtrs trk{nullptr, 0, nullptr, nullptr};      // ref != nullptr: a tracked rollout
     rq::Batch b; rq::StepCfg sc; rq::NoiseCfg nc; rq::SampleCfg smp; bool noise;
 };
 int rollout_check(RolloutFrame& f, const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,
                   bool actor, uint32_t n_steps, int mode, uint32_t flags, const rq_trajectory* traj);
+int rollout_check_reference(const char* who, const rq_device* dev, const rq_env* env, const rq_reference* ref);
+int rollout_track(RolloutFrame& f, rq_env* env, const rq_reference* ref);
 int rollout_begin(RolloutFrame& f, rq_device* dev, rq_env* env, rq_state* state, uint32_t n_steps, uint32_t flags, rq_trajectory* traj);
 void rollout_end(rq_state* state, rq_rng* rng, uint32_t n_steps, rq_trajectory* traj);
+// a failed HIP call of a shared piece, reported as the caller's own RQ_HIP would: `who` is the caller's name, `what` the call
+inline int hip_failed(const char* who, const char* what, hipError_t e) {
+    return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string(who) + ": " + what + " -> " + hipGetErrorString(e));
+}
+// Around a fused launch: under rq_device_set_rollout_timing the span buffer sized for the env's waves (*span: what the launcher takes,
+// null when off), and behind the launch what rq_device_last_rollout_ms goes by.
+int fused_span_begin(const char* who, rq_device* dev, const rq_env* env, uint32_t n_steps, unsigned long long** span);
+void fused_span_end(rq_device* dev, uint32_t n_steps);
+
+// The plain chained rollout (no graph, nothing folded): thaw under auto-reset, then per step observe -> the setpoint taken off the
+// observation if tracked -> actor -> step -> record if recording, plain launches on the device's stream.  thaw / actor / step: the
+// caller's launches, each -> hipError_t; who: the caller's name, which a failure's message begins with as the caller's own would;
+// the env's episode step count is that of this step's observation until `step` moves it on.
+template <typename Thaw, typename Actor, typename Step>
+int rollout_chained(const char* who, const RolloutFrame& f, rq_device* dev, rq_env* env, const rq_params* params, rq_state* state,
+                    const rq_rng* rng, uint32_t n_steps, uint32_t flags, const rq_trajectory* traj, Thaw thaw, Actor actor, Step step) {
+    hipError_t e = hipSuccess;
+    if (n_steps && (flags & RQ_ROLLOUT_AUTORESET))      // envs frozen by an earlier rollout start their next episode
+        if ((e = thaw()) != hipSuccess) return hip_failed(who, "the thaw launch", e);
+    for (uint32_t t = 0; t < n_steps; ++t) {
+        e = rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, rng->epoch + t, nullptr, params->d, state->d, env->obs);
+        if (e != hipSuccess) return hip_failed(who, "rq::launch_observe", e);
+        if (f.trk.ref && (e = rq::launch_track_shift(dev->stream, f.b, state->d, env->st, env->obs, f.trk)) != hipSuccess)
+            return hip_failed(who, "rq::launch_track_shift", e);
+        if ((e = actor()) != hipSuccess) return hip_failed(who, "the actor launch", e);
+        if ((e = step()) != hipSuccess) return hip_failed(who, "the step launch", e);
+        if (traj) {
+            rq::TrajPtrs tt = f.tp; tt.t0 = f.tp.t0 + t;
+            if ((e = rq::launch_record(dev->stream, f.b, env->obs, env->act, env->st, tt)) != hipSuccess)
+                return hip_failed(who, "rq::launch_record", e);
+        }
+    }
+    return RQ_OK;
+}
 int traj_block_to_host(rq_device* dev, const float* d_soa, uint32_t steps, uint32_t n, uint32_t ld, uint32_t dim, float* host);
 
 template <typename T>

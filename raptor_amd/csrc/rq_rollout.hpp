@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "rq_device_math.hpp"
+#include "rq_dispatch.hpp"
 
 namespace rq {
 
@@ -93,8 +94,7 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
 
 // The RATE variant (rq_policy_set_native_interval above 1): the same loop with the policy's hidden state moving on only at an env's
 // native steps - those whose episode step count is a multiple of `interval` - and the action of every other step computed from the
-// last committed state.  Tracked or not (trk.ref), no SampleAndSquash stage (the host refuses the pair).  Instantiated at
-// the end of the two translation units, behind everything else they hold.
+// last committed state.  Tracked or not (trk.ref), no SampleAndSquash stage (the host refuses the pair).
 template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
 __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_rate(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
                                                                uint64_t seed, uint32_t epoch0, uint32_t n_steps,
@@ -124,64 +124,40 @@ struct FusedArgs {
     uint32_t interval;         // the RATE variant's native interval (launch_rollout_fused_rate)
 };
 
-// the 16-bit actors' instantiations (rq_kernels_16bit.hip)
+// the 16-bit actors' instantiations of the three families (rq_kernels_16bit.hip)
 hipError_t launch_rollout_fused_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision);
-
-
-template <bool NZ, bool AR, bool RC, bool SAS, typename ACTOR>
-inline void launch_fused_instance(hipStream_t s, const FusedArgs& a) {
-    const unsigned g = (a.b.n + kFusedBlock - 1) / kFusedBlock;
-    hipLaunchKernelGGL((k_rollout_fused<NZ, AR, RC, SAS, ACTOR>), dim3(g), dim3(kFusedBlock), 0, s,
-                       a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
-                       a.st, a.traj, a.sas, a.span);
-}
-
-// the TRACK variant's instantiations for the 16-bit actors (rq_kernels_16bit.hip)
 hipError_t launch_rollout_fused_track_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision);
-
-template <bool NZ, bool AR, bool RC, typename ACTOR>
-inline void launch_fused_track_instance(hipStream_t s, const FusedArgs& a) {
-    const unsigned g = (a.b.n + kFusedBlock - 1) / kFusedBlock;
-    hipLaunchKernelGGL((k_rollout_fused_track<NZ, AR, RC, ACTOR>), dim3(g), dim3(kFusedBlock), 0, s,
-                       a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
-                       a.st, a.traj, a.trk, a.span);
-}
-template <typename ACTOR>
-inline void launch_fused_track_actor(hipStream_t s, const FusedArgs& a, bool noise, bool ar) {
-    const bool rec = a.traj.obs != nullptr;
-#define RQ_FUSED_RC(NZ, AR) do { if (rec) launch_fused_track_instance<NZ, AR, true, ACTOR>(s, a); \
-                                 else     launch_fused_track_instance<NZ, AR, false, ACTOR>(s, a); } while (0)
-    if (noise) { if (ar) RQ_FUSED_RC(true, true); else RQ_FUSED_RC(true, false); }
-    else       { if (ar) RQ_FUSED_RC(false, true); else RQ_FUSED_RC(false, false); }
-#undef RQ_FUSED_RC
-}
-
-// the RATE variant's instantiations for the 16-bit actors (rq_kernels_16bit.hip)
 hipError_t launch_rollout_fused_rate_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision);
 
-// the RATE instantiation for (noise, auto-reset, recording, tracking) of one actor build: one run-time switch per call
-template <typename ACTOR, bool NZ, bool AR, bool RC, bool TK>
-inline void launch_fused_rate_actor(hipStream_t s, const FusedArgs& a) {
-    const unsigned g = (a.b.n + kFusedBlock - 1) / kFusedBlock;
-    hipLaunchKernelGGL((k_rollout_fused_rate<NZ, AR, RC, TK, ACTOR>), dim3(g), dim3(kFusedBlock), 0, s,
-                       a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
-                       a.st, a.traj, a.trk, a.interval, a.span);
-}
-template <typename ACTOR, bool... DONE, typename... REST>
-inline void launch_fused_rate_actor(hipStream_t s, const FusedArgs& a, bool next, REST... rest) {
-    if (next) launch_fused_rate_actor<ACTOR, DONE..., true>(s, a, rest...);
-    else      launch_fused_rate_actor<ACTOR, DONE..., false>(s, a, rest...);
-}
+inline unsigned fused_grid(const FusedArgs& a) { return (a.b.n + kFusedBlock - 1) / kFusedBlock; }
 
-// the instantiation for (noise, auto-reset, recording) of one actor build; SAS = with the SampleAndSquash output stage
+// One launcher per family: the instantiation for (noise, auto-reset, recording[, tracking]) of one actor build, the run-time bools
+// made template arguments by dispatch_bools.  SAS = with the SampleAndSquash output stage.
 template <bool SAS, typename ACTOR>
 inline void launch_fused_actor(hipStream_t s, const FusedArgs& a, bool noise, bool ar) {
-    const bool rec = a.traj.obs != nullptr;
-#define RQ_FUSED_RC(NZ, AR) do { if (rec) launch_fused_instance<NZ, AR, true, SAS, ACTOR>(s, a); \
-                                 else     launch_fused_instance<NZ, AR, false, SAS, ACTOR>(s, a); } while (0)
-    if (noise) { if (ar) RQ_FUSED_RC(true, true); else RQ_FUSED_RC(true, false); }
-    else       { if (ar) RQ_FUSED_RC(false, true); else RQ_FUSED_RC(false, false); }
-#undef RQ_FUSED_RC
+    dispatch_bools([&](auto NZ, auto AR, auto RC) {
+        hipLaunchKernelGGL((k_rollout_fused<NZ(), AR(), RC(), SAS, ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
+                           a.st, a.traj, a.sas, a.span);
+    }, noise, ar, a.traj.obs != nullptr);
+}
+
+template <typename ACTOR>
+inline void launch_fused_track_actor(hipStream_t s, const FusedArgs& a, bool noise, bool ar) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC) {
+        hipLaunchKernelGGL((k_rollout_fused_track<NZ(), AR(), RC(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
+                           a.st, a.traj, a.trk, a.span);
+    }, noise, ar, a.traj.obs != nullptr);
+}
+
+template <typename ACTOR>
+inline void launch_fused_rate_actor(hipStream_t s, const FusedArgs& a, bool noise, bool ar) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
+        hipLaunchKernelGGL((k_rollout_fused_rate<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
+                           a.st, a.traj, a.trk, a.interval, a.span);
+    }, noise, ar, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
 }  // namespace rq

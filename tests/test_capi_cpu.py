@@ -376,6 +376,19 @@ def test_the_experiment_patch_still_applies_to_the_product_sources(tmp_path):
     assert "ActorBF16Lean" in (dst / "rq_kernels_16bit.hip").read_text()
 
 
+def test_the_bool_dispatcher_hands_over_each_combination_once_and_in_order(tmp_path):
+    """rq::dispatch_bools (raptor_amd/csrc/rq_dispatch.hpp) is what turns (noise, auto-reset, recording, tracking) into the template
+    arguments of every fused launcher: exchanged bools would still compile.  tests/dispatch_driver.cpp includes the header alone
+    under a plain host compiler (no HIP) and calls it with all 16 values of four bools: the callable is entered exactly once per call,
+    with exactly those constants in the order given."""
+    import subprocess
+    exe = str(tmp_path / "dispatch_driver")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "raptor_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "dispatch_driver.cpp")], check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok 16", r.stdout + r.stderr
+
+
 def test_the_hazard_lint_sees_a_move_behind_a_taken_branch():
     """The lint on a reduced rendition of the build it was written for: the move on the taken path (4 and 5 wait states behind
     the MFMA) is reported, the padded variant is not."""
