@@ -82,7 +82,9 @@ extern "C" {
                               (still 5: rq_policy_{set,get}_native_interval added, no struct changed)
                               (still 5: rq_policy_bank_* and rq_rollout_policies, then rq_bank_optimizer_* and rq_trajectory_policies_*
                               added, no struct changed)
-                              (still 5: rq_policy_bank_{set,get}_native_interval and rq_rollout_policies_track added, no struct changed) */
+                              (still 5: rq_policy_bank_{set,get}_native_interval and rq_rollout_policies_track added, no struct changed)
+                              (still 5: rq_reference_bank_{create,destroy}, rq_rollout_track_refs and rq_rollout_policies_track_refs added,
+                              no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -451,6 +453,28 @@ RQ_API int rq_rollout_track(rq_device* dev, rq_env* env, const rq_params* params
                      rq_trajectory* trajectory /* may be NULL */, const rq_reference* reference);
 RQ_API int rq_env_get_tracking_error(const rq_env* env, float* sum_sq, uint32_t* steps, int dst_is_device);
 
+/* ---- A suite of moving setpoints in one rollout: a reference per env ----
+ * A reference bank is n_refs tables of the same length, host_rows [n_refs][rows][6] float32, columns as above.  In
+ * rq_rollout_track_refs env i tracks table reference_id[i] (host array [n_envs]; ids are free per env, also inside a 64-env block)
+ * and computes, bit for bit, what rq_rollout_track computes for it with a rq_reference made of that table: state and hidden state,
+ * statistics and finished-episode records, done codes, the recording, the tracking-error sums and counts, the rng epoch moved on -
+ * fused and chained, every precision, at a native interval, with noise, with or without auto-reset and recording.  The kernels are
+ * rq_rollout_track's: they read row (reference_id[i] * rows + episode step count) of the flat table; the per-env first rows are
+ * built from the ids on the host and cached on the device beside the env's tracking statistics, keyed by (bank, ids) - the same
+ * ids upload nothing, other ids wait for the stream before the rows are rewritten.
+ * rq_reference_bank_create refuses a null argument, n_refs == 0, rows == 0, a non-finite entry and n_refs * rows >= 2^28 (the row
+ * index is a uint32).  The rollouts refuse, before anything is enqueued (state, rng epoch, statistics and recording untouched):
+ * a null argument, a bank of another rq_device (RQ_ERR_SHAPE_MISMATCH), rows < episode_step_limit, an id >= n_refs (the message
+ * names the env), a policy with a SampleAndSquash stage, and everything rq_rollout_track refuses. */
+typedef struct rq_reference_bank rq_reference_bank;
+RQ_API int rq_reference_bank_create(rq_device* dev, const float* host_rows /* [n_refs][rows][6] */, uint32_t n_refs, uint32_t rows,
+                                    rq_reference_bank** out);
+RQ_API int rq_reference_bank_destroy(rq_reference_bank* references);
+RQ_API int rq_rollout_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state,
+                                 rq_policy* policy, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                 rq_trajectory* trajectory /* may be NULL */, const rq_reference_bank* references,
+                                 const uint32_t* reference_id /* host [n_envs] */);
+
 /* ---- Learner: the student's gradient over a recorded trajectory (README.md:208-216, the distillation step's regression) ----
  * Forward: the policy on the recorded observations obs [T][22][ld] under rq_trajectory_relabel's episode rules (GRU state back to
  * the learned initial state after done codes 1 and 2, held on code 4) -> action [T][4][ld_action] (ld_action >= n_envs; only the
@@ -619,6 +643,13 @@ RQ_API int rq_policy_bank_get_native_interval(const rq_policy_bank* bank, uint32
 RQ_API int rq_rollout_policies_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
                                      const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                      rq_trajectory* trajectory, const rq_reference* reference);
+/* rq_rollout_policies_track with a reference bank: env i is flown by policy policy_id[i] at its native interval on table
+ * reference_id[i] - P policies on M setpoints in one rollout.  policy_id is constant on every 64-env block; reference_id is free per
+ * env.  Bit for bit rq_rollout_policies_track with a rq_reference made of table r on the envs with reference_id[i] == r.  Refused as
+ * rq_rollout_policies_track and rq_rollout_track_refs refuse.  Teacher banks do not track. */
+RQ_API int rq_rollout_policies_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
+                                          const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                          rq_trajectory* trajectory, const rq_reference_bank* references, const uint32_t* reference_id);
 
 /* ---- Distilling a bank: the update of rq_trajectory_distill for every policy of a bank at once - a sweep of learning rates or a seed
  * population costs one student's launch count, and "fly the bank, distil the bank, fly it again" never leaves the device.  The

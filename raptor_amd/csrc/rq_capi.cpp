@@ -109,8 +109,8 @@ int check_env_objects(const rq_device* dev, const rq_env* env, const rq_params* 
 int env_track_stats(rq_env* env, float** sum_sq, uint32_t** steps) {
     const size_t ld = env->ld;
     if (env->track_block.empty()) {
-        if (env->track_block.alloc(2 * 4 * ld) != hipSuccess) return fail(RQ_ERR_OUT_OF_MEMORY, "tracking statistics: device allocation failed");
-        const hipError_t e = hipMemsetAsync(env->track_block.get(), 0, 2 * 4 * ld, env->dev->stream);
+        if (env->track_block.alloc(3 * 4 * ld) != hipSuccess) return fail(RQ_ERR_OUT_OF_MEMORY, "tracking statistics: device allocation failed");
+        const hipError_t e = hipMemsetAsync(env->track_block.get(), 0, 3 * 4 * ld, env->dev->stream);
         if (e != hipSuccess) { env->track_block.reset(); return fail(RQ_ERR_HIP, "tracking statistics: hipMemsetAsync failed"); }
     }
     *sum_sq = (float*)env->track_block.get();

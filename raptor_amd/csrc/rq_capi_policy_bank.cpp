@@ -256,12 +256,14 @@ RQ_API int rq_policy_bank_get_hidden(rq_policy_bank* bank, float* host_out, uint
 // ones a bank's rollout always made; otherwise the RATE kernels, which take both.
 static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
                                  const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
-                                 rq_trajectory* traj, const rq_reference* ref) {
+                                 rq_trajectory* traj, const rq_reference* ref, const rq_reference_bank* refs = nullptr,
+                                 const uint32_t* reference_id = nullptr) {
     RolloutFrame f;
     int rc = rollout_check(f, dev, env, params, state, rng, bank && policy_id, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy bank lives on another device");
     // a tracked rollout is refused here, before anything is enqueued (as rq_rollout_track refuses it)
     if (ref) { rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc; }
+    rc = rollout_check_reference_bank(__func__, dev, env, refs, reference_id); if (rc) return rc;
     rc = bank_check_ids(bank, policy_id, env->n); if (rc) return rc;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = bank_size(bank, env->n); if (rc) return rc;
@@ -269,12 +271,13 @@ static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* p
     rc = bank_table(bank, dev, env->uid, policy_id, env->n); if (rc) return rc;
     rc = bank_apply_reset(bank); if (rc) return rc;
     rc = rollout_track(f, env, ref); if (rc) return rc;
+    rc = rollout_track_refs(f, dev, env, refs, reference_id); if (rc) return rc;
     const bool rated = bank->rated;
     rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
     if (mode == RQ_ROLLOUT_FUSED) {
         unsigned long long* span = nullptr;
         rc = fused_span_begin(__func__, dev, env, n_steps, &span); if (rc) return rc;
-        if (ref || rated)
+        if (f.trk.ref || rated)
             RQ_HIP(rq::launch_rollout_fused_bank_rate(dev->stream, f.b, f.sc, f.nc, f.noise, f.smp, rng->seed, rng->epoch, n_steps, flags,
                                                       params->d, state->d, bank->hidden, bank->weights, bank->images, bank->table,
                                                       bank->intervals_dev, env->st, f.tp, f.trk, span));
@@ -311,6 +314,15 @@ RQ_API int rq_rollout_policies_track(rq_device* dev, rq_env* env, const rq_param
                                      rq_trajectory* traj, const rq_reference* reference) {
     RQ_REQUIRE(reference, RQ_ERR_INVALID_ARGUMENT, "null reference");
     return rollout_policies_impl(dev, env, params, state, bank, policy_id, rng, n_steps, mode, flags, traj, reference);
+}
+
+RQ_API int rq_rollout_policies_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
+                                          const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                          rq_trajectory* traj, const rq_reference_bank* references, const uint32_t* reference_id) {
+    RQ_REQUIRE(references, RQ_ERR_INVALID_ARGUMENT, "null reference bank");
+    RQ_REQUIRE(reference_id, RQ_ERR_INVALID_ARGUMENT, "null reference_id");
+    return rollout_policies_impl(dev, env, params, state, bank, policy_id, rng, n_steps, mode, flags, traj, nullptr, references,
+                                 reference_id);
 }
 
 }  // extern "C"

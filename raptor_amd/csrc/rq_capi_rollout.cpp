@@ -53,6 +53,49 @@ int rollout_track(RolloutFrame& f, rq_env* env, const rq_reference* ref) {
     return RQ_OK;
 }
 
+int rollout_check_reference_bank(const char* who, const rq_device* dev, const rq_env* env, const rq_reference_bank* refs,
+                                 const uint32_t* reference_id) {
+    if (!refs) return RQ_OK;
+    if (refs->dev != dev) return fail(RQ_ERR_SHAPE_MISMATCH, std::string(who) + ": reference bank lives on another device");
+    if (refs->rows < env->cfg.episode_step_limit)
+        return fail(RQ_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": reference bank has fewer rows than episode_step_limit: every table must cover an episode");
+    for (uint32_t i = 0; i < env->n; ++i)
+        if (reference_id[i] >= refs->n_refs)
+            return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": reference id out of range: env " + std::to_string(i) +
+                                                     " names reference " + std::to_string(reference_id[i]) + " of a bank of " +
+                                                     std::to_string(refs->n_refs));
+    return RQ_OK;
+}
+
+int rollout_track_refs(RolloutFrame& f, rq_device* dev, rq_env* env, const rq_reference_bank* refs, const uint32_t* reference_id) {
+    if (!refs) return RQ_OK;
+    const uint32_t n = env->n;
+    int rc = env_track_stats(env, &f.trk.sq, &f.trk.steps); if (rc) return rc;
+    uint32_t* row0 = f.trk.steps + env->ld;                       // the block's third array
+    const bool same = env->row0_valid && env->row0_key == refs->uid && env->row0_ids.size() == n &&
+                      std::memcmp(env->row0_ids.data(), reference_id, (size_t)n * sizeof(uint32_t)) == 0;
+    if (!same) {
+        env->row0_valid = false;
+        std::vector<uint32_t> first;
+        try {                                   // nothing throws across the boundary
+            env->row0_ids.assign(reference_id, reference_id + n);
+            first.resize(n);
+        } catch (const std::bad_alloc&) {
+            return fail(RQ_ERR_OUT_OF_MEMORY, "reference bank: host allocation failed");
+        }
+        for (uint32_t i = 0; i < n; ++i) first[i] = reference_id[i] * refs->rows;       // < n_refs * rows < 2^28
+        RQ_HIP(hipStreamSynchronize(dev->stream));                // a rollout in flight reads the rows of the ids before
+        RQ_HIP(hipMemcpyAsync(row0, first.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, dev->stream));
+        RQ_HIP(hipStreamSynchronize(dev->stream));                // `first` is pageable and goes away
+        env->row0_valid = true;
+        env->row0_key = refs->uid;
+        env->row0_gen = fresh_version();
+    }
+    f.trk.ref = refs->d; f.trk.rows = refs->rows; f.trk.row0_at = env->ld; f.row0_gen = env->row0_gen;
+    return RQ_OK;
+}
+
 int rollout_begin(RolloutFrame& f, rq_device* dev, rq_env* env, rq_state* state, uint32_t n_steps, uint32_t flags, rq_trajectory* traj) {
     obs_cache_drop_if(dev, env);
     if (n_steps) { const int rc = state_make_private(state, true); if (rc) return rc; }      // steps the state in place
@@ -100,12 +143,15 @@ static constexpr size_t kMaxGraphs = 8;       // executable graphs kept per env 
 
 static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy* policy,
                         rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags, rq_trajectory* traj,
-                        const rq_reference* ref = nullptr) {
+                        const rq_reference* ref = nullptr, const rq_reference_bank* refs = nullptr,
+                        const uint32_t* reference_id = nullptr) {
     RolloutFrame f;
+    const bool tracked = ref || refs;
     int rc = rollout_check(f, dev, env, params, state, rng, policy != nullptr, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(policy->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy lives on another device");
-    if (ref) {          // a tracked rollout is refused here, before anything is enqueued
-        rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc;
+    if (tracked) {      // a tracked rollout is refused here, before anything is enqueued
+        if (ref) { rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc; }
+        rc = rollout_check_reference_bank(__func__, dev, env, refs, reference_id); if (rc) return rc;
         RQ_REQUIRE(policy->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
                    "tracked rollouts do not carry the SampleAndSquash stage");
     }
@@ -114,6 +160,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
     rc = policy_size(policy, env->n); if (rc) return rc;
     RQ_REQUIRE(policy->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy batch does not match the env");
     rc = rollout_track(f, env, ref); if (rc) return rc;
+    rc = rollout_track_refs(f, dev, env, refs, reference_id); if (rc) return rc;
     rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
     const rq::TrajPtrs& tp = f.tp; const rq::TrackPtrs& trk = f.trk;
     const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
@@ -125,7 +172,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
             RQ_HIP(rq::launch_rollout_fused_rate(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
                                                  params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
                                                  policy->precision, tp, trk, interval, span));
-        } else if (ref) {
+        } else if (tracked) {
             RQ_HIP(rq::launch_rollout_fused_track(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
                                                   params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
                                                   policy->precision, tp, trk, span));
@@ -141,13 +188,13 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
         // observation of the rollout is a launch of its own, the one assembled by the last step is not used)
         // A tracked rollout puts one small kernel in front of the actor: it takes the setpoint off the assembled observation,
         // wherever that came from, and keeps the tracking error (the observation the last step assembles is never shifted).
-        const uint32_t step_nodes = ref ? 3u : 2u;
+        const uint32_t step_nodes = tracked ? 3u : 2u;
         const bool fold_observe = traj == nullptr;
         auto enqueue_step = [&](uint32_t epoch, const uint32_t* epoch_base, uint32_t t_record) -> hipError_t {
             hipError_t e = hipSuccess;
             if (!fold_observe)
                 e = rq::launch_observe(dev->stream, b, nc, noise, rng->seed, epoch, epoch_base, params->d, state->d, env->obs);
-            if (e == hipSuccess && ref)
+            if (e == hipSuccess && tracked)
                 e = rq::launch_track_shift(dev->stream, b, state->d, env->st, env->obs, trk);
             if (e == hipSuccess && interval > 1)     // the env's episode step count is that of this step's observation: k_step moves it on
                 e = rq::launch_actor_step_rate(dev->stream, env->n, packed_of(policy), env->obs, env->ld, policy->hidden,
@@ -182,6 +229,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                     g.packed == packed_of(policy) && g.weights == policy->w_dev && g.flags == flags &&
                     g.precision == policy->precision && g.seed == rng->seed && g.sas_mode == policy->sas_mode &&
                     g.sas_seed == policy->sas_seed && g.ls_image == policy->ls_image && g.ref == trk.ref && g.ref_rows == trk.rows &&
+                    g.row0_at == trk.row0_at && g.row0_gen == f.row0_gen &&      // (a reference bank: which ids the rows were built from)
                     g.interval == interval &&
                     std::memcmp(&g.cfg, &env->cfg, sizeof(rq_env_config)) == 0) { exec = g.exec; break; }
             if (!exec) {
@@ -215,7 +263,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                     try {                       // nothing throws across the boundary
                         env->graphs.push_back({params->d, state->d, policy->hidden, packed_of(policy), policy->w_dev, env->obs, flags,
                                                policy->precision, env->cfg, rng->seed, policy->sas_mode, policy->sas_seed,
-                                               policy->ls_image, trk.ref, trk.rows, interval, exec});
+                                               policy->ls_image, trk.ref, trk.rows, trk.row0_at, f.row0_gen, interval, exec});
                     } catch (const std::bad_alloc&) {
                         (void)hipGraphExecDestroy(exec);
                         return fail(RQ_ERR_OUT_OF_MEMORY, "rollout: host allocation failed");
@@ -282,6 +330,50 @@ RQ_API int rq_rollout_track(rq_device* dev, rq_env* env, const rq_params* params
                      const rq_reference* reference) {
     RQ_REQUIRE(reference, RQ_ERR_INVALID_ARGUMENT, "null reference");
     return rollout_impl(dev, env, params, state, policy, rng, n_steps, mode, flags, trajectory, reference);
+}
+
+RQ_API int rq_reference_bank_create(rq_device* dev, const float* host_rows, uint32_t n_refs, uint32_t rows, rq_reference_bank** out) {
+    RQ_REQUIRE(dev && host_rows && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    RQ_REQUIRE(n_refs > 0 && rows > 0, RQ_ERR_INVALID_ARGUMENT, "a reference bank needs at least one table of at least one row");
+    // the row an env reads, first row of its table + episode step count, is a uint32 on the device
+    RQ_REQUIRE((uint64_t)n_refs * rows < (1ull << 28), RQ_ERR_INVALID_ARGUMENT, "a reference bank holds fewer than 2^28 rows in all");
+    const size_t floats = (size_t)n_refs * rows * 6;
+    for (size_t j = 0; j < floats; ++j)
+        RQ_REQUIRE(std::isfinite(host_rows[j]), RQ_ERR_INVALID_ARGUMENT,
+                   "reference bank holds a non-finite entry: table " + std::to_string(j / ((size_t)rows * 6)) + ", row " +
+                       std::to_string(j / 6 % rows));
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    rq_reference_bank* r = new (std::nothrow) rq_reference_bank();
+    RQ_REQUIRE(r, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
+    r->dev = dev; r->ordinal = dev->ordinal; r->n_refs = n_refs; r->rows = rows;
+    if (r->d.alloc(floats) != hipSuccess) {
+        delete r;
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_reference_bank_create: device allocation failed");
+    }
+    // (synchronous: the caller's rows are its own again on return)
+    const hipError_t e = hipMemcpy(r->d, host_rows, floats * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete r;
+        return fail(RQ_ERR_HIP, std::string("rq_reference_bank_create: hipMemcpy -> ") + hipGetErrorString(e));
+    }
+    *out = r;
+    return RQ_OK;
+}
+
+RQ_API int rq_reference_bank_destroy(rq_reference_bank* references) {
+    if (!references) return RQ_OK;
+    DeviceScope on_device(references->ordinal);     // (hipFree synchronises the device: no launch still reads the tables)
+    delete references;
+    return RQ_OK;
+}
+
+RQ_API int rq_rollout_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy* policy,
+                                 rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags, rq_trajectory* trajectory,
+                                 const rq_reference_bank* references, const uint32_t* reference_id) {
+    RQ_REQUIRE(references, RQ_ERR_INVALID_ARGUMENT, "null reference bank");
+    RQ_REQUIRE(reference_id, RQ_ERR_INVALID_ARGUMENT, "null reference_id");
+    return rollout_impl(dev, env, params, state, policy, rng, n_steps, mode, flags, trajectory, nullptr, references, reference_id);
 }
 
 // ---------------------------------------------------------------------------- Trajectory

@@ -384,8 +384,10 @@ __device__ __forceinline__ void observe_head(const QuadState& y, f32x2 LA01, f32
 // chained kernels and a caller that subtracts on the host agree bit for bit.  The three functions below are the only place any
 // path does this arithmetic: single rounded operations in a fixed order, nothing the compiler may contract.
 // (k is clamped to the table: the host refuses rows < episode_step_limit, the clamp keeps a stale step count inside the block)
-__device__ __forceinline__ void track_row(const float* __restrict__ ref, uint32_t rows, uint32_t k, float (&r)[6]) {
-    const float* row = ref + (size_t)(k < rows ? k : rows - 1u) * 6u;
+// row0: the first row of the env's own table in a reference bank's flat [M * rows][6] block (TrackPtrs::row0_at; 0: the single table) -
+// the host keeps M * rows below 2^28, so row0 + k stays a uint32 and the offset is formed in size_t
+__device__ __forceinline__ void track_row(const float* __restrict__ ref, uint32_t rows, uint32_t row0, uint32_t k, float (&r)[6]) {
+    const float* row = ref + (size_t)(row0 + (k < rows ? k : rows - 1u)) * 6u;
 #pragma unroll
     for (int j = 0; j < 6; ++j) r[j] = row[j];
 }

@@ -1258,7 +1258,7 @@ __global__ __launch_bounds__(kBlock) void k_track_shift(Batch b, const float* __
     const uint32_t i = env_index();
     if (i >= b.n) return;
     float tr[6], o[15];
-    track_row(trk.ref, trk.rows, st.steps[i], tr);
+    track_row(trk.ref, trk.rows, trk.row0_at != 0 ? trk.steps[(size_t)trk.row0_at + i] : 0u, st.steps[i], tr);
 #pragma unroll
     for (int j = 0; j < 3; ++j) { o[j] = field(obs, j, b.ld)[i]; o[12 + j] = field(obs, (12 + j), b.ld)[i]; }
     track_shift(tr, o);

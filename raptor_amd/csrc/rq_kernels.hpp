@@ -70,9 +70,16 @@ struct TrajPtrs {
 struct TrackPtrs {
     const float* ref;     // [rows][6] row-major: target position, target linear velocity (world frame); nullptr = untracked
     uint32_t rows;
+    // A reference bank (rq_rollout_track_refs): `ref` is M tables one after another, [M * rows][6], and env i reads the table that
+    // begins at row steps[row0_at + i] = reference_id[i] * rows - per lane, with no wave granularity: the row was a per-lane gather
+    // already.  The env's tracking block holds that [ld] array behind the counts.  0 (wave-uniform: a kernel argument) = every env's
+    // table begins at row 0, the single reference.  An offset in what was the struct's padding, not a pointer: the RATE kernels take
+    // TrackPtrs by value in their TRACK = false instantiations too, and a struct that grew would move their argument block.
+    uint32_t row0_at;
     float* sq;            // [ld]: running sum of |p - p_ref|^2 over the steps taken
     uint32_t* steps;      // [ld]: how many
 };
+static_assert(sizeof(TrackPtrs) == 32, "the kernels' argument blocks hold TrackPtrs by value");
 
 // SampleAndSquash output stage of the actor (rq_policy_set_sample_and_squash): mode = rq_sample_and_squash_mode
 struct SasArgs {

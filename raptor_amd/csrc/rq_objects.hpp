@@ -204,7 +204,15 @@ struct rq_env {
     DeviceBuffer<float> act;    // [RQ_ACTION_DIM][ld]
     DeviceBuffer<char> stats_block;
     rq::StatsPtrs st{};         // views into stats_block
-    DeviceBuffer<char> track_block;     // tracked rollouts' statistics, [ld] float sums then [ld] uint32 counts (env_track_stats: first use)
+    // tracked rollouts' statistics, [ld] float sums then [ld] uint32 counts, and behind them the [ld] uint32 first rows of a reference
+    // bank's rollout (env_track_stats: first use)
+    DeviceBuffer<char> track_block;
+    // what the first rows were built from, cached as the policy bank caches its id table: (row0_key = the reference bank's uid,
+    // row0_ids = one id per env) - a loop of rollouts with one assignment uploads them once; other ids wait for the stream, then
+    // rewrite the rows.  row0_gen names the upload: a chained rollout's hipGraph is keyed by it.
+    bool row0_valid = false;
+    uint64_t row0_key = 0, row0_gen = 0;
+    std::vector<uint32_t> row0_ids;
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
     // epoch-counter bump); one executable graph per distinct argument set
     struct GraphEntry {
@@ -212,6 +220,7 @@ struct rq_env {
         uint32_t flags; int precision; rq_env_config cfg; uint64_t seed;
         int sas_mode; uint64_t sas_seed; const float* ls_image;
         const float* ref; uint32_t ref_rows;     // tracked rollouts: the reference table (nullptr: untracked)
+        uint32_t row0_at; uint64_t row0_gen;     // a reference bank's per-env first rows and which upload they are (0, 0: none)
         uint32_t interval;                       // the policy's native interval: the actor nodes of another one are other kernels
         hipGraphExec_t exec;
     };
@@ -261,6 +270,16 @@ struct rq_reference {
     int ordinal = 0;
     uint32_t rows = 0;
     DeviceBuffer<float> d;              // [rows][6] row-major
+};
+
+// M moving setpoints of one length on the device (rq_reference_bank_create), one after another: env i of a rollout reads the table
+// that begins at row reference_id[i] * rows
+struct rq_reference_bank {
+    const rq_device* dev = nullptr;     // compared, never followed (as rq_reference::dev)
+    int ordinal = 0;
+    uint32_t n_refs = 0, rows = 0;
+    DeviceBuffer<float> d;              // [n_refs * rows][6] row-major
+    uint64_t uid = fresh_version();     // what an env knows the bank by, beside its address (rq_env::row0_key)
 };
 
 struct rq_policy {
@@ -465,13 +484,20 @@ int require_bank_native_rate(const rq_policy_bank* bank, const char* what);
 // the recording's length and the state's version move on.
 struct RolloutFrame {
     rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
-    rq::TrackPtrs trk{nullptr, 0, nullptr, nullptr};      // ref != nullptr: a tracked rollout
+    rq::TrackPtrs trk{};                                          // ref != nullptr: a tracked rollout
+    uint64_t row0_gen = 0;                                         // a reference bank's rollout: rq_env::row0_gen
     rq::Batch b; rq::StepCfg sc; rq::NoiseCfg nc; rq::SampleCfg smp; bool noise;
 };
 int rollout_check(RolloutFrame& f, const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,
                   bool actor, uint32_t n_steps, int mode, uint32_t flags, const rq_trajectory* traj);
 int rollout_check_reference(const char* who, const rq_device* dev, const rq_env* env, const rq_reference* ref);
 int rollout_track(RolloutFrame& f, rq_env* env, const rq_reference* ref);
+// The same two for a reference bank (rq_rollout_track_refs, rq_rollout_policies_track_refs; a null bank: nothing).  The check also
+// reads every id (an id outside the bank is refused naming the env); rollout_track_refs, inside the scope, puts the per-env first
+// rows on the device unless the env holds them for (bank, ids) already.
+int rollout_check_reference_bank(const char* who, const rq_device* dev, const rq_env* env, const rq_reference_bank* refs,
+                                 const uint32_t* reference_id);
+int rollout_track_refs(RolloutFrame& f, rq_device* dev, rq_env* env, const rq_reference_bank* refs, const uint32_t* reference_id);
 int rollout_begin(RolloutFrame& f, rq_device* dev, rq_env* env, rq_state* state, uint32_t n_steps, uint32_t flags, rq_trajectory* traj);
 void rollout_end(rq_state* state, rq_rng* rng, uint32_t n_steps, rq_trajectory* traj);
 // a failed HIP call of a shared piece, reported as the caller's own RQ_HIP would: `who` is the caller's name, `what` the call

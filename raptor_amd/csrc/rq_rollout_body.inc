@@ -38,7 +38,12 @@
     // tracked rollouts: the env's running sum of |p - p_ref|^2 and the steps it covers (rq_env_get_tracking_error)
     float trk_sq = 0.0f;
     uint32_t trk_n = 0;
-    if constexpr (TRACK) { trk_sq = trk.sq[i]; trk_n = trk.steps[i]; }
+    // (a reference bank: the first row of the env's own table, loaded once per launch and carried in one register)
+    [[maybe_unused]] uint32_t trk_row0 = 0;
+    if constexpr (TRACK) {
+        trk_sq = trk.sq[i]; trk_n = trk.steps[i];
+        if (trk.row0_at != 0) trk_row0 = trk.steps[(size_t)trk.row0_at + i];       // wave-uniform test (kernel argument)
+    }
     // RATE (rq_policy_set_native_interval): the env's episode step count modulo the native interval - the launch's only division.
     // The hidden state moves on at the steps where it is 0; at the others the policy acts from the last committed state.
     [[maybe_unused]] uint32_t phase = 0;
@@ -165,7 +170,7 @@
             // the setpoint of this step: the row of the env's own episode step count (lanes are at different rows: per-lane
             // loads of a table that stays in the cache), taken off what the policy sees; the error on the true position
             float tr[6];
-            track_row(trk.ref, trk.rows, ep_steps, tr);
+            track_row(trk.ref, trk.rows, trk_row0, ep_steps, tr);
             track_shift(tr, o);
             if (AUTORESET || !frozen) { trk_sq = track_accumulate(trk_sq, y.P01[0], y.P01[1], y.p2, tr); trk_n += 1; }
         }

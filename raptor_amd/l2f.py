@@ -174,6 +174,59 @@ class Reference:
         self._fin = weakref.finalize(self, _lib.load().rq_reference_destroy, h)
 
 
+def _reference_tables(tables):
+    """The tables of a ``ReferenceBank`` as the C layer takes them, or ValueError: float32 [M >= 1, rows >= 1, 6], finite, contiguous;
+    a list of M tables of equal length is stacked."""
+    if isinstance(tables, (list, tuple)):
+        if not tables:
+            raise ValueError("a reference bank holds at least one table")
+        rows = [_reference_table(t) for t in tables]
+        if len({t.shape[0] for t in rows}) != 1:
+            raise ValueError("the tables of a reference bank have the same number of rows; got " + ", ".join(str(t.shape[0]) for t in rows))
+        return np.ascontiguousarray(np.stack(rows))
+    if not isinstance(tables, np.ndarray) or tables.dtype != np.float32:
+        raise ValueError("a reference bank is a float32 NumPy array [M, rows, 6] or a list of M [rows, 6] tables")
+    if tables.ndim != 3 or tables.shape[2] != 6 or tables.shape[0] < 1 or tables.shape[1] < 1:
+        raise ValueError(f"a reference bank has shape [M >= 1, rows >= 1, 6]; got {tables.shape}")
+    if not np.isfinite(tables).all():
+        raise ValueError("a reference table holds finite entries only")
+    if tables.shape[0] * tables.shape[1] >= 1 << 28:
+        raise ValueError("a reference bank holds fewer than 2^28 rows in all")
+    return np.ascontiguousarray(tables)
+
+
+class ReferenceBank:
+    """M moving setpoints of the same length for ``vector.rollout(..., reference=bank, reference_ids=ids)`` and
+    ``PolicyBank.fly(..., reference=bank, reference_ids=ids)``: ``tables`` float32 [M, rows, 6] (or a list of M [rows, 6] tables),
+    columns as in ``Reference``.  Env i flies table ``ids[i]`` - ids are free per env - and computes, bit for bit, what it computes
+    with ``Reference(tables[ids[i]])``.  The tables are copied to ``device`` once, here (``raptor_amd.tracking.suite`` makes some)."""
+
+    def __init__(self, device, tables):
+        t = _reference_tables(tables)           # refused before the device is touched
+        h = C.c_void_p()
+        _lib.call("rq_reference_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), C.byref(h))
+        self._h = h
+        self._device = device
+        self.n_references = int(t.shape[0])
+        self.rows = int(t.shape[1])
+        self._fin = weakref.finalize(self, _lib.load().rq_reference_bank_destroy, h)
+
+
+def _checked_reference(reference, reference_ids, n_envs):
+    """What a rollout's ``reference`` / ``reference_ids`` pair must be, before any library call -> the ids as uint32 (a
+    ``ReferenceBank``) or None (a ``Reference``, or no reference); ValueError otherwise."""
+    if isinstance(reference, ReferenceBank):
+        if reference_ids is None:
+            raise ValueError("a ReferenceBank flies the envs by reference_ids: one reference id per env is required")
+        from .tracking import check_reference_ids
+        return check_reference_ids(reference_ids, reference.n_references, n_envs)
+    if reference_ids is not None:
+        raise ValueError("reference_ids belong to a ReferenceBank: a Reference is every env's table")
+    if reference is not None and not isinstance(reference, Reference):
+        raise ValueError("reference must be an l2f.Reference or an l2f.ReferenceBank")
+    return None
+
+
 class _Handle:
     """Lazily created C object (the reference's constructors take no device argument)."""
     _destroy = None
@@ -628,7 +681,7 @@ class VectorModule:
                   state._require("VectorState"), None, next_state._ensure(env), rng._require("rng"), None)
 
     def rollout(self, device, env, params, state, policy, rng, n_steps, mode="fused", autoreset=False,
-                trajectory=None, teacher_ids=None, reference=None, policy_ids=None):
+                trajectory=None, teacher_ids=None, reference=None, policy_ids=None, reference_ids=None):
         """The loop body README.md:95-99, ``n_steps`` times, entirely on the device; with
         ``trajectory`` every transition is also appended to that buffer.  ``policy`` is a ``Raptor`` or a
         ``raptor_amd.teachers.TeacherBank``; with a bank, ``teacher_ids`` ([N] integers) names the teacher that flies
@@ -636,11 +689,14 @@ class VectorModule:
         ``reference`` (a ``Reference``): the policy tracks that moving setpoint - it sees position and linear velocity relative to
         the row of each env's own episode step count; everything else (state, reward, termination, statistics) stays absolute, a
         ``trajectory`` records what the policy saw, and ``env.tracking_error()`` accumulates.  ``Raptor`` policies only.
+        ``reference`` may also be a ``ReferenceBank`` with ``reference_ids`` ([N] integers, free per env): env i tracks table
+        ``reference_ids[i]`` and computes what it computes with that table as its ``Reference``.
         ``policy`` may also be a ``raptor_amd.policy_bank.PolicyBank``: ``policy_ids`` ([N] integers, constant on every aligned
         block of 64 envs) names the student policy that flies each env, both modes, every policy at the bank's native interval for
         it.  A bank does not take ``reference`` here: ``PolicyBank.fly(..., reference=ref)`` is the bank's tracked rollout."""
         if reference is not None and teacher_ids is not None:
             raise ValueError("reference and teacher_ids do not combine: a TeacherBank rollout does not track")
+        ref_ids = _checked_reference(reference, reference_ids, self.N_ENVIRONMENTS)
         m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
         from .policy_bank import PolicyBank, check_policy_ids
         if isinstance(policy, PolicyBank):
@@ -674,12 +730,13 @@ class VectorModule:
         if teacher_ids is not None:
             raise ValueError("teacher_ids belong to a TeacherBank rollout; a Raptor policy flies every env itself")
         if reference is not None:
-            if not isinstance(reference, Reference):
-                raise ValueError("reference must be an l2f.Reference")
-            _lib.call("rq_rollout_track", device._h, env._require("environment"), params._require("VectorParameters"),
-                      state._require("VectorState"), policy._handle(device), rng._require("rng"), int(n_steps), m,
-                      ROLLOUT_AUTORESET if autoreset else 0,
-                      trajectory._require("trajectory") if trajectory is not None else None, reference._h)
+            args = (device._h, env._require("environment"), params._require("VectorParameters"), state._require("VectorState"),
+                    policy._handle(device), rng._require("rng"), int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0,
+                    trajectory._require("trajectory") if trajectory is not None else None, reference._h)
+            if ref_ids is None:
+                _lib.call("rq_rollout_track", *args)
+            else:
+                _lib.call("rq_rollout_track_refs", *args, ref_ids.ctypes.data)
             return
         fast = _lib.fast
         if fast is not None and trajectory is None and state._mirror is None and hasattr(fast, "rollout"):

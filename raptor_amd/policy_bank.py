@@ -188,36 +188,47 @@ class PolicyBank:
         return out
 
     def fly(self, vector, device, env, params, state, rng, n_steps, policy_ids, mode="fused", autoreset=False, trajectory=None,
-            reference=None):
+            reference=None, reference_ids=None):
         """The bank's own rollout call: ``vector.rollout(..., bank, ..., policy_ids=ids)`` - every policy at its native interval -
         and, with ``reference`` (an ``l2f.Reference``), on that moving setpoint: each env sees position and linear velocity relative
         to the row of its own episode step count, a ``trajectory`` records what the policy saw and ``env.tracking_error()``
-        accumulates, as in a ``Raptor`` policy's tracked rollout."""
-        from .l2f import ROLLOUT_AUTORESET, ROLLOUT_CHAINED, ROLLOUT_FUSED, Reference
+        accumulates, as in a ``Raptor`` policy's tracked rollout.  With an ``l2f.ReferenceBank`` and ``reference_ids`` ([N] integers,
+        free per env, also inside a block) env i tracks table ``reference_ids[i]``: one rollout flies P policies on M setpoints."""
+        from .l2f import ROLLOUT_AUTORESET, ROLLOUT_CHAINED, ROLLOUT_FUSED, _checked_reference
         m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
         ids = check_policy_ids(policy_ids, self.n_policies, vector.N_ENVIRONMENTS)
+        ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)
         args = (device._h, env._require("environment"), params._require("VectorParameters"), state._require("VectorState"), self._h,
                 ids.ctypes.data, rng._require("rng"), int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0,
                 trajectory._require("trajectory") if trajectory is not None else None)
         if reference is None:
             _lib.call("rq_rollout_policies", *args)
-        else:
-            if not isinstance(reference, Reference):
-                raise ValueError("reference must be an l2f.Reference")
+        elif ref_ids is None:
             _lib.call("rq_rollout_policies_track", *args, reference._h)
+        else:
+            _lib.call("rq_rollout_policies_track_refs", *args, reference._h, ref_ids.ctypes.data)
 
     def evaluate(self, vector, device, env, params, state, rng, n_steps, policy_ids=None, mode="fused", autoreset=True,
-                 reference=None):
+                 reference=None, reference_ids=None):
         """The closed-loop evaluation of the whole bank: statistics and hidden state start afresh, one rollout of ``n_steps`` flies
         env i with policy ``policy_ids[i]`` (default: blocks dealt round-robin) at its native interval ->
         ``policy_episode_table`` of what it finished.  With ``reference`` the bank tracks that moving setpoint and the table gains
-        ``tracking_rmse`` [P] (``policy_tracking_table`` of ``env.tracking_error()``, which starts afresh too)."""
+        ``tracking_rmse`` [P] (``policy_tracking_table`` of ``env.tracking_error()``, which starts afresh too).  With an
+        ``l2f.ReferenceBank`` and ``reference_ids`` (``tracking.spread_reference_ids(N, M, policy_ids)`` deals them evenly inside
+        every policy's envs) ``tracking_rmse`` is [P, M]: policy p on setpoint r (``tracking.reference_tracking_table``)."""
         ids = block_policy_assignment(vector.N_ENVIRONMENTS, self.n_policies) if policy_ids is None else policy_ids
+        from .l2f import _checked_reference
+        ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
         env.reset_statistics()
         self.reset()
-        self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference)
+        self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
+                 reference_ids=reference_ids)
         table = policy_episode_table(env, ids, self.n_policies)
-        if reference is not None:
+        if ref_ids is not None:
+            from .tracking import reference_tracking_table
+            sum_sq, steps = env.tracking_error()
+            table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, ref_ids, reference.n_references, ids, self.n_policies)
+        elif reference is not None:
             sum_sq, steps = env.tracking_error()
             table["tracking_rmse"] = policy_tracking_table(sum_sq, steps, ids, self.n_policies)
         return table
