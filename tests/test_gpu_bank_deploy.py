@@ -7,15 +7,19 @@ flown, as a batch of its own (`VectorModule(n_g, OFFSET + 64 g)`, same seed, con
 invariant of the engine.  Every comparison is on the bits, no tolerance: the bank's kernels call the single-policy kernels' own
 device functions.  Recordings are compared where a transition was taken (done code != 4) and on every done code.
 """
+from functools import partial
+
 import numpy as np
 import pytest
 
+import rollout_common
+from rollout_common import LIMIT, OFFSET, STEPS, assert_same, assert_same_recording, bank_weights, bits, fly_slice, ids_of, join, snapshot
+
 pytestmark = pytest.mark.gpu
 
-OFFSET = 1000                  # global id of the bank batch's env 0
-LIMIT = 16                     # episode_step_limit: 40 steps cross two episode ends per env
-STEPS = 40
-NOISE = dict(noise_position=0.01, noise_orientation=0.005, noise_linear_velocity=0.02, noise_angular_velocity=0.01)
+# every bank of this file flies through PolicyBank.fly (tests/test_gpu_policy_bank.py keeps to vector.rollout(..., policy_ids=))
+Batch, fly_bank = partial(rollout_common.Batch, via="fly"), partial(rollout_common.fly_bank, via="fly")
+
 # N = 200: three full blocks and a ragged one of 8; a non-monotone assignment with a policy reused on non-adjacent blocks
 N, P = 200, 3
 BLOCK_IDS = [2, 0, 2, 1]
@@ -23,105 +27,8 @@ RATES = (4, 1, 3)              # 3 does not divide 16: the phase reset at an epi
 ONES = (1, 1, 1)
 
 
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint8)
-
-
-def bank_weights(weights, n_policies):
-    """policy k = the shipped weights + 0.05 * default_rng(100 + k).standard_normal(2084), float32"""
-    return np.stack([weights + np.float32(0.05) * np.random.default_rng(100 + k).standard_normal(2084).astype(np.float32)
-                     for k in range(n_policies)]).astype(np.float32)
-
-
-def ids_of(block_ids, n):
-    return np.repeat(np.asarray(block_ids, np.uint32), 64)[:n]
-
-
-class Batch:
-    """The l2f-shaped objects of one batch on the GPU: domain randomisation on, seed 3."""
-
-    def __init__(self, device, n, offset=OFFSET, limit=LIMIT, noise=False):
-        import raptor_amd.l2f as l2f
-        self.device, self.n = device, n
-        self.vector = v = l2f.VectorModule(n, offset)
-        self.rng, self.env, self.params, self.state = v.VectorRng(), v.VectorEnvironment(), v.VectorParameters(), v.VectorState()
-        v.initialize_rng(device, self.rng, 3)
-        v.initialize_environment(device, self.env)
-        cfg = self.env.config
-        cfg.episode_step_limit = limit
-        cfg.domain_randomization = 1
-        for k, val in (NOISE if noise else {}).items():
-            setattr(cfg, k, val)
-        self.env.config = cfg
-        v.sample_initial_parameters(device, self.env, self.params, self.rng)
-        v.sample_initial_state(device, self.env, self.params, self.state, self.rng)
-
-    def fly(self, actor, steps, mode="fused", autoreset=True, record=False, ids=None, ref=None):
-        """`steps`: a number or a list of launches; a bank flies through PolicyBank.fly.  -> the recording (dict) or None"""
-        launches = list(steps) if isinstance(steps, (list, tuple)) else [steps]
-        tr = self.vector.Trajectory(self.env, sum(launches)) if record else None
-        for s in launches:
-            if ids is not None:
-                actor.fly(self.vector, self.device, self.env, self.params, self.state, self.rng, s, ids, mode, autoreset, trajectory=tr,
-                          reference=ref)
-            else:
-                self.vector.rollout(self.device, self.env, self.params, self.state, actor, self.rng, s, mode, autoreset, trajectory=tr,
-                                    reference=ref)
-        return tr.numpy() if record else None
-
-    def snapshot(self, hidden):
-        e = self.env
-        sq, cnt = e.tracking_error()
-        return dict(state=self.state.numpy(), hidden=hidden, returns=e.returns(), steps=e.episode_steps(), rewards=e.rewards(),
-                    terminated=e.terminated(), done=e.done_codes(), frozen=e.frozen(), episode=e.episode_index(),
-                    fin_ret=e.finished_returns(), fin_len=e.finished_lengths(), fin_cnt=e.finished_counts(),
-                    fin_term=e.finished_terminated(), track_sq=sq, track_steps=cnt, epoch=np.array([self.rng.epoch], np.uint32))
-
-
-def assert_same(a, b, what=""):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.asarray(a[k]).shape == np.asarray(b[k]).shape, f"{what}: {k} shape"
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), f"{what}: {k} differs"
-
-
-def assert_same_recording(ra, rb, what=""):
-    assert np.array_equal(ra["done"], rb["done"]), f"{what}: done codes"
-    live = ra["done"] != 4
-    for k in ("obs", "act", "rew"):
-        assert np.array_equal(_bits(ra[k][live]), _bits(rb[k][live])), f"{what}: {k}"
-
-
 def differs(a, b):
-    return any(not np.array_equal(_bits(a[k]), _bits(b[k])) for k in ("state", "hidden"))
-
-
-def fly_bank(device, W, n, ids, rates=ONES, ref=None, steps=STEPS, mode="fused", autoreset=True, noise=False, record=False,
-             limit=LIMIT):
-    from raptor_amd.policy_bank import PolicyBank
-    bank = PolicyBank(device, W, native_interval=list(rates))
-    assert np.array_equal(bank.native_interval, np.asarray(rates, np.uint32))
-    b = Batch(device, n, limit=limit, noise=noise)
-    rec = b.fly(bank, steps, mode, autoreset, record, ids=ids, ref=ref)
-    return b, b.snapshot(bank.hidden(n)), rec
-
-
-def fly_slice(device, w, rate, n, offset, ref=None, steps=STEPS, mode="fused", autoreset=True, noise=False, record=False, limit=LIMIT):
-    from raptor_amd.foundation_policy import Raptor
-    pol = Raptor(device, weights=w, native_interval=int(rate))
-    b = Batch(device, n, offset=offset, limit=limit, noise=noise)
-    rec = b.fly(pol, steps, mode, autoreset, record, ref=ref)
-    return b.snapshot(pol.hidden_state(n)), rec
-
-
-def join(slices):
-    """slices' (snapshot, recording) in block order -> the batch's"""
-    snaps, recs = zip(*slices)
-    snap = {k: np.concatenate([s[k] for s in snaps]) for k in snaps[0] if k != "epoch"}
-    assert all(np.array_equal(s["epoch"], snaps[0]["epoch"]) for s in snaps)
-    snap["epoch"] = snaps[0]["epoch"]
-    rec = None if recs[0] is None else {k: np.concatenate([r[k] for r in recs], axis=1) for k in recs[0]}
-    return snap, rec
+    return any(not np.array_equal(bits(a[k]), bits(b[k])) for k in ("state", "hidden"))
 
 
 @pytest.fixture(scope="module")
@@ -158,7 +65,7 @@ def slices(device, W, ref):
     def get(rates, tracked, autoreset, noise, record):
         key = (tuple(rates), tracked, autoreset, noise, record)
         if key not in _slices:
-            _slices[key] = join([fly_slice(device, W[p], rates[p], min(64, N - 64 * g), OFFSET + 64 * g, ref=ref if tracked else None,
+            _slices[key] = join([fly_slice(device, W[p], min(64, N - 64 * g), OFFSET + 64 * g, rate=rates[p], ref=ref if tracked else None,
                                            autoreset=autoreset, noise=noise, record=record) for g, p in enumerate(BLOCK_IDS)])
         return _slices[key]
     return get
@@ -169,7 +76,7 @@ CASES = [("rate", RATES, False), ("track", ONES, True), ("both", RATES, True)]
 
 
 def crossed_episode_ends(snap, autoreset):
-    assert (snap["fin_cnt"] >= (2 if autoreset else 1)).all()
+    assert (snap["fin_counts"] >= (2 if autoreset else 1)).all()
     assert snap["frozen"].all() != autoreset
 
 
@@ -180,7 +87,7 @@ def test_rate_bank_equals_slices(device, W, slices, autoreset, noise):
     ids = ids_of(BLOCK_IDS, N)
     _, snap, _ = fly_bank(device, W, N, ids, RATES, autoreset=autoreset, noise=noise)
     want, _ = slices(RATES, False, autoreset, noise, False)
-    assert_same(snap, want, f"rate autoreset={autoreset} noise={noise}")
+    assert_same(snap, want, what=f"rate autoreset={autoreset} noise={noise}")
     assert snap["epoch"][0] == STEPS
     crossed_episode_ends(snap, autoreset)
     assert not snap["track_steps"].any()
@@ -188,8 +95,8 @@ def test_rate_bank_equals_slices(device, W, slices, autoreset, noise):
     _, plain, _ = fly_bank(device, W, N, ids, ONES, autoreset=autoreset, noise=noise)
     assert differs(snap, plain)
     own = ids == 1
-    assert np.array_equal(_bits(snap["state"][own]), _bits(plain["state"][own]))
-    assert np.array_equal(_bits(snap["hidden"][own]), _bits(plain["hidden"][own]))
+    assert np.array_equal(bits(snap["state"][own]), bits(plain["state"][own]))
+    assert np.array_equal(bits(snap["hidden"][own]), bits(plain["hidden"][own]))
     for p in (0, 2):
         assert not np.array_equal(snap["hidden"][ids == p], plain["hidden"][ids == p]), p
 
@@ -201,10 +108,10 @@ def test_track_bank_equals_slices(device, W, slices, ref, autoreset, noise):
     ids = ids_of(BLOCK_IDS, N)
     _, snap, _ = fly_bank(device, W, N, ids, ONES, ref=ref, autoreset=autoreset, noise=noise)
     want, _ = slices(ONES, True, autoreset, noise, False)
-    assert_same(snap, want, f"track autoreset={autoreset} noise={noise}")       # track_sq and track_steps among the keys
+    assert_same(snap, want, what=f"track autoreset={autoreset} noise={noise}")       # track_sq and track_steps among the keys
     crossed_episode_ends(snap, autoreset)
     # every step an env took counts: all of them under auto-reset, its one episode's without
-    assert np.array_equal(snap["track_steps"], np.full(N, STEPS, np.uint32) if autoreset else snap["fin_len"]) and (snap["track_sq"] > 0).all()
+    assert np.array_equal(snap["track_steps"], np.full(N, STEPS, np.uint32) if autoreset else snap["fin_lengths"]) and (snap["track_sq"] > 0).all()
     _, untracked, _ = fly_bank(device, W, N, ids, ONES, autoreset=autoreset, noise=noise)
     assert differs(snap, untracked)
     assert not untracked["track_steps"].any()
@@ -218,15 +125,15 @@ def test_rate_and_track_recorded(device, W, slices, ref, table, autoreset, noise
     _, snap, rec = fly_bank(device, W, N, ids, RATES, ref=ref, autoreset=autoreset, noise=noise, record=True)
     want, want_rec = slices(RATES, True, autoreset, noise, True)
     assert rec["done"].shape == (STEPS, N)
-    assert_same(snap, want, "rate + track, recorded")
+    assert_same(snap, want, what="rate + track, recorded")
     assert_same_recording(rec, want_rec, "rate + track, recorded")
     assert (rec["done"] == 2).any() and ((rec["done"] == 4).any() != autoreset)
     # recording changes nothing, and the recorded observations are setpoint-relative: another flight than rate alone records
     unrecorded, _ = slices(RATES, True, autoreset, noise, False)
-    assert_same(snap, unrecorded, "recorded against unrecorded")
+    assert_same(snap, unrecorded, what="recorded against unrecorded")
     _, _, rec_rate = fly_bank(device, W, N, ids, RATES, autoreset=autoreset, noise=noise, record=True)
     # step 0: the same states, the same noise; only the setpoint's row 0 (position 0, velocity != 0) lies between the two
-    assert np.array_equal(_bits(rec["obs"][0][:, :12]), _bits(rec_rate["obs"][0][:, :12]))
+    assert np.array_equal(bits(rec["obs"][0][:, :12]), bits(rec_rate["obs"][0][:, :12]))
     assert np.array_equal(rec["obs"][0][:, 12:15], rec_rate["obs"][0][:, 12:15] - table[0, 3:])         # (a float32 subtraction, after the noise)
     assert not np.array_equal(rec["obs"][1], rec_rate["obs"][1])
 
@@ -241,9 +148,9 @@ def test_chained_equals_fused(device, W, slices, ref, case, autoreset):
     for noise in (False, True):
         want, want_rec = slices(rates, tracked, autoreset, noise, True)
         _, snap_c, _ = fly_bank(device, W, N, ids, rates, ref=r, mode="chained", autoreset=autoreset, noise=noise)
-        assert_same(snap_c, want, f"chained noise={noise}")
+        assert_same(snap_c, want, what=f"chained noise={noise}")
         _, snap_r, rec_c = fly_bank(device, W, N, ids, rates, ref=r, mode="chained", autoreset=autoreset, noise=noise, record=True)
-        assert_same(snap_r, want, f"chained, recorded noise={noise}")
+        assert_same(snap_r, want, what=f"chained, recorded noise={noise}")
         assert_same_recording(rec_c, want_rec, f"chained noise={noise}")
 
 
@@ -257,13 +164,13 @@ def test_two_wave_build(device, W, ref):
     ids = block_policy_assignment(n, p)
     _, snap_f, _ = fly_bank(device, W[:p], n, ids, rates, ref=ref, steps=steps, limit=limit)
     _, snap_c, _ = fly_bank(device, W[:p], n, ids, rates, ref=ref, steps=steps, limit=limit, mode="chained")
-    assert_same(snap_f, snap_c, "two-wave fused against chained")
-    assert (snap_f["fin_cnt"] == 2).all() and (snap_f["track_steps"] == steps).all()
+    assert_same(snap_f, snap_c, what="two-wave fused against chained")
+    assert (snap_f["fin_counts"] == 2).all() and (snap_f["track_steps"] == steps).all()
     for g in (0, 1, 1024, 1025):
         lo, hi = 64 * g, min(64 * g + 64, n)
-        want, _ = fly_slice(device, W[ids[lo]], rates[ids[lo]], hi - lo, OFFSET + lo, ref=ref, steps=steps, limit=limit)
-        cut = {k: (v if k == "epoch" else v[lo:hi]) for k, v in snap_f.items()}
-        assert_same(cut, want, f"block {g}")
+        want, _ = fly_slice(device, W[ids[lo]], hi - lo, OFFSET + lo, rate=rates[ids[lo]], ref=ref, steps=steps, limit=limit)
+        cut = {k: v[lo:hi] for k, v in snap_f.items()}
+        assert_same(cut, want, what=f"block {g}")
 
 
 # ------------------------------------------------------------------------------ 6. two launches join -
@@ -273,7 +180,7 @@ def test_two_launches_join(device, W, slices, ref, mode):
     the tracking sums carry on"""
     _, snap, rec = fly_bank(device, W, N, ids_of(BLOCK_IDS, N), RATES, ref=ref, steps=[25, 15], mode=mode, record=True)
     want, want_rec = slices(RATES, True, True, False, True)
-    assert_same(snap, want, "25 + 15")
+    assert_same(snap, want, what="25 + 15")
     assert_same_recording(rec, want_rec, "25 + 15")
 
 
@@ -285,8 +192,8 @@ def test_uniform_bank_is_the_policy(device, W, ref, mode):
     assert list(bank.native_interval) == [4, 4, 4]
     b = Batch(device, N)
     rec = b.fly(bank, STEPS, mode, True, True, ids=np.full(N, 1, np.uint32), ref=ref)
-    want, want_rec = fly_slice(device, W[1], 4, N, OFFSET, ref=ref, mode=mode, record=True)
-    assert_same(b.snapshot(bank.hidden(N)), want, mode)
+    want, want_rec = fly_slice(device, W[1], N, OFFSET, rate=4, ref=ref, mode=mode, record=True)
+    assert_same(snapshot(b, bank.hidden(N)), want, what=mode)
     assert_same_recording(rec, want_rec, mode)
 
 
@@ -298,7 +205,7 @@ def test_evaluate_with_reference(device, W, slices, ref):
     bank = PolicyBank(device, W, native_interval=list(RATES))
     b = Batch(device, N)
     table = bank.evaluate(b.vector, device, b.env, b.params, b.state, b.rng, STEPS, ids, reference=ref)
-    assert_same(b.snapshot(bank.hidden(N)), want, "evaluate")
+    assert_same(snapshot(b, bank.hidden(N)), want, what="evaluate")
     assert table["tracking_rmse"].shape == (P,)
     for p in range(P):
         m = ids == p
@@ -341,7 +248,7 @@ def test_refusals_enqueue_nothing(device, W, ref, table):
         return w
 
     def look():
-        return dict(b.snapshot(bank.hidden(N)), intervals=intervals(), weights=bank_weights_now(), recorded=np.array([len(tr)]))
+        return dict(snapshot(b, bank.hidden(N)), intervals=intervals(), weights=bank_weights_now(), recorded=np.array([len(tr)]))
 
     def refused(name, *args):
         with pytest.raises(_lib.RaptorQuadError) as e:
@@ -381,7 +288,7 @@ def test_refusals_enqueue_nothing(device, W, ref, table):
         err = attempt()
         assert err.status == status, (what, err)
         assert words in str(err), (what, err)
-        assert_same(look(), before, what)
+        assert_same(look(), before, what=what)
     assert "policy 0 of the bank has native interval 4" in str(learn(distiller.loss_and_grad))
     # the Python surface refuses a bad interval itself; vector.rollout keeps refusing a bank's reference and names no new call
     for bad in (0, 65, [1, 2], [1, 2, 3, 4], 1.5):
@@ -389,7 +296,7 @@ def test_refusals_enqueue_nothing(device, W, ref, table):
             bank.native_interval = bad
     with pytest.raises(ValueError, match="does not track a reference"):
         b.vector.rollout(device, b.env, b.params, b.state, bank, b.rng, 5, "fused", True, policy_ids=ids, reference=ref)
-    assert_same(look(), before, "ValueError")
+    assert_same(look(), before, what="ValueError")
     assert list(bank.native_interval) == list(RATES)
     # after the refusals: a valid tracked flight at these intervals, then back at interval 1 the learner takes the bank again
     bank.fly(b.vector, device, b.env, b.params, b.state, b.rng, 5, ids, "fused", True, trajectory=tr, reference=ref)

@@ -15,13 +15,13 @@ import pytest
 
 import distill_reference as D
 import policy_grad_reference as R
-from distill_common import _ld, _perturbed, _record, forward
+from distill_common import (DEVICE, HOST, INITIAL, Opt, _adam, _ld, _lib, _perturbed, _record, _targets, distill, forward, get_weights,
+                            loss_grad, same)
 from gpu_common import World
+from rollout_common import ids_of
 
 pytestmark = pytest.mark.gpu
 
-CURRENT, INITIAL = 0, 1
-HOST, DEVICE, ASYNC = 0, 1, 2
 NW = 2084
 # Roundings the loss seed adds on a path from dL/da to a gradient element beyond policy_grad_reference.K_paths (as defined in
 # tests/test_gpu_distill.py, restated): the fp32 subtract a - y in the seeded backward and the one rounding to fp32 of acc * (2 / M)
@@ -33,73 +33,6 @@ N, T, P = 300, 20, 3
 BLOCK_IDS = [2, 0, 2, 1, 0]
 CFG = [dict(lr=2e-3, betas=(0.9, 0.999), eps=1e-8, wd=0.0), dict(lr=1e-3, betas=(0.8, 0.99), eps=1e-7, wd=0.01),
        dict(lr=5e-4, betas=(0.95, 0.9995), eps=1e-8, wd=0.0)]
-
-
-def _lib():
-    from raptor_amd import _lib as L
-    return L
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def ids_of(block_ids, n):
-    return np.ascontiguousarray(np.repeat(np.asarray(block_ids, np.uint32), 64)[:n])
-
-
-def _targets(traj, n, seed):
-    """[T, 4, ld] float32: N(0, 1) labels; NaN in the padding columns and on frozen steps"""
-    rec = traj.numpy()
-    steps, ld = len(traj), _ld(traj)
-    y = np.full((steps, 4, ld), np.nan, np.float32)
-    y[:, :, :n] = np.random.default_rng(seed).standard_normal((steps, 4, n)).astype(np.float32)
-    y[:, :, :n][np.broadcast_to((rec["done"] == 4)[:, None, :], (steps, 4, n))] = np.nan
-    return y
-
-
-def _adam(cfg):
-    return _lib().AdamConfig(cfg["lr"], cfg["betas"][0], cfg["betas"][1], cfg["eps"], cfg["wd"])
-
-
-# ---- the single-policy calls (the reference) ----
-def loss_grad(traj, pol, target):
-    L = _lib()
-    loss, g = np.empty(1, np.float32), np.empty(NW, np.float32)
-    t = np.ascontiguousarray(target, np.float32)
-    L.call("rq_trajectory_policy_loss_grad", traj._require("trajectory"), pol._handle(), L.fptr(t), t.shape[2], INITIAL, L.fptr(loss),
-           L.fptr(g), HOST)
-    return loss[0], g
-
-
-class Opt:
-    def __init__(self, pol, cfg):
-        self.cfg, self.h = _adam(cfg), C.c_void_p()
-        _lib().call("rq_optimizer_create", pol._handle(), C.byref(self.cfg), C.byref(self.h))
-
-    def close(self):
-        _lib().call("rq_optimizer_destroy", self.h)
-
-
-def distill(traj, pol, opt, n_updates, target):
-    L = _lib()
-    losses = np.empty(n_updates, np.float32)
-    t = np.ascontiguousarray(target, np.float32)
-    L.call("rq_trajectory_distill", traj._require("trajectory"), pol._handle(), opt.h, L.fptr(t), t.shape[2], INITIAL, n_updates,
-           L.fptr(losses), HOST)
-    return losses
-
-
-def get_weights(pol):
-    L = _lib()
-    w = np.empty(NW, np.float32)
-    L.call("rq_policy_get_weights", pol._handle(), L.fptr(w))
-    return w
 
 
 # ---- the bank's calls ----
@@ -206,7 +139,7 @@ def test_a_bank_of_one_is_the_distiller(device, oracle, weights, steps, n):
     l_ref, g_ref = loss_grad(traj, pol, y)
     l_bank, g_bank = bank_loss_grad(traj, bank, ids, y)
     assert same(l_bank[0], l_ref) and same(g_bank[0], g_ref) and g_ref.any()
-    opt, bopt = Opt(pol, cfg), BankOpt(bank, cfg)
+    opt, bopt = Opt(pol, **cfg), BankOpt(bank, cfg)
     ref_losses = distill(traj, pol, opt, 3, y)
     losses = bank_distill(traj, bank, bopt, ids, 3, y)
     assert losses.shape == (3, 1) and same(losses[:, 0], ref_losses)
@@ -222,7 +155,7 @@ def _single_reference(case, w, cfg, cols, updates):
     pol = Raptor(case.device, weights=w)
     pol.reset()
     loss, g = loss_grad(traj, pol, y)
-    opt = Opt(pol, cfg)
+    opt = Opt(pol, **cfg)
     losses = np.concatenate([distill(traj, pol, opt, 1, y) for _ in range(updates)])
     out = (loss, g, losses, get_weights(pol))
     opt.close()

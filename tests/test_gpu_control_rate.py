@@ -15,16 +15,13 @@ from raptor_amd import _lib
 from raptor_amd._lib import RaptorQuadError
 from raptor_amd.foundation_policy import Raptor
 from gpu_common import World
+from rollout_common import assert_same, assert_same_recording, roll, world_snapshot
 
 pytestmark = pytest.mark.gpu
 
 LIMIT = 9
 CHUNKS = (23, 7)
 KW = dict(episode_step_limit=LIMIT, termination_position=0.6)
-
-
-def _roll(w, n_steps, mode="fused", autoreset=True, **kw):
-    w.vector.rollout(w.device, w.env, w.params, w.state, w.policy, w.rng, n_steps, mode, autoreset, **kw)
 
 
 def _world(device, oracle, n, interval=None, precision="fp32", ragged=True, **over):
@@ -43,29 +40,6 @@ def _world(device, oracle, n, interval=None, precision="fp32", ragged=True, **ov
     return w
 
 
-def _snapshot(w, tracked=False):
-    e = w.env
-    snap = dict(state=w.state.numpy(), hidden=w.policy.hidden_state(w.n), returns=e.returns(), steps=e.episode_steps(),
-                fin_returns=e.finished_returns(), fin_lengths=e.finished_lengths(), fin_counts=e.finished_counts(),
-                fin_terminated=e.finished_terminated(), rewards=e.rewards(), terminated=e.terminated(), done=e.done_codes(),
-                frozen=e.frozen(), episode=e.episode_index())
-    if tracked:
-        snap["track_sq"], snap["track_steps"] = e.tracking_error()
-    return snap
-
-
-def _assert_same(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
-
-
-def _assert_same_recording(ta, tb):
-    ra, rb = ta.numpy(), tb.numpy()
-    for k in ("obs", "act", "rew", "done"):
-        assert np.array_equal(ra[k].view(np.uint8), rb[k].view(np.uint8)), k
-
-
 # ------------------------------------------------------------------ 1 -----
 @pytest.mark.parametrize("mode", ["fused", "chained"])
 def test_interval_one_is_what_it_was(device, oracle, mode):
@@ -74,14 +48,14 @@ def test_interval_one_is_what_it_was(device, oracle, mode):
     assert a.policy.native_interval == 1 and b.policy.native_interval == 1
     ta, tb = (w.vector.Trajectory(w.env, sum(CHUNKS)) for w in (a, b))
     for chunk in CHUNKS:
-        _roll(a, chunk, mode, trajectory=ta)
-        _roll(b, chunk, mode, trajectory=tb)
-    _assert_same(_snapshot(a), _snapshot(b))
-    _assert_same_recording(ta, tb)
+        roll(a, chunk, mode, trajectory=ta)
+        roll(b, chunk, mode, trajectory=tb)
+    assert_same(world_snapshot(a), world_snapshot(b))
+    assert_same_recording(ta.numpy(), tb.numpy(), frozen_too=True)
     for chunk in CHUNKS:                          # and without a recording (the chained mode's other step: observe folded in)
-        _roll(a, chunk, mode)
-        _roll(b, chunk, mode)
-    _assert_same(_snapshot(a), _snapshot(b))
+        roll(a, chunk, mode)
+        roll(b, chunk, mode)
+    assert_same(world_snapshot(a), world_snapshot(b))
     assert a.env.finished_counts().min() >= 1
 
 
@@ -132,11 +106,11 @@ def test_rollout_rule_from_one_step_rollouts(device, oracle, n, interval):
     a, b = _world(device, oracle, n, interval=interval), _world(device, oracle, n)
     tentative_seen = ended_mid_interval = 0
     for chunk in CHUNKS:
-        _roll(a, chunk, "fused")
+        roll(a, chunk, "fused")
         for _ in range(chunk):
             k = b.env.episode_steps()
             before = b.policy.hidden_state(n)
-            _roll(b, 1, "fused")
+            roll(b, 1, "fused")
             ended = b.env.done_codes() != 0
             keep = (k % interval != 0) & ~ended
             ended_mid_interval += int((ended & ((k + 1) % interval != 0)).sum())
@@ -146,7 +120,7 @@ def test_rollout_rule_from_one_step_rollouts(device, oracle, n, interval):
                 h[keep] = before[keep]
                 b.policy.set_hidden_state(h)
     assert tentative_seen > 0 and ended_mid_interval > 0
-    _assert_same(_snapshot(a), _snapshot(b))
+    assert_same(world_snapshot(a), world_snapshot(b))
     assert a.env.finished_counts().min() >= 1
 
 
@@ -158,19 +132,19 @@ def test_fused_equals_chained_equals_one_step_launches(device, oracle, precision
     a, b, c = (_world(device, oracle, n, interval=4, precision=precision, noise_position=noise) for _ in range(3))
     ta, tb, tc = (w.vector.Trajectory(w.env, sum(CHUNKS)) for w in (a, b, c))
     for chunk in CHUNKS:
-        _roll(a, chunk, "fused", trajectory=ta)
-        _roll(b, chunk, "chained", trajectory=tb)
+        roll(a, chunk, "fused", trajectory=ta)
+        roll(b, chunk, "chained", trajectory=tb)
         for _ in range(chunk):
-            _roll(c, 1, "fused", trajectory=tc)
-    sa = _snapshot(a)
-    _assert_same(sa, _snapshot(b))
-    _assert_same(sa, _snapshot(c))
-    _assert_same_recording(ta, tb)
-    _assert_same_recording(ta, tc)
+            roll(c, 1, "fused", trajectory=tc)
+    sa = world_snapshot(a)
+    assert_same(sa, world_snapshot(b))
+    assert_same(sa, world_snapshot(c))
+    assert_same_recording(ta.numpy(), tb.numpy(), frozen_too=True)
+    assert_same_recording(ta.numpy(), tc.numpy(), frozen_too=True)
     for chunk in CHUNKS:                          # unrecorded: the other fused instantiation, the chained mode's folded observe
-        _roll(a, chunk, "fused")
-        _roll(b, chunk, "chained")
-    _assert_same(_snapshot(a), _snapshot(b))
+        roll(a, chunk, "fused")
+        roll(b, chunk, "chained")
+    assert_same(world_snapshot(a), world_snapshot(b))
     assert sa["fin_counts"].min() >= 1
 
 
@@ -179,36 +153,36 @@ def test_without_autoreset_envs_freeze_and_thaw_at_phase_zero(device, oracle):
     n = 65
     a, b, c = (_world(device, oracle, n, interval=4) for _ in range(3))
     for chunk in (3, 2):                          # nobody but the displaced third has ended yet: a launch ends mid-interval
-        _roll(a, chunk, "fused", False)
-        _roll(b, chunk, "chained", False)
+        roll(a, chunk, "fused", False)
+        roll(b, chunk, "chained", False)
         for _ in range(chunk):
-            _roll(c, 1, "fused", False)
-    sa = _snapshot(a)
-    _assert_same(sa, _snapshot(b))
-    _assert_same(sa, _snapshot(c))
+            roll(c, 1, "fused", False)
+    sa = world_snapshot(a)
+    assert_same(sa, world_snapshot(b))
+    assert_same(sa, world_snapshot(c))
     frozen = sa["frozen"] != 0
     assert frozen[::3].all() and not frozen.all() and (sa["steps"][~frozen] == 5).all()
     # frozen envs add nothing and keep their hidden state: two more steps move the others only
-    _roll(a, 2, "fused", False)
-    _roll(b, 2, "chained", False)
-    s2 = _snapshot(a)
-    _assert_same(s2, _snapshot(b))
+    roll(a, 2, "fused", False)
+    roll(b, 2, "chained", False)
+    s2 = world_snapshot(a)
+    assert_same(s2, world_snapshot(b))
     assert np.array_equal(s2["hidden"][frozen], sa["hidden"][frozen]) and np.array_equal(s2["state"][frozen], sa["state"][frozen])
     assert np.array_equal(s2["fin_counts"][frozen], sa["fin_counts"][frozen]) and (s2["done"][frozen] == 4).all()
     # a later auto-reset rollout thaws the frozen ones at k = 0 while the others stand at k = 7: one step commits the thawed
     # envs' state (native) and leaves the others' alone (7 % 4 != 0)
     h_before = a.policy.hidden_state(n)
-    _roll(a, 1, "fused", True)
-    _roll(b, 1, "chained", True)
-    s3 = _snapshot(a)
-    _assert_same(s3, _snapshot(b))
+    roll(a, 1, "fused", True)
+    roll(b, 1, "chained", True)
+    s3 = world_snapshot(a)
+    assert_same(s3, world_snapshot(b))
     assert (s3["steps"][frozen] == 1).all() and (s3["steps"][~frozen] == 8).all()
     assert np.array_equal(s3["hidden"][~frozen], h_before[~frozen])
     assert (s3["hidden"][frozen] != h_before[frozen]).any(axis=1).all()
     for chunk in CHUNKS:
-        _roll(a, chunk, "fused", True)
-        _roll(b, chunk, "chained", True)
-    _assert_same(_snapshot(a), _snapshot(b))
+        roll(a, chunk, "fused", True)
+        roll(b, chunk, "chained", True)
+    assert_same(world_snapshot(a), world_snapshot(b))
 
 
 # ------------------------------------------------------------------ 5 -----
@@ -220,17 +194,17 @@ def test_with_tracking(device, oracle, precision):
     a, b, c = (_world(device, oracle, n, interval=4, precision=precision) for _ in range(3))
     ta, tb = (w.vector.Trajectory(w.env, sum(CHUNKS)) for w in (a, b))
     for chunk in CHUNKS:
-        _roll(a, chunk, "fused", reference=ref, trajectory=ta)
-        _roll(b, chunk, "chained", reference=ref, trajectory=tb)
-        _roll(c, chunk, "fused")
-    sa = _snapshot(a, tracked=True)
-    _assert_same(sa, _snapshot(b, tracked=True))
-    _assert_same_recording(ta, tb)
+        roll(a, chunk, "fused", reference=ref, trajectory=ta)
+        roll(b, chunk, "chained", reference=ref, trajectory=tb)
+        roll(c, chunk, "fused")
+    sa = world_snapshot(a)
+    assert_same(sa, world_snapshot(b))
+    assert_same_recording(ta.numpy(), tb.numpy(), frozen_too=True)
     for chunk in CHUNKS:
-        _roll(a, chunk, "fused", reference=ref)
-        _roll(b, chunk, "chained", reference=ref)
-    s2 = _snapshot(a, tracked=True)
-    _assert_same(s2, _snapshot(b, tracked=True))
+        roll(a, chunk, "fused", reference=ref)
+        roll(b, chunk, "chained", reference=ref)
+    s2 = world_snapshot(a)
+    assert_same(s2, world_snapshot(b))
     assert np.array_equal(s2["track_steps"], np.full(n, 2 * sum(CHUNKS), np.uint32)) and (s2["track_sq"] > 0).all()
     assert not np.array_equal(sa["state"], c.state.numpy())              # the setpoint moved what the policy did
 
@@ -244,15 +218,15 @@ def test_chained_graph_replay_is_keyed_by_the_interval(device, oracle):
     a.policy._handle(device)
     for seg, interval in enumerate((4, 1, 4)):
         a.policy.native_interval = interval
-        _roll(a, steps, "chained")
+        roll(a, steps, "chained")
         f = _world(device, oracle, n, ragged=False)
         f.policy._handle(device)
         for earlier in (4, 1, 4)[:seg + 1]:
             f.policy.native_interval = earlier
-            _roll(f, steps, "fused")
-        _assert_same(_snapshot(a), _snapshot(f))
+            roll(f, steps, "fused")
+        assert_same(world_snapshot(a), world_snapshot(f))
     b = _world(device, oracle, n, ragged=False)          # and the interval matters: R = 1 throughout flies another last episode
-    _roll(b, 3 * steps, "fused")
+    roll(b, 3 * steps, "fused")
     assert not np.array_equal(b.env.finished_returns(), a.env.finished_returns())
 
 
@@ -302,7 +276,7 @@ def test_refusals_name_the_interval_and_change_nothing(device, oracle):
     n, T = 65, 12
     a = _world(device, oracle, n, interval=4)
     tr = a.vector.Trajectory(a.env, T + 5)
-    _roll(a, T, "fused", trajectory=tr)
+    roll(a, T, "fused", trajectory=tr)
     pol = a.policy
     obs = np.random.default_rng(0).uniform(-1, 1, (n, 22)).astype(np.float32)
 
@@ -318,12 +292,12 @@ def test_refusals_name_the_interval_and_change_nothing(device, oracle):
     pol.evaluate_step(obs)                        # call 0 of the counter: native; the next call (index 1) is not
     w0, h0, moved0 = policy_state()               # (takes call 1; call 2 is not native either)
     assert not moved0
-    before, epoch = _snapshot(a), a.rng.epoch
+    before, epoch = world_snapshot(a), a.rng.epoch
 
     def unchanged():
         w1, h1, moved1 = policy_state()           # calls 2, 3 of the counter at the two checks that see "not native" ...
         assert np.array_equal(w1, w0) and np.array_equal(h1, h0)
-        _assert_same(before, _snapshot(a))
+        assert_same(before, world_snapshot(a))
         assert a.rng.epoch == epoch and len(tr) == T and pol.native_interval == 4
         return moved1
 
@@ -398,7 +372,7 @@ def test_it_does_something(device, oracle):
     for interval in (4, 1):
         w = World(device, oracle, n, seed=0, domain_randomization=0, init_guidance=1.0, dt=0.0025, episode_step_limit=2000)
         w.policy.native_interval = interval
-        _roll(w, 2000, "fused", False)
+        roll(w, 2000, "fused", False)
         s = w.state.numpy()
         assert np.isfinite(s).all() and np.isfinite(w.policy.hidden_state(n)).all()
         out[interval] = s

@@ -11,74 +11,17 @@ import pytest
 
 import distill_reference as D
 import policy_grad_reference as R
-from distill_common import _ld, _perturbed, _record, forward
+from distill_common import (ASYNC, DEVICE, HOST, INITIAL, Opt, _bits, _ld, _lib, _perturbed, _record, _targets, distill, forward,
+                            get_weights, loss_grad)
 from gpu_common import World
 
 pytestmark = pytest.mark.gpu
 
-CURRENT, INITIAL = 0, 1
-HOST, DEVICE, ASYNC = 0, 1, 2
 # Roundings the loss seed adds on a path from dL/da to a gradient element, beyond policy_grad_reference.K_paths, counted from the
 # kernels: the fp32 subtract a - y in k_policy_loss_backward, and the one rounding to fp32 of acc * (2 / M) in k_policy_loss_reduce.
 # That product is formed in float64 (1 / M, 2 x, the product: three roundings of 2^-53 each, together below 2^-27 of one fp32
 # rounding), carried as the fraction.
 C_SEED = 2 + 2.0 ** -27
-
-
-def _lib():
-    from raptor_amd import _lib as L
-    return L
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _targets(traj, n, seed, nan_frozen=True):
-    """[T, 4, ld] float32: N(0, 1) labels; NaN in the padding columns and on frozen steps"""
-    rec = traj.numpy()
-    T, ld = len(traj), _ld(traj)
-    y = np.full((T, 4, ld), np.nan, np.float32)
-    y[:, :, :n] = np.random.default_rng(seed).standard_normal((T, 4, n)).astype(np.float32)
-    if nan_frozen:
-        y[:, :, :n][np.broadcast_to((rec["done"] == 4)[:, None, :], (T, 4, n))] = np.nan
-    return y
-
-
-def loss_grad(traj, pol, target=None, start=INITIAL, ld=None):
-    L = _lib()
-    loss, g = np.empty(1, np.float32), np.empty(2084, np.float32)
-    t = None if target is None else np.ascontiguousarray(target, np.float32)
-    L.call("rq_trajectory_policy_loss_grad", traj._require("trajectory"), pol._handle(), None if t is None else L.fptr(t),
-           0 if t is None else (ld or t.shape[2]), start, L.fptr(loss), L.fptr(g), HOST)
-    return loss[0], g
-
-
-class Opt:
-    def __init__(self, pol, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, wd=0.0):
-        L = _lib()
-        self.cfg = L.AdamConfig(lr, betas[0], betas[1], eps, wd)
-        self.h = C.c_void_p()
-        L.call("rq_optimizer_create", pol._handle(), C.byref(self.cfg), C.byref(self.h))
-
-    def close(self):
-        _lib().call("rq_optimizer_destroy", self.h)
-
-
-def distill(traj, pol, opt, n_updates, target=None, start=INITIAL):
-    L = _lib()
-    losses = np.empty(n_updates, np.float32)
-    t = None if target is None else np.ascontiguousarray(target, np.float32)
-    L.call("rq_trajectory_distill", traj._require("trajectory"), pol._handle(), opt.h, None if t is None else L.fptr(t),
-           0 if t is None else t.shape[2], start, n_updates, L.fptr(losses), HOST)
-    return losses
-
-
-def get_weights(pol):
-    L = _lib()
-    w = np.empty(2084, np.float32)
-    L.call("rq_policy_get_weights", pol._handle(), L.fptr(w))
-    return w
 
 
 CASES = [(1, 1), (37, 16), (2, 63), (1, 65), (500, 1000), (37, 65536)]

@@ -9,107 +9,14 @@ code != 4: the steps an env sat out frozen are never written by the fused kernel
 import numpy as np
 import pytest
 
+from rollout_common import (OFFSET, STEPS, Batch, assert_same, assert_same_recording, bank_weights, bits, fly_bank, fly_slice, ids_of,
+                            join, snapshot)
+
 pytestmark = pytest.mark.gpu
-
-OFFSET = 1000                  # global id of the bank batch's env 0
-LIMIT = 16                     # episode_step_limit: 40 steps cross two episode ends per env
-STEPS = 40
-NOISE = dict(noise_position=0.01, noise_orientation=0.005, noise_linear_velocity=0.02, noise_angular_velocity=0.01)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint8)
-
-
-def bank_weights(weights, n_policies):
-    """policy k = the shipped weights + 0.05 * default_rng(100 + k).standard_normal(2084), float32"""
-    return np.stack([weights + np.float32(0.05) * np.random.default_rng(100 + k).standard_normal(2084).astype(np.float32)
-                     for k in range(n_policies)]).astype(np.float32)
-
-
-class Batch:
-    """The l2f-shaped objects of one batch on the GPU: domain randomisation on, seed 3."""
-
-    def __init__(self, device, n, offset=OFFSET, limit=LIMIT, noise=False):
-        import raptor_amd.l2f as l2f
-        self.device, self.n = device, n
-        self.vector = v = l2f.VectorModule(n, offset)
-        self.rng, self.env, self.params, self.state = v.VectorRng(), v.VectorEnvironment(), v.VectorParameters(), v.VectorState()
-        v.initialize_rng(device, self.rng, 3)
-        v.initialize_environment(device, self.env)
-        cfg = self.env.config
-        cfg.episode_step_limit = limit
-        cfg.domain_randomization = 1
-        for k, val in (NOISE if noise else {}).items():
-            setattr(cfg, k, val)
-        self.env.config = cfg
-        v.sample_initial_parameters(device, self.env, self.params, self.rng)
-        v.sample_initial_state(device, self.env, self.params, self.state, self.rng)
-
-    def fly(self, actor, steps, mode="fused", autoreset=True, record=False, ids=None):
-        """`steps`: a number or a list of launches.  -> the recording (dict) or None"""
-        launches = list(steps) if isinstance(steps, (list, tuple)) else [steps]
-        tr = self.vector.Trajectory(self.env, sum(launches)) if record else None
-        for s in launches:
-            self.vector.rollout(self.device, self.env, self.params, self.state, actor, self.rng, s, mode, autoreset, trajectory=tr,
-                                policy_ids=ids)
-        return tr.numpy() if record else None
-
-    def snapshot(self, hidden):
-        e = self.env
-        return dict(state=self.state.numpy(), hidden=hidden, returns=e.returns(), steps=e.episode_steps(), rewards=e.rewards(),
-                    terminated=e.terminated(), done=e.done_codes(), frozen=e.frozen(), episode=e.episode_index(),
-                    fin_ret=e.finished_returns(), fin_len=e.finished_lengths(), fin_cnt=e.finished_counts(),
-                    fin_term=e.finished_terminated(), epoch=np.array([self.rng.epoch], np.uint32))
-
-
-def assert_same(a, b, what=""):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.asarray(a[k]).shape == np.asarray(b[k]).shape, f"{what}: {k} shape"
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), f"{what}: {k} differs"
-
-
-def assert_same_recording(ra, rb, what=""):
-    assert np.array_equal(ra["done"], rb["done"]), f"{what}: done codes"
-    live = ra["done"] != 4
-    for k in ("obs", "act", "rew"):
-        assert np.array_equal(_bits(ra[k][live]), _bits(rb[k][live])), f"{what}: {k}"
-
-
-def fly_bank(device, W, n, ids, steps=STEPS, mode="fused", autoreset=True, noise=False, record=False, limit=LIMIT, bank=None):
-    from raptor_amd.policy_bank import PolicyBank
-    bank = bank if bank is not None else PolicyBank(device, W)
-    b = Batch(device, n, limit=limit, noise=noise)
-    rec = b.fly(bank, steps, mode, autoreset, record, ids=ids)
-    return b, b.snapshot(bank.hidden(n)), rec
-
-
-def fly_slice(device, w, n, offset, steps=STEPS, mode="fused", autoreset=True, noise=False, record=False, limit=LIMIT):
-    from raptor_amd.foundation_policy import Raptor
-    pol = Raptor(device, weights=w)
-    b = Batch(device, n, offset=offset, limit=limit, noise=noise)
-    rec = b.fly(pol, steps, mode, autoreset, record)
-    return b.snapshot(pol.hidden_state(n)), rec
-
-
-def join(slices):
-    """slices' (snapshot, recording) in block order -> the batch's"""
-    snaps, recs = zip(*slices)
-    snap = {k: np.concatenate([s[k] for s in snaps]) for k in snaps[0] if k != "epoch"}
-    assert all(np.array_equal(s["epoch"], snaps[0]["epoch"]) for s in snaps)
-    snap["epoch"] = snaps[0]["epoch"]
-    rec = None if recs[0] is None else {k: np.concatenate([r[k] for r in recs], axis=1) for k in recs[0]}
-    return snap, rec
-
 
 # N = 200: three full blocks and a ragged one of 8; a non-monotone assignment with a policy reused on non-adjacent blocks
 N, P = 200, 3
 BLOCK_IDS = [2, 0, 2, 1]
-
-
-def ids_of(block_ids, n):
-    return np.repeat(np.asarray(block_ids, np.uint32), 64)[:n]
 
 
 @pytest.fixture(scope="module")
@@ -145,9 +52,9 @@ def slices(device, W):
 def test_bank_equals_slices_fused(device, W, slices, autoreset, noise):
     _, snap, _ = fly_bank(device, W[:P], N, ids_of(BLOCK_IDS, N), autoreset=autoreset, noise=noise)
     ref, _ = slices(autoreset, noise, False)
-    assert_same(snap, ref, f"autoreset={autoreset} noise={noise}")
+    assert_same(snap, ref, what=f"autoreset={autoreset} noise={noise}")
     assert snap["epoch"][0] == STEPS
-    assert (snap["fin_cnt"] >= (2 if autoreset else 1)).all()          # episode ends were crossed
+    assert (snap["fin_counts"] >= (2 if autoreset else 1)).all()          # episode ends were crossed
     assert snap["frozen"].all() != autoreset
 
 
@@ -158,7 +65,7 @@ def test_bank_recording_equals_slices(device, W, slices, autoreset, noise):
     _, snap, rec = fly_bank(device, W[:P], N, ids_of(BLOCK_IDS, N), autoreset=autoreset, noise=noise, record=True)
     ref, ref_rec = slices(autoreset, noise, True)
     assert rec["done"].shape == (STEPS, N)
-    assert_same(snap, ref, "recorded")
+    assert_same(snap, ref, what="recorded")
     assert_same_recording(rec, ref_rec, "recorded")
     assert (rec["done"] == 2).any() and ((rec["done"] == 4).any() != autoreset)
 
@@ -170,12 +77,12 @@ def test_bank_fused_equals_chained(device, W, slices, autoreset, noise):
     ids = ids_of(BLOCK_IDS, N)
     _, snap_c, _ = fly_bank(device, W[:P], N, ids, mode="chained", autoreset=autoreset, noise=noise)
     ref, ref_rec = slices(autoreset, noise, True)
-    assert_same(snap_c, ref, "chained")
+    assert_same(snap_c, ref, what="chained")
     _, snap_r, rec_c = fly_bank(device, W[:P], N, ids, mode="chained", autoreset=autoreset, noise=noise, record=True)
-    assert_same(snap_r, ref, "chained, recorded")
+    assert_same(snap_r, ref, what="chained, recorded")
     assert_same_recording(rec_c, ref_rec, "chained")
     _, snap_f, rec_f = fly_bank(device, W[:P], N, ids, mode="fused", autoreset=autoreset, noise=noise, record=True)
-    assert_same(snap_f, snap_r, "fused against chained")
+    assert_same(snap_f, snap_r, what="fused against chained")
     assert_same_recording(rec_f, rec_c, "fused against chained")
 
 
@@ -192,16 +99,16 @@ def test_thaw_takes_each_policys_initial_state(device, W):
         b = Batch(device, min(64, N - 64 * g), offset=OFFSET + 64 * g)
         b.fly(pol, 20, autoreset=False)
         b.fly(pol, 5, autoreset=True)
-        thawed.append((b.snapshot(pol.hidden_state(b.n)), None))
+        thawed.append((snapshot(b, pol.hidden_state(b.n)), None))
     ref2, _ = join(thawed)
     for mode in ("fused", "chained"):
         from raptor_amd.policy_bank import PolicyBank
         bank = PolicyBank(device, W[:P])
         b = Batch(device, N)
         b.fly(bank, 20, mode, autoreset=False, ids=ids)
-        assert_same(b.snapshot(bank.hidden(N)), ref, f"{mode}: frozen")
+        assert_same(snapshot(b, bank.hidden(N)), ref, what=f"{mode}: frozen")
         b.fly(bank, 5, mode, autoreset=True, ids=ids)
-        assert_same(b.snapshot(bank.hidden(N)), ref2, f"{mode}: thawed")
+        assert_same(snapshot(b, bank.hidden(N)), ref2, what=f"{mode}: thawed")
         assert not b.env.frozen().any()
 
 
@@ -211,7 +118,7 @@ def test_thaw_takes_each_policys_initial_state(device, W):
 def test_one_id_everywhere_is_the_single_policy_rollout(device, W, n, mode):
     _, snap, rec = fly_bank(device, W[:P], n, np.full(n, 1, np.uint32), mode=mode, record=True)
     ref, ref_rec = fly_slice(device, W[1], n, OFFSET, mode=mode, record=True)
-    assert_same(snap, ref, f"n={n} {mode}")
+    assert_same(snap, ref, what=f"n={n} {mode}")
     assert_same_recording(rec, ref_rec, f"n={n} {mode}")
 
 
@@ -224,13 +131,13 @@ def test_two_wave_build(device, W):
     ids = block_policy_assignment(n, p)
     _, snap_f, _ = fly_bank(device, W[:p], n, ids, steps=steps, limit=limit)
     _, snap_c, _ = fly_bank(device, W[:p], n, ids, steps=steps, limit=limit, mode="chained")
-    assert_same(snap_f, snap_c, "two-wave fused against chained")
-    assert (snap_f["fin_cnt"] == 2).all()
+    assert_same(snap_f, snap_c, what="two-wave fused against chained")
+    assert (snap_f["fin_counts"] == 2).all()
     for g in (0, 1024, 1025):
         lo, hi = 64 * g, min(64 * g + 64, n)
         ref, _ = fly_slice(device, W[ids[lo]], hi - lo, OFFSET + lo, steps=steps, limit=limit)
-        cut = {k: (v if k == "epoch" else v[lo:hi]) for k, v in snap_f.items()}
-        assert_same(cut, ref, f"block {g}")
+        cut = {k: v[lo:hi] for k, v in snap_f.items()}
+        assert_same(cut, ref, what=f"block {g}")
 
 
 # ------------------------------------------------------------------------------ 6. two launches join -
@@ -238,7 +145,7 @@ def test_two_wave_build(device, W):
 def test_two_launches_join(device, W, slices, mode):
     _, snap, rec = fly_bank(device, W[:P], N, ids_of(BLOCK_IDS, N), steps=[20, 20], mode=mode, record=True)
     ref, ref_rec = slices(True, False, True)
-    assert_same(snap, ref, "2 x 20")
+    assert_same(snap, ref, what="2 x 20")
     assert_same_recording(rec, ref_rec, "2 x 20")
 
 
@@ -254,17 +161,17 @@ def test_set_weights_and_reset(device, W):
     _, snap_a, _ = fly_bank(device, None, N, ids, bank=bank)
     _, snap_b, _ = fly_bank(device, W2, N, ids)
     _, snap_0, _ = fly_bank(device, W[:P], N, ids)
-    assert_same(snap_a, snap_b, "set_weights")
+    assert_same(snap_a, snap_b, what="set_weights")
     blk = slice(192, 200)                                           # the block policy 1 flies
     assert not np.array_equal(snap_a["state"][blk], snap_0["state"][blk])
-    assert np.array_equal(_bits(snap_a["state"][:192]), _bits(snap_0["state"][:192]))
+    assert np.array_equal(bits(snap_a["state"][:192]), bits(snap_0["state"][:192]))
     h0 = W2[ids][:, 2000:2016]
-    assert not np.array_equal(_bits(bank.hidden(N)), _bits(h0))
+    assert not np.array_equal(bits(bank.hidden(N)), bits(h0))
     bank.reset()
-    assert np.array_equal(_bits(bank.hidden(N)), _bits(h0))
+    assert np.array_equal(bits(bank.hidden(N)), bits(h0))
     # ... and a rollout after reset() starts from it: a fresh batch flown by the used bank equals one flown by a new bank
     _, snap_c, _ = fly_bank(device, None, N, ids, bank=bank)
-    assert_same(snap_c, snap_b, "after reset")
+    assert_same(snap_c, snap_b, what="after reset")
 
 
 # ------------------------------------------------------------------------------ 8. refusals -
@@ -300,19 +207,19 @@ def test_refusals_leave_everything_untouched(device, W):
              ("trajectory without room", dict(steps=7), -1, "too small"),
              ("unknown mode", dict(mode=7), -1, "unknown mode"),
              ("unknown flag", dict(flags=2), -1, "unknown flags")]
-    before = b.snapshot(bank.hidden(N))
+    before = snapshot(b, bank.hidden(N))
     for mode in (_lib.ROLLOUT_FUSED, _lib.ROLLOUT_CHAINED):
         for what, kw, status, words in cases:
             err = call(**dict(dict(mode=mode), **kw))
             assert err.status == status, (what, err)
             assert words in str(err), (what, err)
-            assert_same(b.snapshot(bank.hidden(N)), before, what)
+            assert_same(snapshot(b, bank.hidden(N)), before, what=what)
             assert len(tr) == 4 and len(tr_other) == 0, what
     # the Python surface refuses the two id errors itself, before the library is called
     for bad in (too_big, split, ids[:-1]):
         with pytest.raises(ValueError):
             b.vector.rollout(device, b.env, b.params, b.state, bank, b.rng, 5, "fused", True, policy_ids=bad)
-    assert_same(b.snapshot(bank.hidden(N)), before, "ValueError")
+    assert_same(snapshot(b, bank.hidden(N)), before, what="ValueError")
 
 
 # ------------------------------------------------------------------------------ 9. the per-policy table -
@@ -325,12 +232,12 @@ def test_policy_episode_table(device, W, slices):
     for p in range(P):
         m = ids == p
         assert table["envs"][p] == m.sum()
-        assert table["episodes"][p] == ref["fin_cnt"][m].sum()
-        r = ref["fin_ret"][m].astype(np.float64)
+        assert table["episodes"][p] == ref["fin_counts"][m].sum()
+        r = ref["fin_returns"][m].astype(np.float64)
         assert np.isclose(table["mean_return"][p], r.mean(), rtol=1e-12)
         assert np.isclose(table["std_return"][p], r.std(), rtol=1e-9)
-        assert np.isclose(table["mean_length"][p], ref["fin_len"][m].astype(np.float64).mean(), rtol=1e-12)
-        assert np.isclose(table["termination_share"][p], ref["fin_term"][m].sum() / ref["fin_cnt"][m].sum(), rtol=1e-12)
+        assert np.isclose(table["mean_length"][p], ref["fin_lengths"][m].astype(np.float64).mean(), rtol=1e-12)
+        assert np.isclose(table["termination_share"][p], ref["fin_terminated"][m].sum() / ref["fin_counts"][m].sum(), rtol=1e-12)
     bank = PolicyBank(device, W[:P])
     fresh = Batch(device, N)
     again = bank.evaluate(fresh.vector, device, fresh.env, fresh.params, fresh.state, fresh.rng, STEPS, ids)

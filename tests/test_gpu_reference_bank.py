@@ -12,6 +12,8 @@ import raptor_amd.l2f as l2f
 from raptor_amd import _lib
 from raptor_amd._lib import RaptorQuadError
 from gpu_common import World
+from rollout_common import (assert_same, assert_same_recording, bank_weights, bits, push, random_table, roll, snapshot,
+                            world_snapshot)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,14 +23,6 @@ M = 3
 KW = dict(seed=5, episode_step_limit=LIMIT, termination_position=0.6)
 
 
-def _table(rows, seed=1):
-    """Entries of order 0.1 m and 0.1 m/s, different in every row."""
-    g = np.random.default_rng(seed)
-    t = (0.1 * g.uniform(-1.0, 1.0, (rows, 6))).astype(np.float32)
-    assert len({r.tobytes() for r in t}) == rows
-    return t
-
-
 def _ids(n, shift=0):
     """every wave holds all three ids and neighbouring lanes differ"""
     return ((np.arange(n) * 7 + 1 + shift) % M).astype(np.uint32)
@@ -36,7 +30,7 @@ def _ids(n, shift=0):
 
 @pytest.fixture(scope="module")
 def tables():
-    t = np.stack([_table(LIMIT, 11 + r) for r in range(M)])
+    t = np.stack([random_table(LIMIT, 11 + r) for r in range(M)])
     assert len({r.tobytes() for r in t.reshape(-1, 6)}) == M * LIMIT
     t.setflags(write=False)
     return t
@@ -54,44 +48,12 @@ def refs(device, tables):
     return [l2f.Reference(device, np.array(tables[r])) for r in range(M)]
 
 
-def _roll(w, n_steps, mode="fused", autoreset=True, **kw):
-    w.vector.rollout(w.device, w.env, w.params, w.state, w.policy, w.rng, n_steps, mode, autoreset, **kw)
-
-
-def _snapshot(w, hidden=None):
-    e = w.env
-    sq, steps = e.tracking_error()
-    return dict(state=w.state.numpy(), hidden=w.policy.hidden_state(w.n) if hidden is None else hidden, returns=e.returns(),
-                steps=e.episode_steps(), fin_returns=e.finished_returns(), fin_lengths=e.finished_lengths(),
-                fin_counts=e.finished_counts(), fin_terminated=e.finished_terminated(), rewards=e.rewards(),
-                terminated=e.terminated(), done=e.done_codes(), frozen=e.frozen(), episode=e.episode_index(), track_sq=sq,
-                track_steps=steps, epoch=np.full(w.n, w.rng.epoch, np.uint32))
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint8)
-
-
-def _assert_same(a, b, rows=slice(None), what=""):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert np.array_equal(_bits(a[k][rows]), _bits(b[k][rows])), f"{what}: {k}"
-
-
-def _push(w, which):
-    """a third of the envs (which, which + 3, ...) goes outside termination_position: it terminates at its next step and flies its
-    following episodes out of phase with the rest"""
-    s = w.state.numpy()
-    s[which::3, 0] = 0.7
-    w.state.set(s)
-
-
-def _fly(w, roll, chunks=CHUNKS, pushes=True):
+def _fly(w, launch, chunks=CHUNKS, pushes=True):
     """the launches of every world of this file: a push before each of the first two (the same in every world)"""
     for j, chunk in enumerate(chunks):
         if pushes and j < 2:
-            _push(w, j)
-        roll(w, chunk)
+            push(w, j)
+        launch(w, chunk)
 
 
 def _ragged(w, ids):
@@ -114,8 +76,8 @@ def _single_reference_worlds(device, oracle, refs, n, precision, autoreset, nois
             b = World(device, oracle, n, noise_position=noise, **KW)
             b.policy.set_precision(precision)
             b.policy.native_interval = interval
-            _fly(b, lambda w, c: _roll(w, c, "fused", autoreset, reference=refs[r]), chunks)
-            out.append(_snapshot(b))
+            _fly(b, lambda w, c: roll(w, c, "fused", autoreset, reference=refs[r]), chunks)
+            out.append(world_snapshot(b))
         _singles[key] = out
     return _singles[key]
 
@@ -123,7 +85,7 @@ def _single_reference_worlds(device, oracle, refs, n, precision, autoreset, nois
 def _assert_slices(snap, singles, ids, what=""):
     for r in range(M):
         if (ids == r).any():
-            _assert_same(snap, singles[r], ids == r, f"{what} reference {r}")
+            assert_same(snap, singles[r], rows=ids == r, what=f"{what} reference {r}")
 
 
 # ------------------------------------------------------------------ 1 -----
@@ -139,8 +101,8 @@ def test_slices_equal_single_references(device, oracle, bank, refs, n, precision
     for mode in ("fused", "chained"):
         a = World(device, oracle, n, noise_position=noise, **KW)
         a.policy.set_precision(precision)
-        _fly(a, lambda w, c: _roll(w, c, mode, autoreset, reference=bank, reference_ids=ids))
-        snap = _snapshot(a)
+        _fly(a, lambda w, c: roll(w, c, mode, autoreset, reference=bank, reference_ids=ids))
+        snap = world_snapshot(a)
         _assert_slices(snap, singles, ids, f"{mode} n={n} {precision} autoreset={autoreset} noise={noise}")
         assert snap["fin_counts"].min() >= 1
         assert snap["epoch"][0] == sum(CHUNKS)
@@ -163,9 +125,9 @@ def test_one_table_is_the_reference(device, oracle, tables, refs, mode):
     one = l2f.ReferenceBank(device, [np.array(tables[1])])           # the list form
     assert (one.n_references, one.rows) == (1, LIMIT)
     a, b = World(device, oracle, n, **KW), World(device, oracle, n, **KW)
-    _fly(a, lambda w, c: _roll(w, c, mode, reference=one, reference_ids=np.zeros(n, np.int64)))
-    _fly(b, lambda w, c: _roll(w, c, mode, reference=refs[1]))
-    _assert_same(_snapshot(a), _snapshot(b), what=mode)
+    _fly(a, lambda w, c: roll(w, c, mode, reference=one, reference_ids=np.zeros(n, np.int64)))
+    _fly(b, lambda w, c: roll(w, c, mode, reference=refs[1]))
+    assert_same(world_snapshot(a), world_snapshot(b), what=mode)
     assert a.env.finished_counts().min() >= 1
 
 
@@ -182,19 +144,20 @@ def test_recording_and_distiller(device, oracle, bank, refs):
     for mode in ("fused", "chained"):
         a = World(device, oracle, n, **KW)
         ta = a.vector.Trajectory(a.env, T)
-        _fly(a, lambda w, c: _roll(w, c, mode, trajectory=ta, reference=bank, reference_ids=ids))
+        _fly(a, lambda w, c: roll(w, c, mode, trajectory=ta, reference=bank, reference_ids=ids))
         ra = ta.numpy()
         singles, trajs = [], []
         for r in range(M):
             b = World(device, oracle, n, **KW)
             tb = b.vector.Trajectory(b.env, T)
-            _fly(b, lambda w, c: _roll(w, c, mode, trajectory=tb, reference=refs[r]))
+            _fly(b, lambda w, c: roll(w, c, mode, trajectory=tb, reference=refs[r]))
             rb = tb.numpy()
-            for k in ("obs", "act", "rew", "done"):
-                assert np.array_equal(_bits(ra[k][:, ids == r]), _bits(rb[k][:, ids == r])), (mode, k, r)
-            singles.append(_snapshot(b))
+            own = ids == r
+            assert_same_recording({k: v[:, own] for k, v in ra.items()}, {k: v[:, own] for k, v in rb.items()},
+                                  f"{mode} reference {r}", frozen_too=True)
+            singles.append(world_snapshot(b))
             trajs.append((b, tb))
-        _assert_slices(_snapshot(a), singles, ids, mode)
+        _assert_slices(world_snapshot(a), singles, ids, mode)
         assert (ra["done"] == 1).any() and (ra["done"] == 2).any()
         # the joined recording, made in trajectory 0 from the others' columns
         joined = trajs[0][1]
@@ -205,14 +168,12 @@ def test_recording_and_distiller(device, oracle, bank, refs):
             for k in views:
                 views[k].index_copy_(views[k].dim() - 1, cols, src[k].index_select(src[k].dim() - 1, cols))
         torch.cuda.synchronize()
-        rj = joined.numpy()
-        for k in ("obs", "act", "rew", "done"):
-            assert np.array_equal(_bits(rj[k]), _bits(ra[k])), (mode, k)
+        assert_same_recording(joined.numpy(), ra, what=f"{mode} joined", frozen_too=True)
         target = torch.zeros((T, 4, n), dtype=torch.float32, device=views["obs"].device)
         loss_a = Distiller(Raptor(device), lr=1e-3).step(ta, target=target)
         loss_j = Distiller(Raptor(device), lr=1e-3).step(joined, target=target)
         la, lj = np.asarray(loss_a.cpu()), np.asarray(loss_j.cpu())
-        assert np.isfinite(la).all() and la[0] > 0 and np.array_equal(_bits(la), _bits(lj)), (mode, la, lj)
+        assert np.isfinite(la).all() and la[0] > 0 and np.array_equal(bits(la), bits(lj)), (mode, la, lj)
 
 
 # ------------------------------------------------------------------ 4 -----
@@ -223,24 +184,19 @@ def test_native_interval(device, oracle, bank, refs, n):
     for mode in ("fused", "chained"):
         a = World(device, oracle, n, **KW)
         a.policy.native_interval = 4
-        _fly(a, lambda w, c: _roll(w, c, mode, reference=bank, reference_ids=ids))
-        _assert_slices(_snapshot(a), singles, ids, f"{mode} n={n} interval 4")
+        _fly(a, lambda w, c: roll(w, c, mode, reference=bank, reference_ids=ids))
+        _assert_slices(world_snapshot(a), singles, ids, f"{mode} n={n} interval 4")
     plain = _single_reference_worlds(device, oracle, refs, n, "fp32", True, 0.0)
     assert not np.array_equal(plain[0]["hidden"], singles[0]["hidden"])           # the interval is not a no-op
 
 
 # ------------------------------------------------------------------ 5 -----
-def _bank_weights(weights, n_policies):
-    return np.stack([weights + np.float32(0.05) * np.random.default_rng(100 + k).standard_normal(2084).astype(np.float32)
-                     for k in range(n_policies)]).astype(np.float32)
-
-
 def test_policy_bank(device, oracle, weights, bank, refs):
     """192 envs, three blocks, two policies at intervals (1, 4), reference ids per lane"""
     from raptor_amd.policy_bank import PolicyBank
     from raptor_amd.tracking import reference_tracking_table
     n, P = 192, 2
-    W = _bank_weights(weights, P)
+    W = bank_weights(weights, P)
     pids = np.repeat(np.array([1, 0, 1], np.uint32), 64)
     ids = _ids(n)
 
@@ -248,7 +204,7 @@ def test_policy_bank(device, oracle, weights, bank, refs):
         w = World(device, oracle, n, **KW)
         pb = PolicyBank(device, W, native_interval=[1, 4])
         _fly(w, lambda w_, c: pb.fly(w_.vector, device, w_.env, w_.params, w_.state, w_.rng, c, pids, mode, True, **kw))
-        return w, _snapshot(w, pb.hidden(n))
+        return w, snapshot(w, pb.hidden(n))
 
     for mode in ("fused", "chained"):
         singles = [fly(mode, reference=refs[r])[1] for r in range(M)]
@@ -279,20 +235,20 @@ def test_graph_replay_follows_the_ids(device, oracle, tables):
     """From 25 steps on the chained mode replays a cached hipGraph: the same bank with other ids must not fly the old ones"""
     n, limit = 65, 30
     kw = dict(seed=6, episode_step_limit=limit, termination_position=0.6)
-    big = l2f.ReferenceBank(device, np.stack([_table(limit, 21 + r) for r in range(M)]))
+    big = l2f.ReferenceBank(device, np.stack([random_table(limit, 21 + r) for r in range(M)]))
     a = World(device, oracle, n, **kw)
     fresh = World(device, oracle, n, **kw)              # the same history, launch for launch, never through a graph
     for shift in (0, 1, 0):
         ids = _ids(n, shift)
-        _roll(a, 27, "chained", reference=big, reference_ids=ids)
-        _roll(fresh, 27, "fused", reference=big, reference_ids=ids)
-        _assert_same(_snapshot(a), _snapshot(fresh), what=f"shift {shift}")
+        roll(a, 27, "chained", reference=big, reference_ids=ids)
+        roll(fresh, 27, "fused", reference=big, reference_ids=ids)
+        assert_same(world_snapshot(a), world_snapshot(fresh), what=f"shift {shift}")
     assert a.env.finished_counts().min() >= 1
     # not vacuous: the second run with the first run's ids is another flight
     stale = World(device, oracle, n, **kw)
     for shift in (0, 0, 0):
-        _roll(stale, 27, "fused", reference=big, reference_ids=_ids(n, shift))
-    assert not np.array_equal(_snapshot(stale)["state"], _snapshot(a)["state"])
+        roll(stale, 27, "fused", reference=big, reference_ids=_ids(n, shift))
+    assert not np.array_equal(world_snapshot(stale)["state"], world_snapshot(a)["state"])
 
 
 # ------------------------------------------------------------------ 7 -----
@@ -301,15 +257,15 @@ def test_refusals_enqueue_nothing(device, oracle, weights, tables, bank):
     n = 128
     ids = _ids(n)
     a = World(device, oracle, n, **KW)
-    _roll(a, 3, "fused", reference=bank, reference_ids=ids)
+    roll(a, 3, "fused", reference=bank, reference_ids=ids)
     tr = a.vector.Trajectory(a.env, 10)
-    _roll(a, 2, "fused", trajectory=tr, reference=bank, reference_ids=ids)
-    pb = PolicyBank(device, _bank_weights(weights, 2))
+    roll(a, 2, "fused", trajectory=tr, reference=bank, reference_ids=ids)
+    pb = PolicyBank(device, bank_weights(weights, 2))
     pids = np.repeat(np.array([1, 0], np.uint32), 64)
     pb.fly(a.vector, device, a.env, a.params, a.state, a.rng, 2, pids, reference=bank, reference_ids=ids)
 
     def look():
-        return dict(_snapshot(a), bank_hidden=pb.hidden(n), recorded=np.full(n, len(tr)), recording=tr.numpy()["obs"].transpose(1, 0, 2))
+        return dict(world_snapshot(a), bank_hidden=pb.hidden(n), recorded=np.full(n, len(tr)), recording=tr.numpy()["obs"].transpose(1, 0, 2))
 
     before, epoch = look(), a.rng.epoch
     assert epoch == 7 and len(tr) == 2
@@ -349,12 +305,12 @@ def test_refusals_enqueue_nothing(device, oracle, weights, tables, bank):
         err = attempt(who, mode, **kw)
         assert err.status == status, (who, mode, what, err)
         assert words in str(err), (who, mode, what, err)
-        _assert_same(look(), before, what=f"{who} {mode} {what}")
+        assert_same(look(), before, what=f"{who} {mode} {what}")
         assert a.rng.epoch == epoch, what
     a.policy.set_sample_and_squash("mean")
     for mode in (_lib.ROLLOUT_FUSED, _lib.ROLLOUT_CHAINED):
         assert "SampleAndSquash" in str(attempt("policy", mode))
-        _assert_same(look(), before, what="SampleAndSquash")
+        assert_same(look(), before, what="SampleAndSquash")
     a.policy.set_sample_and_squash("off")
     # creation: refused before the device is touched
     h = C.c_void_p()
@@ -369,9 +325,9 @@ def test_refusals_enqueue_nothing(device, oracle, weights, tables, bank):
     # a teacher bank still does not track (the Python surface says so before any call)
     with pytest.raises(ValueError, match="teacher_ids"):
         a.vector.rollout(device, a.env, a.params, a.state, a.policy, a.rng, 5, reference=bank, reference_ids=ids, teacher_ids=ids)
-    _assert_same(look(), before, what="after everything")
+    assert_same(look(), before, what="after everything")
     assert a.rng.epoch == epoch
-    _roll(a, 3, "fused", reference=bank, reference_ids=ids)          # and it still flies
+    roll(a, 3, "fused", reference=bank, reference_ids=ids)          # and it still flies
     assert a.rng.epoch == epoch + 3
 
 
@@ -383,8 +339,8 @@ def test_two_launches_join(device, oracle, bank, mode):
     ids = _ids(n)
     a, b = World(device, oracle, n, **KW), World(device, oracle, n, **KW)
     for w in (a, b):
-        _push(w, 0)
-    _fly(a, lambda w, c: _roll(w, c, mode, reference=bank, reference_ids=ids), pushes=False)
-    _fly(b, lambda w, c: _roll(w, c, mode, reference=bank, reference_ids=ids), chunks=(sum(CHUNKS),), pushes=False)
-    _assert_same(_snapshot(a), _snapshot(b), what=mode)
+        push(w, 0)
+    _fly(a, lambda w, c: roll(w, c, mode, reference=bank, reference_ids=ids), pushes=False)
+    _fly(b, lambda w, c: roll(w, c, mode, reference=bank, reference_ids=ids), chunks=(sum(CHUNKS),), pushes=False)
+    assert_same(world_snapshot(a), world_snapshot(b), what=mode)
     assert a.env.finished_counts().min() >= 1 and len(np.unique(a.env.episode_steps()[:64])) >= 2

@@ -6,6 +6,7 @@ import pytest
 
 import teacher_reference as R
 from gpu_common import World
+from rollout_common import assert_same, assert_same_recording, bits, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -27,39 +28,12 @@ def _bank(device, W, in_dim, widths, act="relu", out_act="tanh", precision="fp32
     return TeacherBank.from_layers(device, W, in_dim, widths, act, out_act, precision)
 
 
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint8)
-
-
-def _snapshot(w):
-    e = w.env
-    return dict(state=w.state.numpy().copy(), returns=e.returns(), steps=e.episode_steps(), rewards=e.rewards(),
-                terminated=e.terminated(), done=e.done_codes(), frozen=e.frozen(), episode=e.episode_index(),
-                fin_ret=e.finished_returns(), fin_len=e.finished_lengths(), fin_cnt=e.finished_counts(),
-                fin_term=e.finished_terminated(), epoch=None)
-
-
-def _assert_same(a, b, what=""):
-    for k in a:
-        if a[k] is None:
-            continue
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), f"{what}: {k} differs"
-
-
 def _fly(device, oracle, n, bank, ids, mode, steps, autoreset, seed=7, record=True, chunks=None, **cfg):
     w = World(device, oracle, n, seed=seed, **cfg)
     tr = w.vector.Trajectory(w.env, sum(steps) if isinstance(steps, (list, tuple)) else steps) if record else None
     for s in (steps if isinstance(steps, (list, tuple)) else [steps]):
         w.vector.rollout(device, w.env, w.params, w.state, bank, w.rng, s, mode, autoreset, trajectory=tr, teacher_ids=ids)
     return w, tr
-
-
-def _assert_same_recording(ra, rb):
-    live = (ra["done"] != 4) & (rb["done"] != 4)
-    assert np.array_equal(ra["done"], rb["done"])
-    for k in ("obs", "act"):
-        assert np.array_equal(_bits(ra[k][live]), _bits(rb[k][live])), k
-    assert np.array_equal(_bits(ra["rew"][live]), _bits(rb["rew"][live]))
 
 
 # ------------------------------------------------------------------------------ 1. constant-action teachers -
@@ -81,14 +55,14 @@ def test_constant_action_teachers_fly_like_vector_step(device, oracle, mode):
     obs = np.zeros((n, u.env.OBSERVATION_DIM), np.float32)
     for t in range(T):
         u.vector.observe(device, u.env, u.params, u.state, obs, u.rng)
-        assert np.array_equal(_bits(obs[:, :22]), _bits(rec["obs"][t])), t
+        assert np.array_equal(bits(obs[:, :22]), bits(rec["obs"][t])), t
         assert np.array_equal(rec["act"][t], c[ids])
         u.vector.step(device, u.env, u.params, u.state, c[ids], u.next_state, u.rng)
         u.state.assign(u.next_state)
-        assert np.array_equal(_bits(u.env.rewards()), _bits(rec["rew"][t])), t
+        assert np.array_equal(bits(u.env.rewards()), bits(rec["rew"][t])), t
         assert np.array_equal(u.env.done_codes(), rec["done"][t]), t
     assert (rec["done"] == 0).all()
-    _assert_same(_snapshot(w), _snapshot(u), mode)
+    assert_same(snapshot(w), snapshot(u), what=mode)
     # the oracle's env: observe / step / stats_update / sample_initial_state with auto-reset and 4-step episodes
     T2 = 11
     w2, tr2 = _fly(device, oracle, n, bank, ids, mode, T2, True, seed=5, episode_step_limit=4)
@@ -99,12 +73,12 @@ def test_constant_action_teachers_fly_like_vector_step(device, oracle, mode):
     reset = np.zeros(n, bool)      # re-sampled envs start from the oracle's sin / cos: within INIT_TOL-grown bars, not bit for bit
     for t in range(T2):
         o = O.observe(v.cfg, v.seed, t, 0, P, S)[:, :22].astype(np.float32)
-        assert np.array_equal(_bits(o[~reset]), _bits(rec2["obs"][t][~reset])), t
+        assert np.array_equal(bits(o[~reset]), bits(rec2["obs"][t][~reset])), t
         assert np.abs(o[reset] - rec2["obs"][t][reset]).max(initial=0.0) < 1e-4, t
         S, r, term = O.step(v.cfg, P, S, c[ids])
         O.stats_update(v.cfg, r, term, st)
         ended = term.astype(bool) | (st.steps == 0)
-        assert np.array_equal(_bits(r[~reset]), _bits(rec2["rew"][t][~reset])), t
+        assert np.array_equal(bits(r[~reset]), bits(rec2["rew"][t][~reset])), t
         assert np.abs(r[reset] - rec2["rew"][t][reset]).max(initial=0.0) < 1e-4, t
         codes = np.where(term != 0, 1, np.where(ended, 2, 0)).astype(np.uint8)
         assert np.array_equal(codes, rec2["done"][t]), t
@@ -150,18 +124,18 @@ def test_fused_equals_chained(device, oracle, arch, n, kind):
             cfg.update(noise_position=0.01, noise_linear_velocity=0.02)
         wf, tf = _fly(device, oracle, n, bank, ids, "fused", [50, 30], autoreset, seed=n, **cfg)
         wc, tc = _fly(device, oracle, n, bank, ids, "chained", 80, autoreset, seed=n, **cfg)
-        _assert_same(_snapshot(wf), _snapshot(wc), f"n={n} {kind} autoreset={autoreset}")
-        _assert_same_recording(tf.numpy(), tc.numpy())
+        assert_same(snapshot(wf), snapshot(wc), what=f"n={n} {kind} autoreset={autoreset}")
+        assert_same_recording(tf.numpy(), tc.numpy())
         assert (tf.numpy()["done"] != 0).any()                 # episode ends were crossed
     # a freezing rollout, then an auto-reset one (thaw)
     wf, tf = _fly(device, oracle, n, bank, ids, "fused", 30, False, seed=n + 1, episode_step_limit=7)
     wc, tc = _fly(device, oracle, n, bank, ids, "chained", 30, False, seed=n + 1, episode_step_limit=7)
-    _assert_same(_snapshot(wf), _snapshot(wc), "freezing")
-    _assert_same_recording(tf.numpy(), tc.numpy())
+    assert_same(snapshot(wf), snapshot(wc), what="freezing")
+    assert_same_recording(tf.numpy(), tc.numpy())
     assert wf.env.frozen().all()
     for w, mode in ((wf, "fused"), (wc, "chained")):
         w.vector.rollout(device, w.env, w.params, w.state, bank, w.rng, 5, mode, True, teacher_ids=ids)
-    _assert_same(_snapshot(wf), _snapshot(wc), "thaw")
+    assert_same(snapshot(wf), snapshot(wc), what="thaw")
     assert not wf.env.frozen().any()
 
 
@@ -180,7 +154,7 @@ def test_recorded_actions_equal_relabelling_and_the_oracle(device, oracle, kind)
     rec = tr.numpy()
     live = rec["done"] != 4
     lab = tr.relabel_teachers(bank, ids)
-    assert np.array_equal(_bits(lab[live]), _bits(rec["act"][live]))
+    assert np.array_equal(bits(lab[live]), bits(rec["act"][live]))
     ref, e = R.relabel_bound(W, in_dim, widths, "tanh", "identity", rec["obs"], ids, "fp32" if kind == "stack" else kind)
     R.assert_within(np.where(live[..., None], rec["act"], ref), ref, e, kind)
     # the oracle's env replaying the recorded actions from the same start (noise off): observations, rewards, done codes
@@ -189,9 +163,9 @@ def test_recorded_actions_equal_relabelling_and_the_oracle(device, oracle, kind)
     alive = np.ones(n, bool)
     for t in range(T):
         o = oracle.observe(v.cfg, v.seed, t, 0, v.P, S)
-        assert np.array_equal(_bits(o[alive, :22].astype(np.float32)), _bits(rec["obs"][t][alive])), t
+        assert np.array_equal(bits(o[alive, :22].astype(np.float32)), bits(rec["obs"][t][alive])), t
         S2, r, term = oracle.step(v.cfg, v.P, S, rec["act"][t])
-        assert np.array_equal(_bits(r[alive].astype(np.float32)), _bits(rec["rew"][t][alive])), t
+        assert np.array_equal(bits(r[alive].astype(np.float32)), bits(rec["rew"][t][alive])), t
         assert np.array_equal(np.where(term[alive] != 0, 1, 0), rec["done"][t][alive]), t
         S = np.where(alive[:, None], S2, S)
         alive &= term == 0
@@ -215,9 +189,9 @@ def test_a_neighbours_teacher_leaves_a_row_alone(device, oracle):
         keep = ids == 0
         ra, rb = ta.numpy(), tb.numpy()
         for k in ("obs", "act", "rew", "done"):
-            assert np.array_equal(_bits(ra[k][:, keep]), _bits(rb[k][:, keep])), (mode, k)
+            assert np.array_equal(bits(ra[k][:, keep]), bits(rb[k][:, keep])), (mode, k)
         assert np.isnan(rb["act"][:, ~keep]).all()
-        assert np.array_equal(_bits(wa.state.numpy()[keep]), _bits(wb.state.numpy()[keep]))
+        assert np.array_equal(bits(wa.state.numpy()[keep]), bits(wb.state.numpy()[keep]))
 
 
 # ------------------------------------------------------------------------------ 6. evaluate -
@@ -235,17 +209,17 @@ def test_evaluate_equals_a_one_step_relabel(device, oracle, kind):
     obs = tr.numpy()["obs"][0]
     lab = tr.relabel_teachers(bank, ids)[0]
     wide = np.concatenate([obs, rng.standard_normal((n, 9)).astype(np.float32)], axis=1)      # obs_stride 31
-    assert np.array_equal(_bits(bank.evaluate(wide, ids)), _bits(lab))
-    assert np.array_equal(_bits(bank.evaluate(obs[3:4], ids[3:4])), _bits(lab[3:4]))      # batch 1
-    assert np.array_equal(_bits(bank.evaluate(obs[:37], ids[:37])), _bits(lab[:37]))     # ragged
+    assert np.array_equal(bits(bank.evaluate(wide, ids)), bits(lab))
+    assert np.array_equal(bits(bank.evaluate(obs[3:4], ids[3:4])), bits(lab[3:4]))      # batch 1
+    assert np.array_equal(bits(bank.evaluate(obs[:37], ids[:37])), bits(lab[:37]))     # ragged
     # the env's device buffers: its observation in, host actions out / its action buffer out
     full = np.zeros((n, w.env.OBSERVATION_DIM), np.float32)
     w.vector.observe(device, w.env, w.params, w.state, None, w.rng)
     full = w.env.observation()
     lab2 = bank.evaluate(full[:, :22], ids)
-    assert np.array_equal(_bits(bank.evaluate(None, ids, env=w.env)), _bits(lab2))
+    assert np.array_equal(bits(bank.evaluate(None, ids, env=w.env)), bits(lab2))
     assert bank.evaluate(None, ids, env=w.env, to_device=True) is None
-    assert np.array_equal(_bits(w.env.action()), _bits(lab2))
+    assert np.array_equal(bits(w.env.action()), bits(lab2))
 
 
 # ------------------------------------------------------------------------------ 7. refusals -
@@ -259,7 +233,7 @@ def test_refusals_leave_everything_untouched(device, oracle):
     other = World(device, oracle, n, seed=4)
     tr = w.vector.Trajectory(w.env, 10)
     w.vector.rollout(device, w.env, w.params, w.state, bank, w.rng, 3, "fused", False, trajectory=tr, teacher_ids=ids)
-    before = _snapshot(w)
+    before = snapshot(w)
     rec = tr.numpy()
     bf = _bank(device, W, 22, [16, 16], precision="bf16")
     stack = _bank(device, _weights(rng, K, 22, [16, 16, 16]), 22, [16, 16, 16])
@@ -288,15 +262,15 @@ def test_refusals_leave_everything_untouched(device, oracle):
         w.vector.rollout(device, w.env, w.params, w.state, bank, w.rng, 2, "fused", False)              # ids required
     with pytest.raises(ValueError):
         w.vector.rollout(device, w.env, w.params, w.state, w.policy, w.rng, 2, "fused", False, teacher_ids=ids)
-    _assert_same(before, _snapshot(w), "after refusals")
-    assert len(tr) == 3 and np.array_equal(_bits(tr.numpy()["obs"]), _bits(rec["obs"]))
+    assert_same(before, snapshot(w), what="after refusals")
+    assert len(tr) == 3 and np.array_equal(bits(tr.numpy()["obs"]), bits(rec["obs"]))
     # the rng epoch did not move: the next rollout equals one on a world that never saw the refusals
     w.vector.rollout(device, w.env, w.params, w.state, bank, w.rng, 4, "fused", False, trajectory=tr, teacher_ids=ids)
     u = World(device, oracle, n, seed=4)
     ut = u.vector.Trajectory(u.env, 10)
     u.vector.rollout(device, u.env, u.params, u.state, bank, u.rng, 3, "fused", False, trajectory=ut, teacher_ids=ids)
     u.vector.rollout(device, u.env, u.params, u.state, bank, u.rng, 4, "fused", False, trajectory=ut, teacher_ids=ids)
-    _assert_same(_snapshot(w), _snapshot(u), "epoch")
+    assert_same(snapshot(w), snapshot(u), what="epoch")
 
 
 # ------------------------------------------------------------------------------ 8. resident executor -
@@ -331,6 +305,6 @@ def test_a_teacher_rollout_between_resident_loop_iterations(device, oracle):
 
     on, off = run(True), run(False)
     for x, y in zip(on[:3], off[:3]):
-        assert np.array_equal(_bits(x), _bits(y))
+        assert np.array_equal(bits(x), bits(y))
     assert on[3]["commands"] > 0 and on[3]["starts"] >= 2          # the executor served the loop, was retired, and came back
     assert off[3]["commands"] == 0

@@ -10,23 +10,16 @@ import raptor_amd.l2f as l2f
 from raptor_amd import _lib, tracking
 from raptor_amd._lib import RaptorQuadError
 from gpu_common import World, _lib_set_epoch
+from rollout_common import assert_same, assert_same_recording, random_table, roll, world_snapshot
 
 pytestmark = pytest.mark.gpu
 
 LIMIT = 9           # episode_step_limit of tests 1 - 6: episodes end and restart inside every rollout
 
 
-def _table(rows, seed=1):
-    """Entries of order 0.1 m and 0.1 m/s, different in every row."""
-    g = np.random.default_rng(seed)
-    t = (0.1 * g.uniform(-1.0, 1.0, (rows, 6))).astype(np.float32)
-    assert len({r.tobytes() for r in t}) == rows
-    return t
-
-
 @pytest.fixture(scope="module")
 def table():
-    t = _table(LIMIT)
+    t = random_table(LIMIT)
     t.setflags(write=False)
     return t
 
@@ -36,23 +29,8 @@ def ref(device, table):
     return l2f.Reference(device, table)
 
 
-def _roll(w, n_steps, mode="fused", autoreset=True, **kw):
-    w.vector.rollout(w.device, w.env, w.params, w.state, w.policy, w.rng, n_steps, mode, autoreset, **kw)
-
-
-def _snapshot(w):
-    e = w.env
-    sq, steps = e.tracking_error()
-    return dict(state=w.state.numpy(), hidden=w.policy.hidden_state(w.n), returns=e.returns(), steps=e.episode_steps(),
-                fin_returns=e.finished_returns(), fin_lengths=e.finished_lengths(), fin_counts=e.finished_counts(),
-                fin_terminated=e.finished_terminated(), rewards=e.rewards(), terminated=e.terminated(), done=e.done_codes(),
-                frozen=e.frozen(), episode=e.episode_index(), track_sq=sq, track_steps=steps)
-
-
-def _assert_same(a, b, skip=()):
-    for k in a:
-        if k not in skip:
-            assert np.array_equal(a[k], b[k]), k
+# a tracked world against an untracked one: the tracking sums are the one thing that lies between them (asserted beside the call)
+UNTRACKED_SKIP = ("track_sq", "track_steps")
 
 
 # ------------------------------------------------------------------ 1 -----
@@ -62,9 +40,9 @@ def test_zero_reference_is_a_no_op(device, oracle, mode):
     a, b = (World(device, oracle, n, seed=5, episode_step_limit=LIMIT) for _ in range(2))
     zero = l2f.Reference(device, tracking.hold(LIMIT))
     for chunk in (7, 12):
-        _roll(a, chunk, mode, reference=zero)
-        _roll(b, chunk, mode)
-    _assert_same(_snapshot(a), _snapshot(b), skip=("track_sq", "track_steps"))
+        roll(a, chunk, mode, reference=zero)
+        roll(b, chunk, mode)
+    assert_same(world_snapshot(a), world_snapshot(b), skip=UNTRACKED_SKIP)
     assert a.env.finished_counts().min() >= 1
     assert np.array_equal(a.env.tracking_error()[1], np.full(n, 19, np.uint32)) and not b.env.tracking_error()[1].any()
 
@@ -93,7 +71,7 @@ def test_one_tracked_step_equals_the_api_with_the_host_subtracting(device, oracl
         _lib_set_epoch(b, a.rng.epoch)
         k = a.env.episode_steps()
         ragged |= len(np.unique(k)) > 2
-        _roll(a, 1, "fused", reference=ref)
+        roll(a, 1, "fused", reference=ref)
         b.vector.observe(device, b.env, b.params, b.state, obs, b.rng)
         obs[:, :3] -= table[k, :3]
         obs[:, 12:15] -= table[k, 3:]
@@ -118,13 +96,13 @@ def test_tracked_fused_equals_chained_equals_one_step_launches(device, oracle, r
     for w in (a, b, c):
         w.policy.set_precision(precision)
     for chunk in (7, 12):
-        _roll(a, chunk, "fused", reference=ref)
-        _roll(b, chunk, "chained", reference=ref)
+        roll(a, chunk, "fused", reference=ref)
+        roll(b, chunk, "chained", reference=ref)
         for _ in range(chunk):
-            _roll(c, 1, "fused", reference=ref)
-    sa, sb, sc = _snapshot(a), _snapshot(b), _snapshot(c)
-    _assert_same(sa, sb)
-    _assert_same(sa, sc)
+            roll(c, 1, "fused", reference=ref)
+    sa, sb, sc = world_snapshot(a), world_snapshot(b), world_snapshot(c)
+    assert_same(sa, sb)
+    assert_same(sa, sc)
     assert sa["fin_counts"].min() >= 1
     assert np.array_equal(sa["track_steps"], np.full(n, 19, np.uint32)) and (sa["track_sq"] > 0).all()
 
@@ -138,13 +116,13 @@ def test_tracked_without_autoreset_frozen_envs_accumulate_nothing(device, oracle
         s[::3, 0] = 0.7
         w.state.set(s)
     for chunk in (7, 12):
-        _roll(a, chunk, "fused", False, reference=ref)
-        _roll(b, chunk, "chained", False, reference=ref)
+        roll(a, chunk, "fused", False, reference=ref)
+        roll(b, chunk, "chained", False, reference=ref)
         for _ in range(chunk):
-            _roll(c, 1, "fused", False, reference=ref)
-    sa, sb, sc = _snapshot(a), _snapshot(b), _snapshot(c)
-    _assert_same(sa, sb)
-    _assert_same(sa, sc)
+            roll(c, 1, "fused", False, reference=ref)
+    sa, sb, sc = world_snapshot(a), world_snapshot(b), world_snapshot(c)
+    assert_same(sa, sb)
+    assert_same(sa, sc)
     assert sa["frozen"].all()
     # an env stepped until its episode ended and then sat still: its tracked steps are its one episode's length
     assert np.array_equal(sa["track_steps"], sa["fin_lengths"]) and sa["track_steps"].max() == LIMIT
@@ -157,14 +135,14 @@ def test_tracked_chained_graph_replay_is_keyed_by_the_reference(device, oracle):
     n, limit = 65, 30
     kw = dict(seed=6, episode_step_limit=limit, termination_position=0.6)
     a, b = World(device, oracle, n, **kw), World(device, oracle, n, **kw)
-    r1, r2 = l2f.Reference(device, _table(limit, 2)), l2f.Reference(device, _table(limit + 3, 3))
+    r1, r2 = l2f.Reference(device, random_table(limit, 2)), l2f.Reference(device, random_table(limit + 3, 3))
     for r in (r1, r2, r1):
-        _roll(a, 27, "fused", reference=r)
-        _roll(b, 27, "chained", reference=r)
-        _assert_same(_snapshot(a), _snapshot(b))
-    _roll(a, 25, "fused")
-    _roll(b, 25, "chained")
-    _assert_same(_snapshot(a), _snapshot(b))
+        roll(a, 27, "fused", reference=r)
+        roll(b, 27, "chained", reference=r)
+        assert_same(world_snapshot(a), world_snapshot(b))
+    roll(a, 25, "fused")
+    roll(b, 25, "chained")
+    assert_same(world_snapshot(a), world_snapshot(b))
     assert a.env.finished_counts().min() >= 1
 
 
@@ -175,13 +153,12 @@ def test_tracked_recording(device, oracle, table, ref):
     a, b, u = (World(device, oracle, n, **kw) for _ in range(3))
     ta, tb, tu = (w.vector.Trajectory(w.env, T) for w in (a, b, u))
     for chunk in (7, 12):
-        _roll(a, chunk, "fused", trajectory=ta, reference=ref)
-        _roll(b, chunk, "chained", trajectory=tb, reference=ref)
-        _roll(u, chunk, "fused", trajectory=tu)
+        roll(a, chunk, "fused", trajectory=ta, reference=ref)
+        roll(b, chunk, "chained", trajectory=tb, reference=ref)
+        roll(u, chunk, "fused", trajectory=tu)
     ra, rb, ru = ta.numpy(), tb.numpy(), tu.numpy()
-    for k in ("obs", "act", "rew", "done"):
-        assert np.array_equal(ra[k], rb[k]), k
-    _assert_same(_snapshot(a), _snapshot(b))
+    assert_same_recording(ra, rb, frozen_too=True)
+    assert_same(world_snapshot(a), world_snapshot(b))
     a.policy.reset()
     assert np.array_equal(ta.relabel(a.policy), ra["act"])
     # what the policy saw is recorded: the first observation is the untracked one minus row 0, bit for bit, and the rest moved
@@ -200,7 +177,7 @@ def test_tracking_accumulators_against_float64(device, oracle, table, ref):
         k = a.env.episode_steps()
         p = a.state.numpy()[:, :3].astype(np.float64)
         want += ((p - table[k, :3].astype(np.float64)) ** 2).sum(axis=1)
-        _roll(a, 1, "fused", reference=ref)
+        roll(a, 1, "fused", reference=ref)
     sq, steps = a.env.tracking_error()
     rel = np.abs(sq - want) / want
     print("tracking sum: max relative error vs float64", rel.max())
@@ -216,17 +193,17 @@ def test_tracking_accumulators_against_float64(device, oracle, table, ref):
 def test_refusals_leave_the_env_alone(device, oracle, table, ref):
     n = 65
     a = World(device, oracle, n, seed=5, episode_step_limit=LIMIT)
-    _roll(a, 3, "fused", reference=ref)
-    before, epoch = _snapshot(a), a.rng.epoch
+    roll(a, 3, "fused", reference=ref)
+    before, epoch = world_snapshot(a), a.rng.epoch
 
     def refused(match, **kw):
         for mode in ("fused", "chained"):
             with pytest.raises(RaptorQuadError, match=match):
-                _roll(a, 5, mode, **kw)
-        _assert_same(before, _snapshot(a))
+                roll(a, 5, mode, **kw)
+        assert_same(before, world_snapshot(a))
         assert a.rng.epoch == epoch
 
-    refused("fewer rows than episode_step_limit", reference=l2f.Reference(device, _table(LIMIT - 1)))
+    refused("fewer rows than episode_step_limit", reference=l2f.Reference(device, random_table(LIMIT - 1)))
     other = l2f.Device(0)
     refused("reference lives on another device", reference=l2f.Reference(other, np.array(table)))
     a.policy.set_sample_and_squash("mean")
@@ -244,8 +221,8 @@ def test_refusals_leave_the_env_alone(device, oracle, table, ref):
         assert not h.value
     with pytest.raises(RaptorQuadError, match="null reference"):
         _lib.call("rq_rollout_track", device._h, a.env._h, a.params._h, a.state._h, a.policy._handle(device), a.rng._h, 1, 0, 1, None, None)
-    _assert_same(before, _snapshot(a))
-    _roll(a, 3, "fused", reference=ref)                   # and it still flies
+    assert_same(before, world_snapshot(a))
+    roll(a, 3, "fused", reference=ref)                   # and it still flies
     assert np.array_equal(a.env.tracking_error()[1], np.full(n, 6, np.uint32))
 
 
@@ -259,9 +236,9 @@ def test_the_policy_tracks_a_figure_eight(device, oracle):
     a = World(device, oracle, n, seed=0, domain_randomization=0, init_guidance=1.0)
     t = tracking.lissajous(500, 0.01, amplitude=(0.3, 0.15, 0), period=5.0)
     r = l2f.Reference(device, t)
-    _roll(a, 200, "fused", False, reference=r)
+    roll(a, 200, "fused", False, reference=r)
     a_sq0, a_n0 = a.env.tracking_error()
-    _roll(a, 300, "fused", False, reference=r)
+    roll(a, 300, "fused", False, reference=r)
     sq, steps = a.env.tracking_error()
     assert not a.env.finished_terminated().any() and np.array_equal(steps, np.full(n, 500, np.uint32))
     rmse = np.sqrt((sq.astype(np.float64) - a_sq0) / 300)
