@@ -8,7 +8,12 @@ operand images are HIP launches enqueued back to back, and nothing of the record
 --torch-optimizer keeps the earlier loop instead - trajectory_actions + masked_mse + torch.optim.Adam + set_weights, the way any
 other loss than the masked MSE still goes - and prints the same lines.
 
+--figure-eight / --suite: every collection - the teachers' epochs (--teacher-epochs K) and the student's alike - flies the
+figure-eight of examples/track_figure_eight.py, or the setpoints of raptor_amd.tracking.suite dealt evenly inside every teacher's
+envs, so behaviour cloning starts on the paths the student is ranked on (examples/evaluate_checkpoints.py --suite).
+
     python examples/distill.py [--envs 16384] [--steps 100] [--epochs 3] [--adam-steps 10] [--lr 1e-3] [--torch-optimizer]
+                               [--teacher-epochs K] [--figure-eight | --suite]
 """
 import argparse
 import os
@@ -20,6 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import raptor_amd.l2f as l2f                       # noqa: E402
+from raptor_amd import tracking                    # noqa: E402
 from raptor_amd.foundation_policy import Raptor    # noqa: E402
 from raptor_amd.teachers import TeacherBank, balanced_teacher_assignment, parameter_count    # noqa: E402
 from raptor_amd.training import Distiller, masked_mse, trajectory_actions  # noqa: E402
@@ -37,7 +43,11 @@ def main():
                     help="the first K epochs collect with the teachers flying the envs (behaviour cloning), then the student acts")
     ap.add_argument("--torch-optimizer", action="store_true",
                     help="the loss and Adam in torch (trajectory_actions + masked_mse) instead of Distiller.step")
+    ap.add_argument("--figure-eight", action="store_true", help="every collection tracks a figure-eight")
+    ap.add_argument("--suite", action="store_true", help="every collection tracks a suite of setpoints, a reference per env")
     args = ap.parse_args()
+    if args.figure_eight and args.suite:
+        ap.error("--figure-eight and --suite do not combine: the suite holds the figure-eight")
 
     device = l2f.Device()
     vector = l2f.vector(args.envs)
@@ -45,6 +55,10 @@ def main():
     params, state = vector.VectorParameters(), vector.VectorState()
     vector.initialize_rng(device, rng, 0)
     vector.initialize_environment(device, env)
+    cfg = env.config
+    if args.figure_eight or args.suite:
+        cfg.init_guidance = 1.0                    # hover at the origin, where the paths start
+        env.config = cfg
     vector.sample_initial_parameters(device, env, params, rng)
     vector.sample_initial_state(device, env, params, state, rng)
     n, T = env.N_ENVIRONMENTS, args.steps
@@ -54,6 +68,14 @@ def main():
     bank = TeacherBank(device, (np.random.default_rng(1).standard_normal((args.teachers, parameter_count(22, 64, 64))) * 0.1)
                        .astype(np.float32), 22, 64, 64, "relu", "tanh")
     ids = balanced_teacher_assignment(n, args.teachers)
+    # the setpoint both kinds of epoch fly: a row per step of an episode (the env reads the row of its own episode step count)
+    ref, ref_ids = None, None
+    rows = int(cfg.episode_step_limit)
+    if args.figure_eight:
+        ref = l2f.Reference(device, tracking.lissajous(rows, float(cfg.dt), amplitude=(0.3, 0.15, 0.0), period=5.0))
+    if args.suite:
+        ref = l2f.ReferenceBank(device, list(tracking.suite(rows, float(cfg.dt)).values()))
+        ref_ids = tracking.spread_reference_ids(n, ref.n_references, ids)
     if args.torch_optimizer:
         weights = torch.tensor(student.weights, device="cuda", requires_grad=True)
         opt = torch.optim.Adam([weights], lr=args.lr)
@@ -65,9 +87,11 @@ def main():
         traj.reset()
         student.reset()
         if epoch < args.teacher_epochs:     # the teachers act: the recorded actions ARE their labels
-            vector.rollout(device, env, params, state, bank, rng, T, "fused", autoreset=True, trajectory=traj, teacher_ids=ids)
+            bank.fly(vector, device, env, params, state, rng, T, ids, "fused", autoreset=True, trajectory=traj, reference=ref,
+                     reference_ids=ref_ids)
         else:
-            vector.rollout(device, env, params, state, student, rng, T, "fused", autoreset=True, trajectory=traj)
+            vector.rollout(device, env, params, state, student, rng, T, "fused", autoreset=True, trajectory=traj, reference=ref,
+                           reference_ids=ref_ids)
             traj.relabel_teachers(bank, ids, overwrite=True, fetch=False)      # stored actions <- the teachers' labels
         torch.cuda.synchronize()
         t0 = time.perf_counter()

@@ -37,6 +37,7 @@
  *     student-visited states                            :208-216 rq_teacher_bank_create / rq_trajectory_relabel_teachers
  *   distillation: the teachers flying their own
  *     quadrotors (checks, teacher-acting collection)    :207-216 rq_rollout_teachers / rq_teacher_bank_evaluate
+ *     ... on a moving setpoint, one table or one per env          rq_rollout_teachers_track / rq_rollout_teachers_track_refs
  *   distillation: the student's regression gradient    :208-216 rq_trajectory_policy_forward / _backward + rq_policy_set_weights;
  *                                                              rq_trajectory_distill (loss, Adam and repack on the device)
  *   (the reference is single-process) env shards over
@@ -84,7 +85,8 @@ extern "C" {
                               added, no struct changed)
                               (still 5: rq_policy_bank_{set,get}_native_interval and rq_rollout_policies_track added, no struct changed)
                               (still 5: rq_reference_bank_{create,destroy}, rq_rollout_track_refs and rq_rollout_policies_track_refs added,
-                              no struct changed) */
+                              no struct changed)
+                              (still 5: rq_rollout_teachers_track and rq_rollout_teachers_track_refs added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -441,7 +443,8 @@ RQ_API int rq_rollout_record(rq_device* dev, rq_env* env, const rq_params* param
  * state - termination_position must contain the path.  A trajectory buffer records the shifted observation (what the policy saw),
  * so a tracked recording goes into rq_trajectory_relabel*, the learner and rq_trajectory_distill as it is.
  * Refused before anything is enqueued: a null argument, rows < episode_step_limit (no modulo: the table covers an episode), a
- * reference of another rq_device, a policy with a SampleAndSquash stage.  Teacher banks do not track.
+ * reference of another rq_device, a policy with a SampleAndSquash stage.  A teacher bank tracks through its own entry points
+ * (rq_rollout_teachers_track, rq_rollout_teachers_track_refs).
  * Tracking error: per env, sum_sq = fp32 running sum of |p - ref[k][0..2]|^2 on the true (noise-free) position at observe time over
  * the steps actually taken (a frozen env adds nothing), steps = their count; both exist in tracked rollouts only, are the same bit
  * for bit in both modes, and are zeroed by rq_env_reset_statistics.  Either destination may be NULL. */
@@ -583,6 +586,27 @@ RQ_API int rq_teacher_bank_evaluate(rq_teacher_bank* bank, rq_env* env, const ui
 RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
                                const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                rq_trajectory* trajectory);
+/* rq_rollout_teachers on a moving setpoint: rq_rollout_track's one difference (after the observation is complete, noise included, the
+ * row of the env's own episode step count comes off the position and linear velocity the teacher sees; state, reward, termination and
+ * statistics stay absolute; a trajectory records what the teacher saw, so rq_trajectory_relabel_teachers of a tracked recording
+ * returns the recorded actions; rq_env_get_tracking_error accumulates over the steps actually taken) with env i flown by teacher
+ * teacher_id[i].  A teacher has no state to hold: there is no native interval.  trajectory may be NULL.  Both modes, the banks each
+ * mode runs as in rq_rollout_teachers (fused: one launch of the same kernel, tracking a wave-uniform switch; chained: the shift is a
+ * launch of its own between the observation and the bank); fused and chained give the same bits.  Refused before anything is enqueued
+ * (state, rng epoch, statistics and trajectory untouched), beside rq_rollout_teachers' refusals: a NULL reference
+ * (RQ_ERR_INVALID_ARGUMENT), a reference of another device (RQ_ERR_SHAPE_MISMATCH), one with fewer rows than episode_step_limit
+ * (RQ_ERR_INVALID_ARGUMENT). */
+RQ_API int rq_rollout_teachers_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
+                                     const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                     rq_trajectory* trajectory /* may be NULL */, const rq_reference* reference);
+/* The same with a reference bank: env i is flown by teacher teacher_id[i] on table reference_id[i] (host array
+ * [n_envs]) - K teachers on M setpoints in one rollout.  Both id arrays are free per env, also inside a 16-env tile of one teacher.
+ * Bit for bit rq_rollout_teachers_track with a rq_reference made of table r on the envs with reference_id[i] == r.  Refused as
+ * rq_rollout_teachers_track and rq_rollout_track_refs refuse (an id >= n_refs: the message names the env). */
+RQ_API int rq_rollout_teachers_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
+                                          const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                          rq_trajectory* trajectory /* may be NULL */, const rq_reference_bank* references,
+                                          const uint32_t* reference_id /* host [n_envs] */);
 
 /* ---- Policy bank: many student policies in ONE rollout, one per wave.  Post-training writes a checkpoint per epoch and its
  * users pick the student by closed-loop return, episode length and share terminated; sweeps and seed populations ask the same
@@ -646,7 +670,7 @@ RQ_API int rq_rollout_policies_track(rq_device* dev, rq_env* env, const rq_param
 /* rq_rollout_policies_track with a reference bank: env i is flown by policy policy_id[i] at its native interval on table
  * reference_id[i] - P policies on M setpoints in one rollout.  policy_id is constant on every 64-env block; reference_id is free per
  * env.  Bit for bit rq_rollout_policies_track with a rq_reference made of table r on the envs with reference_id[i] == r.  Refused as
- * rq_rollout_policies_track and rq_rollout_track_refs refuse.  Teacher banks do not track. */
+ * rq_rollout_policies_track and rq_rollout_track_refs refuse.  The teacher bank's twin: rq_rollout_teachers_track_refs. */
 RQ_API int rq_rollout_policies_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
                                           const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                           rq_trajectory* trajectory, const rq_reference_bank* references, const uint32_t* reference_id);

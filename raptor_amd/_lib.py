@@ -221,6 +221,8 @@ _SIGNATURES = {
     "rq_reference_bank_destroy": [_vp],
     "rq_rollout_track_refs": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp],
     "rq_rollout_policies_track_refs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp],
+    "rq_rollout_teachers_track": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp],
+    "rq_rollout_teachers_track_refs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp],
 }
 _RESTYPES = {"rq_last_error": C.c_char_p, "rq_status_string": C.c_char_p}
 

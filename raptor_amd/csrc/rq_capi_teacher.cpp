@@ -279,19 +279,29 @@ RQ_API int rq_teacher_bank_evaluate(rq_teacher_bank* bank, rq_env* env, const ui
     return RQ_OK;
 }
 
-RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
-                               const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
-                               rq_trajectory* traj) {
+}  // extern "C"
+
+// rq_rollout_teachers (no reference), rq_rollout_teachers_track (ref) and rq_rollout_teachers_track_refs (refs + reference_id): one
+// frame.  A tracked rollout's checks and the reference bank's row cache are the ones every tracked rollout uses (rq_capi_rollout.cpp).
+static int rollout_teachers_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
+                                 const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                 rq_trajectory* traj, const rq_reference* ref, const rq_reference_bank* refs = nullptr,
+                                 const uint32_t* reference_id = nullptr) {
     RolloutFrame f;
     int rc = rollout_check(f, dev, env, params, state, rng, bank && teacher_id, n_steps, mode, flags, traj); if (rc) return rc;
     RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "teacher bank lives on another device");
     RQ_REQUIRE(mode != RQ_ROLLOUT_FUSED || (!bank->layers && bank->precision == RQ_POLICY_FP32), RQ_ERR_INVALID_ARGUMENT,
                "the fused teacher rollout runs the fp32 two-hidden-layer {16, 32, 64} family: fly this bank (bf16 / f16x2 precision "
                "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
+    // a tracked rollout is refused here, before anything is enqueued (as rq_rollout_track refuses it)
+    if (ref) { rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc; }
+    rc = rollout_check_reference_bank(__func__, dev, env, refs, reference_id); if (rc) return rc;
     rc = check_ids(bank, teacher_id, env->n); if (rc) return rc;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     uint32_t n_tiles = 0;
     rc = bank_tiles(bank, dev, env->uid, teacher_id, env->n, &n_tiles); if (rc) return rc;
+    rc = rollout_track(f, env, ref); if (rc) return rc;
+    rc = rollout_track_refs(f, dev, env, refs, reference_id); if (rc) return rc;
     if (mode == RQ_ROLLOUT_CHAINED && n_steps) RQ_HIP(bank->sink.reserve(dev->stream, RQ_POLICY_NUM_WEIGHTS + (size_t)16 * env->ld));
     rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
     const rq::TrajPtrs& tp = f.tp;
@@ -300,11 +310,12 @@ RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* par
     if (mode == RQ_ROLLOUT_FUSED) {
         rq::TeacherRolloutArgs a{b, sc, nc, smp, rng->seed, rng->epoch, n_steps, noise ? 1u : 0u,
                                  (flags & RQ_ROLLOUT_AUTORESET) ? 1u : 0u, params->d, state->d, env->st, tp,
-                                 bank->in_dim, bank->images_f32, bank->tiles, bank->tiles + n_tiles};
+                                 bank->in_dim, bank->images_f32, bank->tiles, bank->tiles + n_tiles, f.trk};
         RQ_HIP(rq::launch_rollout_teachers(dev->stream, n_tiles, bank->h1, bank->h2, bank->act, bank->out_act, a));
     } else if (n_steps) {
-        // one step = observe -> the bank on the env's buffers (rq_teacher_bank_evaluate's launch) -> step (-> record), plain launches on
-        // the device's stream.  k_step's auto-reset also resets a policy state: here it writes the bank's sink (zero weight block)
+        // one step = observe (-> the setpoint's row taken off it: the frame's trk) -> the bank on the env's buffers
+        // (rq_teacher_bank_evaluate's launch) -> step (-> record), plain launches on the device's stream.  k_step's auto-reset also
+        // resets a policy state: here it writes the bank's sink (zero weight block)
         float* sink_w = bank->sink;
         float* sink_h = bank->sink + RQ_POLICY_NUM_WEIGHTS;
         RQ_HIP(hipMemsetAsync(sink_w, 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float), dev->stream));
@@ -317,6 +328,30 @@ RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* par
     }
     rollout_end(state, rng, n_steps, traj);
     return RQ_OK;
+}
+
+extern "C" {
+
+RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
+                               const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                               rq_trajectory* traj) {
+    return rollout_teachers_impl(dev, env, params, state, bank, teacher_id, rng, n_steps, mode, flags, traj, nullptr);
+}
+
+RQ_API int rq_rollout_teachers_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
+                                     const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                     rq_trajectory* traj, const rq_reference* reference) {
+    RQ_REQUIRE(reference, RQ_ERR_INVALID_ARGUMENT, "null reference");
+    return rollout_teachers_impl(dev, env, params, state, bank, teacher_id, rng, n_steps, mode, flags, traj, reference);
+}
+
+RQ_API int rq_rollout_teachers_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
+                                          const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
+                                          rq_trajectory* traj, const rq_reference_bank* references, const uint32_t* reference_id) {
+    RQ_REQUIRE(references, RQ_ERR_INVALID_ARGUMENT, "null reference bank");
+    RQ_REQUIRE(reference_id, RQ_ERR_INVALID_ARGUMENT, "null reference_id");
+    return rollout_teachers_impl(dev, env, params, state, bank, teacher_id, rng, n_steps, mode, flags, traj, nullptr, references,
+                                 reference_id);
 }
 
 }  // extern "C"

@@ -437,12 +437,14 @@ hipError_t launch_teacher_relabel(hipStream_t s, uint32_t n_tiles, uint32_t ld, 
 
 // a teacher bank flying its envs (rq_teacher_rollout.hip k_rollout_teachers, the register-stationary fp32 family): the loop body
 // README.md:95-99 x n_steps with env i driven by the teacher of its tile; tiles as launch_teacher_relabel's.  traj.obs == nullptr:
-// no recording.  noise / autoreset: wave-uniform switches (0 / 1).
+// no recording.  noise / autoreset: wave-uniform switches (0 / 1).  trk.ref != nullptr: on a moving setpoint (a fourth wave-uniform
+// switch), a single table or a reference bank's per-env tables (TrackPtrs::row0_at).
 struct TeacherRolloutArgs {
     Batch b; StepCfg c; NoiseCfg nc; SampleCfg sc; uint64_t seed; uint32_t epoch0, n_steps;
     uint32_t noise, autoreset;
     const float* params; float* state; StatsPtrs st; TrajPtrs traj;
     uint32_t in_dim; const float* images; const uint32_t* tile_teacher; const uint32_t* tile_env;
+    TrackPtrs trk;
 };
 hipError_t launch_rollout_teachers(hipStream_t s, uint32_t n_tiles, uint32_t h1, uint32_t h2, int act, int out_act,
                                    const TeacherRolloutArgs& a);

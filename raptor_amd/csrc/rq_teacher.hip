@@ -689,6 +689,15 @@ __global__ __launch_bounds__(64, 1) void k_rollout_teachers(TeacherRolloutArgs a
     uint8_t last_d = st.last_done[i];
     uint32_t ep = st.episode[i];
     bool frozen = st.frozen[i] != 0;
+    // on a moving setpoint (rq_rollout_teachers_track[_refs]): the env's tracking sums, and the first row of its own table in a
+    // reference bank - a per-lane gather, so the 16 envs of a tile may fly 16 different tables
+    const bool track = a.trk.ref != nullptr;                    // wave-uniform
+    float trk_sq = 0.0f;
+    uint32_t trk_n = 0, trk_row0 = 0;
+    if (track) {
+        trk_sq = a.trk.sq[i]; trk_n = a.trk.steps[i];
+        if (a.trk.row0_at != 0) trk_row0 = a.trk.steps[(size_t)a.trk.row0_at + i];
+    }
     // sample_initial_state for the episode counter ep, as step_env's auto-reset and k_thaw_frozen make it
     auto resample = [&]() {
         float s0[17], la0[4];
@@ -713,6 +722,14 @@ __global__ __launch_bounds__(64, 1) void k_rollout_teachers(TeacherRolloutArgs a
         float o[22];
         if (a.noise) observe_head<true>(y, LA01, LA23, a.nc, a.seed, a.epoch0 + t, genv, o);
         else         observe_head<false>(y, LA01, LA23, a.nc, a.seed, a.epoch0 + t, genv, o);
+        if (track) {
+            // the row of the env's own episode step count comes off the finished observation (noise included), so the recording
+            // holds what the teacher saw; the error is kept on the true position, for the envs that step (rq_rollout_body.inc)
+            float tr[6];
+            track_row(a.trk.ref, a.trk.rows, trk_row0, s.steps, tr);
+            track_shift(tr, o);
+            if (a.autoreset || !frozen) { trk_sq = track_accumulate(trk_sq, y.P01[0], y.P01[1], y.p2, tr); trk_n += 1; }
+        }
         // K-step s, k-slot q: feature 4s + q (features 22, 23 are the bias slot / padding, set by finish)
         float X[6];
 #pragma unroll
@@ -787,11 +804,13 @@ __global__ __launch_bounds__(64, 1) void k_rollout_teachers(TeacherRolloutArgs a
         st.last_done[i] = last_d;
         st.episode[i] = ep;
         st.frozen[i] = frozen ? 1 : 0;
+        if (track) { a.trk.sq[i] = trk_sq; a.trk.steps[i] = trk_n; }
     }
 }
 
 // ---------------------------------------------------------------------------- launcher ---
-// Instantiated per (H1, H2) and activation pair only: noise, auto-reset and recording are kernel arguments (9 x 4 = 36 kernels).
+// Instantiated per (H1, H2) and activation pair only: noise, auto-reset, recording and tracking are kernel arguments (9 x 4 = 36
+// kernels).
 template <int H1, int H2>
 static hipError_t launch_teachers_hh(hipStream_t s, uint32_t n_tiles, int act, int out_act, const TeacherRolloutArgs& a) {
 #define RQ_TR(A, O) k_rollout_teachers<H1, H2, A, O><<<n_tiles, 64, 0, s>>>(a)

@@ -688,14 +688,16 @@ class VectorModule:
         each env (``mode="fused"``: fp32 banks of two hidden layers of 16 / 32 / 64 units; ``"chained"``: every bank).
         ``reference`` (a ``Reference``): the policy tracks that moving setpoint - it sees position and linear velocity relative to
         the row of each env's own episode step count; everything else (state, reward, termination, statistics) stays absolute, a
-        ``trajectory`` records what the policy saw, and ``env.tracking_error()`` accumulates.  ``Raptor`` policies only.
+        ``trajectory`` records what the policy saw, and ``env.tracking_error()`` accumulates.  ``Raptor`` policies only here: a
+        ``TeacherBank``'s tracked rollout is ``TeacherBank.fly(..., reference=ref)``.
         ``reference`` may also be a ``ReferenceBank`` with ``reference_ids`` ([N] integers, free per env): env i tracks table
         ``reference_ids[i]`` and computes what it computes with that table as its ``Reference``.
         ``policy`` may also be a ``raptor_amd.policy_bank.PolicyBank``: ``policy_ids`` ([N] integers, constant on every aligned
         block of 64 envs) names the student policy that flies each env, both modes, every policy at the bank's native interval for
         it.  A bank does not take ``reference`` here: ``PolicyBank.fly(..., reference=ref)`` is the bank's tracked rollout."""
         if reference is not None and teacher_ids is not None:
-            raise ValueError("reference and teacher_ids do not combine: a TeacherBank rollout does not track")
+            raise ValueError("reference and teacher_ids do not combine here: a teacher bank's tracked rollout is its own call, "
+                             "TeacherBank.fly(..., teacher_ids, reference=ref)")
         ref_ids = _checked_reference(reference, reference_ids, self.N_ENVIRONMENTS)
         m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
         from .policy_bank import PolicyBank, check_policy_ids
@@ -717,7 +719,7 @@ class VectorModule:
         from .teachers import TeacherBank
         if isinstance(policy, TeacherBank):
             if reference is not None:
-                raise ValueError("a TeacherBank rollout does not track a reference")
+                raise ValueError("a TeacherBank does not take reference here: TeacherBank.fly(..., reference=ref) is its tracked rollout")
             if teacher_ids is None:
                 raise ValueError("a TeacherBank flies the envs by teacher_ids: one teacher id per env is required")
             ids = np.ascontiguousarray(teacher_ids, np.uint32)

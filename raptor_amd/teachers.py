@@ -152,6 +152,59 @@ class TeacherBank:
         _lib.call("rq_teacher_bank_set_precision", self._h, PRECISIONS[precision])
         self.precision = precision
 
+    def fly(self, vector, device, env, params, state, rng, n_steps, teacher_ids, mode="fused", autoreset=False, trajectory=None,
+            reference=None, reference_ids=None):
+        """The bank's own rollout call: ``vector.rollout(..., bank, ..., teacher_ids=ids)`` and, with ``reference`` (an
+        ``l2f.Reference``), on that moving setpoint: each env sees position and linear velocity relative to the row of its own episode
+        step count, a ``trajectory`` records what the teacher saw (``relabel_teachers`` of it returns the recorded actions) and
+        ``env.tracking_error()`` accumulates, as in a ``Raptor`` policy's tracked rollout.  With an ``l2f.ReferenceBank`` and
+        ``reference_ids`` ([N] integers, free per env, also inside a teacher's 16-env tile) env i tracks table ``reference_ids[i]``:
+        one rollout flies K teachers on M setpoints.  ``mode="fused"``: fp32 banks of two hidden layers of 16 / 32 / 64 units;
+        ``"chained"``: every bank.  An MLP has no state to hold: there is no native interval."""
+        from .l2f import ROLLOUT_AUTORESET, ROLLOUT_CHAINED, ROLLOUT_FUSED, _checked_reference
+        ids = np.ascontiguousarray(teacher_ids, np.uint32)
+        if ids.shape != (vector.N_ENVIRONMENTS,):
+            raise ValueError("teacher_ids must hold one id per env")
+        ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)
+        if reference is None:
+            vector.rollout(device, env, params, state, self, rng, n_steps, mode=mode, autoreset=autoreset, trajectory=trajectory,
+                           teacher_ids=ids)
+            return
+        m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
+        args = (device._h, env._require("environment"), params._require("VectorParameters"), state._require("VectorState"), self._h,
+                ids.ctypes.data, rng._require("rng"), int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0,
+                trajectory._require("trajectory") if trajectory is not None else None)
+        if ref_ids is None:
+            _lib.call("rq_rollout_teachers_track", *args, reference._h)
+        else:
+            _lib.call("rq_rollout_teachers_track_refs", *args, reference._h, ref_ids.ctypes.data)
+
+    def closed_loop(self, vector, device, env, params, state, rng, n_steps, teacher_ids, mode="fused", autoreset=True,
+                    reference=None, reference_ids=None):
+        """The closed-loop check of the whole bank: the env's statistics start afresh, one ``fly`` of ``n_steps`` ->
+        ``teacher_episode_table`` of what it finished.  With ``reference`` the table gains ``tracking_rmse`` [K]
+        (``policy_bank.policy_tracking_table`` of ``env.tracking_error()``, grouped by teacher); with an ``l2f.ReferenceBank`` and
+        ``reference_ids`` (``tracking.spread_reference_ids(N, M, teacher_ids)`` deals them evenly inside every teacher's envs) it is
+        [K, M]: teacher k on setpoint r (``tracking.reference_tracking_table``) - what a student's tracking error stands against."""
+        from .l2f import _checked_reference
+        ids = np.ascontiguousarray(teacher_ids, np.uint32)
+        if ids.shape != (vector.N_ENVIRONMENTS,):
+            raise ValueError("teacher_ids must hold one id per env")
+        ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
+        env.reset_statistics()
+        self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
+                 reference_ids=reference_ids)
+        table = teacher_episode_table(env, ids, self.n_teachers)
+        if ref_ids is not None:
+            from .tracking import reference_tracking_table
+            sum_sq, steps = env.tracking_error()
+            table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, ref_ids, reference.n_references, ids, self.n_teachers)
+        elif reference is not None:
+            from .policy_bank import policy_tracking_table
+            sum_sq, steps = env.tracking_error()
+            table["tracking_rmse"] = policy_tracking_table(sum_sq, steps, ids, self.n_teachers)
+        return table
+
 
 def balanced_teacher_assignment(n_envs, n_teachers):
     """teacher id of every env (uint32 [n_envs], contiguous groups) with WHOLE 16-env tiles per teacher.
