@@ -86,7 +86,8 @@ extern "C" {
                               (still 5: rq_policy_bank_{set,get}_native_interval and rq_rollout_policies_track added, no struct changed)
                               (still 5: rq_reference_bank_{create,destroy}, rq_rollout_track_refs and rq_rollout_policies_track_refs added,
                               no struct changed)
-                              (still 5: rq_rollout_teachers_track and rq_rollout_teachers_track_refs added, no struct changed) */
+                              (still 5: rq_rollout_teachers_track and rq_rollout_teachers_track_refs added, no struct changed)
+                              (still 5: rq_wrench_bank_{create,destroy} and rq_env_{set,get}_wrench_schedule added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -477,6 +478,45 @@ RQ_API int rq_rollout_track_refs(rq_device* dev, rq_env* env, const rq_params* p
                                  rq_policy* policy, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                  rq_trajectory* trajectory /* may be NULL */, const rq_reference_bank* references,
                                  const uint32_t* reference_id /* host [n_envs] */);
+
+/* ---- Wrench schedule: scheduled gusts, pokes and payloads.  The per-episode constant wrench of the state (RQ_S_FORCE / RQ_S_TORQUE,
+ * drawn at sample_initial_state) cannot express a gust from 1.5 s to 2.5 s, a one-step poke or a payload that hangs on from step 200.
+ * A WRENCH BANK is n_tables tables of one length, host_rows [n_tables][rows][6] float32 row-major: columns 0..2 a force in the world
+ * frame, 3..5 a torque in the body frame; `units` belongs to the bank: RQ_WRENCH_RELATIVE (force in multiples of m g, torque in
+ * multiples of m g arm - the units of disturbance_force_std / disturbance_torque_std, meaningful across a domain-randomised
+ * population) or RQ_WRENCH_ABSOLUTE (N and N m).  A schedule is attached to an ENV - a property of the world, not of who flies: a
+ * bank plus one table id per env.  While it is attached EVERY transition of env i, in every call that steps (rq_step, the rollouts
+ * of a policy, a policy bank and a teacher bank, fused or chained), is computed with the wrench
+ *     k   = the env's episode step count before the step, clamped to rows - 1      (the count rq_rollout_track indexes with)
+ *     row = table[wrench_id[i]][k]
+ *     mg  = mass * gravity                        arm = sqrt((x0 * x0) + (y0 * y0))      x0, y0 = RQ_P_ROTOR_POS + 0, + 1
+ *     fs  = relative ? mg : 1.0f                  ts  = relative ? mg * arm : 1.0f
+ *     w[j]     = f[j]     + (fs * row[j])         j = 0..2     f = the state's RQ_S_FORCE / RQ_S_TORQUE (the per-episode draw)
+ *     w[3 + j] = f[3 + j] + (ts * row[3 + j])
+ * every *, + and sqrt one correctly rounded fp32 operation in this order, nothing contracted to an fma: NumPy float32 on the host
+ * reproduces the bits (raptor_amd.disturbances.compose).  The schedule is never written into the state: RQ_S_FORCE / RQ_S_TORQUE of
+ * the next state stay the per-episode base and a new episode's base is sampled as before; reward, termination, RNG streams,
+ * statistics and observations are those of the resulting motion.  A frozen env reads nothing; rq_env_reset_statistics zeroes the
+ * step count and so restarts the table; the scales come from the params passed to the call (rq_params_set after attaching is
+ * honoured).
+ * rq_wrench_bank_create refuses a null argument, n_tables == 0, rows == 0, a non-finite entry, n_tables * rows >= 2^28 and an
+ * unknown `units`, all before the device is looked at.  rq_env_set_wrench_schedule (bank NULL: detach; wrench_id NULL: table 0 for
+ * every env) refuses a bank of another rq_device (RQ_ERR_SHAPE_MISMATCH) and an id >= n_tables (the message names the env), waits
+ * for the device's stream and uploads the per-env first rows once.  rq_wrench_bank_destroy is refused while the bank is attached
+ * to a live env; rq_env_destroy detaches.  Every call that steps refuses, before anything is enqueued (state, rng epoch,
+ * statistics and recording untouched), a bank with rows < episode_step_limit.  In fused mode a schedule is flown by the fp32
+ * policy and policy-bank kernels (k_rollout_fused_wrench); a bf16 / f16x2 policy, a SampleAndSquash stage and rq_rollout_teachers*
+ * are refused in fused mode while a schedule is attached (nothing runs chained in their place) - all three run chained.  The
+ * small-batch loop steps such an env with plain launches (no resident executor, no speculative policy step). */
+typedef struct rq_wrench_bank rq_wrench_bank;
+enum rq_wrench_units { RQ_WRENCH_RELATIVE = 0, RQ_WRENCH_ABSOLUTE = 1 };
+RQ_API int rq_wrench_bank_create(rq_device* dev, const float* host_rows /* [n_tables][rows][6] */, uint32_t n_tables, uint32_t rows,
+                                 int units /* rq_wrench_units */, rq_wrench_bank** out);
+RQ_API int rq_wrench_bank_destroy(rq_wrench_bank* bank);
+RQ_API int rq_env_set_wrench_schedule(rq_env* env, rq_wrench_bank* bank /* NULL detaches */,
+                                      const uint32_t* wrench_id /* host [n_envs] or NULL = table 0 */);
+RQ_API int rq_env_get_wrench_schedule(const rq_env* env, rq_wrench_bank** bank /* NULL when none */,
+                                      uint32_t* wrench_id_out /* host [n_envs] or NULL */);
 
 /* ---- Learner: the student's gradient over a recorded trajectory (README.md:208-216, the distillation step's regression) ----
  * Forward: the policy on the recorded observations obs [T][22][ld] under rq_trajectory_relabel's episode rules (GRU state back to

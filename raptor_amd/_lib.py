@@ -223,6 +223,10 @@ _SIGNATURES = {
     "rq_rollout_policies_track_refs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp],
     "rq_rollout_teachers_track": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp],
     "rq_rollout_teachers_track_refs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp, _vp],
+    "rq_wrench_bank_create": [_vp, _fp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)],
+    "rq_wrench_bank_destroy": [_vp],
+    "rq_env_set_wrench_schedule": [_vp, _vp, _vp],
+    "rq_env_get_wrench_schedule": [_vp, C.POINTER(_vp), _vp],
 }
 _RESTYPES = {"rq_last_error": C.c_char_p, "rq_status_string": C.c_char_p}
 

@@ -277,7 +277,11 @@ static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* p
     if (mode == RQ_ROLLOUT_FUSED) {
         unsigned long long* span = nullptr;
         rc = fused_span_begin(__func__, dev, env, n_steps, &span); if (rc) return rc;
-        if (f.trk.ref || rated)
+        if (f.wr.rows)
+            RQ_HIP(rq::launch_rollout_fused_wrench(dev->stream, f.b, f.sc, f.nc, f.noise, f.smp, rng->seed, rng->epoch, n_steps, flags,
+                                                   params->d, state->d, bank->hidden, bank->weights, bank->images, bank->table,
+                                                   bank->intervals_dev, 1u, env->st, f.tp, f.trk, f.wr, span));
+        else if (f.trk.ref || rated)
             RQ_HIP(rq::launch_rollout_fused_bank_rate(dev->stream, f.b, f.sc, f.nc, f.noise, f.smp, rng->seed, rng->epoch, n_steps, flags,
                                                       params->d, state->d, bank->hidden, bank->weights, bank->images, bank->table,
                                                       bank->intervals_dev, env->st, f.tp, f.trk, span));
@@ -296,7 +300,7 @@ static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* p
                                : rq::launch_actor_step_bank(dev->stream, env->n, bank->images, bank->table, env->obs, env->ld,
                                                             bank->hidden, bank->ld, env->act, env->ld, env->st.frozen); },
             [&] { return rq::launch_step_bank(dev->stream, f.b, f.sc, params->d, state->d, env->act, env->st, flags, f.smp, rng->seed,
-                                              bank->hidden, bank->weights, bank->table); });
+                                              bank->hidden, bank->weights, bank->table, f.wr); });
         if (rc) return rc;
     }
     rollout_end(state, rng, n_steps, traj);

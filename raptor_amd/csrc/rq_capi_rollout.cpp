@@ -35,7 +35,24 @@ int rollout_check(RolloutFrame& f, const rq_device* dev, const rq_env* env, cons
                    "trajectory buffer too small for this rollout");
         f.tp = {traj->obs, traj->act, traj->rew, traj->done, traj->length};
     }
+    return env_wrench("rollout", env, &f.wr);
+}
+
+int env_wrench(const char* who, const rq_env* env, rq::WrenchPtrs* wr) {
+    *wr = rq::WrenchPtrs{};
+    const rq_wrench_bank* bank = env->wrench;
+    if (!bank) return RQ_OK;
+    if (bank->rows < env->cfg.episode_step_limit)
+        return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env's wrench schedule has fewer rows (" + std::to_string(bank->rows) +
+                                                 ") than episode_step_limit (" + std::to_string(env->cfg.episode_step_limit) +
+                                                 "): every table must cover an episode");
+    *wr = {bank->d, env->wrench_row0, bank->rows, bank->units == RQ_WRENCH_RELATIVE ? 1u : 0u};
     return RQ_OK;
+}
+
+int wrench_refuses_fused(const char* who, const char* what) {
+    return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env carries a wrench schedule, which the fused kernel of " + what +
+                                             " is not taught: fly it with mode RQ_ROLLOUT_CHAINED (\"chained\"), or detach the schedule");
 }
 
 int rollout_check_reference(const char* who, const rq_device* dev, const rq_env* env, const rq_reference* ref) {
@@ -155,6 +172,10 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
         RQ_REQUIRE(policy->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
                    "tracked rollouts do not carry the SampleAndSquash stage");
     }
+    if (f.wr.rows && mode == RQ_ROLLOUT_FUSED) {        // a schedule is flown fused by the fp32 builds alone; nothing runs chained in its place
+        if (policy->precision != RQ_POLICY_FP32) return wrench_refuses_fused(__func__, "a bf16 / f16x2 policy");
+        if (policy->sas_mode != RQ_SAS_OFF) return wrench_refuses_fused(__func__, "a policy with a SampleAndSquash stage");
+    }
     const uint32_t interval = policy->native_interval;      // above 1: the RATE kernels (a SampleAndSquash stage cannot be set beside it)
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = policy_size(policy, env->n); if (rc) return rc;
@@ -168,7 +189,11 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
     if (mode == RQ_ROLLOUT_FUSED) {
         unsigned long long* span = nullptr;
         rc = fused_span_begin(__func__, dev, env, n_steps, &span); if (rc) return rc;
-        if (interval > 1) {
+        if (f.wr.rows) {
+            RQ_HIP(rq::launch_rollout_fused_wrench(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
+                                                   params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), nullptr, nullptr,
+                                                   interval, env->st, tp, trk, f.wr, span));
+        } else if (interval > 1) {
             RQ_HIP(rq::launch_rollout_fused_rate(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
                                                  params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
                                                  policy->precision, tp, trk, interval, span));
@@ -207,7 +232,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
             if (e == hipSuccess)
                 e = rq::launch_step(dev->stream, b, sc, params->d, state->d, env->act, state->d, env->st,
                                     /*rollout=*/1, flags, smp, rng->seed, policy->hidden, policy->w_dev, rq::Mailbox{},
-                                    fold_observe ? env->obs : nullptr, nc, noise, epoch + 1, epoch_base);
+                                    fold_observe ? env->obs : nullptr, nc, noise, epoch + 1, epoch_base, f.wr);
             if (e == hipSuccess && traj) {
                 rq::TrajPtrs tt = tp; tt.t0 = tp.t0 + t_record;
                 e = rq::launch_record(dev->stream, b, env->obs, env->act, env->st, tt);
@@ -230,7 +255,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                     g.precision == policy->precision && g.seed == rng->seed && g.sas_mode == policy->sas_mode &&
                     g.sas_seed == policy->sas_seed && g.ls_image == policy->ls_image && g.ref == trk.ref && g.ref_rows == trk.rows &&
                     g.row0_at == trk.row0_at && g.row0_gen == f.row0_gen &&      // (a reference bank: which ids the rows were built from)
-                    g.interval == interval &&
+                    g.interval == interval && g.wrench_gen == env->wrench_gen &&
                     std::memcmp(&g.cfg, &env->cfg, sizeof(rq_env_config)) == 0) { exec = g.exec; break; }
             if (!exec) {
                 // Built node by node (rq_kernels.hpp GraphSink), NOT by stream capture: while any stream of a process captures, HIP
@@ -263,7 +288,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                     try {                       // nothing throws across the boundary
                         env->graphs.push_back({params->d, state->d, policy->hidden, packed_of(policy), policy->w_dev, env->obs, flags,
                                                policy->precision, env->cfg, rng->seed, policy->sas_mode, policy->sas_seed,
-                                               policy->ls_image, trk.ref, trk.rows, trk.row0_at, f.row0_gen, interval, exec});
+                                               policy->ls_image, trk.ref, trk.rows, trk.row0_at, f.row0_gen, interval, env->wrench_gen, exec});
                     } catch (const std::bad_alloc&) {
                         (void)hipGraphExecDestroy(exec);
                         return fail(RQ_ERR_OUT_OF_MEMORY, "rollout: host allocation failed");
@@ -365,6 +390,94 @@ RQ_API int rq_reference_bank_destroy(rq_reference_bank* references) {
     if (!references) return RQ_OK;
     DeviceScope on_device(references->ordinal);     // (hipFree synchronises the device: no launch still reads the tables)
     delete references;
+    return RQ_OK;
+}
+
+// ---------------------------------------------------------------------------- Wrench schedule
+RQ_API int rq_wrench_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, int units, rq_wrench_bank** out) {
+    RQ_REQUIRE(dev && host_rows && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    RQ_REQUIRE(n_tables > 0 && rows > 0, RQ_ERR_INVALID_ARGUMENT, "a wrench bank needs at least one table of at least one row");
+    // the row an env reads, first row of its table + episode step count, is a uint32 on the device
+    RQ_REQUIRE((uint64_t)n_tables * rows < (1ull << 28), RQ_ERR_INVALID_ARGUMENT, "a wrench bank holds fewer than 2^28 rows in all");
+    RQ_REQUIRE(units == RQ_WRENCH_RELATIVE || units == RQ_WRENCH_ABSOLUTE, RQ_ERR_INVALID_ARGUMENT,
+               "unknown units: RQ_WRENCH_RELATIVE or RQ_WRENCH_ABSOLUTE");
+    const size_t floats = (size_t)n_tables * rows * 6;
+    for (size_t j = 0; j < floats; ++j)
+        RQ_REQUIRE(std::isfinite(host_rows[j]), RQ_ERR_INVALID_ARGUMENT,
+                   "wrench bank holds a non-finite entry: table " + std::to_string(j / ((size_t)rows * 6)) + ", row " +
+                       std::to_string(j / 6 % rows));
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    rq_wrench_bank* r = new (std::nothrow) rq_wrench_bank();
+    RQ_REQUIRE(r, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
+    r->dev = dev; r->ordinal = dev->ordinal; r->n_tables = n_tables; r->rows = rows; r->units = units;
+    if (r->d.alloc(floats) != hipSuccess) {
+        delete r;
+        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_wrench_bank_create: device allocation failed");
+    }
+    // (synchronous: the caller's rows are its own again on return)
+    const hipError_t e = hipMemcpy(r->d, host_rows, floats * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete r;
+        return fail(RQ_ERR_HIP, std::string("rq_wrench_bank_create: hipMemcpy -> ") + hipGetErrorString(e));
+    }
+    *out = r;
+    return RQ_OK;
+}
+
+RQ_API int rq_wrench_bank_destroy(rq_wrench_bank* bank) {
+    if (!bank) return RQ_OK;
+    RQ_REQUIRE(bank->attached == 0, RQ_ERR_INVALID_ARGUMENT,
+               "the wrench bank is attached to " + std::to_string(bank->attached) +
+                   " live env(s): detach it (rq_env_set_wrench_schedule with a NULL bank) or destroy the env first");
+    DeviceScope on_device(bank->ordinal);     // (hipFree synchronises the device: no launch still reads the tables)
+    delete bank;
+    return RQ_OK;
+}
+
+RQ_API int rq_env_set_wrench_schedule(rq_env* env, rq_wrench_bank* bank, const uint32_t* wrench_id) {
+    RQ_REQUIRE(env, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    rq_device* dev = env->dev;
+    if (bank) {
+        RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "wrench bank lives on another device");
+        if (wrench_id)
+            for (uint32_t i = 0; i < env->n; ++i)
+                RQ_REQUIRE(wrench_id[i] < bank->n_tables, RQ_ERR_INVALID_ARGUMENT,
+                           "wrench id out of range: env " + std::to_string(i) + " names table " + std::to_string(wrench_id[i]) +
+                               " of a bank of " + std::to_string(bank->n_tables));
+    }
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;      // (retires a running resident executor)
+    RQ_HIP(hipStreamSynchronize(dev->stream));                // a launch in flight reads the rows of the schedule before
+    obs_cache_drop_if(dev, env);
+    if (!bank) {
+        if (env->wrench) env->wrench->attached -= 1;
+        env->wrench = nullptr; env->wrench_gen = 0; env->wrench_ids.clear();
+        return RQ_OK;
+    }
+    std::vector<uint32_t> ids, first;
+    try {                                   // nothing throws across the boundary
+        if (wrench_id) ids.assign(wrench_id, wrench_id + env->n); else ids.assign(env->n, 0u);
+        first.assign(env->ld, 0u);
+    } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "wrench schedule: host allocation failed");
+    }
+    for (uint32_t i = 0; i < env->n; ++i) first[i] = ids[i] * bank->rows;       // < n_tables * rows < 2^28
+    if (env->wrench_row0.empty() && env->wrench_row0.alloc(env->ld) != hipSuccess)
+        return fail(RQ_ERR_OUT_OF_MEMORY, "wrench schedule: device allocation failed");
+    // (synchronous: `first` is pageable and goes away)
+    RQ_HIP(hipMemcpy(env->wrench_row0, first.data(), (size_t)env->ld * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (env->wrench) env->wrench->attached -= 1;
+    bank->attached += 1;
+    env->wrench = bank;
+    env->wrench_ids.swap(ids);
+    env->wrench_gen = fresh_version();
+    return RQ_OK;
+}
+
+RQ_API int rq_env_get_wrench_schedule(const rq_env* env, rq_wrench_bank** bank, uint32_t* wrench_id_out) {
+    RQ_REQUIRE(env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *bank = env->wrench;
+    if (env->wrench && wrench_id_out) std::memcpy(wrench_id_out, env->wrench_ids.data(), (size_t)env->n * sizeof(uint32_t));
     return RQ_OK;
 }
 

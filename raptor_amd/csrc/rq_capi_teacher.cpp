@@ -293,6 +293,7 @@ static int rollout_teachers_impl(rq_device* dev, rq_env* env, const rq_params* p
     RQ_REQUIRE(mode != RQ_ROLLOUT_FUSED || (!bank->layers && bank->precision == RQ_POLICY_FP32), RQ_ERR_INVALID_ARGUMENT,
                "the fused teacher rollout runs the fp32 two-hidden-layer {16, 32, 64} family: fly this bank (bf16 / f16x2 precision "
                "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
+    if (f.wr.rows && mode == RQ_ROLLOUT_FUSED) return wrench_refuses_fused(__func__, "a teacher bank");
     // a tracked rollout is refused here, before anything is enqueued (as rq_rollout_track refuses it)
     if (ref) { rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc; }
     rc = rollout_check_reference_bank(__func__, dev, env, refs, reference_id); if (rc) return rc;
@@ -323,7 +324,7 @@ static int rollout_teachers_impl(rq_device* dev, rq_env* env, const rq_params* p
             [&] { return rq::launch_thaw_frozen(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, sink_h, sink_w); },
             [&] { return bank_label_launch(bank, dev, env->n, n_tiles, env->ld, 1, env->obs, env->act); },
             [&] { return rq::launch_step(dev->stream, b, sc, params->d, state->d, env->act, state->d, env->st, /*rollout=*/1, flags, smp,
-                                         rng->seed, sink_h, sink_w); });
+                                         rng->seed, sink_h, sink_w, rq::Mailbox{}, nullptr, rq::NoiseCfg{}, false, 0, nullptr, f.wr); });
         if (rc) return rc;
     }
     rollout_end(state, rng, n_steps, traj);

@@ -59,6 +59,8 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
     int rc = check_env_objects(dev, env, params, state); if (rc) return rc;
     RQ_REQUIRE(params && state && next_state && rng, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(next_state->env == env, RQ_ERR_SHAPE_MISMATCH, "next_state belongs to another env");
+    rq::WrenchPtrs wr{};
+    rc = env_wrench(__func__, env, &wr); if (rc) return rc;       // the env's wrench schedule, refused before anything is enqueued
     DeviceScope on_device(dev, rq::KeepResident{}); rc = on_device.rc; if (rc) return rc;
     // small batches: the kernel also assembles the observation of the state it writes, for the next observe() (ObservationCache)
     const bool cache_obs = env->n < kGpuLayoutMinEnvs && !rq::noise_enabled(env->cfg) && !params->exposed &&
@@ -95,7 +97,7 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
     StepPair pair{};
     pair.b = batch_of(env); pair.c = rq::step_cfg(env->cfg); pair.sc = rq::sample_cfg(env->cfg); pair.seed = rng->seed;
     pair.params = params->d; pair.state_in = state->d; pair.act = env->act; pair.state_out = next_state->d; pair.st = env->st;
-    pair.mb_step = mb; pair.obs_alt = cache_obs ? env->obs_alt : nullptr;
+    pair.mb_step = mb; pair.obs_alt = cache_obs ? env->obs_alt : nullptr; pair.wr = wr;
     pair.spec = pol != nullptr;
     if (pol) {
         pair.packed = packed_of(pol); pair.hidden_out = pol->hidden_alt; pair.ld_h = pol->ld; pair.pol_act = pol->act;

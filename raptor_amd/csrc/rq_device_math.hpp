@@ -404,6 +404,32 @@ __device__ __forceinline__ float track_accumulate(float sum, float px, float py,
     return __fadd_rn(sum, __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx))));
 }
 
+// ------------------------------------------------------------------ wrench schedule ----
+// A wrench schedule (rq_env_set_wrench_schedule) adds, at every transition, row k of the env's own table [rows][6] = (force in the
+// world frame, torque in the body frame) to the per-episode disturbance of the state, k = the env's episode step count before the
+// step (the count track_row indexes with), clamped to the table.  Relative units scale the force by m g and the torque by m g arm,
+// arm = sqrt(x0^2 + y0^2) of rotor 0.  The three functions below are the only place any path does this arithmetic: single rounded
+// operations in a fixed order, nothing the compiler may contract, so NumPy float32 on the host reproduces the bits
+// (raptor_amd.disturbances.compose).  The composed wrench goes to make_disturbance and nowhere else: the state keeps the base.
+__device__ __forceinline__ void wrench_scales(uint32_t relative, float mass, float gravity, float x0, float y0, float& fs, float& ts) {
+    const float mg = __fmul_rn(mass, gravity);
+    // (sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS this HIP's __fsqrt_rn is the native approximation, off NumPy's
+    // by an ulp for some arms; sqrtf is the IEEE square root under the build's flags - once per launch, not per step)
+    const float arm = sqrtf(__fadd_rn(__fmul_rn(x0, x0), __fmul_rn(y0, y0)));
+    fs = relative ? mg : 1.0f;
+    ts = relative ? __fmul_rn(mg, arm) : 1.0f;
+}
+// row0: the first row of the env's own table in the bank's flat [n_tables * rows][6] block (the host keeps n_tables * rows below 2^28)
+__device__ __forceinline__ void wrench_row(const float* __restrict__ tab, uint32_t rows, uint32_t row0, uint32_t k, float (&r)[6]) {
+    const float* row = tab + (size_t)(row0 + (k < rows ? k : rows - 1u)) * 6u;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) r[j] = row[j];
+}
+__device__ __forceinline__ void wrench_compose(const float (&f)[6], float fs, float ts, const float (&r)[6], float (&w)[6]) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { w[j] = __fadd_rn(f[j], __fmul_rn(fs, r[j])); w[3 + j] = __fadd_rn(f[3 + j], __fmul_rn(ts, r[3 + j])); }
+}
+
 // ------------------------------------------------------------------ parameter sampling -
 
 __device__ __forceinline__ void sample_params(const SampleCfg& c, uint64_t seed, uint32_t epoch, uint64_t genv,

@@ -450,12 +450,15 @@ struct ObsNext {
     const uint32_t* epoch_base;
 };
 
-template <bool ROLLOUT>
+// WRENCH: the env carries a wrench schedule - the transition is computed with the state's per-episode wrench plus the row of the
+// env's episode step count (rq_device_math.hpp wrench_*); the next state keeps the base.  A compile-time switch: the kernels without
+// a schedule are compiled from what they were compiled from before it existed.
+template <bool ROLLOUT, bool WRENCH = false>
 __device__ __forceinline__ void step_env(uint32_t i, const Batch& b, const StepCfg& c, const float* __restrict__ params,
                                          const float* state, float* __restrict__ action, float* next_state,
                                          const StatsPtrs& st, uint32_t flags, const SampleCfg& sc, uint64_t seed,
                                          float* __restrict__ hidden, const float* __restrict__ weights,
-                                         const Mailbox& mb, const ObsNext& on) {
+                                         const Mailbox& mb, const ObsNext& on, const WrenchPtrs& wr = WrenchPtrs{}) {
     if (ROLLOUT && st.frozen[i]) { st.last_done[i] = 4; return; }
     const size_t ld = b.ld;
     const EnvConsts k = make_consts([&](int f) { return field(params, f, ld)[i]; });
@@ -473,7 +476,17 @@ __device__ __forceinline__ void step_env(uint32_t i, const Batch& b, const StepC
         for (int j = 0; j < 4; ++j) a[j] = field(action, j, ld)[i];
     }
     Stats s = load_stats(st, i);
-    const Disturbance ds = make_disturbance(k, c.gravity, f6);
+    Disturbance ds;
+    if constexpr (WRENCH) {
+        float fs, ts, wrow[6], w6[6];
+        wrench_scales(wr.relative, field(params, RQ_P_MASS, ld)[i], c.gravity, field(params, RQ_P_ROTOR_POS, ld)[i],
+                      field(params, (RQ_P_ROTOR_POS + 1), ld)[i], fs, ts);
+        wrench_row(wr.rows, wr.n_rows, wr.row0[i], s.steps, wrow);
+        wrench_compose(f6, fs, ts, wrow, w6);
+        ds = make_disturbance(k, c.gravity, w6);
+    } else {
+        ds = make_disturbance(k, c.gravity, f6);
+    }
     bool term;
     const float r = step_inplace<false>(c, k, ds, y, a, AC01, AC23, term);
     if (c.action_history_raw) { AC01 = f32x2{a[0], a[1]}; AC23 = f32x2{a[2], a[3]}; }   // what ActionHistory(1) keeps
@@ -539,6 +552,19 @@ __global__ __launch_bounds__(kBlock) void k_step(Batch b, StepCfg c, const float
     const uint32_t i = env_index();
     if (i < b.n)
         step_env<ROLLOUT>(i, b, c, params, state, action, next_state, st, flags, sc, seed, hidden, weights, mb, on);
+    mailbox_signal(mb);
+}
+
+// k_step for an env that carries a wrench schedule (a kernel of its own: k_step's argument block and listing stay what they were)
+template <bool ROLLOUT>
+__global__ __launch_bounds__(kBlock) void k_step_wrench(Batch b, StepCfg c, const float* __restrict__ params,
+                                                        const float* state, float* __restrict__ action,
+                                                        float* next_state, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                        uint64_t seed, float* __restrict__ hidden,
+                                                        const float* __restrict__ weights, Mailbox mb, ObsNext on, WrenchPtrs wr) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<ROLLOUT, true>(i, b, c, params, state, action, next_state, st, flags, sc, seed, hidden, weights, mb, on, wr);
     mailbox_signal(mb);
 }
 // ------------------------------------------------------------------ resident executor ---
@@ -1099,10 +1125,16 @@ hipError_t launch_actor_relabel(hipStream_t s, uint32_t n, uint32_t ld, uint32_t
 hipError_t launch_step(hipStream_t s, Batch b, StepCfg c, const float* params, const float* state,
                        float* action, float* next_state, StatsPtrs st, int rollout, uint32_t flags,
                        SampleCfg sc, uint64_t seed, float* hidden, const float* weights, Mailbox mb, float* obs_of_next,
-                       NoiseCfg nc, bool noise, uint32_t obs_epoch, const uint32_t* obs_epoch_base) {
+                       NoiseCfg nc, bool noise, uint32_t obs_epoch, const uint32_t* obs_epoch_base, WrenchPtrs wr) {
     if (b.n == 0) return hipSuccess;
     const ObsNext on{obs_of_next, nc, noise ? 1u : 0u, obs_epoch, obs_epoch_base};
-    if (rollout)
+    if (wr.rows != nullptr && rollout)
+        RQ_KLAUNCH(k_step_wrench<true>, grid_for(b.n, kBlock), kBlock, s, b, c, params, state, action, next_state, st, flags,
+                   sc, seed, hidden, weights, mb, on, wr);
+    else if (wr.rows != nullptr)
+        RQ_KLAUNCH(k_step_wrench<false>, grid_for(b.n, kBlock), kBlock, s, b, c, params, state, action, next_state, st, flags,
+                   sc, seed, hidden, weights, mb, on, wr);
+    else if (rollout)
         RQ_KLAUNCH(k_step<true>, grid_for(b.n, kBlock), kBlock, s, b, c, params, state, action, next_state, st, flags,
                    sc, seed, hidden, weights, mb, on);
     else
@@ -1299,9 +1331,10 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const uint32_t* __restrict__ block_policy, uint32_t image_floats,
                                                                StatsPtrs st, TrajPtrs traj,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool TRACK = false, RATE = false, SAS = false;
+    constexpr bool TRACK = false, RATE = false, SAS = false, WRENCH = false;
     constexpr TrackPtrs trk{};
     constexpr SasArgs sas{};
+    constexpr WrenchPtrs wr{};
     constexpr uint32_t interval = 1;
     const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
 #include "rq_rollout_body.inc"
@@ -1324,8 +1357,9 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false;
+    constexpr bool RATE = true, SAS = false, WRENCH = false;
     constexpr SasArgs sas{};
+    constexpr WrenchPtrs wr{};
     const uint32_t policy = block_policy[blockIdx.x];
     const uint32_t interval = policy_interval[policy];
     const float* __restrict__ packed = images + (size_t)policy * image_floats;
@@ -1376,6 +1410,61 @@ hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, Noi
     const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span, trk};
     if (b.n > 65536u) launch_fused_bank_rate_actor<ActorF32Lean>(s, a, images, block_policy, policy_interval, noise, ar);
     else              launch_fused_bank_rate_actor<ActorF32>(s, a, images, block_policy, policy_interval, noise, ar);
+    return hipGetLastError();
+}
+
+// ---- the fused kernel of an env that carries a wrench schedule
+// The text of k_rollout_fused_bank_rate - the RATE loop, image and interval chosen per workgroup - with WRENCH on: the scales and the
+// env's first row are loaded once per launch, every step asks for its row ahead of the actor and rebuilds the disturbance just before
+// the env step (rq_rollout_body.inc).  The block tables are optional: block_policy == nullptr is ONE policy, whose image is `images`
+// and whose native interval is `single_interval`.  At interval 1 the RATE text computes the plain kernel's bits (see above), so this
+// one entry point serves rq_rollout, rq_rollout_record, rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every
+// native interval.  fp32 actors only: the host refuses the 16-bit policies and the SampleAndSquash stage while a schedule is attached.
+template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_wrench(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ images,
+                                                               const uint32_t* __restrict__ block_policy,
+                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
+                                                               uint32_t single_interval,
+                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool RATE = true, SAS = false, WRENCH = true;
+    constexpr SasArgs sas{};
+    uint32_t policy = 0, interval = single_interval;
+    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
+        policy = block_policy[blockIdx.x];
+        interval = policy_interval[policy];
+    }
+    const float* __restrict__ packed = images + (size_t)policy * image_floats;
+#include "rq_rollout_body.inc"
+}
+
+template <typename ACTOR>
+static inline void launch_fused_wrench_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
+                                             const uint32_t* policy_interval, WrenchPtrs wr, bool noise, bool ar) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
+        hipLaunchKernelGGL((k_rollout_fused_wrench<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
+                           policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, wr, a.span);
+    }, noise, ar, a.traj.obs != nullptr, a.trk.ref != nullptr);
+}
+
+hipError_t launch_rollout_fused_wrench(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                       uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                       const float* params, float* state, float* hidden, const float* weights,
+                                       const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
+                                       uint32_t interval, StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
+                                       unsigned long long* span) {
+    if (b.n == 0 || n_steps == 0) return hipSuccess;
+    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span, trk, interval};
+    if (b.n > 65536u) launch_fused_wrench_actor<ActorF32Lean>(s, a, images, block_policy, policy_interval, wr, noise, ar);
+    else              launch_fused_wrench_actor<ActorF32>(s, a, images, block_policy, policy_interval, wr, noise, ar);
     return hipGetLastError();
 }
 
@@ -1478,10 +1567,26 @@ __global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const 
                        weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{});
 }
 
+// k_step_bank for an env that carries a wrench schedule
+__global__ __launch_bounds__(kBlock) void k_step_bank_wrench(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                             float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                             uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                             const uint32_t* __restrict__ block_policy, WrenchPtrs wr) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                             weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr);
+}
+
 hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
                             uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
-                            const uint32_t* block_policy) {
+                            const uint32_t* block_policy, WrenchPtrs wr) {
     if (b.n == 0) return hipSuccess;
+    if (wr.rows != nullptr) {
+        k_step_bank_wrench<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, params, state, action, st, flags, sc, seed, hidden, weights,
+                                                                    block_policy, wr);
+        return hipGetLastError();
+    }
     k_step_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, params, state, action, st, flags, sc, seed, hidden, weights, block_policy);
     return hipGetLastError();
 }

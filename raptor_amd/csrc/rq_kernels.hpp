@@ -81,6 +81,14 @@ struct TrackPtrs {
 };
 static_assert(sizeof(TrackPtrs) == 32, "the kernels' argument blocks hold TrackPtrs by value");
 
+// A wrench schedule (rq_env_set_wrench_schedule): the bank's tables and the env's per-env first rows (rq_device_math.hpp wrench_*).
+struct WrenchPtrs {
+    const float* rows;        // [n_tables * n_rows][6] row-major: force (world frame), torque (body frame); nullptr = no schedule
+    const uint32_t* row0;     // [ld]: wrench_id[i] * n_rows, the first row of env i's table
+    uint32_t n_rows;          // rows of one table
+    uint32_t relative;        // 1: multiples of m g / m g arm (RQ_WRENCH_RELATIVE); 0: N / N m
+};
+
 // SampleAndSquash output stage of the actor (rq_policy_set_sample_and_squash): mode = rq_sample_and_squash_mode
 struct SasArgs {
     uint32_t mode;                // RQ_SAS_OFF / RQ_SAS_MEAN / RQ_SAS_SAMPLE
@@ -265,7 +273,7 @@ hipError_t launch_step(hipStream_t s, Batch b, StepCfg c, const float* params, c
                        float* action, float* next_state, StatsPtrs st, int rollout, uint32_t flags,
                        SampleCfg sc, uint64_t seed, float* hidden, const float* weights, Mailbox mb = Mailbox{},
                        float* obs_of_next = nullptr, NoiseCfg nc = NoiseCfg{}, bool noise = false, uint32_t obs_epoch = 0,
-                       const uint32_t* obs_epoch_base = nullptr);
+                       const uint32_t* obs_epoch_base = nullptr, WrenchPtrs wr = WrenchPtrs{});
 // chained rollouts under auto-reset: envs left frozen by an earlier rollout start their next episode
 // (sample_initial_state with the env's episode counter + policy state reset), as the fused kernel's prologue does
 hipError_t launch_thaw_frozen(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
@@ -289,6 +297,15 @@ hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg
                                      const float* params, float* state, float* hidden, const float* weights,
                                      const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
                                      uint32_t interval, unsigned long long* span = nullptr);
+// The fused kernel for an env that carries a wrench schedule (wr.rows != nullptr; fp32 policies, no SampleAndSquash stage): the RATE
+// text with the wrench of every step composed from the env's own row.  block_policy == nullptr: one policy - `images` is its operand
+// image, `interval` its native interval; otherwise a policy bank's tables, as launch_rollout_fused_bank_rate takes them.
+hipError_t launch_rollout_fused_wrench(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
+                                       uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
+                                       const float* params, float* state, float* hidden, const float* weights,
+                                       const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
+                                       uint32_t interval, StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
+                                       unsigned long long* span = nullptr);
 // ---- policy bank (rq_rollout_policies, rq_rollout_policies_track): P fp32 operand images [P][RQ_PACKED_FLOATS], raw weights
 // [P][RQ_POLICY_NUM_WEIGHTS], block_policy [ceil(n / 64)]: the policy of each 64-env block, and policy_interval [P]: every entry
 // 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL (rq_policy_bank_set_native_interval).  Plain launches: none of them appends to a GraphSink.
@@ -315,7 +332,7 @@ hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* i
 // initial state.
 hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
                             uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
-                            const uint32_t* block_policy);
+                            const uint32_t* block_policy, WrenchPtrs wr = WrenchPtrs{});
 hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
                                    StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy);
 hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden, const float* weights, const uint32_t* block_policy);

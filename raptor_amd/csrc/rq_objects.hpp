@@ -58,6 +58,7 @@ struct StepPair {
     rq::Batch b; rq::StepCfg c; rq::SampleCfg sc; uint64_t seed;
     const float* params; const float* state_in; float* act; float* state_out; rq::StatsPtrs st;
     rq::Mailbox mb_step; float* obs_alt;
+    rq::WrenchPtrs wr;             // the env's wrench schedule (rows == nullptr: none)
     bool spec;
     const float* packed; float* hidden_out; uint32_t ld_h; float* pol_act; int precision; rq::SasArgs sas;
     rq::Mailbox mb_spec; const float* hidden_in;
@@ -192,6 +193,7 @@ struct rq_rng {
     bool initialized = false;
 };
 
+struct rq_wrench_bank;
 struct rq_env {
     rq_device* dev = nullptr;
     uint64_t uid = fresh_version();   // what the device's caches know this env by, beside its address
@@ -213,6 +215,13 @@ struct rq_env {
     bool row0_valid = false;
     uint64_t row0_key = 0, row0_gen = 0;
     std::vector<uint32_t> row0_ids;
+    // The wrench schedule (rq_env_set_wrench_schedule): the bank, the ids it was attached with, and beside the statistics the [ld]
+    // first rows (id * rows) every stepping kernel reads.  wrench_gen names the attachment (0: none): a chained rollout's hipGraph
+    // is keyed by it.  The bank cannot be destroyed while it is attached, so the pointer is followed.
+    rq_wrench_bank* wrench = nullptr;
+    std::vector<uint32_t> wrench_ids;
+    DeviceBuffer<uint32_t> wrench_row0;
+    uint64_t wrench_gen = 0;
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
     // epoch-counter bump); one executable graph per distinct argument set
     struct GraphEntry {
@@ -222,6 +231,7 @@ struct rq_env {
         const float* ref; uint32_t ref_rows;     // tracked rollouts: the reference table (nullptr: untracked)
         uint32_t row0_at; uint64_t row0_gen;     // a reference bank's per-env first rows and which upload they are (0, 0: none)
         uint32_t interval;                       // the policy's native interval: the actor nodes of another one are other kernels
+        uint64_t wrench_gen;                     // the env's wrench schedule at construction (0: none): the step nodes carry its pointers
         hipGraphExec_t exec;
     };
     std::vector<GraphEntry> graphs;
@@ -280,6 +290,17 @@ struct rq_reference_bank {
     uint32_t n_refs = 0, rows = 0;
     DeviceBuffer<float> d;              // [n_refs * rows][6] row-major
     uint64_t uid = fresh_version();     // what an env knows the bank by, beside its address (rq_env::row0_key)
+};
+
+// the tables of a wrench schedule on the device (rq_wrench_bank_create), one after another: env i of an env it is attached to reads
+// the table that begins at row wrench_id[i] * rows
+struct rq_wrench_bank {
+    const rq_device* dev = nullptr;     // compared, never followed (as rq_reference::dev)
+    int ordinal = 0;
+    uint32_t n_tables = 0, rows = 0;
+    int units = RQ_WRENCH_RELATIVE;
+    DeviceBuffer<float> d;              // [n_tables * rows][6] row-major
+    uint32_t attached = 0;              // live envs it is attached to: rq_wrench_bank_destroy is refused while any
 };
 
 struct rq_policy {
@@ -418,6 +439,12 @@ int state_make_private(rq_state* s, bool keep);
 inline rq::Batch batch_of(const rq_env* env) { return {env->n, env->ld, env->offset}; }
 // the env's tracking statistics, allocated and zeroed (on the device's stream) at their first use; call inside a DeviceScope
 int env_track_stats(rq_env* env, float** sum_sq, uint32_t** steps);
+// The env's wrench schedule as the kernels take it (*wr all-null: none attached).  Every call that steps asks here before anything is
+// enqueued: a bank with fewer rows than episode_step_limit is refused (`who`: the caller's name; the config may have changed since
+// the schedule was attached).
+int env_wrench(const char* who, const rq_env* env, rq::WrenchPtrs* wr);
+// ... and what fused mode cannot fly while a schedule is attached, refused naming the schedule (`what`: bf16 / f16x2 policy, ...)
+int wrench_refuses_fused(const char* who, const char* what);
 
 // ---- rq_small_batch.cpp: the small-batch loop (rq_device::mailbox, obs_cache, spec) ----
 void small_batch_setup(rq_device* dev);      // rq_device_create: settings
@@ -477,7 +504,7 @@ int require_bank_native_rate(const rq_policy_bank* bank, const char* what);
 
 // ---- rq_capi_rollout.cpp ----
 // What a rollout of any kind (a policy's, a policy bank's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope:
-// the checks all make, and where a recording goes; rollout_check_reference, behind the caller's device check: a tracked rollout's
+// the checks all make (the env's wrench schedule among them: RolloutFrame::wr), and where a recording goes; rollout_check_reference, behind the caller's device check: a tracked rollout's
 // table (`who`: the caller's name, as its own messages begin).  rollout_track, inside the scope: the tracked rollout's pointers (a
 // null reference: none).  rollout_begin, after what is the caller's own (policy sizing; tile list and sink): the observation cache
 // dropped, the state private, the env's configuration as the kernels take it, the `done` rows preset.  rollout_end: the noise epoch,
@@ -486,6 +513,7 @@ struct RolloutFrame {
     rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
     rq::TrackPtrs trk{};                                          // ref != nullptr: a tracked rollout
     uint64_t row0_gen = 0;                                         // a reference bank's rollout: rq_env::row0_gen
+    rq::WrenchPtrs wr{};                                           // rows != nullptr: the env carries a wrench schedule (rollout_check)
     rq::Batch b; rq::StepCfg sc; rq::NoiseCfg nc; rq::SampleCfg smp; bool noise;
 };
 int rollout_check(RolloutFrame& f, const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,

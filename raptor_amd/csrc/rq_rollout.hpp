@@ -67,8 +67,9 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const float* __restrict__ packed, StatsPtrs st,
                                                                TrajPtrs traj, SasArgs sas,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool TRACK = false, RATE = false;
+    constexpr bool TRACK = false, RATE = false, WRENCH = false;
     constexpr TrackPtrs trk{};
+    constexpr WrenchPtrs wr{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -86,8 +87,9 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const float* __restrict__ packed, StatsPtrs st,
                                                                TrajPtrs traj, TrackPtrs trk,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool TRACK = true, SAS = false, RATE = false;
+    constexpr bool TRACK = true, SAS = false, RATE = false, WRENCH = false;
     constexpr SasArgs sas{};
+    constexpr WrenchPtrs wr{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -105,8 +107,9 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const float* __restrict__ packed, StatsPtrs st,
                                                                TrajPtrs traj, TrackPtrs trk, uint32_t interval,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false;
+    constexpr bool RATE = true, SAS = false, WRENCH = false;
     constexpr SasArgs sas{};
+    constexpr WrenchPtrs wr{};
 #include "rq_rollout_body.inc"
 }
 

@@ -2,8 +2,9 @@
 // (TRACK = false), k_rollout_fused_track (TRACK = true, SAS = false) and k_rollout_fused_rate (RATE = true, SAS = false).  Text, not a function: the untracked kernel is compiled from
 // exactly what it was compiled from when the body stood between its braces - its listing does not move when the tracked variant
 // changes - and a __device__ function in between does cost that (the work-group-size folds of a kernel are made before inlining).
-// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, ACTOR and the names
-// b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, interval, span.
+// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, ACTOR and the names
+// b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, interval, span.
+// WRENCH (k_rollout_fused_wrench alone; every other entry point defines it false and an empty wr): the env carries a wrench schedule.
     // kernel-level timing (rq_device_set_rollout_timing): every wave leaves the wall-clock ticks (constant rate) at which it
     // came in and went out, and its XCD: the eight dies' counters are offset against one another by microseconds, one die's
     // are consistent - the host takes first-in / last-out per die
@@ -48,6 +49,14 @@
     // The hidden state moves on at the steps where it is 0; at the others the policy acts from the last committed state.
     [[maybe_unused]] uint32_t phase = 0;
     if constexpr (RATE) phase = ep_steps % interval;
+    // WRENCH: the two scales (from the params of this call) and the first row of the env's own table, once per launch
+    [[maybe_unused]] float wr_fs = 1.0f, wr_ts = 1.0f;
+    [[maybe_unused]] uint32_t wr_row0 = 0;
+    if constexpr (WRENCH) {
+        wrench_scales(wr.relative, field(params, RQ_P_MASS, ld)[i], c.gravity, field(params, RQ_P_ROTOR_POS, ld)[i],
+                      field(params, (RQ_P_ROTOR_POS + 1), ld)[i], wr_fs, wr_ts);
+        wr_row0 = wr.row0[i];
+    }
     const uint8_t last_t_raw = st.last_terminated[i];
     uint8_t last_d = AUTORESET ? (uint8_t)0 : st.last_done[i];       // auto-reset: rebuilt in the epilogue
     const uint8_t frozen_raw = st.frozen[i];
@@ -165,6 +174,10 @@
         const uint64_t live = AUTORESET ? ~0ull : __builtin_amdgcn_ballot_w64(!frozen);
         if (!AUTORESET && live == 0) break;   // wave-uniform exit: every env of the wave is frozen
         float o[22], a[4];
+        // WRENCH: this step's row of the env's own table (lanes are at different rows: per-lane loads of a table that stays in the
+        // cache), asked for here so that the actor's MFMA batches cover the latency; it is consumed just before the env step
+        [[maybe_unused]] float wr_row[6];
+        if constexpr (WRENCH) wrench_row(wr.rows, wr.n_rows, wr_row0, ep_steps, wr_row);
         observe_head<NOISE>(y, LA01, LA23, nc, seed, epoch0 + t, genv, o);
         if constexpr (TRACK) {
             // the setpoint of this step: the row of the env's own episode step count (lanes are at different rows: per-lane
@@ -229,6 +242,11 @@
         // (round 4 measured the 16-bit builds without this barrier - the env step free to mix with their co-executing MFMAs:
         // no gain)
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (WRENCH) {      // the wrench of this transition: the per-episode base (f6, which the state keeps) + the scaled row
+            float w6[6];
+            wrench_compose(f6, wr_fs, wr_ts, wr_row, w6);
+            ds = make_disturbance(k, c.gravity, w6);
+        }
         QuadState yn = y;
         f32x2 A01, A23;
         bool term;

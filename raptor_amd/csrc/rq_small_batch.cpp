@@ -162,7 +162,8 @@ rq_policy* speculation_candidate(rq_device* dev, const rq_env* env, bool cache_o
     if (!cache_obs) return nullptr;
     speculation_unused(dev);      // the previous step's speculated policy step, if nobody took it (this may suspend speculation)
     const Speculation& sp = dev->spec;
-    rq_policy* pol = sp.enabled && !sp.suspended && action ? sp.last_policy : nullptr;
+    // (an env that carries a wrench schedule is stepped by plain launches: neither speculated on nor handed to the resident executor)
+    rq_policy* pol = sp.enabled && !sp.suspended && action && !env->wrench ? sp.last_policy : nullptr;
     return pol && policy_registry(pol, 0) && pol->dev == dev && pol->batch == env->n && pol->ld == env->ld && pol->hidden &&
            pol->hidden_alt && !pol->needs_reset && pol->sas_mode != RQ_SAS_SAMPLE && pol->native_interval == 1 ? pol : nullptr;
 }
@@ -193,7 +194,7 @@ int speculation_take(rq_device* dev, rq_policy* pol, const float* observation, u
 // the two launches of a small-batch step on the device's stream (also the replay of a command the resident executor never consumed)
 hipError_t launch_step_pair(rq_device* dev, const StepPair& p) {
     hipError_t e = rq::launch_step(dev->stream, p.b, p.c, p.params, p.state_in, p.act, p.state_out, p.st, /*rollout=*/0, 0u, p.sc, p.seed,
-                                   nullptr, nullptr, p.mb_step, p.obs_alt, rq::NoiseCfg{}, false, 0u, nullptr);
+                                   nullptr, nullptr, p.mb_step, p.obs_alt, rq::NoiseCfg{}, false, 0u, nullptr, p.wr);
     if (e == hipSuccess && p.spec)
         e = rq::launch_actor_step(dev->stream, p.b.n, p.packed, p.obs_alt, p.b.ld, p.hidden_out, p.ld_h, p.pol_act, p.ld_h, nullptr,
                                   p.precision, p.sas, p.mb_spec, p.hidden_in);

@@ -37,7 +37,7 @@ from . import _lib
 from ._lib import (ACTION_DIM, OBSERVATION_DIM, PARAM_DIM, STATE_DIM, ROLLOUT_AUTORESET, ROLLOUT_CHAINED,
                    ROLLOUT_FUSED, EnvConfig, RaptorQuadError)
 
-__all__ = ["Device", "Reference", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
+__all__ = ["Device", "Reference", "WrenchBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
 
 
 class UI:
@@ -212,6 +212,28 @@ class ReferenceBank:
         self._fin = weakref.finalize(self, _lib.load().rq_reference_bank_destroy, h)
 
 
+class WrenchBank:
+    """M wrench tables of the same length for ``env.set_wrench_schedule(bank, ids)``: ``tables`` float32 [M, rows, 6] (or a list of M
+    [rows, 6] tables; ``raptor_amd.disturbances`` builds them), columns 0..2 a force in the world frame and 3..5 a torque in the body
+    frame.  ``units``: "relative" (multiples of m g and of m g arm, the default) or "absolute" (N and N m).  While the bank is
+    attached to an env, every transition of env i adds the row of its own episode step count of table ``ids[i]`` to the per-episode
+    disturbance (include/raptor_quad.h "Wrench schedule").  The tables are copied to ``device`` once, here."""
+
+    def __init__(self, device, tables, units="relative"):
+        from . import disturbances
+        t = disturbances.check_tables(tables)          # refused before the device is touched
+        u = disturbances.check_units(units)
+        h = C.c_void_p()
+        _lib.call("rq_wrench_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), u, C.byref(h))
+        self._h = h
+        self._device = device
+        self.n_tables = int(t.shape[0])
+        self.rows = int(t.shape[1])
+        self.units = units
+        # (the library refuses to destroy a bank that is still attached to a live env; the envs hold their bank, so it outlives them)
+        self._fin = weakref.finalize(self, _lib.load().rq_wrench_bank_destroy, h)
+
+
 def _checked_reference(reference, reference_ids, n_envs):
     """What a rollout's ``reference`` / ``reference_ids`` pair must be, before any library call -> the ids as uint32 (a
     ``ReferenceBank``) or None (a ``Reference``, or no reference); ValueError otherwise."""
@@ -225,6 +247,21 @@ def _checked_reference(reference, reference_ids, n_envs):
     if reference is not None and not isinstance(reference, Reference):
         raise ValueError("reference must be an l2f.Reference or an l2f.ReferenceBank")
     return None
+
+
+def _checked_wrench_ids(env, wrench_ids, ref_ids, n_envs):
+    """What ``wrench_ids`` of ``PolicyBank.evaluate`` / ``TeacherBank.closed_loop`` must be, before any library call -> the ids as
+    uint32, or None (none given); ValueError otherwise."""
+    if wrench_ids is None:
+        return None
+    schedule = getattr(env, "wrench_schedule", None)
+    if schedule is None:
+        raise ValueError("wrench_ids name tables of the env's wrench schedule: attach one first (env.set_wrench_schedule(bank))")
+    if ref_ids is not None:
+        raise ValueError("wrench_ids group the tracking error by disturbance scenario and reference_ids by setpoint: give one of them "
+                         "(a single l2f.Reference goes with wrench_ids)")
+    from .disturbances import check_wrench_ids
+    return check_wrench_ids(wrench_ids, schedule[0].n_tables, n_envs)
 
 
 class _Handle:
@@ -431,6 +468,31 @@ class VectorModule:
 
             def reset_statistics(self):
                 _lib.call("rq_env_reset_statistics", self._require("environment"))
+
+            # --- wrench schedule (scheduled gusts, pokes, payloads: raptor_amd.disturbances) ---
+            _wrench = None
+
+            def set_wrench_schedule(self, bank, ids=None):
+                """Attach ``bank`` (an ``l2f.WrenchBank``): from now on every transition of env i, in every call that steps this
+                env, is computed with the row of its episode step count of table ``ids[i]`` ([N] integers, free per env; None:
+                table 0 for every env) added to its per-episode disturbance.  The tables must cover ``episode_step_limit``."""
+                if not isinstance(bank, WrenchBank):
+                    raise ValueError("bank must be an l2f.WrenchBank (clear_wrench_schedule() detaches)")
+                from .disturbances import check_wrench_ids
+                a = (np.zeros(mod.N_ENVIRONMENTS, np.uint32) if ids is None
+                     else check_wrench_ids(ids, bank.n_tables, mod.N_ENVIRONMENTS))
+                _lib.call("rq_env_set_wrench_schedule", self._require("environment"), bank._h, a.ctypes.data)
+                self._wrench = (bank, a.copy())
+
+            def clear_wrench_schedule(self):
+                if self._h is not None:
+                    _lib.call("rq_env_set_wrench_schedule", self._h, None, None)
+                self._wrench = None
+
+            @property
+            def wrench_schedule(self):
+                """(bank, ids) of the attached schedule, or None."""
+                return None if self._wrench is None else (self._wrench[0], self._wrench[1].copy())
 
             def tracking_error(self):
                 """-> (sum_sq [N] float32, steps [N] uint32): per env, the running sum of |p - p_ref|^2 over the steps it took in

@@ -209,22 +209,32 @@ class PolicyBank:
             _lib.call("rq_rollout_policies_track_refs", *args, reference._h, ref_ids.ctypes.data)
 
     def evaluate(self, vector, device, env, params, state, rng, n_steps, policy_ids=None, mode="fused", autoreset=True,
-                 reference=None, reference_ids=None):
+                 reference=None, reference_ids=None, wrench_ids=None):
         """The closed-loop evaluation of the whole bank: statistics and hidden state start afresh, one rollout of ``n_steps`` flies
         env i with policy ``policy_ids[i]`` (default: blocks dealt round-robin) at its native interval ->
         ``policy_episode_table`` of what it finished.  With ``reference`` the bank tracks that moving setpoint and the table gains
         ``tracking_rmse`` [P] (``policy_tracking_table`` of ``env.tracking_error()``, which starts afresh too).  With an
         ``l2f.ReferenceBank`` and ``reference_ids`` (``tracking.spread_reference_ids(N, M, policy_ids)`` deals them evenly inside
-        every policy's envs) ``tracking_rmse`` is [P, M]: policy p on setpoint r (``tracking.reference_tracking_table``)."""
+        every policy's envs) ``tracking_rmse`` is [P, M]: policy p on setpoint r (``tracking.reference_tracking_table``).
+        ``wrench_ids`` ([N] integers; the env carries a wrench schedule, ``env.set_wrench_schedule(bank)``): env i flies
+        disturbance scenario ``wrench_ids[i]`` of the attached bank (dealt like reference ids) and, on an ``l2f.Reference`` such as
+        ``tracking.hold``, ``tracking_rmse`` is [P, M] over the scenarios: P checkpoints x M disturbances in one launch."""
         ids = block_policy_assignment(vector.N_ENVIRONMENTS, self.n_policies) if policy_ids is None else policy_ids
-        from .l2f import _checked_reference
+        from .l2f import _checked_reference, _checked_wrench_ids
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
+        w_ids = _checked_wrench_ids(env, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
+        if w_ids is not None:
+            env.set_wrench_schedule(env.wrench_schedule[0], w_ids)
         env.reset_statistics()
         self.reset()
         self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
                  reference_ids=reference_ids)
         table = policy_episode_table(env, ids, self.n_policies)
-        if ref_ids is not None:
+        if w_ids is not None and reference is not None:
+            from .tracking import reference_tracking_table
+            sum_sq, steps = env.tracking_error()
+            table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, w_ids, env.wrench_schedule[0].n_tables, ids, self.n_policies)
+        elif ref_ids is not None:
             from .tracking import reference_tracking_table
             sum_sq, steps = env.tracking_error()
             table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, ref_ids, reference.n_references, ids, self.n_policies)

@@ -180,22 +180,32 @@ class TeacherBank:
             _lib.call("rq_rollout_teachers_track_refs", *args, reference._h, ref_ids.ctypes.data)
 
     def closed_loop(self, vector, device, env, params, state, rng, n_steps, teacher_ids, mode="fused", autoreset=True,
-                    reference=None, reference_ids=None):
+                    reference=None, reference_ids=None, wrench_ids=None):
         """The closed-loop check of the whole bank: the env's statistics start afresh, one ``fly`` of ``n_steps`` ->
         ``teacher_episode_table`` of what it finished.  With ``reference`` the table gains ``tracking_rmse`` [K]
         (``policy_bank.policy_tracking_table`` of ``env.tracking_error()``, grouped by teacher); with an ``l2f.ReferenceBank`` and
         ``reference_ids`` (``tracking.spread_reference_ids(N, M, teacher_ids)`` deals them evenly inside every teacher's envs) it is
-        [K, M]: teacher k on setpoint r (``tracking.reference_tracking_table``) - what a student's tracking error stands against."""
-        from .l2f import _checked_reference
+        [K, M]: teacher k on setpoint r (``tracking.reference_tracking_table``) - what a student's tracking error stands against.
+        ``wrench_ids`` ([N] integers; the env carries a wrench schedule): env i flies disturbance scenario ``wrench_ids[i]`` of the
+        attached bank and, on an ``l2f.Reference``, ``tracking_rmse`` is [K, M] over the scenarios (``mode="chained"``: the fused
+        teacher kernel does not fly a schedule)."""
+        from .l2f import _checked_reference, _checked_wrench_ids
         ids = np.ascontiguousarray(teacher_ids, np.uint32)
         if ids.shape != (vector.N_ENVIRONMENTS,):
             raise ValueError("teacher_ids must hold one id per env")
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
+        w_ids = _checked_wrench_ids(env, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
+        if w_ids is not None:
+            env.set_wrench_schedule(env.wrench_schedule[0], w_ids)
         env.reset_statistics()
         self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
                  reference_ids=reference_ids)
         table = teacher_episode_table(env, ids, self.n_teachers)
-        if ref_ids is not None:
+        if w_ids is not None and reference is not None:
+            from .tracking import reference_tracking_table
+            sum_sq, steps = env.tracking_error()
+            table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, w_ids, env.wrench_schedule[0].n_tables, ids, self.n_teachers)
+        elif ref_ids is not None:
             from .tracking import reference_tracking_table
             sum_sq, steps = env.tracking_error()
             table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, ref_ids, reference.n_references, ids, self.n_teachers)
