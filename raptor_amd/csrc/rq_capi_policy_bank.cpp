@@ -253,7 +253,7 @@ RQ_API int rq_policy_bank_get_hidden(rq_policy_bank* bank, float* host_out, uint
 }
 
 // rq_rollout_policies (ref == nullptr) and rq_rollout_policies_track.  With no reference and every interval 1 the launches are the
-// ones a bank's rollout always made; otherwise the RATE kernels, which take both.
+// ones a bank's rollout always made; otherwise the RATE kernels, which take both (fused: rq_fused_route.hpp).
 static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
                                  const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                  rq_trajectory* traj, const rq_reference* ref, const rq_reference_bank* refs = nullptr,
@@ -277,18 +277,10 @@ static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* p
     if (mode == RQ_ROLLOUT_FUSED) {
         unsigned long long* span = nullptr;
         rc = fused_span_begin(__func__, dev, env, n_steps, &span); if (rc) return rc;
-        if (f.wr.rows)
-            RQ_HIP(rq::launch_rollout_fused_wrench(dev->stream, f.b, f.sc, f.nc, f.noise, f.smp, rng->seed, rng->epoch, n_steps, flags,
-                                                   params->d, state->d, bank->hidden, bank->weights, bank->images, bank->table,
-                                                   bank->intervals_dev, 1u, env->st, f.tp, f.trk, f.wr, span));
-        else if (f.trk.ref || rated)
-            RQ_HIP(rq::launch_rollout_fused_bank_rate(dev->stream, f.b, f.sc, f.nc, f.noise, f.smp, rng->seed, rng->epoch, n_steps, flags,
-                                                      params->d, state->d, bank->hidden, bank->weights, bank->images, bank->table,
-                                                      bank->intervals_dev, env->st, f.tp, f.trk, span));
-        else
-            RQ_HIP(rq::launch_rollout_fused_bank(dev->stream, f.b, f.sc, f.nc, f.noise, f.smp, rng->seed, rng->epoch, n_steps, flags,
-                                                 params->d, state->d, bank->hidden, bank->weights, bank->images, bank->table, env->st,
-                                                 f.tp, span));
+        rq::FusedArgs a = fused_args(f, env, params, state, rng, n_steps, flags, span);
+        a.hidden = bank->hidden; a.weights = bank->weights;
+        a.images = bank->images; a.block_policy = bank->table; a.policy_interval = bank->intervals_dev; a.bank_rated = rated;
+        RQ_HIP(rq::launch_rollout_fused(dev->stream, a));
         fused_span_end(dev, n_steps);
     } else {
         rc = rollout_chained(__func__, f, dev, env, params, state, rng, n_steps, flags, traj,

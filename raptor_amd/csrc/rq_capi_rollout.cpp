@@ -132,6 +132,17 @@ void rollout_end(rq_state* state, rq_rng* rng, uint32_t n_steps, rq_trajectory* 
     if (n_steps) state->version = fresh_version();
 }
 
+rq::FusedArgs fused_args(const RolloutFrame& f, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,
+                         uint32_t n_steps, uint32_t flags, unsigned long long* span) {
+    rq::FusedArgs a;
+    a.b = f.b; a.c = f.sc; a.nc = f.nc; a.sc = f.smp; a.noise = f.noise;
+    a.seed = rng->seed; a.epoch0 = rng->epoch; a.n_steps = n_steps;
+    a.autoreset = (flags & RQ_ROLLOUT_AUTORESET) != 0;
+    a.params = params->d; a.state = state->d; a.st = env->st;
+    a.traj = f.tp; a.trk = f.trk; a.wr = f.wr; a.span = span;
+    return a;
+}
+
 int fused_span_begin(const char* who, rq_device* dev, const rq_env* env, uint32_t n_steps, unsigned long long** span) {
     if (dev->k_timing && n_steps) {                   // one (in, out) record per wave = per workgroup of the fused kernel
         const uint32_t waves = (env->n + 63u) / 64u;
@@ -183,29 +194,14 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
     rc = rollout_track(f, env, ref); if (rc) return rc;
     rc = rollout_track_refs(f, dev, env, refs, reference_id); if (rc) return rc;
     rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
-    const rq::TrajPtrs& tp = f.tp; const rq::TrackPtrs& trk = f.trk;
-    const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
-    const bool noise = f.noise;
     if (mode == RQ_ROLLOUT_FUSED) {
         unsigned long long* span = nullptr;
         rc = fused_span_begin(__func__, dev, env, n_steps, &span); if (rc) return rc;
-        if (f.wr.rows) {
-            RQ_HIP(rq::launch_rollout_fused_wrench(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
-                                                   params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), nullptr, nullptr,
-                                                   interval, env->st, tp, trk, f.wr, span));
-        } else if (interval > 1) {
-            RQ_HIP(rq::launch_rollout_fused_rate(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
-                                                 params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
-                                                 policy->precision, tp, trk, interval, span));
-        } else if (tracked) {
-            RQ_HIP(rq::launch_rollout_fused_track(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
-                                                  params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
-                                                  policy->precision, tp, trk, span));
-        } else {
-            RQ_HIP(rq::launch_rollout_fused(dev->stream, b, sc, nc, noise, smp, rng->seed, rng->epoch, n_steps, flags,
-                                            params->d, state->d, policy->hidden, policy->w_dev, packed_of(policy), env->st,
-                                            policy->precision, sas_of(policy, rng->epoch, nullptr, env->offset), tp, span));
-        }
+        rq::FusedArgs a = fused_args(f, env, params, state, rng, n_steps, flags, span);
+        a.hidden = policy->hidden; a.weights = policy->w_dev;
+        a.precision = policy->precision; a.images = packed_of(policy); a.interval = interval;
+        a.sas = sas_of(policy, rng->epoch, nullptr, env->offset);
+        RQ_HIP(rq::launch_rollout_fused(dev->stream, a));
         fused_span_end(dev, n_steps);
     } else {
         // one step = observe -> evaluate_step -> step (-> record) on the stream.  Without a recording the step kernel
@@ -218,9 +214,9 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
         auto enqueue_step = [&](uint32_t epoch, const uint32_t* epoch_base, uint32_t t_record) -> hipError_t {
             hipError_t e = hipSuccess;
             if (!fold_observe)
-                e = rq::launch_observe(dev->stream, b, nc, noise, rng->seed, epoch, epoch_base, params->d, state->d, env->obs);
+                e = rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, epoch, epoch_base, params->d, state->d, env->obs);
             if (e == hipSuccess && tracked)
-                e = rq::launch_track_shift(dev->stream, b, state->d, env->st, env->obs, trk);
+                e = rq::launch_track_shift(dev->stream, f.b, state->d, env->st, env->obs, f.trk);
             if (e == hipSuccess && interval > 1)     // the env's episode step count is that of this step's observation: k_step moves it on
                 e = rq::launch_actor_step_rate(dev->stream, env->n, packed_of(policy), env->obs, env->ld, policy->hidden,
                                                policy->ld, env->act, env->ld, env->st.frozen, policy->precision, env->st.steps,
@@ -230,33 +226,34 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                                           policy->ld, env->act, env->ld, env->st.frozen, policy->precision,
                                           sas_of(policy, epoch, epoch_base, env->offset));
             if (e == hipSuccess)
-                e = rq::launch_step(dev->stream, b, sc, params->d, state->d, env->act, state->d, env->st,
-                                    /*rollout=*/1, flags, smp, rng->seed, policy->hidden, policy->w_dev, rq::Mailbox{},
-                                    fold_observe ? env->obs : nullptr, nc, noise, epoch + 1, epoch_base, f.wr);
+                e = rq::launch_step(dev->stream, f.b, f.sc, params->d, state->d, env->act, state->d, env->st,
+                                    /*rollout=*/1, flags, f.smp, rng->seed, policy->hidden, policy->w_dev, rq::Mailbox{},
+                                    fold_observe ? env->obs : nullptr, f.nc, f.noise, epoch + 1, epoch_base, f.wr);
             if (e == hipSuccess && traj) {
-                rq::TrajPtrs tt = tp; tt.t0 = tp.t0 + t_record;
-                e = rq::launch_record(dev->stream, b, env->obs, env->act, env->st, tt);
+                rq::TrajPtrs tt = f.tp; tt.t0 = f.tp.t0 + t_record;
+                e = rq::launch_record(dev->stream, f.b, env->obs, env->act, env->st, tt);
             }
             return e;
         };
         if (n_steps && (flags & RQ_ROLLOUT_AUTORESET))   // envs frozen by an earlier rollout start their next episode
-            RQ_HIP(rq::launch_thaw_frozen(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, policy->hidden,
+            RQ_HIP(rq::launch_thaw_frozen(dev->stream, f.b, f.smp, rng->seed, params->d, state->d, env->st, policy->hidden,
                                           policy->w_dev));
         if (fold_observe && n_steps)     // the rollout's first observation (after the thaw: of the re-sampled states)
-            RQ_HIP(rq::launch_observe(dev->stream, b, nc, noise, rng->seed, rng->epoch, nullptr, params->d, state->d, env->obs));
+            RQ_HIP(rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, rng->epoch, nullptr, params->d, state->d, env->obs));
         uint32_t done_steps = 0;
         if (!traj && n_steps >= kGraphSteps) {
             // replay a captured graph of kGraphSteps steps; kernel boundaries stay (~1.5 us each) but the
             // host no longer pays ~3.5 us per launch, which is what bounds small batches
+            rq_env::GraphKey key;      // what the graph's nodes carry by value: another value of any of these is another graph
+            key.params = params->d; key.state = state->d; key.hidden = policy->hidden; key.packed = packed_of(policy);
+            key.weights = policy->w_dev; key.obs = env->obs; key.flags = flags; key.precision = policy->precision; key.cfg = env->cfg;
+            key.seed = rng->seed; key.sas_mode = policy->sas_mode; key.sas_seed = policy->sas_seed; key.ls_image = policy->ls_image;
+            key.ref = f.trk.ref; key.ref_rows = f.trk.rows; key.row0_at = f.trk.row0_at;
+            key.row0_gen = f.row0_gen;      // (a reference bank: which ids the rows were built from)
+            key.interval = interval; key.wrench_gen = env->wrench_gen;
             hipGraphExec_t exec = nullptr;
             for (auto& g : env->graphs)
-                if (g.params == params->d && g.state == state->d && g.hidden == policy->hidden && g.obs == env->obs &&
-                    g.packed == packed_of(policy) && g.weights == policy->w_dev && g.flags == flags &&
-                    g.precision == policy->precision && g.seed == rng->seed && g.sas_mode == policy->sas_mode &&
-                    g.sas_seed == policy->sas_seed && g.ls_image == policy->ls_image && g.ref == trk.ref && g.ref_rows == trk.rows &&
-                    g.row0_at == trk.row0_at && g.row0_gen == f.row0_gen &&      // (a reference bank: which ids the rows were built from)
-                    g.interval == interval && g.wrench_gen == env->wrench_gen &&
-                    std::memcmp(&g.cfg, &env->cfg, sizeof(rq_env_config)) == 0) { exec = g.exec; break; }
+                if (g.key == key) { exec = g.exec; break; }
             if (!exec) {
                 // Built node by node (rq_kernels.hpp GraphSink), NOT by stream capture: while any stream of a process captures, HIP
                 // fails hipDeviceSynchronize on every other thread (hipErrorStreamCaptureUnsupported) and invalidates the capture -
@@ -286,9 +283,7 @@ static int rollout_impl(rq_device* dev, rq_env* env, const rq_params* params, rq
                         env->graphs.erase(env->graphs.begin());
                     }
                     try {                       // nothing throws across the boundary
-                        env->graphs.push_back({params->d, state->d, policy->hidden, packed_of(policy), policy->w_dev, env->obs, flags,
-                                               policy->precision, env->cfg, rng->seed, policy->sas_mode, policy->sas_seed,
-                                               policy->ls_image, trk.ref, trk.rows, trk.row0_at, f.row0_gen, interval, env->wrench_gen, exec});
+                        env->graphs.push_back({key, exec});
                     } catch (const std::bad_alloc&) {
                         (void)hipGraphExecDestroy(exec);
                         return fail(RQ_ERR_OUT_OF_MEMORY, "rollout: host allocation failed");

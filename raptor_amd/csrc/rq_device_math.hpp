@@ -1112,7 +1112,7 @@ struct ActorF32T {
 
 
 typedef ActorF32T<false> ActorF32;       // 512-register budget (1 wave/SIMD), all four tiles in flight
-typedef ActorF32T<true> ActorF32Lean;    // 256-register budget (2 waves/SIMD); which one runs: launch_rollout_fused
+typedef ActorF32T<true> ActorF32Lean;    // 256-register budget (2 waves/SIMD); which one runs: route_fused (rq_fused_route.hpp)
 
 // ---- bf16 operands on v_mfma_f32_16x16x32_bf16, fp32 accumulate, fp32 gates (BASELINE config 5) -----
 // Same Q layout and the same register-stationary scheme; K = 32 per instruction and lane-group q

@@ -188,7 +188,7 @@ hipError_t launch_policy_grad_forward(hipStream_t s, uint32_t n, uint32_t ld, ui
     if (n == 0 || steps == 0) return hipSuccess;
     const unsigned g = (n + kFusedBlock - 1) / kFusedBlock;
     const uint32_t si = start_initial ? 1u : 0u;
-    if (n > 65536u)        // launch_actor_relabel's choice of build (the two give the same bits)
+    if (n > kOneWavePerSimdEnvs)        // launch_actor_relabel's choice of build (the two give the same bits)
         k_policy_grad_forward<ActorF32Lean><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, act, ld_act, saved);
     else
         k_policy_grad_forward<ActorF32><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, act, ld_act, saved);
@@ -216,7 +216,7 @@ hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint3
     if (n == 0 || steps == 0) return hipErrorInvalidValue;
     const unsigned g = (n + kFusedBlock - 1) / kFusedBlock;
     const uint32_t si = start_initial ? 1u : 0u, waves = (n + 63) / 64;
-    if (n > 65536u)        // launch_policy_grad_forward's choice of build
+    if (n > kOneWavePerSimdEnvs)        // launch_policy_grad_forward's choice of build
         k_policy_grad_forward_state<ActorF32Lean><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, saved);
     else
         k_policy_grad_forward_state<ActorF32><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, saved);

@@ -132,7 +132,7 @@ hipError_t launch_policy_loss_grad_bank(hipStream_t s, uint32_t n, uint32_t ld, 
     if (n == 0 || steps == 0 || n_policies == 0) return hipErrorInvalidValue;
     const unsigned g = (n + kFusedBlock - 1) / kFusedBlock;
     const uint32_t si = start_initial ? 1u : 0u, waves = (n + 63) / 64;
-    if (n > 65536u)        // launch_policy_loss_grad's choice of build
+    if (n > kOneWavePerSimdEnvs)        // launch_policy_loss_grad's choice of build
         k_policy_grad_forward_state_bank<ActorF32Lean><<<g, kFusedBlock, 0, s>>>(n, ld, steps, images, block_policy,
                                                                                  (uint32_t)RQ_PACKED_FLOATS, obs, done, hidden, ld_h, si, saved);
     else

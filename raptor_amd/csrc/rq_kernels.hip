@@ -1097,7 +1097,7 @@ hipError_t launch_actor_sequence(hipStream_t s, uint32_t n, uint32_t steps, cons
     const uint32_t squash = ((uint32_t)precision >> 8) & 1u;
     precision &= 0xff;
     const unsigned g = grid_for(n, kFusedBlock);
-    const bool lean = n > 65536u;          // two waves per SIMD only pay when there are that many
+    const bool lean = n > kOneWavePerSimdEnvs;          // two waves per SIMD only pay when there are that many
 #define RQ_LAUNCH_SEQ(ACT) k_actor_sequence<ACT><<<g, kFusedBlock, 0, s>>>(n, steps, packed, obs, stride, hidden, ld_h, act, squash)
     if (precision == RQ_POLICY_F16X2_MFMA) RQ_LAUNCH_SEQ(ActorF16X2);
     else if (precision == RQ_POLICY_BF16_MFMA) RQ_LAUNCH_SEQ(ActorBF16);          // one build at every size (round 5: see ActorBF16Lean)
@@ -1113,7 +1113,7 @@ hipError_t launch_actor_relabel(hipStream_t s, uint32_t n, uint32_t ld, uint32_t
     const uint32_t squash = ((uint32_t)precision >> 8) & 1u;
     precision &= 0xff;
     const unsigned g = grid_for(n, kFusedBlock);
-    const bool lean = n > 65536u;
+    const bool lean = n > kOneWavePerSimdEnvs;
 #define RQ_LAUNCH_RELABEL(ACT) k_actor_relabel<ACT><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, act, squash)
     if (precision == RQ_POLICY_F16X2_MFMA) RQ_LAUNCH_RELABEL(ActorF16X2);
     else if (precision == RQ_POLICY_BF16_MFMA) RQ_LAUNCH_RELABEL(ActorBF16);      // one build at every size (round 5: see ActorBF16Lean)
@@ -1147,61 +1147,6 @@ hipError_t launch_thaw_frozen(hipStream_t s, Batch b, SampleCfg c, uint64_t seed
                               StatsPtrs st, float* hidden, const float* weights) {
     if (b.n == 0) return hipSuccess;
     k_thaw_frozen<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, seed, params, state, st, hidden, weights);
-    return hipGetLastError();
-}
-
-hipError_t launch_rollout_fused(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                const float* params, float* state, float* hidden, const float* weights,
-                                const float* packed, StatsPtrs st, int precision, SasArgs sas, TrajPtrs traj,
-                                unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, packed, st, traj, sas, span};
-    // the 16-bit actors live in their own translation unit (rq_kernels_16bit.hip: another instruction scheduler)
-    if (precision == RQ_POLICY_F16X2_MFMA || precision == RQ_POLICY_BF16_MFMA)
-        return launch_rollout_fused_16bit(s, a, noise, ar, precision);
-    // Two builds of the same loop (same arithmetic, GRU two tiles at a time): a 512-register one for one wave per
-    // SIMD - every batch up to 65 536 envs (1024 SIMDs x 64 lanes) - and a 256-register one, two waves per SIMD,
-    // beyond.  The 256-register build parks loop invariants in scratch before the loop (~7 us per launch); at one
-    // wave per SIMD both run the loop at the same speed (3.21 vs 3.23 us/step), so the small batches take the
-    // build with the cheaper prologue.  With the SampleAndSquash stage: only the 256-register builds carry it.
-    const bool lean = b.n > 65536u;
-    if (sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a, noise, ar);
-    else if (lean)              launch_fused_actor<false, ActorF32Lean>(s, a, noise, ar);
-    else                        launch_fused_actor<false, ActorF32>(s, a, noise, ar);
-    return hipGetLastError();
-}
-
-hipError_t launch_rollout_fused_track(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                      uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                      const float* params, float* state, float* hidden, const float* weights,
-                                      const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
-                                      unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, packed, st, traj, SasArgs{}, span, trk};
-    if (precision == RQ_POLICY_F16X2_MFMA || precision == RQ_POLICY_BF16_MFMA)
-        return launch_rollout_fused_track_16bit(s, a, noise, ar, precision);
-    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
-    if (b.n > 65536u) launch_fused_track_actor<ActorF32Lean>(s, a, noise, ar);
-    else              launch_fused_track_actor<ActorF32>(s, a, noise, ar);
-    return hipGetLastError();
-}
-
-hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                     const float* params, float* state, float* hidden, const float* weights,
-                                     const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
-                                     uint32_t interval, unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, packed, st, traj, SasArgs{}, span, trk, interval};
-    if (precision == RQ_POLICY_F16X2_MFMA || precision == RQ_POLICY_BF16_MFMA)
-        return launch_rollout_fused_rate_16bit(s, a, noise, ar, precision);
-    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
-    if (b.n > 65536u) launch_fused_rate_actor<ActorF32Lean>(s, a, noise, ar);
-    else              launch_fused_rate_actor<ActorF32>(s, a, noise, ar);
     return hipGetLastError();
 }
 
@@ -1367,50 +1312,21 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
 }
 
 template <typename ACTOR>
-static inline void launch_fused_bank_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
-                                           bool noise, bool ar) {
+static inline void launch_fused_bank_actor(hipStream_t s, const FusedArgs& a) {
     dispatch_bools([&](auto NZ, auto AR, auto RC) {
         hipLaunchKernelGGL((k_rollout_fused_bank<NZ(), AR(), RC(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
-                           (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.span);
-    }, noise, ar, a.traj.obs != nullptr);
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
+                           a.block_policy, (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.span);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr);
 }
 
 template <typename ACTOR>
-static inline void launch_fused_bank_rate_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
-                                                const uint32_t* policy_interval, bool noise, bool ar) {
+static inline void launch_fused_bank_rate_actor(hipStream_t s, const FusedArgs& a) {
     dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
         hipLaunchKernelGGL((k_rollout_fused_bank_rate<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
-                           policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.trk, a.span);
-    }, noise, ar, a.traj.obs != nullptr, a.trk.ref != nullptr);
-}
-
-hipError_t launch_rollout_fused_bank(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                     const float* params, float* state, float* hidden, const float* weights,
-                                     const float* images, const uint32_t* block_policy, StatsPtrs st, TrajPtrs traj,
-                                     unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span};
-    // the two builds of launch_rollout_fused: 512 registers and one wave per SIMD up to 65 536 envs, 256 registers and two beyond
-    if (b.n > 65536u) launch_fused_bank_actor<ActorF32Lean>(s, a, images, block_policy, noise, ar);
-    else              launch_fused_bank_actor<ActorF32>(s, a, images, block_policy, noise, ar);
-    return hipGetLastError();
-}
-
-hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                          uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                          const float* params, float* state, float* hidden, const float* weights,
-                                          const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
-                                          StatsPtrs st, TrajPtrs traj, TrackPtrs trk, unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span, trk};
-    if (b.n > 65536u) launch_fused_bank_rate_actor<ActorF32Lean>(s, a, images, block_policy, policy_interval, noise, ar);
-    else              launch_fused_bank_rate_actor<ActorF32>(s, a, images, block_policy, policy_interval, noise, ar);
-    return hipGetLastError();
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
+                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.st, a.traj, a.trk, a.span);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
 // ---- the fused kernel of an env that carries a wrench schedule
@@ -1444,27 +1360,47 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
 #include "rq_rollout_body.inc"
 }
 
+// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
 template <typename ACTOR>
-static inline void launch_fused_wrench_actor(hipStream_t s, const FusedArgs& a, const float* images, const uint32_t* block_policy,
-                                             const uint32_t* policy_interval, WrenchPtrs wr, bool noise, bool ar) {
+static inline void launch_fused_wrench_actor(hipStream_t s, const FusedArgs& a) {
     dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
         hipLaunchKernelGGL((k_rollout_fused_wrench<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, images, block_policy,
-                           policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, wr, a.span);
-    }, noise, ar, a.traj.obs != nullptr, a.trk.ref != nullptr);
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
+                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.wr, a.span);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
-hipError_t launch_rollout_fused_wrench(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                       uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                       const float* params, float* state, float* hidden, const float* weights,
-                                       const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
-                                       uint32_t interval, StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
-                                       unsigned long long* span) {
-    if (b.n == 0 || n_steps == 0) return hipSuccess;
-    const bool ar = (flags & RQ_ROLLOUT_AUTORESET) != 0;
-    const FusedArgs a{b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, weights, nullptr, st, traj, SasArgs{}, span, trk, interval};
-    if (b.n > 65536u) launch_fused_wrench_actor<ActorF32Lean>(s, a, images, block_policy, policy_interval, wr, noise, ar);
-    else              launch_fused_wrench_actor<ActorF32>(s, a, images, block_policy, policy_interval, wr, noise, ar);
+// ---- the fused rollout's one launcher: every family above and in rq_rollout.hpp, chosen by route_fused
+// One fp32 build's instantiations, SAS = false (the SampleAndSquash stage: ActorF32Lean alone, below).
+template <typename ACTOR>
+static void launch_fused_f32_actor(hipStream_t s, const FusedArgs& a, FusedFamily family) {
+    switch (family) {
+    case FusedFamily::PLAIN:     launch_fused_actor<false, ACTOR>(s, a); break;
+    case FusedFamily::TRACK:     launch_fused_track_actor<ACTOR>(s, a); break;
+    case FusedFamily::RATE:      launch_fused_rate_actor<ACTOR>(s, a); break;
+    case FusedFamily::WRENCH:    launch_fused_wrench_actor<ACTOR>(s, a); break;
+    case FusedFamily::BANK:      launch_fused_bank_actor<ACTOR>(s, a); break;
+    case FusedFamily::BANK_RATE: launch_fused_bank_rate_actor<ACTOR>(s, a); break;
+    case FusedFamily::UNSUPPORTED: break;
+    }
+}
+
+hipError_t launch_rollout_fused(hipStream_t s, const FusedArgs& a) {
+    if (a.b.n == 0 || a.n_steps == 0) return hipSuccess;
+    const FusedRoute r = route_fused(fused_traits(a));
+    if (r.family == FusedFamily::UNSUPPORTED) return hipErrorInvalidValue;
+    switch (r.build) {
+    case FusedBuild::BF16:
+    case FusedBuild::F16X2:      // the 16-bit actors live in their own translation unit (rq_kernels_16bit.hip: a place for per-build flags)
+        return launch_rollout_fused_16bit(s, a, r.family);
+    case FusedBuild::F32_LEAN:
+        if (a.sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a);      // (PLAIN: route_fused allows the stage nowhere else)
+        else                          launch_fused_f32_actor<ActorF32Lean>(s, a, r.family);
+        break;
+    case FusedBuild::F32:
+        launch_fused_f32_actor<ActorF32>(s, a, r.family);
+        break;
+    }
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include "../../include/raptor_quad.h"
+#include "rq_fused_route.hpp"
 
 namespace rq {
 
@@ -278,51 +279,11 @@ hipError_t launch_step(hipStream_t s, Batch b, StepCfg c, const float* params, c
 // (sample_initial_state with the env's episode counter + policy state reset), as the fused kernel's prologue does
 hipError_t launch_thaw_frozen(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
                               StatsPtrs st, float* hidden, const float* weights);
-// the loop body README.md:95-99 x n_steps in one launch
-hipError_t launch_rollout_fused(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                const float* params, float* state, float* hidden, const float* weights,
-                                const float* packed, StatsPtrs st, int precision, SasArgs sas, TrajPtrs traj,
-                                unsigned long long* span = nullptr);
-// the TRACK variant of the fused kernel (no SampleAndSquash stage)
-hipError_t launch_rollout_fused_track(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                      uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                      const float* params, float* state, float* hidden, const float* weights,
-                                      const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
-                                      unsigned long long* span = nullptr);
-// the RATE variant of the fused kernel: the hidden state moves on at the steps whose episode step count is a
-// multiple of `interval`; tracked when trk.ref != nullptr; no SampleAndSquash stage
-hipError_t launch_rollout_fused_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                     const float* params, float* state, float* hidden, const float* weights,
-                                     const float* packed, StatsPtrs st, int precision, TrajPtrs traj, TrackPtrs trk,
-                                     uint32_t interval, unsigned long long* span = nullptr);
-// The fused kernel for an env that carries a wrench schedule (wr.rows != nullptr; fp32 policies, no SampleAndSquash stage): the RATE
-// text with the wrench of every step composed from the env's own row.  block_policy == nullptr: one policy - `images` is its operand
-// image, `interval` its native interval; otherwise a policy bank's tables, as launch_rollout_fused_bank_rate takes them.
-hipError_t launch_rollout_fused_wrench(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                       uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                       const float* params, float* state, float* hidden, const float* weights,
-                                       const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
-                                       uint32_t interval, StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
-                                       unsigned long long* span = nullptr);
 // ---- policy bank (rq_rollout_policies, rq_rollout_policies_track): P fp32 operand images [P][RQ_PACKED_FLOATS], raw weights
 // [P][RQ_POLICY_NUM_WEIGHTS], block_policy [ceil(n / 64)]: the policy of each 64-env block, and policy_interval [P]: every entry
 // 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL (rq_policy_bank_set_native_interval).  Plain launches: none of them appends to a GraphSink.
-// The fused kernel with the image chosen per wave; _rate: k_rollout_fused_rate with image and interval chosen per wave, on a moving
-// setpoint when trk.ref != nullptr.
-hipError_t launch_rollout_fused_bank(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                     uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                     const float* params, float* state, float* hidden, const float* weights,
-                                     const float* images, const uint32_t* block_policy, StatsPtrs st, TrajPtrs traj,
-                                     unsigned long long* span = nullptr);
-hipError_t launch_rollout_fused_bank_rate(hipStream_t s, Batch b, StepCfg c, NoiseCfg nc, bool noise, SampleCfg sc,
-                                          uint64_t seed, uint32_t epoch0, uint32_t n_steps, uint32_t flags,
-                                          const float* params, float* state, float* hidden, const float* weights,
-                                          const float* images, const uint32_t* block_policy, const uint32_t* policy_interval,
-                                          StatsPtrs st, TrajPtrs traj, TrackPtrs trk, unsigned long long* span = nullptr);
-// The chained counterpart's actor step; _rate stores the hidden state of the rows at a native step only (steps: the envs' episode step
-// counts, as launch_actor_step_rate takes them).
+// The fused rollout: launch_rollout_fused below (FusedArgs).  The chained counterpart's actor step; _rate stores the hidden state of
+// the rows at a native step only (steps: the envs' episode step counts, as launch_actor_step_rate takes them).
 hipError_t launch_actor_step_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy, const float* obs,
                                   uint32_t ld_obs, float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen);
 hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy,
@@ -465,6 +426,39 @@ struct TeacherRolloutArgs {
 };
 hipError_t launch_rollout_teachers(hipStream_t s, uint32_t n_tiles, uint32_t h1, uint32_t h2, int act, int out_act,
                                    const TeacherRolloutArgs& a);
+
+// A fused rollout - the loop body README.md:95-99 x n_steps in one launch - of a policy or a policy bank, described once: what any of
+// the kernel families (rq_fused_route.hpp) takes.  Set the fields by name; what a rollout does not use keeps its default.
+struct FusedArgs {
+    Batch b{}; StepCfg c{}; NoiseCfg nc{}; SampleCfg sc{}; uint64_t seed = 0; uint32_t epoch0 = 0, n_steps = 0;
+    bool noise = false, autoreset = false;
+    const float* params = nullptr; float* state = nullptr; float* hidden = nullptr;
+    const float* weights = nullptr;                // raw weights (a bank: [P][RQ_POLICY_NUM_WEIGHTS]): the policy-state reset reads them
+    StatsPtrs st{};
+    TrajPtrs traj{};                               // obs != nullptr: recorded
+    TrackPtrs trk{};                               // ref != nullptr: on a moving setpoint
+    WrenchPtrs wr{};                               // rows != nullptr: the env's wrench schedule (fp32, no SampleAndSquash stage)
+    // The actor.  One policy (block_policy == nullptr): `images` is its operand image in `precision`, with its output stage and its
+    // native interval.  A policy bank (fp32, no output stage): the tables described above - `interval` is not read - and whether an
+    // entry of policy_interval is above 1 (the host's knowledge: the table is on the device).
+    int precision = RQ_POLICY_FP32;
+    const float* images = nullptr; const uint32_t* block_policy = nullptr; const uint32_t* policy_interval = nullptr;
+    SasArgs sas{};                                 // mode != RQ_SAS_OFF: only one policy, untracked, at interval 1
+    uint32_t interval = 1;
+    bool bank_rated = false;
+    // != nullptr: every wave leaves (in, out | xcd << 60, loop begin, loop end) wall-clock ticks at span[4 * workgroup] and, behind
+    // all of those, the core-clock cycles its steps took at span[4 * workgroups + workgroup] (rq_device_last_rollout_ms).  Round 2
+    // took the kernel's begin / end from hipExtLaunchKernel events; calibrated under rocprofv3 in one process, an event-carrying
+    // launch itself runs ~4 us longer than a plain one and the events read ~4 us more on top.
+    unsigned long long* span = nullptr;
+};
+inline FusedTraits fused_traits(const FusedArgs& a) {
+    return {a.b.n, a.precision, a.sas.mode != RQ_SAS_OFF, a.trk.ref != nullptr, a.wr.rows != nullptr, a.interval,
+            a.block_policy != nullptr, a.bank_rated};
+}
+// The kernel route_fused(fused_traits(a)) names, enqueued on s; hipErrorInvalidValue, and nothing launched, for a description no
+// kernel is built for.  n == 0 or n_steps == 0: nothing to do.
+hipError_t launch_rollout_fused(hipStream_t s, const FusedArgs& a);
 // layout changes at the boundary (device pointers): field-major [dim][ld] <-> row-major [n][dim|stride],
 // dim <= 32; rows_to_soa zeroes the padding lanes n..ld-1
 // slabs > 1: consecutive [dim][ld] blocks (the steps of a trajectory) -> consecutive [n][dim] blocks, one launch

@@ -223,17 +223,25 @@ struct rq_env {
     DeviceBuffer<uint32_t> wrench_row0;
     uint64_t wrench_gen = 0;
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
-    // epoch-counter bump); one executable graph per distinct argument set
-    struct GraphEntry {
-        const float* params; float* state; float* hidden; const float* packed; const float* weights; const float* obs;
-        uint32_t flags; int precision; rq_env_config cfg; uint64_t seed;
-        int sas_mode; uint64_t sas_seed; const float* ls_image;
-        const float* ref; uint32_t ref_rows;     // tracked rollouts: the reference table (nullptr: untracked)
-        uint32_t row0_at; uint64_t row0_gen;     // a reference bank's per-env first rows and which upload they are (0, 0: none)
-        uint32_t interval;                       // the policy's native interval: the actor nodes of another one are other kernels
-        uint64_t wrench_gen;                     // the env's wrench schedule at construction (0: none): the step nodes carry its pointers
-        hipGraphExec_t exec;
+    // epoch-counter bump); one executable graph per distinct argument set: what the nodes carry by value, named once
+    struct GraphKey {
+        const float* params = nullptr; float* state = nullptr; float* hidden = nullptr; const float* packed = nullptr;
+        const float* weights = nullptr; const float* obs = nullptr;
+        uint32_t flags = 0; int precision = 0; rq_env_config cfg{}; uint64_t seed = 0;
+        int sas_mode = 0; uint64_t sas_seed = 0; const float* ls_image = nullptr;
+        const float* ref = nullptr; uint32_t ref_rows = 0;     // tracked rollouts: the reference table (nullptr: untracked)
+        uint32_t row0_at = 0; uint64_t row0_gen = 0;           // a reference bank's per-env first rows and which upload they are (0, 0: none)
+        uint32_t interval = 1;                                 // the policy's native interval: the actor nodes of another one are other kernels
+        uint64_t wrench_gen = 0;                               // the env's wrench schedule at construction (0: none): the step nodes carry its pointers
+        bool operator==(const GraphKey& o) const {             // field by field (padding is not compared); cfg is plain floats and words
+            return params == o.params && state == o.state && hidden == o.hidden && packed == o.packed && weights == o.weights &&
+                   obs == o.obs && flags == o.flags && precision == o.precision && seed == o.seed && sas_mode == o.sas_mode &&
+                   sas_seed == o.sas_seed && ls_image == o.ls_image && ref == o.ref && ref_rows == o.ref_rows && row0_at == o.row0_at &&
+                   row0_gen == o.row0_gen && interval == o.interval && wrench_gen == o.wrench_gen &&
+                   std::memcmp(&cfg, &o.cfg, sizeof(rq_env_config)) == 0;
+        }
     };
+    struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;
     DeviceBuffer<uint32_t> epoch_dev;    // device-side noise epoch read by the graph's observe nodes
     bool obs_exposed = false;        // rq_env_observation_device_ptr was called: the caller may write the buffer (no observation cache)
@@ -528,6 +536,10 @@ int rollout_check_reference_bank(const char* who, const rq_device* dev, const rq
 int rollout_track_refs(RolloutFrame& f, rq_device* dev, rq_env* env, const rq_reference_bank* refs, const uint32_t* reference_id);
 int rollout_begin(RolloutFrame& f, rq_device* dev, rq_env* env, rq_state* state, uint32_t n_steps, uint32_t flags, rq_trajectory* traj);
 void rollout_end(rq_state* state, rq_rng* rng, uint32_t n_steps, rq_trajectory* traj);
+// The fused mode's launch description, all but the actor: the frame, the env and the call's own arguments (span: fused_span_begin's).
+// The caller adds the policy's fields or the bank's and makes the one rq::launch_rollout_fused call.
+rq::FusedArgs fused_args(const RolloutFrame& f, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,
+                         uint32_t n_steps, uint32_t flags, unsigned long long* span);
 // a failed HIP call of a shared piece, reported as the caller's own RQ_HIP would: `who` is the caller's name, `what` the call
 inline int hip_failed(const char* who, const char* what, hipError_t e) {
     return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string(who) + ": " + what + " -> " + hipGetErrorString(e));

@@ -114,53 +114,39 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
 }
 
 // ------------------------------------------------------------------ launch -------------
-// span != nullptr: every wave leaves (in, out | xcd << 60, loop begin, loop end) wall-clock ticks at span[4 * workgroup]
-// and, behind all of those, the core-clock cycles its steps took at span[4 * workgroups + workgroup]
-// (rq_device_last_rollout_ms).  Round 2 took the kernel's begin / end from hipExtLaunchKernel events; calibrated under
-// rocprofv3 in one process, an event-carrying launch itself runs ~4 us longer than a plain one and the events read
-// ~4 us more on top.
-struct FusedArgs {
-    Batch b; StepCfg c; NoiseCfg nc; SampleCfg sc; uint64_t seed; uint32_t epoch0, n_steps;
-    const float* params; float* state; float* hidden; const float* weights; const float* packed;
-    StatsPtrs st; TrajPtrs traj; SasArgs sas; unsigned long long* span;
-    TrackPtrs trk;             // ref != nullptr: the TRACK variant
-    uint32_t interval;         // the RATE variant's native interval (launch_rollout_fused_rate)
-};
-
-// the 16-bit actors' instantiations of the three families (rq_kernels_16bit.hip)
-hipError_t launch_rollout_fused_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision);
-hipError_t launch_rollout_fused_track_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision);
-hipError_t launch_rollout_fused_rate_16bit(hipStream_t s, const FusedArgs& a, bool noise, bool ar, int precision);
+// the 16-bit actors' instantiations of `family`: PLAIN, TRACK or RATE (rq_kernels_16bit.hip); the actor is a.precision's
+hipError_t launch_rollout_fused_16bit(hipStream_t s, const FusedArgs& a, FusedFamily family);
 
 inline unsigned fused_grid(const FusedArgs& a) { return (a.b.n + kFusedBlock - 1) / kFusedBlock; }
 
 // One launcher per family: the instantiation for (noise, auto-reset, recording[, tracking]) of one actor build, the run-time bools
-// made template arguments by dispatch_bools.  SAS = with the SampleAndSquash output stage.
+// made template arguments by dispatch_bools, the launch description (rq_kernels.hpp FusedArgs) unpacked into the kernel's positional
+// parameters.  SAS = with the SampleAndSquash output stage.
 template <bool SAS, typename ACTOR>
-inline void launch_fused_actor(hipStream_t s, const FusedArgs& a, bool noise, bool ar) {
+inline void launch_fused_actor(hipStream_t s, const FusedArgs& a) {
     dispatch_bools([&](auto NZ, auto AR, auto RC) {
         hipLaunchKernelGGL((k_rollout_fused<NZ(), AR(), RC(), SAS, ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
                            a.st, a.traj, a.sas, a.span);
-    }, noise, ar, a.traj.obs != nullptr);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr);
 }
 
 template <typename ACTOR>
-inline void launch_fused_track_actor(hipStream_t s, const FusedArgs& a, bool noise, bool ar) {
+inline void launch_fused_track_actor(hipStream_t s, const FusedArgs& a) {
     dispatch_bools([&](auto NZ, auto AR, auto RC) {
         hipLaunchKernelGGL((k_rollout_fused_track<NZ(), AR(), RC(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
                            a.st, a.traj, a.trk, a.span);
-    }, noise, ar, a.traj.obs != nullptr);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr);
 }
 
 template <typename ACTOR>
-inline void launch_fused_rate_actor(hipStream_t s, const FusedArgs& a, bool noise, bool ar) {
+inline void launch_fused_rate_actor(hipStream_t s, const FusedArgs& a) {
     dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
         hipLaunchKernelGGL((k_rollout_fused_rate<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.packed,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
                            a.st, a.traj, a.trk, a.interval, a.span);
-    }, noise, ar, a.traj.obs != nullptr, a.trk.ref != nullptr);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
 }  // namespace rq
