@@ -1,6 +1,6 @@
 // rq_capi_policy_bank.cpp - the policy bank: P fp32 student policies (checkpoints of a run, a sweep, a seed population) flown in ONE
 // rollout, one policy per 64-env block (= per wave of the fused kernel).  The student-side mirror of the teacher bank's rollout
-// (rq_capi_teacher.cpp): same frame (rollout_check / rollout_begin / rollout_end), the id table cached in the bank.
+// (rq_capi_teacher.cpp): same frame (rollout_run), the id table cached in the bank.
 #include "rq_objects.hpp"
 
 using namespace rqh;
@@ -252,64 +252,67 @@ RQ_API int rq_policy_bank_get_hidden(rq_policy_bank* bank, float* host_out, uint
     return soa_to_host(bank->dev, bank->hidden, batch, bank->ld, RQ_POLICY_HIDDEN_DIM, host_out);
 }
 
-// rq_rollout_policies (ref == nullptr) and rq_rollout_policies_track.  With no reference and every interval 1 the launches are the
-// ones a bank's rollout always made; otherwise the RATE kernels, which take both (fused: rq_fused_route.hpp).
-static int rollout_policies_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
-                                 const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
-                                 rq_trajectory* traj, const rq_reference* ref, const rq_reference_bank* refs = nullptr,
-                                 const uint32_t* reference_id = nullptr) {
-    RolloutFrame f;
-    int rc = rollout_check(f, dev, env, params, state, rng, bank && policy_id, n_steps, mode, flags, traj); if (rc) return rc;
-    RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "policy bank lives on another device");
-    // a tracked rollout is refused here, before anything is enqueued (as rq_rollout_track refuses it)
-    if (ref) { rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc; }
-    rc = rollout_check_reference_bank(__func__, dev, env, refs, reference_id); if (rc) return rc;
-    rc = bank_check_ids(bank, policy_id, env->n); if (rc) return rc;
-    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
-    rc = bank_size(bank, env->n); if (rc) return rc;
-    RQ_REQUIRE(bank->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");
-    rc = bank_table(bank, dev, env->uid, policy_id, env->n); if (rc) return rc;
-    rc = bank_apply_reset(bank); if (rc) return rc;
-    rc = rollout_track(f, env, ref); if (rc) return rc;
-    rc = rollout_track_refs(f, dev, env, refs, reference_id); if (rc) return rc;
-    const bool rated = bank->rated;
-    rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
-    if (mode == RQ_ROLLOUT_FUSED) {
-        unsigned long long* span = nullptr;
-        rc = fused_span_begin(__func__, dev, env, n_steps, &span); if (rc) return rc;
-        rq::FusedArgs a = fused_args(f, env, params, state, rng, n_steps, flags, span);
-        a.hidden = bank->hidden; a.weights = bank->weights;
-        a.images = bank->images; a.block_policy = bank->table; a.policy_interval = bank->intervals_dev; a.bank_rated = rated;
-        RQ_HIP(rq::launch_rollout_fused(dev->stream, a));
-        fused_span_end(dev, n_steps);
-    } else {
-        rc = rollout_chained(__func__, f, dev, env, params, state, rng, n_steps, flags, traj,
-            [&] { return rq::launch_thaw_frozen_bank(dev->stream, f.b, f.smp, rng->seed, params->d, state->d, env->st, bank->hidden,
-                                                     bank->weights, bank->table); },
-            [&] { return rated ? rq::launch_actor_step_rate_bank(dev->stream, env->n, bank->images, bank->table, bank->intervals_dev,
-                                                                 env->obs, env->ld, bank->hidden, bank->ld, env->act, env->ld,
-                                                                 env->st.frozen, env->st.steps)
-                               : rq::launch_actor_step_bank(dev->stream, env->n, bank->images, bank->table, env->obs, env->ld,
-                                                            bank->hidden, bank->ld, env->act, env->ld, env->st.frozen); },
-            [&] { return rq::launch_step_bank(dev->stream, f.b, f.sc, params->d, state->d, env->act, env->st, flags, f.smp, rng->seed,
-                                              bank->hidden, bank->weights, bank->table, f.wr); });
-        if (rc) return rc;
+}  // extern "C"
+
+namespace {
+
+// A bank's policies fly the envs by policy_id, plain launches when chained.  With every interval 1 the launches are the ones a
+// bank's rollout always made; otherwise the RATE kernels (fused: rq_fused_route.hpp).
+struct PolicyBankActor {
+    static constexpr bool kFoldAndReplay = false;
+    rq_policy_bank* bank; const uint32_t* policy_id;
+    bool given() const { return bank && policy_id; }
+    int check(const RolloutCall& c, const RolloutFrame&) const {
+        RQ_REFUSE(c.who, bank->dev == c.dev, RQ_ERR_SHAPE_MISMATCH, "policy bank lives on another device");
+        return bank_check_ids(bank, policy_id, c.env->n);
     }
-    rollout_end(state, rng, n_steps, traj);
-    return RQ_OK;
-}
+    int prepare(const RolloutCall& c) const {
+        int rc = bank_size(bank, c.env->n); if (rc) return rc;
+        RQ_REFUSE(c.who, bank->ld == c.env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");
+        rc = bank_table(bank, c.dev, c.env->uid, policy_id, c.env->n); if (rc) return rc;
+        return bank_apply_reset(bank);
+    }
+    int fused(const RolloutCall& c, const RolloutFrame& f) const {
+        rq::FusedArgs a = fused_args(c, f);
+        a.hidden = bank->hidden; a.weights = bank->weights;
+        a.images = bank->images; a.block_policy = bank->table; a.policy_interval = bank->intervals_dev; a.bank_rated = bank->rated;
+        return fused_launch(c, a);
+    }
+    hipError_t thaw(const RolloutCall& c, const RolloutFrame& f) const {
+        return rq::launch_thaw_frozen_bank(c.dev->stream, f.b, f.smp, c.rng->seed, c.params->d, c.state->d, c.env->st, bank->hidden,
+                                           bank->weights, bank->table);
+    }
+    hipError_t act(const RolloutCall& c, const RolloutFrame&, uint32_t, const uint32_t*) const {
+        const rq_env* env = c.env;
+        return bank->rated ? rq::launch_actor_step_rate_bank(c.dev->stream, env->n, bank->images, bank->table, bank->intervals_dev,
+                                                             env->obs, env->ld, bank->hidden, bank->ld, env->act, env->ld,
+                                                             env->st.frozen, env->st.steps)
+                           : rq::launch_actor_step_bank(c.dev->stream, env->n, bank->images, bank->table, env->obs, env->ld,
+                                                        bank->hidden, bank->ld, env->act, env->ld, env->st.frozen);
+    }
+    hipError_t step(const RolloutCall& c, const RolloutFrame& f, uint32_t, const uint32_t*, bool) const {
+        return rq::launch_step_bank(c.dev->stream, f.b, f.sc, c.params->d, c.state->d, c.env->act, c.env->st, c.flags, f.smp,
+                                    c.rng->seed, bank->hidden, bank->weights, bank->table, f.wr);
+    }
+};
+
+}  // namespace
+
+extern "C" {
 
 RQ_API int rq_rollout_policies(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
                                const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                rq_trajectory* traj) {
-    return rollout_policies_impl(dev, env, params, state, bank, policy_id, rng, n_steps, mode, flags, traj, nullptr);
+    return rollout_run({__func__, dev, env, params, state, rng, n_steps, mode, flags, traj, nullptr, nullptr},
+                       PolicyBankActor{bank, policy_id});
 }
 
 RQ_API int rq_rollout_policies_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
                                      const uint32_t* policy_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                      rq_trajectory* traj, const rq_reference* reference) {
     RQ_REQUIRE(reference, RQ_ERR_INVALID_ARGUMENT, "null reference");
-    return rollout_policies_impl(dev, env, params, state, bank, policy_id, rng, n_steps, mode, flags, traj, reference);
+    return rollout_run({__func__, dev, env, params, state, rng, n_steps, mode, flags, traj, reference, nullptr},
+                       PolicyBankActor{bank, policy_id});
 }
 
 RQ_API int rq_rollout_policies_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_policy_bank* bank,
@@ -317,8 +320,8 @@ RQ_API int rq_rollout_policies_track_refs(rq_device* dev, rq_env* env, const rq_
                                           rq_trajectory* traj, const rq_reference_bank* references, const uint32_t* reference_id) {
     RQ_REQUIRE(references, RQ_ERR_INVALID_ARGUMENT, "null reference bank");
     RQ_REQUIRE(reference_id, RQ_ERR_INVALID_ARGUMENT, "null reference_id");
-    return rollout_policies_impl(dev, env, params, state, bank, policy_id, rng, n_steps, mode, flags, traj, nullptr, references,
-                                 reference_id);
+    return rollout_run({__func__, dev, env, params, state, rng, n_steps, mode, flags, traj, references, reference_id},
+                       PolicyBankActor{bank, policy_id});
 }
 
 }  // extern "C"

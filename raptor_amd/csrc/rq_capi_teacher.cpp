@@ -281,69 +281,71 @@ RQ_API int rq_teacher_bank_evaluate(rq_teacher_bank* bank, rq_env* env, const ui
 
 }  // extern "C"
 
-// rq_rollout_teachers (no reference), rq_rollout_teachers_track (ref) and rq_rollout_teachers_track_refs (refs + reference_id): one
-// frame.  A tracked rollout's checks and the reference bank's row cache are the ones every tracked rollout uses (rq_capi_rollout.cpp).
-static int rollout_teachers_impl(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
-                                 const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
-                                 rq_trajectory* traj, const rq_reference* ref, const rq_reference_bank* refs = nullptr,
-                                 const uint32_t* reference_id = nullptr) {
-    RolloutFrame f;
-    int rc = rollout_check(f, dev, env, params, state, rng, bank && teacher_id, n_steps, mode, flags, traj); if (rc) return rc;
-    RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "teacher bank lives on another device");
-    RQ_REQUIRE(mode != RQ_ROLLOUT_FUSED || (!bank->layers && bank->precision == RQ_POLICY_FP32), RQ_ERR_INVALID_ARGUMENT,
-               "the fused teacher rollout runs the fp32 two-hidden-layer {16, 32, 64} family: fly this bank (bf16 / f16x2 precision "
-               "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
-    if (f.wr.rows && mode == RQ_ROLLOUT_FUSED) return wrench_refuses_fused(__func__, "a teacher bank");
-    // a tracked rollout is refused here, before anything is enqueued (as rq_rollout_track refuses it)
-    if (ref) { rc = rollout_check_reference(__func__, dev, env, ref); if (rc) return rc; }
-    rc = rollout_check_reference_bank(__func__, dev, env, refs, reference_id); if (rc) return rc;
-    rc = check_ids(bank, teacher_id, env->n); if (rc) return rc;
-    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+namespace {
+
+// The bank's teachers fly the envs by teacher_id, plain launches when chained: the actor is the bank on the env's buffers
+// (rq_teacher_bank_evaluate's launch).  k_step's auto-reset also resets a policy state: a teacher has none, so it writes the
+// bank's sink (a zero weight block and a [16][ld] target).
+struct TeacherActor {
+    static constexpr bool kFoldAndReplay = false;
+    rq_teacher_bank* bank; const uint32_t* teacher_id;
     uint32_t n_tiles = 0;
-    rc = bank_tiles(bank, dev, env->uid, teacher_id, env->n, &n_tiles); if (rc) return rc;
-    rc = rollout_track(f, env, ref); if (rc) return rc;
-    rc = rollout_track_refs(f, dev, env, refs, reference_id); if (rc) return rc;
-    if (mode == RQ_ROLLOUT_CHAINED && n_steps) RQ_HIP(bank->sink.reserve(dev->stream, RQ_POLICY_NUM_WEIGHTS + (size_t)16 * env->ld));
-    rc = rollout_begin(f, dev, env, state, n_steps, flags, traj); if (rc) return rc;
-    const rq::TrajPtrs& tp = f.tp;
-    const rq::Batch& b = f.b; const rq::StepCfg& sc = f.sc; const rq::NoiseCfg& nc = f.nc; const rq::SampleCfg& smp = f.smp;
-    const bool noise = f.noise;
-    if (mode == RQ_ROLLOUT_FUSED) {
-        rq::TeacherRolloutArgs a{b, sc, nc, smp, rng->seed, rng->epoch, n_steps, noise ? 1u : 0u,
-                                 (flags & RQ_ROLLOUT_AUTORESET) ? 1u : 0u, params->d, state->d, env->st, tp,
-                                 bank->in_dim, bank->images_f32, bank->tiles, bank->tiles + n_tiles, f.trk};
-        RQ_HIP(rq::launch_rollout_teachers(dev->stream, n_tiles, bank->h1, bank->h2, bank->act, bank->out_act, a));
-    } else if (n_steps) {
-        // one step = observe (-> the setpoint's row taken off it: the frame's trk) -> the bank on the env's buffers
-        // (rq_teacher_bank_evaluate's launch) -> step (-> record), plain launches on the device's stream.  k_step's auto-reset also
-        // resets a policy state: here it writes the bank's sink (zero weight block)
-        float* sink_w = bank->sink;
-        float* sink_h = bank->sink + RQ_POLICY_NUM_WEIGHTS;
-        RQ_HIP(hipMemsetAsync(sink_w, 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float), dev->stream));
-        rc = rollout_chained(__func__, f, dev, env, params, state, rng, n_steps, flags, traj,
-            [&] { return rq::launch_thaw_frozen(dev->stream, b, smp, rng->seed, params->d, state->d, env->st, sink_h, sink_w); },
-            [&] { return bank_label_launch(bank, dev, env->n, n_tiles, env->ld, 1, env->obs, env->act); },
-            [&] { return rq::launch_step(dev->stream, b, sc, params->d, state->d, env->act, state->d, env->st, /*rollout=*/1, flags, smp,
-                                         rng->seed, sink_h, sink_w, rq::Mailbox{}, nullptr, rq::NoiseCfg{}, false, 0, nullptr, f.wr); });
-        if (rc) return rc;
+    bool given() const { return bank && teacher_id; }
+    float* sink_w() const { return bank->sink; }
+    float* sink_h() const { return bank->sink + RQ_POLICY_NUM_WEIGHTS; }
+    int check(const RolloutCall& c, const RolloutFrame& f) const {
+        RQ_REFUSE(c.who, bank->dev == c.dev, RQ_ERR_SHAPE_MISMATCH, "teacher bank lives on another device");
+        RQ_REFUSE(c.who, c.mode != RQ_ROLLOUT_FUSED || (!bank->layers && bank->precision == RQ_POLICY_FP32), RQ_ERR_INVALID_ARGUMENT,
+                  "the fused teacher rollout runs the fp32 two-hidden-layer {16, 32, 64} family: fly this bank (bf16 / f16x2 precision "
+                  "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
+        if (f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return wrench_refuses_fused(c.who, "a teacher bank");
+        return check_ids(bank, teacher_id, c.env->n);
     }
-    rollout_end(state, rng, n_steps, traj);
-    return RQ_OK;
-}
+    int prepare(const RolloutCall& c) {
+        const int rc = bank_tiles(bank, c.dev, c.env->uid, teacher_id, c.env->n, &n_tiles); if (rc) return rc;
+        if (c.mode == RQ_ROLLOUT_CHAINED && c.n_steps) {
+            RQ_HIP(bank->sink.reserve(c.dev->stream, RQ_POLICY_NUM_WEIGHTS + (size_t)16 * c.env->ld));
+            RQ_HIP(hipMemsetAsync(sink_w(), 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float), c.dev->stream));
+        }
+        return RQ_OK;
+    }
+    int fused(const RolloutCall& c, const RolloutFrame& f) const {
+        rq::TeacherRolloutArgs a{f.b, f.sc, f.nc, f.smp, c.rng->seed, c.rng->epoch, c.n_steps, f.noise ? 1u : 0u,
+                                 (c.flags & RQ_ROLLOUT_AUTORESET) ? 1u : 0u, c.params->d, c.state->d, c.env->st, f.tp,
+                                 bank->in_dim, bank->images_f32, bank->tiles, bank->tiles + n_tiles, f.trk};
+        RQ_HIP(rq::launch_rollout_teachers(c.dev->stream, n_tiles, bank->h1, bank->h2, bank->act, bank->out_act, a));
+        return RQ_OK;
+    }
+    hipError_t thaw(const RolloutCall& c, const RolloutFrame& f) const {
+        return rq::launch_thaw_frozen(c.dev->stream, f.b, f.smp, c.rng->seed, c.params->d, c.state->d, c.env->st, sink_h(), sink_w());
+    }
+    hipError_t act(const RolloutCall& c, const RolloutFrame&, uint32_t, const uint32_t*) const {
+        return bank_label_launch(bank, c.dev, c.env->n, n_tiles, c.env->ld, 1, c.env->obs, c.env->act);
+    }
+    hipError_t step(const RolloutCall& c, const RolloutFrame& f, uint32_t, const uint32_t*, bool) const {
+        return rq::launch_step(c.dev->stream, f.b, f.sc, c.params->d, c.state->d, c.env->act, c.state->d, c.env->st, /*rollout=*/1,
+                               c.flags, f.smp, c.rng->seed, sink_h(), sink_w(), rq::Mailbox{}, nullptr, rq::NoiseCfg{}, false, 0,
+                               nullptr, f.wr);
+    }
+};
+
+}  // namespace
 
 extern "C" {
 
 RQ_API int rq_rollout_teachers(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
                                const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                rq_trajectory* traj) {
-    return rollout_teachers_impl(dev, env, params, state, bank, teacher_id, rng, n_steps, mode, flags, traj, nullptr);
+    return rollout_run({__func__, dev, env, params, state, rng, n_steps, mode, flags, traj, nullptr, nullptr},
+                       TeacherActor{bank, teacher_id});
 }
 
 RQ_API int rq_rollout_teachers_track(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
                                      const uint32_t* teacher_id, rq_rng* rng, uint32_t n_steps, int mode, uint32_t flags,
                                      rq_trajectory* traj, const rq_reference* reference) {
     RQ_REQUIRE(reference, RQ_ERR_INVALID_ARGUMENT, "null reference");
-    return rollout_teachers_impl(dev, env, params, state, bank, teacher_id, rng, n_steps, mode, flags, traj, reference);
+    return rollout_run({__func__, dev, env, params, state, rng, n_steps, mode, flags, traj, reference, nullptr},
+                       TeacherActor{bank, teacher_id});
 }
 
 RQ_API int rq_rollout_teachers_track_refs(rq_device* dev, rq_env* env, const rq_params* params, rq_state* state, rq_teacher_bank* bank,
@@ -351,8 +353,8 @@ RQ_API int rq_rollout_teachers_track_refs(rq_device* dev, rq_env* env, const rq_
                                           rq_trajectory* traj, const rq_reference_bank* references, const uint32_t* reference_id) {
     RQ_REQUIRE(references, RQ_ERR_INVALID_ARGUMENT, "null reference bank");
     RQ_REQUIRE(reference_id, RQ_ERR_INVALID_ARGUMENT, "null reference_id");
-    return rollout_teachers_impl(dev, env, params, state, bank, teacher_id, rng, n_steps, mode, flags, traj, nullptr, references,
-                                 reference_id);
+    return rollout_run({__func__, dev, env, params, state, rng, n_steps, mode, flags, traj, references, reference_id},
+                       TeacherActor{bank, teacher_id});
 }
 
 }  // extern "C"

@@ -12,7 +12,8 @@
 //   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory; the distillation update (loss, Adam, repack),
 //                        for one policy and for a policy bank
 //   rq_memory.hpp        rq::DeviceBuffer / rq::PinnedBuffer: every object below owns its device and pinned memory through them
-// rollout_check / rollout_begin / rollout_end (rq_capi_rollout.cpp) are the frame rq_rollout*, rq_rollout_policies* and rq_rollout_teachers share.
+// The ten rq_rollout* entry points (a policy's, a policy bank's, the teacher bank's; plain, _track, _track_refs) each describe their call
+// (RolloutCall) and go through rollout_run below with the actor type of their file; their row tables are one type (RowTables).
 // Helpers live in namespace rqh (each .cpp says `using namespace rqh;`); nothing here is visible outside libraptor_quad.so.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -282,32 +283,22 @@ struct rq_trajectory {
     } grad;
 };
 
-// a moving setpoint's table on the device (rq_reference_create)
-struct rq_reference {
-    const rq_device* dev = nullptr;     // compared, never followed: the device may be gone before its references
-    int ordinal = 0;
-    uint32_t rows = 0;
-    DeviceBuffer<float> d;              // [rows][6] row-major
-};
-
-// M moving setpoints of one length on the device (rq_reference_bank_create), one after another: env i of a rollout reads the table
-// that begins at row reference_id[i] * rows
-struct rq_reference_bank {
-    const rq_device* dev = nullptr;     // compared, never followed (as rq_reference::dev)
-    int ordinal = 0;
-    uint32_t n_refs = 0, rows = 0;
-    DeviceBuffer<float> d;              // [n_refs * rows][6] row-major
-    uint64_t uid = fresh_version();     // what an env knows the bank by, beside its address (rq_env::row0_key)
-};
-
-// the tables of a wrench schedule on the device (rq_wrench_bank_create), one after another: env i of an env it is attached to reads
-// the table that begins at row wrench_id[i] * rows
-struct rq_wrench_bank {
-    const rq_device* dev = nullptr;     // compared, never followed (as rq_reference::dev)
+// Row tables on the device, [rows][6] row-major each, one after another: a moving setpoint (rq_reference_create: one table), M of
+// them (rq_reference_bank_create) or the tables of a wrench schedule (rq_wrench_bank_create).  Env i of a rollout or of an env the
+// tables are attached to reads the table that begins at row id[i] * rows; a single reference is every env's table 0.
+namespace rqh {
+struct RowTables {
+    const rq_device* dev = nullptr;     // compared, never followed: the device may be gone before its tables
     int ordinal = 0;
     uint32_t n_tables = 0, rows = 0;
-    int units = RQ_WRENCH_RELATIVE;
     DeviceBuffer<float> d;              // [n_tables * rows][6] row-major
+    uint64_t uid = fresh_version();     // what an env knows the tables by, beside their address (rq_env::row0_key)
+};
+}  // namespace rqh
+struct rq_reference : rqh::RowTables {};
+struct rq_reference_bank : rqh::RowTables {};
+struct rq_wrench_bank : rqh::RowTables {
+    int units = RQ_WRENCH_RELATIVE;
     uint32_t attached = 0;              // live envs it is attached to: rq_wrench_bank_destroy is refused while any
 };
 
@@ -510,13 +501,17 @@ int bank_wave_lists(rq_policy_bank* bank);        // `waves` for the current tab
 // require_native_rate refuses a policy
 int require_bank_native_rate(const rq_policy_bank* bank, const char* what);
 
-// ---- rq_capi_rollout.cpp ----
-// What a rollout of any kind (a policy's, a policy bank's, the teacher bank's) is framed by.  rollout_check, before the call's DeviceScope:
-// the checks all make (the env's wrench schedule among them: RolloutFrame::wr), and where a recording goes; rollout_check_reference, behind the caller's device check: a tracked rollout's
-// table (`who`: the caller's name, as its own messages begin).  rollout_track, inside the scope: the tracked rollout's pointers (a
-// null reference: none).  rollout_begin, after what is the caller's own (policy sizing; tile list and sink): the observation cache
-// dropped, the state private, the env's configuration as the kernels take it, the `done` rows preset.  rollout_end: the noise epoch,
-// the recording's length and the state's version move on.
+// ---- rq_capi_rollout.cpp: the frame of every rollout ----
+// One call of any of the ten rq_rollout* entry points, as its body describes it.
+struct RolloutCall {
+    const char* who;                  // the public entry point's name: what a refusal's message begins with
+    rq_device* dev; rq_env* env; const rq_params* params; rq_state* state; rq_rng* rng;
+    uint32_t n_steps; int mode; uint32_t flags; rq_trajectory* traj;
+    const RowTables* tables;          // a tracked rollout's reference or reference bank (null: untracked)
+    const uint32_t* reference_id;     // a reference bank's table per env (null: `tables` is one reference, every env's table)
+};
+// What rollout_run gathers on its way and the launches take: where a recording goes, the tracked rollout's pointers, the env's wrench
+// schedule and the env's configuration as the kernels take it.
 struct RolloutFrame {
     rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
     rq::TrackPtrs trk{};                                          // ref != nullptr: a tracked rollout
@@ -524,54 +519,147 @@ struct RolloutFrame {
     rq::WrenchPtrs wr{};                                           // rows != nullptr: the env carries a wrench schedule (rollout_check)
     rq::Batch b; rq::StepCfg sc; rq::NoiseCfg nc; rq::SampleCfg smp; bool noise;
 };
-int rollout_check(RolloutFrame& f, const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,
-                  bool actor, uint32_t n_steps, int mode, uint32_t flags, const rq_trajectory* traj);
-int rollout_check_reference(const char* who, const rq_device* dev, const rq_env* env, const rq_reference* ref);
-int rollout_track(RolloutFrame& f, rq_env* env, const rq_reference* ref);
-// The same two for a reference bank (rq_rollout_track_refs, rq_rollout_policies_track_refs; a null bank: nothing).  The check also
-// reads every id (an id outside the bank is refused naming the env); rollout_track_refs, inside the scope, puts the per-env first
-// rows on the device unless the env holds them for (bank, ids) already.
-int rollout_check_reference_bank(const char* who, const rq_device* dev, const rq_env* env, const rq_reference_bank* refs,
-                                 const uint32_t* reference_id);
-int rollout_track_refs(RolloutFrame& f, rq_device* dev, rq_env* env, const rq_reference_bank* refs, const uint32_t* reference_id);
-int rollout_begin(RolloutFrame& f, rq_device* dev, rq_env* env, rq_state* state, uint32_t n_steps, uint32_t flags, rq_trajectory* traj);
-void rollout_end(rq_state* state, rq_rng* rng, uint32_t n_steps, rq_trajectory* traj);
-// The fused mode's launch description, all but the actor: the frame, the env and the call's own arguments (span: fused_span_begin's).
-// The caller adds the policy's fields or the bank's and makes the one rq::launch_rollout_fused call.
-rq::FusedArgs fused_args(const RolloutFrame& f, const rq_env* env, const rq_params* params, const rq_state* state, const rq_rng* rng,
-                         uint32_t n_steps, uint32_t flags, unsigned long long* span);
+// a refusal inside the frame, worded as RQ_REQUIRE words it but begun with the call's own name
+#define RQ_REFUSE(who, cond, status, msg)                                          \
+    do {                                                                           \
+        if (!(cond)) return rq::fail((status), std::string(who) + ": " + (msg));   \
+    } while (0)
+// The pieces of rollout_run, in its order.  rollout_check, before the call's DeviceScope: what every rollout refuses (`actor`: the
+// caller was given what acts), where a recording goes and the env's wrench schedule.  rollout_check_tables: a tracked rollout's
+// tables and, with ids, every id (one outside the bank is refused naming the env).  rollout_track, inside the scope: the tracked
+// rollout's pointers; with ids the per-env first rows go to the device unless the env holds them for (tables, ids) already.
+// rollout_begin, after the actor's preparation: the observation cache dropped, the state private, the env's configuration as the
+// kernels take it, the `done` rows preset.  rollout_end: the noise epoch, the recording's length and the state's version move on.
+int rollout_check(RolloutFrame& f, const RolloutCall& c, bool actor);
+int rollout_check_tables(const RolloutCall& c);
+int rollout_track(RolloutFrame& f, const RolloutCall& c);
+int rollout_begin(RolloutFrame& f, const RolloutCall& c);
+void rollout_end(const RolloutCall& c);
+// One id per env -> the [env->ld] first rows (id * rows; null ids: table 0) at dst on the device, synchronised before the pageable
+// rows go away.  `what` begins the message of a failed host allocation.  A reference bank's rows and a wrench schedule's.
+int upload_first_rows(const char* what, rq_device* dev, const rq_env* env, const uint32_t* ids, uint32_t rows, uint32_t* dst);
 // a failed HIP call of a shared piece, reported as the caller's own RQ_HIP would: `who` is the caller's name, `what` the call
 inline int hip_failed(const char* who, const char* what, hipError_t e) {
     return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string(who) + ": " + what + " -> " + hipGetErrorString(e));
 }
-// Around a fused launch: under rq_device_set_rollout_timing the span buffer sized for the env's waves (*span: what the launcher takes,
-// null when off), and behind the launch what rq_device_last_rollout_ms goes by.
-int fused_span_begin(const char* who, rq_device* dev, const rq_env* env, uint32_t n_steps, unsigned long long** span);
-void fused_span_end(rq_device* dev, uint32_t n_steps);
+// The fused mode of a policy or a policy bank.  fused_args: the launch description, all but the actor; the actor adds its fields and
+// calls fused_launch: under rq_device_set_rollout_timing the span buffer sized for the env's waves, the one
+// rq::launch_rollout_fused (rq_fused_route.hpp picks the kernel), and behind it what rq_device_last_rollout_ms goes by.
+rq::FusedArgs fused_args(const RolloutCall& c, const RolloutFrame& f);
+int fused_launch(const RolloutCall& c, rq::FusedArgs& a);
 
-// The plain chained rollout (no graph, nothing folded): thaw under auto-reset, then per step observe -> the setpoint taken off the
-// observation if tracked -> actor -> step -> record if recording, plain launches on the device's stream.  thaw / actor / step: the
-// caller's launches, each -> hipError_t; who: the caller's name, which a failure's message begins with as the caller's own would;
-// the env's episode step count is that of this step's observation until `step` moves it on.
-template <typename Thaw, typename Actor, typename Step>
-int rollout_chained(const char* who, const RolloutFrame& f, rq_device* dev, rq_env* env, const rq_params* params, rq_state* state,
-                    const rq_rng* rng, uint32_t n_steps, uint32_t flags, const rq_trajectory* traj, Thaw thaw, Actor actor, Step step) {
+constexpr uint32_t kGraphSteps = 25;   // steps per replayed graph (divides the 500-step episode)
+constexpr size_t kMaxGraphs = 8;       // executable graphs kept per env (one per distinct argument set)
+
+// The chained rollout: thaw under auto-reset, then per step observe -> the setpoint taken off the observation if tracked (one small
+// kernel in front of the actor, wherever the observation came from; it keeps the tracking error) -> actor -> step -> record if
+// recording, on the device's stream.  The actor's launches: thaw(c, f), act(c, f, epoch, epoch_base), step(c, f, epoch, epoch_base,
+// fold), each -> hipError_t; the env's episode step count is that of this step's observation until `step` moves it on.
+// An actor with kFoldAndReplay (one policy) turns two options on when nothing is recorded.  fold: its step kernel also assembles the
+// NEXT step's observation (two launches per step instead of three; the rollout's first observation is a launch of its own, the one
+// the last step assembles is not used and never shifted).  Replay: kGraphSteps steps go out as one hipGraph keyed by what the
+// actor's graph_key(c, f) says its nodes carry by value; kernel boundaries stay (~1.5 us each) but the host no longer pays ~3.5 us
+// per launch, which is what bounds small batches.  The banks go out as plain launches.
+template <typename Actor>
+int rollout_chained(const RolloutCall& c, const RolloutFrame& f, const Actor& actor) {
+    rq_device* dev = c.dev; rq_env* env = c.env; const rq_rng* rng = c.rng;
+    const uint32_t n_steps = c.n_steps;
+    const bool fold = Actor::kFoldAndReplay && !c.traj;
+    const char* what = "";            // the launch a failure is reported for
+    auto one_step = [&](uint32_t epoch, const uint32_t* epoch_base, uint32_t t_record) -> hipError_t {
+        hipError_t e = hipSuccess;
+        if (!fold) {
+            what = "rq::launch_observe";
+            e = rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, epoch, epoch_base, c.params->d, c.state->d, env->obs);
+        }
+        if (e == hipSuccess && f.trk.ref) { what = "rq::launch_track_shift"; e = rq::launch_track_shift(dev->stream, f.b, c.state->d, env->st, env->obs, f.trk); }
+        if (e == hipSuccess) { what = "the actor launch"; e = actor.act(c, f, epoch, epoch_base); }
+        if (e == hipSuccess) { what = "the step launch"; e = actor.step(c, f, epoch, epoch_base, fold); }
+        if (e == hipSuccess && c.traj) {
+            rq::TrajPtrs tt = f.tp; tt.t0 = f.tp.t0 + t_record;
+            what = "rq::launch_record"; e = rq::launch_record(dev->stream, f.b, env->obs, env->act, env->st, tt);
+        }
+        return e;
+    };
     hipError_t e = hipSuccess;
-    if (n_steps && (flags & RQ_ROLLOUT_AUTORESET))      // envs frozen by an earlier rollout start their next episode
-        if ((e = thaw()) != hipSuccess) return hip_failed(who, "the thaw launch", e);
-    for (uint32_t t = 0; t < n_steps; ++t) {
-        e = rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, rng->epoch + t, nullptr, params->d, state->d, env->obs);
-        if (e != hipSuccess) return hip_failed(who, "rq::launch_observe", e);
-        if (f.trk.ref && (e = rq::launch_track_shift(dev->stream, f.b, state->d, env->st, env->obs, f.trk)) != hipSuccess)
-            return hip_failed(who, "rq::launch_track_shift", e);
-        if ((e = actor()) != hipSuccess) return hip_failed(who, "the actor launch", e);
-        if ((e = step()) != hipSuccess) return hip_failed(who, "the step launch", e);
-        if (traj) {
-            rq::TrajPtrs tt = f.tp; tt.t0 = f.tp.t0 + t;
-            if ((e = rq::launch_record(dev->stream, f.b, env->obs, env->act, env->st, tt)) != hipSuccess)
-                return hip_failed(who, "rq::launch_record", e);
+    if (n_steps && (c.flags & RQ_ROLLOUT_AUTORESET))      // envs frozen by an earlier rollout start their next episode
+        if ((e = actor.thaw(c, f)) != hipSuccess) return hip_failed(c.who, "the thaw launch", e);
+    if (fold && n_steps) {           // the rollout's first observation (after the thaw: of the re-sampled states)
+        e = rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, rng->epoch, nullptr, c.params->d, c.state->d, env->obs);
+        if (e != hipSuccess) return hip_failed(c.who, "rq::launch_observe", e);
+    }
+    uint32_t done_steps = 0;
+    if constexpr (Actor::kFoldAndReplay) {
+        if (fold && n_steps >= kGraphSteps) {
+            const rq_env::GraphKey key = actor.graph_key(c, f);     // another value of any of its fields is another graph
+            const uint32_t step_nodes = f.trk.ref ? 3u : 2u;
+            hipGraphExec_t exec = nullptr;
+            for (auto& g : env->graphs)
+                if (g.key == key) { exec = g.exec; break; }
+            if (!exec) {
+                // Built node by node (rq_kernels.hpp GraphSink), NOT by stream capture: while any stream of a process captures, HIP
+                // fails hipDeviceSynchronize on every other thread (hipErrorStreamCaptureUnsupported) and invalidates the capture -
+                // a learner's PyTorch thread on the same GPU broke the rollout and was broken by it (tools/foreign_soak.py, round 6).
+                // Should the construction fail all the same, the steps go out as plain launches: same kernels, same order.
+                hipGraph_t graph = nullptr;
+                hipError_t ce = dev->graphs_enabled ? hipGraphCreate(&graph, 0) : hipErrorNotSupported;
+                if (ce == hipSuccess) {
+                    rq::GraphSink sink;
+                    sink.graph = graph;
+                    rq::set_graph_sink(&sink);
+                    for (uint32_t t = 0; t < kGraphSteps && ce == hipSuccess; ++t) ce = one_step(t, env->epoch_dev, 0);
+                    if (ce == hipSuccess) ce = rq::launch_add_u32(dev->stream, env->epoch_dev, kGraphSteps);
+                    rq::set_graph_sink(nullptr);
+                    if (ce == hipSuccess && sink.nodes != step_nodes * kGraphSteps + 1) ce = hipErrorUnknown;     // a launcher that bypassed the sink
+                }
+                if (ce == hipSuccess) ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+                if (graph) (void)hipGraphDestroy(graph);
+                if (ce != hipSuccess) {
+                    (void)hipGetLastError();         // the failed construction's; the direct launches below report their own
+                    exec = nullptr;
+                    ++dev->graph_fallbacks;
+                } else {
+                    if (env->graphs.size() >= kMaxGraphs) {        // least recently created goes (a replay is cheap to rebuild)
+                        RQ_HIP(hipStreamSynchronize(dev->stream));
+                        (void)hipGraphExecDestroy(env->graphs.front().exec);
+                        env->graphs.erase(env->graphs.begin());
+                    }
+                    try {                       // nothing throws across the boundary
+                        env->graphs.push_back({key, exec});
+                    } catch (const std::bad_alloc&) {
+                        (void)hipGraphExecDestroy(exec);
+                        return fail(RQ_ERR_OUT_OF_MEMORY, "rollout: host allocation failed");
+                    }
+                }
+            }
+            if (exec) {
+                RQ_HIP(rq::launch_set_u32(dev->stream, env->epoch_dev, rng->epoch));
+                for (; done_steps + kGraphSteps <= n_steps; done_steps += kGraphSteps)
+                    RQ_HIP(hipGraphLaunch(exec, dev->stream));
+            }
         }
     }
+    for (uint32_t t = done_steps; t < n_steps; ++t)
+        if ((e = one_step(rng->epoch + t, nullptr, t)) != hipSuccess) return hip_failed(c.who, what, e);
+    return RQ_OK;
+}
+
+// A rollout of any kind, start to end: every refusal comes before the DeviceScope, hence before anything is enqueued or any object
+// modified.  The actor (one policy: rq_capi_rollout.cpp; a policy bank: rq_capi_policy_bank.cpp; the teacher bank:
+// rq_capi_teacher.cpp) supplies given() (it was handed what acts), check(c, f) (its refusals, its own device first), prepare(c)
+// (inside the scope: sizing, tables, a pending reset, the sink), fused(c, f) and the chained launches rollout_chained takes.
+template <typename Actor>
+int rollout_run(const RolloutCall& c, Actor actor) {
+    RolloutFrame f;
+    int rc = rollout_check(f, c, actor.given()); if (rc) return rc;
+    rc = actor.check(c, f); if (rc) return rc;
+    rc = rollout_check_tables(c); if (rc) return rc;
+    DeviceScope on_device(c.dev); rc = on_device.rc; if (rc) return rc;
+    rc = actor.prepare(c); if (rc) return rc;
+    rc = rollout_track(f, c); if (rc) return rc;
+    rc = rollout_begin(f, c); if (rc) return rc;
+    rc = c.mode == RQ_ROLLOUT_FUSED ? actor.fused(c, f) : rollout_chained(c, f, actor); if (rc) return rc;
+    rollout_end(c);
     return RQ_OK;
 }
 int traj_block_to_host(rq_device* dev, const float* d_soa, uint32_t steps, uint32_t n, uint32_t ld, uint32_t dim, float* host);

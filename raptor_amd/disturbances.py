@@ -110,26 +110,8 @@ def suite(rows, dt):
 def check_tables(tables):
     """The tables of a ``WrenchBank`` as the C layer takes them, or ValueError: float32 [M >= 1, rows >= 1, 6], finite, contiguous;
     a list of M ``[rows, 6]`` tables of equal length is stacked."""
-    if isinstance(tables, (list, tuple)):
-        if not tables:
-            raise ValueError("a wrench bank holds at least one table")
-        for t in tables:
-            if not isinstance(t, np.ndarray) or t.dtype != np.float32:
-                raise ValueError("a wrench table is a float32 NumPy array [rows, 6] (raptor_amd.disturbances builds them)")
-            if t.ndim != 2 or t.shape[1] != 6 or t.shape[0] < 1:
-                raise ValueError(f"a wrench table has shape [rows >= 1, 6]: force, torque; got {t.shape}")
-        if len({t.shape[0] for t in tables}) != 1:
-            raise ValueError("the tables of a wrench bank have the same number of rows; got " + ", ".join(str(t.shape[0]) for t in tables))
-        tables = np.stack(tables)
-    if not isinstance(tables, np.ndarray) or tables.dtype != np.float32:
-        raise ValueError("a wrench bank is a float32 NumPy array [M, rows, 6] or a list of M [rows, 6] tables")
-    if tables.ndim != 3 or tables.shape[2] != 6 or tables.shape[0] < 1 or tables.shape[1] < 1:
-        raise ValueError(f"a wrench bank has shape [M >= 1, rows >= 1, 6]; got {tables.shape}")
-    if not np.isfinite(tables).all():
-        raise ValueError("a wrench table holds finite entries only")
-    if tables.shape[0] * tables.shape[1] >= 1 << 28:
-        raise ValueError("a wrench bank holds fewer than 2^28 rows in all")
-    return np.ascontiguousarray(tables)
+    from .l2f import _stacked_tables
+    return _stacked_tables(tables, "wrench", "force, torque", "raptor_amd.disturbances")
 
 
 def check_units(units):

@@ -148,15 +148,40 @@ class Device:
         return n.value
 
 
-def _reference_table(table):
-    """The table of a ``Reference`` as the C layer takes it, or ValueError: float32, C-contiguous, [rows >= 1, 6], finite."""
+def _table(table, noun, columns, builder):
+    """One ``[rows, 6]`` table as the C layer takes it, or ValueError: float32, C-contiguous, [rows >= 1, 6], finite.  ``noun``:
+    "reference" / "wrench"; ``columns``: what the six columns are; ``builder``: the module that builds such tables."""
     if not isinstance(table, np.ndarray) or table.dtype != np.float32:
-        raise ValueError("a reference table is a float32 NumPy array [rows, 6] (raptor_amd.tracking builds them)")
+        raise ValueError(f"a {noun} table is a float32 NumPy array [rows, 6] ({builder} builds them)")
     if table.ndim != 2 or table.shape[1] != 6 or table.shape[0] < 1:
-        raise ValueError(f"a reference table has shape [rows >= 1, 6]: target position, target velocity; got {table.shape}")
+        raise ValueError(f"a {noun} table has shape [rows >= 1, 6]: {columns}; got {table.shape}")
     if not np.isfinite(table).all():
-        raise ValueError("a reference table holds finite entries only")
+        raise ValueError(f"a {noun} table holds finite entries only")
     return np.ascontiguousarray(table)
+
+
+def _stacked_tables(tables, noun, columns, builder):
+    """The tables of a bank (``ReferenceBank``, ``WrenchBank``) as the C layer takes them, or ValueError: float32 [M >= 1, rows >= 1,
+    6], finite, contiguous; a list of M ``[rows, 6]`` tables of equal length is stacked."""
+    if isinstance(tables, (list, tuple)):
+        if not tables:
+            raise ValueError(f"a {noun} bank holds at least one table")
+        rows = [_table(t, noun, columns, builder) for t in tables]
+        if len({t.shape[0] for t in rows}) != 1:
+            raise ValueError(f"the tables of a {noun} bank have the same number of rows; got " + ", ".join(str(t.shape[0]) for t in rows))
+        tables = np.stack(rows)
+    if not isinstance(tables, np.ndarray) or tables.dtype != np.float32:
+        raise ValueError(f"a {noun} bank is a float32 NumPy array [M, rows, 6] or a list of M [rows, 6] tables")
+    if tables.ndim != 3 or tables.shape[2] != 6 or tables.shape[0] < 1 or tables.shape[1] < 1:
+        raise ValueError(f"a {noun} bank has shape [M >= 1, rows >= 1, 6]; got {tables.shape}")
+    if not np.isfinite(tables).all():
+        raise ValueError(f"a {noun} table holds finite entries only")
+    if tables.shape[0] * tables.shape[1] >= 1 << 28:
+        raise ValueError(f"a {noun} bank holds fewer than 2^28 rows in all")
+    return np.ascontiguousarray(tables)
+
+
+_REFERENCE_NOUNS = ("reference", "target position, target velocity", "raptor_amd.tracking")
 
 
 class Reference:
@@ -165,34 +190,13 @@ class Reference:
     own episode step count, so ``rows`` must cover ``episode_step_limit``.  The table is copied to ``device`` once, here."""
 
     def __init__(self, device, table):
-        t = _reference_table(table)             # refused before the device is touched
+        t = _table(table, *_REFERENCE_NOUNS)    # refused before the device is touched
         h = C.c_void_p()
         _lib.call("rq_reference_create", device._h, _lib.fptr(t), int(t.shape[0]), C.byref(h))
         self._h = h
         self._device = device
         self.rows = int(t.shape[0])
         self._fin = weakref.finalize(self, _lib.load().rq_reference_destroy, h)
-
-
-def _reference_tables(tables):
-    """The tables of a ``ReferenceBank`` as the C layer takes them, or ValueError: float32 [M >= 1, rows >= 1, 6], finite, contiguous;
-    a list of M tables of equal length is stacked."""
-    if isinstance(tables, (list, tuple)):
-        if not tables:
-            raise ValueError("a reference bank holds at least one table")
-        rows = [_reference_table(t) for t in tables]
-        if len({t.shape[0] for t in rows}) != 1:
-            raise ValueError("the tables of a reference bank have the same number of rows; got " + ", ".join(str(t.shape[0]) for t in rows))
-        return np.ascontiguousarray(np.stack(rows))
-    if not isinstance(tables, np.ndarray) or tables.dtype != np.float32:
-        raise ValueError("a reference bank is a float32 NumPy array [M, rows, 6] or a list of M [rows, 6] tables")
-    if tables.ndim != 3 or tables.shape[2] != 6 or tables.shape[0] < 1 or tables.shape[1] < 1:
-        raise ValueError(f"a reference bank has shape [M >= 1, rows >= 1, 6]; got {tables.shape}")
-    if not np.isfinite(tables).all():
-        raise ValueError("a reference table holds finite entries only")
-    if tables.shape[0] * tables.shape[1] >= 1 << 28:
-        raise ValueError("a reference bank holds fewer than 2^28 rows in all")
-    return np.ascontiguousarray(tables)
 
 
 class ReferenceBank:
@@ -202,7 +206,7 @@ class ReferenceBank:
     with ``Reference(tables[ids[i]])``.  The tables are copied to ``device`` once, here (``raptor_amd.tracking.suite`` makes some)."""
 
     def __init__(self, device, tables):
-        t = _reference_tables(tables)           # refused before the device is touched
+        t = _stacked_tables(tables, *_REFERENCE_NOUNS)      # refused before the device is touched
         h = C.c_void_p()
         _lib.call("rq_reference_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), C.byref(h))
         self._h = h
@@ -262,6 +266,45 @@ def _checked_wrench_ids(env, wrench_ids, ref_ids, n_envs):
                          "(a single l2f.Reference goes with wrench_ids)")
     from .disturbances import check_wrench_ids
     return check_wrench_ids(wrench_ids, schedule[0].n_tables, n_envs)
+
+
+_MODES = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}
+
+
+def _rollout_call(entry, device, env, params, state, actor_handle, ids, rng, n_steps, mode, autoreset, trajectory, reference, ref_ids):
+    """The one library call of every rollout.  ``entry``: "rq_rollout" (``ids`` None), "rq_rollout_policies" or
+    "rq_rollout_teachers" (``ids``: the actor's id per env); ``mode``: ``_MODES[...]``; ``reference`` / ``ref_ids`` as ``_checked_reference`` left them pick the
+    entry point itself, its ``_track`` or its ``_track_refs`` twin.  The untracked single-policy call has two names: with a
+    ``trajectory`` it is ``rq_rollout_record``."""
+    args = (device._h, env._require("environment"), params._require("VectorParameters"), state._require("VectorState"), actor_handle)
+    if ids is not None:
+        args += (ids.ctypes.data,)
+    args += (rng._require("rng"), int(n_steps), mode, ROLLOUT_AUTORESET if autoreset else 0)
+    traj = trajectory._require("trajectory") if trajectory is not None else None
+    if reference is not None:
+        args += (traj, reference._h)
+        if ref_ids is None:
+            return _lib.call(entry + "_track", *args)
+        return _lib.call(entry + "_track_refs", *args, ref_ids.ctypes.data)
+    if entry != "rq_rollout":
+        return _lib.call(entry, *args, traj)
+    if traj is None:
+        return _lib.call(entry, *args)
+    return _lib.call("rq_rollout_record", *args, traj)
+
+
+def tracking_rmse(env, reference, ref_ids, w_ids, actor_ids, n_actors):
+    """``tracking_rmse`` of a bank's closed-loop table, from ``env.tracking_error()`` grouped by actor (policy or teacher): [n_actors,
+    M] over the disturbance scenarios (``w_ids``) or over the setpoints (``ref_ids`` of a ``ReferenceBank``), [n_actors] on a single
+    ``Reference``."""
+    from .tracking import reference_tracking_table
+    sum_sq, steps = env.tracking_error()
+    if w_ids is not None:
+        return reference_tracking_table(sum_sq, steps, w_ids, env.wrench_schedule[0].n_tables, actor_ids, n_actors)
+    if ref_ids is not None:
+        return reference_tracking_table(sum_sq, steps, ref_ids, reference.n_references, actor_ids, n_actors)
+    from .policy_bank import policy_tracking_table
+    return policy_tracking_table(sum_sq, steps, actor_ids, n_actors)
 
 
 class _Handle:
@@ -657,9 +700,8 @@ class VectorModule:
                 the device); ``overwrite=True`` replaces the stored actions with the teachers' (the regression
                 targets of the distillation step, README.md:208-216)."""
                 T, N = len(self), mod.N_ENVIRONMENTS
-                ids = np.ascontiguousarray(teacher_ids, np.uint32)
-                if ids.shape != (N,):
-                    raise ValueError("teacher_ids must hold one id per env")
+                from .teachers import check_teacher_ids
+                ids = check_teacher_ids(teacher_ids, N)
                 out = np.empty((T, N, 4), np.float32) if fetch else None
                 _lib.call("rq_trajectory_relabel_teachers", self._h, bank._h, ids.ctypes.data,
                           _lib.fptr(out) if fetch else None, 1 if overwrite else 0)
@@ -761,8 +803,10 @@ class VectorModule:
             raise ValueError("reference and teacher_ids do not combine here: a teacher bank's tracked rollout is its own call, "
                              "TeacherBank.fly(..., teacher_ids, reference=ref)")
         ref_ids = _checked_reference(reference, reference_ids, self.N_ENVIRONMENTS)
-        m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
+        m = _MODES[mode]
+        entry, handle, ids = "rq_rollout", None, None
         from .policy_bank import PolicyBank, check_policy_ids
+        from .teachers import TeacherBank, check_teacher_ids
         if isinstance(policy, PolicyBank):
             if reference is not None:
                 raise ValueError("a PolicyBank rollout does not track a reference")
@@ -771,52 +815,30 @@ class VectorModule:
             if policy_ids is None:
                 raise ValueError("a PolicyBank flies the envs by policy_ids: one policy id per env is required")
             ids = check_policy_ids(policy_ids, policy.n_policies, self.N_ENVIRONMENTS)
-            _lib.call("rq_rollout_policies", device._h, env._require("environment"), params._require("VectorParameters"),
-                      state._require("VectorState"), policy._h, ids.ctypes.data, rng._require("rng"), int(n_steps), m,
-                      ROLLOUT_AUTORESET if autoreset else 0, trajectory._require("trajectory") if trajectory is not None else None)
-            return
-        if policy_ids is not None:
+            entry, handle = "rq_rollout_policies", policy._h
+        elif policy_ids is not None:
             raise ValueError("policy_ids belong to a PolicyBank rollout; a Raptor policy flies every env itself and a TeacherBank "
                              "takes teacher_ids")
-        from .teachers import TeacherBank
-        if isinstance(policy, TeacherBank):
+        elif isinstance(policy, TeacherBank):
             if reference is not None:
                 raise ValueError("a TeacherBank does not take reference here: TeacherBank.fly(..., reference=ref) is its tracked rollout")
             if teacher_ids is None:
                 raise ValueError("a TeacherBank flies the envs by teacher_ids: one teacher id per env is required")
-            ids = np.ascontiguousarray(teacher_ids, np.uint32)
-            if ids.shape != (self.N_ENVIRONMENTS,):
-                raise ValueError("teacher_ids must hold one id per env")
-            _lib.call("rq_rollout_teachers", device._h, env._require("environment"), params._require("VectorParameters"),
-                      state._require("VectorState"), policy._h, ids.ctypes.data, rng._require("rng"), int(n_steps), m,
-                      ROLLOUT_AUTORESET if autoreset else 0, trajectory._require("trajectory") if trajectory is not None else None)
-            return
-        if teacher_ids is not None:
+            ids = check_teacher_ids(teacher_ids, self.N_ENVIRONMENTS)
+            entry, handle = "rq_rollout_teachers", policy._h
+        elif teacher_ids is not None:
             raise ValueError("teacher_ids belong to a TeacherBank rollout; a Raptor policy flies every env itself")
-        if reference is not None:
-            args = (device._h, env._require("environment"), params._require("VectorParameters"), state._require("VectorState"),
-                    policy._handle(device), rng._require("rng"), int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0,
-                    trajectory._require("trajectory") if trajectory is not None else None, reference._h)
-            if ref_ids is None:
-                _lib.call("rq_rollout_track", *args)
-            else:
-                _lib.call("rq_rollout_track_refs", *args, ref_ids.ctypes.data)
-            return
-        fast = _lib.fast
-        if fast is not None and trajectory is None and state._mirror is None and hasattr(fast, "rollout"):
-            status = fast.rollout(_lib.fn_addr("rq_rollout"), device._h, env._h, params._h, state._h, policy._handle(device), rng._h,
-                                  int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0)
-            if status == 0:
-                return
-            if status != 1:
-                _lib.check(status)
-        args = (device._h, env._require("environment"), params._require("VectorParameters"),
-                state._require("VectorState"), policy._handle(device), rng._require("rng"), int(n_steps), m,
-                ROLLOUT_AUTORESET if autoreset else 0)
-        if trajectory is None:
-            _lib.call("rq_rollout", *args)
         else:
-            _lib.call("rq_rollout_record", *args, trajectory._require("trajectory"))
+            handle = policy._handle(device)
+            fast = _lib.fast
+            if fast is not None and reference is None and trajectory is None and state._mirror is None and hasattr(fast, "rollout"):
+                status = fast.rollout(_lib.fn_addr("rq_rollout"), device._h, env._h, params._h, state._h, handle, rng._h,
+                                      int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0)
+                if status == 0:
+                    return
+                if status != 1:
+                    _lib.check(status)
+        _rollout_call(entry, device, env, params, state, handle, ids, rng, n_steps, m, autoreset, trajectory, reference, ref_ids)
 
 
     # ------------------------------------------------------------------ ui-server messages (README.md:63-92)

@@ -194,19 +194,12 @@ class PolicyBank:
         to the row of its own episode step count, a ``trajectory`` records what the policy saw and ``env.tracking_error()``
         accumulates, as in a ``Raptor`` policy's tracked rollout.  With an ``l2f.ReferenceBank`` and ``reference_ids`` ([N] integers,
         free per env, also inside a block) env i tracks table ``reference_ids[i]``: one rollout flies P policies on M setpoints."""
-        from .l2f import ROLLOUT_AUTORESET, ROLLOUT_CHAINED, ROLLOUT_FUSED, _checked_reference
-        m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
+        from .l2f import _MODES, _checked_reference, _rollout_call
         ids = check_policy_ids(policy_ids, self.n_policies, vector.N_ENVIRONMENTS)
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)
-        args = (device._h, env._require("environment"), params._require("VectorParameters"), state._require("VectorState"), self._h,
-                ids.ctypes.data, rng._require("rng"), int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0,
-                trajectory._require("trajectory") if trajectory is not None else None)
-        if reference is None:
-            _lib.call("rq_rollout_policies", *args)
-        elif ref_ids is None:
-            _lib.call("rq_rollout_policies_track", *args, reference._h)
-        else:
-            _lib.call("rq_rollout_policies_track_refs", *args, reference._h, ref_ids.ctypes.data)
+        m = _MODES[mode]
+        _rollout_call("rq_rollout_policies", device, env, params, state, self._h, ids, rng, n_steps, m, autoreset, trajectory,
+                      reference, ref_ids)
 
     def evaluate(self, vector, device, env, params, state, rng, n_steps, policy_ids=None, mode="fused", autoreset=True,
                  reference=None, reference_ids=None, wrench_ids=None):
@@ -220,7 +213,7 @@ class PolicyBank:
         disturbance scenario ``wrench_ids[i]`` of the attached bank (dealt like reference ids) and, on an ``l2f.Reference`` such as
         ``tracking.hold``, ``tracking_rmse`` is [P, M] over the scenarios: P checkpoints x M disturbances in one launch."""
         ids = block_policy_assignment(vector.N_ENVIRONMENTS, self.n_policies) if policy_ids is None else policy_ids
-        from .l2f import _checked_reference, _checked_wrench_ids
+        from .l2f import _checked_reference, _checked_wrench_ids, tracking_rmse
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
         w_ids = _checked_wrench_ids(env, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
         if w_ids is not None:
@@ -230,15 +223,6 @@ class PolicyBank:
         self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
                  reference_ids=reference_ids)
         table = policy_episode_table(env, ids, self.n_policies)
-        if w_ids is not None and reference is not None:
-            from .tracking import reference_tracking_table
-            sum_sq, steps = env.tracking_error()
-            table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, w_ids, env.wrench_schedule[0].n_tables, ids, self.n_policies)
-        elif ref_ids is not None:
-            from .tracking import reference_tracking_table
-            sum_sq, steps = env.tracking_error()
-            table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, ref_ids, reference.n_references, ids, self.n_policies)
-        elif reference is not None:
-            sum_sq, steps = env.tracking_error()
-            table["tracking_rmse"] = policy_tracking_table(sum_sq, steps, ids, self.n_policies)
+        if reference is not None:
+            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, w_ids, ids, self.n_policies)
         return table

@@ -161,23 +161,12 @@ class TeacherBank:
         ``reference_ids`` ([N] integers, free per env, also inside a teacher's 16-env tile) env i tracks table ``reference_ids[i]``:
         one rollout flies K teachers on M setpoints.  ``mode="fused"``: fp32 banks of two hidden layers of 16 / 32 / 64 units;
         ``"chained"``: every bank.  An MLP has no state to hold: there is no native interval."""
-        from .l2f import ROLLOUT_AUTORESET, ROLLOUT_CHAINED, ROLLOUT_FUSED, _checked_reference
-        ids = np.ascontiguousarray(teacher_ids, np.uint32)
-        if ids.shape != (vector.N_ENVIRONMENTS,):
-            raise ValueError("teacher_ids must hold one id per env")
+        from .l2f import _MODES, _checked_reference, _rollout_call
+        ids = check_teacher_ids(teacher_ids, vector.N_ENVIRONMENTS)
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)
-        if reference is None:
-            vector.rollout(device, env, params, state, self, rng, n_steps, mode=mode, autoreset=autoreset, trajectory=trajectory,
-                           teacher_ids=ids)
-            return
-        m = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}[mode]
-        args = (device._h, env._require("environment"), params._require("VectorParameters"), state._require("VectorState"), self._h,
-                ids.ctypes.data, rng._require("rng"), int(n_steps), m, ROLLOUT_AUTORESET if autoreset else 0,
-                trajectory._require("trajectory") if trajectory is not None else None)
-        if ref_ids is None:
-            _lib.call("rq_rollout_teachers_track", *args, reference._h)
-        else:
-            _lib.call("rq_rollout_teachers_track_refs", *args, reference._h, ref_ids.ctypes.data)
+        m = _MODES[mode]
+        _rollout_call("rq_rollout_teachers", device, env, params, state, self._h, ids, rng, n_steps, m, autoreset, trajectory,
+                      reference, ref_ids)
 
     def closed_loop(self, vector, device, env, params, state, rng, n_steps, teacher_ids, mode="fused", autoreset=True,
                     reference=None, reference_ids=None, wrench_ids=None):
@@ -189,10 +178,8 @@ class TeacherBank:
         ``wrench_ids`` ([N] integers; the env carries a wrench schedule): env i flies disturbance scenario ``wrench_ids[i]`` of the
         attached bank and, on an ``l2f.Reference``, ``tracking_rmse`` is [K, M] over the scenarios (``mode="chained"``: the fused
         teacher kernel does not fly a schedule)."""
-        from .l2f import _checked_reference, _checked_wrench_ids
-        ids = np.ascontiguousarray(teacher_ids, np.uint32)
-        if ids.shape != (vector.N_ENVIRONMENTS,):
-            raise ValueError("teacher_ids must hold one id per env")
+        from .l2f import _checked_reference, _checked_wrench_ids, tracking_rmse
+        ids = check_teacher_ids(teacher_ids, vector.N_ENVIRONMENTS)
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
         w_ids = _checked_wrench_ids(env, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
         if w_ids is not None:
@@ -201,19 +188,17 @@ class TeacherBank:
         self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
                  reference_ids=reference_ids)
         table = teacher_episode_table(env, ids, self.n_teachers)
-        if w_ids is not None and reference is not None:
-            from .tracking import reference_tracking_table
-            sum_sq, steps = env.tracking_error()
-            table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, w_ids, env.wrench_schedule[0].n_tables, ids, self.n_teachers)
-        elif ref_ids is not None:
-            from .tracking import reference_tracking_table
-            sum_sq, steps = env.tracking_error()
-            table["tracking_rmse"] = reference_tracking_table(sum_sq, steps, ref_ids, reference.n_references, ids, self.n_teachers)
-        elif reference is not None:
-            from .policy_bank import policy_tracking_table
-            sum_sq, steps = env.tracking_error()
-            table["tracking_rmse"] = policy_tracking_table(sum_sq, steps, ids, self.n_teachers)
+        if reference is not None:
+            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, w_ids, ids, self.n_teachers)
         return table
+
+
+def check_teacher_ids(teacher_ids, n_envs):
+    """One teacher id per env -> contiguous uint32 [n_envs]; ValueError otherwise (the library checks the range)."""
+    ids = np.ascontiguousarray(teacher_ids, np.uint32)
+    if ids.shape != (int(n_envs),):
+        raise ValueError("teacher_ids must hold one id per env")
+    return ids
 
 
 def balanced_teacher_assignment(n_envs, n_teachers):

@@ -117,3 +117,93 @@ def test_entry_points_are_declared_and_bound():
     assert lib.rq_policy_bank_destroy(None) == 0
     assert lib.rq_policy_bank_reset(None) == -1
     assert lib.rq_rollout_policies(None, None, None, None, None, None, None, 1, 0, 0, None) != 0
+
+
+class _Stand:
+    """a stand-in for anything that carries a handle: an l2f object, a Raptor"""
+
+    def __init__(self, h):
+        self._h, self._mirror = h, None
+
+    def _require(self, what):
+        return self._h
+
+    def _handle(self, device):
+        return self._h
+
+
+def test_every_rollout_is_one_library_call(monkeypatch):
+    """{Raptor, PolicyBank, TeacherBank} x {no reference, Reference, ReferenceBank + ids}, and a Raptor with a trajectory, through
+    vector.rollout / PolicyBank.fly / TeacherBank.fly: one library call each, by the expected name, with as many arguments as the
+    entry point declares, the ids and the reference where it takes them; what is refused is refused before the library."""
+    import ctypes as C
+    import raptor_amd.l2f as l2f
+    from raptor_amd import _lib
+    from raptor_amd.policy_bank import PolicyBank
+    from raptor_amd.teachers import TeacherBank
+    calls = []
+    monkeypatch.setattr(_lib, "call", lambda name, *a: calls.append((name, a)))
+    monkeypatch.setattr(_lib, "fast", None)              # the shortcut in front of the plain call would follow the stand-in handles
+    n = 128
+    vector = l2f.vector(n)
+    device, env, params, state, rng, traj, raptor = (_Stand(h) for h in ("dev", "env", "params", "state", "rng", "traj", "policy"))
+    world = (device, env, params, state)
+    bank = PolicyBank.__new__(PolicyBank)
+    bank.n_policies, bank._h = 2, "bank"
+    teachers = TeacherBank.__new__(TeacherBank)
+    teachers.n_teachers, teachers._h = 3, "teachers"
+    ref = l2f.Reference.__new__(l2f.Reference)
+    ref._h = "ref"
+    refs = l2f.ReferenceBank.__new__(l2f.ReferenceBank)
+    refs._h, refs.n_references = "refs", 4
+    pids = block_policy_assignment(n, 2)
+    tids = (np.arange(n) % 3).astype(np.uint32)
+    rids = (np.arange(n) % 4).astype(np.uint32)
+
+    def one(name, fly, ids=None, reference=None, ref_ids=None, trajectory=None):
+        del calls[:]
+        fly()
+        assert [c[0] for c in calls] == [name], (name, calls)
+        a = calls[0][1]
+        assert len(a) == len(_lib._SIGNATURES[name]), name
+        at = 5 if ids is not None else 4                  # the actor's handle, then its ids, then rng ...
+        assert a[:4] == ("dev", "env", "params", "state") and a[4] in ("policy", "bank", "teachers"), name
+        if ids is not None:
+            got = np.ctypeslib.as_array((C.c_uint32 * n).from_address(a[5]))
+            assert np.array_equal(got, ids), name
+        assert a[at + 1:at + 5] == ("rng", 7, _lib.ROLLOUT_CHAINED, _lib.ROLLOUT_AUTORESET), name
+        tail = list(a[at + 5:])
+        if name != "rq_rollout":
+            assert tail.pop(0) == (trajectory._h if trajectory is not None else None), name
+        if reference is not None:
+            assert tail.pop(0) == reference._h, name
+        if ref_ids is not None:
+            got = np.ctypeslib.as_array((C.c_uint32 * n).from_address(tail.pop(0)))
+            assert np.array_equal(got, ref_ids), name
+        assert tail == [], name
+
+    kw = dict(mode="chained", autoreset=True)
+    for reference, ref_ids, suffix in ((None, None, ""), (ref, None, "_track"), (refs, rids, "_track_refs")):
+        rkw = dict(kw, reference=reference, reference_ids=ref_ids) if reference is not None else kw
+        one("rq_rollout" + suffix, lambda: vector.rollout(*world, raptor, rng, 7, **rkw), None, reference, ref_ids)
+        one("rq_rollout_policies" + suffix, lambda: bank.fly(vector, *world, rng, 7, pids, **rkw), pids, reference, ref_ids)
+        one("rq_rollout_teachers" + suffix, lambda: teachers.fly(vector, *world, rng, 7, tids, **rkw), tids, reference, ref_ids)
+    one("rq_rollout_record", lambda: vector.rollout(*world, raptor, rng, 7, trajectory=traj, **kw), trajectory=traj)
+    # a bank through vector.rollout is the same call; a recording rides along in every tracked call
+    one("rq_rollout_policies", lambda: vector.rollout(*world, bank, rng, 7, policy_ids=pids, **kw), pids)
+    one("rq_rollout_teachers", lambda: vector.rollout(*world, teachers, rng, 7, teacher_ids=tids, trajectory=traj, **kw), tids,
+        trajectory=traj)
+    one("rq_rollout_track", lambda: vector.rollout(*world, raptor, rng, 7, reference=ref, trajectory=traj, **kw), None, ref,
+        trajectory=traj)
+    # refused before the library is reached
+    del calls[:]
+    for words, fly in (("reference and teacher_ids do not combine", lambda: vector.rollout(*world, teachers, rng, 7, teacher_ids=tids, reference=ref)),
+                       ("reference_ids belong to a ReferenceBank", lambda: vector.rollout(*world, raptor, rng, 7, reference=ref, reference_ids=rids)),
+                       ("reference_ids belong to a ReferenceBank", lambda: bank.fly(vector, *world, rng, 7, pids, reference=ref, reference_ids=rids)),
+                       ("a ReferenceBank flies the envs by reference_ids", lambda: vector.rollout(*world, raptor, rng, 7, reference=refs)),
+                       ("a ReferenceBank flies the envs by reference_ids", lambda: teachers.fly(vector, *world, rng, 7, tids, reference=refs)),
+                       ("policy_ids belong to a PolicyBank", lambda: vector.rollout(*world, raptor, rng, 7, policy_ids=pids)),
+                       ("teacher_ids must hold one id per env", lambda: teachers.fly(vector, *world, rng, 7, tids[:64]))):
+        with pytest.raises(ValueError, match=words):
+            fly()
+    assert calls == []
