@@ -298,7 +298,17 @@ typedef enum rq_policy_precision {
                                  arithmetic: RQ_POLICY_FP32 stays the default and the benchmarked configuration.
                                  Range (round 3): observations and layer_0's output are SATURATED at the largest f16,
                                  +-65 504 (a NaN input reads as -65 504), before they are split - an input beyond that is a
-                                 bounded error (the gates saturate), never an infinity or NaN in the GRU state */
+                                 bounded error (the gates saturate), never an infinity or NaN in the GRU state.
+                                 WEIGHTS have no such clamp: an operand of magnitude >= 65 520 would split into hi = inf,
+                                 lo = -inf, a NaN in every contraction it enters.  The operands are W0, b0, W2 as they are and
+                                 the rows of Wi / Wh after their pre-scale (r and z rows x -log2 e, n rows x -2 log2 e: a
+                                 weight of 22 708 in an n row is already out of range).  Such parameters are REFUSED with
+                                 RQ_ERR_INVALID_ARGUMENT and a message that names the first offending weight index
+                                 ("weight 1779 is outside the f16 range ..."): by rq_policy_set_precision(F16X2), by
+                                 rq_policy_set_weights and rq_policy_set_standardize on a policy that is in F16X2 (the
+                                 folded layer_0 counts), and by rq_policy_pack_image(F16X2).  The refused call changes
+                                 nothing: precision, parameters, stages and every result stay what they were.  fp32 and
+                                 bf16 carry such weights.  rq_teacher_bank_set_precision refuses likewise. */
 } rq_policy_precision;
 
 /* weights: RQ_POLICY_NUM_WEIGHTS float32 in the order documented at RQ_POLICY_NUM_WEIGHTS

@@ -64,6 +64,16 @@ int require_native_rate(const rq_policy* pol, const char* what) {
     return RQ_OK;
 }
 
+// RQ_POLICY_F16X2_MFMA cannot hold a weight whose operand reaches 65 520 after the gate pre-scale (rq::policy_f16x2_misfit)
+int refuse_f16x2_misfit(const float* w_eff, const char* who) {
+    const int i = rq::policy_f16x2_misfit(w_eff);
+    if (i < 0) return RQ_OK;
+    char msg[256];
+    std::snprintf(msg, sizeof msg, "%s: weight %d is outside the f16 range (magnitude >= 65520 after the gate pre-scale of -log2 e on the "
+                  "r and z rows, -2 log2 e on the n rows): the f16x2 image cannot hold it, use fp32 or bf16", who, i);
+    return fail(RQ_ERR_INVALID_ARGUMENT, msg);
+}
+
 int policy_images16(rq_policy* pol) {
     if (!pol->images16_stale) return RQ_OK;
     int rc = policy_mirror(pol); if (rc) return rc;
@@ -89,24 +99,34 @@ using namespace rqh;
 extern "C" {
 
 // ---------------------------------------------------------------------------- Policy ----
-// (re)build the effective parameters and both MFMA operand images, and upload them
-static int policy_upload(rq_policy* p) {
+// the parameters the kernels see: `weights` with the optional Standardize stage folded into layer_0
+static void effective_weights(const rq_policy* p, const float* weights, float* eff) {
+    std::memcpy(eff, weights, sizeof(float) * RQ_POLICY_NUM_WEIGHTS);
+    if (!p->standardize) return;
+    // Standardize (x - mean) / std followed by Dense folds into the Dense:
+    //   W0' = W0 diag(1/std),  b0' = b0 - W0' mean      (semantics unpinned)
+    for (int o = 0; o < 16; ++o) {
+        float shift = 0.0f;
+        for (int k = 0; k < RQ_POLICY_INPUT_DIM; ++k) {
+            const float w = weights[o * 22 + k] * p->std_inv[k];
+            eff[o * 22 + k] = w;
+            shift += w * p->std_mean[k];
+        }
+        eff[352 + o] = weights[352 + o] - shift;
+    }
+}
+
+// (re)build the effective parameters and both MFMA operand images, and upload them.  `weights`: the new raw parameters
+// (p->w_host itself when only a stage changed).  A policy in RQ_POLICY_F16X2_MFMA refuses parameters its image cannot hold,
+// and is then left exactly as it was.
+static int policy_upload(rq_policy* p, const float* weights, const char* who) {
+    float eff[RQ_POLICY_NUM_WEIGHTS];
+    effective_weights(p, weights, eff);
+    if (p->precision == RQ_POLICY_F16X2_MFMA) { const int rc = refuse_f16x2_misfit(eff, who); if (rc) return rc; }
+    if (weights != p->w_host) std::memcpy(p->w_host, weights, sizeof(p->w_host));
+    std::memcpy(p->w_eff, eff, sizeof(p->w_eff));
     p->version = fresh_version();
     p->weight_version = fresh_version();
-    std::memcpy(p->w_eff, p->w_host, sizeof(p->w_eff));
-    if (p->standardize) {
-        // Standardize (x - mean) / std followed by Dense folds into the Dense:
-        //   W0' = W0 diag(1/std),  b0' = b0 - W0' mean      (semantics unpinned)
-        for (int o = 0; o < 16; ++o) {
-            float shift = 0.0f;
-            for (int k = 0; k < RQ_POLICY_INPUT_DIM; ++k) {
-                const float w = p->w_host[o * 22 + k] * p->std_inv[k];
-                p->w_eff[o * 22 + k] = w;
-                shift += w * p->std_mean[k];
-            }
-            p->w_eff[352 + o] = p->w_host[352 + o] - shift;
-        }
-    }
     std::vector<float> packed, packed16, packed_split;
     try {                                   // nothing throws across the boundary
         packed.resize(rq::RQ_PACKED_FLOATS); packed16.resize(rq::RQ_PACKED_BF16_FLOATS); packed_split.resize(rq::RQ_PACKED_F16X2_FLOATS);
@@ -142,7 +162,7 @@ RQ_API int rq_policy_create(rq_device* dev, const float* weights, size_t n_weigh
         return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_create: device allocation failed");
     }
     policy_registry(p, +1);
-    rc = policy_upload(p);
+    rc = policy_upload(p, p->w_host, "rq_policy_create");
     if (rc) { rq_policy_destroy(p); return rc; }
     *out = p;
     return RQ_OK;
@@ -166,8 +186,7 @@ RQ_API int rq_policy_set_weights(rq_policy* pol, const float* weights, size_t n_
                "expected 2084 weights: W0[16,22] b0[16] Wi[48,16] Wh[48,16] bi[48] bh[48] h0[16] W2[4,16] b2[4]");
     DeviceScope on_device(pol->dev); int rc = on_device.rc; if (rc) return rc;
     if (device_registry(pol->dev, 0)) { rc = resident_retire(pol->dev); if (rc) return rc; }
-    std::memcpy(pol->w_host, weights, sizeof(pol->w_host));
-    return policy_upload(pol);
+    return policy_upload(pol, weights, "rq_policy_set_weights");
 }
 
 RQ_API int rq_policy_get_weights(rq_policy* pol, float* host_out) {
@@ -190,7 +209,10 @@ RQ_API int rq_policy_pack_image(const float* weights, size_t n_weights, int prec
     RQ_REQUIRE(capacity >= need, RQ_ERR_INVALID_ARGUMENT, "image buffer too small");
     if (precision == RQ_POLICY_FP32) rq::pack_policy(weights, image);
     else if (precision == RQ_POLICY_BF16_MFMA) rq::pack_policy_bf16(weights, image);
-    else rq::pack_policy_f16x2(weights, image);
+    else {
+        const int rc = refuse_f16x2_misfit(weights, "rq_policy_pack_image"); if (rc) return rc;
+        rq::pack_policy_f16x2(weights, image);
+    }
     return RQ_OK;
 }
 
@@ -199,7 +221,8 @@ RQ_API int rq_policy_set_precision(rq_policy* pol, int precision) {
     pol->version = fresh_version();
     RQ_REQUIRE(precision == RQ_POLICY_FP32 || precision == RQ_POLICY_BF16_MFMA || precision == RQ_POLICY_F16X2_MFMA,
                RQ_ERR_INVALID_ARGUMENT, "unknown precision");
-    if (precision != RQ_POLICY_FP32) { int rc = policy_images16(pol); if (rc) return rc; }
+    if (precision != RQ_POLICY_FP32) { int rc = policy_images16(pol); if (rc) return rc; }      // (fetches w_eff after a device-side update)
+    if (precision == RQ_POLICY_F16X2_MFMA) { int rc = refuse_f16x2_misfit(pol->w_eff, "rq_policy_set_precision"); if (rc) return rc; }
     pol->precision = precision;
     return RQ_OK;
 }
@@ -208,15 +231,26 @@ RQ_API int rq_policy_set_standardize(rq_policy* pol, const float* mean, const fl
     RQ_REQUIRE(pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE((mean == nullptr) == (std == nullptr), RQ_ERR_INVALID_ARGUMENT, "mean and std must be given together");
     { int rc = policy_mirror(pol); if (rc) return rc; }
+    if (mean)
+        for (int k = 0; k < RQ_POLICY_INPUT_DIM; ++k) RQ_REQUIRE(std[k] > 0.0f, RQ_ERR_INVALID_ARGUMENT, "std must be positive");
+    const bool was = pol->standardize;                 // a refused fold (f16x2 range) leaves the stage as it was
+    float old_mean[RQ_POLICY_INPUT_DIM], old_inv[RQ_POLICY_INPUT_DIM];
+    std::memcpy(old_mean, pol->std_mean, sizeof(old_mean));
+    std::memcpy(old_inv, pol->std_inv, sizeof(old_inv));
     if (mean) {
         for (int k = 0; k < RQ_POLICY_INPUT_DIM; ++k) {
-            RQ_REQUIRE(std[k] > 0.0f, RQ_ERR_INVALID_ARGUMENT, "std must be positive");
             pol->std_mean[k] = mean[k];
             pol->std_inv[k] = 1.0f / std[k];
         }
     }
     pol->standardize = mean != nullptr;
-    return policy_upload(pol);
+    const int rc = policy_upload(pol, pol->w_host, "rq_policy_set_standardize");
+    if (rc == RQ_ERR_INVALID_ARGUMENT) {
+        pol->standardize = was;
+        std::memcpy(pol->std_mean, old_mean, sizeof(old_mean));
+        std::memcpy(pol->std_inv, old_inv, sizeof(old_inv));
+    }
+    return rc;
 }
 
 RQ_API int rq_policy_set_squash(rq_policy* pol, int enable) {
@@ -431,7 +465,7 @@ RQ_API int rq_policy_selftest(rq_policy* pol, const float* input, const float* e
         tmp->standardize = true;
         std::memcpy(tmp->std_mean, pol->std_mean, sizeof(tmp->std_mean));
         std::memcpy(tmp->std_inv, pol->std_inv, sizeof(tmp->std_inv));
-        rc = policy_upload(tmp);
+        rc = policy_upload(tmp, tmp->w_host, "rq_policy_selftest");
         if (rc) { rq_policy_destroy(tmp); return rc; }
     }
     std::vector<float> act;

@@ -352,6 +352,8 @@ void pack_policy(const float* weights, float* packed);
 void pack_policy_bf16(const float* weights, float* packed);
 // and for the split-f16 actor: 72 dword images of f16 pairs + 24 fp32 images
 void pack_policy_f16x2(const float* weights, float* packed);
+// the first weight whose pre-scaled operand has no f16 hi / lo split (magnitude >= 65 520), or -1 when the image holds them all
+int policy_f16x2_misfit(const float* weights);
 // The learner's transposed operands (rq_grad.hpp k_policy_grad_backward): unscaled weights, one 64-lane image per A operand.
 // K-step (g, r) of a transposed gate product carries gate row 16 g + 4 q + r in k-slot q - the row the Q-layout delta holds
 // in register r - so lane (q, j) = W[16 g + 4 q + r][j]; W2T: lane (q, j) = W2[q][j] (the 4 actions on K).

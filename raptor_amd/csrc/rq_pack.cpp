@@ -204,6 +204,25 @@ void pack_policy_f16x2(const float* w, float* packed) {
     }
 }
 
+// The first weight (checkpoint order) whose split operand does not fit f16, or -1: an operand of magnitude >= 65 520 after
+// the pre-scale becomes hi = inf, lo = -inf, and inf - inf is a NaN in every contraction it enters.  Exactly the operands
+// pack_policy_f16x2 splits: W0 and b0 (layer_0's bias rides a K-slot), the gate rows of W_i and W_h under their pre-scale,
+// W2; the gate biases, b2 and h0 stay fp32.  A non-finite weight is the caller's (every precision carries it as it is).
+int policy_f16x2_misfit(const float* w) {
+    enum { B0 = 352, WI = 368, WH = 1136, BI = 1904, W2 = 2016, B2 = 2080 };
+    const float kS = -1.4426950408889634f, kT = -2.8853900817779268f;
+    auto misfits = [](float v) { return std::isfinite(v) && (to_f16_rne(v) & 0x7c00u) == 0x7c00u; };
+    for (int i = 0; i < RQ_POLICY_NUM_WEIGHTS; ++i) {
+        float k;
+        if (i < WI) k = 1.0f;                                              // W0, b0
+        else if (i < BI) k = ((i - (i < WH ? WI : WH)) / 16) < 32 ? kS : kT;   // row of W_i / W_h: r, z | n
+        else if (i >= W2 && i < B2) k = 1.0f;
+        else continue;
+        if (misfits(k * w[i])) return i;
+    }
+    return -1;
+}
+
 void pack_logstd_head(const float* w_ls, const float* b_ls, float* image) {
     for (int l = 0; l < 64; ++l) {
         const int q = l >> 4, j = l & 15;

@@ -105,11 +105,15 @@ class Raptor:
                 self._device = device if device is not None else _get_default_device()
             h = C.c_void_p()
             _lib.call("rq_policy_create", self._device._h, _lib.fptr(self._weights), self._weights.size, C.byref(h))
+            try:      # (f16x2 refuses weights whose pre-scaled operand reaches 65 520: no policy then, as if creation had failed)
+                _lib.call("rq_policy_set_precision", h, PRECISIONS[self._precision])
+                if self._native_interval != 1:
+                    _lib.call("rq_policy_set_native_interval", h, self._native_interval)
+            except _lib.RaptorQuadError:
+                _lib.load().rq_policy_destroy(h)
+                raise
             self._h = h
             self._fin = weakref.finalize(self, _lib.load().rq_policy_destroy, h)
-            _lib.call("rq_policy_set_precision", h, PRECISIONS[self._precision])
-            if self._native_interval != 1:
-                _lib.call("rq_policy_set_native_interval", h, self._native_interval)
         elif device is not None and device is not self._device:
             raise _lib.RaptorQuadError(-5, "policy was created on another device")
         return self._h
@@ -129,9 +133,9 @@ class Raptor:
     def set_precision(self, precision):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}")
-        self._precision = precision
-        if self._h is not None:
+        if self._h is not None:       # (refused for f16x2 with weights outside its range: the policy then keeps the precision it had)
             _lib.call("rq_policy_set_precision", self._h, PRECISIONS[precision])
+        self._precision = precision
 
     @staticmethod
     def _checked_interval(interval):
@@ -160,9 +164,9 @@ class Raptor:
         w = np.array(weights, dtype=np.float32, copy=True).reshape(-1)
         if w.size != POLICY_NUM_WEIGHTS:
             raise ValueError(f"expected {POLICY_NUM_WEIGHTS} weights")
-        self._weights, self._weights_on_device = w, False
-        if self._h is not None:
+        if self._h is not None:       # (an f16x2 policy refuses weights outside its range and stays as it was)
             _lib.call("rq_policy_set_weights", self._h, _lib.fptr(w), w.size)
+        self._weights, self._weights_on_device = w, False
 
     def set_standardize(self, mean=None, std=None):
         """Optional Standardize input stage (x - mean) / std (not part of the shipped checkpoint;

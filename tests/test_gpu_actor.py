@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+from actor_reference import _actor_bf16_model, _bf16       # noqa: F401
 from gpu_common import ACTOR_TOL, World, BF16_KAT_TOL      # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -97,30 +98,6 @@ def test_optional_standardize_and_squash_stages(device, oracle, weights):
     pol.reset()
     h = np.zeros((300, 16), np.float32)
     assert np.abs(pol.evaluate_step(x) - oracle.actor_batch_step(weights, x, h)).max() < 5e-5   # |x| up to ~10
-
-
-def _bf16(x):
-    """round-to-nearest-even fp32 -> bf16 -> fp32 (numpy)"""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32)
-    return r.view(np.float32)
-
-
-def _actor_bf16_model(w, x, h):
-    """The bf16 kernel's arithmetic in numpy: operands rounded to bf16, fp32 accumulate, fp32 gates."""
-    W0, b0 = w[0:352].reshape(16, 22), w[352:368]
-    Wi, Wh = w[368:1136].reshape(48, 16), w[1136:1904].reshape(48, 16)
-    bi, bh, W2, b2 = w[1904:1952], w[1952:2000], w[2016:2080].reshape(4, 16), w[2080:2084]
-    sig = lambda v: 1.0 / (1.0 + np.exp(-v))
-    y0 = np.maximum(_bf16(x[:, :22]) @ _bf16(W0).T + _bf16(b0), 0).astype(np.float32)
-    # the gate rows are pre-scaled (r, z by -log2 e, n by -2 log2 e) BEFORE they are rounded to bf16 (pack_policy_bf16)
-    k = np.concatenate([np.full(32, -1.4426950408889634, np.float32), np.full(16, -2.8853900817779268, np.float32)])[:, None]
-    gi, gh = (_bf16(y0) @ _bf16(k * Wi).T) / k.T, (_bf16(h) @ _bf16(k * Wh).T) / k.T
-    r = sig(gi[:, :16] + gh[:, :16] + bi[:16] + bh[:16])
-    z = sig(gi[:, 16:32] + gh[:, 16:32] + bi[16:32] + bh[16:32])
-    n = np.tanh(gi[:, 32:] + bi[32:] + r * (gh[:, 32:] + bh[32:]))
-    hn = ((1 - z) * n + z * h).astype(np.float32)
-    return (_bf16(hn) @ _bf16(W2).T + b2).astype(np.float32), hn
 
 
 def test_bf16_actor_against_kats_and_bf16_model(device, weights, kat):

@@ -16,8 +16,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _loop(device, n, iters, resident, between=None, seed=0):
-    """The README loop as written; -> (observations, actions, final state, hidden state, rewards, resident statistics)."""
+def _loop(device, n, iters, resident, between=None, seed=0, weights=None):
+    """The README loop as written (`weights`: another checkpoint than the shipped one);
+    -> (observations, actions, final state, hidden state, rewards, resident statistics)."""
     import raptor_amd.l2f as l2f
     from raptor_amd.foundation_policy import Raptor
     device.set_resident(resident)
@@ -28,7 +29,7 @@ def _loop(device, n, iters, resident, between=None, seed=0):
     vector.initialize_environment(device, env)
     vector.sample_initial_parameters(device, env, params, rng)
     vector.sample_initial_state(device, env, params, state, rng)
-    policy = Raptor(device)
+    policy = Raptor(device, weights=weights)
     policy.reset()
     obs = np.zeros((n, env.OBSERVATION_DIM), np.float32)
     O, A = [], []
@@ -62,6 +63,20 @@ def test_readme_loop_is_bit_identical_with_and_without_the_resident_executor(dev
     assert _same(off, on)
     assert off[6]["commands"] == 0 and on[6]["commands"] >= 140 and on[6]["replays"] == 0, (off[6], on[6])
     assert on[6]["starts"] <= 10         # one kernel per 0.75 ms of looping (rq_resident.cpp kResidentHostLifeNs), none per iteration
+
+
+@pytest.mark.parametrize("n", [8, 200])
+@pytest.mark.parametrize("family", ["perturbed", "fresh", "sat8"])
+def test_readme_loop_is_bit_identical_with_and_without_the_resident_executor_on_other_weights(device, family, n):
+    """The same on weights the shipped checkpoint does not resemble (tests/actor_reference.py: perturbed, fresh, gates saturated):
+    the single-tile policy step and the general kernel against the launches that tests/test_gpu_actor_float64.py holds to float64."""
+    import actor_reference as AR
+    w = AR.weights(family)
+    off = _loop(device, n, 150, False, weights=w)
+    on = _loop(device, n, 150, True, weights=w)
+    assert _same(off, on)
+    assert off[6]["commands"] == 0 and on[6]["commands"] >= 140 and on[6]["replays"] == 0, (off[6], on[6])
+    assert on[6]["starts"] <= 10
 
 
 def test_beyond_256_envs_the_loop_keeps_its_launches(device):
@@ -299,6 +314,19 @@ def test_the_policy_alone_is_bit_identical_with_and_without_the_resident_executo
     and fetched behind the line (up to 16), compact rows and rows of a wider array."""
     off = _policy_loop(device, batch, 400, False, wide=wide)
     on = _policy_loop(device, batch, 400, True, wide=wide)
+    assert np.array_equal(off[0].view(np.uint32), on[0].view(np.uint32)) and np.array_equal(off[1].view(np.uint32), on[1].view(np.uint32))
+    assert off[2]["commands"] == 0 and on[2]["commands"] >= 390 and on[2]["replays"] == 0, (off[2], on[2])
+
+
+@pytest.mark.parametrize("batch", [1, 16])
+@pytest.mark.parametrize("family", ["perturbed", "fresh", "sat8"])
+def test_the_policy_alone_is_bit_identical_with_and_without_the_resident_executor_on_other_weights(device, family, batch):
+    """The same 400 steps on the weight families of tests/actor_reference.py, rows in the poll (1) and behind the line (16)."""
+    import actor_reference as AR
+    from raptor_amd.foundation_policy import Raptor
+    w = AR.weights(family)
+    off = _policy_loop(device, batch, 400, False, policy=Raptor(device, weights=w))
+    on = _policy_loop(device, batch, 400, True, policy=Raptor(device, weights=w))
     assert np.array_equal(off[0].view(np.uint32), on[0].view(np.uint32)) and np.array_equal(off[1].view(np.uint32), on[1].view(np.uint32))
     assert off[2]["commands"] == 0 and on[2]["commands"] >= 390 and on[2]["replays"] == 0, (off[2], on[2])
 
