@@ -583,6 +583,29 @@ RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* policy, rq_optimiz
 /* the policy's current parameters, 2 084 floats in the checkpoint order (after device-side updates: fetched from the device) */
 RQ_API int rq_policy_get_weights(rq_policy* policy, float* host_out);
 
+/* ---- Probes: what the GRU state knows about the quadrotor, and how early in an episode it knows it ----
+ * Both calls read the state ENTERING every recorded step under the forward's episode rules from the learned initial state
+ * (RQ_GRAD_START_INITIAL): the saved state a learner call above left in the trajectory if it was made by this policy at its current
+ * weights with that start over the current length, else the forward is run first (its state-only form) and tagged.  The policy's own
+ * hidden state is not changed.  Refusals as for rq_trajectory_policy_forward, and null pointers, before anything is enqueued.
+ * rq_trajectory_get_hidden: out [length][n_envs][16], the learner layout.
+ * rq_trajectory_probe_moments: targets y [n_targets][ld_targets], constant over time per env (1 <= n_targets <= 15, ld_targets >=
+ * n_envs; columns >= n_envs are never read into a sum).  Per env an integer AGE: 0 at t = 0; a step is live when its done code is
+ * not 4; a live step contributes the sample z = [1, h (16), y (n_targets), 0 ...] of D = 32 entries at its age; after a live step
+ * with code 1 or 2 the age is 0 again, after any other live step it is one more; a frozen step changes and contributes nothing.
+ * age_edges: host array [n_buckets + 1], strictly ascending, 1 <= n_buckets <= 32; a sample of age a belongs to bucket b when
+ * age_edges[b] <= a < age_edges[b + 1], any other sample is dropped.  moments [n_buckets][32][32] doubles: per bucket the full
+ * symmetric sum of z z^T (fp32 products and sums within a block of 64 envs, float64 across blocks); counts [n_buckets]: the samples.
+ * Deterministic: no float atomics, the same bits every run.
+ * memory: RQ_DST_HOST = targets, moments and counts are host arrays (targets checked finite in the envs' columns; synchronous);
+ * RQ_DST_DEVICE / RQ_DST_DEVICE_ASYNC = device memory of the trajectory's device (synchronised before return / only enqueued on
+ * rq_device_stream()); age_edges is a host array in every mode and is read before the call returns. */
+RQ_API int rq_trajectory_get_hidden(rq_trajectory* t, rq_policy* policy, float* out, int memory);
+RQ_API int rq_trajectory_probe_moments(rq_trajectory* t, rq_policy* policy,
+                                       const float* targets, uint32_t ld_targets, uint32_t n_targets,
+                                       const uint32_t* age_edges, uint32_t n_buckets,
+                                       double* moments, uint64_t* counts, int memory);
+
 /* ---- Teacher bank: the distillation step of the reference (README.md:208-216: ~1000 teacher policies, one per
  * sampled quadrotor, queried on the states the student visited).  The teachers'
  * architecture is not in the reference tree - this is rl-tools' plain MLP family [UPSTREAM-UNVERIFIED]:

@@ -184,6 +184,8 @@ _SIGNATURES = {
     "rq_optimizer_set_lr": [_vp, C.c_double],
     "rq_trajectory_distill": [_vp, _vp, _vp, _fp, C.c_uint32, C.c_int, C.c_uint32, _fp, C.c_int],
     "rq_policy_get_weights": [_vp, _fp],
+    "rq_trajectory_get_hidden": [_vp, _vp, _fp, C.c_int],
+    "rq_trajectory_probe_moments": [_vp, _vp, _fp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_int],
     "rq_comm_unique_id": [_vp, C.c_size_t],
     "rq_comm_create": [_vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.POINTER(_vp)],
     "rq_comm_destroy": [_vp],

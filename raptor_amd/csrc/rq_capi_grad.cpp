@@ -8,10 +8,10 @@
 
 using namespace rqh;
 
-namespace {
+namespace rqh {
 
 // what both directions refuse: only the fp32 student without input or output stages has a gradient here
-int check_pair(rq_trajectory* t, rq_policy* pol, const char* what) {
+int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what) {
     RQ_REQUIRE(t && pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(pol->dev == t->env->dev, RQ_ERR_SHAPE_MISMATCH, std::string(what) + ": the policy lives on another device");
     RQ_REQUIRE(t->length > 0, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": the trajectory is empty");
@@ -23,6 +23,27 @@ int check_pair(rq_trajectory* t, rq_policy* pol, const char* what) {
                std::string(what) + ": the SampleAndSquash stage has no gradient here (RQ_SAS_OFF)");
     return require_native_rate(pol, what);
 }
+
+int grad_saved_initial(rq_trajectory* t, rq_policy* pol) {
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    if (t->grad.valid && t->grad.policy == pol && t->grad.weight_version == pol->weight_version && t->grad.length == t->length &&
+        t->grad.start == RQ_GRAD_START_INITIAL)
+        return RQ_OK;
+    t->grad.valid = false;
+    RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)t->length * RQ_POLICY_HIDDEN_DIM * env->ld));
+    RQ_HIP(rq::launch_policy_grad_forward_state(dev->stream, env->n, env->ld, t->length, pol->w_packed, t->obs, t->done, nullptr, pol->ld,
+                                                1, t->grad.saved));
+    t->grad.valid = true; t->grad.policy = pol; t->grad.weight_version = pol->weight_version; t->grad.length = t->length;
+    t->grad.start = RQ_GRAD_START_INITIAL;
+    return RQ_OK;
+}
+
+}  // namespace rqh
+
+namespace {
+
+int check_pair(rq_trajectory* t, rq_policy* pol, const char* what) { return grad_check_pair(t, pol, what); }
 
 int check_memory(int memory) {
     RQ_REQUIRE(memory >= RQ_DST_HOST && memory <= RQ_DST_DEVICE_ASYNC, RQ_ERR_INVALID_ARGUMENT, "memory must be 0, 1 or 2");

@@ -209,18 +209,25 @@ hipError_t launch_policy_grad_backward(hipStream_t s, uint32_t n, uint32_t ld, u
     return hipGetLastError();
 }
 
-hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed, const float* gpacked,
-                                   const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial,
-                                   float* saved, const float* target, uint32_t ld_y, float* partial, float* grad, float* loss,
-                                   unsigned long long* live) {
+hipError_t launch_policy_grad_forward_state(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
+                                            const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h,
+                                            int start_initial, float* saved) {
     if (n == 0 || steps == 0) return hipErrorInvalidValue;
     const unsigned g = (n + kFusedBlock - 1) / kFusedBlock;
-    const uint32_t si = start_initial ? 1u : 0u, waves = (n + 63) / 64;
+    const uint32_t si = start_initial ? 1u : 0u;
     if (n > kOneWavePerSimdEnvs)        // launch_policy_grad_forward's choice of build
         k_policy_grad_forward_state<ActorF32Lean><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, saved);
     else
         k_policy_grad_forward_state<ActorF32><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, saved);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed, const float* gpacked,
+                                   const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial,
+                                   float* saved, const float* target, uint32_t ld_y, float* partial, float* grad, float* loss,
+                                   unsigned long long* live) {
+    const uint32_t si = start_initial ? 1u : 0u, waves = (n + 63) / 64;
+    hipError_t e = launch_policy_grad_forward_state(s, n, ld, steps, packed, obs, done, hidden, ld_h, start_initial, saved);
     if (e != hipSuccess) return e;
     float* wave_sse = partial + (size_t)waves * RQ_POLICY_NUM_WEIGHTS;         // partial: [waves][2084] | sse [waves] | live [waves]
     uint32_t* wave_live = reinterpret_cast<uint32_t*>(wave_sse + waves);

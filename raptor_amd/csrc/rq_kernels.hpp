@@ -234,6 +234,10 @@ hipError_t launch_policy_grad_backward(hipStream_t s, uint32_t n, uint32_t ld, u
 // [2084] = d/dtheta of loss = mean over live entries of (a - y)^2, loss [1], live [1] = M.  partial: [waves][2084] floats followed
 // by 2 x waves words (policy_loss_partial_floats).  Deterministic; M = 0 gives loss 0 and a zero gradient.
 constexpr size_t policy_loss_partial_floats(uint32_t n) { return (size_t)((n + 63) / 64) * (RQ_POLICY_NUM_WEIGHTS + 2); }
+// its first launch alone: the forward that saves the state and stores no action (the probes read nothing else)
+hipError_t launch_policy_grad_forward_state(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
+                                            const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h,
+                                            int start_initial, float* saved);
 hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed, const float* gpacked,
                                    const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial,
                                    float* saved, const float* target, uint32_t ld_y, float* partial, float* grad, float* loss,

@@ -280,6 +280,10 @@ struct rq_trajectory {
         int start = 0;                 // enum rq_grad_start
         DeviceBuffer<float> out;       // the loss-seeded calls: grad [2084] | losses [n_updates] before they go to the caller
         DeviceBuffer<unsigned long long> live;    // [1]: M, the live entries of the last loss
+        // the probes (rq_capi_probe.cpp): the waves' partial moments and counts (rq::probe_partial_floats), and the call's small
+        // device-side block: moments | counts | age edges (| the targets of a host-memory call)
+        DeviceBuffer<float> probe;
+        DeviceBuffer<double> probe_io;
     } grad;
 };
 
@@ -488,6 +492,13 @@ int policy_images16(rq_policy* pol);     // the bf16 / f16x2 images repacked fro
 // what is defined at the native rate only (sequence evaluation, relabelling, the learner, the self test) refuses a policy whose
 // native interval is above 1: a recording does not carry the phase it started at
 int require_native_rate(const rq_policy* pol, const char* what);
+
+// ---- rq_capi_grad.cpp: what the learner and the probes (rq_capi_probe.cpp) share ----
+// what every call over a (recording, policy) pair refuses: only the fp32 student without input or output stages, at the native rate
+int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what);
+// inside the caller's DeviceScope: t->grad.saved holds the state of a forward by `pol` from the learned initial state at its current
+// weights - the one a forward or a loss call left if its tags say so, else the state-only forward is enqueued and tagged
+int grad_saved_initial(rq_trajectory* t, rq_policy* pol);
 
 // ---- rq_capi_policy_bank.cpp: what the bank's rollout and its learner (rq_capi_grad.cpp) share; all but bank_check_ids need the
 // caller's DeviceScope ----

@@ -1,0 +1,222 @@
+// rq_probe.hip - linear probes of the GRU state: the second moments of z = [1, h_t (16), y (M)], zero-padded to D = 32, over the
+// state entering every recorded step (rq_trajectory::Grad::saved, what the learner's forward leaves), split by the age of the episode.
+//
+//   kernel            what                                                                       bound
+//   k_probe_moments   a wave per 64 envs, t = 0 .. T-1: S_b += z z^T for the bucket b of the age  HBM (64 B/env-step read) / f32 MFMA rate
+//   k_probe_reduce    the waves' partials in ascending wave order, in float64                     HBM (4 KB per wave and bucket)
+//   k_probe_hidden_rows   saved [T][16][ld] -> [T][n][16], the learner layout (rq_trajectory_get_hidden)
+//
+// Layout.  Lane l of a wave IS env 64 w + l: it loads its 16 state rows (16 coalesced 256-byte reads per step), keeps its age and
+// its targets in registers and owns row l of the wave's LDS tile, [64][PZ_ROW]: columns 0 .. 31 = z, column 32 = the bucket of the
+// sample (-1: none).  The contraction runs over envs on v_mfma_f32_16x16x4_f32: both operands need feature j on lane j and the env
+// on the k-slot q (lane = 16 q + j), so K-step u reads rows 4u + q column-wise: A = B = z[16 a + j] of env 4u + q.  Of the 2 x 2
+// output tiles S[a][b] three are computed; S[1][0] is S[0][1] transposed - the same products in the same order, hence the same
+// bits - and the reduction mirrors it.  PZ_ROW = 49: odd, so the row-wise writes of a step touch 32 distinct banks per half wave,
+// and = 17 mod 32, so the two rows a half wave reads column-wise share one bank only.
+//
+// The age rule is the forward's episode rule (rq_grad_forward.inc): age 0 at t = 0; a step is live when its done code is not 4
+// and its column is below n; a live step contributes (h entering step t, age); after a live step with code 1 or 2 the age is 0
+// again, after any other live step it grows by 1; a frozen step changes nothing and contributes nothing.  Sample of age a goes to
+// bucket b when edges[b] <= a < edges[b + 1]; others are dropped.  The lane keeps idx = the number of edges <= age, which moves by
+// at most one per step (the edges ascend strictly).
+//
+// Lanes of a wave sit in different buckets at the same step (episodes end at different times): every bucket present is handled in a
+// wave-uniform loop, the one whose accumulators are in registers first.  A lane that is not live or not in the bucket contributes
+// through SELECTS, never products: an exact zero whatever its registers or its LDS row hold (NaN in a padding column or in the
+// state of a frozen step reaches no sum).  The accumulators of the bucket in flight are added to the wave's own partial slot
+// [wave][bucket][D][D] when another bucket takes over and at the end: plain loads and stores to memory no other wave touches.
+//
+// Not a translation unit of its own: rq_teacher.hip includes this file at its end, so the kernels live in that unit's code object
+// and its listing (the library ships three code objects and the gate that decodes them counts them).  Nothing here uses anything
+// of that unit, and adding kernels to a unit leaves its other kernels' text as it was (tools/kernel_listing_diff.py).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rq_probe.hpp"
+
+namespace rq {
+
+namespace {
+
+typedef float pf32x4 __attribute__((ext_vector_type(4)));
+
+enum { PZ_BUCKET = 32, PZ_ROW = 49, PZ_TILE = 32 * 32 };
+
+__device__ __forceinline__ pf32x4 probe_mfma(float a, float b, pf32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// the accumulators of bucket `b` into the wave's slot; `first`: the slot has not been written yet
+__device__ __forceinline__ void probe_flush(float* __restrict__ slot, uint32_t* __restrict__ count, bool first, uint32_t lane,
+                                            const pf32x4& s00, const pf32x4& s01, const pf32x4& s11, uint32_t cnt) {
+    const uint32_t q = lane >> 4, j = lane & 15;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float* p00 = slot + (4 * q + r) * 32 + j;
+        float* p11 = slot + (16 + 4 * q + r) * 32 + 16 + j;
+        if (first) {
+            p00[0] = s00[r]; p00[16] = s01[r]; p11[0] = s11[r];
+        } else {
+            p00[0] = p00[0] + s00[r]; p00[16] = p00[16] + s01[r]; p11[0] = p11[0] + s11[r];
+        }
+    }
+    if (lane == 0) count[0] = first ? cnt : count[0] + cnt;
+}
+
+__global__ __launch_bounds__(64) void k_probe_moments(uint32_t n, uint32_t ld, uint32_t steps, const float* __restrict__ saved,
+                                                      const uint8_t* __restrict__ done, const float* __restrict__ y, uint32_t ld_y,
+                                                      uint32_t n_targets, const ProbeEdges edges, uint32_t n_buckets,
+                                                      float* __restrict__ partial, uint32_t* __restrict__ wave_counts) {
+    __shared__ float zt[64 * PZ_ROW];
+    __shared__ uint32_t ed[kProbeMaxBuckets + 1];
+    const uint32_t lane = threadIdx.x & 63, q = lane >> 4, j = lane & 15;
+    const uint32_t wave = blockIdx.x, e = wave * 64 + lane;
+    const bool ev = e < n;                           // e < ld (the launcher checks): the forward saved the state of every column
+    const uint32_t ey = ev ? e : 0u;                 // padding lanes read env 0's targets and select them away
+    if (lane <= n_buckets) ed[lane] = edges.v[lane];
+    float* row = zt + lane * PZ_ROW;
+    row[0] = 1.0f;
+#pragma unroll
+    for (uint32_t m = 0; m < kProbeMaxTargets; ++m) {
+        const float v = y[(size_t)(m < n_targets ? m : 0u) * ld_y + ey];
+        row[17 + m] = ev && m < n_targets ? v : 0.0f;
+    }
+    __syncthreads();
+    const uint32_t idx0 = ed[0] == 0u ? 1u : 0u;     // edges <= age 0
+    uint32_t age = 0, idx = idx0;
+
+    float* const wave_slot = partial + (size_t)wave * n_buckets * PZ_TILE;
+    uint32_t* const wave_count = wave_counts + (size_t)wave * n_buckets;
+    const pf32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    pf32x4 s00 = zero, s01 = zero, s11 = zero;
+    uint32_t cnt = 0, touched = 0;
+    int cur = -1;                                     // the bucket in flight (wave-uniform)
+
+    float hn[16];
+    uint32_t dn = 4;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) hn[r] = saved[(size_t)r * ld + e];
+    dn = done[e];
+
+    for (uint32_t s = 0; s < steps; ++s) {
+        float h[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) h[r] = hn[r];
+        const uint32_t d = dn;
+        if (s + 1 < steps) {                          // the next step's rows are on their way while this one is contracted
+#pragma unroll
+            for (int r = 0; r < 16; ++r) hn[r] = saved[((size_t)(s + 1) * 16 + r) * ld + e];
+            dn = done[(size_t)(s + 1) * ld + e];
+        }
+        const bool live = ev && d != 4u;
+        const int bk = live && idx >= 1u && idx <= n_buckets ? (int)idx - 1 : -1;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) row[1 + r] = h[r];
+        row[PZ_BUCKET] = __int_as_float(bk);
+        if (live) {
+            if (d == 1u || d == 2u) { age = 0; idx = idx0; }
+            else {
+                ++age;
+                if (idx <= n_buckets && ed[idx] == age) ++idx;
+            }
+        }
+        __syncthreads();
+
+        uint64_t todo = __builtin_amdgcn_ballot_w64(bk >= 0);
+        bool head = true;
+        while (todo) {
+            int b;
+            const uint64_t in_cur = head && cur >= 0 ? __builtin_amdgcn_ballot_w64(bk == cur) : 0ull;
+            if (in_cur) b = cur;
+            else b = __builtin_amdgcn_readlane(bk, (int)__builtin_ctzll(todo));
+            head = false;
+            const uint64_t members = __builtin_amdgcn_ballot_w64(bk == b);
+            todo &= ~members;
+            if (b != cur) {
+                if (cur >= 0) {
+                    probe_flush(wave_slot + (size_t)cur * PZ_TILE, wave_count + cur, !((touched >> cur) & 1u), lane, s00, s01, s11, cnt);
+                    touched |= 1u << cur;
+                }
+                s00 = s01 = s11 = zero;
+                cnt = 0;
+                cur = b;
+            }
+            cnt += (uint32_t)__builtin_popcountll(members);
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                if (((members >> (4 * u)) & 0xfull) == 0) continue;          // none of envs 4u .. 4u+3 is in the bucket: exact zeros
+                const float* src = zt + (4 * u + q) * PZ_ROW;                // k-slot q = env 4u + q of the wave
+                const bool in = __float_as_int(src[PZ_BUCKET]) == b;
+                const float lo = in ? src[j] : 0.0f, hi = in ? src[16 + j] : 0.0f;
+                s00 = probe_mfma(lo, lo, s00);
+                s01 = probe_mfma(lo, hi, s01);
+                s11 = probe_mfma(hi, hi, s11);
+            }
+        }
+        __syncthreads();
+    }
+    if (cur >= 0) {
+        probe_flush(wave_slot + (size_t)cur * PZ_TILE, wave_count + cur, !((touched >> cur) & 1u), lane, s00, s01, s11, cnt);
+        touched |= 1u << cur;
+    }
+    for (uint32_t b = 0; b < n_buckets; ++b)          // a bucket this wave never met: zeros, so that the reduction reads no stale word
+        if (!((touched >> b) & 1u)) probe_flush(wave_slot + (size_t)b * PZ_TILE, wave_count + b, true, lane, zero, zero, zero, 0u);
+}
+
+// moments[b][i][k] = sum over waves w = 0, 1, ... of the partial, in that order, in float64; the lower left tile is the upper
+// right one mirrored (k_probe_moments computes S[0][1] only).  counts[b] = the waves' counts.
+__global__ __launch_bounds__(256) void k_probe_reduce(uint32_t waves, uint32_t n_buckets, const float* __restrict__ partial,
+                                                      const uint32_t* __restrict__ wave_counts, double* __restrict__ moments,
+                                                      unsigned long long* __restrict__ counts) {
+    const uint32_t o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= n_buckets * PZ_TILE) return;
+    const uint32_t b = o / PZ_TILE, i = (o % PZ_TILE) / 32, k = o % 32;
+    const uint32_t src = i >= 16 && k < 16 ? k * 32 + i : i * 32 + k;
+    double acc = 0.0;
+    for (uint32_t w = 0; w < waves; ++w) acc += (double)partial[((size_t)w * n_buckets + b) * PZ_TILE + src];
+    moments[o] = acc;
+    if (o % PZ_TILE == 0) {
+        unsigned long long c = 0;
+        for (uint32_t w = 0; w < waves; ++w) c += wave_counts[(size_t)w * n_buckets + b];
+        counts[b] = c;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_probe_hidden_rows(uint32_t n, uint32_t ld, uint32_t steps, const float* __restrict__ saved,
+                                                           float* __restrict__ out) {
+    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    for (uint32_t t = blockIdx.y; t < steps; t += gridDim.y) {
+        float v[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = saved[((size_t)t * 16 + r) * ld + e];      // coalesced over envs
+        float* dst = out + ((size_t)t * n + e) * 16;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dst[r] = v[r];
+    }
+}
+
+}  // namespace
+
+hipError_t launch_probe_moments(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, const uint8_t* done,
+                                const float* y, uint32_t ld_y, uint32_t n_targets, const ProbeEdges& edges, uint32_t n_buckets,
+                                float* partial, double* moments, unsigned long long* counts) {
+    if (n == 0 || steps == 0 || n_targets == 0 || n_targets > kProbeMaxTargets || n_buckets == 0 || n_buckets > kProbeMaxBuckets)
+        return hipErrorInvalidValue;
+    const uint32_t waves = (n + 63) / 64;
+    if (ld < 64 * waves) return hipErrorInvalidValue;          // every lane of every wave reads its own column of saved / done
+    uint32_t* wave_counts = reinterpret_cast<uint32_t*>(partial + (size_t)waves * n_buckets * PZ_TILE);
+    k_probe_moments<<<waves, 64, 0, s>>>(n, ld, steps, saved, done, y, ld_y, n_targets, edges, n_buckets, partial, wave_counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    k_probe_reduce<<<(n_buckets * PZ_TILE + 255) / 256, 256, 0, s>>>(waves, n_buckets, partial, wave_counts, moments, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_probe_hidden_rows(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, float* out) {
+    if (n == 0 || steps == 0) return hipSuccess;
+    k_probe_hidden_rows<<<dim3((n + 255) / 256, steps < 65535u ? steps : 65535u), 256, 0, s>>>(n, ld, steps, saved, out);
+    return hipGetLastError();
+}
+
+}  // namespace rq

@@ -1,0 +1,32 @@
+// rq_probe.hpp - what the host layer (rq_capi_probe.cpp) needs of rq_probe.hip: the second moments of z = [1, h_t, y] over the
+// saved state of a recording, split by episode age.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace rq {
+
+constexpr uint32_t kProbeDim = 32;             // D: 1 + 16 hidden + up to 15 targets, zero-padded
+constexpr uint32_t kProbeMaxTargets = 15;
+constexpr uint32_t kProbeMaxBuckets = 32;
+
+// the wave partials: S [waves][n_buckets][D][D] floats, then counts [waves][n_buckets] words
+constexpr size_t probe_partial_floats(uint32_t n, uint32_t n_buckets) {
+    return (size_t)((n + 63) / 64) * n_buckets * (kProbeDim * kProbeDim + 1);
+}
+
+// the age edges travel by value, as a kernel argument: edges v[0 .. n_buckets], strictly ascending
+struct ProbeEdges { uint32_t v[kProbeMaxBuckets + 1]; };
+
+// saved [steps][16][ld], done [steps][ld], y [n_targets][ld_y] (columns below n are read) -> moments [n_buckets][D][D] doubles (the full symmetric matrix) and counts [n_buckets].  Two launches:
+// k_probe_moments (a wave per 64 envs) and k_probe_reduce (the waves' partials in ascending wave order, in float64).
+// Deterministic: no atomics, every order fixed.
+hipError_t launch_probe_moments(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, const uint8_t* done,
+                                const float* y, uint32_t ld_y, uint32_t n_targets, const ProbeEdges& edges, uint32_t n_buckets,
+                                float* partial, double* moments, unsigned long long* counts);
+
+// saved [steps][16][ld] -> out [steps][n][16], the learner layout
+hipError_t launch_probe_hidden_rows(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, float* out);
+
+}  // namespace rq

@@ -831,3 +831,6 @@ hipError_t launch_rollout_teachers(hipStream_t s, uint32_t n_tiles, uint32_t h1,
 }
 
 }  // namespace rq
+
+// the probes of the GRU state: kernels of their own in this unit's code object (see the file's header)
+#include "rq_probe.hip"

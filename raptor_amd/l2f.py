@@ -694,6 +694,25 @@ class VectorModule:
                           _lib.fptr(out) if fetch else None, 1 if overwrite else 0)
                 return out
 
+            def hidden(self, policy, device=False):
+                """The GRU state of ``policy`` ENTERING every recorded step, [T, N, 16] float32: its forward over the
+                recorded observations from the learned initial state (back to it after done codes 1 and 2, held on code
+                4) - what ``raptor_amd.probing`` reads.  NumPy, or with ``device=True`` a torch tensor on the engine's
+                device.  The policy's own hidden state is not changed."""
+                T, N = len(self), mod.N_ENVIRONMENTS
+                pol = policy._handle(self._env._device)
+                self._learner_forwards = getattr(self, "_learner_forwards", 0) + 1     # the saved state may be this call's now
+                if not device:
+                    out = np.empty((T, N, 16), np.float32)
+                    _lib.call("rq_trajectory_get_hidden", self._require("trajectory"), pol, _lib.fptr(out), 0)
+                    return out
+                import torch
+                dev = torch.device(f"cuda:{_ordinal_of(self)}")
+                out = torch.empty((T, N, 16), dtype=torch.float32, device=dev)
+                torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
+                _lib.call("rq_trajectory_get_hidden", self._require("trajectory"), pol, out.data_ptr(), 1)
+                return out
+
             def relabel_teachers(self, bank, teacher_ids, overwrite=False, fetch=True):
                 """Actions of MLP teacher ``teacher_ids[i]`` of ``bank`` (raptor_amd.teachers.TeacherBank) on every
                 recorded step of env i, in one launch on the matrix cores -> [T, N, 4] (``fetch=False``: only on

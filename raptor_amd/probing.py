@@ -1,0 +1,195 @@
+"""Linear probes of the policy's GRU state: what does h_t know about the quadrotor it flies, and how early in an episode?
+
+The policy is one set of weights for any quadrotor because the GRU identifies the system in flight.  A probe regresses per-env
+targets y (log mass, thrust-to-weight, motor lag, ...) on the state h_t ENTERING each recorded step, separately for every bucket of
+episode age.  The data-sized part runs on the device in one pass over the recording (rq_trajectory_probe_moments, csrc/rq_probe.hip):
+per bucket the second moments S = sum of z z^T with z = [1, h (16), y (M)].  Everything after that is 17 x 17 algebra per bucket
+in float64, here: the fit solves the normal equations, and R^2 on ANOTHER recording needs only that recording's moments.
+
+    y, names = probing.targets_from_params(params.numpy(), env.config, ["log_mass", "thrust_to_weight", "tau_rise"])
+    y, mean, std = probing.standardise(y)
+    probe = probing.HiddenProbe(policy, y, names, probing.log_age_edges(500, 10))
+    W = probe.fit(probe.moments(traj_a))
+    r2 = probe.r2(probe.moments(traj_b), W)          # [buckets, targets], held out
+
+Age follows the forward's episode rule: 0 at the first recorded step; a step is live when its done code is not 4; after a live
+step with code 1 or 2 the age is 0 again, after any other live step one more; frozen steps neither count nor age.
+"""
+
+import numpy as np
+
+from . import _lib
+
+HIDDEN = _lib.POLICY_HIDDEN_DIM
+DIM = 32                      # z = [1, h (16), y (M <= 15)], zero-padded
+MAX_TARGETS, MAX_BUCKETS = 15, 32
+MIN_SAMPLES = HIDDEN + 2      # a bucket with fewer samples than unknowns + 1 is not fitted
+
+# rq_param_field (include/raptor_quad.h)
+_P_MASS, _P_JXX, _P_JZZ = 0, 1, 3
+_P_C0, _P_C1, _P_C2, _P_TORQUE_CONST, _P_TAU_RISE, _P_TAU_FALL = 16, 17, 18, 19, 20, 21
+_P_RPM_MAX, _P_HOVER_ACTION = 23, 25
+
+
+def _thrust_to_weight(p, g):
+    r = p[:, _P_RPM_MAX]
+    return 4.0 * (p[:, _P_C0] + p[:, _P_C1] * r + p[:, _P_C2] * r * r) / (p[:, _P_MASS] * g)
+
+
+TARGETS = {
+    "log_mass": lambda p, g: np.log(p[:, _P_MASS]),
+    "thrust_to_weight": _thrust_to_weight,            # four rotors at RPM_MAX over m g
+    "log_jxx": lambda p, g: np.log(p[:, _P_JXX]),
+    "log_jzz": lambda p, g: np.log(p[:, _P_JZZ]),
+    "tau_rise": lambda p, g: p[:, _P_TAU_RISE],
+    "tau_fall": lambda p, g: p[:, _P_TAU_FALL],
+    "torque_const": lambda p, g: p[:, _P_TORQUE_CONST],
+    "hover_action": lambda p, g: p[:, _P_HOVER_ACTION],
+}
+
+
+def targets_from_params(params, config, names):
+    """``params`` [N, 26] (``VectorParameters.numpy()``), ``config`` the env's configuration (its ``gravity`` is read; a float is
+    taken as g) -> (y [N, M] float32, names).  Supported names: the keys of ``TARGETS``."""
+    p = np.asarray(params, np.float64)
+    if p.ndim != 2 or p.shape[1] != _lib.PARAM_DIM:
+        raise ValueError(f"params must be [N, {_lib.PARAM_DIM}]")
+    names = list(names)
+    unknown = [n for n in names if n not in TARGETS]
+    if unknown:
+        raise ValueError(f"unknown target(s) {unknown}; supported: {sorted(TARGETS)}")
+    if not 1 <= len(names) <= MAX_TARGETS:
+        raise ValueError(f"1 .. {MAX_TARGETS} targets, not {len(names)}")
+    g = float(getattr(config, "gravity", config))
+    y = np.stack([TARGETS[n](p, g) for n in names], axis=1)
+    return y.astype(np.float32), names
+
+
+def standardise(y):
+    """-> (y standardised to zero mean and unit variance over envs, mean [M], std [M]).  The probe's R^2 is SST - SSE over SST from
+    fp32 moments: a target far from zero mean would lose both to cancellation.  A constant target keeps std 1."""
+    y = np.asarray(y, np.float64)
+    mean = y.mean(axis=0)
+    std = y.std(axis=0)
+    std = np.where(std > 0, std, 1.0)
+    return ((y - mean) / std).astype(np.float32), mean, std
+
+
+def log_age_edges(limit, n):
+    """n buckets of episode age up to ``limit`` (exclusive), doubling: 0, 1, 2, 4, 8, ..., limit -> uint32 [n + 1]."""
+    n, limit = int(n), int(limit)
+    if not 1 <= n <= MAX_BUCKETS:
+        raise ValueError(f"1 .. {MAX_BUCKETS} buckets, not {n}")
+    edges = [0] + [1 << k for k in range(n - 1)] + [limit]
+    if any(b <= a for a, b in zip(edges, edges[1:])) or limit >= 1 << 32:
+        raise ValueError(f"{n} doubling buckets do not fit below {limit}")
+    return np.asarray(edges, np.uint32)
+
+
+class ProbeMoments:
+    """Per age bucket the sums of z z^T, ``S`` [B, 32, 32] float64, and the samples, ``counts`` [B].  Moments of several
+    recordings (or of several devices' shares of one) add with ``+``."""
+
+    def __init__(self, S, counts):
+        self.S = np.asarray(S, np.float64)
+        self.counts = np.asarray(counts, np.uint64)
+        if self.S.ndim != 3 or self.S.shape[1:] != (DIM, DIM) or self.counts.shape != (self.S.shape[0],):
+            raise ValueError("S must be [B, 32, 32] and counts [B]")
+
+    def __add__(self, other):
+        if self.S.shape != other.S.shape:
+            raise ValueError("moments of different bucket counts do not add")
+        return ProbeMoments(self.S + other.S, self.counts + other.counts)
+
+    def __radd__(self, other):          # sum([...]) starts from 0
+        return self if isinstance(other, int) and other == 0 else NotImplemented
+
+
+class HiddenProbe:
+    """``targets`` [N, M] float32 (finite; one row per env, constant over time), ``names`` [M], ``age_edges`` [B + 1] strictly
+    ascending (``log_age_edges``).  ``policy``: the fp32 policy without Standardize / SampleAndSquash stages, at the native rate."""
+
+    def __init__(self, policy, targets, names, age_edges):
+        y = np.asarray(targets, np.float32)
+        if y.ndim != 2 or not 1 <= y.shape[1] <= MAX_TARGETS:
+            raise ValueError(f"targets must be [N, 1 .. {MAX_TARGETS}]")
+        if len(names) != y.shape[1]:
+            raise ValueError("one name per target")
+        if not np.isfinite(y).all():
+            raise ValueError("targets must be finite")
+        e = np.asarray(age_edges, np.int64)
+        if e.ndim != 1 or not 2 <= e.size <= MAX_BUCKETS + 1 or (np.diff(e) <= 0).any() or e[0] < 0 or e[-1] >= 1 << 32:
+            raise ValueError(f"age_edges must be 2 .. {MAX_BUCKETS + 1} strictly ascending uint32 values")
+        self.policy, self.names = policy, list(names)
+        self.age_edges = e.astype(np.uint32)
+        self.n_targets, self.n_buckets = y.shape[1], e.size - 1
+        self._y = np.ascontiguousarray(y.T)           # [M, N]: what the engine reads
+        self._y_dev = None
+
+    # ---- the device's part ----
+    def moments(self, traj, device=False):
+        """The moments of ``traj`` under this probe's policy -> ProbeMoments (host, float64).  ``device=True`` (torch): targets,
+        moments and counts stay in device memory for the call - the targets are uploaded once per probe - and only the
+        B x 8 KB result crosses."""
+        N = self._y.shape[1]
+        pol = self.policy._handle(traj._env._device)
+        h = traj._require("trajectory")
+        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1      # the saved state may be this call's now
+        B, M = self.n_buckets, self.n_targets
+        edges = self.age_edges.ctypes.data
+        if not device:
+            S, counts = np.empty((B, DIM, DIM), np.float64), np.empty(B, np.uint64)
+            _lib.call("rq_trajectory_probe_moments", h, pol, _lib.fptr(self._y), N, M, edges, B, S.ctypes.data, counts.ctypes.data, 0)
+            return ProbeMoments(S, counts)
+        import torch
+        dev = traj.tensors()["done"].device
+        if self._y_dev is None or self._y_dev.device != dev:
+            self._y_dev = torch.from_numpy(self._y).to(dev)
+        S = torch.empty((B, DIM, DIM), dtype=torch.float64, device=dev)
+        counts = torch.empty(B, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the engine runs on its own stream
+        _lib.call("rq_trajectory_probe_moments", h, pol, self._y_dev.data_ptr(), N, M, edges, B, S.data_ptr(), counts.data_ptr(), 1)
+        return ProbeMoments(S.cpu().numpy(), counts.cpu().numpy().astype(np.uint64))
+
+    # ---- the host's part: float64 algebra on [B, 32, 32] ----
+    def _blocks(self, moments):
+        K, M = 1 + HIDDEN, self.n_targets
+        S = moments.S
+        if S.shape[0] != self.n_buckets:
+            raise ValueError(f"moments of {S.shape[0]} buckets, the probe has {self.n_buckets}")
+        return S[:, :K, :K], S[:, :K, K:K + M], S[:, K:K + M, K:K + M]
+
+    def fit(self, moments, ridge=1e-6):
+        """-> W [B, 17, M]: per bucket the least-squares read-out y ~ W[0] + h . W[1:], from the normal equations G W = C in
+        float64.  ``ridge`` is relative: ridge x the mean second moment of the hidden features is added to their diagonal, the
+        intercept is not penalised.  A bucket with fewer than 18 samples gives NaN rows."""
+        G, Cm, _ = self._blocks(moments)
+        K = 1 + HIDDEN
+        W = np.full((self.n_buckets, K, self.n_targets), np.nan)
+        for b in range(self.n_buckets):
+            if int(moments.counts[b]) < MIN_SAMPLES:
+                continue
+            A = G[b].copy()
+            lam = float(ridge) * np.trace(A[1:, 1:]) / HIDDEN
+            A[np.arange(1, K), np.arange(1, K)] += lam
+            try:
+                W[b] = np.linalg.solve(A, Cm[b])
+            except np.linalg.LinAlgError:
+                W[b] = np.linalg.lstsq(A, Cm[b], rcond=None)[0]
+        return W
+
+    def r2(self, moments, W):
+        """-> R^2 [B, M] of the read-out ``W`` on the data behind ``moments`` - the recording it was fitted on, or a held-out
+        one - from the moments alone: SSE = sum yy - 2 tr(W^T C) + tr(W^T G W) per target, SST = sum yy - (sum y)^2 / n."""
+        G, Cm, Y = self._blocks(moments)
+        out = np.full((self.n_buckets, self.n_targets), np.nan)
+        for b in range(self.n_buckets):
+            n = float(moments.counts[b])
+            if n < MIN_SAMPLES or not np.isfinite(W[b]).all():
+                continue
+            yy = np.diag(Y[b])
+            sse = yy - 2.0 * np.einsum("km,km->m", W[b], Cm[b]) + np.einsum("km,kl,lm->m", W[b], G[b], W[b])
+            sst = yy - Cm[b][0] ** 2 / n
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out[b] = np.where(sst > 0, 1.0 - sse / sst, np.nan)
+        return out
