@@ -606,6 +606,44 @@ RQ_API int rq_trajectory_probe_moments(rq_trajectory* t, rq_policy* policy,
                                        const uint32_t* age_edges, uint32_t n_buckets,
                                        double* moments, uint64_t* counts, int memory);
 
+/* TIMED MOMENTS: rq_trajectory_probe_moments for targets that change during an episode (the wrench of a scheduled gust, the velocity
+ * of a moving setpoint).  Everything is as above except the targets: targets [length][n_targets][ld_targets] float32, length = the
+ * trajectory's current length, and the sample of a live step t of env i is z = [1, h_t (16), targets[t][0 .. n_targets-1][i], 0 ...].
+ * The age rule, the buckets and the dropped samples, D = 32, 1 <= n_targets <= 15, ld_targets >= n_envs, fp32 products and sums
+ * inside a block of 64 envs and float64 across blocks in ascending block order, the full symmetric matrix and the counts are
+ * unchanged.  A target value takes part in a sum only if its step is live, its age falls in a bucket and its column is below
+ * n_envs; everything else (frozen steps, dropped ages, padding columns - NaN included) is selected away, never multiplied.  Targets
+ * that do not change over time give the bits of rq_trajectory_probe_moments.  memory as above: RQ_DST_HOST copies the targets in
+ * and first checks all length x n_targets x n_envs entries finite (the message names step, target and env); the device modes check
+ * the pointers' device only.
+ * WRENCH TARGETS: the scheduled wrench every env of a recording was flown with, rebuilt on the device from what decides it - a pure
+ * function of the bank, one table id per env (wrench_id, host [n_envs]; NULL: table 0), the params, the episode step count of every
+ * env when the recording began (start_steps, host uint32 [n_envs], what rq_env_get_episode_steps returned right before the rollout
+ * that recorded step 0; NULL: all 0) and the recording's done codes.  out [length][6][ld_out]; per env, k = start_steps[i], and at
+ * step t with done code d:
+ *     d == 4: the six outputs are 0.0f, k stays
+ *     else    row = table[wrench_id[i]][min(k, rows - 1)]
+ *             units_out RQ_WRENCH_RELATIVE: out = row (refused for an RQ_WRENCH_ABSOLUTE bank)
+ *             units_out RQ_WRENCH_ABSOLUTE: out[j] = fs * row[j], out[3 + j] = ts * row[3 + j], fs and ts as in "Wrench schedule"
+ *                                           above from the params of this call (1.0f for an RQ_WRENCH_ABSOLUTE bank), one rounded
+ *                                           fp32 product each
+ *             then k = 0 if d is 1 or 2, else k + 1
+ * This is the scheduled part of the wrench of that transition; the per-episode base (RQ_S_FORCE / RQ_S_TORQUE) is not part of it.
+ * Bank and ids are arguments, not read from the env's attachment: that they are what was flown is the caller's business.  Columns
+ * >= n_envs are not written.  wrench_id and start_steps are host arrays in every mode and are read before return; `memory` speaks
+ * of `out`.  With RQ_DST_DEVICE_ASYNC this call and the moments chain on rq_device_stream() without a host synchronisation.
+ * Refused before anything is enqueued, outputs untouched: a null trajectory, bank, params or out; an empty trajectory; a bank of
+ * another device or params of another env (RQ_ERR_SHAPE_MISMATCH); an unknown units_out; relative output from an absolute bank;
+ * ld_out < n_envs; rows < episode_step_limit; an id >= n_tables and start_steps[i] >= episode_step_limit (both name the env). */
+RQ_API int rq_trajectory_probe_moments_timed(rq_trajectory* t, rq_policy* policy,
+                                             const float* targets, uint32_t ld_targets, uint32_t n_targets,
+                                             const uint32_t* age_edges, uint32_t n_buckets,
+                                             double* moments, uint64_t* counts, int memory);
+RQ_API int rq_trajectory_wrench_targets(rq_trajectory* t, const rq_wrench_bank* bank,
+                                        const uint32_t* wrench_id /* host [n_envs] or NULL = table 0 */, const rq_params* params,
+                                        const uint32_t* start_steps /* host [n_envs] or NULL = 0 */,
+                                        int units_out /* rq_wrench_units */, float* out, uint32_t ld_out, int memory);
+
 /* ---- Teacher bank: the distillation step of the reference (README.md:208-216: ~1000 teacher policies, one per
  * sampled quadrotor, queried on the states the student visited).  The teachers'
  * architecture is not in the reference tree - this is rl-tools' plain MLP family [UPSTREAM-UNVERIFIED]:

@@ -284,6 +284,13 @@ struct rq_trajectory {
         // device-side block: moments | counts | age edges (| the targets of a host-memory call)
         DeviceBuffer<float> probe;
         DeviceBuffer<double> probe_io;
+        // targets per step (rq_trajectory_probe_moments_timed): the device side of a host-memory call's targets [length][M][ld_targets]
+        DeviceBuffer<float> probe_targets;
+        // rq_trajectory_wrench_targets: first rows [n] | start steps [n] on the device, and the pinned rows they were copied from -
+        // a call with the rows of the call before uploads nothing; other rows wait for the stream, then rewrite the pinned block
+        DeviceBuffer<uint32_t> probe_rows;
+        PinnedBuffer<uint32_t> probe_rows_host;
+        bool probe_rows_valid = false;
     } grad;
 };
 

@@ -26,6 +26,19 @@ hipError_t launch_probe_moments(hipStream_t s, uint32_t n, uint32_t ld, uint32_t
                                 const float* y, uint32_t ld_y, uint32_t n_targets, const ProbeEdges& edges, uint32_t n_buckets,
                                 float* partial, double* moments, unsigned long long* counts);
 
+// The same with targets per step, y [steps][n_targets][ld_y] (k_probe_moments_timed, then k_probe_reduce): targets that do not change
+// over time give the bits of launch_probe_moments.
+hipError_t launch_probe_moments_timed(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, const uint8_t* done,
+                                      const float* y, uint32_t ld_y, uint32_t n_targets, const ProbeEdges& edges, uint32_t n_buckets,
+                                      float* partial, double* moments, unsigned long long* counts);
+
+// done [steps][ld], tab [..][6] (a wrench bank's rows), row0 / start [n] (the env's first row in tab, its episode step count at step 0),
+// params [RQ_PARAM_DIM][ld] -> out [steps][6][ld_out] (columns below n are written): the scheduled wrench row of every step, 0.0f on
+// frozen steps; scale: in N / N m through wrench_scales of the params (else the row as it is).
+hipError_t launch_probe_wrench_targets(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const uint8_t* done, const float* tab,
+                                       uint32_t rows, const uint32_t* row0, const uint32_t* start, bool scale, const float* params,
+                                       float gravity, float* out, uint32_t ld_out);
+
 // saved [steps][16][ld] -> out [steps][n][16], the learner layout
 hipError_t launch_probe_hidden_rows(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, float* out);
 

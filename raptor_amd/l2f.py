@@ -713,6 +713,40 @@ class VectorModule:
                 _lib.call("rq_trajectory_get_hidden", self._require("trajectory"), pol, out.data_ptr(), 1)
                 return out
 
+            def wrench_targets(self, bank, ids, params, start_steps=None, units="relative", device=False):
+                """The scheduled wrench every env was flown with at every recorded step, rebuilt on the device
+                (rq_trajectory_wrench_targets): ``bank`` an ``l2f.WrenchBank`` and ``ids`` [N] its table per env (None: table
+                0) - what ``env.set_wrench_schedule`` was given -, ``params`` the VectorParameters flown, ``start_steps`` [N] what
+                ``env.episode_steps()`` returned right before the rollout that recorded step 0 (None: 0).  ``units``: "relative"
+                (the rows themselves) or "absolute" (N and N m).  -> NumPy [T, N, 6] (columns ``probing.WRENCH_NAMES``), zeros on
+                frozen steps; with ``device=True`` a torch tensor [T, 6, ld] on the engine's device, the layout
+                ``HiddenProbe.moments(traj, targets=..., device=True)`` takes.  The per-episode base disturbance is not part of it."""
+                from .disturbances import check_units, check_wrench_ids
+                if not isinstance(bank, WrenchBank):
+                    raise ValueError("bank must be an l2f.WrenchBank")
+                T, N = len(self), mod.N_ENVIRONMENTS
+                u = check_units(units)
+                a = None if ids is None else check_wrench_ids(ids, bank.n_tables, N)
+                k = None
+                if start_steps is not None:
+                    k = np.asarray(start_steps)
+                    if k.shape != (N,) or k.dtype == bool or not np.issubdtype(k.dtype, np.integer) or (k < 0).any():
+                        raise ValueError(f"start_steps must be {N} non-negative integers (env.episode_steps())")
+                    k = np.ascontiguousarray(k.astype(np.uint32))
+                h, p = self._require("trajectory"), params._require("VectorParameters")
+                ia, ka = (None if a is None else a.ctypes.data), (None if k is None else k.ctypes.data)
+                if not device:
+                    out = np.empty((T, 6, N), np.float32)
+                    _lib.call("rq_trajectory_wrench_targets", h, bank._h, ia, p, ka, u, _lib.fptr(out), N, 0)
+                    return np.ascontiguousarray(out.transpose(0, 2, 1))
+                import torch
+                dev = torch.device(f"cuda:{_ordinal_of(self)}")
+                ld = self._env._ld()
+                out = torch.zeros((T, 6, ld), dtype=torch.float32, device=dev)
+                torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
+                _lib.call("rq_trajectory_wrench_targets", h, bank._h, ia, p, ka, u, out.data_ptr(), ld, 1)
+                return out
+
             def relabel_teachers(self, bank, teacher_ids, overwrite=False, fetch=True):
                 """Actions of MLP teacher ``teacher_ids[i]`` of ``bank`` (raptor_amd.teachers.TeacherBank) on every
                 recorded step of env i, in one launch on the matrix cores -> [T, N, 4] (``fetch=False``: only on

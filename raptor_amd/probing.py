@@ -12,6 +12,14 @@ in float64, here: the fit solves the normal equations, and R^2 on ANOTHER record
     W = probe.fit(probe.moments(traj_a))
     r2 = probe.r2(probe.moments(traj_b), W)          # [buckets, targets], held out
 
+Targets that change during an episode - the wrench of a scheduled gust, the velocity of a moving setpoint - go with the recording,
+not with the probe (rq_trajectory_probe_moments_timed): "does the state know what is pushing on the vehicle right now, and how many
+steps after the onset?"
+
+    Y = traj.wrench_targets(bank, ids, params, start_steps, device=True)       # [T, 6, ld] on the device, never on the host
+    probe = probing.HiddenProbe(policy, None, probing.WRENCH_NAMES, edges)
+    m = probe.moments(traj, targets=Y, device=True)
+
 Age follows the forward's episode rule: 0 at the first recorded step; a step is live when its done code is not 4; after a live
 step with code 1 or 2 the age is 0 again, after any other live step one more; frozen steps neither count nor age.
 """
@@ -24,6 +32,7 @@ HIDDEN = _lib.POLICY_HIDDEN_DIM
 DIM = 32                      # z = [1, h (16), y (M <= 15)], zero-padded
 MAX_TARGETS, MAX_BUCKETS = 15, 32
 MIN_SAMPLES = HIDDEN + 2      # a bucket with fewer samples than unknowns + 1 is not fitted
+WRENCH_NAMES = ["fx", "fy", "fz", "tx", "ty", "tz"]          # the columns of ``Trajectory.wrench_targets``
 
 # rq_param_field (include/raptor_quad.h)
 _P_MASS, _P_JXX, _P_JZZ = 0, 1, 3
@@ -86,6 +95,49 @@ def log_age_edges(limit, n):
     return np.asarray(edges, np.uint32)
 
 
+def episode_steps(done, start_steps=None):
+    """The episode step count every env of a recording had at every step: ``done`` [T, N] codes, ``start_steps`` [N] the counts
+    when the recording began (``env.episode_steps()`` right before the rollout; None: 0) -> k [T, N] int64, -1 on a frozen step
+    (code 4).  k stays across a frozen step, is 0 after a step with code 1 or 2 and one more after any other - the row a wrench
+    schedule or a moving setpoint was read at (clamped to the table)."""
+    done = np.asarray(done)
+    if done.ndim != 2:
+        raise ValueError("done must be [T, N]")
+    T, N = done.shape
+    k = np.zeros(N, np.int64) if start_steps is None else np.asarray(start_steps).astype(np.int64).copy()
+    if k.shape != (N,):
+        raise ValueError(f"start_steps must be [{N}]")
+    out = np.full((T, N), -1, np.int64)
+    for t in range(T):
+        live = done[t] != 4
+        out[t, live] = k[live]
+        k = np.where((done[t] == 1) | (done[t] == 2), 0, np.where(live, k + 1, k))
+    return out
+
+
+def table_targets(table, k, ids=None):
+    """Per-step targets gathered from any row table along ``k`` (``episode_steps``): ``table`` [rows, C], or [M, rows, C] with
+    ``ids`` [N] naming every env's table -> float32 [T, N, C], row min(k, rows - 1), zeros where k is -1 (frozen).  A reference's
+    velocity columns, for instance, ask "does the state know where the path goes?"."""
+    tab = np.asarray(table, np.float32)
+    k = np.asarray(k, np.int64)
+    if k.ndim != 2:
+        raise ValueError("k must be [T, N]")
+    if tab.ndim == 2:
+        if ids is not None:
+            raise ValueError("ids belong to a bank of tables [M, rows, C]")
+        tab, ids = tab[None], np.zeros(k.shape[1], np.int64)
+    elif tab.ndim == 3:
+        ids = np.zeros(k.shape[1], np.int64) if ids is None else np.asarray(ids).astype(np.int64)
+        if ids.shape != (k.shape[1],) or (ids < 0).any() or (ids >= tab.shape[0]).any():
+            raise ValueError(f"ids must be [{k.shape[1]}] table numbers below {tab.shape[0]}")
+    else:
+        raise ValueError("table must be [rows, C] or [M, rows, C]")
+    out = tab[ids[None, :], np.clip(k, 0, tab.shape[1] - 1)]
+    out[k < 0] = 0.0
+    return out
+
+
 class ProbeMoments:
     """Per age bucket the sums of z z^T, ``S`` [B, 32, 32] float64, and the samples, ``counts`` [B].  Moments of several
     recordings (or of several devices' shares of one) add with ``+``."""
@@ -107,30 +159,83 @@ class ProbeMoments:
 
 class HiddenProbe:
     """``targets`` [N, M] float32 (finite; one row per env, constant over time), ``names`` [M], ``age_edges`` [B + 1] strictly
-    ascending (``log_age_edges``).  ``policy``: the fp32 policy without Standardize / SampleAndSquash stages, at the native rate."""
+    ascending (``log_age_edges``).  ``policy``: the fp32 policy without Standardize / SampleAndSquash stages, at the native rate.
+    ``targets=None``: the probe fixes only M = ``len(names)`` and every ``moments`` call brings the targets of its recording, one
+    value per step (``moments(traj, targets=Y)``)."""
 
-    def __init__(self, policy, targets, names, age_edges):
-        y = np.asarray(targets, np.float32)
-        if y.ndim != 2 or not 1 <= y.shape[1] <= MAX_TARGETS:
-            raise ValueError(f"targets must be [N, 1 .. {MAX_TARGETS}]")
-        if len(names) != y.shape[1]:
-            raise ValueError("one name per target")
-        if not np.isfinite(y).all():
-            raise ValueError("targets must be finite")
+    def __init__(self, policy, targets=None, names=(), age_edges=(0, 1)):
+        if targets is None:
+            if not 1 <= len(names) <= MAX_TARGETS:
+                raise ValueError(f"1 .. {MAX_TARGETS} names, not {len(names)}")
+            y = None
+        else:
+            y = np.asarray(targets, np.float32)
+            if y.ndim != 2 or not 1 <= y.shape[1] <= MAX_TARGETS:
+                raise ValueError(f"targets must be [N, 1 .. {MAX_TARGETS}]")
+            if len(names) != y.shape[1]:
+                raise ValueError("one name per target")
+            if not np.isfinite(y).all():
+                raise ValueError("targets must be finite")
         e = np.asarray(age_edges, np.int64)
         if e.ndim != 1 or not 2 <= e.size <= MAX_BUCKETS + 1 or (np.diff(e) <= 0).any() or e[0] < 0 or e[-1] >= 1 << 32:
             raise ValueError(f"age_edges must be 2 .. {MAX_BUCKETS + 1} strictly ascending uint32 values")
         self.policy, self.names = policy, list(names)
         self.age_edges = e.astype(np.uint32)
-        self.n_targets, self.n_buckets = y.shape[1], e.size - 1
-        self._y = np.ascontiguousarray(y.T)           # [M, N]: what the engine reads
+        self.n_targets, self.n_buckets = len(self.names), e.size - 1
+        self._y = None if y is None else np.ascontiguousarray(y.T)           # [M, N]: what the engine reads
         self._y_dev = None
 
     # ---- the device's part ----
-    def moments(self, traj, device=False):
+    def _moments_timed(self, traj, targets, device):
+        """``moments(traj, targets=Y)``: everything wrong with Y raises ValueError before any library call"""
+        B, M = self.n_buckets, self.n_targets
+        T, N = len(traj), int(traj._env.N_ENVIRONMENTS)
+        edges = self.age_edges.ctypes.data
+        if not device:
+            y = np.asarray(targets)
+            if y.dtype != np.float32:
+                raise ValueError(f"targets must be float32, not {y.dtype}")
+            if y.shape != (T, N, M):
+                raise ValueError(f"targets must be [T, N, M] = [{T}, {N}, {M}], not {list(y.shape)}")
+            if not np.isfinite(y).all():
+                raise ValueError("targets must be finite")
+            y = np.ascontiguousarray(y.transpose(0, 2, 1))          # the engine's [T, M, N], once
+            pol = self.policy._handle(traj._env._device)
+            h = traj._require("trajectory")
+            traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
+            S, counts = np.empty((B, DIM, DIM), np.float64), np.empty(B, np.uint64)
+            _lib.call("rq_trajectory_probe_moments_timed", h, pol, _lib.fptr(y), N, M, edges, B, S.ctypes.data, counts.ctypes.data, 0)
+            return ProbeMoments(S, counts)
+        import torch
+        if not isinstance(targets, torch.Tensor):
+            raise ValueError("device=True takes a torch tensor [T, M, ld >= N] on the trajectory's device")
+        dev = traj.tensors()["done"].device
+        if targets.dtype != torch.float32:
+            raise ValueError(f"targets must be float32, not {targets.dtype}")
+        if targets.dim() != 3 or tuple(targets.shape[:2]) != (T, M) or targets.shape[2] < N:
+            raise ValueError(f"targets must be [T, M, ld >= N] = [{T}, {M}, >= {N}], not {list(targets.shape)}")
+        if targets.device != dev or not targets.is_contiguous():
+            raise ValueError(f"targets must be a contiguous tensor on {dev}")
+        pol = self.policy._handle(traj._env._device)
+        h = traj._require("trajectory")
+        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
+        S = torch.empty((B, DIM, DIM), dtype=torch.float64, device=dev)
+        counts = torch.empty(B, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the engine runs on its own stream
+        _lib.call("rq_trajectory_probe_moments_timed", h, pol, targets.data_ptr(), int(targets.shape[2]), M, edges, B, S.data_ptr(),
+                  counts.data_ptr(), 1)
+        return ProbeMoments(S.cpu().numpy(), counts.cpu().numpy().astype(np.uint64))
+
+    def moments(self, traj, targets=None, device=False):
         """The moments of ``traj`` under this probe's policy -> ProbeMoments (host, float64).  ``device=True`` (torch): targets,
         moments and counts stay in device memory for the call - the targets are uploaded once per probe - and only the
-        B x 8 KB result crosses."""
+        B x 8 KB result crosses.
+        ``targets=Y``: the targets of THIS recording, one value per step - NumPy float32 [T, N, M], finite, or with ``device=True`` a
+        torch tensor [T, M, ld >= N] on the trajectory's device (what ``traj.wrench_targets(..., device=True)`` returns)."""
+        if targets is not None:
+            return self._moments_timed(traj, targets, device)
+        if self._y is None:
+            raise ValueError("this probe holds no targets: pass the recording's, moments(traj, targets=Y)")
         N = self._y.shape[1]
         pol = self.policy._handle(traj._env._device)
         h = traj._require("trajectory")

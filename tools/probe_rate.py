@@ -11,6 +11,13 @@ ways alternate for --rounds rounds after one warm-up each; medians are reported,
 records what was measured, and how far the two results are apart.
 
     python tools/probe_rate.py [--envs 65536] [--steps 500] [--buckets 10] [--targets 7] [--rounds 5] [--json profiles/probe_rate.json]
+
+--timed: targets per step instead (rq_trajectory_probe_moments_timed, M = 6: the scheduled wrench of a recording flown under
+raptor_amd.disturbances.suite, generated on the device by rq_trajectory_wrench_targets).  Timed, alternating, --rounds rounds
+(7 by default here) after one warm-up each, medians reported, every round kept:
+(a) the timed moments, (b) the untimed kernel at the same M on the same recording (per-env targets: the wrench of one step),
+(c) the generation of the target tensor on its own, (d) the same moments in torch from the hidden tensor and the target tensor.
+The forward is excluded as above.  With --json the figures go under the key "timed" of that file; what else it holds is kept.
 """
 import argparse
 import ctypes as C
@@ -33,9 +40,14 @@ ap.add_argument("--envs", type=int, default=65536)
 ap.add_argument("--steps", type=int, default=500)
 ap.add_argument("--buckets", type=int, default=10)
 ap.add_argument("--targets", type=int, default=7)
-ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--rounds", type=int, default=None)
 ap.add_argument("--json", default=None)
+ap.add_argument("--timed", action="store_true")
 args = ap.parse_args()
+if args.rounds is None:
+    args.rounds = 7 if args.timed else 5
+if args.timed:
+    args.targets = 6
 N, T, B, M = args.envs, args.steps, args.buckets, args.targets
 
 device = l2f.Device()
@@ -55,11 +67,23 @@ def measure(fn):
 
 
 sh = Shard(device, N, 0)
+if args.timed:                                                         # the recording is flown under a wrench schedule
+    from raptor_amd import disturbances
+    cfg = sh.env.config
+    bank = l2f.WrenchBank(device, list(disturbances.suite(int(cfg.episode_step_limit), float(cfg.dt)).values()))
+    ids = (np.arange(N) % bank.n_tables).astype(np.uint32)
+    sh.env.set_wrench_schedule(bank, ids)
+    start = sh.env.episode_steps()
 traj = sh.vector.Trajectory(sh.env, T)
 sh.vector.rollout(device, sh.env, sh.params, sh.state, sh.policy, sh.rng, T, "fused", autoreset=True, trajectory=traj)
-names = ["log_mass", "thrust_to_weight", "log_jxx", "log_jzz", "tau_rise", "torque_const", "hover_action"][:M]
-y, names = probing.targets_from_params(sh.params.numpy(), sh.env.config, names)
-y, _, _ = probing.standardise(y)
+if args.timed:
+    names = list(probing.WRENCH_NAMES)
+    Y_dev = traj.wrench_targets(bank, ids, sh.params, start, units="relative", device=True)       # [T, 6, ld]
+    y = np.ascontiguousarray(Y_dev[T // 3, :, :N].cpu().numpy().T)     # [N, 6]: the untimed kernel's targets, one step's wrench
+else:
+    names = ["log_mass", "thrust_to_weight", "log_jxx", "log_jzz", "tau_rise", "torque_const", "hover_action"][:M]
+    y, names = probing.targets_from_params(sh.params.numpy(), sh.env.config, names)
+    y, _, _ = probing.standardise(y)
 edges = probing.log_age_edges(min(T, int(sh.env.config.episode_step_limit)), B)
 dev = traj.tensors()["done"].device
 y_dev = torch.from_numpy(np.ascontiguousarray(y.T)).to(dev)            # [M, N]
@@ -74,8 +98,8 @@ def kernel_path():
               C.c_void_p(S_dev.data_ptr()), C.c_void_p(counts_dev.data_ptr()), 1)
 
 
-def torch_path(hidden, done, dtype=torch.float32):
-    """hidden [T, N, 16], done [T, ld] uint8 -> (S [B, K, K] in `dtype` with K = 17 + M, counts [B])"""
+def torch_path(hidden, done, dtype=torch.float32, targets=None):
+    """hidden [T, N, 16], done [T, ld] uint8 -> (S [B, K, K] in `dtype` with K = 17 + M, counts [B]); targets [T, M, ld]: per step"""
     d = done[:, :N]
     live = d != 4
     ended = live & ((d == 1) | (d == 2))
@@ -84,7 +108,8 @@ def torch_path(hidden, done, dtype=torch.float32):
     age = (seen - live.long()) - torch.cat([torch.zeros_like(base[:1]), base[:-1]])
     bucket = torch.bucketize(age, edges_dev, right=True) - 1
     bucket = torch.where(live & (age >= edges_dev[0]) & (age < edges_dev[-1]), bucket, torch.full_like(bucket, -1))
-    z = torch.cat([torch.ones((T, N, 1), device=dev), hidden, y_dev.t().expand(T, N, len(names))], dim=2).reshape(T * N, -1).to(dtype)
+    yz = y_dev.t().expand(T, N, len(names)) if targets is None else targets[:, :, :N].permute(0, 2, 1)
+    z = torch.cat([torch.ones((T, N, 1), device=dev), hidden, yz], dim=2).reshape(T * N, -1).to(dtype)
     zero = torch.zeros((), device=dev, dtype=dtype)
     S, counts = [], []
     for b in range(B):
@@ -94,6 +119,73 @@ def torch_path(hidden, done, dtype=torch.float32):
         counts.append(m.sum())
     return torch.stack(S), torch.stack(counts)
 
+
+def timed_path():
+    _lib.call("rq_trajectory_probe_moments_timed", h_traj, pol, C.c_void_p(Y_dev.data_ptr()), int(Y_dev.shape[2]), 6,
+              edges.ctypes.data, B, C.c_void_p(S_dev.data_ptr()), C.c_void_p(counts_dev.data_ptr()), 1)
+
+
+def generate_path():
+    _lib.call("rq_trajectory_wrench_targets", h_traj, bank._h, ids.ctypes.data, sh.params._require("VectorParameters"),
+              start.ctypes.data, 0, C.c_void_p(Y_gen.data_ptr()), int(Y_gen.shape[2]), 1)
+
+
+def run_timed():
+    kernel_path()                                                      # runs the forward and tags its state; allocations
+    timed_path()
+    generate_path()
+    fetch_ms, hidden = measure(lambda: traj.hidden(sh.policy, device=True))
+    done = traj.tensors()["done"]
+    torch_path(hidden, done, targets=Y_dev)                            # warm-up: code objects, the allocator's blocks
+    rows = []
+    for r in range(args.rounds):
+        a, _ = measure(timed_path)
+        S_k, c_k = S_dev.cpu().numpy(), counts_dev.cpu().numpy()
+        u, _ = measure(kernel_path)
+        g, _ = measure(generate_path)
+        b, (S_t, c_t) = measure(lambda: torch_path(hidden, done, targets=Y_dev))
+        rows.append(dict(round=r, timed_moments_ms=a, untimed_moments_ms=u, wrench_targets_ms=g, torch_ms=b))
+        print(f"round {r}: timed moments {a:.2f} ms; untimed at M = 6 {u:.2f} ms; wrench targets {g:.2f} ms; torch {b:.2f} ms", flush=True)
+    S_t32 = S_t.double().cpu().numpy()
+    del S_t
+    S_64 = torch_path(hidden, done, torch.float64, targets=Y_dev)[0].cpu().numpy()       # untimed: what both are measured against
+    scale = np.sqrt(np.einsum("bii,bjj->bij", S_64, S_64))
+    scale = np.where(scale > 0, scale, 1.0)
+    med = {k: float(np.median([x[k] for x in rows])) for k in ("timed_moments_ms", "untimed_moments_ms", "wrench_targets_ms", "torch_ms")}
+    ld = int(done.shape[1])
+    read_bytes = int(T) * (16 + 6) * ld * 4
+    K = 17 + 6
+    res = dict(gpu=torch.cuda.get_device_name(0), library_sha256=library_sha256(LIB),
+               clock="host time.perf_counter between device synchronisations (torch.cuda.synchronize and the engine's stream)",
+               envs=N, steps=T, buckets=B, targets=names, age_edges=[int(e) for e in edges], rounds=rows,
+               timed_moments_ms_median=med["timed_moments_ms"], untimed_moments_ms_median=med["untimed_moments_ms"],
+               wrench_targets_ms_median=med["wrench_targets_ms"], torch_ms_median=med["torch_ms"],
+               ratio_timed_over_untimed=med["timed_moments_ms"] / med["untimed_moments_ms"],
+               ratio_expected_from_traffic=(64 + 4 * 6) / 64,
+               ratio_torch_over_timed=med["torch_ms"] / med["timed_moments_ms"],
+               hidden_fetch_ms=fetch_ms, state_and_target_bytes=read_bytes,
+               state_and_target_read_GBps_at_median=read_bytes / (med["timed_moments_ms"] * 1e-3) / 1e9,
+               target_bytes_written=int(T) * 6 * ld * 4,
+               target_write_GBps_at_median=int(T) * 6 * ld * 4 / (med["wrench_targets_ms"] * 1e-3) / 1e9,
+               generated_equals_timed_input=bool(torch.equal(Y_gen, Y_dev)),
+               counts_equal=bool(np.array_equal(c_k, c_t.cpu().numpy())),
+               error_measure="max over buckets and elements of |S - S64| / sqrt(S64_ii S64_jj), S64 = the same torch code in float64",
+               timed_moments_error=float((np.abs(S_k[:, :K, :K] - S_64) / scale).max()),
+               torch_fp32_error=float((np.abs(S_t32 - S_64) / scale).max()),
+               excluded="the forward that saves the state (run once, before the timed rounds); the torch path also excludes the "
+                        "fetch of the [T, N, 16] hidden tensor (hidden_fetch_ms) and the generation of the targets")
+    print(json.dumps(res))
+    if args.json:
+        old = json.load(open(args.json)) if os.path.exists(args.json) else {}
+        old["timed"] = res
+        with open(args.json, "w") as f:
+            json.dump(old, f, indent=1)
+
+
+if args.timed:
+    Y_gen = torch.zeros_like(Y_dev)
+    run_timed()
+    sys.exit(0)
 
 kernel_path()                                                          # runs the forward and tags its state; allocations
 fetch_ms, hidden = measure(lambda: traj.hidden(sh.policy, device=True))
