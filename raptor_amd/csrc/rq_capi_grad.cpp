@@ -3,7 +3,8 @@
 // through time along the recorded episode structure (rq_trajectory_policy_backward); and the whole distillation update on the device:
 // masked-MSE loss and gradient (rq_trajectory_policy_loss_grad), Adam and the operand images (rq_trajectory_distill); and that update
 // for every policy of a policy bank at once (rq_trajectory_policies_loss_grad, rq_bank_optimizer_*, rq_trajectory_policies_distill).
-// Kernels: rq_grad.hpp, rq_grad_bank.hpp.
+// Every call with a `memory` argument reads refusals, DeviceScope, prepare, in, launch, out, finish: the staging copies and the final
+// wait are one rq::CallMemory (rq_call_memory.hpp), the staging buffers are reserved here.  Kernels: rq_grad.hpp, rq_grad_bank.hpp.
 #include "rq_objects.hpp"
 
 using namespace rqh;
@@ -25,30 +26,31 @@ int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what) {
 }
 
 int grad_saved_initial(rq_trajectory* t, rq_policy* pol) {
-    rq_env* env = t->env;
-    rq_device* dev = env->dev;
-    if (t->grad.valid && t->grad.policy == pol && t->grad.weight_version == pol->weight_version && t->grad.length == t->length &&
-        t->grad.start == RQ_GRAD_START_INITIAL)
+    rq_env* env = t->env; rq_device* dev = env->dev;
+    if (t->grad.matches(pol, t->length) && t->grad.weight_version == pol->weight_version && t->grad.start == RQ_GRAD_START_INITIAL)
         return RQ_OK;
     t->grad.valid = false;
     RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)t->length * RQ_POLICY_HIDDEN_DIM * env->ld));
     RQ_HIP(rq::launch_policy_grad_forward_state(dev->stream, env->n, env->ld, t->length, pol->w_packed, t->obs, t->done, nullptr, pol->ld,
                                                 1, t->grad.saved));
-    t->grad.valid = true; t->grad.policy = pol; t->grad.weight_version = pol->weight_version; t->grad.length = t->length;
-    t->grad.start = RQ_GRAD_START_INITIAL;
+    t->grad.stamp(pol, t->length, RQ_GRAD_START_INITIAL);
+    return RQ_OK;
+}
+
+int check_memory(int memory) {
+    RQ_REQUIRE(CallMemory::valid(memory), RQ_ERR_INVALID_ARGUMENT, "memory must be 0, 1 or 2");
+    return RQ_OK;
+}
+
+int check_device_array(const CallMemory& mem, const void* p, const char* what, const char* noun) {
+    RQ_REQUIRE(mem.host() || mem.on_device(p), RQ_ERR_SHAPE_MISMATCH,
+               std::string(what) + ": " + noun + " lives on another device (or on the host): device memory of the trajectory's device is expected");
     return RQ_OK;
 }
 
 }  // namespace rqh
 
 namespace {
-
-int check_pair(rq_trajectory* t, rq_policy* pol, const char* what) { return grad_check_pair(t, pol, what); }
-
-int check_memory(int memory) {
-    RQ_REQUIRE(memory >= RQ_DST_HOST && memory <= RQ_DST_DEVICE_ASYNC, RQ_ERR_INVALID_ARGUMENT, "memory must be 0, 1 or 2");
-    return RQ_OK;
-}
 
 // the transposed image of the backward, packed once per weight version (a device-side update writes it itself)
 int ensure_grad_image(rq_policy* pol) {
@@ -75,29 +77,22 @@ int loss_check_call(rq_trajectory* t, const float* target, uint32_t ld_target, i
     int rc = check_memory(memory); if (rc) return rc;
     RQ_REQUIRE(start == RQ_GRAD_START_CURRENT || start == RQ_GRAD_START_INITIAL, RQ_ERR_INVALID_ARGUMENT,
                "start must be RQ_GRAD_START_CURRENT or RQ_GRAD_START_INITIAL");
-    rq_env* env = t->env;
-    rq_device* dev = env->dev;
+    const rq_device* dev = t->env->dev;
     if (target) {
-        RQ_REQUIRE(ld_target >= env->n, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": ld_target must be at least the number of envs");
-        if (memory != RQ_DST_HOST) {
-            hipPointerAttribute_t at{};
-            const hipError_t e = hipPointerGetAttributes(&at, target);
-            if (e != hipSuccess) (void)hipGetLastError();
-            RQ_REQUIRE(e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == dev->ordinal, RQ_ERR_SHAPE_MISMATCH,
-                       std::string(what) + ": the target lives on another device (or on the host): device memory of the trajectory's device is expected");
-        }
+        RQ_REQUIRE(ld_target >= t->env->n, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": ld_target must be at least the number of envs");
+        return check_device_array(CallMemory(memory, dev->stream, dev->ordinal), target, what, "the target");
     }
     return RQ_OK;
 }
 
 int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, const char* what) {
-    int rc = check_pair(t, pol, what); if (rc) return rc;
+    int rc = grad_check_pair(t, pol, what); if (rc) return rc;
     return loss_check_call(t, target, ld_target, start, memory, what);
 }
 
 // the workspace and the target on the device; out_floats: what t->grad.out is to hold (gradients, then losses)
-int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, int memory, size_t out_floats, const float** d_target,
-                   uint32_t* ld_y) {
+int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, const CallMemory& mem, size_t out_floats,
+                   const float** d_target, uint32_t* ld_y) {
     rq_env* env = t->env;
     rq_device* dev = env->dev;
     const uint32_t T = t->length, ld = env->ld;
@@ -106,23 +101,22 @@ int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, in
     RQ_HIP(t->grad.partial.reserve(dev->stream, rq::policy_loss_partial_floats(env->n)));
     RQ_HIP(t->grad.out.reserve(dev->stream, out_floats));
     RQ_HIP(t->grad.live.reserve(dev->stream, 1));
-    *d_target = target ? target : t->act.get();          // the stored actions: what a relabel or a teacher-acting rollout left
+    *d_target = t->act.get();          // the stored actions: what a relabel or a teacher-acting rollout left
     *ld_y = target ? ld_target : ld;
-    if (target && memory == RQ_DST_HOST) {
+    if (target) {
         const size_t floats = (size_t)T * RQ_ACTION_DIM * ld_target;
-        RQ_HIP(t->grad.rows.reserve(dev->stream, floats));
-        RQ_HIP(hipMemcpyAsync(t->grad.rows, target, floats * sizeof(float), hipMemcpyHostToDevice, dev->stream));
-        *d_target = t->grad.rows;
+        if (mem.host()) RQ_HIP(t->grad.rows.reserve(dev->stream, floats));
+        RQ_HIP(mem.in(target, floats, t->grad.rows.get(), d_target));
     }
     return RQ_OK;
 }
 
-int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, size_t n_losses,
-               const float** d_target, uint32_t* ld_y) {
+int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, const CallMemory& mem,
+               size_t n_losses, const float** d_target, uint32_t* ld_y) {
     int rc = RQ_OK;
     if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, t->env->n); if (rc) return rc; }
     rc = ensure_grad_image(pol); if (rc) return rc;
-    return loss_workspace(t, target, ld_target, memory, RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y);
+    return loss_workspace(t, target, ld_target, mem, RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y);
 }
 
 hipError_t enqueue_loss_grad(rq_trajectory* t, rq_policy* pol, int start, const float* d_target, uint32_t ld_y, float* d_grad,
@@ -153,7 +147,7 @@ int bank_loss_check(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* poli
 }
 
 int bank_loss_begin(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target, uint32_t ld_target,
-                    int start, int memory, size_t n_losses, const float** d_target, uint32_t* ld_y) {
+                    int start, const CallMemory& mem, size_t n_losses, const float** d_target, uint32_t* ld_y) {
     rq_env* env = t->env;
     int rc = RQ_OK;
     if (start == RQ_GRAD_START_CURRENT) {
@@ -164,7 +158,7 @@ int bank_loss_begin(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* poli
     rc = bank_wave_lists(bank); if (rc) return rc;
     rc = bank_grad_images(bank); if (rc) return rc;
     if (start == RQ_GRAD_START_CURRENT) { rc = bank_apply_reset(bank); if (rc) return rc; }
-    return loss_workspace(t, target, ld_target, memory, (size_t)bank->n_policies * RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y);
+    return loss_workspace(t, target, ld_target, mem, (size_t)bank->n_policies * RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y);
 }
 
 hipError_t enqueue_bank_loss_grad(rq_trajectory* t, rq_policy_bank* bank, int start, const float* d_target, uint32_t ld_y, float* d_grad,
@@ -181,13 +175,57 @@ bool adam_config_ok(const rq_adam_config& c) {
     return c.lr >= 0.0 && c.eps >= 0.0 && c.weight_decay >= 0.0 && c.beta1 >= 0.0 && c.beta1 < 1.0 && c.beta2 >= 0.0 && c.beta2 < 1.0;
 }
 
+// Adam's state for `slots` policies, inside the caller's DeviceScope: moments zeroed, slot p's hyper-parameters from config[n_cfg == 1
+// ? 0 : p], the repack's gather table.  zero_grad: the bank's gradient rows start at zero.  `who` begins the message of a failure.
+int adam_alloc(const char* who, AdamBuffers* o, rq_device* dev, const rq_adam_config* config, uint32_t n_cfg, uint32_t slots,
+               bool zero_grad) {
+    o->dev = dev; o->ordinal = dev->ordinal;
+    const size_t entries = (size_t)rq::RQ_PACKED_FLOATS + rq::RQ_PACKED_GRAD_FLOATS, floats = (size_t)slots * RQ_POLICY_NUM_WEIGHTS;
+    std::vector<rq::PackGather> table;
+    std::vector<rq::AdamState> st;
+    try {
+        table.resize(entries); rq::pack_gather_table(table.data());
+        st.resize(slots);
+    } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed");
+    }
+    for (uint32_t p = 0; p < slots; ++p) {
+        const rq_adam_config& c = config[n_cfg == 1 ? 0 : p];
+        st[p] = rq::AdamState{c.lr, c.beta1, c.beta2, c.eps, c.weight_decay, 1.0, 1.0, 0u, 0u};
+    }
+    hipError_t e = o->m.alloc(floats);
+    if (e == hipSuccess) e = o->v.alloc(floats);
+    if (e == hipSuccess) e = o->grad.alloc(floats);
+    if (e == hipSuccess) e = o->state.alloc(slots);
+    if (e == hipSuccess) e = o->table.alloc(entries);
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e == hipSuccess) e = hipMemset(o->m, 0, floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(o->v, 0, floats * sizeof(float));
+    if (e == hipSuccess && zero_grad) e = hipMemset(o->grad, 0, floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(o->state, st.data(), (size_t)slots * sizeof(rq::AdamState), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->table, table.data(), entries * sizeof(rq::PackGather), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return RQ_OK;
+}
+
+template <typename Optimizer>
+int adam_destroy(Optimizer* opt) {
+    if (!opt) return RQ_OK;
+    DeviceScope on_device(opt->ordinal);
+    if (device_registry(opt->dev, 0)) (void)hipStreamSynchronize(opt->dev->stream);      // an update may still be queued
+    delete opt;
+    return RQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* pol, int start, float* action, uint32_t ld_action,
                                         int memory) {
-    int rc = check_pair(t, pol, "rq_trajectory_policy_forward"); if (rc) return rc;
+    int rc = grad_check_pair(t, pol, "rq_trajectory_policy_forward"); if (rc) return rc;
     rc = check_memory(memory); if (rc) return rc;
     RQ_REQUIRE(action, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(start == RQ_GRAD_START_CURRENT || start == RQ_GRAD_START_INITIAL, RQ_ERR_INVALID_ARGUMENT,
@@ -197,36 +235,28 @@ RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* pol, int st
     RQ_REQUIRE(ld_action >= env->n, RQ_ERR_INVALID_ARGUMENT, "ld_action must be at least the number of envs");
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const uint32_t T = t->length, ld = env->ld;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
     if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, env->n); if (rc) return rc; }
     rc = ensure_grad_image(pol); if (rc) return rc;
     t->grad.valid = false;
     RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld));
-    float* d_act = action;
-    if (memory == RQ_DST_HOST) {
-        RQ_HIP(t->grad.rows.reserve(dev->stream, (size_t)T * RQ_ACTION_DIM * ld_action));
-        d_act = t->grad.rows;
-    }
+    if (mem.host()) RQ_HIP(t->grad.rows.reserve(dev->stream, (size_t)T * RQ_ACTION_DIM * ld_action));
+    // the envs' columns only go back: the caller's columns n .. ld_action-1 stay as they were
+    float* d_act = mem.out(action, ld_action, t->grad.rows.get(), ld_action, env->n, (size_t)T * RQ_ACTION_DIM);
     RQ_HIP(rq::launch_policy_grad_forward(dev->stream, env->n, ld, T, pol->w_packed, t->obs, t->done,
                                           start == RQ_GRAD_START_CURRENT ? pol->hidden : nullptr, pol->ld,
                                           start == RQ_GRAD_START_INITIAL, d_act, ld_action, t->grad.saved));
-    t->grad.valid = true;
-    t->grad.policy = pol;
-    t->grad.weight_version = pol->weight_version;
-    t->grad.length = T;
-    t->grad.start = start;
-    if (memory == RQ_DST_HOST)            // the envs' columns only: the caller's columns n .. ld_action-1 stay as they were
-        RQ_HIP(hipMemcpy2DAsync(action, (size_t)ld_action * sizeof(float), d_act, (size_t)ld_action * sizeof(float),
-                                (size_t)env->n * sizeof(float), (size_t)T * RQ_ACTION_DIM, hipMemcpyDeviceToHost, dev->stream));
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    t->grad.stamp(pol, T, start);
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 
 RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* pol, const float* grad_action, uint32_t ld_grad,
                                          float* grad_weights, float* grad_hidden_start, int memory) {
-    int rc = check_pair(t, pol, "rq_trajectory_policy_backward"); if (rc) return rc;
+    int rc = grad_check_pair(t, pol, "rq_trajectory_policy_backward"); if (rc) return rc;
     rc = check_memory(memory); if (rc) return rc;
     RQ_REQUIRE(grad_action && grad_weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    RQ_REQUIRE(t->grad.valid && t->grad.policy == pol && t->grad.length == t->length, RQ_ERR_INVALID_ARGUMENT,
+    RQ_REQUIRE(t->grad.matches(pol, t->length), RQ_ERR_INVALID_ARGUMENT,
                "rq_trajectory_policy_backward: no matching forward (rq_trajectory_policy_forward with this policy on this "
                "recording first)");
     RQ_REQUIRE(t->grad.weight_version == pol->weight_version, RQ_ERR_INVALID_ARGUMENT,
@@ -238,30 +268,22 @@ RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* pol, const
     RQ_REQUIRE(ld_grad >= env->n, RQ_ERR_INVALID_ARGUMENT, "ld_grad must be at least the number of envs");
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const uint32_t T = t->length, ld = env->ld, waves = (env->n + 63) / 64;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
     RQ_HIP(t->grad.partial.reserve(dev->stream, (size_t)waves * RQ_POLICY_NUM_WEIGHTS));
-    const float* d_ga = grad_action;
-    float* d_gw = grad_weights;
-    float* d_gh = grad_hidden_start;
-    const size_t ga_bytes = (size_t)T * RQ_ACTION_DIM * ld_grad * sizeof(float);
-    const size_t gh_bytes = (size_t)RQ_POLICY_HIDDEN_DIM * ld * sizeof(float);
-    const size_t gw_bytes = (size_t)RQ_POLICY_NUM_WEIGHTS * sizeof(float);
-    if (memory == RQ_DST_HOST) {          // one device block: dL/da | dL/dtheta | dL/dh_start
-        const size_t off_gw = (ga_bytes + 255) & ~(size_t)255, off_gh = off_gw + ((gw_bytes + 255) & ~(size_t)255);
-        RQ_HIP(t->grad.rows.reserve(dev->stream, (off_gh + gh_bytes) / sizeof(float)));
-        char* base = reinterpret_cast<char*>(t->grad.rows.get());
-        RQ_HIP(hipMemcpyAsync(base, grad_action, ga_bytes, hipMemcpyHostToDevice, dev->stream));
-        d_ga = reinterpret_cast<const float*>(base);
-        d_gw = reinterpret_cast<float*>(base + off_gw);
-        d_gh = grad_hidden_start ? reinterpret_cast<float*>(base + off_gh) : nullptr;
+    const size_t ga_floats = (size_t)T * RQ_ACTION_DIM * ld_grad, gh_floats = (size_t)RQ_POLICY_HIDDEN_DIM * ld;
+    float *s_ga = nullptr, *s_gw = nullptr, *s_gh = nullptr;
+    if (mem.host()) {          // one device block: dL/da | dL/dtheta | dL/dh_start, each begun at a multiple of 256 bytes
+        const size_t off_gw = (ga_floats + 63) & ~(size_t)63, off_gh = off_gw + ((RQ_POLICY_NUM_WEIGHTS + 63) & ~(size_t)63);
+        RQ_HIP(t->grad.rows.reserve(dev->stream, off_gh + gh_floats));
+        s_ga = t->grad.rows; s_gw = s_ga + off_gw; s_gh = s_ga + off_gh;
     }
+    const float* d_ga = nullptr; RQ_HIP(mem.in(grad_action, ga_floats, s_ga, &d_ga));
+    float* d_gw = mem.out(grad_weights, RQ_POLICY_NUM_WEIGHTS, s_gw);
+    float* d_gh = grad_hidden_start ? mem.out(grad_hidden_start, gh_floats, s_gh) : nullptr;
     RQ_HIP(rq::launch_policy_grad_backward(dev->stream, env->n, ld, T, pol->w_packed, pol->w_packed_grad, t->obs, t->done,
                                            t->grad.saved, d_ga, ld_grad, t->grad.start == RQ_GRAD_START_INITIAL, d_gh,
                                            t->grad.partial, d_gw));
-    if (memory == RQ_DST_HOST) {
-        RQ_HIP(hipMemcpyAsync(grad_weights, d_gw, gw_bytes, hipMemcpyDeviceToHost, dev->stream));
-        if (grad_hidden_start) RQ_HIP(hipMemcpyAsync(grad_hidden_start, d_gh, gh_bytes, hipMemcpyDeviceToHost, dev->stream));
-    }
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 
@@ -270,20 +292,16 @@ RQ_API int rq_trajectory_policy_loss_grad(rq_trajectory* t, rq_policy* pol, cons
                                           float* loss, float* grad_weights, int memory) {
     RQ_REQUIRE(t && pol && loss && grad_weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
     int rc = loss_check(t, pol, target, ld_target, start, memory, "rq_trajectory_policy_loss_grad"); if (rc) return rc;
-    DeviceScope on_device(t->env->dev); rc = on_device.rc; if (rc) return rc;
-    const float* d_target = nullptr; uint32_t ld_y = 0;
-    rc = loss_begin(t, pol, target, ld_target, start, memory, 1, &d_target, &ld_y); if (rc) return rc;
     rq_device* dev = t->env->dev;
-    float* d_grad = memory == RQ_DST_HOST ? t->grad.out.get() : grad_weights;
-    float* d_loss = memory == RQ_DST_HOST ? t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS : loss;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    const float* d_target = nullptr; uint32_t ld_y = 0;
+    rc = loss_begin(t, pol, target, ld_target, start, mem, 1, &d_target, &ld_y); if (rc) return rc;
+    float* d_grad = mem.out(grad_weights, RQ_POLICY_NUM_WEIGHTS, t->grad.out.get());
+    float* d_loss = mem.out(loss, 1, t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS);
     RQ_HIP(enqueue_loss_grad(t, pol, start, d_target, ld_y, d_grad, d_loss));
-    // the saved state is the forward's: a rq_trajectory_policy_backward may follow
-    t->grad.valid = true; t->grad.policy = pol; t->grad.weight_version = pol->weight_version; t->grad.length = t->length; t->grad.start = start;
-    if (memory == RQ_DST_HOST) {
-        RQ_HIP(hipMemcpyAsync(grad_weights, d_grad, RQ_POLICY_NUM_WEIGHTS * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
-        RQ_HIP(hipMemcpyAsync(loss, d_loss, sizeof(float), hipMemcpyDeviceToHost, dev->stream));
-    }
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    t->grad.stamp(pol, t->length, start);          // the saved state is the forward's: a rq_trajectory_policy_backward may follow
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 
@@ -295,40 +313,14 @@ RQ_API int rq_optimizer_create(rq_policy* pol, const rq_adam_config* config, rq_
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     rq_optimizer* o = new (std::nothrow) rq_optimizer();
     RQ_REQUIRE(o, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
-    o->dev = dev; o->ordinal = dev->ordinal; o->policy = pol;
-    const size_t entries = (size_t)rq::RQ_PACKED_FLOATS + rq::RQ_PACKED_GRAD_FLOATS;
-    std::vector<rq::PackGather> table;
-    try { table.resize(entries); rq::pack_gather_table(table.data()); } catch (const std::bad_alloc&) {
-        delete o;
-        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_optimizer_create: host allocation failed");
-    }
-    const rq::AdamState st{config->lr, config->beta1, config->beta2, config->eps, config->weight_decay, 1.0, 1.0, 0u, 0u};
-    hipError_t e = o->m.alloc(RQ_POLICY_NUM_WEIGHTS);
-    if (e == hipSuccess) e = o->v.alloc(RQ_POLICY_NUM_WEIGHTS);
-    if (e == hipSuccess) e = o->grad.alloc(RQ_POLICY_NUM_WEIGHTS);
-    if (e == hipSuccess) e = o->state.alloc(1);
-    if (e == hipSuccess) e = o->table.alloc(entries);
-    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
-    if (e == hipSuccess) e = hipMemset(o->m, 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(o->v, 0, RQ_POLICY_NUM_WEIGHTS * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(o->state, &st, sizeof(st), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->table, table.data(), entries * sizeof(rq::PackGather), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        delete o;
-        return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string("rq_optimizer_create: ") + hipGetErrorString(e));
-    }
+    o->policy = pol;
+    rc = adam_alloc("rq_optimizer_create", o, dev, config, 1, 1, false);
+    if (rc) { delete o; return rc; }
     *out = o;
     return RQ_OK;
 }
 
-RQ_API int rq_optimizer_destroy(rq_optimizer* opt) {
-    if (!opt) return RQ_OK;
-    DeviceScope on_device(opt->ordinal);
-    if (device_registry(opt->dev, 0)) (void)hipStreamSynchronize(opt->dev->stream);      // an update may still be queued
-    delete opt;
-    return RQ_OK;
-}
+RQ_API int rq_optimizer_destroy(rq_optimizer* opt) { return adam_destroy(opt); }
 
 RQ_API int rq_optimizer_set_lr(rq_optimizer* opt, double lr) {
     RQ_REQUIRE(opt, RQ_ERR_INVALID_ARGUMENT, "null argument");
@@ -345,11 +337,12 @@ RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer*
                "rq_trajectory_distill: the optimizer was made for another policy");
     RQ_REQUIRE(n_updates > 0, RQ_ERR_INVALID_ARGUMENT, "n_updates must be positive");
     int rc = loss_check(t, pol, target, ld_target, start, memory, "rq_trajectory_distill"); if (rc) return rc;
-    DeviceScope on_device(t->env->dev); rc = on_device.rc; if (rc) return rc;          // (retires a resident executor: it holds the old operands)
-    const float* d_target = nullptr; uint32_t ld_y = 0;
-    rc = loss_begin(t, pol, target, ld_target, start, memory, n_updates, &d_target, &ld_y); if (rc) return rc;
     rq_device* dev = t->env->dev;
-    float* d_losses = memory == RQ_DST_HOST ? t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS : losses;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;          // (retires a resident executor: it holds the old operands)
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    const float* d_target = nullptr; uint32_t ld_y = 0;
+    rc = loss_begin(t, pol, target, ld_target, start, mem, n_updates, &d_target, &ld_y); if (rc) return rc;
+    float* d_losses = mem.out(losses, n_updates, t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS);
     hipError_t e = hipSuccess;
     uint32_t done_updates = 0;
     for (; done_updates < n_updates && e == hipSuccess; ++done_updates) {
@@ -364,9 +357,7 @@ RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer*
         pol->mirror_stale = pol->images16_stale = true;
     }
     RQ_HIP(e);
-    if (memory == RQ_DST_HOST)
-        RQ_HIP(hipMemcpyAsync(losses, d_losses, (size_t)n_updates * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 
@@ -378,14 +369,15 @@ RQ_API int rq_trajectory_policies_loss_grad(rq_trajectory* t, rq_policy_bank* ba
     rq_device* dev = t->env->dev;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const size_t P = bank->n_policies, grad_floats = P * RQ_POLICY_NUM_WEIGHTS;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
     const float* d_target = nullptr; uint32_t ld_y = 0;
-    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, start, memory, P, &d_target, &ld_y); if (rc) return rc;
-    float* d_grad = memory == RQ_DST_HOST ? t->grad.out.get() : grad_weights;
-    float* d_loss = memory == RQ_DST_HOST ? t->grad.out.get() + grad_floats : loss;
+    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, start, mem, P, &d_target, &ld_y); if (rc) return rc;
+    float* d_grad = mem.host() ? t->grad.out.get() : grad_weights;
+    float* d_loss = mem.out(loss, P, t->grad.out.get() + grad_floats);
     RQ_HIP(enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, d_grad, d_loss));
     // (t->grad.valid stays false: the saved state is no single policy's, rq_trajectory_policy_backward has nothing to follow)
-    if (memory == RQ_DST_HOST) {
-        // a policy that owns no wave has no gradient row on the device: the caller's row stays as it was
+    if (mem.host()) {
+        // a policy that owns no wave has no gradient row on the device: the caller's row stays as it was (the losses: finish)
         std::vector<uint32_t> owns;
         try { owns.assign(P, 0u); } catch (const std::bad_alloc&) { return fail(RQ_ERR_OUT_OF_MEMORY, "host allocation failed"); }
         for (uint32_t id : bank->table_ids) owns[id] = 1u;
@@ -393,9 +385,8 @@ RQ_API int rq_trajectory_policies_loss_grad(rq_trajectory* t, rq_policy_bank* ba
             if (owns[p])
                 RQ_HIP(hipMemcpyAsync(grad_weights + p * RQ_POLICY_NUM_WEIGHTS, d_grad + p * RQ_POLICY_NUM_WEIGHTS,
                                       RQ_POLICY_NUM_WEIGHTS * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
-        RQ_HIP(hipMemcpyAsync(loss, d_loss, P * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
     }
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 
@@ -412,48 +403,14 @@ RQ_API int rq_bank_optimizer_create(rq_policy_bank* bank, const rq_adam_config* 
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     rq_bank_optimizer* o = new (std::nothrow) rq_bank_optimizer();
     RQ_REQUIRE(o, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
-    o->dev = dev; o->ordinal = dev->ordinal; o->bank = bank; o->bank_uid = bank->uid; o->n_policies = P;
-    const size_t entries = (size_t)rq::RQ_PACKED_FLOATS + rq::RQ_PACKED_GRAD_FLOATS, floats = (size_t)P * RQ_POLICY_NUM_WEIGHTS;
-    std::vector<rq::PackGather> table;
-    std::vector<rq::AdamState> st;
-    try {
-        table.resize(entries); rq::pack_gather_table(table.data());
-        st.resize(P);
-    } catch (const std::bad_alloc&) {
-        delete o;
-        return fail(RQ_ERR_OUT_OF_MEMORY, "rq_bank_optimizer_create: host allocation failed");
-    }
-    for (uint32_t p = 0; p < P; ++p) {
-        const rq_adam_config& c = config[n_cfg == 1 ? 0 : p];
-        st[p] = rq::AdamState{c.lr, c.beta1, c.beta2, c.eps, c.weight_decay, 1.0, 1.0, 0u, 0u};
-    }
-    hipError_t e = o->m.alloc(floats);
-    if (e == hipSuccess) e = o->v.alloc(floats);
-    if (e == hipSuccess) e = o->grad.alloc(floats);
-    if (e == hipSuccess) e = o->state.alloc(P);
-    if (e == hipSuccess) e = o->table.alloc(entries);
-    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
-    if (e == hipSuccess) e = hipMemset(o->m, 0, floats * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(o->v, 0, floats * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(o->grad, 0, floats * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(o->state, st.data(), (size_t)P * sizeof(rq::AdamState), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->table, table.data(), entries * sizeof(rq::PackGather), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        delete o;
-        return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string("rq_bank_optimizer_create: ") + hipGetErrorString(e));
-    }
+    o->bank = bank; o->bank_uid = bank->uid; o->n_policies = P;
+    rc = adam_alloc("rq_bank_optimizer_create", o, dev, config, n_cfg, P, true);
+    if (rc) { delete o; return rc; }
     *out = o;
     return RQ_OK;
 }
 
-RQ_API int rq_bank_optimizer_destroy(rq_bank_optimizer* opt) {
-    if (!opt) return RQ_OK;
-    DeviceScope on_device(opt->ordinal);
-    if (device_registry(opt->dev, 0)) (void)hipStreamSynchronize(opt->dev->stream);      // an update may still be queued
-    delete opt;
-    return RQ_OK;
-}
+RQ_API int rq_bank_optimizer_destroy(rq_bank_optimizer* opt) { return adam_destroy(opt); }
 
 RQ_API int rq_bank_optimizer_set_lr(rq_bank_optimizer* opt, const double* lr, uint32_t n) {
     RQ_REQUIRE(opt && lr, RQ_ERR_INVALID_ARGUMENT, "null argument");
@@ -476,9 +433,10 @@ RQ_API int rq_trajectory_policies_distill(rq_trajectory* t, rq_policy_bank* bank
     rq_device* dev = t->env->dev;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const size_t P = bank->n_policies, n_losses = (size_t)n_updates * P;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
     const float* d_target = nullptr; uint32_t ld_y = 0;
-    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, start, memory, n_losses, &d_target, &ld_y); if (rc) return rc;
-    float* d_losses = memory == RQ_DST_HOST ? t->grad.out.get() + P * RQ_POLICY_NUM_WEIGHTS : losses;
+    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, start, mem, n_losses, &d_target, &ld_y); if (rc) return rc;
+    float* d_losses = mem.out(losses, n_losses, t->grad.out.get() + P * RQ_POLICY_NUM_WEIGHTS);
     hipError_t e = hipSuccess;
     for (uint32_t k = 0; k < n_updates && e == hipSuccess; ++k) {       // back to back: nothing waits in between
         e = enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, opt->grad, d_losses + (size_t)k * P);
@@ -486,9 +444,7 @@ RQ_API int rq_trajectory_policies_distill(rq_trajectory* t, rq_policy_bank* bank
                                                              opt->v, opt->state, opt->table, bank->images, bank->gimages);
     }
     RQ_HIP(e);
-    if (memory == RQ_DST_HOST)
-        RQ_HIP(hipMemcpyAsync(losses, d_losses, n_losses * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 

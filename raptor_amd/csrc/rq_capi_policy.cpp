@@ -408,7 +408,7 @@ RQ_API int rq_policy_evaluate_sequence(rq_policy* pol, const float* observation,
     RQ_REQUIRE(pol && observation && action, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(steps > 0 && batch > 0, RQ_ERR_INVALID_ARGUMENT, "empty sequence");
     RQ_REQUIRE(obs_stride >= RQ_POLICY_INPUT_DIM, RQ_ERR_INVALID_ARGUMENT, "obs_stride < 22");
-    RQ_REQUIRE(memory >= RQ_DST_HOST && memory <= RQ_DST_DEVICE_ASYNC, RQ_ERR_INVALID_ARGUMENT, "memory must be 0, 1 or 2");
+    RQ_REQUIRE(CallMemory::valid(memory), RQ_ERR_INVALID_ARGUMENT, "memory must be 0, 1 or 2");
     RQ_REQUIRE(pol->sas_mode != RQ_SAS_SAMPLE, RQ_ERR_INVALID_ARGUMENT,
                "sequence evaluation is a deterministic pass: RQ_SAS_SAMPLE is defined for evaluate_step and rollouts");
     { const int rate_rc = require_native_rate(pol, "rq_policy_evaluate_sequence"); if (rate_rc) return rate_rc; }
@@ -419,20 +419,17 @@ RQ_API int rq_policy_evaluate_sequence(rq_policy* pol, const float* observation,
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     rc = policy_size(pol, batch); if (rc) return rc;
     const size_t rows = (size_t)steps * batch;
-    const float* d_obs = observation;
-    float* d_act = action;
-    if (memory == RQ_DST_HOST) {
-        const size_t obs_bytes = ((rows - 1) * obs_stride + RQ_POLICY_INPUT_DIM) * sizeof(float);
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    if (mem.host()) {
         RQ_HIP(dev->rows.reserve(dev->stream, rows * obs_stride));
         RQ_HIP(dev->rows2.reserve(dev->stream, rows * RQ_ACTION_DIM));
-        RQ_HIP(hipMemcpyAsync(dev->rows, observation, obs_bytes, hipMemcpyHostToDevice, dev->stream));
-        d_obs = dev->rows; d_act = dev->rows2;
     }
+    const float* d_obs = nullptr;          // (the last row ends with its 22 floats: the caller's array need not hold a whole stride there)
+    RQ_HIP(mem.in(observation, (rows - 1) * obs_stride + RQ_POLICY_INPUT_DIM, dev->rows.get(), &d_obs));
+    float* d_act = mem.out(action, rows * RQ_ACTION_DIM, dev->rows2.get());
     RQ_HIP(rq::launch_actor_sequence(dev->stream, batch, steps, packed_of(pol), d_obs, obs_stride, pol->hidden, pol->ld,
                                      d_act, mode_of(pol)));
-    if (memory == RQ_DST_HOST)
-        RQ_HIP(hipMemcpyAsync(action, dev->rows2, rows * RQ_ACTION_DIM * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 

@@ -4,7 +4,8 @@
 // is the caller's, in float64 (raptor_amd/probing.py).  rq_trajectory_wrench_targets rebuilds such targets on the device: the
 // scheduled wrench every env was flown with at every recorded step.
 // The first three read the saved state of a forward by this policy from the learned initial state at its current weights: the one a
-// learner call left, or the state-only forward run here (grad_saved_initial, rq_capi_grad.cpp).  Kernels: rq_probe.hip.
+// learner call left, or the state-only forward run here (grad_saved_initial, rq_capi_grad.cpp).  Like the learner's calls each goes
+// through one rq::CallMemory (rq_call_memory.hpp): refusals, DeviceScope, prepare, in, launch, out, finish.  Kernels: rq_probe.hip.
 #include <cmath>
 
 #include "rq_objects.hpp"
@@ -13,28 +14,6 @@
 using namespace rqh;
 
 namespace {
-
-int check_memory(int memory) {
-    RQ_REQUIRE(memory >= RQ_DST_HOST && memory <= RQ_DST_DEVICE_ASYNC, RQ_ERR_INVALID_ARGUMENT, "memory must be 0, 1 or 2");
-    return RQ_OK;
-}
-
-// a device-memory call's array: device memory of the trajectory's device
-int check_device_array(const rq_device* dev, const void* p, const char* what, const char* name) {
-    hipPointerAttribute_t at{};
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    RQ_REQUIRE(e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == dev->ordinal, RQ_ERR_SHAPE_MISMATCH,
-               std::string(what) + ": " + name + " lives on another device (or on the host): device memory of the trajectory's device is expected");
-    return RQ_OK;
-}
-
-// RQ_HIP inside a body two entry points share: the message begins with the entry point's name
-#define PROBE_HIP(who, expr)                                           \
-    do {                                                               \
-        const hipError_t e_ = (expr);                                  \
-        if (e_ != hipSuccess) return hip_failed((who), #expr, e_);     \
-    } while (0)
 
 // rq_trajectory_probe_moments (targets [n_targets][ld_targets]) and, `timed`, rq_trajectory_probe_moments_timed (targets
 // [length][n_targets][ld_targets]): one set of refusals, one device block, one of two launches.  `what`: the entry point's name.
@@ -60,7 +39,8 @@ int probe_moments(const char* what, bool timed, rq_trajectory* t, rq_policy* pol
     rq_device* dev = env->dev;
     RQ_REFUSE(what, ld_targets >= env->n, RQ_ERR_INVALID_ARGUMENT, "ld_targets must be at least the number of envs");
     const uint32_t blocks = timed ? t->length : 1u;          // [n_targets][ld_targets] blocks of targets: one, or one per step
-    if (memory == RQ_DST_HOST) {
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    if (mem.host()) {
         for (uint32_t s = 0; s < blocks; ++s)
             for (uint32_t m = 0; m < n_targets; ++m)
                 for (uint32_t i = 0; i < env->n; ++i)
@@ -68,35 +48,29 @@ int probe_moments(const char* what, bool timed, rq_trajectory* t, rq_policy* pol
                               "targets must be finite (" + (timed ? "step " + std::to_string(s) + ", " : std::string()) + "target " +
                                   std::to_string(m) + ", env " + std::to_string(i) + " is not)");
     } else {
-        rc = check_device_array(dev, targets, what, "targets"); if (rc) return rc;
-        rc = check_device_array(dev, moments, what, "moments"); if (rc) return rc;
-        rc = check_device_array(dev, counts, what, "counts"); if (rc) return rc;
+        rc = check_device_array(mem, targets, what, "targets"); if (rc) return rc;
+        rc = check_device_array(mem, moments, what, "moments"); if (rc) return rc;
+        rc = check_device_array(mem, counts, what, "counts"); if (rc) return rc;
     }
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = grad_saved_initial(t, pol); if (rc) return rc;
-    PROBE_HIP(what, t->grad.probe.reserve(dev->stream, rq::probe_partial_floats(env->n, n_buckets)));
-    const size_t moment_doubles = (size_t)n_buckets * rq::kProbeDim * rq::kProbeDim;
-    const float* d_y = targets;
-    double* d_moments = moments;
-    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(counts);
-    if (memory == RQ_DST_HOST) {          // one device block: moments | counts | targets (targets per step: a block of their own)
-        const size_t y_floats = (size_t)blocks * n_targets * ld_targets;
-        PROBE_HIP(what, t->grad.probe_io.reserve(dev->stream, moment_doubles + n_buckets + (timed ? 0 : (y_floats + 1) / 2)));
-        if (timed) PROBE_HIP(what, t->grad.probe_targets.reserve(dev->stream, y_floats));
-        d_moments = t->grad.probe_io;
-        d_counts = reinterpret_cast<unsigned long long*>(d_moments + moment_doubles);
-        float* y_dev = timed ? t->grad.probe_targets.get() : reinterpret_cast<float*>(d_moments + moment_doubles + n_buckets);
-        PROBE_HIP(what, hipMemcpyAsync(y_dev, targets, y_floats * sizeof(float), hipMemcpyHostToDevice, dev->stream));
-        d_y = y_dev;
+    RQ_HIP_AS(what, t->grad.probe.reserve(dev->stream, rq::probe_partial_floats(env->n, n_buckets)));
+    const size_t moment_doubles = (size_t)n_buckets * rq::kProbeDim * rq::kProbeDim, y_floats = (size_t)blocks * n_targets * ld_targets;
+    double* s_moments = nullptr; unsigned long long* s_counts = nullptr; float* s_y = nullptr;
+    if (mem.host()) {          // one device block: moments | counts | targets (targets per step: a block of their own)
+        RQ_HIP_AS(what, t->grad.probe_io.reserve(dev->stream, moment_doubles + n_buckets + (timed ? 0 : (y_floats + 1) / 2)));
+        if (timed) RQ_HIP_AS(what, t->grad.probe_targets.reserve(dev->stream, y_floats));
+        s_moments = t->grad.probe_io;
+        s_counts = reinterpret_cast<unsigned long long*>(s_moments + moment_doubles);
+        s_y = timed ? t->grad.probe_targets.get() : reinterpret_cast<float*>(s_moments + moment_doubles + n_buckets);
     }
-    PROBE_HIP(what, (timed ? rq::launch_probe_moments_timed : rq::launch_probe_moments)(
+    const float* d_y = nullptr; RQ_HIP_AS(what, mem.in(targets, y_floats, s_y, &d_y));
+    double* d_moments = mem.out(moments, moment_doubles, s_moments);
+    unsigned long long* d_counts = mem.out(reinterpret_cast<unsigned long long*>(counts), n_buckets, s_counts);
+    RQ_HIP_AS(what, (timed ? rq::launch_probe_moments_timed : rq::launch_probe_moments)(
                         dev->stream, env->n, env->ld, t->length, t->grad.saved, t->done, d_y, ld_targets, n_targets, edges, n_buckets,
                         t->grad.probe, d_moments, d_counts));
-    if (memory == RQ_DST_HOST) {
-        PROBE_HIP(what, hipMemcpyAsync(moments, d_moments, moment_doubles * sizeof(double), hipMemcpyDeviceToHost, dev->stream));
-        PROBE_HIP(what, hipMemcpyAsync(counts, d_counts, (size_t)n_buckets * sizeof(uint64_t), hipMemcpyDeviceToHost, dev->stream));
-    }
-    if (memory != RQ_DST_DEVICE_ASYNC) PROBE_HIP(what, hipStreamSynchronize(dev->stream));
+    RQ_HIP_AS(what, mem.finish());
     return RQ_OK;
 }
 
@@ -111,18 +85,15 @@ RQ_API int rq_trajectory_get_hidden(rq_trajectory* t, rq_policy* pol, float* out
     RQ_REQUIRE(out, RQ_ERR_INVALID_ARGUMENT, "null argument: out");
     rq_env* env = t->env;
     rq_device* dev = env->dev;
-    if (memory != RQ_DST_HOST) { rc = check_device_array(dev, out, what, "out"); if (rc) return rc; }
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    rc = check_device_array(mem, out, what, "out"); if (rc) return rc;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     rc = grad_saved_initial(t, pol); if (rc) return rc;
     const size_t floats = (size_t)t->length * env->n * RQ_POLICY_HIDDEN_DIM;
-    float* d_out = out;
-    if (memory == RQ_DST_HOST) {
-        RQ_HIP(t->grad.rows.reserve(dev->stream, floats));
-        d_out = t->grad.rows;
-    }
+    if (mem.host()) RQ_HIP(t->grad.rows.reserve(dev->stream, floats));
+    float* d_out = mem.out(out, floats, t->grad.rows.get());
     RQ_HIP(rq::launch_probe_hidden_rows(dev->stream, env->n, env->ld, t->length, t->grad.saved, d_out));
-    if (memory == RQ_DST_HOST) RQ_HIP(hipMemcpyAsync(out, d_out, floats * sizeof(float), hipMemcpyDeviceToHost, dev->stream));
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 
@@ -167,7 +138,8 @@ RQ_API int rq_trajectory_wrench_targets(rq_trajectory* t, const rq_wrench_bank* 
         RQ_REQUIRE(start_steps[i] < limit, RQ_ERR_INVALID_ARGUMENT,
                    "start_steps out of range: env " + std::to_string(i) + " starts at episode step " + std::to_string(start_steps[i]) +
                        ", episode_step_limit is " + std::to_string(limit));
-    if (memory != RQ_DST_HOST) { rc = check_device_array(dev, out, what, "out"); if (rc) return rc; }
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    rc = check_device_array(mem, out, what, "out"); if (rc) return rc;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
 
     // first rows | start steps go through the trajectory's pinned block and are uploaded only when they differ from the call
@@ -194,20 +166,14 @@ RQ_API int rq_trajectory_wrench_targets(rq_trajectory* t, const rq_wrench_bank* 
         RQ_HIP(hipMemcpyAsync(g.probe_rows, rows_host, 2 * (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, dev->stream));
         g.probe_rows_valid = true;
     }
-    float* d_out = out;
-    uint32_t d_ld = ld_out;
-    if (memory == RQ_DST_HOST) {          // packed [length][6][n] on the device: only the envs' columns go back
-        RQ_HIP(g.rows.reserve(dev->stream, (size_t)t->length * 6 * n));
-        d_out = g.rows;
-        d_ld = n;
-    }
+    // a host-memory call: packed [length][6][n] on the device, only the envs' columns go back
+    if (mem.host()) RQ_HIP(g.rows.reserve(dev->stream, (size_t)t->length * 6 * n));
+    const uint32_t d_ld = mem.host() ? n : ld_out;
+    float* d_out = mem.out(out, ld_out, g.rows.get(), n, n, (size_t)t->length * 6);
     const bool scale = units_out == RQ_WRENCH_ABSOLUTE && bank->units == RQ_WRENCH_RELATIVE;
     RQ_HIP(rq::launch_probe_wrench_targets(dev->stream, n, env->ld, t->length, t->done, bank->d, bank->rows, g.probe_rows,
                                            g.probe_rows.get() + n, scale, params->d, env->cfg.gravity, d_out, d_ld));
-    if (memory == RQ_DST_HOST)
-        RQ_HIP(hipMemcpy2DAsync(out, (size_t)ld_out * sizeof(float), d_out, (size_t)n * sizeof(float), (size_t)n * sizeof(float),
-                                (size_t)t->length * 6, hipMemcpyDeviceToHost, dev->stream));
-    if (memory != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(dev->stream));
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 

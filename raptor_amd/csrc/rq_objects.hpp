@@ -12,6 +12,7 @@
 //   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory; the distillation update (loss, Adam, repack),
 //                        for one policy and for a policy bank
 //   rq_memory.hpp        rq::DeviceBuffer / rq::PinnedBuffer: every object below owns its device and pinned memory through them
+//   rq_call_memory.hpp   rq::CallMemory: the `memory` argument of the learner's and the probes' calls - staging in and out, the final wait
 // The ten rq_rollout* entry points (a policy's, a policy bank's, the teacher bank's; plain, _track, _track_refs) each describe their call
 // (RolloutCall) and go through rollout_run below with the actor type of their file; their row tables are one type (RowTables).
 // Helpers live in namespace rqh (each .cpp says `using namespace rqh;`); nothing here is visible outside libraptor_quad.so.
@@ -38,11 +39,13 @@
 
 #include "rq_host.hpp"
 #include "rq_memory.hpp"
+#include "rq_call_memory.hpp"
 
 using rq::fail;
 using rq::DeviceScope;
 using rq::DeviceBuffer;
 using rq::PinnedBuffer;
+using rq::CallMemory;
 
 inline uint32_t round_up64(uint32_t n) { return (n + 63u) & ~63u; }
 
@@ -278,6 +281,8 @@ struct rq_trajectory {
         uint64_t weight_version = 0;   // rq_policy::weight_version at the forward
         uint32_t length = 0;
         int start = 0;                 // enum rq_grad_start
+        void stamp(const rq_policy* pol, uint32_t steps, int from);      // `saved` is now pol's forward over `steps` steps from `from`
+        bool matches(const rq_policy* pol, uint32_t steps) const { return valid && policy == pol && length == steps; }
         DeviceBuffer<float> out;       // the loss-seeded calls: grad [2084] | losses [n_updates] before they go to the caller
         DeviceBuffer<unsigned long long> live;    // [1]: M, the live entries of the last loss
         // the probes (rq_capi_probe.cpp): the waves' partial moments and counts (rq::probe_partial_floats), and the call's small
@@ -348,27 +353,26 @@ struct rq_policy {
     bool images16_stale = false;  // w_packed_bf16, w_packed_f16x2 are older than w_dev
 };
 
-// Adam's state for one policy (rq_capi_grad.cpp; kernel: rq_grad.hpp k_adam_repack)
-struct rq_optimizer {
-    rq_device* dev = nullptr;
-    int ordinal = 0;
-    rq_policy* policy = nullptr;
-    DeviceBuffer<float> m, v, grad;          // [2084] each
-    DeviceBuffer<rq::AdamState> state;       // [1]
-    DeviceBuffer<rq::PackGather> table;      // pack_gather_table
-};
+inline void rq_trajectory::Grad::stamp(const rq_policy* pol, uint32_t steps, int from) {
+    valid = true; policy = pol; weight_version = pol->weight_version; length = steps; start = from;
+}
 
-struct rq_policy_bank;
-// Adam's state for every policy of a bank (rq_capi_grad.cpp; kernel: rq_grad_bank.hpp k_adam_repack_bank)
-struct rq_bank_optimizer {
+// Adam's state (rq_capi_grad.cpp adam_alloc) for one policy (kernel: rq_grad.hpp k_adam_repack) or a bank's (rq_grad_bank.hpp)
+namespace rqh {
+struct AdamBuffers {
     rq_device* dev = nullptr;
     int ordinal = 0;
+    DeviceBuffer<float> m, v, grad;          // [slots][2084] each
+    DeviceBuffer<rq::AdamState> state;       // [slots]: every hyper-parameter per policy
+    DeviceBuffer<rq::PackGather> table;      // pack_gather_table, shared
+};
+}  // namespace rqh
+struct rq_optimizer : rqh::AdamBuffers { rq_policy* policy = nullptr; };
+struct rq_policy_bank;
+struct rq_bank_optimizer : rqh::AdamBuffers {
     const rq_policy_bank* bank = nullptr;    // compared, with bank_uid, never followed
     uint64_t bank_uid = 0;
     uint32_t n_policies = 0;
-    DeviceBuffer<float> m, v, grad;          // [n_policies][2084] each
-    DeviceBuffer<rq::AdamState> state;       // [n_policies]: every hyper-parameter per policy
-    DeviceBuffer<rq::PackGather> table;      // pack_gather_table, shared
 };
 
 struct rq_teacher_bank {
@@ -506,6 +510,9 @@ int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what);
 // inside the caller's DeviceScope: t->grad.saved holds the state of a forward by `pol` from the learned initial state at its current
 // weights - the one a forward or a loss call left if its tags say so, else the state-only forward is enqueued and tagged
 int grad_saved_initial(rq_trajectory* t, rq_policy* pol);
+// what every `memory` argument refuses: its range; an array (`noun`: as the message names it) that is not the call's device's memory
+int check_memory(int memory);
+int check_device_array(const CallMemory& mem, const void* p, const char* what, const char* noun);
 
 // ---- rq_capi_policy_bank.cpp: what the bank's rollout and its learner (rq_capi_grad.cpp) share; all but bank_check_ids need the
 // caller's DeviceScope ----
@@ -560,6 +567,12 @@ int upload_first_rows(const char* what, rq_device* dev, const rq_env* env, const
 inline int hip_failed(const char* who, const char* what, hipError_t e) {
     return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string(who) + ": " + what + " -> " + hipGetErrorString(e));
 }
+// RQ_HIP inside a body several entry points share: the message begins with the entry point's name
+#define RQ_HIP_AS(who, expr)                                                \
+    do {                                                                    \
+        const hipError_t e_ = (expr);                                       \
+        if (e_ != hipSuccess) return rqh::hip_failed((who), #expr, e_);     \
+    } while (0)
 // The fused mode of a policy or a policy bank.  fused_args: the launch description, all but the actor; the actor adds its fields and
 // calls fused_launch: under rq_device_set_rollout_timing the span buffer sized for the env's waves, the one
 // rq::launch_rollout_fused (rq_fused_route.hpp picks the kernel), and behind it what rq_device_last_rollout_ms goes by.
@@ -686,11 +699,11 @@ template <typename T>
 int copy_out(const rq_env* env, const T* src, T* dst, int dst_is_device) {
     RQ_REQUIRE(env && dst, RQ_ERR_INVALID_ARGUMENT, "null argument");
     DeviceScope on_device(env->dev); int rc = on_device.rc; if (rc) return rc;
-    RQ_REQUIRE(dst_is_device >= RQ_DST_HOST && dst_is_device <= RQ_DST_DEVICE_ASYNC, RQ_ERR_INVALID_ARGUMENT,
-               "dst_is_device must be 0, 1 or 2");
+    RQ_REQUIRE(CallMemory::valid(dst_is_device), RQ_ERR_INVALID_ARGUMENT, "dst_is_device must be 0, 1 or 2");
+    CallMemory mem(dst_is_device, env->dev->stream, env->dev->ordinal);
     RQ_HIP(hipMemcpyAsync(dst, src, (size_t)env->n * sizeof(T),
                           dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, env->dev->stream));
-    if (dst_is_device != RQ_DST_DEVICE_ASYNC) RQ_HIP(hipStreamSynchronize(env->dev->stream));
+    RQ_HIP(mem.finish());
     return RQ_OK;
 }
 
