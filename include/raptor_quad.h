@@ -39,7 +39,8 @@
  *     quadrotors (checks, teacher-acting collection)    :207-216 rq_rollout_teachers / rq_teacher_bank_evaluate
  *     ... on a moving setpoint, one table or one per env          rq_rollout_teachers_track / rq_rollout_teachers_track_refs
  *   distillation: the student's regression gradient    :208-216 rq_trajectory_policy_forward / _backward + rq_policy_set_weights;
- *                                                              rq_trajectory_distill (loss, Adam and repack on the device)
+ *                                                              rq_trajectory_distill (loss, Adam and repack on the device);
+ *                                                              rq_trajectory_*_weighted (a weight per env or per env and step)
  *   (the reference is single-process) env shards over
  *     GPUs + all-gather of episode returns (RCCL)                rq_env_create(global_env_offset) / rq_comm_* / rq_allgather_returns
  *
@@ -814,6 +815,45 @@ RQ_API int rq_bank_optimizer_set_lr(rq_bank_optimizer* optimizer, const double* 
 RQ_API int rq_trajectory_policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* optimizer,
                                           const uint32_t* policy_id, const float* target, uint32_t ld_target, int start,
                                           uint32_t n_updates, float* losses, int memory);
+
+/* ---- A weighted loss: the four loss calls above with a weight per env, or per env and step - hold out some envs of a recording and
+ * report their loss (a 0/1 mask and its complement), trust good teachers more than bad ones, stress the first second after a reset.
+ * weight: float32 [weight_steps][ld_weight], ld_weight >= n_envs; weight_steps = 1: one weight per env for every step; weight_steps
+ * = the trajectory's length T: one per env and step, w[t][i].  Entry (t, i, k) - action k of env i at step t - COUNTS when it is live
+ * (done code != 4, i < n_envs) and its weight is > 0.  Everything else is selected away, never multiplied: frozen steps, padding
+ * columns, and weights that are 0, negative or NaN; NaN in the target, the observation or the weight of an entry that does not count
+ * goes nowhere.  On a counting entry, in fp32 as the unweighted calls:
+ *     e = a - y,   seed = fl(w e)  (dL/da before the scale),   term = fl(seed e),
+ *     W4 = the sum of w over the counting entries (4 x the sum over the counting env-steps),
+ *     loss = sum(term) / W4,   grad = (sum over the waves of their partial gradients) x 2 / W4.
+ * Normaliser: W4 is accumulated in float64 - per lane over the lane's own entries in the order the kernel walks them, the 64 lanes of
+ * a wave folded 0 .. 63, the waves in ascending order (for a bank: policy p's waves, W4_p) - and the scale is applied once, the
+ * float64 product acc x (2 / W4) rounded to fp32 once; squared errors and partial gradients are reduced in wave order as in the
+ * unweighted calls.  No float atomics: the same bits every run.  W4 = 0 (nothing counts) gives loss 0 and a zero gradient, not NaN;
+ * the update then runs Adam on a zero gradient, which with zero moments and weight_decay = 0 leaves the weights as they are.  With
+ * every weight 1.0f W4 is the integer M and each call returns the bits of its unweighted sibling: loss, gradient, updated weights.
+ * Everything else - target == NULL meaning the stored actions, start, memory, the saved state a rq_trajectory_policy_backward may
+ * follow, ordering on the stream, the optimizer belonging to the policy or bank, a policy of a bank that owns no block - is the
+ * sibling's.  The weight travels like the target: RQ_DST_HOST copies a host array in, RQ_DST_DEVICE* take device memory of the
+ * trajectory's device, which an enqueued-only call may still be reading when it returns.
+ * Refused before anything is enqueued, outputs untouched (rq_last_error names the argument): a null weight; weight_steps that is
+ * neither 1 nor T; ld_weight < n_envs; with RQ_DST_HOST a weight that is negative or not finite in the envs' columns (the message
+ * names step and env - device memory is not read by the host: there such a weight drops its entries); a weight that is not device
+ * memory of the trajectory's device when one is announced; and every refusal of the sibling. */
+RQ_API int rq_trajectory_policy_loss_grad_weighted(rq_trajectory* t, rq_policy* policy, const float* target, uint32_t ld_target,
+                                                   const float* weight, uint32_t ld_weight, uint32_t weight_steps, int start,
+                                                   float* loss, float* grad_weights, int memory);
+RQ_API int rq_trajectory_distill_weighted(rq_trajectory* t, rq_policy* policy, rq_optimizer* optimizer, const float* target,
+                                          uint32_t ld_target, const float* weight, uint32_t ld_weight, uint32_t weight_steps,
+                                          int start, uint32_t n_updates, float* losses, int memory);
+RQ_API int rq_trajectory_policies_loss_grad_weighted(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id,
+                                                     const float* target, uint32_t ld_target, const float* weight,
+                                                     uint32_t ld_weight, uint32_t weight_steps, int start, float* loss,
+                                                     float* grad_weights, int memory);
+RQ_API int rq_trajectory_policies_distill_weighted(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* optimizer,
+                                                   const uint32_t* policy_id, const float* target, uint32_t ld_target,
+                                                   const float* weight, uint32_t ld_weight, uint32_t weight_steps, int start,
+                                                   uint32_t n_updates, float* losses, int memory);
 
 
 /* ---- Multi-GPU: the path's one exchange ---------------------------------------------

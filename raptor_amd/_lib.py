@@ -183,6 +183,8 @@ _SIGNATURES = {
     "rq_optimizer_destroy": [_vp],
     "rq_optimizer_set_lr": [_vp, C.c_double],
     "rq_trajectory_distill": [_vp, _vp, _vp, _fp, C.c_uint32, C.c_int, C.c_uint32, _fp, C.c_int],
+    "rq_trajectory_policy_loss_grad_weighted": [_vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, C.c_int, _fp, _fp, C.c_int],
+    "rq_trajectory_distill_weighted": [_vp, _vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, _fp, C.c_int],
     "rq_policy_get_weights": [_vp, _fp],
     "rq_trajectory_get_hidden": [_vp, _vp, _fp, C.c_int],
     "rq_trajectory_probe_moments": [_vp, _vp, _fp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_int],
@@ -217,6 +219,9 @@ _SIGNATURES = {
     "rq_bank_optimizer_destroy": [_vp],
     "rq_bank_optimizer_set_lr": [_vp, _vp, C.c_uint32],
     "rq_trajectory_policies_distill": [_vp, _vp, _vp, _vp, _fp, C.c_uint32, C.c_int, C.c_uint32, _fp, C.c_int],
+    "rq_trajectory_policies_loss_grad_weighted": [_vp, _vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, C.c_int, _fp, _fp, C.c_int],
+    "rq_trajectory_policies_distill_weighted": [_vp, _vp, _vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, _fp,
+                                                C.c_int],
     "rq_reference_create": [_vp, _fp, C.c_uint32, C.POINTER(_vp)],
     "rq_reference_destroy": [_vp],
     "rq_rollout_track": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp],

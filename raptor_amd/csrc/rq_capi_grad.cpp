@@ -3,9 +3,12 @@
 // through time along the recorded episode structure (rq_trajectory_policy_backward); and the whole distillation update on the device:
 // masked-MSE loss and gradient (rq_trajectory_policy_loss_grad), Adam and the operand images (rq_trajectory_distill); and that update
 // for every policy of a policy bank at once (rq_trajectory_policies_loss_grad, rq_bank_optimizer_*, rq_trajectory_policies_distill).
+// The four loss calls have a *_weighted sibling each - a weight per env, or per env and step, in the loss - that shares their body.
 // Every call with a `memory` argument reads refusals, DeviceScope, prepare, in, launch, out, finish: the staging copies and the final
 // wait are one rq::CallMemory (rq_call_memory.hpp), the staging buffers are reserved here.  Kernels: rq_grad.hpp, rq_grad_bank.hpp.
 #include "rq_objects.hpp"
+
+#include <cfloat>
 
 using namespace rqh;
 
@@ -73,59 +76,92 @@ int ensure_grad_image(rq_policy* pol) {
 // a resident executor included, alone).  loss_begin, inside it: the workspace and the target on the device; n_losses: floats wanted
 // behind the gradient in t->grad.out.  -> d_target / ld_y as the kernel takes them.  loss_check_call and loss_workspace are the parts
 // that do not ask whose weights they are: the bank's calls below share them.
-int loss_check_call(rq_trajectory* t, const float* target, uint32_t ld_target, int start, int memory, const char* what) {
+// The *_weighted calls are their siblings with a LossWeight that is `given`: the weight [steps][ld] as the caller named it.  It
+// travels like the target - a host array is copied in behind the target's staging, a device array is used where it lies.
+struct LossWeight { bool given; const float* w; uint32_t ld, steps; };
+constexpr LossWeight kNoWeight{false, nullptr, 0, 0};
+
+int loss_check_call(rq_trajectory* t, const float* target, uint32_t ld_target, const LossWeight& wt, int start, int memory,
+                    const char* what) {
     int rc = check_memory(memory); if (rc) return rc;
     RQ_REQUIRE(start == RQ_GRAD_START_CURRENT || start == RQ_GRAD_START_INITIAL, RQ_ERR_INVALID_ARGUMENT,
                "start must be RQ_GRAD_START_CURRENT or RQ_GRAD_START_INITIAL");
     const rq_device* dev = t->env->dev;
+    const CallMemory mem(memory, dev->stream, dev->ordinal);
+    const uint32_t n = t->env->n;
     if (target) {
-        RQ_REQUIRE(ld_target >= t->env->n, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": ld_target must be at least the number of envs");
-        return check_device_array(CallMemory(memory, dev->stream, dev->ordinal), target, what, "the target");
+        RQ_REQUIRE(ld_target >= n, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": ld_target must be at least the number of envs");
+        rc = check_device_array(mem, target, what, "the target"); if (rc) return rc;
     }
+    if (!wt.given) return RQ_OK;
+    RQ_REQUIRE(wt.w, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": weight is null");
+    RQ_REQUIRE(wt.steps == 1 || wt.steps == t->length, RQ_ERR_INVALID_ARGUMENT,
+               std::string(what) + ": weight_steps must be 1 (a weight per env) or the trajectory's length " + std::to_string(t->length) +
+                   " (one per env and step), not " + std::to_string(wt.steps));
+    RQ_REQUIRE(wt.ld >= n, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": ld_weight must be at least the number of envs");
+    if (!mem.host()) return check_device_array(mem, wt.w, what, "the weight");
+    // a host array can be read here: a weight that cannot be meant is refused by name (on the device it is dropped, rq_grad_backward.inc)
+    for (uint32_t s = 0; s < wt.steps; ++s)
+        for (uint32_t i = 0; i < n; ++i) {
+            const float w = wt.w[(size_t)s * wt.ld + i];
+            RQ_REQUIRE(w >= 0.0f && w <= FLT_MAX, RQ_ERR_INVALID_ARGUMENT,
+                       std::string(what) + ": weight of step " + std::to_string(s) + ", env " + std::to_string(i) +
+                           " is negative or not finite (" + std::to_string(w) + ")");
+        }
     return RQ_OK;
 }
 
-int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, int memory, const char* what) {
+int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, const LossWeight& wt, int start, int memory,
+               const char* what) {
     int rc = grad_check_pair(t, pol, what); if (rc) return rc;
-    return loss_check_call(t, target, ld_target, start, memory, what);
+    return loss_check_call(t, target, ld_target, wt, start, memory, what);
 }
 
-// the workspace and the target on the device; out_floats: what t->grad.out is to hold (gradients, then losses)
-int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, const CallMemory& mem, size_t out_floats,
-                   const float** d_target, uint32_t* ld_y) {
+// the workspace, the target and the weight on the device; out_floats: what t->grad.out is to hold (gradients, then losses).
+// -> *d_weight: the weight as the kernel takes it (null without one)
+int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, const LossWeight& wt, const CallMemory& mem,
+                   size_t out_floats, const float** d_target, uint32_t* ld_y, const float** d_weight) {
     rq_env* env = t->env;
     rq_device* dev = env->dev;
     const uint32_t T = t->length, ld = env->ld;
     t->grad.valid = false;
     RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld));
-    RQ_HIP(t->grad.partial.reserve(dev->stream, rq::policy_loss_partial_floats(env->n)));
+    RQ_HIP(t->grad.partial.reserve(dev->stream, wt.given ? rq::policy_loss_weighted_partial_floats(env->n)
+                                                         : rq::policy_loss_partial_floats(env->n)));
     RQ_HIP(t->grad.out.reserve(dev->stream, out_floats));
     RQ_HIP(t->grad.live.reserve(dev->stream, 1));
     *d_target = t->act.get();          // the stored actions: what a relabel or a teacher-acting rollout left
     *ld_y = target ? ld_target : ld;
-    if (target) {
-        const size_t floats = (size_t)T * RQ_ACTION_DIM * ld_target;
-        if (mem.host()) RQ_HIP(t->grad.rows.reserve(dev->stream, floats));
-        RQ_HIP(mem.in(target, floats, t->grad.rows.get(), d_target));
-    }
+    *d_weight = nullptr;
+    // host-memory calls: one device block, the target | the weight, the second begun at a multiple of 256 bytes
+    const size_t y_floats = target ? (size_t)T * RQ_ACTION_DIM * ld_target : 0, w_floats = wt.given ? (size_t)wt.steps * wt.ld : 0;
+    const size_t off_w = wt.given ? (y_floats + 63) & ~(size_t)63 : y_floats;
+    if (mem.host() && off_w + w_floats > 0) RQ_HIP(t->grad.rows.reserve(dev->stream, off_w + w_floats));
+    if (target) RQ_HIP(mem.in(target, y_floats, t->grad.rows.get(), d_target));
+    if (wt.given) RQ_HIP(mem.in(wt.w, w_floats, t->grad.rows.get() + off_w, d_weight));
     return RQ_OK;
 }
 
-int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start, const CallMemory& mem,
-               size_t n_losses, const float** d_target, uint32_t* ld_y) {
+int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, const LossWeight& wt, int start,
+               const CallMemory& mem, size_t n_losses, const float** d_target, uint32_t* ld_y, const float** d_weight) {
     int rc = RQ_OK;
     if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, t->env->n); if (rc) return rc; }
     rc = ensure_grad_image(pol); if (rc) return rc;
-    return loss_workspace(t, target, ld_target, mem, RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y);
+    return loss_workspace(t, target, ld_target, wt, mem, RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y, d_weight);
 }
 
-hipError_t enqueue_loss_grad(rq_trajectory* t, rq_policy* pol, int start, const float* d_target, uint32_t ld_y, float* d_grad,
-                             float* d_loss) {
+// d_weight null: the unweighted kernels, as they were; else the weighted pair, wt's strides
+hipError_t enqueue_loss_grad(rq_trajectory* t, rq_policy* pol, int start, const float* d_target, uint32_t ld_y, const float* d_weight,
+                             const LossWeight& wt, float* d_grad, float* d_loss) {
     rq_env* env = t->env;
+    const float* hidden = start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr;
+    if (d_weight)
+        return rq::launch_policy_loss_grad_weighted(env->dev->stream, env->n, env->ld, t->length, pol->w_packed, pol->w_packed_grad,
+                                                    t->obs, t->done, hidden, pol->ld, start == RQ_GRAD_START_INITIAL, t->grad.saved,
+                                                    d_target, ld_y, d_weight, wt.ld, wt.steps, t->grad.partial, d_grad, d_loss);
     return rq::launch_policy_loss_grad(env->dev->stream, env->n, env->ld, t->length, pol->w_packed, pol->w_packed_grad, t->obs,
-                                       t->done, start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr, pol->ld,
-                                       start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y, t->grad.partial, d_grad,
-                                       d_loss, t->grad.live);
+                                       t->done, hidden, pol->ld, start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y,
+                                       t->grad.partial, d_grad, d_loss, t->grad.live);
 }
 
 // ---- the same for a policy bank (rq_trajectory_policies_loss_grad / _distill) ----
@@ -134,11 +170,11 @@ hipError_t enqueue_loss_grad(rq_trajectory* t, rq_policy* pol, int start, const 
 // pending reset applied - as rq_rollout_policies does -, then the workspace; n_losses: floats wanted behind the [P][2084]
 // gradients in t->grad.out.
 int bank_loss_check(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target, uint32_t ld_target,
-                    int start, int memory, const char* what) {
+                    const LossWeight& wt, int start, int memory, const char* what) {
     RQ_REQUIRE(bank->dev == t->env->dev, RQ_ERR_SHAPE_MISMATCH, std::string(what) + ": the policy bank lives on another device");
     RQ_REQUIRE(t->length > 0, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": the trajectory is empty");
     int rc = require_bank_native_rate(bank, what); if (rc) return rc;
-    rc = loss_check_call(t, target, ld_target, start, memory, what); if (rc) return rc;
+    rc = loss_check_call(t, target, ld_target, wt, start, memory, what); if (rc) return rc;
     rc = bank_check_ids(bank, policy_id, t->env->n); if (rc) return rc;
     if (start == RQ_GRAD_START_CURRENT)
         RQ_REQUIRE(bank->batch == t->env->n || bank->batch == 0 || bank->needs_reset, RQ_ERR_SHAPE_MISMATCH,
@@ -147,7 +183,8 @@ int bank_loss_check(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* poli
 }
 
 int bank_loss_begin(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target, uint32_t ld_target,
-                    int start, const CallMemory& mem, size_t n_losses, const float** d_target, uint32_t* ld_y) {
+                    const LossWeight& wt, int start, const CallMemory& mem, size_t n_losses, const float** d_target, uint32_t* ld_y,
+                    const float** d_weight) {
     rq_env* env = t->env;
     int rc = RQ_OK;
     if (start == RQ_GRAD_START_CURRENT) {
@@ -158,17 +195,24 @@ int bank_loss_begin(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* poli
     rc = bank_wave_lists(bank); if (rc) return rc;
     rc = bank_grad_images(bank); if (rc) return rc;
     if (start == RQ_GRAD_START_CURRENT) { rc = bank_apply_reset(bank); if (rc) return rc; }
-    return loss_workspace(t, target, ld_target, mem, (size_t)bank->n_policies * RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y);
+    return loss_workspace(t, target, ld_target, wt, mem, (size_t)bank->n_policies * RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y,
+                          d_weight);
 }
 
-hipError_t enqueue_bank_loss_grad(rq_trajectory* t, rq_policy_bank* bank, int start, const float* d_target, uint32_t ld_y, float* d_grad,
-                                  float* d_loss) {
+hipError_t enqueue_bank_loss_grad(rq_trajectory* t, rq_policy_bank* bank, int start, const float* d_target, uint32_t ld_y,
+                                  const float* d_weight, const LossWeight& wt, float* d_grad, float* d_loss) {
     rq_env* env = t->env;
+    const float* hidden = start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr;
+    if (d_weight)
+        return rq::launch_policy_loss_grad_weighted_bank(env->dev->stream, env->n, env->ld, t->length, bank->n_policies, bank->images,
+                                                         bank->gimages, bank->table, bank->waves, bank->waves + bank->n_policies + 1,
+                                                         t->obs, t->done, hidden, bank->ld, start == RQ_GRAD_START_INITIAL,
+                                                         t->grad.saved, d_target, ld_y, d_weight, wt.ld, wt.steps, t->grad.partial,
+                                                         d_grad, d_loss);
     return rq::launch_policy_loss_grad_bank(env->dev->stream, env->n, env->ld, t->length, bank->n_policies, bank->images, bank->gimages,
-                                            bank->table, bank->waves, bank->waves + bank->n_policies + 1, t->obs, t->done,
-                                            start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr, bank->ld,
-                                            start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y, t->grad.partial, d_grad,
-                                            d_loss);
+                                            bank->table, bank->waves, bank->waves + bank->n_policies + 1, t->obs, t->done, hidden,
+                                            bank->ld, start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y, t->grad.partial,
+                                            d_grad, d_loss);
 }
 
 bool adam_config_ok(const rq_adam_config& c) {
@@ -288,21 +332,34 @@ RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* pol, const
 }
 
 // ---------------------------------------------------------------------------- the update on the device ---
-RQ_API int rq_trajectory_policy_loss_grad(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start,
-                                          float* loss, float* grad_weights, int memory) {
+// Each call and its *_weighted sibling are one body: `wt` is kNoWeight or the sibling's weight, `what` the name in the messages.
+static int policy_loss_grad(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, const LossWeight& wt, int start,
+                            float* loss, float* grad_weights, int memory, const char* what) {
     RQ_REQUIRE(t && pol && loss && grad_weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = loss_check(t, pol, target, ld_target, start, memory, "rq_trajectory_policy_loss_grad"); if (rc) return rc;
+    int rc = loss_check(t, pol, target, ld_target, wt, start, memory, what); if (rc) return rc;
     rq_device* dev = t->env->dev;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     CallMemory mem(memory, dev->stream, dev->ordinal);
-    const float* d_target = nullptr; uint32_t ld_y = 0;
-    rc = loss_begin(t, pol, target, ld_target, start, mem, 1, &d_target, &ld_y); if (rc) return rc;
+    const float *d_target = nullptr, *d_weight = nullptr; uint32_t ld_y = 0;
+    rc = loss_begin(t, pol, target, ld_target, wt, start, mem, 1, &d_target, &ld_y, &d_weight); if (rc) return rc;
     float* d_grad = mem.out(grad_weights, RQ_POLICY_NUM_WEIGHTS, t->grad.out.get());
     float* d_loss = mem.out(loss, 1, t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS);
-    RQ_HIP(enqueue_loss_grad(t, pol, start, d_target, ld_y, d_grad, d_loss));
+    RQ_HIP(enqueue_loss_grad(t, pol, start, d_target, ld_y, d_weight, wt, d_grad, d_loss));
     t->grad.stamp(pol, t->length, start);          // the saved state is the forward's: a rq_trajectory_policy_backward may follow
     RQ_HIP(mem.finish());
     return RQ_OK;
+}
+
+RQ_API int rq_trajectory_policy_loss_grad(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, int start,
+                                          float* loss, float* grad_weights, int memory) {
+    return policy_loss_grad(t, pol, target, ld_target, kNoWeight, start, loss, grad_weights, memory, "rq_trajectory_policy_loss_grad");
+}
+
+RQ_API int rq_trajectory_policy_loss_grad_weighted(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target,
+                                                   const float* weight, uint32_t ld_weight, uint32_t weight_steps, int start,
+                                                   float* loss, float* grad_weights, int memory) {
+    return policy_loss_grad(t, pol, target, ld_target, LossWeight{true, weight, ld_weight, weight_steps}, start, loss, grad_weights,
+                            memory, "rq_trajectory_policy_loss_grad_weighted");
 }
 
 RQ_API int rq_optimizer_create(rq_policy* pol, const rq_adam_config* config, rq_optimizer** out) {
@@ -330,23 +387,23 @@ RQ_API int rq_optimizer_set_lr(rq_optimizer* opt, double lr) {
     return RQ_OK;
 }
 
-RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer* opt, const float* target, uint32_t ld_target,
-                                 int start, uint32_t n_updates, float* losses, int memory) {
+static int policy_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer* opt, const float* target, uint32_t ld_target,
+                          const LossWeight& wt, int start, uint32_t n_updates, float* losses, int memory, const char* what) {
     RQ_REQUIRE(t && pol && opt && losses, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(policy_registry(pol, 0) && opt->policy == pol, RQ_ERR_INVALID_ARGUMENT,
-               "rq_trajectory_distill: the optimizer was made for another policy");
+               std::string(what) + ": the optimizer was made for another policy");
     RQ_REQUIRE(n_updates > 0, RQ_ERR_INVALID_ARGUMENT, "n_updates must be positive");
-    int rc = loss_check(t, pol, target, ld_target, start, memory, "rq_trajectory_distill"); if (rc) return rc;
+    int rc = loss_check(t, pol, target, ld_target, wt, start, memory, what); if (rc) return rc;
     rq_device* dev = t->env->dev;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;          // (retires a resident executor: it holds the old operands)
     CallMemory mem(memory, dev->stream, dev->ordinal);
-    const float* d_target = nullptr; uint32_t ld_y = 0;
-    rc = loss_begin(t, pol, target, ld_target, start, mem, n_updates, &d_target, &ld_y); if (rc) return rc;
+    const float *d_target = nullptr, *d_weight = nullptr; uint32_t ld_y = 0;
+    rc = loss_begin(t, pol, target, ld_target, wt, start, mem, n_updates, &d_target, &ld_y, &d_weight); if (rc) return rc;
     float* d_losses = mem.out(losses, n_updates, t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS);
     hipError_t e = hipSuccess;
     uint32_t done_updates = 0;
     for (; done_updates < n_updates && e == hipSuccess; ++done_updates) {
-        e = enqueue_loss_grad(t, pol, start, d_target, ld_y, opt->grad, d_losses + done_updates);
+        e = enqueue_loss_grad(t, pol, start, d_target, ld_y, d_weight, wt, opt->grad, d_losses + done_updates);
         if (e == hipSuccess) e = rq::launch_adam_repack(dev->stream, opt->grad, pol->w_dev, opt->m, opt->v, opt->state, opt->table,
                                                         pol->w_packed, pol->w_packed_grad);
     }
@@ -361,20 +418,33 @@ RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer*
     return RQ_OK;
 }
 
+RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer* opt, const float* target, uint32_t ld_target,
+                                 int start, uint32_t n_updates, float* losses, int memory) {
+    return policy_distill(t, pol, opt, target, ld_target, kNoWeight, start, n_updates, losses, memory, "rq_trajectory_distill");
+}
+
+RQ_API int rq_trajectory_distill_weighted(rq_trajectory* t, rq_policy* pol, rq_optimizer* opt, const float* target, uint32_t ld_target,
+                                          const float* weight, uint32_t ld_weight, uint32_t weight_steps, int start,
+                                          uint32_t n_updates, float* losses, int memory) {
+    return policy_distill(t, pol, opt, target, ld_target, LossWeight{true, weight, ld_weight, weight_steps}, start, n_updates, losses,
+                          memory, "rq_trajectory_distill_weighted");
+}
+
 // ---------------------------------------------------------------------------- the update on the device, a bank at once ---
-RQ_API int rq_trajectory_policies_loss_grad(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target,
-                                            uint32_t ld_target, int start, float* loss, float* grad_weights, int memory) {
+static int policies_loss_grad(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target,
+                              uint32_t ld_target, const LossWeight& wt, int start, float* loss, float* grad_weights, int memory,
+                              const char* what) {
     RQ_REQUIRE(t && bank && policy_id && loss && grad_weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = bank_loss_check(t, bank, policy_id, target, ld_target, start, memory, "rq_trajectory_policies_loss_grad"); if (rc) return rc;
+    int rc = bank_loss_check(t, bank, policy_id, target, ld_target, wt, start, memory, what); if (rc) return rc;
     rq_device* dev = t->env->dev;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const size_t P = bank->n_policies, grad_floats = P * RQ_POLICY_NUM_WEIGHTS;
     CallMemory mem(memory, dev->stream, dev->ordinal);
-    const float* d_target = nullptr; uint32_t ld_y = 0;
-    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, start, mem, P, &d_target, &ld_y); if (rc) return rc;
+    const float *d_target = nullptr, *d_weight = nullptr; uint32_t ld_y = 0;
+    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, wt, start, mem, P, &d_target, &ld_y, &d_weight); if (rc) return rc;
     float* d_grad = mem.host() ? t->grad.out.get() : grad_weights;
     float* d_loss = mem.out(loss, P, t->grad.out.get() + grad_floats);
-    RQ_HIP(enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, d_grad, d_loss));
+    RQ_HIP(enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, d_weight, wt, d_grad, d_loss));
     // (t->grad.valid stays false: the saved state is no single policy's, rq_trajectory_policy_backward has nothing to follow)
     if (mem.host()) {
         // a policy that owns no wave has no gradient row on the device: the caller's row stays as it was (the losses: finish)
@@ -388,6 +458,19 @@ RQ_API int rq_trajectory_policies_loss_grad(rq_trajectory* t, rq_policy_bank* ba
     }
     RQ_HIP(mem.finish());
     return RQ_OK;
+}
+
+RQ_API int rq_trajectory_policies_loss_grad(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target,
+                                            uint32_t ld_target, int start, float* loss, float* grad_weights, int memory) {
+    return policies_loss_grad(t, bank, policy_id, target, ld_target, kNoWeight, start, loss, grad_weights, memory,
+                              "rq_trajectory_policies_loss_grad");
+}
+
+RQ_API int rq_trajectory_policies_loss_grad_weighted(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id,
+                                                     const float* target, uint32_t ld_target, const float* weight, uint32_t ld_weight,
+                                                     uint32_t weight_steps, int start, float* loss, float* grad_weights, int memory) {
+    return policies_loss_grad(t, bank, policy_id, target, ld_target, LossWeight{true, weight, ld_weight, weight_steps}, start, loss,
+                              grad_weights, memory, "rq_trajectory_policies_loss_grad_weighted");
 }
 
 RQ_API int rq_bank_optimizer_create(rq_policy_bank* bank, const rq_adam_config* config, uint32_t n_cfg, rq_bank_optimizer** out) {
@@ -422,30 +505,45 @@ RQ_API int rq_bank_optimizer_set_lr(rq_bank_optimizer* opt, const double* lr, ui
     return RQ_OK;
 }
 
-RQ_API int rq_trajectory_policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* opt, const uint32_t* policy_id,
-                                          const float* target, uint32_t ld_target, int start, uint32_t n_updates, float* losses,
-                                          int memory) {
+static int policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* opt, const uint32_t* policy_id,
+                            const float* target, uint32_t ld_target, const LossWeight& wt, int start, uint32_t n_updates,
+                            float* losses, int memory, const char* what) {
     RQ_REQUIRE(t && bank && opt && policy_id && losses, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(opt->bank == bank && opt->bank_uid == bank->uid, RQ_ERR_INVALID_ARGUMENT,
-               "rq_trajectory_policies_distill: the optimizer was made for another bank");
+               std::string(what) + ": the optimizer was made for another bank");
     RQ_REQUIRE(n_updates > 0, RQ_ERR_INVALID_ARGUMENT, "n_updates must be positive");
-    int rc = bank_loss_check(t, bank, policy_id, target, ld_target, start, memory, "rq_trajectory_policies_distill"); if (rc) return rc;
+    int rc = bank_loss_check(t, bank, policy_id, target, ld_target, wt, start, memory, what); if (rc) return rc;
     rq_device* dev = t->env->dev;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const size_t P = bank->n_policies, n_losses = (size_t)n_updates * P;
     CallMemory mem(memory, dev->stream, dev->ordinal);
-    const float* d_target = nullptr; uint32_t ld_y = 0;
-    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, start, mem, n_losses, &d_target, &ld_y); if (rc) return rc;
+    const float *d_target = nullptr, *d_weight = nullptr; uint32_t ld_y = 0;
+    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, wt, start, mem, n_losses, &d_target, &ld_y, &d_weight); if (rc) return rc;
     float* d_losses = mem.out(losses, n_losses, t->grad.out.get() + P * RQ_POLICY_NUM_WEIGHTS);
     hipError_t e = hipSuccess;
     for (uint32_t k = 0; k < n_updates && e == hipSuccess; ++k) {       // back to back: nothing waits in between
-        e = enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, opt->grad, d_losses + (size_t)k * P);
+        e = enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, d_weight, wt, opt->grad, d_losses + (size_t)k * P);
         if (e == hipSuccess) e = rq::launch_adam_repack_bank(dev->stream, bank->n_policies, bank->waves, opt->grad, bank->weights, opt->m,
                                                              opt->v, opt->state, opt->table, bank->images, bank->gimages);
     }
     RQ_HIP(e);
     RQ_HIP(mem.finish());
     return RQ_OK;
+}
+
+RQ_API int rq_trajectory_policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* opt, const uint32_t* policy_id,
+                                          const float* target, uint32_t ld_target, int start, uint32_t n_updates, float* losses,
+                                          int memory) {
+    return policies_distill(t, bank, opt, policy_id, target, ld_target, kNoWeight, start, n_updates, losses, memory,
+                            "rq_trajectory_policies_distill");
+}
+
+RQ_API int rq_trajectory_policies_distill_weighted(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* opt,
+                                                   const uint32_t* policy_id, const float* target, uint32_t ld_target,
+                                                   const float* weight, uint32_t ld_weight, uint32_t weight_steps, int start,
+                                                   uint32_t n_updates, float* losses, int memory) {
+    return policies_distill(t, bank, opt, policy_id, target, ld_target, LossWeight{true, weight, ld_weight, weight_steps}, start,
+                            n_updates, losses, memory, "rq_trajectory_policies_distill_weighted");
 }
 
 }  // extern "C"

@@ -17,6 +17,10 @@
 //   k_policy_loss_reduce_bank          per policy: its waves' partials in ascending wave order (a CSR list), x 2 / M_p; loss_p
 //   k_adam_repack_bank                 one workgroup per policy: k_adam_repack on slot p; a policy without a wave is skipped whole
 //   k_adam_set_lr_bank                 [P] learning rates in stream order
+// The same two updates with a weight per env, or per env and step, in the loss (hold-out masks, teacher quality, emphasis by episode age):
+//   k_policy_loss_backward_weighted[_bank]   dL/da = w (a - y) where the entry is live and w > 0; + per wave the weighted squared
+//                                            error and, in float64, the sum of the counting weights
+//   k_policy_loss_reduce_weighted[_bank]     the reductions above with W4 = that sum over the waves, in wave order, in M's place
 // The forwards and the backwards are one text each (rq_grad_forward.inc, rq_grad_backward.inc), compiled once per kernel.
 //
 // Layouts (rq_device_math.hpp "actor"): a wave owns 64 envs as 4 tiles of 16; lane (q, j) = (l >> 4, l & 15) holds, in the Q
@@ -82,6 +86,13 @@ __device__ __forceinline__ float sigm2(float x) { return __builtin_amdgcn_rcpf(1
 #define RQ_GRAD_BANK 0
 #include "rq_grad_backward.inc"
 
+// the same with a weight per env, or per env and step, on every entry of the loss (rq_grad_backward.inc, RQ_GRAD_WEIGHTED)
+#define RQ_GRAD_BACKWARD_KERNEL k_policy_loss_backward_weighted
+#define RQ_GRAD_SEEDED 1
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_WEIGHTED 1
+#include "rq_grad_backward.inc"
+
 // grad[p] = sum over waves w = 0, 1, ... of partial[w][p], in that order
 __global__ __launch_bounds__(256) void k_policy_grad_reduce(uint32_t waves, const float* __restrict__ partial,
                                                             float* __restrict__ grad) {
@@ -125,6 +136,34 @@ __global__ __launch_bounds__(256) void k_policy_loss_reduce(uint32_t waves, cons
         for (uint32_t w = 0; w < waves; ++w) acc += wave_sse[w];
         loss[0] = M ? (float)((double)acc * inv) : 0.0f;
         live_out[0] = M;
+    }
+}
+
+// The weighted seeded backward's reduction: k_policy_loss_reduce with the normaliser W4 = the waves' wave_wsum added in ascending
+// wave order in float64 (every thread adds them itself, beside the partials it is walking anyway: one order, no exchange) in the
+// place of M: grad = sum x 2 / W4, the product in float64 and one rounding to fp32, loss = SSE / W4.  W4 = 0 (nothing counts): loss
+// and gradient 0.  With every weight 1.0f W4 is the integer M exactly, and the results are k_policy_loss_reduce's bits.
+__global__ __launch_bounds__(256) void k_policy_loss_reduce_weighted(uint32_t waves, const float* __restrict__ partial,
+                                                                    const float* __restrict__ wave_sse,
+                                                                    const double* __restrict__ wave_wsum, float* __restrict__ grad,
+                                                                    float* __restrict__ loss) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= RQ_POLICY_NUM_WEIGHTS) return;
+    float acc = 0.0f;
+    double W4 = 0.0;
+#pragma unroll 8
+    for (uint32_t w = 0; w < waves; ++w) {
+        acc += partial[(size_t)w * RQ_POLICY_NUM_WEIGHTS + p];
+        W4 += wave_wsum[w];
+    }
+    const bool any = W4 > 0.0;
+    const double inv = any ? 1.0 / W4 : 0.0;
+    grad[p] = any ? (float)((double)acc * (2.0 * inv)) : 0.0f;
+    if (p == 0) {
+        float sse = 0.0f;
+#pragma unroll 8
+        for (uint32_t w = 0; w < waves; ++w) sse += wave_sse[w];
+        loss[0] = any ? (float)((double)sse * inv) : 0.0f;
     }
 }
 
@@ -236,6 +275,26 @@ hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint3
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_policy_loss_reduce<<<(RQ_POLICY_NUM_WEIGHTS + 255) / 256, 256, 0, s>>>(waves, partial, wave_sse, wave_live, grad, loss, live);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_loss_grad_weighted(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
+                                            const float* gpacked, const float* obs, const uint8_t* done, const float* hidden,
+                                            uint32_t ld_h, int start_initial, float* saved, const float* target, uint32_t ld_y,
+                                            const float* weight, uint32_t ld_w, uint32_t weight_steps, float* partial, float* grad,
+                                            float* loss) {
+    if (weight == nullptr || ld_w < n || (weight_steps != 1 && weight_steps != steps)) return hipErrorInvalidValue;
+    const uint32_t si = start_initial ? 1u : 0u, waves = (n + 63) / 64;
+    hipError_t e = launch_policy_grad_forward_state(s, n, ld, steps, packed, obs, done, hidden, ld_h, start_initial, saved);
+    if (e != hipSuccess) return e;
+    // partial: [waves][2084] | wsum [waves] float64 (8 336 bytes per wave before it: aligned) | sse [waves]
+    double* wave_wsum = reinterpret_cast<double*>(partial + (size_t)waves * RQ_POLICY_NUM_WEIGHTS);
+    float* wave_sse = reinterpret_cast<float*>(wave_wsum + waves);
+    k_policy_loss_backward_weighted<<<waves, 64, 0, s>>>(n, ld, steps, packed, gpacked, obs, done, saved, target, ld_y, weight, ld_w,
+                                                         weight_steps == 1 ? 0u : ld_w, si, partial, wave_sse, wave_wsum);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    k_policy_loss_reduce_weighted<<<(RQ_POLICY_NUM_WEIGHTS + 255) / 256, 256, 0, s>>>(waves, partial, wave_sse, wave_wsum, grad, loss);
     return hipGetLastError();
 }
 

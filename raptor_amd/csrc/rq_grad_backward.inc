@@ -4,7 +4,9 @@
 //                            1: it is formed here from the masked squared error against a target (k_policy_loss_backward)
 //   RQ_GRAD_BANK             1: both images are those of the wave's policy, images + block_policy[blockIdx.x] * image_floats and
 //                            gimages + block_policy[blockIdx.x] * gimage_floats (k_policy_loss_backward_bank); 0: `packed`, `gpacked`
-// One text for both, and each a kernel of its own rather than a call into a shared function: the existing kernel's listing stays
+//   RQ_GRAD_WEIGHTED         with RQ_GRAD_SEEDED 1 only; 1: every entry carries a weight w (k_policy_loss_backward_weighted, ..._bank),
+//                            below; 0 or not defined: none
+// One text for all, and each a kernel of its own rather than a call into a shared function: the existing kernel's listing stays
 // the parent build's to the instruction.
 //
 // RQ_GRAD_SEEDED: `target` y [steps][4][ld_y].  From the recomputed h' the action is the forward's own layer_2 (ActorF32T::run): the
@@ -14,6 +16,19 @@
 // multiplied, so NaN in the targets or in the observations of frozen steps goes nowhere.  The 2 / M of the mean is applied once, by
 // the reduction.  Beside its partials the wave leaves its squared error (lane-local sums, folded lane 0 .. 63) and its count of
 // live entries in wave_sse / wave_live [gridDim.x].
+//
+// RQ_GRAD_WEIGHTED: `weight` w [1 or steps][ld_w], env i of step s at weight[s * w_step + i] (w_step = 0: one weight per env for
+// every step; ld_w: one per env and step).  An entry COUNTS where it is live and w > 0 - a weight that is 0, negative or NaN drops it,
+// selected like the frozen steps, so NaN in its target goes nowhere either.  On a counting entry e = a - y, dL/da = fl(w e) before the
+// 2 / W4 of the reduction, and its squared error is fl(fl(w e) e): with w = 1.0f both are the unweighted kernel's bits.  In place of
+// the live count the wave leaves W4's share, the sum of w over its counting entries (so each env-step's weight four times): per lane
+// in float64 in the order the lane walks its entries, the lanes folded 0 .. 63 in float64, in wave_wsum [gridDim.x].
+#ifndef RQ_GRAD_WEIGHTED
+#define RQ_GRAD_WEIGHTED 0
+#endif
+#if RQ_GRAD_WEIGHTED && !RQ_GRAD_SEEDED
+#error "RQ_GRAD_WEIGHTED weights the loss seed: it needs RQ_GRAD_SEEDED 1"
+#endif
 __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
         uint32_t n, uint32_t ld, uint32_t steps,
 #if RQ_GRAD_BANK
@@ -24,12 +39,22 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
 #endif
         const float* __restrict__ obs, const uint8_t* __restrict__ done, const float* __restrict__ saved,
 #if RQ_GRAD_SEEDED
-        const float* __restrict__ target, uint32_t ld_y, uint32_t start_initial, float* __restrict__ partial,
+        const float* __restrict__ target, uint32_t ld_y,
+#if RQ_GRAD_WEIGHTED
+        const float* __restrict__ weight, uint32_t ld_w, uint32_t w_step,
+#endif
+        uint32_t start_initial, float* __restrict__ partial,
+#if RQ_GRAD_WEIGHTED
+        float* __restrict__ wave_sse, double* __restrict__ wave_wsum) {
+    __shared__ double wfold[64];
+    double wsum = 0.0;                  // this lane's weights of counting entries
+#else
         float* __restrict__ wave_sse, uint32_t* __restrict__ wave_live) {
+    uint32_t live_entries = 0;          // the wave's live entries
+#endif
     float* const gh_start = nullptr;
     __shared__ float red[16 * 17];      // row = env of the tile, column 4 q + i = p_i of lane group q
     float sse = 0.0f;                   // this lane's squared errors
-    uint32_t live_entries = 0;          // the wave's live entries
 #else
         const float* __restrict__ gact, uint32_t ld_g, uint32_t start_initial, float* __restrict__ gh_start,
         float* __restrict__ partial) {
@@ -80,6 +105,12 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
             const float daB = ev ? gact[((size_t)s * 4 + q) * ld_g + e] : 0.0f;   // lane (q, j): dL/da_q of env (t, j)
 #endif
             const uint8_t d = done[(size_t)s * ld + ec];
+#if RQ_GRAD_WEIGHTED
+            // the entry's label and weight, asked for here so that the recompute hides the wait; both arrays hold every env's column
+            // of every step (e < n <= ld_y, ld_w), what they hold where the entry does not count is selected away below
+            const float y_in = ev ? target[((size_t)s * 4 + q) * ld_y + e] : 0.0f;
+            const float w_in = ev ? weight[(size_t)s * w_step + e] : 0.0f;
+#endif
 
             // ---- recompute: layer_0, the gates' chains (bias, W_h h, W_i y0: the forward's order), the gates ----
             f32x4 y0 = mfma16(W[QW_L0], X[0], zero);
@@ -125,10 +156,19 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
             __syncthreads();
             const float a = (red[j * 17 + q] + red[j * 17 + 4 + q]) + (red[j * 17 + 8 + q] + red[j * 17 + 12 + q]);
             const bool live = ev && d != 4;
+#if RQ_GRAD_WEIGHTED
+            const float wt = live ? w_in : 0.0f;
+            const bool counts = wt > 0.0f;                       // false for 0, a negative weight and NaN
+            const float err = counts ? a - y_in : 0.0f;
+            const float daB = counts ? wt * err : 0.0f;          // lane (q, j): dL/da_q of env (t, j), before the 2 / W4
+            sse += daB * err;
+            wsum += counts ? (double)wt : 0.0;
+#else
             const float y = live ? target[((size_t)s * 4 + q) * ld_y + e] : 0.0f;
             const float daB = live ? a - y : 0.0f;               // lane (q, j): dL/da_q of env (t, j), before the 2 / M
             sse += daB * daB;
             live_entries += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live));
+#endif
 #endif
             // ---- the episode structure, backwards: an end feeds h0 and cuts the recurrence; a frozen step passes it on ----
             const bool ended = d == 1 || d == 2, frozen = d == 4;
@@ -286,15 +326,25 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
 #if RQ_GRAD_SEEDED
     __syncthreads();
     sums[lane] = sse;
+#if RQ_GRAD_WEIGHTED
+    wfold[lane] = wsum;
+#endif
     __syncthreads();
     if (lane == 0) {
         float acc = 0.0f;
         for (int l = 0; l < 64; ++l) acc += sums[l];
         wave_sse[blockIdx.x] = acc;
+#if RQ_GRAD_WEIGHTED
+        double wacc = 0.0;
+        for (int l = 0; l < 64; ++l) wacc += wfold[l];
+        wave_wsum[blockIdx.x] = wacc;
+#else
         wave_live[blockIdx.x] = live_entries;
+#endif
     }
 #endif
 }
 #undef RQ_GRAD_BACKWARD_KERNEL
 #undef RQ_GRAD_SEEDED
 #undef RQ_GRAD_BANK
+#undef RQ_GRAD_WEIGHTED

@@ -5,6 +5,8 @@
 //   k_policy_grad_forward_state_bank   k_policy_grad_forward_state, the wave's image picked per block      waves
 //   k_policy_loss_backward_bank        k_policy_loss_backward, both images picked per block                waves
 //   k_policy_loss_reduce_bank          policy p: its waves' partials in ascending wave order, x 2 / M_p    (ceil(2084 / 256), P)
+//   k_policy_loss_backward_weighted_bank   k_policy_loss_backward_weighted, both images picked per block   waves
+//   k_policy_loss_reduce_weighted_bank     policy p: as above with W4_p, its waves' float64 weight sums    (ceil(2084 / 256), P)
 //   k_adam_repack_bank                 k_adam_repack on slot p; a policy that owns no wave is skipped       P
 //   k_adam_set_lr_bank                 up to 256 learning rates, carried as kernel arguments                1
 // The weights are wave-uniform MFMA operands read once from an image pointer, so the seeded pair is the single policy's text
@@ -26,6 +28,12 @@ namespace rq {
 #define RQ_GRAD_BACKWARD_KERNEL k_policy_loss_backward_bank
 #define RQ_GRAD_SEEDED 1
 #define RQ_GRAD_BANK 1
+#include "rq_grad_backward.inc"
+
+#define RQ_GRAD_BACKWARD_KERNEL k_policy_loss_backward_weighted_bank
+#define RQ_GRAD_SEEDED 1
+#define RQ_GRAD_BANK 1
+#define RQ_GRAD_WEIGHTED 1
 #include "rq_grad_backward.inc"
 
 // k_policy_loss_reduce per policy (blockIdx.y): M_p = the live entries of p's waves (an integer sum), grad [p][:] = the partials of
@@ -63,6 +71,41 @@ __global__ __launch_bounds__(256) void k_policy_loss_reduce_bank(const uint32_t*
         float acc = 0.0f;
         for (uint32_t k = w0; k < w1; ++k) acc += wave_sse[wave_list[k]];
         loss[pol] = M ? (float)((double)acc * inv) : 0.0f;
+    }
+}
+
+// k_policy_loss_reduce_weighted per policy (blockIdx.y), as k_policy_loss_reduce_bank is k_policy_loss_reduce per policy: W4_p = the
+// wave_wsum of p's waves added in ascending wave order in float64, grad [p][:] = its waves' partials in that order x 2 / W4_p, loss
+// [p] = SSE_p / W4_p.  W4_p = 0 (none of p's entries counts): loss and gradient 0, and Adam sees a zero gradient.  A policy that owns
+// no wave: loss NaN, its gradient row is not written.
+__global__ __launch_bounds__(256) void k_policy_loss_reduce_weighted_bank(const uint32_t* __restrict__ wave_offsets,
+                                                                         const uint32_t* __restrict__ wave_list,
+                                                                         const float* __restrict__ partial,
+                                                                         const float* __restrict__ wave_sse,
+                                                                         const double* __restrict__ wave_wsum, float* __restrict__ grad,
+                                                                         float* __restrict__ loss) {
+    const uint32_t pol = blockIdx.y;
+    const uint32_t w0 = wave_offsets[pol], w1 = wave_offsets[pol + 1];
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (w0 == w1) {
+        if (p == 0) loss[pol] = __builtin_nanf("");
+        return;
+    }
+    if (p >= RQ_POLICY_NUM_WEIGHTS) return;
+    float acc = 0.0f;
+    double W4 = 0.0;
+    for (uint32_t k = w0; k < w1; ++k) {
+        const uint32_t w = wave_list[k];
+        acc += partial[(size_t)w * RQ_POLICY_NUM_WEIGHTS + p];
+        W4 += wave_wsum[w];
+    }
+    const bool any = W4 > 0.0;
+    const double inv = any ? 1.0 / W4 : 0.0;
+    grad[(size_t)pol * RQ_POLICY_NUM_WEIGHTS + p] = any ? (float)((double)acc * (2.0 * inv)) : 0.0f;
+    if (p == 0) {
+        float sse = 0.0f;
+        for (uint32_t k = w0; k < w1; ++k) sse += wave_sse[wave_list[k]];
+        loss[pol] = any ? (float)((double)sse * inv) : 0.0f;
     }
 }
 
@@ -149,6 +192,36 @@ hipError_t launch_policy_loss_grad_bank(hipStream_t s, uint32_t n, uint32_t ld, 
     if (e != hipSuccess) return e;
     k_policy_loss_reduce_bank<<<dim3((RQ_POLICY_NUM_WEIGHTS + 255) / 256, n_policies), 256, 0, s>>>(wave_offsets, wave_list, partial,
                                                                                                    wave_sse, wave_live, grad, loss);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_loss_grad_weighted_bank(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, uint32_t n_policies,
+                                                 const float* images, const float* gimages, const uint32_t* block_policy,
+                                                 const uint32_t* wave_offsets, const uint32_t* wave_list, const float* obs,
+                                                 const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial, float* saved,
+                                                 const float* target, uint32_t ld_y, const float* weight, uint32_t ld_w,
+                                                 uint32_t weight_steps, float* partial, float* grad, float* loss) {
+    if (n == 0 || steps == 0 || n_policies == 0) return hipErrorInvalidValue;
+    if (weight == nullptr || ld_w < n || (weight_steps != 1 && weight_steps != steps)) return hipErrorInvalidValue;
+    const unsigned g = (n + kFusedBlock - 1) / kFusedBlock;
+    const uint32_t si = start_initial ? 1u : 0u, waves = (n + 63) / 64;
+    if (n > kOneWavePerSimdEnvs)        // launch_policy_loss_grad_bank's choice of build
+        k_policy_grad_forward_state_bank<ActorF32Lean><<<g, kFusedBlock, 0, s>>>(n, ld, steps, images, block_policy,
+                                                                                 (uint32_t)RQ_PACKED_FLOATS, obs, done, hidden, ld_h, si, saved);
+    else
+        k_policy_grad_forward_state_bank<ActorF32><<<g, kFusedBlock, 0, s>>>(n, ld, steps, images, block_policy,
+                                                                             (uint32_t)RQ_PACKED_FLOATS, obs, done, hidden, ld_h, si, saved);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    double* wave_wsum = reinterpret_cast<double*>(partial + (size_t)waves * RQ_POLICY_NUM_WEIGHTS);   // launch_policy_loss_grad_weighted's layout
+    float* wave_sse = reinterpret_cast<float*>(wave_wsum + waves);
+    k_policy_loss_backward_weighted_bank<<<waves, 64, 0, s>>>(n, ld, steps, images, gimages, block_policy, (uint32_t)RQ_PACKED_FLOATS,
+                                                              (uint32_t)RQ_PACKED_GRAD_FLOATS, obs, done, saved, target, ld_y, weight, ld_w,
+                                                              weight_steps == 1 ? 0u : ld_w, si, partial, wave_sse, wave_wsum);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    k_policy_loss_reduce_weighted_bank<<<dim3((RQ_POLICY_NUM_WEIGHTS + 255) / 256, n_policies), 256, 0, s>>>(
+        wave_offsets, wave_list, partial, wave_sse, wave_wsum, grad, loss);
     return hipGetLastError();
 }
 

@@ -242,6 +242,17 @@ hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint3
                                    const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial,
                                    float* saved, const float* target, uint32_t ld_y, float* partial, float* grad, float* loss,
                                    unsigned long long* live);
+// The same with a weight on every entry of the loss (rq_grad_backward.inc, RQ_GRAD_WEIGHTED): weight [weight_steps][ld_w], weight_steps
+// = 1 (per env) or steps (per env and step), ld_w >= n.  An entry counts where it is live and its weight > 0; loss = sum w (a - y)^2 /
+// W4, W4 = the sum of w over the counting entries in float64, grad its gradient; W4 = 0 gives loss 0 and a zero gradient.  Weights of
+// 1.0f give launch_policy_loss_grad's bits.  partial: [waves][2084] floats, a float64 and a float per wave
+// (policy_loss_weighted_partial_floats).
+constexpr size_t policy_loss_weighted_partial_floats(uint32_t n) { return (size_t)((n + 63) / 64) * (RQ_POLICY_NUM_WEIGHTS + 3); }
+hipError_t launch_policy_loss_grad_weighted(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
+                                            const float* gpacked, const float* obs, const uint8_t* done, const float* hidden,
+                                            uint32_t ld_h, int start_initial, float* saved, const float* target, uint32_t ld_y,
+                                            const float* weight, uint32_t ld_w, uint32_t weight_steps, float* partial, float* grad,
+                                            float* loss);
 // Adam's state on the device: hyper-parameters, the step count t and the running powers beta^t (1 before the first step)
 struct AdamState { double lr, beta1, beta2, eps, weight_decay, beta1_t, beta2_t; uint32_t step, pad; };
 // one element of an operand image as a function of the flat weights: 0 (a == PACK_GATHER_NONE), k w[a], or k (w[a] + w[b])
@@ -263,6 +274,13 @@ hipError_t launch_policy_loss_grad_bank(hipStream_t s, uint32_t n, uint32_t ld, 
                                         const uint32_t* wave_list, const float* obs, const uint8_t* done, const float* hidden,
                                         uint32_t ld_h, int start_initial, float* saved, const float* target, uint32_t ld_y,
                                         float* partial, float* grad, float* loss);
+// (the bank's weighted form: launch_policy_loss_grad_weighted per policy, W4_p over its own blocks; partial as there)
+hipError_t launch_policy_loss_grad_weighted_bank(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, uint32_t n_policies,
+                                                 const float* images, const float* gimages, const uint32_t* block_policy,
+                                                 const uint32_t* wave_offsets, const uint32_t* wave_list, const float* obs,
+                                                 const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial, float* saved,
+                                                 const float* target, uint32_t ld_y, const float* weight, uint32_t ld_w,
+                                                 uint32_t weight_steps, float* partial, float* grad, float* loss);
 hipError_t launch_adam_repack_bank(hipStream_t s, uint32_t n_policies, const uint32_t* wave_offsets, const float* grad, float* w, float* m,
                                    float* v, AdamState* st, const PackGather* table, float* images, float* gimages);
 hipError_t launch_adam_set_lr_bank(hipStream_t s, AdamState* st, uint32_t n_policies, const double* lr, uint32_t n_lr);

@@ -16,7 +16,13 @@ For the distillation loss itself - the masked MSE against the labels - the whole
     losses = distiller.step(traj, updates=10)               # 10 x (forward, loss-seeded backward, Adam, repack), one enqueue
     loss, grad = distiller.loss_and_grad(traj)              # the same loss and its gradient, no update
 
-Any other loss goes the first way.
+Entries can be weighted, per env or per env and step, without leaving that path (rq_trajectory_*_weighted):
+
+    train, held_out = holdout_weights(N, 0.1, seed=0)       # two 0/1 masks over the envs
+    distiller.step(traj, weight=train, updates=10)          # trains on nine tenths of the recording
+    val, _ = distiller.loss_and_grad(traj, weight=held_out) # the loss on the rest: a validation loss, no second recording
+
+``weighted_mse`` is the same loss in torch, for the first way; any loss beyond that goes the first way too.
 
 A sweep or a seed population is distilled in one go: ``BankDistiller`` runs that update for every policy of a
 ``policy_bank.PolicyBank`` at once, each on the 64-env blocks of the recording that ``policy_ids`` deals it, with its own
@@ -70,6 +76,80 @@ def masked_mse(act, target, live):
     a = torch.where(live, act, zero)
     t = torch.where(live, target, zero)
     return ((a - t) ** 2).sum() / live.sum()
+
+
+def weighted_mse(act, target, live, weight):
+    """``masked_mse`` with a weight on every entry: sum(w (act - target)^2) / sum(w) over the entries that COUNT - ``live`` and
+    ``weight > 0`` - the loss of ``Distiller.step(..., weight=...)`` stated in torch.  ``weight`` broadcasts against ``act``
+    (``w[None, None, :]`` for one weight per env of a [T, 4, N] tensor, ``w[:, None, :]`` for one per step and env).
+
+    As in ``masked_mse`` the selection is applied to the INPUTS: where an entry does not count - a frozen step, a weight that is 0,
+    negative or NaN - act, target and weight are replaced by 0 before any arithmetic, so NaN there goes nowhere, in the loss or in
+    its gradient.  Nothing counts: 0, with a zero gradient."""
+    import torch
+    zero = torch.zeros((), dtype=act.dtype, device=act.device)
+    w = torch.broadcast_to(weight.to(act.dtype), act.shape)
+    counts = live & (w > 0)
+    a = torch.where(counts, act, zero)
+    t = torch.where(counts, target, zero)
+    w = torch.where(counts, w, zero)
+    total = w.sum()
+    return (w * (a - t) ** 2).sum() / torch.where(total > 0, total, torch.ones_like(total))
+
+
+def holdout_weights(n_envs, fraction, seed):
+    """-> (train, held_out): two complementary float32 [n_envs] arrays of 0 and 1 for ``weight=``; exactly
+    ``round(fraction * n_envs)`` envs, drawn without replacement, are held out.  A pure function of its arguments
+    (``numpy.random.default_rng(seed)``'s permutation): the same split every epoch and every run."""
+    n_envs = int(n_envs)
+    if n_envs < 0 or not 0.0 <= fraction <= 1.0:
+        raise ValueError("n_envs must be non-negative and fraction in [0, 1]")
+    held = np.zeros(n_envs, np.float32)
+    held[np.random.default_rng(seed).permutation(n_envs)[:int(round(fraction * n_envs))]] = 1.0
+    return (1.0 - held).astype(np.float32), held
+
+
+def _loss_weight(traj, weight):
+    """The refusals Python makes itself for ``weight=``, before the library does anything for the call -> (w, ld_weight,
+    weight_steps): ``w`` a contiguous float32 NumPy array or device tensor, [weight_steps, ld_weight]."""
+    what = "weight must be float32, [>= N] (one per env) or [1 or T, >= N] (one per step and env)"
+    tensor = hasattr(weight, "data_ptr")
+    if tensor:
+        import torch
+        if weight.dtype != torch.float32 or weight.dim() not in (1, 2):
+            raise ValueError(f"{what}, not {weight.dtype} {tuple(weight.shape)}")
+        if not weight.is_cuda:
+            raise ValueError("a tensor weight must live on the trajectory's device (a host weight is passed as a NumPy array)")
+        w = weight.contiguous()
+    else:
+        w = np.asarray(weight)
+        if w.dtype != np.float32 or w.ndim not in (1, 2):
+            raise ValueError(f"{what}, not {w.dtype} {w.shape}")
+        w = np.ascontiguousarray(w)
+    w = w.reshape(1, -1) if len(w.shape) == 1 else w
+    N = int(traj._env.N_ENVIRONMENTS)
+    if w.shape[1] < N:
+        raise ValueError(f"{what}: {w.shape[1]} columns for {N} envs")
+    if not tensor:
+        cols = w[:, :N]
+        if not np.isfinite(cols).all() or (cols < 0).any():
+            s, i = np.argwhere(~(np.isfinite(cols) & (cols >= 0)))[0]
+            raise ValueError(f"weight must be finite and non-negative: step {s}, env {i} holds {cols[s, i]}")
+    if w.shape[0] != 1 and w.shape[0] != len(traj):
+        raise ValueError(f"{what}: {w.shape[0]} rows for a trajectory of {len(traj)} steps")
+    return w, int(w.shape[1]), int(w.shape[0])
+
+
+def _weight_pointer(w, dev):
+    """a checked weight where the call wants it - device memory of ``dev``, or the host for ``dev`` None -> (pointer, keep-alive)"""
+    tensor = hasattr(w, "data_ptr")
+    if dev is None:
+        w = w.cpu().numpy() if tensor else w
+        return C.c_void_p(w.ctypes.data), w
+    if not tensor:
+        import torch
+        w = torch.from_numpy(w).to(dev)            # a hold-out mask need not be a tensor: uploaded here
+    return _device_ptr(w), w
 
 
 def _sync_weights(policy, weights):
@@ -127,14 +207,19 @@ class Distiller:
     back; no action or gradient tensor the size of the recording exists, and the weights do not visit the host).
 
     The loss is ``masked_mse(trajectory_actions(traj, policy, w)[:, :, :N], target[:, :, :N], live)`` with ``live`` = done code
-    != 4: a loss other than this masked MSE still goes through ``trajectory_actions`` and torch.  The update is
+    != 4: a loss other than this (weighted) masked MSE still goes through ``trajectory_actions`` and torch.  The update is
     ``torch.optim.Adam``'s with these hyper-parameters (``weight_decay`` decoupled as in ``AdamW``; 0 = none).  ``policy`` must be
     the fp32 policy without Standardize / SampleAndSquash stages; its weights are updated in place - the next rollout, relabel or
     ``evaluate_step`` runs the updated policy, ``policy.weights`` fetches them when first read.
 
     ``target``: None - the trajectory's own stored actions (what ``relabel_teachers(..., overwrite=True)`` or a teacher-acting
     rollout left there) - or a [T, 4, ld_target] float32 array with ld_target >= N: a torch tensor on the trajectory's device, or
-    (``loss_and_grad`` only needs it) a NumPy array.  ``start`` as in ``trajectory_actions``."""
+    (``loss_and_grad`` only needs it) a NumPy array.  ``start`` as in ``trajectory_actions``.
+
+    ``weight``: None - every live entry counts the same, the calls above - or float32 weights, [>= N] (one per env) or [1 or T,
+    >= N] (one per step and env), NumPy or a tensor on the trajectory's device: the loss becomes ``weighted_mse`` - sum(w (a - y)^2)
+    / sum(w) over the live entries with w > 0; a weight of 0 drops its entries, NaN in their targets included
+    (rq_trajectory_distill_weighted).  A NumPy weight must be finite and non-negative; beside a device target it is uploaded."""
 
     def __init__(self, policy, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         self.policy = policy
@@ -142,6 +227,7 @@ class Distiller:
         self._h = None
         self._fin = None
         self._target_in_flight = None      # the target an enqueued-only step may still be reading (a contiguous copy, perhaps)
+        self._weight_in_flight = None      # and the weight (an uploaded copy, perhaps)
 
     def _handle(self, traj):
         pol = self.policy._handle(traj._env._device)
@@ -185,30 +271,33 @@ class Distiller:
             return None
         return traj.tensors()["act"].device
 
-    def loss_and_grad(self, traj, target=None, start="initial"):
+    def loss_and_grad(self, traj, target=None, start="initial", weight=None):
         """-> (loss, dloss/dweights [2084]): device tensors when torch is present, NumPy otherwise (or with a NumPy target)."""
         if start not in START:
             raise ValueError('start must be "initial" or "current"')
+        w = None if weight is None else _loss_weight(traj, weight)
         ptr, ld_t, on_device, keep = self._target(traj, target)
         pol = self.policy._handle(traj._env._device)
         dev = self._torch_device(traj) if on_device is not False else None
         traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1      # the trajectory's saved state is this call's now
+        name, wargs = "rq_trajectory_policy_loss_grad", ()
+        if w is not None:
+            wptr, wkeep = _weight_pointer(w[0], dev)
+            name, wargs = name + "_weighted", (wptr, w[1], w[2])
         if dev is None:
             loss, grad = np.empty(1, np.float32), np.empty(_lib.POLICY_NUM_WEIGHTS, np.float32)
             if on_device:
                 raise ValueError("a device target needs torch")
-            _lib.call("rq_trajectory_policy_loss_grad", traj._require("trajectory"), pol, ptr, ld_t, START[start],
-                      _lib.fptr(loss), _lib.fptr(grad), 0)
+            _lib.call(name, traj._require("trajectory"), pol, ptr, ld_t, *wargs, START[start], _lib.fptr(loss), _lib.fptr(grad), 0)
             return loss[0], grad
         import torch
         loss = torch.empty((), dtype=torch.float32, device=dev)
         grad = torch.empty(_lib.POLICY_NUM_WEIGHTS, dtype=torch.float32, device=dev)
         torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
-        _lib.call("rq_trajectory_policy_loss_grad", traj._require("trajectory"), pol, ptr, ld_t, START[start],
-                  _device_ptr(loss), _device_ptr(grad), 1)
+        _lib.call(name, traj._require("trajectory"), pol, ptr, ld_t, *wargs, START[start], _device_ptr(loss), _device_ptr(grad), 1)
         return loss, grad
 
-    def step(self, traj, target=None, start="initial", updates=1, wait=True):
+    def step(self, traj, target=None, start="initial", updates=1, wait=True, weight=None):
         """``updates`` Adam steps on the recording, enqueued in one call -> the loss before each of them, [updates] (a device
         tensor when torch is present, NumPy otherwise).  ``wait=False`` (torch only) returns once the work is enqueued on the
         engine's stream: what the engine is asked to do next is ordered behind it; read the losses after ``device.synchronize()``."""
@@ -217,21 +306,28 @@ class Distiller:
         updates = int(updates)
         if updates < 1:
             raise ValueError("updates must be at least 1")
+        w = None if weight is None else _loss_weight(traj, weight)
         ptr, ld_t, on_device, keep = self._target(traj, target)
         pol, opt = self._handle(traj)
         dev = self._torch_device(traj)
+        if on_device is False:
+            dev = None
         traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
-        if dev is None or on_device is False:
+        name, wargs, wkeep = "rq_trajectory_distill", (), None
+        if w is not None:
+            wptr, wkeep = _weight_pointer(w[0], dev)
+            name, wargs = name + "_weighted", (wptr, w[1], w[2])
+        if dev is None:
             losses = np.empty(updates, np.float32)
-            _lib.call("rq_trajectory_distill", traj._require("trajectory"), pol, opt, ptr, ld_t, START[start], updates,
-                      _lib.fptr(losses), 0)
+            _lib.call(name, traj._require("trajectory"), pol, opt, ptr, ld_t, *wargs, START[start], updates, _lib.fptr(losses), 0)
         else:
             import torch
             losses = torch.empty(updates, dtype=torch.float32, device=dev)
             torch.cuda.current_stream(dev).synchronize()      # once per call, not per update
-            _lib.call("rq_trajectory_distill", traj._require("trajectory"), pol, opt, ptr, ld_t, START[start], updates,
-                      _device_ptr(losses), 1 if wait else 2)
+            _lib.call(name, traj._require("trajectory"), pol, opt, ptr, ld_t, *wargs, START[start], updates, _device_ptr(losses),
+                      1 if wait else 2)
         self._target_in_flight = keep      # until the next step: with wait=False the engine's stream may not have read it yet
+        self._weight_in_flight = wkeep
         self.policy._weights_on_device = True
         return losses
 
@@ -254,8 +350,9 @@ class BankDistiller:
     recording of its blocks; the cost is one student's launches.  The bank's weights are updated in place on the device: its next
     rollout flies them, ``bank.weights`` fetches them when first read.  A policy that owns no block is left alone (loss NaN).
 
-    ``policy_ids``: one id per env of the trajectory, constant on every aligned block of 64 (``check_policy_ids``).  ``target``
-    and ``start`` as for ``Distiller``; ``start="current"`` reads the bank's hidden state."""
+    ``policy_ids``: one id per env of the trajectory, constant on every aligned block of 64 (``check_policy_ids``).  ``target``,
+    ``start`` and ``weight`` as for ``Distiller``; ``start="current"`` reads the bank's hidden state.  With a ``weight`` policy p's
+    loss is normalised by the weights of ITS blocks; a policy none of whose entries counts gets loss 0 and a zero gradient."""
 
     def __init__(self, bank, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         P = int(bank.n_policies)
@@ -268,6 +365,7 @@ class BankDistiller:
         self._h = None
         self._fin = None
         self._target_in_flight = None
+        self._weight_in_flight = None
 
     def _handle(self):
         if self._h is None:
@@ -296,49 +394,62 @@ class BankDistiller:
             raise ValueError("updates must be at least 1")
         return check_policy_ids(policy_ids, self.bank.n_policies, traj._env.N_ENVIRONMENTS), updates
 
-    def loss_and_grad(self, traj, policy_ids, target=None, start="initial"):
+    def loss_and_grad(self, traj, policy_ids, target=None, start="initial", weight=None):
         """-> (loss [P], dloss/dweights [P, 2084]), every policy's over its own blocks; no update.  Device tensors when torch is
         present, NumPy otherwise (or with a NumPy target).  A policy that owns no block: loss NaN, its gradient row zero."""
         ids, _ = self._check(traj, policy_ids, start)
         P = int(self.bank.n_policies)
+        w = None if weight is None else _loss_weight(traj, weight)
         ptr, ld_t, on_device, keep = Distiller._target(traj, target)
         dev = Distiller._torch_device(traj) if on_device is not False else None
         traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
+        name, wargs = "rq_trajectory_policies_loss_grad", ()
+        if w is not None:
+            wptr, wkeep = _weight_pointer(w[0], dev)
+            name, wargs = name + "_weighted", (wptr, w[1], w[2])
         if dev is None:
             if on_device:
                 raise ValueError("a device target needs torch")
             loss, grad = np.empty(P, np.float32), np.zeros((P, _lib.POLICY_NUM_WEIGHTS), np.float32)
-            _lib.call("rq_trajectory_policies_loss_grad", traj._require("trajectory"), self.bank._h, ids.ctypes.data, ptr, ld_t,
-                      START[start], _lib.fptr(loss), _lib.fptr(grad), 0)
+            _lib.call(name, traj._require("trajectory"), self.bank._h, ids.ctypes.data, ptr, ld_t, *wargs, START[start],
+                      _lib.fptr(loss), _lib.fptr(grad), 0)
             return loss, grad
         import torch
         loss = torch.empty(P, dtype=torch.float32, device=dev)
         grad = torch.zeros((P, _lib.POLICY_NUM_WEIGHTS), dtype=torch.float32, device=dev)
         torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
-        _lib.call("rq_trajectory_policies_loss_grad", traj._require("trajectory"), self.bank._h, ids.ctypes.data, ptr, ld_t,
-                  START[start], _device_ptr(loss), _device_ptr(grad), 1)
+        _lib.call(name, traj._require("trajectory"), self.bank._h, ids.ctypes.data, ptr, ld_t, *wargs, START[start],
+                  _device_ptr(loss), _device_ptr(grad), 1)
         return loss, grad
 
-    def step(self, traj, policy_ids, target=None, start="initial", updates=1, wait=True):
+    def step(self, traj, policy_ids, target=None, start="initial", updates=1, wait=True, weight=None):
         """``updates`` Adam steps of every policy on its blocks of the recording, enqueued in one call -> the losses before each
         of them, [updates, P] (a device tensor when torch is present, NumPy otherwise).  ``wait=False`` (torch only) returns once
         the work is enqueued on the engine's stream: a rollout of the bank asked for next flies the updated weights."""
         ids, updates = self._check(traj, policy_ids, start, updates)
         P = int(self.bank.n_policies)
+        w = None if weight is None else _loss_weight(traj, weight)
         ptr, ld_t, on_device, keep = Distiller._target(traj, target)
         opt = self._handle()
         dev = Distiller._torch_device(traj)
+        if on_device is False:
+            dev = None
         traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
-        if dev is None or on_device is False:
+        name, wargs, wkeep = "rq_trajectory_policies_distill", (), None
+        if w is not None:
+            wptr, wkeep = _weight_pointer(w[0], dev)
+            name, wargs = name + "_weighted", (wptr, w[1], w[2])
+        if dev is None:
             losses = np.empty((updates, P), np.float32)
-            _lib.call("rq_trajectory_policies_distill", traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, ptr, ld_t,
-                      START[start], updates, _lib.fptr(losses), 0)
+            _lib.call(name, traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, ptr, ld_t, *wargs, START[start], updates,
+                      _lib.fptr(losses), 0)
         else:
             import torch
             losses = torch.empty((updates, P), dtype=torch.float32, device=dev)
             torch.cuda.current_stream(dev).synchronize()      # once per call, not per update
-            _lib.call("rq_trajectory_policies_distill", traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, ptr, ld_t,
-                      START[start], updates, _device_ptr(losses), 1 if wait else 2)
+            _lib.call(name, traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, ptr, ld_t, *wargs, START[start], updates,
+                      _device_ptr(losses), 1 if wait else 2)
         self._target_in_flight = keep      # until the next step: with wait=False the engine's stream may not have read it yet
+        self._weight_in_flight = wkeep
         self.bank._weights_on_device = True
         return losses
