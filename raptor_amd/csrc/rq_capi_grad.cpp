@@ -34,8 +34,11 @@ int grad_saved_initial(rq_trajectory* t, rq_policy* pol) {
         return RQ_OK;
     t->grad.valid = false;
     RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)t->length * RQ_POLICY_HIDDEN_DIM * env->ld));
-    RQ_HIP(rq::launch_policy_grad_forward_state(dev->stream, env->n, env->ld, t->length, pol->w_packed, t->obs, t->done, nullptr, pol->ld,
-                                                1, t->grad.saved));
+    rq::LossLaunch a;
+    a.n = env->n; a.ld = env->ld; a.steps = t->length;
+    a.packed = pol->w_packed; a.obs = t->obs; a.done = t->done;
+    a.ld_h = pol->ld; a.start_initial = true; a.saved = t->grad.saved;
+    RQ_HIP(rq::launch_policy_grad_forward_state(dev->stream, a));
     t->grad.stamp(pol, t->length, RQ_GRAD_START_INITIAL);
     return RQ_OK;
 }
@@ -74,7 +77,8 @@ int ensure_grad_image(rq_policy* pol) {
 
 // What the two loss-seeded calls share.  loss_check: the refusals, before the call's DeviceScope (a refused call leaves the device,
 // a resident executor included, alone).  loss_begin, inside it: the workspace and the target on the device; n_losses: floats wanted
-// behind the gradient in t->grad.out.  -> d_target / ld_y as the kernel takes them.  loss_check_call and loss_workspace are the parts
+// behind the gradient in t->grad.out.  -> the launch (rq::LossLaunch) but for `grad` and `loss`, which the call sets - an update loop
+// per iteration - before it hands it to rq::launch_policy_loss_grad.  loss_check_call and loss_workspace are the parts
 // that do not ask whose weights they are: the bank's calls below share them.
 // The *_weighted calls are their siblings with a LossWeight that is `given`: the weight [steps][ld] as the caller named it.  It
 // travels like the target - a host array is copied in behind the target's staging, a device array is used where it lies.
@@ -117,51 +121,46 @@ int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t l
     return loss_check_call(t, target, ld_target, wt, start, memory, what);
 }
 
-// the workspace, the target and the weight on the device; out_floats: what t->grad.out is to hold (gradients, then losses).
-// -> *d_weight: the weight as the kernel takes it (null without one)
-int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, const LossWeight& wt, const CallMemory& mem,
-                   size_t out_floats, const float** d_target, uint32_t* ld_y, const float** d_weight) {
+// -> *a: the launch as far as it does not ask whose weights they are - the recording, the workspace reserved, the target and the
+// weight on the device (staged through `mem`), the strides.  out_floats: what t->grad.out is to hold (gradients, then losses).
+int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, const LossWeight& wt, int start, const CallMemory& mem,
+                   size_t out_floats, rq::LossLaunch* a) {
     rq_env* env = t->env;
     rq_device* dev = env->dev;
     const uint32_t T = t->length, ld = env->ld;
     t->grad.valid = false;
     RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld));
-    RQ_HIP(t->grad.partial.reserve(dev->stream, wt.given ? rq::policy_loss_weighted_partial_floats(env->n)
-                                                         : rq::policy_loss_partial_floats(env->n)));
+    RQ_HIP(t->grad.partial.reserve(dev->stream, rq::loss_partial_layout(env->n, wt.given).floats));
     RQ_HIP(t->grad.out.reserve(dev->stream, out_floats));
-    RQ_HIP(t->grad.live.reserve(dev->stream, 1));
-    *d_target = t->act.get();          // the stored actions: what a relabel or a teacher-acting rollout left
-    *ld_y = target ? ld_target : ld;
-    *d_weight = nullptr;
+    RQ_HIP(t->grad.live.reserve(dev->stream, 1));      // k_policy_loss_reduce stores M here; nobody reads it (the kernel's text stays)
+    a->n = env->n; a->ld = ld; a->steps = T;
+    a->obs = t->obs; a->done = t->done; a->saved = t->grad.saved;
+    a->start_initial = start == RQ_GRAD_START_INITIAL;
+    a->partial = t->grad.partial; a->live = t->grad.live;
+    a->target = t->act.get();          // the stored actions: what a relabel or a teacher-acting rollout left
+    a->ld_y = target ? ld_target : ld;
     // host-memory calls: one device block, the target | the weight, the second begun at a multiple of 256 bytes
     const size_t y_floats = target ? (size_t)T * RQ_ACTION_DIM * ld_target : 0, w_floats = wt.given ? (size_t)wt.steps * wt.ld : 0;
     const size_t off_w = wt.given ? (y_floats + 63) & ~(size_t)63 : y_floats;
     if (mem.host() && off_w + w_floats > 0) RQ_HIP(t->grad.rows.reserve(dev->stream, off_w + w_floats));
-    if (target) RQ_HIP(mem.in(target, y_floats, t->grad.rows.get(), d_target));
-    if (wt.given) RQ_HIP(mem.in(wt.w, w_floats, t->grad.rows.get() + off_w, d_weight));
+    if (target) RQ_HIP(mem.in(target, y_floats, t->grad.rows.get(), &a->target));
+    if (wt.given) {
+        RQ_HIP(mem.in(wt.w, w_floats, t->grad.rows.get() + off_w, &a->weight));
+        a->ld_w = wt.ld; a->weight_steps = wt.steps;
+    }
     return RQ_OK;
 }
 
 int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, const LossWeight& wt, int start,
-               const CallMemory& mem, size_t n_losses, const float** d_target, uint32_t* ld_y, const float** d_weight) {
+               const CallMemory& mem, size_t n_losses, rq::LossLaunch* a) {
     int rc = RQ_OK;
     if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, t->env->n); if (rc) return rc; }
     rc = ensure_grad_image(pol); if (rc) return rc;
-    return loss_workspace(t, target, ld_target, wt, mem, RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y, d_weight);
-}
-
-// d_weight null: the unweighted kernels, as they were; else the weighted pair, wt's strides
-hipError_t enqueue_loss_grad(rq_trajectory* t, rq_policy* pol, int start, const float* d_target, uint32_t ld_y, const float* d_weight,
-                             const LossWeight& wt, float* d_grad, float* d_loss) {
-    rq_env* env = t->env;
-    const float* hidden = start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr;
-    if (d_weight)
-        return rq::launch_policy_loss_grad_weighted(env->dev->stream, env->n, env->ld, t->length, pol->w_packed, pol->w_packed_grad,
-                                                    t->obs, t->done, hidden, pol->ld, start == RQ_GRAD_START_INITIAL, t->grad.saved,
-                                                    d_target, ld_y, d_weight, wt.ld, wt.steps, t->grad.partial, d_grad, d_loss);
-    return rq::launch_policy_loss_grad(env->dev->stream, env->n, env->ld, t->length, pol->w_packed, pol->w_packed_grad, t->obs,
-                                       t->done, hidden, pol->ld, start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y,
-                                       t->grad.partial, d_grad, d_loss, t->grad.live);
+    rc = loss_workspace(t, target, ld_target, wt, start, mem, RQ_POLICY_NUM_WEIGHTS + n_losses, a); if (rc) return rc;
+    a->packed = pol->w_packed; a->gpacked = pol->w_packed_grad;
+    a->hidden = start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr;
+    a->ld_h = pol->ld;
+    return RQ_OK;
 }
 
 // ---- the same for a policy bank (rq_trajectory_policies_loss_grad / _distill) ----
@@ -183,8 +182,7 @@ int bank_loss_check(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* poli
 }
 
 int bank_loss_begin(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target, uint32_t ld_target,
-                    const LossWeight& wt, int start, const CallMemory& mem, size_t n_losses, const float** d_target, uint32_t* ld_y,
-                    const float** d_weight) {
+                    const LossWeight& wt, int start, const CallMemory& mem, size_t n_losses, rq::LossLaunch* a) {
     rq_env* env = t->env;
     int rc = RQ_OK;
     if (start == RQ_GRAD_START_CURRENT) {
@@ -195,24 +193,14 @@ int bank_loss_begin(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* poli
     rc = bank_wave_lists(bank); if (rc) return rc;
     rc = bank_grad_images(bank); if (rc) return rc;
     if (start == RQ_GRAD_START_CURRENT) { rc = bank_apply_reset(bank); if (rc) return rc; }
-    return loss_workspace(t, target, ld_target, wt, mem, (size_t)bank->n_policies * RQ_POLICY_NUM_WEIGHTS + n_losses, d_target, ld_y,
-                          d_weight);
-}
-
-hipError_t enqueue_bank_loss_grad(rq_trajectory* t, rq_policy_bank* bank, int start, const float* d_target, uint32_t ld_y,
-                                  const float* d_weight, const LossWeight& wt, float* d_grad, float* d_loss) {
-    rq_env* env = t->env;
-    const float* hidden = start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr;
-    if (d_weight)
-        return rq::launch_policy_loss_grad_weighted_bank(env->dev->stream, env->n, env->ld, t->length, bank->n_policies, bank->images,
-                                                         bank->gimages, bank->table, bank->waves, bank->waves + bank->n_policies + 1,
-                                                         t->obs, t->done, hidden, bank->ld, start == RQ_GRAD_START_INITIAL,
-                                                         t->grad.saved, d_target, ld_y, d_weight, wt.ld, wt.steps, t->grad.partial,
-                                                         d_grad, d_loss);
-    return rq::launch_policy_loss_grad_bank(env->dev->stream, env->n, env->ld, t->length, bank->n_policies, bank->images, bank->gimages,
-                                            bank->table, bank->waves, bank->waves + bank->n_policies + 1, t->obs, t->done, hidden,
-                                            bank->ld, start == RQ_GRAD_START_INITIAL, t->grad.saved, d_target, ld_y, t->grad.partial,
-                                            d_grad, d_loss);
+    rc = loss_workspace(t, target, ld_target, wt, start, mem, (size_t)bank->n_policies * RQ_POLICY_NUM_WEIGHTS + n_losses, a);
+    if (rc) return rc;
+    a->packed = bank->images; a->gpacked = bank->gimages;
+    a->n_policies = bank->n_policies; a->block_policy = bank->table;
+    a->wave_offsets = bank->waves; a->wave_list = bank->waves + bank->n_policies + 1;
+    a->hidden = start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr;
+    a->ld_h = bank->ld;
+    return RQ_OK;
 }
 
 bool adam_config_ok(const rq_adam_config& c) {
@@ -340,11 +328,11 @@ static int policy_loss_grad(rq_trajectory* t, rq_policy* pol, const float* targe
     rq_device* dev = t->env->dev;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     CallMemory mem(memory, dev->stream, dev->ordinal);
-    const float *d_target = nullptr, *d_weight = nullptr; uint32_t ld_y = 0;
-    rc = loss_begin(t, pol, target, ld_target, wt, start, mem, 1, &d_target, &ld_y, &d_weight); if (rc) return rc;
-    float* d_grad = mem.out(grad_weights, RQ_POLICY_NUM_WEIGHTS, t->grad.out.get());
-    float* d_loss = mem.out(loss, 1, t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS);
-    RQ_HIP(enqueue_loss_grad(t, pol, start, d_target, ld_y, d_weight, wt, d_grad, d_loss));
+    rq::LossLaunch a;
+    rc = loss_begin(t, pol, target, ld_target, wt, start, mem, 1, &a); if (rc) return rc;
+    a.grad = mem.out(grad_weights, RQ_POLICY_NUM_WEIGHTS, t->grad.out.get());
+    a.loss = mem.out(loss, 1, t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS);
+    RQ_HIP(rq::launch_policy_loss_grad(dev->stream, a));
     t->grad.stamp(pol, t->length, start);          // the saved state is the forward's: a rq_trajectory_policy_backward may follow
     RQ_HIP(mem.finish());
     return RQ_OK;
@@ -397,13 +385,15 @@ static int policy_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer* opt, c
     rq_device* dev = t->env->dev;
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;          // (retires a resident executor: it holds the old operands)
     CallMemory mem(memory, dev->stream, dev->ordinal);
-    const float *d_target = nullptr, *d_weight = nullptr; uint32_t ld_y = 0;
-    rc = loss_begin(t, pol, target, ld_target, wt, start, mem, n_updates, &d_target, &ld_y, &d_weight); if (rc) return rc;
+    rq::LossLaunch a;
+    rc = loss_begin(t, pol, target, ld_target, wt, start, mem, n_updates, &a); if (rc) return rc;
+    a.grad = opt->grad;
     float* d_losses = mem.out(losses, n_updates, t->grad.out.get() + RQ_POLICY_NUM_WEIGHTS);
     hipError_t e = hipSuccess;
     uint32_t done_updates = 0;
     for (; done_updates < n_updates && e == hipSuccess; ++done_updates) {
-        e = enqueue_loss_grad(t, pol, start, d_target, ld_y, d_weight, wt, opt->grad, d_losses + done_updates);
+        a.loss = d_losses + done_updates;
+        e = rq::launch_policy_loss_grad(dev->stream, a);
         if (e == hipSuccess) e = rq::launch_adam_repack(dev->stream, opt->grad, pol->w_dev, opt->m, opt->v, opt->state, opt->table,
                                                         pol->w_packed, pol->w_packed_grad);
     }
@@ -440,11 +430,11 @@ static int policies_loss_grad(rq_trajectory* t, rq_policy_bank* bank, const uint
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const size_t P = bank->n_policies, grad_floats = P * RQ_POLICY_NUM_WEIGHTS;
     CallMemory mem(memory, dev->stream, dev->ordinal);
-    const float *d_target = nullptr, *d_weight = nullptr; uint32_t ld_y = 0;
-    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, wt, start, mem, P, &d_target, &ld_y, &d_weight); if (rc) return rc;
-    float* d_grad = mem.host() ? t->grad.out.get() : grad_weights;
-    float* d_loss = mem.out(loss, P, t->grad.out.get() + grad_floats);
-    RQ_HIP(enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, d_weight, wt, d_grad, d_loss));
+    rq::LossLaunch a;
+    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, wt, start, mem, P, &a); if (rc) return rc;
+    float* d_grad = a.grad = mem.host() ? t->grad.out.get() : grad_weights;
+    a.loss = mem.out(loss, P, t->grad.out.get() + grad_floats);
+    RQ_HIP(rq::launch_policy_loss_grad(dev->stream, a));
     // (t->grad.valid stays false: the saved state is no single policy's, rq_trajectory_policy_backward has nothing to follow)
     if (mem.host()) {
         // a policy that owns no wave has no gradient row on the device: the caller's row stays as it was (the losses: finish)
@@ -517,12 +507,14 @@ static int policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_opti
     DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
     const size_t P = bank->n_policies, n_losses = (size_t)n_updates * P;
     CallMemory mem(memory, dev->stream, dev->ordinal);
-    const float *d_target = nullptr, *d_weight = nullptr; uint32_t ld_y = 0;
-    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, wt, start, mem, n_losses, &d_target, &ld_y, &d_weight); if (rc) return rc;
+    rq::LossLaunch a;
+    rc = bank_loss_begin(t, bank, policy_id, target, ld_target, wt, start, mem, n_losses, &a); if (rc) return rc;
+    a.grad = opt->grad;
     float* d_losses = mem.out(losses, n_losses, t->grad.out.get() + P * RQ_POLICY_NUM_WEIGHTS);
     hipError_t e = hipSuccess;
     for (uint32_t k = 0; k < n_updates && e == hipSuccess; ++k) {       // back to back: nothing waits in between
-        e = enqueue_bank_loss_grad(t, bank, start, d_target, ld_y, d_weight, wt, opt->grad, d_losses + (size_t)k * P);
+        a.loss = d_losses + (size_t)k * P;
+        e = rq::launch_policy_loss_grad(dev->stream, a);
         if (e == hipSuccess) e = rq::launch_adam_repack_bank(dev->stream, bank->n_policies, bank->waves, opt->grad, bank->weights, opt->m,
                                                              opt->v, opt->state, opt->table, bank->images, bank->gimages);
     }

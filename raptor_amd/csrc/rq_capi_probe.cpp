@@ -16,7 +16,7 @@ using namespace rqh;
 namespace {
 
 // rq_trajectory_probe_moments (targets [n_targets][ld_targets]) and, `timed`, rq_trajectory_probe_moments_timed (targets
-// [length][n_targets][ld_targets]): one set of refusals, one device block, one of two launches.  `what`: the entry point's name.
+// [length][n_targets][ld_targets]): one set of refusals, one device block, one launch.  `what`: the entry point's name.
 int probe_moments(const char* what, bool timed, rq_trajectory* t, rq_policy* pol, const float* targets, uint32_t ld_targets,
                   uint32_t n_targets, const uint32_t* age_edges, uint32_t n_buckets, double* moments, uint64_t* counts, int memory) {
     int rc = grad_check_pair(t, pol, what); if (rc) return rc;
@@ -67,9 +67,8 @@ int probe_moments(const char* what, bool timed, rq_trajectory* t, rq_policy* pol
     const float* d_y = nullptr; RQ_HIP_AS(what, mem.in(targets, y_floats, s_y, &d_y));
     double* d_moments = mem.out(moments, moment_doubles, s_moments);
     unsigned long long* d_counts = mem.out(reinterpret_cast<unsigned long long*>(counts), n_buckets, s_counts);
-    RQ_HIP_AS(what, (timed ? rq::launch_probe_moments_timed : rq::launch_probe_moments)(
-                        dev->stream, env->n, env->ld, t->length, t->grad.saved, t->done, d_y, ld_targets, n_targets, edges, n_buckets,
-                        t->grad.probe, d_moments, d_counts));
+    RQ_HIP_AS(what, rq::launch_probe_moments(dev->stream, env->n, env->ld, t->length, t->grad.saved, t->done, d_y, ld_targets, n_targets,
+                                             edges, n_buckets, t->grad.probe, d_moments, d_counts, timed));
     RQ_HIP_AS(what, mem.finish());
     return RQ_OK;
 }

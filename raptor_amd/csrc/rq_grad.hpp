@@ -21,7 +21,9 @@
 //   k_policy_loss_backward_weighted[_bank]   dL/da = w (a - y) where the entry is live and w > 0; + per wave the weighted squared
 //                                            error and, in float64, the sum of the counting weights
 //   k_policy_loss_reduce_weighted[_bank]     the reductions above with W4 = that sum over the waves, in wave order, in M's place
-// The forwards and the backwards are one text each (rq_grad_forward.inc, rq_grad_backward.inc), compiled once per kernel.
+// The forwards, the backwards, the loss reductions and the Adam kernels are one text each (rq_grad_forward.inc, rq_grad_backward.inc,
+// rq_loss_reduce.inc, rq_adam_repack.inc), compiled once per kernel.  Every form of the loss launch goes through one launcher,
+// launch_policy_loss_grad (rq_grad_bank.hpp), from one description (rq_loss_launch.hpp).
 //
 // Layouts (rq_device_math.hpp "actor"): a wave owns 64 envs as 4 tiles of 16; lane (q, j) = (l >> 4, l & 15) holds, in the Q
 // layout, rows 4q .. 4q+3 of a 16-vector of env (tile t, j).  What the reverse pass needs where:
@@ -104,111 +106,22 @@ __global__ __launch_bounds__(256) void k_policy_grad_reduce(uint32_t waves, cons
     grad[p] = acc;
 }
 
-// The seeded backward's reduction: the partials in wave order as k_policy_grad_reduce sums them, M = the live entries of all
-// waves (4 x the live env-steps; an integer sum), grad = sum x 2 / M with the scale applied once - the product in float64, one
-// rounding to fp32 - and loss = SSE / M with the waves' SSE summed in wave order.  M = 0 (every step frozen): loss and gradient 0.
-// out[0] = loss; live_out[0] = M.
-__global__ __launch_bounds__(256) void k_policy_loss_reduce(uint32_t waves, const float* __restrict__ partial,
-                                                           const float* __restrict__ wave_sse, const uint32_t* __restrict__ wave_live,
-                                                           float* __restrict__ grad, float* __restrict__ loss,
-                                                           unsigned long long* __restrict__ live_out) {
-    __shared__ unsigned long long cnt[256];
-    unsigned long long mine = 0;
-    for (uint32_t w = threadIdx.x; w < waves; w += 256) mine += wave_live[w];
-    cnt[threadIdx.x] = mine;
-    __syncthreads();
-    for (uint32_t h = 128; h > 0; h >>= 1) {
-        if (threadIdx.x < h) cnt[threadIdx.x] += cnt[threadIdx.x + h];
-        __syncthreads();
-    }
-    const unsigned long long M = cnt[0];
-    const double inv = M ? 1.0 / (double)M : 0.0;
-    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-    if (p < RQ_POLICY_NUM_WEIGHTS) {
-        float acc = 0.0f;
-#pragma unroll 8
-        for (uint32_t w = 0; w < waves; ++w) acc += partial[(size_t)w * RQ_POLICY_NUM_WEIGHTS + p];
-        grad[p] = M ? (float)((double)acc * (2.0 * inv)) : 0.0f;
-    }
-    if (p == 0) {
-        float acc = 0.0f;
-#pragma unroll 8
-        for (uint32_t w = 0; w < waves; ++w) acc += wave_sse[w];
-        loss[0] = M ? (float)((double)acc * inv) : 0.0f;
-        live_out[0] = M;
-    }
-}
+// The seeded backward's reduction (rq_loss_reduce.inc): the partials in wave order as k_policy_grad_reduce sums them, x 2 / M once;
+// out[0] = loss, live_out[0] = M
+#define RQ_LOSS_REDUCE_KERNEL k_policy_loss_reduce
+#define RQ_GRAD_BANK 0
+#include "rq_loss_reduce.inc"
 
-// The weighted seeded backward's reduction: k_policy_loss_reduce with the normaliser W4 = the waves' wave_wsum added in ascending
-// wave order in float64 (every thread adds them itself, beside the partials it is walking anyway: one order, no exchange) in the
-// place of M: grad = sum x 2 / W4, the product in float64 and one rounding to fp32, loss = SSE / W4.  W4 = 0 (nothing counts): loss
-// and gradient 0.  With every weight 1.0f W4 is the integer M exactly, and the results are k_policy_loss_reduce's bits.
-__global__ __launch_bounds__(256) void k_policy_loss_reduce_weighted(uint32_t waves, const float* __restrict__ partial,
-                                                                    const float* __restrict__ wave_sse,
-                                                                    const double* __restrict__ wave_wsum, float* __restrict__ grad,
-                                                                    float* __restrict__ loss) {
-    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= RQ_POLICY_NUM_WEIGHTS) return;
-    float acc = 0.0f;
-    double W4 = 0.0;
-#pragma unroll 8
-    for (uint32_t w = 0; w < waves; ++w) {
-        acc += partial[(size_t)w * RQ_POLICY_NUM_WEIGHTS + p];
-        W4 += wave_wsum[w];
-    }
-    const bool any = W4 > 0.0;
-    const double inv = any ? 1.0 / W4 : 0.0;
-    grad[p] = any ? (float)((double)acc * (2.0 * inv)) : 0.0f;
-    if (p == 0) {
-        float sse = 0.0f;
-#pragma unroll 8
-        for (uint32_t w = 0; w < waves; ++w) sse += wave_sse[w];
-        loss[0] = any ? (float)((double)sse * inv) : 0.0f;
-    }
-}
+// the same with W4, the waves' float64 weight sums, in M's place (rq_loss_reduce.inc, RQ_GRAD_WEIGHTED)
+#define RQ_LOSS_REDUCE_KERNEL k_policy_loss_reduce_weighted
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_WEIGHTED 1
+#include "rq_loss_reduce.inc"
 
-// Adam (torch.optim.Adam's update; weight_decay decoupled as in AdamW) on the device's master weights, then both fp32 operand
-// images rebuilt from them: one workgroup.  Hyper-parameters, the step count and the running powers beta^t live in device memory
-// (AdamState), so that updates queue back to back.  Per element, in float64 from the fp32 inputs and rounded to fp32 once each:
-//     m' = beta1 m + (1 - beta1) g,  v' = beta2 v + (1 - beta2) g g,
-//     w' = w (1 - lr wd) - lr (m' / (1 - beta1^t)) / (sqrt(v' / (1 - beta2^t)) + eps)
-// The images come from a gather table (rq_pack.cpp pack_gather_table: pack_policy / pack_policy_grad run on symbols): element e is
-// 0, k w[a] or k (w[a] + w[b]) in fp32 - the host packers' expressions, no contraction - so the images equal theirs bit for bit.
-__global__ __launch_bounds__(1024) void k_adam_repack(const float* __restrict__ grad, float* __restrict__ w, float* __restrict__ m,
-                                                      float* __restrict__ v, AdamState* __restrict__ st,
-                                                      const PackGather* __restrict__ table, uint32_t n_forward, uint32_t n_grad,
-                                                      float* __restrict__ packed, float* __restrict__ gpacked) {
-    __shared__ float ws[RQ_POLICY_NUM_WEIGHTS];
-    const double lr = st->lr, beta1 = st->beta1, beta2 = st->beta2, eps = st->eps, wd = st->weight_decay;
-    const double b1t = st->beta1_t * beta1, b2t = st->beta2_t * beta2;
-    const uint32_t step = st->step;
-    for (uint32_t p = threadIdx.x; p < RQ_POLICY_NUM_WEIGHTS; p += 1024) {
-        const double g = grad[p];
-        const double mm = beta1 * (double)m[p] + (1.0 - beta1) * g;
-        const double vv = beta2 * (double)v[p] + (1.0 - beta2) * g * g;
-        const double mhat = mm / (1.0 - b1t), vhat = vv / (1.0 - b2t);
-        double x = w[p];
-        x = x * (1.0 - lr * wd) - lr * mhat / (sqrt(vhat) + eps);
-        const float xf = (float)x;
-        m[p] = (float)mm;
-        v[p] = (float)vv;
-        w[p] = xf;
-        ws[p] = xf;
-    }
-    __syncthreads();                    // every thread has read the state; the weights are in LDS
-    if (threadIdx.x == 0) { st->beta1_t = b1t; st->beta2_t = b2t; st->step = step + 1; }
-    for (uint32_t e = threadIdx.x; e < n_forward + n_grad; e += 1024) {
-        const PackGather t = table[e];
-        float x = 0.0f;
-        if (t.a != PACK_GATHER_NONE) {
-            x = ws[t.a];
-            if (t.b != PACK_GATHER_NONE) x = x + ws[t.b];
-            x = t.k * x;
-        }
-        if (e < n_forward) packed[e] = x;
-        else gpacked[e - n_forward] = x;
-    }
-}
+// Adam on the master weights, then both operand images from a gather table: one workgroup (rq_adam_repack.inc)
+#define RQ_ADAM_KERNEL k_adam_repack
+#define RQ_GRAD_BANK 0
+#include "rq_adam_repack.inc"
 
 __global__ void k_adam_set_lr(AdamState* st, double lr) {
     if (threadIdx.x == 0 && blockIdx.x == 0) st->lr = lr;
@@ -245,56 +158,6 @@ hipError_t launch_policy_grad_backward(hipStream_t s, uint32_t n, uint32_t ld, u
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_policy_grad_reduce<<<(RQ_POLICY_NUM_WEIGHTS + 255) / 256, 256, 0, s>>>(waves, partial, grad);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_grad_forward_state(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
-                                            const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h,
-                                            int start_initial, float* saved) {
-    if (n == 0 || steps == 0) return hipErrorInvalidValue;
-    const unsigned g = (n + kFusedBlock - 1) / kFusedBlock;
-    const uint32_t si = start_initial ? 1u : 0u;
-    if (n > kOneWavePerSimdEnvs)        // launch_policy_grad_forward's choice of build
-        k_policy_grad_forward_state<ActorF32Lean><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, saved);
-    else
-        k_policy_grad_forward_state<ActorF32><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, saved);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed, const float* gpacked,
-                                   const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial,
-                                   float* saved, const float* target, uint32_t ld_y, float* partial, float* grad, float* loss,
-                                   unsigned long long* live) {
-    const uint32_t si = start_initial ? 1u : 0u, waves = (n + 63) / 64;
-    hipError_t e = launch_policy_grad_forward_state(s, n, ld, steps, packed, obs, done, hidden, ld_h, start_initial, saved);
-    if (e != hipSuccess) return e;
-    float* wave_sse = partial + (size_t)waves * RQ_POLICY_NUM_WEIGHTS;         // partial: [waves][2084] | sse [waves] | live [waves]
-    uint32_t* wave_live = reinterpret_cast<uint32_t*>(wave_sse + waves);
-    k_policy_loss_backward<<<waves, 64, 0, s>>>(n, ld, steps, packed, gpacked, obs, done, saved, target, ld_y, si, partial,
-                                                wave_sse, wave_live);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    k_policy_loss_reduce<<<(RQ_POLICY_NUM_WEIGHTS + 255) / 256, 256, 0, s>>>(waves, partial, wave_sse, wave_live, grad, loss, live);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_loss_grad_weighted(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
-                                            const float* gpacked, const float* obs, const uint8_t* done, const float* hidden,
-                                            uint32_t ld_h, int start_initial, float* saved, const float* target, uint32_t ld_y,
-                                            const float* weight, uint32_t ld_w, uint32_t weight_steps, float* partial, float* grad,
-                                            float* loss) {
-    if (weight == nullptr || ld_w < n || (weight_steps != 1 && weight_steps != steps)) return hipErrorInvalidValue;
-    const uint32_t si = start_initial ? 1u : 0u, waves = (n + 63) / 64;
-    hipError_t e = launch_policy_grad_forward_state(s, n, ld, steps, packed, obs, done, hidden, ld_h, start_initial, saved);
-    if (e != hipSuccess) return e;
-    // partial: [waves][2084] | wsum [waves] float64 (8 336 bytes per wave before it: aligned) | sse [waves]
-    double* wave_wsum = reinterpret_cast<double*>(partial + (size_t)waves * RQ_POLICY_NUM_WEIGHTS);
-    float* wave_sse = reinterpret_cast<float*>(wave_wsum + waves);
-    k_policy_loss_backward_weighted<<<waves, 64, 0, s>>>(n, ld, steps, packed, gpacked, obs, done, saved, target, ld_y, weight, ld_w,
-                                                         weight_steps == 1 ? 0u : ld_w, si, partial, wave_sse, wave_wsum);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    k_policy_loss_reduce_weighted<<<(RQ_POLICY_NUM_WEIGHTS + 255) / 256, 256, 0, s>>>(waves, partial, wave_sse, wave_wsum, grad, loss);
     return hipGetLastError();
 }
 

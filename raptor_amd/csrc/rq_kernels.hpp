@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "../../include/raptor_quad.h"
 #include "rq_fused_route.hpp"
+#include "rq_loss_launch.hpp"
 
 namespace rq {
 
@@ -229,30 +230,12 @@ hipError_t launch_policy_grad_backward(hipStream_t s, uint32_t n, uint32_t ld, u
                                        const float* gpacked, const float* obs, const uint8_t* done, const float* saved,
                                        const float* grad_act, uint32_t ld_g, int start_initial, float* grad_h_start,
                                        float* partial, float* grad);
-// The distillation update on the device (rq_grad.hpp).  launch_policy_loss_grad: the forward without the action store, the backward
-// seeded by the masked squared error against target [steps][4][ld_y] (live = done code != 4, column < n) and the reduction: grad
-// [2084] = d/dtheta of loss = mean over live entries of (a - y)^2, loss [1], live [1] = M.  partial: [waves][2084] floats followed
-// by 2 x waves words (policy_loss_partial_floats).  Deterministic; M = 0 gives loss 0 and a zero gradient.
-constexpr size_t policy_loss_partial_floats(uint32_t n) { return (size_t)((n + 63) / 64) * (RQ_POLICY_NUM_WEIGHTS + 2); }
-// its first launch alone: the forward that saves the state and stores no action (the probes read nothing else)
-hipError_t launch_policy_grad_forward_state(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
-                                            const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h,
-                                            int start_initial, float* saved);
-hipError_t launch_policy_loss_grad(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed, const float* gpacked,
-                                   const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial,
-                                   float* saved, const float* target, uint32_t ld_y, float* partial, float* grad, float* loss,
-                                   unsigned long long* live);
-// The same with a weight on every entry of the loss (rq_grad_backward.inc, RQ_GRAD_WEIGHTED): weight [weight_steps][ld_w], weight_steps
-// = 1 (per env) or steps (per env and step), ld_w >= n.  An entry counts where it is live and its weight > 0; loss = sum w (a - y)^2 /
-// W4, W4 = the sum of w over the counting entries in float64, grad its gradient; W4 = 0 gives loss 0 and a zero gradient.  Weights of
-// 1.0f give launch_policy_loss_grad's bits.  partial: [waves][2084] floats, a float64 and a float per wave
-// (policy_loss_weighted_partial_floats).
-constexpr size_t policy_loss_weighted_partial_floats(uint32_t n) { return (size_t)((n + 63) / 64) * (RQ_POLICY_NUM_WEIGHTS + 3); }
-hipError_t launch_policy_loss_grad_weighted(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
-                                            const float* gpacked, const float* obs, const uint8_t* done, const float* hidden,
-                                            uint32_t ld_h, int start_initial, float* saved, const float* target, uint32_t ld_y,
-                                            const float* weight, uint32_t ld_w, uint32_t weight_steps, float* partial, float* grad,
-                                            float* loss);
+// The distillation update on the device (rq_grad.hpp, rq_grad_bank.hpp).  launch_policy_loss_grad: every form of the loss launch -
+// one policy or a bank, weighted or not - as rq_loss_launch.hpp's LossLaunch describes it.  Deterministic.
+hipError_t launch_policy_loss_grad(hipStream_t s, const LossLaunch& a);
+// its first launch alone: the forward that saves the state and stores no action (the probes read nothing else); what it does not
+// read of the description - the transposed image, the target, the weight, the workspace, the outputs - may stay unset
+hipError_t launch_policy_grad_forward_state(hipStream_t s, const LossLaunch& a);
 // Adam's state on the device: hyper-parameters, the step count t and the running powers beta^t (1 before the first step)
 struct AdamState { double lr, beta1, beta2, eps, weight_decay, beta1_t, beta2_t; uint32_t step, pad; };
 // one element of an operand image as a function of the flat weights: 0 (a == PACK_GATHER_NONE), k w[a], or k (w[a] + w[b])
@@ -263,24 +246,9 @@ enum { PACK_GATHER_NONE = 0xFFFF };
 hipError_t launch_adam_repack(hipStream_t s, const float* grad, float* w, float* m, float* v, AdamState* st, const PackGather* table,
                               float* packed, float* gpacked);
 hipError_t launch_adam_set_lr(hipStream_t s, AdamState* st, double lr);
-// The same update for a policy bank (rq_grad_bank.hpp): images [P][RQ_PACKED_FLOATS], gimages [P][RQ_PACKED_GRAD_FLOATS],
-// block_policy [ceil(n / 64)] as the bank's rollout takes them, and the policies' waves as a CSR list: wave_offsets [P + 1] into
-// wave_list [ceil(n / 64)], ascending within a policy.  launch_policy_loss_grad_bank: grad [P][2084] and loss [P], each policy's over
-// its own blocks (M_p = 0: 0; a policy without a wave: loss NaN, its gradient row not written); partial as above.
-// launch_adam_repack_bank: one Adam step per policy that owns a wave, on w / m / v [P][2084] with st [P], and both its images
-// rebuilt.  launch_adam_set_lr_bank: lr [n_lr], n_lr = 1 (for all) or P, a host array read before the call returns.
-hipError_t launch_policy_loss_grad_bank(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, uint32_t n_policies, const float* images,
-                                        const float* gimages, const uint32_t* block_policy, const uint32_t* wave_offsets,
-                                        const uint32_t* wave_list, const float* obs, const uint8_t* done, const float* hidden,
-                                        uint32_t ld_h, int start_initial, float* saved, const float* target, uint32_t ld_y,
-                                        float* partial, float* grad, float* loss);
-// (the bank's weighted form: launch_policy_loss_grad_weighted per policy, W4_p over its own blocks; partial as there)
-hipError_t launch_policy_loss_grad_weighted_bank(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, uint32_t n_policies,
-                                                 const float* images, const float* gimages, const uint32_t* block_policy,
-                                                 const uint32_t* wave_offsets, const uint32_t* wave_list, const float* obs,
-                                                 const uint8_t* done, const float* hidden, uint32_t ld_h, int start_initial, float* saved,
-                                                 const float* target, uint32_t ld_y, const float* weight, uint32_t ld_w,
-                                                 uint32_t weight_steps, float* partial, float* grad, float* loss);
+// The bank's (rq_grad_bank.hpp).  launch_adam_repack_bank: one Adam step per policy that owns a wave (wave_offsets [P + 1], the CSR
+// list of the loss launch), on w / m / v [P][2084] with st [P], and both its images rebuilt.  launch_adam_set_lr_bank: lr [n_lr], n_lr
+// = 1 (for all) or P, a host array read before the call returns.
 hipError_t launch_adam_repack_bank(hipStream_t s, uint32_t n_policies, const uint32_t* wave_offsets, const float* grad, float* w, float* m,
                                    float* v, AdamState* st, const PackGather* table, float* images, float* gimages);
 hipError_t launch_adam_set_lr_bank(hipStream_t s, AdamState* st, uint32_t n_policies, const double* lr, uint32_t n_lr);

@@ -7,6 +7,7 @@
 //   k_probe_hidden_rows   saved [T][16][ld] -> [T][n][16], the learner layout (rq_trajectory_get_hidden)
 //   k_probe_moments_timed   k_probe_moments with targets per step, y [T][M][ld_y]              HBM ((64 + 4 M) B/env-step read)
 //   k_probe_wrench_targets  a lane per env, t = 0 .. T-1: the scheduled wrench row the env flew  HBM (24 B/env-step written)
+// k_probe_moments and k_probe_moments_timed are one text (rq_probe_moments.inc under RQ_PROBE_TIMED), compiled once per kernel.
 //
 // Layout.  Lane l of a wave IS env 64 w + l: it loads its 16 state rows (16 coalesced 256-byte reads per step), keeps its age and
 // its targets in registers and owns row l of the wave's LDS tile, [64][PZ_ROW]: columns 0 .. 31 = z, column 32 = the bucket of the
@@ -66,105 +67,10 @@ __device__ __forceinline__ void probe_flush(float* __restrict__ slot, uint32_t* 
     if (lane == 0) count[0] = first ? cnt : count[0] + cnt;
 }
 
-__global__ __launch_bounds__(64) void k_probe_moments(uint32_t n, uint32_t ld, uint32_t steps, const float* __restrict__ saved,
-                                                      const uint8_t* __restrict__ done, const float* __restrict__ y, uint32_t ld_y,
-                                                      uint32_t n_targets, const ProbeEdges edges, uint32_t n_buckets,
-                                                      float* __restrict__ partial, uint32_t* __restrict__ wave_counts) {
-    __shared__ float zt[64 * PZ_ROW];
-    __shared__ uint32_t ed[kProbeMaxBuckets + 1];
-    const uint32_t lane = threadIdx.x & 63, q = lane >> 4, j = lane & 15;
-    const uint32_t wave = blockIdx.x, e = wave * 64 + lane;
-    const bool ev = e < n;                           // e < ld (the launcher checks): the forward saved the state of every column
-    const uint32_t ey = ev ? e : 0u;                 // padding lanes read env 0's targets and select them away
-    if (lane <= n_buckets) ed[lane] = edges.v[lane];
-    float* row = zt + lane * PZ_ROW;
-    row[0] = 1.0f;
-#pragma unroll
-    for (uint32_t m = 0; m < kProbeMaxTargets; ++m) {
-        const float v = y[(size_t)(m < n_targets ? m : 0u) * ld_y + ey];
-        row[17 + m] = ev && m < n_targets ? v : 0.0f;
-    }
-    __syncthreads();
-    const uint32_t idx0 = ed[0] == 0u ? 1u : 0u;     // edges <= age 0
-    uint32_t age = 0, idx = idx0;
-
-    float* const wave_slot = partial + (size_t)wave * n_buckets * PZ_TILE;
-    uint32_t* const wave_count = wave_counts + (size_t)wave * n_buckets;
-    const pf32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    pf32x4 s00 = zero, s01 = zero, s11 = zero;
-    uint32_t cnt = 0, touched = 0;
-    int cur = -1;                                     // the bucket in flight (wave-uniform)
-
-    float hn[16];
-    uint32_t dn = 4;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hn[r] = saved[(size_t)r * ld + e];
-    dn = done[e];
-
-    for (uint32_t s = 0; s < steps; ++s) {
-        float h[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h[r] = hn[r];
-        const uint32_t d = dn;
-        if (s + 1 < steps) {                          // the next step's rows are on their way while this one is contracted
-#pragma unroll
-            for (int r = 0; r < 16; ++r) hn[r] = saved[((size_t)(s + 1) * 16 + r) * ld + e];
-            dn = done[(size_t)(s + 1) * ld + e];
-        }
-        const bool live = ev && d != 4u;
-        const int bk = live && idx >= 1u && idx <= n_buckets ? (int)idx - 1 : -1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) row[1 + r] = h[r];
-        row[PZ_BUCKET] = __int_as_float(bk);
-        if (live) {
-            if (d == 1u || d == 2u) { age = 0; idx = idx0; }
-            else {
-                ++age;
-                if (idx <= n_buckets && ed[idx] == age) ++idx;
-            }
-        }
-        __syncthreads();
-
-        uint64_t todo = __builtin_amdgcn_ballot_w64(bk >= 0);
-        bool head = true;
-        while (todo) {
-            int b;
-            const uint64_t in_cur = head && cur >= 0 ? __builtin_amdgcn_ballot_w64(bk == cur) : 0ull;
-            if (in_cur) b = cur;
-            else b = __builtin_amdgcn_readlane(bk, (int)__builtin_ctzll(todo));
-            head = false;
-            const uint64_t members = __builtin_amdgcn_ballot_w64(bk == b);
-            todo &= ~members;
-            if (b != cur) {
-                if (cur >= 0) {
-                    probe_flush(wave_slot + (size_t)cur * PZ_TILE, wave_count + cur, !((touched >> cur) & 1u), lane, s00, s01, s11, cnt);
-                    touched |= 1u << cur;
-                }
-                s00 = s01 = s11 = zero;
-                cnt = 0;
-                cur = b;
-            }
-            cnt += (uint32_t)__builtin_popcountll(members);
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                if (((members >> (4 * u)) & 0xfull) == 0) continue;          // none of envs 4u .. 4u+3 is in the bucket: exact zeros
-                const float* src = zt + (4 * u + q) * PZ_ROW;                // k-slot q = env 4u + q of the wave
-                const bool in = __float_as_int(src[PZ_BUCKET]) == b;
-                const float lo = in ? src[j] : 0.0f, hi = in ? src[16 + j] : 0.0f;
-                s00 = probe_mfma(lo, lo, s00);
-                s01 = probe_mfma(lo, hi, s01);
-                s11 = probe_mfma(hi, hi, s11);
-            }
-        }
-        __syncthreads();
-    }
-    if (cur >= 0) {
-        probe_flush(wave_slot + (size_t)cur * PZ_TILE, wave_count + cur, !((touched >> cur) & 1u), lane, s00, s01, s11, cnt);
-        touched |= 1u << cur;
-    }
-    for (uint32_t b = 0; b < n_buckets; ++b)          // a bucket this wave never met: zeros, so that the reduction reads no stale word
-        if (!((touched >> b) & 1u)) probe_flush(wave_slot + (size_t)b * PZ_TILE, wave_count + b, true, lane, zero, zero, zero, 0u);
-}
+// the moment kernel is one text (rq_probe_moments.inc), compiled once per kernel
+#define RQ_PROBE_KERNEL k_probe_moments
+#define RQ_PROBE_TIMED 0
+#include "rq_probe_moments.inc"
 
 // moments[b][i][k] = sum over waves w = 0, 1, ... of the partial, in that order, in float64; the lower left tile is the upper
 // right one mirrored (k_probe_moments computes S[0][1] only).  counts[b] = the waves' counts.
@@ -199,118 +105,10 @@ __global__ __launch_bounds__(256) void k_probe_hidden_rows(uint32_t n, uint32_t 
     }
 }
 
-// k_probe_moments with targets that change over time: y [steps][n_targets][ld_y].  A second body, not a shared one: k_probe_moments'
-// text stays what it was.  What differs: the lane's n_targets values of step s + 1 are loaded beside its 16 state rows while step s
-// is contracted, and written into its row beside h every step - raw, like h: what is not live, not in a bucket or a padding lane is
-// selected away where the tile is read (`in`), so NaN there reaches no sum.  Columns 17 + n_targets .. 31 are zeroed once.  Every
-// bucket decision, flush and MFMA is the untimed kernel's in the untimed kernel's order: targets constant over time give its bits.
-__global__ __launch_bounds__(64) void k_probe_moments_timed(uint32_t n, uint32_t ld, uint32_t steps, const float* __restrict__ saved,
-                                                            const uint8_t* __restrict__ done, const float* __restrict__ y,
-                                                            uint32_t ld_y, uint32_t n_targets, const ProbeEdges edges,
-                                                            uint32_t n_buckets, float* __restrict__ partial,
-                                                            uint32_t* __restrict__ wave_counts) {
-    __shared__ float zt[64 * PZ_ROW];
-    __shared__ uint32_t ed[kProbeMaxBuckets + 1];
-    const uint32_t lane = threadIdx.x & 63, q = lane >> 4, j = lane & 15;
-    const uint32_t wave = blockIdx.x, e = wave * 64 + lane;
-    const bool ev = e < n;                           // e < ld (the launcher checks)
-    const uint32_t ey = ev ? e : 0u;                 // padding lanes read column 0 and are selected away (their bucket is -1)
-    if (lane <= n_buckets) ed[lane] = edges.v[lane];
-    float* row = zt + lane * PZ_ROW;
-    row[0] = 1.0f;
-#pragma unroll
-    for (uint32_t m = 0; m < kProbeMaxTargets; ++m) row[17 + m] = 0.0f;
-    __syncthreads();
-    const uint32_t idx0 = ed[0] == 0u ? 1u : 0u;     // edges <= age 0
-    uint32_t age = 0, idx = idx0;
-
-    float* const wave_slot = partial + (size_t)wave * n_buckets * PZ_TILE;
-    uint32_t* const wave_count = wave_counts + (size_t)wave * n_buckets;
-    const pf32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    pf32x4 s00 = zero, s01 = zero, s11 = zero;
-    uint32_t cnt = 0, touched = 0;
-    int cur = -1;                                     // the bucket in flight (wave-uniform)
-
-    float hn[16], yn[kProbeMaxTargets];
-    uint32_t dn = 4;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hn[r] = saved[(size_t)r * ld + e];
-#pragma unroll
-    for (uint32_t m = 0; m < kProbeMaxTargets; ++m) yn[m] = m < n_targets ? y[(size_t)m * ld_y + ey] : 0.0f;
-    dn = done[e];
-
-    for (uint32_t s = 0; s < steps; ++s) {
-        float h[16], yv[kProbeMaxTargets];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h[r] = hn[r];
-#pragma unroll
-        for (uint32_t m = 0; m < kProbeMaxTargets; ++m) yv[m] = yn[m];
-        const uint32_t d = dn;
-        if (s + 1 < steps) {                          // the next step's rows are on their way while this one is contracted
-#pragma unroll
-            for (int r = 0; r < 16; ++r) hn[r] = saved[((size_t)(s + 1) * 16 + r) * ld + e];
-#pragma unroll
-            for (uint32_t m = 0; m < kProbeMaxTargets; ++m)
-                if (m < n_targets) yn[m] = y[((size_t)(s + 1) * n_targets + m) * ld_y + ey];
-            dn = done[(size_t)(s + 1) * ld + e];
-        }
-        const bool live = ev && d != 4u;
-        const int bk = live && idx >= 1u && idx <= n_buckets ? (int)idx - 1 : -1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) row[1 + r] = h[r];
-#pragma unroll
-        for (uint32_t m = 0; m < kProbeMaxTargets; ++m)
-            if (m < n_targets) row[17 + m] = yv[m];
-        row[PZ_BUCKET] = __int_as_float(bk);
-        if (live) {
-            if (d == 1u || d == 2u) { age = 0; idx = idx0; }
-            else {
-                ++age;
-                if (idx <= n_buckets && ed[idx] == age) ++idx;
-            }
-        }
-        __syncthreads();
-
-        uint64_t todo = __builtin_amdgcn_ballot_w64(bk >= 0);
-        bool head = true;
-        while (todo) {
-            int b;
-            const uint64_t in_cur = head && cur >= 0 ? __builtin_amdgcn_ballot_w64(bk == cur) : 0ull;
-            if (in_cur) b = cur;
-            else b = __builtin_amdgcn_readlane(bk, (int)__builtin_ctzll(todo));
-            head = false;
-            const uint64_t members = __builtin_amdgcn_ballot_w64(bk == b);
-            todo &= ~members;
-            if (b != cur) {
-                if (cur >= 0) {
-                    probe_flush(wave_slot + (size_t)cur * PZ_TILE, wave_count + cur, !((touched >> cur) & 1u), lane, s00, s01, s11, cnt);
-                    touched |= 1u << cur;
-                }
-                s00 = s01 = s11 = zero;
-                cnt = 0;
-                cur = b;
-            }
-            cnt += (uint32_t)__builtin_popcountll(members);
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                if (((members >> (4 * u)) & 0xfull) == 0) continue;          // none of envs 4u .. 4u+3 is in the bucket: exact zeros
-                const float* src = zt + (4 * u + q) * PZ_ROW;                // k-slot q = env 4u + q of the wave
-                const bool in = __float_as_int(src[PZ_BUCKET]) == b;
-                const float lo = in ? src[j] : 0.0f, hi = in ? src[16 + j] : 0.0f;
-                s00 = probe_mfma(lo, lo, s00);
-                s01 = probe_mfma(lo, hi, s01);
-                s11 = probe_mfma(hi, hi, s11);
-            }
-        }
-        __syncthreads();
-    }
-    if (cur >= 0) {
-        probe_flush(wave_slot + (size_t)cur * PZ_TILE, wave_count + cur, !((touched >> cur) & 1u), lane, s00, s01, s11, cnt);
-        touched |= 1u << cur;
-    }
-    for (uint32_t b = 0; b < n_buckets; ++b)          // a bucket this wave never met: zeros, so that the reduction reads no stale word
-        if (!((touched >> b) & 1u)) probe_flush(wave_slot + (size_t)b * PZ_TILE, wave_count + b, true, lane, zero, zero, zero, 0u);
-}
+// k_probe_moments with targets that change over time: y [steps][n_targets][ld_y]
+#define RQ_PROBE_KERNEL k_probe_moments_timed
+#define RQ_PROBE_TIMED 1
+#include "rq_probe_moments.inc"
 
 // The scheduled wrench env i was flown with at every recorded step, rebuilt from what decides it: the table, the env's first row
 // (id * rows), its episode step count when the recording began and the recording's done codes.  k in a register: a frozen step
@@ -349,29 +147,17 @@ __global__ __launch_bounds__(256) void k_probe_wrench_targets(uint32_t n, uint32
 
 hipError_t launch_probe_moments(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, const uint8_t* done,
                                 const float* y, uint32_t ld_y, uint32_t n_targets, const ProbeEdges& edges, uint32_t n_buckets,
-                                float* partial, double* moments, unsigned long long* counts) {
-    if (n == 0 || steps == 0 || n_targets == 0 || n_targets > kProbeMaxTargets || n_buckets == 0 || n_buckets > kProbeMaxBuckets)
-        return hipErrorInvalidValue;
-    const uint32_t waves = (n + 63) / 64;
-    if (ld < 64 * waves) return hipErrorInvalidValue;          // every lane of every wave reads its own column of saved / done
-    uint32_t* wave_counts = reinterpret_cast<uint32_t*>(partial + (size_t)waves * n_buckets * PZ_TILE);
-    k_probe_moments<<<waves, 64, 0, s>>>(n, ld, steps, saved, done, y, ld_y, n_targets, edges, n_buckets, partial, wave_counts);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    k_probe_reduce<<<(n_buckets * PZ_TILE + 255) / 256, 256, 0, s>>>(waves, n_buckets, partial, wave_counts, moments, counts);
-    return hipGetLastError();
-}
-
-hipError_t launch_probe_moments_timed(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, const uint8_t* done,
-                                      const float* y, uint32_t ld_y, uint32_t n_targets, const ProbeEdges& edges, uint32_t n_buckets,
-                                      float* partial, double* moments, unsigned long long* counts) {
+                                float* partial, double* moments, unsigned long long* counts, bool timed) {
     if (n == 0 || steps == 0 || n_targets == 0 || n_targets > kProbeMaxTargets || n_buckets == 0 || n_buckets > kProbeMaxBuckets ||
         ld_y < n)
         return hipErrorInvalidValue;
     const uint32_t waves = (n + 63) / 64;
     if (ld < 64 * waves) return hipErrorInvalidValue;          // every lane of every wave reads its own column of saved / done
     uint32_t* wave_counts = reinterpret_cast<uint32_t*>(partial + (size_t)waves * n_buckets * PZ_TILE);
-    k_probe_moments_timed<<<waves, 64, 0, s>>>(n, ld, steps, saved, done, y, ld_y, n_targets, edges, n_buckets, partial, wave_counts);
+    if (timed)
+        k_probe_moments_timed<<<waves, 64, 0, s>>>(n, ld, steps, saved, done, y, ld_y, n_targets, edges, n_buckets, partial, wave_counts);
+    else
+        k_probe_moments<<<waves, 64, 0, s>>>(n, ld, steps, saved, done, y, ld_y, n_targets, edges, n_buckets, partial, wave_counts);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_probe_reduce<<<(n_buckets * PZ_TILE + 255) / 256, 256, 0, s>>>(waves, n_buckets, partial, wave_counts, moments, counts);

@@ -19,18 +19,13 @@ constexpr size_t probe_partial_floats(uint32_t n, uint32_t n_buckets) {
 // the age edges travel by value, as a kernel argument: edges v[0 .. n_buckets], strictly ascending
 struct ProbeEdges { uint32_t v[kProbeMaxBuckets + 1]; };
 
-// saved [steps][16][ld], done [steps][ld], y [n_targets][ld_y] (columns below n are read) -> moments [n_buckets][D][D] doubles (the full symmetric matrix) and counts [n_buckets].  Two launches:
-// k_probe_moments (a wave per 64 envs) and k_probe_reduce (the waves' partials in ascending wave order, in float64).
-// Deterministic: no atomics, every order fixed.
+// saved [steps][16][ld], done [steps][ld], y [n_targets][ld_y] or, `timed`, targets per step y [steps][n_targets][ld_y] (columns below
+// n <= ld_y are read) -> moments [n_buckets][D][D] doubles (the full symmetric matrix) and counts [n_buckets].  Two launches:
+// k_probe_moments or k_probe_moments_timed (a wave per 64 envs) and k_probe_reduce (the waves' partials in ascending wave order, in
+// float64).  Deterministic: no atomics, every order fixed; timed targets that do not change over time give the untimed bits.
 hipError_t launch_probe_moments(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, const uint8_t* done,
                                 const float* y, uint32_t ld_y, uint32_t n_targets, const ProbeEdges& edges, uint32_t n_buckets,
-                                float* partial, double* moments, unsigned long long* counts);
-
-// The same with targets per step, y [steps][n_targets][ld_y] (k_probe_moments_timed, then k_probe_reduce): targets that do not change
-// over time give the bits of launch_probe_moments.
-hipError_t launch_probe_moments_timed(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, const uint8_t* done,
-                                      const float* y, uint32_t ld_y, uint32_t n_targets, const ProbeEdges& edges, uint32_t n_buckets,
-                                      float* partial, double* moments, unsigned long long* counts);
+                                float* partial, double* moments, unsigned long long* counts, bool timed);
 
 // done [steps][ld], tab [..][6] (a wrench bank's rows), row0 / start [n] (the env's first row in tab, its episode step count at step 0),
 // params [RQ_PARAM_DIM][ld] -> out [steps][6][ld_out] (columns below n are written): the scheduled wrench row of every step, 0.0f on

@@ -275,26 +275,17 @@ class Distiller:
         """-> (loss, dloss/dweights [2084]): device tensors when torch is present, NumPy otherwise (or with a NumPy target)."""
         if start not in START:
             raise ValueError('start must be "initial" or "current"')
-        w = None if weight is None else _loss_weight(traj, weight)
-        ptr, ld_t, on_device, keep = self._target(traj, target)
-        pol = self.policy._handle(traj._env._device)
-        dev = self._torch_device(traj) if on_device is not False else None
-        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1      # the trajectory's saved state is this call's now
-        name, wargs = "rq_trajectory_policy_loss_grad", ()
-        if w is not None:
-            wptr, wkeep = _weight_pointer(w[0], dev)
-            name, wargs = name + "_weighted", (wptr, w[1], w[2])
+        suffix, pol, args, dev, _ = _loss_call(traj, target, weight, start, lambda: self.policy._handle(traj._env._device), False)
+        name = "rq_trajectory_policy_loss_grad" + suffix
         if dev is None:
             loss, grad = np.empty(1, np.float32), np.empty(_lib.POLICY_NUM_WEIGHTS, np.float32)
-            if on_device:
-                raise ValueError("a device target needs torch")
-            _lib.call(name, traj._require("trajectory"), pol, ptr, ld_t, *wargs, START[start], _lib.fptr(loss), _lib.fptr(grad), 0)
+            _lib.call(name, traj._require("trajectory"), pol, *args, _lib.fptr(loss), _lib.fptr(grad), 0)
             return loss[0], grad
         import torch
         loss = torch.empty((), dtype=torch.float32, device=dev)
         grad = torch.empty(_lib.POLICY_NUM_WEIGHTS, dtype=torch.float32, device=dev)
         torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
-        _lib.call(name, traj._require("trajectory"), pol, ptr, ld_t, *wargs, START[start], _device_ptr(loss), _device_ptr(grad), 1)
+        _lib.call(name, traj._require("trajectory"), pol, *args, _device_ptr(loss), _device_ptr(grad), 1)
         return loss, grad
 
     def step(self, traj, target=None, start="initial", updates=1, wait=True, weight=None):
@@ -306,30 +297,41 @@ class Distiller:
         updates = int(updates)
         if updates < 1:
             raise ValueError("updates must be at least 1")
-        w = None if weight is None else _loss_weight(traj, weight)
-        ptr, ld_t, on_device, keep = self._target(traj, target)
-        pol, opt = self._handle(traj)
-        dev = self._torch_device(traj)
-        if on_device is False:
-            dev = None
-        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
-        name, wargs, wkeep = "rq_trajectory_distill", (), None
-        if w is not None:
-            wptr, wkeep = _weight_pointer(w[0], dev)
-            name, wargs = name + "_weighted", (wptr, w[1], w[2])
+        suffix, (pol, opt), args, dev, keep = _loss_call(traj, target, weight, start, lambda: self._handle(traj), True)
+        name = "rq_trajectory_distill" + suffix
         if dev is None:
             losses = np.empty(updates, np.float32)
-            _lib.call(name, traj._require("trajectory"), pol, opt, ptr, ld_t, *wargs, START[start], updates, _lib.fptr(losses), 0)
+            _lib.call(name, traj._require("trajectory"), pol, opt, *args, updates, _lib.fptr(losses), 0)
         else:
             import torch
             losses = torch.empty(updates, dtype=torch.float32, device=dev)
             torch.cuda.current_stream(dev).synchronize()      # once per call, not per update
-            _lib.call(name, traj._require("trajectory"), pol, opt, ptr, ld_t, *wargs, START[start], updates, _device_ptr(losses),
-                      1 if wait else 2)
-        self._target_in_flight = keep      # until the next step: with wait=False the engine's stream may not have read it yet
-        self._weight_in_flight = wkeep
+            _lib.call(name, traj._require("trajectory"), pol, opt, *args, updates, _device_ptr(losses), 1 if wait else 2)
+        # until the next step: with wait=False the engine's stream may not have read the target or the weight yet
+        self._target_in_flight, self._weight_in_flight = keep
         self.policy._weights_on_device = True
         return losses
+
+
+def _loss_call(traj, target, weight, start, handles, host_ok):
+    """What the four loss calls prepare alike, in the order they always did.  First the refusals Python makes itself for ``weight``
+    and ``target``; then ``handles()``, the caller's library handles - an optimizer is created there, so a call Python refuses
+    leaves the library untouched; then the device, the trajectory's ``_learner_forwards`` (its saved state is this call's now) and
+    the weight where the call wants it.  ``host_ok``: whether a device target may go on without torch (else it is refused).
+    -> (suffix of the entry point, what ``handles()`` gave, the arguments from ``target`` to ``start`` - the weight's three among
+    them with the suffix "_weighted" -, the torch device or None for the NumPy path, (target, weight) to keep alive)"""
+    w = None if weight is None else _loss_weight(traj, weight)
+    ptr, ld_t, on_device, keep = Distiller._target(traj, target)
+    h = handles()
+    dev = Distiller._torch_device(traj) if on_device is not False else None
+    traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
+    suffix, wargs, wkeep = "", (), None
+    if w is not None:
+        wptr, wkeep = _weight_pointer(w[0], dev)
+        suffix, wargs = "_weighted", (wptr, w[1], w[2])
+    if dev is None and on_device and not host_ok:
+        raise ValueError("a device target needs torch")
+    return suffix, h, (ptr, ld_t, *wargs, START[start]), dev, (keep, wkeep)
 
 
 def _per_policy(name, value, n_policies):
@@ -399,27 +401,17 @@ class BankDistiller:
         present, NumPy otherwise (or with a NumPy target).  A policy that owns no block: loss NaN, its gradient row zero."""
         ids, _ = self._check(traj, policy_ids, start)
         P = int(self.bank.n_policies)
-        w = None if weight is None else _loss_weight(traj, weight)
-        ptr, ld_t, on_device, keep = Distiller._target(traj, target)
-        dev = Distiller._torch_device(traj) if on_device is not False else None
-        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
-        name, wargs = "rq_trajectory_policies_loss_grad", ()
-        if w is not None:
-            wptr, wkeep = _weight_pointer(w[0], dev)
-            name, wargs = name + "_weighted", (wptr, w[1], w[2])
+        suffix, _, args, dev, _ = _loss_call(traj, target, weight, start, lambda: None, False)
+        name = "rq_trajectory_policies_loss_grad" + suffix
         if dev is None:
-            if on_device:
-                raise ValueError("a device target needs torch")
             loss, grad = np.empty(P, np.float32), np.zeros((P, _lib.POLICY_NUM_WEIGHTS), np.float32)
-            _lib.call(name, traj._require("trajectory"), self.bank._h, ids.ctypes.data, ptr, ld_t, *wargs, START[start],
-                      _lib.fptr(loss), _lib.fptr(grad), 0)
+            _lib.call(name, traj._require("trajectory"), self.bank._h, ids.ctypes.data, *args, _lib.fptr(loss), _lib.fptr(grad), 0)
             return loss, grad
         import torch
         loss = torch.empty(P, dtype=torch.float32, device=dev)
         grad = torch.zeros((P, _lib.POLICY_NUM_WEIGHTS), dtype=torch.float32, device=dev)
         torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
-        _lib.call(name, traj._require("trajectory"), self.bank._h, ids.ctypes.data, ptr, ld_t, *wargs, START[start],
-                  _device_ptr(loss), _device_ptr(grad), 1)
+        _lib.call(name, traj._require("trajectory"), self.bank._h, ids.ctypes.data, *args, _device_ptr(loss), _device_ptr(grad), 1)
         return loss, grad
 
     def step(self, traj, policy_ids, target=None, start="initial", updates=1, wait=True, weight=None):
@@ -428,28 +420,18 @@ class BankDistiller:
         the work is enqueued on the engine's stream: a rollout of the bank asked for next flies the updated weights."""
         ids, updates = self._check(traj, policy_ids, start, updates)
         P = int(self.bank.n_policies)
-        w = None if weight is None else _loss_weight(traj, weight)
-        ptr, ld_t, on_device, keep = Distiller._target(traj, target)
-        opt = self._handle()
-        dev = Distiller._torch_device(traj)
-        if on_device is False:
-            dev = None
-        traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1
-        name, wargs, wkeep = "rq_trajectory_policies_distill", (), None
-        if w is not None:
-            wptr, wkeep = _weight_pointer(w[0], dev)
-            name, wargs = name + "_weighted", (wptr, w[1], w[2])
+        suffix, opt, args, dev, keep = _loss_call(traj, target, weight, start, self._handle, True)
+        name = "rq_trajectory_policies_distill" + suffix
         if dev is None:
             losses = np.empty((updates, P), np.float32)
-            _lib.call(name, traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, ptr, ld_t, *wargs, START[start], updates,
-                      _lib.fptr(losses), 0)
+            _lib.call(name, traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, *args, updates, _lib.fptr(losses), 0)
         else:
             import torch
             losses = torch.empty((updates, P), dtype=torch.float32, device=dev)
             torch.cuda.current_stream(dev).synchronize()      # once per call, not per update
-            _lib.call(name, traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, ptr, ld_t, *wargs, START[start], updates,
-                      _device_ptr(losses), 1 if wait else 2)
-        self._target_in_flight = keep      # until the next step: with wait=False the engine's stream may not have read it yet
-        self._weight_in_flight = wkeep
+            _lib.call(name, traj._require("trajectory"), self.bank._h, opt, ids.ctypes.data, *args, updates, _device_ptr(losses),
+                      1 if wait else 2)
+        # until the next step: with wait=False the engine's stream may not have read the target or the weight yet
+        self._target_in_flight, self._weight_in_flight = keep
         self.bank._weights_on_device = True
         return losses

@@ -41,14 +41,15 @@ def _record(device, oracle, n, T, seed, frozen=True, finite=True):
     w.vector.rollout(device, w.env, w.params, w.state, w.policy, w.rng, T - T1, "fused", autoreset=True, trajectory=traj)
     # terminations (code 1) are rare in a short recording of the shipped policy; for the policy codes 1 and 2 are the same event
     # (an episode end), so every other step-limit end is relabelled a termination in place
+    import torch
     done = traj.tensors()["done"]
     ends = (done == 2).nonzero()
     done[ends[::2, 0], ends[::2, 1]] = 1
     if finite:
-        import torch
         obs = traj.tensors()["obs"]
         draw = torch.randn(obs.shape, device=obs.device, generator=torch.Generator(obs.device).manual_seed(seed))
         obs.copy_(torch.where((done == 4)[:, None, :], draw, obs))
+    torch.cuda.synchronize()            # the engine's stream does not order itself against torch's: traj.numpy() must see these writes
     return w, traj
 
 

@@ -444,6 +444,41 @@ def test_the_fused_route_names_the_family_and_the_register_build_of_every_launch
     assert got[(65536, 0, 0, 0, 1, 0, 0)] == ("PLAIN", "ActorF32") and got[(65537, 0, 0, 0, 1, 0, 0)] == ("PLAIN", "ActorF32Lean")
 
 
+def test_the_loss_workspace_layout_is_the_two_sizes_of_before_and_its_regions_do_not_meet(tmp_path):
+    """rq::loss_partial_layout (raptor_amd/csrc/rq_loss_launch.hpp) is the one statement of where a loss launch's waves leave their
+    partial gradients, squared errors and normalisers: the launcher carves the workspace by it and the C layer reserves by it.
+    tests/loss_launch_driver.cpp includes the header alone under a plain host compiler and prints the layout of 7 batch sizes (a
+    partial wave, wave boundaries, both sides of 65 536) in both forms.  Held here against figures written down here: the totals
+    the launchers reserved before the layout had one statement - waves x (2084 + 2) floats, weighted waves x (2084 + 3) - and what
+    each region must hold: 2084 floats per wave, a float per wave, and a uint32 (unweighted) or a float64 (weighted) per wave."""
+    import subprocess
+    exe = str(tmp_path / "loss_launch_driver")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "raptor_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "loss_launch_driver.cpp")], check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = {}
+    for line in r.stdout.splitlines():
+        n, weighted, *rest = map(int, line.split())
+        assert (n, weighted) not in got, line
+        got[(n, weighted)] = rest
+    assert sorted(got) == sorted((n, w) for n in (1, 64, 65, 129, 65536, 65537, 70001) for w in (0, 1))
+    for (n, weighted), (waves, floats, partial, wsum, sse, live) in got.items():
+        assert waves == -(-n // 64), (n, weighted)
+        assert floats == waves * (2084 + 3 if weighted else 2084 + 2), (n, weighted)
+        # [begin, end) in floats of every region the form has; the one it does not have is empty
+        regions = [(partial, partial + waves * 2084), (sse, sse + waves)]
+        regions.append((wsum, wsum + 2 * waves) if weighted else (live, live + waves))
+        absent = live if weighted else wsum
+        assert absent == floats, (n, weighted)
+        regions.sort()
+        assert regions[0][0] >= 0 and regions[-1][1] <= floats, (n, weighted, regions)
+        assert all(a[1] <= b[0] for a, b in zip(regions, regions[1:])), (n, weighted, regions)
+        assert sum(e - b for b, e in regions) == floats, (n, weighted)      # and nothing is left over
+        if weighted:
+            assert wsum % 2 == 0, (n, wsum)      # float64 from a 256-byte aligned base: an even float offset is 8-byte aligned
+
+
 def test_the_hazard_lint_sees_a_move_behind_a_taken_branch():
     """The lint on a reduced rendition of the build it was written for: the move on the taken path (4 and 5 wait states behind
     the MFMA) is reported, the padded variant is not."""
