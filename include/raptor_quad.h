@@ -41,6 +41,8 @@
  *   distillation: the student's regression gradient    :208-216 rq_trajectory_policy_forward / _backward + rq_policy_set_weights;
  *                                                              rq_trajectory_distill (loss, Adam and repack on the device);
  *                                                              rq_trajectory_*_weighted (a weight per env or per env and step)
+ *   distillation: which teachers the student imitates
+ *     badly, and how the error falls with episode age   :208-216 rq_trajectory_policy_error_table / rq_trajectory_policies_error_table
  *   (the reference is single-process) env shards over
  *     GPUs + all-gather of episode returns (RCCL)                rq_env_create(global_env_offset) / rq_comm_* / rq_allgather_returns
  *
@@ -854,6 +856,40 @@ RQ_API int rq_trajectory_policies_distill_weighted(rq_trajectory* t, rq_policy_b
                                                    const uint32_t* policy_id, const float* target, uint32_t ld_target,
                                                    const float* weight, uint32_t ld_weight, uint32_t weight_steps, int start,
                                                    uint32_t n_updates, float* losses, int memory);
+
+/* ---- Imitation error per env and episode age: how well the student imitates, as a table, from the forward alone - which teachers it
+ * imitates badly (group the envs by teacher), how the error falls with episode age (the in-context adaptation curve), a held-out
+ * loss without a backward, the error per setpoint, wrench scenario or policy of a sweep: all sums of this one table.
+ * The actions a_t are those of rq_trajectory_policy_forward, bit for bit (the same step, the same episode rules, the same start);
+ * the target y [T][4][ld_target] is the loss calls' (NULL: the trajectory's stored actions, ld_target ignored).  AGE is the probes':
+ * 0 at the first recorded step; a step is live when its done code is not 4; after a live step with code 1 or 2 the age is 0 again,
+ * after any other live step one more; frozen steps neither count nor age.  age_edges: host array [n_buckets + 1], strictly ascending,
+ * 1 <= n_buckets <= 32, read before the call returns; a live step of age k belongs to bucket b when age_edges[b] <= k <
+ * age_edges[b + 1], a live step outside every bucket is counted nowhere.  Per live step, in fp32, every operation rounded once and
+ * none fused:  d_k = a_k - y_k,  e = ((d_0 d_0 + d_1 d_1) + d_2 d_2) + d_3 d_3.
+ * sse [n_buckets][ld_out]: sse[b][i] = the sequential fp32 sum, in time order, of e over the steps of env i in bucket b (an env that
+ * returns to a bucket in a later episode goes on from its total); count [n_buckets][ld_out]: the number of those steps.  ld_out >=
+ * n_envs; every cell (b, i < n_envs) is written, columns >= n_envs are left as they were.  A frozen step, a step outside the buckets
+ * and a padding column are selected away before any arithmetic: NaN in their targets or observations reaches no sum.  One lane sums
+ * one env: no atomics, the same bits every run.  sum(sse) / (4 sum(count)) over all cells of edges {0, 2^32 - 1} is the masked MSE
+ * of rq_trajectory_policy_loss_grad, summed in another order.
+ * rq_trajectory_policies_error_table: the same for a bank, env i by policy policy_id[i] (host array, constant on every aligned block
+ * of 64); a column block holds, bit for bit, what a rq_policy created from that policy's weights gives on it.
+ * The calls read the recording and the policy and leave the trajectory's saved state alone: a rq_trajectory_policy_backward whose
+ * forward came before the call may follow it and gives what it would have given without it.  The policy's hidden state is not changed.
+ * memory: RQ_DST_HOST = target, sse and count are host arrays (synchronous); RQ_DST_DEVICE / RQ_DST_DEVICE_ASYNC = device memory of
+ * the trajectory's device (synchronised before return / only enqueued on rq_device_stream()).
+ * Refused before anything is enqueued, outputs untouched: every refusal of rq_trajectory_policy_loss_grad /
+ * rq_trajectory_policies_loss_grad (a bf16 / f16x2 policy, a Standardize or SampleAndSquash stage, a native interval above 1,
+ * objects of two devices, an empty trajectory, ld_target < n_envs, a target that is not device memory when one is announced, bad
+ * ids); ld_out < n_envs; n_buckets outside 1 .. 32; edges that do not ascend strictly; a null argument; sse or count that is not
+ * device memory of the trajectory's device when one is announced. */
+RQ_API int rq_trajectory_policy_error_table(rq_trajectory* t, rq_policy* policy, const float* target, uint32_t ld_target,
+                                            const uint32_t* age_edges, uint32_t n_buckets, int start, float* sse, uint32_t* count,
+                                            uint32_t ld_out, int memory);
+RQ_API int rq_trajectory_policies_error_table(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target,
+                                              uint32_t ld_target, const uint32_t* age_edges, uint32_t n_buckets, int start,
+                                              float* sse, uint32_t* count, uint32_t ld_out, int memory);
 
 
 /* ---- Multi-GPU: the path's one exchange ---------------------------------------------

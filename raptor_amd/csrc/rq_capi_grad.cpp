@@ -4,6 +4,8 @@
 // masked-MSE loss and gradient (rq_trajectory_policy_loss_grad), Adam and the operand images (rq_trajectory_distill); and that update
 // for every policy of a policy bank at once (rq_trajectory_policies_loss_grad, rq_bank_optimizer_*, rq_trajectory_policies_distill).
 // The four loss calls have a *_weighted sibling each - a weight per env, or per env and step, in the loss - that shares their body.
+// rq_trajectory_policy_error_table / rq_trajectory_policies_error_table: the forward alone against the loss calls' target - the
+// squared imitation error per env and bucket of episode age; the trajectory's saved state is not theirs and stays as it was.
 // Every call with a `memory` argument reads refusals, DeviceScope, prepare, in, launch, out, finish: the staging copies and the final
 // wait are one rq::CallMemory (rq_call_memory.hpp), the staging buffers are reserved here.  Kernels: rq_grad.hpp, rq_grad_bank.hpp.
 #include "rq_objects.hpp"
@@ -200,6 +202,71 @@ int bank_loss_begin(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* poli
     a->wave_offsets = bank->waves; a->wave_list = bank->waves + bank->n_policies + 1;
     a->hidden = start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr;
     a->ld_h = bank->ld;
+    return RQ_OK;
+}
+
+// ---- the imitation error table (rq_trajectory_policy_error_table / rq_trajectory_policies_error_table) ----
+// error_table_check: what the two calls refuse beyond their loss sibling's refusals (loss_check / bank_loss_check, which come first and
+// have found `memory` valid), before the call's DeviceScope; -> the buckets in *a.  error_table_begin, inside it: the recording, the
+// target and the outputs as the launch takes them.  The trajectory's saved state - t->grad.saved, its stamp - is not touched: the
+// kernel stores nothing of the pass, and a rq_trajectory_policy_backward whose forward came before may follow.
+// RQ_DST_HOST announces host arrays: device memory in their place is refused by name rather than handed to a host-to-device copy
+int check_host_array(const CallMemory& mem, const void* p, const char* what, const char* noun) {
+    if (!mem.host() || !p) return RQ_OK;
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();         // pageable memory the runtime has not seen: the query's error stays here
+    RQ_REQUIRE(!(e == hipSuccess && at.type == hipMemoryTypeDevice), RQ_ERR_SHAPE_MISMATCH,
+               std::string(what) + ": " + noun + " is device memory: RQ_DST_HOST expects a host array (RQ_DST_DEVICE takes device memory)");
+    return RQ_OK;
+}
+
+int error_table_check(const char* what, rq_trajectory* t, const float* target, const uint32_t* age_edges, uint32_t n_buckets, float* sse,
+                      uint32_t* count, uint32_t ld_out, int memory, rq::ErrorTableLaunch* a) {
+    RQ_REFUSE(what, age_edges, RQ_ERR_INVALID_ARGUMENT, "null argument: age_edges");
+    RQ_REFUSE(what, sse, RQ_ERR_INVALID_ARGUMENT, "null argument: sse");
+    RQ_REFUSE(what, count, RQ_ERR_INVALID_ARGUMENT, "null argument: count");
+    RQ_REFUSE(what, n_buckets >= 1 && n_buckets <= rq::kErrorTableMaxBuckets, RQ_ERR_INVALID_ARGUMENT,
+              "n_buckets must be 1 .. 32, not " + std::to_string(n_buckets));
+    for (uint32_t b = 0; b <= n_buckets; ++b) {
+        RQ_REFUSE(what, b == 0 || age_edges[b] > age_edges[b - 1], RQ_ERR_INVALID_ARGUMENT,
+                  "age_edges must ascend strictly (age_edges[" + std::to_string(b) + "] does not)");
+        a->edges[b] = age_edges[b];
+    }
+    a->n_buckets = n_buckets;
+    RQ_REFUSE(what, ld_out >= t->env->n, RQ_ERR_INVALID_ARGUMENT, "ld_out must be at least the number of envs");
+    const rq_device* dev = t->env->dev;
+    const CallMemory mem(memory, dev->stream, dev->ordinal);
+    int rc = check_device_array(mem, sse, what, "sse"); if (rc) return rc;
+    rc = check_device_array(mem, count, what, "count"); if (rc) return rc;
+    rc = check_host_array(mem, target, what, "the target"); if (rc) return rc;
+    rc = check_host_array(mem, sse, what, "sse"); if (rc) return rc;
+    return check_host_array(mem, count, what, "count");
+}
+
+int error_table_begin(rq_trajectory* t, const float* target, uint32_t ld_target, int start, CallMemory& mem, float* sse, uint32_t* count,
+                      uint32_t ld_out, rq::ErrorTableLaunch* a) {
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    const uint32_t T = t->length, ld = env->ld, B = a->n_buckets;
+    rq::LossLaunch& p = a->pass;
+    p.n = env->n; p.ld = ld; p.steps = T;
+    p.obs = t->obs; p.done = t->done;
+    p.start_initial = start == RQ_GRAD_START_INITIAL;
+    p.target = t->act.get();           // the stored actions: what a relabel or a teacher-acting rollout left
+    p.ld_y = target ? ld_target : ld;
+    // host-memory calls: one device block, sse [B][ld] | count [B][ld] | the target; only the envs' columns go back
+    const size_t cells = (size_t)B * ld, y_floats = target ? (size_t)T * RQ_ACTION_DIM * ld_target : 0;
+    float* s_sse = nullptr; uint32_t* s_count = nullptr;
+    if (mem.host()) {
+        RQ_HIP(t->grad.rows.reserve(dev->stream, 2 * cells + y_floats));
+        s_sse = t->grad.rows.get();
+        s_count = reinterpret_cast<uint32_t*>(s_sse + cells);
+    }
+    if (target) RQ_HIP(mem.in(target, y_floats, mem.host() ? s_sse + 2 * cells : nullptr, &p.target));
+    a->sse = mem.out(sse, ld_out, s_sse, ld, env->n, B);
+    a->count = mem.out(count, ld_out, s_count, ld, env->n, B);
+    a->ld_out = mem.host() ? ld : ld_out;
     return RQ_OK;
 }
 
@@ -536,6 +603,56 @@ RQ_API int rq_trajectory_policies_distill_weighted(rq_trajectory* t, rq_policy_b
                                                    uint32_t n_updates, float* losses, int memory) {
     return policies_distill(t, bank, opt, policy_id, target, ld_target, LossWeight{true, weight, ld_weight, weight_steps}, start,
                             n_updates, losses, memory, "rq_trajectory_policies_distill_weighted");
+}
+
+// ---------------------------------------------------------------------------- the imitation error table ---
+RQ_API int rq_trajectory_policy_error_table(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target,
+                                            const uint32_t* age_edges, uint32_t n_buckets, int start, float* sse, uint32_t* count,
+                                            uint32_t ld_out, int memory) {
+    const char* what = __func__;
+    RQ_REQUIRE(t && pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = loss_check(t, pol, target, ld_target, kNoWeight, start, memory, what); if (rc) return rc;
+    rq::ErrorTableLaunch a;
+    rc = error_table_check(what, t, target, age_edges, n_buckets, sse, count, ld_out, memory, &a); if (rc) return rc;
+    rq_device* dev = t->env->dev;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, t->env->n); if (rc) return rc; }
+    rc = error_table_begin(t, target, ld_target, start, mem, sse, count, ld_out, &a); if (rc) return rc;
+    a.pass.packed = pol->w_packed;
+    a.pass.hidden = start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr;
+    a.pass.ld_h = pol->ld;
+    RQ_HIP(rq::launch_policy_error_table(dev->stream, a));
+    RQ_HIP(mem.finish());
+    return RQ_OK;
+}
+
+RQ_API int rq_trajectory_policies_error_table(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const float* target,
+                                              uint32_t ld_target, const uint32_t* age_edges, uint32_t n_buckets, int start, float* sse,
+                                              uint32_t* count, uint32_t ld_out, int memory) {
+    const char* what = __func__;
+    RQ_REQUIRE(t && bank && policy_id, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = bank_loss_check(t, bank, policy_id, target, ld_target, kNoWeight, start, memory, what); if (rc) return rc;
+    rq::ErrorTableLaunch a;
+    rc = error_table_check(what, t, target, age_edges, n_buckets, sse, count, ld_out, memory, &a); if (rc) return rc;
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    if (start == RQ_GRAD_START_CURRENT) {
+        rc = bank_size(bank, env->n); if (rc) return rc;
+        RQ_REQUIRE(bank->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");
+    }
+    rc = bank_table(bank, dev, env->uid, policy_id, env->n); if (rc) return rc;
+    if (start == RQ_GRAD_START_CURRENT) { rc = bank_apply_reset(bank); if (rc) return rc; }
+    rc = error_table_begin(t, target, ld_target, start, mem, sse, count, ld_out, &a); if (rc) return rc;
+    a.pass.packed = bank->images;
+    a.pass.n_policies = bank->n_policies; a.pass.block_policy = bank->table;
+    a.pass.hidden = start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr;
+    a.pass.ld_h = bank->ld;
+    RQ_HIP(rq::launch_policy_error_table(dev->stream, a));
+    RQ_HIP(mem.finish());
+    return RQ_OK;
 }
 
 }  // extern "C"

@@ -21,6 +21,9 @@
 //   k_policy_loss_backward_weighted[_bank]   dL/da = w (a - y) where the entry is live and w > 0; + per wave the weighted squared
 //                                            error and, in float64, the sum of the counting weights
 //   k_policy_loss_reduce_weighted[_bank]     the reductions above with W4 = that sum over the waves, in wave order, in M's place
+// How well the student imitates, per env and bucket of episode age, from the forward alone:
+//   k_policy_error_table[_bank]   the forward storing nothing of the pass: the lane sums its env's squared error (a - y)^2 over the
+//                                 four actions per age bucket, sse / count [n_buckets][ld_out]; launch_policy_error_table
 // The forwards, the backwards, the loss reductions and the Adam kernels are one text each (rq_grad_forward.inc, rq_grad_backward.inc,
 // rq_loss_reduce.inc, rq_adam_repack.inc), compiled once per kernel.  Every form of the loss launch goes through one launcher,
 // launch_policy_loss_grad (rq_grad_bank.hpp), from one description (rq_loss_launch.hpp).
@@ -43,6 +46,7 @@
 #include <stdint.h>
 
 #include "rq_rollout.hpp"      // the actors, field(), kFusedBlock, WavesPerSimd
+#include "rq_probe.hpp"        // ProbeEdges, kProbeMaxBuckets: the error table's age buckets are the probe's
 
 namespace rq {
 
@@ -60,6 +64,14 @@ namespace rq {
 #define RQ_GRAD_FORWARD_KERNEL k_policy_grad_forward_state
 #define RQ_GRAD_STORE_ACT 0
 #define RQ_GRAD_BANK 0
+#include "rq_grad_forward.inc"
+
+// the same pass storing nothing of it: the squared imitation error against a target, per env and bucket of episode age, summed in
+// the lane (rq_grad_forward.inc, RQ_GRAD_ERROR_TABLE) - 16 B/env-step of target read in place of 80 B/env-step of stores
+#define RQ_GRAD_FORWARD_KERNEL k_policy_error_table
+#define RQ_GRAD_STORE_ACT 0
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_ERROR_TABLE 1
 #include "rq_grad_forward.inc"
 
 // ------------------------------------------------------------------ backward -----------

@@ -9,6 +9,7 @@
 //   k_policy_loss_reduce_weighted_bank     policy p: as above with W4_p, its waves' float64 weight sums    (ceil(2084 / 256), P)
 //   k_adam_repack_bank                 k_adam_repack on slot p; a policy that owns no wave is skipped       P
 //   k_adam_set_lr_bank                 up to 256 learning rates, carried as kernel arguments                1
+//   k_policy_error_table_bank          k_policy_error_table, the wave's image picked per block             waves
 // The weights are wave-uniform MFMA operands read once from an image pointer, so the seeded pair is the single policy's text
 // (rq_grad_forward.inc, rq_grad_backward.inc under RQ_GRAD_BANK) with that pointer chosen by block_policy[blockIdx.x], as
 // k_rollout_fused_bank chooses it: a wave computes what it computes for a policy of its own, bit for bit.  The reduction is the single
@@ -25,6 +26,13 @@ namespace rq {
 #define RQ_GRAD_FORWARD_KERNEL k_policy_grad_forward_state_bank
 #define RQ_GRAD_STORE_ACT 0
 #define RQ_GRAD_BANK 1
+#include "rq_grad_forward.inc"
+
+// k_policy_error_table with the wave's image picked per block (rq_grad_forward.inc under RQ_GRAD_BANK and RQ_GRAD_ERROR_TABLE)
+#define RQ_GRAD_FORWARD_KERNEL k_policy_error_table_bank
+#define RQ_GRAD_STORE_ACT 0
+#define RQ_GRAD_BANK 1
+#define RQ_GRAD_ERROR_TABLE 1
 #include "rq_grad_forward.inc"
 
 #define RQ_GRAD_BACKWARD_KERNEL k_policy_loss_backward_bank
@@ -121,6 +129,38 @@ hipError_t launch_policy_loss_grad(hipStream_t s, const LossLaunch& a) {
     else
         k_policy_loss_reduce<<<rgrid, 256, 0, s>>>(lay.waves, partial, wave_sse, wave_live, a.grad, a.loss, a.live);
     return hipGetLastError();
+}
+
+// the error table of a launch in the build `Actor`: the single kernel or the bank's, picked here and nowhere else
+template <typename Actor>
+static hipError_t launch_error_table(hipStream_t s, const ErrorTableLaunch& a, const ProbeEdges& edges) {
+    const LossLaunch& p = a.pass;
+    const unsigned g = (p.n + kFusedBlock - 1) / kFusedBlock;
+    const uint32_t si = p.start_initial ? 1u : 0u;
+    if (p.block_policy)
+        k_policy_error_table_bank<Actor><<<g, kFusedBlock, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.block_policy, (uint32_t)RQ_PACKED_FLOATS, p.obs,
+                                                                   p.done, p.hidden, p.ld_h, si, p.target, p.ld_y, edges, a.n_buckets, a.sse,
+                                                                   a.count, a.ld_out);
+    else
+        k_policy_error_table<Actor><<<g, kFusedBlock, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.obs, p.done, p.hidden, p.ld_h, si, p.target, p.ld_y,
+                                                              edges, a.n_buckets, a.sse, a.count, a.ld_out);
+    return hipGetLastError();
+}
+
+// The error table (rq_loss_launch.hpp ErrorTableLaunch): one launch, the forward's choice of build.  A description whose strides or
+// buckets would let a lane read or write beside its column is refused here, whatever the caller checked.
+hipError_t launch_policy_error_table(hipStream_t s, const ErrorTableLaunch& a) {
+    static_assert(kErrorTableMaxBuckets == kProbeMaxBuckets, "the error table's buckets are the probe's");
+    const LossLaunch& p = a.pass;
+    if (p.n == 0 || p.steps == 0 || (p.block_policy && p.n_policies == 0)) return hipErrorInvalidValue;
+    if (a.n_buckets < 1 || a.n_buckets > kErrorTableMaxBuckets || a.ld_out < p.n || p.ld_y < p.n || p.ld < p.n) return hipErrorInvalidValue;
+    if (!p.packed || !p.obs || !p.done || !p.target || !a.sse || !a.count || (!p.start_initial && !p.hidden)) return hipErrorInvalidValue;
+    ProbeEdges edges{};
+    for (uint32_t b = 0; b <= a.n_buckets; ++b) {
+        if (b > 0 && a.edges[b] <= a.edges[b - 1]) return hipErrorInvalidValue;
+        edges.v[b] = a.edges[b];
+    }
+    return p.n > kOneWavePerSimdEnvs ? launch_error_table<ActorF32Lean>(s, a, edges) : launch_error_table<ActorF32>(s, a, edges);
 }
 
 hipError_t launch_adam_repack_bank(hipStream_t s, uint32_t n_policies, const uint32_t* wave_offsets, const float* grad, float* w, float* m,

@@ -1,6 +1,7 @@
 // rq_loss_launch.hpp - what one loss-and-gradient launch of the learner is (LossLaunch; launch_policy_loss_grad, rq_grad_bank.hpp,
 // reads it and the C layer, rq_capi_grad.cpp, fills it), and where the per-wave regions of its workspace lie (loss_partial_layout:
-// the one statement of that layout - the launcher carves by it, the C layer reserves by it).  Host code without a HIP dependency: a
+// the one statement of that layout - the launcher carves by it, the C layer reserves by it); and its sibling without a backward, the
+// error table's launch (ErrorTableLaunch; launch_policy_error_table).  Host code without a HIP dependency: a
 // plain host compiler takes this file alone (tests/loss_launch_driver.cpp does, and holds the layout against tests/test_capi_cpu.py's
 // own figures).
 #pragma once
@@ -65,6 +66,21 @@ struct LossLaunch {
     float* grad = nullptr;
     float* loss = nullptr;
     unsigned long long* live = nullptr; // a single policy, unweighted: [1] = the live entries
+};
+
+// One error-table launch (launch_policy_error_table, rq_grad_bank.hpp): the forward alone, storing nothing of the pass, and the squared
+// imitation error per env and bucket of episode age.  `pass` is read as a loss launch's forward reads it - n, ld, steps, packed (a
+// bank: block_policy and n_policies too), obs, done, hidden, ld_h, start_initial, target, ld_y; `saved`, the transposed images, the
+// weight, the workspace and the loss outputs are not touched.
+constexpr uint32_t kErrorTableMaxBuckets = 32;      // the probe's (rq_probe.hpp kProbeMaxBuckets)
+struct ErrorTableLaunch {
+    LossLaunch pass;
+    uint32_t n_buckets = 0;                           // 1 .. kErrorTableMaxBuckets
+    uint32_t edges[kErrorTableMaxBuckets + 1] = {};   // edges[0 .. n_buckets], strictly ascending: bucket b holds ages [edges[b], edges[b + 1])
+    // sse [n_buckets][ld_out] and count [n_buckets][ld_out], ld_out >= n: every cell (b, i < n) is written, columns >= n are left
+    float* sse = nullptr;
+    uint32_t* count = nullptr;
+    uint32_t ld_out = 0;
 };
 
 }  // namespace rq

@@ -24,6 +24,13 @@ Entries can be weighted, per env or per env and step, without leaving that path 
 
 ``weighted_mse`` is the same loss in torch, for the first way; any loss beyond that goes the first way too.
 
+How well the student imitates - per env and per bucket of episode age - is one forward pass, no backward (rq_trajectory_policy_error_table):
+
+    table = imitation_error(traj, policy, edges=probing.log_age_edges(500, 10), target=labels)   # sse, count [B, N]
+    table.by_age()                                          # the in-context adaptation curve, [B]
+    table.by_group(teacher_of, n_teachers)                  # which teachers the student imitates badly, [G, B]
+    table.loss()                                            # the masked MSE: a held-out loss without a backward
+
 A sweep or a seed population is distilled in one go: ``BankDistiller`` runs that update for every policy of a
 ``policy_bank.PolicyBank`` at once, each on the 64-env blocks of the recording that ``policy_ids`` deals it, with its own
 hyper-parameters - one student's launch count for the whole bank, and the bank flies its next rollout with the updated weights:
@@ -332,6 +339,136 @@ def _loss_call(traj, target, weight, start, handles, host_ok):
     if dev is None and on_device and not host_ok:
         raise ValueError("a device target needs torch")
     return suffix, h, (ptr, ld_t, *wargs, START[start]), dev, (keep, wkeep)
+
+
+MAX_BUCKETS = 32              # rq::kErrorTableMaxBuckets, the probes' limit
+
+
+class ErrorTable:
+    """What ``imitation_error`` returns: ``sse`` [B, N] float32 - per age bucket and env the sum over its live steps of the squared
+    imitation error (a - y)^2 summed over the four actions -, ``count`` [B, N] - the number of those steps - and ``edges`` [B + 1]
+    (uint32, NumPy).  The arrays are NumPy or torch tensors, as the call made them; every method below works in float64 on whatever
+    they are and returns the same kind.  A mean over nothing is NaN."""
+
+    def __init__(self, sse, count, edges):
+        self.sse, self.count = sse, count
+        self.edges = np.asarray(edges, np.uint32)
+        if len(sse.shape) != 2 or tuple(sse.shape) != tuple(count.shape) or self.edges.shape != (sse.shape[0] + 1,):
+            raise ValueError("sse and count must be [B, N] and edges [B + 1]")
+
+    def _f64(self):
+        if hasattr(self.sse, "data_ptr"):
+            import torch
+            return self.sse.to(torch.float64), self.count.to(torch.float64)
+        return np.asarray(self.sse, np.float64), np.asarray(self.count, np.float64)
+
+    @staticmethod
+    def _mean(s, c):
+        """s / (4 c) where c > 0, NaN elsewhere"""
+        if hasattr(s, "data_ptr"):
+            import torch
+            return torch.where(c > 0, s / (4.0 * torch.clamp(c, min=1.0)), torch.full_like(s, float("nan")))
+        return np.where(c > 0, s / (4.0 * np.maximum(c, 1.0)), np.nan)
+
+    def mse(self):
+        """-> [B, N]: the mean squared error per action of env i at the ages of bucket b"""
+        return self._mean(*self._f64())
+
+    def per_env(self):
+        """-> [N]: every env's error over all buckets - with ``edges=None`` its error over the whole recording"""
+        s, c = self._f64()
+        return self._mean(s.sum(0), c.sum(0))
+
+    def by_age(self):
+        """-> [B]: the error of all envs by age bucket, the in-context adaptation curve"""
+        s, c = self._f64()
+        return self._mean(s.sum(1), c.sum(1))
+
+    def by_group(self, ids, n_groups):
+        """``ids`` [N] integers below ``n_groups`` - the teacher, reference, wrench scenario or policy of every env -> [G, B]: the
+        error of each group's envs by age bucket."""
+        s, c = self._f64()
+        G, N = int(n_groups), int(s.shape[1])
+        g = np.asarray(ids.cpu() if hasattr(ids, "data_ptr") else ids)
+        if g.shape != (N,) or not np.issubdtype(g.dtype, np.integer) or (N and (g.min() < 0 or g.max() >= G)):
+            raise ValueError(f"ids must be [{N}] integers below {G}")
+        if hasattr(s, "data_ptr"):
+            import torch
+            at = torch.as_tensor(g.astype(np.int64), device=s.device)
+            zero = torch.zeros((G, s.shape[0]), dtype=torch.float64, device=s.device)
+            return self._mean(zero.index_add(0, at, s.T), zero.index_add(0, at, c.T))
+        gs, gc = np.zeros((G, s.shape[0])), np.zeros((G, s.shape[0]))
+        np.add.at(gs, g, s.T)
+        np.add.at(gc, g, c.T)
+        return self._mean(gs, gc)
+
+    def loss(self):
+        """-> the masked MSE over everything the table counts: sum(sse) / (4 sum(count)).  With ``edges=None`` that is the loss of
+        ``Distiller.loss_and_grad`` on the same recording and target, summed in another order."""
+        s, c = self._f64()
+        return self._mean(s.sum(), c.sum())
+
+
+def _age_edges(edges):
+    """The refusals Python makes itself for ``edges=`` -> uint32 [B + 1]; None: one bucket for every age."""
+    if edges is None:
+        return np.asarray([0, 2 ** 32 - 1], np.uint32)
+    e = np.asarray(edges)
+    if e.ndim != 1 or not 2 <= e.size <= MAX_BUCKETS + 1 or not (np.issubdtype(e.dtype, np.integer) or np.all(e == np.floor(e))):
+        raise ValueError(f"edges must be 2 .. {MAX_BUCKETS + 1} strictly ascending uint32 values")
+    e = e.astype(np.int64) if not np.issubdtype(e.dtype, np.unsignedinteger) else e.astype(np.uint64)
+    if (e[1:] <= e[:-1]).any() or e[0] < 0 or e[-1] >= 1 << 32:
+        raise ValueError(f"edges must be 2 .. {MAX_BUCKETS + 1} strictly ascending uint32 values")
+    return np.ascontiguousarray(e.astype(np.uint32))
+
+
+def imitation_error(traj, policy, edges=None, target=None, start="initial", policy_ids=None):
+    """How well ``policy`` imitates ``target`` on the recording, per env and bucket of episode age -> ``ErrorTable``.  One forward
+    pass on the device (rq_trajectory_policy_error_table): no backward, no action tensor, no pass over the done codes on the host.
+
+    ``policy``: a ``Raptor`` (fp32, no Standardize / SampleAndSquash stage, native rate), or a ``PolicyBank`` together with
+    ``policy_ids`` - one id per env, constant on every aligned block of 64 -, each env scored under its own policy.  ``edges``:
+    [B + 1] strictly ascending episode ages, B <= 32 (``probing.log_age_edges``); a live step of age k falls in bucket b when
+    ``edges[b] <= k < edges[b + 1]`` and is counted nowhere outside them; None: one bucket for every age, the per-env error.  Age is
+    the probes': 0 at the first recorded step and after an episode end, one more after every other live step; frozen steps neither
+    count nor age.  ``target`` and ``start`` as for ``Distiller``.
+
+    The table's arrays are device tensors when torch is present and the target is not NumPy, NumPy otherwise; the call orders itself
+    against torch's current stream as ``Distiller.loss_and_grad`` does.  The trajectory's saved state is not touched: a pending
+    ``trajectory_actions`` backward stays valid."""
+    if start not in START:
+        raise ValueError('start must be "initial" or "current"')
+    e = _age_edges(edges)
+    N = int(traj._env.N_ENVIRONMENTS)
+    bank = hasattr(policy, "n_policies")
+    if bank and policy_ids is None:
+        raise ValueError("a PolicyBank needs policy_ids: one id per env, constant on every aligned block of 64")
+    if not bank and policy_ids is not None:
+        raise ValueError("policy_ids belong to a PolicyBank")
+    ids = None
+    if bank:
+        from .policy_bank import check_policy_ids
+        ids = check_policy_ids(policy_ids, policy.n_policies, N)
+    ptr, ld_t, on_device, keep = Distiller._target(traj, target)
+    if target is not None and ld_t < N:
+        raise ValueError(f"target must be [{len(traj)}, 4, >= N]: {ld_t} columns for {N} envs")
+    head = (policy._h, ids.ctypes.data) if bank else (policy._handle(traj._env._device),)
+    name = "rq_trajectory_policies_error_table" if bank else "rq_trajectory_policy_error_table"
+    dev = Distiller._torch_device(traj) if on_device is not False else None
+    if dev is None and on_device:
+        raise ValueError("a device target needs torch")
+    B = e.size - 1
+    if dev is None:
+        sse, count = np.empty((B, N), np.float32), np.empty((B, N), np.uint32)
+        _lib.call(name, traj._require("trajectory"), *head, ptr, ld_t, e.ctypes.data, B, START[start], _lib.fptr(sse), count.ctypes.data, N, 0)
+        return ErrorTable(sse, count, e)
+    import torch
+    sse = torch.empty((B, N), dtype=torch.float32, device=dev)
+    count = torch.empty((B, N), dtype=torch.int32, device=dev)          # the engine's uint32; a recording has fewer than 2^31 steps
+    torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
+    _lib.call(name, traj._require("trajectory"), *head, ptr, ld_t, e.ctypes.data, B, START[start], _device_ptr(sse), _device_ptr(count), N, 1)
+    del keep
+    return ErrorTable(sse, count, e)
 
 
 def _per_policy(name, value, n_policies):
