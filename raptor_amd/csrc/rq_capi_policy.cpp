@@ -363,8 +363,11 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
         if (rx.running) {
             rc = mailbox_put_in(dev, observation, batch, RQ_POLICY_INPUT_DIM, obs_stride); if (rc) return rc;     // what a replay reads
             const rq::Mailbox mb = mailbox_for(dev, true, RQ_POLICY_INPUT_DIM, MbOut::out);
-            resident_post(dev, PolicyCmd{batch, packed_of(pol), pol->obs, pol->hidden, pol->ld, pol->act, pol->precision,
-                                         sas_of(pol, pol->sas_counter, nullptr, 0), mb});
+            PolicyCmd cmd;      // what a replay launches: the rows in, in place, the actions out
+            cmd.n = batch; cmd.packed = packed_of(pol); cmd.obs = pol->obs; cmd.ld_obs = pol->ld; cmd.hidden = pol->hidden; cmd.ld_h = pol->ld;
+            cmd.act = pol->act; cmd.ld_act = pol->ld; cmd.precision = pol->precision; cmd.sas = sas_of(pol, pol->sas_counter, nullptr, 0);
+            cmd.mb = mb;
+            resident_post(dev, cmd);
             pol->version = fresh_version();                 // as policy_size does for the launch: the hidden state moves on
             rx.policy_streak.n = streak;
             rc = resident_drain(dev); if (rc) return rc;    // (a kernel that had left: noticed in there, replayed as the launch)
@@ -381,22 +384,16 @@ RQ_API int rq_policy_evaluate_step(rq_policy* pol, rq_env* env, const float* obs
     if (rows_in) rc = mailbox_put_in(dev, observation, batch, RQ_POLICY_INPUT_DIM, obs_stride);
     else if (observation) rc = host_to_soa(dev, observation, batch, obs_stride, pol->ld, RQ_POLICY_INPUT_DIM, pol->obs);
     if (rc) return rc;
-    const float* d_obs = observation ? pol->obs : env->obs;
-    const uint32_t ld_obs = observation ? pol->ld : env->ld;
-    float* d_act = action ? pol->act : env->act;
-    const uint32_t ld_act = action ? pol->ld : env->ld;
     rq::Mailbox mb{};
     if (mailbox) mb = mailbox_for(dev, rows_in, RQ_POLICY_INPUT_DIM, action ? MbOut::out : MbOut::none);
-    if (rated) {
-        RQ_HIP_MB(rq::launch_actor_step_rate(dev->stream, batch, packed_of(pol), d_obs, ld_obs, pol->hidden, pol->ld, d_act, ld_act,
-                                             nullptr, pol->precision, nullptr, pol->native_interval,
-                                             pol->rate_counter % pol->native_interval == 0 ? 1u : 0u, mb), dev, mb);
-        pol->rate_counter += 1;
-    } else {
-        RQ_HIP_MB(rq::launch_actor_step(dev->stream, batch, packed_of(pol), d_obs, ld_obs, pol->hidden, pol->ld, d_act,
-                                        ld_act, nullptr, pol->precision,
-                                        sas_of(pol, pol->sas_counter, nullptr, env ? env->offset : 0), mb), dev, mb);
-    }
+    rq::ActorStepLaunch a;
+    a.n = batch; a.packed = packed_of(pol); a.precision = pol->precision; a.hidden = pol->hidden; a.ld_h = pol->ld; a.mb = mb;
+    a.obs = observation ? pol->obs.get() : env->obs.get(); a.ld_obs = observation ? pol->ld : env->ld;
+    a.act = action ? pol->act.get() : env->act.get();      a.ld_act = action ? pol->ld : env->ld;
+    a.sas = sas_of(pol, pol->sas_counter, nullptr, env ? env->offset : 0);      // (off under a native interval above 1)
+    a.interval = pol->native_interval; a.native = pol->rate_counter % pol->native_interval == 0;      // one call counter for the batch
+    RQ_HIP_MB(rq::launch_actor_step(dev->stream, a), dev, mb);
+    if (rated) pol->rate_counter += 1;
     if (pol->sas_mode == RQ_SAS_SAMPLE) pol->sas_counter += 1;
     if (action && mailbox) return mailbox_copy_out(dev, mb.seq, mb.rows_out, action, (size_t)batch * RQ_ACTION_DIM);
     if (action) return soa_to_host(dev, pol->act, batch, pol->ld, RQ_ACTION_DIM, action);

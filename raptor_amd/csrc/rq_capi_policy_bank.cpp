@@ -278,21 +278,22 @@ struct PolicyBankActor {
         a.images = bank->images; a.block_policy = bank->table; a.policy_interval = bank->intervals_dev; a.bank_rated = bank->rated;
         return fused_launch(c, a);
     }
-    hipError_t thaw(const RolloutCall& c, const RolloutFrame& f) const {
-        return rq::launch_thaw_frozen_bank(c.dev->stream, f.b, f.smp, c.rng->seed, c.params->d, c.state->d, c.env->st, bank->hidden,
-                                           bank->weights, bank->table);
+    rq::EnvStepLaunch env_step(const RolloutCall& c, const RolloutFrame& f) const {
+        rq::EnvStepLaunch e = env_step_launch(c, f);
+        e.hidden = bank->hidden; e.weights = bank->weights; e.block_policy = bank->table;
+        return e;
     }
+    hipError_t thaw(const RolloutCall& c, const RolloutFrame& f) const { return rq::launch_thaw_frozen(c.dev->stream, env_step(c, f)); }
     hipError_t act(const RolloutCall& c, const RolloutFrame&, uint32_t, const uint32_t*) const {
         const rq_env* env = c.env;
-        return bank->rated ? rq::launch_actor_step_rate_bank(c.dev->stream, env->n, bank->images, bank->table, bank->intervals_dev,
-                                                             env->obs, env->ld, bank->hidden, bank->ld, env->act, env->ld,
-                                                             env->st.frozen, env->st.steps)
-                           : rq::launch_actor_step_bank(c.dev->stream, env->n, bank->images, bank->table, env->obs, env->ld,
-                                                        bank->hidden, bank->ld, env->act, env->ld, env->st.frozen);
+        rq::ActorStepLaunch a;
+        a.n = env->n; a.images = bank->images; a.block_policy = bank->table; a.policy_interval = bank->rated ? bank->intervals_dev.get() : nullptr;
+        a.obs = env->obs; a.ld_obs = env->ld; a.hidden = bank->hidden; a.ld_h = bank->ld; a.act = env->act; a.ld_act = env->ld;
+        a.frozen = env->st.frozen; a.steps = env->st.steps;
+        return rq::launch_actor_step(c.dev->stream, a);
     }
     hipError_t step(const RolloutCall& c, const RolloutFrame& f, uint32_t, const uint32_t*, bool) const {
-        return rq::launch_step_bank(c.dev->stream, f.b, f.sc, c.params->d, c.state->d, c.env->act, c.env->st, c.flags, f.smp,
-                                    c.rng->seed, bank->hidden, bank->weights, bank->table, f.wr);
+        return rq::launch_step(c.dev->stream, env_step(c, f));
     }
 };
 

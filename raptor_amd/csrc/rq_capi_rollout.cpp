@@ -141,6 +141,13 @@ rq::FusedArgs fused_args(const RolloutCall& c, const RolloutFrame& f) {
     return a;
 }
 
+rq::EnvStepLaunch env_step_launch(const RolloutCall& c, const RolloutFrame& f) {
+    rq::EnvStepLaunch e;
+    e.b = f.b; e.c = f.sc; e.params = c.params->d; e.state = c.state->d; e.action = c.env->act; e.next_state = c.state->d; e.st = c.env->st;
+    e.rollout = true; e.flags = c.flags; e.sc = f.smp; e.seed = c.rng->seed; e.wr = f.wr;
+    return e;
+}
+
 int fused_launch(const RolloutCall& c, rq::FusedArgs& a) {
     rq_device* dev = c.dev;
     if (dev->k_timing && c.n_steps) {                   // one (in, out) record per wave = per workgroup of the fused kernel
@@ -192,23 +199,26 @@ struct PolicyActor {
         a.sas = sas_of(policy, c.rng->epoch, nullptr, c.env->offset);
         return fused_launch(c, a);
     }
-    hipError_t thaw(const RolloutCall& c, const RolloutFrame& f) const {
-        return rq::launch_thaw_frozen(c.dev->stream, f.b, f.smp, c.rng->seed, c.params->d, c.state->d, c.env->st, policy->hidden,
-                                      policy->w_dev);
+    rq::EnvStepLaunch env_step(const RolloutCall& c, const RolloutFrame& f) const {
+        rq::EnvStepLaunch e = env_step_launch(c, f);
+        e.hidden = policy->hidden; e.weights = policy->w_dev;
+        return e;
     }
+    hipError_t thaw(const RolloutCall& c, const RolloutFrame& f) const { return rq::launch_thaw_frozen(c.dev->stream, env_step(c, f)); }
     hipError_t act(const RolloutCall& c, const RolloutFrame&, uint32_t epoch, const uint32_t* epoch_base) const {
         const rq_env* env = c.env;
-        if (policy->native_interval > 1)
-            return rq::launch_actor_step_rate(c.dev->stream, env->n, packed_of(policy), env->obs, env->ld, policy->hidden, policy->ld,
-                                              env->act, env->ld, env->st.frozen, policy->precision, env->st.steps,
-                                              policy->native_interval, 0u);
-        return rq::launch_actor_step(c.dev->stream, env->n, packed_of(policy), env->obs, env->ld, policy->hidden, policy->ld, env->act,
-                                     env->ld, env->st.frozen, policy->precision, sas_of(policy, epoch, epoch_base, env->offset));
+        rq::ActorStepLaunch a;
+        a.n = env->n; a.packed = packed_of(policy); a.precision = policy->precision;
+        a.obs = env->obs; a.ld_obs = env->ld; a.hidden = policy->hidden; a.ld_h = policy->ld; a.act = env->act; a.ld_act = env->ld;
+        a.frozen = env->st.frozen;
+        a.sas = sas_of(policy, epoch, epoch_base, env->offset);      // (off under a native interval above 1)
+        a.steps = env->st.steps; a.interval = policy->native_interval;
+        return rq::launch_actor_step(c.dev->stream, a);
     }
     hipError_t step(const RolloutCall& c, const RolloutFrame& f, uint32_t epoch, const uint32_t* epoch_base, bool fold) const {
-        return rq::launch_step(c.dev->stream, f.b, f.sc, c.params->d, c.state->d, c.env->act, c.state->d, c.env->st, /*rollout=*/1,
-                               c.flags, f.smp, c.rng->seed, policy->hidden, policy->w_dev, rq::Mailbox{},
-                               fold ? c.env->obs.get() : nullptr, f.nc, f.noise, epoch + 1, epoch_base, f.wr);
+        rq::EnvStepLaunch e = env_step(c, f);
+        if (fold) { e.obs_of_next = c.env->obs; e.nc = f.nc; e.noise = f.noise; e.obs_epoch = epoch + 1; e.obs_epoch_base = epoch_base; }
+        return rq::launch_step(c.dev->stream, e);
     }
     rq_env::GraphKey graph_key(const RolloutCall& c, const RolloutFrame& f) const {
         rq_env::GraphKey key;

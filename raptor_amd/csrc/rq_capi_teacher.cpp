@@ -316,16 +316,17 @@ struct TeacherActor {
         RQ_HIP(rq::launch_rollout_teachers(c.dev->stream, n_tiles, bank->h1, bank->h2, bank->act, bank->out_act, a));
         return RQ_OK;
     }
-    hipError_t thaw(const RolloutCall& c, const RolloutFrame& f) const {
-        return rq::launch_thaw_frozen(c.dev->stream, f.b, f.smp, c.rng->seed, c.params->d, c.state->d, c.env->st, sink_h(), sink_w());
+    rq::EnvStepLaunch env_step(const RolloutCall& c, const RolloutFrame& f) const {
+        rq::EnvStepLaunch e = env_step_launch(c, f);
+        e.hidden = sink_h(); e.weights = sink_w();
+        return e;
     }
+    hipError_t thaw(const RolloutCall& c, const RolloutFrame& f) const { return rq::launch_thaw_frozen(c.dev->stream, env_step(c, f)); }
     hipError_t act(const RolloutCall& c, const RolloutFrame&, uint32_t, const uint32_t*) const {
         return bank_label_launch(bank, c.dev, c.env->n, n_tiles, c.env->ld, 1, c.env->obs, c.env->act);
     }
     hipError_t step(const RolloutCall& c, const RolloutFrame& f, uint32_t, const uint32_t*, bool) const {
-        return rq::launch_step(c.dev->stream, f.b, f.sc, c.params->d, c.state->d, c.env->act, c.state->d, c.env->st, /*rollout=*/1,
-                               c.flags, f.smp, c.rng->seed, sink_h(), sink_w(), rq::Mailbox{}, nullptr, rq::NoiseCfg{}, false, 0,
-                               nullptr, f.wr);
+        return rq::launch_step(c.dev->stream, env_step(c, f));
     }
 };
 

@@ -95,35 +95,38 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
     obs_cache_drop(dev);
     next_state->version = fresh_version();
     StepPair pair{};
-    pair.b = batch_of(env); pair.c = rq::step_cfg(env->cfg); pair.sc = rq::sample_cfg(env->cfg); pair.seed = rng->seed;
-    pair.params = params->d; pair.state_in = state->d; pair.act = env->act; pair.state_out = next_state->d; pair.st = env->st;
-    pair.mb_step = mb; pair.obs_alt = cache_obs ? env->obs_alt : nullptr; pair.wr = wr;
+    rq::EnvStepLaunch& es = pair.step;
+    es.b = batch_of(env); es.c = rq::step_cfg(env->cfg); es.sc = rq::sample_cfg(env->cfg); es.seed = rng->seed;
+    es.params = params->d; es.state = state->d; es.action = env->act; es.next_state = next_state->d; es.st = env->st;
+    es.mb = mb; es.obs_of_next = cache_obs ? env->obs_alt.get() : nullptr; es.wr = wr;
     pair.spec = pol != nullptr;
-    if (pol) {
-        pair.packed = packed_of(pol); pair.hidden_out = pol->hidden_alt; pair.ld_h = pol->ld; pair.pol_act = pol->act;
-        pair.precision = pol->precision; pair.sas = sas_of(pol, 0, nullptr, 0); pair.hidden_in = pol->hidden;
-        pair.mb_spec = mailbox_for(dev, false, 0, MbOut::act);
+    if (pol) {      // on the observation the step leaves, out of place: hidden -> hidden_alt
+        rq::ActorStepLaunch& as = pair.actor;
+        as.n = env->n; as.packed = packed_of(pol); as.obs = es.obs_of_next; as.ld_obs = env->ld;
+        as.hidden_in = pol->hidden; as.hidden = pol->hidden_alt; as.ld_h = pol->ld; as.act = pol->act; as.ld_act = pol->ld;
+        as.precision = pol->precision; as.sas = sas_of(pol, 0, nullptr, 0);
+        as.mb = mailbox_for(dev, false, 0, MbOut::act);
     }
     if (resident) {
         if (!rx.running) {
             rq::ResidentArgs ra{};
-            ra.b = pair.b; ra.c = pair.c; ra.sc = pair.sc; ra.seed = pair.seed;
-            ra.params = pair.params; ra.act = pair.act; ra.st = pair.st; ra.ld_h = pol->ld; ra.pol_act = pol->act;
+            ra.b = es.b; ra.c = es.c; ra.sc = es.sc; ra.seed = es.seed;
+            ra.params = es.params; ra.act = es.action; ra.st = es.st; ra.ld_h = pol->ld; ra.pol_act = pol->act;
             rc = resident_start(dev, ra, want);
         }
         if (rc == RQ_OK && rx.running) rc = resident_drain(dev);     // one command slot: the previous command must have been taken out of it
-        if (rc) { mailbox_abort(dev, pair.mb_spec); mailbox_abort(dev, mb); return rc; }
+        if (rc) { mailbox_abort(dev, pair.actor.mb); mailbox_abort(dev, mb); return rc; }
     }
     if (resident && rx.running) {
         resident_post(dev, pair);
     } else {
         const hipError_t e = launch_step_pair(dev, pair);
         if (e != hipSuccess) {
-            mailbox_abort(dev, pair.mb_spec); mailbox_abort(dev, mb);      // (pair.mb_spec is empty without a speculated step)
+            mailbox_abort(dev, pair.actor.mb); mailbox_abort(dev, mb);      // (pair.actor.mb is empty without a speculated step)
             return fail(RQ_ERR_HIP, std::string("rq_step: launch -> ") + hipGetErrorString(e));
         }
     }
-    if (cache_obs) obs_cache_fill(dev, env, params, next_state, mb.seq, pol, pair.mb_spec.seq);
+    if (cache_obs) obs_cache_fill(dev, env, params, next_state, mb.seq, pol, pair.actor.mb.seq);
     if (dts) for (uint32_t i = 0; i < env->n; ++i) dts[i] = env->cfg.dt;
     return RQ_OK;
 }

@@ -141,94 +141,25 @@ __global__ __launch_bounds__(kBlock) void k_observe(Batch b, NoiseCfg nc, uint64
 }
 
 // ------------------------------------------------------------------ actor --------------
-// MFMA ignores the EXEC mask and mixes the lanes of a wave, so every MFMA must execute in
-// wave-uniform control flow with all 64 lanes holding valid data: lanes past the end of the
-// batch (and frozen envs) compute on a clamped index and only their STORES are predicated —
-// no lane leaves early.
-// One 64-env group per wave (every batch up to 262 144 envs, and the host-row mailbox path of the small ones); the large
-// batches take k_actor_stream below.
-template <typename ACTOR>
-__global__ __launch_bounds__(kBlock, 2) void k_actor_step(uint32_t n, const float* __restrict__ packed,
-                                                       const float* __restrict__ obs, uint32_t ld_obs,
-                                                       const float* hidden_in, float* hidden,   // the same buffer unless speculative
-                                                       uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
-                                                       const uint8_t* __restrict__ frozen, SasArgs sas,
-                                                       Mailbox mb) {
-    ACTOR actor;
-    actor.template load<kBlock / 64>(packed);     // 18 KB of operand image per wave
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave_base = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64;
-    if (wave_base >= n) { mailbox_signal(mb); return; }          // wave-uniform
-    const uint32_t i0 = wave_base + lane;
-    const uint32_t i = i0 < n ? i0 : n - 1;
-    float x[22], hQ[4][4], a[4];
-    if (mb.rows_in != nullptr) {         // wave-uniform (kernel argument)
-#pragma unroll
-        for (int k = 0; k < 22; ++k) x[k] = mb.rows_in[(size_t)i * mb.in_stride + k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
-    }
-    load_hidden_q(hidden_in, ld_h, wave_base, n, hQ);      // == hidden unless the new state goes elsewhere (speculation)
-    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
-    const bool commit = (i0 < n) && fz == 0;
-    const uint64_t commit_mask = __builtin_amdgcn_ballot_w64(commit);
-    actor.step(x, hQ, a);
-    if (sas.mode)                        // wave-uniform (kernel argument)
-        sample_and_squash(sas, sas.epoch + (sas.epoch_base != nullptr ? *sas.epoch_base : 0u), sas.env_offset + i, hQ, a);
-    store_hidden_q(hidden, ld_h, wave_base, commit_mask, hQ);
-    if (commit) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
-        if (mb.rows_out != nullptr) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) mb.rows_out[(size_t)i * 4 + k] = a[k];
-        }
-    }
-    mailbox_signal(mb);
-}
-
-// k_actor_step under a native interval above 1 (rq_policy_set_native_interval, launch_actor_step_rate): the same loads, the same
-// ACTOR::step, the same action stores - and the hidden state written back only for the rows at a native step.
-template <typename ACTOR>
-__global__ __launch_bounds__(kBlock, 2) void k_actor_step_rate(uint32_t n, const float* __restrict__ packed,
-                                                            const float* __restrict__ obs, uint32_t ld_obs,
-                                                            float* hidden, uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
-                                                            const uint8_t* __restrict__ frozen,
-                                                            const uint32_t* __restrict__ steps, uint32_t interval, uint32_t native,
-                                                            Mailbox mb) {
-    ACTOR actor;
-    actor.template load<kBlock / 64>(packed);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave_base = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64;
-    if (wave_base >= n) { mailbox_signal(mb); return; }          // wave-uniform
-    const uint32_t i0 = wave_base + lane;
-    const uint32_t i = i0 < n ? i0 : n - 1;
-    float x[22], hQ[4][4], a[4];
-    if (mb.rows_in != nullptr) {         // wave-uniform (kernel argument)
-#pragma unroll
-        for (int k = 0; k < 22; ++k) x[k] = mb.rows_in[(size_t)i * mb.in_stride + k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
-    }
-    load_hidden_q(hidden, ld_h, wave_base, n, hQ);
-    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
-    const bool commit = (i0 < n) && fz == 0;
-    const bool at_native = steps != nullptr ? steps[i] % interval == 0 : native != 0;
-    const uint64_t hidden_mask = __builtin_amdgcn_ballot_w64(commit && at_native);
-    actor.step(x, hQ, a);
-    store_hidden_q(hidden, ld_h, wave_base, hidden_mask, hQ);
-    if (commit) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
-        if (mb.rows_out != nullptr) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) mb.rows_out[(size_t)i * 4 + k] = a[k];
-        }
-    }
-    mailbox_signal(mb);
-}
+// One 64-env group per wave (every batch up to 262 144 envs, and the host-row mailbox path of the small ones), in four kernels of one
+// text (rq_actor_step.inc): one policy or a policy bank, plain or under a native interval above 1.  The large batches of one policy
+// take k_actor_stream below.
+#define RQ_ACTOR_KERNEL k_actor_step
+#define RQ_ACTOR_BANK 0
+#define RQ_ACTOR_RATE 0
+#include "rq_actor_step.inc"
+#define RQ_ACTOR_KERNEL k_actor_step_rate
+#define RQ_ACTOR_BANK 0
+#define RQ_ACTOR_RATE 1
+#include "rq_actor_step.inc"
+#define RQ_ACTOR_KERNEL k_actor_step_bank
+#define RQ_ACTOR_BANK 1
+#define RQ_ACTOR_RATE 0
+#include "rq_actor_step.inc"
+#define RQ_ACTOR_KERNEL k_actor_step_rate_bank
+#define RQ_ACTOR_BANK 1
+#define RQ_ACTOR_RATE 1
+#include "rq_actor_step.inc"
 
 // The streaming form for the large batches (from 262 144 envs): a wave works through groups_per_wave consecutive 64-env groups,
 // the next group's inputs in flight while this one is on the matrix cores - the 18 KB operand image per wave is amortised and
@@ -981,30 +912,10 @@ hipError_t launch_resident(hipStream_t s, const ResidentArgs& ra) {
     return hipGetLastError();
 }
 
-// Chained-mode counterpart of the fused kernel's prologue under auto-reset: envs left frozen by an earlier
-// rollout start their next episode (sample_initial_state with the env's episode counter, policy state reset).
-__global__ __launch_bounds__(kBlock) void k_thaw_frozen(Batch b, SampleCfg c, uint64_t seed,
-                                                        const float* __restrict__ params, float* __restrict__ state,
-                                                        StatsPtrs st, float* __restrict__ hidden,
-                                                        const float* __restrict__ weights) {
-    const uint32_t i = env_index();
-    if (i >= b.n || !st.frozen[i]) return;
-    const size_t ld = b.ld;
-    const uint32_t ep = st.episode[i];
-    float s[17], la[4], f[6];
-    sample_state(c, seed, ep, b.env_offset + i, field(params, RQ_P_MASS, ld)[i], field(params, RQ_P_HOVER_RPM, ld)[i],
-                 field(params, RQ_P_ROTOR_POS, ld)[i], field(params, (RQ_P_ROTOR_POS + 1), ld)[i], s, la, f);
-#pragma unroll
-    for (int k = 0; k < 17; ++k) field(state, k, ld)[i] = s[k];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) field(state, (RQ_S_LAST_ACTION + k), ld)[i] = la[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) field(state, (RQ_S_FORCE + k), ld)[i] = f[k];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) field(hidden, j, ld)[i] = weights[OFF_H0 + j];
-    st.episode[i] = ep + 1;
-    st.frozen[i] = 0;
-}
+// Chained-mode counterpart of the fused kernel's prologue under auto-reset; the bank's, of the same text, is with the bank's kernels
+#define RQ_THAW_KERNEL k_thaw_frozen
+#define RQ_THAW_BANK 0
+#include "rq_thaw_frozen.inc"
 
 __global__ __launch_bounds__(kBlock) void k_fill_f32(float* p, float v, uint32_t count) {
     const uint32_t i = env_index();
@@ -1048,46 +959,49 @@ hipError_t launch_add_u32(hipStream_t s, uint32_t* p, uint32_t add) {
     return RQ_KLAUNCH_STATUS();
 }
 
-hipError_t launch_actor_step(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
-                             float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
-                             int precision, SasArgs sas, Mailbox mb, const float* hidden_in) {
-    if (hidden_in == nullptr) hidden_in = hidden;
-    if (n == 0) return hipSuccess;
-    // enough waves to fill the 1024 SIMDs first, then several 64-env groups per wave so that the
-    // per-wave operand-image load (18 KB, more than a group's own 14.8 KB of data) is amortised
-    // (2 097 152 envs, groups per wave 2 / 4 / 8 / 11 / 16 / 32: 125.9 / 119.6 / 116.6 / 116.2 / 122.2 / 110.8 us)
-    const uint32_t groups = (n + 63) / 64;
-    static const uint32_t forced = [] { const char* e = std::getenv("RQ_ACTOR_GROUPS_PER_WAVE"); return e ? (uint32_t)std::atoi(e) : 0u; }();
-    const uint32_t gpw = forced ? forced : actor_groups_per_wave(n);       // the override: launch-shape sweeps (tools/)
-    const unsigned grid = grid_for((groups + gpw - 1) / gpw * 64, kBlock);
-    // the streaming kernel: no host rows (they exist below 1 024 envs only) and every byte offset in 32 bits; otherwise one
-    // group per wave
-    const bool stream = gpw > 1 && mb.rows_in == nullptr && mb.rows_out == nullptr && mb.flag == nullptr &&
-                        (uint64_t)(ld_h > ld_obs ? ld_h : ld_obs) * 4u * 26u < 0x7FFFFFFFull;
-    const unsigned grid1 = grid_for(groups * 64, kBlock);
-#define RQ_LAUNCH_ACTOR(ACT)                                                                                                            \
-    do {                                                                                                                                \
-        if (stream) RQ_KLAUNCH(k_actor_stream<ACT>, grid, kBlock, s, n, gpw, packed, obs, ld_obs, hidden_in, hidden, ld_h, act, ld_act, frozen, sas);   \
-        else        RQ_KLAUNCH(k_actor_step<ACT>, grid1, kBlock, s, n, packed, obs, ld_obs, hidden_in, hidden, ld_h, act, ld_act, frozen, sas, mb);    \
-    } while (0)
-    if (precision == RQ_POLICY_F16X2_MFMA)     RQ_LAUNCH_ACTOR(ActorF16X2);
-    else if (precision == RQ_POLICY_BF16_MFMA) RQ_LAUNCH_ACTOR(ActorBF16);
-    else                                       RQ_LAUNCH_ACTOR(ActorF32Lean);   // the two-tiles-per-pass build: ~30 registers fewer live, 2-3 % faster at every size
-#undef RQ_LAUNCH_ACTOR
-    return RQ_KLAUNCH_STATUS();
-}
+// ---- the actor step's one launcher: the four kernels of rq_actor_step.inc and k_actor_stream, chosen by route_actor_step
+static_assert(kBlock == (int)kActorBlock, "route_actor_step counts its grid in workgroups of kBlock threads");
 
-hipError_t launch_actor_step_rate(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
-                                  float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
-                                  int precision, const uint32_t* steps, uint32_t interval, uint32_t native, Mailbox mb) {
-    if (n == 0) return hipSuccess;
-    const unsigned grid = grid_for((n + 63) / 64 * 64, kBlock);
-#define RQ_LAUNCH_ACTOR(ACT) RQ_KLAUNCH(k_actor_step_rate<ACT>, grid, kBlock, s, n, packed, obs, ld_obs, hidden, ld_h, act, ld_act, frozen, \
-                                        steps, interval, native, mb)
-    if (precision == RQ_POLICY_F16X2_MFMA)     RQ_LAUNCH_ACTOR(ActorF16X2);
-    else if (precision == RQ_POLICY_BF16_MFMA) RQ_LAUNCH_ACTOR(ActorBF16);
-    else                                       RQ_LAUNCH_ACTOR(ActorF32Lean);   // launch_actor_step's build: the same bits
+// The kernel templates of this file come out in the order in which its launchers name them.  What is named here, in this order, and
+// the bank's two below the fused rollout's launcher keep the listing in the order it always had: the same code object, byte for byte.
+static void launch_actor_step_of_bank(hipStream_t s, const ActorStepLaunch& a, const ActorStepRoute& r);
+
+hipError_t launch_actor_step(hipStream_t s, const ActorStepLaunch& a) {
+    if (a.n == 0) return hipSuccess;
+    // the override: launch-shape sweeps (tools/actor_gpw_sweep.py)
+    static const uint32_t forced = [] { const char* e = std::getenv("RQ_ACTOR_GROUPS_PER_WAVE"); return e ? (uint32_t)std::atoi(e) : 0u; }();
+    const ActorStepRoute r = route_actor_step(actor_step_traits(a, forced));
+    if (r.family == ActorFamily::UNSUPPORTED || (r.family == ActorFamily::BANK_RATE && a.steps == nullptr)) return hipErrorInvalidValue;
+    const float* hidden_in = a.hidden_in != nullptr ? a.hidden_in : a.hidden;
+    const bool stream = r.family == ActorFamily::STREAM;
+#define RQ_LAUNCH_ACTOR(ACT)                                                                                                          \
+    do {                                                                                                                              \
+        if (stream) RQ_KLAUNCH(k_actor_stream<ACT>, r.grid, kBlock, s, a.n, r.groups_per_wave, a.packed, a.obs, a.ld_obs, hidden_in,  \
+                               a.hidden, a.ld_h, a.act, a.ld_act, a.frozen, a.sas);                                                   \
+        else        RQ_KLAUNCH(k_actor_step<ACT>, r.grid, kBlock, s, a.n, a.packed, a.obs, a.ld_obs, hidden_in, a.hidden, a.ld_h,     \
+                               a.act, a.ld_act, a.frozen, a.sas, a.mb);                                                               \
+    } while (0)
+#define RQ_LAUNCH_ACTOR_RATE(ACT)                                                                                                     \
+    RQ_KLAUNCH(k_actor_step_rate<ACT>, r.grid, kBlock, s, a.n, a.packed, a.obs, a.ld_obs, a.hidden, a.ld_h, a.act, a.ld_act, a.frozen, \
+               a.steps, a.interval, a.native ? 1u : 0u, a.mb)
+    switch (r.family) {
+    case ActorFamily::STEP:
+    case ActorFamily::STREAM:
+        if (r.build == ActorBuild::F16X2)     RQ_LAUNCH_ACTOR(ActorF16X2);
+        else if (r.build == ActorBuild::BF16) RQ_LAUNCH_ACTOR(ActorBF16);
+        else                                  RQ_LAUNCH_ACTOR(ActorF32Lean);
+        break;
+    case ActorFamily::RATE:
+        if (r.build == ActorBuild::F16X2)     RQ_LAUNCH_ACTOR_RATE(ActorF16X2);
+        else if (r.build == ActorBuild::BF16) RQ_LAUNCH_ACTOR_RATE(ActorBF16);
+        else                                  RQ_LAUNCH_ACTOR_RATE(ActorF32Lean);
+        break;
+    default:
+        launch_actor_step_of_bank(s, a, r);
+        break;
+    }
 #undef RQ_LAUNCH_ACTOR
+#undef RQ_LAUNCH_ACTOR_RATE
     return RQ_KLAUNCH_STATUS();
 }
 
@@ -1122,32 +1036,41 @@ hipError_t launch_actor_relabel(hipStream_t s, uint32_t n, uint32_t ld, uint32_t
     return hipGetLastError();
 }
 
-hipError_t launch_step(hipStream_t s, Batch b, StepCfg c, const float* params, const float* state,
-                       float* action, float* next_state, StatsPtrs st, int rollout, uint32_t flags,
-                       SampleCfg sc, uint64_t seed, float* hidden, const float* weights, Mailbox mb, float* obs_of_next,
-                       NoiseCfg nc, bool noise, uint32_t obs_epoch, const uint32_t* obs_epoch_base, WrenchPtrs wr) {
-    if (b.n == 0) return hipSuccess;
-    const ObsNext on{obs_of_next, nc, noise ? 1u : 0u, obs_epoch, obs_epoch_base};
-    if (wr.rows != nullptr && rollout)
-        RQ_KLAUNCH(k_step_wrench<true>, grid_for(b.n, kBlock), kBlock, s, b, c, params, state, action, next_state, st, flags,
-                   sc, seed, hidden, weights, mb, on, wr);
-    else if (wr.rows != nullptr)
-        RQ_KLAUNCH(k_step_wrench<false>, grid_for(b.n, kBlock), kBlock, s, b, c, params, state, action, next_state, st, flags,
-                   sc, seed, hidden, weights, mb, on, wr);
-    else if (rollout)
-        RQ_KLAUNCH(k_step<true>, grid_for(b.n, kBlock), kBlock, s, b, c, params, state, action, next_state, st, flags,
-                   sc, seed, hidden, weights, mb, on);
-    else
-        RQ_KLAUNCH(k_step<false>, grid_for(b.n, kBlock), kBlock, s, b, c, params, state, action, next_state, st, flags,
-                   sc, seed, hidden, weights, mb, on);
-    return RQ_KLAUNCH_STATUS();
-}
+// ---- the env step's one launcher.  (A bank's two kernels are defined with the bank's, below.)
+__global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action, StatsPtrs st,
+                            uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                            const uint32_t* __restrict__ block_policy);
+__global__ __launch_bounds__(kBlock) void k_step_bank_wrench(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
+                                   StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
+                                   const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr);
 
-hipError_t launch_thaw_frozen(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
-                              StatsPtrs st, float* hidden, const float* weights) {
-    if (b.n == 0) return hipSuccess;
-    k_thaw_frozen<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, seed, params, state, st, hidden, weights);
-    return hipGetLastError();
+hipError_t launch_step(hipStream_t s, const EnvStepLaunch& e) {
+    if (e.b.n == 0) return hipSuccess;
+    const unsigned grid = grid_for(e.b.n, kBlock);
+    const bool wrench = e.wr.rows != nullptr;
+    const ObsNext on{e.obs_of_next, e.nc, e.noise ? 1u : 0u, e.obs_epoch, e.obs_epoch_base};
+    if (e.block_policy != nullptr) {
+        if (!e.rollout || e.next_state != e.state || mailbox_used(e.mb) || e.obs_of_next != nullptr) return hipErrorInvalidValue;
+        if (wrench)
+            RQ_KLAUNCH(k_step_bank_wrench, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed,
+                       e.hidden, e.weights, e.block_policy, e.wr);
+        else
+            RQ_KLAUNCH(k_step_bank, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed, e.hidden,
+                       e.weights, e.block_policy);
+    } else if (wrench && e.rollout) {
+        RQ_KLAUNCH(k_step_wrench<true>, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
+                   e.hidden, e.weights, e.mb, on, e.wr);
+    } else if (wrench) {
+        RQ_KLAUNCH(k_step_wrench<false>, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
+                   e.hidden, e.weights, e.mb, on, e.wr);
+    } else if (e.rollout) {
+        RQ_KLAUNCH(k_step<true>, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
+                   e.hidden, e.weights, e.mb, on);
+    } else {
+        RQ_KLAUNCH(k_step<false>, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
+                   e.hidden, e.weights, e.mb, on);
+    }
+    return RQ_KLAUNCH_STATUS();
 }
 
 __global__ __launch_bounds__(kBlock) void k_record(Batch b, const float* __restrict__ obs,
@@ -1404,90 +1327,14 @@ hipError_t launch_rollout_fused(hipStream_t s, const FusedArgs& a) {
     return hipGetLastError();
 }
 
-// ---- the bank's chained actor step
-// k_actor_step with the image of the wave's block (block = wave_base / 64); the chained bank rollout's actor: no host rows, no
-// SampleAndSquash stage, no speculation.  The wave index is made a scalar first: the table read is then a scalar load too.
-template <typename ACTOR>
-__global__ __launch_bounds__(kBlock, 2) void k_actor_step_bank(uint32_t n, const float* __restrict__ images,
-                                                            const uint32_t* __restrict__ block_policy, uint32_t image_floats,
-                                                            const float* __restrict__ obs, uint32_t ld_obs,
-                                                            float* hidden, uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
-                                                            const uint8_t* __restrict__ frozen) {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint32_t wave_base = wave * 64u;
-    if (wave_base >= n) return;                                  // wave-uniform; the table has ceil(n / 64) entries
-    ACTOR actor;
-    actor.template load<kBlock / 64>(images + (size_t)block_policy[wave] * image_floats);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t i0 = wave_base + lane;
-    const uint32_t i = i0 < n ? i0 : n - 1;
-    float x[22], hQ[4][4], a[4];
-#pragma unroll
-    for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
-    load_hidden_q(hidden, ld_h, wave_base, n, hQ);
-    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
-    const bool commit = (i0 < n) && fz == 0;
-    const uint64_t commit_mask = __builtin_amdgcn_ballot_w64(commit);
-    actor.step(x, hQ, a);
-    store_hidden_q(hidden, ld_h, wave_base, commit_mask, hQ);
-    if (commit) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
-    }
-}
-
-// k_actor_step_bank under the policies' native intervals (the chained bank rollout's actor when any interval is above 1):
-// k_actor_step_rate's rule - the hidden state is stored only for the rows at a native step, steps[i] % interval == 0 - with the image
-// and the interval of the wave's block.  steps: the envs' episode step counts at this step's observation (k_step_bank moves them on).
-template <typename ACTOR>
-__global__ __launch_bounds__(kBlock, 2) void k_actor_step_rate_bank(uint32_t n, const float* __restrict__ images,
-                                                            const uint32_t* __restrict__ block_policy,
-                                                            const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
-                                                            const float* __restrict__ obs, uint32_t ld_obs,
-                                                            float* hidden, uint32_t ld_h, float* __restrict__ act, uint32_t ld_act,
-                                                            const uint8_t* __restrict__ frozen, const uint32_t* __restrict__ steps) {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint32_t wave_base = wave * 64u;
-    if (wave_base >= n) return;                                  // wave-uniform; the table has ceil(n / 64) entries
-    const uint32_t policy = block_policy[wave];
-    const uint32_t interval = policy_interval[policy];
-    ACTOR actor;
-    actor.template load<kBlock / 64>(images + (size_t)policy * image_floats);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t i0 = wave_base + lane;
-    const uint32_t i = i0 < n ? i0 : n - 1;
-    float x[22], hQ[4][4], a[4];
-#pragma unroll
-    for (int k = 0; k < 22; ++k) x[k] = field(obs, k, ld_obs)[i];
-    load_hidden_q(hidden, ld_h, wave_base, n, hQ);
-    const uint32_t fz = frozen != nullptr ? (uint32_t)frozen[i] : 0u;
-    const bool commit = (i0 < n) && fz == 0;
-    const bool at_native = steps[i] % interval == 0;
-    const uint64_t hidden_mask = __builtin_amdgcn_ballot_w64(commit && at_native);
-    actor.step(x, hQ, a);
-    store_hidden_q(hidden, ld_h, wave_base, hidden_mask, hQ);
-    if (commit) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) field(act, k, ld_act)[i] = a[k];
-    }
-}
-
-// launch_actor_step's build for fp32 policies (one 64-env group per wave): the same bits
-hipError_t launch_actor_step_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy, const float* obs,
-                                  uint32_t ld_obs, float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen) {
-    if (n == 0) return hipSuccess;
-    k_actor_step_bank<ActorF32Lean><<<grid_for((n + 63) / 64 * 64, kBlock), kBlock, 0, s>>>(
-        n, images, block_policy, (uint32_t)RQ_PACKED_FLOATS, obs, ld_obs, hidden, ld_h, act, ld_act, frozen);
-    return hipGetLastError();
-}
-
-hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy,
-                                       const uint32_t* policy_interval, const float* obs, uint32_t ld_obs, float* hidden, uint32_t ld_h,
-                                       float* act, uint32_t ld_act, const uint8_t* frozen, const uint32_t* steps) {
-    if (n == 0) return hipSuccess;
-    k_actor_step_rate_bank<ActorF32Lean><<<grid_for((n + 63) / 64 * 64, kBlock), kBlock, 0, s>>>(
-        n, images, block_policy, policy_interval, (uint32_t)RQ_PACKED_FLOATS, obs, ld_obs, hidden, ld_h, act, ld_act, frozen, steps);
-    return hipGetLastError();
+// ---- the bank's chained actor step: launch_actor_step's build for fp32 policies, the same bits
+static void launch_actor_step_of_bank(hipStream_t s, const ActorStepLaunch& a, const ActorStepRoute& r) {
+    if (r.family == ActorFamily::BANK)
+        RQ_KLAUNCH(k_actor_step_bank<ActorF32Lean>, r.grid, kBlock, s, a.n, a.images, a.block_policy, (uint32_t)RQ_PACKED_FLOATS, a.obs,
+                   a.ld_obs, a.hidden, a.ld_h, a.act, a.ld_act, a.frozen);
+    else
+        RQ_KLAUNCH(k_actor_step_rate_bank<ActorF32Lean>, r.grid, kBlock, s, a.n, a.images, a.block_policy, a.policy_interval,
+                   (uint32_t)RQ_PACKED_FLOATS, a.obs, a.ld_obs, a.hidden, a.ld_h, a.act, a.ld_act, a.frozen, a.steps);
 }
 
 // ---- the bank's env step, thaw and initial hidden state
@@ -1514,49 +1361,20 @@ __global__ __launch_bounds__(kBlock) void k_step_bank_wrench(Batch b, StepCfg c,
                              weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr);
 }
 
-hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
-                            uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
-                            const uint32_t* block_policy, WrenchPtrs wr) {
-    if (b.n == 0) return hipSuccess;
-    if (wr.rows != nullptr) {
-        k_step_bank_wrench<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, params, state, action, st, flags, sc, seed, hidden, weights,
-                                                                    block_policy, wr);
-        return hipGetLastError();
-    }
-    k_step_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, params, state, action, st, flags, sc, seed, hidden, weights, block_policy);
-    return hipGetLastError();
-}
-
 // k_thaw_frozen likewise: an env left frozen starts its next episode with ITS policy's initial state
-__global__ __launch_bounds__(kBlock) void k_thaw_frozen_bank(Batch b, SampleCfg c, uint64_t seed,
-                                                             const float* __restrict__ params, float* __restrict__ state,
-                                                             StatsPtrs st, float* __restrict__ hidden,
-                                                             const float* __restrict__ weights,
-                                                             const uint32_t* __restrict__ block_policy) {
-    const uint32_t i = env_index();
-    if (i >= b.n || !st.frozen[i]) return;
-    const size_t ld = b.ld;
-    const uint32_t ep = st.episode[i];
-    const float* w = weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS;
-    float s[17], la[4], f[6];
-    sample_state(c, seed, ep, b.env_offset + i, field(params, RQ_P_MASS, ld)[i], field(params, RQ_P_HOVER_RPM, ld)[i],
-                 field(params, RQ_P_ROTOR_POS, ld)[i], field(params, (RQ_P_ROTOR_POS + 1), ld)[i], s, la, f);
-#pragma unroll
-    for (int k = 0; k < 17; ++k) field(state, k, ld)[i] = s[k];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) field(state, (RQ_S_LAST_ACTION + k), ld)[i] = la[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) field(state, (RQ_S_FORCE + k), ld)[i] = f[k];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) field(hidden, j, ld)[i] = w[OFF_H0 + j];
-    st.episode[i] = ep + 1;
-    st.frozen[i] = 0;
-}
+#define RQ_THAW_KERNEL k_thaw_frozen_bank
+#define RQ_THAW_BANK 1
+#include "rq_thaw_frozen.inc"
 
-hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
-                                   StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy) {
-    if (b.n == 0) return hipSuccess;
-    k_thaw_frozen_bank<<<grid_for(b.n, kBlock), kBlock, 0, s>>>(b, c, seed, params, state, st, hidden, weights, block_policy);
+// ---- the thaw's launcher
+hipError_t launch_thaw_frozen(hipStream_t s, const EnvStepLaunch& e) {
+    if (e.b.n == 0) return hipSuccess;
+    if (e.next_state != e.state) return hipErrorInvalidValue;
+    if (e.block_policy != nullptr)
+        k_thaw_frozen_bank<<<grid_for(e.b.n, kBlock), kBlock, 0, s>>>(e.b, e.sc, e.seed, e.params, e.next_state, e.st, e.hidden, e.weights,
+                                                                     e.block_policy);
+    else
+        k_thaw_frozen<<<grid_for(e.b.n, kBlock), kBlock, 0, s>>>(e.b, e.sc, e.seed, e.params, e.next_state, e.st, e.hidden, e.weights);
     return hipGetLastError();
 }
 

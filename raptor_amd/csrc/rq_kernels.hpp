@@ -7,28 +7,9 @@
 #include "../../include/raptor_quad.h"
 #include "rq_fused_route.hpp"
 #include "rq_loss_launch.hpp"
+#include "rq_step_launch.hpp"      // StepCfg, NoiseCfg, SampleCfg, StatsPtrs, WrenchPtrs, SasArgs, Batch, Mailbox; the chained step's launches
 
 namespace rq {
-
-struct StepCfg {   // the rq_env_config members one transition reads
-    float dt, gravity;
-    uint32_t episode_step_limit;
-    float reward_scale, reward_constant, reward_termination_penalty;
-    float reward_position, reward_orientation, reward_linear_velocity, reward_angular_velocity, reward_action;
-    uint32_t termination_enabled;
-    float termination_position, termination_linear_velocity, termination_angular_velocity;
-    uint32_t action_history_raw;
-};
-
-struct NoiseCfg { float position, orientation, linear_velocity, angular_velocity; };
-
-struct SampleCfg {   // rq_env_config members the samplers read
-    float gravity;
-    uint32_t domain_randomization;
-    float dr_scale_min, dr_scale_max, dr_t2w_min, dr_t2w_max, dr_kq_min, dr_kq_max, dr_tau_min, dr_tau_max;
-    float init_guidance, init_max_position, init_max_angle, init_max_linear_velocity, init_max_angular_velocity;
-    float disturbance_force_std, disturbance_torque_std;
-};
 
 inline StepCfg step_cfg(const rq_env_config& c) {
     return {c.dt, c.gravity, c.episode_step_limit, c.reward_scale, c.reward_constant,
@@ -52,15 +33,6 @@ inline SampleCfg sample_cfg(const rq_env_config& c) {
             c.init_max_angular_velocity, c.disturbance_force_std, c.disturbance_torque_std};
 }
 
-// Episode statistics of one VectorEnvironment, all [ld] arrays on the device.
-struct StatsPtrs {
-    float* returns; uint32_t* steps;
-    float* fin_returns; uint32_t* fin_lengths; uint32_t* fin_counts; uint32_t* fin_terminated;
-    float* last_reward; uint8_t* last_terminated;
-    uint8_t* frozen; uint32_t* episode;
-    uint8_t* last_done;   // per transition: 0 running, 1 terminated, 2 step limit reached, 4 env frozen (not stepped)
-};
-
 // Trajectory buffer of a rollout: step-major, field-major within a step,
 //   obs [T][22][ld], act [T][4][ld] (raw actor output), rew [T][ld], done [T][ld] (codes of last_done).
 struct TrajPtrs {
@@ -82,42 +54,6 @@ struct TrackPtrs {
     uint32_t* steps;      // [ld]: how many
 };
 static_assert(sizeof(TrackPtrs) == 32, "the kernels' argument blocks hold TrackPtrs by value");
-
-// A wrench schedule (rq_env_set_wrench_schedule): the bank's tables and the env's per-env first rows (rq_device_math.hpp wrench_*).
-struct WrenchPtrs {
-    const float* rows;        // [n_tables * n_rows][6] row-major: force (world frame), torque (body frame); nullptr = no schedule
-    const uint32_t* row0;     // [ld]: wrench_id[i] * n_rows, the first row of env i's table
-    uint32_t n_rows;          // rows of one table
-    uint32_t relative;        // 1: multiples of m g / m g arm (RQ_WRENCH_RELATIVE); 0: N / N m
-};
-
-// SampleAndSquash output stage of the actor (rq_policy_set_sample_and_squash): mode = rq_sample_and_squash_mode
-struct SasArgs {
-    uint32_t mode;                // RQ_SAS_OFF / RQ_SAS_MEAN / RQ_SAS_SAMPLE
-    uint32_t epoch;               // sampling counter of this launch (+ *epoch_base inside a replayed hipGraph)
-    const uint32_t* epoch_base;
-    const float* ls_image;        // 20 x 64 floats: log-std head operands + bias (pack_logstd_head), RQ_SAS_SAMPLE only
-    uint64_t seed;
-    uint64_t env_offset;          // global id of batch element 0 (k_actor_step; the fused kernel has its Batch)
-};
-
-struct Batch {           // which envs a launch covers
-    uint32_t n, ld;      // envs, leading dimension of every SoA buffer
-    uint64_t env_offset; // global id of env 0 (RNG key)
-};
-
-// Small-batch hand-over to/from the host without a copy command or a stream synchronisation: the kernel
-// reads its input rows from / mirrors its output rows into pinned host memory and the last workgroup to
-// finish publishes `seq` in a pinned flag the host spins on (measured: 7.3 us per launch + result against
-// 14.3 us for kernel + hipMemcpyAsync + hipStreamSynchronize, tools/synclat.hip).  All-null = not used.
-struct Mailbox {
-    const float* rows_in;   // row-major input [n][in_stride] replacing the field-major one, or nullptr
-    uint32_t in_stride;
-    float* rows_out;        // row-major mirror [n][dim] of the kernel's output, or nullptr
-    uint32_t* counter;      // device: workgroups finished (left at 0)
-    uint32_t* flag;         // pinned host: receives seq when every workgroup is done, or nullptr
-    uint32_t seq;
-};
 
 // ---- resident executor of the small-batch loop (rq_kernels.hip k_resident_loop; host side: rq_capi_vector.cpp resident_*) ----
 struct ResidentArgs {
@@ -184,31 +120,11 @@ void set_graph_sink(GraphSink* sink);      // nullptr: the launchers launch agai
 
 hipError_t launch_set_u32(hipStream_t s, uint32_t* p, uint32_t value);
 hipError_t launch_add_u32(hipStream_t s, uint32_t* p, uint32_t add);
-// Raptor.evaluate_step (README.md:97): obs [>=22][ld_obs] -> act [4][ld_act]; hidden [16][ld_h] in/out.
-// frozen != nullptr: envs with frozen[i] != 0 are skipped (rollout semantics).
-// `precision`: rq_policy_precision; `sas`: the optional SampleAndSquash output stage.
-// hidden_in != nullptr: the state BEFORE the step is read from there and `hidden` only written (speculative evaluation).
-// `packed`: the MFMA A-operand image of the policy (rq::pack_policy), RQ_PACKED_FLOATS floats
-// 64-env groups one wave of k_actor_step works through at n envs (1 = the non-streaming instantiation); bench.py's
-// actor_groups_per_wave mirrors this.  From 262 144 envs on the launch keeps ~1 024 waves - one per SIMD - and lets each
-// stream through groups / 1 024 groups (tools/actor_gpw_sweep.py, round 4: 1 048 576 envs 61.5 us with 16 groups per wave
-// against 103 with 32 = 512 waves; 2 097 152 envs 119 - 124 us with 32 against 128 with 8 and 137 with 1 or 16)
-inline uint32_t actor_groups_per_wave(uint32_t n) {
-    const uint32_t groups = (n + 63u) / 64u;
-    if (groups < 4096u) return 1u;
-    const uint32_t g = groups / 1024u;
-    return g > 64u ? 64u : g;
-}
-hipError_t launch_actor_step(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
-                             float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
-                             int precision, SasArgs sas, Mailbox mb = Mailbox{}, const float* hidden_in = nullptr);
-// The same step under a native interval above 1 (rq_policy_set_native_interval): the actions are written as above, the hidden state
-// only for the rows at a native step - steps != nullptr: row i iff steps[i] % interval == 0 (the chained rollout: the env's episode
-// step count at observe time); steps == nullptr: every row iff native != 0 (evaluate_step: one call counter for the batch).
-// One 64-env group per wave at every batch size.
-hipError_t launch_actor_step_rate(hipStream_t s, uint32_t n, const float* packed, const float* obs, uint32_t ld_obs,
-                                  float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen,
-                                  int precision, const uint32_t* steps, uint32_t interval, uint32_t native, Mailbox mb = Mailbox{});
+// The chained step's three launches, each from its description (rq_step_launch.hpp: the fields say what they mean).  The actor
+// step and the env step append a node under a GraphSink, the thaw launches.
+// launch_actor_step: Raptor.evaluate_step (README.md:97) of one policy or a policy bank, by the kernel route_actor_step names for
+// actor_step_traits(a) - hipErrorInvalidValue, and nothing launched, for a description no kernel is built for.
+hipError_t launch_actor_step(hipStream_t s, const ActorStepLaunch& a);
 // Raptor over a sequence: obs [steps][n][stride] (first 22 columns) -> act [steps][n][4], both row-major on
 // the device; hidden [16][ld_h] is the state before step 0 on entry and after the last step on return
 hipError_t launch_actor_sequence(hipStream_t s, uint32_t n, uint32_t steps, const float* packed, const float* obs,
@@ -257,38 +173,16 @@ hipError_t launch_adam_repack_bank(hipStream_t s, uint32_t n_policies, const uin
 hipError_t launch_adam_set_lr_bank(hipStream_t s, AdamState* st, uint32_t n_policies, const double* lr, uint32_t n_lr);
 // dst [rows][ld] <- src [rows] (device), row by row
 hipError_t launch_fill_rows(hipStream_t s, float* dst, uint32_t ld, const float* src, uint32_t rows);
-// vector.step (README.md:98) + reward/termination/statistics.  rollout != 0 adds the
-// episode-end handling of rq_rollout (freeze or auto-reset incl. hidden-state reset).
-// With mb.rows_in the actions come from the mailbox and are also written to `action` (field-major).
-// obs_of_next != nullptr: the observation of the state just written (after an auto-reset: of the re-sampled one), as
-// vector.observe would assemble it - with the noise draw of epoch obs_epoch + *obs_epoch_base when `noise` - goes to
-// obs_of_next [RQ_OBSERVATION_DIM][ld] and, row-major, to mb.rows_out.
-hipError_t launch_step(hipStream_t s, Batch b, StepCfg c, const float* params, const float* state,
-                       float* action, float* next_state, StatsPtrs st, int rollout, uint32_t flags,
-                       SampleCfg sc, uint64_t seed, float* hidden, const float* weights, Mailbox mb = Mailbox{},
-                       float* obs_of_next = nullptr, NoiseCfg nc = NoiseCfg{}, bool noise = false, uint32_t obs_epoch = 0,
-                       const uint32_t* obs_epoch_base = nullptr, WrenchPtrs wr = WrenchPtrs{});
-// chained rollouts under auto-reset: envs left frozen by an earlier rollout start their next episode
-// (sample_initial_state with the env's episode counter + policy state reset), as the fused kernel's prologue does
-hipError_t launch_thaw_frozen(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
-                              StatsPtrs st, float* hidden, const float* weights);
-// ---- policy bank (rq_rollout_policies, rq_rollout_policies_track): P fp32 operand images [P][RQ_PACKED_FLOATS], raw weights
-// [P][RQ_POLICY_NUM_WEIGHTS], block_policy [ceil(n / 64)]: the policy of each 64-env block, and policy_interval [P]: every entry
-// 1 .. RQ_POLICY_MAX_NATIVE_INTERVAL (rq_policy_bank_set_native_interval).  Plain launches: none of them appends to a GraphSink.
-// The fused rollout: launch_rollout_fused below (FusedArgs).  The chained counterpart's actor step; _rate stores the hidden state of
-// the rows at a native step only (steps: the envs' episode step counts, as launch_actor_step_rate takes them).
-hipError_t launch_actor_step_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy, const float* obs,
-                                  uint32_t ld_obs, float* hidden, uint32_t ld_h, float* act, uint32_t ld_act, const uint8_t* frozen);
-hipError_t launch_actor_step_rate_bank(hipStream_t s, uint32_t n, const float* images, const uint32_t* block_policy,
-                                       const uint32_t* policy_interval, const float* obs, uint32_t ld_obs, float* hidden, uint32_t ld_h,
-                                       float* act, uint32_t ld_act, const uint8_t* frozen, const uint32_t* steps);
-// Env step and thaw (both reset a policy state to the initial state of the env's own policy); hidden [16][ld] <- every column's
-// initial state.
-hipError_t launch_step_bank(hipStream_t s, Batch b, StepCfg c, const float* params, float* state, float* action, StatsPtrs st,
-                            uint32_t flags, SampleCfg sc, uint64_t seed, float* hidden, const float* weights,
-                            const uint32_t* block_policy, WrenchPtrs wr = WrenchPtrs{});
-hipError_t launch_thaw_frozen_bank(hipStream_t s, Batch b, SampleCfg c, uint64_t seed, const float* params, float* state,
-                                   StatsPtrs st, float* hidden, const float* weights, const uint32_t* block_policy);
+// launch_step: vector.step (README.md:98) + reward / termination / statistics, with a rollout's episode-end handling, host rows,
+// the folded observation and a wrench schedule as the description asks; a bank's step (block_policy set) is a rollout's, in place,
+// without host rows or a folded observation - anything else: hipErrorInvalidValue.
+hipError_t launch_step(hipStream_t s, const EnvStepLaunch& e);
+// launch_thaw_frozen: chained rollouts under auto-reset - envs left frozen by an earlier rollout start their next episode
+// (sample_initial_state with the env's episode counter + policy state reset, a bank's env to ITS policy's initial state), as the
+// fused kernel's prologue does.  In place: state == next_state.
+hipError_t launch_thaw_frozen(hipStream_t s, const EnvStepLaunch& e);
+// rq_policy_bank_reset: hidden [16][ld] <- the initial state of every column's policy (weights [P][RQ_POLICY_NUM_WEIGHTS], block_policy
+// [ld / 64])
 hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden, const float* weights, const uint32_t* block_policy);
 // chained mode of a tracked rollout, between the observation's assembly (k_observe, or the k_step before) and the actor: the row of
 // each env's episode step count comes off obs [RQ_OBSERVATION_DIM][ld] in place, and the envs that are not frozen add this step's

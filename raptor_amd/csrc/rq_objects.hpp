@@ -58,20 +58,11 @@ inline uint64_t fresh_version() {
 }
 
 // the two launches of a small-batch step: k_step (+ the next observation) and the speculative policy step on it
-struct StepPair {
-    rq::Batch b; rq::StepCfg c; rq::SampleCfg sc; uint64_t seed;
-    const float* params; const float* state_in; float* act; float* state_out; rq::StatsPtrs st;
-    rq::Mailbox mb_step; float* obs_alt;
-    rq::WrenchPtrs wr;             // the env's wrench schedule (rows == nullptr: none)
-    bool spec;
-    const float* packed; float* hidden_out; uint32_t ld_h; float* pol_act; int precision; rq::SasArgs sas;
-    rq::Mailbox mb_spec; const float* hidden_in;
-};
+// (`spec`: there is one; it reads the observation the step leaves in step.obs_of_next)
+struct StepPair { rq::EnvStepLaunch step; bool spec; rq::ActorStepLaunch actor; };
 
 // the launch of a small-batch policy step on host rows (mailbox in -> out): what a policy command replays as
-struct PolicyCmd {
-    uint32_t batch; const float* packed; float* obs; float* hidden; uint32_t ld; float* act; int precision; rq::SasArgs sas; rq::Mailbox mb;
-};
+using PolicyCmd = rq::ActorStepLaunch;
 
 // ---- resident executor (rq_resident.cpp; kernels: rq_kernels.hip k_resident_small / k_resident_loop / k_resident_policy) -------------
 constexpr uint32_t kResidentMaxEnvs = 256;            // one workgroup, a wave per SIMD of one CU (at 512 envs the launches, spread over the chip, are faster)
@@ -578,6 +569,9 @@ inline int hip_failed(const char* who, const char* what, hipError_t e) {
 // rq::launch_rollout_fused (rq_fused_route.hpp picks the kernel), and behind it what rq_device_last_rollout_ms goes by.
 rq::FusedArgs fused_args(const RolloutCall& c, const RolloutFrame& f);
 int fused_launch(const RolloutCall& c, rq::FusedArgs& a);
+// The chained mode's env step, and its thaw: the description, all but the actor's share of it - where a policy state is reset
+// (hidden, weights, block_policy) and, folding, the next observation.  A rollout's step, in place.
+rq::EnvStepLaunch env_step_launch(const RolloutCall& c, const RolloutFrame& f);
 
 constexpr uint32_t kGraphSteps = 25;   // steps per replayed graph (divides the 500-step episode)
 constexpr size_t kMaxGraphs = 8;       // executable graphs kept per env (one per distinct argument set)

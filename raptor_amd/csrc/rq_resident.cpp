@@ -118,13 +118,8 @@ int resident_gone(rq_device* dev) {
         if ((int32_t)(f - rx.pending_last) < 0) {
             RQ_REQUIRE((int32_t)(f - rx.pending_first) < 0, RQ_ERR_HIP, "the resident executor left in the middle of a command");
             ++rx.replays;
-            if (rx.bound.policy_kind) {
-                const PolicyCmd& p = rx.last.policy;
-                RQ_HIP(rq::launch_actor_step(dev->stream, p.batch, p.packed, p.obs, p.ld, p.hidden, p.ld, p.act, p.ld, nullptr, p.precision,
-                                             p.sas, p.mb));
-            } else {
-                RQ_HIP(launch_step_pair(dev, rx.last.step));
-            }
+            if (rx.bound.policy_kind) RQ_HIP(rq::launch_actor_step(dev->stream, rx.last.policy));
+            else                      RQ_HIP(launch_step_pair(dev, rx.last.step));
         }
     }
     return RQ_OK;
@@ -239,28 +234,29 @@ static uint32_t checksum(const float* rows, uint32_t n, uint32_t dim, uint32_t s
 // the loop's actions, n x 4 dwords, beside the line where the small kernel reads them in the same load; in device memory all kernels do
 void resident_post(rq_device* dev, const StepPair& p) {
     ResidentExecutor& rx = dev->resident;
-    const float* a = p.mb_step.rows_in;
-    if (p.b.n <= rq::kResidentSmallEnvs || rx.cmd_on_device) {
+    const rq::EnvStepLaunch& e = p.step;
+    const float* a = e.mb.rows_in;
+    if (e.b.n <= rq::kResidentSmallEnvs || rx.cmd_on_device) {
         __m128i* rows = reinterpret_cast<__m128i*>(rx.cmd + kRwRows);
-        for (uint32_t k = 0; k < p.b.n; ++k) _mm_store_si128(rows + k, _mm_loadu_si128(reinterpret_cast<const __m128i*>(a) + k));
+        for (uint32_t k = 0; k < e.b.n; ++k) _mm_store_si128(rows + k, _mm_loadu_si128(reinterpret_cast<const __m128i*>(a) + k));
     }
     rx.last.step = p;
-    const uint32_t bits = (p.obs_alt == rx.bound.obs[1] ? rq::kRbObsSel : 0u) | (p.hidden_in == rx.bound.hidden[1] ? rq::kRbHiddenSel : 0u);
-    post(rx, bits, p.state_in, p.state_out, p.mb_step.seq, p.mb_spec.seq, checksum(a, p.b.n, RQ_ACTION_DIM, RQ_ACTION_DIM), p.mb_step.seq);
+    const uint32_t bits = (e.obs_of_next == rx.bound.obs[1] ? rq::kRbObsSel : 0u) | (p.actor.hidden_in == rx.bound.hidden[1] ? rq::kRbHiddenSel : 0u);
+    post(rx, bits, e.state, e.next_state, e.mb.seq, p.actor.mb.seq, checksum(a, e.b.n, RQ_ACTION_DIM, RQ_ACTION_DIM), e.mb.seq);
 }
 
 // the policy's observation rows, each padded to kResidentPolicyRow floats: whole 16-byte stores
 void resident_post(rq_device* dev, const PolicyCmd& p) {
     ResidentExecutor& rx = dev->resident;
     __m128i* rows = reinterpret_cast<__m128i*>(rx.cmd + kRwRows);
-    for (uint32_t i = 0; i < p.batch; ++i) {
+    for (uint32_t i = 0; i < p.n; ++i) {
         alignas(16) float row[rq::kResidentPolicyRow] = {};
         std::memcpy(row, p.mb.rows_in + (size_t)i * p.mb.in_stride, RQ_POLICY_INPUT_DIM * sizeof(float));
         for (uint32_t k = 0; k < rq::kResidentPolicyRow / 4; ++k)
             _mm_store_si128(rows + (size_t)i * (rq::kResidentPolicyRow / 4) + k, _mm_load_si128(reinterpret_cast<const __m128i*>(row) + k));
     }
     rx.last.policy = p;
-    post(rx, 0u, nullptr, nullptr, 0u, p.mb.seq, checksum(p.mb.rows_in, p.batch, RQ_POLICY_INPUT_DIM, p.mb.in_stride), p.mb.seq);
+    post(rx, 0u, nullptr, nullptr, 0u, p.mb.seq, checksum(p.mb.rows_in, p.n, RQ_POLICY_INPUT_DIM, p.mb.in_stride), p.mb.seq);
 }
 
 }  // namespace rqh

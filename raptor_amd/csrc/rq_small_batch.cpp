@@ -193,11 +193,8 @@ int speculation_take(rq_device* dev, rq_policy* pol, const float* observation, u
 
 // the two launches of a small-batch step on the device's stream (also the replay of a command the resident executor never consumed)
 hipError_t launch_step_pair(rq_device* dev, const StepPair& p) {
-    hipError_t e = rq::launch_step(dev->stream, p.b, p.c, p.params, p.state_in, p.act, p.state_out, p.st, /*rollout=*/0, 0u, p.sc, p.seed,
-                                   nullptr, nullptr, p.mb_step, p.obs_alt, rq::NoiseCfg{}, false, 0u, nullptr, p.wr);
-    if (e == hipSuccess && p.spec)
-        e = rq::launch_actor_step(dev->stream, p.b.n, p.packed, p.obs_alt, p.b.ld, p.hidden_out, p.ld_h, p.pol_act, p.ld_h, nullptr,
-                                  p.precision, p.sas, p.mb_spec, p.hidden_in);
+    hipError_t e = rq::launch_step(dev->stream, p.step);
+    if (e == hipSuccess && p.spec) e = rq::launch_actor_step(dev->stream, p.actor);
     return e;
 }
 

@@ -444,6 +444,92 @@ def test_the_fused_route_names_the_family_and_the_register_build_of_every_launch
     assert got[(65536, 0, 0, 0, 1, 0, 0)] == ("PLAIN", "ActorF32") and got[(65537, 0, 0, 0, 1, 0, 0)] == ("PLAIN", "ActorF32Lean")
 
 
+def _expected_actor_step_route(n, precision, actor, interval, mailbox, sas, hidden_in, forced, ld):
+    """(family, actor build, groups per wave, grid in workgroups of 256 threads) of one actor step, written from the launchers this
+    route replaced (launch_actor_step, launch_actor_step_rate, launch_actor_step_bank, launch_actor_step_rate_bank) - not from the
+    header.  precision: 0 fp32, 1 bf16, 2 f16x2; actor: 0 a policy (native interval `interval`), 1 a bank, 2 a bank with its interval
+    table (a bank's intervals are its own: `interval` says nothing about it); ld: 0 = n rounded up to 64, else max(ld_h, ld_obs)."""
+    bank = actor != 0
+    rated = actor == 2 if bank else interval > 1
+    # what the old signatures could not express: the bank's launchers took no precision, no mailbox, no output stage and no second
+    # hidden buffer; the rate launcher no output stage and no second hidden buffer
+    if bank and (precision != 0 or mailbox or sas or hidden_in):
+        return "UNSUPPORTED", "-", 0, 0
+    if rated and (sas or hidden_in):
+        return "UNSUPPORTED", "-", 0, 0
+    build = ("ActorF32Lean", "ActorBF16", "ActorF16X2")[precision]
+    groups = (n + 63) // 64
+
+    def grid_for(threads):
+        return (threads + 255) // 256
+    if bank:        # k_actor_step[_rate]_bank<ActorF32Lean><<<grid_for((n + 63) / 64 * 64, kBlock)
+        return "BANK_RATE" if rated else "BANK", build, 1, grid_for(groups * 64)
+    if rated:       # launch_actor_step_rate: grid_for((n + 63) / 64 * 64, kBlock)
+        return "RATE", build, 1, grid_for(groups * 64)
+    gpw = forced if forced else (1 if groups < 4096 else min(64, groups // 1024))
+    ld_max = ld if ld else groups * 64
+    # "no host rows ... and every byte offset in 32 bits": refused when max(ld_h, ld_obs) * 4 * 26 >= 2^31 - 1
+    stream = gpw > 1 and not mailbox and ld_max * 4 * 26 < 2 ** 31 - 1
+    if stream:
+        return "STREAM", build, gpw, grid_for((groups + gpw - 1) // gpw * 64)
+    return "STEP", build, 1, grid_for(groups * 64)
+
+
+def test_the_actor_step_route_names_the_kernel_the_build_and_the_grid_of_every_launch(tmp_path):
+    """rq::route_actor_step (raptor_amd/csrc/rq_step_launch.hpp) decides which kernel takes an actor step - k_actor_step, the
+    streaming kernel, the rate kernel or a bank's - in which build, at how many 64-env groups per wave and on how many workgroups.
+    The bit-exact GPU suites cannot see a wrong pick between k_actor_step and k_actor_stream - same arithmetic - nor a grid with
+    workgroups to spare, so the whole grid is held here: tests/actor_step_route_driver.cpp includes the header alone under a plain
+    host compiler (no HIP) and prints the route of 9 batch sizes (a lone env, wave and workgroup boundaries, the mailbox threshold
+    1 024, bench.py's 65 536 and 2 097 152, a ragged and a whole batch of the 4 096 groups from which the step streams) x 3 precisions x (policy, bank, rated bank) x
+    interval 1 / 3 x mailbox x SampleAndSquash x hidden_in x forced groups per wave 0 / 4 x three leading dimensions (the batch's own
+    and the two either side of the 31-bit byte-offset limit); every row, the unsupported ones included, must be
+    _expected_actor_step_route's."""
+    import itertools
+    import subprocess
+    exe = str(tmp_path / "actor_step_route_driver")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "raptor_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "actor_step_route_driver.cpp")], check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = {}
+    for line in r.stdout.splitlines():
+        *key, family, build, gpw, grid = line.split()
+        assert tuple(map(int, key)) not in got, line
+        got[tuple(map(int, key))] = (family, build, int(gpw), int(grid))
+    ns = (1, 64, 65, 1023, 1024, 65536, 262143, 262144, 2097152)
+    lds = (0, 20648881, 20648882)
+    grid = list(itertools.product(ns, (0, 1, 2), (0, 1, 2), (1, 3), (0, 1), (0, 1), (0, 1), (0, 4), lds))
+    assert sorted(got) == sorted(grid)
+    wrong = [(key, got[key], _expected_actor_step_route(*key)) for key in grid if got[key] != _expected_actor_step_route(*key)]
+    assert not wrong, wrong[:10]
+    assert {f for f, *_ in got.values()} == {"UNSUPPORTED", "STEP", "STREAM", "RATE", "BANK", "BANK_RATE"}
+    assert {b for _, b, *_ in got.values()} == {"-", "ActorF32Lean", "ActorBF16", "ActorF16X2"}
+    # a few rows by hand.  One policy, nothing special: one workgroup per four waves, streaming from 4 096 groups on (262 081 envs)
+    assert got[(1, 0, 0, 1, 0, 0, 0, 0, 0)] == ("STEP", "ActorF32Lean", 1, 1)
+    assert got[(1023, 0, 0, 1, 0, 0, 0, 0, 0)] == ("STEP", "ActorF32Lean", 1, 4)
+    assert got[(65536, 0, 0, 1, 0, 0, 0, 0, 0)] == ("STEP", "ActorF32Lean", 1, 256)
+    assert got[(262143, 0, 0, 1, 0, 0, 0, 0, 0)] == ("STREAM", "ActorF32Lean", 4, 256)
+    assert got[(262144, 0, 0, 1, 0, 0, 0, 0, 0)] == ("STREAM", "ActorF32Lean", 4, 256)
+    assert got[(2097152, 1, 0, 1, 0, 0, 0, 0, 0)] == ("STREAM", "ActorBF16", 32, 256)
+    # the forced shape streams a small batch too - unless host rows are exchanged
+    assert got[(65, 0, 0, 1, 0, 0, 0, 4, 0)] == ("STREAM", "ActorF32Lean", 4, 1)
+    assert got[(65, 0, 0, 1, 1, 0, 0, 4, 0)] == ("STEP", "ActorF32Lean", 1, 1)
+    # byte offsets beyond 31 bits: max(ld_h, ld_obs) * 4 * 26 >= 2^31 - 1 keeps the stream kernel out, whichever of the two it is
+    assert 20648881 * 104 < 2 ** 31 - 1 <= 20648882 * 104
+    for hidden_in in (0, 1):
+        assert got[(2097152, 0, 0, 1, 0, 0, hidden_in, 0, 20648881)] == ("STREAM", "ActorF32Lean", 32, 256)
+        assert got[(2097152, 0, 0, 1, 0, 0, hidden_in, 0, 20648882)] == ("STEP", "ActorF32Lean", 1, 8192)
+    # bench.py's own rendition, at the sizes it measures and names kernels at (and around the threshold)
+    import bench
+    for n in (65536, 262143, 262144, 2097152):
+        family, _, gpw, grid_wg = got[(n, 0, 0, 1, 0, 0, 0, 0, 0)]
+        assert gpw == bench.actor_groups_per_wave(n), n
+        kernel = bench.actor_step_kernel_name(n)
+        assert kernel == {"STEP": "rq::k_actor_step<rq::ActorF32T<true> >", "STREAM": "rq::k_actor_stream<rq::ActorF32T<true> >"}[family], n
+        assert grid_wg * 256 == bench.launch_grid(kernel, n), n
+
+
 def test_the_loss_workspace_layout_is_the_two_sizes_of_before_and_its_regions_do_not_meet(tmp_path):
     """rq::loss_partial_layout (raptor_amd/csrc/rq_loss_launch.hpp) is the one statement of where a loss launch's waves leave their
     partial gradients, squared errors and normalisers: the launcher carves the workspace by it and the C layer reserves by it.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """k_actor_step launch-shape sweep: 64-env groups per wave (RQ_ACTOR_GROUPS_PER_WAVE, read once per process by
-launch_actor_step) against the batch size.  One process per setting:
+launch_actor_step and handed to rq::route_actor_step, raptor_amd/csrc/rq_step_launch.hpp, in place of its own
+actor_groups_per_wave: the route says which kernel and grid a setting means) against the batch size.  One process per setting:
 
     python tools/actor_gpw_sweep.py            # the sweep (spawns itself)
     RQ_ACTOR_GROUPS_PER_WAVE=16 python tools/actor_gpw_sweep.py --one 2097152
