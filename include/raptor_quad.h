@@ -891,6 +891,37 @@ RQ_API int rq_trajectory_policies_error_table(rq_trajectory* t, rq_policy_bank* 
                                               uint32_t ld_target, const uint32_t* age_edges, uint32_t n_buckets, int start,
                                               float* sse, uint32_t* count, uint32_t ld_out, int memory);
 
+/* ---- Effective feedback gains per env and episode age: what the policy does with what it knows.  At every live recorded step, at
+ * the recorded observation x (22) and the state h (16) entering the step, with the checkpoint's names
+ *     p0 = W0 x + b0,  y0 = relu(p0),  m_k = [p0_k > 0]  (ReLU'(0) = 0),
+ *     r = s(Wir y0 + bir + Whr h + bhr),  z = s(Wiz y0 + biz + Whz h + bhz),  c = Whn h + bhn,  n = tanh(Win y0 + bin + r c),
+ *     h' = (1 - z) n + z h,  a = W2 h' + b2,
+ *     A[i][k] = da_i/dp0_k = m_k sum_u W2[i][u] ((1 - z_u)(1 - n_u^2)(Win[u][k] + c_u r_u (1 - r_u) Wir[u][k])
+ *                                              + (h_u - n_u) z_u (1 - z_u) Wiz[u][k]),
+ * the instantaneous gain at fixed h is G = da/dx = A W0 [4][22] (columns: position 0..2, R row-major 3..11, linear velocity 12..14,
+ * angular velocity 15..17, previous action 18..21).  The path of x_t into later actions through the recurrence is not part of it.
+ * W0 is constant over the recording, so the calls sum A alone and the caller multiplies the sums by W0 once.  The step, the episode
+ * rules and the start are those of rq_trajectory_policy_forward; AGE, age_edges and the buckets are those of the error table above.
+ * sum [n_buckets][4][16][ld_out]: cell (b, i, k, e) = the sequential fp32 sum, in time order, of A_t[i][k] over the live steps of env
+ * e whose age lies in bucket b (an env that returns to a bucket in a later episode goes on from its total); count
+ * [n_buckets][ld_out]: the number of those steps.  ld_out >= n_envs; every cell with e < n_envs is written, columns >= n_envs are
+ * left as they were.  A frozen step, a step outside the buckets and a padding column are selected away before any arithmetic on the
+ * sums: NaN in a frozen observation reaches no sum.  One lane sums its own env's rows: no atomics, the same bits every run.
+ * rq_trajectory_policies_gain_table: the same for a bank, env e by policy policy_id[e] (host array, constant on every aligned block
+ * of 64); a column block holds, bit for bit, what a rq_policy created from that policy's weights gives on it.
+ * The calls read the recording and the policy and leave the trajectory's saved state alone: a rq_trajectory_policy_backward whose
+ * forward came before the call may follow it.  The policy's hidden state is not changed.  There is no target.
+ * memory: RQ_DST_HOST = sum and count are host arrays (synchronous); RQ_DST_DEVICE / RQ_DST_DEVICE_ASYNC = device memory of the
+ * trajectory's device (synchronised before return / only enqueued on rq_device_stream()).
+ * Refused before anything is enqueued, outputs untouched, in the error table's words: a bf16 / f16x2 policy, a Standardize or
+ * SampleAndSquash stage, a native interval above 1, objects of two devices, an empty trajectory, bad ids; ld_out < n_envs; n_buckets
+ * outside 1 .. 32; edges that do not ascend strictly; a null argument; sum or count that is not device memory of the trajectory's
+ * device when one is announced. */
+RQ_API int rq_trajectory_policy_gain_table(rq_trajectory* t, rq_policy* policy, const uint32_t* age_edges, uint32_t n_buckets,
+                                           int start, float* sum, uint32_t* count, uint32_t ld_out, int memory);
+RQ_API int rq_trajectory_policies_gain_table(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const uint32_t* age_edges,
+                                             uint32_t n_buckets, int start, float* sum, uint32_t* count, uint32_t ld_out, int memory);
+
 
 /* ---- Multi-GPU: the path's one exchange ---------------------------------------------
  * Envs are independent, so a batch shards over GPUs with no data-path collective: one process per GPU, rank r

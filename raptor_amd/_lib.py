@@ -224,6 +224,8 @@ _SIGNATURES = {
                                                 C.c_int],
     "rq_trajectory_policy_error_table": [_vp, _vp, _fp, C.c_uint32, _vp, C.c_uint32, C.c_int, _fp, _vp, C.c_uint32, C.c_int],
     "rq_trajectory_policies_error_table": [_vp, _vp, _vp, _fp, C.c_uint32, _vp, C.c_uint32, C.c_int, _fp, _vp, C.c_uint32, C.c_int],
+    "rq_trajectory_policy_gain_table": [_vp, _vp, _vp, C.c_uint32, C.c_int, _fp, _vp, C.c_uint32, C.c_int],
+    "rq_trajectory_policies_gain_table": [_vp, _vp, _vp, _vp, C.c_uint32, C.c_int, _fp, _vp, C.c_uint32, C.c_int],
     "rq_reference_create": [_vp, _fp, C.c_uint32, C.POINTER(_vp)],
     "rq_reference_destroy": [_vp],
     "rq_rollout_track": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_int, C.c_uint32, _vp, _vp],

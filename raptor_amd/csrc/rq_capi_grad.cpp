@@ -6,6 +6,8 @@
 // The four loss calls have a *_weighted sibling each - a weight per env, or per env and step, in the loss - that shares their body.
 // rq_trajectory_policy_error_table / rq_trajectory_policies_error_table: the forward alone against the loss calls' target - the
 // squared imitation error per env and bucket of episode age; the trajectory's saved state is not theirs and stays as it was.
+// rq_trajectory_policy_gain_table / rq_trajectory_policies_gain_table: A = da/dp0 summed per env and bucket of episode age, the
+// effective feedback gains up to the constant W0; no target, the saved state stays as it was too.
 // Every call with a `memory` argument reads refusals, DeviceScope, prepare, in, launch, out, finish: the staging copies and the final
 // wait are one rq::CallMemory (rq_call_memory.hpp), the staging buffers are reserved here.  Kernels: rq_grad.hpp, rq_grad_bank.hpp.
 #include "rq_objects.hpp"
@@ -221,10 +223,12 @@ int check_host_array(const CallMemory& mem, const void* p, const char* what, con
     return RQ_OK;
 }
 
+// `Launch` is rq::ErrorTableLaunch or rq::GainTableLaunch (edges, n_buckets); `noun` names the float output, "sse" or "sum".
+template <typename Launch>
 int error_table_check(const char* what, rq_trajectory* t, const float* target, const uint32_t* age_edges, uint32_t n_buckets, float* sse,
-                      uint32_t* count, uint32_t ld_out, int memory, rq::ErrorTableLaunch* a) {
+                      uint32_t* count, uint32_t ld_out, int memory, Launch* a, const char* noun = "sse") {
     RQ_REFUSE(what, age_edges, RQ_ERR_INVALID_ARGUMENT, "null argument: age_edges");
-    RQ_REFUSE(what, sse, RQ_ERR_INVALID_ARGUMENT, "null argument: sse");
+    RQ_REFUSE(what, sse, RQ_ERR_INVALID_ARGUMENT, std::string("null argument: ") + noun);
     RQ_REFUSE(what, count, RQ_ERR_INVALID_ARGUMENT, "null argument: count");
     RQ_REFUSE(what, n_buckets >= 1 && n_buckets <= rq::kErrorTableMaxBuckets, RQ_ERR_INVALID_ARGUMENT,
               "n_buckets must be 1 .. 32, not " + std::to_string(n_buckets));
@@ -237,10 +241,10 @@ int error_table_check(const char* what, rq_trajectory* t, const float* target, c
     RQ_REFUSE(what, ld_out >= t->env->n, RQ_ERR_INVALID_ARGUMENT, "ld_out must be at least the number of envs");
     const rq_device* dev = t->env->dev;
     const CallMemory mem(memory, dev->stream, dev->ordinal);
-    int rc = check_device_array(mem, sse, what, "sse"); if (rc) return rc;
+    int rc = check_device_array(mem, sse, what, noun); if (rc) return rc;
     rc = check_device_array(mem, count, what, "count"); if (rc) return rc;
     rc = check_host_array(mem, target, what, "the target"); if (rc) return rc;
-    rc = check_host_array(mem, sse, what, "sse"); if (rc) return rc;
+    rc = check_host_array(mem, sse, what, noun); if (rc) return rc;
     return check_host_array(mem, count, what, "count");
 }
 
@@ -265,6 +269,31 @@ int error_table_begin(rq_trajectory* t, const float* target, uint32_t ld_target,
     }
     if (target) RQ_HIP(mem.in(target, y_floats, mem.host() ? s_sse + 2 * cells : nullptr, &p.target));
     a->sse = mem.out(sse, ld_out, s_sse, ld, env->n, B);
+    a->count = mem.out(count, ld_out, s_count, ld, env->n, B);
+    a->ld_out = mem.host() ? ld : ld_out;
+    return RQ_OK;
+}
+
+// ---- the feedback-gain table (rq_trajectory_policy_gain_table / rq_trajectory_policies_gain_table) ----
+// The error table's refusals (error_table_check, without a target) and its begin without one: sum [B][4][16][.] and count [B][.] as
+// the launch takes them.  The saved state is not touched here either.
+int gain_table_begin(rq_trajectory* t, int start, CallMemory& mem, float* sum, uint32_t* count, uint32_t ld_out, rq::GainTableLaunch* a) {
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    const uint32_t ld = env->ld, B = a->n_buckets;
+    rq::LossLaunch& p = a->pass;
+    p.n = env->n; p.ld = ld; p.steps = t->length;
+    p.obs = t->obs; p.done = t->done;
+    p.start_initial = start == RQ_GRAD_START_INITIAL;
+    // host-memory calls: one device block, sum [B][64][ld] | count [B][ld]; only the envs' columns go back
+    const size_t rows = (size_t)B * RQ_ACTION_DIM * RQ_POLICY_HIDDEN_DIM, cells = rows * ld;
+    float* s_sum = nullptr; uint32_t* s_count = nullptr;
+    if (mem.host()) {
+        RQ_HIP(t->grad.rows.reserve(dev->stream, cells + (size_t)B * ld));
+        s_sum = t->grad.rows.get();
+        s_count = reinterpret_cast<uint32_t*>(s_sum + cells);
+    }
+    a->sum = mem.out(sum, ld_out, s_sum, ld, env->n, rows);
     a->count = mem.out(count, ld_out, s_count, ld, env->n, B);
     a->ld_out = mem.host() ? ld : ld_out;
     return RQ_OK;
@@ -651,6 +680,56 @@ RQ_API int rq_trajectory_policies_error_table(rq_trajectory* t, rq_policy_bank* 
     a.pass.hidden = start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr;
     a.pass.ld_h = bank->ld;
     RQ_HIP(rq::launch_policy_error_table(dev->stream, a));
+    RQ_HIP(mem.finish());
+    return RQ_OK;
+}
+
+// ---------------------------------------------------------------------------- the feedback-gain table ---
+RQ_API int rq_trajectory_policy_gain_table(rq_trajectory* t, rq_policy* pol, const uint32_t* age_edges, uint32_t n_buckets, int start,
+                                           float* sum, uint32_t* count, uint32_t ld_out, int memory) {
+    const char* what = __func__;
+    RQ_REQUIRE(t && pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = loss_check(t, pol, nullptr, 0, kNoWeight, start, memory, what); if (rc) return rc;
+    rq::GainTableLaunch a;
+    rc = error_table_check(what, t, nullptr, age_edges, n_buckets, sum, count, ld_out, memory, &a, "sum"); if (rc) return rc;
+    rq_device* dev = t->env->dev;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, t->env->n); if (rc) return rc; }
+    rc = ensure_grad_image(pol); if (rc) return rc;
+    rc = gain_table_begin(t, start, mem, sum, count, ld_out, &a); if (rc) return rc;
+    a.pass.packed = pol->w_packed; a.pass.gpacked = pol->w_packed_grad;
+    a.pass.hidden = start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr;
+    a.pass.ld_h = pol->ld;
+    RQ_HIP(rq::launch_policy_gain_table(dev->stream, a));
+    RQ_HIP(mem.finish());
+    return RQ_OK;
+}
+
+RQ_API int rq_trajectory_policies_gain_table(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const uint32_t* age_edges,
+                                             uint32_t n_buckets, int start, float* sum, uint32_t* count, uint32_t ld_out, int memory) {
+    const char* what = __func__;
+    RQ_REQUIRE(t && bank && policy_id, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = bank_loss_check(t, bank, policy_id, nullptr, 0, kNoWeight, start, memory, what); if (rc) return rc;
+    rq::GainTableLaunch a;
+    rc = error_table_check(what, t, nullptr, age_edges, n_buckets, sum, count, ld_out, memory, &a, "sum"); if (rc) return rc;
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    if (start == RQ_GRAD_START_CURRENT) {
+        rc = bank_size(bank, env->n); if (rc) return rc;
+        RQ_REQUIRE(bank->ld == env->ld, RQ_ERR_SHAPE_MISMATCH, "policy bank batch does not match the env");
+    }
+    rc = bank_table(bank, dev, env->uid, policy_id, env->n); if (rc) return rc;
+    rc = bank_grad_images(bank); if (rc) return rc;
+    if (start == RQ_GRAD_START_CURRENT) { rc = bank_apply_reset(bank); if (rc) return rc; }
+    rc = gain_table_begin(t, start, mem, sum, count, ld_out, &a); if (rc) return rc;
+    a.pass.packed = bank->images; a.pass.gpacked = bank->gimages;
+    a.pass.n_policies = bank->n_policies; a.pass.block_policy = bank->table;
+    a.pass.hidden = start == RQ_GRAD_START_CURRENT ? bank->hidden.get() : nullptr;
+    a.pass.ld_h = bank->ld;
+    RQ_HIP(rq::launch_policy_gain_table(dev->stream, a));
     RQ_HIP(mem.finish());
     return RQ_OK;
 }

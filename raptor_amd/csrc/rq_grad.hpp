@@ -24,8 +24,11 @@
 // How well the student imitates, per env and bucket of episode age, from the forward alone:
 //   k_policy_error_table[_bank]   the forward storing nothing of the pass: the lane sums its env's squared error (a - y)^2 over the
 //                                 four actions per age bucket, sse / count [n_buckets][ld_out]; launch_policy_error_table
-// The forwards, the backwards, the loss reductions and the Adam kernels are one text each (rq_grad_forward.inc, rq_grad_backward.inc,
-// rq_loss_reduce.inc, rq_adam_repack.inc), compiled once per kernel.  Every form of the loss launch goes through one launcher,
+// What the policy does with what it knows, the effective feedback gains per env and bucket of episode age:
+//   k_policy_gain_table[_bank]    the backward's recompute walked forwards, four local seeds e_i through W2 and Wi^T: the lane sums
+//                                 A = da/dp0 [4][16] per age bucket, sum [n_buckets][4][16][ld_out]; launch_policy_gain_table
+// The forwards, the backwards, the gain table, the loss reductions and the Adam kernels are one text each (rq_grad_forward.inc,
+// rq_grad_backward.inc, rq_gain_table.inc, rq_loss_reduce.inc, rq_adam_repack.inc), compiled once per kernel.  Every form of the loss launch goes through one launcher,
 // launch_policy_loss_grad (rq_grad_bank.hpp), from one description (rq_loss_launch.hpp).
 //
 // Layouts (rq_device_math.hpp "actor"): a wave owns 64 envs as 4 tiles of 16; lane (q, j) = (l >> 4, l & 15) holds, in the Q
@@ -106,6 +109,12 @@ __device__ __forceinline__ float sigm2(float x) { return __builtin_amdgcn_rcpf(1
 #define RQ_GRAD_BANK 0
 #define RQ_GRAD_WEIGHTED 1
 #include "rq_grad_backward.inc"
+
+// the backward's recompute walked forwards with four local seeds and no weight gradient: da/dp0 per env and bucket of episode age,
+// summed in the lane (rq_gain_table.inc) - nothing of the recording's Jacobians is stored
+#define RQ_GAIN_TABLE_KERNEL k_policy_gain_table
+#define RQ_GRAD_BANK 0
+#include "rq_gain_table.inc"
 
 // grad[p] = sum over waves w = 0, 1, ... of partial[w][p], in that order
 __global__ __launch_bounds__(256) void k_policy_grad_reduce(uint32_t waves, const float* __restrict__ partial,

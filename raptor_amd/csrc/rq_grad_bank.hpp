@@ -10,6 +10,7 @@
 //   k_adam_repack_bank                 k_adam_repack on slot p; a policy that owns no wave is skipped       P
 //   k_adam_set_lr_bank                 up to 256 learning rates, carried as kernel arguments                1
 //   k_policy_error_table_bank          k_policy_error_table, the wave's image picked per block             waves
+//   k_policy_gain_table_bank           k_policy_gain_table, both images picked per block                   waves
 // The weights are wave-uniform MFMA operands read once from an image pointer, so the seeded pair is the single policy's text
 // (rq_grad_forward.inc, rq_grad_backward.inc under RQ_GRAD_BANK) with that pointer chosen by block_policy[blockIdx.x], as
 // k_rollout_fused_bank chooses it: a wave computes what it computes for a policy of its own, bit for bit.  The reduction is the single
@@ -45,6 +46,11 @@ namespace rq {
 #define RQ_GRAD_BANK 1
 #define RQ_GRAD_WEIGHTED 1
 #include "rq_grad_backward.inc"
+
+// k_policy_gain_table with both of the wave's images picked per block (rq_gain_table.inc under RQ_GRAD_BANK)
+#define RQ_GAIN_TABLE_KERNEL k_policy_gain_table_bank
+#define RQ_GRAD_BANK 1
+#include "rq_gain_table.inc"
 
 // k_policy_loss_reduce per policy (blockIdx.y), segmented by the CSR list (rq_loss_reduce.inc under RQ_GRAD_BANK)
 #define RQ_LOSS_REDUCE_KERNEL k_policy_loss_reduce_bank
@@ -161,6 +167,31 @@ hipError_t launch_policy_error_table(hipStream_t s, const ErrorTableLaunch& a) {
         edges.v[b] = a.edges[b];
     }
     return p.n > kOneWavePerSimdEnvs ? launch_error_table<ActorF32Lean>(s, a, edges) : launch_error_table<ActorF32>(s, a, edges);
+}
+
+// The gain table (rq_loss_launch.hpp GainTableLaunch): one launch, one wave per 64-env block, the single kernel or the bank's picked
+// here and nowhere else.  A description whose strides or buckets would let a lane read or write beside its cells is refused here,
+// whatever the caller checked.
+hipError_t launch_policy_gain_table(hipStream_t s, const GainTableLaunch& a) {
+    const LossLaunch& p = a.pass;
+    if (p.n == 0 || p.steps == 0 || (p.block_policy && p.n_policies == 0)) return hipErrorInvalidValue;
+    if (a.n_buckets < 1 || a.n_buckets > kErrorTableMaxBuckets || a.ld_out < p.n || p.ld < p.n) return hipErrorInvalidValue;
+    if (!p.packed || !p.gpacked || !p.obs || !p.done || !a.sum || !a.count || (!p.start_initial && (!p.hidden || p.ld_h < p.n)))
+        return hipErrorInvalidValue;
+    ProbeEdges edges{};
+    for (uint32_t b = 0; b <= a.n_buckets; ++b) {
+        if (b > 0 && a.edges[b] <= a.edges[b - 1]) return hipErrorInvalidValue;
+        edges.v[b] = a.edges[b];
+    }
+    const uint32_t waves = (p.n + 63) / 64, si = p.start_initial ? 1u : 0u;
+    if (p.block_policy)
+        k_policy_gain_table_bank<<<waves, 64, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.gpacked, p.block_policy, (uint32_t)RQ_PACKED_FLOATS,
+                                                      (uint32_t)RQ_PACKED_GRAD_FLOATS, p.obs, p.done, p.hidden, p.ld_h, si, edges, a.n_buckets,
+                                                      a.sum, a.count, a.ld_out);
+    else
+        k_policy_gain_table<<<waves, 64, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.gpacked, p.obs, p.done, p.hidden, p.ld_h, si, edges,
+                                                 a.n_buckets, a.sum, a.count, a.ld_out);
+    return hipGetLastError();
 }
 
 hipError_t launch_adam_repack_bank(hipStream_t s, uint32_t n_policies, const uint32_t* wave_offsets, const float* grad, float* w, float* m,

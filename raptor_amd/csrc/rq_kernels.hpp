@@ -155,6 +155,9 @@ hipError_t launch_policy_grad_forward_state(hipStream_t s, const LossLaunch& a);
 // The forward alone, storing nothing of the pass: the squared imitation error per env and bucket of episode age, one policy or a bank,
 // as rq_loss_launch.hpp's ErrorTableLaunch describes it.  One launch; a lane sums its own env: deterministic, no atomics.
 hipError_t launch_policy_error_table(hipStream_t s, const ErrorTableLaunch& a);
+// The backward's recompute walked forwards with four local seeds: A = da/dp0 [4][16] summed per env and bucket of episode age, one
+// policy or a bank, as rq_loss_launch.hpp's GainTableLaunch describes it.  One launch; a lane sums its own rows: deterministic.
+hipError_t launch_policy_gain_table(hipStream_t s, const GainTableLaunch& a);
 // Adam's state on the device: hyper-parameters, the step count t and the running powers beta^t (1 before the first step)
 struct AdamState { double lr, beta1, beta2, eps, weight_decay, beta1_t, beta2_t; uint32_t step, pad; };
 // one element of an operand image as a function of the flat weights: 0 (a == PACK_GATHER_NONE), k w[a], or k (w[a] + w[b])

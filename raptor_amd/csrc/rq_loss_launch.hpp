@@ -1,7 +1,8 @@
 // rq_loss_launch.hpp - what one loss-and-gradient launch of the learner is (LossLaunch; launch_policy_loss_grad, rq_grad_bank.hpp,
 // reads it and the C layer, rq_capi_grad.cpp, fills it), and where the per-wave regions of its workspace lie (loss_partial_layout:
 // the one statement of that layout - the launcher carves by it, the C layer reserves by it); and its sibling without a backward, the
-// error table's launch (ErrorTableLaunch; launch_policy_error_table).  Host code without a HIP dependency: a
+// error table's launch (ErrorTableLaunch; launch_policy_error_table), and the gain table's (GainTableLaunch;
+// launch_policy_gain_table; tests/gain_launch_driver.cpp holds its defaults).  Host code without a HIP dependency: a
 // plain host compiler takes this file alone (tests/loss_launch_driver.cpp does, and holds the layout against tests/test_capi_cpu.py's
 // own figures).
 #pragma once
@@ -79,6 +80,21 @@ struct ErrorTableLaunch {
     uint32_t edges[kErrorTableMaxBuckets + 1] = {};   // edges[0 .. n_buckets], strictly ascending: bucket b holds ages [edges[b], edges[b + 1])
     // sse [n_buckets][ld_out] and count [n_buckets][ld_out], ld_out >= n: every cell (b, i < n) is written, columns >= n are left
     float* sse = nullptr;
+    uint32_t* count = nullptr;
+    uint32_t ld_out = 0;
+};
+
+// One gain-table launch (launch_policy_gain_table, rq_grad_bank.hpp): the backward's recompute walked forwards with four local seeds,
+// storing nothing of the pass, and A = da/dp0 [4][16] summed per env and bucket of episode age.  `pass` is read as the seeded
+// backward reads it - n, ld, steps, packed and gpacked (a bank: block_policy and n_policies too), obs, done - plus the forward's
+// hidden, ld_h, start_initial; there is no target, and `saved`, the weight, the workspace and the loss outputs are not touched.
+struct GainTableLaunch {
+    LossLaunch pass;
+    uint32_t n_buckets = 0;                           // 1 .. kErrorTableMaxBuckets
+    uint32_t edges[kErrorTableMaxBuckets + 1] = {};   // as ErrorTableLaunch's
+    // sum [n_buckets][4][16][ld_out], cell (b, i, k, e) = the sum of A_t[i][k] over env e's live steps in bucket b, and count
+    // [n_buckets][ld_out], ld_out >= n: every cell with e < n is written, columns >= n are left
+    float* sum = nullptr;
     uint32_t* count = nullptr;
     uint32_t ld_out = 0;
 };

@@ -20,6 +20,13 @@ steps after the onset?"
     probe = probing.HiddenProbe(policy, None, probing.WRENCH_NAMES, edges)
     m = probe.moments(traj, targets=Y, device=True)
 
+What the policy DOES with what it knows is read off the same recording as effective feedback gains (``feedback_gains``,
+rq_trajectory_policy_gain_table): the local Jacobian da/dobs [4, 22] at every live step, summed per env and age bucket on the device.
+
+    gains = probing.feedback_gains(traj, policy, edges=probing.log_age_edges(500, 10))
+    g = gains.by_age()                                # [B, 4, 22]: how the control law settles over an episode's first steps
+    kp = probing.GainTable.block(g, "position")       # [B, 4, 3]: the position gain
+
 Age follows the forward's episode rule: 0 at the first recorded step; a step is live when its done code is not 4; after a live
 step with code 1 or 2 the age is 0 again, after any other live step one more; frozen steps neither count nor age.
 """
@@ -298,3 +305,172 @@ class HiddenProbe:
             with np.errstate(divide="ignore", invalid="ignore"):
                 out[b] = np.where(sst > 0, 1.0 - sse / sst, np.nan)
         return out
+
+
+# ---------------------------------------------------------------------------- the effective feedback gains ---
+# the 22 columns of a gain G = da/dobs, by block of the observation
+OBSERVATION_BLOCKS = {"position": (0, 3), "orientation": (3, 12), "linear_velocity": (12, 15), "angular_velocity": (15, 18),
+                      "last_action": (18, 22)}
+_W0 = (0, 16 * 22)            # layer_0's weights in the flat checkpoint, [16, 22] row-major
+
+
+class GainTable:
+    """What ``feedback_gains`` returns: ``sum`` [B, 4, 16, N] float32 - per age bucket and env the sum over its live steps of
+    A = da/dp0, the Jacobian of the four actions with respect to layer_0's 16 pre-activations -, ``count`` [B, N] - the number of
+    those steps -, ``edges`` [B + 1] (uint32, NumPy) and ``W0``, layer_0's weights: [16, 22], or [P, 16, 22] together with
+    ``policy_ids`` [N] for a bank.  The gain is G = da/dobs = A W0 [4, 22]; W0 is constant over a recording, so the sums hold A and
+    every method multiplies by W0 once, after its reduction over envs (under a bank each policy's part by its own W0, then the
+    parts are added).  The arrays are NumPy or torch tensors, as the call made them; every method works in float64 on whatever they
+    are and returns the same kind.  A mean over nothing is NaN."""
+
+    def __init__(self, sum, count, edges, W0, policy_ids=None):
+        self.sum, self.count = sum, count
+        self.edges = np.asarray(edges, np.uint32)
+        self.W0 = np.asarray(W0, np.float64)
+        if len(sum.shape) != 4 or tuple(sum.shape[1:3]) != (4, HIDDEN) or tuple(count.shape) != (sum.shape[0], sum.shape[3]) \
+                or self.edges.shape != (sum.shape[0] + 1,):
+            raise ValueError("sum must be [B, 4, 16, N], count [B, N] and edges [B + 1]")
+        N = int(sum.shape[3])
+        if policy_ids is None:
+            if self.W0.shape != (HIDDEN, 22):
+                raise ValueError("W0 must be [16, 22] (or [P, 16, 22] with policy_ids)")
+            self.W0, self.policy_ids = self.W0[None], np.zeros(N, np.int64)
+            self._bank = False
+        else:
+            self.policy_ids = np.asarray(policy_ids).astype(np.int64)
+            if self.W0.ndim != 3 or self.W0.shape[1:] != (HIDDEN, 22) or self.policy_ids.shape != (N,) or \
+                    (N and (self.policy_ids.min() < 0 or self.policy_ids.max() >= self.W0.shape[0])):
+                raise ValueError(f"W0 must be [P, 16, 22] and policy_ids [{N}] integers below P")
+            self._bank = True
+
+    # ---- float64 views, [B, 4, 16, N] and [B, N], and W0 of the same kind ----
+    def _torch(self):
+        return hasattr(self.sum, "data_ptr")
+
+    def _f64(self):
+        if self._torch():
+            import torch
+            return self.sum.to(torch.float64), self.count.to(torch.float64), torch.as_tensor(self.W0, device=self.sum.device)
+        return np.asarray(self.sum, np.float64), np.asarray(self.count, np.float64), self.W0
+
+    def _index(self, ids):
+        if self._torch():
+            import torch
+            return torch.as_tensor(np.asarray(ids, np.int64), device=self.sum.device)
+        return np.asarray(ids, np.int64)
+
+    def _grouped(self, s, c, ids, G):
+        """s [B, 4, 16, N], c [B, N], ids [N] below G -> (gs [G, P, B, 4, 16], gc [G, B]): the sums of A by group and policy"""
+        P, B, N = self.W0.shape[0], int(s.shape[0]), int(s.shape[3])
+        key = np.asarray(ids, np.int64) * P + self.policy_ids
+        if self._torch():
+            import torch
+            gs = torch.zeros((G * P, B, 4, HIDDEN), dtype=torch.float64, device=s.device).index_add(0, self._index(key), s.permute(3, 0, 1, 2))
+            gc = torch.zeros((G, B), dtype=torch.float64, device=s.device).index_add(0, self._index(ids), c.T)
+        else:
+            gs, gc = np.zeros((G * P, B, 4, HIDDEN)), np.zeros((G, B))
+            np.add.at(gs, key, s.transpose(3, 0, 1, 2))
+            np.add.at(gc, np.asarray(ids, np.int64), c.T)
+        return gs.reshape(G, P, B, 4, HIDDEN), gc
+
+    def _gains(self, gs, gc, W0):
+        """gs [G, P, B, 4, 16] sums of A, gc [G, B] -> [G, B, 4, 22]: each policy's part times its own W0, added, over the count"""
+        if self._torch():
+            import torch
+            g = torch.einsum("gpbik,pkf->gbif", gs, W0)
+            n = gc[:, :, None, None]
+            return torch.where(n > 0, g / torch.clamp(n, min=1.0), torch.full_like(g, float("nan")))
+        g = np.einsum("gpbik,pkf->gbif", gs, W0)
+        n = gc[:, :, None, None]
+        return np.where(n > 0, g / np.maximum(n, 1.0), np.nan)
+
+    def by_age(self):
+        """-> [B, 4, 22]: the mean gain of all envs by age bucket - how the control law settles over an episode's first steps"""
+        return self.by_group(np.zeros(int(self.sum.shape[3]), np.int64), 1)[0]
+
+    def by_group(self, ids, n_groups):
+        """``ids`` [N] integers below ``n_groups`` - the policy, scenario or parameter bin of every env -> [G, B, 4, 22]: the mean
+        gain of each group's envs by age bucket.  A group may mix the policies of a bank."""
+        s, c, W0 = self._f64()
+        G, N = int(n_groups), int(s.shape[3])
+        g = np.asarray(ids.cpu() if hasattr(ids, "data_ptr") else ids)
+        if g.shape != (N,) or not np.issubdtype(g.dtype, np.integer) or (N and (g.min() < 0 or g.max() >= G)):
+            raise ValueError(f"ids must be [{N}] integers below {G}")
+        return self._gains(*self._grouped(s, c, g, G), W0)
+
+    def per_env(self, bucket=None):
+        """-> [4, 22, N]: every env's mean gain at the ages of ``bucket``; None: over all buckets"""
+        s, c, W0 = self._f64()
+        if bucket is None:
+            s, c = s.sum(0), c.sum(0)
+        else:
+            s, c = s[int(bucket)], c[int(bucket)]
+        if self._torch():
+            import torch
+            g = torch.einsum("ike,ekf->ife", s, W0[self._index(self.policy_ids)])
+            return torch.where(c > 0, g / torch.clamp(c, min=1.0), torch.full_like(g, float("nan")))
+        g = np.einsum("ike,ekf->ife", s, W0[self.policy_ids])
+        return np.where(c > 0, g / np.maximum(c, 1.0), np.nan)
+
+    @staticmethod
+    def block(g, name, axis=None):
+        """The columns of the observation block ``name`` (``OBSERVATION_BLOCKS``) of a gain array ``g``.  ``axis``: where its 22
+        columns lie; None: the last axis if that has 22 entries (``by_age``, ``by_group``), else the one before it (``per_env``)."""
+        if name not in OBSERVATION_BLOCKS:
+            raise ValueError(f"unknown block {name!r}; the blocks: {sorted(OBSERVATION_BLOCKS)}")
+        if axis is None:
+            axis = -1 if g.shape[-1] == 22 else -2
+        if g.shape[axis] != 22:
+            raise ValueError("the axis holds no 22 observation columns")
+        a, z = OBSERVATION_BLOCKS[name]
+        index = [slice(None)] * len(g.shape)
+        index[axis] = slice(a, z)
+        return g[tuple(index)]
+
+
+def feedback_gains(traj, policy, edges=None, start="initial", policy_ids=None):
+    """The policy's effective feedback gains on the recording, per env and bucket of episode age -> ``GainTable``.  One pass on
+    the device (rq_trajectory_policy_gain_table) that stores nothing of the recording's Jacobians.
+
+    At every live step, at the recorded observation x and the state h entering the step, the gain is the local Jacobian
+    G = da/dx [4, 22] of the action: its columns are the position gain (0..2), the attitude gain (3..11, R row-major), the damping
+    gain (12..14, linear velocity), the rate gain (15..17, angular velocity) and the action feedback (18..21)
+    (``OBSERVATION_BLOCKS``).  G is the INSTANTANEOUS gain at fixed h: the path of x_t into later actions through the recurrence is
+    not part of it.  ReLU'(0) = 0, as in the learner's backward.
+
+    ``policy``: a ``Raptor`` (fp32, no Standardize / SampleAndSquash stage, native rate), or a ``PolicyBank`` together with
+    ``policy_ids`` - one id per env, constant on every aligned block of 64.  ``edges`` and the ages as for
+    ``training.imitation_error`` (None: one bucket for every age); ``start`` as for ``Distiller``.
+
+    The table's arrays are device tensors when torch is present, NumPy otherwise; the call orders itself against torch's current
+    stream.  The trajectory's saved state is not touched: a pending ``trajectory_actions`` backward stays valid."""
+    from .training import START, Distiller, _age_edges, _device_ptr
+    if start not in START:
+        raise ValueError('start must be "initial" or "current"')
+    e = _age_edges(edges)
+    N = int(traj._env.N_ENVIRONMENTS)
+    bank = hasattr(policy, "n_policies")
+    if bank and policy_ids is None:
+        raise ValueError("a PolicyBank needs policy_ids: one id per env, constant on every aligned block of 64")
+    if not bank and policy_ids is not None:
+        raise ValueError("policy_ids belong to a PolicyBank")
+    ids = None
+    if bank:
+        from .policy_bank import check_policy_ids
+        ids = check_policy_ids(policy_ids, policy.n_policies, N)
+    head = (policy._h, ids.ctypes.data) if bank else (policy._handle(traj._env._device),)
+    name = "rq_trajectory_policies_gain_table" if bank else "rq_trajectory_policy_gain_table"
+    dev = Distiller._torch_device(traj)
+    B = e.size - 1
+    if dev is None:
+        total, count = np.empty((B, 4, HIDDEN, N), np.float32), np.empty((B, N), np.uint32)
+        _lib.call(name, traj._require("trajectory"), *head, e.ctypes.data, B, START[start], _lib.fptr(total), count.ctypes.data, N, 0)
+    else:
+        import torch
+        total = torch.empty((B, 4, HIDDEN, N), dtype=torch.float32, device=dev)
+        count = torch.empty((B, N), dtype=torch.int32, device=dev)          # the engine's uint32; a recording has fewer than 2^31 steps
+        torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
+        _lib.call(name, traj._require("trajectory"), *head, e.ctypes.data, B, START[start], _device_ptr(total), _device_ptr(count), N, 1)
+    w = np.asarray(policy.weights, np.float64)                # after any device-side update: fetched when first read
+    W0 = w[..., _W0[0]:_W0[1]].reshape(w.shape[:-1] + (HIDDEN, 22))
+    return GainTable(total, count, e, W0, ids if bank else None)
