@@ -922,6 +922,49 @@ RQ_API int rq_trajectory_policy_gain_table(rq_trajectory* t, rq_policy* policy, 
 RQ_API int rq_trajectory_policies_gain_table(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const uint32_t* age_edges,
                                              uint32_t n_buckets, int start, float* sum, uint32_t* count, uint32_t ld_out, int memory);
 
+/* ---- Flight table: deviation, tilt and effort per env and episode age, read off a recording - how far a quadrotor was thrown, how
+ * long it took to come back, how hard the motors worked and whether the commands hit their limits.  No policy takes part: the call
+ * reads the recording alone, one pass that stores nothing of it.  With x the recorded observation of a step (x[0..2] the position
+ * relative to the setpoint - under a moving setpoint too -, x[11] = R22 the cosine of the tilt, x[12..14] the linear and x[15..17]
+ * the angular velocity, x[18..21] the previous action), a[0..3] the recorded action and r the recorded reward.
+ * AGE: age = start_steps[i] at the first recorded step (host uint32 [n_envs], what rq_env_get_episode_steps returned right before
+ * the rollout that recorded step 0; NULL: 0).  A step is live when its done code is not 4; after a live step with code 1 or 2 the age
+ * is 0, after any other live step one more; a frozen step changes nothing and contributes nothing.  This is the row index of a
+ * wrench schedule or a moving setpoint: a bucket of age is "time since the poke".  age_edges: host array [n_buckets + 1], strictly
+ * ascending, 1 <= n_buckets <= 32; a live step of age k belongs to bucket b when age_edges[b] <= k < age_edges[b + 1], a live step
+ * outside every bucket is counted nowhere.  start_steps and age_edges are host arrays in every mode and are read before return.
+ * Per counted step, in fp32, every operation rounded once and none fused, sq3(p, q, s) = (p p + q q) + s s:
+ *     RQ_FLIGHT_POS2       sq3(x0, x1, x2)
+ *     RQ_FLIGHT_VEL2       sq3(x12, x13, x14)
+ *     RQ_FLIGHT_OMEGA2     sq3(x15, x16, x17)
+ *     RQ_FLIGHT_TILT       1.0f - x11
+ *     RQ_FLIGHT_ACT2       sq3(a0, a1, a2) + a3 a3
+ *     RQ_FLIGHT_DACT2      sq3(d0, d1, d2) + d3 d3,  d_k = a_k - x[18 + k]  (the change of command)
+ *     RQ_FLIGHT_SATURATED  the number of k with |a_k| >= 1.0f, as a float (the env clips there)
+ *     RQ_FLIGHT_OUTSIDE    1.0f where POS2 > tol2, else 0.0f;  tol2 = (float)tolerance * (float)tolerance, one fp32 product
+ *     RQ_FLIGHT_REWARD     r
+ * sum [n_buckets][RQ_FLIGHT_SUMS][ld_out]: cell (b, c, i) = the sequential fp32 sum s = s + v, in time order from 0.0f, of column c
+ * over the steps of env i in bucket b (an env that returns to a bucket in a later episode goes on from its total).
+ * peak [n_buckets][RQ_FLIGHT_PEAKS][ld_out]: the largest POS2, TILT and OMEGA2 of those steps, each from 0.0f by
+ * p = v > p ? v : p, so a NaN never replaces a peak.  count [n_buckets][ld_out]: the number of those steps.
+ * ld_out >= n_envs; every cell with column below n_envs is written, columns at or beyond n_envs are left as they were.  A frozen
+ * step, a step outside the buckets and a padding column are selected away before any arithmetic: NaN there reaches no cell.  NaN
+ * in a live, counted step goes into the cells of its own env and nowhere else.  One lane walks one env: no atomics, the same bits
+ * every run.
+ * memory speaks of sum, peak and count: RQ_DST_HOST = host arrays (synchronous); RQ_DST_DEVICE / RQ_DST_DEVICE_ASYNC = device memory
+ * of the trajectory's device (synchronised before return / only enqueued on rq_device_stream()).
+ * Refused before anything is enqueued, outputs untouched: a null trajectory, age_edges, sum, peak or count; an empty trajectory;
+ * ld_out < n_envs; n_buckets outside 1 .. 32; edges that do not ascend strictly; a tolerance that is negative or not finite; an
+ * unknown memory; sum, peak or count that is not device memory of the trajectory's device when one is announced. */
+enum { RQ_FLIGHT_POS2, RQ_FLIGHT_VEL2, RQ_FLIGHT_OMEGA2, RQ_FLIGHT_TILT, RQ_FLIGHT_ACT2, RQ_FLIGHT_DACT2,
+       RQ_FLIGHT_SATURATED, RQ_FLIGHT_OUTSIDE, RQ_FLIGHT_REWARD, RQ_FLIGHT_SUMS };      /* 9 */
+enum { RQ_FLIGHT_PEAK_POS2, RQ_FLIGHT_PEAK_TILT, RQ_FLIGHT_PEAK_OMEGA2, RQ_FLIGHT_PEAKS }; /* 3 */
+RQ_API int rq_trajectory_flight_table(rq_trajectory* t, const uint32_t* start_steps /* host [n_envs] or NULL = 0 */,
+                                      float tolerance, const uint32_t* age_edges, uint32_t n_buckets,
+                                      float* sum   /* [n_buckets][RQ_FLIGHT_SUMS][ld_out]  */,
+                                      float* peak  /* [n_buckets][RQ_FLIGHT_PEAKS][ld_out] */,
+                                      uint32_t* count /* [n_buckets][ld_out] */, uint32_t ld_out, int memory);
+
 
 /* ---- Multi-GPU: the path's one exchange ---------------------------------------------
  * Envs are independent, so a batch shards over GPUs with no data-path collective: one process per GPU, rank r

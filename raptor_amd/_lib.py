@@ -190,6 +190,7 @@ _SIGNATURES = {
     "rq_trajectory_probe_moments": [_vp, _vp, _fp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_int],
     "rq_trajectory_probe_moments_timed": [_vp, _vp, _fp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_int],
     "rq_trajectory_wrench_targets": [_vp, _vp, _vp, _vp, _vp, C.c_int, _fp, C.c_uint32, C.c_int],
+    "rq_trajectory_flight_table": [_vp, _vp, C.c_float, _vp, C.c_uint32, _fp, _fp, _vp, C.c_uint32, C.c_int],
     "rq_comm_unique_id": [_vp, C.c_size_t],
     "rq_comm_create": [_vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.POINTER(_vp)],
     "rq_comm_destroy": [_vp],

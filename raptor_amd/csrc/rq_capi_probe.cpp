@@ -2,7 +2,8 @@
 // learner layout (rq_trajectory_get_hidden) and the second moments of [1, h_t, y] per bucket of episode age
 // (rq_trajectory_probe_moments; rq_trajectory_probe_moments_timed with targets per step); the 17 x 17 solve per bucket that follows
 // is the caller's, in float64 (raptor_amd/probing.py).  rq_trajectory_wrench_targets rebuilds such targets on the device: the
-// scheduled wrench every env was flown with at every recorded step.
+// scheduled wrench every env was flown with at every recorded step.  rq_trajectory_flight_table reads the recording alone - no
+// policy, no saved state: deviation, tilt, rates, effort and reward per env and bucket of episode age.
 // The first three read the saved state of a forward by this policy from the learned initial state at its current weights: the one a
 // learner call left, or the state-only forward run here (grad_saved_initial, rq_capi_grad.cpp).  Like the learner's calls each goes
 // through one rq::CallMemory (rq_call_memory.hpp): refusals, DeviceScope, prepare, in, launch, out, finish.  Kernels: rq_probe.hip.
@@ -172,6 +173,76 @@ RQ_API int rq_trajectory_wrench_targets(rq_trajectory* t, const rq_wrench_bank* 
     const bool scale = units_out == RQ_WRENCH_ABSOLUTE && bank->units == RQ_WRENCH_RELATIVE;
     RQ_HIP(rq::launch_probe_wrench_targets(dev->stream, n, env->ld, t->length, t->done, bank->d, bank->rows, g.probe_rows,
                                            g.probe_rows.get() + n, scale, params->d, env->cfg.gravity, d_out, d_ld));
+    RQ_HIP(mem.finish());
+    return RQ_OK;
+}
+
+RQ_API int rq_trajectory_flight_table(rq_trajectory* t, const uint32_t* start_steps, float tolerance, const uint32_t* age_edges,
+                                      uint32_t n_buckets, float* sum, float* peak, uint32_t* count, uint32_t ld_out, int memory) {
+    const char* what = __func__;
+    RQ_REQUIRE(t, RQ_ERR_INVALID_ARGUMENT, "null argument: trajectory");
+    RQ_REQUIRE(age_edges, RQ_ERR_INVALID_ARGUMENT, "null argument: age_edges");
+    RQ_REQUIRE(sum, RQ_ERR_INVALID_ARGUMENT, "null argument: sum");
+    RQ_REQUIRE(peak, RQ_ERR_INVALID_ARGUMENT, "null argument: peak");
+    RQ_REQUIRE(count, RQ_ERR_INVALID_ARGUMENT, "null argument: count");
+    int rc = check_memory(memory); if (rc) return rc;
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    const uint32_t n = env->n, B = n_buckets;
+    RQ_REQUIRE(t->length > 0, RQ_ERR_INVALID_ARGUMENT, "the trajectory is empty");
+    RQ_REQUIRE(ld_out >= n, RQ_ERR_INVALID_ARGUMENT, "ld_out must be at least the number of envs");
+    RQ_REQUIRE(B >= 1 && B <= rq::kFlightMaxBuckets, RQ_ERR_INVALID_ARGUMENT, "n_buckets must be 1 .. 32, not " + std::to_string(B));
+    rq::FlightTableLaunch a;
+    for (uint32_t b = 0; b <= B; ++b) {
+        RQ_REQUIRE(b == 0 || age_edges[b] > age_edges[b - 1], RQ_ERR_INVALID_ARGUMENT,
+                   "age_edges must ascend strictly (age_edges[" + std::to_string(b) + "] does not)");
+        a.edges[b] = age_edges[b];
+    }
+    a.n_buckets = B;
+    RQ_REQUIRE(std::isfinite(tolerance) && tolerance >= 0.0f, RQ_ERR_INVALID_ARGUMENT, "tolerance must be finite and not negative");
+    a.tol2 = tolerance * tolerance;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    rc = check_device_array(mem, sum, what, "sum"); if (rc) return rc;
+    rc = check_device_array(mem, peak, what, "peak"); if (rc) return rc;
+    rc = check_device_array(mem, count, what, "count"); if (rc) return rc;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+
+    // the start steps go through the trajectory's pinned block and are uploaded only when they differ from the call before
+    rq_trajectory::Grad& g = t->grad;
+    if (start_steps) {
+        if (g.flight_start_host.count() < (size_t)n) {
+            if (!g.flight_start_host.empty()) RQ_HIP(hipStreamSynchronize(dev->stream));      // a copy may still read the old block
+            g.flight_start_host.reset();
+            g.flight_start_valid = false;
+            RQ_HIP(g.flight_start_host.alloc(n));
+        }
+        RQ_HIP(g.flight_start.reserve(dev->stream, n));
+        uint32_t* host = g.flight_start_host;
+        bool same = g.flight_start_valid;
+        for (uint32_t i = 0; same && i < n; ++i) same = host[i] == start_steps[i];
+        if (!same) {
+            if (g.flight_start_valid) RQ_HIP(hipStreamSynchronize(dev->stream));
+            g.flight_start_valid = false;
+            for (uint32_t i = 0; i < n; ++i) host[i] = start_steps[i];
+            RQ_HIP(hipMemcpyAsync(g.flight_start, host, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, dev->stream));
+            g.flight_start_valid = true;
+        }
+        a.start = g.flight_start;
+    }
+    // a host-memory call: packed sum [B][9][n] | peak [B][3][n] | count [B][n] on the device, only the envs' columns go back
+    const size_t sums = (size_t)B * RQ_FLIGHT_SUMS * n, peaks = (size_t)B * RQ_FLIGHT_PEAKS * n, counts = (size_t)B * n;
+    float* s_sum = nullptr;
+    if (mem.host()) {
+        RQ_HIP(g.rows.reserve(dev->stream, sums + peaks + counts));
+        s_sum = g.rows.get();
+    }
+    a.n = n; a.ld = env->ld; a.steps = t->length;
+    a.obs = t->obs; a.act = t->act; a.rew = t->rew; a.done = t->done;
+    a.sum = mem.out(sum, ld_out, s_sum, n, n, (size_t)B * RQ_FLIGHT_SUMS);
+    a.peak = mem.out(peak, ld_out, s_sum ? s_sum + sums : nullptr, n, n, (size_t)B * RQ_FLIGHT_PEAKS);
+    a.count = mem.out(count, ld_out, s_sum ? reinterpret_cast<uint32_t*>(s_sum + sums + peaks) : nullptr, n, n, (size_t)B);
+    a.ld_out = mem.host() ? n : ld_out;
+    RQ_HIP(rq::launch_trajectory_flight_table(dev->stream, a));
     RQ_HIP(mem.finish());
     return RQ_OK;
 }

@@ -287,6 +287,11 @@ struct rq_trajectory {
         DeviceBuffer<uint32_t> probe_rows;
         PinnedBuffer<uint32_t> probe_rows_host;
         bool probe_rows_valid = false;
+        // rq_trajectory_flight_table: the start steps [n] on the device and the pinned block they were copied from, kept as the
+        // wrench targets keep theirs - the starts of the call before upload nothing
+        DeviceBuffer<uint32_t> flight_start;
+        PinnedBuffer<uint32_t> flight_start_host;
+        bool flight_start_valid = false;
     } grad;
 };
 

@@ -7,6 +7,8 @@
 //   k_probe_hidden_rows   saved [T][16][ld] -> [T][n][16], the learner layout (rq_trajectory_get_hidden)
 //   k_probe_moments_timed   k_probe_moments with targets per step, y [T][M][ld_y]              HBM ((64 + 4 M) B/env-step read)
 //   k_probe_wrench_targets  a lane per env, t = 0 .. T-1: the scheduled wrench row the env flew  HBM (24 B/env-step written)
+//   k_trajectory_flight_table   a lane per env, t = 0 .. T-1: deviation, tilt, rates, effort, reward per age bucket - nine sums,
+//                               three peaks, a count (rq_flight_table.inc; reads no saved state)  HBM (77 B/env-step read)
 // k_probe_moments and k_probe_moments_timed are one text (rq_probe_moments.inc under RQ_PROBE_TIMED), compiled once per kernel.
 //
 // Layout.  Lane l of a wave IS env 64 w + l: it loads its 16 state rows (16 coalesced 256-byte reads per step), keeps its age and
@@ -143,6 +145,15 @@ __global__ __launch_bounds__(256) void k_probe_wrench_targets(uint32_t n, uint32
     }
 }
 
+// The flight table (rq_flight_table.inc): the loads of the next step ahead of the arithmetic, workgroups of four waves - what
+// tools/flight_table_sweep.hip measured (profiles/flight_table_sweep.txt: one step ahead is worth 18 % at 10 buckets, a second or a
+// third nothing; four waves a workgroup 4 - 7 % over one).
+#define RQ_FLIGHT_KERNEL k_trajectory_flight_table
+#define RQ_FLIGHT_DEPTH 1
+#define RQ_FLIGHT_BLOCK 256
+#include "rq_flight_table.inc"
+constexpr uint32_t kFlightBlock = 256;
+
 }  // namespace
 
 hipError_t launch_probe_moments(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, const uint8_t* done,
@@ -170,6 +181,15 @@ hipError_t launch_probe_wrench_targets(hipStream_t s, uint32_t n, uint32_t ld, u
     if (n == 0 || steps == 0 || rows == 0 || ld < n || ld_out < n) return hipErrorInvalidValue;
     k_probe_wrench_targets<<<(n + 255) / 256, 256, 0, s>>>(n, ld, steps, done, tab, rows, row0, start, scale ? 1u : 0u, params, gravity,
                                                            out, ld_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_trajectory_flight_table(hipStream_t s, const FlightTableLaunch& a) {
+    if (flight_launch_refusal(a)) return hipErrorInvalidValue;      // a lane would touch memory beside its column
+    ProbeEdges edges{};
+    for (uint32_t b = 0; b <= a.n_buckets; ++b) edges.v[b] = a.edges[b];
+    k_trajectory_flight_table<<<(a.n + kFlightBlock - 1) / kFlightBlock, kFlightBlock, 0, s>>>(
+        a.n, a.ld, a.steps, a.obs, a.act, a.rew, a.done, a.start, a.tol2, edges, a.n_buckets, a.sum, a.peak, a.count, a.ld_out);
     return hipGetLastError();
 }
 

@@ -1,9 +1,11 @@
 // rq_probe.hpp - what the host layer (rq_capi_probe.cpp) needs of rq_probe.hip: the second moments of z = [1, h_t, y] over the
-// saved state of a recording, split by episode age.
+// saved state of a recording, split by episode age; and the flight table, which reads the recording alone (rq_flight_launch.hpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "rq_flight_launch.hpp"
 
 namespace rq {
 
@@ -33,6 +35,11 @@ hipError_t launch_probe_moments(hipStream_t s, uint32_t n, uint32_t ld, uint32_t
 hipError_t launch_probe_wrench_targets(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const uint8_t* done, const float* tab,
                                        uint32_t rows, const uint32_t* row0, const uint32_t* start, bool scale, const float* params,
                                        float gravity, float* out, uint32_t ld_out);
+
+// One pass over the recording, a lane per env: sum / peak / count per bucket of episode age (FlightTableLaunch).  A description that
+// would let a lane touch memory beside its column - ld_out < n, ld < n, n_buckets outside 1 .. 32, edges that do not ascend strictly,
+// a null pointer (`start` may be null) - is refused with hipErrorInvalidValue and nothing is launched.  Deterministic: no atomics.
+hipError_t launch_trajectory_flight_table(hipStream_t s, const FlightTableLaunch& a);
 
 // saved [steps][16][ld] -> out [steps][n][16], the learner layout
 hipError_t launch_probe_hidden_rows(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* saved, float* out);

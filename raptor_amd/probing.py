@@ -27,6 +27,13 @@ rq_trajectory_policy_gain_table): the local Jacobian da/dobs [4, 22] at every li
     g = gains.by_age()                                # [B, 4, 22]: how the control law settles over an episode's first steps
     kp = probing.GainTable.block(g, "position")       # [B, 4, 3]: the position gain
 
+How the vehicles FLEW needs no policy at all (``flight_table``, rq_trajectory_flight_table): deviation from the setpoint, tilt, rates,
+effort, saturation and reward per env and age bucket, with the age counted from ``start_steps`` - the row of a wrench schedule or a
+moving setpoint, so a bucket of age is "time since the poke".
+
+    table = probing.flight_table(traj, edges=probing.linear_age_edges(90, 250, 32), start_steps=start, tolerance=0.05)
+    curves = table.by_group(wrench_ids, M)            # dict of [M, B]: a step response per scenario
+
 Age follows the forward's episode rule: 0 at the first recorded step; a step is live when its done code is not 4; after a live
 step with code 1 or 2 the age is 0 again, after any other live step one more; frozen steps neither count nor age.
 """
@@ -474,3 +481,193 @@ def feedback_gains(traj, policy, edges=None, start="initial", policy_ids=None):
     w = np.asarray(policy.weights, np.float64)                # after any device-side update: fetched when first read
     W0 = w[..., _W0[0]:_W0[1]].reshape(w.shape[:-1] + (HIDDEN, 22))
     return GainTable(total, count, e, W0, ids if bank else None)
+
+
+# ---------------------------------------------------------------------------- the flight table ---
+# the columns of ``FlightTable.sum`` and ``FlightTable.peak``, in the order of the header's enums (RQ_FLIGHT_*, RQ_FLIGHT_PEAK_*)
+FLIGHT_SUMS = ["pos2", "vel2", "omega2", "tilt", "act2", "dact2", "saturated", "outside", "reward"]
+FLIGHT_PEAKS = ["pos2", "tilt", "omega2"]
+
+
+def linear_age_edges(lo, hi, n):
+    """n equal buckets of episode age over [lo, hi) -> uint32 [n + 1]; the width is (hi - lo) // n, at least 1, and the last edge
+    is lo + n * width <= hi.  Around the onset of a poke: ``linear_age_edges(onset - 10, onset + 150, 32)``."""
+    lo, hi, n = int(lo), int(hi), int(n)
+    if not 1 <= n <= MAX_BUCKETS:
+        raise ValueError(f"1 .. {MAX_BUCKETS} buckets, not {n}")
+    if lo < 0 or hi >= 1 << 32 or hi <= lo:
+        raise ValueError(f"[{lo}, {hi}) is no range of uint32 ages")
+    width = (hi - lo) // n
+    if width == 0:
+        raise ValueError(f"{n} buckets over [{lo}, {hi}) would have width 0")
+    return np.asarray([lo + k * width for k in range(n + 1)], np.uint32)
+
+
+class FlightTable:
+    """What ``flight_table`` returns: ``sum`` [B, 9, N] float32 (columns ``FLIGHT_SUMS``) - per age bucket and env the sums over its
+    live steps of the squared deviation from the setpoint, the squared linear and angular velocity, the tilt 1 - R22, the squared
+    action, the squared change of action, the number of saturated commands, the steps outside the tolerance and the reward -,
+    ``peak`` [B, 3, N] float32 (columns ``FLIGHT_PEAKS``) - the largest squared deviation, tilt and squared rate -, ``count``
+    [B, N] - the number of those steps - and ``edges`` [B + 1] (uint32, NumPy).  The arrays are NumPy or torch tensors, as the call
+    made them; every method works in float64 on whatever they are and returns the same kind.  A mean over nothing is NaN."""
+
+    CURVES = ["rms_position", "mean_tilt", "rms_rate", "effort", "command_change", "share_saturated", "share_outside", "mean_reward"]
+
+    def __init__(self, sum, peak, count, edges):
+        self.sum, self.peak, self.count = sum, peak, count
+        self.edges = np.asarray(edges, np.uint32)
+        if len(sum.shape) != 3 or sum.shape[1] != len(FLIGHT_SUMS) or tuple(peak.shape) != (sum.shape[0], len(FLIGHT_PEAKS), sum.shape[2]) \
+                or tuple(count.shape) != (sum.shape[0], sum.shape[2]) or self.edges.shape != (sum.shape[0] + 1,):
+            raise ValueError("sum must be [B, 9, N], peak [B, 3, N], count [B, N] and edges [B + 1]")
+
+    def _torch(self):
+        return hasattr(self.sum, "data_ptr")
+
+    def _f64(self):
+        if self._torch():
+            import torch
+            return self.sum.to(torch.float64), self.count.to(torch.float64)
+        return np.asarray(self.sum, np.float64), np.asarray(self.count, np.float64)
+
+    @staticmethod
+    def _over(s, c):
+        """s / c where c > 0, NaN elsewhere"""
+        if hasattr(s, "data_ptr"):
+            import torch
+            return torch.where(c > 0, s / torch.clamp(c, min=1.0), torch.full_like(s, float("nan")))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(c > 0, s / np.maximum(c, 1.0), np.nan)
+
+    @staticmethod
+    def _column(name):
+        if name not in FLIGHT_SUMS:
+            raise ValueError(f"unknown column {name!r}; the columns: {FLIGHT_SUMS}")
+        return FLIGHT_SUMS.index(name)
+
+    def mean(self, name):
+        """-> [B, N]: the mean of column ``name`` (``FLIGHT_SUMS``) over the steps of env i at the ages of bucket b"""
+        s, c = self._f64()
+        return self._over(s[:, self._column(name)], c)
+
+    def rms_position(self):
+        """-> [B, N]: the root-mean-square distance from the setpoint"""
+        return self.mean("pos2") ** 0.5
+
+    @classmethod
+    def _curves(cls, s, c):
+        """s [..., 9] sums and c [...] counts in float64 -> the dict of curves [...]"""
+        m = {name: cls._over(s[..., k], c) for k, name in enumerate(FLIGHT_SUMS)}
+        return {"rms_position": m["pos2"] ** 0.5, "mean_tilt": m["tilt"], "rms_rate": m["omega2"] ** 0.5, "effort": m["act2"],
+                "command_change": m["dact2"], "share_saturated": m["saturated"] / 4.0, "share_outside": m["outside"],
+                "mean_reward": m["reward"]}
+
+    def by_age(self):
+        """-> a dict of [B] curves over all envs (``CURVES``): the step response of the fleet"""
+        s, c = self._f64()
+        return self._curves(s.sum(2), c.sum(1))
+
+    def _ids(self, ids, n_groups):
+        G, N = int(n_groups), int(self.sum.shape[2])
+        g = np.asarray(ids.cpu() if hasattr(ids, "data_ptr") else ids)
+        if g.shape != (N,) or g.dtype == bool or not np.issubdtype(g.dtype, np.integer) or (N and (g.min() < 0 or g.max() >= G)):
+            raise ValueError(f"ids must be [{N}] integers below {G}")
+        return g.astype(np.int64), G
+
+    def by_group(self, ids, n_groups):
+        """``ids`` [N] integers below ``n_groups`` - the wrench scenario, reference, teacher or policy of every env -> the dict of
+        ``by_age`` with [G, B] curves, each over its group's envs; a group without a counted step gives NaN."""
+        g, G = self._ids(ids, n_groups)
+        s, c = self._f64()
+        B = int(s.shape[0])
+        if self._torch():
+            import torch
+            at = torch.as_tensor(g, device=s.device)
+            gs = torch.zeros((G, B, len(FLIGHT_SUMS)), dtype=torch.float64, device=s.device).index_add(0, at, s.permute(2, 0, 1))
+            gc = torch.zeros((G, B), dtype=torch.float64, device=s.device).index_add(0, at, c.T)
+        else:
+            gs, gc = np.zeros((G, B, len(FLIGHT_SUMS))), np.zeros((G, B))
+            np.add.at(gs, g, s.transpose(2, 0, 1))
+            np.add.at(gc, g, c.T)
+        return self._curves(gs, gc)
+
+    def peak_by_group(self, ids, n_groups):
+        """-> [G, B, 3] (columns ``FLIGHT_PEAKS``): the maximum over a group's envs of the peaks; NaN where the group counted nothing"""
+        g, G = self._ids(ids, n_groups)
+        _, c = self._f64()
+        B = int(self.peak.shape[0])
+        if self._torch():
+            import torch
+            p = self.peak.to(torch.float64)
+            at = torch.as_tensor(g, device=p.device)
+            out = torch.zeros((G, B, len(FLIGHT_PEAKS)), dtype=torch.float64, device=p.device)
+            src = p.permute(2, 0, 1)
+            out = out.scatter_reduce(0, at[:, None, None].expand_as(src), src, "amax", include_self=True)
+            gc = torch.zeros((G, B), dtype=torch.float64, device=p.device).index_add(0, at, c.T)
+            return torch.where((gc > 0)[:, :, None], out, torch.full_like(out, float("nan")))
+        p = np.asarray(self.peak, np.float64)
+        out, gc = np.zeros((G, B, len(FLIGHT_PEAKS))), np.zeros((G, B))
+        np.maximum.at(out, g, p.transpose(2, 0, 1))
+        np.add.at(gc, g, c.T)
+        return np.where((gc > 0)[:, :, None], out, np.nan)
+
+    def per_env(self):
+        """-> the dict of ``by_age`` with [N] curves: every env over all buckets - with ``edges=None`` over the whole recording"""
+        s, c = self._f64()
+        return self._curves(s.sum(0).T, c.sum(0))
+
+    @staticmethod
+    def recovery(curve, onset_bucket, level):
+        """A host helper: the first bucket at or after ``onset_bucket`` from which ``curve`` [B] stays <= ``level`` to its end, or
+        -1 (a NaN is not below the level)."""
+        y = np.asarray(curve.cpu() if hasattr(curve, "data_ptr") else curve, np.float64)
+        if y.ndim != 1 or not 0 <= int(onset_bucket) < y.size:
+            raise ValueError("curve must be [B] and onset_bucket one of its buckets")
+        with np.errstate(invalid="ignore"):
+            ok = y <= float(level)
+        for b in range(int(onset_bucket), y.size):
+            if ok[b:].all():
+                return b
+        return -1
+
+
+def flight_table(traj, edges=None, start_steps=None, tolerance=0.05, device=None):
+    """The flight of every env of the recording, per bucket of episode age -> ``FlightTable``.  One pass on the device
+    (rq_trajectory_flight_table) that reads the recording alone - no policy - and stores nothing of it.
+
+    ``edges``: [B + 1] strictly ascending episode ages, B <= 32 (``linear_age_edges``, ``log_age_edges``); None: one bucket for
+    every age.  ``start_steps`` [N]: what ``env.episode_steps()`` returned right before the rollout that recorded step 0 (None: 0) -
+    the age is the row index of a wrench schedule or a moving setpoint, so a bucket of age is "time since the poke".
+    ``tolerance``: the distance from the setpoint beyond which a step counts as ``outside``.
+
+    ``device``: True - torch tensors on the trajectory's device; False - NumPy; None - tensors when torch is present.  The call
+    orders itself against torch's current stream as ``training.imitation_error`` does."""
+    from .training import Distiller, _age_edges, _device_ptr
+    e = _age_edges(edges)
+    N = int(traj._env.N_ENVIRONMENTS)
+    tol = float(tolerance)
+    if not np.isfinite(tol) or tol < 0:
+        raise ValueError("tolerance must be finite and not negative")
+    k = None
+    if start_steps is not None:
+        k = np.asarray(start_steps)
+        if k.shape != (N,) or k.dtype == bool or not np.issubdtype(k.dtype, np.integer) or (k < 0).any() or (k >= 1 << 32).any():
+            raise ValueError(f"start_steps must be {N} non-negative integers (env.episode_steps())")
+        k = np.ascontiguousarray(k.astype(np.uint32))
+    dev = None if device is False else Distiller._torch_device(traj)
+    if device and dev is None:
+        raise ValueError("device=True needs torch")
+    B, ka = e.size - 1, None if k is None else k.ctypes.data
+    if dev is None:
+        total, peak = np.empty((B, len(FLIGHT_SUMS), N), np.float32), np.empty((B, len(FLIGHT_PEAKS), N), np.float32)
+        count = np.empty((B, N), np.uint32)
+        _lib.call("rq_trajectory_flight_table", traj._require("trajectory"), ka, tol, e.ctypes.data, B, _lib.fptr(total), _lib.fptr(peak),
+                  count.ctypes.data, N, 0)
+        return FlightTable(total, peak, count, e)
+    import torch
+    total = torch.empty((B, len(FLIGHT_SUMS), N), dtype=torch.float32, device=dev)
+    peak = torch.empty((B, len(FLIGHT_PEAKS), N), dtype=torch.float32, device=dev)
+    count = torch.empty((B, N), dtype=torch.int32, device=dev)          # the engine's uint32; a recording has fewer than 2^31 steps
+    torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
+    _lib.call("rq_trajectory_flight_table", traj._require("trajectory"), ka, tol, e.ctypes.data, B, _device_ptr(total), _device_ptr(peak),
+              _device_ptr(count), N, 1)
+    return FlightTable(total, peak, count, e)
