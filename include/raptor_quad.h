@@ -90,7 +90,8 @@ extern "C" {
                               (still 5: rq_reference_bank_{create,destroy}, rq_rollout_track_refs and rq_rollout_policies_track_refs added,
                               no struct changed)
                               (still 5: rq_rollout_teachers_track and rq_rollout_teachers_track_refs added, no struct changed)
-                              (still 5: rq_wrench_bank_{create,destroy} and rq_env_{set,get}_wrench_schedule added, no struct changed) */
+                              (still 5: rq_wrench_bank_{create,destroy} and rq_env_{set,get}_wrench_schedule added, no struct changed)
+                              (still 5: rq_vehicle_bank_{create,destroy} and rq_env_{set,get}_vehicle_schedule added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -530,6 +531,47 @@ RQ_API int rq_env_set_wrench_schedule(rq_env* env, rq_wrench_bank* bank /* NULL 
                                       const uint32_t* wrench_id /* host [n_envs] or NULL = table 0 */);
 RQ_API int rq_env_get_wrench_schedule(const rq_env* env, rq_wrench_bank** bank /* NULL when none */,
                                       uint32_t* wrench_id_out /* host [n_envs] or NULL */);
+
+/* ---- Vehicle schedule: the vehicle itself changes in mid-episode (a payload picked up or dropped, battery sag, a damaged propeller
+ * set, slow motors).  A wrench schedule pushes on the vehicle; the mass, the inertia and the thrust the dynamics divide and multiply
+ * by stay those of the params.  A VEHICLE BANK is n_tables tables of one length, host_rows [n_tables][rows][4] float32 row-major,
+ * every entry a positive finite factor: column 0 the mass, 1 the inertia (all three axes), 2 the thrust curve (c0, c1, c2 alike),
+ * 3 the motor time constant (rise and fall alike).  A schedule is attached to an ENV: a bank plus one table id per env.  While it
+ * is attached EVERY transition of env i, in every call that steps (rq_step, the rollouts of a policy, a policy bank and a teacher
+ * bank, chained; fused as said below), is computed from the EFFECTIVE parameters
+ *     k    = the env's episode step count before the step, clamped to rows - 1   (the count the wrench schedule indexes with)
+ *     row  = table[vehicle_id[i]][k]
+ *     mass' = mass * row[0]
+ *     Jxx' = Jxx * row[1]     Jyy' = Jyy * row[1]     Jzz' = Jzz * row[1]
+ *     c0'  = c0 * row[2]      c1'  = c1 * row[2]      c2'  = c2 * row[2]
+ *     tau_rise' = tau_rise * row[3]                   tau_fall' = tau_fall * row[3]
+ *     every other field (rotor positions, torque constant, rpm range, hover rpm, hover action): the base value
+ * every * one correctly rounded fp32 multiplication, nothing contracted.  The transition is the existing one on those 26 fields -
+ * the per-env constants, reciprocals included, are made from the effective fields; the dynamics, reward, termination and counters
+ * are unchanged: bit for bit what a caller gets who writes raptor_amd.vehicles.compose(P, row) with rq_params_set before every
+ * rq_step.  Hence: a row of four 1.0f gives the unscheduled bits (x * 1.0f is x); the params object is never written - the base
+ * values come from the params passed to the call, rq_params_set after attaching is honoured; a new episode's state is sampled from
+ * the BASE parameters (mass, hover rpm); the reward's action baseline stays the base hover action; with a wrench schedule in
+ * relative units attached as well the wrench scales use the step's effective mass (m g = mass' * gravity); a frozen env reads
+ * nothing; rq_env_reset_statistics zeroes the step count and so restarts the table; whether an env's rotors rise and fall alike
+ * is decided from tau_rise == tau_fall of the base fields (equal inputs times one factor are equal, and so are their reciprocals).
+ * rq_vehicle_bank_create refuses a null argument, n_tables == 0, rows == 0, a factor that is not finite or not > 0 (the message names
+ * table, row and column) and n_tables * rows >= 2^28, all before the device is looked at.  rq_env_set_vehicle_schedule (bank NULL:
+ * detach; vehicle_id NULL: table 0 for every env) refuses a bank of another rq_device (RQ_ERR_SHAPE_MISMATCH) and an id >= n_tables
+ * (the message names the env).  rq_vehicle_bank_destroy is refused while the bank is attached to a live env; rq_env_destroy
+ * detaches.  Every call that steps refuses, before anything is enqueued (state, rng epoch, statistics and recording untouched), a
+ * bank with rows < episode_step_limit.  In fused mode a schedule is flown by the fp32 policy and policy-bank kernels
+ * (k_rollout_fused_vehicle); a bf16 / f16x2 policy, a SampleAndSquash stage, rq_rollout_teachers* and an env that carries a wrench
+ * schedule too are refused in fused mode while a vehicle schedule is attached (nothing runs chained in their place) - all four run
+ * chained.  The small-batch loop steps such an env with plain launches (no resident executor, no speculative policy step). */
+typedef struct rq_vehicle_bank rq_vehicle_bank;
+RQ_API int rq_vehicle_bank_create(rq_device* dev, const float* host_rows /* [n_tables][rows][4] */, uint32_t n_tables, uint32_t rows,
+                                  rq_vehicle_bank** out);
+RQ_API int rq_vehicle_bank_destroy(rq_vehicle_bank* bank);
+RQ_API int rq_env_set_vehicle_schedule(rq_env* env, rq_vehicle_bank* bank /* NULL detaches */,
+                                       const uint32_t* vehicle_id /* host [n_envs] or NULL = table 0 */);
+RQ_API int rq_env_get_vehicle_schedule(const rq_env* env, rq_vehicle_bank** bank /* NULL when none */,
+                                       uint32_t* vehicle_id_out /* host [n_envs] or NULL */);
 
 /* ---- Learner: the student's gradient over a recorded trajectory (README.md:208-216, the distillation step's regression) ----
  * Forward: the policy on the recorded observations obs [T][22][ld] under rq_trajectory_relabel's episode rules (GRU state back to

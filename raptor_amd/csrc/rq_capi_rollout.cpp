@@ -35,7 +35,29 @@ int rollout_check(RolloutFrame& f, const RolloutCall& c, bool actor) {
                   "trajectory buffer too small for this rollout");
         f.tp = {traj->obs, traj->act, traj->rew, traj->done, traj->length};
     }
-    return env_wrench("rollout", c.env, &f.wr);
+    rc = env_wrench("rollout", c.env, &f.wr); if (rc) return rc;
+    rc = env_vehicle("rollout", c.env, &f.vh); if (rc) return rc;
+    // a vehicle schedule is flown fused by the fp32 builds alone and without a wrench schedule beside it; nothing runs chained in
+    // its place (the actors refuse what is theirs: a 16-bit policy, a SampleAndSquash stage, a teacher bank)
+    if (f.vh.rows && f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return vehicle_refuses_fused(c.who, "an env that carries a wrench schedule too");
+    return RQ_OK;
+}
+
+int env_vehicle(const char* who, const rq_env* env, rq::VehiclePtrs* vh) {
+    *vh = rq::VehiclePtrs{};
+    const rq_vehicle_bank* bank = env->vehicle;
+    if (!bank) return RQ_OK;
+    if (bank->rows < env->cfg.episode_step_limit)
+        return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env's vehicle schedule has fewer rows (" + std::to_string(bank->rows) +
+                                                 ") than episode_step_limit (" + std::to_string(env->cfg.episode_step_limit) +
+                                                 "): every table must cover an episode");
+    *vh = {bank->d, env->vehicle_row0, bank->rows, 0u};
+    return RQ_OK;
+}
+
+int vehicle_refuses_fused(const char* who, const char* what) {
+    return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env carries a vehicle schedule, which the fused kernel of " + what +
+                                             " is not taught: fly it with mode RQ_ROLLOUT_CHAINED (\"chained\"), or detach the schedule");
 }
 
 int env_wrench(const char* who, const rq_env* env, rq::WrenchPtrs* wr) {
@@ -137,14 +159,14 @@ rq::FusedArgs fused_args(const RolloutCall& c, const RolloutFrame& f) {
     a.seed = c.rng->seed; a.epoch0 = c.rng->epoch; a.n_steps = c.n_steps;
     a.autoreset = (c.flags & RQ_ROLLOUT_AUTORESET) != 0;
     a.params = c.params->d; a.state = c.state->d; a.st = c.env->st;
-    a.traj = f.tp; a.trk = f.trk; a.wr = f.wr;
+    a.traj = f.tp; a.trk = f.trk; a.wr = f.wr; a.vh = f.vh;
     return a;
 }
 
 rq::EnvStepLaunch env_step_launch(const RolloutCall& c, const RolloutFrame& f) {
     rq::EnvStepLaunch e;
     e.b = f.b; e.c = f.sc; e.params = c.params->d; e.state = c.state->d; e.action = c.env->act; e.next_state = c.state->d; e.st = c.env->st;
-    e.rollout = true; e.flags = c.flags; e.sc = f.smp; e.seed = c.rng->seed; e.wr = f.wr;
+    e.rollout = true; e.flags = c.flags; e.sc = f.smp; e.seed = c.rng->seed; e.wr = f.wr; e.vh = f.vh;
     return e;
 }
 
@@ -184,6 +206,10 @@ struct PolicyActor {
         if (f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) {        // a schedule is flown fused by the fp32 builds alone; nothing runs chained in its place
             if (policy->precision != RQ_POLICY_FP32) return wrench_refuses_fused(c.who, "a bf16 / f16x2 policy");
             if (policy->sas_mode != RQ_SAS_OFF) return wrench_refuses_fused(c.who, "a policy with a SampleAndSquash stage");
+        }
+        if (f.vh.rows && c.mode == RQ_ROLLOUT_FUSED) {        // likewise a vehicle schedule
+            if (policy->precision != RQ_POLICY_FP32) return vehicle_refuses_fused(c.who, "a bf16 / f16x2 policy");
+            if (policy->sas_mode != RQ_SAS_OFF) return vehicle_refuses_fused(c.who, "a policy with a SampleAndSquash stage");
         }
         return RQ_OK;
     }
@@ -227,16 +253,17 @@ struct PolicyActor {
         key.seed = c.rng->seed; key.sas_mode = policy->sas_mode; key.sas_seed = policy->sas_seed; key.ls_image = policy->ls_image;
         key.ref = f.trk.ref; key.ref_rows = f.trk.rows; key.row0_at = f.trk.row0_at;
         key.row0_gen = f.row0_gen;      // (a reference bank: which ids the rows were built from)
-        key.interval = policy->native_interval; key.wrench_gen = c.env->wrench_gen;
+        key.interval = policy->native_interval; key.wrench_gen = c.env->wrench_gen; key.vehicle_gen = c.env->vehicle_gen;
         return key;
     }
 };
 
 // The tables of rq_reference_create (`single`: one table, named without a bank's words), rq_reference_bank_create and
 // rq_wrench_bank_create: refused before the device is looked at, then allocated and uploaded.  T: the handle's type.
+// `cols`: 6, or a vehicle bank's 4 positive factors (`positive`: an entry that is not > 0 is refused too, naming its column).
 template <typename T>
 int row_tables_create(const char* who, const char* noun, bool single, rq_device* dev, const float* host_rows, uint32_t n_tables,
-                      uint32_t rows, T** out) {
+                      uint32_t rows, T** out, uint32_t cols = 6, bool positive = false) {
     RQ_REFUSE(who, dev && host_rows && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     if (single) RQ_REFUSE(who, rows > 0, RQ_ERR_INVALID_ARGUMENT, "a reference needs at least one row");
@@ -244,11 +271,16 @@ int row_tables_create(const char* who, const char* noun, bool single, rq_device*
     // the row an env reads, first row of its table + episode step count, is a uint32 on the device
     RQ_REFUSE(who, single || (uint64_t)n_tables * rows < (1ull << 28), RQ_ERR_INVALID_ARGUMENT,
               std::string("a ") + noun + " holds fewer than 2^28 rows in all");
-    const size_t floats = (size_t)n_tables * rows * 6;
-    for (size_t j = 0; j < floats; ++j)
+    const size_t floats = (size_t)n_tables * rows * cols;
+    for (size_t j = 0; j < floats; ++j) {
         RQ_REFUSE(who, std::isfinite(host_rows[j]), RQ_ERR_INVALID_ARGUMENT,
                   std::string(noun) + " holds a non-finite entry" +
-                      (single ? "" : ": table " + std::to_string(j / ((size_t)rows * 6)) + ", row " + std::to_string(j / 6 % rows)));
+                      (single ? "" : ": table " + std::to_string(j / ((size_t)rows * cols)) + ", row " + std::to_string(j / cols % rows)) +
+                      (positive ? ", column " + std::to_string(j % cols) : ""));
+        RQ_REFUSE(who, !positive || host_rows[j] > 0.0f, RQ_ERR_INVALID_ARGUMENT,
+                  std::string(noun) + " holds a factor that is not > 0: table " + std::to_string(j / ((size_t)rows * cols)) + ", row " +
+                      std::to_string(j / cols % rows) + ", column " + std::to_string(j % cols));
+    }
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     T* r = new (std::nothrow) T();
     RQ_REFUSE(who, r, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -376,6 +408,61 @@ RQ_API int rq_env_get_wrench_schedule(const rq_env* env, rq_wrench_bank** bank, 
     RQ_REQUIRE(env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
     *bank = env->wrench;
     if (env->wrench && wrench_id_out) std::memcpy(wrench_id_out, env->wrench_ids.data(), (size_t)env->n * sizeof(uint32_t));
+    return RQ_OK;
+}
+
+// ---------------------------------------------------------------------------- Vehicle schedule
+RQ_API int rq_vehicle_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, rq_vehicle_bank** out) {
+    return row_tables_create(__func__, "vehicle bank", false, dev, host_rows, n_tables, rows, out, 4, true);
+}
+
+RQ_API int rq_vehicle_bank_destroy(rq_vehicle_bank* bank) {
+    RQ_REQUIRE(!bank || bank->attached == 0, RQ_ERR_INVALID_ARGUMENT,
+               "the vehicle bank is attached to " + std::to_string(bank->attached) +
+                   " live env(s): detach it (rq_env_set_vehicle_schedule with a NULL bank) or destroy the env first");
+    return row_tables_destroy(bank);
+}
+
+RQ_API int rq_env_set_vehicle_schedule(rq_env* env, rq_vehicle_bank* bank, const uint32_t* vehicle_id) {
+    RQ_REQUIRE(env, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    rq_device* dev = env->dev;
+    if (bank) {
+        RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "vehicle bank lives on another device");
+        if (vehicle_id)
+            for (uint32_t i = 0; i < env->n; ++i)
+                RQ_REQUIRE(vehicle_id[i] < bank->n_tables, RQ_ERR_INVALID_ARGUMENT,
+                           "vehicle id out of range: env " + std::to_string(i) + " names table " + std::to_string(vehicle_id[i]) +
+                               " of a bank of " + std::to_string(bank->n_tables));
+    }
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;      // (retires a running resident executor)
+    RQ_HIP(hipStreamSynchronize(dev->stream));                // a launch in flight reads the rows of the schedule before
+    obs_cache_drop_if(dev, env);
+    if (!bank) {
+        if (env->vehicle) env->vehicle->attached -= 1;
+        env->vehicle = nullptr; env->vehicle_gen = 0; env->vehicle_ids.clear();
+        return RQ_OK;
+    }
+    std::vector<uint32_t> ids;
+    try {                                   // nothing throws across the boundary
+        if (vehicle_id) ids.assign(vehicle_id, vehicle_id + env->n); else ids.assign(env->n, 0u);
+    } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "vehicle schedule: host allocation failed");
+    }
+    if (env->vehicle_row0.empty() && env->vehicle_row0.alloc(env->ld) != hipSuccess)
+        return fail(RQ_ERR_OUT_OF_MEMORY, "vehicle schedule: device allocation failed");
+    rc = upload_first_rows("vehicle schedule", dev, env, vehicle_id, bank->rows, env->vehicle_row0); if (rc) return rc;
+    if (env->vehicle) env->vehicle->attached -= 1;
+    bank->attached += 1;
+    env->vehicle = bank;
+    env->vehicle_ids.swap(ids);
+    env->vehicle_gen = fresh_version();
+    return RQ_OK;
+}
+
+RQ_API int rq_env_get_vehicle_schedule(const rq_env* env, rq_vehicle_bank** bank, uint32_t* vehicle_id_out) {
+    RQ_REQUIRE(env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *bank = env->vehicle;
+    if (env->vehicle && vehicle_id_out) std::memcpy(vehicle_id_out, env->vehicle_ids.data(), (size_t)env->n * sizeof(uint32_t));
     return RQ_OK;
 }
 

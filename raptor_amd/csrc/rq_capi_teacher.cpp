@@ -299,6 +299,7 @@ struct TeacherActor {
                   "the fused teacher rollout runs the fp32 two-hidden-layer {16, 32, 64} family: fly this bank (bf16 / f16x2 precision "
                   "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
         if (f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return wrench_refuses_fused(c.who, "a teacher bank");
+        if (f.vh.rows && c.mode == RQ_ROLLOUT_FUSED) return vehicle_refuses_fused(c.who, "a teacher bank");
         return check_ids(bank, teacher_id, c.env->n);
     }
     int prepare(const RolloutCall& c) {

@@ -430,6 +430,48 @@ __device__ __forceinline__ void wrench_compose(const float (&f)[6], float fs, fl
     for (int j = 0; j < 3; ++j) { w[j] = __fadd_rn(f[j], __fmul_rn(fs, r[j])); w[3 + j] = __fadd_rn(f[3 + j], __fmul_rn(ts, r[3 + j])); }
 }
 
+// ------------------------------------------------------------------ vehicle schedule ---
+// A vehicle schedule (rq_env_set_vehicle_schedule) computes every transition from the EFFECTIVE parameters: the base fields times
+// row k of the env's own table [rows][4] = factors on (mass, inertia, thrust curve, motor time constant), k = the env's episode step
+// count before the step (the count wrench_row and track_row index with), clamped to the table.  mass * r[0]; Jxx, Jyy, Jzz * r[1];
+// c0, c1, c2 * r[2]; tau_rise, tau_fall * r[3]; every other field the base value.  Every product is one rounded multiplication the
+// compiler may not contract (raptor_amd.vehicles.compose is the NumPy float32 restatement), and the per-env constants are made from
+// the effective fields the way make_consts makes them from the base ones: a row of ones gives make_consts' bits.  The functions
+// below are the only place any path does this arithmetic.
+// row0: the first row of the env's own table in the bank's flat [n_tables * rows][4] block (the host keeps n_tables * rows below
+// 2^28); one 16-byte load
+__device__ __forceinline__ void vehicle_row(const float* __restrict__ tab, uint32_t rows, uint32_t row0, uint32_t k, float (&r)[4]) {
+    const float4 v = *reinterpret_cast<const float4*>(tab + (size_t)(row0 + (k < rows ? k : rows - 1u)) * 4u);
+    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
+}
+// parameter field f of the effective vehicle, from its base value (f is a constant wherever this is called)
+__device__ __forceinline__ float vehicle_field(int f, float base, const float (&r)[4]) {
+    if (f == RQ_P_MASS) return __fmul_rn(base, r[0]);
+    if (f == RQ_P_JXX || f == RQ_P_JYY || f == RQ_P_JZZ) return __fmul_rn(base, r[1]);
+    if (f == RQ_P_THRUST_C0 || f == RQ_P_THRUST_C1 || f == RQ_P_THRUST_C2) return __fmul_rn(base, r[2]);
+    if (f == RQ_P_TAU_RISE || f == RQ_P_TAU_FALL) return __fmul_rn(base, r[3]);
+    return base;
+}
+// The nine base fields a schedule scales, kept by the fused kernel through its loop (the other builds let them die after make_consts),
+// and the members of EnvConsts made from them, rebuilt for one step: make_consts' expressions on the effective fields.
+struct VehicleBase { float mass, jx, jy, jz, c0, c1, c2, tau_rise, tau_fall; };
+template <typename F>
+__device__ __forceinline__ VehicleBase vehicle_base(F p) {
+    return {p(RQ_P_MASS), p(RQ_P_JXX), p(RQ_P_JYY), p(RQ_P_JZZ), p(RQ_P_THRUST_C0), p(RQ_P_THRUST_C1), p(RQ_P_THRUST_C2),
+            p(RQ_P_TAU_RISE), p(RQ_P_TAU_FALL)};
+}
+__device__ __forceinline__ void vehicle_consts(const VehicleBase& b, const float (&r)[4], EnvConsts& k) {
+    const float inv_m = 1.0f / __fmul_rn(b.mass, r[0]);
+    k.IM = f32x2{inv_m, inv_m + inv_m};
+    const float jx = __fmul_rn(b.jx, r[1]), jy = __fmul_rn(b.jy, r[1]);
+    k.J12 = f32x2{jx, jy};
+    k.IJ12 = f32x2{1.0f / jx, 1.0f / jy};
+    k.jz = __fmul_rn(b.jz, r[1]);
+    k.ijz = 1.0f / k.jz;
+    k.c0 = __fmul_rn(b.c0, r[2]); k.c1 = __fmul_rn(b.c1, r[2]); k.c2 = __fmul_rn(b.c2, r[2]);
+    k.itr = 1.0f / __fmul_rn(b.tau_rise, r[3]); k.itf = 1.0f / __fmul_rn(b.tau_fall, r[3]);
+}
+
 // ------------------------------------------------------------------ parameter sampling -
 
 __device__ __forceinline__ void sample_params(const SampleCfg& c, uint64_t seed, uint32_t epoch, uint64_t genv,

@@ -384,15 +384,24 @@ struct ObsNext {
 // WRENCH: the env carries a wrench schedule - the transition is computed with the state's per-episode wrench plus the row of the
 // env's episode step count (rq_device_math.hpp wrench_*); the next state keeps the base.  A compile-time switch: the kernels without
 // a schedule are compiled from what they were compiled from before it existed.
-template <bool ROLLOUT, bool WRENCH = false>
+// VEHICLE: the env carries a vehicle schedule - the per-env constants are made from the effective parameter fields, the base ones
+// times the row of the env's episode step count (rq_device_math.hpp vehicle_*); a new episode is sampled from the base fields, and a
+// relative wrench schedule beside it scales by the effective mass.  A compile-time switch like WRENCH.
+template <bool ROLLOUT, bool WRENCH = false, bool VEHICLE = false>
 __device__ __forceinline__ void step_env(uint32_t i, const Batch& b, const StepCfg& c, const float* __restrict__ params,
                                          const float* state, float* __restrict__ action, float* next_state,
                                          const StatsPtrs& st, uint32_t flags, const SampleCfg& sc, uint64_t seed,
                                          float* __restrict__ hidden, const float* __restrict__ weights,
-                                         const Mailbox& mb, const ObsNext& on, const WrenchPtrs& wr = WrenchPtrs{}) {
+                                         const Mailbox& mb, const ObsNext& on, const WrenchPtrs& wr = WrenchPtrs{},
+                                         const VehiclePtrs& vh = VehiclePtrs{}) {
     if (ROLLOUT && st.frozen[i]) { st.last_done[i] = 4; return; }
     const size_t ld = b.ld;
-    const EnvConsts k = make_consts([&](int f) { return field(params, f, ld)[i]; });
+    [[maybe_unused]] float vrow[4];
+    if constexpr (VEHICLE) vehicle_row(vh.rows, vh.n_rows, vh.row0[i], st.steps[i], vrow);      // (the count load_stats reads below)
+    const EnvConsts k = make_consts([&](int f) {
+        if constexpr (VEHICLE) return vehicle_field(f, field(params, f, ld)[i], vrow);
+        else return field(params, f, ld)[i];
+    });
     QuadState y;
     float f6[6], a[4];
     f32x2 AC01, AC23;
@@ -410,7 +419,9 @@ __device__ __forceinline__ void step_env(uint32_t i, const Batch& b, const StepC
     Disturbance ds;
     if constexpr (WRENCH) {
         float fs, ts, wrow[6], w6[6];
-        wrench_scales(wr.relative, field(params, RQ_P_MASS, ld)[i], c.gravity, field(params, RQ_P_ROTOR_POS, ld)[i],
+        float mass = field(params, RQ_P_MASS, ld)[i];
+        if constexpr (VEHICLE) mass = vehicle_field(RQ_P_MASS, mass, vrow);       // m g of the step's effective mass
+        wrench_scales(wr.relative, mass, c.gravity, field(params, RQ_P_ROTOR_POS, ld)[i],
                       field(params, (RQ_P_ROTOR_POS + 1), ld)[i], fs, ts);
         wrench_row(wr.rows, wr.n_rows, wr.row0[i], s.steps, wrow);
         wrench_compose(f6, fs, ts, wrow, w6);
@@ -496,6 +507,21 @@ __global__ __launch_bounds__(kBlock) void k_step_wrench(Batch b, StepCfg c, cons
     const uint32_t i = env_index();
     if (i < b.n)
         step_env<ROLLOUT, true>(i, b, c, params, state, action, next_state, st, flags, sc, seed, hidden, weights, mb, on, wr);
+    mailbox_signal(mb);
+}
+
+// k_step for an env that carries a vehicle schedule, with (WRENCH) or without a wrench schedule beside it (kernels of their own, as
+// k_step_wrench is: k_step's and k_step_wrench's argument blocks and listings stay what they were)
+template <bool ROLLOUT, bool WRENCH>
+__global__ __launch_bounds__(kBlock) void k_step_vehicle(Batch b, StepCfg c, const float* __restrict__ params,
+                                                         const float* state, float* __restrict__ action,
+                                                         float* next_state, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                         uint64_t seed, float* __restrict__ hidden,
+                                                         const float* __restrict__ weights, Mailbox mb, ObsNext on, WrenchPtrs wr,
+                                                         VehiclePtrs vh) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<ROLLOUT, WRENCH, true>(i, b, c, params, state, action, next_state, st, flags, sc, seed, hidden, weights, mb, on, wr, vh);
     mailbox_signal(mb);
 }
 // ------------------------------------------------------------------ resident executor ---
@@ -1043,14 +1069,36 @@ __global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const 
 __global__ __launch_bounds__(kBlock) void k_step_bank_wrench(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
                                    StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
                                    const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr);
+template <bool WRENCH>
+__global__ __launch_bounds__(kBlock) void k_step_bank_vehicle(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
+                                    StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
+                                    const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh);
+
+// the vehicle schedule's kernels, by the route's two bools
+static void launch_step_vehicle(hipStream_t s, const EnvStepLaunch& e, const EnvStepRoute& r, unsigned grid, const ObsNext& on) {
+    const auto kernel = r.rollout ? (r.wrench ? &k_step_vehicle<true, true> : &k_step_vehicle<true, false>)
+                                  : (r.wrench ? &k_step_vehicle<false, true> : &k_step_vehicle<false, false>);
+    RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed, e.hidden,
+               e.weights, e.mb, on, e.wr, e.vh);
+}
 
 hipError_t launch_step(hipStream_t s, const EnvStepLaunch& e) {
     if (e.b.n == 0) return hipSuccess;
     const unsigned grid = grid_for(e.b.n, kBlock);
-    const bool wrench = e.wr.rows != nullptr;
+    const EnvStepRoute route = route_env_step(e);
+    const bool wrench = route.wrench;
     const ObsNext on{e.obs_of_next, e.nc, e.noise ? 1u : 0u, e.obs_epoch, e.obs_epoch_base};
-    if (e.block_policy != nullptr) {
-        if (!e.rollout || e.next_state != e.state || mailbox_used(e.mb) || e.obs_of_next != nullptr) return hipErrorInvalidValue;
+    if (route.family == EnvStepFamily::UNSUPPORTED) return hipErrorInvalidValue;
+    if (route.family == EnvStepFamily::VEHICLE) {
+        launch_step_vehicle(s, e, route, grid, on);
+    } else if (route.family == EnvStepFamily::BANK_VEHICLE) {
+        if (wrench)
+            RQ_KLAUNCH(k_step_bank_vehicle<true>, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed,
+                       e.hidden, e.weights, e.block_policy, e.wr, e.vh);
+        else
+            RQ_KLAUNCH(k_step_bank_vehicle<false>, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed,
+                       e.hidden, e.weights, e.block_policy, e.wr, e.vh);
+    } else if (e.block_policy != nullptr) {
         if (wrench)
             RQ_KLAUNCH(k_step_bank_wrench, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed,
                        e.hidden, e.weights, e.block_policy, e.wr);
@@ -1203,6 +1251,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr TrackPtrs trk{};
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
+    constexpr bool VEHICLE = false;
+    constexpr VehiclePtrs vh{};
     constexpr uint32_t interval = 1;
     const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
 #include "rq_rollout_body.inc"
@@ -1228,6 +1278,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr bool RATE = true, SAS = false, WRENCH = false;
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
+    constexpr bool VEHICLE = false;
+    constexpr VehiclePtrs vh{};
     const uint32_t policy = block_policy[blockIdx.x];
     const uint32_t interval = policy_interval[policy];
     const float* __restrict__ packed = images + (size_t)policy * image_floats;
@@ -1272,8 +1324,9 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = true;
+    constexpr bool RATE = true, SAS = false, WRENCH = true, VEHICLE = false;
     constexpr SasArgs sas{};
+    constexpr VehiclePtrs vh{};
     uint32_t policy = 0, interval = single_interval;
     if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
         policy = block_policy[blockIdx.x];
@@ -1290,6 +1343,49 @@ static inline void launch_fused_wrench_actor(hipStream_t s, const FusedArgs& a) 
         hipLaunchKernelGGL((k_rollout_fused_wrench<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
                            a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
                            a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.wr, a.span);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
+}
+
+// ---- the fused kernel of an env that carries a vehicle schedule
+// Built as k_rollout_fused_wrench is - the RATE loop with optional block tables, so one entry point serves rq_rollout,
+// rq_rollout_record, rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every native interval - with VEHICLE on: the
+// nine base fields the schedule scales stay live, the env's first row is loaded once per launch, every step asks for its 16-byte row
+// of factors ahead of the actor and, just before the env step, rebuilds the scheduled members of the per-env constants (1/m, 2/m; J
+// and 1/J; c0..c2; 1/tau_rise, 1/tau_fall: six reciprocals, eleven products) and the folded disturbance from them
+// (rq_rollout_body.inc).  fp32 actors only: the host refuses the 16-bit policies, the SampleAndSquash stage and a wrench schedule
+// beside a vehicle schedule in fused mode.
+template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_vehicle(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ images,
+                                                               const uint32_t* __restrict__ block_policy,
+                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
+                                                               uint32_t single_interval,
+                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, VehiclePtrs vh,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = true;
+    constexpr SasArgs sas{};
+    constexpr WrenchPtrs wr{};
+    uint32_t policy = 0, interval = single_interval;
+    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
+        policy = block_policy[blockIdx.x];
+        interval = policy_interval[policy];
+    }
+    const float* __restrict__ packed = images + (size_t)policy * image_floats;
+#include "rq_rollout_body.inc"
+}
+
+// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
+template <typename ACTOR>
+static inline void launch_fused_vehicle_actor(hipStream_t s, const FusedArgs& a) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
+        hipLaunchKernelGGL((k_rollout_fused_vehicle<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
+                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.vh, a.span);
     }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
@@ -1317,11 +1413,13 @@ hipError_t launch_rollout_fused(hipStream_t s, const FusedArgs& a) {
     case FusedBuild::F16X2:      // the 16-bit actors live in their own translation unit (rq_kernels_16bit.hip: a place for per-build flags)
         return launch_rollout_fused_16bit(s, a, r.family);
     case FusedBuild::F32_LEAN:
-        if (a.sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a);      // (PLAIN: route_fused allows the stage nowhere else)
-        else                          launch_fused_f32_actor<ActorF32Lean>(s, a, r.family);
+        if (r.vehicle)                     launch_fused_vehicle_actor<ActorF32Lean>(s, a);    // (a vehicle schedule: its own entry point)
+        else if (a.sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a);      // (PLAIN: route_fused allows the stage nowhere else)
+        else                               launch_fused_f32_actor<ActorF32Lean>(s, a, r.family);
         break;
     case FusedBuild::F32:
-        launch_fused_f32_actor<ActorF32>(s, a, r.family);
+        if (r.vehicle) launch_fused_vehicle_actor<ActorF32>(s, a);
+        else           launch_fused_f32_actor<ActorF32>(s, a, r.family);
         break;
     }
     return hipGetLastError();
@@ -1360,6 +1458,22 @@ __global__ __launch_bounds__(kBlock) void k_step_bank_wrench(Batch b, StepCfg c,
         step_env<true, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
                              weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr);
 }
+
+// ... and for one that carries a vehicle schedule, with or without a wrench schedule beside it
+template <bool WRENCH>
+__global__ __launch_bounds__(kBlock) void k_step_bank_vehicle(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                              float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                              uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                              const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true, WRENCH, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                                     weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr, vh);
+}
+template __global__ void k_step_bank_vehicle<false>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t, SampleCfg, uint64_t,
+                                                    float*, const float*, const uint32_t*, WrenchPtrs, VehiclePtrs);
+template __global__ void k_step_bank_vehicle<true>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t, SampleCfg, uint64_t,
+                                                   float*, const float*, const uint32_t*, WrenchPtrs, VehiclePtrs);
 
 // k_thaw_frozen likewise: an env left frozen starts its next episode with ITS policy's initial state
 #define RQ_THAW_KERNEL k_thaw_frozen_bank

@@ -70,6 +70,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr bool TRACK = false, RATE = false, WRENCH = false;
     constexpr TrackPtrs trk{};
     constexpr WrenchPtrs wr{};
+    constexpr bool VEHICLE = false;
+    constexpr VehiclePtrs vh{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -90,6 +92,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr bool TRACK = true, SAS = false, RATE = false, WRENCH = false;
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
+    constexpr bool VEHICLE = false;
+    constexpr VehiclePtrs vh{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -110,6 +114,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr bool RATE = true, SAS = false, WRENCH = false;
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
+    constexpr bool VEHICLE = false;
+    constexpr VehiclePtrs vh{};
 #include "rq_rollout_body.inc"
 }
 

@@ -2,9 +2,10 @@
 // (TRACK = false), k_rollout_fused_track (TRACK = true, SAS = false) and k_rollout_fused_rate (RATE = true, SAS = false).  Text, not a function: the untracked kernel is compiled from
 // exactly what it was compiled from when the body stood between its braces - its listing does not move when the tracked variant
 // changes - and a __device__ function in between does cost that (the work-group-size folds of a kernel are made before inlining).
-// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, ACTOR and the names
-// b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, interval, span.
+// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, VEHICLE, ACTOR and the
+// names b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, vh, interval, span.
 // WRENCH (k_rollout_fused_wrench alone; every other entry point defines it false and an empty wr): the env carries a wrench schedule.
+// VEHICLE (k_rollout_fused_vehicle alone; every other entry point defines it false and an empty vh): the env carries a vehicle schedule.
     // kernel-level timing (rq_device_set_rollout_timing): every wave leaves the wall-clock ticks (constant rate) at which it
     // came in and went out, and its XCD: the eight dies' counters are offset against one another by microseconds, one die's
     // are consistent - the host takes first-in / last-out per die
@@ -56,6 +57,14 @@
         wrench_scales(wr.relative, field(params, RQ_P_MASS, ld)[i], c.gravity, field(params, RQ_P_ROTOR_POS, ld)[i],
                       field(params, (RQ_P_ROTOR_POS + 1), ld)[i], wr_fs, wr_ts);
         wr_row0 = wr.row0[i];
+    }
+    // VEHICLE: the nine base fields the schedule scales stay live through the loop (the other builds let them die after make_consts),
+    // and the first row of the env's own table, once per launch
+    [[maybe_unused]] VehicleBase vh_base{};
+    [[maybe_unused]] uint32_t vh_row0 = 0;
+    if constexpr (VEHICLE) {
+        vh_base = vehicle_base([&](int f) { return field(params, f, ld)[i]; });
+        vh_row0 = vh.row0[i];
     }
     const uint8_t last_t_raw = st.last_terminated[i];
     uint8_t last_d = AUTORESET ? (uint8_t)0 : st.last_done[i];       // auto-reset: rebuilt in the epilogue
@@ -164,7 +173,10 @@
     bool frozen = AUTORESET ? false : was_frozen;
     uint32_t last_step = n_steps;                      // without auto-reset: the last step of this launch the env took
     // wave-uniform: no env of this wave distinguishes rotor spin-up from spin-down (see dynamics<SYM_TAU>)
-    const bool sym_tau = __builtin_amdgcn_ballot_w64(k.itr != k.itf) == 0;
+    // (VEHICLE: decided from the base time constants, so that it holds for every row - equal inputs times one factor are equal, and
+    // so are their reciprocals; a comparison of reciprocals could be broken by one row)
+    const bool sym_tau = VEHICLE ? __builtin_amdgcn_ballot_w64(vh_base.tau_rise != vh_base.tau_fall) == 0
+                                 : __builtin_amdgcn_ballot_w64(k.itr != k.itf) == 0;
 
     // The loop exists twice, once per dynamics variant (round 3): with the wave-uniform choice inside the loop the two
     // variants met in a join that cost the state's registers a copy per step (~8 moves) plus the branch itself.
@@ -178,6 +190,9 @@
         // cache), asked for here so that the actor's MFMA batches cover the latency; it is consumed just before the env step
         [[maybe_unused]] float wr_row[6];
         if constexpr (WRENCH) wrench_row(wr.rows, wr.n_rows, wr_row0, ep_steps, wr_row);
+        // VEHICLE: likewise this step's 16-byte row of factors, one load; it is consumed just before the env step
+        [[maybe_unused]] float vh_row[4];
+        if constexpr (VEHICLE) vehicle_row(vh.rows, vh.n_rows, vh_row0, ep_steps, vh_row);
         observe_head<NOISE>(y, LA01, LA23, nc, seed, epoch0 + t, genv, o);
         if constexpr (TRACK) {
             // the setpoint of this step: the row of the env's own episode step count (lanes are at different rows: per-lane
@@ -250,7 +265,15 @@
         QuadState yn = y;
         f32x2 A01, A23;
         bool term;
-        const float r = step_inplace<SYM>(c, k, ds, yn, a, A01, A23, term);
+        float r;
+        if constexpr (VEHICLE) {     // this transition's vehicle: the scheduled members of the constants rebuilt from the base fields
+            EnvConsts kv = k;
+            vehicle_consts(vh_base, vh_row, kv);
+            ds = make_disturbance(kv, c.gravity, f6);
+            r = step_inplace<SYM>(c, kv, ds, yn, a, A01, A23, term);
+        } else {
+            r = step_inplace<SYM>(c, k, ds, yn, a, A01, A23, term);
+        }
         // the reward is wanted HERE: left to itself its arithmetic sinks below the episode-end block, which overwrites the
         // state it reads - and the state then lives twice, nine copies per step
         asm volatile("" :: "v"(r));

@@ -37,7 +37,7 @@ from . import _lib
 from ._lib import (ACTION_DIM, OBSERVATION_DIM, PARAM_DIM, STATE_DIM, ROLLOUT_AUTORESET, ROLLOUT_CHAINED,
                    ROLLOUT_FUSED, EnvConfig, RaptorQuadError)
 
-__all__ = ["Device", "Reference", "WrenchBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
+__all__ = ["Device", "Reference", "WrenchBank", "VehicleBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
 
 
 class UI:
@@ -238,6 +238,26 @@ class WrenchBank:
         self._fin = weakref.finalize(self, _lib.load().rq_wrench_bank_destroy, h)
 
 
+class VehicleBank:
+    """M vehicle tables of the same length for ``env.set_vehicle_schedule(bank, ids)``: ``tables`` float32 [M, rows, 4] (or a list of
+    M [rows, 4] tables; ``raptor_amd.vehicles`` builds them), positive factors on the mass, the inertia, the thrust curve and the
+    motor time constant.  While the bank is attached to an env, every transition of env i is computed from its parameters times
+    the row of its own episode step count of table ``ids[i]`` (include/raptor_quad.h "Vehicle schedule").  The tables are copied
+    to ``device`` once, here."""
+
+    def __init__(self, device, tables):
+        from . import vehicles
+        t = vehicles.check_tables(tables)          # refused before the device is touched
+        h = C.c_void_p()
+        _lib.call("rq_vehicle_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), C.byref(h))
+        self._h = h
+        self._device = device
+        self.n_tables = int(t.shape[0])
+        self.rows = int(t.shape[1])
+        # (the library refuses to destroy a bank that is still attached to a live env; the envs hold their bank, so it outlives them)
+        self._fin = weakref.finalize(self, _lib.load().rq_vehicle_bank_destroy, h)
+
+
 def _checked_reference(reference, reference_ids, n_envs):
     """What a rollout's ``reference`` / ``reference_ids`` pair must be, before any library call -> the ids as uint32 (a
     ``ReferenceBank``) or None (a ``Reference``, or no reference); ValueError otherwise."""
@@ -268,6 +288,23 @@ def _checked_wrench_ids(env, wrench_ids, ref_ids, n_envs):
     return check_wrench_ids(wrench_ids, schedule[0].n_tables, n_envs)
 
 
+def _checked_vehicle_ids(env, vehicle_ids, wrench_ids, ref_ids, n_envs):
+    """What ``vehicle_ids`` of ``PolicyBank.evaluate`` / ``TeacherBank.closed_loop`` must be, before any library call -> the ids as
+    uint32, or None (none given); ValueError otherwise."""
+    if vehicle_ids is None:
+        return None
+    schedule = getattr(env, "vehicle_schedule", None)
+    if schedule is None:
+        raise ValueError("vehicle_ids name tables of the env's vehicle schedule: attach one first (env.set_vehicle_schedule(bank))")
+    if wrench_ids is not None:
+        raise ValueError("vehicle_ids group the tracking error by vehicle scenario and wrench_ids by disturbance: give one of them")
+    if ref_ids is not None:
+        raise ValueError("vehicle_ids group the tracking error by vehicle scenario and reference_ids by setpoint: give one of them "
+                         "(a single l2f.Reference goes with vehicle_ids)")
+    from .vehicles import check_vehicle_ids
+    return check_vehicle_ids(vehicle_ids, schedule[0].n_tables, n_envs)
+
+
 _MODES = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}
 
 
@@ -293,12 +330,14 @@ def _rollout_call(entry, device, env, params, state, actor_handle, ids, rng, n_s
     return _lib.call("rq_rollout_record", *args, traj)
 
 
-def tracking_rmse(env, reference, ref_ids, w_ids, actor_ids, n_actors):
+def tracking_rmse(env, reference, ref_ids, w_ids, actor_ids, n_actors, v_ids=None):
     """``tracking_rmse`` of a bank's closed-loop table, from ``env.tracking_error()`` grouped by actor (policy or teacher): [n_actors,
-    M] over the disturbance scenarios (``w_ids``) or over the setpoints (``ref_ids`` of a ``ReferenceBank``), [n_actors] on a single
-    ``Reference``."""
+    M] over the disturbance scenarios (``w_ids``), the vehicle scenarios (``v_ids``) or the setpoints (``ref_ids`` of a
+    ``ReferenceBank``), [n_actors] on a single ``Reference``."""
     from .tracking import reference_tracking_table
     sum_sq, steps = env.tracking_error()
+    if v_ids is not None:
+        return reference_tracking_table(sum_sq, steps, v_ids, env.vehicle_schedule[0].n_tables, actor_ids, n_actors)
     if w_ids is not None:
         return reference_tracking_table(sum_sq, steps, w_ids, env.wrench_schedule[0].n_tables, actor_ids, n_actors)
     if ref_ids is not None:
@@ -536,6 +575,31 @@ class VectorModule:
             def wrench_schedule(self):
                 """(bank, ids) of the attached schedule, or None."""
                 return None if self._wrench is None else (self._wrench[0], self._wrench[1].copy())
+
+            # --- vehicle schedule (payloads, battery sag, slow motors: raptor_amd.vehicles) ---
+            _vehicle = None
+
+            def set_vehicle_schedule(self, bank, ids=None):
+                """Attach ``bank`` (an ``l2f.VehicleBank``): from now on every transition of env i, in every call that steps this
+                env, is computed from its parameters times the row of its episode step count of table ``ids[i]`` ([N] integers,
+                free per env; None: table 0 for every env).  The tables must cover ``episode_step_limit``."""
+                if not isinstance(bank, VehicleBank):
+                    raise ValueError("bank must be an l2f.VehicleBank (clear_vehicle_schedule() detaches)")
+                from .vehicles import check_vehicle_ids
+                a = (np.zeros(mod.N_ENVIRONMENTS, np.uint32) if ids is None
+                     else check_vehicle_ids(ids, bank.n_tables, mod.N_ENVIRONMENTS))
+                _lib.call("rq_env_set_vehicle_schedule", self._require("environment"), bank._h, a.ctypes.data)
+                self._vehicle = (bank, a.copy())
+
+            def clear_vehicle_schedule(self):
+                if self._h is not None:
+                    _lib.call("rq_env_set_vehicle_schedule", self._h, None, None)
+                self._vehicle = None
+
+            @property
+            def vehicle_schedule(self):
+                """(bank, ids) of the attached schedule, or None."""
+                return None if self._vehicle is None else (self._vehicle[0], self._vehicle[1].copy())
 
             def tracking_error(self):
                 """-> (sum_sq [N] float32, steps [N] uint32): per env, the running sum of |p - p_ref|^2 over the steps it took in

@@ -169,7 +169,7 @@ class TeacherBank:
                       reference, ref_ids)
 
     def closed_loop(self, vector, device, env, params, state, rng, n_steps, teacher_ids, mode="fused", autoreset=True,
-                    reference=None, reference_ids=None, wrench_ids=None):
+                    reference=None, reference_ids=None, wrench_ids=None, vehicle_ids=None):
         """The closed-loop check of the whole bank: the env's statistics start afresh, one ``fly`` of ``n_steps`` ->
         ``teacher_episode_table`` of what it finished.  With ``reference`` the table gains ``tracking_rmse`` [K]
         (``policy_bank.policy_tracking_table`` of ``env.tracking_error()``, grouped by teacher); with an ``l2f.ReferenceBank`` and
@@ -177,19 +177,23 @@ class TeacherBank:
         [K, M]: teacher k on setpoint r (``tracking.reference_tracking_table``) - what a student's tracking error stands against.
         ``wrench_ids`` ([N] integers; the env carries a wrench schedule): env i flies disturbance scenario ``wrench_ids[i]`` of the
         attached bank and, on an ``l2f.Reference``, ``tracking_rmse`` is [K, M] over the scenarios (``mode="chained"``: the fused
-        teacher kernel does not fly a schedule)."""
-        from .l2f import _checked_reference, _checked_wrench_ids, tracking_rmse
+        teacher kernel does not fly a schedule).  ``vehicle_ids`` likewise name the tables of the env's vehicle schedule; giving both
+        is refused."""
+        from .l2f import _checked_reference, _checked_vehicle_ids, _checked_wrench_ids, tracking_rmse
         ids = check_teacher_ids(teacher_ids, vector.N_ENVIRONMENTS)
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
         w_ids = _checked_wrench_ids(env, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
+        v_ids = _checked_vehicle_ids(env, vehicle_ids, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
         if w_ids is not None:
             env.set_wrench_schedule(env.wrench_schedule[0], w_ids)
+        if v_ids is not None:
+            env.set_vehicle_schedule(env.vehicle_schedule[0], v_ids)
         env.reset_statistics()
         self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
                  reference_ids=reference_ids)
         table = teacher_episode_table(env, ids, self.n_teachers)
         if reference is not None:
-            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, w_ids, ids, self.n_teachers)
+            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, w_ids, ids, self.n_teachers, v_ids)
         return table
 
 
