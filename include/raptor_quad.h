@@ -91,7 +91,8 @@ extern "C" {
                               no struct changed)
                               (still 5: rq_rollout_teachers_track and rq_rollout_teachers_track_refs added, no struct changed)
                               (still 5: rq_wrench_bank_{create,destroy} and rq_env_{set,get}_wrench_schedule added, no struct changed)
-                              (still 5: rq_vehicle_bank_{create,destroy} and rq_env_{set,get}_vehicle_schedule added, no struct changed) */
+                              (still 5: rq_vehicle_bank_{create,destroy} and rq_env_{set,get}_vehicle_schedule added, no struct changed)
+                              (still 5: rq_wind_bank_{create,destroy} and rq_env_{set,get}_wind_schedule added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -572,6 +573,47 @@ RQ_API int rq_env_set_vehicle_schedule(rq_env* env, rq_vehicle_bank* bank /* NUL
                                        const uint32_t* vehicle_id /* host [n_envs] or NULL = table 0 */);
 RQ_API int rq_env_get_vehicle_schedule(const rq_env* env, rq_vehicle_bank** bank /* NULL when none */,
                                        uint32_t* vehicle_id_out /* host [n_envs] or NULL */);
+
+/* ---- Wind schedule: the air moves, and the vehicle is dragged towards the air's velocity.  A wrench schedule applies a force that is
+ * the same whatever the vehicle does; the force of wind depends on the vehicle's own velocity through the air: a quadrotor in a steady
+ * wind leans into it and settles, one that drifts with the wind feels nothing, still air damps every motion.  A WIND BANK is n_tables
+ * tables of one length, host_rows [n_tables][rows][4] float32 row-major: columns 0..2 the air velocity w in the world frame, m/s;
+ * column 3 the specific drag d in 1/s, the drag force per unit mass and unit air speed (>= 0).  The drag is linear, the rotor-drag
+ * regime of small multirotors.  A schedule is attached to an ENV: a bank plus one table id per env.  While it is attached EVERY
+ * transition of env i, in every call that steps (rq_step, the rollouts of a policy, a policy bank and a teacher bank, chained; fused
+ * as said below), is computed as
+ *     k    = the env's episode step count before the step, clamped to rows - 1   (the count the other two schedules index with)
+ *     row  = table[wind_id[i]][k]
+ *     md   = mass * row[3]            mass: the params' RQ_P_MASS (with a vehicle schedule attached too: the step's effective mass)
+ *     u[j] = row[j] - v[j]            j = 0..2, v = the linear velocity of the state BEFORE the step (state fields 7..9)
+ *     w[j] = b[j] + (md * u[j])       b = the state's RQ_S_FORCE, or, with a wrench schedule attached too, the wrench-composed force
+ *     torque: unchanged
+ * every *, - and + one correctly rounded fp32 operation, in this order, nothing contracted (raptor_amd.winds.compose is the NumPy
+ * float32 restatement).  The drag is a ZERO-ORDER HOLD: it is evaluated once, at the state entering the step, and held across the
+ * four RK4 stages; it is not re-evaluated as the velocity changes inside the step.  At dt * d <= 0.01 * d this is benign for any
+ * physical d, and it makes the transition bit for bit what a caller gets who writes this force into the state's force columns
+ * before every rq_step.  The composed force goes to the dynamics and nowhere else.  Hence: the next state keeps the per-episode base
+ * (RQ_S_FORCE is not written); a frozen env reads nothing; rq_env_reset_statistics zeroes the step count and so restarts the table;
+ * the mass comes from the params passed to the call, rq_params_set after attaching is honoured; reward, termination, RNG streams,
+ * statistics and observations are those of the resulting motion - the policy still sees the velocity over ground; a row with d = 0
+ * adds +-0 to the force, which changes no bit of a base that is not -0.
+ * rq_wind_bank_create refuses a null argument, n_tables == 0, rows == 0, an entry that is not finite, a negative drag (the message
+ * names table, row and column) and n_tables * rows >= 2^28, all before the device is looked at.  rq_env_set_wind_schedule (bank NULL:
+ * detach; wind_id NULL: table 0 for every env) refuses a bank of another rq_device (RQ_ERR_SHAPE_MISMATCH) and an id >= n_tables (the
+ * message names the env).  rq_wind_bank_destroy is refused while the bank is attached to a live env; rq_env_destroy detaches.  Every
+ * call that steps refuses, before anything is enqueued (state, rng epoch, statistics and recording untouched), a bank with rows <
+ * episode_step_limit.  In fused mode a schedule is flown by the fp32 policy and policy-bank kernels (k_rollout_fused_wind); a bf16 /
+ * f16x2 policy, a SampleAndSquash stage, rq_rollout_teachers* and an env that carries a wrench or a vehicle schedule too are refused
+ * in fused mode while a wind schedule is attached (nothing runs chained in their place) - all of them run chained.  The small-batch
+ * loop steps such an env with plain launches (no resident executor, no speculative policy step). */
+typedef struct rq_wind_bank rq_wind_bank;
+RQ_API int rq_wind_bank_create(rq_device* dev, const float* host_rows /* [n_tables][rows][4] */, uint32_t n_tables, uint32_t rows,
+                               rq_wind_bank** out);
+RQ_API int rq_wind_bank_destroy(rq_wind_bank* bank);
+RQ_API int rq_env_set_wind_schedule(rq_env* env, rq_wind_bank* bank /* NULL detaches */,
+                                    const uint32_t* wind_id /* host [n_envs] or NULL = table 0 */);
+RQ_API int rq_env_get_wind_schedule(const rq_env* env, rq_wind_bank** bank /* NULL when none */,
+                                    uint32_t* wind_id_out /* host [n_envs] or NULL */);
 
 /* ---- Learner: the student's gradient over a recorded trajectory (README.md:208-216, the distillation step's regression) ----
  * Forward: the policy on the recorded observations obs [T][22][ld] under rq_trajectory_relabel's episode rules (GRU state back to

@@ -245,6 +245,10 @@ _SIGNATURES = {
     "rq_vehicle_bank_destroy": [_vp],
     "rq_env_set_vehicle_schedule": [_vp, _vp, _vp],
     "rq_env_get_vehicle_schedule": [_vp, C.POINTER(_vp), _vp],
+    "rq_wind_bank_create": [_vp, _fp, C.c_uint32, C.c_uint32, C.POINTER(_vp)],
+    "rq_wind_bank_destroy": [_vp],
+    "rq_env_set_wind_schedule": [_vp, _vp, _vp],
+    "rq_env_get_wind_schedule": [_vp, C.POINTER(_vp), _vp],
 }
 _RESTYPES = {"rq_last_error": C.c_char_p, "rq_status_string": C.c_char_p}
 

@@ -488,6 +488,7 @@ RQ_API int rq_env_destroy(rq_env* env) {
     if (device_registry(env->dev, 0)) (void)resident_retire(env->dev);     // keeps a resident executor
     if (env->wrench) env->wrench->attached -= 1;          // detaches the wrench schedule: its bank may be destroyed now
     if (env->vehicle) env->vehicle->attached -= 1;        // ... and the vehicle schedule
+    if (env->wind) env->wind->attached -= 1;              // ... and the wind schedule
     for (float* b : env->state_pool) (void)hipFree(b);
     for (auto& g : env->graphs) (void)hipGraphExecDestroy(g.exec);
     delete env;

@@ -40,7 +40,28 @@ int rollout_check(RolloutFrame& f, const RolloutCall& c, bool actor) {
     // a vehicle schedule is flown fused by the fp32 builds alone and without a wrench schedule beside it; nothing runs chained in
     // its place (the actors refuse what is theirs: a 16-bit policy, a SampleAndSquash stage, a teacher bank)
     if (f.vh.rows && f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return vehicle_refuses_fused(c.who, "an env that carries a wrench schedule too");
+    // a wind schedule likewise, and without either of the other two beside it
+    rc = env_wind("rollout", c.env, &f.wd); if (rc) return rc;
+    if (f.wd.rows && f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return wind_refuses_fused(c.who, "an env that carries a wrench schedule too");
+    if (f.wd.rows && f.vh.rows && c.mode == RQ_ROLLOUT_FUSED) return wind_refuses_fused(c.who, "an env that carries a vehicle schedule too");
     return RQ_OK;
+}
+
+int env_wind(const char* who, const rq_env* env, rq::WindPtrs* wd) {
+    *wd = rq::WindPtrs{};
+    const rq_wind_bank* bank = env->wind;
+    if (!bank) return RQ_OK;
+    if (bank->rows < env->cfg.episode_step_limit)
+        return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env's wind schedule has fewer rows (" + std::to_string(bank->rows) +
+                                                 ") than episode_step_limit (" + std::to_string(env->cfg.episode_step_limit) +
+                                                 "): every table must cover an episode");
+    *wd = {bank->d, env->wind_row0, bank->rows, 0u};
+    return RQ_OK;
+}
+
+int wind_refuses_fused(const char* who, const char* what) {
+    return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env carries a wind schedule, which the fused kernel of " + what +
+                                             " is not taught: fly it with mode RQ_ROLLOUT_CHAINED (\"chained\"), or detach the schedule");
 }
 
 int env_vehicle(const char* who, const rq_env* env, rq::VehiclePtrs* vh) {
@@ -159,14 +180,14 @@ rq::FusedArgs fused_args(const RolloutCall& c, const RolloutFrame& f) {
     a.seed = c.rng->seed; a.epoch0 = c.rng->epoch; a.n_steps = c.n_steps;
     a.autoreset = (c.flags & RQ_ROLLOUT_AUTORESET) != 0;
     a.params = c.params->d; a.state = c.state->d; a.st = c.env->st;
-    a.traj = f.tp; a.trk = f.trk; a.wr = f.wr; a.vh = f.vh;
+    a.traj = f.tp; a.trk = f.trk; a.wr = f.wr; a.vh = f.vh; a.wd = f.wd;
     return a;
 }
 
 rq::EnvStepLaunch env_step_launch(const RolloutCall& c, const RolloutFrame& f) {
     rq::EnvStepLaunch e;
     e.b = f.b; e.c = f.sc; e.params = c.params->d; e.state = c.state->d; e.action = c.env->act; e.next_state = c.state->d; e.st = c.env->st;
-    e.rollout = true; e.flags = c.flags; e.sc = f.smp; e.seed = c.rng->seed; e.wr = f.wr; e.vh = f.vh;
+    e.rollout = true; e.flags = c.flags; e.sc = f.smp; e.seed = c.rng->seed; e.wr = f.wr; e.vh = f.vh; e.wd = f.wd;
     return e;
 }
 
@@ -211,6 +232,10 @@ struct PolicyActor {
             if (policy->precision != RQ_POLICY_FP32) return vehicle_refuses_fused(c.who, "a bf16 / f16x2 policy");
             if (policy->sas_mode != RQ_SAS_OFF) return vehicle_refuses_fused(c.who, "a policy with a SampleAndSquash stage");
         }
+        if (f.wd.rows && c.mode == RQ_ROLLOUT_FUSED) {        // ... and a wind schedule
+            if (policy->precision != RQ_POLICY_FP32) return wind_refuses_fused(c.who, "a bf16 / f16x2 policy");
+            if (policy->sas_mode != RQ_SAS_OFF) return wind_refuses_fused(c.who, "a policy with a SampleAndSquash stage");
+        }
         return RQ_OK;
     }
     int prepare(const RolloutCall& c) const {
@@ -254,16 +279,18 @@ struct PolicyActor {
         key.ref = f.trk.ref; key.ref_rows = f.trk.rows; key.row0_at = f.trk.row0_at;
         key.row0_gen = f.row0_gen;      // (a reference bank: which ids the rows were built from)
         key.interval = policy->native_interval; key.wrench_gen = c.env->wrench_gen; key.vehicle_gen = c.env->vehicle_gen;
+        key.wind_gen = c.env->wind_gen;
         return key;
     }
 };
 
 // The tables of rq_reference_create (`single`: one table, named without a bank's words), rq_reference_bank_create and
 // rq_wrench_bank_create: refused before the device is looked at, then allocated and uploaded.  T: the handle's type.
-// `cols`: 6, or a vehicle bank's 4 positive factors (`positive`: an entry that is not > 0 is refused too, naming its column).
+// `cols`: 6, or a vehicle bank's 4 positive factors (`positive`: an entry that is not > 0 is refused too, naming its column), or a wind
+// bank's 4 (`nonneg_col`: the column whose entries, the specific drag, must not be negative).
 template <typename T>
 int row_tables_create(const char* who, const char* noun, bool single, rq_device* dev, const float* host_rows, uint32_t n_tables,
-                      uint32_t rows, T** out, uint32_t cols = 6, bool positive = false) {
+                      uint32_t rows, T** out, uint32_t cols = 6, bool positive = false, int nonneg_col = -1) {
     RQ_REFUSE(who, dev && host_rows && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     if (single) RQ_REFUSE(who, rows > 0, RQ_ERR_INVALID_ARGUMENT, "a reference needs at least one row");
@@ -276,9 +303,12 @@ int row_tables_create(const char* who, const char* noun, bool single, rq_device*
         RQ_REFUSE(who, std::isfinite(host_rows[j]), RQ_ERR_INVALID_ARGUMENT,
                   std::string(noun) + " holds a non-finite entry" +
                       (single ? "" : ": table " + std::to_string(j / ((size_t)rows * cols)) + ", row " + std::to_string(j / cols % rows)) +
-                      (positive ? ", column " + std::to_string(j % cols) : ""));
+                      (positive || nonneg_col >= 0 ? ", column " + std::to_string(j % cols) : ""));
         RQ_REFUSE(who, !positive || host_rows[j] > 0.0f, RQ_ERR_INVALID_ARGUMENT,
                   std::string(noun) + " holds a factor that is not > 0: table " + std::to_string(j / ((size_t)rows * cols)) + ", row " +
+                      std::to_string(j / cols % rows) + ", column " + std::to_string(j % cols));
+        RQ_REFUSE(who, (int)(j % cols) != nonneg_col || host_rows[j] >= 0.0f, RQ_ERR_INVALID_ARGUMENT,
+                  std::string(noun) + " holds a negative drag: table " + std::to_string(j / ((size_t)rows * cols)) + ", row " +
                       std::to_string(j / cols % rows) + ", column " + std::to_string(j % cols));
     }
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
@@ -463,6 +493,61 @@ RQ_API int rq_env_get_vehicle_schedule(const rq_env* env, rq_vehicle_bank** bank
     RQ_REQUIRE(env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
     *bank = env->vehicle;
     if (env->vehicle && vehicle_id_out) std::memcpy(vehicle_id_out, env->vehicle_ids.data(), (size_t)env->n * sizeof(uint32_t));
+    return RQ_OK;
+}
+
+// ---------------------------------------------------------------------------- Wind schedule
+RQ_API int rq_wind_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, rq_wind_bank** out) {
+    return row_tables_create(__func__, "wind bank", false, dev, host_rows, n_tables, rows, out, 4, false, 3);
+}
+
+RQ_API int rq_wind_bank_destroy(rq_wind_bank* bank) {
+    RQ_REQUIRE(!bank || bank->attached == 0, RQ_ERR_INVALID_ARGUMENT,
+               "the wind bank is attached to " + std::to_string(bank->attached) +
+                   " live env(s): detach it (rq_env_set_wind_schedule with a NULL bank) or destroy the env first");
+    return row_tables_destroy(bank);
+}
+
+RQ_API int rq_env_set_wind_schedule(rq_env* env, rq_wind_bank* bank, const uint32_t* wind_id) {
+    RQ_REQUIRE(env, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    rq_device* dev = env->dev;
+    if (bank) {
+        RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "wind bank lives on another device");
+        if (wind_id)
+            for (uint32_t i = 0; i < env->n; ++i)
+                RQ_REQUIRE(wind_id[i] < bank->n_tables, RQ_ERR_INVALID_ARGUMENT,
+                           "wind id out of range: env " + std::to_string(i) + " names table " + std::to_string(wind_id[i]) +
+                               " of a bank of " + std::to_string(bank->n_tables));
+    }
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;      // (retires a running resident executor)
+    RQ_HIP(hipStreamSynchronize(dev->stream));                // a launch in flight reads the rows of the schedule before
+    obs_cache_drop_if(dev, env);
+    if (!bank) {
+        if (env->wind) env->wind->attached -= 1;
+        env->wind = nullptr; env->wind_gen = 0; env->wind_ids.clear();
+        return RQ_OK;
+    }
+    std::vector<uint32_t> ids;
+    try {                                   // nothing throws across the boundary
+        if (wind_id) ids.assign(wind_id, wind_id + env->n); else ids.assign(env->n, 0u);
+    } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, "wind schedule: host allocation failed");
+    }
+    if (env->wind_row0.empty() && env->wind_row0.alloc(env->ld) != hipSuccess)
+        return fail(RQ_ERR_OUT_OF_MEMORY, "wind schedule: device allocation failed");
+    rc = upload_first_rows("wind schedule", dev, env, wind_id, bank->rows, env->wind_row0); if (rc) return rc;
+    if (env->wind) env->wind->attached -= 1;
+    bank->attached += 1;
+    env->wind = bank;
+    env->wind_ids.swap(ids);
+    env->wind_gen = fresh_version();
+    return RQ_OK;
+}
+
+RQ_API int rq_env_get_wind_schedule(const rq_env* env, rq_wind_bank** bank, uint32_t* wind_id_out) {
+    RQ_REQUIRE(env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *bank = env->wind;
+    if (env->wind && wind_id_out) std::memcpy(wind_id_out, env->wind_ids.data(), (size_t)env->n * sizeof(uint32_t));
     return RQ_OK;
 }
 

@@ -300,6 +300,7 @@ struct TeacherActor {
                   "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
         if (f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return wrench_refuses_fused(c.who, "a teacher bank");
         if (f.vh.rows && c.mode == RQ_ROLLOUT_FUSED) return vehicle_refuses_fused(c.who, "a teacher bank");
+        if (f.wd.rows && c.mode == RQ_ROLLOUT_FUSED) return wind_refuses_fused(c.who, "a teacher bank");
         return check_ids(bank, teacher_id, c.env->n);
     }
     int prepare(const RolloutCall& c) {

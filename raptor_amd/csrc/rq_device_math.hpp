@@ -472,6 +472,31 @@ __device__ __forceinline__ void vehicle_consts(const VehicleBase& b, const float
     k.itr = 1.0f / __fmul_rn(b.tau_rise, r[3]); k.itf = 1.0f / __fmul_rn(b.tau_fall, r[3]);
 }
 
+// ------------------------------------------------------------------ wind schedule ------
+// A wind schedule (rq_env_set_wind_schedule) adds, at every transition, a linear drag against the air to the force the transition is
+// computed with: row k of the env's own table [rows][4] = (air velocity in the world frame, m/s; specific drag d, 1/s), k = the env's
+// episode step count before the step (the count wrench_row and vehicle_row index with), clamped to the table.
+//     md = mass * row[3];  u[j] = row[j] - v[j];  w[j] = b[j] + (md * u[j])        j = 0..2
+// v the linear velocity of the state BEFORE the step, b the force the step would be computed with without the wind (the state's
+// per-episode force, or the wrench-composed one), mass the step's mass (the effective one beside a vehicle schedule).  A zero-order
+// hold: evaluated once at the state entering the step and held across the four RK4 stages.  The torque is not touched.  Single
+// rounded operations in this order, nothing the compiler may contract (raptor_amd.winds.compose is the NumPy float32 restatement).
+// The composed force goes to make_disturbance and nowhere else: the state keeps the base.  The two functions below are the only
+// place any path does this.
+// row0: the first row of the env's own table in the bank's flat [n_tables * rows][4] block (the host keeps n_tables * rows below
+// 2^28); one 16-byte load
+__device__ __forceinline__ void wind_row(const float* __restrict__ tab, uint32_t rows, uint32_t row0, uint32_t k, float (&r)[4]) {
+    const float4 v = *reinterpret_cast<const float4*>(tab + (size_t)(row0 + (k < rows ? k : rows - 1u)) * 4u);
+    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
+}
+// f: the six-wrench the step would use (force, torque); the force is replaced by the drag-composed one, the torque stays
+__device__ __forceinline__ void wind_compose(float (&f)[6], float mass, float vx, float vy, float vz, const float (&r)[4]) {
+    const float md = __fmul_rn(mass, r[3]);
+    f[0] = __fadd_rn(f[0], __fmul_rn(md, __fsub_rn(r[0], vx)));
+    f[1] = __fadd_rn(f[1], __fmul_rn(md, __fsub_rn(r[1], vy)));
+    f[2] = __fadd_rn(f[2], __fmul_rn(md, __fsub_rn(r[2], vz)));
+}
+
 // ------------------------------------------------------------------ parameter sampling -
 
 __device__ __forceinline__ void sample_params(const SampleCfg& c, uint64_t seed, uint32_t epoch, uint64_t genv,

@@ -387,13 +387,17 @@ struct ObsNext {
 // VEHICLE: the env carries a vehicle schedule - the per-env constants are made from the effective parameter fields, the base ones
 // times the row of the env's episode step count (rq_device_math.hpp vehicle_*); a new episode is sampled from the base fields, and a
 // relative wrench schedule beside it scales by the effective mass.  A compile-time switch like WRENCH.
-template <bool ROLLOUT, bool WRENCH = false, bool VEHICLE = false>
+// WIND: the env carries a wind schedule - the force the transition is computed with (the state's, or the wrench-composed one) gains
+// the linear drag against the air velocity of the row of the env's episode step count, from the velocity of the state before the
+// step and the step's (effective) mass, held across the RK4 stages (rq_device_math.hpp wind_*); the next state keeps the base.  A
+// compile-time switch like the other two.
+template <bool ROLLOUT, bool WRENCH = false, bool VEHICLE = false, bool WIND = false>
 __device__ __forceinline__ void step_env(uint32_t i, const Batch& b, const StepCfg& c, const float* __restrict__ params,
                                          const float* state, float* __restrict__ action, float* next_state,
                                          const StatsPtrs& st, uint32_t flags, const SampleCfg& sc, uint64_t seed,
                                          float* __restrict__ hidden, const float* __restrict__ weights,
                                          const Mailbox& mb, const ObsNext& on, const WrenchPtrs& wr = WrenchPtrs{},
-                                         const VehiclePtrs& vh = VehiclePtrs{}) {
+                                         const VehiclePtrs& vh = VehiclePtrs{}, const WindPtrs& wd = WindPtrs{}) {
     if (ROLLOUT && st.frozen[i]) { st.last_done[i] = 4; return; }
     const size_t ld = b.ld;
     [[maybe_unused]] float vrow[4];
@@ -417,7 +421,24 @@ __device__ __forceinline__ void step_env(uint32_t i, const Batch& b, const StepC
     }
     Stats s = load_stats(st, i);
     Disturbance ds;
-    if constexpr (WRENCH) {
+    if constexpr (WIND) {
+        float w6[6], drow[4];
+        float mass = field(params, RQ_P_MASS, ld)[i];
+        if constexpr (VEHICLE) mass = vehicle_field(RQ_P_MASS, mass, vrow);       // the step's effective mass
+        wind_row(wd.rows, wd.n_rows, wd.row0[i], s.steps, drow);
+        if constexpr (WRENCH) {
+            float fs, ts, wrow[6];
+            wrench_scales(wr.relative, mass, c.gravity, field(params, RQ_P_ROTOR_POS, ld)[i],
+                          field(params, (RQ_P_ROTOR_POS + 1), ld)[i], fs, ts);
+            wrench_row(wr.rows, wr.n_rows, wr.row0[i], s.steps, wrow);
+            wrench_compose(f6, fs, ts, wrow, w6);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) w6[j] = f6[j];
+        }
+        wind_compose(w6, mass, y.V01[0], y.V01[1], y.VW[0], drow);     // y: the state before the step
+        ds = make_disturbance(k, c.gravity, w6);
+    } else if constexpr (WRENCH) {
         float fs, ts, wrow[6], w6[6];
         float mass = field(params, RQ_P_MASS, ld)[i];
         if constexpr (VEHICLE) mass = vehicle_field(RQ_P_MASS, mass, vrow);       // m g of the step's effective mass
@@ -522,6 +543,22 @@ __global__ __launch_bounds__(kBlock) void k_step_vehicle(Batch b, StepCfg c, con
     const uint32_t i = env_index();
     if (i < b.n)
         step_env<ROLLOUT, WRENCH, true>(i, b, c, params, state, action, next_state, st, flags, sc, seed, hidden, weights, mb, on, wr, vh);
+    mailbox_signal(mb);
+}
+
+// k_step for an env that carries a wind schedule, alone or beside a wrench schedule (WRENCH), a vehicle schedule (VEHICLE) or both
+// (kernels of their own again: the argument blocks and listings of the kernels above stay what they were)
+template <bool ROLLOUT, bool WRENCH, bool VEHICLE>
+__global__ __launch_bounds__(kBlock) void k_step_wind(Batch b, StepCfg c, const float* __restrict__ params,
+                                                      const float* state, float* __restrict__ action,
+                                                      float* next_state, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                      uint64_t seed, float* __restrict__ hidden,
+                                                      const float* __restrict__ weights, Mailbox mb, ObsNext on, WrenchPtrs wr,
+                                                      VehiclePtrs vh, WindPtrs wd) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<ROLLOUT, WRENCH, VEHICLE, true>(i, b, c, params, state, action, next_state, st, flags, sc, seed, hidden, weights, mb, on,
+                                                 wr, vh, wd);
     mailbox_signal(mb);
 }
 // ------------------------------------------------------------------ resident executor ---
@@ -1074,6 +1111,28 @@ __global__ __launch_bounds__(kBlock) void k_step_bank_vehicle(Batch b, StepCfg c
                                     StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
                                     const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh);
 
+template <bool WRENCH, bool VEHICLE>
+__global__ __launch_bounds__(kBlock) void k_step_bank_wind(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
+                                    StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
+                                    const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
+                                    WindPtrs wd);
+
+// the wind schedule's kernels: `family` says what the step would be without the wind (its bank-ness and whether a vehicle schedule
+// stands beside it), `wrench` whether a wrench schedule does
+static void launch_step_wind(hipStream_t s, const EnvStepLaunch& e, const EnvStepRoute& r, unsigned grid, const ObsNext& on) {
+    dispatch_bools([&](auto WR, auto VH, auto RO) {
+        if (e.block_policy != nullptr) {
+            const auto kernel = &k_step_bank_wind<WR(), VH()>;
+            RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed, e.hidden,
+                       e.weights, e.block_policy, e.wr, e.vh, e.wd);
+        } else {
+            const auto kernel = &k_step_wind<RO(), WR(), VH()>;
+            RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
+                       e.hidden, e.weights, e.mb, on, e.wr, e.vh, e.wd);
+        }
+    }, r.wrench, r.family == EnvStepFamily::VEHICLE || r.family == EnvStepFamily::BANK_VEHICLE, r.rollout);
+}
+
 // the vehicle schedule's kernels, by the route's two bools
 static void launch_step_vehicle(hipStream_t s, const EnvStepLaunch& e, const EnvStepRoute& r, unsigned grid, const ObsNext& on) {
     const auto kernel = r.rollout ? (r.wrench ? &k_step_vehicle<true, true> : &k_step_vehicle<true, false>)
@@ -1089,7 +1148,9 @@ hipError_t launch_step(hipStream_t s, const EnvStepLaunch& e) {
     const bool wrench = route.wrench;
     const ObsNext on{e.obs_of_next, e.nc, e.noise ? 1u : 0u, e.obs_epoch, e.obs_epoch_base};
     if (route.family == EnvStepFamily::UNSUPPORTED) return hipErrorInvalidValue;
-    if (route.family == EnvStepFamily::VEHICLE) {
+    if (route.wind) {
+        launch_step_wind(s, e, route, grid, on);
+    } else if (route.family == EnvStepFamily::VEHICLE) {
         launch_step_vehicle(s, e, route, grid, on);
     } else if (route.family == EnvStepFamily::BANK_VEHICLE) {
         if (wrench)
@@ -1253,6 +1314,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WrenchPtrs wr{};
     constexpr bool VEHICLE = false;
     constexpr VehiclePtrs vh{};
+    constexpr bool WIND = false;
+    constexpr WindPtrs wd{};
     constexpr uint32_t interval = 1;
     const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
 #include "rq_rollout_body.inc"
@@ -1280,6 +1343,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WrenchPtrs wr{};
     constexpr bool VEHICLE = false;
     constexpr VehiclePtrs vh{};
+    constexpr bool WIND = false;
+    constexpr WindPtrs wd{};
     const uint32_t policy = block_policy[blockIdx.x];
     const uint32_t interval = policy_interval[policy];
     const float* __restrict__ packed = images + (size_t)policy * image_floats;
@@ -1324,9 +1389,10 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = true, VEHICLE = false;
+    constexpr bool RATE = true, SAS = false, WRENCH = true, VEHICLE = false, WIND = false;
     constexpr SasArgs sas{};
     constexpr VehiclePtrs vh{};
+    constexpr WindPtrs wd{};
     uint32_t policy = 0, interval = single_interval;
     if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
         policy = block_policy[blockIdx.x];
@@ -1367,9 +1433,10 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, VehiclePtrs vh,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = true;
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = true, WIND = false;
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
+    constexpr WindPtrs wd{};
     uint32_t policy = 0, interval = single_interval;
     if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
         policy = block_policy[blockIdx.x];
@@ -1386,6 +1453,49 @@ static inline void launch_fused_vehicle_actor(hipStream_t s, const FusedArgs& a)
         hipLaunchKernelGGL((k_rollout_fused_vehicle<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
                            a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
                            a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.vh, a.span);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
+}
+
+// ---- the fused kernel of an env that carries a wind schedule
+// Built as k_rollout_fused_wrench is - the RATE loop with optional block tables, one entry point for rq_rollout, rq_rollout_record,
+// rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every native interval - with WIND on: the mass and the env's
+// first row are loaded once per launch, every step asks for its 16-byte row ahead of the actor and, just before the env step, adds
+// the drag against the air at the state before the step to the force (one product for m d, three differences, three products, three
+// sums) and folds the disturbance from it (rq_rollout_body.inc).  fp32 actors only: the host refuses the 16-bit policies, the
+// SampleAndSquash stage and another schedule beside a wind schedule in fused mode.
+template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_wind(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ images,
+                                                               const uint32_t* __restrict__ block_policy,
+                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
+                                                               uint32_t single_interval,
+                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WindPtrs wd,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = true;
+    constexpr SasArgs sas{};
+    constexpr WrenchPtrs wr{};
+    constexpr VehiclePtrs vh{};
+    uint32_t policy = 0, interval = single_interval;
+    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
+        policy = block_policy[blockIdx.x];
+        interval = policy_interval[policy];
+    }
+    const float* __restrict__ packed = images + (size_t)policy * image_floats;
+#include "rq_rollout_body.inc"
+}
+
+// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
+template <typename ACTOR>
+static inline void launch_fused_wind_actor(hipStream_t s, const FusedArgs& a) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
+        hipLaunchKernelGGL((k_rollout_fused_wind<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
+                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.wd, a.span);
     }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
@@ -1413,13 +1523,15 @@ hipError_t launch_rollout_fused(hipStream_t s, const FusedArgs& a) {
     case FusedBuild::F16X2:      // the 16-bit actors live in their own translation unit (rq_kernels_16bit.hip: a place for per-build flags)
         return launch_rollout_fused_16bit(s, a, r.family);
     case FusedBuild::F32_LEAN:
-        if (r.vehicle)                     launch_fused_vehicle_actor<ActorF32Lean>(s, a);    // (a vehicle schedule: its own entry point)
+        if (r.wind)                        launch_fused_wind_actor<ActorF32Lean>(s, a);       // (a wind schedule: its own entry point)
+        else if (r.vehicle)                launch_fused_vehicle_actor<ActorF32Lean>(s, a);    // (a vehicle schedule: likewise)
         else if (a.sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a);      // (PLAIN: route_fused allows the stage nowhere else)
         else                               launch_fused_f32_actor<ActorF32Lean>(s, a, r.family);
         break;
     case FusedBuild::F32:
-        if (r.vehicle) launch_fused_vehicle_actor<ActorF32>(s, a);
-        else           launch_fused_f32_actor<ActorF32>(s, a, r.family);
+        if (r.wind)         launch_fused_wind_actor<ActorF32>(s, a);
+        else if (r.vehicle) launch_fused_vehicle_actor<ActorF32>(s, a);
+        else                launch_fused_f32_actor<ActorF32>(s, a, r.family);
         break;
     }
     return hipGetLastError();
@@ -1474,6 +1586,28 @@ template __global__ void k_step_bank_vehicle<false>(Batch, StepCfg, const float*
                                                     float*, const float*, const uint32_t*, WrenchPtrs, VehiclePtrs);
 template __global__ void k_step_bank_vehicle<true>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t, SampleCfg, uint64_t,
                                                    float*, const float*, const uint32_t*, WrenchPtrs, VehiclePtrs);
+
+// ... and for one that carries a wind schedule, alone or beside the other two
+template <bool WRENCH, bool VEHICLE>
+__global__ __launch_bounds__(kBlock) void k_step_bank_wind(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                           float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                           uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                           const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
+                                                           WindPtrs wd) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true, WRENCH, VEHICLE, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                                              weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr, vh,
+                                              wd);
+}
+#define RQ_STEP_BANK_WIND(WR, VH)                                                                                                    \
+    template __global__ void k_step_bank_wind<WR, VH>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t, SampleCfg,   \
+                                                      uint64_t, float*, const float*, const uint32_t*, WrenchPtrs, VehiclePtrs, WindPtrs);
+RQ_STEP_BANK_WIND(false, false)
+RQ_STEP_BANK_WIND(true, false)
+RQ_STEP_BANK_WIND(false, true)
+RQ_STEP_BANK_WIND(true, true)
+#undef RQ_STEP_BANK_WIND
 
 // k_thaw_frozen likewise: an env left frozen starts its next episode with ITS policy's initial state
 #define RQ_THAW_KERNEL k_thaw_frozen_bank

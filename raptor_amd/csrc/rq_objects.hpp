@@ -190,6 +190,7 @@ struct rq_rng {
 
 struct rq_wrench_bank;
 struct rq_vehicle_bank;
+struct rq_wind_bank;
 struct rq_env {
     rq_device* dev = nullptr;
     uint64_t uid = fresh_version();   // what the device's caches know this env by, beside its address
@@ -223,6 +224,11 @@ struct rq_env {
     std::vector<uint32_t> vehicle_ids;
     DeviceBuffer<uint32_t> vehicle_row0;
     uint64_t vehicle_gen = 0;
+    // The wind schedule (rq_env_set_wind_schedule), kept alike.
+    rq_wind_bank* wind = nullptr;
+    std::vector<uint32_t> wind_ids;
+    DeviceBuffer<uint32_t> wind_row0;
+    uint64_t wind_gen = 0;
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
     // epoch-counter bump); one executable graph per distinct argument set: what the nodes carry by value, named once
     struct GraphKey {
@@ -235,11 +241,13 @@ struct rq_env {
         uint32_t interval = 1;                                 // the policy's native interval: the actor nodes of another one are other kernels
         uint64_t wrench_gen = 0;                               // the env's wrench schedule at construction (0: none): the step nodes carry its pointers
         uint64_t vehicle_gen = 0;                              // ... and its vehicle schedule
+        uint64_t wind_gen = 0;                                 // ... and its wind schedule
         bool operator==(const GraphKey& o) const {             // field by field (padding is not compared); cfg is plain floats and words
             return params == o.params && state == o.state && hidden == o.hidden && packed == o.packed && weights == o.weights &&
                    obs == o.obs && flags == o.flags && precision == o.precision && seed == o.seed && sas_mode == o.sas_mode &&
                    sas_seed == o.sas_seed && ls_image == o.ls_image && ref == o.ref && ref_rows == o.ref_rows && row0_at == o.row0_at &&
                    row0_gen == o.row0_gen && interval == o.interval && wrench_gen == o.wrench_gen && vehicle_gen == o.vehicle_gen &&
+                   wind_gen == o.wind_gen &&
                    std::memcmp(&cfg, &o.cfg, sizeof(rq_env_config)) == 0;
         }
     };
@@ -323,6 +331,10 @@ struct rq_wrench_bank : rqh::RowTables {
 // the tables of a vehicle schedule (rq_vehicle_bank_create): `d` is [n_tables * rows][4] row-major, positive factors
 struct rq_vehicle_bank : rqh::RowTables {
     uint32_t attached = 0;              // live envs it is attached to: rq_vehicle_bank_destroy is refused while any
+};
+// the tables of a wind schedule (rq_wind_bank_create): `d` is [n_tables * rows][4] row-major, air velocity and specific drag
+struct rq_wind_bank : rqh::RowTables {
+    uint32_t attached = 0;              // live envs it is attached to: rq_wind_bank_destroy is refused while any
 };
 
 struct rq_policy {
@@ -470,6 +482,10 @@ int wrench_refuses_fused(const char* who, const char* what);
 // cannot fly while one is attached: a bf16 / f16x2 policy, a SampleAndSquash stage, a teacher bank, a wrench schedule beside it.
 int env_vehicle(const char* who, const rq_env* env, rq::VehiclePtrs* vh);
 int vehicle_refuses_fused(const char* who, const char* what);
+// The env's wind schedule likewise; fused mode cannot fly it beside a bf16 / f16x2 policy, a SampleAndSquash stage, a teacher bank or
+// another schedule.
+int env_wind(const char* who, const rq_env* env, rq::WindPtrs* wd);
+int wind_refuses_fused(const char* who, const char* what);
 
 // ---- rq_small_batch.cpp: the small-batch loop (rq_device::mailbox, obs_cache, spec) ----
 void small_batch_setup(rq_device* dev);      // rq_device_create: settings
@@ -554,6 +570,7 @@ struct RolloutFrame {
     uint64_t row0_gen = 0;                                         // a reference bank's rollout: rq_env::row0_gen
     rq::WrenchPtrs wr{};                                           // rows != nullptr: the env carries a wrench schedule (rollout_check)
     rq::VehiclePtrs vh{};                                          // rows != nullptr: the env carries a vehicle schedule (rollout_check)
+    rq::WindPtrs wd{};                                             // rows != nullptr: the env carries a wind schedule (rollout_check)
     rq::Batch b; rq::StepCfg sc; rq::NoiseCfg nc; rq::SampleCfg smp; bool noise;
 };
 // a refusal inside the frame, worded as RQ_REQUIRE words it but begun with the call's own name

@@ -72,6 +72,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WrenchPtrs wr{};
     constexpr bool VEHICLE = false;
     constexpr VehiclePtrs vh{};
+    constexpr bool WIND = false;
+    constexpr WindPtrs wd{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -94,6 +96,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WrenchPtrs wr{};
     constexpr bool VEHICLE = false;
     constexpr VehiclePtrs vh{};
+    constexpr bool WIND = false;
+    constexpr WindPtrs wd{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -116,6 +120,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WrenchPtrs wr{};
     constexpr bool VEHICLE = false;
     constexpr VehiclePtrs vh{};
+    constexpr bool WIND = false;
+    constexpr WindPtrs wd{};
 #include "rq_rollout_body.inc"
 }
 

@@ -2,10 +2,11 @@
 // (TRACK = false), k_rollout_fused_track (TRACK = true, SAS = false) and k_rollout_fused_rate (RATE = true, SAS = false).  Text, not a function: the untracked kernel is compiled from
 // exactly what it was compiled from when the body stood between its braces - its listing does not move when the tracked variant
 // changes - and a __device__ function in between does cost that (the work-group-size folds of a kernel are made before inlining).
-// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, VEHICLE, ACTOR and the
-// names b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, vh, interval, span.
+// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, VEHICLE, WIND, ACTOR and
+// the names b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, vh, wd, interval, span.
 // WRENCH (k_rollout_fused_wrench alone; every other entry point defines it false and an empty wr): the env carries a wrench schedule.
 // VEHICLE (k_rollout_fused_vehicle alone; every other entry point defines it false and an empty vh): the env carries a vehicle schedule.
+// WIND (k_rollout_fused_wind alone; every other entry point defines it false and an empty wd): the env carries a wind schedule.
     // kernel-level timing (rq_device_set_rollout_timing): every wave leaves the wall-clock ticks (constant rate) at which it
     // came in and went out, and its XCD: the eight dies' counters are offset against one another by microseconds, one die's
     // are consistent - the host takes first-in / last-out per die
@@ -65,6 +66,13 @@
     if constexpr (VEHICLE) {
         vh_base = vehicle_base([&](int f) { return field(params, f, ld)[i]; });
         vh_row0 = vh.row0[i];
+    }
+    // WIND: the mass (from the params of this call) and the first row of the env's own table, once per launch
+    [[maybe_unused]] float wd_mass = 0.0f;
+    [[maybe_unused]] uint32_t wd_row0 = 0;
+    if constexpr (WIND) {
+        wd_mass = field(params, RQ_P_MASS, ld)[i];
+        wd_row0 = wd.row0[i];
     }
     const uint8_t last_t_raw = st.last_terminated[i];
     uint8_t last_d = AUTORESET ? (uint8_t)0 : st.last_done[i];       // auto-reset: rebuilt in the epilogue
@@ -193,6 +201,9 @@
         // VEHICLE: likewise this step's 16-byte row of factors, one load; it is consumed just before the env step
         [[maybe_unused]] float vh_row[4];
         if constexpr (VEHICLE) vehicle_row(vh.rows, vh.n_rows, vh_row0, ep_steps, vh_row);
+        // WIND: likewise this step's 16-byte row of air velocity and drag, one load; it is consumed just before the env step
+        [[maybe_unused]] float wd_row[4];
+        if constexpr (WIND) wind_row(wd.rows, wd.n_rows, wd_row0, ep_steps, wd_row);
         observe_head<NOISE>(y, LA01, LA23, nc, seed, epoch0 + t, genv, o);
         if constexpr (TRACK) {
             // the setpoint of this step: the row of the env's own episode step count (lanes are at different rows: per-lane
@@ -260,6 +271,13 @@
         if constexpr (WRENCH) {      // the wrench of this transition: the per-episode base (f6, which the state keeps) + the scaled row
             float w6[6];
             wrench_compose(f6, wr_fs, wr_ts, wr_row, w6);
+            ds = make_disturbance(k, c.gravity, w6);
+        }
+        if constexpr (WIND) {        // the force of this transition: the per-episode base (f6, which the state keeps) + the drag against
+            float w6[6];             // the air at y, the state before the step, held across the RK4 stages
+#pragma unroll
+            for (int j = 0; j < 6; ++j) w6[j] = f6[j];
+            wind_compose(w6, wd_mass, y.V01[0], y.V01[1], y.VW[0], wd_row);
             ds = make_disturbance(k, c.gravity, w6);
         }
         QuadState yn = y;

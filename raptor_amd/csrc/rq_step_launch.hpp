@@ -57,6 +57,14 @@ struct VehiclePtrs {
     uint32_t pad_;
 };
 
+// A wind schedule (rq_env_set_wind_schedule): the bank's tables and the env's per-env first rows (rq_device_math.hpp wind_*).
+struct WindPtrs {
+    const float* rows;        // [n_tables * n_rows][4] row-major: air velocity (world frame, m/s), specific drag (1/s); nullptr = none
+    const uint32_t* row0;     // [ld]: wind_id[i] * n_rows, the first row of env i's table
+    uint32_t n_rows;          // rows of one table
+    uint32_t pad_;
+};
+
 // SampleAndSquash output stage of the actor (rq_policy_set_sample_and_squash): mode = rq_sample_and_squash_mode
 struct SasArgs {
     uint32_t mode;                // RQ_SAS_OFF / RQ_SAS_MEAN / RQ_SAS_SAMPLE
@@ -195,6 +203,7 @@ struct EnvStepLaunch {
     NoiseCfg nc{}; bool noise = false; uint32_t obs_epoch = 0; const uint32_t* obs_epoch_base = nullptr;
     WrenchPtrs wr{};                         // rows set: the env's wrench schedule
     VehiclePtrs vh{};                        // rows set: the env's vehicle schedule (not used: the kernels without it)
+    WindPtrs wd{};                           // rows set: the env's wind schedule (not used: the kernels without it)
     // The thaw of a chained rollout under auto-reset reads b, sc, seed, params, st, hidden, weights and block_policy, and re-samples
     // into next_state.
 };
@@ -202,17 +211,19 @@ struct EnvStepLaunch {
 // Which kernel serves an env step (launch_step switches on the answer): k_step<rollout>, k_step_wrench<rollout>, k_step_bank,
 // k_step_bank_wrench - the kernels there were before a vehicle schedule existed, under their names - and, with a vehicle schedule,
 // k_step_vehicle<rollout, wrench> and k_step_bank_vehicle<wrench>.  A bank's step is a rollout's, in place, without host rows or a
-// folded observation.
+// folded observation.  With a wind schedule (`wind`): k_step_wind<rollout, wrench, vehicle> or k_step_bank_wind<wrench, vehicle>,
+// whichever of the two `family` - what the step would be without the wind - belongs to; vehicle = family is [BANK_]VEHICLE.
 enum class EnvStepFamily { UNSUPPORTED, STEP, WRENCH, VEHICLE, BANK, BANK_WRENCH, BANK_VEHICLE };
-struct EnvStepRoute { EnvStepFamily family; bool rollout, wrench; };      // wrench: VEHICLE's and BANK_VEHICLE's template bool
+// wrench: VEHICLE's and BANK_VEHICLE's template bool
+struct EnvStepRoute { EnvStepFamily family; bool rollout, wrench; bool wind = false; };
 inline EnvStepRoute route_env_step(const EnvStepLaunch& e) {
-    const bool wrench = e.wr.rows != nullptr, vehicle = e.vh.rows != nullptr;
+    const bool wrench = e.wr.rows != nullptr, vehicle = e.vh.rows != nullptr, wind = e.wd.rows != nullptr;
     if (e.block_policy != nullptr) {
         if (!e.rollout || e.next_state != e.state || mailbox_used(e.mb) || e.obs_of_next != nullptr)
-            return {EnvStepFamily::UNSUPPORTED, e.rollout, wrench};
-        return {vehicle ? EnvStepFamily::BANK_VEHICLE : wrench ? EnvStepFamily::BANK_WRENCH : EnvStepFamily::BANK, true, wrench};
+            return {EnvStepFamily::UNSUPPORTED, e.rollout, wrench, false};
+        return {vehicle ? EnvStepFamily::BANK_VEHICLE : wrench ? EnvStepFamily::BANK_WRENCH : EnvStepFamily::BANK, true, wrench, wind};
     }
-    return {vehicle ? EnvStepFamily::VEHICLE : wrench ? EnvStepFamily::WRENCH : EnvStepFamily::STEP, e.rollout, wrench};
+    return {vehicle ? EnvStepFamily::VEHICLE : wrench ? EnvStepFamily::WRENCH : EnvStepFamily::STEP, e.rollout, wrench, wind};
 }
 
 }  // namespace rq

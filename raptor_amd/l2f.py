@@ -37,7 +37,7 @@ from . import _lib
 from ._lib import (ACTION_DIM, OBSERVATION_DIM, PARAM_DIM, STATE_DIM, ROLLOUT_AUTORESET, ROLLOUT_CHAINED,
                    ROLLOUT_FUSED, EnvConfig, RaptorQuadError)
 
-__all__ = ["Device", "Reference", "WrenchBank", "VehicleBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
+__all__ = ["Device", "Reference", "WrenchBank", "VehicleBank", "WindBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
 
 
 class UI:
@@ -258,6 +258,26 @@ class VehicleBank:
         self._fin = weakref.finalize(self, _lib.load().rq_vehicle_bank_destroy, h)
 
 
+class WindBank:
+    """M wind tables of the same length for ``env.set_wind_schedule(bank, ids)``: ``tables`` float32 [M, rows, 4] (or a list of M
+    [rows, 4] tables; ``raptor_amd.winds`` builds them), the air velocity in the world frame (m/s) and the specific drag (1/s).
+    While the bank is attached to an env, every transition of env i is computed with the linear drag against the air of the row of
+    its own episode step count of table ``ids[i]`` (include/raptor_quad.h "Wind schedule").  The tables are copied to ``device``
+    once, here."""
+
+    def __init__(self, device, tables):
+        from . import winds
+        t = winds.check_tables(tables)             # refused before the device is touched
+        h = C.c_void_p()
+        _lib.call("rq_wind_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), C.byref(h))
+        self._h = h
+        self._device = device
+        self.n_tables = int(t.shape[0])
+        self.rows = int(t.shape[1])
+        # (the library refuses to destroy a bank that is still attached to a live env; the envs hold their bank, so it outlives them)
+        self._fin = weakref.finalize(self, _lib.load().rq_wind_bank_destroy, h)
+
+
 def _checked_reference(reference, reference_ids, n_envs):
     """What a rollout's ``reference`` / ``reference_ids`` pair must be, before any library call -> the ids as uint32 (a
     ``ReferenceBank``) or None (a ``Reference``, or no reference); ValueError otherwise."""
@@ -305,6 +325,24 @@ def _checked_vehicle_ids(env, vehicle_ids, wrench_ids, ref_ids, n_envs):
     return check_vehicle_ids(vehicle_ids, schedule[0].n_tables, n_envs)
 
 
+def _checked_wind_ids(env, wind_ids, wrench_ids, vehicle_ids, ref_ids, n_envs):
+    """What ``wind_ids`` of ``PolicyBank.evaluate`` must be, before any library call -> the ids as uint32, or None (none given);
+    ValueError otherwise."""
+    if wind_ids is None:
+        return None
+    schedule = getattr(env, "wind_schedule", None)
+    if schedule is None:
+        raise ValueError("wind_ids name tables of the env's wind schedule: attach one first (env.set_wind_schedule(bank))")
+    if wrench_ids is not None or vehicle_ids is not None:
+        raise ValueError("wind_ids group the tracking error by wind scenario, wrench_ids by disturbance and vehicle_ids by vehicle "
+                         "scenario: give one of them")
+    if ref_ids is not None:
+        raise ValueError("wind_ids group the tracking error by wind scenario and reference_ids by setpoint: give one of them "
+                         "(a single l2f.Reference goes with wind_ids)")
+    from .winds import check_wind_ids
+    return check_wind_ids(wind_ids, schedule[0].n_tables, n_envs)
+
+
 _MODES = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}
 
 
@@ -330,12 +368,14 @@ def _rollout_call(entry, device, env, params, state, actor_handle, ids, rng, n_s
     return _lib.call("rq_rollout_record", *args, traj)
 
 
-def tracking_rmse(env, reference, ref_ids, w_ids, actor_ids, n_actors, v_ids=None):
+def tracking_rmse(env, reference, ref_ids, w_ids, actor_ids, n_actors, v_ids=None, wind_ids=None):
     """``tracking_rmse`` of a bank's closed-loop table, from ``env.tracking_error()`` grouped by actor (policy or teacher): [n_actors,
-    M] over the disturbance scenarios (``w_ids``), the vehicle scenarios (``v_ids``) or the setpoints (``ref_ids`` of a
+    M] over the disturbance scenarios (``w_ids``), the vehicle scenarios (``v_ids``), the wind scenarios (``wind_ids``) or the setpoints (``ref_ids`` of a
     ``ReferenceBank``), [n_actors] on a single ``Reference``."""
     from .tracking import reference_tracking_table
     sum_sq, steps = env.tracking_error()
+    if wind_ids is not None:
+        return reference_tracking_table(sum_sq, steps, wind_ids, env.wind_schedule[0].n_tables, actor_ids, n_actors)
     if v_ids is not None:
         return reference_tracking_table(sum_sq, steps, v_ids, env.vehicle_schedule[0].n_tables, actor_ids, n_actors)
     if w_ids is not None:
@@ -600,6 +640,31 @@ class VectorModule:
             def vehicle_schedule(self):
                 """(bank, ids) of the attached schedule, or None."""
                 return None if self._vehicle is None else (self._vehicle[0], self._vehicle[1].copy())
+
+            # --- wind schedule (air that moves and drags: raptor_amd.winds) ---
+            _wind = None
+
+            def set_wind_schedule(self, bank, ids=None):
+                """Attach ``bank`` (an ``l2f.WindBank``): from now on every transition of env i, in every call that steps this env,
+                is computed with the drag against the air of the row of its episode step count of table ``ids[i]`` ([N] integers,
+                free per env; None: table 0 for every env).  The tables must cover ``episode_step_limit``."""
+                if not isinstance(bank, WindBank):
+                    raise ValueError("bank must be an l2f.WindBank (clear_wind_schedule() detaches)")
+                from .winds import check_wind_ids
+                a = (np.zeros(mod.N_ENVIRONMENTS, np.uint32) if ids is None
+                     else check_wind_ids(ids, bank.n_tables, mod.N_ENVIRONMENTS))
+                _lib.call("rq_env_set_wind_schedule", self._require("environment"), bank._h, a.ctypes.data)
+                self._wind = (bank, a.copy())
+
+            def clear_wind_schedule(self):
+                if self._h is not None:
+                    _lib.call("rq_env_set_wind_schedule", self._h, None, None)
+                self._wind = None
+
+            @property
+            def wind_schedule(self):
+                """(bank, ids) of the attached schedule, or None."""
+                return None if self._wind is None else (self._wind[0], self._wind[1].copy())
 
             def tracking_error(self):
                 """-> (sum_sq [N] float32, steps [N] uint32): per env, the running sum of |p - p_ref|^2 over the steps it took in

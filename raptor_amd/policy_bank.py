@@ -202,7 +202,7 @@ class PolicyBank:
                       reference, ref_ids)
 
     def evaluate(self, vector, device, env, params, state, rng, n_steps, policy_ids=None, mode="fused", autoreset=True,
-                 reference=None, reference_ids=None, wrench_ids=None, vehicle_ids=None):
+                 reference=None, reference_ids=None, wrench_ids=None, vehicle_ids=None, wind_ids=None):
         """The closed-loop evaluation of the whole bank: statistics and hidden state start afresh, one rollout of ``n_steps`` flies
         env i with policy ``policy_ids[i]`` (default: blocks dealt round-robin) at its native interval ->
         ``policy_episode_table`` of what it finished.  With ``reference`` the bank tracks that moving setpoint and the table gains
@@ -213,21 +213,25 @@ class PolicyBank:
         disturbance scenario ``wrench_ids[i]`` of the attached bank (dealt like reference ids) and, on an ``l2f.Reference`` such as
         ``tracking.hold``, ``tracking_rmse`` is [P, M] over the scenarios: P checkpoints x M disturbances in one launch.
         ``vehicle_ids`` likewise name the tables of the env's vehicle schedule (``env.set_vehicle_schedule(bank)``): [P, M] over the
-        vehicle scenarios; ``wrench_ids`` and ``vehicle_ids`` together are refused."""
+        vehicle scenarios, and ``wind_ids`` those of its wind schedule (``env.set_wind_schedule(bank)``): [P, M] over the wind
+        scenarios.  At most one of ``wrench_ids``, ``vehicle_ids`` and ``wind_ids``: two together are refused."""
         ids = block_policy_assignment(vector.N_ENVIRONMENTS, self.n_policies) if policy_ids is None else policy_ids
-        from .l2f import _checked_reference, _checked_vehicle_ids, _checked_wrench_ids, tracking_rmse
+        from .l2f import _checked_reference, _checked_vehicle_ids, _checked_wind_ids, _checked_wrench_ids, tracking_rmse
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
         w_ids = _checked_wrench_ids(env, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
         v_ids = _checked_vehicle_ids(env, vehicle_ids, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
+        a_ids = _checked_wind_ids(env, wind_ids, wrench_ids, vehicle_ids, ref_ids, vector.N_ENVIRONMENTS)
         if w_ids is not None:
             env.set_wrench_schedule(env.wrench_schedule[0], w_ids)
         if v_ids is not None:
             env.set_vehicle_schedule(env.vehicle_schedule[0], v_ids)
+        if a_ids is not None:
+            env.set_wind_schedule(env.wind_schedule[0], a_ids)
         env.reset_statistics()
         self.reset()
         self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
                  reference_ids=reference_ids)
         table = policy_episode_table(env, ids, self.n_policies)
         if reference is not None:
-            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, w_ids, ids, self.n_policies, v_ids)
+            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, w_ids, ids, self.n_policies, v_ids, a_ids)
         return table

@@ -1,0 +1,726 @@
+"""The wind schedule (rq_wind_bank_*, rq_env_set_wind_schedule): a table of air velocity and specific drag per env, honoured by
+everything that steps the env.  The anchor is independent of every new kernel but k_step's: rq_step with a schedule attached against
+the oracle's step fed the state with raptor_amd.winds.compose in its force columns - the existing suite shows the oracle's step and
+k_step agree bit for bit.  Everything else is held to that path, or to the kernels without a schedule, on the bits: no tolerance
+anywhere but in the closed form, whose tolerance is tests/test_wind_cpu.py's."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import raptor_amd.l2f as l2f
+from raptor_amd import _lib, disturbances, probing, tracking, vehicles, winds
+from raptor_amd._lib import RaptorQuadError
+from gpu_common import World
+from rollout_common import (NOISE, OFFSET, Batch, assert_same, assert_same_recording, bank_weights, bits, ids_of, random_table,
+                            roll, snapshot, world_snapshot)
+from test_wind_cpu import check_closed_form, oracle_trace
+
+pytestmark = pytest.mark.gpu
+
+P_MASS, P_ROTOR_XY = 0, slice(4, 6)         # RQ_P_MASS, RQ_P_ROTOR_POS + 0 / + 1
+S_VEL, S_WRENCH = slice(7, 10), slice(21, 27)          # RQ_S_LINEAR_VELOCITY; RQ_S_FORCE, RQ_S_TORQUE
+
+
+def _mixed_ids(n, m, shift=0):
+    """every wave holds all m ids and neighbouring lanes differ"""
+    return ((np.arange(n) * 7 + 1 + shift) % m).astype(np.uint32)
+
+
+def _fed(S, mass, row):
+    """the state with the drag-composed force in its force columns: what the oracle's step is fed"""
+    fed = S.copy()
+    fed[:, S_WRENCH] = winds.compose(S[:, S_WRENCH], mass, S[:, S_VEL], row)
+    return fed
+
+
+# ------------------------------------------------------------------ 1. the anchor -----
+def test_step_with_a_schedule_equals_the_oracle_fed_the_composed_force(device, oracle):
+    n, limit = 70, 12                        # one full wave plus a ragged 6
+    # three tables that between them move all four columns; rows with d = 0 beside w != 0 and rows with w = 0 beside d > 0
+    a = winds.gust(limit, 0.01, (4.0, -2.0, 0.0), 0.02, 0.05, 0.6)
+    a[7:, 3] = 0.0
+    b = winds.ramp(limit, 0.01, (0.0, 3.0, -1.5), 0.0, 0.08, 0.35)
+    c = winds.turbulence(limit, 0.01, (-2.0, 0.5, 1.0), 1.0, 0.05, 0.9, 3)
+    c[0:3, 3] = 0.0
+    tables = np.stack([a, b, c]).astype(np.float32)
+    assert all(len(np.unique(tables[:, :, col])) > 2 for col in range(3)) and len(np.unique(tables[:, :, 3])) > 2
+    assert ((tables[:, :, 3] == 0) & (tables[:, :, 0:3] != 0).any(-1)).any() and ((tables[:, :, 3] > 0) & (tables[:, :, 0:3] == 0).all(-1)).any()
+    ids = _mixed_ids(n, 3)
+    w = World(device, oracle, n, seed=4, domain_randomization=1, episode_step_limit=limit, disturbance_force_std=0.05,
+              disturbance_torque_std=0.02)
+    bank = l2f.WindBank(device, tables)
+    w.env.set_wind_schedule(bank, ids)
+    got = w.env.wind_schedule
+    assert got[0] is bank and np.array_equal(got[1], ids)
+    act = np.random.default_rng(7).uniform(-1, 1, (n, 4)).astype(np.float32)
+    P = w.params.numpy()
+    assert np.array_equal(P, w.P) and len(np.unique(P[:, P_MASS])) > n // 2          # a domain-randomised population
+    composed_differs = 0
+    for doubled in (False, True):
+        if doubled:                          # rq_params_set after attaching is honoured: the mass comes from the call's params
+            P = P.copy()
+            P[:, P_MASS] *= 2
+            w.params.set(P)
+        for t in range(limit):
+            S = w.state.numpy()
+            k = w.env.episode_steps()
+            fed = _fed(S, P[:, P_MASS], tables[ids, np.minimum(k, limit - 1)])
+            composed_differs += int((fed != S).any())
+            ns, r, term = oracle.step(w.cfg, P, fed, act)
+            ended = (term != 0) | (k + 1 >= limit)
+            w.vector.step(device, w.env, w.params, w.state, act, w.next_state, w.rng)
+            out = w.next_state.numpy()
+            assert np.array_equal(bits(out[:, :21]), bits(ns[:, :21])), (doubled, t)
+            assert np.array_equal(bits(out[:, S_WRENCH]), bits(S[:, S_WRENCH])), (doubled, t)          # the state keeps the base
+            assert np.array_equal(bits(w.env.rewards()), bits(r)) and np.array_equal(w.env.terminated(), term), (doubled, t)
+            assert np.array_equal(w.env.done_codes() != 0, ended), (doubled, t)
+            w.state.assign(w.next_state)
+        assert (w.env.finished_counts() >= (2 if doubled else 1)).all()
+    assert composed_differs >= 2 * (limit - 2)
+    # not vacuous the other way: after clear_wind_schedule the plain oracle step matches again and the composed one does not
+    w.env.clear_wind_schedule()
+    assert w.env.wind_schedule is None
+    for t in range(4):
+        w.vector.step(device, w.env, w.params, w.state, act, w.state, w.rng)
+    S = w.state.numpy()
+    ns, _, _ = oracle.step(w.cfg, P, S, act)
+    w.vector.step(device, w.env, w.params, w.state, act, w.next_state, w.rng)
+    assert np.array_equal(bits(w.next_state.numpy()), bits(ns))
+    assert not np.array_equal(ns[:, :21], oracle.step(w.cfg, P, _fed(S, P[:, P_MASS], tables[ids, 4]), act)[0][:, :21])
+
+
+# ------------------------------------------------------------------ 2. the closed form -----
+def test_the_closed_form_on_the_device(device, oracle):
+    """tests/test_wind_cpu.py's loop through rq_step gives the oracle's trace bit for bit, and so the closed form within the
+    tolerance measured there."""
+    n = 4
+    v = l2f.VectorModule(n, 0)
+    rng, env, params, state, nxt = v.VectorRng(), v.VectorEnvironment(), v.VectorParameters(), v.VectorState(), v.VectorState()
+    v.initialize_rng(device, rng, 5)
+    v.initialize_environment(device, env)
+    cfg = env.config
+    cfg.domain_randomization = 0
+    cfg.termination_enabled = 0
+    cfg.disturbance_force_std = 0.0
+    cfg.disturbance_torque_std = 0.0
+    env.config = cfg
+    v.sample_initial_parameters(device, env, params, rng)
+    v.sample_initial_state(device, env, params, state, rng)
+
+    def step(ocfg, P, S, act):
+        assert np.array_equal(bits(params.numpy()), bits(P))
+        state.set(np.ascontiguousarray(S))
+        v.step(device, env, params, state, act, nxt, rng)
+        return nxt.numpy()
+
+    want = oracle_trace(oracle)
+    got = oracle_trace(oracle, step)
+    for g, o, what in zip(got[:3], want[:3], ("wind", "calm", "still air")):
+        assert np.array_equal(bits(g), bits(o)), what
+    check_closed_form(got[0], got[1], got[2], want[3].dt, "device")
+
+
+# ------------------------------------------------------------------ the rollouts' shared shape -----
+N, LIMIT, LAUNCHES = 200, 16, (20, 20)       # four blocks, the last ragged; 40 steps as two launches cross episode ends
+T = sum(LAUNCHES)
+M = 4
+# a velocity threshold that the envs in table 1's storm cross within a few steps (90 m/s^2 from row 3 on: 0.9 m/s per step, far more
+# than the rotors can hold against) and the envs in the mild winds do not
+KW = dict(seed=5, domain_randomization=1, episode_step_limit=LIMIT, termination_linear_velocity=2.5, disturbance_force_std=0.05,
+          disturbance_torque_std=0.02, **NOISE)
+BLOCK_IDS = [2, 0, 2, 1]                     # the policy bank's blocks: non-monotone, policy 2 twice
+RATES = [1, 4, 2]                            # ... and its native intervals
+
+
+def _suite(limit):
+    storm = winds.ramp(limit, 0.01, (60.0, 0.0, 0.0), 0.03, 0.0, 1.5)
+    return np.stack([winds.steady(limit, (3.0, -1.0, 0.5), 0.35), storm, winds.turbulence(limit, 0.01, (0.0, 4.0, 0.0), 2.0, 0.05, 0.5, 1),
+                     winds.still_air(limit, 0.8)]).astype(np.float32)
+
+
+@pytest.fixture(scope="module")
+def suite(device):
+    t = _suite(LIMIT)
+    t.setflags(write=False)
+    return t, l2f.WindBank(device, np.array(t))
+
+
+@pytest.fixture(scope="module")
+def dragless_bank(device):
+    """d = 0 in every row, the air moving all the same"""
+    t = _suite(LIMIT)[:2].copy()
+    t[:, :, 3] = 0.0
+    return l2f.WindBank(device, t)
+
+
+@pytest.fixture(scope="module")
+def setpoints(device):
+    t = np.stack([random_table(LIMIT, 51 + r) for r in range(3)])
+    return t, l2f.Reference(device, np.array(t[1])), l2f.ReferenceBank(device, t)
+
+
+def _reference_kw(setpoints, kind, n=N):
+    _, single, many = setpoints
+    return {"none": {}, "single": dict(reference=single), "bank": dict(reference=many, reference_ids=_mixed_ids(n, 3, 2))}[kind]
+
+
+def _fly_policy(device, oracle, schedule, mode, autoreset, record, ref_kw, interval=1, n=N, launches=LAUNCHES, kw=KW):
+    """a fresh world flown by its own policy -> world, snapshot, recording; schedule: (bank, ids) or None"""
+    w = World(device, oracle, n, **kw)
+    w.policy.native_interval = interval
+    base = w.state.numpy()[:, S_WRENCH]
+    assert (base != 0).all() and not (bits(base) == 0x80000000).any()          # a nonzero base force, and no -0
+    if schedule is not None:
+        w.env.set_wind_schedule(*schedule)
+    tr = w.vector.Trajectory(w.env, sum(launches)) if record else None
+    for c in launches:
+        roll(w, c, mode, autoreset, trajectory=tr, **ref_kw)
+    return w, world_snapshot(w), tr.numpy() if record else None
+
+
+def _fly_policy_bank(device, oracle, weights, schedule, mode, autoreset, record, ref_kw, launches=LAUNCHES):
+    from raptor_amd.policy_bank import PolicyBank
+    w = World(device, oracle, N, **KW)
+    pb = PolicyBank(device, bank_weights(weights, 3), native_interval=RATES)
+    pids = ids_of(BLOCK_IDS, N)
+    if schedule is not None:
+        w.env.set_wind_schedule(*schedule)
+    tr = w.vector.Trajectory(w.env, sum(launches)) if record else None
+    for c in launches:
+        pb.fly(w.vector, device, w.env, w.params, w.state, w.rng, c, pids, mode, autoreset, trajectory=tr, **ref_kw)
+    return w, snapshot(w, pb.hidden(N)), tr.numpy() if record else None
+
+
+def _fly(device, oracle, weights, setpoints, call, schedule, mode, autoreset, launches=LAUNCHES):
+    if call.startswith("policy_bank"):
+        ref_kw = _reference_kw(setpoints, "bank") if call.endswith("refs") else {}
+        return _fly_policy_bank(device, oracle, weights, schedule, mode, autoreset, True, ref_kw, launches)
+    ref_kw = _reference_kw(setpoints, "bank") if call == "track_refs" else {}
+    return _fly_policy(device, oracle, schedule, mode, autoreset, True, ref_kw, launches=launches)
+
+
+CALLS = ["rollout", "track_refs", "policy_bank", "policy_bank_refs"]
+
+
+# ------------------------------------------------------------------ 3. no drag is no schedule -----
+@pytest.mark.parametrize("autoreset", [True, False])
+@pytest.mark.parametrize("mode", ["fused", "chained"])
+@pytest.mark.parametrize("call", CALLS)
+def test_a_bank_without_drag_is_no_schedule(device, oracle, weights, dragless_bank, setpoints, call, mode, autoreset):
+    """crosses the schedule's kernels with the ones that existed before it: snapshot and recording, bit for bit.  b + (0 * u) keeps
+    b's bits unless b is -0: the worlds' sampled base forces are nonzero (asserted where the worlds are made, and below on what the
+    flight leaves behind)"""
+    ids = _mixed_ids(N, 2)
+    out = [_fly(device, oracle, weights, setpoints, call, schedule, mode, autoreset)[1:] for schedule in ((dragless_bank, ids), None)]
+    what = f"{call} {mode} autoreset={autoreset}"
+    left = out[1][0]["state"][:, S_WRENCH]
+    assert (left != 0).all() and not (bits(left) == 0x80000000).any()
+    assert_same(out[0][0], out[1][0], what=what)
+    assert_same_recording(out[0][1], out[1][1], what)
+    assert out[0][0]["fin_counts"].min() >= 1 and out[0][0]["epoch"][0] == T
+
+
+# ------------------------------------------------------------------ 4. fused = chained = the step-by-step loop -----
+@pytest.mark.parametrize("autoreset", [True, False])
+@pytest.mark.parametrize("call", CALLS)
+def test_fused_equals_chained_equals_the_loop(device, oracle, weights, suite, setpoints, call, autoreset):
+    tables, bank = suite
+    ids = _mixed_ids(N, M)
+    what = f"{call} autoreset={autoreset}"
+    wf, sf, rf = _fly(device, oracle, weights, setpoints, call, (bank, ids), "fused", autoreset)
+    wc, sc, rc = _fly(device, oracle, weights, setpoints, call, (bank, ids), "chained", autoreset)
+    assert_same(sf, sc, what=what)           # state, hidden state, statistics, finished-episode records, done codes, tracking sums, rng epoch
+    assert_same_recording(rf, rc, what)
+    assert sf["epoch"][0] == T
+    # two launches joined equal one
+    w1, s1, r1 = _fly(device, oracle, weights, setpoints, call, (bank, ids), "fused", autoreset, launches=(T,))
+    assert_same(sf, s1, what=what + ", one launch")
+    assert_same_recording(rf, r1, what + ", one launch")
+    # not vacuous: the storm ends episodes early for some envs and not for others, and lanes of one wave sit at different rows
+    terminated = sf["fin_terminated"] > 0
+    print(f"\n[{what}] envs with a terminated episode: {int(terminated.sum())} of {N}; per table {[int(terminated[ids == r].sum()) for r in range(M)]}")
+    assert terminated.any() and not terminated.all()
+    if autoreset:
+        assert len(np.unique(sf["steps"][:64])) >= 3, "one wave's lanes were never at different rows"
+    plain = _fly(device, oracle, weights, setpoints, call, None, "fused", autoreset)[1]
+    assert not np.array_equal(plain["state"], sf["state"])
+    if call.startswith("policy_bank"):
+        return                               # (a bank's flight is held to single policies in test_policy_bank_evaluate_by_wind)
+    loop = _engine_loop(device, oracle, suite, setpoints, ids, "bank" if call == "track_refs" else "none")
+    first_end = np.argmax(loop["done"] != 0, axis=0)            # every episode ends within LIMIT < T steps
+    assert (loop["done"][first_end, np.arange(N)] != 0).all() and first_end.max() < LIMIT
+    assert len(np.unique(first_end)) >= 3
+    in_first = np.arange(T)[:, None] <= first_end[None, :]      # [T, N]: the transitions of each env's first episode
+    for k in ("obs", "act", "rew", "done"):
+        assert np.array_equal(bits(rf[k][in_first]), bits(loop[k][in_first])), f"{what}: the loop's {k}"
+    at_end = (first_end, np.arange(N))
+    if not autoreset:                        # the env froze where its first episode ended: the loop's values of that step
+        assert sf["frozen"].all()
+        for k, lk in (("state", "state"), ("hidden", "hidden"), ("fin_returns", "fin_returns"), ("fin_lengths", "fin_lengths"),
+                      ("fin_terminated", "fin_terminated"), ("rewards", "rew")):
+            assert np.array_equal(bits(sf[k]), bits(loop[lk][at_end])), f"{what}: the loop's {k} at the episode end"
+    else:
+        assert (sf["fin_counts"] >= 2).all()
+
+
+_engine_loops = {}
+
+
+def _engine_loop(device, oracle, suite, setpoints, ids, ref):
+    """The host loop that composes the drag itself, no schedule attached: observe -> (the setpoint's row off the observation, on the
+    host) -> evaluate_step -> winds.compose into the state's force columns -> rq_step (held to the oracle's step on the same inputs,
+    bit for bit) -> the base force back -> assign, for T steps; per step what a recording holds and what a rollout leaves behind.
+    The API has no per-env reset, so the loop is the yardstick of every env's FIRST episode: what it does after an env's episode end
+    is not looked at."""
+    if ref not in _engine_loops:
+        tables, bank = suite
+        u = World(device, oracle, N, **KW)
+        P = u.params.numpy()
+        obs = np.zeros((N, 26), np.float32)
+        rids = {"none": None, "bank": _mixed_ids(N, 3, 2)}[ref]
+        out = dict(obs=[], act=[], rew=[], done=[], state=[], hidden=[], fin_returns=[], fin_lengths=[], fin_terminated=[])
+        for t in range(T):
+            u.vector.observe(device, u.env, u.params, u.state, obs, u.rng)
+            o = obs[:, :22].copy()
+            k = np.minimum(u.env.episode_steps(), LIMIT - 1)
+            if rids is not None:
+                row = setpoints[0][rids, k]
+                o[:, 0:3] -= row[:, 0:3]
+                o[:, 12:15] -= row[:, 3:6]
+            a = u.policy.evaluate_step(o)
+            S = u.state.numpy()
+            fed = _fed(S, P[:, P_MASS], tables[ids, k])
+            ns, r, term = oracle.step(u.cfg, P, fed, a)
+            u.state.set(fed)                 # the caller who writes the force into the state before the step
+            u.vector.step(device, u.env, u.params, u.state, a, u.next_state, u.rng)
+            got = u.next_state.numpy()
+            assert np.array_equal(bits(got[:, :21]), bits(ns[:, :21])) and np.array_equal(bits(u.env.rewards()), bits(r)), t
+            got[:, S_WRENCH] = S[:, S_WRENCH]                     # the state keeps the per-episode base
+            u.state.set(got)
+            for key, x in (("obs", o), ("act", a), ("rew", r), ("done", u.env.done_codes()), ("state", got),
+                           ("hidden", u.policy.hidden_state(N)), ("fin_returns", u.env.finished_returns()),
+                           ("fin_lengths", u.env.finished_lengths()), ("fin_terminated", u.env.finished_terminated())):
+                out[key].append(np.array(x))
+        _engine_loops[ref] = {k: np.stack(v) for k, v in out.items()}
+    return _engine_loops[ref]
+
+
+def test_freeze_then_thaw(device, oracle, suite):
+    """a rollout without auto-reset freezes every env at its episode end (a frozen env reads nothing), one with auto-reset thaws them:
+    fused = chained through both, and rq_env_reset_statistics restarts the table at row 0"""
+    tables, bank = suite
+    n = 70
+    ids = _mixed_ids(n, M)
+    snaps = []
+    for mode in ("fused", "chained"):
+        w = World(device, oracle, n, **KW)
+        w.env.set_wind_schedule(bank, ids)
+        roll(w, LIMIT + 2, mode, False)
+        frozen = world_snapshot(w)
+        assert frozen["frozen"].all() and (frozen["steps"] == 0).all()
+        roll(w, 5, mode, False)              # later steps do not touch a frozen env
+        after = world_snapshot(w)
+        assert_same(after, frozen, skip=("epoch", "done"), what=f"frozen, {mode}")
+        assert (after["done"] == 4).all()
+        roll(w, 10, mode, True)              # thawed: a new episode, the table from row 0
+        snaps.append(world_snapshot(w))
+    assert_same(snaps[0], snaps[1], what="freeze then thaw")
+    assert not snaps[0]["frozen"].any()
+    # reset_statistics zeroes the step count: the next step reads row 0 again
+    u = World(device, oracle, n, seed=6, domain_randomization=1, episode_step_limit=LIMIT)
+    restart = np.stack([winds.gust(LIMIT, 0.01, (5.0, 0.0, 0.0), 0.0, 0.04, 0.7), winds.ramp(LIMIT, 0.01, (0.0, -6.0, 2.0), 0.04, 0.0, 0.4)])
+    rid = _mixed_ids(n, 2)
+    u.env.set_wind_schedule(l2f.WindBank(device, restart), rid)
+    act = np.random.default_rng(9).uniform(-1, 1, (n, 4)).astype(np.float32)
+    for _ in range(4):
+        u.vector.step(device, u.env, u.params, u.state, act, u.state, u.rng)
+    assert (u.env.episode_steps() == 4).all()
+    u.env.reset_statistics()
+    assert (u.env.episode_steps() == 0).all()
+    S, P = u.state.numpy(), u.params.numpy()
+    ns = {k: oracle.step(u.cfg, P, _fed(S, P[:, P_MASS], restart[rid, k]), act)[0] for k in (0, 4)}
+    u.vector.step(device, u.env, u.params, u.state, act, u.next_state, u.rng)
+    out = u.next_state.numpy()
+    assert np.array_equal(bits(out[:, :21]), bits(ns[0][:, :21])) and (out[:, :21] != ns[4][:, :21]).any(axis=1).all()
+
+
+# ------------------------------------------------------------------ 6. other shapes -----
+@pytest.mark.parametrize("n", [8, 65])
+def test_small_batches(device, oracle, suite, n):
+    tables, bank = suite
+    ids = _mixed_ids(n, M)
+    out = [_fly_policy(device, oracle, (bank, ids), mode, True, True, {}, n=n)[1:] for mode in ("fused", "chained")]
+    assert_same(out[0][0], out[1][0], what=f"{n} envs")
+    assert_same_recording(out[0][1], out[1][1], f"{n} envs")
+    assert out[0][0]["fin_counts"].min() >= 2
+
+
+def test_native_interval_four(device, oracle, suite):
+    tables, bank = suite
+    ids = _mixed_ids(N, M)
+    out = [_fly_policy(device, oracle, (bank, ids), mode, True, True, {}, interval=4)[1:] for mode in ("fused", "chained")]
+    assert_same(out[0][0], out[1][0], what="interval 4")
+    assert_same_recording(out[0][1], out[1][1], "interval 4")
+    one = _fly_policy(device, oracle, (bank, ids), "fused", True, True, {}, interval=1)[1]
+    assert not np.array_equal(one["state"], out[0][0]["state"])
+
+
+def test_the_two_wave_build(device):
+    """beyond 65 536 envs the fused kernel is the 256-register build: fused = chained, bit for bit"""
+    from raptor_amd.foundation_policy import Raptor
+    n, limit, steps = 65605, 4, 6            # (the second episode is at row 2 when the launch ends)
+    bank = l2f.WindBank(device, _suite(limit))
+    ids = _mixed_ids(n, M)
+    snaps = []
+    for mode in ("fused", "chained"):
+        b = Batch(device, n, limit=limit, noise=True)
+        b.env.set_wind_schedule(bank, ids)
+        pol = Raptor(device)
+        b.fly(pol, steps, mode, True)
+        snaps.append(snapshot(b, pol.hidden_state(n)))
+    assert_same(snaps[0], snaps[1], what="65 605 envs")
+    assert snaps[0]["fin_counts"].min() >= 1
+    plain = Batch(device, n, limit=limit, noise=True)
+    pol = Raptor(device)
+    plain.fly(pol, steps, "fused", True)
+    assert not np.array_equal(snapshot(plain, pol.hidden_state(n))["state"], snaps[0]["state"])
+
+
+# ------------------------------------------------------------------ 7. all three schedules -----
+def test_all_three_schedules_chained_equal_the_loop_that_composes_them(device, oracle, suite):
+    """a vehicle, a relative wrench and a wind schedule on one env, chained: the host loop feeds the oracle the vehicle-composed params
+    and a force composed wrench-then-wind with the step's EFFECTIVE mass; fused is refused with "chained" in the message"""
+    tables, bank = suite
+    n, steps = 70, 12
+    gusts = np.stack([disturbances.calm(LIMIT), disturbances.poke(LIMIT, (0.4, -0.3, 0.1), 3, steps=5),
+                      disturbances.torque_kick(LIMIT, (0.02, -0.03, 0.01), 5) + disturbances.payload(LIMIT, 0.25, 2)]).astype(np.float32)
+    cars = np.stack([vehicles.nominal(LIMIT), vehicles.payload_pickup(LIMIT, 3, 1.6, 1.2), vehicles.battery_sag(LIMIT, 2, 10, 0.8)])
+    wbank, vbank = l2f.WrenchBank(device, gusts, "relative"), l2f.VehicleBank(device, cars)
+    aids, wids, vids = _mixed_ids(n, M), _mixed_ids(n, 3, 1), _mixed_ids(n, 3, 2)
+    calm_storm = np.array(tables)
+    calm_storm[1] = winds.steady(LIMIT, (-4.0, 2.0, 1.0), 0.6)          # (no storm here: the envs are compared while they live)
+    abank = l2f.WindBank(device, calm_storm)
+    cfg = dict(seed=4, domain_randomization=1, episode_step_limit=LIMIT, disturbance_force_std=0.05, disturbance_torque_std=0.02, **NOISE)
+    w = World(device, oracle, n, **cfg)
+    w.env.set_vehicle_schedule(vbank, vids)
+    w.env.set_wrench_schedule(wbank, wids)
+    w.env.set_wind_schedule(abank, aids)
+    tr = w.vector.Trajectory(w.env, steps)
+    before = world_snapshot(w)
+    for record in (None, tr):
+        with pytest.raises(RaptorQuadError, match="chained"):
+            roll(w, steps, "fused", True, trajectory=record)
+    assert_same(world_snapshot(w), before, what="three schedules, fused refused")
+    assert w.rng.epoch == 0 and len(tr) == 0
+    roll(w, steps, "chained", False, trajectory=tr)
+    rec = tr.numpy()
+    # the loop: the oracle alone steps, the engine observes and evaluates the policy
+    u = World(device, oracle, n, **cfg)
+    P = u.params.numpy()
+    obs = np.zeros((n, 26), np.float32)
+    live = np.ones(n, bool)
+    differs = 0
+    for t in range(steps):
+        u.vector.observe(device, u.env, u.params, u.state, obs, u.rng)
+        o = np.ascontiguousarray(obs[:, :22])
+        a = u.policy.evaluate_step(o)
+        S = u.state.numpy()
+        k = np.full(n, t)                    # every env compared is in its first episode: its step count is the step
+        Pe = vehicles.compose(P, cars[vids, k])
+        fed = S.copy()
+        fed[:, S_WRENCH] = disturbances.compose(S[:, S_WRENCH], Pe[:, P_MASS], u.cfg.gravity, P[:, P_ROTOR_XY], gusts[wids, k])
+        fed[:, S_WRENCH] = winds.compose(fed[:, S_WRENCH], Pe[:, P_MASS], S[:, S_VEL], calm_storm[aids, k])
+        base_mass = S.copy()
+        base_mass[:, S_WRENCH] = disturbances.compose(S[:, S_WRENCH], Pe[:, P_MASS], u.cfg.gravity, P[:, P_ROTOR_XY], gusts[wids, k])
+        base_mass[:, S_WRENCH] = winds.compose(base_mass[:, S_WRENCH], P[:, P_MASS], S[:, S_VEL], calm_storm[aids, k])
+        differs += int((fed != base_mass).any())
+        ns, r, term = oracle.step(u.cfg, Pe, fed, a)
+        ns[:, S_WRENCH] = S[:, S_WRENCH]                     # the state keeps the per-episode base
+        assert np.array_equal(bits(o[live]), bits(rec["obs"][t][live])) and np.array_equal(bits(a[live]), bits(rec["act"][t][live])), t
+        assert np.array_equal(bits(r[live]), bits(rec["rew"][t][live])), t
+        assert np.array_equal((term != 0)[live], (rec["done"][t] == 1)[live]), t
+        u.state.set(ns)                      # the oracle's state goes on
+        live &= rec["done"][t] == 0
+    assert differs >= 3 and live.sum() >= n // 2
+    assert np.array_equal(bits(w.state.numpy()[live]), bits(u.state.numpy()[live]))
+
+
+# ------------------------------------------------------------------ 8. refusals -----
+def _teachers(device, K=5):
+    from raptor_amd.teachers import TeacherBank, layers_parameter_count
+    g = np.random.default_rng(2)
+    widths = [32, 16]
+    W = np.empty((K, layers_parameter_count(22, widths)), np.float32)
+    for k in range(K):
+        parts, prev = [], 22
+        for h in widths + [4]:
+            parts += [g.standard_normal(h * prev) * 0.2 / np.sqrt(prev), g.standard_normal(h) * 0.1]
+            prev = h
+        W[k] = np.concatenate(parts).astype(np.float32)
+    return TeacherBank.from_layers(device, W, 22, widths, "tanh", "identity", "fp32")
+
+
+def test_refusals_leave_everything_untouched(device, oracle, weights, suite):
+    from raptor_amd.policy_bank import PolicyBank
+    tables, bank = suite
+    n = 128
+    ids = _mixed_ids(n, M)
+    pids = ids_of([1, 0], n)
+    teachers = _teachers(device, 2)
+    W = bank_weights(weights, 2)
+
+    def world():
+        w = World(device, oracle, n, **KW)
+        return w, PolicyBank(device, W), w.vector.Trajectory(w.env, 30)
+
+    a, pb, tr = world()
+    c, pb_c, tr_c = world()                  # the twin that never carries a schedule
+    for w, p, t in ((a, pb, tr), (c, pb_c, tr_c)):
+        roll(w, 3, "fused", True, trajectory=t)
+        p.fly(w.vector, device, w.env, w.params, w.state, w.rng, 2, pids)
+    a.env.set_wind_schedule(bank, ids)
+
+    def look():
+        return dict(world_snapshot(a), bank_hidden=pb.hidden(n), recorded=np.full(n, len(tr)), recording=tr.numpy()["obs"].transpose(1, 0, 2))
+
+    before, epoch = look(), a.rng.epoch
+    assert epoch == 5 and len(tr) == 3
+    act = np.zeros((n, 4), np.float32)
+    calls = {
+        "step": lambda w, p, t, mode: w.vector.step(device, w.env, w.params, w.state, act, w.state, w.rng),
+        "rollout": lambda w, p, t, mode: roll(w, 2, mode, True),
+        "record": lambda w, p, t, mode: roll(w, 2, mode, True, trajectory=t),
+        "policies": lambda w, p, t, mode: p.fly(w.vector, device, w.env, w.params, w.state, w.rng, 2, pids, mode, True),
+        "teachers": lambda w, p, t, mode: teachers.fly(w.vector, device, w.env, w.params, w.state, w.rng, 2, pids, mode, True),
+    }
+
+    def refused(what, words, call, mode="chained"):
+        with pytest.raises(RaptorQuadError) as e:
+            calls[call](a, pb, tr, mode)
+        assert words in str(e.value), (what, e.value)
+        assert_same(look(), before, what=what)
+        assert a.rng.epoch == epoch, what
+
+    # the limit raised after attaching: the bank no longer covers an episode, and every call that steps says so
+    cfg = a.env.config
+    cfg.episode_step_limit = LIMIT + 1
+    a.env.config = cfg
+    for call in calls:
+        for mode in (("chained",) if call == "step" else ("fused", "chained")):
+            if (call, mode) != ("teachers", "fused"):
+                refused(f"short bank, {call} {mode}", "wind schedule has fewer rows (16) than episode_step_limit (17)", call, mode)
+    cfg.episode_step_limit = LIMIT
+    a.env.config = cfg
+    # fused mode with what the schedule's fused kernel is not taught: refused naming "chained", nothing runs chained instead
+    for precision in ("bf16", "f16x2"):
+        a.policy.set_precision(precision)
+        refused(f"fused {precision}", "chained", "rollout", "fused")
+        refused(f"fused {precision} recorded", "wind schedule, which the fused kernel of a bf16 / f16x2 policy", "record", "fused")
+    a.policy.set_precision("fp32")
+    a.policy.set_sample_and_squash("mean")
+    refused("fused SampleAndSquash", "SampleAndSquash", "rollout", "fused")
+    refused("fused SampleAndSquash", "chained", "record", "fused")
+    a.policy.set_sample_and_squash("off")
+    refused("fused teachers", "a teacher bank", "teachers", "fused")
+    refused("fused teachers", "chained", "teachers", "fused")
+    a.env.set_wrench_schedule(l2f.WrenchBank(device, [disturbances.calm(LIMIT)]))
+    for call in ("rollout", "record", "policies"):
+        refused(f"fused {call} with a wrench schedule too", "wind schedule, which the fused kernel of an env that carries a wrench schedule too", call, "fused")
+        refused(f"fused {call} with a wrench schedule too", "chained", call, "fused")
+    a.env.clear_wrench_schedule()
+    a.env.set_vehicle_schedule(l2f.VehicleBank(device, [vehicles.nominal(LIMIT)]))
+    for call in ("rollout", "record", "policies"):
+        refused(f"fused {call} with a vehicle schedule too", "wind schedule, which the fused kernel of an env that carries a vehicle schedule too", call, "fused")
+        refused(f"fused {call} with a vehicle schedule too", "chained", call, "fused")
+    a.env.clear_vehicle_schedule()
+    # creation: what rq_wind_bank_create refuses (the Python checks stood aside)
+    rows = np.array(tables[:1])
+    out = C.c_void_p()
+    for value, col, words in ((np.nan, 1, "non-finite entry"), (np.inf, 3, "non-finite entry"), (-0.5, 3, "negative drag")):
+        bad = rows.copy()
+        bad[0, 2, col] = value
+        with pytest.raises(RaptorQuadError) as e:
+            _lib.call("rq_wind_bank_create", device._h, _lib.fptr(bad), 1, LIMIT, C.byref(out))
+        assert words in str(e.value) and f"table 0, row 2, column {col}" in str(e.value)
+    for nt, nr in ((0, LIMIT), (1, 0)):
+        with pytest.raises(RaptorQuadError, match="at least one"):
+            _lib.call("rq_wind_bank_create", device._h, _lib.fptr(rows), nt, nr, C.byref(out))
+    # a bank of another rq_device; an id outside the bank; destroying an attached bank
+    other = l2f.WindBank(l2f.Device(0), np.array(tables))
+    with pytest.raises(RaptorQuadError) as e:
+        a.env.set_wind_schedule(other, ids)
+    assert e.value.status == -5 and "another device" in str(e.value)
+    far = ids.copy()
+    far[77] = M
+    with pytest.raises(RaptorQuadError) as e:
+        _lib.call("rq_env_set_wind_schedule", a.env._h, bank._h, far.ctypes.data)
+    assert "env 77 names table 4 of a bank of 4" in str(e.value)
+    with pytest.raises(RaptorQuadError) as e:
+        _lib.call("rq_wind_bank_destroy", bank._h)
+    assert "attached to" in str(e.value)
+    got, back = C.c_void_p(), np.zeros(n, np.uint32)
+    _lib.call("rq_env_get_wind_schedule", a.env._h, C.byref(got), back.ctypes.data)
+    assert got.value == bank._h.value and np.array_equal(back, ids)          # still attached, with the ids it was attached with
+    assert_same(look(), before, what="after the refusals")
+    # detached, every one of those calls works again and gives what an env that never carried a schedule gives
+    a.env.clear_wind_schedule()
+    _lib.call("rq_env_get_wind_schedule", a.env._h, C.byref(got), None)
+    assert not got.value
+    for w, p, t in ((a, pb, tr), (c, pb_c, tr_c)):
+        for precision, sas, mode in (("bf16", "off", "fused"), ("fp32", "mean", "fused"), ("fp32", "off", "chained")):
+            w.policy.set_precision(precision)
+            w.policy.set_sample_and_squash(sas)
+            calls["rollout"](w, p, t, mode)
+            calls["record"](w, p, t, mode)
+        w.policy.set_sample_and_squash("off")
+        calls["step"](w, p, t, "chained")
+        calls["policies"](w, p, t, "fused")
+        calls["teachers"](w, p, t, "fused")
+    assert_same(dict(world_snapshot(a), bank_hidden=pb.hidden(n)), dict(world_snapshot(c), bank_hidden=pb_c.hidden(n)),
+                what="after clear_wind_schedule")
+    assert_same_recording(tr.numpy(), tr_c.numpy(), "after clear_wind_schedule", frozen_too=True)
+    # a bank is destroyed once nothing carries it
+    solo = l2f.WindBank(device, [winds.calm(LIMIT)])
+    d = World(device, oracle, 8, **KW)
+    d.env.set_wind_schedule(solo)
+    with pytest.raises(RaptorQuadError):
+        _lib.call("rq_wind_bank_destroy", solo._h)
+    d.env.clear_wind_schedule()
+    solo._fin()                              # destroys the bank: no longer attached
+
+
+# ------------------------------------------------------------------ 9. a teacher bank -----
+def test_a_teacher_bank_chained(device, oracle, suite):
+    """rq_rollout_teachers in chained mode on a wind-carrying env equals observe -> rq_teacher_bank_evaluate -> step -> assign over a
+    window without episode ends of the envs compared; fused is refused naming "chained\""""
+    K = 5
+    teachers = _teachers(device, K)
+    n, steps = 70, 12
+    tables, bank = suite
+    ids = _mixed_ids(n, M)
+    tids = (np.arange(n) % K).astype(np.uint32)
+    cfg = dict(seed=3, domain_randomization=1, episode_step_limit=LIMIT, **NOISE)
+    w = World(device, oracle, n, **cfg)
+    w.env.set_wind_schedule(bank, ids)
+    tr = w.vector.Trajectory(w.env, steps)
+    with pytest.raises(RaptorQuadError, match="chained"):
+        teachers.fly(w.vector, device, w.env, w.params, w.state, w.rng, steps, tids, "fused", False, trajectory=tr)
+    assert w.rng.epoch == 0 and len(tr) == 0
+    teachers.fly(w.vector, device, w.env, w.params, w.state, w.rng, steps, tids, "chained", False, trajectory=tr)
+    rec = tr.numpy()
+    u = World(device, oracle, n, **cfg)
+    u.env.set_wind_schedule(bank, ids)
+    obs = np.zeros((n, 26), np.float32)
+    live = np.ones(n, bool)
+    for t in range(steps):
+        u.vector.observe(device, u.env, u.params, u.state, obs, u.rng)
+        o = np.ascontiguousarray(obs[:, :22])
+        a = teachers.evaluate(o, tids)
+        assert np.array_equal(bits(o[live]), bits(rec["obs"][t][live])) and np.array_equal(bits(a[live]), bits(rec["act"][t][live])), t
+        u.vector.step(device, u.env, u.params, u.state, a, u.next_state, u.rng)
+        u.state.assign(u.next_state)
+        assert np.array_equal(bits(u.env.rewards()[live]), bits(rec["rew"][t][live])), t
+        assert np.array_equal(u.env.done_codes()[live], rec["done"][t][live]), t
+        live &= rec["done"][t] == 0
+    assert live.sum() >= n // 2
+    calm = World(device, oracle, n, **cfg)
+    teachers.fly(calm.vector, device, calm.env, calm.params, calm.state, calm.rng, steps, tids, "chained", False)
+    assert not np.array_equal(snapshot(calm)["state"], snapshot(w)["state"])
+
+
+# ------------------------------------------------------------------ 10. graph replay -----
+def test_graph_replay_follows_the_schedule(device, oracle):
+    """From 25 steps on the chained mode replays a cached hipGraph whose step nodes carry the schedule's pointers: attaching other
+    ids, detaching and attaching again must not fly a graph built for another schedule"""
+    n, limit = 70, 30
+    kw = dict(seed=6, domain_randomization=1, episode_step_limit=limit)
+    bank = l2f.WindBank(device, np.delete(_suite(limit), 1, axis=0))
+    a, fresh = World(device, oracle, n, **kw), World(device, oracle, n, **kw)       # `fresh`: the same history, never through a graph
+    states = []
+    for shift in (0, 1, None, 0):
+        for w in (a, fresh):
+            if shift is None:
+                w.env.clear_wind_schedule()
+            else:
+                w.env.set_wind_schedule(bank, _mixed_ids(n, 3, shift))
+        roll(a, 27, "chained")
+        roll(fresh, 27, "fused")
+        assert_same(world_snapshot(a), world_snapshot(fresh), what=f"shift {shift}")
+        states.append(a.state.numpy())
+    stale = World(device, oracle, n, **kw)
+    stale.env.set_wind_schedule(bank, _mixed_ids(n, 3, 0))
+    for _ in range(2):
+        roll(stale, 27, "fused")
+    assert not np.array_equal(stale.state.numpy(), states[1])
+
+
+# ------------------------------------------------------------------ 11. PolicyBank.evaluate(wind_ids=) -----
+@pytest.mark.parametrize("mode", ["fused", "chained"])
+def test_policy_bank_evaluate_by_wind(device, weights, suite, mode):
+    """tracking_rmse is [P, M]; each cell is what a single Raptor flies on that scenario's envs alone (the same global env ids)"""
+    from raptor_amd.foundation_policy import Raptor
+    from raptor_amd.policy_bank import PolicyBank
+    tables, bank = suite
+    n, Pn, steps = 128, 2, 40
+    W = bank_weights(weights, Pn)
+    pids = ids_of([1, 0], n)
+    aids = np.tile(np.repeat(np.arange(M, dtype=np.uint32), 64 // M), n // 64)          # runs of 16 envs per scenario inside a block
+    hold = l2f.Reference(device, tracking.hold(LIMIT))
+    whole = Batch(device, n, limit=LIMIT, noise=True, via="fly")
+    whole.env.set_wind_schedule(bank)
+    pb = PolicyBank(device, W)
+    table = pb.evaluate(whole.vector, device, whole.env, whole.params, whole.state, whole.rng, steps, pids, mode=mode, reference=hold,
+                        wind_ids=aids)
+    assert np.array_equal(whole.env.wind_schedule[1], aids)
+    rmse = np.asarray(table["tracking_rmse"])
+    assert rmse.shape == (Pn, M) and np.isfinite(rmse).all() and len(np.unique(rmse)) == Pn * M
+    sq, cnt = whole.env.tracking_error()
+    for lo in range(0, n, 16):
+        p, m = int(pids[lo]), int(aids[lo])
+        b = Batch(device, 16, offset=OFFSET + lo, limit=LIMIT, noise=True)
+        b.env.set_wind_schedule(bank, np.full(16, m, np.uint32))
+        b.fly(Raptor(device, weights=W[p]), steps, mode, True, ref=hold)
+        bsq, bcnt = b.env.tracking_error()
+        assert np.array_equal(bits(bsq), bits(sq[lo:lo + 16])) and np.array_equal(bcnt, cnt[lo:lo + 16]), (lo, p, m)
+        assert np.isclose(np.sqrt(bsq.astype(np.float64).sum() / bcnt.sum()), rmse[p, m], rtol=1e-12, atol=0), (lo, p, m)
+    whole.env.set_wrench_schedule(l2f.WrenchBank(device, [disturbances.calm(LIMIT)]))
+    whole.env.set_vehicle_schedule(l2f.VehicleBank(device, [vehicles.nominal(LIMIT)]))
+    for kw in (dict(wrench_ids=np.zeros(n, np.uint32)), dict(vehicle_ids=np.zeros(n, np.uint32))):
+        with pytest.raises(ValueError, match="give one of them"):
+            pb.evaluate(whole.vector, device, whole.env, whole.params, whole.state, whole.rng, steps, pids, mode="chained", reference=hold,
+                        wind_ids=aids, **kw)
+
+
+# ------------------------------------------------------------------ 12. physics, signs only -----
+def test_wind_tilts_and_displaces_and_still_air_damps(device, oracle):
+    """the shipped policy on tracking.hold, 300 steps: in a steady +x wind of 6 m/s (d = 0.5 / s: 3 m/s^2 on a vehicle at rest) the
+    mean tilt is larger than in calm air and the mean x of the state is displaced downwind during the first second; still air with
+    d = 2 / s leaves a smaller rms linear velocity than d = 0 from the same initial states.  Signs only."""
+    n, limit = 128, 300
+    hold = l2f.Reference(device, tracking.hold(limit))
+    bank = l2f.WindBank(device, [winds.calm(limit), winds.steady(limit, (6.0, 0.0, 0.0), 0.5), winds.still_air(limit, 2.0)])
+    kw = dict(seed=8, domain_randomization=1, episode_step_limit=limit, init_max_position=0.05, init_max_linear_velocity=1.0,
+              init_max_angle=0.3, init_max_angular_velocity=0.2)
+    recs, tilt = {}, None
+    for name, table in (("calm", 0), ("wind", 1), ("still", 2)):
+        w = World(device, oracle, n, **kw)               # the same seed: the same quadrotors from the same initial states
+        ids = np.full(n, table, np.uint32)
+        ids[1::2] = 0                                    # odd envs fly calm air in every world: the group the others stand against
+        w.env.set_wind_schedule(bank, ids)
+        tr = w.vector.Trajectory(w.env, limit)
+        roll(w, limit, "fused", True, trajectory=tr, reference=hold)
+        if name == "wind":                               # [group, bucket]: the odd envs in calm air, the even ones in the wind
+            ft = probing.flight_table(tr, edges=probing.linear_age_edges(0, limit, 3), device=False)
+            tilt = np.asarray(ft.by_group((ids != 0).astype(np.uint32), 2)["mean_tilt"], np.float64)
+        recs[name] = tr.numpy()
+    even = np.arange(n) % 2 == 0
+    x = {k: r["obs"][:100, :, 0][:, even].astype(np.float64).mean() for k, r in recs.items()}
+    speed = {k: np.sqrt((r["obs"][:100, :, 12:15][:, even].astype(np.float64) ** 2).sum(-1).mean()) for k, r in recs.items()}
+    print(f"\n[wind 6 m/s +x] mean tilt by third of the episode: wind {np.round(tilt[1], 5)}, calm {np.round(tilt[0], 5)}; "
+          f"mean x over the first second: wind {x['wind']:.4f} m, calm {x['calm']:.4f} m; rms speed over the first second: still air "
+          f"{speed['still']:.4f} m/s, calm {speed['calm']:.4f} m/s")
+    assert np.array_equal(bits(recs["calm"]["obs"][:, ~even]), bits(recs["wind"]["obs"][:, ~even]))          # the calm group is the same flight
+    assert (tilt[1] > tilt[0]).all()
+    assert x["wind"] > x["calm"]
+    assert speed["still"] < speed["calm"]
