@@ -486,9 +486,7 @@ RQ_API int rq_env_destroy(rq_env* env) {
     if (!env) return RQ_OK;
     DeviceScope on_device(env->ordinal);   // hipFree synchronises the device; the parent is not touched - unless it is alive and
     if (device_registry(env->dev, 0)) (void)resident_retire(env->dev);     // keeps a resident executor
-    if (env->wrench) env->wrench->attached -= 1;          // detaches the wrench schedule: its bank may be destroyed now
-    if (env->vehicle) env->vehicle->attached -= 1;        // ... and the vehicle schedule
-    if (env->wind) env->wind->attached -= 1;              // ... and the wind schedule
+    for (auto& slot : env->schedule) slot.detach();       // its banks may be destroyed now
     for (float* b : env->state_pool) (void)hipFree(b);
     for (auto& g : env->graphs) (void)hipGraphExecDestroy(g.exec);
     delete env;

@@ -35,66 +35,26 @@ int rollout_check(RolloutFrame& f, const RolloutCall& c, bool actor) {
                   "trajectory buffer too small for this rollout");
         f.tp = {traj->obs, traj->act, traj->rew, traj->done, traj->length};
     }
-    rc = env_wrench("rollout", c.env, &f.wr); if (rc) return rc;
-    rc = env_vehicle("rollout", c.env, &f.vh); if (rc) return rc;
-    // a vehicle schedule is flown fused by the fp32 builds alone and without a wrench schedule beside it; nothing runs chained in
-    // its place (the actors refuse what is theirs: a 16-bit policy, a SampleAndSquash stage, a teacher bank)
-    if (f.vh.rows && f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return vehicle_refuses_fused(c.who, "an env that carries a wrench schedule too");
-    // a wind schedule likewise, and without either of the other two beside it
-    rc = env_wind("rollout", c.env, &f.wd); if (rc) return rc;
-    if (f.wd.rows && f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return wind_refuses_fused(c.who, "an env that carries a wrench schedule too");
-    if (f.wd.rows && f.vh.rows && c.mode == RQ_ROLLOUT_FUSED) return wind_refuses_fused(c.who, "an env that carries a vehicle schedule too");
+    // A schedule is flown fused by the fp32 builds alone and without another schedule beside it; nothing runs chained in its place
+    // (the actors refuse what is theirs: a 16-bit policy, a SampleAndSquash stage, a teacher bank).  Kind by kind, each refused beside
+    // the kinds before it, earliest first.
+    rc = env_schedules("rollout", c.env, f.sched); if (rc) return rc;
+    for (int k = 0; k < kScheduleKinds && c.mode == RQ_ROLLOUT_FUSED; ++k)
+        for (int j = 0; j < k && f.sched[k].rows; ++j)
+            if (f.sched[j].rows)
+                return refuses_fused(c.who, k, (std::string("an env that carries a ") + kTableKinds[j].noun + " schedule too").c_str());
     return RQ_OK;
 }
 
-int env_wind(const char* who, const rq_env* env, rq::WindPtrs* wd) {
-    *wd = rq::WindPtrs{};
-    const rq_wind_bank* bank = env->wind;
-    if (!bank) return RQ_OK;
-    if (bank->rows < env->cfg.episode_step_limit)
-        return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env's wind schedule has fewer rows (" + std::to_string(bank->rows) +
-                                                 ") than episode_step_limit (" + std::to_string(env->cfg.episode_step_limit) +
-                                                 "): every table must cover an episode");
-    *wd = {bank->d, env->wind_row0, bank->rows, 0u};
-    return RQ_OK;
+int schedule_too_short(const char* who, const rq_env* env, int kind) {
+    return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env's " + kTableKinds[kind].noun + " schedule has fewer rows (" +
+                                             std::to_string(env->schedule[kind].bank->rows) + ") than episode_step_limit (" +
+                                             std::to_string(env->cfg.episode_step_limit) + "): every table must cover an episode");
 }
 
-int wind_refuses_fused(const char* who, const char* what) {
-    return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env carries a wind schedule, which the fused kernel of " + what +
-                                             " is not taught: fly it with mode RQ_ROLLOUT_CHAINED (\"chained\"), or detach the schedule");
-}
-
-int env_vehicle(const char* who, const rq_env* env, rq::VehiclePtrs* vh) {
-    *vh = rq::VehiclePtrs{};
-    const rq_vehicle_bank* bank = env->vehicle;
-    if (!bank) return RQ_OK;
-    if (bank->rows < env->cfg.episode_step_limit)
-        return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env's vehicle schedule has fewer rows (" + std::to_string(bank->rows) +
-                                                 ") than episode_step_limit (" + std::to_string(env->cfg.episode_step_limit) +
-                                                 "): every table must cover an episode");
-    *vh = {bank->d, env->vehicle_row0, bank->rows, 0u};
-    return RQ_OK;
-}
-
-int vehicle_refuses_fused(const char* who, const char* what) {
-    return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env carries a vehicle schedule, which the fused kernel of " + what +
-                                             " is not taught: fly it with mode RQ_ROLLOUT_CHAINED (\"chained\"), or detach the schedule");
-}
-
-int env_wrench(const char* who, const rq_env* env, rq::WrenchPtrs* wr) {
-    *wr = rq::WrenchPtrs{};
-    const rq_wrench_bank* bank = env->wrench;
-    if (!bank) return RQ_OK;
-    if (bank->rows < env->cfg.episode_step_limit)
-        return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env's wrench schedule has fewer rows (" + std::to_string(bank->rows) +
-                                                 ") than episode_step_limit (" + std::to_string(env->cfg.episode_step_limit) +
-                                                 "): every table must cover an episode");
-    *wr = {bank->d, env->wrench_row0, bank->rows, bank->units == RQ_WRENCH_RELATIVE ? 1u : 0u};
-    return RQ_OK;
-}
-
-int wrench_refuses_fused(const char* who, const char* what) {
-    return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env carries a wrench schedule, which the fused kernel of " + what +
+int refuses_fused(const char* who, int kind, const char* what) {
+    return fail(RQ_ERR_INVALID_ARGUMENT, std::string(who) + ": the env carries a " + kTableKinds[kind].noun +
+                                             " schedule, which the fused kernel of " + what +
                                              " is not taught: fly it with mode RQ_ROLLOUT_CHAINED (\"chained\"), or detach the schedule");
 }
 
@@ -112,17 +72,14 @@ int rollout_check_tables(const RolloutCall& c) {
     return RQ_OK;
 }
 
-int upload_first_rows(const char* what, rq_device* dev, const rq_env* env, const uint32_t* ids, uint32_t rows, uint32_t* dst) {
-    std::vector<uint32_t> first;
-    try {                                   // nothing throws across the boundary
-        first.assign(env->ld, 0u);
-    } catch (const std::bad_alloc&) {
-        return fail(RQ_ERR_OUT_OF_MEMORY, std::string(what) + ": host allocation failed");
+int first_rows_failed(const char* what, const rq::FirstRowsStatus& s) {
+    switch (s.what) {
+    case rq::FirstRowsStatus::host_allocation: return fail(RQ_ERR_OUT_OF_MEMORY, std::string(what) + ": host allocation failed");
+    case rq::FirstRowsStatus::device_allocation: return fail(RQ_ERR_OUT_OF_MEMORY, std::string(what) + ": device allocation failed");
+    case rq::FirstRowsStatus::copy: return hip_failed("upload_first_rows", "hipMemcpyAsync", s.hip);
+    case rq::FirstRowsStatus::synchronize: return hip_failed("upload_first_rows", "hipStreamSynchronize", s.hip);
+    default: return RQ_OK;
     }
-    for (uint32_t i = 0; ids && i < env->n; ++i) first[i] = ids[i] * rows;       // < n_tables * rows < 2^28
-    RQ_HIP(hipMemcpyAsync(dst, first.data(), (size_t)env->ld * sizeof(uint32_t), hipMemcpyHostToDevice, dev->stream));
-    RQ_HIP(hipStreamSynchronize(dev->stream));                // `first` is pageable and goes away
-    return RQ_OK;
 }
 
 int rollout_track(RolloutFrame& f, const RolloutCall& c) {
@@ -145,7 +102,8 @@ int rollout_track(RolloutFrame& f, const RolloutCall& c) {
             return fail(RQ_ERR_OUT_OF_MEMORY, "reference bank: host allocation failed");
         }
         RQ_HIP(hipStreamSynchronize(c.dev->stream));              // a rollout in flight reads the rows of the ids before
-        rc = upload_first_rows("reference bank", c.dev, env, c.reference_id, t->rows, f.trk.steps + env->ld); if (rc) return rc;
+        const rq::FirstRowsStatus up = rq::upload_first_rows(c.dev->stream, c.reference_id, n, env->ld, t->rows, f.trk.steps + env->ld);
+        if (up) return first_rows_failed("reference bank", up);
         env->row0_valid = true;
         env->row0_key = t->uid;
         env->row0_gen = fresh_version();
@@ -180,14 +138,14 @@ rq::FusedArgs fused_args(const RolloutCall& c, const RolloutFrame& f) {
     a.seed = c.rng->seed; a.epoch0 = c.rng->epoch; a.n_steps = c.n_steps;
     a.autoreset = (c.flags & RQ_ROLLOUT_AUTORESET) != 0;
     a.params = c.params->d; a.state = c.state->d; a.st = c.env->st;
-    a.traj = f.tp; a.trk = f.trk; a.wr = f.wr; a.vh = f.vh; a.wd = f.wd;
+    a.traj = f.tp; a.trk = f.trk; set_schedules(a, f.sched);
     return a;
 }
 
 rq::EnvStepLaunch env_step_launch(const RolloutCall& c, const RolloutFrame& f) {
     rq::EnvStepLaunch e;
     e.b = f.b; e.c = f.sc; e.params = c.params->d; e.state = c.state->d; e.action = c.env->act; e.next_state = c.state->d; e.st = c.env->st;
-    e.rollout = true; e.flags = c.flags; e.sc = f.smp; e.seed = c.rng->seed; e.wr = f.wr; e.vh = f.vh; e.wd = f.wd;
+    e.rollout = true; e.flags = c.flags; e.sc = f.smp; e.seed = c.rng->seed; set_schedules(e, f.sched);
     return e;
 }
 
@@ -224,17 +182,10 @@ struct PolicyActor {
         RQ_REFUSE(c.who, policy->dev == c.dev, RQ_ERR_SHAPE_MISMATCH, "policy lives on another device");
         RQ_REFUSE(c.who, !c.tables || policy->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
                   "tracked rollouts do not carry the SampleAndSquash stage");
-        if (f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) {        // a schedule is flown fused by the fp32 builds alone; nothing runs chained in its place
-            if (policy->precision != RQ_POLICY_FP32) return wrench_refuses_fused(c.who, "a bf16 / f16x2 policy");
-            if (policy->sas_mode != RQ_SAS_OFF) return wrench_refuses_fused(c.who, "a policy with a SampleAndSquash stage");
-        }
-        if (f.vh.rows && c.mode == RQ_ROLLOUT_FUSED) {        // likewise a vehicle schedule
-            if (policy->precision != RQ_POLICY_FP32) return vehicle_refuses_fused(c.who, "a bf16 / f16x2 policy");
-            if (policy->sas_mode != RQ_SAS_OFF) return vehicle_refuses_fused(c.who, "a policy with a SampleAndSquash stage");
-        }
-        if (f.wd.rows && c.mode == RQ_ROLLOUT_FUSED) {        // ... and a wind schedule
-            if (policy->precision != RQ_POLICY_FP32) return wind_refuses_fused(c.who, "a bf16 / f16x2 policy");
-            if (policy->sas_mode != RQ_SAS_OFF) return wind_refuses_fused(c.who, "a policy with a SampleAndSquash stage");
+        for (int k = 0; k < kScheduleKinds && c.mode == RQ_ROLLOUT_FUSED; ++k) {      // a schedule is flown fused by the fp32 builds alone
+            if (!f.sched[k].rows) continue;
+            if (policy->precision != RQ_POLICY_FP32) return refuses_fused(c.who, k, "a bf16 / f16x2 policy");
+            if (policy->sas_mode != RQ_SAS_OFF) return refuses_fused(c.who, k, "a policy with a SampleAndSquash stage");
         }
         return RQ_OK;
     }
@@ -278,38 +229,36 @@ struct PolicyActor {
         key.seed = c.rng->seed; key.sas_mode = policy->sas_mode; key.sas_seed = policy->sas_seed; key.ls_image = policy->ls_image;
         key.ref = f.trk.ref; key.ref_rows = f.trk.rows; key.row0_at = f.trk.row0_at;
         key.row0_gen = f.row0_gen;      // (a reference bank: which ids the rows were built from)
-        key.interval = policy->native_interval; key.wrench_gen = c.env->wrench_gen; key.vehicle_gen = c.env->vehicle_gen;
-        key.wind_gen = c.env->wind_gen;
+        key.interval = policy->native_interval;
+        for (int k = 0; k < kScheduleKinds; ++k) key.schedule_gen[k] = c.env->schedule[k].gen;
         return key;
     }
 };
 
-// The tables of rq_reference_create (`single`: one table, named without a bank's words), rq_reference_bank_create and
-// rq_wrench_bank_create: refused before the device is looked at, then allocated and uploaded.  T: the handle's type.
-// `cols`: 6, or a vehicle bank's 4 positive factors (`positive`: an entry that is not > 0 is refused too, naming its column), or a wind
-// bank's 4 (`nonneg_col`: the column whose entries, the specific drag, must not be negative).
+// The tables of rq_reference_create (one table, named without a bank's words), rq_reference_bank_create and the three schedule
+// banks: refused before the device is looked at, then allocated and uploaded.  T: the handle's type; `kind`: its row of kTableKinds.
 template <typename T>
-int row_tables_create(const char* who, const char* noun, bool single, rq_device* dev, const float* host_rows, uint32_t n_tables,
-                      uint32_t rows, T** out, uint32_t cols = 6, bool positive = false, int nonneg_col = -1) {
+int row_tables_create(const char* who, int kind, rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, T** out) {
+    const TableKind& tk = kTableKinds[kind];
+    const bool single = kind == kReference, names_column = tk.rule != TableKind::kFinite;
+    const uint32_t cols = tk.cols;
+    const std::string noun = tk.tables;
     RQ_REFUSE(who, dev && host_rows && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     if (single) RQ_REFUSE(who, rows > 0, RQ_ERR_INVALID_ARGUMENT, "a reference needs at least one row");
-    RQ_REFUSE(who, n_tables > 0 && rows > 0, RQ_ERR_INVALID_ARGUMENT, std::string("a ") + noun + " needs at least one table of at least one row");
+    RQ_REFUSE(who, n_tables > 0 && rows > 0, RQ_ERR_INVALID_ARGUMENT, "a " + noun + " needs at least one table of at least one row");
     // the row an env reads, first row of its table + episode step count, is a uint32 on the device
-    RQ_REFUSE(who, single || (uint64_t)n_tables * rows < (1ull << 28), RQ_ERR_INVALID_ARGUMENT,
-              std::string("a ") + noun + " holds fewer than 2^28 rows in all");
+    RQ_REFUSE(who, single || (uint64_t)n_tables * rows < (1ull << 28), RQ_ERR_INVALID_ARGUMENT, "a " + noun + " holds fewer than 2^28 rows in all");
     const size_t floats = (size_t)n_tables * rows * cols;
     for (size_t j = 0; j < floats; ++j) {
-        RQ_REFUSE(who, std::isfinite(host_rows[j]), RQ_ERR_INVALID_ARGUMENT,
-                  std::string(noun) + " holds a non-finite entry" +
-                      (single ? "" : ": table " + std::to_string(j / ((size_t)rows * cols)) + ", row " + std::to_string(j / cols % rows)) +
-                      (positive || nonneg_col >= 0 ? ", column " + std::to_string(j % cols) : ""));
-        RQ_REFUSE(who, !positive || host_rows[j] > 0.0f, RQ_ERR_INVALID_ARGUMENT,
-                  std::string(noun) + " holds a factor that is not > 0: table " + std::to_string(j / ((size_t)rows * cols)) + ", row " +
-                      std::to_string(j / cols % rows) + ", column " + std::to_string(j % cols));
-        RQ_REFUSE(who, (int)(j % cols) != nonneg_col || host_rows[j] >= 0.0f, RQ_ERR_INVALID_ARGUMENT,
-                  std::string(noun) + " holds a negative drag: table " + std::to_string(j / ((size_t)rows * cols)) + ", row " +
-                      std::to_string(j / cols % rows) + ", column " + std::to_string(j % cols));
+        const char* bad = !std::isfinite(host_rows[j])                                                     ? " holds a non-finite entry"
+                          : tk.rule == TableKind::kPositive && !(host_rows[j] > 0.0f)                       ? " holds a factor that is not > 0"
+                          : tk.rule == TableKind::kNonNegativeColumn && (int)(j % cols) == tk.rule_col && !(host_rows[j] >= 0.0f)
+                              ? " holds a negative drag"
+                              : nullptr;
+        RQ_REFUSE(who, !bad, RQ_ERR_INVALID_ARGUMENT,
+                  noun + bad + (single ? "" : ": table " + std::to_string(j / ((size_t)rows * cols)) + ", row " + std::to_string(j / cols % rows)) +
+                      (names_column ? ", column " + std::to_string(j % cols) : ""));
     }
     DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
     T* r = new (std::nothrow) T();
@@ -335,6 +284,45 @@ int row_tables_destroy(T* tables) {
     if (!tables) return RQ_OK;
     DeviceScope on_device(tables->ordinal);
     delete tables;
+    return RQ_OK;
+}
+
+
+// ---- the schedules' entry points, one body per verb; `kind`: the schedule's row of kTableKinds ----
+int schedule_bank_destroy(const char* who, int kind, ScheduleBank* bank) {
+    const TableKind& tk = kTableKinds[kind];
+    RQ_REFUSE(who, !bank || bank->attached == 0, RQ_ERR_INVALID_ARGUMENT,
+              std::string("the ") + tk.tables + " is attached to " + std::to_string(bank->attached) + " live env(s): detach it (" + tk.detach +
+                  " with a NULL bank) or destroy the env first");
+    return RQ_OK;
+}
+
+// attach `bank` with one id per env (null: table 0 for all), or detach (null bank)
+int env_schedule_set(const char* who, int kind, rq_env* env, ScheduleBank* bank, const uint32_t* id) {
+    const std::string noun = kTableKinds[kind].noun;
+    RQ_REFUSE(who, env, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    rq_device* dev = env->dev;
+    if (bank) {
+        RQ_REFUSE(who, bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, noun + " bank lives on another device");
+        for (uint32_t i = 0; id && i < env->n; ++i)
+            RQ_REFUSE(who, id[i] < bank->n_tables, RQ_ERR_INVALID_ARGUMENT,
+                      noun + " id out of range: env " + std::to_string(i) + " names table " + std::to_string(id[i]) + " of a bank of " +
+                          std::to_string(bank->n_tables));
+    }
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;      // (retires a running resident executor)
+    RQ_HIP_AS(who, hipStreamSynchronize(dev->stream));        // a launch in flight reads the rows of the schedule before
+    obs_cache_drop_if(dev, env);
+    auto& slot = env->schedule[kind];
+    if (!bank) { slot.detach(); return RQ_OK; }
+    return first_rows_failed((noun + " schedule").c_str(), slot.attach(dev->stream, bank, id, env->n, env->ld));
+}
+
+template <typename T>
+int env_schedule_get(const char* who, int kind, const rq_env* env, T** bank, uint32_t* id_out) {
+    RQ_REFUSE(who, env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    const auto& slot = env->schedule[kind];
+    *bank = static_cast<T*>(slot.bank);
+    if (slot.bank && id_out) std::memcpy(id_out, slot.ids.data(), (size_t)env->n * sizeof(uint32_t));
     return RQ_OK;
 }
 
@@ -371,184 +359,63 @@ RQ_API int rq_rollout_track_refs(rq_device* dev, rq_env* env, const rq_params* p
 
 // ---------------------------------------------------------------------------- Tracking
 RQ_API int rq_reference_create(rq_device* dev, const float* host_rows, uint32_t rows, rq_reference** out) {
-    return row_tables_create(__func__, "reference", true, dev, host_rows, 1, rows, out);
+    return row_tables_create(__func__, kReference, dev, host_rows, 1, rows, out);
 }
 
 RQ_API int rq_reference_destroy(rq_reference* reference) { return row_tables_destroy(reference); }
 
 RQ_API int rq_reference_bank_create(rq_device* dev, const float* host_rows, uint32_t n_refs, uint32_t rows, rq_reference_bank** out) {
-    return row_tables_create(__func__, "reference bank", false, dev, host_rows, n_refs, rows, out);
+    return row_tables_create(__func__, kReferenceBank, dev, host_rows, n_refs, rows, out);
 }
 
 RQ_API int rq_reference_bank_destroy(rq_reference_bank* references) { return row_tables_destroy(references); }
 
-// ---------------------------------------------------------------------------- Wrench schedule
+// ---------------------------------------------------------------------------- Schedules: wrench, vehicle, wind
 RQ_API int rq_wrench_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, int units, rq_wrench_bank** out) {
     RQ_REQUIRE(units == RQ_WRENCH_RELATIVE || units == RQ_WRENCH_ABSOLUTE, RQ_ERR_INVALID_ARGUMENT,
                "unknown units: RQ_WRENCH_RELATIVE or RQ_WRENCH_ABSOLUTE");
-    const int rc = row_tables_create(__func__, "wrench bank", false, dev, host_rows, n_tables, rows, out);
+    const int rc = row_tables_create(__func__, kWrench, dev, host_rows, n_tables, rows, out);
     if (rc == RQ_OK) (*out)->units = units;
     return rc;
 }
+RQ_API int rq_vehicle_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, rq_vehicle_bank** out) {
+    return row_tables_create(__func__, kVehicle, dev, host_rows, n_tables, rows, out);
+}
+RQ_API int rq_wind_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, rq_wind_bank** out) {
+    return row_tables_create(__func__, kWind, dev, host_rows, n_tables, rows, out);
+}
 
 RQ_API int rq_wrench_bank_destroy(rq_wrench_bank* bank) {
-    RQ_REQUIRE(!bank || bank->attached == 0, RQ_ERR_INVALID_ARGUMENT,
-               "the wrench bank is attached to " + std::to_string(bank->attached) +
-                   " live env(s): detach it (rq_env_set_wrench_schedule with a NULL bank) or destroy the env first");
-    return row_tables_destroy(bank);
+    const int rc = schedule_bank_destroy(__func__, kWrench, bank);
+    return rc ? rc : row_tables_destroy(bank);
+}
+RQ_API int rq_vehicle_bank_destroy(rq_vehicle_bank* bank) {
+    const int rc = schedule_bank_destroy(__func__, kVehicle, bank);
+    return rc ? rc : row_tables_destroy(bank);
+}
+RQ_API int rq_wind_bank_destroy(rq_wind_bank* bank) {
+    const int rc = schedule_bank_destroy(__func__, kWind, bank);
+    return rc ? rc : row_tables_destroy(bank);
 }
 
 RQ_API int rq_env_set_wrench_schedule(rq_env* env, rq_wrench_bank* bank, const uint32_t* wrench_id) {
-    RQ_REQUIRE(env, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    rq_device* dev = env->dev;
-    if (bank) {
-        RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "wrench bank lives on another device");
-        if (wrench_id)
-            for (uint32_t i = 0; i < env->n; ++i)
-                RQ_REQUIRE(wrench_id[i] < bank->n_tables, RQ_ERR_INVALID_ARGUMENT,
-                           "wrench id out of range: env " + std::to_string(i) + " names table " + std::to_string(wrench_id[i]) +
-                               " of a bank of " + std::to_string(bank->n_tables));
-    }
-    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;      // (retires a running resident executor)
-    RQ_HIP(hipStreamSynchronize(dev->stream));                // a launch in flight reads the rows of the schedule before
-    obs_cache_drop_if(dev, env);
-    if (!bank) {
-        if (env->wrench) env->wrench->attached -= 1;
-        env->wrench = nullptr; env->wrench_gen = 0; env->wrench_ids.clear();
-        return RQ_OK;
-    }
-    std::vector<uint32_t> ids;
-    try {                                   // nothing throws across the boundary
-        if (wrench_id) ids.assign(wrench_id, wrench_id + env->n); else ids.assign(env->n, 0u);
-    } catch (const std::bad_alloc&) {
-        return fail(RQ_ERR_OUT_OF_MEMORY, "wrench schedule: host allocation failed");
-    }
-    if (env->wrench_row0.empty() && env->wrench_row0.alloc(env->ld) != hipSuccess)
-        return fail(RQ_ERR_OUT_OF_MEMORY, "wrench schedule: device allocation failed");
-    rc = upload_first_rows("wrench schedule", dev, env, wrench_id, bank->rows, env->wrench_row0); if (rc) return rc;
-    if (env->wrench) env->wrench->attached -= 1;
-    bank->attached += 1;
-    env->wrench = bank;
-    env->wrench_ids.swap(ids);
-    env->wrench_gen = fresh_version();
-    return RQ_OK;
+    return env_schedule_set(__func__, kWrench, env, bank, wrench_id);
+}
+RQ_API int rq_env_set_vehicle_schedule(rq_env* env, rq_vehicle_bank* bank, const uint32_t* vehicle_id) {
+    return env_schedule_set(__func__, kVehicle, env, bank, vehicle_id);
+}
+RQ_API int rq_env_set_wind_schedule(rq_env* env, rq_wind_bank* bank, const uint32_t* wind_id) {
+    return env_schedule_set(__func__, kWind, env, bank, wind_id);
 }
 
 RQ_API int rq_env_get_wrench_schedule(const rq_env* env, rq_wrench_bank** bank, uint32_t* wrench_id_out) {
-    RQ_REQUIRE(env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    *bank = env->wrench;
-    if (env->wrench && wrench_id_out) std::memcpy(wrench_id_out, env->wrench_ids.data(), (size_t)env->n * sizeof(uint32_t));
-    return RQ_OK;
+    return env_schedule_get(__func__, kWrench, env, bank, wrench_id_out);
 }
-
-// ---------------------------------------------------------------------------- Vehicle schedule
-RQ_API int rq_vehicle_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, rq_vehicle_bank** out) {
-    return row_tables_create(__func__, "vehicle bank", false, dev, host_rows, n_tables, rows, out, 4, true);
-}
-
-RQ_API int rq_vehicle_bank_destroy(rq_vehicle_bank* bank) {
-    RQ_REQUIRE(!bank || bank->attached == 0, RQ_ERR_INVALID_ARGUMENT,
-               "the vehicle bank is attached to " + std::to_string(bank->attached) +
-                   " live env(s): detach it (rq_env_set_vehicle_schedule with a NULL bank) or destroy the env first");
-    return row_tables_destroy(bank);
-}
-
-RQ_API int rq_env_set_vehicle_schedule(rq_env* env, rq_vehicle_bank* bank, const uint32_t* vehicle_id) {
-    RQ_REQUIRE(env, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    rq_device* dev = env->dev;
-    if (bank) {
-        RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "vehicle bank lives on another device");
-        if (vehicle_id)
-            for (uint32_t i = 0; i < env->n; ++i)
-                RQ_REQUIRE(vehicle_id[i] < bank->n_tables, RQ_ERR_INVALID_ARGUMENT,
-                           "vehicle id out of range: env " + std::to_string(i) + " names table " + std::to_string(vehicle_id[i]) +
-                               " of a bank of " + std::to_string(bank->n_tables));
-    }
-    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;      // (retires a running resident executor)
-    RQ_HIP(hipStreamSynchronize(dev->stream));                // a launch in flight reads the rows of the schedule before
-    obs_cache_drop_if(dev, env);
-    if (!bank) {
-        if (env->vehicle) env->vehicle->attached -= 1;
-        env->vehicle = nullptr; env->vehicle_gen = 0; env->vehicle_ids.clear();
-        return RQ_OK;
-    }
-    std::vector<uint32_t> ids;
-    try {                                   // nothing throws across the boundary
-        if (vehicle_id) ids.assign(vehicle_id, vehicle_id + env->n); else ids.assign(env->n, 0u);
-    } catch (const std::bad_alloc&) {
-        return fail(RQ_ERR_OUT_OF_MEMORY, "vehicle schedule: host allocation failed");
-    }
-    if (env->vehicle_row0.empty() && env->vehicle_row0.alloc(env->ld) != hipSuccess)
-        return fail(RQ_ERR_OUT_OF_MEMORY, "vehicle schedule: device allocation failed");
-    rc = upload_first_rows("vehicle schedule", dev, env, vehicle_id, bank->rows, env->vehicle_row0); if (rc) return rc;
-    if (env->vehicle) env->vehicle->attached -= 1;
-    bank->attached += 1;
-    env->vehicle = bank;
-    env->vehicle_ids.swap(ids);
-    env->vehicle_gen = fresh_version();
-    return RQ_OK;
-}
-
 RQ_API int rq_env_get_vehicle_schedule(const rq_env* env, rq_vehicle_bank** bank, uint32_t* vehicle_id_out) {
-    RQ_REQUIRE(env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    *bank = env->vehicle;
-    if (env->vehicle && vehicle_id_out) std::memcpy(vehicle_id_out, env->vehicle_ids.data(), (size_t)env->n * sizeof(uint32_t));
-    return RQ_OK;
+    return env_schedule_get(__func__, kVehicle, env, bank, vehicle_id_out);
 }
-
-// ---------------------------------------------------------------------------- Wind schedule
-RQ_API int rq_wind_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, rq_wind_bank** out) {
-    return row_tables_create(__func__, "wind bank", false, dev, host_rows, n_tables, rows, out, 4, false, 3);
-}
-
-RQ_API int rq_wind_bank_destroy(rq_wind_bank* bank) {
-    RQ_REQUIRE(!bank || bank->attached == 0, RQ_ERR_INVALID_ARGUMENT,
-               "the wind bank is attached to " + std::to_string(bank->attached) +
-                   " live env(s): detach it (rq_env_set_wind_schedule with a NULL bank) or destroy the env first");
-    return row_tables_destroy(bank);
-}
-
-RQ_API int rq_env_set_wind_schedule(rq_env* env, rq_wind_bank* bank, const uint32_t* wind_id) {
-    RQ_REQUIRE(env, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    rq_device* dev = env->dev;
-    if (bank) {
-        RQ_REQUIRE(bank->dev == dev, RQ_ERR_SHAPE_MISMATCH, "wind bank lives on another device");
-        if (wind_id)
-            for (uint32_t i = 0; i < env->n; ++i)
-                RQ_REQUIRE(wind_id[i] < bank->n_tables, RQ_ERR_INVALID_ARGUMENT,
-                           "wind id out of range: env " + std::to_string(i) + " names table " + std::to_string(wind_id[i]) +
-                               " of a bank of " + std::to_string(bank->n_tables));
-    }
-    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;      // (retires a running resident executor)
-    RQ_HIP(hipStreamSynchronize(dev->stream));                // a launch in flight reads the rows of the schedule before
-    obs_cache_drop_if(dev, env);
-    if (!bank) {
-        if (env->wind) env->wind->attached -= 1;
-        env->wind = nullptr; env->wind_gen = 0; env->wind_ids.clear();
-        return RQ_OK;
-    }
-    std::vector<uint32_t> ids;
-    try {                                   // nothing throws across the boundary
-        if (wind_id) ids.assign(wind_id, wind_id + env->n); else ids.assign(env->n, 0u);
-    } catch (const std::bad_alloc&) {
-        return fail(RQ_ERR_OUT_OF_MEMORY, "wind schedule: host allocation failed");
-    }
-    if (env->wind_row0.empty() && env->wind_row0.alloc(env->ld) != hipSuccess)
-        return fail(RQ_ERR_OUT_OF_MEMORY, "wind schedule: device allocation failed");
-    rc = upload_first_rows("wind schedule", dev, env, wind_id, bank->rows, env->wind_row0); if (rc) return rc;
-    if (env->wind) env->wind->attached -= 1;
-    bank->attached += 1;
-    env->wind = bank;
-    env->wind_ids.swap(ids);
-    env->wind_gen = fresh_version();
-    return RQ_OK;
-}
-
 RQ_API int rq_env_get_wind_schedule(const rq_env* env, rq_wind_bank** bank, uint32_t* wind_id_out) {
-    RQ_REQUIRE(env && bank, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    *bank = env->wind;
-    if (env->wind && wind_id_out) std::memcpy(wind_id_out, env->wind_ids.data(), (size_t)env->n * sizeof(uint32_t));
-    return RQ_OK;
+    return env_schedule_get(__func__, kWind, env, bank, wind_id_out);
 }
 
 // ---------------------------------------------------------------------------- Trajectory

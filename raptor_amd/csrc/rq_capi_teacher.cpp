@@ -298,9 +298,8 @@ struct TeacherActor {
         RQ_REFUSE(c.who, c.mode != RQ_ROLLOUT_FUSED || (!bank->layers && bank->precision == RQ_POLICY_FP32), RQ_ERR_INVALID_ARGUMENT,
                   "the fused teacher rollout runs the fp32 two-hidden-layer {16, 32, 64} family: fly this bank (bf16 / f16x2 precision "
                   "or a dense stack) with mode RQ_ROLLOUT_CHAINED (\"chained\")");
-        if (f.wr.rows && c.mode == RQ_ROLLOUT_FUSED) return wrench_refuses_fused(c.who, "a teacher bank");
-        if (f.vh.rows && c.mode == RQ_ROLLOUT_FUSED) return vehicle_refuses_fused(c.who, "a teacher bank");
-        if (f.wd.rows && c.mode == RQ_ROLLOUT_FUSED) return wind_refuses_fused(c.who, "a teacher bank");
+        for (int k = 0; k < kScheduleKinds && c.mode == RQ_ROLLOUT_FUSED; ++k)
+            if (f.sched[k].rows) return refuses_fused(c.who, k, "a teacher bank");
         return check_ids(bank, teacher_id, c.env->n);
     }
     int prepare(const RolloutCall& c) {

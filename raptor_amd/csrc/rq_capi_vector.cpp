@@ -59,12 +59,8 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
     int rc = check_env_objects(dev, env, params, state); if (rc) return rc;
     RQ_REQUIRE(params && state && next_state && rng, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(next_state->env == env, RQ_ERR_SHAPE_MISMATCH, "next_state belongs to another env");
-    rq::WrenchPtrs wr{};
-    rc = env_wrench(__func__, env, &wr); if (rc) return rc;       // the env's wrench schedule, refused before anything is enqueued
-    rq::VehiclePtrs vh{};
-    rc = env_vehicle(__func__, env, &vh); if (rc) return rc;      // ... and its vehicle schedule
-    rq::WindPtrs wd{};
-    rc = env_wind(__func__, env, &wd); if (rc) return rc;         // ... and its wind schedule
+    SchedulePtrs sched[kScheduleKinds];
+    rc = env_schedules(__func__, env, sched); if (rc) return rc;  // the env's schedules, refused before anything is enqueued
     DeviceScope on_device(dev, rq::KeepResident{}); rc = on_device.rc; if (rc) return rc;
     // small batches: the kernel also assembles the observation of the state it writes, for the next observe() (ObservationCache)
     const bool cache_obs = env->n < kGpuLayoutMinEnvs && !rq::noise_enabled(env->cfg) && !params->exposed &&
@@ -102,7 +98,7 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
     rq::EnvStepLaunch& es = pair.step;
     es.b = batch_of(env); es.c = rq::step_cfg(env->cfg); es.sc = rq::sample_cfg(env->cfg); es.seed = rng->seed;
     es.params = params->d; es.state = state->d; es.action = env->act; es.next_state = next_state->d; es.st = env->st;
-    es.mb = mb; es.obs_of_next = cache_obs ? env->obs_alt.get() : nullptr; es.wr = wr; es.vh = vh; es.wd = wd;
+    es.mb = mb; es.obs_of_next = cache_obs ? env->obs_alt.get() : nullptr; set_schedules(es, sched);
     pair.spec = pol != nullptr;
     if (pol) {      // on the observation the step leaves, out of place: hidden -> hidden_alt
         rq::ActorStepLaunch& as = pair.actor;

@@ -12,6 +12,7 @@
 //   rq_capi_grad.cpp     the student's forward / backward over a recorded trajectory; the distillation update (loss, Adam, repack),
 //                        for one policy and for a policy bank
 //   rq_memory.hpp        rq::DeviceBuffer / rq::PinnedBuffer: every object below owns its device and pinned memory through them
+//   rq_env_schedule.hpp  rq::EnvSchedule: a schedule slot of an env - bank, ids, first rows on the device, attachment number
 //   rq_call_memory.hpp   rq::CallMemory: the `memory` argument of the learner's and the probes' calls - staging in and out, the final wait
 // The ten rq_rollout* entry points (a policy's, a policy bank's, the teacher bank's; plain, _track, _track_refs) each describe their call
 // (RolloutCall) and go through rollout_run below with the actor type of their file; their row tables are one type (RowTables).
@@ -40,6 +41,7 @@
 #include "rq_host.hpp"
 #include "rq_memory.hpp"
 #include "rq_call_memory.hpp"
+#include "rq_env_schedule.hpp"
 
 using rq::fail;
 using rq::DeviceScope;
@@ -188,9 +190,48 @@ struct rq_rng {
     bool initialized = false;
 };
 
-struct rq_wrench_bank;
-struct rq_vehicle_bank;
-struct rq_wind_bank;
+// Row tables on the device, [rows][cols] row-major each, one after another: a moving setpoint (rq_reference_create: one table), M of
+// them (rq_reference_bank_create) or the tables of a schedule (rq_wrench_bank_create and its kin).  Env i of a rollout or of an env the
+// tables are attached to reads the table that begins at row id[i] * rows; a single reference is every env's table 0.
+namespace rqh {
+struct RowTables {
+    const rq_device* dev = nullptr;     // compared, never followed: the device may be gone before its tables
+    int ordinal = 0;
+    uint32_t n_tables = 0, rows = 0;
+    DeviceBuffer<float> d;              // [n_tables * rows][cols] row-major
+    uint64_t uid = fresh_version();     // what an env knows the tables by, beside their address (rq_env::row0_key)
+};
+// the tables of a schedule, of any kind: what an env's slot (rq::EnvSchedule) attaches
+struct ScheduleBank : RowTables {
+    uint32_t attached = 0;              // live envs it is attached to: the bank's destruction is refused while any
+};
+
+// What a kind of row tables is to the host: its words, its shape and what an entry may be.  The two references and the three kinds
+// of schedule are rows of one table (kTableKinds); everything else about a schedule is the kernels'.
+struct TableKind {
+    const char* tables;                 // what a message calls the tables: "reference", "wrench bank"
+    const char* noun;                   // a schedule's kind, as in "wrench schedule", "wrench id" (a reference: none)
+    uint32_t cols;
+    enum Rule { kFinite, kPositive, kNonNegativeColumn } rule;      // every entry finite; and > 0; and those of `rule_col` >= 0
+    int rule_col;                       // (a rule about columns names the column in every message)
+    const char* detach;                 // the entry point that detaches: what a refused destruction names
+};
+// the schedules first, in the order every walk over them takes: it is the order in which refusals are heard
+enum TableKindId { kWrench, kVehicle, kWind, kScheduleKinds, kReference = kScheduleKinds, kReferenceBank, kTableKindCount };
+inline constexpr TableKind kTableKinds[kTableKindCount] = {
+    {"wrench bank", "wrench", 6, TableKind::kFinite, -1, "rq_env_set_wrench_schedule"},
+    {"vehicle bank", "vehicle", 4, TableKind::kPositive, -1, "rq_env_set_vehicle_schedule"},      // factors on mass, inertia, thrust, motor lag
+    {"wind bank", "wind", 4, TableKind::kNonNegativeColumn, 3, "rq_env_set_wind_schedule"},       // air velocity, specific drag
+    {"reference", nullptr, 6, TableKind::kFinite, -1, nullptr},
+    {"reference bank", nullptr, 6, TableKind::kFinite, -1, nullptr},
+};
+}  // namespace rqh
+struct rq_reference : rqh::RowTables {};
+struct rq_reference_bank : rqh::RowTables {};
+struct rq_wrench_bank : rqh::ScheduleBank { int units = RQ_WRENCH_RELATIVE; };
+struct rq_vehicle_bank : rqh::ScheduleBank {};
+struct rq_wind_bank : rqh::ScheduleBank {};
+
 struct rq_env {
     rq_device* dev = nullptr;
     uint64_t uid = fresh_version();   // what the device's caches know this env by, beside its address
@@ -212,23 +253,10 @@ struct rq_env {
     bool row0_valid = false;
     uint64_t row0_key = 0, row0_gen = 0;
     std::vector<uint32_t> row0_ids;
-    // The wrench schedule (rq_env_set_wrench_schedule): the bank, the ids it was attached with, and beside the statistics the [ld]
-    // first rows (id * rows) every stepping kernel reads.  wrench_gen names the attachment (0: none): a chained rollout's hipGraph
-    // is keyed by it.  The bank cannot be destroyed while it is attached, so the pointer is followed.
-    rq_wrench_bank* wrench = nullptr;
-    std::vector<uint32_t> wrench_ids;
-    DeviceBuffer<uint32_t> wrench_row0;
-    uint64_t wrench_gen = 0;
-    // The vehicle schedule (rq_env_set_vehicle_schedule), kept as the wrench schedule is: bank, ids, first rows, attachment number.
-    rq_vehicle_bank* vehicle = nullptr;
-    std::vector<uint32_t> vehicle_ids;
-    DeviceBuffer<uint32_t> vehicle_row0;
-    uint64_t vehicle_gen = 0;
-    // The wind schedule (rq_env_set_wind_schedule), kept alike.
-    rq_wind_bank* wind = nullptr;
-    std::vector<uint32_t> wind_ids;
-    DeviceBuffer<uint32_t> wind_row0;
-    uint64_t wind_gen = 0;
+    // The schedules (rq_env_set_wrench_schedule and its kin), one slot per kind, indexed by rqh::TableKindId: the bank, the ids it was
+    // attached with, the [ld] first rows every stepping kernel reads and the number that names the attachment.
+    rq::EnvSchedule<rqh::ScheduleBank> schedule[rqh::kScheduleKinds];
+    bool has_schedule() const { for (const auto& s : schedule) if (s.bank) return true; return false; }
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
     // epoch-counter bump); one executable graph per distinct argument set: what the nodes carry by value, named once
     struct GraphKey {
@@ -239,15 +267,12 @@ struct rq_env {
         const float* ref = nullptr; uint32_t ref_rows = 0;     // tracked rollouts: the reference table (nullptr: untracked)
         uint32_t row0_at = 0; uint64_t row0_gen = 0;           // a reference bank's per-env first rows and which upload they are (0, 0: none)
         uint32_t interval = 1;                                 // the policy's native interval: the actor nodes of another one are other kernels
-        uint64_t wrench_gen = 0;                               // the env's wrench schedule at construction (0: none): the step nodes carry its pointers
-        uint64_t vehicle_gen = 0;                              // ... and its vehicle schedule
-        uint64_t wind_gen = 0;                                 // ... and its wind schedule
+        uint64_t schedule_gen[rqh::kScheduleKinds] = {};      // the env's schedules at construction (0: none): the step nodes carry their pointers
         bool operator==(const GraphKey& o) const {             // field by field (padding is not compared); cfg is plain floats and words
             return params == o.params && state == o.state && hidden == o.hidden && packed == o.packed && weights == o.weights &&
                    obs == o.obs && flags == o.flags && precision == o.precision && seed == o.seed && sas_mode == o.sas_mode &&
                    sas_seed == o.sas_seed && ls_image == o.ls_image && ref == o.ref && ref_rows == o.ref_rows && row0_at == o.row0_at &&
-                   row0_gen == o.row0_gen && interval == o.interval && wrench_gen == o.wrench_gen && vehicle_gen == o.vehicle_gen &&
-                   wind_gen == o.wind_gen &&
+                   row0_gen == o.row0_gen && interval == o.interval && std::equal(schedule_gen, schedule_gen + rqh::kScheduleKinds, o.schedule_gen) &&
                    std::memcmp(&cfg, &o.cfg, sizeof(rq_env_config)) == 0;
         }
     };
@@ -308,33 +333,6 @@ struct rq_trajectory {
         PinnedBuffer<uint32_t> flight_start_host;
         bool flight_start_valid = false;
     } grad;
-};
-
-// Row tables on the device, [rows][6] row-major each, one after another: a moving setpoint (rq_reference_create: one table), M of
-// them (rq_reference_bank_create) or the tables of a wrench schedule (rq_wrench_bank_create).  Env i of a rollout or of an env the
-// tables are attached to reads the table that begins at row id[i] * rows; a single reference is every env's table 0.
-namespace rqh {
-struct RowTables {
-    const rq_device* dev = nullptr;     // compared, never followed: the device may be gone before its tables
-    int ordinal = 0;
-    uint32_t n_tables = 0, rows = 0;
-    DeviceBuffer<float> d;              // [n_tables * rows][6] row-major
-    uint64_t uid = fresh_version();     // what an env knows the tables by, beside their address (rq_env::row0_key)
-};
-}  // namespace rqh
-struct rq_reference : rqh::RowTables {};
-struct rq_reference_bank : rqh::RowTables {};
-struct rq_wrench_bank : rqh::RowTables {
-    int units = RQ_WRENCH_RELATIVE;
-    uint32_t attached = 0;              // live envs it is attached to: rq_wrench_bank_destroy is refused while any
-};
-// the tables of a vehicle schedule (rq_vehicle_bank_create): `d` is [n_tables * rows][4] row-major, positive factors
-struct rq_vehicle_bank : rqh::RowTables {
-    uint32_t attached = 0;              // live envs it is attached to: rq_vehicle_bank_destroy is refused while any
-};
-// the tables of a wind schedule (rq_wind_bank_create): `d` is [n_tables * rows][4] row-major, air velocity and specific drag
-struct rq_wind_bank : rqh::RowTables {
-    uint32_t attached = 0;              // live envs it is attached to: rq_wind_bank_destroy is refused while any
 };
 
 struct rq_policy {
@@ -472,20 +470,34 @@ int state_make_private(rq_state* s, bool keep);
 inline rq::Batch batch_of(const rq_env* env) { return {env->n, env->ld, env->offset}; }
 // the env's tracking statistics, allocated and zeroed (on the device's stream) at their first use; call inside a DeviceScope
 int env_track_stats(rq_env* env, float** sum_sq, uint32_t** steps);
-// The env's wrench schedule as the kernels take it (*wr all-null: none attached).  Every call that steps asks here before anything is
-// enqueued: a bank with fewer rows than episode_step_limit is refused (`who`: the caller's name; the config may have changed since
-// the schedule was attached).
-int env_wrench(const char* who, const rq_env* env, rq::WrenchPtrs* wr);
-// ... and what fused mode cannot fly while a schedule is attached, refused naming the schedule (`what`: bf16 / f16x2 policy, ...)
-int wrench_refuses_fused(const char* who, const char* what);
-// The env's vehicle schedule likewise (*vh all-null: none attached; fewer rows than episode_step_limit refused), and what fused mode
-// cannot fly while one is attached: a bf16 / f16x2 policy, a SampleAndSquash stage, a teacher bank, a wrench schedule beside it.
-int env_vehicle(const char* who, const rq_env* env, rq::VehiclePtrs* vh);
-int vehicle_refuses_fused(const char* who, const char* what);
-// The env's wind schedule likewise; fused mode cannot fly it beside a bf16 / f16x2 policy, a SampleAndSquash stage, a teacher bank or
-// another schedule.
-int env_wind(const char* who, const rq_env* env, rq::WindPtrs* wd);
-int wind_refuses_fused(const char* who, const char* what);
+// ---- rq_capi_rollout.cpp: the env's schedules ----
+// One schedule as the kernels take it, before it is typed (all-null: none attached).  `flag`: the wrench bank's units, 1 = relative.
+struct SchedulePtrs { const float* rows = nullptr; const uint32_t* row0 = nullptr; uint32_t n_rows = 0, flag = 0; };
+int schedule_too_short(const char* who, const rq_env* env, int kind);      // the refusal below, worded
+// The env's schedules, p[kScheduleKinds] in kind order.  Every call that steps asks here before anything is enqueued: a bank with
+// fewer rows than episode_step_limit is refused (`who`: the caller's name; the config may have changed since the schedule was
+// attached).  Nothing is allocated and no string made unless it refuses: rq_step asks on every call.
+inline int env_schedules(const char* who, const rq_env* env, SchedulePtrs* p) {
+    for (int k = 0; k < kScheduleKinds; ++k) {
+        p[k] = SchedulePtrs{};
+        const auto& s = env->schedule[k];
+        if (!s.bank) continue;
+        if (s.bank->rows < env->cfg.episode_step_limit) return schedule_too_short(who, env, k);
+        p[k] = {s.bank->d, s.row0, s.bank->rows,
+                k == kWrench && static_cast<const rq_wrench_bank*>(s.bank)->units == RQ_WRENCH_RELATIVE ? 1u : 0u};
+    }
+    return RQ_OK;
+}
+// ... typed, for the launch descriptions (rq::EnvStepLaunch, rq::FusedArgs): the kernels' argument types are one per kind
+template <typename Launch>
+void set_schedules(Launch& l, const SchedulePtrs* p) {
+    l.wr = {p[kWrench].rows, p[kWrench].row0, p[kWrench].n_rows, p[kWrench].flag};
+    l.vh = {p[kVehicle].rows, p[kVehicle].row0, p[kVehicle].n_rows, 0u};
+    l.wd = {p[kWind].rows, p[kWind].row0, p[kWind].n_rows, 0u};
+}
+// What fused mode cannot fly while a schedule of `kind` is attached, refused naming the schedule (`what`: a bf16 / f16x2 policy, a
+// SampleAndSquash stage, a teacher bank, another schedule beside it); nothing runs chained in its place.
+int refuses_fused(const char* who, int kind, const char* what);
 
 // ---- rq_small_batch.cpp: the small-batch loop (rq_device::mailbox, obs_cache, spec) ----
 void small_batch_setup(rq_device* dev);      // rq_device_create: settings
@@ -562,15 +574,13 @@ struct RolloutCall {
     const RowTables* tables;          // a tracked rollout's reference or reference bank (null: untracked)
     const uint32_t* reference_id;     // a reference bank's table per env (null: `tables` is one reference, every env's table)
 };
-// What rollout_run gathers on its way and the launches take: where a recording goes, the tracked rollout's pointers, the env's wrench
-// schedule and the env's configuration as the kernels take it.
+// What rollout_run gathers on its way and the launches take: where a recording goes, the tracked rollout's pointers, the env's
+// schedules and the env's configuration as the kernels take it.
 struct RolloutFrame {
     rq::TrajPtrs tp{nullptr, nullptr, nullptr, nullptr, 0};
     rq::TrackPtrs trk{};                                          // ref != nullptr: a tracked rollout
     uint64_t row0_gen = 0;                                         // a reference bank's rollout: rq_env::row0_gen
-    rq::WrenchPtrs wr{};                                           // rows != nullptr: the env carries a wrench schedule (rollout_check)
-    rq::VehiclePtrs vh{};                                          // rows != nullptr: the env carries a vehicle schedule (rollout_check)
-    rq::WindPtrs wd{};                                             // rows != nullptr: the env carries a wind schedule (rollout_check)
+    SchedulePtrs sched[kScheduleKinds];                            // rows != nullptr: the env carries a schedule of that kind (rollout_check)
     rq::Batch b; rq::StepCfg sc; rq::NoiseCfg nc; rq::SampleCfg smp; bool noise;
 };
 // a refusal inside the frame, worded as RQ_REQUIRE words it but begun with the call's own name
@@ -579,8 +589,8 @@ struct RolloutFrame {
         if (!(cond)) return rq::fail((status), std::string(who) + ": " + (msg));   \
     } while (0)
 // The pieces of rollout_run, in its order.  rollout_check, before the call's DeviceScope: what every rollout refuses (`actor`: the
-// caller was given what acts), where a recording goes and the env's wrench schedule.  rollout_check_tables: a tracked rollout's
-// tables and, with ids, every id (one outside the bank is refused naming the env).  rollout_track, inside the scope: the tracked
+// caller was given what acts), where a recording goes, the env's schedules and which of them fused mode does not fly side by side.
+// rollout_check_tables: a tracked rollout's tables and, with ids, every id (one outside the bank is refused naming the env).  rollout_track, inside the scope: the tracked
 // rollout's pointers; with ids the per-env first rows go to the device unless the env holds them for (tables, ids) already.
 // rollout_begin, after the actor's preparation: the observation cache dropped, the state private, the env's configuration as the
 // kernels take it, the `done` rows preset.  rollout_end: the noise epoch, the recording's length and the state's version move on.
@@ -589,9 +599,9 @@ int rollout_check_tables(const RolloutCall& c);
 int rollout_track(RolloutFrame& f, const RolloutCall& c);
 int rollout_begin(RolloutFrame& f, const RolloutCall& c);
 void rollout_end(const RolloutCall& c);
-// One id per env -> the [env->ld] first rows (id * rows; null ids: table 0) at dst on the device, synchronised before the pageable
-// rows go away.  `what` begins the message of a failed host allocation.  A reference bank's rows and a wrench schedule's.
-int upload_first_rows(const char* what, rq_device* dev, const rq_env* env, const uint32_t* ids, uint32_t rows, uint32_t* dst);
+// A failed rq::upload_first_rows or rq::EnvSchedule::attach, worded: `what` ("reference bank", "wrench schedule") begins the message
+// of a failed allocation.
+int first_rows_failed(const char* what, const rq::FirstRowsStatus& s);
 // a failed HIP call of a shared piece, reported as the caller's own RQ_HIP would: `who` is the caller's name, `what` the call
 inline int hip_failed(const char* who, const char* what, hipError_t e) {
     return fail(e == hipErrorOutOfMemory ? RQ_ERR_OUT_OF_MEMORY : RQ_ERR_HIP, std::string(who) + ": " + what + " -> " + hipGetErrorString(e));

@@ -162,9 +162,8 @@ rq_policy* speculation_candidate(rq_device* dev, const rq_env* env, bool cache_o
     if (!cache_obs) return nullptr;
     speculation_unused(dev);      // the previous step's speculated policy step, if nobody took it (this may suspend speculation)
     const Speculation& sp = dev->spec;
-    // (an env that carries a wrench, a vehicle or a wind schedule is stepped by plain launches: neither speculated on nor handed to the
-    // resident executor)
-    rq_policy* pol = sp.enabled && !sp.suspended && action && !env->wrench && !env->vehicle && !env->wind ? sp.last_policy : nullptr;
+    // (an env that carries a schedule is stepped by plain launches: neither speculated on nor handed to the resident executor)
+    rq_policy* pol = sp.enabled && !sp.suspended && action && !env->has_schedule() ? sp.last_policy : nullptr;
     return pol && policy_registry(pol, 0) && pol->dev == dev && pol->batch == env->n && pol->ld == env->ld && pol->hidden &&
            pol->hidden_alt && !pol->needs_reset && pol->sas_mode != RQ_SAS_SAMPLE && pol->native_interval == 1 ? pol : nullptr;
 }

@@ -110,8 +110,8 @@ def suite(rows, dt):
 def check_tables(tables):
     """The tables of a ``WrenchBank`` as the C layer takes them, or ValueError: float32 [M >= 1, rows >= 1, 6], finite, contiguous;
     a list of M ``[rows, 6]`` tables of equal length is stacked."""
-    from .l2f import _stacked_tables
-    return _stacked_tables(tables, "wrench", "force, torque", "raptor_amd.disturbances")
+    from . import schedules
+    return schedules.check_tables(schedules.WRENCH, tables)
 
 
 def check_units(units):
@@ -122,16 +122,8 @@ def check_units(units):
 
 def check_wrench_ids(ids, n_tables, n_envs):
     """One table id per env, each in [0, n_tables) -> contiguous uint32; ValueError otherwise."""
-    a = np.asarray(ids)
-    if a.ndim != 1 or a.size != int(n_envs):
-        raise ValueError(f"wrench ids must hold one id per env: {a.size if a.ndim == 1 else a.shape} ids for {int(n_envs)} envs")
-    if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
-        raise ValueError("wrench ids must be integers")
-    a = a.astype(np.int64)
-    bad = np.flatnonzero((a < 0) | (a >= int(n_tables)))
-    if bad.size:
-        raise ValueError(f"wrench id out of range: env {int(bad[0])} names table {int(a[bad[0]])} of a bank of {int(n_tables)}")
-    return np.ascontiguousarray(a.astype(np.uint32))
+    from . import schedules
+    return schedules.check_ids(schedules.WRENCH, ids, n_tables, n_envs)
 
 
 def compose(base6, mass, gravity, rotor_xy, row, units=RELATIVE):

@@ -33,7 +33,7 @@ import weakref
 
 import numpy as np
 
-from . import _lib
+from . import _lib, schedules
 from ._lib import (ACTION_DIM, OBSERVATION_DIM, PARAM_DIM, STATE_DIM, ROLLOUT_AUTORESET, ROLLOUT_CHAINED,
                    ROLLOUT_FUSED, EnvConfig, RaptorQuadError)
 
@@ -148,49 +148,13 @@ class Device:
         return n.value
 
 
-def _table(table, noun, columns, builder):
-    """One ``[rows, 6]`` table as the C layer takes it, or ValueError: float32, C-contiguous, [rows >= 1, 6], finite.  ``noun``:
-    "reference" / "wrench"; ``columns``: what the six columns are; ``builder``: the module that builds such tables."""
-    if not isinstance(table, np.ndarray) or table.dtype != np.float32:
-        raise ValueError(f"a {noun} table is a float32 NumPy array [rows, 6] ({builder} builds them)")
-    if table.ndim != 2 or table.shape[1] != 6 or table.shape[0] < 1:
-        raise ValueError(f"a {noun} table has shape [rows >= 1, 6]: {columns}; got {table.shape}")
-    if not np.isfinite(table).all():
-        raise ValueError(f"a {noun} table holds finite entries only")
-    return np.ascontiguousarray(table)
-
-
-def _stacked_tables(tables, noun, columns, builder):
-    """The tables of a bank (``ReferenceBank``, ``WrenchBank``) as the C layer takes them, or ValueError: float32 [M >= 1, rows >= 1,
-    6], finite, contiguous; a list of M ``[rows, 6]`` tables of equal length is stacked."""
-    if isinstance(tables, (list, tuple)):
-        if not tables:
-            raise ValueError(f"a {noun} bank holds at least one table")
-        rows = [_table(t, noun, columns, builder) for t in tables]
-        if len({t.shape[0] for t in rows}) != 1:
-            raise ValueError(f"the tables of a {noun} bank have the same number of rows; got " + ", ".join(str(t.shape[0]) for t in rows))
-        tables = np.stack(rows)
-    if not isinstance(tables, np.ndarray) or tables.dtype != np.float32:
-        raise ValueError(f"a {noun} bank is a float32 NumPy array [M, rows, 6] or a list of M [rows, 6] tables")
-    if tables.ndim != 3 or tables.shape[2] != 6 or tables.shape[0] < 1 or tables.shape[1] < 1:
-        raise ValueError(f"a {noun} bank has shape [M >= 1, rows >= 1, 6]; got {tables.shape}")
-    if not np.isfinite(tables).all():
-        raise ValueError(f"a {noun} table holds finite entries only")
-    if tables.shape[0] * tables.shape[1] >= 1 << 28:
-        raise ValueError(f"a {noun} bank holds fewer than 2^28 rows in all")
-    return np.ascontiguousarray(tables)
-
-
-_REFERENCE_NOUNS = ("reference", "target position, target velocity", "raptor_amd.tracking")
-
-
 class Reference:
     """A moving setpoint for ``vector.rollout(..., reference=ref)``: ``table`` [rows, 6] float32, columns 0..2 the target position and
     3..5 the target linear velocity in the world frame (``raptor_amd.tracking.lissajous`` / ``hold``).  An env reads the row of its
     own episode step count, so ``rows`` must cover ``episode_step_limit``.  The table is copied to ``device`` once, here."""
 
     def __init__(self, device, table):
-        t = _table(table, *_REFERENCE_NOUNS)    # refused before the device is touched
+        t = schedules.check_table(schedules.REFERENCE, table)    # refused before the device is touched
         h = C.c_void_p()
         _lib.call("rq_reference_create", device._h, _lib.fptr(t), int(t.shape[0]), C.byref(h))
         self._h = h
@@ -206,7 +170,7 @@ class ReferenceBank:
     with ``Reference(tables[ids[i]])``.  The tables are copied to ``device`` once, here (``raptor_amd.tracking.suite`` makes some)."""
 
     def __init__(self, device, tables):
-        t = _stacked_tables(tables, *_REFERENCE_NOUNS)      # refused before the device is touched
+        t = schedules.check_tables(schedules.REFERENCE, tables)      # refused before the device is touched
         h = C.c_void_p()
         _lib.call("rq_reference_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), C.byref(h))
         self._h = h
@@ -216,66 +180,63 @@ class ReferenceBank:
         self._fin = weakref.finalize(self, _lib.load().rq_reference_bank_destroy, h)
 
 
-class WrenchBank:
+class _ScheduleBank:
+    """M tables of one kind of schedule on ``device``: checked (``schedules.check_tables``), copied once, destroyed with the object.
+    A subclass names its ``_kind`` and may add arguments to the library's create call (``_create_arguments``)."""
+    _kind = None
+
+    def __init__(self, device, tables):
+        t = schedules.check_tables(self._kind, tables)          # refused before the device is touched
+        extra = self._create_arguments()
+        h = C.c_void_p()
+        _lib.call(f"rq_{self._kind.noun}_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), *extra, C.byref(h))
+        self._h = h
+        self._device = device
+        self.n_tables = int(t.shape[0])
+        self.rows = int(t.shape[1])
+        # (the library refuses to destroy a bank that is still attached to a live env; the envs hold their bank, so it outlives them)
+        self._fin = weakref.finalize(self, getattr(_lib.load(), f"rq_{self._kind.noun}_bank_destroy"), h)
+
+    def _create_arguments(self):
+        return ()
+
+
+class WrenchBank(_ScheduleBank):
     """M wrench tables of the same length for ``env.set_wrench_schedule(bank, ids)``: ``tables`` float32 [M, rows, 6] (or a list of M
     [rows, 6] tables; ``raptor_amd.disturbances`` builds them), columns 0..2 a force in the world frame and 3..5 a torque in the body
     frame.  ``units``: "relative" (multiples of m g and of m g arm, the default) or "absolute" (N and N m).  While the bank is
     attached to an env, every transition of env i adds the row of its own episode step count of table ``ids[i]`` to the per-episode
     disturbance (include/raptor_quad.h "Wrench schedule").  The tables are copied to ``device`` once, here."""
+    _kind = schedules.WRENCH
 
     def __init__(self, device, tables, units="relative"):
-        from . import disturbances
-        t = disturbances.check_tables(tables)          # refused before the device is touched
-        u = disturbances.check_units(units)
-        h = C.c_void_p()
-        _lib.call("rq_wrench_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), u, C.byref(h))
-        self._h = h
-        self._device = device
-        self.n_tables = int(t.shape[0])
-        self.rows = int(t.shape[1])
         self.units = units
-        # (the library refuses to destroy a bank that is still attached to a live env; the envs hold their bank, so it outlives them)
-        self._fin = weakref.finalize(self, _lib.load().rq_wrench_bank_destroy, h)
+        super().__init__(device, tables)
+
+    def _create_arguments(self):
+        from .disturbances import check_units
+        return (check_units(self.units),)
 
 
-class VehicleBank:
+class VehicleBank(_ScheduleBank):
     """M vehicle tables of the same length for ``env.set_vehicle_schedule(bank, ids)``: ``tables`` float32 [M, rows, 4] (or a list of
     M [rows, 4] tables; ``raptor_amd.vehicles`` builds them), positive factors on the mass, the inertia, the thrust curve and the
     motor time constant.  While the bank is attached to an env, every transition of env i is computed from its parameters times
     the row of its own episode step count of table ``ids[i]`` (include/raptor_quad.h "Vehicle schedule").  The tables are copied
     to ``device`` once, here."""
-
-    def __init__(self, device, tables):
-        from . import vehicles
-        t = vehicles.check_tables(tables)          # refused before the device is touched
-        h = C.c_void_p()
-        _lib.call("rq_vehicle_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), C.byref(h))
-        self._h = h
-        self._device = device
-        self.n_tables = int(t.shape[0])
-        self.rows = int(t.shape[1])
-        # (the library refuses to destroy a bank that is still attached to a live env; the envs hold their bank, so it outlives them)
-        self._fin = weakref.finalize(self, _lib.load().rq_vehicle_bank_destroy, h)
+    _kind = schedules.VEHICLE
 
 
-class WindBank:
+class WindBank(_ScheduleBank):
     """M wind tables of the same length for ``env.set_wind_schedule(bank, ids)``: ``tables`` float32 [M, rows, 4] (or a list of M
     [rows, 4] tables; ``raptor_amd.winds`` builds them), the air velocity in the world frame (m/s) and the specific drag (1/s).
     While the bank is attached to an env, every transition of env i is computed with the linear drag against the air of the row of
     its own episode step count of table ``ids[i]`` (include/raptor_quad.h "Wind schedule").  The tables are copied to ``device``
     once, here."""
+    _kind = schedules.WIND
 
-    def __init__(self, device, tables):
-        from . import winds
-        t = winds.check_tables(tables)             # refused before the device is touched
-        h = C.c_void_p()
-        _lib.call("rq_wind_bank_create", device._h, _lib.fptr(t), int(t.shape[0]), int(t.shape[1]), C.byref(h))
-        self._h = h
-        self._device = device
-        self.n_tables = int(t.shape[0])
-        self.rows = int(t.shape[1])
-        # (the library refuses to destroy a bank that is still attached to a live env; the envs hold their bank, so it outlives them)
-        self._fin = weakref.finalize(self, _lib.load().rq_wind_bank_destroy, h)
+
+_BANKS = {schedules.WRENCH: WrenchBank, schedules.VEHICLE: VehicleBank, schedules.WIND: WindBank}
 
 
 def _checked_reference(reference, reference_ids, n_envs):
@@ -291,56 +252,6 @@ def _checked_reference(reference, reference_ids, n_envs):
     if reference is not None and not isinstance(reference, Reference):
         raise ValueError("reference must be an l2f.Reference or an l2f.ReferenceBank")
     return None
-
-
-def _checked_wrench_ids(env, wrench_ids, ref_ids, n_envs):
-    """What ``wrench_ids`` of ``PolicyBank.evaluate`` / ``TeacherBank.closed_loop`` must be, before any library call -> the ids as
-    uint32, or None (none given); ValueError otherwise."""
-    if wrench_ids is None:
-        return None
-    schedule = getattr(env, "wrench_schedule", None)
-    if schedule is None:
-        raise ValueError("wrench_ids name tables of the env's wrench schedule: attach one first (env.set_wrench_schedule(bank))")
-    if ref_ids is not None:
-        raise ValueError("wrench_ids group the tracking error by disturbance scenario and reference_ids by setpoint: give one of them "
-                         "(a single l2f.Reference goes with wrench_ids)")
-    from .disturbances import check_wrench_ids
-    return check_wrench_ids(wrench_ids, schedule[0].n_tables, n_envs)
-
-
-def _checked_vehicle_ids(env, vehicle_ids, wrench_ids, ref_ids, n_envs):
-    """What ``vehicle_ids`` of ``PolicyBank.evaluate`` / ``TeacherBank.closed_loop`` must be, before any library call -> the ids as
-    uint32, or None (none given); ValueError otherwise."""
-    if vehicle_ids is None:
-        return None
-    schedule = getattr(env, "vehicle_schedule", None)
-    if schedule is None:
-        raise ValueError("vehicle_ids name tables of the env's vehicle schedule: attach one first (env.set_vehicle_schedule(bank))")
-    if wrench_ids is not None:
-        raise ValueError("vehicle_ids group the tracking error by vehicle scenario and wrench_ids by disturbance: give one of them")
-    if ref_ids is not None:
-        raise ValueError("vehicle_ids group the tracking error by vehicle scenario and reference_ids by setpoint: give one of them "
-                         "(a single l2f.Reference goes with vehicle_ids)")
-    from .vehicles import check_vehicle_ids
-    return check_vehicle_ids(vehicle_ids, schedule[0].n_tables, n_envs)
-
-
-def _checked_wind_ids(env, wind_ids, wrench_ids, vehicle_ids, ref_ids, n_envs):
-    """What ``wind_ids`` of ``PolicyBank.evaluate`` must be, before any library call -> the ids as uint32, or None (none given);
-    ValueError otherwise."""
-    if wind_ids is None:
-        return None
-    schedule = getattr(env, "wind_schedule", None)
-    if schedule is None:
-        raise ValueError("wind_ids name tables of the env's wind schedule: attach one first (env.set_wind_schedule(bank))")
-    if wrench_ids is not None or vehicle_ids is not None:
-        raise ValueError("wind_ids group the tracking error by wind scenario, wrench_ids by disturbance and vehicle_ids by vehicle "
-                         "scenario: give one of them")
-    if ref_ids is not None:
-        raise ValueError("wind_ids group the tracking error by wind scenario and reference_ids by setpoint: give one of them "
-                         "(a single l2f.Reference goes with wind_ids)")
-    from .winds import check_wind_ids
-    return check_wind_ids(wind_ids, schedule[0].n_tables, n_envs)
 
 
 _MODES = {"fused": ROLLOUT_FUSED, "chained": ROLLOUT_CHAINED}
@@ -368,18 +279,14 @@ def _rollout_call(entry, device, env, params, state, actor_handle, ids, rng, n_s
     return _lib.call("rq_rollout_record", *args, traj)
 
 
-def tracking_rmse(env, reference, ref_ids, w_ids, actor_ids, n_actors, v_ids=None, wind_ids=None):
+def tracking_rmse(env, reference, ref_ids, schedule_ids, actor_ids, n_actors):
     """``tracking_rmse`` of a bank's closed-loop table, from ``env.tracking_error()`` grouped by actor (policy or teacher): [n_actors,
-    M] over the disturbance scenarios (``w_ids``), the vehicle scenarios (``v_ids``), the wind scenarios (``wind_ids``) or the setpoints (``ref_ids`` of a
-    ``ReferenceBank``), [n_actors] on a single ``Reference``."""
+    M] over the scenarios of a schedule (``schedule_ids``: what ``schedules.checked_schedule_ids`` answered - disturbances, vehicles or winds)
+    or the setpoints (``ref_ids`` of a ``ReferenceBank``), [n_actors] on a single ``Reference``."""
     from .tracking import reference_tracking_table
     sum_sq, steps = env.tracking_error()
-    if wind_ids is not None:
-        return reference_tracking_table(sum_sq, steps, wind_ids, env.wind_schedule[0].n_tables, actor_ids, n_actors)
-    if v_ids is not None:
-        return reference_tracking_table(sum_sq, steps, v_ids, env.vehicle_schedule[0].n_tables, actor_ids, n_actors)
-    if w_ids is not None:
-        return reference_tracking_table(sum_sq, steps, w_ids, env.wrench_schedule[0].n_tables, actor_ids, n_actors)
+    if schedule_ids is not None:
+        return reference_tracking_table(sum_sq, steps, schedule_ids.ids, schedule_ids.bank.n_tables, actor_ids, n_actors)
     if ref_ids is not None:
         return reference_tracking_table(sum_sq, steps, ref_ids, reference.n_references, actor_ids, n_actors)
     from .policy_bank import policy_tracking_table
@@ -591,80 +498,64 @@ class VectorModule:
             def reset_statistics(self):
                 _lib.call("rq_env_reset_statistics", self._require("environment"))
 
-            # --- wrench schedule (scheduled gusts, pokes, payloads: raptor_amd.disturbances) ---
-            _wrench = None
+            # --- the schedules: wrench (scheduled gusts, pokes, payloads: raptor_amd.disturbances), vehicle (payloads, battery sag,
+            # slow motors: raptor_amd.vehicles), wind (air that moves and drags: raptor_amd.winds).  One implementation; what is
+            # attached of a kind is kept as (bank, ids) under _<noun>. ---
+            _wrench = _vehicle = _wind = None
+
+            def _set_schedule(self, kind, bank, ids):
+                if not isinstance(bank, _BANKS[kind]):
+                    raise ValueError(f"bank must be an l2f.{_BANKS[kind].__name__} (clear_{kind.noun}_schedule() detaches)")
+                a = (np.zeros(mod.N_ENVIRONMENTS, np.uint32) if ids is None
+                     else schedules.check_ids(kind, ids, bank.n_tables, mod.N_ENVIRONMENTS))
+                _lib.call(f"rq_env_set_{kind.noun}_schedule", self._require("environment"), bank._h, a.ctypes.data)
+                setattr(self, "_" + kind.noun, (bank, a.copy()))
+
+            def _clear_schedule(self, kind):
+                if self._h is not None:
+                    _lib.call(f"rq_env_set_{kind.noun}_schedule", self._h, None, None)
+                setattr(self, "_" + kind.noun, None)
+
+            def _schedule(self, kind):
+                attached = getattr(self, "_" + kind.noun)
+                return None if attached is None else (attached[0], attached[1].copy())
 
             def set_wrench_schedule(self, bank, ids=None):
                 """Attach ``bank`` (an ``l2f.WrenchBank``): from now on every transition of env i, in every call that steps this
                 env, is computed with the row of its episode step count of table ``ids[i]`` ([N] integers, free per env; None:
                 table 0 for every env) added to its per-episode disturbance.  The tables must cover ``episode_step_limit``."""
-                if not isinstance(bank, WrenchBank):
-                    raise ValueError("bank must be an l2f.WrenchBank (clear_wrench_schedule() detaches)")
-                from .disturbances import check_wrench_ids
-                a = (np.zeros(mod.N_ENVIRONMENTS, np.uint32) if ids is None
-                     else check_wrench_ids(ids, bank.n_tables, mod.N_ENVIRONMENTS))
-                _lib.call("rq_env_set_wrench_schedule", self._require("environment"), bank._h, a.ctypes.data)
-                self._wrench = (bank, a.copy())
-
-            def clear_wrench_schedule(self):
-                if self._h is not None:
-                    _lib.call("rq_env_set_wrench_schedule", self._h, None, None)
-                self._wrench = None
-
-            @property
-            def wrench_schedule(self):
-                """(bank, ids) of the attached schedule, or None."""
-                return None if self._wrench is None else (self._wrench[0], self._wrench[1].copy())
-
-            # --- vehicle schedule (payloads, battery sag, slow motors: raptor_amd.vehicles) ---
-            _vehicle = None
+                self._set_schedule(schedules.WRENCH, bank, ids)
 
             def set_vehicle_schedule(self, bank, ids=None):
                 """Attach ``bank`` (an ``l2f.VehicleBank``): from now on every transition of env i, in every call that steps this
                 env, is computed from its parameters times the row of its episode step count of table ``ids[i]`` ([N] integers,
                 free per env; None: table 0 for every env).  The tables must cover ``episode_step_limit``."""
-                if not isinstance(bank, VehicleBank):
-                    raise ValueError("bank must be an l2f.VehicleBank (clear_vehicle_schedule() detaches)")
-                from .vehicles import check_vehicle_ids
-                a = (np.zeros(mod.N_ENVIRONMENTS, np.uint32) if ids is None
-                     else check_vehicle_ids(ids, bank.n_tables, mod.N_ENVIRONMENTS))
-                _lib.call("rq_env_set_vehicle_schedule", self._require("environment"), bank._h, a.ctypes.data)
-                self._vehicle = (bank, a.copy())
-
-            def clear_vehicle_schedule(self):
-                if self._h is not None:
-                    _lib.call("rq_env_set_vehicle_schedule", self._h, None, None)
-                self._vehicle = None
-
-            @property
-            def vehicle_schedule(self):
-                """(bank, ids) of the attached schedule, or None."""
-                return None if self._vehicle is None else (self._vehicle[0], self._vehicle[1].copy())
-
-            # --- wind schedule (air that moves and drags: raptor_amd.winds) ---
-            _wind = None
+                self._set_schedule(schedules.VEHICLE, bank, ids)
 
             def set_wind_schedule(self, bank, ids=None):
                 """Attach ``bank`` (an ``l2f.WindBank``): from now on every transition of env i, in every call that steps this env,
                 is computed with the drag against the air of the row of its episode step count of table ``ids[i]`` ([N] integers,
                 free per env; None: table 0 for every env).  The tables must cover ``episode_step_limit``."""
-                if not isinstance(bank, WindBank):
-                    raise ValueError("bank must be an l2f.WindBank (clear_wind_schedule() detaches)")
-                from .winds import check_wind_ids
-                a = (np.zeros(mod.N_ENVIRONMENTS, np.uint32) if ids is None
-                     else check_wind_ids(ids, bank.n_tables, mod.N_ENVIRONMENTS))
-                _lib.call("rq_env_set_wind_schedule", self._require("environment"), bank._h, a.ctypes.data)
-                self._wind = (bank, a.copy())
+                self._set_schedule(schedules.WIND, bank, ids)
 
-            def clear_wind_schedule(self):
-                if self._h is not None:
-                    _lib.call("rq_env_set_wind_schedule", self._h, None, None)
-                self._wind = None
+            def clear_wrench_schedule(self): self._clear_schedule(schedules.WRENCH)
+            def clear_vehicle_schedule(self): self._clear_schedule(schedules.VEHICLE)
+            def clear_wind_schedule(self): self._clear_schedule(schedules.WIND)
+
+            @property
+            def wrench_schedule(self):
+                """(bank, ids) of the attached schedule, or None."""
+                return self._schedule(schedules.WRENCH)
+
+            @property
+            def vehicle_schedule(self):
+                """(bank, ids) of the attached schedule, or None."""
+                return self._schedule(schedules.VEHICLE)
 
             @property
             def wind_schedule(self):
                 """(bank, ids) of the attached schedule, or None."""
-                return None if self._wind is None else (self._wind[0], self._wind[1].copy())
+                return self._schedule(schedules.WIND)
 
             def tracking_error(self):
                 """-> (sum_sq [N] float32, steps [N] uint32): per env, the running sum of |p - p_ref|^2 over the steps it took in

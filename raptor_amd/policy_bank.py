@@ -216,22 +216,18 @@ class PolicyBank:
         vehicle scenarios, and ``wind_ids`` those of its wind schedule (``env.set_wind_schedule(bank)``): [P, M] over the wind
         scenarios.  At most one of ``wrench_ids``, ``vehicle_ids`` and ``wind_ids``: two together are refused."""
         ids = block_policy_assignment(vector.N_ENVIRONMENTS, self.n_policies) if policy_ids is None else policy_ids
-        from .l2f import _checked_reference, _checked_vehicle_ids, _checked_wind_ids, _checked_wrench_ids, tracking_rmse
+        from . import schedules
+        from .l2f import _checked_reference, tracking_rmse
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
-        w_ids = _checked_wrench_ids(env, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
-        v_ids = _checked_vehicle_ids(env, vehicle_ids, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
-        a_ids = _checked_wind_ids(env, wind_ids, wrench_ids, vehicle_ids, ref_ids, vector.N_ENVIRONMENTS)
-        if w_ids is not None:
-            env.set_wrench_schedule(env.wrench_schedule[0], w_ids)
-        if v_ids is not None:
-            env.set_vehicle_schedule(env.vehicle_schedule[0], v_ids)
-        if a_ids is not None:
-            env.set_wind_schedule(env.wind_schedule[0], a_ids)
+        given = {schedules.WRENCH: wrench_ids, schedules.VEHICLE: vehicle_ids, schedules.WIND: wind_ids}
+        s_ids = schedules.checked_schedule_ids(env, given, ref_ids, vector.N_ENVIRONMENTS)
+        if s_ids is not None:
+            s_ids.attach(env)
         env.reset_statistics()
         self.reset()
         self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
                  reference_ids=reference_ids)
         table = policy_episode_table(env, ids, self.n_policies)
         if reference is not None:
-            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, w_ids, ids, self.n_policies, v_ids, a_ids)
+            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, s_ids, ids, self.n_policies)
         return table

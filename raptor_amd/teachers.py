@@ -179,21 +179,20 @@ class TeacherBank:
         attached bank and, on an ``l2f.Reference``, ``tracking_rmse`` is [K, M] over the scenarios (``mode="chained"``: the fused
         teacher kernel does not fly a schedule).  ``vehicle_ids`` likewise name the tables of the env's vehicle schedule; giving both
         is refused."""
-        from .l2f import _checked_reference, _checked_vehicle_ids, _checked_wrench_ids, tracking_rmse
+        from . import schedules
+        from .l2f import _checked_reference, tracking_rmse
         ids = check_teacher_ids(teacher_ids, vector.N_ENVIRONMENTS)
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
-        w_ids = _checked_wrench_ids(env, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
-        v_ids = _checked_vehicle_ids(env, vehicle_ids, wrench_ids, ref_ids, vector.N_ENVIRONMENTS)
-        if w_ids is not None:
-            env.set_wrench_schedule(env.wrench_schedule[0], w_ids)
-        if v_ids is not None:
-            env.set_vehicle_schedule(env.vehicle_schedule[0], v_ids)
+        given = {schedules.WRENCH: wrench_ids, schedules.VEHICLE: vehicle_ids}
+        s_ids = schedules.checked_schedule_ids(env, given, ref_ids, vector.N_ENVIRONMENTS)
+        if s_ids is not None:
+            s_ids.attach(env)
         env.reset_statistics()
         self.fly(vector, device, env, params, state, rng, n_steps, ids, mode=mode, autoreset=autoreset, reference=reference,
                  reference_ids=reference_ids)
         table = teacher_episode_table(env, ids, self.n_teachers)
         if reference is not None:
-            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, w_ids, ids, self.n_teachers, v_ids)
+            table["tracking_rmse"] = tracking_rmse(env, reference, ref_ids, s_ids, ids, self.n_teachers)
         return table
 
 

@@ -121,53 +121,17 @@ def suite(rows, dt):
     }
 
 
-def _one_table(table):
-    if not isinstance(table, np.ndarray) or table.dtype != np.float32:
-        raise ValueError("a wind table is a float32 NumPy array [rows, 4] (raptor_amd.winds builds them)")
-    if table.ndim != 2 or table.shape[1] != 4 or table.shape[0] < 1:
-        raise ValueError(f"a wind table has shape [rows >= 1, 4]: {', '.join(WIND_NAMES)}; got {table.shape}")
-    return table
-
-
 def check_tables(tables):
     """The tables of a ``WindBank`` as the C layer takes them, or ValueError: float32 [M >= 1, rows >= 1, 4], every entry finite, the
     drag column >= 0, contiguous; a list of M ``[rows, 4]`` tables of equal length is stacked."""
-    if isinstance(tables, (list, tuple)):
-        if not tables:
-            raise ValueError("a wind bank holds at least one table")
-        rows = [_one_table(t) for t in tables]
-        if len({t.shape[0] for t in rows}) != 1:
-            raise ValueError("the tables of a wind bank have the same number of rows; got " + ", ".join(str(t.shape[0]) for t in rows))
-        tables = np.stack(rows)
-    if not isinstance(tables, np.ndarray) or tables.dtype != np.float32:
-        raise ValueError("a wind bank is a float32 NumPy array [M, rows, 4] or a list of M [rows, 4] tables")
-    if tables.ndim != 3 or tables.shape[2] != 4 or tables.shape[0] < 1 or tables.shape[1] < 1:
-        raise ValueError(f"a wind bank has shape [M >= 1, rows >= 1, 4]; got {tables.shape}")
-    bad = np.argwhere(~np.isfinite(tables))
-    if bad.size:
-        t, r, c = (int(x) for x in bad[0])
-        raise ValueError(f"a wind table holds a non-finite entry: table {t}, row {r}, column {c} ({WIND_NAMES[c]})")
-    bad = np.argwhere(tables[:, :, DRAG] < 0)
-    if bad.size:
-        t, r = (int(x) for x in bad[0])
-        raise ValueError(f"a wind table holds a negative drag: table {t}, row {r}, column {DRAG} ({WIND_NAMES[DRAG]})")
-    if tables.shape[0] * tables.shape[1] >= 1 << 28:
-        raise ValueError("a wind bank holds fewer than 2^28 rows in all")
-    return np.ascontiguousarray(tables)
+    from . import schedules
+    return schedules.check_tables(schedules.WIND, tables)
 
 
 def check_wind_ids(ids, n_tables, n_envs):
     """One table id per env, each in [0, n_tables) -> contiguous uint32; ValueError otherwise."""
-    a = np.asarray(ids)
-    if a.ndim != 1 or a.size != int(n_envs):
-        raise ValueError(f"wind ids must hold one id per env: {a.size if a.ndim == 1 else a.shape} ids for {int(n_envs)} envs")
-    if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
-        raise ValueError("wind ids must be integers")
-    a = a.astype(np.int64)
-    bad = np.flatnonzero((a < 0) | (a >= int(n_tables)))
-    if bad.size:
-        raise ValueError(f"wind id out of range: env {int(bad[0])} names table {int(a[bad[0]])} of a bank of {int(n_tables)}")
-    return np.ascontiguousarray(a.astype(np.uint32))
+    from . import schedules
+    return schedules.check_ids(schedules.WIND, ids, n_tables, n_envs)
 
 
 def compose(base6, mass, velocity3, row4):

@@ -1,4 +1,4 @@
-// fake_hip_memory.hpp - TESTS ONLY: what tests/host_memory_driver.cpp and tests/call_memory_driver.cpp read of the stand-in in
+// fake_hip_memory.hpp - TESTS ONLY: what tests/host_memory_driver.cpp, tests/call_memory_driver.cpp and tests/env_schedule_driver.cpp read of the stand-in in
 // fake_hip_memory.cpp.
 #pragma once
 #include <cstddef>

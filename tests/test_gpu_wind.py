@@ -14,17 +14,13 @@ from raptor_amd._lib import RaptorQuadError
 from gpu_common import World
 from rollout_common import (NOISE, OFFSET, Batch, assert_same, assert_same_recording, bank_weights, bits, ids_of, random_table,
                             roll, snapshot, world_snapshot)
+from schedule_common import LAUNCHES, N, Flights, mixed_ids as _mixed_ids, teachers as _teachers
 from test_wind_cpu import check_closed_form, oracle_trace
 
 pytestmark = pytest.mark.gpu
 
 P_MASS, P_ROTOR_XY = 0, slice(4, 6)         # RQ_P_MASS, RQ_P_ROTOR_POS + 0 / + 1
 S_VEL, S_WRENCH = slice(7, 10), slice(21, 27)          # RQ_S_LINEAR_VELOCITY; RQ_S_FORCE, RQ_S_TORQUE
-
-
-def _mixed_ids(n, m, shift=0):
-    """every wave holds all m ids and neighbouring lanes differ"""
-    return ((np.arange(n) * 7 + 1 + shift) % m).astype(np.uint32)
 
 
 def _fed(S, mass, row):
@@ -122,15 +118,14 @@ def test_the_closed_form_on_the_device(device, oracle):
 
 
 # ------------------------------------------------------------------ the rollouts' shared shape -----
-N, LIMIT, LAUNCHES = 200, 16, (20, 20)       # four blocks, the last ragged; 40 steps as two launches cross episode ends
+LIMIT = 16
 T = sum(LAUNCHES)
 M = 4
 # a velocity threshold that the envs in table 1's storm cross within a few steps (90 m/s^2 from row 3 on: 0.9 m/s per step, far more
 # than the rotors can hold against) and the envs in the mild winds do not
 KW = dict(seed=5, domain_randomization=1, episode_step_limit=LIMIT, termination_linear_velocity=2.5, disturbance_force_std=0.05,
           disturbance_torque_std=0.02, **NOISE)
-BLOCK_IDS = [2, 0, 2, 1]                     # the policy bank's blocks: non-monotone, policy 2 twice
-RATES = [1, 4, 2]                            # ... and its native intervals
+RATES = [1, 4, 2]                            # the policy bank's native intervals
 
 
 def _suite(limit):
@@ -160,45 +155,8 @@ def setpoints(device):
     return t, l2f.Reference(device, np.array(t[1])), l2f.ReferenceBank(device, t)
 
 
-def _reference_kw(setpoints, kind, n=N):
-    _, single, many = setpoints
-    return {"none": {}, "single": dict(reference=single), "bank": dict(reference=many, reference_ids=_mixed_ids(n, 3, 2))}[kind]
-
-
-def _fly_policy(device, oracle, schedule, mode, autoreset, record, ref_kw, interval=1, n=N, launches=LAUNCHES, kw=KW):
-    """a fresh world flown by its own policy -> world, snapshot, recording; schedule: (bank, ids) or None"""
-    w = World(device, oracle, n, **kw)
-    w.policy.native_interval = interval
-    base = w.state.numpy()[:, S_WRENCH]
-    assert (base != 0).all() and not (bits(base) == 0x80000000).any()          # a nonzero base force, and no -0
-    if schedule is not None:
-        w.env.set_wind_schedule(*schedule)
-    tr = w.vector.Trajectory(w.env, sum(launches)) if record else None
-    for c in launches:
-        roll(w, c, mode, autoreset, trajectory=tr, **ref_kw)
-    return w, world_snapshot(w), tr.numpy() if record else None
-
-
-def _fly_policy_bank(device, oracle, weights, schedule, mode, autoreset, record, ref_kw, launches=LAUNCHES):
-    from raptor_amd.policy_bank import PolicyBank
-    w = World(device, oracle, N, **KW)
-    pb = PolicyBank(device, bank_weights(weights, 3), native_interval=RATES)
-    pids = ids_of(BLOCK_IDS, N)
-    if schedule is not None:
-        w.env.set_wind_schedule(*schedule)
-    tr = w.vector.Trajectory(w.env, sum(launches)) if record else None
-    for c in launches:
-        pb.fly(w.vector, device, w.env, w.params, w.state, w.rng, c, pids, mode, autoreset, trajectory=tr, **ref_kw)
-    return w, snapshot(w, pb.hidden(N)), tr.numpy() if record else None
-
-
-def _fly(device, oracle, weights, setpoints, call, schedule, mode, autoreset, launches=LAUNCHES):
-    if call.startswith("policy_bank"):
-        ref_kw = _reference_kw(setpoints, "bank") if call.endswith("refs") else {}
-        return _fly_policy_bank(device, oracle, weights, schedule, mode, autoreset, True, ref_kw, launches)
-    ref_kw = _reference_kw(setpoints, "bank") if call == "track_refs" else {}
-    return _fly_policy(device, oracle, schedule, mode, autoreset, True, ref_kw, launches=launches)
-
+_flights = Flights("wind", KW, RATES, nonzero_base_force=True)
+_fly_policy, _fly_policy_bank, _fly = _flights.fly_policy, _flights.fly_policy_bank, _flights.fly
 
 CALLS = ["rollout", "track_refs", "policy_bank", "policy_bank_refs"]
 
@@ -447,20 +405,6 @@ def test_all_three_schedules_chained_equal_the_loop_that_composes_them(device, o
 
 
 # ------------------------------------------------------------------ 8. refusals -----
-def _teachers(device, K=5):
-    from raptor_amd.teachers import TeacherBank, layers_parameter_count
-    g = np.random.default_rng(2)
-    widths = [32, 16]
-    W = np.empty((K, layers_parameter_count(22, widths)), np.float32)
-    for k in range(K):
-        parts, prev = [], 22
-        for h in widths + [4]:
-            parts += [g.standard_normal(h * prev) * 0.2 / np.sqrt(prev), g.standard_normal(h) * 0.1]
-            prev = h
-        W[k] = np.concatenate(parts).astype(np.float32)
-    return TeacherBank.from_layers(device, W, 22, widths, "tanh", "identity", "fp32")
-
-
 def test_refusals_leave_everything_untouched(device, oracle, weights, suite):
     from raptor_amd.policy_bank import PolicyBank
     tables, bank = suite

@@ -14,6 +14,7 @@ from raptor_amd._lib import RaptorQuadError
 from gpu_common import World
 from rollout_common import (NOISE, OFFSET, Batch, assert_same, assert_same_recording, bank_weights, bits, ids_of, join, random_table,
                             roll, snapshot, world_snapshot)
+from schedule_common import LAUNCHES, N, Flights, mixed_ids as _mixed_ids, reference_kw as _reference_kw
 
 pytestmark = pytest.mark.gpu
 
@@ -21,12 +22,6 @@ P_MASS, P_ROTOR_XY = 0, slice(4, 6)         # RQ_P_MASS, RQ_P_ROTOR_POS + 0 / + 
 S_WRENCH = slice(21, 27)                    # RQ_S_FORCE, RQ_S_TORQUE
 
 
-def _mixed_ids(n, m, shift=0):
-    """every wave holds all m ids and neighbouring lanes differ"""
-    return ((np.arange(n) * 7 + 1 + shift) % m).astype(np.uint32)
-
-
-# ------------------------------------------------------------------ 1. the anchor -----
 def _anchor_tables(units):
     """calm; a force gust on steps 3..6; a torque kick at step 5 plus a payload - in the bank's units"""
     rows = 12
@@ -125,12 +120,11 @@ def test_a_constant_force_gives_the_closed_form(device):
 
 
 # ------------------------------------------------------------------ the rollouts' shared shape -----
-N, LIMIT, LAUNCHES = 200, 16, (20, 20)       # four blocks, the last ragged; 40 steps as two launches cross episode ends
+LIMIT = 16
 T = sum(LAUNCHES)
 M = 3
 # gusts strong enough, and a velocity threshold tight enough, that the gusted envs terminate mid-episode (table 0 is calm)
 KW = dict(seed=5, domain_randomization=1, episode_step_limit=LIMIT, termination_linear_velocity=2.5, **NOISE)
-BLOCK_IDS = [2, 0, 2, 1]                     # the policy bank's blocks: non-monotone, policy 2 twice
 
 
 @pytest.fixture(scope="module")
@@ -153,34 +147,8 @@ def setpoints(device):
     return t, l2f.Reference(device, np.array(t[1])), l2f.ReferenceBank(device, t)
 
 
-def _reference_kw(setpoints, kind, n=N):
-    _, single, many = setpoints
-    return {"none": {}, "single": dict(reference=single), "bank": dict(reference=many, reference_ids=_mixed_ids(n, M, 2))}[kind]
-
-
-def _fly_policy(device, oracle, schedule, mode, autoreset, record, ref_kw, interval=1, n=N, launches=LAUNCHES, kw=KW):
-    """a fresh world flown by its own policy -> world, snapshot, recording; schedule: (bank, ids) or None"""
-    w = World(device, oracle, n, **kw)
-    w.policy.native_interval = interval
-    if schedule is not None:
-        w.env.set_wrench_schedule(*schedule)
-    tr = w.vector.Trajectory(w.env, sum(launches)) if record else None
-    for c in launches:
-        roll(w, c, mode, autoreset, trajectory=tr, **ref_kw)
-    return w, world_snapshot(w), tr.numpy() if record else None
-
-
-def _fly_policy_bank(device, oracle, weights, schedule, mode, autoreset, record, ref_kw):
-    from raptor_amd.policy_bank import PolicyBank
-    w = World(device, oracle, N, **KW)
-    pb = PolicyBank(device, bank_weights(weights, 3))
-    pids = ids_of(BLOCK_IDS, N)
-    if schedule is not None:
-        w.env.set_wrench_schedule(*schedule)
-    tr = w.vector.Trajectory(w.env, T) if record else None
-    for c in LAUNCHES:
-        pb.fly(w.vector, device, w.env, w.params, w.state, w.rng, c, pids, mode, autoreset, trajectory=tr, **ref_kw)
-    return w, snapshot(w, pb.hidden(N)), tr.numpy() if record else None
+_flights = Flights("wrench", KW)
+_fly_policy, _fly_policy_bank = _flights.fly_policy, _flights.fly_policy_bank
 
 
 # ------------------------------------------------------------------ 3. a zero table is no schedule -----

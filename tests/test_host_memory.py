@@ -1,7 +1,8 @@
 """rq::DeviceBuffer / rq::PinnedBuffer (raptor_amd/csrc/rq_memory.hpp), the one owner of device and pinned memory in the C layer, on
 the CPU: the header is compiled with a short driver (tests/host_memory_driver.cpp) against a stand-in for the five HIP entry
 points it calls (tests/fake_hip_memory.cpp) that counts calls, logs their order and fails an allocation on request.  rq::CallMemory
-(raptor_amd/csrc/rq_call_memory.hpp) the same way, with the four entry points more that it calls."""
+(raptor_amd/csrc/rq_call_memory.hpp) the same way, with the four entry points more that it calls, and rq::EnvSchedule
+(raptor_amd/csrc/rq_env_schedule.hpp), an env's slot per kind of schedule, with entry points both of them call."""
 import os
 import subprocess
 
@@ -23,6 +24,16 @@ def test_call_memory_against_a_counting_hip_stand_in(tmp_path):
     host memory, for another ordinal and for a failing query, whose sticky error is taken - and asks nothing in a host-memory call.
     A copy that fails in finish() is returned with no copy and no synchronise after it.  valid: 0, 1, 2, not -1 or 3."""
     _run_driver(tmp_path, "call_memory_driver.cpp")
+
+
+def test_env_schedule_slot_against_a_counting_hip_stand_in(tmp_path):
+    """rq::EnvSchedule (raptor_amd/csrc/rq_env_schedule.hpp), the slot an env keeps per kind of schedule, with
+    tests/env_schedule_driver.cpp.  A first attach makes exactly one device allocation, one upload and one synchronise, a later one
+    no allocation; the uploaded first rows are id * rows below n and 0 up to ld, all 0 with null ids; the banks' `attached` counts
+    follow attach, re-attach and detach, and detach leaves generation 0 and no ids; two attachments carry different non-zero
+    generations; a failing allocation or copy is returned and leaves bank, ids, generation and both counts as they were; an env
+    object that goes with three attached slots lets all three banks go; every block is freed exactly once."""
+    _run_driver(tmp_path, "env_schedule_driver.cpp")
 
 
 def _run_driver(tmp_path, driver):
