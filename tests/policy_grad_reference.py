@@ -34,6 +34,15 @@ value rounded|, which is at most u * K * A where
 
     bound = 2 u K A + 2^-120 (an absolute floor: subnormal products)
 
+Where it holds.  The Lipschitz remark bounds a factor's error by the error of its argument, an ABSOLUTE quantity of order u times
+the gate chain's operands, while A charges the factor RELATIVE to its own size: 2 u K |dh| (1 - z) shrinks with 1 - z, and the
+kernel's 1 - z~, formed from a rounded gate (rq_grad_backward.inc:197-204), is off by u-sized amounts however small it is.  The
+bound therefore holds where the derivative factors are of order one and the observations of order one - the shipped checkpoint, its
+perturbations, the recordings it flies - and not on saturated or signed gates or observations x 2^10, where a plain float32
+evaluation of these very formulas leaves it by up to five orders of magnitude.  There ``policy_grad_window.window_bound`` is the
+bound to use: it carries an absolute error beside every value (short windows, T <= 3); tests/test_gpu_policy_grad_float64.py holds
+the kernels to it on every weight and input family of tests/actor_reference.py.
+
 What the bound is good for: A propagates |J| - the Jacobians with every sign dropped - so it grows along an episode by about the
 spectral radius of |J| per step (~1.7 for the shipped policy: A / max |g| is ~0.4 after 9 recurrent steps, ~1e3 after 24, ~1e20
 after 100), while the signed products the gradient itself is made of stay bounded.  It is therefore a useful check over the short
