@@ -92,7 +92,8 @@ extern "C" {
                               (still 5: rq_rollout_teachers_track and rq_rollout_teachers_track_refs added, no struct changed)
                               (still 5: rq_wrench_bank_{create,destroy} and rq_env_{set,get}_wrench_schedule added, no struct changed)
                               (still 5: rq_vehicle_bank_{create,destroy} and rq_env_{set,get}_vehicle_schedule added, no struct changed)
-                              (still 5: rq_wind_bank_{create,destroy} and rq_env_{set,get}_wind_schedule added, no struct changed) */
+                              (still 5: rq_wind_bank_{create,destroy} and rq_env_{set,get}_wind_schedule added, no struct changed)
+                              (still 5: rq_delay_bank_{create,destroy} and rq_env_{set,clear,get}_delay_schedule added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -614,6 +615,48 @@ RQ_API int rq_env_set_wind_schedule(rq_env* env, rq_wind_bank* bank /* NULL deta
                                     const uint32_t* wind_id /* host [n_envs] or NULL = table 0 */);
 RQ_API int rq_env_get_wind_schedule(const rq_env* env, rq_wind_bank** bank /* NULL when none */,
                                     uint32_t* wind_id_out /* host [n_envs] or NULL */);
+
+/* ---- Delay schedule: control latency.  Estimator, radio and ESC put one to several control periods between the actor's output and
+ * the rotors' setpoint; the three schedules above change the force, the plant or nothing of the loop itself.  A DELAY BANK is
+ * n_tables tables of one length, host_rows [n_tables][rows] uint8 row-major: the delay in steps, 0 <= d <= RQ_DELAY_MAX_STEPS (160 ms
+ * at dt = 10 ms).  A schedule is attached to an ENV: a bank plus one table id per env.  While it is attached EVERY transition of env
+ * i, in every call that steps (rq_step, the rollouts of a policy, a policy bank and a teacher bank, chained; fused as said below),
+ * is computed as
+ *     k    = the env's episode step count before the step, clamped to rows - 1   (the count the other schedules index with)
+ *     d    = table[delay_id[i]][k]
+ *     a_k  = the action given to the step: the policy's output, the teacher's, the caller's array in rq_step
+ *     u_k  = a_{k-d} if d <= k, four +0.0f otherwise     (a command older than the episode is the zero sample_initial_state leaves
+ *                                                          in the action history; d = 0: a_k itself)
+ *     next state, reward, termination = those of the step computed from u_k, except
+ *     RQ_S_LAST_ACTION of the next state = clamp(a_k, -1, 1), or a_k under action_history_raw
+ * A controller sees what it sent, not what arrived: the observation's action history, a recording's actions (a_k), relabelling and
+ * distillation all see the actor's own output (raptor_amd.delays.applied is the NumPy restatement of the rule; applied_actions
+ * rebuilds u from a recording).  A table of zeros gives the bits of no schedule.
+ * The env owns the COMMAND HISTORY: a ring on the device, allocated at the first attachment and kept, in which a step that commits
+ * (not frozen) writes a_k at the slot of its episode step count.  It persists across calls: a step early in one call reads what the
+ * call before wrote, whichever mode either flew in.  Attaching zeroes it - commands from before an attachment read as zero - and
+ * an episode end or rq_env_reset_statistics needs no clearing, a command older than the episode being zero by the rule.
+ * rq_delay_bank_create refuses a null argument, n_tables == 0, rows == 0, an entry above RQ_DELAY_MAX_STEPS (the message names table
+ * and row) and n_tables * rows >= 2^28, all before the device is looked at.  rq_env_set_delay_schedule (bank NULL: detach, as
+ * rq_env_clear_delay_schedule does; delay_id NULL: table 0 for every env) refuses a bank of another rq_device
+ * (RQ_ERR_SHAPE_MISMATCH) and an id >= n_tables (the message names the env).  rq_delay_bank_destroy is refused while the bank is
+ * attached to a live env; rq_env_destroy detaches.  Unlike the other schedules' banks, one with rows < episode_step_limit is flown:
+ * the steps past the table hold its last row (constant latency is a table of one row).  In fused mode a schedule is flown by the
+ * fp32 policy and policy-bank kernels (k_rollout_fused_delay); a bf16 /
+ * f16x2 policy, a SampleAndSquash stage, rq_rollout_teachers* and an env that carries another schedule too are refused in fused mode
+ * while a delay schedule is attached (nothing runs chained in their place, state, statistics, hidden state and history untouched) -
+ * all of them run chained.  The small-batch loop steps such an env with plain launches (no resident executor, no speculative policy
+ * step).  Not modelled: observation (sensor) latency, delays in fractions of a step, delays above RQ_DELAY_MAX_STEPS. */
+#define RQ_DELAY_MAX_STEPS 16
+typedef struct rq_delay_bank rq_delay_bank;
+RQ_API int rq_delay_bank_create(rq_device* dev, const uint8_t* host_rows /* [n_tables][rows] */, uint32_t n_tables, uint32_t rows,
+                                rq_delay_bank** out);
+RQ_API int rq_delay_bank_destroy(rq_delay_bank* bank);
+RQ_API int rq_env_set_delay_schedule(rq_env* env, rq_delay_bank* bank /* NULL detaches */,
+                                     const uint32_t* delay_id /* host [n_envs] or NULL = table 0 */);
+RQ_API int rq_env_clear_delay_schedule(rq_env* env);
+RQ_API int rq_env_get_delay_schedule(const rq_env* env, rq_delay_bank** bank /* NULL when none */,
+                                     uint32_t* delay_id_out /* host [n_envs] or NULL */);
 
 /* ---- Learner: the student's gradient over a recorded trajectory (README.md:208-216, the distillation step's regression) ----
  * Forward: the policy on the recorded observations obs [T][22][ld] under rq_trajectory_relabel's episode rules (GRU state back to

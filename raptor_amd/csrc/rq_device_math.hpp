@@ -497,6 +497,36 @@ __device__ __forceinline__ void wind_compose(float (&f)[6], float mass, float vx
     f[2] = __fadd_rn(f[2], __fmul_rn(md, __fsub_rn(r[2], vz)));
 }
 
+// ------------------------------------------------------------------ delay schedule -----
+// A delay schedule (rq_env_set_delay_schedule) puts d control periods between the actor's command and the rotors' setpoint: d = row k
+// of the env's own table of bytes, k = the env's episode step count before the step (the count the other schedules index with),
+// clamped to the table.  With a_k the command the actor gives at step k, the transition is computed from
+//     u_k = a_{k-d}  if d <= k,   four +0.0f otherwise        (a command older than the episode is the zero sample_state leaves)
+// and d = 0 takes a_k as it stands in registers.  The commands live in the env's ring (DelayPtrs): slot k mod kDelaySlots, four
+// field rows of ld.  A step reads slot k - d and, where it commits, writes a_k to slot k; the two never coincide (kDelaySlots is
+// twice the longest delay).  Plain loads and stores: one lane's store and its later load of one address stay in program order, so
+// d = 1 reads at step k + 1 what the same lane wrote at step k, in one launch or across two.  The next state's last-action columns
+// keep the actor's own command (delay_history: the clamp step_inplace applies, or a_k raw), not what arrived.  The functions below
+// are the only place any path does this.
+__device__ __forceinline__ uint32_t delay_row(const uint8_t* __restrict__ tab, uint32_t rows, uint32_t row0, uint32_t k) {
+    return tab[(size_t)row0 + (k < rows ? k : rows - 1u)];
+}
+// u <- the command given d steps ago, 1 <= d <= k; four zeros for d > k; left alone for d = 0 (the caller has a_k)
+__device__ __forceinline__ void delay_read(const float* ring, size_t ld, uint32_t i, uint32_t k, uint32_t d, float (&u)[4]) {
+    const bool reaches = d != 0 && d <= k;
+    const float* slot = ring + (size_t)((k - d) & (kDelaySlots - 1u)) * 4u * ld + i;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) u[j] = reaches ? slot[(size_t)j * ld] : 0.0f;
+}
+// the command of step k into its slot (the caller knows that the step commits)
+__device__ __forceinline__ void delay_write(float* ring, size_t ld, uint32_t i, uint32_t k, const float (&a)[4]) {
+    float* slot = ring + (size_t)(k & (kDelaySlots - 1u)) * 4u * ld + i;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) slot[(size_t)j * ld] = a[j];
+}
+// what the last-action columns keep of the actor's command: step_inplace's clamp (the raw command is the caller's to keep)
+__device__ __forceinline__ f32x2 delay_history(float a0, float a1) { return f32x2{clampf(a0, -1.0f, 1.0f), clampf(a1, -1.0f, 1.0f)}; }
+
 // ------------------------------------------------------------------ parameter sampling -
 
 __device__ __forceinline__ void sample_params(const SampleCfg& c, uint64_t seed, uint32_t epoch, uint64_t genv,

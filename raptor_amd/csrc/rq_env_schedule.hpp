@@ -14,9 +14,9 @@
 
 namespace rq {
 
-// what went wrong, for the caller to word: `hip` is the failed call's error (copy, synchronize)
+// what went wrong, for the caller to word: `hip` is the failed call's error (copy, synchronize, zero)
 struct FirstRowsStatus {
-    enum What { ok, host_allocation, device_allocation, copy, synchronize } what = ok;
+    enum What { ok, host_allocation, device_allocation, copy, synchronize, zero } what = ok;
     hipError_t hip = hipSuccess;
     explicit operator bool() const { return what != ok; }      // true: failed
 };
@@ -80,6 +80,23 @@ struct EnvSchedule {
     void detach() {
         if (bank) bank->attached -= 1;
         bank = nullptr; gen = 0; ids.clear();
+    }
+};
+
+// The command history of an env's delay schedule (rq_env_set_delay_schedule): `floats` floats on the device, allocated at the first
+// attachment and kept, zeroed at every attachment - commands from before an attachment read as zero.  attach() is the slot's, with
+// the history made ready first: a failure anywhere leaves the slot and both banks as they were (a copy that fails behind the
+// zeroing leaves the history zeroed and the schedule before attached: its commands of before read as zero).
+struct DelayHistory {
+    DeviceBuffer<float> ring;
+
+    template <typename Bank>
+    FirstRowsStatus attach(hipStream_t stream, EnvSchedule<Bank>& slot, Bank* to, const uint32_t* id, uint32_t n, uint32_t ld, size_t floats) {
+        if (ring.empty() && ring.alloc(floats) != hipSuccess) return {FirstRowsStatus::device_allocation};
+        // (stream-ordered: the caller has drained the stream, and every launch that reads the ring comes after)
+        const hipError_t e = hipMemsetAsync(ring, 0, floats * sizeof(float), stream);
+        if (e != hipSuccess) return {FirstRowsStatus::zero, e};
+        return slot.attach(stream, to, id, n, ld);
     }
 };
 

@@ -391,13 +391,17 @@ struct ObsNext {
 // the linear drag against the air velocity of the row of the env's episode step count, from the velocity of the state before the
 // step and the step's (effective) mass, held across the RK4 stages (rq_device_math.hpp wind_*); the next state keeps the base.  A
 // compile-time switch like the other two.
-template <bool ROLLOUT, bool WRENCH = false, bool VEHICLE = false, bool WIND = false>
+// DELAY: the env carries a delay schedule - the transition is computed from the command the actor gave d steps ago, d the row of the
+// env's episode step count, out of the env's command history; this step's command goes into the history, and the next state's
+// last-action columns keep it (rq_device_math.hpp delay_*).  A compile-time switch like the other three.
+template <bool ROLLOUT, bool WRENCH = false, bool VEHICLE = false, bool WIND = false, bool DELAY = false>
 __device__ __forceinline__ void step_env(uint32_t i, const Batch& b, const StepCfg& c, const float* __restrict__ params,
                                          const float* state, float* __restrict__ action, float* next_state,
                                          const StatsPtrs& st, uint32_t flags, const SampleCfg& sc, uint64_t seed,
                                          float* __restrict__ hidden, const float* __restrict__ weights,
                                          const Mailbox& mb, const ObsNext& on, const WrenchPtrs& wr = WrenchPtrs{},
-                                         const VehiclePtrs& vh = VehiclePtrs{}, const WindPtrs& wd = WindPtrs{}) {
+                                         const VehiclePtrs& vh = VehiclePtrs{}, const WindPtrs& wd = WindPtrs{},
+                                         const DelayPtrs& dl = DelayPtrs{}) {
     if (ROLLOUT && st.frozen[i]) { st.last_done[i] = 4; return; }
     const size_t ld = b.ld;
     [[maybe_unused]] float vrow[4];
@@ -451,7 +455,21 @@ __device__ __forceinline__ void step_env(uint32_t i, const Batch& b, const StepC
         ds = make_disturbance(k, c.gravity, f6);
     }
     bool term;
-    const float r = step_inplace<false>(c, k, ds, y, a, AC01, AC23, term);
+    float r;
+    if constexpr (DELAY) {       // the command that acts: the one given d steps ago; this step's goes into the history (a step of
+        float u[4];              // this kernel commits) and into the last-action columns
+        const uint32_t d = delay_row(dl.rows, dl.n_rows, dl.row0[i], s.steps);
+        delay_read(dl.ring, ld, i, s.steps, d, u);
+        if (d == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) u[j] = a[j];
+        }
+        delay_write(dl.ring, ld, i, s.steps, a);
+        r = step_inplace<false>(c, k, ds, y, u, AC01, AC23, term);
+        AC01 = delay_history(a[0], a[1]); AC23 = delay_history(a[2], a[3]);
+    } else {
+        r = step_inplace<false>(c, k, ds, y, a, AC01, AC23, term);
+    }
     if (c.action_history_raw) { AC01 = f32x2{a[0], a[1]}; AC23 = f32x2{a[2], a[3]}; }   // what ActionHistory(1) keeps
     const bool ended = stats_update(c.episode_step_limit, r, term, s);
     st.last_reward[i] = r;
@@ -559,6 +577,22 @@ __global__ __launch_bounds__(kBlock) void k_step_wind(Batch b, StepCfg c, const 
     if (i < b.n)
         step_env<ROLLOUT, WRENCH, VEHICLE, true>(i, b, c, params, state, action, next_state, st, flags, sc, seed, hidden, weights, mb, on,
                                                  wr, vh, wd);
+    mailbox_signal(mb);
+}
+
+// k_step for an env that carries a delay schedule, alone or beside any of the other three (kernels of their own again: the argument
+// blocks and listings of the kernels above stay what they were)
+template <bool ROLLOUT, bool WRENCH, bool VEHICLE, bool WIND>
+__global__ __launch_bounds__(kBlock) void k_step_delay(Batch b, StepCfg c, const float* __restrict__ params,
+                                                       const float* state, float* __restrict__ action,
+                                                       float* next_state, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                       uint64_t seed, float* __restrict__ hidden,
+                                                       const float* __restrict__ weights, Mailbox mb, ObsNext on, WrenchPtrs wr,
+                                                       VehiclePtrs vh, WindPtrs wd, DelayPtrs dl) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<ROLLOUT, WRENCH, VEHICLE, WIND, true>(i, b, c, params, state, action, next_state, st, flags, sc, seed, hidden, weights,
+                                                       mb, on, wr, vh, wd, dl);
     mailbox_signal(mb);
 }
 // ------------------------------------------------------------------ resident executor ---
@@ -1117,6 +1151,27 @@ __global__ __launch_bounds__(kBlock) void k_step_bank_wind(Batch b, StepCfg c, c
                                     const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
                                     WindPtrs wd);
 
+template <bool WRENCH, bool VEHICLE, bool WIND>
+__global__ __launch_bounds__(kBlock) void k_step_bank_delay(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
+                                    StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
+                                    const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
+                                    WindPtrs wd, DelayPtrs dl);
+
+// the delay schedule's kernels: `family`, `wrench` and `wind` say what the step would be without the delay
+static void launch_step_delay(hipStream_t s, const EnvStepLaunch& e, const EnvStepRoute& r, unsigned grid, const ObsNext& on) {
+    dispatch_bools([&](auto WR, auto VH, auto WD, auto RO) {
+        if (e.block_policy != nullptr) {
+            const auto kernel = &k_step_bank_delay<WR(), VH(), WD()>;
+            RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed, e.hidden,
+                       e.weights, e.block_policy, e.wr, e.vh, e.wd, e.dl);
+        } else {
+            const auto kernel = &k_step_delay<RO(), WR(), VH(), WD()>;
+            RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
+                       e.hidden, e.weights, e.mb, on, e.wr, e.vh, e.wd, e.dl);
+        }
+    }, r.wrench, r.family == EnvStepFamily::VEHICLE || r.family == EnvStepFamily::BANK_VEHICLE, r.wind, r.rollout);
+}
+
 // the wind schedule's kernels: `family` says what the step would be without the wind (its bank-ness and whether a vehicle schedule
 // stands beside it), `wrench` whether a wrench schedule does
 static void launch_step_wind(hipStream_t s, const EnvStepLaunch& e, const EnvStepRoute& r, unsigned grid, const ObsNext& on) {
@@ -1148,7 +1203,9 @@ hipError_t launch_step(hipStream_t s, const EnvStepLaunch& e) {
     const bool wrench = route.wrench;
     const ObsNext on{e.obs_of_next, e.nc, e.noise ? 1u : 0u, e.obs_epoch, e.obs_epoch_base};
     if (route.family == EnvStepFamily::UNSUPPORTED) return hipErrorInvalidValue;
-    if (route.wind) {
+    if (route.delay) {
+        launch_step_delay(s, e, route, grid, on);
+    } else if (route.wind) {
         launch_step_wind(s, e, route, grid, on);
     } else if (route.family == EnvStepFamily::VEHICLE) {
         launch_step_vehicle(s, e, route, grid, on);
@@ -1316,6 +1373,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr VehiclePtrs vh{};
     constexpr bool WIND = false;
     constexpr WindPtrs wd{};
+    constexpr bool DELAY = false;
+    constexpr DelayPtrs dl{};
     constexpr uint32_t interval = 1;
     const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
 #include "rq_rollout_body.inc"
@@ -1345,6 +1404,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr VehiclePtrs vh{};
     constexpr bool WIND = false;
     constexpr WindPtrs wd{};
+    constexpr bool DELAY = false;
+    constexpr DelayPtrs dl{};
     const uint32_t policy = block_policy[blockIdx.x];
     const uint32_t interval = policy_interval[policy];
     const float* __restrict__ packed = images + (size_t)policy * image_floats;
@@ -1389,7 +1450,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = true, VEHICLE = false, WIND = false;
+    constexpr bool RATE = true, SAS = false, WRENCH = true, VEHICLE = false, WIND = false, DELAY = false;
+    constexpr DelayPtrs dl{};
     constexpr SasArgs sas{};
     constexpr VehiclePtrs vh{};
     constexpr WindPtrs wd{};
@@ -1433,7 +1495,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, VehiclePtrs vh,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = true, WIND = false;
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = true, WIND = false, DELAY = false;
+    constexpr DelayPtrs dl{};
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
     constexpr WindPtrs wd{};
@@ -1476,7 +1539,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WindPtrs wd,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = true;
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = true, DELAY = false;
+    constexpr DelayPtrs dl{};
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
     constexpr VehiclePtrs vh{};
@@ -1496,6 +1560,50 @@ static inline void launch_fused_wind_actor(hipStream_t s, const FusedArgs& a) {
         hipLaunchKernelGGL((k_rollout_fused_wind<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
                            a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
                            a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.wd, a.span);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
+}
+
+// ---- the fused kernel of an env that carries a delay schedule
+// Built as k_rollout_fused_wind is - the RATE loop with optional block tables, one entry point for rq_rollout, rq_rollout_record,
+// rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every native interval - with DELAY on: the env's first row is
+// loaded once per launch, every step asks for its byte of delay and, from the env's command history, for the four floats of the
+// command given that many steps ago, ahead of the actor; after the actor the step's own command goes into the history where the
+// step commits, and the env step is computed from the old one (rq_rollout_body.inc).  fp32 actors only: the host refuses the 16-bit
+// policies, the SampleAndSquash stage and another schedule beside a delay schedule in fused mode.
+template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_delay(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ images,
+                                                               const uint32_t* __restrict__ block_policy,
+                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
+                                                               uint32_t single_interval,
+                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, DelayPtrs dl,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = false, DELAY = true;
+    constexpr SasArgs sas{};
+    constexpr WrenchPtrs wr{};
+    constexpr VehiclePtrs vh{};
+    constexpr WindPtrs wd{};
+    uint32_t policy = 0, interval = single_interval;
+    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
+        policy = block_policy[blockIdx.x];
+        interval = policy_interval[policy];
+    }
+    const float* __restrict__ packed = images + (size_t)policy * image_floats;
+#include "rq_rollout_body.inc"
+}
+
+// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
+template <typename ACTOR>
+static inline void launch_fused_delay_actor(hipStream_t s, const FusedArgs& a) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
+        hipLaunchKernelGGL((k_rollout_fused_delay<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
+                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.dl, a.span);
     }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
@@ -1523,13 +1631,15 @@ hipError_t launch_rollout_fused(hipStream_t s, const FusedArgs& a) {
     case FusedBuild::F16X2:      // the 16-bit actors live in their own translation unit (rq_kernels_16bit.hip: a place for per-build flags)
         return launch_rollout_fused_16bit(s, a, r.family);
     case FusedBuild::F32_LEAN:
-        if (r.wind)                        launch_fused_wind_actor<ActorF32Lean>(s, a);       // (a wind schedule: its own entry point)
+        if (r.delay)                       launch_fused_delay_actor<ActorF32Lean>(s, a);      // (a delay schedule: its own entry point)
+        else if (r.wind)                   launch_fused_wind_actor<ActorF32Lean>(s, a);       // (a wind schedule: likewise)
         else if (r.vehicle)                launch_fused_vehicle_actor<ActorF32Lean>(s, a);    // (a vehicle schedule: likewise)
         else if (a.sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a);      // (PLAIN: route_fused allows the stage nowhere else)
         else                               launch_fused_f32_actor<ActorF32Lean>(s, a, r.family);
         break;
     case FusedBuild::F32:
-        if (r.wind)         launch_fused_wind_actor<ActorF32>(s, a);
+        if (r.delay)        launch_fused_delay_actor<ActorF32>(s, a);
+        else if (r.wind)    launch_fused_wind_actor<ActorF32>(s, a);
         else if (r.vehicle) launch_fused_vehicle_actor<ActorF32>(s, a);
         else                launch_fused_f32_actor<ActorF32>(s, a, r.family);
         break;
@@ -1608,6 +1718,33 @@ RQ_STEP_BANK_WIND(true, false)
 RQ_STEP_BANK_WIND(false, true)
 RQ_STEP_BANK_WIND(true, true)
 #undef RQ_STEP_BANK_WIND
+
+// ... and for one that carries a delay schedule, alone or beside the other three
+template <bool WRENCH, bool VEHICLE, bool WIND>
+__global__ __launch_bounds__(kBlock) void k_step_bank_delay(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                            float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                            uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                            const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
+                                                            WindPtrs wd, DelayPtrs dl) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true, WRENCH, VEHICLE, WIND, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                                                    weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr,
+                                                    vh, wd, dl);
+}
+#define RQ_STEP_BANK_DELAY(WR, VH, WD)                                                                                               \
+    template __global__ void k_step_bank_delay<WR, VH, WD>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t,        \
+                                                           SampleCfg, uint64_t, float*, const float*, const uint32_t*, WrenchPtrs,   \
+                                                           VehiclePtrs, WindPtrs, DelayPtrs);
+RQ_STEP_BANK_DELAY(false, false, false)
+RQ_STEP_BANK_DELAY(true, false, false)
+RQ_STEP_BANK_DELAY(false, true, false)
+RQ_STEP_BANK_DELAY(true, true, false)
+RQ_STEP_BANK_DELAY(false, false, true)
+RQ_STEP_BANK_DELAY(true, false, true)
+RQ_STEP_BANK_DELAY(false, true, true)
+RQ_STEP_BANK_DELAY(true, true, true)
+#undef RQ_STEP_BANK_DELAY
 
 // k_thaw_frozen likewise: an env left frozen starts its next episode with ITS policy's initial state
 #define RQ_THAW_KERNEL k_thaw_frozen_bank

@@ -332,6 +332,7 @@ struct FusedArgs {
     WrenchPtrs wr{};                               // rows != nullptr: the env's wrench schedule (fp32, no SampleAndSquash stage)
     VehiclePtrs vh{};                              // rows != nullptr: the env's vehicle schedule (fp32, no stage, no wrench schedule)
     WindPtrs wd{};                                 // rows != nullptr: the env's wind schedule (fp32, no stage, no other schedule)
+    DelayPtrs dl{};                                // rows != nullptr: the env's delay schedule (fp32, no stage, no other schedule)
     // The actor.  One policy (block_policy == nullptr): `images` is its operand image in `precision`, with its output stage and its
     // native interval.  A policy bank (fp32, no output stage): the tables described above - `interval` is not read - and whether an
     // entry of policy_interval is above 1 (the host's knowledge: the table is on the device).
@@ -348,7 +349,7 @@ struct FusedArgs {
 };
 inline FusedTraits fused_traits(const FusedArgs& a) {
     return {a.b.n, a.precision, a.sas.mode != RQ_SAS_OFF, a.trk.ref != nullptr, a.wr.rows != nullptr, a.interval,
-            a.block_policy != nullptr, a.bank_rated, a.vh.rows != nullptr, a.wd.rows != nullptr};
+            a.block_policy != nullptr, a.bank_rated, a.vh.rows != nullptr, a.wd.rows != nullptr, a.dl.rows != nullptr};
 }
 // The kernel route_fused(fused_traits(a)) names, enqueued on s; hipErrorInvalidValue, and nothing launched, for a description no
 // kernel is built for.  n == 0 or n_steps == 0: nothing to do.

@@ -212,16 +212,18 @@ struct TableKind {
     const char* tables;                 // what a message calls the tables: "reference", "wrench bank"
     const char* noun;                   // a schedule's kind, as in "wrench schedule", "wrench id" (a reference: none)
     uint32_t cols;
-    enum Rule { kFinite, kPositive, kNonNegativeColumn } rule;      // every entry finite; and > 0; and those of `rule_col` >= 0
+    enum Rule { kFinite, kPositive, kNonNegativeColumn, kSteps } rule;      // every entry finite; and > 0; and those of `rule_col` >= 0;
+                                        // kSteps: bytes, not floats, each at most RQ_DELAY_MAX_STEPS (rq_delay_bank_create's own check)
     int rule_col;                       // (a rule about columns names the column in every message)
     const char* detach;                 // the entry point that detaches: what a refused destruction names
 };
 // the schedules first, in the order every walk over them takes: it is the order in which refusals are heard
-enum TableKindId { kWrench, kVehicle, kWind, kScheduleKinds, kReference = kScheduleKinds, kReferenceBank, kTableKindCount };
+enum TableKindId { kWrench, kVehicle, kWind, kDelay, kScheduleKinds, kReference = kScheduleKinds, kReferenceBank, kTableKindCount };
 inline constexpr TableKind kTableKinds[kTableKindCount] = {
     {"wrench bank", "wrench", 6, TableKind::kFinite, -1, "rq_env_set_wrench_schedule"},
     {"vehicle bank", "vehicle", 4, TableKind::kPositive, -1, "rq_env_set_vehicle_schedule"},      // factors on mass, inertia, thrust, motor lag
     {"wind bank", "wind", 4, TableKind::kNonNegativeColumn, 3, "rq_env_set_wind_schedule"},       // air velocity, specific drag
+    {"delay bank", "delay", 1, TableKind::kSteps, -1, "rq_env_set_delay_schedule"},               // control latency in steps
     {"reference", nullptr, 6, TableKind::kFinite, -1, nullptr},
     {"reference bank", nullptr, 6, TableKind::kFinite, -1, nullptr},
 };
@@ -231,6 +233,7 @@ struct rq_reference_bank : rqh::RowTables {};
 struct rq_wrench_bank : rqh::ScheduleBank { int units = RQ_WRENCH_RELATIVE; };
 struct rq_vehicle_bank : rqh::ScheduleBank {};
 struct rq_wind_bank : rqh::ScheduleBank {};
+struct rq_delay_bank : rqh::ScheduleBank { rq::DeviceBuffer<uint8_t> steps; };      // [n_tables * rows] bytes; `d` stays empty
 
 struct rq_env {
     rq_device* dev = nullptr;
@@ -256,6 +259,7 @@ struct rq_env {
     // The schedules (rq_env_set_wrench_schedule and its kin), one slot per kind, indexed by rqh::TableKindId: the bank, the ids it was
     // attached with, the [ld] first rows every stepping kernel reads and the number that names the attachment.
     rq::EnvSchedule<rqh::ScheduleBank> schedule[rqh::kScheduleKinds];
+    rq::DelayHistory delay_history;     // the delay schedule's command history: [rq::kDelaySlots][RQ_ACTION_DIM][ld]
     bool has_schedule() const { for (const auto& s : schedule) if (s.bank) return true; return false; }
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
     // epoch-counter bump); one executable graph per distinct argument set: what the nodes carry by value, named once
@@ -472,28 +476,32 @@ inline rq::Batch batch_of(const rq_env* env) { return {env->n, env->ld, env->off
 int env_track_stats(rq_env* env, float** sum_sq, uint32_t** steps);
 // ---- rq_capi_rollout.cpp: the env's schedules ----
 // One schedule as the kernels take it, before it is typed (all-null: none attached).  `flag`: the wrench bank's units, 1 = relative.
-struct SchedulePtrs { const float* rows = nullptr; const uint32_t* row0 = nullptr; uint32_t n_rows = 0, flag = 0; };
+// `ring`: the delay schedule's command history.
+struct SchedulePtrs { const void* rows = nullptr; const uint32_t* row0 = nullptr; uint32_t n_rows = 0, flag = 0; float* ring = nullptr; };
 int schedule_too_short(const char* who, const rq_env* env, int kind);      // the refusal below, worded
 // The env's schedules, p[kScheduleKinds] in kind order.  Every call that steps asks here before anything is enqueued: a bank with
-// fewer rows than episode_step_limit is refused (`who`: the caller's name; the config may have changed since the schedule was
+// fewer rows than episode_step_limit is refused, but a delay bank (`who`: the caller's name; the config may have changed since the schedule was
 // attached).  Nothing is allocated and no string made unless it refuses: rq_step asks on every call.
 inline int env_schedules(const char* who, const rq_env* env, SchedulePtrs* p) {
     for (int k = 0; k < kScheduleKinds; ++k) {
         p[k] = SchedulePtrs{};
         const auto& s = env->schedule[k];
         if (!s.bank) continue;
-        if (s.bank->rows < env->cfg.episode_step_limit) return schedule_too_short(who, env, k);
-        p[k] = {s.bank->d, s.row0, s.bank->rows,
-                k == kWrench && static_cast<const rq_wrench_bank*>(s.bank)->units == RQ_WRENCH_RELATIVE ? 1u : 0u};
+        // (a delay table shorter than an episode holds its last row: a latency is a property of the link, not a course of events)
+        if (k != kDelay && s.bank->rows < env->cfg.episode_step_limit) return schedule_too_short(who, env, k);
+        p[k] = {s.bank->d.get(), s.row0, s.bank->rows,
+                k == kWrench && static_cast<const rq_wrench_bank*>(s.bank)->units == RQ_WRENCH_RELATIVE ? 1u : 0u, nullptr};
+        if (k == kDelay) { p[k].rows = static_cast<const rq_delay_bank*>(s.bank)->steps.get(); p[k].ring = env->delay_history.ring; }
     }
     return RQ_OK;
 }
 // ... typed, for the launch descriptions (rq::EnvStepLaunch, rq::FusedArgs): the kernels' argument types are one per kind
 template <typename Launch>
 void set_schedules(Launch& l, const SchedulePtrs* p) {
-    l.wr = {p[kWrench].rows, p[kWrench].row0, p[kWrench].n_rows, p[kWrench].flag};
-    l.vh = {p[kVehicle].rows, p[kVehicle].row0, p[kVehicle].n_rows, 0u};
-    l.wd = {p[kWind].rows, p[kWind].row0, p[kWind].n_rows, 0u};
+    l.wr = {static_cast<const float*>(p[kWrench].rows), p[kWrench].row0, p[kWrench].n_rows, p[kWrench].flag};
+    l.vh = {static_cast<const float*>(p[kVehicle].rows), p[kVehicle].row0, p[kVehicle].n_rows, 0u};
+    l.wd = {static_cast<const float*>(p[kWind].rows), p[kWind].row0, p[kWind].n_rows, 0u};
+    l.dl = {static_cast<const uint8_t*>(p[kDelay].rows), p[kDelay].row0, p[kDelay].ring, p[kDelay].n_rows, 0u};
 }
 // What fused mode cannot fly while a schedule of `kind` is attached, refused naming the schedule (`what`: a bf16 / f16x2 policy, a
 // SampleAndSquash stage, a teacher bank, another schedule beside it); nothing runs chained in its place.

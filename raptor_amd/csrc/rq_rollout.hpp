@@ -74,6 +74,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr VehiclePtrs vh{};
     constexpr bool WIND = false;
     constexpr WindPtrs wd{};
+    constexpr bool DELAY = false;
+    constexpr DelayPtrs dl{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -98,6 +100,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr VehiclePtrs vh{};
     constexpr bool WIND = false;
     constexpr WindPtrs wd{};
+    constexpr bool DELAY = false;
+    constexpr DelayPtrs dl{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -122,6 +126,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr VehiclePtrs vh{};
     constexpr bool WIND = false;
     constexpr WindPtrs wd{};
+    constexpr bool DELAY = false;
+    constexpr DelayPtrs dl{};
 #include "rq_rollout_body.inc"
 }
 

@@ -2,11 +2,12 @@
 // (TRACK = false), k_rollout_fused_track (TRACK = true, SAS = false) and k_rollout_fused_rate (RATE = true, SAS = false).  Text, not a function: the untracked kernel is compiled from
 // exactly what it was compiled from when the body stood between its braces - its listing does not move when the tracked variant
 // changes - and a __device__ function in between does cost that (the work-group-size folds of a kernel are made before inlining).
-// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, VEHICLE, WIND, ACTOR and
-// the names b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, vh, wd, interval, span.
+// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, VEHICLE, WIND, DELAY, ACTOR
+// and the names b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, vh, wd, dl, interval, span.
 // WRENCH (k_rollout_fused_wrench alone; every other entry point defines it false and an empty wr): the env carries a wrench schedule.
 // VEHICLE (k_rollout_fused_vehicle alone; every other entry point defines it false and an empty vh): the env carries a vehicle schedule.
 // WIND (k_rollout_fused_wind alone; every other entry point defines it false and an empty wd): the env carries a wind schedule.
+// DELAY (k_rollout_fused_delay alone; every other entry point defines it false and an empty dl): the env carries a delay schedule.
     // kernel-level timing (rq_device_set_rollout_timing): every wave leaves the wall-clock ticks (constant rate) at which it
     // came in and went out, and its XCD: the eight dies' counters are offset against one another by microseconds, one die's
     // are consistent - the host takes first-in / last-out per die
@@ -74,6 +75,9 @@
         wd_mass = field(params, RQ_P_MASS, ld)[i];
         wd_row0 = wd.row0[i];
     }
+    // DELAY: the first row of the env's own table, once per launch
+    [[maybe_unused]] uint32_t dl_row0 = 0;
+    if constexpr (DELAY) dl_row0 = dl.row0[i];
     const uint8_t last_t_raw = st.last_terminated[i];
     uint8_t last_d = AUTORESET ? (uint8_t)0 : st.last_done[i];       // auto-reset: rebuilt in the epilogue
     const uint8_t frozen_raw = st.frozen[i];
@@ -204,6 +208,14 @@
         // WIND: likewise this step's 16-byte row of air velocity and drag, one load; it is consumed just before the env step
         [[maybe_unused]] float wd_row[4];
         if constexpr (WIND) wind_row(wd.rows, wd.n_rows, wd_row0, ep_steps, wd_row);
+        // DELAY: likewise this step's byte of delay and, out of the env's command history, the command given that many steps ago
+        // (four loads behind the byte; lanes at one episode age read one slot: coalesced); consumed just before the env step
+        [[maybe_unused]] uint32_t dl_d = 0;
+        [[maybe_unused]] float dl_u[4];
+        if constexpr (DELAY) {
+            dl_d = delay_row(dl.rows, dl.n_rows, dl_row0, ep_steps);
+            delay_read(dl.ring, ld, i, ep_steps, dl_d, dl_u);
+        }
         observe_head<NOISE>(y, LA01, LA23, nc, seed, epoch0 + t, genv, o);
         if constexpr (TRACK) {
             // the setpoint of this step: the row of the env's own episode step count (lanes are at different rows: per-lane
@@ -280,11 +292,22 @@
             wind_compose(w6, wd_mass, y.V01[0], y.V01[1], y.VW[0], wd_row);
             ds = make_disturbance(k, c.gravity, w6);
         }
+        if constexpr (DELAY) {       // a (the actor's command of this step, which the recording took above) goes into the history where
+            // the step commits - not frozen, not a lane past the batch shadowing env n - 1 -; a delay of 0 acts on it as it stands
+            if (valid && (AUTORESET || !frozen)) delay_write(dl.ring, ld, i, ep_steps, a);
+            if (dl_d == 0) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dl_u[j] = a[j];
+            }
+        }
         QuadState yn = y;
         f32x2 A01, A23;
         bool term;
         float r;
-        if constexpr (VEHICLE) {     // this transition's vehicle: the scheduled members of the constants rebuilt from the base fields
+        if constexpr (DELAY) {       // the transition of the delayed command; the last-action columns keep the actor's own
+            r = step_inplace<SYM>(c, k, ds, yn, dl_u, A01, A23, term);
+            A01 = delay_history(a[0], a[1]); A23 = delay_history(a[2], a[3]);
+        } else if constexpr (VEHICLE) {     // this transition's vehicle: the scheduled members of the constants rebuilt from the base fields
             EnvConsts kv = k;
             vehicle_consts(vh_base, vh_row, kv);
             ds = make_disturbance(kv, c.gravity, f6);

@@ -65,6 +65,20 @@ struct WindPtrs {
     uint32_t pad_;
 };
 
+// A delay schedule (rq_env_set_delay_schedule): the bank's tables, the env's per-env first rows and the env's command history
+// (rq_device_math.hpp delay_*).  The history is a ring of kDelaySlots slots x 4 action fields x ld: the slot of the command given at
+// episode step k is k mod kDelaySlots.  Twice the longest delay: the slot a step reads (k - d, 1 <= d <= RQ_DELAY_MAX_STEPS) is never
+// the slot it writes (k).
+constexpr uint32_t kDelaySlots = 2u * RQ_DELAY_MAX_STEPS;
+static_assert((kDelaySlots & (kDelaySlots - 1u)) == 0, "the slot of a step is a mask of its count");
+struct DelayPtrs {
+    const uint8_t* rows;      // [n_tables * n_rows]: the delay in steps, 0 .. RQ_DELAY_MAX_STEPS; nullptr = none
+    const uint32_t* row0;     // [ld]: delay_id[i] * n_rows, the first row of env i's table
+    float* ring;              // [kDelaySlots][4][ld]: the commands the env's actor gave, by episode step
+    uint32_t n_rows;          // rows of one table
+    uint32_t pad_;
+};
+
 // SampleAndSquash output stage of the actor (rq_policy_set_sample_and_squash): mode = rq_sample_and_squash_mode
 struct SasArgs {
     uint32_t mode;                // RQ_SAS_OFF / RQ_SAS_MEAN / RQ_SAS_SAMPLE
@@ -204,6 +218,7 @@ struct EnvStepLaunch {
     WrenchPtrs wr{};                         // rows set: the env's wrench schedule
     VehiclePtrs vh{};                        // rows set: the env's vehicle schedule (not used: the kernels without it)
     WindPtrs wd{};                           // rows set: the env's wind schedule (not used: the kernels without it)
+    DelayPtrs dl{};                          // rows set: the env's delay schedule (not used: the kernels without it)
     // The thaw of a chained rollout under auto-reset reads b, sc, seed, params, st, hidden, weights and block_policy, and re-samples
     // into next_state.
 };
@@ -212,18 +227,20 @@ struct EnvStepLaunch {
 // k_step_bank_wrench - the kernels there were before a vehicle schedule existed, under their names - and, with a vehicle schedule,
 // k_step_vehicle<rollout, wrench> and k_step_bank_vehicle<wrench>.  A bank's step is a rollout's, in place, without host rows or a
 // folded observation.  With a wind schedule (`wind`): k_step_wind<rollout, wrench, vehicle> or k_step_bank_wind<wrench, vehicle>,
-// whichever of the two `family` - what the step would be without the wind - belongs to; vehicle = family is [BANK_]VEHICLE.
+// whichever of the two `family` - what the step would be without the wind - belongs to; vehicle = family is [BANK_]VEHICLE.  With a
+// delay schedule (`delay`): k_step_delay<rollout, wrench, vehicle, wind> or k_step_bank_delay<wrench, vehicle, wind>, named alike.
 enum class EnvStepFamily { UNSUPPORTED, STEP, WRENCH, VEHICLE, BANK, BANK_WRENCH, BANK_VEHICLE };
 // wrench: VEHICLE's and BANK_VEHICLE's template bool
-struct EnvStepRoute { EnvStepFamily family; bool rollout, wrench; bool wind = false; };
+struct EnvStepRoute { EnvStepFamily family; bool rollout, wrench; bool wind = false; bool delay = false; };
 inline EnvStepRoute route_env_step(const EnvStepLaunch& e) {
     const bool wrench = e.wr.rows != nullptr, vehicle = e.vh.rows != nullptr, wind = e.wd.rows != nullptr;
+    const bool delay = e.dl.rows != nullptr;
     if (e.block_policy != nullptr) {
         if (!e.rollout || e.next_state != e.state || mailbox_used(e.mb) || e.obs_of_next != nullptr)
-            return {EnvStepFamily::UNSUPPORTED, e.rollout, wrench, false};
-        return {vehicle ? EnvStepFamily::BANK_VEHICLE : wrench ? EnvStepFamily::BANK_WRENCH : EnvStepFamily::BANK, true, wrench, wind};
+            return {EnvStepFamily::UNSUPPORTED, e.rollout, wrench, false, false};
+        return {vehicle ? EnvStepFamily::BANK_VEHICLE : wrench ? EnvStepFamily::BANK_WRENCH : EnvStepFamily::BANK, true, wrench, wind, delay};
     }
-    return {vehicle ? EnvStepFamily::VEHICLE : wrench ? EnvStepFamily::WRENCH : EnvStepFamily::STEP, e.rollout, wrench, wind};
+    return {vehicle ? EnvStepFamily::VEHICLE : wrench ? EnvStepFamily::WRENCH : EnvStepFamily::STEP, e.rollout, wrench, wind, delay};
 }
 
 }  // namespace rq

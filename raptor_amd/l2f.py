@@ -37,7 +37,7 @@ from . import _lib, schedules
 from ._lib import (ACTION_DIM, OBSERVATION_DIM, PARAM_DIM, STATE_DIM, ROLLOUT_AUTORESET, ROLLOUT_CHAINED,
                    ROLLOUT_FUSED, EnvConfig, RaptorQuadError)
 
-__all__ = ["Device", "Reference", "WrenchBank", "VehicleBank", "WindBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
+__all__ = ["Device", "Reference", "WrenchBank", "VehicleBank", "WindBank", "DelayBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
 
 
 class UI:
@@ -236,7 +236,27 @@ class WindBank(_ScheduleBank):
     _kind = schedules.WIND
 
 
-_BANKS = {schedules.WRENCH: WrenchBank, schedules.VEHICLE: VehicleBank, schedules.WIND: WindBank}
+class DelayBank(_ScheduleBank):
+    """M delay tables of the same length for ``env.set_delay_schedule(bank, ids)``: ``tables`` uint8 [M, rows] (or a list of M [rows]
+    tables; ``raptor_amd.delays`` builds them), the control latency in steps, at most ``delays.MAX_STEPS``.  While the bank is
+    attached to an env, every transition of env i is computed from the command its actor gave as many steps ago as the row of its
+    own episode step count of table ``ids[i]`` says (include/raptor_quad.h "Delay schedule").  The tables are copied to ``device``
+    once, here."""
+    _kind = schedules.DELAY
+
+    def __init__(self, device, tables):
+        from . import delays
+        t = delays.check_tables(tables)                          # refused before the device is touched
+        h = C.c_void_p()
+        _lib.call("rq_delay_bank_create", device._h, t.ctypes.data, int(t.shape[0]), int(t.shape[1]), C.byref(h))
+        self._h = h
+        self._device = device
+        self.n_tables = int(t.shape[0])
+        self.rows = int(t.shape[1])
+        self._fin = weakref.finalize(self, _lib.load().rq_delay_bank_destroy, h)
+
+
+_BANKS = {schedules.WRENCH: WrenchBank, schedules.VEHICLE: VehicleBank, schedules.WIND: WindBank, schedules.DELAY: DelayBank}
 
 
 def _checked_reference(reference, reference_ids, n_envs):
@@ -281,7 +301,7 @@ def _rollout_call(entry, device, env, params, state, actor_handle, ids, rng, n_s
 
 def tracking_rmse(env, reference, ref_ids, schedule_ids, actor_ids, n_actors):
     """``tracking_rmse`` of a bank's closed-loop table, from ``env.tracking_error()`` grouped by actor (policy or teacher): [n_actors,
-    M] over the scenarios of a schedule (``schedule_ids``: what ``schedules.checked_schedule_ids`` answered - disturbances, vehicles or winds)
+    M] over the scenarios of a schedule (``schedule_ids``: what ``schedules.checked_schedule_ids`` answered - disturbances, vehicles, winds or latencies)
     or the setpoints (``ref_ids`` of a ``ReferenceBank``), [n_actors] on a single ``Reference``."""
     from .tracking import reference_tracking_table
     sum_sq, steps = env.tracking_error()
@@ -499,9 +519,9 @@ class VectorModule:
                 _lib.call("rq_env_reset_statistics", self._require("environment"))
 
             # --- the schedules: wrench (scheduled gusts, pokes, payloads: raptor_amd.disturbances), vehicle (payloads, battery sag,
-            # slow motors: raptor_amd.vehicles), wind (air that moves and drags: raptor_amd.winds).  One implementation; what is
-            # attached of a kind is kept as (bank, ids) under _<noun>. ---
-            _wrench = _vehicle = _wind = None
+            # slow motors: raptor_amd.vehicles), wind (air that moves and drags: raptor_amd.winds), delay (control latency:
+            # raptor_amd.delays).  One implementation; what is attached of a kind is kept as (bank, ids) under _<noun>. ---
+            _wrench = _vehicle = _wind = _delay = None
 
             def _set_schedule(self, kind, bank, ids):
                 if not isinstance(bank, _BANKS[kind]):
@@ -538,9 +558,18 @@ class VectorModule:
                 free per env; None: table 0 for every env).  The tables must cover ``episode_step_limit``."""
                 self._set_schedule(schedules.WIND, bank, ids)
 
+            def set_delay_schedule(self, bank, ids=None):
+                """Attach ``bank`` (an ``l2f.DelayBank``): from now on every transition of env i, in every call that steps this
+                env, is computed from the command its actor gave d steps ago, d the row of its episode step count of table
+                ``ids[i]`` ([N] integers, free per env; None: table 0 for every env); the state's last-action columns and a
+                recording keep the actor's own command.  Attaching zeroes the env's command history.  A table shorter than
+                ``episode_step_limit`` holds its last row."""
+                self._set_schedule(schedules.DELAY, bank, ids)
+
             def clear_wrench_schedule(self): self._clear_schedule(schedules.WRENCH)
             def clear_vehicle_schedule(self): self._clear_schedule(schedules.VEHICLE)
             def clear_wind_schedule(self): self._clear_schedule(schedules.WIND)
+            def clear_delay_schedule(self): self._clear_schedule(schedules.DELAY)
 
             @property
             def wrench_schedule(self):
@@ -556,6 +585,11 @@ class VectorModule:
             def wind_schedule(self):
                 """(bank, ids) of the attached schedule, or None."""
                 return self._schedule(schedules.WIND)
+
+            @property
+            def delay_schedule(self):
+                """(bank, ids) of the attached schedule, or None."""
+                return self._schedule(schedules.DELAY)
 
             def tracking_error(self):
                 """-> (sum_sq [N] float32, steps [N] uint32): per env, the running sum of |p - p_ref|^2 over the steps it took in
