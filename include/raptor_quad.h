@@ -93,7 +93,8 @@ extern "C" {
                               (still 5: rq_wrench_bank_{create,destroy} and rq_env_{set,get}_wrench_schedule added, no struct changed)
                               (still 5: rq_vehicle_bank_{create,destroy} and rq_env_{set,get}_vehicle_schedule added, no struct changed)
                               (still 5: rq_wind_bank_{create,destroy} and rq_env_{set,get}_wind_schedule added, no struct changed)
-                              (still 5: rq_delay_bank_{create,destroy} and rq_env_{set,clear,get}_delay_schedule added, no struct changed) */
+                              (still 5: rq_delay_bank_{create,destroy} and rq_env_{set,clear,get}_delay_schedule added, no struct changed)
+                              (still 5: rq_sensor_bank_{create,destroy} and rq_env_{set,clear,get}_sensor_schedule added, no struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -646,7 +647,7 @@ RQ_API int rq_env_get_wind_schedule(const rq_env* env, rq_wind_bank** bank /* NU
  * f16x2 policy, a SampleAndSquash stage, rq_rollout_teachers* and an env that carries another schedule too are refused in fused mode
  * while a delay schedule is attached (nothing runs chained in their place, state, statistics, hidden state and history untouched) -
  * all of them run chained.  The small-batch loop steps such an env with plain launches (no resident executor, no speculative policy
- * step).  Not modelled: observation (sensor) latency, delays in fractions of a step, delays above RQ_DELAY_MAX_STEPS. */
+ * step).  Not modelled: delays in fractions of a step, delays above RQ_DELAY_MAX_STEPS. */
 #define RQ_DELAY_MAX_STEPS 16
 typedef struct rq_delay_bank rq_delay_bank;
 RQ_API int rq_delay_bank_create(rq_device* dev, const uint8_t* host_rows /* [n_tables][rows] */, uint32_t n_tables, uint32_t rows,
@@ -657,6 +658,51 @@ RQ_API int rq_env_set_delay_schedule(rq_env* env, rq_delay_bank* bank /* NULL de
 RQ_API int rq_env_clear_delay_schedule(rq_env* env);
 RQ_API int rq_env_get_delay_schedule(const rq_env* env, rq_delay_bank** bank /* NULL when none */,
                                      uint32_t* delay_id_out /* host [n_envs] or NULL */);
+
+/* ---- Sensor schedule: observation latency.  Motion capture over radio, or an onboard estimator slower than the controller, hands
+ * the policy a state estimate that is one to several control periods old; the delay schedule above is the same on the command side.
+ * A SENSOR BANK is n_tables tables of one length, host_rows [n_tables][rows] uint8 row-major: the delay in steps, 0 <= d <=
+ * RQ_SENSOR_MAX_STEPS.  A schedule is attached to an ENV: a bank plus one table id per env.  While it is attached EVERY observation
+ * assembled for env i (rq_observe, and every rollout of a policy, a policy bank and a teacher bank, chained; fused as said below) is
+ *     k    = the env's episode step count as the observing kernel sees it (0 right after a reset or a thaw)
+ *     z_k  = columns 0..17 of the observation as they are assembled without the schedule (position 0..2, rotation matrix 3..11,
+ *            linear velocity 12..14, angular velocity 15..17), with the observation noise of that call's epoch, BEFORE any setpoint
+ *            row is subtracted
+ *     d    = table[sensor_id[i]][min(k, rows - 1)]           (a table shorter than an episode holds its last row)
+ *     d'   = min(d, k)                                       (an episode younger than the delay sees its first reading held; it
+ *                                                             never sees a reading of the episode before)
+ *     delivered columns 0..17 = the stored bits of z_{k-d'}; columns 18..21 (the controller's own last command) and, in rq_observe's
+ *            26-wide row, the rotor tail 22..25 are today's values
+ * A tracked rollout subtracts the setpoint row of step k from the delivered columns (the controller knows the current setpoint); the
+ * tracking error stays on the true position.  State and env step are unchanged; a recording holds what the policy saw
+ * (raptor_amd.sensors.delivered is the NumPy restatement of the rule).  A table of zeros gives the bits of no schedule.
+ * The env owns the READINGS: a ring on the device of 2 * RQ_SENSOR_MAX_STEPS slots x 18 fields x ld floats, slot k mod 32,
+ * allocated at the first attachment and kept, zeroed at every attachment - readings from before an attachment read as zeros.  An
+ * observation assembled at step k writes z_k to slot k for the envs inside the batch that are not frozen, then reads slot k - d'
+ * where d' >= 1; the two never coincide.  Observing twice at one step rewrites the slot (with noise the later draw stands).  One
+ * ring serves fused and chained launches and persists across calls, freezes and graph replays.
+ * rq_sensor_bank_create refuses a null argument, n_tables == 0, rows == 0, an entry above RQ_SENSOR_MAX_STEPS (the message names
+ * table and row) and n_tables * rows >= 2^28, all before the device is looked at.  rq_env_set_sensor_schedule (bank NULL: detach, as
+ * rq_env_clear_sensor_schedule does; sensor_id NULL: table 0 for every env) refuses a bank of another rq_device
+ * (RQ_ERR_SHAPE_MISMATCH) and an id >= n_tables (the message names the env).  rq_sensor_bank_destroy is refused while the bank is
+ * attached to a live env; rq_env_destroy detaches.  Chained mode delivers with one small kernel over the env's observation buffer
+ * (k_sensor_apply) behind every kernel that assembles an observation: every policy precision, the SampleAndSquash stage, teacher
+ * banks and the four other schedules fly beside a sensor schedule there.  In fused mode the fp32 policy and policy-bank kernels fly
+ * it (k_rollout_fused_sensor); a bf16 / f16x2 policy, a SampleAndSquash stage, rq_rollout_teachers* and an env that carries another
+ * schedule too are refused in fused mode (nothing runs chained in their place; state, statistics, hidden state and readings
+ * untouched).  The small-batch loop observes and steps such an env with plain launches (no observation cache, no mailbox rows, no
+ * speculative policy step, no resident executor).  Not modelled: bias, scale, dropped readings, delays in fractions of a step,
+ * per-column delays. */
+#define RQ_SENSOR_MAX_STEPS 16
+typedef struct rq_sensor_bank rq_sensor_bank;
+RQ_API int rq_sensor_bank_create(rq_device* dev, const uint8_t* host_rows /* [n_tables][rows] */, uint32_t n_tables, uint32_t rows,
+                                 rq_sensor_bank** out);
+RQ_API int rq_sensor_bank_destroy(rq_sensor_bank* bank);
+RQ_API int rq_env_set_sensor_schedule(rq_env* env, rq_sensor_bank* bank /* NULL detaches */,
+                                      const uint32_t* sensor_id /* host [n_envs] or NULL = table 0 */);
+RQ_API int rq_env_clear_sensor_schedule(rq_env* env);
+RQ_API int rq_env_get_sensor_schedule(const rq_env* env, rq_sensor_bank** bank /* NULL when none */,
+                                      uint32_t* sensor_id_out /* host [n_envs] or NULL */);
 
 /* ---- Learner: the student's gradient over a recorded trajectory (README.md:208-216, the distillation step's regression) ----
  * Forward: the policy on the recorded observations obs [T][22][ld] under rq_trajectory_relabel's episode rules (GRU state back to

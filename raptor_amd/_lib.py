@@ -254,6 +254,11 @@ _SIGNATURES = {
     "rq_env_set_delay_schedule": [_vp, _vp, _vp],
     "rq_env_clear_delay_schedule": [_vp],
     "rq_env_get_delay_schedule": [_vp, C.POINTER(_vp), _vp],
+    "rq_sensor_bank_create": [_vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(_vp)],
+    "rq_sensor_bank_destroy": [_vp],
+    "rq_env_set_sensor_schedule": [_vp, _vp, _vp],
+    "rq_env_clear_sensor_schedule": [_vp],
+    "rq_env_get_sensor_schedule": [_vp, C.POINTER(_vp), _vp],
 }
 _RESTYPES = {"rq_last_error": C.c_char_p, "rq_status_string": C.c_char_p}
 

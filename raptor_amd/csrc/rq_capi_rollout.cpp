@@ -318,6 +318,9 @@ int env_schedule_set(const char* who, int kind, rq_env* env, ScheduleBank* bank,
     if (kind == kDelay)      // with the env's command history: made on the first attachment, zeroed at every one
         return first_rows_failed("delay schedule", env->delay_history.attach(dev->stream, slot, bank, id, env->n, env->ld,
                                                                              (size_t)rq::kDelaySlots * RQ_ACTION_DIM * env->ld));
+    if (kind == kSensor)     // with the env's readings: likewise, a ring of its own
+        return first_rows_failed("sensor schedule", env->sensor_history.attach(dev->stream, slot, bank, id, env->n, env->ld,
+                                                                              (size_t)rq::kSensorSlots * rq::kSensorFields * env->ld));
     return first_rows_failed((noun + " schedule").c_str(), slot.attach(dev->stream, bank, id, env->n, env->ld));
 }
 
@@ -330,6 +333,36 @@ int env_schedule_get(const char* who, int kind, const rq_env* env, T** bank, uin
     return RQ_OK;
 }
 
+// a delay bank's and a sensor bank's entries are bytes: their own checks, in the words of row_tables_create, then the same handle
+// (`noun`: "delay", "sensor"; `max_steps`: RQ_DELAY_MAX_STEPS, RQ_SENSOR_MAX_STEPS)
+template <typename T>
+int steps_bank_create(const char* who, const std::string& noun, uint32_t max_steps, rq_device* dev, const uint8_t* host_rows,
+                             uint32_t n_tables, uint32_t rows, T** out) {
+    RQ_REFUSE(who, dev && host_rows && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    RQ_REFUSE(who, n_tables > 0 && rows > 0, RQ_ERR_INVALID_ARGUMENT, "a " + noun + " bank needs at least one table of at least one row");
+    RQ_REFUSE(who, (uint64_t)n_tables * rows < (1ull << 28), RQ_ERR_INVALID_ARGUMENT, "a " + noun + " bank holds fewer than 2^28 rows in all");
+    const size_t bytes = (size_t)n_tables * rows;
+    for (size_t j = 0; j < bytes; ++j)
+        RQ_REFUSE(who, host_rows[j] <= max_steps, RQ_ERR_INVALID_ARGUMENT,
+                  noun + " bank holds a delay above " + std::to_string(max_steps) + " steps: table " + std::to_string(j / rows) +
+                      ", row " + std::to_string(j % rows) + " (" + std::to_string((unsigned)host_rows[j]) + ")");
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    T* r = new (std::nothrow) T();
+    RQ_REFUSE(who, r, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
+    r->dev = dev; r->ordinal = dev->ordinal; r->n_tables = n_tables; r->rows = rows;
+    if (r->steps.alloc(bytes) != hipSuccess) {
+        delete r;
+        return fail(RQ_ERR_OUT_OF_MEMORY, std::string(who) + ": device allocation failed");
+    }
+    const hipError_t e = hipMemcpy(r->steps, host_rows, bytes, hipMemcpyHostToDevice);      // (synchronous, as row_tables_create's)
+    if (e != hipSuccess) {
+        delete r;
+        return hip_failed(who, "hipMemcpy", e);
+    }
+    *out = r;
+    return RQ_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -374,7 +407,7 @@ RQ_API int rq_reference_bank_create(rq_device* dev, const float* host_rows, uint
 
 RQ_API int rq_reference_bank_destroy(rq_reference_bank* references) { return row_tables_destroy(references); }
 
-// ---------------------------------------------------------------------------- Schedules: wrench, vehicle, wind, delay
+// ---------------------------------------------------------------------------- Schedules: wrench, vehicle, wind, delay, sensor
 RQ_API int rq_wrench_bank_create(rq_device* dev, const float* host_rows, uint32_t n_tables, uint32_t rows, int units, rq_wrench_bank** out) {
     RQ_REQUIRE(units == RQ_WRENCH_RELATIVE || units == RQ_WRENCH_ABSOLUTE, RQ_ERR_INVALID_ARGUMENT,
                "unknown units: RQ_WRENCH_RELATIVE or RQ_WRENCH_ABSOLUTE");
@@ -389,33 +422,11 @@ RQ_API int rq_wind_bank_create(rq_device* dev, const float* host_rows, uint32_t 
     return row_tables_create(__func__, kWind, dev, host_rows, n_tables, rows, out);
 }
 
-// a delay bank's entries are bytes: its own checks, in the words of row_tables_create, then the same handle
 RQ_API int rq_delay_bank_create(rq_device* dev, const uint8_t* host_rows, uint32_t n_tables, uint32_t rows, rq_delay_bank** out) {
-    const char* who = __func__;
-    RQ_REFUSE(who, dev && host_rows && out, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    RQ_REFUSE(who, n_tables > 0 && rows > 0, RQ_ERR_INVALID_ARGUMENT, "a delay bank needs at least one table of at least one row");
-    RQ_REFUSE(who, (uint64_t)n_tables * rows < (1ull << 28), RQ_ERR_INVALID_ARGUMENT, "a delay bank holds fewer than 2^28 rows in all");
-    const size_t bytes = (size_t)n_tables * rows;
-    for (size_t j = 0; j < bytes; ++j)
-        RQ_REFUSE(who, host_rows[j] <= RQ_DELAY_MAX_STEPS, RQ_ERR_INVALID_ARGUMENT,
-                  "delay bank holds a delay above " + std::to_string(RQ_DELAY_MAX_STEPS) + " steps: table " + std::to_string(j / rows) +
-                      ", row " + std::to_string(j % rows) + " (" + std::to_string((unsigned)host_rows[j]) + ")");
-    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
-    rq_delay_bank* r = new (std::nothrow) rq_delay_bank();
-    RQ_REFUSE(who, r, RQ_ERR_OUT_OF_MEMORY, "host allocation failed");
-    r->dev = dev; r->ordinal = dev->ordinal; r->n_tables = n_tables; r->rows = rows;
-    if (r->steps.alloc(bytes) != hipSuccess) {
-        delete r;
-        return fail(RQ_ERR_OUT_OF_MEMORY, std::string(who) + ": device allocation failed");
-    }
-    const hipError_t e = hipMemcpy(r->steps, host_rows, bytes, hipMemcpyHostToDevice);      // (synchronous, as row_tables_create's)
-    if (e != hipSuccess) {
-        delete r;
-        return hip_failed(who, "hipMemcpy", e);
-    }
-    *out = r;
-    return RQ_OK;
+    return steps_bank_create(__func__, "delay", RQ_DELAY_MAX_STEPS, dev, host_rows, n_tables, rows, out);
+}
+RQ_API int rq_sensor_bank_create(rq_device* dev, const uint8_t* host_rows, uint32_t n_tables, uint32_t rows, rq_sensor_bank** out) {
+    return steps_bank_create(__func__, "sensor", RQ_SENSOR_MAX_STEPS, dev, host_rows, n_tables, rows, out);
 }
 
 RQ_API int rq_wrench_bank_destroy(rq_wrench_bank* bank) {
@@ -436,6 +447,11 @@ RQ_API int rq_delay_bank_destroy(rq_delay_bank* bank) {
     return rc ? rc : row_tables_destroy(bank);
 }
 
+RQ_API int rq_sensor_bank_destroy(rq_sensor_bank* bank) {
+    const int rc = schedule_bank_destroy(__func__, kSensor, bank);
+    return rc ? rc : row_tables_destroy(bank);
+}
+
 RQ_API int rq_env_set_wrench_schedule(rq_env* env, rq_wrench_bank* bank, const uint32_t* wrench_id) {
     return env_schedule_set(__func__, kWrench, env, bank, wrench_id);
 }
@@ -451,6 +467,11 @@ RQ_API int rq_env_set_delay_schedule(rq_env* env, rq_delay_bank* bank, const uin
 }
 RQ_API int rq_env_clear_delay_schedule(rq_env* env) { return env_schedule_set(__func__, kDelay, env, nullptr, nullptr); }
 
+RQ_API int rq_env_set_sensor_schedule(rq_env* env, rq_sensor_bank* bank, const uint32_t* sensor_id) {
+    return env_schedule_set(__func__, kSensor, env, bank, sensor_id);
+}
+RQ_API int rq_env_clear_sensor_schedule(rq_env* env) { return env_schedule_set(__func__, kSensor, env, nullptr, nullptr); }
+
 RQ_API int rq_env_get_wrench_schedule(const rq_env* env, rq_wrench_bank** bank, uint32_t* wrench_id_out) {
     return env_schedule_get(__func__, kWrench, env, bank, wrench_id_out);
 }
@@ -463,6 +484,10 @@ RQ_API int rq_env_get_wind_schedule(const rq_env* env, rq_wind_bank** bank, uint
 
 RQ_API int rq_env_get_delay_schedule(const rq_env* env, rq_delay_bank** bank, uint32_t* delay_id_out) {
     return env_schedule_get(__func__, kDelay, env, bank, delay_id_out);
+}
+
+RQ_API int rq_env_get_sensor_schedule(const rq_env* env, rq_sensor_bank** bank, uint32_t* sensor_id_out) {
+    return env_schedule_get(__func__, kSensor, env, bank, sensor_id_out);
 }
 
 // ---------------------------------------------------------------------------- Trajectory

@@ -37,17 +37,25 @@ RQ_API int rq_observe(rq_device* dev, rq_env* env, const rq_params* params, cons
     RQ_REQUIRE(params && state && rng, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(rng->initialized, RQ_ERR_NOT_INITIALIZED, "initialize_rng was not called");
     DeviceScope on_device(dev, rq::KeepResident{}); rc = on_device.rc; if (rc) return rc;
-    if (env->n < kGpuLayoutMinEnvs && !rq::noise_enabled(env->cfg) && obs_cache_holds(dev, env, params, state)) {
+    // a sensor schedule: what is observed depends on the env's readings, not on (params, state) alone - no cache, as with noise; and
+    // k_sensor_apply delivers behind k_observe, so the rows leave through soa_to_host, not through the mailbox k_observe fills
+    const bool sensor = env->has_sensor_schedule();
+    if (env->n < kGpuLayoutMinEnvs && !rq::noise_enabled(env->cfg) && !sensor && obs_cache_holds(dev, env, params, state)) {
         rng->epoch += 1;
         return obs_cache_read(dev, env, observation);
     }
     rc = rq::resident_scope_hook(dev); if (rc) return rc;     // a launch on the stream: the resident executor, if any, goes first
     obs_cache_drop_if(dev, env);
-    const bool mailbox = observation && env->n < kGpuLayoutMinEnvs;
+    const bool mailbox = observation && env->n < kGpuLayoutMinEnvs && !sensor;
     rq::Mailbox mb{};
     if (mailbox) { rc = ensure_mailbox(dev); if (rc) return rc; mb = mailbox_for(dev, false, 0, MbOut::out); }
     RQ_HIP_MB(rq::launch_observe(dev->stream, batch_of(env), rq::noise_cfg(env->cfg), rq::noise_enabled(env->cfg),
                                  rng->seed, rng->epoch, nullptr, params->d, state->d, env->obs, mb), dev, mb);
+    if (sensor) {
+        const auto& slot = env->schedule[kSensor];
+        const rq::SensorPtrs sn{static_cast<const rq_sensor_bank*>(slot.bank)->steps.get(), slot.row0, env->sensor_history.ring, slot.bank->rows, 0u};
+        RQ_HIP(rq::launch_sensor_apply(dev->stream, batch_of(env), env->st, env->obs, sn));
+    }
     rng->epoch += 1;
     if (mailbox) return mailbox_copy_out(dev, mb.seq, mb.rows_out, observation, (size_t)env->n * RQ_OBSERVATION_DIM);
     if (observation) return soa_to_host(dev, env->obs, env->n, env->ld, RQ_OBSERVATION_DIM, observation);
@@ -63,8 +71,9 @@ RQ_API int rq_step(rq_device* dev, rq_env* env, const rq_params* params, const r
     rc = env_schedules(__func__, env, sched); if (rc) return rc;  // the env's schedules, refused before anything is enqueued
     DeviceScope on_device(dev, rq::KeepResident{}); rc = on_device.rc; if (rc) return rc;
     // small batches: the kernel also assembles the observation of the state it writes, for the next observe() (ObservationCache)
+    // (nor while a sensor schedule is attached: rq_observe then delivers out of the env's readings, with plain launches)
     const bool cache_obs = env->n < kGpuLayoutMinEnvs && !rq::noise_enabled(env->cfg) && !params->exposed &&
-                           !next_state->exposed && !env->obs_exposed;
+                           !next_state->exposed && !env->obs_exposed && !env->has_sensor_schedule();
     rq_policy* pol = speculation_candidate(dev, env, cache_obs, action != nullptr);     // evaluated on that observation, speculatively
     // Could the resident executor take this step?  The loop's own shape only: host actions in, observation cached, a speculated
     // fp32 policy step behind it, out of place, on buffers the library alone writes - and the same objects as the kernel in flight.

@@ -527,6 +527,35 @@ __device__ __forceinline__ void delay_write(float* ring, size_t ld, uint32_t i, 
 // what the last-action columns keep of the actor's command: step_inplace's clamp (the raw command is the caller's to keep)
 __device__ __forceinline__ f32x2 delay_history(float a0, float a1) { return f32x2{clampf(a0, -1.0f, 1.0f), clampf(a1, -1.0f, 1.0f)}; }
 
+// ------------------------------------------------------------------ sensor schedule ----
+// A sensor schedule (rq_env_set_sensor_schedule) puts d control periods between the reading of the vehicle and the policy that sees
+// it: d = row k of the env's own table of bytes, k = the env's episode step count as the observation is assembled, clamped to the
+// table, and d' = min(d, k) - an episode younger than the delay sees its first reading held, never one of the episode before.  The
+// reading z_k is the observation's columns 0..17 (position, rotation matrix, linear and angular velocity; kSensorFields) as they are
+// assembled, noise included, before any setpoint row comes off; the policy sees z_{k-d'} in their place, the stored bits.  The
+// readings live in the env's ring (SensorPtrs): slot k mod kSensorSlots, kSensorFields field rows of ld.  An observation writes z_k
+// to slot k where the env is inside the batch and not frozen, then reads slot k - d' where d' >= 1; the two never coincide
+// (kSensorSlots is twice the longest delay).  Plain loads and stores, as the delay schedule's above: one lane's store and its later
+// load of one address stay in program order, in one launch or across two.  The functions below are the only place any path does this.
+__device__ __forceinline__ uint32_t sensor_row(const uint8_t* __restrict__ tab, uint32_t rows, uint32_t row0, uint32_t k) {
+    const uint32_t d = tab[(size_t)row0 + (k < rows ? k : rows - 1u)];
+    return d < k ? d : k;       // d'
+}
+// the reading of step k into its slot (the caller knows that the env is inside the batch and not frozen)
+__device__ __forceinline__ void sensor_write(float* ring, size_t ld, uint32_t i, uint32_t k, const float* z) {
+    float* slot = ring + (size_t)(k & (kSensorSlots - 1u)) * kSensorFields * ld + i;
+#pragma unroll
+    for (uint32_t j = 0; j < kSensorFields; ++j) slot[(size_t)j * ld] = z[j];
+}
+// z <- the reading of d' steps ago, 1 <= d' <= k; left alone for d' = 0 (the caller has z_k)
+__device__ __forceinline__ void sensor_read(const float* ring, size_t ld, uint32_t i, uint32_t k, uint32_t dp, float* z) {
+    const float* slot = ring + (size_t)((k - dp) & (kSensorSlots - 1u)) * kSensorFields * ld + i;
+    if (dp != 0) {
+#pragma unroll
+        for (uint32_t j = 0; j < kSensorFields; ++j) z[j] = slot[(size_t)j * ld];
+    }
+}
+
 // ------------------------------------------------------------------ parameter sampling -
 
 __device__ __forceinline__ void sample_params(const SampleCfg& c, uint64_t seed, uint32_t epoch, uint64_t genv,

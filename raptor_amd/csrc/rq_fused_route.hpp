@@ -27,24 +27,27 @@ struct FusedTraits {
     bool vehicle = false;   // the env carries a vehicle schedule
     bool wind = false;      // the env carries a wind schedule
     bool delay = false;     // the env carries a delay schedule
+    bool sensor = false;    // the env carries a sensor schedule
 };
 
 // vehicle: the env carries a vehicle schedule - k_rollout_fused_vehicle flies the launch, whatever `family` (what the launch would be
 // without the schedule) says; the entry point is one for a policy and a bank, tracked or not, at every native interval
-// wind: likewise for a wind schedule and k_rollout_fused_wind; delay: for a delay schedule and k_rollout_fused_delay
-struct FusedRoute { FusedFamily family; FusedBuild build; bool vehicle = false; bool wind = false; bool delay = false; };
+// wind: likewise for a wind schedule and k_rollout_fused_wind; delay: for a delay schedule and k_rollout_fused_delay; sensor: for a
+// sensor schedule and k_rollout_fused_sensor
+struct FusedRoute { FusedFamily family; FusedBuild build; bool vehicle = false; bool wind = false; bool delay = false; bool sensor = false; };
 
 constexpr FusedRoute route_fused(const FusedTraits& t) {
     const bool f32 = t.precision == RQ_POLICY_FP32, bf16 = t.precision == RQ_POLICY_BF16_MFMA, f16x2 = t.precision == RQ_POLICY_F16X2_MFMA;
     // What no kernel is built for (the C layer refuses each before anything is enqueued): a schedule beside a 16-bit policy or a
     // SampleAndSquash stage; that stage anywhere but in the PLAIN family; a bank in anything but fp32; a vehicle schedule beside a
     // 16-bit policy, that stage or a wrench schedule; a wind schedule beside a 16-bit policy, that stage or another schedule;
-    // a delay schedule likewise.
+    // a delay schedule likewise; a sensor schedule likewise.
     const bool unsupported = !(f32 || bf16 || f16x2) || (t.wrench && (!f32 || t.sas)) ||
                              (t.sas && (t.tracked || t.bank || t.interval > 1)) || (t.bank && !f32) ||
                              (t.vehicle && (!f32 || t.sas || t.wrench)) || (t.wind && (!f32 || t.sas || t.wrench || t.vehicle)) ||
-                             (t.delay && (!f32 || t.sas || t.wrench || t.vehicle || t.wind));
-    if (unsupported) return {FusedFamily::UNSUPPORTED, FusedBuild::F32, false, false, false};
+                             (t.delay && (!f32 || t.sas || t.wrench || t.vehicle || t.wind)) ||
+                             (t.sensor && (!f32 || t.sas || t.wrench || t.vehicle || t.wind || t.delay));
+    if (unsupported) return {FusedFamily::UNSUPPORTED, FusedBuild::F32, false, false, false, false};
     // WRENCH and the vehicle, wind and delay schedules' kernels serve one policy (tables null, single_interval = its interval) and a bank (tables set,
     // single_interval = 1) alike; TRACK is a template bool of RATE, BANK_RATE, WRENCH and the vehicle, wind and delay kernels, SAS one of PLAIN.
     const FusedFamily family = t.wrench ? FusedFamily::WRENCH
@@ -61,7 +64,7 @@ constexpr FusedRoute route_fused(const FusedTraits& t) {
                              : f16x2 ? FusedBuild::F16X2
                              : ((family == FusedFamily::PLAIN && t.sas) || t.n > kOneWavePerSimdEnvs) ? FusedBuild::F32_LEAN
                                                                                                       : FusedBuild::F32;
-    return {family, build, t.vehicle, t.wind, t.delay};
+    return {family, build, t.vehicle, t.wind, t.delay, t.sensor};
 }
 
 }  // namespace rq

@@ -1342,6 +1342,32 @@ hipError_t launch_track_shift(hipStream_t s, Batch b, const float* state, StatsP
     return RQ_KLAUNCH_STATUS();
 }
 
+// ------------------------------------------------------------------ sensor schedule ---
+// the chained mode's and rq_observe's share of a sensor schedule: see launch_sensor_apply.  One lane per env over the observation
+// another kernel assembled (a kernel boundary lies between its stores and these loads); the ring sees plain accesses only.
+__global__ __launch_bounds__(kBlock) void k_sensor_apply(Batch b, StatsPtrs st, float* __restrict__ obs, SensorPtrs sn) {
+    const uint32_t i = env_index();
+    if (i >= b.n) return;
+    if (st.frozen[i]) return;                  // no reading is taken of an env whose episode is over: its observation stays
+    const uint32_t k = st.steps[i];
+    const uint32_t dp = sensor_row(sn.rows, sn.n_rows, sn.row0[i], k);
+    float z[kSensorFields];
+#pragma unroll
+    for (uint32_t j = 0; j < kSensorFields; ++j) z[j] = field(obs, j, b.ld)[i];
+    sensor_write(sn.ring, b.ld, i, k, z);
+    if (dp != 0) {
+        sensor_read(sn.ring, b.ld, i, k, dp, z);
+#pragma unroll
+        for (uint32_t j = 0; j < kSensorFields; ++j) field(obs, j, b.ld)[i] = z[j];
+    }
+}
+
+hipError_t launch_sensor_apply(hipStream_t s, Batch b, StatsPtrs st, float* obs, SensorPtrs sn) {
+    if (b.n == 0) return hipSuccess;
+    RQ_KLAUNCH(k_sensor_apply, grid_for(b.n, kBlock), kBlock, s, b, st, obs, sn);
+    return RQ_KLAUNCH_STATUS();
+}
+
 // ------------------------------------------------------------------ policy bank (rq_rollout_policies[_track]) ---
 // A bank of student policies, one per WAVE: the 64-env block g of a batch is flown by policy block_policy[g], whose operand image is
 // images + block_policy[g] * image_floats, at native interval policy_interval[block_policy[g]].  The weights are wave-uniform MFMA A
@@ -1375,6 +1401,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WindPtrs wd{};
     constexpr bool DELAY = false;
     constexpr DelayPtrs dl{};
+    constexpr bool SENSOR = false;
+    constexpr SensorPtrs sn{};
     constexpr uint32_t interval = 1;
     const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
 #include "rq_rollout_body.inc"
@@ -1406,6 +1434,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WindPtrs wd{};
     constexpr bool DELAY = false;
     constexpr DelayPtrs dl{};
+    constexpr bool SENSOR = false;
+    constexpr SensorPtrs sn{};
     const uint32_t policy = block_policy[blockIdx.x];
     const uint32_t interval = policy_interval[policy];
     const float* __restrict__ packed = images + (size_t)policy * image_floats;
@@ -1450,7 +1480,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = true, VEHICLE = false, WIND = false, DELAY = false;
+    constexpr bool RATE = true, SAS = false, WRENCH = true, VEHICLE = false, WIND = false, DELAY = false, SENSOR = false;
+    constexpr SensorPtrs sn{};
     constexpr DelayPtrs dl{};
     constexpr SasArgs sas{};
     constexpr VehiclePtrs vh{};
@@ -1495,7 +1526,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, VehiclePtrs vh,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = true, WIND = false, DELAY = false;
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = true, WIND = false, DELAY = false, SENSOR = false;
+    constexpr SensorPtrs sn{};
     constexpr DelayPtrs dl{};
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
@@ -1539,7 +1571,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WindPtrs wd,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = true, DELAY = false;
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = true, DELAY = false, SENSOR = false;
+    constexpr SensorPtrs sn{};
     constexpr DelayPtrs dl{};
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
@@ -1583,7 +1616,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                uint32_t single_interval,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk, DelayPtrs dl,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = false, DELAY = true;
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = false, DELAY = true, SENSOR = false;
+    constexpr SensorPtrs sn{};
     constexpr SasArgs sas{};
     constexpr WrenchPtrs wr{};
     constexpr VehiclePtrs vh{};
@@ -1604,6 +1638,52 @@ static inline void launch_fused_delay_actor(hipStream_t s, const FusedArgs& a) {
         hipLaunchKernelGGL((k_rollout_fused_delay<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
                            a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
                            a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.dl, a.span);
+    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
+}
+
+// ---- the fused kernel of an env that carries a sensor schedule
+// Built as k_rollout_fused_delay is - the RATE loop with optional block tables, one entry point for rq_rollout, rq_rollout_record,
+// rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every native interval - with SENSOR on: the env's first row is
+// loaded once per launch, every step asks for its byte of delay and, from the env's readings, for the 18 floats of the reading taken
+// that many steps ago (none if no lane of the wave is behind); behind observe_head the step's own reading goes into the ring where the
+// env is inside the batch and not frozen, and the old one takes its place in front of the setpoint's shift and the actor
+// (rq_rollout_body.inc).  fp32 actors only: the host refuses the 16-bit policies, the SampleAndSquash stage and another schedule
+// beside a sensor schedule in fused mode.
+template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
+__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_sensor(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
+                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
+                                                               const float* __restrict__ params,
+                                                               float* __restrict__ state,
+                                                               float* __restrict__ hidden,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ images,
+                                                               const uint32_t* __restrict__ block_policy,
+                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
+                                                               uint32_t single_interval,
+                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, SensorPtrs sn,
+                                                               unsigned long long* __restrict__ span) {
+    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = false, DELAY = false, SENSOR = true;
+    constexpr SasArgs sas{};
+    constexpr WrenchPtrs wr{};
+    constexpr VehiclePtrs vh{};
+    constexpr WindPtrs wd{};
+    constexpr DelayPtrs dl{};
+    uint32_t policy = 0, interval = single_interval;
+    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
+        policy = block_policy[blockIdx.x];
+        interval = policy_interval[policy];
+    }
+    const float* __restrict__ packed = images + (size_t)policy * image_floats;
+#include "rq_rollout_body.inc"
+}
+
+// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
+template <typename ACTOR>
+static inline void launch_fused_sensor_actor(hipStream_t s, const FusedArgs& a) {
+    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
+        hipLaunchKernelGGL((k_rollout_fused_sensor<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
+                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
+                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.sn, a.span);
     }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
@@ -1631,14 +1711,16 @@ hipError_t launch_rollout_fused(hipStream_t s, const FusedArgs& a) {
     case FusedBuild::F16X2:      // the 16-bit actors live in their own translation unit (rq_kernels_16bit.hip: a place for per-build flags)
         return launch_rollout_fused_16bit(s, a, r.family);
     case FusedBuild::F32_LEAN:
-        if (r.delay)                       launch_fused_delay_actor<ActorF32Lean>(s, a);      // (a delay schedule: its own entry point)
+        if (r.sensor)                      launch_fused_sensor_actor<ActorF32Lean>(s, a);     // (a sensor schedule: its own entry point)
+        else if (r.delay)                  launch_fused_delay_actor<ActorF32Lean>(s, a);      // (a delay schedule: likewise)
         else if (r.wind)                   launch_fused_wind_actor<ActorF32Lean>(s, a);       // (a wind schedule: likewise)
         else if (r.vehicle)                launch_fused_vehicle_actor<ActorF32Lean>(s, a);    // (a vehicle schedule: likewise)
         else if (a.sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a);      // (PLAIN: route_fused allows the stage nowhere else)
         else                               launch_fused_f32_actor<ActorF32Lean>(s, a, r.family);
         break;
     case FusedBuild::F32:
-        if (r.delay)        launch_fused_delay_actor<ActorF32>(s, a);
+        if (r.sensor)       launch_fused_sensor_actor<ActorF32>(s, a);
+        else if (r.delay)   launch_fused_delay_actor<ActorF32>(s, a);
         else if (r.wind)    launch_fused_wind_actor<ActorF32>(s, a);
         else if (r.vehicle) launch_fused_vehicle_actor<ActorF32>(s, a);
         else                launch_fused_f32_actor<ActorF32>(s, a, r.family);

@@ -191,6 +191,11 @@ hipError_t launch_bank_initial_hidden(hipStream_t s, uint32_t ld, float* hidden,
 // each env's episode step count comes off obs [RQ_OBSERVATION_DIM][ld] in place, and the envs that are not frozen add this step's
 // tracking error - the fused kernel's arithmetic (rq_device_math.hpp track_*).  Appends a graph node under a GraphSink.
 hipError_t launch_track_shift(hipStream_t s, Batch b, const float* state, StatsPtrs st, float* obs, TrackPtrs trk);
+// an env that carries a sensor schedule, behind whatever assembled its observation in obs [RQ_OBSERVATION_DIM][ld] (k_observe,
+// or the k_step that folds the next one) and in front of launch_track_shift: the envs that are not frozen put columns 0..17 into the
+// slot of their episode step count and take those of d' steps ago in their place (rq_device_math.hpp sensor_*; the fused kernel's
+// functions).  Appends a graph node under a GraphSink.
+hipError_t launch_sensor_apply(hipStream_t s, Batch b, StatsPtrs st, float* obs, SensorPtrs sn);
 // chained mode: copy step t (env obs/action buffers + last reward / done code) into the trajectory
 hipError_t launch_record(hipStream_t s, Batch b, const float* obs, const float* act, StatsPtrs st, TrajPtrs traj);
 // ---- MFMA operand images of the policy (layout rationale: rq_device_math.hpp "actor") ----------
@@ -333,6 +338,7 @@ struct FusedArgs {
     VehiclePtrs vh{};                              // rows != nullptr: the env's vehicle schedule (fp32, no stage, no wrench schedule)
     WindPtrs wd{};                                 // rows != nullptr: the env's wind schedule (fp32, no stage, no other schedule)
     DelayPtrs dl{};                                // rows != nullptr: the env's delay schedule (fp32, no stage, no other schedule)
+    SensorPtrs sn{};                               // rows != nullptr: the env's sensor schedule (fp32, no stage, no other schedule)
     // The actor.  One policy (block_policy == nullptr): `images` is its operand image in `precision`, with its output stage and its
     // native interval.  A policy bank (fp32, no output stage): the tables described above - `interval` is not read - and whether an
     // entry of policy_interval is above 1 (the host's knowledge: the table is on the device).
@@ -349,7 +355,8 @@ struct FusedArgs {
 };
 inline FusedTraits fused_traits(const FusedArgs& a) {
     return {a.b.n, a.precision, a.sas.mode != RQ_SAS_OFF, a.trk.ref != nullptr, a.wr.rows != nullptr, a.interval,
-            a.block_policy != nullptr, a.bank_rated, a.vh.rows != nullptr, a.wd.rows != nullptr, a.dl.rows != nullptr};
+            a.block_policy != nullptr, a.bank_rated, a.vh.rows != nullptr, a.wd.rows != nullptr, a.dl.rows != nullptr,
+            a.sn.rows != nullptr};
 }
 // The kernel route_fused(fused_traits(a)) names, enqueued on s; hipErrorInvalidValue, and nothing launched, for a description no
 // kernel is built for.  n == 0 or n_steps == 0: nothing to do.

@@ -213,17 +213,18 @@ struct TableKind {
     const char* noun;                   // a schedule's kind, as in "wrench schedule", "wrench id" (a reference: none)
     uint32_t cols;
     enum Rule { kFinite, kPositive, kNonNegativeColumn, kSteps } rule;      // every entry finite; and > 0; and those of `rule_col` >= 0;
-                                        // kSteps: bytes, not floats, each at most RQ_DELAY_MAX_STEPS (rq_delay_bank_create's own check)
+                                        // kSteps: bytes, not floats, each at most RQ_DELAY_MAX_STEPS / RQ_SENSOR_MAX_STEPS (the bank's create makes its own check)
     int rule_col;                       // (a rule about columns names the column in every message)
     const char* detach;                 // the entry point that detaches: what a refused destruction names
 };
 // the schedules first, in the order every walk over them takes: it is the order in which refusals are heard
-enum TableKindId { kWrench, kVehicle, kWind, kDelay, kScheduleKinds, kReference = kScheduleKinds, kReferenceBank, kTableKindCount };
+enum TableKindId { kWrench, kVehicle, kWind, kDelay, kSensor, kScheduleKinds, kReference = kScheduleKinds, kReferenceBank, kTableKindCount };
 inline constexpr TableKind kTableKinds[kTableKindCount] = {
     {"wrench bank", "wrench", 6, TableKind::kFinite, -1, "rq_env_set_wrench_schedule"},
     {"vehicle bank", "vehicle", 4, TableKind::kPositive, -1, "rq_env_set_vehicle_schedule"},      // factors on mass, inertia, thrust, motor lag
     {"wind bank", "wind", 4, TableKind::kNonNegativeColumn, 3, "rq_env_set_wind_schedule"},       // air velocity, specific drag
     {"delay bank", "delay", 1, TableKind::kSteps, -1, "rq_env_set_delay_schedule"},               // control latency in steps
+    {"sensor bank", "sensor", 1, TableKind::kSteps, -1, "rq_env_set_sensor_schedule"},            // observation latency in steps
     {"reference", nullptr, 6, TableKind::kFinite, -1, nullptr},
     {"reference bank", nullptr, 6, TableKind::kFinite, -1, nullptr},
 };
@@ -234,6 +235,7 @@ struct rq_wrench_bank : rqh::ScheduleBank { int units = RQ_WRENCH_RELATIVE; };
 struct rq_vehicle_bank : rqh::ScheduleBank {};
 struct rq_wind_bank : rqh::ScheduleBank {};
 struct rq_delay_bank : rqh::ScheduleBank { rq::DeviceBuffer<uint8_t> steps; };      // [n_tables * rows] bytes; `d` stays empty
+struct rq_sensor_bank : rqh::ScheduleBank { rq::DeviceBuffer<uint8_t> steps; };     // likewise
 
 struct rq_env {
     rq_device* dev = nullptr;
@@ -260,6 +262,8 @@ struct rq_env {
     // attached with, the [ld] first rows every stepping kernel reads and the number that names the attachment.
     rq::EnvSchedule<rqh::ScheduleBank> schedule[rqh::kScheduleKinds];
     rq::DelayHistory delay_history;     // the delay schedule's command history: [rq::kDelaySlots][RQ_ACTION_DIM][ld]
+    rq::DelayHistory sensor_history;    // the sensor schedule's readings: [rq::kSensorSlots][rq::kSensorFields][ld], a ring of its own
+    bool has_sensor_schedule() const { return schedule[rqh::kSensor].bank != nullptr; }
     bool has_schedule() const { for (const auto& s : schedule) if (s.bank) return true; return false; }
     // chained rollouts replay a captured hipGraph of kGraphSteps steps (3 kernel nodes per step + the
     // epoch-counter bump); one executable graph per distinct argument set: what the nodes carry by value, named once
@@ -476,11 +480,11 @@ inline rq::Batch batch_of(const rq_env* env) { return {env->n, env->ld, env->off
 int env_track_stats(rq_env* env, float** sum_sq, uint32_t** steps);
 // ---- rq_capi_rollout.cpp: the env's schedules ----
 // One schedule as the kernels take it, before it is typed (all-null: none attached).  `flag`: the wrench bank's units, 1 = relative.
-// `ring`: the delay schedule's command history.
+// `ring`: the delay schedule's command history, the sensor schedule's readings.
 struct SchedulePtrs { const void* rows = nullptr; const uint32_t* row0 = nullptr; uint32_t n_rows = 0, flag = 0; float* ring = nullptr; };
 int schedule_too_short(const char* who, const rq_env* env, int kind);      // the refusal below, worded
 // The env's schedules, p[kScheduleKinds] in kind order.  Every call that steps asks here before anything is enqueued: a bank with
-// fewer rows than episode_step_limit is refused, but a delay bank (`who`: the caller's name; the config may have changed since the schedule was
+// fewer rows than episode_step_limit is refused, but a delay or a sensor bank (`who`: the caller's name; the config may have changed since the schedule was
 // attached).  Nothing is allocated and no string made unless it refuses: rq_step asks on every call.
 inline int env_schedules(const char* who, const rq_env* env, SchedulePtrs* p) {
     for (int k = 0; k < kScheduleKinds; ++k) {
@@ -488,12 +492,17 @@ inline int env_schedules(const char* who, const rq_env* env, SchedulePtrs* p) {
         const auto& s = env->schedule[k];
         if (!s.bank) continue;
         // (a delay table shorter than an episode holds its last row: a latency is a property of the link, not a course of events)
-        if (k != kDelay && s.bank->rows < env->cfg.episode_step_limit) return schedule_too_short(who, env, k);
+        if (k != kDelay && k != kSensor && s.bank->rows < env->cfg.episode_step_limit) return schedule_too_short(who, env, k);
         p[k] = {s.bank->d.get(), s.row0, s.bank->rows,
                 k == kWrench && static_cast<const rq_wrench_bank*>(s.bank)->units == RQ_WRENCH_RELATIVE ? 1u : 0u, nullptr};
         if (k == kDelay) { p[k].rows = static_cast<const rq_delay_bank*>(s.bank)->steps.get(); p[k].ring = env->delay_history.ring; }
+        if (k == kSensor) { p[k].rows = static_cast<const rq_sensor_bank*>(s.bank)->steps.get(); p[k].ring = env->sensor_history.ring; }
     }
     return RQ_OK;
+}
+// the sensor schedule as k_sensor_apply and k_rollout_fused_sensor take it
+inline rq::SensorPtrs sensor_ptrs(const SchedulePtrs* p) {
+    return {static_cast<const uint8_t*>(p[kSensor].rows), p[kSensor].row0, p[kSensor].ring, p[kSensor].n_rows, 0u};
 }
 // ... typed, for the launch descriptions (rq::EnvStepLaunch, rq::FusedArgs): the kernels' argument types are one per kind
 template <typename Launch>
@@ -502,6 +511,7 @@ void set_schedules(Launch& l, const SchedulePtrs* p) {
     l.vh = {static_cast<const float*>(p[kVehicle].rows), p[kVehicle].row0, p[kVehicle].n_rows, 0u};
     l.wd = {static_cast<const float*>(p[kWind].rows), p[kWind].row0, p[kWind].n_rows, 0u};
     l.dl = {static_cast<const uint8_t*>(p[kDelay].rows), p[kDelay].row0, p[kDelay].ring, p[kDelay].n_rows, 0u};
+    l.sn = sensor_ptrs(p);
 }
 // What fused mode cannot fly while a schedule of `kind` is attached, refused naming the schedule (`what`: a bf16 / f16x2 policy, a
 // SampleAndSquash stage, a teacher bank, another schedule beside it); nothing runs chained in its place.
@@ -647,15 +657,23 @@ int rollout_chained(const RolloutCall& c, const RolloutFrame& f, const Actor& ac
     const uint32_t n_steps = c.n_steps;
     const bool fold = Actor::kFoldAndReplay && !c.traj;
     const char* what = "";            // the launch a failure is reported for
+    // A sensor schedule: k_sensor_apply delivers in env->obs, right behind whatever assembled the observation there - the observe
+    // launch, or the step that folds the next one - and in front of the setpoint's shift; one more kernel node per step of a graph.
+    const rq::SensorPtrs sn = sensor_ptrs(f.sched);
+    auto deliver = [&](hipError_t e) -> hipError_t {
+        if (e != hipSuccess || !sn.rows) return e;
+        what = "rq::launch_sensor_apply";
+        return rq::launch_sensor_apply(dev->stream, f.b, env->st, env->obs, sn);
+    };
     auto one_step = [&](uint32_t epoch, const uint32_t* epoch_base, uint32_t t_record) -> hipError_t {
         hipError_t e = hipSuccess;
         if (!fold) {
             what = "rq::launch_observe";
-            e = rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, epoch, epoch_base, c.params->d, c.state->d, env->obs);
+            e = deliver(rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, epoch, epoch_base, c.params->d, c.state->d, env->obs));
         }
         if (e == hipSuccess && f.trk.ref) { what = "rq::launch_track_shift"; e = rq::launch_track_shift(dev->stream, f.b, c.state->d, env->st, env->obs, f.trk); }
         if (e == hipSuccess) { what = "the actor launch"; e = actor.act(c, f, epoch, epoch_base); }
-        if (e == hipSuccess) { what = "the step launch"; e = actor.step(c, f, epoch, epoch_base, fold); }
+        if (e == hipSuccess) { what = "the step launch"; e = actor.step(c, f, epoch, epoch_base, fold); if (fold) e = deliver(e); }
         if (e == hipSuccess && c.traj) {
             rq::TrajPtrs tt = f.tp; tt.t0 = f.tp.t0 + t_record;
             what = "rq::launch_record"; e = rq::launch_record(dev->stream, f.b, env->obs, env->act, env->st, tt);
@@ -666,14 +684,15 @@ int rollout_chained(const RolloutCall& c, const RolloutFrame& f, const Actor& ac
     if (n_steps && (c.flags & RQ_ROLLOUT_AUTORESET))      // envs frozen by an earlier rollout start their next episode
         if ((e = actor.thaw(c, f)) != hipSuccess) return hip_failed(c.who, "the thaw launch", e);
     if (fold && n_steps) {           // the rollout's first observation (after the thaw: of the re-sampled states)
-        e = rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, rng->epoch, nullptr, c.params->d, c.state->d, env->obs);
-        if (e != hipSuccess) return hip_failed(c.who, "rq::launch_observe", e);
+        what = "rq::launch_observe";
+        e = deliver(rq::launch_observe(dev->stream, f.b, f.nc, f.noise, rng->seed, rng->epoch, nullptr, c.params->d, c.state->d, env->obs));
+        if (e != hipSuccess) return hip_failed(c.who, what, e);
     }
     uint32_t done_steps = 0;
     if constexpr (Actor::kFoldAndReplay) {
         if (fold && n_steps >= kGraphSteps) {
             const rq_env::GraphKey key = actor.graph_key(c, f);     // another value of any of its fields is another graph
-            const uint32_t step_nodes = f.trk.ref ? 3u : 2u;
+            const uint32_t step_nodes = (f.trk.ref ? 3u : 2u) + (sn.rows ? 1u : 0u);
             hipGraphExec_t exec = nullptr;
             for (auto& g : env->graphs)
                 if (g.key == key) { exec = g.exec; break; }

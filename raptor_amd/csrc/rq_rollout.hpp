@@ -76,6 +76,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WindPtrs wd{};
     constexpr bool DELAY = false;
     constexpr DelayPtrs dl{};
+    constexpr bool SENSOR = false;
+    constexpr SensorPtrs sn{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -102,6 +104,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WindPtrs wd{};
     constexpr bool DELAY = false;
     constexpr DelayPtrs dl{};
+    constexpr bool SENSOR = false;
+    constexpr SensorPtrs sn{};
     constexpr uint32_t interval = 1;
 #include "rq_rollout_body.inc"
 }
@@ -128,6 +132,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
     constexpr WindPtrs wd{};
     constexpr bool DELAY = false;
     constexpr DelayPtrs dl{};
+    constexpr bool SENSOR = false;
+    constexpr SensorPtrs sn{};
 #include "rq_rollout_body.inc"
 }
 

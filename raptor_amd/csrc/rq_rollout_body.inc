@@ -2,12 +2,13 @@
 // (TRACK = false), k_rollout_fused_track (TRACK = true, SAS = false) and k_rollout_fused_rate (RATE = true, SAS = false).  Text, not a function: the untracked kernel is compiled from
 // exactly what it was compiled from when the body stood between its braces - its listing does not move when the tracked variant
 // changes - and a __device__ function in between does cost that (the work-group-size folds of a kernel are made before inlining).
-// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, VEHICLE, WIND, DELAY, ACTOR
-// and the names b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, vh, wd, dl, interval, span.
+// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, VEHICLE, WIND, DELAY, SENSOR, ACTOR
+// and the names b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, vh, wd, dl, sn, interval, span.
 // WRENCH (k_rollout_fused_wrench alone; every other entry point defines it false and an empty wr): the env carries a wrench schedule.
 // VEHICLE (k_rollout_fused_vehicle alone; every other entry point defines it false and an empty vh): the env carries a vehicle schedule.
 // WIND (k_rollout_fused_wind alone; every other entry point defines it false and an empty wd): the env carries a wind schedule.
 // DELAY (k_rollout_fused_delay alone; every other entry point defines it false and an empty dl): the env carries a delay schedule.
+// SENSOR (k_rollout_fused_sensor alone; every other entry point defines it false and an empty sn): the env carries a sensor schedule.
     // kernel-level timing (rq_device_set_rollout_timing): every wave leaves the wall-clock ticks (constant rate) at which it
     // came in and went out, and its XCD: the eight dies' counters are offset against one another by microseconds, one die's
     // are consistent - the host takes first-in / last-out per die
@@ -78,6 +79,9 @@
     // DELAY: the first row of the env's own table, once per launch
     [[maybe_unused]] uint32_t dl_row0 = 0;
     if constexpr (DELAY) dl_row0 = dl.row0[i];
+    // SENSOR: likewise
+    [[maybe_unused]] uint32_t sn_row0 = 0;
+    if constexpr (SENSOR) sn_row0 = sn.row0[i];
     const uint8_t last_t_raw = st.last_terminated[i];
     uint8_t last_d = AUTORESET ? (uint8_t)0 : st.last_done[i];       // auto-reset: rebuilt in the epilogue
     const uint8_t frozen_raw = st.frozen[i];
@@ -216,7 +220,30 @@
             dl_d = delay_row(dl.rows, dl.n_rows, dl_row0, ep_steps);
             delay_read(dl.ring, ld, i, ep_steps, dl_d, dl_u);
         }
+        // SENSOR: this step's byte of delay, clamped to the episode's age, and out of the env's readings the 18 floats of the
+        // reading taken that many steps ago (lanes at one episode age read one slot: coalesced); skipped when no lane of the wave
+        // is behind (wave-uniform); consumed behind observe_head
+        [[maybe_unused]] uint32_t sn_d = 0;
+        [[maybe_unused]] bool sn_behind = false;
+        [[maybe_unused]] float sn_z[kSensorFields];
+        if constexpr (SENSOR) {
+            sn_d = sensor_row(sn.rows, sn.n_rows, sn_row0, ep_steps);
+            sn_behind = __builtin_amdgcn_ballot_w64(sn_d != 0) != 0;
+            if (sn_behind) {
+#pragma unroll
+                for (uint32_t j = 0; j < kSensorFields; ++j) sn_z[j] = 0.0f;
+                sensor_read(sn.ring, ld, i, ep_steps, sn_d, sn_z);
+            }
+        }
         observe_head<NOISE>(y, LA01, LA23, nc, seed, epoch0 + t, genv, o);
+        if constexpr (SENSOR) {      // the reading of this step goes into the ring where the env is inside the batch - not a lane past it
+            // shadowing env n - 1 - and not frozen; the policy, the setpoint's shift and a recording see the old one
+            if (valid && (AUTORESET || !frozen)) sensor_write(sn.ring, ld, i, ep_steps, o);
+            if (sn_behind) {
+#pragma unroll
+                for (uint32_t j = 0; j < kSensorFields; ++j) o[j] = sn_d != 0 ? sn_z[j] : o[j];
+            }
+        }
         if constexpr (TRACK) {
             // the setpoint of this step: the row of the env's own episode step count (lanes are at different rows: per-lane
             // loads of a table that stays in the cache), taken off what the policy sees; the error on the true position

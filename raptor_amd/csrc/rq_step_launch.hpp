@@ -79,6 +79,21 @@ struct DelayPtrs {
     uint32_t pad_;
 };
 
+// A sensor schedule (rq_env_set_sensor_schedule): the bank's tables, the env's per-env first rows and the env's readings
+// (rq_device_math.hpp sensor_*).  The readings are a ring of kSensorSlots slots x kSensorFields observation fields x ld: the slot of
+// the reading assembled at episode step k is k mod kSensorSlots.  Twice the longest delay: the slot an observation reads (k - d',
+// 1 <= d' <= RQ_SENSOR_MAX_STEPS) is never the slot it writes (k).
+constexpr uint32_t kSensorSlots = 2u * RQ_SENSOR_MAX_STEPS;
+constexpr uint32_t kSensorFields = 18;      // position, rotation matrix, linear and angular velocity: the observation's columns 0..17
+static_assert((kSensorSlots & (kSensorSlots - 1u)) == 0, "the slot of a step is a mask of its count");
+struct SensorPtrs {
+    const uint8_t* rows;      // [n_tables * n_rows]: the delay in steps, 0 .. RQ_SENSOR_MAX_STEPS; nullptr = none
+    const uint32_t* row0;     // [ld]: sensor_id[i] * n_rows, the first row of env i's table
+    float* ring;              // [kSensorSlots][kSensorFields][ld]: the readings assembled for the env, by episode step
+    uint32_t n_rows;          // rows of one table
+    uint32_t pad_;
+};
+
 // SampleAndSquash output stage of the actor (rq_policy_set_sample_and_squash): mode = rq_sample_and_squash_mode
 struct SasArgs {
     uint32_t mode;                // RQ_SAS_OFF / RQ_SAS_MEAN / RQ_SAS_SAMPLE
@@ -219,6 +234,8 @@ struct EnvStepLaunch {
     VehiclePtrs vh{};                        // rows set: the env's vehicle schedule (not used: the kernels without it)
     WindPtrs wd{};                           // rows set: the env's wind schedule (not used: the kernels without it)
     DelayPtrs dl{};                          // rows set: the env's delay schedule (not used: the kernels without it)
+    SensorPtrs sn{};                         // rows set: the env's sensor schedule; no step kernel reads it (k_sensor_apply delivers
+                                             // behind the step that folds the next observation: launch_sensor_apply)
     // The thaw of a chained rollout under auto-reset reads b, sc, seed, params, st, hidden, weights and block_policy, and re-samples
     // into next_state.
 };
@@ -229,6 +246,7 @@ struct EnvStepLaunch {
 // folded observation.  With a wind schedule (`wind`): k_step_wind<rollout, wrench, vehicle> or k_step_bank_wind<wrench, vehicle>,
 // whichever of the two `family` - what the step would be without the wind - belongs to; vehicle = family is [BANK_]VEHICLE.  With a
 // delay schedule (`delay`): k_step_delay<rollout, wrench, vehicle, wind> or k_step_bank_delay<wrench, vehicle, wind>, named alike.
+// A sensor schedule (e.sn) changes nothing here: the step is the step it would be without it.
 enum class EnvStepFamily { UNSUPPORTED, STEP, WRENCH, VEHICLE, BANK, BANK_WRENCH, BANK_VEHICLE };
 // wrench: VEHICLE's and BANK_VEHICLE's template bool
 struct EnvStepRoute { EnvStepFamily family; bool rollout, wrench; bool wind = false; bool delay = false; };

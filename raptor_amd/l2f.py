@@ -37,7 +37,7 @@ from . import _lib, schedules
 from ._lib import (ACTION_DIM, OBSERVATION_DIM, PARAM_DIM, STATE_DIM, ROLLOUT_AUTORESET, ROLLOUT_CHAINED,
                    ROLLOUT_FUSED, EnvConfig, RaptorQuadError)
 
-__all__ = ["Device", "Reference", "WrenchBank", "VehicleBank", "WindBank", "DelayBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
+__all__ = ["Device", "Reference", "WrenchBank", "VehicleBank", "WindBank", "DelayBank", "SensorBank", "UI", "vector", "vector8", "EnvConfig", "RaptorQuadError"]
 
 
 class UI:
@@ -256,7 +256,28 @@ class DelayBank(_ScheduleBank):
         self._fin = weakref.finalize(self, _lib.load().rq_delay_bank_destroy, h)
 
 
-_BANKS = {schedules.WRENCH: WrenchBank, schedules.VEHICLE: VehicleBank, schedules.WIND: WindBank, schedules.DELAY: DelayBank}
+class SensorBank(_ScheduleBank):
+    """M sensor tables of the same length for ``env.set_sensor_schedule(bank, ids)``: ``tables`` uint8 [M, rows] (or a list of M
+    [rows] tables; ``raptor_amd.sensors`` builds them), the observation latency in steps, at most ``sensors.MAX_STEPS``.  While the
+    bank is attached to an env, every observation assembled for env i carries in columns 0..17 the reading taken as many steps ago as
+    the row of its own episode step count of table ``ids[i]`` says, the first reading of the episode where it is younger
+    (include/raptor_quad.h "Sensor schedule").  The tables are copied to ``device`` once, here."""
+    _kind = schedules.SENSOR
+
+    def __init__(self, device, tables):
+        from . import sensors
+        t = sensors.check_tables(tables)                         # refused before the device is touched
+        h = C.c_void_p()
+        _lib.call("rq_sensor_bank_create", device._h, t.ctypes.data, int(t.shape[0]), int(t.shape[1]), C.byref(h))
+        self._h = h
+        self._device = device
+        self.n_tables = int(t.shape[0])
+        self.rows = int(t.shape[1])
+        self._fin = weakref.finalize(self, _lib.load().rq_sensor_bank_destroy, h)
+
+
+_BANKS = {schedules.WRENCH: WrenchBank, schedules.VEHICLE: VehicleBank, schedules.WIND: WindBank, schedules.DELAY: DelayBank,
+          schedules.SENSOR: SensorBank}
 
 
 def _checked_reference(reference, reference_ids, n_envs):
@@ -301,7 +322,7 @@ def _rollout_call(entry, device, env, params, state, actor_handle, ids, rng, n_s
 
 def tracking_rmse(env, reference, ref_ids, schedule_ids, actor_ids, n_actors):
     """``tracking_rmse`` of a bank's closed-loop table, from ``env.tracking_error()`` grouped by actor (policy or teacher): [n_actors,
-    M] over the scenarios of a schedule (``schedule_ids``: what ``schedules.checked_schedule_ids`` answered - disturbances, vehicles, winds or latencies)
+    M] over the scenarios of a schedule (``schedule_ids``: what ``schedules.checked_schedule_ids`` answered - disturbances, vehicles, winds, latencies or sensors)
     or the setpoints (``ref_ids`` of a ``ReferenceBank``), [n_actors] on a single ``Reference``."""
     from .tracking import reference_tracking_table
     sum_sq, steps = env.tracking_error()
@@ -520,8 +541,8 @@ class VectorModule:
 
             # --- the schedules: wrench (scheduled gusts, pokes, payloads: raptor_amd.disturbances), vehicle (payloads, battery sag,
             # slow motors: raptor_amd.vehicles), wind (air that moves and drags: raptor_amd.winds), delay (control latency:
-            # raptor_amd.delays).  One implementation; what is attached of a kind is kept as (bank, ids) under _<noun>. ---
-            _wrench = _vehicle = _wind = _delay = None
+            # raptor_amd.delays), sensor (observation latency: raptor_amd.sensors).  One implementation; what is attached of a kind is kept as (bank, ids) under _<noun>. ---
+            _wrench = _vehicle = _wind = _delay = _sensor = None
 
             def _set_schedule(self, kind, bank, ids):
                 if not isinstance(bank, _BANKS[kind]):
@@ -566,10 +587,19 @@ class VectorModule:
                 ``episode_step_limit`` holds its last row."""
                 self._set_schedule(schedules.DELAY, bank, ids)
 
+            def set_sensor_schedule(self, bank, ids=None):
+                """Attach ``bank`` (an ``l2f.SensorBank``): from now on every observation assembled for env i - ``vector.observe``
+                and every rollout - carries in columns 0..17 the reading taken d steps ago, d the row of its episode step count of
+                table ``ids[i]`` ([N] integers, free per env; None: table 0 for every env), the episode's first reading where the
+                episode is younger; the state and the env step are unchanged and a recording holds what the policy saw.
+                Attaching zeroes the env's readings.  A table shorter than ``episode_step_limit`` holds its last row."""
+                self._set_schedule(schedules.SENSOR, bank, ids)
+
             def clear_wrench_schedule(self): self._clear_schedule(schedules.WRENCH)
             def clear_vehicle_schedule(self): self._clear_schedule(schedules.VEHICLE)
             def clear_wind_schedule(self): self._clear_schedule(schedules.WIND)
             def clear_delay_schedule(self): self._clear_schedule(schedules.DELAY)
+            def clear_sensor_schedule(self): self._clear_schedule(schedules.SENSOR)
 
             @property
             def wrench_schedule(self):
@@ -590,6 +620,11 @@ class VectorModule:
             def delay_schedule(self):
                 """(bank, ids) of the attached schedule, or None."""
                 return self._schedule(schedules.DELAY)
+
+            @property
+            def sensor_schedule(self):
+                """(bank, ids) of the attached schedule, or None."""
+                return self._schedule(schedules.SENSOR)
 
             def tracking_error(self):
                 """-> (sum_sq [N] float32, steps [N] uint32): per env, the running sum of |p - p_ref|^2 over the steps it took in

@@ -202,7 +202,8 @@ class PolicyBank:
                       reference, ref_ids)
 
     def evaluate(self, vector, device, env, params, state, rng, n_steps, policy_ids=None, mode="fused", autoreset=True,
-                 reference=None, reference_ids=None, wrench_ids=None, vehicle_ids=None, wind_ids=None, delay_ids=None):
+                 reference=None, reference_ids=None, wrench_ids=None, vehicle_ids=None, wind_ids=None, delay_ids=None,
+                 sensor_ids=None):
         """The closed-loop evaluation of the whole bank: statistics and hidden state start afresh, one rollout of ``n_steps`` flies
         env i with policy ``policy_ids[i]`` (default: blocks dealt round-robin) at its native interval ->
         ``policy_episode_table`` of what it finished.  With ``reference`` the bank tracks that moving setpoint and the table gains
@@ -215,12 +216,15 @@ class PolicyBank:
         ``vehicle_ids`` likewise name the tables of the env's vehicle schedule (``env.set_vehicle_schedule(bank)``): [P, M] over the
         vehicle scenarios, and ``wind_ids`` those of its wind schedule (``env.set_wind_schedule(bank)``): [P, M] over the wind
         scenarios, and ``delay_ids`` those of its delay schedule (``env.set_delay_schedule(bank)``): [P, M] over the latency
-        scenarios.  At most one of ``wrench_ids``, ``vehicle_ids``, ``wind_ids`` and ``delay_ids``: two together are refused."""
+        scenarios, and ``sensor_ids`` those of its sensor schedule (``env.set_sensor_schedule(bank)``): [P, M] over the sensor
+        scenarios.  At most one of ``wrench_ids``, ``vehicle_ids``, ``wind_ids``, ``delay_ids`` and ``sensor_ids``: two together are
+        refused."""
         ids = block_policy_assignment(vector.N_ENVIRONMENTS, self.n_policies) if policy_ids is None else policy_ids
         from . import schedules
         from .l2f import _checked_reference, tracking_rmse
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
-        given = {schedules.WRENCH: wrench_ids, schedules.VEHICLE: vehicle_ids, schedules.WIND: wind_ids, schedules.DELAY: delay_ids}
+        given = {schedules.WRENCH: wrench_ids, schedules.VEHICLE: vehicle_ids, schedules.WIND: wind_ids, schedules.DELAY: delay_ids,
+                 schedules.SENSOR: sensor_ids}
         s_ids = schedules.checked_schedule_ids(env, given, ref_ids, vector.N_ENVIRONMENTS)
         if s_ids is not None:
             s_ids.attach(env)

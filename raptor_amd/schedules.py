@@ -1,6 +1,6 @@
-"""What the kinds of row tables share on the Python side: the wrench, vehicle, wind and delay schedules (``raptor_amd.disturbances``,
-``raptor_amd.vehicles``, ``raptor_amd.winds``, ``raptor_amd.delays`` build their tables; ``l2f.WrenchBank`` / ``VehicleBank`` /
-``WindBank`` / ``DelayBank`` hold them; ``env.set_*_schedule`` attaches them) and the moving setpoints of ``l2f.Reference`` / ``ReferenceBank``.  A kind is one ``Kind``
+"""What the kinds of row tables share on the Python side: the wrench, vehicle, wind, delay and sensor schedules (``raptor_amd.disturbances``,
+``raptor_amd.vehicles``, ``raptor_amd.winds``, ``raptor_amd.delays``, ``raptor_amd.sensors`` build their tables; ``l2f.WrenchBank`` / ``VehicleBank`` /
+``WindBank`` / ``DelayBank`` / ``SensorBank`` hold them; ``env.set_*_schedule`` attaches them) and the moving setpoints of ``l2f.Reference`` / ``ReferenceBank``.  A kind is one ``Kind``
 record; the checks of tables and ids, the banks and the env's attach / clear / property are written once and driven by it.  What a
 row means is each builder module's ``compose``."""
 from typing import Callable, NamedTuple, Optional
@@ -59,8 +59,12 @@ WIND = Kind("wind", 4, ", ".join(WIND_NAMES), WIND_NAMES, "raptor_amd.winds", _f
 DELAY = Kind("delay", 1, "delay in steps", None, "raptor_amd.delays", _finite, "latency",
              "delay_ids group the tracking error by latency scenario, wrench_ids by disturbance, vehicle_ids by vehicle scenario and "
              "wind_ids by wind scenario: give one of them")
+# (a sensor table likewise: raptor_amd.sensors)
+SENSOR = Kind("sensor", 1, "delay in steps", None, "raptor_amd.sensors", _finite, "sensor",
+              "sensor_ids group the tracking error by sensor scenario, wrench_ids by disturbance, vehicle_ids by vehicle scenario, "
+              "wind_ids by wind scenario and delay_ids by latency scenario: give one of them")
 REFERENCE = Kind("reference", 6, "target position, target velocity", None, "raptor_amd.tracking", _finite)
-KINDS = (WRENCH, VEHICLE, WIND, DELAY)       # the schedules, in the order the C layer walks them
+KINDS = (WRENCH, VEHICLE, WIND, DELAY, SENSOR)       # the schedules, in the order the C layer walks them
 
 
 def check_table(kind, table, entries=True):
@@ -124,7 +128,7 @@ class ScheduleIds(NamedTuple):
 
 
 def checked_schedule_ids(env, given, ref_ids, n_envs):
-    """What the ``wrench_ids`` / ``vehicle_ids`` / ``wind_ids`` / ``delay_ids`` of ``PolicyBank.evaluate`` / ``TeacherBank.closed_loop`` must be,
+    """What the ``wrench_ids`` / ``vehicle_ids`` / ``wind_ids`` / ``delay_ids`` / ``sensor_ids`` of ``PolicyBank.evaluate`` / ``TeacherBank.closed_loop`` must be,
     before any library call.  ``given``: ``{kind: ids or None}`` of the kinds the caller takes, in the order of ``KINDS`` ->
     ``ScheduleIds`` of the one that was given, or None (none was); ValueError otherwise."""
     found = None

@@ -169,7 +169,7 @@ class TeacherBank:
                       reference, ref_ids)
 
     def closed_loop(self, vector, device, env, params, state, rng, n_steps, teacher_ids, mode="fused", autoreset=True,
-                    reference=None, reference_ids=None, wrench_ids=None, vehicle_ids=None, delay_ids=None):
+                    reference=None, reference_ids=None, wrench_ids=None, vehicle_ids=None, delay_ids=None, sensor_ids=None):
         """The closed-loop check of the whole bank: the env's statistics start afresh, one ``fly`` of ``n_steps`` ->
         ``teacher_episode_table`` of what it finished.  With ``reference`` the table gains ``tracking_rmse`` [K]
         (``policy_bank.policy_tracking_table`` of ``env.tracking_error()``, grouped by teacher); with an ``l2f.ReferenceBank`` and
@@ -178,12 +178,13 @@ class TeacherBank:
         ``wrench_ids`` ([N] integers; the env carries a wrench schedule): env i flies disturbance scenario ``wrench_ids[i]`` of the
         attached bank and, on an ``l2f.Reference``, ``tracking_rmse`` is [K, M] over the scenarios (``mode="chained"``: the fused
         teacher kernel does not fly a schedule).  ``vehicle_ids`` likewise name the tables of the env's vehicle schedule and
-        ``delay_ids`` those of its delay schedule; giving two of the three is refused."""
+        ``delay_ids`` those of its delay schedule, ``sensor_ids`` those of its sensor schedule; giving two of the four is refused."""
         from . import schedules
         from .l2f import _checked_reference, tracking_rmse
         ids = check_teacher_ids(teacher_ids, vector.N_ENVIRONMENTS)
         ref_ids = _checked_reference(reference, reference_ids, vector.N_ENVIRONMENTS)       # before the statistics are reset
-        given = {schedules.WRENCH: wrench_ids, schedules.VEHICLE: vehicle_ids, schedules.DELAY: delay_ids}
+        given = {schedules.WRENCH: wrench_ids, schedules.VEHICLE: vehicle_ids, schedules.DELAY: delay_ids,
+                 schedules.SENSOR: sensor_ids}
         s_ids = schedules.checked_schedule_ids(env, given, ref_ids, vector.N_ENVIRONMENTS)
         if s_ids is not None:
             s_ids.attach(env)
