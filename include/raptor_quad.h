@@ -94,7 +94,9 @@ extern "C" {
                               (still 5: rq_vehicle_bank_{create,destroy} and rq_env_{set,get}_vehicle_schedule added, no struct changed)
                               (still 5: rq_wind_bank_{create,destroy} and rq_env_{set,get}_wind_schedule added, no struct changed)
                               (still 5: rq_delay_bank_{create,destroy} and rq_env_{set,clear,get}_delay_schedule added, no struct changed)
-                              (still 5: rq_sensor_bank_{create,destroy} and rq_env_{set,clear,get}_sensor_schedule added, no struct changed) */
+                              (still 5: rq_sensor_bank_{create,destroy} and rq_env_{set,clear,get}_sensor_schedule added, no struct changed)
+                              (still 5: rq_optimizer_{get,set}_state, rq_optimizer_apply and rq_bank_optimizer_{get,set}_state added, no
+                              struct changed) */
 
 #if defined(__GNUC__)
 #define RQ_API __attribute__((visibility("default")))
@@ -746,7 +748,25 @@ RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* policy, co
  * BEFORE each update.  With RQ_DST_DEVICE_ASYNC the call returns after enqueueing; whatever is enqueued on the same stream
  * afterwards - a rollout, a relabel - runs the updated policy.  The host's copy of the weights is refreshed (one 8 KB copy) by the
  * first call that needs it: rq_policy_get_weights, rq_policy_set_precision to a 16-bit precision, rq_policy_set_standardize,
- * rq_policy_selftest.  The policy's hidden state is kept.  Refused beyond the above: an optimizer made for another policy. */
+ * rq_policy_selftest.  The policy's hidden state is kept.  Refused beyond the above: an optimizer made for another policy.
+ * eps = 0 is accepted: an element whose v' is 0 (a gradient that has been exactly 0 since creation, m = v = 0) then updates by
+ * 0 / (sqrt(0) + 0) = NaN, as torch.optim.Adam's does; with eps > 0 that element's update is exactly 0.
+ * The state, for checkpointing a run and for driving the update directly:
+ * rq_optimizer_get_state: m [2084], v [2084], step [1] (updates made so far) and beta_powers [2] = (beta1^step, beta2^step) as the
+ * device carries them - running products, not recomputed powers - into host arrays, behind everything enqueued (as
+ * rq_policy_get_weights).  rq_optimizer_set_state: the reverse from host arrays, bits copied, synchronous (it waits for the updates
+ * enqueued).  The hyper-parameters are not part of the state: they are the rq_adam_config of rq_optimizer_create (and
+ * rq_optimizer_set_lr).  A run restored - rq_policy_set_weights or a policy created from rq_policy_get_weights, an optimizer created
+ * with the same config, rq_optimizer_set_state with what rq_optimizer_get_state gave - continues bit for bit: weights, moments,
+ * step, powers and losses are those of the run that was never interrupted; that is why the two powers are taken, not step alone.
+ * rq_optimizer_apply: ONE Adam update of the optimizer's policy from the caller's gradient grad [2084] (checkpoint order) - the
+ * update of rq_trajectory_distill without its loss: rq_trajectory_policy_loss_grad followed by rq_optimizer_apply of that gradient
+ * is, bit for bit, one rq_trajectory_distill update.  Both fp32 operand images are rebuilt and the host's copy of the weights, the
+ * 16-bit images and a resident executor are made stale exactly as by rq_trajectory_distill.  memory: RQ_DST_HOST - grad is a host
+ * array, the call returns when the update is done -, RQ_DST_DEVICE - device memory of the policy's device - or RQ_DST_DEVICE_ASYNC -
+ * the same, only enqueued.  Refused before anything is enqueued, by all three: a null argument; an optimizer whose policy has been
+ * destroyed; by rq_optimizer_apply also a `memory` outside the three, a gradient that is not where `memory` says, a policy that is
+ * not the fp32 policy or has a Standardize stage. */
 typedef struct rq_optimizer rq_optimizer;
 typedef struct rq_adam_config { double lr, beta1, beta2, eps, weight_decay; } rq_adam_config;
 RQ_API int rq_trajectory_policy_loss_grad(rq_trajectory* t, rq_policy* policy, const float* target, uint32_t ld_target,
@@ -754,6 +774,9 @@ RQ_API int rq_trajectory_policy_loss_grad(rq_trajectory* t, rq_policy* policy, c
 RQ_API int rq_optimizer_create(rq_policy* policy, const rq_adam_config* config, rq_optimizer** out);
 RQ_API int rq_optimizer_destroy(rq_optimizer* optimizer);
 RQ_API int rq_optimizer_set_lr(rq_optimizer* optimizer, double lr);
+RQ_API int rq_optimizer_get_state(rq_optimizer* optimizer, float* m, float* v, uint32_t* step, double* beta_powers /* [2] */);
+RQ_API int rq_optimizer_set_state(rq_optimizer* optimizer, const float* m, const float* v, uint32_t step, const double* beta_powers);
+RQ_API int rq_optimizer_apply(rq_optimizer* optimizer, const float* grad /* [2084] */, int memory);
 RQ_API int rq_trajectory_distill(rq_trajectory* t, rq_policy* policy, rq_optimizer* optimizer, const float* target,
                                  uint32_t ld_target, int start, uint32_t n_updates, float* losses, int memory);
 /* the policy's current parameters, 2 084 floats in the checkpoint order (after device-side updates: fetched from the device) */
@@ -971,6 +994,9 @@ RQ_API int rq_rollout_policies_track_refs(rq_device* dev, rq_env* env, const rq_
  * rq_trajectory_policies_loss_grad: loss [P], grad_weights [P][2084]; a policy that owns no block: loss NaN, its gradient row is
  * left as it was.  rq_bank_optimizer: Adam's state per policy, [P][2084] moments, and the hyper-parameters per policy: config
  * [n_cfg], n_cfg = 1 (one for all) or P; rq_bank_optimizer_set_lr: lr [n], n = 1 or P, in stream order.
+ * rq_bank_optimizer_get_state / rq_bank_optimizer_set_state: rq_optimizer_get_state / _set_state for every policy at once - m, v
+ * [P][2084], step [P], beta_powers [P][2], host arrays; a restored bank run continues bit for bit too.  Refused: a null argument, an
+ * optimizer whose bank has been destroyed.  (There is no bank apply: the bank's update kernel is the single one's text.)
  * rq_trajectory_policies_distill: n_updates x (forward, loss-seeded backward, per-policy reduction, Adam and both operand images of
  * every policy), enqueued back to back; losses [n_updates][P]: the loss before each update.  A policy that owns no block in this
  * assignment is skipped whole - weights, moments, step count, images untouched - and its losses are NaN.  The updated weights are
@@ -987,6 +1013,9 @@ RQ_API int rq_trajectory_policies_loss_grad(rq_trajectory* t, rq_policy_bank* ba
 RQ_API int rq_bank_optimizer_create(rq_policy_bank* bank, const rq_adam_config* config, uint32_t n_cfg, rq_bank_optimizer** out);
 RQ_API int rq_bank_optimizer_destroy(rq_bank_optimizer* optimizer);
 RQ_API int rq_bank_optimizer_set_lr(rq_bank_optimizer* optimizer, const double* lr, uint32_t n);
+RQ_API int rq_bank_optimizer_get_state(rq_bank_optimizer* optimizer, float* m, float* v, uint32_t* step, double* beta_powers);
+RQ_API int rq_bank_optimizer_set_state(rq_bank_optimizer* optimizer, const float* m, const float* v, const uint32_t* step,
+                                       const double* beta_powers);
 RQ_API int rq_trajectory_policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* optimizer,
                                           const uint32_t* policy_id, const float* target, uint32_t ld_target, int start,
                                           uint32_t n_updates, float* losses, int memory);

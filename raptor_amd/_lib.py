@@ -182,6 +182,9 @@ _SIGNATURES = {
     "rq_optimizer_create": [_vp, C.POINTER(AdamConfig), C.POINTER(_vp)],
     "rq_optimizer_destroy": [_vp],
     "rq_optimizer_set_lr": [_vp, C.c_double],
+    "rq_optimizer_get_state": [_vp, _fp, _fp, _vp, _vp],
+    "rq_optimizer_set_state": [_vp, _fp, _fp, C.c_uint32, _vp],
+    "rq_optimizer_apply": [_vp, _fp, C.c_int],
     "rq_trajectory_distill": [_vp, _vp, _vp, _fp, C.c_uint32, C.c_int, C.c_uint32, _fp, C.c_int],
     "rq_trajectory_policy_loss_grad_weighted": [_vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, C.c_int, _fp, _fp, C.c_int],
     "rq_trajectory_distill_weighted": [_vp, _vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, _fp, C.c_int],
@@ -219,6 +222,8 @@ _SIGNATURES = {
     "rq_bank_optimizer_create": [_vp, C.POINTER(AdamConfig), C.c_uint32, C.POINTER(_vp)],
     "rq_bank_optimizer_destroy": [_vp],
     "rq_bank_optimizer_set_lr": [_vp, _vp, C.c_uint32],
+    "rq_bank_optimizer_get_state": [_vp, _fp, _fp, _vp, _vp],
+    "rq_bank_optimizer_set_state": [_vp, _fp, _fp, _vp, _vp],
     "rq_trajectory_policies_distill": [_vp, _vp, _vp, _vp, _fp, C.c_uint32, C.c_int, C.c_uint32, _fp, C.c_int],
     "rq_trajectory_policies_loss_grad_weighted": [_vp, _vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, C.c_int, _fp, _fp, C.c_int],
     "rq_trajectory_policies_distill_weighted": [_vp, _vp, _vp, _vp, _fp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, _fp,

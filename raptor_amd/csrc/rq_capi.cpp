@@ -42,6 +42,16 @@ bool policy_registry(const void* pol, int op) {
     return live.count(pol) != 0;
 }
 
+// live rq_policy_bank objects, likewise: a bank optimizer's state calls refuse an optimizer whose bank is gone
+bool policy_bank_registry(const void* bank, int op) {
+    static std::mutex m;
+    static std::unordered_set<const void*> live;
+    std::lock_guard<std::mutex> lock(m);
+    if (op > 0) { live.insert(bank); return true; }
+    if (op < 0) { live.erase(bank); return false; }
+    return live.count(bank) != 0;
+}
+
 constexpr size_t kStagingFloorFloats = (1u << 20) / sizeof(float);     // the two pinned staging buffers start at 1 MiB
 
 // device SoA [dim][ld] -> host row-major [n][dim]

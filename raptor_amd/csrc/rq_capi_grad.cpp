@@ -3,6 +3,8 @@
 // through time along the recorded episode structure (rq_trajectory_policy_backward); and the whole distillation update on the device:
 // masked-MSE loss and gradient (rq_trajectory_policy_loss_grad), Adam and the operand images (rq_trajectory_distill); and that update
 // for every policy of a policy bank at once (rq_trajectory_policies_loss_grad, rq_bank_optimizer_*, rq_trajectory_policies_distill).
+// Adam's state as host arrays and one update from the caller's gradient - what checkpoints a run and what tests the update kernel on
+// arbitrary inputs (rq_optimizer_get_state / _set_state / _apply, rq_bank_optimizer_get_state / _set_state).
 // The four loss calls have a *_weighted sibling each - a weight per env, or per env and step, in the loss - that shares their body.
 // rq_trajectory_policy_error_table / rq_trajectory_policies_error_table: the forward alone against the loss calls' target - the
 // squared imitation error per env and bucket of episode age; the trajectory's saved state is not theirs and stays as it was.
@@ -338,6 +340,72 @@ int adam_alloc(const char* who, AdamBuffers* o, rq_device* dev, const rq_adam_co
     return RQ_OK;
 }
 
+// k_adam_repack has written w_dev and both fp32 images (rq_trajectory_distill, rq_optimizer_apply): everything derived from the
+// weights is behind - the host's mirror, the 16-bit images, a speculation or a saved state stamped with the old versions
+void policy_updated_on_device(rq_policy* pol) {
+    pol->version = fresh_version();
+    pol->weight_version = fresh_version();
+    pol->grad_image_version = pol->weight_version;
+    pol->mirror_stale = pol->images16_stale = true;
+}
+
+// Adam's state of `slots` policies to the host, behind everything enqueued: m, v [slots][2084], step [slots], beta_powers [slots][2]
+// (beta1^t, beta2^t as the kernel carries them).  Nothing of the caller's is written before every copy has arrived.
+int adam_get_state(const char* who, AdamBuffers* o, uint32_t slots, float* m, float* v, uint32_t* step, double* beta_powers) {
+    const size_t floats = (size_t)slots * RQ_POLICY_NUM_WEIGHTS;
+    std::vector<rq::AdamState> st;
+    std::vector<float> mv;
+    try { st.resize(slots); mv.resize(2 * floats); } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed");
+    }
+    hipStream_t s = o->dev->stream;
+    RQ_HIP_AS(who, hipMemcpyAsync(mv.data(), o->m, floats * sizeof(float), hipMemcpyDeviceToHost, s));
+    RQ_HIP_AS(who, hipMemcpyAsync(mv.data() + floats, o->v, floats * sizeof(float), hipMemcpyDeviceToHost, s));
+    RQ_HIP_AS(who, hipMemcpyAsync(st.data(), o->state, (size_t)slots * sizeof(rq::AdamState), hipMemcpyDeviceToHost, s));
+    RQ_HIP_AS(who, hipStreamSynchronize(s));
+    std::memcpy(m, mv.data(), floats * sizeof(float));
+    std::memcpy(v, mv.data() + floats, floats * sizeof(float));
+    for (uint32_t p = 0; p < slots; ++p) {
+        step[p] = st[p].step;
+        beta_powers[2 * p] = st[p].beta1_t; beta_powers[2 * p + 1] = st[p].beta2_t;
+    }
+    return RQ_OK;
+}
+
+// The reverse, synchronous: the bits of m, v, step and the two powers as given; the hyper-parameters stay the optimizer's own
+// (they are read back from the device first: a rq_*_set_lr enqueued before holds).
+int adam_set_state(const char* who, AdamBuffers* o, uint32_t slots, const float* m, const float* v, const uint32_t* step,
+                   const double* beta_powers) {
+    const size_t floats = (size_t)slots * RQ_POLICY_NUM_WEIGHTS;
+    std::vector<rq::AdamState> st;
+    try { st.resize(slots); } catch (const std::bad_alloc&) {
+        return fail(RQ_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed");
+    }
+    RQ_HIP_AS(who, hipStreamSynchronize(o->dev->stream));         // an update in flight reads and writes the state
+    RQ_HIP_AS(who, hipMemcpy(st.data(), o->state, (size_t)slots * sizeof(rq::AdamState), hipMemcpyDeviceToHost));
+    for (uint32_t p = 0; p < slots; ++p) {
+        st[p].step = step[p];
+        st[p].beta1_t = beta_powers[2 * p]; st[p].beta2_t = beta_powers[2 * p + 1];
+    }
+    RQ_HIP_AS(who, hipMemcpy(o->m, m, floats * sizeof(float), hipMemcpyHostToDevice));
+    RQ_HIP_AS(who, hipMemcpy(o->v, v, floats * sizeof(float), hipMemcpyHostToDevice));
+    RQ_HIP_AS(who, hipMemcpy(o->state, st.data(), (size_t)slots * sizeof(rq::AdamState), hipMemcpyHostToDevice));
+    return RQ_OK;
+}
+
+// what the single optimizer's state calls and rq_optimizer_apply refuse alike: objects die in any order
+int optimizer_check_policy(const rq_optimizer* opt, const char* what) {
+    RQ_REFUSE(what, policy_registry(opt->policy, 0) && device_registry(opt->dev, 0), RQ_ERR_INVALID_ARGUMENT,
+              "the optimizer's policy was destroyed");
+    return RQ_OK;
+}
+
+int bank_optimizer_check_bank(const rq_bank_optimizer* opt, const char* what) {
+    RQ_REFUSE(what, policy_bank_registry(opt->bank, 0) && opt->bank->uid == opt->bank_uid && device_registry(opt->dev, 0),
+              RQ_ERR_INVALID_ARGUMENT, "the optimizer's bank was destroyed");
+    return RQ_OK;
+}
+
 template <typename Optimizer>
 int adam_destroy(Optimizer* opt) {
     if (!opt) return RQ_OK;
@@ -471,6 +539,46 @@ RQ_API int rq_optimizer_set_lr(rq_optimizer* opt, double lr) {
     return RQ_OK;
 }
 
+RQ_API int rq_optimizer_get_state(rq_optimizer* opt, float* m, float* v, uint32_t* step, double* beta_powers) {
+    RQ_REQUIRE(opt && m && v && step && beta_powers, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = optimizer_check_policy(opt, "rq_optimizer_get_state"); if (rc) return rc;
+    DeviceScope on_device(opt->ordinal); rc = on_device.rc; if (rc) return rc;
+    return adam_get_state("rq_optimizer_get_state", opt, 1, m, v, step, beta_powers);
+}
+
+RQ_API int rq_optimizer_set_state(rq_optimizer* opt, const float* m, const float* v, uint32_t step, const double* beta_powers) {
+    RQ_REQUIRE(opt && m && v && beta_powers, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = optimizer_check_policy(opt, "rq_optimizer_set_state"); if (rc) return rc;
+    DeviceScope on_device(opt->ordinal); rc = on_device.rc; if (rc) return rc;
+    return adam_set_state("rq_optimizer_set_state", opt, 1, m, v, &step, beta_powers);
+}
+
+RQ_API int rq_optimizer_apply(rq_optimizer* opt, const float* grad, int memory) {
+    const char* what = "rq_optimizer_apply";
+    RQ_REQUIRE(opt && grad, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_memory(memory); if (rc) return rc;
+    rc = optimizer_check_policy(opt, what); if (rc) return rc;
+    rq_policy* pol = opt->policy;
+    rq_device* dev = opt->dev;
+    // the kernel rebuilds the fp32 images from the raw weights: as rq_trajectory_distill, the fp32 policy without a folded stage only
+    RQ_REQUIRE(pol->precision == RQ_POLICY_FP32, RQ_ERR_INVALID_ARGUMENT,
+               std::string(what) + ": defined for the fp32 policy only (set_precision(RQ_POLICY_FP32)), not bf16 or f16x2");
+    RQ_REQUIRE(!pol->standardize, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": the Standardize stage has no gradient here (disable it)");
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    rc = check_device_array(mem, grad, what, "the gradient"); if (rc) return rc;
+    rc = check_host_array(mem, grad, what, "the gradient"); if (rc) return rc;
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;          // (retires a resident executor: it holds the old operands)
+    rc = ensure_grad_image(pol); if (rc) return rc;                            // the kernel writes both images: the second must exist
+    const float* d_grad = nullptr;
+    RQ_HIP(mem.in(grad, (size_t)RQ_POLICY_NUM_WEIGHTS, opt->grad.get(), &d_grad));
+    const hipError_t e = rq::launch_adam_repack(dev->stream, d_grad, pol->w_dev, opt->m, opt->v, opt->state, opt->table, pol->w_packed,
+                                                pol->w_packed_grad);
+    if (e == hipSuccess) policy_updated_on_device(pol);
+    RQ_HIP(e);
+    RQ_HIP(mem.finish());
+    return RQ_OK;
+}
+
 static int policy_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer* opt, const float* target, uint32_t ld_target,
                           const LossWeight& wt, int start, uint32_t n_updates, float* losses, int memory, const char* what) {
     RQ_REQUIRE(t && pol && opt && losses, RQ_ERR_INVALID_ARGUMENT, "null argument");
@@ -493,12 +601,7 @@ static int policy_distill(rq_trajectory* t, rq_policy* pol, rq_optimizer* opt, c
         if (e == hipSuccess) e = rq::launch_adam_repack(dev->stream, opt->grad, pol->w_dev, opt->m, opt->v, opt->state, opt->table,
                                                         pol->w_packed, pol->w_packed_grad);
     }
-    if (done_updates > 0) {             // the weights on the device are new (even if a later launch failed): everything derived is behind
-        pol->version = fresh_version();
-        pol->weight_version = fresh_version();
-        pol->grad_image_version = pol->weight_version;
-        pol->mirror_stale = pol->images16_stale = true;
-    }
+    if (done_updates > 0) policy_updated_on_device(pol);      // (even if a later launch failed)
     RQ_HIP(e);
     RQ_HIP(mem.finish());
     return RQ_OK;
@@ -589,6 +692,21 @@ RQ_API int rq_bank_optimizer_set_lr(rq_bank_optimizer* opt, const double* lr, ui
     DeviceScope on_device(opt->dev); int rc = on_device.rc; if (rc) return rc;
     RQ_HIP(rq::launch_adam_set_lr_bank(opt->dev->stream, opt->state, opt->n_policies, lr, n));
     return RQ_OK;
+}
+
+RQ_API int rq_bank_optimizer_get_state(rq_bank_optimizer* opt, float* m, float* v, uint32_t* step, double* beta_powers) {
+    RQ_REQUIRE(opt && m && v && step && beta_powers, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = bank_optimizer_check_bank(opt, "rq_bank_optimizer_get_state"); if (rc) return rc;
+    DeviceScope on_device(opt->ordinal); rc = on_device.rc; if (rc) return rc;
+    return adam_get_state("rq_bank_optimizer_get_state", opt, opt->n_policies, m, v, step, beta_powers);
+}
+
+RQ_API int rq_bank_optimizer_set_state(rq_bank_optimizer* opt, const float* m, const float* v, const uint32_t* step,
+                                       const double* beta_powers) {
+    RQ_REQUIRE(opt && m && v && step && beta_powers, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = bank_optimizer_check_bank(opt, "rq_bank_optimizer_set_state"); if (rc) return rc;
+    DeviceScope on_device(opt->ordinal); rc = on_device.rc; if (rc) return rc;
+    return adam_set_state("rq_bank_optimizer_set_state", opt, opt->n_policies, m, v, step, beta_powers);
 }
 
 static int policies_distill(rq_trajectory* t, rq_policy_bank* bank, rq_bank_optimizer* opt, const uint32_t* policy_id,

@@ -177,6 +177,7 @@ RQ_API int rq_policy_bank_create(rq_device* dev, const float* weights, uint32_t 
         delete b;
         return fail(RQ_ERR_OUT_OF_MEMORY, "rq_policy_bank_create: device allocation or upload failed");
     }
+    policy_bank_registry(b, +1);
     *out = b;
     return RQ_OK;
 }
@@ -184,6 +185,7 @@ RQ_API int rq_policy_bank_create(rq_device* dev, const float* weights, uint32_t 
 RQ_API int rq_policy_bank_destroy(rq_policy_bank* bank) {
     if (!bank) return RQ_OK;
     DeviceScope on_device(bank->ordinal);      // (hipFree synchronises the device: no launch still reads the images)
+    policy_bank_registry(bank, -1);            // an optimizer may still name this object: it is checked against the registry
     delete bank;
     return RQ_OK;
 }

@@ -465,10 +465,11 @@ constexpr uint32_t kGpuLayoutMinEnvs = 1024;
 namespace rqh {
 
 // ---- rq_capi.cpp ----
-// live rq_device / rq_policy objects (op: +1 register, -1 unregister, 0 query): objects die in any order, a parent or a remembered
+// live rq_device / rq_policy / rq_policy_bank objects (op: +1 register, -1 unregister, 0 query): objects die in any order, a parent or a remembered
 // policy is followed only while it is in here
 bool device_registry(const void* dev, int op);
 bool policy_registry(const void* pol, int op);
+bool policy_bank_registry(const void* bank, int op);
 int soa_to_host(rq_device* dev, const float* d_soa, uint32_t n, uint32_t ld, uint32_t dim, float* host);
 int host_to_soa(rq_device* dev, const float* host, uint32_t n, uint32_t stride, uint32_t ld, uint32_t dim, float* d_soa);
 int check_env_objects(const rq_device* dev, const rq_env* env, const rq_params* params, const rq_state* state);

@@ -236,8 +236,8 @@ class Distiller:
         self._target_in_flight = None      # the target an enqueued-only step may still be reading (a contiguous copy, perhaps)
         self._weight_in_flight = None      # and the weight (an uploaded copy, perhaps)
 
-    def _handle(self, traj):
-        pol = self.policy._handle(traj._env._device)
+    def _handle(self, traj=None):
+        pol = self.policy._handle(None if traj is None else traj._env._device)
         if self._h is None:
             import weakref
             h = C.c_void_p()
@@ -251,6 +251,44 @@ class Distiller:
         self._cfg.lr = float(lr)
         if self._h is not None:
             _lib.call("rq_optimizer_set_lr", self._h, float(lr))
+
+    def state(self):
+        """Adam's state behind everything enqueued (rq_optimizer_get_state) -> a dict of NumPy arrays: ``m``, ``v`` [2084] float32,
+        ``step`` (uint32 scalar, the updates made) and ``beta_powers`` [2] float64 - (beta1^step, beta2^step) as the device carries
+        them.  Together with ``policy.weights`` that is a checkpoint of the run; the hyper-parameters are the constructor's."""
+        _, opt = self._handle()
+        m, v = np.empty(_lib.POLICY_NUM_WEIGHTS, np.float32), np.empty(_lib.POLICY_NUM_WEIGHTS, np.float32)
+        step, powers = np.zeros(1, np.uint32), np.empty(2, np.float64)
+        _lib.call("rq_optimizer_get_state", opt, _lib.fptr(m), _lib.fptr(v), step.ctypes.data, powers.ctypes.data)
+        return {"m": m, "v": v, "step": step[0], "beta_powers": powers}
+
+    def set_state(self, m, v, step, beta_powers):
+        """The reverse (rq_optimizer_set_state): ``Distiller(policy, same hyper-parameters).set_state(**other.state())`` on a policy
+        holding ``other``'s weights continues ``other``'s run bit for bit."""
+        m, v, powers = _state_arrays(m, v, beta_powers, (_lib.POLICY_NUM_WEIGHTS,), (2,))
+        _, opt = self._handle()
+        _lib.call("rq_optimizer_set_state", opt, _lib.fptr(m), _lib.fptr(v), int(step), powers.ctypes.data)
+
+    def apply(self, grad, wait=True):
+        """One Adam update of the policy from ``grad`` [2084] float32 in the checkpoint order (rq_optimizer_apply): a NumPy array, or
+        a tensor on the policy's device (``wait=False``: enqueued only).  ``loss_and_grad`` followed by ``apply`` of its gradient is
+        one ``step``; a gradient from torch (``trajectory_actions`` and any loss) takes the same update without leaving the device."""
+        if hasattr(grad, "data_ptr"):
+            import torch
+            g = grad.detach().contiguous()
+            if g.dtype != torch.float32 or tuple(g.shape) != (_lib.POLICY_NUM_WEIGHTS,) or not g.is_cuda:
+                raise ValueError(f"grad must be a float32 device tensor of {_lib.POLICY_NUM_WEIGHTS} values (or a NumPy array)")
+            _, opt = self._handle()
+            torch.cuda.current_stream(g.device).synchronize()     # the engine runs on its own stream
+            _lib.call("rq_optimizer_apply", opt, _device_ptr(g), 1 if wait else 2)
+            self._target_in_flight = g                            # an enqueued-only update may still be reading it
+        else:
+            g = np.ascontiguousarray(grad, np.float32)
+            if g.shape != (_lib.POLICY_NUM_WEIGHTS,):
+                raise ValueError(f"grad must hold {_lib.POLICY_NUM_WEIGHTS} values")
+            _, opt = self._handle()
+            _lib.call("rq_optimizer_apply", opt, _lib.fptr(g), 0)
+        self.policy._weights_on_device = True
 
     @staticmethod
     def _target(traj, target):
@@ -318,6 +356,17 @@ class Distiller:
         self._target_in_flight, self._weight_in_flight = keep
         self.policy._weights_on_device = True
         return losses
+
+
+def _state_arrays(m, v, beta_powers, shape, powers_shape):
+    """the refusals Python makes itself for an optimizer state -> contiguous (m, v float32 ``shape``, powers float64)"""
+    m, v = np.ascontiguousarray(m), np.ascontiguousarray(v)
+    if m.dtype != np.float32 or v.dtype != np.float32 or m.shape != shape or v.shape != shape:
+        raise ValueError(f"m and v must be float32 {list(shape)} (their bits are copied)")
+    powers = np.ascontiguousarray(beta_powers, np.float64)
+    if powers.shape != powers_shape:
+        raise ValueError(f"beta_powers must be {list(powers_shape)}")
+    return m, v, powers
 
 
 def _loss_call(traj, target, weight, start, handles, host_ok):
@@ -522,6 +571,24 @@ class BankDistiller:
             c.lr = float(r)
         if self._h is not None:
             _lib.call("rq_bank_optimizer_set_lr", self._h, rates.ctypes.data, rates.size)
+
+    def state(self):
+        """Every policy's Adam state behind everything enqueued (rq_bank_optimizer_get_state) -> a dict of NumPy arrays: ``m``,
+        ``v`` [P, 2084] float32, ``step`` [P] uint32, ``beta_powers`` [P, 2] float64.  As ``Distiller.state``."""
+        P, opt = int(self.bank.n_policies), self._handle()
+        m, v = np.empty((P, _lib.POLICY_NUM_WEIGHTS), np.float32), np.empty((P, _lib.POLICY_NUM_WEIGHTS), np.float32)
+        step, powers = np.zeros(P, np.uint32), np.empty((P, 2), np.float64)
+        _lib.call("rq_bank_optimizer_get_state", opt, _lib.fptr(m), _lib.fptr(v), step.ctypes.data, powers.ctypes.data)
+        return {"m": m, "v": v, "step": step, "beta_powers": powers}
+
+    def set_state(self, m, v, step, beta_powers):
+        """The reverse (rq_bank_optimizer_set_state); a restored bank run continues bit for bit."""
+        P = int(self.bank.n_policies)
+        m, v, powers = _state_arrays(m, v, beta_powers, (P, _lib.POLICY_NUM_WEIGHTS), (P, 2))
+        step = np.ascontiguousarray(step, np.uint32)
+        if step.shape != (P,):
+            raise ValueError(f"step must hold one count per policy ({P})")
+        _lib.call("rq_bank_optimizer_set_state", self._handle(), _lib.fptr(m), _lib.fptr(v), step.ctypes.data, powers.ctypes.data)
 
     def _check(self, traj, policy_ids, start, updates=1):
         """the refusals Python makes itself, before any library call -> (ids, updates)"""

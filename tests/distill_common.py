@@ -104,6 +104,28 @@ class Opt:
         _lib().call("rq_optimizer_destroy", self.h)
 
 
+def opt_state(opt, slots=None, name="rq_optimizer_get_state"):
+    """-> (m, v, step, powers) of an Opt; ``slots``: a bank optimizer's P ([P, 2084], [P], [P, 2])"""
+    L = _lib()
+    shape = (2084,) if slots is None else (slots, 2084)
+    m, v = np.full(shape, np.nan, np.float32), np.full(shape, np.nan, np.float32)
+    step, powers = np.zeros(slots or 1, np.uint32), np.full((slots or 1, 2), np.nan, np.float64)
+    L.call(name, opt.h, L.fptr(m), L.fptr(v), step.ctypes.data, powers.ctypes.data)
+    return (m, v, int(step[0]), powers[0]) if slots is None else (m, v, step, powers)
+
+
+def opt_set_state(opt, m, v, step, powers):
+    L = _lib()
+    m, v, powers = np.ascontiguousarray(m, np.float32), np.ascontiguousarray(v, np.float32), np.ascontiguousarray(powers, np.float64)
+    L.call("rq_optimizer_set_state", opt.h, L.fptr(m), L.fptr(v), int(step), powers.ctypes.data)
+
+
+def opt_apply(opt, grad):
+    L = _lib()
+    g = np.ascontiguousarray(grad, np.float32)
+    L.call("rq_optimizer_apply", opt.h, L.fptr(g), HOST)
+
+
 def distill(traj, pol, opt, n_updates, target=None, start=INITIAL):
     L = _lib()
     losses = np.empty(n_updates, np.float32)

@@ -94,11 +94,32 @@ def test_step_and_loss_and_grad_refuse_before_the_library_is_touched():
     assert d._h is None                         # no optimizer was created on the way
 
 
+def test_the_optimizer_state_calls_refuse_before_the_library_is_touched():
+    from raptor_amd.training import BankDistiller, Distiller
+    bank, _ = _stubs()
+    d, b = Distiller(_Untouchable()), BankDistiller(bank)
+    m, powers = np.zeros(2084, np.float32), np.ones(2)
+    for bad in (dict(m=m[:-1], v=m, step=0, beta_powers=powers), dict(m=m.astype(np.float64), v=m, step=0, beta_powers=powers),
+                dict(m=m, v=m, step=0, beta_powers=np.ones(3))):
+        with pytest.raises(ValueError, match="float32|beta_powers"):
+            d.set_state(**bad)
+    with pytest.raises(ValueError, match="2084 values"):
+        d.apply(m[:-1])
+    M, steps, pw = np.zeros((P, 2084), np.float32), np.zeros(P, np.uint32), np.ones((P, 2))
+    for bad in (dict(m=M[:2], v=M, step=steps, beta_powers=pw), dict(m=M, v=M, step=steps[:2], beta_powers=pw),
+                dict(m=M, v=M, step=steps, beta_powers=pw[:, :1])):
+        with pytest.raises(ValueError, match="float32|beta_powers|one count per policy"):
+            b.set_state(**bad)
+    assert d._h is None and b._h is None        # no optimizer was created on the way
+
+
 def test_the_header_declares_every_bank_learner_call_bound():
     from raptor_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "raptor_quad.h")).read()
     new = ["rq_policy_bank_get_weights", "rq_trajectory_policies_loss_grad", "rq_bank_optimizer_create", "rq_bank_optimizer_destroy",
-           "rq_bank_optimizer_set_lr", "rq_trajectory_policies_distill"]
+           "rq_bank_optimizer_set_lr", "rq_trajectory_policies_distill",
+           "rq_optimizer_get_state", "rq_optimizer_set_state", "rq_optimizer_apply", "rq_bank_optimizer_get_state",
+           "rq_bank_optimizer_set_state"]
     for name in new:
         assert name in _lib._SIGNATURES, name
         m = re.search(r"RQ_API int %s\(([^;]*)\);" % name, hdr, re.S)

@@ -16,7 +16,7 @@ import pytest
 import distill_reference as D
 import policy_grad_reference as R
 from distill_common import (DEVICE, HOST, INITIAL, Opt, _adam, _ld, _lib, _perturbed, _record, _targets, distill, forward, get_weights,
-                            loss_grad, same)
+                            loss_grad, opt_state, same)
 from gpu_common import World
 from rollout_common import ids_of
 
@@ -250,12 +250,19 @@ def test_a_policy_without_a_block_is_left_alone(case):
     cfg = CFG[1]
     bank = PolicyBank(case.device, case.W)                           # P = 4, the ids name 0 .. 2 only
     bopt = BankOpt(bank, cfg)
+    state = lambda: opt_state(bopt, slots=4, name="rq_bank_optimizer_get_state")
     loss, g = bank_loss_grad(case.traj, bank, case.ids, case.y, fill=7.0)
     assert np.isnan(loss[3]) and np.isfinite(loss[:3]).all() and (g[3] == 7.0).all()        # its gradient row: not written
     losses = bank_distill(case.traj, bank, bopt, case.ids, 2, case.y)
     Wn = bank_weights(bank)
     assert np.isnan(losses[:, 3]).all() and np.isfinite(losses[:, :3]).all()
     assert same(Wn[3], case.W[3]) and all(not same(Wn[p], case.W[p]) for p in range(3))
+    # and so are its moments, step count and running powers: those of creation, while the others' have moved twice
+    m, v, step, powers = state()
+    assert not m[3].any() and not v[3].any() and step.tolist() == [2, 2, 2, 0] and powers[3].tolist() == [1.0, 1.0]
+    assert all(m[p].any() and v[p].any() for p in range(3))
+    b1, b2 = cfg["betas"]
+    assert all(powers[p].tolist() == [b1 * b1, b2 * b2] for p in range(3))
     # later it gets blocks, same optimizer: its first update is update 1 of a fresh Distiller - step count and moments untouched
     ids2 = ids_of([3, 0, 3, 1, 0], N)
     losses2 = bank_distill(case.traj, bank, bopt, ids2, 1, case.y)
@@ -263,6 +270,9 @@ def test_a_policy_without_a_block_is_left_alone(case):
     assert same(losses2[0, 3], ref_losses[0]) and same(ref_losses[0], ref_loss)
     assert same(bank_weights(bank)[3], ref_w) and not same(ref_w, case.W[3])
     assert np.isnan(losses2[0, 2]) and same(bank_weights(bank)[2], Wn[2])      # and policy 2 sat this one out
+    m2, v2, step2, powers2 = state()
+    assert same(m2[2], m[2]) and same(v2[2], v[2]) and same(powers2[2].view(np.uint32), powers[2].view(np.uint32))
+    assert step2.tolist() == [3, 3, 2, 1] and powers2[3].tolist() == [b1, b2]
     bopt.close()
 
 

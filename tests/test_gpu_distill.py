@@ -12,7 +12,7 @@ import pytest
 import distill_reference as D
 import policy_grad_reference as R
 from distill_common import (ASYNC, DEVICE, HOST, INITIAL, Opt, _bits, _ld, _lib, _perturbed, _record, _targets, distill, forward,
-                            get_weights, loss_grad)
+                            get_weights, loss_grad, opt_state)
 from gpu_common import World
 
 pytestmark = pytest.mark.gpu
@@ -105,17 +105,18 @@ def test_deterministic_masked_and_indifferent_to_the_targets_stride(device, orac
 
 
 def test_one_update_is_adam_in_float64_to_a_rounding(device, oracle, weights):
-    """rq_trajectory_distill(n_updates = 1), twice, against tests/distill_reference.Adam applied to the fp32 inputs: the gradient
-    fetched with loss_grad beforehand and the weights read back.  k_adam_repack forms m', v' and w' in float64 from the fp32 inputs
-    and rounds each to fp32 ONCE, so
-      update 1 (m = v = 0, exact inputs): |w1 - ref| <= u |ref|   (+ the float64 roundings of the expression, < 2^-48 relative);
-      update 2: w1 and g2 are exact inputs, m1 and v1 are the device's roundings of the reference's, each within u of it, so
-        |w2 - ref| <= u |ref| + lr / (1 - b1^2) * b1 u |m1| / (sqrt(vhat2) + eps)
-                              + lr |mhat2| * (b2 u v1 / (1 - b2^2)) / (2 sqrt(vhat2) (sqrt(vhat2) + eps)^2)
-    which also holds m1 and v1 - that have no getter - to their one rounding.  An error of the gradient does not enter."""
+    """rq_trajectory_distill(n_updates = 1), twice, against float64 Adam applied to the fp32 inputs: the gradient fetched with
+    loss_grad beforehand, the weights read back, and the moments, step count and running powers read through
+    rq_optimizer_get_state.  k_adam_repack forms m', v' and w' in float64 from the fp32 inputs and rounds each to fp32 ONCE, so
+      update 1 (m = v = 0, exact inputs): |w1 - ref| <= u |ref|   (+ the float64 roundings of the expression, < 2^-48 relative),
+        against tests/distill_reference.Adam; m1 and v1 within one rounding of its moments;
+      update 2: w1, m1, v1 (the device's own bits, read back) and g2 are exact inputs, so w2, m2 and v2 lie within the one-rounding
+        bound of tests/adam_reference.py - no propagation term.  An error of the gradient does not enter."""
+    import adam_reference as A
     from raptor_amd.foundation_policy import Raptor
     n, T = 300, 30
     lr, b1, b2, eps = 3e-3, 0.9, 0.999, 1e-8
+    cfg = (lr, b1, b2, eps, 0.0)
     w, traj = _record(device, oracle, n, T, seed=71)
     pol = Raptor(device, weights=_perturbed(weights, 8))
     pol.reset()
@@ -123,29 +124,33 @@ def test_one_update_is_adam_in_float64_to_a_rounding(device, oracle, weights):
     opt = Opt(pol, lr=lr, betas=(b1, b2), eps=eps)
     w0 = get_weights(pol)
     assert np.array_equal(w0, pol.weights)
+    m0, v0, step0, p0 = opt_state(opt)
+    assert not m0.any() and not v0.any() and step0 == 0 and p0.tolist() == [1.0, 1.0]
     loss0, g1 = loss_grad(traj, pol, y)
     losses = distill(traj, pol, opt, 1, y)
     assert _bits(losses[0]) == _bits(loss0)
     w1 = get_weights(pol)
+    m1, v1, step1, p1 = opt_state(opt)
     ref = D.Adam(w0, lr=lr, betas=(b1, b2), eps=eps)
     r1 = ref.step(g1)
     slack = 1.0 + 2.0 ** -20
     e1 = np.abs(w1 - r1)
     print("update 1: max |w - ref| / (u |ref|)", np.max(e1 / (D.U * np.abs(r1) + 2.0 ** -150)))
     assert (e1 <= slack * D.U * np.abs(r1) + 2.0 ** -150).all() and np.abs(w1 - w0).max() > 0.5 * lr
-    m1, v1 = ref.m.copy(), ref.v.copy()
+    assert (np.abs(m1 - ref.m) <= slack * D.U * np.abs(ref.m) + 2.0 ** -126).all() and m1.any()
+    assert (np.abs(v1 - ref.v) <= slack * D.U * np.abs(ref.v) + 2.0 ** -126).all() and v1.any()
+    assert step1 == 1 and p1.tolist() == [b1, b2]
     _, g2 = loss_grad(traj, pol, y)
     distill(traj, pol, opt, 1, y)
     w2 = get_weights(pol)
-    ref.w = w1.astype(np.float64)                                # the exact input of the second update
-    r2 = ref.step(g2)
-    mhat, vhat = ref.m / (1 - b1 ** 2), ref.v / (1 - b2 ** 2)
-    sq = np.sqrt(vhat)
-    bound = D.U * np.abs(r2) + lr / (1 - b1 ** 2) * b1 * D.U * np.abs(m1) / (sq + eps) \
-        + lr * np.abs(mhat) * (b2 * D.U * v1 / (1 - b2 ** 2)) / (2 * np.maximum(sq, 2.0 ** -150) * (sq + eps) ** 2)
-    e2 = np.abs(w2 - r2)
-    print("update 2: max |w - ref| / bound", np.max(e2 / (slack * bound + 2.0 ** -150)))
-    assert (e2 <= slack * bound + 2.0 ** -150).all()
+    m2, v2, step2, p2 = opt_state(opt)
+    r2 = A.adam_exact(w1, m1, v1, g2, cfg, p1)                   # from the exact inputs of the second update
+    bound = A.bound(w1, m1, v1, g2, cfg, p1)
+    for name, got, r, b in zip(("w", "m", "v"), (w2, m2, v2), r2, bound):
+        ok, ratio = A.agrees(got, r, b)
+        print(f"update 2: max |{name} - ref| / bound", ratio.max())
+        assert ok.all(), (name, int(np.argmax(ratio)), ratio.max())
+    assert step2 == 2 and p2.tolist() == [b1 * b1, b2 * b2]
     opt.close()
 
 
