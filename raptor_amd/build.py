@@ -37,7 +37,7 @@ SOURCES = ["rq_kernels.hip", "rq_kernels_16bit.hip", "rq_teacher.hip", "rq_capi.
            "rq_capi_grad.cpp", "rq_capi_probe.cpp"]
 HEADERS = ["rq_kernels.hpp", "rq_device_math.hpp", "rq_rollout.hpp", "rq_dispatch.hpp", "rq_fused_route.hpp", "rq_host.hpp", "rq_memory.hpp", "rq_call_memory.hpp", "rq_env_schedule.hpp", "rq_objects.hpp", "rq_grad.hpp",
            "rq_grad_bank.hpp", "rq_grad_forward.inc", "rq_grad_backward.inc", "rq_loss_reduce.inc", "rq_adam_repack.inc", "rq_loss_launch.hpp", "rq_step_launch.hpp", "rq_actor_step.inc", "rq_thaw_frozen.inc",
-           "rq_teacher.hpp", "rq_rollout_body.inc", "rq_probe.hpp", "rq_probe.hip", "rq_probe_moments.inc", "rq_flight_launch.hpp", "rq_flight_table.inc"]
+           "rq_teacher.hpp", "rq_rollout_body.inc", "rq_rollout_schedule.inc", "rq_probe.hpp", "rq_probe.hip", "rq_probe_moments.inc", "rq_flight_launch.hpp", "rq_flight_table.inc"]
 # per-source flags (none today).  Round 4 built rq_kernels_16bit.hip with -mllvm -amdgpu-sched-strategy=max-ilp; the gain on the bf16 build
 # that ships was inside the box-to-box spread, and the two-waves-per-SIMD bf16 build gave run-to-run different results with it - the
 # gfx950 fault round 5 found (gfx950_errata.py), which _compile() now rewrites out of every listing whatever the scheduler.

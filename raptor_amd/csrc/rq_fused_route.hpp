@@ -1,7 +1,7 @@
 // rq_fused_route.hpp - which kernel flies a fused rollout: the family of the kernel text and the actor build, from what the launch
 // description says (rq_kernels.hpp FusedArgs, fused_traits).  The one place that states the policy; launch_rollout_fused switches on
-// its answer.  Host code without a HIP dependency: a plain host compiler takes this file alone (tests/fused_route_driver.cpp does,
-// and holds every row of the tables below against tests/test_capi_cpu.py's own copy).
+// its answer.  Host code without a HIP dependency: a plain host compiler takes this file alone (tests/route_driver.cpp does, and
+// holds every row of the tables below against tests/test_routes_cpu.py's own copy).
 #pragma once
 #include <stdint.h>
 
@@ -12,7 +12,10 @@ namespace rq {
 // envs that fill the device at one wave per SIMD: 1024 SIMDs x 64 lanes
 constexpr uint32_t kOneWavePerSimdEnvs = 65536u;
 
-enum class FusedFamily { UNSUPPORTED, PLAIN, TRACK, RATE, WRENCH, BANK, BANK_RATE };
+// The schedules an env can carry, in kind order: wrench, vehicle, wind, delay, sensor (rq_objects.hpp kTableKinds).  In fused mode
+// each has one kernel family of its own - k_rollout_fused_<kind>, stamped from rq_rollout_schedule.inc - which serves a policy and a
+// bank, tracked or not, at every native interval; the other families fly the launches without a schedule.
+enum class FusedFamily { UNSUPPORTED, PLAIN, TRACK, RATE, BANK, BANK_RATE, WRENCH, VEHICLE, WIND, DELAY, SENSOR };
 enum class FusedBuild { F32, F32_LEAN, BF16, F16X2 };      // ActorF32, ActorF32Lean, ActorBF16, ActorF16X2
 
 struct FusedTraits {
@@ -30,27 +33,26 @@ struct FusedTraits {
     bool sensor = false;    // the env carries a sensor schedule
 };
 
-// vehicle: the env carries a vehicle schedule - k_rollout_fused_vehicle flies the launch, whatever `family` (what the launch would be
-// without the schedule) says; the entry point is one for a policy and a bank, tracked or not, at every native interval
-// wind: likewise for a wind schedule and k_rollout_fused_wind; delay: for a delay schedule and k_rollout_fused_delay; sensor: for a
-// sensor schedule and k_rollout_fused_sensor
-struct FusedRoute { FusedFamily family; FusedBuild build; bool vehicle = false; bool wind = false; bool delay = false; bool sensor = false; };
+struct FusedRoute { FusedFamily family; FusedBuild build; };
 
 constexpr FusedRoute route_fused(const FusedTraits& t) {
     const bool f32 = t.precision == RQ_POLICY_FP32, bf16 = t.precision == RQ_POLICY_BF16_MFMA, f16x2 = t.precision == RQ_POLICY_F16X2_MFMA;
-    // What no kernel is built for (the C layer refuses each before anything is enqueued): a schedule beside a 16-bit policy or a
-    // SampleAndSquash stage; that stage anywhere but in the PLAIN family; a bank in anything but fp32; a vehicle schedule beside a
-    // 16-bit policy, that stage or a wrench schedule; a wind schedule beside a 16-bit policy, that stage or another schedule;
-    // a delay schedule likewise; a sensor schedule likewise.
-    const bool unsupported = !(f32 || bf16 || f16x2) || (t.wrench && (!f32 || t.sas)) ||
-                             (t.sas && (t.tracked || t.bank || t.interval > 1)) || (t.bank && !f32) ||
-                             (t.vehicle && (!f32 || t.sas || t.wrench)) || (t.wind && (!f32 || t.sas || t.wrench || t.vehicle)) ||
-                             (t.delay && (!f32 || t.sas || t.wrench || t.vehicle || t.wind)) ||
-                             (t.sensor && (!f32 || t.sas || t.wrench || t.vehicle || t.wind || t.delay));
-    if (unsupported) return {FusedFamily::UNSUPPORTED, FusedBuild::F32, false, false, false, false};
-    // WRENCH and the vehicle, wind and delay schedules' kernels serve one policy (tables null, single_interval = its interval) and a bank (tables set,
-    // single_interval = 1) alike; TRACK is a template bool of RATE, BANK_RATE, WRENCH and the vehicle, wind and delay kernels, SAS one of PLAIN.
-    const FusedFamily family = t.wrench ? FusedFamily::WRENCH
+    // the schedules the env carries, in kind order: the enumerators from WRENCH on
+    const bool carried[] = {t.wrench, t.vehicle, t.wind, t.delay, t.sensor};
+    constexpr int kinds = sizeof(carried) / sizeof(carried[0]);
+    static_assert((int)FusedFamily::SENSOR - (int)FusedFamily::WRENCH == kinds - 1, "one family per kind, in kind order");
+    int schedules = 0, kind = 0;
+    for (int k = 0; k < kinds; ++k)
+        if (carried[k]) { ++schedules; kind = k; }
+    // What no kernel is built for (the C layer refuses each before anything is enqueued): more than one schedule in fused mode; a
+    // schedule beside a 16-bit policy or a SampleAndSquash stage; that stage anywhere but in the PLAIN family; a bank in anything but
+    // fp32.
+    const bool unsupported = !(f32 || bf16 || f16x2) || schedules > 1 || (schedules == 1 && (!f32 || t.sas)) ||
+                             (t.sas && (t.tracked || t.bank || t.interval > 1)) || (t.bank && !f32);
+    if (unsupported) return {FusedFamily::UNSUPPORTED, FusedBuild::F32};
+    // A schedule's family serves one policy (tables null, single_interval = its interval) and a bank (tables set, single_interval = 1)
+    // alike; TRACK is a template bool of RATE, BANK_RATE and the schedules' families, SAS one of PLAIN.
+    const FusedFamily family = schedules == 1 ? (FusedFamily)((int)FusedFamily::WRENCH + kind)
                                : t.bank ? (t.tracked || t.bank_rated ? FusedFamily::BANK_RATE : FusedFamily::BANK)
                                : t.interval > 1 ? FusedFamily::RATE
                                : t.tracked ? FusedFamily::TRACK
@@ -64,7 +66,7 @@ constexpr FusedRoute route_fused(const FusedTraits& t) {
                              : f16x2 ? FusedBuild::F16X2
                              : ((family == FusedFamily::PLAIN && t.sas) || t.n > kOneWavePerSimdEnvs) ? FusedBuild::F32_LEAN
                                                                                                       : FusedBuild::F32;
-    return {family, build, t.vehicle, t.wind, t.delay, t.sensor};
+    return {family, build};
 }
 
 }  // namespace rq

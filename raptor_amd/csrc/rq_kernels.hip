@@ -595,6 +595,71 @@ __global__ __launch_bounds__(kBlock) void k_step_delay(Batch b, StepCfg c, const
                                                        mb, on, wr, vh, wd, dl);
     mailbox_signal(mb);
 }
+
+// ---- a policy bank's env step
+// k_step<true> whose policy-state reset (auto-reset at an episode end: h <- initial_hidden_state) reads the weight block of the env's
+// own policy: weights [P][RQ_POLICY_NUM_WEIGHTS], checkpoint order
+__global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                      float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                      uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                      const uint32_t* __restrict__ block_policy) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                       weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{});
+}
+
+// k_step_bank for an env that carries a wrench schedule
+__global__ __launch_bounds__(kBlock) void k_step_bank_wrench(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                             float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                             uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                             const uint32_t* __restrict__ block_policy, WrenchPtrs wr) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                             weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr);
+}
+
+// ... and for one that carries a vehicle schedule, with or without a wrench schedule beside it
+template <bool WRENCH>
+__global__ __launch_bounds__(kBlock) void k_step_bank_vehicle(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                              float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                              uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                              const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true, WRENCH, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                                     weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr, vh);
+}
+
+// ... and for one that carries a wind schedule, alone or beside the other two
+template <bool WRENCH, bool VEHICLE>
+__global__ __launch_bounds__(kBlock) void k_step_bank_wind(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                           float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                           uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                           const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
+                                                           WindPtrs wd) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true, WRENCH, VEHICLE, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                                              weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr, vh,
+                                              wd);
+}
+
+// ... and for one that carries a delay schedule, alone or beside the other three
+template <bool WRENCH, bool VEHICLE, bool WIND>
+__global__ __launch_bounds__(kBlock) void k_step_bank_delay(Batch b, StepCfg c, const float* __restrict__ params, float* state,
+                                                            float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
+                                                            uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
+                                                            const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
+                                                            WindPtrs wd, DelayPtrs dl) {
+    const uint32_t i = env_index();
+    if (i < b.n)
+        step_env<true, WRENCH, VEHICLE, WIND, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
+                                                    weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr,
+                                                    vh, wd, dl);
+}
+
 // ------------------------------------------------------------------ resident executor ---
 // The reference's loop at its own batch (README.md:96-99, `vector8`): observe -> evaluate_step -> step -> assign on a handful of envs
 // with NumPy arrays at every call.  Rounds 3-5 served an iteration with ONE kernel round trip (k_step assembles the next observation,
@@ -1059,8 +1124,7 @@ hipError_t launch_add_u32(hipStream_t s, uint32_t* p, uint32_t add) {
 // ---- the actor step's one launcher: the four kernels of rq_actor_step.inc and k_actor_stream, chosen by route_actor_step
 static_assert(kBlock == (int)kActorBlock, "route_actor_step counts its grid in workgroups of kBlock threads");
 
-// The kernel templates of this file come out in the order in which its launchers name them.  What is named here, in this order, and
-// the bank's two below the fused rollout's launcher keep the listing in the order it always had: the same code object, byte for byte.
+// (the bank's two kernels are launched below the fused rollout's launcher)
 static void launch_actor_step_of_bank(hipStream_t s, const ActorStepLaunch& a, const ActorStepRoute& r);
 
 hipError_t launch_actor_step(hipStream_t s, const ActorStepLaunch& a) {
@@ -1133,109 +1197,51 @@ hipError_t launch_actor_relabel(hipStream_t s, uint32_t n, uint32_t ld, uint32_t
     return hipGetLastError();
 }
 
-// ---- the env step's one launcher.  (A bank's two kernels are defined with the bank's, below.)
-__global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action, StatsPtrs st,
-                            uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
-                            const uint32_t* __restrict__ block_policy);
-__global__ __launch_bounds__(kBlock) void k_step_bank_wrench(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
-                                   StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
-                                   const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr);
-template <bool WRENCH>
-__global__ __launch_bounds__(kBlock) void k_step_bank_vehicle(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
-                                    StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
-                                    const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh);
-
-template <bool WRENCH, bool VEHICLE>
-__global__ __launch_bounds__(kBlock) void k_step_bank_wind(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
-                                    StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
-                                    const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
-                                    WindPtrs wd);
-
-template <bool WRENCH, bool VEHICLE, bool WIND>
-__global__ __launch_bounds__(kBlock) void k_step_bank_delay(Batch b, StepCfg c, const float* __restrict__ params, float* state, float* __restrict__ action,
-                                    StatsPtrs st, uint32_t flags, SampleCfg sc, uint64_t seed, float* __restrict__ hidden,
-                                    const float* __restrict__ weights, const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
-                                    WindPtrs wd, DelayPtrs dl);
-
-// the delay schedule's kernels: `family`, `wrench` and `wind` say what the step would be without the delay
-static void launch_step_delay(hipStream_t s, const EnvStepLaunch& e, const EnvStepRoute& r, unsigned grid, const ObsNext& on) {
-    dispatch_bools([&](auto WR, auto VH, auto WD, auto RO) {
-        if (e.block_policy != nullptr) {
-            const auto kernel = &k_step_bank_delay<WR(), VH(), WD()>;
-            RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed, e.hidden,
-                       e.weights, e.block_policy, e.wr, e.vh, e.wd, e.dl);
-        } else {
-            const auto kernel = &k_step_delay<RO(), WR(), VH(), WD()>;
-            RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
-                       e.hidden, e.weights, e.mb, on, e.wr, e.vh, e.wd, e.dl);
-        }
-    }, r.wrench, r.family == EnvStepFamily::VEHICLE || r.family == EnvStepFamily::BANK_VEHICLE, r.wind, r.rollout);
+// ---- the env step's one launcher: the kernel route_env_step names
+// The launch description unpacked into a kernel's positional parameters, once for the policy's kernels and once for the bank's (a
+// rollout's step in place: no state to read from elsewhere, no host rows, no folded observation); `schedules`: the *Ptrs the
+// kernel's family takes behind them, in nesting order.
+template <typename KERNEL, typename... SCHEDULES>
+static void launch_step_kernel(hipStream_t s, const EnvStepLaunch& e, KERNEL kernel, const ObsNext& on, SCHEDULES... schedules) {
+    RQ_KLAUNCH(kernel, grid_for(e.b.n, kBlock), kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc,
+               e.seed, e.hidden, e.weights, e.mb, on, schedules...);
 }
-
-// the wind schedule's kernels: `family` says what the step would be without the wind (its bank-ness and whether a vehicle schedule
-// stands beside it), `wrench` whether a wrench schedule does
-static void launch_step_wind(hipStream_t s, const EnvStepLaunch& e, const EnvStepRoute& r, unsigned grid, const ObsNext& on) {
-    dispatch_bools([&](auto WR, auto VH, auto RO) {
-        if (e.block_policy != nullptr) {
-            const auto kernel = &k_step_bank_wind<WR(), VH()>;
-            RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed, e.hidden,
-                       e.weights, e.block_policy, e.wr, e.vh, e.wd);
-        } else {
-            const auto kernel = &k_step_wind<RO(), WR(), VH()>;
-            RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
-                       e.hidden, e.weights, e.mb, on, e.wr, e.vh, e.wd);
-        }
-    }, r.wrench, r.family == EnvStepFamily::VEHICLE || r.family == EnvStepFamily::BANK_VEHICLE, r.rollout);
-}
-
-// the vehicle schedule's kernels, by the route's two bools
-static void launch_step_vehicle(hipStream_t s, const EnvStepLaunch& e, const EnvStepRoute& r, unsigned grid, const ObsNext& on) {
-    const auto kernel = r.rollout ? (r.wrench ? &k_step_vehicle<true, true> : &k_step_vehicle<true, false>)
-                                  : (r.wrench ? &k_step_vehicle<false, true> : &k_step_vehicle<false, false>);
-    RQ_KLAUNCH(kernel, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed, e.hidden,
-               e.weights, e.mb, on, e.wr, e.vh);
+template <typename KERNEL, typename... SCHEDULES>
+static void launch_step_bank_kernel(hipStream_t s, const EnvStepLaunch& e, KERNEL kernel, SCHEDULES... schedules) {
+    RQ_KLAUNCH(kernel, grid_for(e.b.n, kBlock), kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed,
+               e.hidden, e.weights, e.block_policy, schedules...);
 }
 
 hipError_t launch_step(hipStream_t s, const EnvStepLaunch& e) {
     if (e.b.n == 0) return hipSuccess;
-    const unsigned grid = grid_for(e.b.n, kBlock);
-    const EnvStepRoute route = route_env_step(e);
-    const bool wrench = route.wrench;
+    const EnvStepRoute r = route_env_step(e);
+    if (!r.supported) return hipErrorInvalidValue;
     const ObsNext on{e.obs_of_next, e.nc, e.noise ? 1u : 0u, e.obs_epoch, e.obs_epoch_base};
-    if (route.family == EnvStepFamily::UNSUPPORTED) return hipErrorInvalidValue;
-    if (route.delay) {
-        launch_step_delay(s, e, route, grid, on);
-    } else if (route.wind) {
-        launch_step_wind(s, e, route, grid, on);
-    } else if (route.family == EnvStepFamily::VEHICLE) {
-        launch_step_vehicle(s, e, route, grid, on);
-    } else if (route.family == EnvStepFamily::BANK_VEHICLE) {
-        if (wrench)
-            RQ_KLAUNCH(k_step_bank_vehicle<true>, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed,
-                       e.hidden, e.weights, e.block_policy, e.wr, e.vh);
-        else
-            RQ_KLAUNCH(k_step_bank_vehicle<false>, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed,
-                       e.hidden, e.weights, e.block_policy, e.wr, e.vh);
-    } else if (e.block_policy != nullptr) {
-        if (wrench)
-            RQ_KLAUNCH(k_step_bank_wrench, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed,
-                       e.hidden, e.weights, e.block_policy, e.wr);
-        else
-            RQ_KLAUNCH(k_step_bank, grid, kBlock, s, e.b, e.c, e.params, e.next_state, e.action, e.st, e.flags, e.sc, e.seed, e.hidden,
-                       e.weights, e.block_policy);
-    } else if (wrench && e.rollout) {
-        RQ_KLAUNCH(k_step_wrench<true>, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
-                   e.hidden, e.weights, e.mb, on, e.wr);
-    } else if (wrench) {
-        RQ_KLAUNCH(k_step_wrench<false>, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
-                   e.hidden, e.weights, e.mb, on, e.wr);
-    } else if (e.rollout) {
-        RQ_KLAUNCH(k_step<true>, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
-                   e.hidden, e.weights, e.mb, on);
-    } else {
-        RQ_KLAUNCH(k_step<false>, grid, kBlock, s, e.b, e.c, e.params, e.state, e.action, e.next_state, e.st, e.flags, e.sc, e.seed,
-                   e.hidden, e.weights, e.mb, on);
-    }
+    // the family's kernel, the schedules inside it and `rollout` its template arguments (a family reads the bools of the kinds it nests)
+    dispatch_bools([&](auto RO, auto WR, auto VH, auto WD) {
+        switch (r.family) {
+        case EnvStepFamily::NONE:
+            if (r.bank) launch_step_bank_kernel(s, e, &k_step_bank);
+            else        launch_step_kernel(s, e, &k_step<RO()>, on);
+            break;
+        case EnvStepFamily::WRENCH:
+            if (r.bank) launch_step_bank_kernel(s, e, &k_step_bank_wrench, e.wr);
+            else        launch_step_kernel(s, e, &k_step_wrench<RO()>, on, e.wr);
+            break;
+        case EnvStepFamily::VEHICLE:
+            if (r.bank) launch_step_bank_kernel(s, e, &k_step_bank_vehicle<WR()>, e.wr, e.vh);
+            else        launch_step_kernel(s, e, &k_step_vehicle<RO(), WR()>, on, e.wr, e.vh);
+            break;
+        case EnvStepFamily::WIND:
+            if (r.bank) launch_step_bank_kernel(s, e, &k_step_bank_wind<WR(), VH()>, e.wr, e.vh, e.wd);
+            else        launch_step_kernel(s, e, &k_step_wind<RO(), WR(), VH()>, on, e.wr, e.vh, e.wd);
+            break;
+        case EnvStepFamily::DELAY:
+            if (r.bank) launch_step_bank_kernel(s, e, &k_step_bank_delay<WR(), VH(), WD()>, e.wr, e.vh, e.wd, e.dl);
+            else        launch_step_kernel(s, e, &k_step_delay<RO(), WR(), VH(), WD()>, on, e.wr, e.vh, e.wd, e.dl);
+            break;
+        }
+    }, r.rollout, r.wrench, r.vehicle, r.wind);
     return RQ_KLAUNCH_STATUS();
 }
 
@@ -1391,19 +1397,6 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const uint32_t* __restrict__ block_policy, uint32_t image_floats,
                                                                StatsPtrs st, TrajPtrs traj,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool TRACK = false, RATE = false, SAS = false, WRENCH = false;
-    constexpr TrackPtrs trk{};
-    constexpr SasArgs sas{};
-    constexpr WrenchPtrs wr{};
-    constexpr bool VEHICLE = false;
-    constexpr VehiclePtrs vh{};
-    constexpr bool WIND = false;
-    constexpr WindPtrs wd{};
-    constexpr bool DELAY = false;
-    constexpr DelayPtrs dl{};
-    constexpr bool SENSOR = false;
-    constexpr SensorPtrs sn{};
-    constexpr uint32_t interval = 1;
     const float* __restrict__ packed = images + (size_t)block_policy[blockIdx.x] * image_floats;
 #include "rq_rollout_body.inc"
 }
@@ -1425,20 +1418,11 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
                                                                StatsPtrs st, TrajPtrs traj, TrackPtrs trk,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false;
-    constexpr SasArgs sas{};
-    constexpr WrenchPtrs wr{};
-    constexpr bool VEHICLE = false;
-    constexpr VehiclePtrs vh{};
-    constexpr bool WIND = false;
-    constexpr WindPtrs wd{};
-    constexpr bool DELAY = false;
-    constexpr DelayPtrs dl{};
-    constexpr bool SENSOR = false;
-    constexpr SensorPtrs sn{};
     const uint32_t policy = block_policy[blockIdx.x];
     const uint32_t interval = policy_interval[policy];
     const float* __restrict__ packed = images + (size_t)policy * image_floats;
+#define RQ_FUSED_TAKES_TRACK
+#define RQ_FUSED_TAKES_RATE
 #include "rq_rollout_body.inc"
 }
 
@@ -1460,232 +1444,48 @@ static inline void launch_fused_bank_rate_actor(hipStream_t s, const FusedArgs& 
     }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
 }
 
-// ---- the fused kernel of an env that carries a wrench schedule
-// The text of k_rollout_fused_bank_rate - the RATE loop, image and interval chosen per workgroup - with WRENCH on: the scales and the
-// env's first row are loaded once per launch, every step asks for its row ahead of the actor and rebuilds the disturbance just before
-// the env step (rq_rollout_body.inc).  The block tables are optional: block_policy == nullptr is ONE policy, whose image is `images`
-// and whose native interval is `single_interval`.  At interval 1 the RATE text computes the plain kernel's bits (see above), so this
-// one entry point serves rq_rollout, rq_rollout_record, rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every
-// native interval.  fp32 actors only: the host refuses the 16-bit policies and the SampleAndSquash stage while a schedule is attached.
-template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
-__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_wrench(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
-                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
-                                                               const float* __restrict__ params,
-                                                               float* __restrict__ state,
-                                                               float* __restrict__ hidden,
-                                                               const float* __restrict__ w,
-                                                               const float* __restrict__ images,
-                                                               const uint32_t* __restrict__ block_policy,
-                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
-                                                               uint32_t single_interval,
-                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WrenchPtrs wr,
-                                                               unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = true, VEHICLE = false, WIND = false, DELAY = false, SENSOR = false;
-    constexpr SensorPtrs sn{};
-    constexpr DelayPtrs dl{};
-    constexpr SasArgs sas{};
-    constexpr VehiclePtrs vh{};
-    constexpr WindPtrs wd{};
-    uint32_t policy = 0, interval = single_interval;
-    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
-        policy = block_policy[blockIdx.x];
-        interval = policy_interval[policy];
-    }
-    const float* __restrict__ packed = images + (size_t)policy * image_floats;
-#include "rq_rollout_body.inc"
-}
-
-// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
-template <typename ACTOR>
-static inline void launch_fused_wrench_actor(hipStream_t s, const FusedArgs& a) {
-    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
-        hipLaunchKernelGGL((k_rollout_fused_wrench<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
-                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.wr, a.span);
-    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
-}
-
-// ---- the fused kernel of an env that carries a vehicle schedule
-// Built as k_rollout_fused_wrench is - the RATE loop with optional block tables, so one entry point serves rq_rollout,
-// rq_rollout_record, rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every native interval - with VEHICLE on: the
-// nine base fields the schedule scales stay live, the env's first row is loaded once per launch, every step asks for its 16-byte row
-// of factors ahead of the actor and, just before the env step, rebuilds the scheduled members of the per-env constants (1/m, 2/m; J
-// and 1/J; c0..c2; 1/tau_rise, 1/tau_fall: six reciprocals, eleven products) and the folded disturbance from them
-// (rq_rollout_body.inc).  fp32 actors only: the host refuses the 16-bit policies, the SampleAndSquash stage and a wrench schedule
-// beside a vehicle schedule in fused mode.
-template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
-__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_vehicle(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
-                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
-                                                               const float* __restrict__ params,
-                                                               float* __restrict__ state,
-                                                               float* __restrict__ hidden,
-                                                               const float* __restrict__ w,
-                                                               const float* __restrict__ images,
-                                                               const uint32_t* __restrict__ block_policy,
-                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
-                                                               uint32_t single_interval,
-                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, VehiclePtrs vh,
-                                                               unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = true, WIND = false, DELAY = false, SENSOR = false;
-    constexpr SensorPtrs sn{};
-    constexpr DelayPtrs dl{};
-    constexpr SasArgs sas{};
-    constexpr WrenchPtrs wr{};
-    constexpr WindPtrs wd{};
-    uint32_t policy = 0, interval = single_interval;
-    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
-        policy = block_policy[blockIdx.x];
-        interval = policy_interval[policy];
-    }
-    const float* __restrict__ packed = images + (size_t)policy * image_floats;
-#include "rq_rollout_body.inc"
-}
-
-// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
-template <typename ACTOR>
-static inline void launch_fused_vehicle_actor(hipStream_t s, const FusedArgs& a) {
-    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
-        hipLaunchKernelGGL((k_rollout_fused_vehicle<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
-                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.vh, a.span);
-    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
-}
-
-// ---- the fused kernel of an env that carries a wind schedule
-// Built as k_rollout_fused_wrench is - the RATE loop with optional block tables, one entry point for rq_rollout, rq_rollout_record,
-// rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every native interval - with WIND on: the mass and the env's
-// first row are loaded once per launch, every step asks for its 16-byte row ahead of the actor and, just before the env step, adds
-// the drag against the air at the state before the step to the force (one product for m d, three differences, three products, three
-// sums) and folds the disturbance from it (rq_rollout_body.inc).  fp32 actors only: the host refuses the 16-bit policies, the
-// SampleAndSquash stage and another schedule beside a wind schedule in fused mode.
-template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
-__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_wind(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
-                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
-                                                               const float* __restrict__ params,
-                                                               float* __restrict__ state,
-                                                               float* __restrict__ hidden,
-                                                               const float* __restrict__ w,
-                                                               const float* __restrict__ images,
-                                                               const uint32_t* __restrict__ block_policy,
-                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
-                                                               uint32_t single_interval,
-                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, WindPtrs wd,
-                                                               unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = true, DELAY = false, SENSOR = false;
-    constexpr SensorPtrs sn{};
-    constexpr DelayPtrs dl{};
-    constexpr SasArgs sas{};
-    constexpr WrenchPtrs wr{};
-    constexpr VehiclePtrs vh{};
-    uint32_t policy = 0, interval = single_interval;
-    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
-        policy = block_policy[blockIdx.x];
-        interval = policy_interval[policy];
-    }
-    const float* __restrict__ packed = images + (size_t)policy * image_floats;
-#include "rq_rollout_body.inc"
-}
-
-// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
-template <typename ACTOR>
-static inline void launch_fused_wind_actor(hipStream_t s, const FusedArgs& a) {
-    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
-        hipLaunchKernelGGL((k_rollout_fused_wind<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
-                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.wd, a.span);
-    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
-}
-
-// ---- the fused kernel of an env that carries a delay schedule
-// Built as k_rollout_fused_wind is - the RATE loop with optional block tables, one entry point for rq_rollout, rq_rollout_record,
-// rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every native interval - with DELAY on: the env's first row is
-// loaded once per launch, every step asks for its byte of delay and, from the env's command history, for the four floats of the
-// command given that many steps ago, ahead of the actor; after the actor the step's own command goes into the history where the
-// step commits, and the env step is computed from the old one (rq_rollout_body.inc).  fp32 actors only: the host refuses the 16-bit
-// policies, the SampleAndSquash stage and another schedule beside a delay schedule in fused mode.
-template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
-__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_delay(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
-                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
-                                                               const float* __restrict__ params,
-                                                               float* __restrict__ state,
-                                                               float* __restrict__ hidden,
-                                                               const float* __restrict__ w,
-                                                               const float* __restrict__ images,
-                                                               const uint32_t* __restrict__ block_policy,
-                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
-                                                               uint32_t single_interval,
-                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, DelayPtrs dl,
-                                                               unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = false, DELAY = true, SENSOR = false;
-    constexpr SensorPtrs sn{};
-    constexpr SasArgs sas{};
-    constexpr WrenchPtrs wr{};
-    constexpr VehiclePtrs vh{};
-    constexpr WindPtrs wd{};
-    uint32_t policy = 0, interval = single_interval;
-    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
-        policy = block_policy[blockIdx.x];
-        interval = policy_interval[policy];
-    }
-    const float* __restrict__ packed = images + (size_t)policy * image_floats;
-#include "rq_rollout_body.inc"
-}
-
-// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
-template <typename ACTOR>
-static inline void launch_fused_delay_actor(hipStream_t s, const FusedArgs& a) {
-    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
-        hipLaunchKernelGGL((k_rollout_fused_delay<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
-                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.dl, a.span);
-    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
-}
-
-// ---- the fused kernel of an env that carries a sensor schedule
-// Built as k_rollout_fused_delay is - the RATE loop with optional block tables, one entry point for rq_rollout, rq_rollout_record,
-// rq_rollout_track[_refs] and rq_rollout_policies[_track[_refs]] at every native interval - with SENSOR on: the env's first row is
-// loaded once per launch, every step asks for its byte of delay and, from the env's readings, for the 18 floats of the reading taken
-// that many steps ago (none if no lane of the wave is behind); behind observe_head the step's own reading goes into the ring where the
-// env is inside the batch and not frozen, and the old one takes its place in front of the setpoint's shift and the actor
-// (rq_rollout_body.inc).  fp32 actors only: the host refuses the 16-bit policies, the SampleAndSquash stage and another schedule
-// beside a sensor schedule in fused mode.
-template <bool NOISE, bool AUTORESET, bool RECORD, bool TRACK, typename ACTOR>
-__global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rollout_fused_sensor(Batch b, StepCfg c, NoiseCfg nc, SampleCfg sc,
-                                                               uint64_t seed, uint32_t epoch0, uint32_t n_steps,
-                                                               const float* __restrict__ params,
-                                                               float* __restrict__ state,
-                                                               float* __restrict__ hidden,
-                                                               const float* __restrict__ w,
-                                                               const float* __restrict__ images,
-                                                               const uint32_t* __restrict__ block_policy,
-                                                               const uint32_t* __restrict__ policy_interval, uint32_t image_floats,
-                                                               uint32_t single_interval,
-                                                               StatsPtrs st, TrajPtrs traj, TrackPtrs trk, SensorPtrs sn,
-                                                               unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false, VEHICLE = false, WIND = false, DELAY = false, SENSOR = true;
-    constexpr SasArgs sas{};
-    constexpr WrenchPtrs wr{};
-    constexpr VehiclePtrs vh{};
-    constexpr WindPtrs wd{};
-    constexpr DelayPtrs dl{};
-    uint32_t policy = 0, interval = single_interval;
-    if (block_policy != nullptr) {                   // wave-uniform (kernel argument): scalar loads, as in k_rollout_fused_bank_rate
-        policy = block_policy[blockIdx.x];
-        interval = policy_interval[policy];
-    }
-    const float* __restrict__ packed = images + (size_t)policy * image_floats;
-#include "rq_rollout_body.inc"
-}
-
-// one policy: the tables null, its image and its interval; a bank: the tables (a.interval, left at 1, is not read)
-template <typename ACTOR>
-static inline void launch_fused_sensor_actor(hipStream_t s, const FusedArgs& a) {
-    dispatch_bools([&](auto NZ, auto AR, auto RC, auto TK) {
-        hipLaunchKernelGGL((k_rollout_fused_sensor<NZ(), AR(), RC(), TK(), ACTOR>), dim3(fused_grid(a)), dim3(kFusedBlock), 0, s,
-                           a.b, a.c, a.nc, a.sc, a.seed, a.epoch0, a.n_steps, a.params, a.state, a.hidden, a.weights, a.images,
-                           a.block_policy, a.policy_interval, (uint32_t)RQ_PACKED_FLOATS, a.interval, a.st, a.traj, a.trk, a.sn, a.span);
-    }, a.noise, a.autoreset, a.traj.obs != nullptr, a.trk.ref != nullptr);
-}
+// ---- the fused kernels of an env that carries a schedule: k_rollout_fused_<kind>, one text (rq_rollout_schedule.inc), what the body
+// (rq_rollout_body.inc) does with each kind:
+// WRENCH: the scales and the env's first row are loaded once per launch, every step asks for its row ahead of the actor and rebuilds
+// the disturbance just before the env step.
+#define RQ_SCHEDULE_KERNEL k_rollout_fused_wrench
+#define RQ_FUSED_TAKES_WRENCH
+#define RQ_SCHEDULE_PTRS WrenchPtrs
+#define RQ_SCHEDULE_NAME wr
+#include "rq_rollout_schedule.inc"
+// VEHICLE: the nine base fields the schedule scales stay live, the env's first row is loaded once per launch, every step asks for its
+// 16-byte row of factors ahead of the actor and, just before the env step, rebuilds the scheduled members of the per-env constants
+// (1/m, 2/m; J and 1/J; c0..c2; 1/tau_rise, 1/tau_fall: six reciprocals, eleven products) and the folded disturbance from them.
+#define RQ_SCHEDULE_KERNEL k_rollout_fused_vehicle
+#define RQ_FUSED_TAKES_VEHICLE
+#define RQ_SCHEDULE_PTRS VehiclePtrs
+#define RQ_SCHEDULE_NAME vh
+#include "rq_rollout_schedule.inc"
+// WIND: the mass and the env's first row are loaded once per launch, every step asks for its 16-byte row ahead of the actor and, just
+// before the env step, adds the drag against the air at the state before the step to the force (one product for m d, three
+// differences, three products, three sums) and folds the disturbance from it.
+#define RQ_SCHEDULE_KERNEL k_rollout_fused_wind
+#define RQ_FUSED_TAKES_WIND
+#define RQ_SCHEDULE_PTRS WindPtrs
+#define RQ_SCHEDULE_NAME wd
+#include "rq_rollout_schedule.inc"
+// DELAY: the env's first row is loaded once per launch, every step asks for its byte of delay and, from the env's command history,
+// for the four floats of the command given that many steps ago, ahead of the actor; after the actor the step's own command goes into
+// the history where the step commits, and the env step is computed from the old one.
+#define RQ_SCHEDULE_KERNEL k_rollout_fused_delay
+#define RQ_FUSED_TAKES_DELAY
+#define RQ_SCHEDULE_PTRS DelayPtrs
+#define RQ_SCHEDULE_NAME dl
+#include "rq_rollout_schedule.inc"
+// SENSOR: the env's first row is loaded once per launch, every step asks for its byte of delay and, from the env's readings, for the
+// 18 floats of the reading taken that many steps ago (none if no lane of the wave is behind); behind observe_head the step's own
+// reading goes into the ring where the env is inside the batch and not frozen, and the old one takes its place in front of the
+// setpoint's shift and the actor.
+#define RQ_SCHEDULE_KERNEL k_rollout_fused_sensor
+#define RQ_FUSED_TAKES_SENSOR
+#define RQ_SCHEDULE_PTRS SensorPtrs
+#define RQ_SCHEDULE_NAME sn
+#include "rq_rollout_schedule.inc"
 
 // ---- the fused rollout's one launcher: every family above and in rq_rollout.hpp, chosen by route_fused
 // One fp32 build's instantiations, SAS = false (the SampleAndSquash stage: ActorF32Lean alone, below).
@@ -1695,9 +1495,13 @@ static void launch_fused_f32_actor(hipStream_t s, const FusedArgs& a, FusedFamil
     case FusedFamily::PLAIN:     launch_fused_actor<false, ACTOR>(s, a); break;
     case FusedFamily::TRACK:     launch_fused_track_actor<ACTOR>(s, a); break;
     case FusedFamily::RATE:      launch_fused_rate_actor<ACTOR>(s, a); break;
-    case FusedFamily::WRENCH:    launch_fused_wrench_actor<ACTOR>(s, a); break;
     case FusedFamily::BANK:      launch_fused_bank_actor<ACTOR>(s, a); break;
     case FusedFamily::BANK_RATE: launch_fused_bank_rate_actor<ACTOR>(s, a); break;
+    case FusedFamily::WRENCH:    launch_fused_schedule_actor<ACTOR>(s, a, a.wr); break;
+    case FusedFamily::VEHICLE:   launch_fused_schedule_actor<ACTOR>(s, a, a.vh); break;
+    case FusedFamily::WIND:      launch_fused_schedule_actor<ACTOR>(s, a, a.wd); break;
+    case FusedFamily::DELAY:     launch_fused_schedule_actor<ACTOR>(s, a, a.dl); break;
+    case FusedFamily::SENSOR:    launch_fused_schedule_actor<ACTOR>(s, a, a.sn); break;
     case FusedFamily::UNSUPPORTED: break;
     }
 }
@@ -1711,19 +1515,11 @@ hipError_t launch_rollout_fused(hipStream_t s, const FusedArgs& a) {
     case FusedBuild::F16X2:      // the 16-bit actors live in their own translation unit (rq_kernels_16bit.hip: a place for per-build flags)
         return launch_rollout_fused_16bit(s, a, r.family);
     case FusedBuild::F32_LEAN:
-        if (r.sensor)                      launch_fused_sensor_actor<ActorF32Lean>(s, a);     // (a sensor schedule: its own entry point)
-        else if (r.delay)                  launch_fused_delay_actor<ActorF32Lean>(s, a);      // (a delay schedule: likewise)
-        else if (r.wind)                   launch_fused_wind_actor<ActorF32Lean>(s, a);       // (a wind schedule: likewise)
-        else if (r.vehicle)                launch_fused_vehicle_actor<ActorF32Lean>(s, a);    // (a vehicle schedule: likewise)
-        else if (a.sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a);      // (PLAIN: route_fused allows the stage nowhere else)
-        else                               launch_fused_f32_actor<ActorF32Lean>(s, a, r.family);
+        if (a.sas.mode != RQ_SAS_OFF) launch_fused_actor<true, ActorF32Lean>(s, a);      // (PLAIN: route_fused allows the stage nowhere else)
+        else                          launch_fused_f32_actor<ActorF32Lean>(s, a, r.family);
         break;
     case FusedBuild::F32:
-        if (r.sensor)       launch_fused_sensor_actor<ActorF32>(s, a);
-        else if (r.delay)   launch_fused_delay_actor<ActorF32>(s, a);
-        else if (r.wind)    launch_fused_wind_actor<ActorF32>(s, a);
-        else if (r.vehicle) launch_fused_vehicle_actor<ActorF32>(s, a);
-        else                launch_fused_f32_actor<ActorF32>(s, a, r.family);
+        launch_fused_f32_actor<ActorF32>(s, a, r.family);
         break;
     }
     return hipGetLastError();
@@ -1739,95 +1535,7 @@ static void launch_actor_step_of_bank(hipStream_t s, const ActorStepLaunch& a, c
                    (uint32_t)RQ_PACKED_FLOATS, a.obs, a.ld_obs, a.hidden, a.ld_h, a.act, a.ld_act, a.frozen, a.steps);
 }
 
-// ---- the bank's env step, thaw and initial hidden state
-// k_step<true> whose policy-state reset (auto-reset at an episode end: h <- initial_hidden_state) reads the weight block of the env's
-// own policy: weights [P][RQ_POLICY_NUM_WEIGHTS], checkpoint order
-__global__ __launch_bounds__(kBlock) void k_step_bank(Batch b, StepCfg c, const float* __restrict__ params, float* state,
-                                                      float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
-                                                      uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
-                                                      const uint32_t* __restrict__ block_policy) {
-    const uint32_t i = env_index();
-    if (i < b.n)
-        step_env<true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
-                       weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{});
-}
-
-// k_step_bank for an env that carries a wrench schedule
-__global__ __launch_bounds__(kBlock) void k_step_bank_wrench(Batch b, StepCfg c, const float* __restrict__ params, float* state,
-                                                             float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
-                                                             uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
-                                                             const uint32_t* __restrict__ block_policy, WrenchPtrs wr) {
-    const uint32_t i = env_index();
-    if (i < b.n)
-        step_env<true, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
-                             weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr);
-}
-
-// ... and for one that carries a vehicle schedule, with or without a wrench schedule beside it
-template <bool WRENCH>
-__global__ __launch_bounds__(kBlock) void k_step_bank_vehicle(Batch b, StepCfg c, const float* __restrict__ params, float* state,
-                                                              float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
-                                                              uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
-                                                              const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh) {
-    const uint32_t i = env_index();
-    if (i < b.n)
-        step_env<true, WRENCH, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
-                                     weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr, vh);
-}
-template __global__ void k_step_bank_vehicle<false>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t, SampleCfg, uint64_t,
-                                                    float*, const float*, const uint32_t*, WrenchPtrs, VehiclePtrs);
-template __global__ void k_step_bank_vehicle<true>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t, SampleCfg, uint64_t,
-                                                   float*, const float*, const uint32_t*, WrenchPtrs, VehiclePtrs);
-
-// ... and for one that carries a wind schedule, alone or beside the other two
-template <bool WRENCH, bool VEHICLE>
-__global__ __launch_bounds__(kBlock) void k_step_bank_wind(Batch b, StepCfg c, const float* __restrict__ params, float* state,
-                                                           float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
-                                                           uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
-                                                           const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
-                                                           WindPtrs wd) {
-    const uint32_t i = env_index();
-    if (i < b.n)
-        step_env<true, WRENCH, VEHICLE, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
-                                              weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr, vh,
-                                              wd);
-}
-#define RQ_STEP_BANK_WIND(WR, VH)                                                                                                    \
-    template __global__ void k_step_bank_wind<WR, VH>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t, SampleCfg,   \
-                                                      uint64_t, float*, const float*, const uint32_t*, WrenchPtrs, VehiclePtrs, WindPtrs);
-RQ_STEP_BANK_WIND(false, false)
-RQ_STEP_BANK_WIND(true, false)
-RQ_STEP_BANK_WIND(false, true)
-RQ_STEP_BANK_WIND(true, true)
-#undef RQ_STEP_BANK_WIND
-
-// ... and for one that carries a delay schedule, alone or beside the other three
-template <bool WRENCH, bool VEHICLE, bool WIND>
-__global__ __launch_bounds__(kBlock) void k_step_bank_delay(Batch b, StepCfg c, const float* __restrict__ params, float* state,
-                                                            float* __restrict__ action, StatsPtrs st, uint32_t flags, SampleCfg sc,
-                                                            uint64_t seed, float* __restrict__ hidden, const float* __restrict__ weights,
-                                                            const uint32_t* __restrict__ block_policy, WrenchPtrs wr, VehiclePtrs vh,
-                                                            WindPtrs wd, DelayPtrs dl) {
-    const uint32_t i = env_index();
-    if (i < b.n)
-        step_env<true, WRENCH, VEHICLE, WIND, true>(i, b, c, params, state, action, state, st, flags, sc, seed, hidden,
-                                                    weights + (size_t)block_policy[i >> 6] * RQ_POLICY_NUM_WEIGHTS, Mailbox{}, ObsNext{}, wr,
-                                                    vh, wd, dl);
-}
-#define RQ_STEP_BANK_DELAY(WR, VH, WD)                                                                                               \
-    template __global__ void k_step_bank_delay<WR, VH, WD>(Batch, StepCfg, const float*, float*, float*, StatsPtrs, uint32_t,        \
-                                                           SampleCfg, uint64_t, float*, const float*, const uint32_t*, WrenchPtrs,   \
-                                                           VehiclePtrs, WindPtrs, DelayPtrs);
-RQ_STEP_BANK_DELAY(false, false, false)
-RQ_STEP_BANK_DELAY(true, false, false)
-RQ_STEP_BANK_DELAY(false, true, false)
-RQ_STEP_BANK_DELAY(true, true, false)
-RQ_STEP_BANK_DELAY(false, false, true)
-RQ_STEP_BANK_DELAY(true, false, true)
-RQ_STEP_BANK_DELAY(false, true, true)
-RQ_STEP_BANK_DELAY(true, true, true)
-#undef RQ_STEP_BANK_DELAY
-
+// ---- the bank's thaw and initial hidden state (its env step is with k_step's)
 // k_thaw_frozen likewise: an env left frozen starts its next episode with ITS policy's initial state
 #define RQ_THAW_KERNEL k_thaw_frozen_bank
 #define RQ_THAW_BANK 1

@@ -67,18 +67,7 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const float* __restrict__ packed, StatsPtrs st,
                                                                TrajPtrs traj, SasArgs sas,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool TRACK = false, RATE = false, WRENCH = false;
-    constexpr TrackPtrs trk{};
-    constexpr WrenchPtrs wr{};
-    constexpr bool VEHICLE = false;
-    constexpr VehiclePtrs vh{};
-    constexpr bool WIND = false;
-    constexpr WindPtrs wd{};
-    constexpr bool DELAY = false;
-    constexpr DelayPtrs dl{};
-    constexpr bool SENSOR = false;
-    constexpr SensorPtrs sn{};
-    constexpr uint32_t interval = 1;
+#define RQ_FUSED_TAKES_SAS
 #include "rq_rollout_body.inc"
 }
 
@@ -95,18 +84,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const float* __restrict__ packed, StatsPtrs st,
                                                                TrajPtrs traj, TrackPtrs trk,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool TRACK = true, SAS = false, RATE = false, WRENCH = false;
-    constexpr SasArgs sas{};
-    constexpr WrenchPtrs wr{};
-    constexpr bool VEHICLE = false;
-    constexpr VehiclePtrs vh{};
-    constexpr bool WIND = false;
-    constexpr WindPtrs wd{};
-    constexpr bool DELAY = false;
-    constexpr DelayPtrs dl{};
-    constexpr bool SENSOR = false;
-    constexpr SensorPtrs sn{};
-    constexpr uint32_t interval = 1;
+    constexpr bool TRACK = true;
+#define RQ_FUSED_TAKES_TRACK
 #include "rq_rollout_body.inc"
 }
 
@@ -123,17 +102,8 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void k_rol
                                                                const float* __restrict__ packed, StatsPtrs st,
                                                                TrajPtrs traj, TrackPtrs trk, uint32_t interval,
                                                                unsigned long long* __restrict__ span) {
-    constexpr bool RATE = true, SAS = false, WRENCH = false;
-    constexpr SasArgs sas{};
-    constexpr WrenchPtrs wr{};
-    constexpr bool VEHICLE = false;
-    constexpr VehiclePtrs vh{};
-    constexpr bool WIND = false;
-    constexpr WindPtrs wd{};
-    constexpr bool DELAY = false;
-    constexpr DelayPtrs dl{};
-    constexpr bool SENSOR = false;
-    constexpr SensorPtrs sn{};
+#define RQ_FUSED_TAKES_TRACK
+#define RQ_FUSED_TAKES_RATE
 #include "rq_rollout_body.inc"
 }
 

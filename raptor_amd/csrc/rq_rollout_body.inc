@@ -1,14 +1,61 @@
-// rq_rollout_body.inc - the body of the fused rollout kernel, included once per entry point by rq_rollout.hpp: k_rollout_fused
-// (TRACK = false), k_rollout_fused_track (TRACK = true, SAS = false) and k_rollout_fused_rate (RATE = true, SAS = false).  Text, not a function: the untracked kernel is compiled from
+// rq_rollout_body.inc - the body of the fused rollout kernel, included once per entry point: k_rollout_fused, k_rollout_fused_track
+// and k_rollout_fused_rate (rq_rollout.hpp), the bank's two (rq_kernels.hip) and the schedules' five (rq_rollout_schedule.inc).  Text,
+// not a function: the untracked kernel is compiled from
 // exactly what it was compiled from when the body stood between its braces - its listing does not move when the tracked variant
 // changes - and a __device__ function in between does cost that (the work-group-size folds of a kernel are made before inlining).
-// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, SAS, TRACK, RATE, WRENCH, VEHICLE, WIND, DELAY, SENSOR, ACTOR
-// and the names b, c, nc, sc, seed, epoch0, n_steps, params, state, hidden, w, packed, st, traj, sas, trk, wr, vh, wd, dl, sn, interval, span.
-// WRENCH (k_rollout_fused_wrench alone; every other entry point defines it false and an empty wr): the env carries a wrench schedule.
-// VEHICLE (k_rollout_fused_vehicle alone; every other entry point defines it false and an empty vh): the env carries a vehicle schedule.
-// WIND (k_rollout_fused_wind alone; every other entry point defines it false and an empty wd): the env carries a wind schedule.
-// DELAY (k_rollout_fused_delay alone; every other entry point defines it false and an empty dl): the env carries a delay schedule.
-// SENSOR (k_rollout_fused_sensor alone; every other entry point defines it false and an empty sn): the env carries a sensor schedule.
+// In scope at the point of inclusion: the template parameters NOISE, AUTORESET, RECORD, ACTOR, the names b, c, nc, sc, seed, epoch0,
+// n_steps, params, state, hidden, w, packed, st, traj, span - and what the entry point says it takes, by a #define in front of the
+// #include (all of them are #undef'd at the end of this file):
+//   RQ_FUSED_TAKES_SAS      SAS and sas: the SampleAndSquash output stage
+//   RQ_FUSED_TAKES_TRACK    TRACK and trk: a moving setpoint
+//   RQ_FUSED_TAKES_RATE     interval: the policy's native interval - RATE is then true
+//   RQ_FUSED_TAKES_WRENCH   wr: the env carries a wrench schedule - WRENCH is then true; likewise _VEHICLE and vh, _WIND and wd, _DELAY
+//                           and dl, _SENSOR and sn (the entry points of rq_rollout_schedule.inc, one each)
+// What an entry point does not take is declared here, once: the switch false, the argument empty, the interval 1 - all constexpr.
+#ifndef RQ_FUSED_TAKES_SAS
+    constexpr bool SAS = false;
+    constexpr SasArgs sas{};
+#endif
+#ifndef RQ_FUSED_TAKES_TRACK
+    constexpr bool TRACK = false;
+    constexpr TrackPtrs trk{};
+#endif
+#ifdef RQ_FUSED_TAKES_RATE
+    constexpr bool RATE = true;
+#else
+    constexpr bool RATE = false;
+    constexpr uint32_t interval = 1;
+#endif
+#ifdef RQ_FUSED_TAKES_WRENCH
+    constexpr bool WRENCH = true;
+#else
+    constexpr bool WRENCH = false;
+    constexpr WrenchPtrs wr{};
+#endif
+#ifdef RQ_FUSED_TAKES_VEHICLE
+    constexpr bool VEHICLE = true;
+#else
+    constexpr bool VEHICLE = false;
+    constexpr VehiclePtrs vh{};
+#endif
+#ifdef RQ_FUSED_TAKES_WIND
+    constexpr bool WIND = true;
+#else
+    constexpr bool WIND = false;
+    constexpr WindPtrs wd{};
+#endif
+#ifdef RQ_FUSED_TAKES_DELAY
+    constexpr bool DELAY = true;
+#else
+    constexpr bool DELAY = false;
+    constexpr DelayPtrs dl{};
+#endif
+#ifdef RQ_FUSED_TAKES_SENSOR
+    constexpr bool SENSOR = true;
+#else
+    constexpr bool SENSOR = false;
+    constexpr SensorPtrs sn{};
+#endif
     // kernel-level timing (rq_device_set_rollout_timing): every wave leaves the wall-clock ticks (constant rate) at which it
     // came in and went out, and its XCD: the eight dies' counters are offset against one another by microseconds, one die's
     // are consistent - the host takes first-in / last-out per die
@@ -484,3 +531,11 @@
             span[4 * (size_t)gridDim.x + blockIdx.x] = c_done - c_loop;      // core-clock cycles between rec[2] and rec[3]
         }
     }
+#undef RQ_FUSED_TAKES_SAS
+#undef RQ_FUSED_TAKES_TRACK
+#undef RQ_FUSED_TAKES_RATE
+#undef RQ_FUSED_TAKES_WRENCH
+#undef RQ_FUSED_TAKES_VEHICLE
+#undef RQ_FUSED_TAKES_WIND
+#undef RQ_FUSED_TAKES_DELAY
+#undef RQ_FUSED_TAKES_SENSOR

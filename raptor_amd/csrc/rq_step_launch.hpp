@@ -240,25 +240,28 @@ struct EnvStepLaunch {
     // into next_state.
 };
 
-// Which kernel serves an env step (launch_step switches on the answer): k_step<rollout>, k_step_wrench<rollout>, k_step_bank,
-// k_step_bank_wrench - the kernels there were before a vehicle schedule existed, under their names - and, with a vehicle schedule,
-// k_step_vehicle<rollout, wrench> and k_step_bank_vehicle<wrench>.  A bank's step is a rollout's, in place, without host rows or a
-// folded observation.  With a wind schedule (`wind`): k_step_wind<rollout, wrench, vehicle> or k_step_bank_wind<wrench, vehicle>,
-// whichever of the two `family` - what the step would be without the wind - belongs to; vehicle = family is [BANK_]VEHICLE.  With a
-// delay schedule (`delay`): k_step_delay<rollout, wrench, vehicle, wind> or k_step_bank_delay<wrench, vehicle, wind>, named alike.
-// A sensor schedule (e.sn) changes nothing here: the step is the step it would be without it.
-enum class EnvStepFamily { UNSUPPORTED, STEP, WRENCH, VEHICLE, BANK, BANK_WRENCH, BANK_VEHICLE };
-// wrench: VEHICLE's and BANK_VEHICLE's template bool
-struct EnvStepRoute { EnvStepFamily family; bool rollout, wrench; bool wind = false; bool delay = false; };
+// Which kernel serves an env step (launch_step switches on the answer).  The kernels are built nested, each family taking the
+// schedules inside it as template bools: delay > wind > vehicle > wrench > none - k_step<rollout>, k_step_wrench<rollout>,
+// k_step_vehicle<rollout, wrench>, k_step_wind<rollout, wrench, vehicle>, k_step_delay<rollout, wrench, vehicle, wind> and, for a bank,
+// k_step_bank, k_step_bank_wrench, k_step_bank_vehicle<wrench>, k_step_bank_wind<wrench, vehicle>, k_step_bank_delay<wrench, vehicle,
+// wind>.  `family` is the outermost schedule attached.  A bank's step is a rollout's, in place, without host rows or a folded
+// observation.  A sensor schedule (e.sn) changes nothing here: the step is the step it would be without it.
+enum class EnvStepFamily { NONE, WRENCH, VEHICLE, WIND, DELAY };      // the nesting order, innermost first
+struct EnvStepRoute {
+    bool supported, bank, rollout;
+    bool wrench, vehicle, wind, delay;      // which schedules are attached
+    EnvStepFamily family;
+};
 inline EnvStepRoute route_env_step(const EnvStepLaunch& e) {
-    const bool wrench = e.wr.rows != nullptr, vehicle = e.vh.rows != nullptr, wind = e.wd.rows != nullptr;
-    const bool delay = e.dl.rows != nullptr;
-    if (e.block_policy != nullptr) {
-        if (!e.rollout || e.next_state != e.state || mailbox_used(e.mb) || e.obs_of_next != nullptr)
-            return {EnvStepFamily::UNSUPPORTED, e.rollout, wrench, false, false};
-        return {vehicle ? EnvStepFamily::BANK_VEHICLE : wrench ? EnvStepFamily::BANK_WRENCH : EnvStepFamily::BANK, true, wrench, wind, delay};
-    }
-    return {vehicle ? EnvStepFamily::VEHICLE : wrench ? EnvStepFamily::WRENCH : EnvStepFamily::STEP, e.rollout, wrench, wind, delay};
+    const bool bank = e.block_policy != nullptr;
+    const bool supported = !bank || (e.rollout && e.next_state == e.state && !mailbox_used(e.mb) && e.obs_of_next == nullptr);
+    const bool wrench = e.wr.rows != nullptr, vehicle = e.vh.rows != nullptr, wind = e.wd.rows != nullptr, delay = e.dl.rows != nullptr;
+    const EnvStepFamily family = delay ? EnvStepFamily::DELAY
+                                 : wind ? EnvStepFamily::WIND
+                                 : vehicle ? EnvStepFamily::VEHICLE
+                                 : wrench ? EnvStepFamily::WRENCH
+                                          : EnvStepFamily::NONE;
+    return {supported, bank, e.rollout, wrench, vehicle, wind, delay, family};
 }
 
 }  // namespace rq

@@ -389,61 +389,6 @@ def test_the_bool_dispatcher_hands_over_each_combination_once_and_in_order(tmp_p
     assert r.returncode == 0 and r.stdout.strip() == "ok 16", r.stdout + r.stderr
 
 
-def _expected_fused_route(n, precision, sas, tracked, interval, actor, wrench):
-    """(family, actor build) of one fused launch, written from the routing tables of the change that introduced rq_fused_route.hpp -
-    not from the header.  precision: 0 fp32, 1 bf16, 2 f16x2; actor: 0 a policy (native interval `interval`), 1 a bank at intervals
-    all 1, 2 a bank with one interval above 1 (a bank's intervals are its own table: `interval` says nothing about it)."""
-    fp32, bank = precision == 0, actor != 0
-    # what the C layer refuses before anything is enqueued
-    if wrench and (not fp32 or sas):
-        return "UNSUPPORTED", "-"
-    if sas and (tracked or (interval > 1 and not bank)):
-        return "UNSUPPORTED", "-"
-    if bank and not fp32:
-        return "UNSUPPORTED", "-"
-    if bank and sas:        # a bank has no SampleAndSquash stage to set: no kernel of its families carries one
-        return "UNSUPPORTED", "-"
-    if bank:
-        family = "WRENCH" if wrench else "BANK_RATE" if tracked or actor == 2 else "BANK"
-    else:
-        family = "WRENCH" if wrench else "RATE" if interval > 1 else "TRACK" if tracked else "PLAIN"
-    if precision == 1:
-        return family, "ActorBF16"
-    if precision == 2:
-        return family, "ActorF16X2"
-    if family == "PLAIN" and sas:
-        return family, "ActorF32Lean"
-    return family, "ActorF32Lean" if n > 65536 else "ActorF32"
-
-
-def test_the_fused_route_names_the_family_and_the_register_build_of_every_launch(tmp_path):
-    """rq::route_fused (raptor_amd/csrc/rq_fused_route.hpp) decides which kernel flies a fused rollout.  The bit-exact GPU suites
-    cannot see a wrong pick between the 512- and the 256-register fp32 build - the arithmetic is the same, only speed is lost - so
-    the whole grid is held here: tests/fused_route_driver.cpp includes the header alone under a plain host compiler (no HIP) and
-    prints family and build of 5 batch sizes (both sides of 65 536) x 3 precisions x SampleAndSquash x tracked x interval 1 / 2 x
-    (policy, bank, rated bank) x wrench; every row, the unsupported ones included, must be _expected_fused_route's."""
-    import itertools
-    import subprocess
-    exe = str(tmp_path / "fused_route_driver")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "raptor_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "fused_route_driver.cpp")], check=True, capture_output=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    got = {}
-    for line in r.stdout.splitlines():
-        *key, family, build = line.split()
-        assert tuple(map(int, key)) not in got, line
-        got[tuple(map(int, key))] = (family, build)
-    grid = list(itertools.product((1, 64, 65536, 65537, 70001), (0, 1, 2), (0, 1), (0, 1), (1, 2), (0, 1, 2), (0, 1)))
-    assert sorted(got) == sorted(grid)
-    wrong = [(key, got[key], _expected_fused_route(*key)) for key in grid if got[key] != _expected_fused_route(*key)]
-    assert not wrong, wrong[:10]
-    # the grid reaches every family and every build, and both fp32 builds on either side of the threshold
-    assert {f for f, _ in got.values()} == {"UNSUPPORTED", "PLAIN", "TRACK", "RATE", "WRENCH", "BANK", "BANK_RATE"}
-    assert {b for _, b in got.values()} == {"-", "ActorF32", "ActorF32Lean", "ActorBF16", "ActorF16X2"}
-    assert got[(65536, 0, 0, 0, 1, 0, 0)] == ("PLAIN", "ActorF32") and got[(65537, 0, 0, 0, 1, 0, 0)] == ("PLAIN", "ActorF32Lean")
-
-
 def _expected_actor_step_route(n, precision, actor, interval, mailbox, sas, hidden_in, forced, ld):
     """(family, actor build, groups per wave, grid in workgroups of 256 threads) of one actor step, written from the launchers this
     route replaced (launch_actor_step, launch_actor_step_rate, launch_actor_step_bank, launch_actor_step_rate_bank) - not from the

@@ -1,7 +1,6 @@
 """The delay schedule without a GPU: the entry points and what they refuse before the device is looked at, raptor_amd.delays (the rule
 against a literal per-env deque, the table builders, the checks), the oracle loop that is the specification the GPU suite reuses
-(tests/test_gpu_delay.py imports it from here), the kernels the two routes pick for the new description rows
-(tests/delay_route_driver.cpp) and the owner of the env's command history (tests/delay_history_driver.cpp on tests/fake_hip_memory,
+(tests/test_gpu_delay.py imports it from here) and the owner of the env's command history (tests/delay_history_driver.cpp on tests/fake_hip_memory,
 a stand-alone program under the address and undefined-behaviour sanitizers)."""
 import collections
 import os
@@ -287,123 +286,6 @@ def test_a_table_of_zeros_is_the_plain_step(oracle):
         S, r, term = oracle_delay_step(oracle, cfg, P, S, a[k], u)
         plain = np.array(oracle.step(cfg, P, plain, a[k])[0])
         assert np.array_equal(bits(S), bits(plain)), k
-
-
-# ------------------------------------------------------------------ the routes ------
-def _expected_fused(n, precision, sas, tracked, interval, actor, wrench, vehicle, wind, delay):
-    """(family, build, vehicle kernel, wind kernel, delay kernel) by hand, from the issue: the delay kernel flies fp32 policies and
-    policy banks, tracked or not, at every interval, in the 512-register build up to 65 536 envs and the 256-register one beyond;
-    beside a bf16 / f16x2 policy, a SampleAndSquash stage or another schedule nothing is built.  Without delay: what the route gave."""
-    fp32, bank = precision == 0, actor != 0
-    unsupported = ("UNSUPPORTED", "-", 0, 0, 0)
-    if wrench and (not fp32 or sas):
-        return unsupported
-    if sas and (tracked or bank or interval > 1):
-        return unsupported
-    if bank and not fp32:
-        return unsupported
-    if vehicle and (not fp32 or sas or wrench):
-        return unsupported
-    if wind and (not fp32 or sas or wrench or vehicle):
-        return unsupported
-    if delay and (not fp32 or sas or wrench or vehicle or wind):
-        return unsupported
-    if wrench:
-        family = "WRENCH"
-    elif bank:
-        family = "BANK_RATE" if tracked or actor == 2 else "BANK"
-    else:
-        family = "RATE" if interval > 1 else "TRACK" if tracked else "PLAIN"
-    if precision:
-        return family, ("ActorBF16", "ActorF16X2")[precision - 1], 0, 0, 0
-    lean = (family == "PLAIN" and sas) or n > 65536
-    return family, "ActorF32Lean" if lean else "ActorF32", vehicle, wind, delay
-
-
-def _expected_step(rollout, bank, wrench, vehicle, mailbox, wind, delay):
-    """(the kernel the step would take without wind and delay, ROLLOUT, WRENCH, wind kernel, delay kernel): the delay's kernels are
-    k_step_delay<ROLLOUT, WRENCH, VEHICLE, WIND> and k_step_bank_delay<WRENCH, VEHICLE, WIND>"""
-    if bank:
-        if not rollout or mailbox:
-            return "UNSUPPORTED", rollout, wrench, 0, 0
-        return ("k_step_bank_vehicle" if vehicle else "k_step_bank_wrench" if wrench else "k_step_bank"), 1, wrench, wind, delay
-    return ("k_step_vehicle" if vehicle else "k_step_wrench" if wrench else "k_step"), rollout, wrench, wind, delay
-
-
-def _compile(tmp_path, source, name, extra=()):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "raptor_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", source)], check=True, capture_output=True)
-    return exe
-
-
-def test_the_routes_pick_the_delay_kernels_and_leave_every_other_row_alone(tmp_path):
-    """tests/delay_route_driver.cpp includes rq_fused_route.hpp and rq_step_launch.hpp alone under a plain host compiler and prints
-    the choice for delay x wind x vehicle x wrench x actor x precision x SampleAndSquash x tracked x interval on both sides of 65 536
-    envs, and the env step's kernel for rollout x bank x wrench x vehicle x host rows x wind x delay.  With the member unset
-    ("legacy") it prints what tests/wind_route_driver.cpp prints, character for character: every old row is unchanged.  Built a
-    second time as a stand-alone program with -fsanitize=address,undefined it prints the same."""
-    import itertools
-    exe = _compile(tmp_path, "delay_route_driver.cpp", "delay_route_driver")
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    fused, step = {}, {}
-    for line in r.stdout.splitlines():
-        kind, *rest = line.split()
-        if kind == "fused":
-            *key, family, build, vk, wk, dk = rest
-            fused[tuple(map(int, key))] = (family, build, int(vk), int(wk), int(dk))
-        else:
-            *key, family, ro, wr, wk, dk = rest
-            step[tuple(map(int, key))] = (family, int(ro), int(wr), int(wk), int(dk))
-    grid = list(itertools.product((64, 65536, 65537), (0, 1, 2), (0, 1), (0, 1), (1, 2), (0, 1, 2), (0, 1), (0, 1), (0, 1), (0, 1)))
-    assert sorted(fused) == sorted(grid)
-    wrong = [(k, fused[k], _expected_fused(*k)) for k in grid if fused[k] != _expected_fused(*k)]
-    assert not wrong, wrong[:10]
-    sgrid = list(itertools.product((0, 1), repeat=7))
-    assert sorted(step) == sorted(sgrid)
-    wrong = [(k, step[k], _expected_step(*k)) for k in sgrid if step[k] != _expected_step(*k)]
-    assert not wrong, wrong[:10]
-    # a few rows by hand
-    assert fused[(64, 0, 0, 0, 1, 0, 0, 0, 0, 1)] == ("PLAIN", "ActorF32", 0, 0, 1)             # rq_rollout, fp32, delay
-    assert fused[(65536, 0, 0, 1, 1, 0, 0, 0, 0, 1)] == ("TRACK", "ActorF32", 0, 0, 1)          # the 512-register build up to 65 536
-    assert fused[(65537, 0, 0, 1, 2, 2, 0, 0, 0, 1)] == ("BANK_RATE", "ActorF32Lean", 0, 0, 1)  # a rated bank, tracked, beyond
-    assert fused[(64, 0, 0, 0, 2, 0, 0, 0, 0, 1)] == ("RATE", "ActorF32", 0, 0, 1)              # a native interval above 1
-    for other in ((1, 0, 0), (0, 1, 0), (0, 0, 1)):                                             # delay + another schedule
-        assert fused[(64, 0, 0, 0, 1, 0) + other + (1,)] == ("UNSUPPORTED", "-", 0, 0, 0)
-    assert fused[(64, 1, 0, 0, 1, 0, 0, 0, 0, 1)] == ("UNSUPPORTED", "-", 0, 0, 0)              # bf16
-    assert fused[(64, 2, 0, 0, 1, 0, 0, 0, 0, 1)] == ("UNSUPPORTED", "-", 0, 0, 0)              # f16x2
-    assert fused[(64, 0, 1, 0, 1, 0, 0, 0, 0, 1)] == ("UNSUPPORTED", "-", 0, 0, 0)              # SampleAndSquash
-    assert fused[(64, 0, 0, 0, 1, 0, 0, 0, 1, 0)] == ("PLAIN", "ActorF32", 0, 1, 0)             # without delay: as before
-    assert step[(0, 0, 0, 0, 1, 0, 1)] == ("k_step", 0, 0, 0, 1)                                # rq_step with host rows: k_step_delay<0, 0, 0, 0>
-    assert step[(1, 0, 1, 1, 0, 1, 1)] == ("k_step_vehicle", 1, 1, 1, 1)                        # all four: k_step_delay<1, 1, 1, 1>
-    assert step[(1, 1, 1, 0, 0, 0, 1)] == ("k_step_bank_wrench", 1, 1, 0, 1)                    # k_step_bank_delay<1, 0, 0>
-    assert step[(0, 1, 0, 0, 0, 0, 1)] == ("UNSUPPORTED", 0, 0, 0, 0)
-    # the rows with `delay` unset: what the wind schedule's driver prints today
-    legacy = subprocess.run([exe, "legacy"], capture_output=True, text=True)
-    assert legacy.returncode == 0
-    old = subprocess.run([_compile(tmp_path, "wind_route_driver.cpp", "wind_route_driver")], capture_output=True, text=True)
-    assert old.returncode == 0 and len(old.stdout.splitlines()) == 1728 + 64
-    assert legacy.stdout == old.stdout
-    for line in old.stdout.splitlines():     # ... and are the delay = 0 rows of the full table
-        kind, *rest = line.split()
-        if kind == "fused":
-            *key, family, build, vk, wk = rest
-            assert fused[tuple(map(int, key)) + (0,)] == (family, build, int(vk), int(wk), 0), line
-        else:
-            *key, family, ro, wr, wk = rest
-            assert step[tuple(map(int, key)) + (0,)] == (family, int(ro), int(wr), int(wk), 0), line
-    # the older drivers still compile under -Wall -Werror against the grown structs
-    for source in ("fused_route_driver.cpp", "actor_step_route_driver.cpp", "vehicle_route_driver.cpp"):
-        _compile(tmp_path, source, source[:-4])
-    # stand-alone under the sanitizers (their runtimes linked into the program itself): same text, nothing reported
-    san = _compile(tmp_path, "delay_route_driver.cpp", "delay_route_driver_san",
-                   ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan",
-                    "-static-libubsan"))
-    for args, want in (([], r.stdout), (["legacy"], old.stdout)):
-        s = subprocess.run([san, *args], capture_output=True, text=True)
-        assert s.returncode == 0 and s.stderr == "", s.stderr[-2000:]
-        assert s.stdout == want
 
 
 # ------------------------------------------------------------------ the ring's owner ------

@@ -1,7 +1,6 @@
 """The host side of the vehicle schedule without a GPU: the four entry points are declared, bound and exported, what needs no device
 is refused with its message before the device is looked at, ``vehicles.compose`` against the rule written out per field, the table
-builders, the Python surface's refusals before any library call, the kernels the two routes pick for the new description rows
-(tests/vehicle_route_driver.cpp), and two closed forms of the oracle's step fed composed parameters."""
+builders, the Python surface's refusals before any library call, and two closed forms of the oracle's step fed composed parameters."""
 import os
 import re
 
@@ -228,85 +227,6 @@ def test_python_refusals_come_before_any_library_call(monkeypatch):
                 lambda: tb.closed_loop(vector, None, env, None, None, None, 1, pids, wrench_ids=ids, vehicle_ids=ids)):
         with pytest.raises(ValueError, match="vehicle_ids .* wrench_ids .* give one of them"):
             fly()
-
-
-# ------------------------------------------------------------------ the routes ------
-def _expected_fused(n, precision, sas, tracked, interval, actor, wrench, vehicle):
-    """(family, build, vehicle kernel) by hand, from the issue: the vehicle kernel flies fp32 policies and policy banks, tracked or
-    not, at every interval, in the 512-register build up to 65 536 envs and the 256-register one beyond; beside a bf16 / f16x2 policy,
-    a SampleAndSquash stage or a wrench schedule nothing is built.  Without a schedule: what the route gave before."""
-    fp32, bank = precision == 0, actor != 0
-    if wrench and (not fp32 or sas):
-        return "UNSUPPORTED", "-", 0
-    if sas and (tracked or bank or interval > 1):
-        return "UNSUPPORTED", "-", 0
-    if bank and not fp32:
-        return "UNSUPPORTED", "-", 0
-    if vehicle and (not fp32 or sas or wrench):
-        return "UNSUPPORTED", "-", 0
-    if wrench:
-        family = "WRENCH"
-    elif bank:
-        family = "BANK_RATE" if tracked or actor == 2 else "BANK"
-    else:
-        family = "RATE" if interval > 1 else "TRACK" if tracked else "PLAIN"
-    if precision:
-        return family, ("ActorBF16", "ActorF16X2")[precision - 1], 0
-    lean = (family == "PLAIN" and sas) or n > 65536
-    return family, "ActorF32Lean" if lean else "ActorF32", vehicle
-
-
-def _expected_step(rollout, bank, wrench, vehicle, mailbox):
-    """(kernel, its ROLLOUT bool, its WRENCH bool): a bank's step is a rollout's without host rows; a vehicle schedule takes its own
-    kernels, whose WRENCH bool says whether a wrench schedule rides along; every other row keeps the kernel it had."""
-    if bank:
-        if not rollout or mailbox:
-            return "UNSUPPORTED", rollout, wrench
-        return ("k_step_bank_vehicle" if vehicle else "k_step_bank_wrench" if wrench else "k_step_bank"), 1, wrench
-    return ("k_step_vehicle" if vehicle else "k_step_wrench" if wrench else "k_step"), rollout, wrench
-
-
-def test_the_routes_pick_the_vehicle_kernels_and_leave_every_other_row_alone(tmp_path):
-    """tests/vehicle_route_driver.cpp includes rq_fused_route.hpp and rq_step_launch.hpp alone under a plain host compiler and prints
-    the choice for schedule x wrench x actor (policy, bank, rated bank) x precision x SampleAndSquash x tracked x interval on both
-    sides of 65 536 envs, and the env step's kernel for rollout x bank x wrench x schedule x host rows (a teacher bank's chained
-    step is the row rollout, no bank; its fused kernel has no route: the C layer refuses it)."""
-    import itertools
-    import subprocess
-    exe = str(tmp_path / "vehicle_route_driver")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "raptor_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "vehicle_route_driver.cpp")], check=True, capture_output=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    fused, step = {}, {}
-    for line in r.stdout.splitlines():
-        kind, *rest = line.split()
-        if kind == "fused":
-            *key, family, build, vk = rest
-            fused[tuple(map(int, key))] = (family, build, int(vk))
-        else:
-            *key, family, ro, wr = rest
-            step[tuple(map(int, key))] = (family, int(ro), int(wr))
-    grid = list(itertools.product((64, 65536, 65537), (0, 1, 2), (0, 1), (0, 1), (1, 2), (0, 1, 2), (0, 1), (0, 1)))
-    assert sorted(fused) == sorted(grid)
-    wrong = [(k, fused[k], _expected_fused(*k)) for k in grid if fused[k] != _expected_fused(*k)]
-    assert not wrong, wrong[:10]
-    sgrid = list(itertools.product((0, 1), repeat=5))
-    assert sorted(step) == sorted(sgrid)
-    wrong = [(k, step[k], _expected_step(*k)) for k in sgrid if step[k] != _expected_step(*k)]
-    assert not wrong, wrong[:10]
-    # a few rows by hand
-    assert fused[(64, 0, 0, 0, 1, 0, 0, 1)] == ("PLAIN", "ActorF32", 1)             # rq_rollout, fp32, a schedule
-    assert fused[(65537, 0, 0, 1, 2, 2, 0, 1)] == ("BANK_RATE", "ActorF32Lean", 1)  # a rated bank, tracked, beyond one wave per SIMD
-    assert fused[(64, 0, 0, 0, 1, 0, 1, 1)] == ("UNSUPPORTED", "-", 0)              # both schedules
-    assert fused[(64, 1, 0, 0, 1, 0, 0, 1)] == ("UNSUPPORTED", "-", 0)              # bf16
-    assert fused[(64, 2, 0, 0, 1, 0, 0, 1)] == ("UNSUPPORTED", "-", 0)              # f16x2
-    assert fused[(64, 0, 1, 0, 1, 0, 0, 1)] == ("UNSUPPORTED", "-", 0)              # SampleAndSquash
-    assert fused[(64, 1, 0, 0, 1, 0, 0, 0)] == ("PLAIN", "ActorBF16", 0)            # without a schedule: as before
-    assert step[(0, 0, 0, 1, 1)] == ("k_step_vehicle", 0, 0)                        # rq_step with host rows
-    assert step[(1, 0, 1, 1, 0)] == ("k_step_vehicle", 1, 1)                        # a chained rollout, both schedules
-    assert step[(1, 1, 0, 1, 0)] == ("k_step_bank_vehicle", 1, 0)
-    assert step[(1, 1, 1, 0, 0)] == ("k_step_bank_wrench", 1, 1) and step[(0, 0, 0, 0, 0)] == ("k_step", 0, 0)
 
 
 # ------------------------------------------------------------------ closed forms on the oracle ------

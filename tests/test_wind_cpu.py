@@ -1,8 +1,7 @@
 """The host side of the wind schedule without a GPU: the four entry points are declared, bound and exported, what needs no device is
 refused with its message before the device is looked at, ``winds.compose`` against the rule written out per operation (and against a
-fused restatement, which differs), the table builders, the Python surface's refusals before any library call, the kernels the two
-routes pick for the new description rows (tests/wind_route_driver.cpp, also under the address and undefined-behaviour sanitizers),
-and the closed form of the oracle's step fed the composed force."""
+fused restatement, which differs), the table builders, the Python surface's refusals before any library call, and the closed
+form of the oracle's step fed the composed force."""
 import os
 import re
 import subprocess
@@ -254,124 +253,6 @@ def test_python_refusals_come_before_any_library_call(monkeypatch):
     for kw in (dict(wrench_ids=ids), dict(vehicle_ids=ids)):
         with pytest.raises(ValueError, match="wind_ids .* give one of them"):
             pb.evaluate(vector, None, env, None, None, None, 1, pids, wind_ids=ids, **kw)
-
-
-# ------------------------------------------------------------------ the routes ------
-def _expected_fused(n, precision, sas, tracked, interval, actor, wrench, vehicle, wind):
-    """(family, build, vehicle kernel, wind kernel) by hand, from the issue: the wind kernel flies fp32 policies and policy banks,
-    tracked or not, at every interval, in the 512-register build up to 65 536 envs and the 256-register one beyond; beside a bf16 /
-    f16x2 policy, a SampleAndSquash stage, a wrench or a vehicle schedule nothing is built.  Without wind: what the route gave."""
-    fp32, bank = precision == 0, actor != 0
-    unsupported = ("UNSUPPORTED", "-", 0, 0)
-    if wrench and (not fp32 or sas):
-        return unsupported
-    if sas and (tracked or bank or interval > 1):
-        return unsupported
-    if bank and not fp32:
-        return unsupported
-    if vehicle and (not fp32 or sas or wrench):
-        return unsupported
-    if wind and (not fp32 or sas or wrench or vehicle):
-        return unsupported
-    if wrench:
-        family = "WRENCH"
-    elif bank:
-        family = "BANK_RATE" if tracked or actor == 2 else "BANK"
-    else:
-        family = "RATE" if interval > 1 else "TRACK" if tracked else "PLAIN"
-    if precision:
-        return family, ("ActorBF16", "ActorF16X2")[precision - 1], 0, 0
-    lean = (family == "PLAIN" and sas) or n > 65536
-    return family, "ActorF32Lean" if lean else "ActorF32", vehicle, wind
-
-
-def _expected_step(rollout, bank, wrench, vehicle, mailbox, wind):
-    """(the kernel the step would take without the wind, ROLLOUT, WRENCH, wind kernel): the wind's kernels are k_step_wind<ROLLOUT,
-    WRENCH, VEHICLE> and k_step_bank_wind<WRENCH, VEHICLE>; a bank's step is a rollout's without host rows."""
-    if bank:
-        if not rollout or mailbox:
-            return "UNSUPPORTED", rollout, wrench, 0
-        return ("k_step_bank_vehicle" if vehicle else "k_step_bank_wrench" if wrench else "k_step_bank"), 1, wrench, wind
-    return ("k_step_vehicle" if vehicle else "k_step_wrench" if wrench else "k_step"), rollout, wrench, wind
-
-
-def _compile(tmp_path, source, name, extra=()):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", *extra, "-I", os.path.join(ROOT, "raptor_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", source)], check=True, capture_output=True)
-    return exe
-
-
-def test_the_routes_pick_the_wind_kernels_and_leave_every_other_row_alone(tmp_path):
-    """tests/wind_route_driver.cpp includes rq_fused_route.hpp and rq_step_launch.hpp alone under a plain host compiler and prints the
-    choice for wind x vehicle x wrench x actor x precision x SampleAndSquash x tracked x interval on both sides of 65 536 envs, and
-    the env step's kernel for rollout x bank x wrench x vehicle x host rows x wind.  Built a second time as a stand-alone program
-    with -fsanitize=address,undefined it prints the same.  With the member unset ("legacy") it prints what
-    tests/vehicle_route_driver.cpp prints, character for character."""
-    import itertools
-    exe = _compile(tmp_path, "wind_route_driver.cpp", "wind_route_driver")
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    fused, step = {}, {}
-    for line in r.stdout.splitlines():
-        kind, *rest = line.split()
-        if kind == "fused":
-            *key, family, build, vk, wk = rest
-            fused[tuple(map(int, key))] = (family, build, int(vk), int(wk))
-        else:
-            *key, family, ro, wr, wk = rest
-            step[tuple(map(int, key))] = (family, int(ro), int(wr), int(wk))
-    grid = list(itertools.product((64, 65536, 65537), (0, 1, 2), (0, 1), (0, 1), (1, 2), (0, 1, 2), (0, 1), (0, 1), (0, 1)))
-    assert sorted(fused) == sorted(grid)
-    wrong = [(k, fused[k], _expected_fused(*k)) for k in grid if fused[k] != _expected_fused(*k)]
-    assert not wrong, wrong[:10]
-    sgrid = list(itertools.product((0, 1), repeat=6))
-    assert sorted(step) == sorted(sgrid)
-    wrong = [(k, step[k], _expected_step(*k)) for k in sgrid if step[k] != _expected_step(*k)]
-    assert not wrong, wrong[:10]
-    # a few rows by hand
-    assert fused[(64, 0, 0, 0, 1, 0, 0, 0, 1)] == ("PLAIN", "ActorF32", 0, 1)             # rq_rollout, fp32, wind
-    assert fused[(65536, 0, 0, 1, 1, 0, 0, 0, 1)] == ("TRACK", "ActorF32", 0, 1)          # the 512-register build up to 65 536
-    assert fused[(65537, 0, 0, 1, 2, 2, 0, 0, 1)] == ("BANK_RATE", "ActorF32Lean", 0, 1)  # a rated bank, tracked, beyond
-    assert fused[(64, 0, 0, 0, 4 // 2, 0, 0, 0, 1)] == ("RATE", "ActorF32", 0, 1)         # a native interval above 1
-    assert fused[(64, 0, 0, 0, 1, 0, 1, 0, 1)] == ("UNSUPPORTED", "-", 0, 0)              # wind + wrench
-    assert fused[(64, 0, 0, 0, 1, 0, 0, 1, 1)] == ("UNSUPPORTED", "-", 0, 0)              # wind + vehicle
-    assert fused[(64, 1, 0, 0, 1, 0, 0, 0, 1)] == ("UNSUPPORTED", "-", 0, 0)              # bf16
-    assert fused[(64, 2, 0, 0, 1, 0, 0, 0, 1)] == ("UNSUPPORTED", "-", 0, 0)              # f16x2
-    assert fused[(64, 0, 1, 0, 1, 0, 0, 0, 1)] == ("UNSUPPORTED", "-", 0, 0)              # SampleAndSquash
-    assert fused[(64, 0, 0, 0, 1, 0, 0, 1, 0)] == ("PLAIN", "ActorF32", 1, 0)             # without wind: as before
-    assert step[(0, 0, 0, 0, 1, 1)] == ("k_step", 0, 0, 1)                                # rq_step with host rows: k_step_wind<0, 0, 0>
-    assert step[(1, 0, 1, 1, 0, 1)] == ("k_step_vehicle", 1, 1, 1)                        # all three: k_step_wind<1, 1, 1>
-    assert step[(1, 1, 1, 0, 0, 1)] == ("k_step_bank_wrench", 1, 1, 1)                    # k_step_bank_wind<1, 0>
-    assert step[(0, 1, 0, 0, 0, 1)] == ("UNSUPPORTED", 0, 0, 0)
-    assert step[(1, 1, 0, 1, 0, 0)] == ("k_step_bank_vehicle", 1, 0, 0)
-    # the rows with `wind` unset: what the vehicle schedule's driver prints today
-    legacy = subprocess.run([exe, "legacy"], capture_output=True, text=True)
-    assert legacy.returncode == 0
-    old = subprocess.run([_compile(tmp_path, "vehicle_route_driver.cpp", "vehicle_route_driver")], capture_output=True, text=True)
-    assert old.returncode == 0 and len(old.stdout.splitlines()) == 864 + 32
-    assert legacy.stdout == old.stdout
-    # ... and are the wind = 0 rows of the full table
-    for line in old.stdout.splitlines():
-        kind, *rest = line.split()
-        if kind == "fused":
-            *key, family, build, vk = rest
-            assert fused[tuple(map(int, key)) + (0,)] == (family, build, int(vk), 0), line
-        else:
-            *key, family, ro, wr = rest
-            assert step[tuple(map(int, key)) + (0,)] == (family, int(ro), int(wr), 0), line
-    # the other two drivers, which switch over the enums without a default, still compile under -Wall -Werror
-    for source in ("fused_route_driver.cpp", "actor_step_route_driver.cpp"):
-        _compile(tmp_path, source, source[:-4])
-    # stand-alone under the sanitizers: same text, nothing reported
-    # (the sanitizers' runtimes linked into the program itself: it needs nothing from the environment it is started in)
-    san = _compile(tmp_path, "wind_route_driver.cpp", "wind_route_driver_san",
-                   ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan",
-                    "-static-libubsan"))
-    for args, want in (([], r.stdout), (["legacy"], old.stdout)):
-        s = subprocess.run([san, *args], capture_output=True, text=True)
-        assert s.returncode == 0 and s.stderr == "", s.stderr[-2000:]
-        assert s.stdout == want
 
 
 # ------------------------------------------------------------------ the closed form on the oracle ------
