@@ -226,7 +226,9 @@ def _reference_ode(P, sp, force, torque, g=9.81):
 @pytest.mark.parametrize("dr", [0, 1])
 def test_step_matches_independent_float64_integration(oracle, dr):
     """30 RK4 steps of the oracle vs scipy's adaptive integrator on an independently written
-    float64 ODE: pins the equations of motion (frames, signs, motor geometry)."""
+    float64 ODE: pins the equations of motion (frames, signs, motor geometry).  (A 30-step comparison at 2e-2 / 1e-3 cannot see an
+    error of 1e-4 per step: tests/env_reference.py holds ONE step, its reward and the observation to an element-wise float64 bound of
+    a few float32 roundings - tests/test_env_reference_cpu.py here, tests/test_gpu_env_float64.py on the kernels.)"""
     from scipy.integrate import solve_ivp
     cfg, P, S, _ = _setup(oracle, dr=dr, n=4, init_guidance=0.0, seed=11,
                           disturbance_force_std=0.05, disturbance_torque_std=0.02)
