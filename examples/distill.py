@@ -55,6 +55,8 @@ def main():
     ap.add_argument("--suite", action="store_true", help="every collection tracks a suite of setpoints, a reference per env")
     ap.add_argument("--holdout", type=float, default=0.0, help="fraction of the envs held out of the updates; their loss is printed")
     ap.add_argument("--teacher-weights", action="store_true", help="weight every env by its teacher's closed-loop survival")
+    ap.add_argument("--native-interval", type=int, default=1,
+                    help="R: fly and distil the student at a deployment control rate, dt = 0.01 / R, its GRU state moving every Rth step")
     args = ap.parse_args()
     if not 0.0 <= args.holdout < 1.0:
         ap.error("--holdout is a fraction in [0, 1)")
@@ -70,12 +72,15 @@ def main():
     cfg = env.config
     if args.figure_eight or args.suite:
         cfg.init_guidance = 1.0                    # hover at the origin, where the paths start
+    if args.native_interval > 1:
+        cfg.dt = 0.01 / args.native_interval       # the control interval the vehicle will be flown at
+    if args.figure_eight or args.suite or args.native_interval > 1:
         env.config = cfg
     vector.sample_initial_parameters(device, env, params, rng)
     vector.sample_initial_state(device, env, params, state, rng)
     n, T = env.N_ENVIRONMENTS, args.steps
 
-    student = Raptor(device)
+    student = Raptor(device, native_interval=args.native_interval)
     # stand-in teachers (the trained ones are not in the reference tree): 22-64-64-4 MLPs, one per group of quadrotors
     bank = TeacherBank(device, (np.random.default_rng(1).standard_normal((args.teachers, parameter_count(22, 64, 64))) * 0.1)
                        .astype(np.float32), 22, 64, 64, "relu", "tanh")
@@ -116,6 +121,7 @@ def main():
     for epoch in range(args.epochs):
         traj.reset()
         student.reset()
+        phase = env.episode_steps()          # the episode step count of every env at the first recorded step
         if epoch < args.teacher_epochs:     # the teachers act: the recorded actions ARE their labels
             bank.fly(vector, device, env, params, state, rng, T, ids, "fused", autoreset=True, trajectory=traj, reference=ref,
                      reference_ids=ref_ids)
@@ -123,6 +129,8 @@ def main():
             vector.rollout(device, env, params, state, student, rng, T, "fused", autoreset=True, trajectory=traj, reference=ref,
                            reference_ids=ref_ids)
             traj.relabel_teachers(bank, ids, overwrite=True, fetch=False)      # stored actions <- the teachers' labels
+        if args.native_interval > 1:
+            traj.start_steps = phase         # the learner at an interval above 1 needs the phase the recording started at
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.torch_optimizer:

@@ -369,9 +369,10 @@ RQ_API int rq_policy_set_sample_and_squash(rq_policy* pol, int mode, const float
  * The env side is untouched: the previous action in the observation stays the action last applied.
  * Setting R keeps weights, precision and hidden state.  Refused, with rq_last_error naming the interval and nothing changed:
  * R = 0 or above the maximum; R > 1 beside a SampleAndSquash stage (whichever is set second); and with R > 1
- * rq_policy_evaluate_sequence, rq_policy_selftest, rq_trajectory_relabel, rq_trajectory_policy_forward / _backward /
- * _loss_grad and rq_trajectory_distill - a recording does not carry the phase it started at, and training is at the native
- * rate.  The small-batch loop neither speculates nor keeps a resident executor for such a policy: its calls are plain launches. */
+ * rq_policy_evaluate_sequence, rq_policy_selftest, rq_trajectory_relabel and the probes - a recording does not carry the phase it
+ * started at.  The learner's calls (rq_trajectory_policy_forward / _backward / _loss_grad[_weighted], rq_trajectory_distill[_weighted],
+ * rq_trajectory_policy_error_table) run at R > 1 over a recording that was given its phase, rq_trajectory_set_start_steps, and are
+ * refused without it.  The small-batch loop neither speculates nor keeps a resident executor for such a policy: its calls are plain launches. */
 #define RQ_POLICY_MAX_NATIVE_INTERVAL 64
 RQ_API int rq_policy_set_native_interval(rq_policy* pol, uint32_t interval);
 RQ_API int rq_policy_get_native_interval(const rq_policy* pol, uint32_t* interval);
@@ -720,6 +721,19 @@ RQ_API int rq_env_get_sensor_schedule(const rq_env* env, rq_sensor_bank** bank /
  * no float atomics, the same bits every run.  Refused (rq_last_error says which): no matching forward, weights changed since it
  * (rq_policy_set_weights, rq_policy_set_standardize), a bf16 / f16x2 policy, a Standardize or SampleAndSquash stage, objects of
  * two devices, an empty trajectory.  Gradients of those stages and of the observations are not computed.
+ * At a deployment control rate (rq_policy_set_native_interval, R > 1) the forward follows the rollout's hold rule: k, the env's
+ * episode step count, is start_steps[i] at the first recorded step (rq_trajectory_set_start_steps), 0 after a step with code 1 or 2,
+ * unchanged by a frozen step and one more after any other; every step computes (a, h') from the committed state c and stores a;
+ * c <- h' where k % R == 0 and the step is not frozen; codes 1 and 2 set c to the learned initial state.  With the policy's state
+ * before the recording rollout as RQ_GRAD_START_CURRENT the actions are the recorded ones bit for bit.  The backward is that
+ * forward's exact gradient: a held step hands dL/dc on unchanged, plus what its own action sends through h'.  The seven calls -
+ * this pair, rq_trajectory_policy_loss_grad[_weighted], rq_trajectory_distill[_weighted], rq_trajectory_policy_error_table - are
+ * refused at R > 1 while the recording has no start steps; a backward is refused ("no matching forward") when the interval or the
+ * start steps changed since its forward.  At R = 1 the start steps are not read and every call gives the bits it gives without them.
+ * rq_trajectory_set_start_steps: start_steps host [n_envs], what rq_env_get_episode_steps answered right before the rollout that
+ * recorded step 0 (the convention of rq_trajectory_flight_table's start_steps); copied before the call returns, the same values
+ * again cost no upload; NULL forgets them, and so does rq_trajectory_reset.  rq_trajectory_get_start_steps: *present = 1 and
+ * start_steps [n_envs] (may be NULL) when the recording has them, else *present = 0 and start_steps untouched.
  * memory: RQ_DST_HOST = host arrays (copied, synchronous), RQ_DST_DEVICE = device pointers (synchronised before return),
  * RQ_DST_DEVICE_ASYNC = device pointers, only enqueued on rq_device_stream(). */
 enum rq_grad_start { RQ_GRAD_START_CURRENT = 0, RQ_GRAD_START_INITIAL = 1 };
@@ -728,6 +742,8 @@ RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* policy, int
 RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* policy, const float* grad_action,
                                          uint32_t ld_grad, float* grad_weights, float* grad_hidden_start,
                                          int memory);
+RQ_API int rq_trajectory_set_start_steps(rq_trajectory* t, const uint32_t* start_steps /* host [n_envs]; NULL forgets */);
+RQ_API int rq_trajectory_get_start_steps(const rq_trajectory* t, uint32_t* start_steps /* host [n_envs] or NULL */, int* present);
 
 /* The distillation update without leaving the device.  The loss is the masked mean squared error between the policy's actions over
  * the recording (the forward above) and a target y [T][4][ld_target] (ld_target >= n_envs): the mean over the LIVE entries - done
@@ -1082,7 +1098,8 @@ RQ_API int rq_trajectory_policies_distill_weighted(rq_trajectory* t, rq_policy_b
  * memory: RQ_DST_HOST = target, sse and count are host arrays (synchronous); RQ_DST_DEVICE / RQ_DST_DEVICE_ASYNC = device memory of
  * the trajectory's device (synchronised before return / only enqueued on rq_device_stream()).
  * Refused before anything is enqueued, outputs untouched: every refusal of rq_trajectory_policy_loss_grad /
- * rq_trajectory_policies_loss_grad (a bf16 / f16x2 policy, a Standardize or SampleAndSquash stage, a native interval above 1,
+ * rq_trajectory_policies_loss_grad (a bf16 / f16x2 policy, a Standardize or SampleAndSquash stage, a native interval above 1 -
+ * of a bank, or of a policy over a recording without start steps, rq_trajectory_set_start_steps -,
  * objects of two devices, an empty trajectory, ld_target < n_envs, a target that is not device memory when one is announced, bad
  * ids); ld_out < n_envs; n_buckets outside 1 .. 32; edges that do not ascend strictly; a null argument; sse or count that is not
  * device memory of the trajectory's device when one is announced. */

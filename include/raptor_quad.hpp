@@ -110,6 +110,12 @@ struct Trajectory : detail::Handle<rq_trajectory, rq_trajectory_destroy> {
     Trajectory(Environment& e, std::uint32_t capacity_steps) { check(rq_trajectory_create(e.h, capacity_steps, &h)); }
     std::uint32_t length() const { std::uint32_t n = 0; check(rq_trajectory_length(h, &n, nullptr)); return n; }
     void reset() { check(rq_trajectory_reset(h)); }
+    // the episode step count of every env at the first recorded step, [n_envs] (nullptr forgets): the phase the learner's calls
+    // start from at a native interval above 1
+    void set_start_steps(const std::uint32_t* start_steps) { check(rq_trajectory_set_start_steps(h, start_steps)); }
+    bool get_start_steps(std::uint32_t* start_steps) const {
+        int present = 0; check(rq_trajectory_get_start_steps(h, start_steps, &present)); return present != 0;
+    }
 };
 
 // a bank of MLP teachers (README.md:208-216): input (in_dim <= 22) -> h1 -> h2 -> 4

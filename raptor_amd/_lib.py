@@ -171,6 +171,8 @@ _SIGNATURES = {
     "rq_trajectory_create": [_vp, C.c_uint32, C.POINTER(_vp)],
     "rq_trajectory_destroy": [_vp],
     "rq_trajectory_reset": [_vp],
+    "rq_trajectory_set_start_steps": [_vp, _vp],
+    "rq_trajectory_get_start_steps": [_vp, _vp, C.POINTER(C.c_int)],
     "rq_trajectory_length": [_vp, _u32p, _u32p],
     "rq_trajectory_get": [_vp, _fp, _fp, _fp, _u8p],
     "rq_trajectory_device_ptrs": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _u32p],

@@ -21,7 +21,7 @@ using namespace rqh;
 namespace rqh {
 
 // what both directions refuse: only the fp32 student without input or output stages has a gradient here
-int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what) {
+int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what, bool rated) {
     RQ_REQUIRE(t && pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(pol->dev == t->env->dev, RQ_ERR_SHAPE_MISMATCH, std::string(what) + ": the policy lives on another device");
     RQ_REQUIRE(t->length > 0, RQ_ERR_INVALID_ARGUMENT, std::string(what) + ": the trajectory is empty");
@@ -31,11 +31,14 @@ int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what) {
                std::string(what) + ": the Standardize stage has no gradient here (disable it)");
     RQ_REQUIRE(pol->sas_mode == RQ_SAS_OFF, RQ_ERR_INVALID_ARGUMENT,
                std::string(what) + ": the SampleAndSquash stage has no gradient here (RQ_SAS_OFF)");
-    return require_native_rate(pol, what);
+    if (rated && t->grad.start_steps_set) return RQ_OK;      // the recording carries its phase: any interval
+    return require_native_rate(pol, what, rated ? ", or give the recording the phase it started at (rq_trajectory_set_start_steps)" : "");
 }
 
 int grad_saved_initial(rq_trajectory* t, rq_policy* pol) {
     rq_env* env = t->env; rq_device* dev = env->dev;
+    // (the probes' refusals have found the policy at the native rate: `matches` then never takes a rated forward's state, whose
+    // stamp carries the interval it ran at)
     if (t->grad.matches(pol, t->length) && t->grad.weight_version == pol->weight_version && t->grad.start == RQ_GRAD_START_INITIAL)
         return RQ_OK;
     t->grad.valid = false;
@@ -121,9 +124,10 @@ int loss_check_call(rq_trajectory* t, const float* target, uint32_t ld_target, c
     return RQ_OK;
 }
 
+// `rated`: the call has kernels for a native interval above 1 (the loss calls, the error table; not the gain table)
 int loss_check(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, const LossWeight& wt, int start, int memory,
-               const char* what) {
-    int rc = grad_check_pair(t, pol, what); if (rc) return rc;
+               const char* what, bool rated = true) {
+    int rc = grad_check_pair(t, pol, what, rated); if (rc) return rc;
     return loss_check_call(t, target, ld_target, wt, start, memory, what);
 }
 
@@ -157,6 +161,21 @@ int loss_workspace(rq_trajectory* t, const float* target, uint32_t ld_target, co
     return RQ_OK;
 }
 
+// A policy at a deployment control rate: its interval and the recording's start steps into the launch - at the native rate the
+// launch keeps its defaults and the start steps are not read.  want_mask: the forward's ballots of the native envs, which a backward
+// reads, reserved in the trajectory's workspace.  Inside the caller's DeviceScope.
+int rate_begin(rq_trajectory* t, const rq_policy* pol, bool want_mask, rq::LossLaunch* a) {
+    if (pol->native_interval <= 1) return RQ_OK;
+    rq_env* env = t->env;
+    a->interval = pol->native_interval;
+    a->start_steps = t->grad.start_steps;
+    if (want_mask) {
+        RQ_HIP(t->grad.native_mask.reserve(env->dev->stream, (size_t)t->length * (env->ld / 64)));
+        a->native_mask = t->grad.native_mask;
+    }
+    return RQ_OK;
+}
+
 int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t ld_target, const LossWeight& wt, int start,
                const CallMemory& mem, size_t n_losses, rq::LossLaunch* a) {
     int rc = RQ_OK;
@@ -166,7 +185,7 @@ int loss_begin(rq_trajectory* t, rq_policy* pol, const float* target, uint32_t l
     a->packed = pol->w_packed; a->gpacked = pol->w_packed_grad;
     a->hidden = start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr;
     a->ld_h = pol->ld;
-    return RQ_OK;
+    return rate_begin(t, pol, true, a);
 }
 
 // ---- the same for a policy bank (rq_trajectory_policies_loss_grad / _distill) ----
@@ -421,7 +440,7 @@ extern "C" {
 
 RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* pol, int start, float* action, uint32_t ld_action,
                                         int memory) {
-    int rc = grad_check_pair(t, pol, "rq_trajectory_policy_forward"); if (rc) return rc;
+    int rc = grad_check_pair(t, pol, "rq_trajectory_policy_forward", true); if (rc) return rc;
     rc = check_memory(memory); if (rc) return rc;
     RQ_REQUIRE(action, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(start == RQ_GRAD_START_CURRENT || start == RQ_GRAD_START_INITIAL, RQ_ERR_INVALID_ARGUMENT,
@@ -439,9 +458,12 @@ RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* pol, int st
     if (mem.host()) RQ_HIP(t->grad.rows.reserve(dev->stream, (size_t)T * RQ_ACTION_DIM * ld_action));
     // the envs' columns only go back: the caller's columns n .. ld_action-1 stay as they were
     float* d_act = mem.out(action, ld_action, t->grad.rows.get(), ld_action, env->n, (size_t)T * RQ_ACTION_DIM);
+    rq::LossLaunch rate;
+    rc = rate_begin(t, pol, true, &rate); if (rc) return rc;
     RQ_HIP(rq::launch_policy_grad_forward(dev->stream, env->n, ld, T, pol->w_packed, t->obs, t->done,
                                           start == RQ_GRAD_START_CURRENT ? pol->hidden : nullptr, pol->ld,
-                                          start == RQ_GRAD_START_INITIAL, d_act, ld_action, t->grad.saved));
+                                          start == RQ_GRAD_START_INITIAL, d_act, ld_action, t->grad.saved, rate.interval,
+                                          rate.start_steps, rate.native_mask));
     t->grad.stamp(pol, T, start);
     RQ_HIP(mem.finish());
     return RQ_OK;
@@ -449,7 +471,7 @@ RQ_API int rq_trajectory_policy_forward(rq_trajectory* t, rq_policy* pol, int st
 
 RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* pol, const float* grad_action, uint32_t ld_grad,
                                          float* grad_weights, float* grad_hidden_start, int memory) {
-    int rc = grad_check_pair(t, pol, "rq_trajectory_policy_backward"); if (rc) return rc;
+    int rc = grad_check_pair(t, pol, "rq_trajectory_policy_backward", true); if (rc) return rc;
     rc = check_memory(memory); if (rc) return rc;
     RQ_REQUIRE(grad_action && grad_weights, RQ_ERR_INVALID_ARGUMENT, "null argument");
     RQ_REQUIRE(t->grad.matches(pol, t->length), RQ_ERR_INVALID_ARGUMENT,
@@ -478,8 +500,48 @@ RQ_API int rq_trajectory_policy_backward(rq_trajectory* t, rq_policy* pol, const
     float* d_gh = grad_hidden_start ? mem.out(grad_hidden_start, gh_floats, s_gh) : nullptr;
     RQ_HIP(rq::launch_policy_grad_backward(dev->stream, env->n, ld, T, pol->w_packed, pol->w_packed_grad, t->obs, t->done,
                                            t->grad.saved, d_ga, ld_grad, t->grad.start == RQ_GRAD_START_INITIAL, d_gh,
-                                           t->grad.partial, d_gw));
+                                           t->grad.partial, d_gw, t->grad.interval, t->grad.native_mask));
     RQ_HIP(mem.finish());
+    return RQ_OK;
+}
+
+// ---------------------------------------------------------------------------- the recording's phase ---
+// The episode step count every env had at the first recorded step - env.episode_steps read before the recording rollout -, which the
+// learner's calls need at a native interval above 1.  Kept on the device with its pinned host copy, as rq_trajectory_flight_table keeps
+// its starts: the same values again upload nothing and leave a saved forward valid; other values, and NULL (forget them), renew the
+// generation a forward is stamped with.
+RQ_API int rq_trajectory_set_start_steps(rq_trajectory* t, const uint32_t* start_steps) {
+    RQ_REQUIRE(t, RQ_ERR_INVALID_ARGUMENT, "null argument: trajectory");
+    rq_trajectory::Grad& g = t->grad;
+    if (!start_steps) {
+        if (g.start_steps_set) { g.start_steps_set = false; g.start_steps_gen = fresh_version(); }
+        return RQ_OK;
+    }
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    const uint32_t n = env->n, ld = env->ld;
+    DeviceScope on_device(dev); int rc = on_device.rc; if (rc) return rc;
+    const bool first = g.start_steps_host.empty();
+    if (first) RQ_HIP(g.start_steps_host.alloc(ld));
+    RQ_HIP(g.start_steps.reserve(dev->stream, ld));
+    uint32_t* host = g.start_steps_host;
+    bool same = g.start_steps_set;
+    for (uint32_t i = 0; same && i < n; ++i) same = host[i] == start_steps[i];
+    if (same) return RQ_OK;
+    if (!first) RQ_HIP(hipStreamSynchronize(dev->stream));      // a copy may still read the pinned block
+    g.start_steps_set = false;
+    g.start_steps_gen = fresh_version();
+    for (uint32_t i = 0; i < ld; ++i) host[i] = i < n ? start_steps[i] : 0u;
+    RQ_HIP(hipMemcpyAsync(g.start_steps, host, (size_t)ld * sizeof(uint32_t), hipMemcpyHostToDevice, dev->stream));
+    g.start_steps_set = true;
+    return RQ_OK;
+}
+
+RQ_API int rq_trajectory_get_start_steps(const rq_trajectory* t, uint32_t* start_steps, int* present) {
+    RQ_REQUIRE(t && present, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    *present = t->grad.start_steps_set ? 1 : 0;
+    if (start_steps && t->grad.start_steps_set)
+        for (uint32_t i = 0; i < t->env->n; ++i) start_steps[i] = t->grad.start_steps_host[i];
     return RQ_OK;
 }
 
@@ -769,6 +831,7 @@ RQ_API int rq_trajectory_policy_error_table(rq_trajectory* t, rq_policy* pol, co
     a.pass.packed = pol->w_packed;
     a.pass.hidden = start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr;
     a.pass.ld_h = pol->ld;
+    rc = rate_begin(t, pol, false, &a.pass); if (rc) return rc;
     RQ_HIP(rq::launch_policy_error_table(dev->stream, a));
     RQ_HIP(mem.finish());
     return RQ_OK;
@@ -807,7 +870,7 @@ RQ_API int rq_trajectory_policy_gain_table(rq_trajectory* t, rq_policy* pol, con
                                            float* sum, uint32_t* count, uint32_t ld_out, int memory) {
     const char* what = __func__;
     RQ_REQUIRE(t && pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = loss_check(t, pol, nullptr, 0, kNoWeight, start, memory, what); if (rc) return rc;
+    int rc = loss_check(t, pol, nullptr, 0, kNoWeight, start, memory, what, false); if (rc) return rc;
     rq::GainTableLaunch a;
     rc = error_table_check(what, t, nullptr, age_edges, n_buckets, sum, count, ld_out, memory, &a, "sum"); if (rc) return rc;
     rq_device* dev = t->env->dev;

@@ -57,10 +57,10 @@ int policy_mirror(rq_policy* pol) {
     return RQ_OK;
 }
 
-int require_native_rate(const rq_policy* pol, const char* what) {
+int require_native_rate(const rq_policy* pol, const char* what, const char* or_else) {
     RQ_REQUIRE(pol->native_interval == 1, RQ_ERR_INVALID_ARGUMENT,
                std::string(what) + ": defined at the native rate only, the policy's native interval is " +
-                   std::to_string(pol->native_interval) + " (rq_policy_set_native_interval(policy, 1))");
+                   std::to_string(pol->native_interval) + " (rq_policy_set_native_interval(policy, 1))" + or_else);
     return RQ_OK;
 }
 

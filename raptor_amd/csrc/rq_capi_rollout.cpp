@@ -523,6 +523,10 @@ RQ_API int rq_trajectory_reset(rq_trajectory* t) {
     RQ_REQUIRE(t, RQ_ERR_INVALID_ARGUMENT, "null argument");
     t->length = 0;
     t->grad.valid = false;
+    if (t->grad.start_steps_set) {          // the next recording starts at a phase of its own (rq_trajectory_set_start_steps)
+        t->grad.start_steps_set = false;
+        t->grad.start_steps_gen = fresh_version();
+    }
     return RQ_OK;
 }
 

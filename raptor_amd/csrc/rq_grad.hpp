@@ -27,6 +27,12 @@
 // What the policy does with what it knows, the effective feedback gains per env and bucket of episode age:
 //   k_policy_gain_table[_bank]    the backward's recompute walked forwards, four local seeds e_i through W2 and Wi^T: the lane sums
 //                                 A = da/dp0 [4][16] per age bucket, sum [n_buckets][4][16][ld_out]; launch_policy_gain_table
+// The single policy at a deployment control rate (rq_policy_set_native_interval; the recording's phase: rq_trajectory_set_start_steps):
+//   k_policy_grad_forward_rate, k_policy_grad_forward_state_rate, k_policy_error_table_rate   the forwards with the rollout's hold
+//                                 rule - h' committed where the episode step count is a multiple of the interval, the action from
+//                                 h' at every step; the two that save also leave a ballot of the native envs per wave and step
+//   k_policy_grad_backward_rate, k_policy_loss_backward_rate, k_policy_loss_backward_weighted_rate   the backwards reading that
+//                                 ballot: a held step passes dL/dc on as a frozen one does and keeps its dL/da
 // The forwards, the backwards, the gain table, the loss reductions and the Adam kernels are one text each (rq_grad_forward.inc,
 // rq_grad_backward.inc, rq_gain_table.inc, rq_loss_reduce.inc, rq_adam_repack.inc), compiled once per kernel.  Every form of the loss launch goes through one launcher,
 // launch_policy_loss_grad (rq_grad_bank.hpp), from one description (rq_loss_launch.hpp).
@@ -77,6 +83,27 @@ namespace rq {
 #define RQ_GRAD_ERROR_TABLE 1
 #include "rq_grad_forward.inc"
 
+// The three forwards at a deployment control rate (rq_grad_forward.inc, RQ_GRAD_RATE): kernels of their own, the ones above keep
+// their listings
+#define RQ_GRAD_FORWARD_KERNEL k_policy_grad_forward_rate
+#define RQ_GRAD_STORE_ACT 1
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_RATE 1
+#include "rq_grad_forward.inc"
+
+#define RQ_GRAD_FORWARD_KERNEL k_policy_grad_forward_state_rate
+#define RQ_GRAD_STORE_ACT 0
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_RATE 1
+#include "rq_grad_forward.inc"
+
+#define RQ_GRAD_FORWARD_KERNEL k_policy_error_table_rate
+#define RQ_GRAD_STORE_ACT 0
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_ERROR_TABLE 1
+#define RQ_GRAD_RATE 1
+#include "rq_grad_forward.inc"
+
 // ------------------------------------------------------------------ backward -----------
 // The LDS tile of the outer products: row = env of the tile, columns = the deltas (A operands) and inputs (B operands).
 enum {
@@ -108,6 +135,26 @@ __device__ __forceinline__ float sigm2(float x) { return __builtin_amdgcn_rcpf(1
 #define RQ_GRAD_SEEDED 1
 #define RQ_GRAD_BANK 0
 #define RQ_GRAD_WEIGHTED 1
+#include "rq_grad_backward.inc"
+
+// the three backwards behind a forward at a deployment control rate (rq_grad_backward.inc, RQ_GRAD_RATE)
+#define RQ_GRAD_BACKWARD_KERNEL k_policy_grad_backward_rate
+#define RQ_GRAD_SEEDED 0
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_RATE 1
+#include "rq_grad_backward.inc"
+
+#define RQ_GRAD_BACKWARD_KERNEL k_policy_loss_backward_rate
+#define RQ_GRAD_SEEDED 1
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_RATE 1
+#include "rq_grad_backward.inc"
+
+#define RQ_GRAD_BACKWARD_KERNEL k_policy_loss_backward_weighted_rate
+#define RQ_GRAD_SEEDED 1
+#define RQ_GRAD_BANK 0
+#define RQ_GRAD_WEIGHTED 1
+#define RQ_GRAD_RATE 1
 #include "rq_grad_backward.inc"
 
 // the backward's recompute walked forwards with four local seeds and no weight gradient: da/dp0 per env and bucket of episode age,
@@ -157,10 +204,22 @@ __global__ __launch_bounds__(256) void k_fill_rows(float* __restrict__ dst, uint
 
 hipError_t launch_policy_grad_forward(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
                                       const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h,
-                                      int start_initial, float* act, uint32_t ld_act, float* saved) {
+                                      int start_initial, float* act, uint32_t ld_act, float* saved, uint32_t interval,
+                                      const uint32_t* start_steps, unsigned long long* native_mask) {
     if (n == 0 || steps == 0) return hipSuccess;
     const unsigned g = (n + kFusedBlock - 1) / kFusedBlock;
     const uint32_t si = start_initial ? 1u : 0u;
+    if (interval > 1) {        // a deployment control rate: the kernels with the hold rule; the mask is indexed by 64-env wave
+        static_assert(kFusedBlock == 64, "native_mask [steps][ld / 64] is written per workgroup of one wave");
+        if (!start_steps || !native_mask || (ld & 63u) != 0 || ld < n) return hipErrorInvalidValue;
+        if (n > kOneWavePerSimdEnvs)
+            k_policy_grad_forward_rate<ActorF32Lean><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, interval,
+                                                                               start_steps, native_mask, act, ld_act, saved);
+        else
+            k_policy_grad_forward_rate<ActorF32><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, interval,
+                                                                           start_steps, native_mask, act, ld_act, saved);
+        return hipGetLastError();
+    }
     if (n > kOneWavePerSimdEnvs)        // launch_actor_relabel's choice of build (the two give the same bits)
         k_policy_grad_forward<ActorF32Lean><<<g, kFusedBlock, 0, s>>>(n, ld, steps, packed, obs, done, hidden, ld_h, si, act, ld_act, saved);
     else
@@ -171,11 +230,16 @@ hipError_t launch_policy_grad_forward(hipStream_t s, uint32_t n, uint32_t ld, ui
 hipError_t launch_policy_grad_backward(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
                                        const float* gpacked, const float* obs, const uint8_t* done, const float* saved,
                                        const float* grad_act, uint32_t ld_g, int start_initial, float* grad_h_start,
-                                       float* partial, float* grad) {
+                                       float* partial, float* grad, uint32_t interval, const unsigned long long* native_mask) {
     if (n == 0 || steps == 0) return hipSuccess;
     const uint32_t waves = (n + 63) / 64;
-    k_policy_grad_backward<<<waves, 64, 0, s>>>(n, ld, steps, packed, gpacked, obs, done, saved, grad_act, ld_g,
-                                                start_initial ? 1u : 0u, grad_h_start, partial);
+    if (interval > 1) {
+        if (!native_mask || (ld & 63u) != 0 || ld < n) return hipErrorInvalidValue;
+        k_policy_grad_backward_rate<<<waves, 64, 0, s>>>(n, ld, steps, packed, gpacked, obs, done, saved, native_mask, grad_act, ld_g,
+                                                         start_initial ? 1u : 0u, grad_h_start, partial);
+    } else
+        k_policy_grad_backward<<<waves, 64, 0, s>>>(n, ld, steps, packed, gpacked, obs, done, saved, grad_act, ld_g,
+                                                    start_initial ? 1u : 0u, grad_h_start, partial);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_policy_grad_reduce<<<(RQ_POLICY_NUM_WEIGHTS + 255) / 256, 256, 0, s>>>(waves, partial, grad);

@@ -23,8 +23,19 @@
 // 2 / W4 of the reduction, and its squared error is fl(fl(w e) e): with w = 1.0f both are the unweighted kernel's bits.  In place of
 // the live count the wave leaves W4's share, the sum of w over its counting entries (so each env-step's weight four times): per lane
 // in float64 in the order the lane walks its entries, the lanes folded 0 .. 63 in float64, in wave_wsum [gridDim.x].
+//
+// RQ_GRAD_RATE (optional, default 0) 1: the forward ran at a deployment control rate (rq_grad_forward.inc, RQ_GRAD_RATE) and left
+// native_mask [steps][ld / 64], the wave's ballot of the envs at a native step; `saved` is the committed state entering every step.
+// The wave reads its word with one wave-uniform load per step and tests bit 16 t + j for tile t.  A held step - not native, not
+// frozen - treats the recurrence as a frozen step does, din = 0 and pass = dc: its h' reached the action alone, so the new dc is
+// W_h^T delta + dh z + pass with dh = W2^T da.  Its dL/da stays live: the seed, the weights, the squared error and the counts ask
+// for d != 4 as before.  Episode ends come first, as before.  Selects only: no rounding the native-rate kernels do not have
+// (k_policy_grad_backward_rate, k_policy_loss_backward_rate, k_policy_loss_backward_weighted_rate).
 #ifndef RQ_GRAD_WEIGHTED
 #define RQ_GRAD_WEIGHTED 0
+#endif
+#ifndef RQ_GRAD_RATE
+#define RQ_GRAD_RATE 0
 #endif
 #if RQ_GRAD_WEIGHTED && !RQ_GRAD_SEEDED
 #error "RQ_GRAD_WEIGHTED weights the loss seed: it needs RQ_GRAD_SEEDED 1"
@@ -38,6 +49,9 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
         const float* __restrict__ packed, const float* __restrict__ gpacked,
 #endif
         const float* __restrict__ obs, const uint8_t* __restrict__ done, const float* __restrict__ saved,
+#if RQ_GRAD_RATE
+        const unsigned long long* __restrict__ native_mask,
+#endif
 #if RQ_GRAD_SEEDED
         const float* __restrict__ target, uint32_t ld_y,
 #if RQ_GRAD_WEIGHTED
@@ -87,6 +101,9 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
     const float x5c = q == 2 ? 1.0f : 0.0f;
 
     for (uint32_t s = steps; s-- > 0;) {
+#if RQ_GRAD_RATE
+        const uint64_t native_wave = native_mask[(size_t)s * (ld >> 6) + blockIdx.x];      // wave-uniform
+#endif
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const uint32_t e = wave_base + 16 * t + j;           // < ld: the state of every column was saved
@@ -172,12 +189,18 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
 #endif
             // ---- the episode structure, backwards: an end feeds h0 and cuts the recurrence; a frozen step passes it on ----
             const bool ended = d == 1 || d == 2, frozen = d == 4;
+#if RQ_GRAD_RATE
+            // frozen, or held between two native steps: the state after the step is the state before it
+            const bool hold = frozen || ((native_wave >> (16 * t + j)) & 1ull) == 0;
+#else
+            const bool hold = frozen;
+#endif
             f32x4 din, pass;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (ended) { bH0[r] += dc[t][r]; dc[t][r] = 0.0f; }
-                din[r] = frozen ? 0.0f : dc[t][r];
-                pass[r] = frozen ? dc[t][r] : 0.0f;
+                din[r] = hold ? 0.0f : dc[t][r];
+                pass[r] = hold ? dc[t][r] : 0.0f;
             }
             // An env that receives nothing at this step (dL/da = 0 and nothing from later steps: padding columns, masked-out
             // frozen steps) contributes exactly nothing, whatever its recorded observation holds - a recording leaves the
@@ -348,3 +371,4 @@ __global__ __launch_bounds__(64, 1) void RQ_GRAD_BACKWARD_KERNEL(
 #undef RQ_GRAD_SEEDED
 #undef RQ_GRAD_BANK
 #undef RQ_GRAD_WEIGHTED
+#undef RQ_GRAD_RATE

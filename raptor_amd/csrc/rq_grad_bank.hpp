@@ -77,6 +77,13 @@ __global__ __launch_bounds__(256) void k_adam_set_lr_bank(AdamState* __restrict_
     if (i < count) st[first + i].lr = rates.lr[i * stride];
 }
 
+// A deployment control rate (LossLaunch::interval > 1) is a single policy's: the start steps given, the mask - but for the error
+// table, which stores nothing - too, and one mask word per 64-env block of the recording's stride.
+static bool rate_launch_ok(const LossLaunch& a, bool needs_mask = true) {
+    if (a.interval <= 1) return true;
+    return !a.block_policy && a.start_steps && (a.native_mask || !needs_mask) && (a.ld & 63u) == 0 && a.ld >= a.n;
+}
+
 // the forward of a loss launch in the build `Actor`
 template <typename Actor>
 static hipError_t launch_loss_forward(hipStream_t s, const LossLaunch& a) {
@@ -85,6 +92,9 @@ static hipError_t launch_loss_forward(hipStream_t s, const LossLaunch& a) {
     if (a.block_policy)
         k_policy_grad_forward_state_bank<Actor><<<g, kFusedBlock, 0, s>>>(a.n, a.ld, a.steps, a.packed, a.block_policy, (uint32_t)RQ_PACKED_FLOATS,
                                                                           a.obs, a.done, a.hidden, a.ld_h, si, a.saved);
+    else if (a.interval > 1)
+        k_policy_grad_forward_state_rate<Actor><<<g, kFusedBlock, 0, s>>>(a.n, a.ld, a.steps, a.packed, a.obs, a.done, a.hidden, a.ld_h, si,
+                                                                          a.interval, a.start_steps, a.native_mask, a.saved);
     else
         k_policy_grad_forward_state<Actor><<<g, kFusedBlock, 0, s>>>(a.n, a.ld, a.steps, a.packed, a.obs, a.done, a.hidden, a.ld_h, si, a.saved);
     return hipGetLastError();
@@ -93,6 +103,7 @@ static hipError_t launch_loss_forward(hipStream_t s, const LossLaunch& a) {
 // The first launch of a loss launch alone: the forward that saves the state and stores no action (the probes read nothing else).
 hipError_t launch_policy_grad_forward_state(hipStream_t s, const LossLaunch& a) {
     if (a.n == 0 || a.steps == 0 || (a.block_policy && a.n_policies == 0)) return hipErrorInvalidValue;
+    if (!rate_launch_ok(a)) return hipErrorInvalidValue;
     // launch_policy_grad_forward's choice of build (the two give the same bits)
     return a.n > kOneWavePerSimdEnvs ? launch_loss_forward<ActorF32Lean>(s, a) : launch_loss_forward<ActorF32>(s, a);
 }
@@ -118,9 +129,16 @@ hipError_t launch_policy_loss_grad(hipStream_t s, const LossLaunch& a) {
     else if (bank)
         k_policy_loss_backward_bank<<<lay.waves, 64, 0, s>>>(a.n, a.ld, a.steps, a.packed, a.gpacked, a.block_policy, fl, gfl, a.obs, a.done,
                                                              a.saved, a.target, a.ld_y, si, partial, wave_sse, wave_live);
+    else if (weighted && a.interval > 1)
+        k_policy_loss_backward_weighted_rate<<<lay.waves, 64, 0, s>>>(a.n, a.ld, a.steps, a.packed, a.gpacked, a.obs, a.done, a.saved,
+                                                                      a.native_mask, a.target, a.ld_y, a.weight, a.ld_w, w_step, si, partial,
+                                                                      wave_sse, wave_wsum);
     else if (weighted)
         k_policy_loss_backward_weighted<<<lay.waves, 64, 0, s>>>(a.n, a.ld, a.steps, a.packed, a.gpacked, a.obs, a.done, a.saved, a.target,
                                                                  a.ld_y, a.weight, a.ld_w, w_step, si, partial, wave_sse, wave_wsum);
+    else if (a.interval > 1)
+        k_policy_loss_backward_rate<<<lay.waves, 64, 0, s>>>(a.n, a.ld, a.steps, a.packed, a.gpacked, a.obs, a.done, a.saved, a.native_mask,
+                                                             a.target, a.ld_y, si, partial, wave_sse, wave_live);
     else
         k_policy_loss_backward<<<lay.waves, 64, 0, s>>>(a.n, a.ld, a.steps, a.packed, a.gpacked, a.obs, a.done, a.saved, a.target, a.ld_y, si,
                                                         partial, wave_sse, wave_live);
@@ -147,6 +165,10 @@ static hipError_t launch_error_table(hipStream_t s, const ErrorTableLaunch& a, c
         k_policy_error_table_bank<Actor><<<g, kFusedBlock, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.block_policy, (uint32_t)RQ_PACKED_FLOATS, p.obs,
                                                                    p.done, p.hidden, p.ld_h, si, p.target, p.ld_y, edges, a.n_buckets, a.sse,
                                                                    a.count, a.ld_out);
+    else if (p.interval > 1)
+        k_policy_error_table_rate<Actor><<<g, kFusedBlock, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.obs, p.done, p.hidden, p.ld_h, si, p.interval,
+                                                                   p.start_steps, p.target, p.ld_y, edges, a.n_buckets, a.sse, a.count,
+                                                                   a.ld_out);
     else
         k_policy_error_table<Actor><<<g, kFusedBlock, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.obs, p.done, p.hidden, p.ld_h, si, p.target, p.ld_y,
                                                               edges, a.n_buckets, a.sse, a.count, a.ld_out);
@@ -161,6 +183,7 @@ hipError_t launch_policy_error_table(hipStream_t s, const ErrorTableLaunch& a) {
     if (p.n == 0 || p.steps == 0 || (p.block_policy && p.n_policies == 0)) return hipErrorInvalidValue;
     if (a.n_buckets < 1 || a.n_buckets > kErrorTableMaxBuckets || a.ld_out < p.n || p.ld_y < p.n || p.ld < p.n) return hipErrorInvalidValue;
     if (!p.packed || !p.obs || !p.done || !p.target || !a.sse || !a.count || (!p.start_initial && !p.hidden)) return hipErrorInvalidValue;
+    if (!rate_launch_ok(p, false)) return hipErrorInvalidValue;
     ProbeEdges edges{};
     for (uint32_t b = 0; b <= a.n_buckets; ++b) {
         if (b > 0 && a.edges[b] <= a.edges[b - 1]) return hipErrorInvalidValue;

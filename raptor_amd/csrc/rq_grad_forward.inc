@@ -14,10 +14,23 @@
 //                            back to a bucket in a later episode goes on from the stored total.  The kernel zeroes its column's
 //                            n_buckets cells first: no atomics, no exchange between lanes, no memset, the same bits every run.  What
 //                            is frozen, outside every bucket or a padding lane is selected away before any arithmetic.
+//   RQ_GRAD_RATE             (optional, default 0) 1: the policy is flown at a deployment control rate (rq_policy_set_native_interval):
+//                            the kernel takes `interval` and start_steps [ld], the episode step count k every env had at the first
+//                            recorded step.  The lane keeps phase = k % interval (the launch's only division) and moves it as the
+//                            rollout does (rq_rollout_body.inc): 0 after done code 1 or 2, unmoved on code 4, + 1 modulo the interval
+//                            otherwise.  A step is native where phase == 0: there, unless frozen, h' is committed; elsewhere the
+//                            committed state and the actor's carry stay, and the action is still that of h'.  `saved` is then the
+//                            committed state entering every step, and the saving kernels leave the wave's ballot of `native` in
+//                            native_mask [t][ld / 64] for the backward, which walks time the other way and cannot rebuild k across an
+//                            episode end (k_policy_grad_forward_rate, k_policy_grad_forward_state_rate; k_policy_error_table_rate
+//                            stores nothing and takes no mask).  Selects only: no rounding the native-rate kernels do not have.
 // One text for all, and each a kernel of its own rather than a call into a shared function: the existing kernel's listing stays
 // the parent build's to the instruction.
 #ifndef RQ_GRAD_ERROR_TABLE
 #define RQ_GRAD_ERROR_TABLE 0
+#endif
+#ifndef RQ_GRAD_RATE
+#define RQ_GRAD_RATE 0
 #endif
 template <typename ACTOR>
 __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void RQ_GRAD_FORWARD_KERNEL(
@@ -28,6 +41,12 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void RQ_GR
         const float* __restrict__ packed,
 #endif
         const float* __restrict__ obs, const uint8_t* __restrict__ done, const float* __restrict__ hidden, uint32_t ld_h, uint32_t start_initial,
+#if RQ_GRAD_RATE
+        uint32_t interval, const uint32_t* __restrict__ start_steps,
+#if !RQ_GRAD_ERROR_TABLE
+        unsigned long long* __restrict__ native_mask,
+#endif
+#endif
 #if RQ_GRAD_STORE_ACT
         float* __restrict__ act, uint32_t ld_act,
 #endif
@@ -63,6 +82,9 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void RQ_GR
     }
     typename ACTOR::Carry carry;
     actor.prime(hQ, carry);
+#if RQ_GRAD_RATE
+    uint32_t phase = start_steps[i] % interval;      // padding lanes shadow env n - 1 here too
+#endif
 #if RQ_GRAD_ERROR_TABLE
     if (lane <= n_buckets) ed[lane] = edges.v[lane];
     float* const sse_col = sse + i0;                 // the lane's own column; written where `valid` only (i0 < n <= ld_out)
@@ -109,8 +131,22 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void RQ_GR
             for (int r = 0; r < 4; ++r) hn[tt][r] = hQ[tt][r];
         const typename ACTOR::Saved before = actor.carry_of(carry);
         actor.template step_fused<0>(x, hn, a, carry, [] {});
+#if RQ_GRAD_RATE
+        const bool native = phase == 0;
+#if !RQ_GRAD_ERROR_TABLE
+        {
+            const uint64_t native_wave = __builtin_amdgcn_ballot_w64(native);
+            if (lane == 0) native_mask[(size_t)t * (ld >> 6) + (wave_base >> 6)] = native_wave;
+        }
+#endif
+        if (d == 1 || d == 2) phase = 0;                                        // the first step of every episode is native
+        else if (d != 4) { phase += 1; phase = phase >= interval ? 0u : phase; }
+        select_hidden_q(__builtin_amdgcn_ballot_w64(d != 4 && native), hn, hQ);  // frozen or between native steps: nothing committed
+        const uint64_t held = __builtin_amdgcn_ballot_w64(d == 4 || !native);
+#else
         select_hidden_q(__builtin_amdgcn_ballot_w64(d != 4), hn, hQ);          // frozen: state not advanced
         const uint64_t held = __builtin_amdgcn_ballot_w64(d == 4);
+#endif
         if (held != 0) actor.hold_carry(held, before, carry);
         const uint64_t ended = __builtin_amdgcn_ballot_w64(d == 1 || d == 2);
         if (ended != 0) {                                                       // episode end: the learned initial state
@@ -152,3 +188,4 @@ __global__ __launch_bounds__(kFusedBlock, WavesPerSimd<ACTOR>::value) void RQ_GR
 #undef RQ_GRAD_STORE_ACT
 #undef RQ_GRAD_BANK
 #undef RQ_GRAD_ERROR_TABLE
+#undef RQ_GRAD_RATE

@@ -139,13 +139,17 @@ hipError_t launch_actor_relabel(hipStream_t s, uint32_t n, uint32_t ld, uint32_t
 // state, writes act [steps][4][ld_act] and leaves `hidden` alone.  Backward: dL/da [steps][4][ld_g] -> per-wave partial gradients
 // partial [ceil(n / 64)][2084] (flat weight order) and dL/dh_start [16][ld] (grad_h_start, may be null; start_initial = 0 only),
 // then a fixed-order sum of the partials into grad [2084].  `gpacked`: the transposed image (pack_policy_grad).
+// interval > 1: the policy's native interval - the kernels with the rollout's hold rule; start_steps [ld] the episode step count of
+// every env at step 0, native_mask [steps][ld / 64] the forward's ballots of the native envs, which the backward reads.  interval
+// <= 1: neither is read, the native-rate kernels run.
 hipError_t launch_policy_grad_forward(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
                                       const float* obs, const uint8_t* done, const float* hidden, uint32_t ld_h,
-                                      int start_initial, float* act, uint32_t ld_act, float* saved);
+                                      int start_initial, float* act, uint32_t ld_act, float* saved, uint32_t interval,
+                                      const uint32_t* start_steps, unsigned long long* native_mask);
 hipError_t launch_policy_grad_backward(hipStream_t s, uint32_t n, uint32_t ld, uint32_t steps, const float* packed,
                                        const float* gpacked, const float* obs, const uint8_t* done, const float* saved,
                                        const float* grad_act, uint32_t ld_g, int start_initial, float* grad_h_start,
-                                       float* partial, float* grad);
+                                       float* partial, float* grad, uint32_t interval, const unsigned long long* native_mask);
 // The distillation update on the device (rq_grad.hpp, rq_grad_bank.hpp).  launch_policy_loss_grad: every form of the loss launch -
 // one policy or a bank, weighted or not - as rq_loss_launch.hpp's LossLaunch describes it.  Deterministic.
 hipError_t launch_policy_loss_grad(hipStream_t s, const LossLaunch& a);

@@ -54,6 +54,12 @@ struct LossLaunch {
     uint32_t ld_h = 0;
     bool start_initial = false;
     float* saved = nullptr;
+    // a single policy at a deployment control rate: its native interval (<= 1: the native rate, the next two are not read),
+    // start_steps [ld] the episode step count of every env at step 0, native_mask [steps][ld / 64] the forward's ballots of the envs
+    // at a native step, written, which the backward reads; `saved` is then the committed state entering every step
+    uint32_t interval = 1;
+    const uint32_t* start_steps = nullptr;
+    unsigned long long* native_mask = nullptr;
     const float* target = nullptr;      // y [steps][4][ld_y]; an entry is live where its done code is not 4 and its column < n
     uint32_t ld_y = 0;
     // null: loss = the mean of (a - y)^2 over the live entries.  Else weight [weight_steps][ld_w], weight_steps = 1 (per env) or

@@ -320,8 +320,20 @@ struct rq_trajectory {
         uint64_t weight_version = 0;   // rq_policy::weight_version at the forward
         uint32_t length = 0;
         int start = 0;                 // enum rq_grad_start
+        uint32_t interval = 1;         // rq_policy::native_interval at the forward (rq_policy_set_native_interval renews no version)
+        uint64_t start_gen = 0;        // start_steps_gen at a forward with interval > 1; 0 at the native rate, where no start is read
         void stamp(const rq_policy* pol, uint32_t steps, int from);      // `saved` is now pol's forward over `steps` steps from `from`
-        bool matches(const rq_policy* pol, uint32_t steps) const { return valid && policy == pol && length == steps; }
+        // `saved` is pol's forward over `steps` steps at pol's interval and, above 1, from the start steps the recording has now
+        bool matches(const rq_policy* pol, uint32_t steps) const;
+        // The recording's phase (rq_trajectory_set_start_steps): the episode step count of every env at the first recorded step,
+        // [ld] on the device (columns >= n: 0) and the pinned block it was copied from, kept as the flight table keeps its starts -
+        // the starts of the call before upload nothing.  start_steps_gen is renewed whenever they change or are forgotten.
+        DeviceBuffer<uint32_t> start_steps;
+        PinnedBuffer<uint32_t> start_steps_host;
+        bool start_steps_set = false;
+        uint64_t start_steps_gen = 0;
+        // [length][ld / 64]: a forward at a deployment control rate leaves the ballot of the envs at a native step per wave and step
+        DeviceBuffer<unsigned long long> native_mask;
         DeviceBuffer<float> out;       // the loss-seeded calls: grad [2084] | losses [n_updates] before they go to the caller
         DeviceBuffer<unsigned long long> live;    // [1]: M, the live entries of the last loss
         // the probes (rq_capi_probe.cpp): the waves' partial moments and counts (rq::probe_partial_floats), and the call's small
@@ -380,6 +392,10 @@ struct rq_policy {
 
 inline void rq_trajectory::Grad::stamp(const rq_policy* pol, uint32_t steps, int from) {
     valid = true; policy = pol; weight_version = pol->weight_version; length = steps; start = from;
+    interval = pol->native_interval; start_gen = interval > 1 ? start_steps_gen : 0;
+}
+inline bool rq_trajectory::Grad::matches(const rq_policy* pol, uint32_t steps) const {
+    return valid && policy == pol && length == steps && interval == pol->native_interval && (interval <= 1 || start_gen == start_steps_gen);
 }
 
 // Adam's state (rq_capi_grad.cpp adam_alloc) for one policy (kernel: rq_grad.hpp k_adam_repack) or a bank's (rq_grad_bank.hpp)
@@ -558,13 +574,15 @@ const float* packed_of(const rq_policy* pol);
 int policy_size(rq_policy* pol, uint32_t batch);
 int policy_mirror(rq_policy* pol);       // w_host / w_eff <- w_dev after a device-side update (one 8 KB copy; nothing to do otherwise)
 int policy_images16(rq_policy* pol);     // the bf16 / f16x2 images repacked from the weights if an update left them behind
-// what is defined at the native rate only (sequence evaluation, relabelling, the learner, the self test) refuses a policy whose
-// native interval is above 1: a recording does not carry the phase it started at
-int require_native_rate(const rq_policy* pol, const char* what);
+// what is defined at the native rate only (sequence evaluation, relabelling, the probes, the self test) refuses a policy whose
+// native interval is above 1: a recording does not carry the phase it started at.  `or_else`: appended to the refusal's message
+int require_native_rate(const rq_policy* pol, const char* what, const char* or_else = "");
 
 // ---- rq_capi_grad.cpp: what the learner and the probes (rq_capi_probe.cpp) share ----
-// what every call over a (recording, policy) pair refuses: only the fp32 student without input or output stages, at the native rate
-int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what);
+// what every call over a (recording, policy) pair refuses: only the fp32 student without input or output stages, at the native rate -
+// or, `rated` (the learner's seven calls), at a native interval above 1 over a recording that carries its phase
+// (rq_trajectory_set_start_steps)
+int grad_check_pair(rq_trajectory* t, rq_policy* pol, const char* what, bool rated = false);
 // inside the caller's DeviceScope: t->grad.saved holds the state of a forward by `pol` from the learned initial state at its current
 // weights - the one a forward or a loss call left if its tags say so, else the state-only forward is enqueued and tagged
 int grad_saved_initial(rq_trajectory* t, rq_policy* pol);

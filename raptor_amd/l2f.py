@@ -748,6 +748,28 @@ class VectorModule:
             def reset(self):
                 _lib.call("rq_trajectory_reset", self._h)
 
+            @property
+            def start_steps(self):
+                """The episode step count every env had at the first recorded step, [N] uint32, or None: the phase a learner call
+                at a deployment control rate (``Raptor(native_interval=R)``, R > 1) starts from.  Set it to ``env.episode_steps()``
+                read right before the rollout that recorded step 0 (the convention of ``probing.flight_table(start_steps=...)``);
+                None forgets it, and so does ``reset()``.  At the native rate it is not read."""
+                N, present = mod.N_ENVIRONMENTS, C.c_int()
+                k = np.empty(N, np.uint32)
+                _lib.call("rq_trajectory_get_start_steps", self._require("trajectory"), k.ctypes.data, C.byref(present))
+                return k if present.value else None
+
+            @start_steps.setter
+            def start_steps(self, start_steps):
+                N = mod.N_ENVIRONMENTS
+                k = None
+                if start_steps is not None:
+                    k = np.asarray(start_steps)
+                    if k.shape != (N,) or k.dtype == bool or not np.issubdtype(k.dtype, np.integer) or (k < 0).any():
+                        raise ValueError(f"start_steps must be {N} non-negative integers (env.episode_steps())")
+                    k = np.ascontiguousarray(k.astype(np.uint32))
+                _lib.call("rq_trajectory_set_start_steps", self._require("trajectory"), None if k is None else k.ctypes.data)
+
             def numpy(self):
                 """-> dict(obs [T,N,22], act [T,N,4], rew [T,N], done [T,N] uint8)"""
                 T, N = len(self), mod.N_ENVIRONMENTS

@@ -67,7 +67,11 @@ def trajectory_actions(traj, policy, weights, start="initial"):
     The trajectory keeps the state saved by its LAST forward only: a backward whose forward is no longer the trajectory's latest
     (another ``trajectory_actions`` call on the same trajectory in between, even under ``torch.no_grad``) raises instead of
     differentiating the other forward.  A loss with two terms over one trajectory (e.g. both start modes) takes one backward per
-    term, each right after its forward."""
+    term, each right after its forward.
+
+    A ``Raptor`` with ``native_interval > 1`` is served once ``traj.start_steps`` is set (``env.episode_steps()`` read right before
+    the recording rollout): both directions then follow the rollout's hold rule, and a backward after the interval or the start
+    steps changed raises."""
     return _TrajectoryActions.apply(weights, traj, policy, start)
 
 
@@ -217,7 +221,8 @@ class Distiller:
     != 4: a loss other than this (weighted) masked MSE still goes through ``trajectory_actions`` and torch.  The update is
     ``torch.optim.Adam``'s with these hyper-parameters (``weight_decay`` decoupled as in ``AdamW``; 0 = none).  ``policy`` must be
     the fp32 policy without Standardize / SampleAndSquash stages; its weights are updated in place - the next rollout, relabel or
-    ``evaluate_step`` runs the updated policy, ``policy.weights`` fetches them when first read.
+    ``evaluate_step`` runs the updated policy, ``policy.weights`` fetches them when first read.  With ``native_interval > 1`` the
+    update is that of the policy flown at that rate, over a recording whose ``traj.start_steps`` is set (refused without it).
 
     ``target``: None - the trajectory's own stored actions (what ``relabel_teachers(..., overwrite=True)`` or a teacher-acting
     rollout left there) - or a [T, 4, ld_target] float32 array with ld_target >= N: a torch tensor on the trajectory's device, or
@@ -475,7 +480,7 @@ def imitation_error(traj, policy, edges=None, target=None, start="initial", poli
     """How well ``policy`` imitates ``target`` on the recording, per env and bucket of episode age -> ``ErrorTable``.  One forward
     pass on the device (rq_trajectory_policy_error_table): no backward, no action tensor, no pass over the done codes on the host.
 
-    ``policy``: a ``Raptor`` (fp32, no Standardize / SampleAndSquash stage, native rate), or a ``PolicyBank`` together with
+    ``policy``: a ``Raptor`` (fp32, no Standardize / SampleAndSquash stage; ``native_interval > 1`` once ``traj.start_steps`` is set), or a ``PolicyBank`` together with
     ``policy_ids`` - one id per env, constant on every aligned block of 64 -, each env scored under its own policy.  ``edges``:
     [B + 1] strictly ascending episode ages, B <= 32 (``probing.log_age_edges``); a live step of age k falls in bucket b when
     ``edges[b] <= k < edges[b + 1]`` and is counted nowhere outside them; None: one bucket for every age, the per-env error.  Age is

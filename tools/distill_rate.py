@@ -14,6 +14,12 @@ out (0): what a hold-out split or a teacher ranking passes.  The result becomes 
 are kept.
 
     python tools/distill_rate.py --weighted [--shapes 65536x500] [--updates 10] [--rounds 5] [--json profiles/distill_rate.json]
+
+--native-interval R times a third thing: Distiller.step(traj, updates=K) of a student at the native rate against the same call of a
+student with native_interval R, on one recording flown at that interval (traj.start_steps set), the two alternating for --rounds
+rounds after a warm-up each.  The result becomes key "rated" of the JSON file, whose other keys are kept.
+
+    python tools/distill_rate.py --native-interval 4 [--shapes 65536x500] [--updates 10] [--rounds 5] [--json profiles/distill_rate.json]
 """
 import argparse
 import json
@@ -34,14 +40,15 @@ from raptor_amd.training import Distiller, masked_mse, trajectory_actions    # n
 ap = argparse.ArgumentParser()
 ap.add_argument("--shapes", default=None, help="ENVSxSTEPS,... (16384x100,65536x500; --weighted: 65536x500)")
 ap.add_argument("--weighted", action="store_true", help="time the weighted update against the unweighted one instead")
+ap.add_argument("--native-interval", type=int, default=0, help="time the update at this native interval against the native-rate one")
 ap.add_argument("--updates", type=int, default=10)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--lr", type=float, default=1e-3)
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 if args.shapes is None:
-    args.shapes = "65536x500" if args.weighted else "16384x100,65536x500"
-if args.weighted and args.json is None:
+    args.shapes = "65536x500" if args.weighted or args.native_interval else "16384x100,65536x500"
+if (args.weighted or args.native_interval) and args.json is None:
     args.json = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "distill_rate.json")
 
 device = l2f.Device()
@@ -104,14 +111,54 @@ def weighted_rates():
     return dict(gpu=torch.cuda.get_device_name(0), library_sha256=library_sha256(LIB), lr=args.lr, shapes=out)
 
 
-if args.weighted:
-    entry = weighted_rates()
-    print(json.dumps(dict(weighted=entry)))
+def rated_rates(R):
+    """-> the "rated" entry: per shape the medians of the update at the native rate and at interval R, and their ratio"""
+    out = []
+    for shape in args.shapes.split(","):
+        n, T = (int(x) for x in shape.split("x"))
+        sh = Shard(device, n, 0)
+        traj = sh.vector.Trajectory(sh.env, T)
+        sh.policy.native_interval = R
+        sh.policy.reset()
+        start_steps = sh.env.episode_steps()
+        sh.vector.rollout(device, sh.env, sh.params, sh.state, sh.policy, sh.rng, T, "fused", autoreset=True, trajectory=traj)
+        traj.start_steps = start_steps
+        teacher = Raptor(device, weights=sh.policy.weights * np.float32(0.98))
+        teacher.reset()
+        traj.relabel(teacher, overwrite=True, fetch=False)          # the stored actions: the labels (a teacher at the native rate)
+        start = sh.policy.weights.copy()
+        forms = dict(native=1, rated=R)
+
+        def update(interval):
+            student = Raptor(device, weights=start, native_interval=interval)
+            return float(Distiller(student, lr=args.lr).step(traj, updates=args.updates)[-1])
+
+        for interval in forms.values():
+            update(interval)                                 # warm-up: allocations, first launches
+        rows = []
+        for r in range(args.rounds):
+            row = dict(round=r)
+            for name, interval in forms.items():
+                row[name + "_ms"], _, row[name + "_last_loss"] = measure(lambda: update(interval))
+            rows.append(row)
+            print(f"{n} x {T} round {r}: " + ", ".join(f"{k} {row[k + '_ms']:.1f} ms" for k in forms), flush=True)
+        med = {k: float(np.median([x[k + "_ms"] for x in rows])) for k in forms}
+        out.append(dict(envs=n, steps=T, updates=args.updates, **{k + "_ms_median": v for k, v in med.items()},
+                        rated_over_native=med["rated"] / med["native"], rounds=rows))
+        del traj, sh
+        torch.cuda.empty_cache()
+    return dict(gpu=torch.cuda.get_device_name(0), library_sha256=library_sha256(LIB), lr=args.lr, native_interval=R, shapes=out)
+
+
+if args.weighted or args.native_interval:
+    key = "weighted" if args.weighted else "rated"
+    entry = weighted_rates() if args.weighted else rated_rates(args.native_interval)
+    print(json.dumps({key: entry}))
     doc = {}
     if os.path.exists(args.json):
         with open(args.json) as f:
             doc = json.load(f)
-    doc["weighted"] = entry
+    doc[key] = entry
     with open(args.json, "w") as f:
         json.dump(doc, f, indent=1)
     sys.exit(0)
