@@ -1141,6 +1141,43 @@ RQ_API int rq_trajectory_policy_gain_table(rq_trajectory* t, rq_policy* policy, 
 RQ_API int rq_trajectory_policies_gain_table(rq_trajectory* t, rq_policy_bank* bank, const uint32_t* policy_id, const uint32_t* age_edges,
                                              uint32_t n_buckets, int start, float* sum, uint32_t* count, uint32_t ld_out, int memory);
 
+/* ---- Lagged gains per env: how far back the policy's memory reaches.  The gain table above holds h fixed; this call follows the
+ * path of an observation into LATER actions through the recurrence - the linearised impulse response of the control law along the
+ * flown trajectory.  With the gain table's names p0, m, r, z, c, n, h, h', a at every live recorded step s of an env (all gates
+ * those of step s, h the state entering it):
+ *     E_s[u][j] = dh'_u/dp0_j = m_j ((1 - z_u)(1 - n_u^2)(Win[u][j] + c_u r_u (1 - r_u) Wir[u][j]) + (h_u - n_u) z_u (1 - z_u) Wiz[u][j])
+ *     D_s[u][v] = dh'_u/dh_v  = z_u [u == v] + (1 - z_u)(1 - n_u^2)(r_u Whn[u][v] + c_u r_u (1 - r_u) Whr[u][v])
+ *                               + (h_u - n_u) z_u (1 - z_u) Whz[u][v]
+ * The chain runs over the env's live steps (done code != 4).  For a live step t let s_0 = t, s_1, s_2, ... be the live steps before
+ * it, taken back in time; the chain stops before it would leave t's episode or the recording - it never crosses a live step with
+ * done code 1 or 2 and never goes before recorded step 0 - and L(t) is the number of steps it reaches back.  For 0 <= k <= L(t)
+ *     A^(0)_t = W2 E_t                                    (the gain table's A)
+ *     A^(k)_t = W2 D_t D_(s_1) ... D_(s_(k-1)) E_(s_k)    [4][16] = da_t/dp0_(s_k), everything else held fixed,
+ * and the gain at lag k is G^(k) = A^(k) W0 [4][22]: the caller multiplies the sums by W0 once, as for the gain table.  The step,
+ * the episode rules, the reset after an episode end, the state held on frozen steps and `start` are those of
+ * rq_trajectory_policy_forward.
+ * sum [n_lags][4][16][ld_out]: cell (k, i, j, e) = the fp32 sum of A^(k)_t[i][j] over the counted steps t of env e; count
+ * [n_lags][ld_out]: their number.  t is counted at lag k when it is live, selected and k <= L(t).  1 <= n_lags <= 16, ld_out >=
+ * n_envs; every cell with e < n_envs is written, columns >= n_envs are left as they were; a lag that no step reaches has count 0 and
+ * sum exactly 0.0f.
+ * select: uint8 [length][ld_select], or NULL = every live step.  A step t with select[t][e] == 0 seeds nothing and counts nowhere; it
+ * still takes part in the chains of later steps.  (Windows of episode age, "after the poke", held-out envs.)  It follows `memory`
+ * like sum and count.
+ * A frozen step, a padding column and an unselected step are selected away before arithmetic reaches a sum: NaN in a frozen
+ * observation reaches no cell.  No atomics; the order of accumulation is the kernel's own (back in time) but fixed: the same bits
+ * every run.
+ * The call runs the learner's state-saving forward itself, so it REPLACES THE TRAJECTORY'S SAVED STATE: a
+ * rq_trajectory_policy_backward pending from an earlier forward is refused afterwards (no matching forward).  The policy's hidden
+ * state is not changed.
+ * memory: RQ_DST_HOST = sum, count and select are host arrays (synchronous); RQ_DST_DEVICE / RQ_DST_DEVICE_ASYNC = device memory of
+ * the trajectory's device (synchronised before return / only enqueued on rq_device_stream()).
+ * Refused before anything is enqueued, outputs untouched, in the gain table's words: a bf16 / f16x2 policy, a Standardize or
+ * SampleAndSquash stage, a native interval above 1, objects of two devices, an empty trajectory; ld_out < n_envs; n_lags outside
+ * 1 .. 16; ld_select < n_envs with a select; a null trajectory, policy, sum or count; an array that is not device memory of the
+ * trajectory's device when one is announced.  There is no bank variant. */
+RQ_API int rq_trajectory_policy_lag_table(rq_trajectory* t, rq_policy* policy, uint32_t n_lags, int start, const uint8_t* select,
+                                          uint32_t ld_select, float* sum, uint32_t* count, uint32_t ld_out, int memory);
+
 /* ---- Flight table: deviation, tilt and effort per env and episode age, read off a recording - how far a quadrotor was thrown, how
  * long it took to come back, how hard the motors worked and whether the commands hit their limits.  No policy takes part: the call
  * reads the recording alone, one pass that stores nothing of it.  With x the recorded observation of a step (x[0..2] the position

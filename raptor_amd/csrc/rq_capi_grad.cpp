@@ -915,4 +915,69 @@ RQ_API int rq_trajectory_policies_gain_table(rq_trajectory* t, rq_policy_bank* b
     return RQ_OK;
 }
 
+// ---------------------------------------------------------------------------- the lagged-gain table ---
+// Reads refusals, DeviceScope, prepare, in, launch, out, finish as its siblings.  The call runs the learner's state-saving forward
+// itself: the trajectory's saved state becomes this call's and is stamped for nobody - a backward pending from an earlier forward
+// finds no matching forward.
+RQ_API int rq_trajectory_policy_lag_table(rq_trajectory* t, rq_policy* pol, uint32_t n_lags, int start, const uint8_t* select,
+                                          uint32_t ld_select, float* sum, uint32_t* count, uint32_t ld_out, int memory) {
+    const char* what = __func__;
+    RQ_REQUIRE(t && pol, RQ_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = loss_check(t, pol, nullptr, 0, kNoWeight, start, memory, what, false); if (rc) return rc;
+    RQ_REFUSE(what, sum, RQ_ERR_INVALID_ARGUMENT, "null argument: sum");
+    RQ_REFUSE(what, count, RQ_ERR_INVALID_ARGUMENT, "null argument: count");
+    RQ_REFUSE(what, n_lags >= 1 && n_lags <= rq::kLagTableMaxLags, RQ_ERR_INVALID_ARGUMENT,
+              "n_lags must be 1 .. 16, not " + std::to_string(n_lags));
+    rq_env* env = t->env;
+    rq_device* dev = env->dev;
+    const uint32_t n = env->n, ld = env->ld, T = t->length;
+    RQ_REFUSE(what, ld_out >= n, RQ_ERR_INVALID_ARGUMENT, "ld_out must be at least the number of envs");
+    RQ_REFUSE(what, !select || ld_select >= n, RQ_ERR_INVALID_ARGUMENT, "ld_select must be at least the number of envs");
+    {
+        const CallMemory mem(memory, dev->stream, dev->ordinal);
+        rc = check_device_array(mem, sum, what, "sum"); if (rc) return rc;
+        rc = check_device_array(mem, count, what, "count"); if (rc) return rc;
+        if (select) { rc = check_device_array(mem, select, what, "select"); if (rc) return rc; }
+        rc = check_host_array(mem, sum, what, "sum"); if (rc) return rc;
+        rc = check_host_array(mem, count, what, "count"); if (rc) return rc;
+        rc = check_host_array(mem, select, what, "select"); if (rc) return rc;
+    }
+    DeviceScope on_device(dev); rc = on_device.rc; if (rc) return rc;
+    CallMemory mem(memory, dev->stream, dev->ordinal);
+    if (start == RQ_GRAD_START_CURRENT) { rc = policy_size(pol, n); if (rc) return rc; }
+    rc = ensure_grad_image(pol); if (rc) return rc;
+    t->grad.valid = false;               // as rq_trajectory_policy_forward: the saved state is about to be overwritten
+    RQ_HIP(t->grad.saved.reserve(dev->stream, (size_t)T * RQ_POLICY_HIDDEN_DIM * ld));
+    rq::LagTableLaunch a;
+    rq::LossLaunch& p = a.pass;
+    p.n = n; p.ld = ld; p.steps = T;
+    p.packed = pol->w_packed; p.gpacked = pol->w_packed_grad;
+    p.obs = t->obs; p.done = t->done; p.saved = t->grad.saved;
+    p.start_initial = start == RQ_GRAD_START_INITIAL;
+    p.hidden = start == RQ_GRAD_START_CURRENT ? pol->hidden.get() : nullptr;
+    p.ld_h = pol->ld;
+    a.n_lags = n_lags;
+    // host-memory calls: one device block, sum [n_lags][64][ld] | count [n_lags][ld] | select [T][ld_select] bytes; only the envs'
+    // columns go back
+    const size_t rows = (size_t)n_lags * RQ_ACTION_DIM * RQ_POLICY_HIDDEN_DIM, cells = rows * ld;
+    const size_t sel_bytes = select ? (size_t)T * ld_select : 0;
+    float* s_sum = nullptr; uint32_t* s_count = nullptr; uint8_t* s_select = nullptr;
+    if (mem.host()) {
+        RQ_HIP(t->grad.rows.reserve(dev->stream, cells + (size_t)n_lags * ld + (sel_bytes + 3) / 4));
+        s_sum = t->grad.rows.get();
+        s_count = reinterpret_cast<uint32_t*>(s_sum + cells);
+        s_select = reinterpret_cast<uint8_t*>(s_count + (size_t)n_lags * ld);
+    }
+    if (select) {
+        RQ_HIP(mem.in(select, sel_bytes, s_select, &a.select));
+        a.ld_select = ld_select;
+    }
+    a.sum = mem.out(sum, ld_out, s_sum, ld, n, rows);
+    a.count = mem.out(count, ld_out, s_count, ld, n, n_lags);
+    a.ld_out = mem.host() ? ld : ld_out;
+    RQ_HIP(rq::launch_policy_lag_table(dev->stream, a));
+    RQ_HIP(mem.finish());
+    return RQ_OK;
+}
+
 }  // extern "C"

@@ -27,6 +27,9 @@
 // What the policy does with what it knows, the effective feedback gains per env and bucket of episode age:
 //   k_policy_gain_table[_bank]    the backward's recompute walked forwards, four local seeds e_i through W2 and Wi^T: the lane sums
 //                                 A = da/dp0 [4][16] per age bucket, sum [n_buckets][4][16][ld_out]; launch_policy_gain_table
+// How far back the policy's memory reaches, the lagged gains da_t/dp0_(t-k) per env and lag along the recorded episodes:
+//   k_policy_lag_table<K>         the backward's recompute and W_h^T / W_i^T products with four action seeds and a window of K lags,
+//                                 one wave per 16 envs: sum [n_lags][4][16][ld_out]; launch_policy_lag_table
 // The single policy at a deployment control rate (rq_policy_set_native_interval; the recording's phase: rq_trajectory_set_start_steps):
 //   k_policy_grad_forward_rate, k_policy_grad_forward_state_rate, k_policy_error_table_rate   the forwards with the rollout's hold
 //                                 rule - h' committed where the episode step count is a multiple of the interval, the action from
@@ -34,7 +37,7 @@
 //   k_policy_grad_backward_rate, k_policy_loss_backward_rate, k_policy_loss_backward_weighted_rate   the backwards reading that
 //                                 ballot: a held step passes dL/dc on as a frozen one does and keeps its dL/da
 // The forwards, the backwards, the gain table, the loss reductions and the Adam kernels are one text each (rq_grad_forward.inc,
-// rq_grad_backward.inc, rq_gain_table.inc, rq_loss_reduce.inc, rq_adam_repack.inc), compiled once per kernel.  Every form of the loss launch goes through one launcher,
+// rq_grad_backward.inc, rq_gain_table.inc, rq_lag_table.inc, rq_loss_reduce.inc, rq_adam_repack.inc), compiled once per kernel.  Every form of the loss launch goes through one launcher,
 // launch_policy_loss_grad (rq_grad_bank.hpp), from one description (rq_loss_launch.hpp).
 //
 // Layouts (rq_device_math.hpp "actor"): a wave owns 64 envs as 4 tiles of 16; lane (q, j) = (l >> 4, l & 15) holds, in the Q
@@ -162,6 +165,10 @@ __device__ __forceinline__ float sigm2(float x) { return __builtin_amdgcn_rcpf(1
 #define RQ_GAIN_TABLE_KERNEL k_policy_gain_table
 #define RQ_GRAD_BANK 0
 #include "rq_gain_table.inc"
+
+// the reverse sweep with four action seeds and a sliding window of K lags over the saved state: da_t/dp0_(t-k) per env and lag, one
+// wave per 16 envs, the window in registers and the sums in LDS (rq_lag_table.inc); launch_policy_lag_table (rq_grad_bank.hpp)
+#include "rq_lag_table.inc"
 
 // grad[p] = sum over waves w = 0, 1, ... of partial[w][p], in that order
 __global__ __launch_bounds__(256) void k_policy_grad_reduce(uint32_t waves, const float* __restrict__ partial,

@@ -217,6 +217,26 @@ hipError_t launch_policy_gain_table(hipStream_t s, const GainTableLaunch& a) {
     return hipGetLastError();
 }
 
+// The lag table (rq_loss_launch.hpp LagTableLaunch): the forward that saves the state, then one reverse sweep with one wave per 16
+// envs, in the smallest instantiation that holds the asked lags.
+hipError_t launch_policy_lag_table(hipStream_t s, const LagTableLaunch& a) {
+    if (!lag_table_launch_ok(a)) return hipErrorInvalidValue;
+    const LossLaunch& p = a.pass;
+    hipError_t e = launch_policy_grad_forward_state(s, p);
+    if (e != hipSuccess) return e;
+    const uint32_t waves = (p.n + 15) / 16;
+    if (a.n_lags <= 4)
+        k_policy_lag_table<4><<<waves, 64, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.gpacked, p.obs, p.done, p.saved, a.select, a.ld_select,
+                                                   a.n_lags, a.sum, a.count, a.ld_out);
+    else if (a.n_lags <= 8)
+        k_policy_lag_table<8><<<waves, 64, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.gpacked, p.obs, p.done, p.saved, a.select, a.ld_select,
+                                                   a.n_lags, a.sum, a.count, a.ld_out);
+    else
+        k_policy_lag_table<16><<<waves, 64, 0, s>>>(p.n, p.ld, p.steps, p.packed, p.gpacked, p.obs, p.done, p.saved, a.select, a.ld_select,
+                                                    a.n_lags, a.sum, a.count, a.ld_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_adam_repack_bank(hipStream_t s, uint32_t n_policies, const uint32_t* wave_offsets, const float* grad, float* w, float* m,
                                    float* v, AdamState* st, const PackGather* table, float* images, float* gimages) {
     if (n_policies == 0) return hipErrorInvalidValue;

@@ -162,6 +162,9 @@ hipError_t launch_policy_error_table(hipStream_t s, const ErrorTableLaunch& a);
 // The backward's recompute walked forwards with four local seeds: A = da/dp0 [4][16] summed per env and bucket of episode age, one
 // policy or a bank, as rq_loss_launch.hpp's GainTableLaunch describes it.  One launch; a lane sums its own rows: deterministic.
 hipError_t launch_policy_gain_table(hipStream_t s, const GainTableLaunch& a);
+// The lagged gains A^(k) = da_t/dp0_(t-k) [4][16] summed per env and lag, as rq_loss_launch.hpp's LagTableLaunch describes it: the
+// state-saving forward, then one reverse sweep, one wave per 16 envs.  A lane sums its own rows: deterministic, no atomics.
+hipError_t launch_policy_lag_table(hipStream_t s, const LagTableLaunch& a);
 // Adam's state on the device: hyper-parameters, the step count t and the running powers beta^t (1 before the first step)
 struct AdamState { double lr, beta1, beta2, eps, weight_decay, beta1_t, beta2_t; uint32_t step, pad; };
 // one element of an operand image as a function of the flat weights: 0 (a == PACK_GATHER_NONE), k w[a], or k (w[a] + w[b])

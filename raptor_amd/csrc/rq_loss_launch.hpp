@@ -2,7 +2,8 @@
 // reads it and the C layer, rq_capi_grad.cpp, fills it), and where the per-wave regions of its workspace lie (loss_partial_layout:
 // the one statement of that layout - the launcher carves by it, the C layer reserves by it); and its sibling without a backward, the
 // error table's launch (ErrorTableLaunch; launch_policy_error_table), and the gain table's (GainTableLaunch;
-// launch_policy_gain_table; tests/gain_launch_driver.cpp holds its defaults).  Host code without a HIP dependency: a
+// launch_policy_gain_table; tests/gain_launch_driver.cpp holds its defaults), and the lag table's (LagTableLaunch;
+// launch_policy_lag_table).  Host code without a HIP dependency: a
 // plain host compiler takes this file alone (tests/loss_launch_driver.cpp does, and holds the layout against tests/test_capi_cpu.py's
 // own figures).
 #pragma once
@@ -104,5 +105,33 @@ struct GainTableLaunch {
     uint32_t* count = nullptr;
     uint32_t ld_out = 0;
 };
+
+// One lag-table launch (launch_policy_lag_table, rq_grad_bank.hpp): the forward that saves the state, then the reverse sweep with four
+// action seeds and a window of lags, A^(k) = da_t/dp0_(t-k) [4][16] summed per env and lag.  `pass` is read as a loss launch's forward
+// reads it - n, ld, steps, packed, obs, done, hidden, ld_h, start_initial, saved (written) - plus gpacked; a single policy at the
+// native rate: block_policy stays null and interval 1.  There is no target, and the workspace and the loss outputs are not touched.
+constexpr uint32_t kLagTableMaxLags = 16;
+struct LagTableLaunch {
+    LossLaunch pass;
+    uint32_t n_lags = 0;                              // 1 .. kLagTableMaxLags
+    // null: every live step seeds.  Else select [steps][ld_select], ld_select >= n: a step whose byte is 0 seeds nothing and counts
+    // nowhere, and still takes part in the chains of later steps
+    const uint8_t* select = nullptr;
+    uint32_t ld_select = 0;
+    // sum [n_lags][4][16][ld_out], cell (k, i, j, e) = the sum of A^(k)_t[i][j] over env e's counted steps t, and count
+    // [n_lags][ld_out], ld_out >= n: every cell with e < n is written, columns >= n are left
+    float* sum = nullptr;
+    uint32_t* count = nullptr;
+    uint32_t ld_out = 0;
+};
+
+// A description whose strides would let a lane leave its column, or that names no array the kernels read or write, is no launch:
+// launch_policy_lag_table refuses it, whatever the caller checked.
+constexpr bool lag_table_launch_ok(const LagTableLaunch& a) {
+    const LossLaunch& p = a.pass;
+    return p.n > 0 && p.steps > 0 && p.ld >= p.n && a.ld_out >= p.n && a.n_lags >= 1 && a.n_lags <= kLagTableMaxLags &&
+           p.block_policy == nullptr && p.interval <= 1 && p.packed && p.gpacked && p.obs && p.done && p.saved && a.sum && a.count &&
+           (p.start_initial || (p.hidden && p.ld_h >= p.n)) && (a.select == nullptr || a.ld_select >= p.n);
+}
 
 }  // namespace rq

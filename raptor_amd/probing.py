@@ -483,6 +483,134 @@ def feedback_gains(traj, policy, edges=None, start="initial", policy_ids=None):
     return GainTable(total, count, e, W0, ids if bank else None)
 
 
+# ---------------------------------------------------------------------------- the lagged gains ---
+MAX_LAGS = 16
+
+
+class LagTable:
+    """What ``lag_gains`` returns: ``sum`` [K, 4, 16, N] float32 - per lag k and env the sum over its counted steps t of
+    A^(k)_t = da_t/dp0_(t-k), the Jacobian of the four actions with respect to layer_0's 16 pre-activations k live steps earlier in
+    the same episode -, ``count`` [K, N] - the number of those steps - and ``W0`` [16, 22], layer_0's weights.  The lagged gain is
+    G^(k) = A^(k) W0 [4, 22]; every method multiplies by W0 once, after its reduction over envs.  The arrays are NumPy or torch
+    tensors, as the call made them; every method works in float64 on whatever they are and returns the same kind.  A mean over
+    nothing - a lag no counted step reaches - is NaN."""
+
+    def __init__(self, sum, count, W0):
+        self.sum, self.count = sum, count
+        self.W0 = np.asarray(W0, np.float64)
+        if len(sum.shape) != 4 or tuple(sum.shape[1:3]) != (4, HIDDEN) or tuple(count.shape) != (sum.shape[0], sum.shape[3]) \
+                or self.W0.shape != (HIDDEN, 22):
+            raise ValueError("sum must be [K, 4, 16, N], count [K, N] and W0 [16, 22]")
+
+    def _torch(self):
+        return hasattr(self.sum, "data_ptr")
+
+    def _f64(self):
+        if self._torch():
+            import torch
+            return self.sum.to(torch.float64), self.count.to(torch.float64), torch.as_tensor(self.W0, device=self.sum.device)
+        return np.asarray(self.sum, np.float64), np.asarray(self.count, np.float64), self.W0
+
+    def _mean(self, g, n):
+        """g [..., 4, 22, (N)] sums of gains, n broadcastable counts -> g / n, NaN where n is 0"""
+        if self._torch():
+            import torch
+            return torch.where(n > 0, g / torch.clamp(n, min=1.0), torch.full_like(g, float("nan")))
+        return np.where(n > 0, g / np.maximum(n, 1.0), np.nan)
+
+    def by_group(self, ids, n_groups):
+        """``ids`` [N] integers below ``n_groups`` -> [G, K, 4, 22]: the mean lagged gain of each group's envs"""
+        s, c, W0 = self._f64()
+        G, N = int(n_groups), int(s.shape[3])
+        g = np.asarray(ids.cpu() if hasattr(ids, "data_ptr") else ids)
+        if g.shape != (N,) or not np.issubdtype(g.dtype, np.integer) or (N and (g.min() < 0 or g.max() >= G)):
+            raise ValueError(f"ids must be [{N}] integers below {G}")
+        g = g.astype(np.int64)
+        if self._torch():
+            import torch
+            at = torch.as_tensor(g, device=s.device)
+            gs = torch.zeros((G,) + tuple(s.shape[:3]), dtype=torch.float64, device=s.device).index_add(0, at, s.permute(3, 0, 1, 2))
+            gc = torch.zeros((G, int(c.shape[0])), dtype=torch.float64, device=s.device).index_add(0, at, c.T)
+            return self._mean(torch.einsum("gkij,jf->gkif", gs, W0), gc[:, :, None, None])
+        gs, gc = np.zeros((G,) + s.shape[:3]), np.zeros((G, c.shape[0]))
+        np.add.at(gs, g, s.transpose(3, 0, 1, 2))
+        np.add.at(gc, g, c.T)
+        return self._mean(np.einsum("gkij,jf->gkif", gs, W0), gc[:, :, None, None])
+
+    def by_lag(self):
+        """-> [K, 4, 22]: the mean gain of all envs at every lag - the policy's impulse response, observation to command"""
+        return self.by_group(np.zeros(int(self.sum.shape[3]), np.int64), 1)[0]
+
+    def per_env(self):
+        """-> [K, 4, 22, N]: every env's mean gain at every lag"""
+        s, c, W0 = self._f64()
+        if self._torch():
+            import torch
+            return self._mean(torch.einsum("kije,jf->kife", s, W0), c[:, None, None, :])
+        return self._mean(np.einsum("kije,jf->kife", s, W0), c[:, None, None, :])
+
+    def norm_by_lag(self):
+        """-> {block: [K]}: the Frobenius norm of the mean gain at every lag, per observation block of ``OBSERVATION_BLOCKS`` - how
+        fast what was seen fades from the commands (NumPy, whatever the arrays are)"""
+        g = self.by_lag()
+        g = g.cpu().numpy() if hasattr(g, "data_ptr") else g
+        return {name: np.sqrt((g[:, :, a:z] ** 2).sum(axis=(1, 2))) for name, (a, z) in OBSERVATION_BLOCKS.items()}
+
+
+def lag_gains(traj, policy, n_lags=MAX_LAGS, select=None, start="initial", device=None):
+    """The policy's lagged gains on the recording, per env and lag -> ``LagTable``.  The state-saving forward and one reverse sweep
+    on the device (rq_trajectory_policy_lag_table).
+
+    Where ``feedback_gains`` holds the hidden state fixed, this follows an observation into LATER commands through the recurrence:
+    at lag k the gain is da_t/dobs_(t-k) [4, 22] over the live steps of one episode, everything else held fixed - the linearised
+    impulse response of the control law along the flown trajectory, up to ``n_lags`` <= 16 lags (lag 0 is ``feedback_gains``'
+    instantaneous gain).  A chain never leaves its episode or the recording, so a step of episode age a counts at lags 0 .. a only.
+
+    ``select``: None - every live step -, or [T, N] (NumPy or a tensor on the trajectory's device; nonzero = selected): an
+    unselected step t seeds nothing and counts nowhere, and still takes part in the chains of later steps.  An age window is
+    ``episode_steps(done) < 20``.  ``policy``: a ``Raptor`` (fp32, no Standardize / SampleAndSquash stage, native rate); there is no
+    bank variant.  ``start`` as for ``Distiller``.  ``device`` as for ``flight_table``.
+
+    The call REPLACES the trajectory's saved state: a ``trajectory_actions`` backward pending from before it is refused."""
+    from .training import START, Distiller, _device_ptr
+    if start not in START:
+        raise ValueError('start must be "initial" or "current"')
+    K = int(n_lags)
+    if not 1 <= K <= MAX_LAGS:
+        raise ValueError(f"n_lags must be 1 .. {MAX_LAGS}, not {n_lags}")
+    N, T = int(traj._env.N_ENVIRONMENTS), len(traj)
+    dev = None if device is False else Distiller._torch_device(traj)
+    if device and dev is None:
+        raise ValueError("device=True needs torch")
+    on_device = hasattr(select, "data_ptr")
+    if select is not None:
+        if tuple(select.shape) != (T, N):
+            raise ValueError(f"select must be [{T}, {N}]: one entry per recorded step and env")
+        if on_device and dev is None:
+            select = select.cpu().numpy()
+            on_device = False
+    head = (traj._require("trajectory"), policy._handle(traj._env._device), K, START[start])
+    traj._learner_forwards = getattr(traj, "_learner_forwards", 0) + 1      # the saved state is this call's now
+    if dev is None:
+        sel = None if select is None else np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+        total, count = np.empty((K, 4, HIDDEN, N), np.float32), np.empty((K, N), np.uint32)
+        _lib.call("rq_trajectory_policy_lag_table", *head, None if sel is None else sel.ctypes.data, N, _lib.fptr(total),
+                  count.ctypes.data, N, 0)
+    else:
+        import torch
+        sel = None
+        if select is not None:
+            sel = (select.to(dev) if on_device else torch.as_tensor(np.asarray(select), device=dev)) != 0
+            sel = sel.to(torch.uint8).contiguous()
+        total = torch.empty((K, 4, HIDDEN, N), dtype=torch.float32, device=dev)
+        count = torch.empty((K, N), dtype=torch.int32, device=dev)          # the engine's uint32; a recording has fewer than 2^31 steps
+        torch.cuda.current_stream(dev).synchronize()          # the engine runs on its own stream
+        _lib.call("rq_trajectory_policy_lag_table", *head, None if sel is None else _device_ptr(sel), N, _device_ptr(total),
+                  _device_ptr(count), N, 1)
+    w = np.asarray(policy.weights, np.float64)
+    return LagTable(total, count, w[_W0[0]:_W0[1]].reshape(HIDDEN, 22))
+
+
 # ---------------------------------------------------------------------------- the flight table ---
 # the columns of ``FlightTable.sum`` and ``FlightTable.peak``, in the order of the header's enums (RQ_FLIGHT_*, RQ_FLIGHT_PEAK_*)
 FLIGHT_SUMS = ["pos2", "vel2", "omega2", "tilt", "act2", "dact2", "saturated", "outside", "reward"]
